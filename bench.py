@@ -6,7 +6,10 @@ synthetic tensor-product B-spline Poisson patch, driven t
 reference's own API surface (EqualOrderSpline -> ExtractedSpline -> assembleMatrix / assembleVector
 -> solveLinearSystem) for every workload and rank count.
 
-    python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg3|auto]
+    python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg3|auto] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line; --full adds the CPU baseline, the companion steps,
+the live PMC passes, the self-check and the nodal error; --dump-outputs writes what the last timed step computed.
 
 One "step" = one full pass of the hot path over the patch: generator construction (1-D tables, M or
 its implicit form, control functions), explicit/implicit M^T, M^T A M with boundary conditions, M^T b,
@@ -140,6 +143,57 @@ def hashed_values(n, seed):
 def spmv_bytes(nnzK, ncp):
     # fp64 values + int32 columns, row pointer, x read once, y written once
     return 12 * nnzK + 4 * (ncp + 1) + 16 * ncp
+
+
+DUMP_VECTOR_SAMPLE = 1 << 19        # entries kept of a longer vector (values + indices: 8 MB in fp64)
+DUMP_K_BLOCKS, DUMP_K_ROWS = 8, 384  # rows of K written: 8 blocks of 384 rows at seeded places
+DUMP_K_MAX_ENTRIES = 1200000         # (3 arrays of 8 B per entry: 29 MB; with the three vectors at most 53 MB in all)
+
+
+def dump_outputs(out_dir, state, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files -- U (IGA dofs, what
+    solveLinearSystem returns), u = M U (the FE function), M^T b and rows of K = M^T A M.  A vector longer than
+    DUMP_VECTOR_SAMPLE is sampled at fixed indices (seed 0; <name>_index.npy holds them); K is written as
+    (row, column, value) triples of row blocks starting at seeded places (seed 1).  Several ranks: one set per rank,
+    names suffixed _rank<r>."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    written = []
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+        written.append(name + sfx)
+
+    def save_vector(name, x):
+        n = x.shape[0]
+        if n > DUMP_VECTOR_SAMPLE:
+            idx = np.unique(np.random.default_rng(0).integers(0, n, size=DUMP_VECTOR_SAMPLE))
+            save(name + "_index", idx)
+            x = x[idx]
+        save(name, x)
+
+    save_vector("U", state["U"].get_local())
+    save_vector("u", state["u"].vector().get_local())
+    save_vector("rhs", state["rhs"].get_local())
+    K = state["K"]
+    nr = K.shape[0]
+    if nr <= DUMP_K_BLOCKS * DUMP_K_ROWS:
+        starts, nb = [0], nr
+    else:
+        starts = np.sort(np.random.default_rng(1).integers(0, nr - DUMP_K_ROWS + 1, size=DUMP_K_BLOCKS)).tolist()
+        nb = DUMP_K_ROWS
+    rows, cols, vals = [], [], []
+    for r0 in starts:
+        blk = K.rows_to_scipy(r0, r0 + nb) if hasattr(K, "rows_to_scipy") else K.to_scipy()[r0:r0 + nb]
+        blk = blk.tocsr()
+        rows.append(r0 + np.repeat(np.arange(nb), np.diff(blk.indptr)))
+        cols.append(blk.indices)
+        vals.append(blk.data)
+    rows, cols, vals = (np.concatenate(a)[:DUMP_K_MAX_ENTRIES] for a in (rows, cols, vals))
+    save("K_row", rows)
+    save("K_col", cols)
+    save("K_val", vals)
+    log("[bench] outputs of the last timed step written to %s: %s" % (out_dir, ", ".join(written)))
 
 
 # ------------------------------------------------------------------------------------ the path
@@ -297,6 +351,8 @@ def run(args, wl, d, p, nel):
         step(True)
     barrier()
     elapsed = transport.allreduce_max(time.perf_counter() - t_start)
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, state, rank, world)      # (before any companion step replaces the state)
 
     gen, spline, K, u, solver = state["gen"], state["spline"], state["K"], state["u"], state["solver"]
     ncp = sum(gen.getNcp(f) for f in range(nf))
@@ -316,24 +372,25 @@ def run(args, wl, d, p, nel):
     # ---- per-rank self-check of the solve that was timed: || rhs - K U || over the rank's rows (halo through the
     # communicator), relative to || rhs ||; a communicator that lost or reordered an exchange shows up here
     self_check = None
-    try:
-        U_loc, rhs_loc = state["U"], state["rhs"]
-        if dcomm is not None:
-            xext = dcomm.halo_extend(U_loc)
-            g0 = dcomm.g0 - dcomm.halo_lo
-            KU = K.mult_offset(xext, g0)
-        else:
-            KU = K.mult(U_loc)
-        if KU is not None:
-            rr = rhs_loc.get_local() - KU.get_local()
-            num, den = float(rr @ rr), float(rhs_loc.get_local() @ rhs_loc.get_local())
+    if getattr(args, "full", False):
+        try:
+            U_loc, rhs_loc = state["U"], state["rhs"]
             if dcomm is not None:
-                num, den = [float(v) for v in dcomm.allreduce_sum([num, den])]
-            self_check = float(np.sqrt(num / den)) if den > 0 else 0.0
-            if rank == 0:
-                log("[bench] self-check ||rhs - K U|| / ||rhs|| over all ranks: %.3e" % self_check)
-    except Exception as e:                                # (diagnostic only)
-        log("[bench] self-check skipped:", repr(e))
+                xext = dcomm.halo_extend(U_loc)
+                g0 = dcomm.g0 - dcomm.halo_lo
+                KU = K.mult_offset(xext, g0)
+            else:
+                KU = K.mult(U_loc)
+            if KU is not None:
+                rr = rhs_loc.get_local() - KU.get_local()
+                num, den = float(rr @ rr), float(rhs_loc.get_local() @ rhs_loc.get_local())
+                if dcomm is not None:
+                    num, den = [float(v) for v in dcomm.allreduce_sum([num, den])]
+                self_check = float(np.sqrt(num / den)) if den > 0 else 0.0
+                if rank == 0:
+                    log("[bench] self-check ||rhs - K U|| / ||rhs|| over all ranks: %.3e" % self_check)
+        except Exception as e:                            # (diagnostic only)
+            log("[bench] self-check skipped:", repr(e))
 
     # ---- companion figures, measured live after the timed loop (one extra step each):
     #  * "materialised": the FE matrix written in row blocks inside the step and read back by the PtAP (what the step
@@ -542,8 +599,14 @@ def main():
     ap.add_argument("--p", type=int, default=0)
     ap.add_argument("--d", type=int, default=0)
     ap.add_argument("--rtol", type=float, default=1e-6)
-    ap.add_argument("--check", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the CPU baseline, the companion steps, the live HBM traffic passes, "
+                         "the self-check of the timed solve, the nodal error and the offline general-path figures")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (U, u = M U, M^T b, rows of K; a fixed seeded sample of "
+                         "each when large) as DIR/<name>.npy")
+    ap.add_argument("--check", type=int, default=-1, help="1 / 0: nodal error vs the manufactured solution (default: with --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="no CPU baseline (it runs with --full only)")
     ap.add_argument("--cpu-nel", type=int, default=0)
     ap.add_argument("--slab", type=int, default=-1, help="1: force the implicit-M / z-slab streaming path on one GPU")
     ap.add_argument("--solver", default="auto", help="cg | gmres | bicgstab | lu (auto: cg; cfg4 lu as demos/biharmonic; cfg5 gmres)")
@@ -551,16 +614,23 @@ def main():
     ap.add_argument("--cheb-degree", type=int, default=8)
     ap.add_argument("--live-traffic", type=int, default=-1,
                     help="1 / 0: measure the HBM traffic of the product kernel with rocprofv3 --pmc in a child run of this "
-                         "command (default: when N = 1, the headline workload, rocprofv3 present and no profiler around this run)")
+                         "command (default: with --full, when N = 1, the headline workload, rocprofv3 present and no profiler "
+                         "around this run)")
     ap.add_argument("--geometry", default="identity",
                     help="identity (the benchmark's unit cube) | volume: a smooth rational volume map -- the forms integrate on "
                          "the mapped patch (sum-factorised element matrices in row blocks, csrc/tg_assemble.hip)")
     ap.add_argument("--mapped-companion", type=int, default=-1,
                     help="1 / 0: after the timed run, one step of the same size on the rational volume map (default: on "
-                         "for the headline workload on one rank)")
-    ap.add_argument("--companion", type=int, default=1,
-                    help="1: after the timed loop run one more step with the FE matrix' pattern verified entry by entry")
+                         "for the headline workload on one rank with --full)")
+    ap.add_argument("--companion", type=int, default=-1,
+                    help="1: after the timed loop run one more step with the FE matrix' pattern verified entry by entry "
+                         "(default: with --full)")
     args = ap.parse_args()
+    # a plain run does only what its headline figure needs; the rest is switched on by --full
+    if args.check < 0:
+        args.check = int(args.full)
+    if args.companion < 0:
+        args.companion = int(args.full)
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # launched plainly: become the launcher of N ranks (one per GPU), like torch.distributed.run would
@@ -591,8 +661,8 @@ def main():
     if live < 0:
         import shutil
         profiled = any(k.startswith(("ROCPROF", "ROCP_", "ROCTRACER")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-        live = int(wl == "cfg3" and world == 1 and args.gpus == 1 and not args.nel and not args.p and not args.d and
-                   shutil.which("rocprofv3") is not None and not profiled)
+        live = int(args.full and wl == "cfg3" and world == 1 and args.gpus == 1 and not args.nel and not args.p and
+                   not args.d and shutil.which("rocprofv3") is not None and not profiled)
     if live and world == 1 and args.gpus == 1:
         import subprocess, tempfile
         dst = os.path.join(tempfile.mkdtemp(prefix="tigar_pmc_", dir="/tmp"), "pmc.json")
@@ -610,11 +680,11 @@ def main():
     mapped_res = None
     mc = args.mapped_companion
     if mc < 0:
-        mc = int(wl == "cfg3" and world == 1 and args.geometry == "identity" and bool(args.companion))
+        mc = int(args.full and wl == "cfg3" and world == 1 and args.geometry == "identity" and bool(args.companion))
     if mc and args.geometry == "identity" and d == 3 and wl in ("cfg2", "cfg3"):
         import copy
         a2 = copy.copy(args)
-        a2.geometry, a2.steps, a2.warmup, a2.companion, a2.check = "volume", 1, 1, 0, 0
+        a2.geometry, a2.steps, a2.warmup, a2.companion, a2.check, a2.dump_outputs = "volume", 1, 1, 0, 0, None
         try:
             # the identity run's blocks (sliced K, walk buffers) sit idle in the caching allocator with sizes the mapped
             # run does not ask for; hand them back first, or every mapped step trims under pressure inside its stages
@@ -787,7 +857,7 @@ def main():
                            "achieved": pt["achieved_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
                            "frac": pt["frac_of_hbm_peak"], "traffic": None,
                            "bytes_per_launch": pt["algorithmic_bytes"], "bytes_definition": pt["bytes_definition"]}
-    if wl == "cfg3" and res["comm_world"] == 1 and not args.nel and not args.p:
+    if args.full and wl == "cfg3" and res["comm_world"] == 1 and not args.nel and not args.p:
         # the general-CSR contract keeps a tracked number: the same step with the fast path switched off (offline runs,
         # committed under profiles/; A arbitrary sparse in both, M Kronecker in the first, nothing assumed in the second)
         ref = {}
@@ -806,7 +876,7 @@ def main():
                 pass
         if ref:
             out["config"]["general_path_reference"] = ref
-    if not args.no_cpu_baseline and res["comm_world"] == 1 and wl in ("cfg1", "cfg2", "cfg3"):   # (rank 0 at N=1 only)
+    if args.full and not args.no_cpu_baseline and res["comm_world"] == 1 and wl in ("cfg1", "cfg2", "cfg3"):   # (rank 0 at N=1 only)
         # bounded samples (SURVEY 8d / BASELINE.md section 4 plan 64^3 at p=3): all cores at 64^3 elements when the host has
         # the memory for it (A 10.7 GB + M, M^T 8.4 GB + blocks of A*M of 3.6 GB; checked against MemAvailable -- a
         # box must not be driven out of memory), else 48^3 / 40^3; one thread at half that edge (a one-thread 64^3

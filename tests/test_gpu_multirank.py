@@ -538,7 +538,8 @@ def test_bench_launcher_with_two_ranks_on_the_shared_gpu(tmp_path):
             env.pop(k, None)
         env.update(extra_env)
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--workload", "cfg2",
-                              "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--companion", "0", "--live-traffic", "0"],
+                              "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--companion", "0",
+                              "--live-traffic", "0"],
                              env=env, capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -574,7 +575,8 @@ def test_rccl_asked_for_on_a_shared_gpu_falls_back_to_ipc(tmp_path):
             env.pop(k, None)
         env.update(extra_env)
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--workload", "cfg2",
-                              "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--companion", "0", "--live-traffic", "0"],
+                              "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--companion", "0",
+                              "--live-traffic", "0"],
                              env=env, capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

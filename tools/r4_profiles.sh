@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 bench() { # name args...
   n=$1; shift
-  timeout 900 python bench.py "$@" > $O/r4_bench_$n.json 2> $O/r4_bench_$n.log
+  timeout 900 python bench.py --full "$@" > $O/r4_bench_$n.json 2> $O/r4_bench_$n.log
   grep -h "stages" $O/r4_bench_$n.log | tail -1 | cut -c1-240
 }
 stats() { # name args...   rocprofv3 --kernel-trace --stats of the bench command + summary of the trace database

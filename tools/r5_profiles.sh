@@ -16,17 +16,17 @@ stats() { # name cmd...   rocprofv3 --kernel-trace --stats of the command + per-
 pmc() { n=$1; shift; timeout 1800 python tools/pmc_hbm.py $O/r5_${n}_pmc_hbm.json -- "$@" > $O/r5_${n}_pmc.log 2>&1; }
 case "${1:-all}" in
 headline)
-  timeout 900 python bench.py --steps 10 --warmup 2 > $O/r5_bench_cfg3.json 2> $O/r5_bench_cfg3.log
+  timeout 900 python bench.py --full --steps 10 --warmup 2 > $O/r5_bench_cfg3.json 2> $O/r5_bench_cfg3.log
   stats cfg3 python $R/bench.py --steps 5 --warmup 1 $W
   pmc cfg3 python $R/bench.py --steps 2 --warmup 1 $W
   ;;
 mappedbench)
-  timeout 900 python bench.py --geometry volume --steps 3 --warmup 1 --no-cpu-baseline --companion 0 --live-traffic 0 > $O/r5_bench_cfg3_mapped_geometry.json 2> $O/r5_bench_cfg3_mapped_geometry.log
+  timeout 900 python bench.py --full --geometry volume --steps 3 --warmup 1 --no-cpu-baseline --companion 0 --live-traffic 0 > $O/r5_bench_cfg3_mapped_geometry.json 2> $O/r5_bench_cfg3_mapped_geometry.log
   stats cfg3_mapped python $R/bench.py --geometry volume --steps 2 --warmup 1 $W
   pmc cfg3_mapped python $R/bench.py --geometry volume --steps 1 --warmup 1 $W
   ;;
 mapped)
-  timeout 900 python bench.py --geometry volume --steps 3 --warmup 1 --no-cpu-baseline --companion 0 --live-traffic 0 > $O/r5_bench_cfg3_mapped_geometry.json 2> $O/r5_bench_cfg3_mapped_geometry.log
+  timeout 900 python bench.py --full --geometry volume --steps 3 --warmup 1 --no-cpu-baseline --companion 0 --live-traffic 0 > $O/r5_bench_cfg3_mapped_geometry.json 2> $O/r5_bench_cfg3_mapped_geometry.log
   stats cfg3_mapped python $R/bench.py --geometry volume --steps 2 --warmup 1 $W
   pmc cfg3_mapped python $R/bench.py --geometry volume --steps 1 --warmup 1 $W
   python tools/pmc_sq.py k_asf3 -- python tools/asm_bench.py 3 64 laplace 1 > $O/r5_assembly_p3_laplace_sq_counters.txt 2>&1
@@ -48,11 +48,11 @@ table)
   pmc elemsplit python $R/tools/elem_ptap_bench.py 3 64 /dev/null 0
   ;;
 small)
-  timeout 600 python bench.py --workload cfg2 --steps 10 --warmup 2 --no-cpu-baseline > $O/r5_bench_cfg2.json 2> $O/r5_bench_cfg2.log
-  timeout 600 python bench.py --workload cfg4 --steps 5 --warmup 2 > $O/r5_bench_cfg4_lu.json 2> $O/r5_bench_cfg4_lu.log
-  timeout 600 python bench.py --workload cfg4 --solver cg --rtol 1e-10 --steps 5 --warmup 2 > $O/r5_bench_cfg4_cg.json 2> $O/r5_bench_cfg4_cg.log
-  timeout 600 python bench.py --workload cfg5 --rtol 1e-10 --steps 10 --warmup 2 > $O/r5_bench_cfg5.json 2> $O/r5_bench_cfg5.log
-  TIGAR_COMM=ipc TIGAR_DEVICE=0 timeout 900 python bench.py --workload cfg2 --gpus 2 --steps 5 --warmup 2 $W > $O/r5_bench_cfg2_2ranks_ipc_one_gpu.json 2> $O/r5_bench_cfg2_2ranks.log
+  timeout 600 python bench.py --full --workload cfg2 --steps 10 --warmup 2 --no-cpu-baseline > $O/r5_bench_cfg2.json 2> $O/r5_bench_cfg2.log
+  timeout 600 python bench.py --full --workload cfg4 --steps 5 --warmup 2 > $O/r5_bench_cfg4_lu.json 2> $O/r5_bench_cfg4_lu.log
+  timeout 600 python bench.py --full --workload cfg4 --solver cg --rtol 1e-10 --steps 5 --warmup 2 > $O/r5_bench_cfg4_cg.json 2> $O/r5_bench_cfg4_cg.log
+  timeout 600 python bench.py --full --workload cfg5 --rtol 1e-10 --steps 10 --warmup 2 > $O/r5_bench_cfg5.json 2> $O/r5_bench_cfg5.log
+  TIGAR_COMM=ipc TIGAR_DEVICE=0 timeout 900 python bench.py --full --workload cfg2 --gpus 2 --steps 5 --warmup 2 $W > $O/r5_bench_cfg2_2ranks_ipc_one_gpu.json 2> $O/r5_bench_cfg2_2ranks.log
   ;;
 esac
 ls $O | head -60

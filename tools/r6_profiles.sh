@@ -27,7 +27,7 @@ elemsplit)
   ;;
 general)
   # cfg3's size with NOTHING assumed about M or A: M materialised chunk by chunk, A in row blocks, element chunks
-  $GEN timeout 900 python bench.py --workload cfg3 --steps 3 --warmup 1 $W > $O/r6_bench_cfg3_general_elements.json 2> $O/r6_bench_cfg3_general_elements.log
+  $GEN timeout 900 python bench.py --full --workload cfg3 --steps 3 --warmup 1 $W > $O/r6_bench_cfg3_general_elements.json 2> $O/r6_bench_cfg3_general_elements.log
   stats cfg3_general $GEN python $R/bench.py --workload cfg3 --steps 2 --warmup 1 $W
   pmc cfg3_general $GEN python $R/bench.py --workload cfg3 --steps 1 --warmup 1 $W
   ;;
@@ -46,7 +46,7 @@ quad)
   pmc asm_quad_p3 python $R/tools/asm_bench.py 3 64 laplace 3
   python tools/pmc_sq.py k_asf3 -- python tools/asm_bench.py 3 64 laplace 3 > $O/r6_asm_quad_p3_sq_counters.txt 2>&1
   TIGAR_ASM_QUAD=0 timeout 600 python tools/pmc_hbm.py $O/r6_asm_elem_p3_pmc_hbm.json -- python tools/asm_bench.py 3 64 laplace 3 > $O/r6_asm_elem_p3_pmc.log 2>&1
-  timeout 900 python bench.py --steps 3 --warmup 1 $W --geometry volume > $O/r6_bench_cfg3_mapped_geometry.json 2> $O/r6_bench_cfg3_mapped_geometry.log
+  timeout 900 python bench.py --full --steps 3 --warmup 1 $W --geometry volume > $O/r6_bench_cfg3_mapped_geometry.json 2> $O/r6_bench_cfg3_mapped_geometry.log
   stats cfg3_mapped python $R/bench.py --steps 2 --warmup 1 $W --geometry volume
   pmc cfg3_mapped python $R/bench.py --steps 1 --warmup 1 $W --geometry volume
   ;;
@@ -61,14 +61,14 @@ halfstorage)
   ;;
 cholesky)
   # the direct solves on the final tree: cfg4 (narrow band: look-ahead, sweeps) and a 3-D system (wide band: groups of panels)
-  timeout 300 python bench.py --workload cfg4 --solver lu --steps 5 --warmup 1 --no-cpu-baseline --companion 0 > $O/r6_bench_cfg4_cholesky.json 2> $O/r6_bench_cfg4_cholesky.log
+  timeout 300 python bench.py --full --workload cfg4 --solver lu --steps 5 --warmup 1 --no-cpu-baseline --companion 0 > $O/r6_bench_cfg4_cholesky.json 2> $O/r6_bench_cfg4_cholesky.log
   stats cfg4_cholesky python $R/bench.py --workload cfg4 --solver lu --steps 3 --warmup 1 --no-cpu-baseline --companion 0
   pmc cfg4_cholesky python $R/bench.py --workload cfg4 --solver lu --steps 2 --warmup 1 --no-cpu-baseline --companion 0
   python tools/kernel_trace.py --sum -- python tools/direct3d_bench.py 2 64 > $O/r6_direct3d_64_kernel_stats.txt 2>&1
   { for a in "2 48" "2 64" "3 40"; do TIGAR_TRACE=1 timeout 300 python tools/direct3d_bench.py $a 2>&1 | grep "default solver\|K:\|workgroups"; done; } > $O/r6_direct3d_final.txt 2>&1
   ;;
 headline)
-  timeout 900 python bench.py --steps 10 --warmup 2 > $O/r6_bench_cfg3.json 2> $O/r6_bench_cfg3.log
+  timeout 900 python bench.py --full --steps 10 --warmup 2 > $O/r6_bench_cfg3.json 2> $O/r6_bench_cfg3.log
   stats cfg3 python $R/bench.py --steps 5 --warmup 1 $W
   pmc cfg3 python $R/bench.py --steps 2 --warmup 1 $W
   ;;
