@@ -24,6 +24,7 @@ typedef struct tg_vec_s *tg_vec_t;   /* device-resident fp64 vector             
 typedef struct tg_ptap_s *tg_ptap_t; /* symbolic plan of K = M^T A M             */
 typedef struct tg_cellplan_s *tg_cellplan_t; /* K = M^T A M on a cell-local FE space: dense blocks per cell */
 typedef struct tg_comm_s *tg_comm_t; /* RCCL communicator + z-slab descriptor    */
+typedef struct tg_fd_s *tg_fd_t;     /* fast diagonalization preconditioner (csrc/tg_fd.hip) */
 
 /* ---- runtime ------------------------------------------------------------------ */
 int tg_init(int device);                   /* binds the HIP device, creates the stream */
@@ -429,6 +430,26 @@ enum { TG_KSP_NONZERO_GUESS = 1, TG_KSP_STAGNATION_GUARD = 2, TG_KSP_SYMMETRIC =
 int tg_krylov_solve_flags(tg_csr_t k, tg_vec_t b, tg_vec_t x, int method, int pc, double rtol,
                           double atol, int maxit, int restart, int flags, tg_comm_t comm, int *iters,
                           double *resnorm, int *status);
+
+/* Fast diagonalization preconditioner for CG on tensor-product patches (csrc/tg_fd.hip): per field block (dofs
+ * [offset, offset + prod shape), direction 0 fastest) z = S P^-1 S r on the free box [lo, hi), P the Kronecker sum of the
+ * 1-D parametric stiffness / mass matrices with coefficients c_k / c_m, S = D^-1/2 with D = diag K / diag P (or I), and
+ * z_i = r_i / K_ii off the box.  tg_fd_add_block takes, per direction k (concatenated over k), the generalized
+ * eigenvectors Q_k (nf_k x nf_k, row-major, Q_k^T M_k Q_k = I), their eigenvalues and the diagonals of the 1-D stiffness /
+ * mass on the free box (nf_k = hi_k - lo_k <= 4096).  tg_fd_fit records diag K and returns per block the four sums
+ * <diag K, t_a> over the free box (rhs[4 b + a]; t_a = diagonal of stiffness term a < d, a = 3 the mass term);
+ * tg_fd_set_coefficients takes coef[4 b + a] in the same order (>= 0) and scaling (1 = D^-1/2, 0 = none).
+ * tg_fd_apply: z = B r (bit-reproducible).  tg_krylov_solve_fd: CG with it, convergence and status as tg_krylov_solve;
+ * flags: TG_KSP_NONZERO_GUESS, TG_KSP_SYMMETRIC. */
+int tg_fd_create(int64_t n, tg_fd_t *out);
+int tg_fd_add_block(tg_fd_t fd, int d, int64_t offset, const int64_t *shape, const int64_t *lo, const int64_t *hi,
+                    const double *Q, const double *lam, const double *dk, const double *dm);
+int tg_fd_fit(tg_fd_t fd, tg_csr_t k, double *rhs);
+int tg_fd_set_coefficients(tg_fd_t fd, const double *coef, int scaling);
+int tg_fd_apply(tg_fd_t fd, tg_vec_t r, tg_vec_t z);
+int tg_fd_destroy(tg_fd_t fd);
+int tg_krylov_solve_fd(tg_csr_t k, tg_fd_t fd, tg_vec_t b, tg_vec_t x, double rtol, double atol, int maxit, int flags,
+                       int *iters, double *resnorm, int *status);
 
 /* generateM for a spline given by element-wise Bezier extraction operators (Rhino T-splines,
  * tIGAr/RhinoTSplines.py:37-137 + the row loop of tIGAr/common.py:1554-1571): FE row (e, n) holds

@@ -15,3 +15,4 @@ from .common import (AbstractExtractionGenerator, AbstractCoordinateChartSpline,
                      TensorNodeGrid, multTranspose, generateIdentityPermutation,
                      ExtractedNonlinearProblem, ExtractedNonlinearSolver, NewtonSolver)
 from .NURBS import NURBSControlMesh      # noqa: E402,F401
+from .fastdiag import FastDiagonalization  # noqa: E402,F401

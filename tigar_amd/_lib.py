@@ -177,6 +177,14 @@ PROTOTYPES = {
     "tg_krylov_solve_flags": (C.c_int, [handle, handle, handle, C.c_int, C.c_int, C.c_double, C.c_double,
                                         C.c_int, C.c_int, C.c_int, handle, C.POINTER(C.c_int), c_f64p,
                                         C.POINTER(C.c_int)]),
+    "tg_fd_create": (C.c_int, [C.c_int64, C.POINTER(handle)]),
+    "tg_fd_add_block": (C.c_int, [handle, C.c_int, C.c_int64, c_i64p, c_i64p, c_i64p, c_f64p, c_f64p, c_f64p, c_f64p]),
+    "tg_fd_fit": (C.c_int, [handle, handle, c_f64p]),
+    "tg_fd_set_coefficients": (C.c_int, [handle, c_f64p, C.c_int]),
+    "tg_fd_apply": (C.c_int, [handle, handle, handle]),
+    "tg_fd_destroy": (C.c_int, [handle]),
+    "tg_krylov_solve_fd": (C.c_int, [handle, handle, handle, handle, C.c_double, C.c_double, C.c_int, C.c_int,
+                                     C.POINTER(C.c_int), c_f64p, C.POINTER(C.c_int)]),
     "tg_lu_band_info": (C.c_int, [handle, C.POINTER(C.c_int), C.POINTER(C.c_int), c_i64p]),
     "tg_lu_solve": (C.c_int, [handle, handle, handle, C.POINTER(C.c_int)]),
     "tg_chol_solve": (C.c_int, [handle, handle, handle, C.POINTER(C.c_int)]),

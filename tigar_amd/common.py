@@ -18,6 +18,7 @@ instead of the reference's ``print("ERROR"); exit()``.
 import abc
 import os
 import sys
+import time
 import numpy
 from numpy import array, zeros, arange
 
@@ -1183,11 +1184,13 @@ class PETScKrylovSolver(object):
             else:
                 preconditioner = "jacobi"
                 note += "Jacobi stands in for it with %s)" % method
-        if preconditioner not in ("none", "jacobi", "chebyshev"):
-            raise ValueError("unknown preconditioner %r (none, jacobi, chebyshev, or one of dolfin's: %s)"
-                             % (preconditioner, ", ".join(self.STRONG_PCS)))
+        if preconditioner not in ("none", "jacobi", "chebyshev", "fast_diagonalization"):
+            raise ValueError("unknown preconditioner %r (none, jacobi, chebyshev, fast_diagonalization, or one of dolfin's: "
+                             "%s)" % (preconditioner, ", ".join(self.STRONG_PCS)))
         if preconditioner == "chebyshev" and method != "cg":
             raise ValueError("the Chebyshev polynomial preconditioner serves cg (a fixed symmetric polynomial)")
+        if preconditioner == "fast_diagonalization" and (method != "cg" or self.method_requested != "cg"):
+            raise ValueError("the fast diagonalization preconditioner serves cg only (a symmetric positive definite P)")
         self.method, self.preconditioner = method, preconditioner
         if method != self.method_requested and self.method_requested != "default":
             note = (note or "") + " (method %r requested: %s runs in its place)" % (self.method_requested, method)
@@ -1206,7 +1209,10 @@ class PETScKrylovSolver(object):
                            # (not a dolfin parameter) give up with status -3 after 25 GMRES restart cycles without
                            # progress instead of running to the iteration limit as PETSc does; set by the default
                            # solver that stands in for the reference's direct LU on large systems
-                           "stagnation_guard": False}
+                           "stagnation_guard": False,
+                           # (not dolfin parameters) fast_diagonalization: None = coefficients fitted to diag K, or
+                           # (c_0, .., c_{d-1}, c_mass); "diagonal" = D^-1/2 P^-1 D^-1/2 with D = diag K / diag P, or "none"
+                           "fd_coefficients": None, "fd_scaling": "diagonal"}
         self.comm = comm
         self.last = None
         self.note = note       # appended to the non-convergence message (who chose this solver / what stands in)
@@ -1219,6 +1225,8 @@ class PETScKrylovSolver(object):
         (the convergence test stays relative to ||B b||, PETSc's default [ext])."""
         A, x, b = _as_device_csr(A), _as_device_vector(x), _as_device_vector(b)
         guess = bool(self.parameters["nonzero_initial_guess"])
+        if self.preconditioner == "fast_diagonalization":
+            return self._solve_fd(A, x, b, guess)
 
         def run(pc):
             return _dev.krylov_solve(
@@ -1260,6 +1268,29 @@ class PETScKrylovSolver(object):
                                "residual %.3e.%s" % (self.method, self.preconditioner,
                                                      self.REASONS.get(status, "status %d" % status), its, res,
                                                      self.note or ""))
+        return its
+
+
+    def _solve_fd(self, A, x, b, guess):
+        from .fastdiag import FastDiagonalization
+        if self.comm is not None:
+            raise ValueError("fast_diagonalization: several ranks are not supported (the transform of the slab direction "
+                             "would need an all-to-all)")
+        fd = FastDiagonalization(A, coefficients=self.parameters["fd_coefficients"], scaling=self.parameters["fd_scaling"])
+        t0 = time.perf_counter()
+        its, res, status = _dev.krylov_solve_fd(A, fd.device, b, x, self.parameters["relative_tolerance"],
+                                                self.parameters["absolute_tolerance"],
+                                                self.parameters["maximum_iterations"], nonzero_initial_guess=guess,
+                                                symmetric=bool(getattr(A, "symmetric_by_construction", False)))
+        self.last = {"iterations": its, "residual_norm": res, "status": status, "method": self.method,
+                     "preconditioner": "fast_diagonalization", "method_requested": self.method_requested,
+                     "preconditioner_requested": self.preconditioner_requested,
+                     "fd": {"coefficients": fd.coefficients, "setup_seconds": fd.setup_seconds,
+                            "setup_reused": fd.setup_reused, "fit_seconds": fd.fit_seconds, "scaling": fd.scaling,
+                            "solve_seconds": time.perf_counter() - t0}}
+        if status < 0 and self.parameters["error_on_nonconvergence"]:
+            raise RuntimeError("Krylov solver (cg, fast_diagonalization) did not converge: %s after %d iterations, "
+                               "preconditioned residual %.3e." % (self.REASONS.get(status, "status %d" % status), its, res))
         return its
 
 
@@ -1627,7 +1658,47 @@ class ExtractedSpline(object):
     def extractMatrix(self, A, applyBCs=True, diag=1):
         """Apply extraction to an FE matrix ``A``: ``M^T A M`` (PtAP), then rows and columns
         of ``zeroDofs`` zeroed with ``diag`` on the diagonal (tIGAr/common.py:1176-1204).
-        The symbolic plan is cached and reused while A's pattern is unchanged."""
+        The symbolic plan is cached and reused while A's pattern is unchanged.  A K of a single tensor-product patch on
+        one rank carries ``K.tensor_structure`` (what the fast diagonalization preconditioner needs, tigar_amd/fastdiag.py);
+        otherwise ``K.tensor_structure_refusal`` says why not."""
+        K = self._extract_matrix(A, applyBCs, diag)
+        if isinstance(K, DeviceCSR):
+            ts, why = self._tensor_structure(applyBCs)
+            if ts is not None:
+                K.tensor_structure = ts
+            else:
+                K.tensor_structure_refusal = why
+        return K
+
+    def tensor_structure(self):
+        """the ``fastdiag.TensorStructure`` of this spline's K (zero dofs applied), or None"""
+        return self._tensor_structure(True)[0]
+
+    def _tensor_structure(self, applyBCs):
+        """(descriptor, None) when the space qualifies for the fast diagonalization preconditioner, else (None, reason)"""
+        if self._distributed():
+            return None, "several ranks (the transform of the slab direction would need an all-to-all)"
+        gen = getattr(self, "_generator", None)
+        perm = getattr(gen, "permutation", None)
+        if perm is not None and numpy.asarray(perm).size and \
+                not numpy.array_equal(numpy.asarray(perm), numpy.arange(numpy.asarray(perm).size)):
+            return None, "a dof permutation was applied to the generator (the dofs are no longer numbered as a tensor grid)"
+        if getattr(self, "_kron_fields", None) is not None and self._kron is None:
+            return None, "fields on different bases (FieldListSpline / compatible spaces) are not supported"
+        kx = self._kron if self._kron is not None else getattr(self, "_kron_scalar", None)
+        if kx is None:
+            return None, ("the extraction operator is not the Kronecker product of 1-D B-spline factors (not a single "
+                          "tensor-product patch)")
+        if kx.d not in (2, 3):
+            return None, "only 2-D and 3-D patches are supported"
+        nf = self.nFields if self._kron is None else 1
+        if self._kron is not None and self.nFields != 1:
+            return None, "the extraction operator is not the Kronecker product of 1-D B-spline factors"
+        cache = self.__dict__.setdefault("_fd_cache", {})
+        from .fastdiag import TensorStructure
+        return TensorStructure(kx, nf, self.zeroDofs if applyBCs else None, cache), None
+
+    def _extract_matrix(self, A, applyBCs=True, diag=1):
         from .implicit import LazyFEMatrix
         zd = self.zeroDofs if applyBCs else None
         if isinstance(A, LazyFEMatrix) or self._distributed() or (self._implicit() and self.nFields > 1):

@@ -736,6 +736,53 @@ def krylov_solve(K, b, x, method="cg", pc="jacobi", rtol=1e-6, atol=1e-15, maxit
     return iters.value, res.value, status.value
 
 
+class DeviceFD(object):
+    """Fast diagonalization preconditioner on the device (csrc/tg_fd.hip): one block per field, see tigar_amd/fastdiag.py"""
+
+    def __init__(self, n):
+        self._h = handle()
+        check(_lib.lib().tg_fd_create(int(n), C.byref(self._h)), "tg_fd_create")
+        self.n = int(n)
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().tg_fd_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def add_block(self, offset, shape, lo, hi, Q, lam, dk, dm):
+        """per direction k: Q[k] (nf x nf, Q^T M Q = I), lam[k], dk[k] / dm[k] (1-D diagonals on the free box)"""
+        d = len(shape)
+        qs = _f64(np.concatenate([np.ascontiguousarray(q, dtype=np.float64).ravel() for q in Q]))
+        ls, ks, ms = (_f64(np.concatenate([np.asarray(v, dtype=np.float64) for v in vs])) for vs in (lam, dk, dm))
+        sh, l0, h0 = _i64(shape), _i64(lo), _i64(hi)
+        check(_lib.lib().tg_fd_add_block(self._h, d, int(offset), _p(sh, c_i64p), _p(l0, c_i64p), _p(h0, c_i64p),
+                                         _p(qs, c_f64p), _p(ls, c_f64p), _p(ks, c_f64p), _p(ms, c_f64p)), "tg_fd_add_block")
+
+    def fit(self, K, nblocks):
+        """diag K recorded; per block the sums <diag K, t_a> (array [nblocks, 4]: a < d stiffness terms, 3 = mass)"""
+        rhs = np.zeros(4 * nblocks)
+        check(_lib.lib().tg_fd_fit(self._h, K._h, _p(rhs, c_f64p)), "tg_fd_fit")
+        return rhs.reshape(nblocks, 4)
+
+    def set_coefficients(self, coef, scaling):
+        c = _f64(np.asarray(coef, dtype=np.float64).ravel())
+        check(_lib.lib().tg_fd_set_coefficients(self._h, _p(c, c_f64p), 1 if scaling else 0), "tg_fd_set_coefficients")
+
+    def apply(self, r, z):
+        check(_lib.lib().tg_fd_apply(self._h, r._h, z._h), "tg_fd_apply")
+
+
+def krylov_solve_fd(K, fd, b, x, rtol=1e-6, atol=1e-15, maxit=10000, nonzero_initial_guess=False, symmetric=False):
+    iters, status, res = C.c_int(), C.c_int(), C.c_double()
+    flags = (TG_KSP_NONZERO_GUESS if nonzero_initial_guess else 0) | (TG_KSP_SYMMETRIC if symmetric else 0)
+    check(_lib.lib().tg_krylov_solve_fd(K._h, fd._h, b._h, x._h, float(rtol), float(atol), int(maxit), flags,
+                                        C.byref(iters), C.byref(res), C.byref(status)), "tg_krylov_solve_fd")
+    return iters.value, res.value, status.value
+
+
 def lu_band_info(K):
     """(kl, ku, bytes of the band storage) of a square DeviceCSR"""
     kl, ku, nb = C.c_int(), C.c_int(), C.c_int64()
