@@ -451,6 +451,29 @@ int tg_fd_destroy(tg_fd_t fd);
 int tg_krylov_solve_fd(tg_csr_t k, tg_fd_t fd, tg_vec_t b, tg_vec_t x, double rtol, double atol, int maxit, int flags,
                        int *iters, double *resnorm, int *status);
 
+/* Block kernels of the LOBPCG eigensolver (csrc/tg_eig.hip; tigar_amd/eigen.py).  A block is a tg_vec_t of n * k doubles,
+ * row-major (entry (i, j) at i * k + j), 1 <= k <= 64 (other widths: error).  Every result is bit-reproducible (fixed
+ * summation orders, no floating-point atomics).  tg_spmm: Y = A X for a canonical CSR A (loose-row / view CSRs: error), A
+ * read once.  tg_block_gram: G = X^T Y (kx x ky, row-major, host).  tg_block_combine: Y = sum_s X_s C_s over the inputs
+ * that are not null (C_s: k_s x ky, row-major, host; Y must not be an input).  tg_block_residual: R = AX - BX diag(lam)
+ * with the rows where mask != 0 zeroed, W = dinv .* R (W = R without dinv; W optional), rnorm2[j] = |R_j|^2 and
+ * bxnorm2[j] = |BX_j|^2 (optional) on the host.  tg_block_get_column / tg_block_set_column: column j of X to / from v.
+ * tg_csr_decoupled_rows: mark[i] = 1 where the only non-zero of row i of A and of B (B null = identity) is the diagonal,
+ * 0 elsewhere, da / db = the diagonals, *count = rows marked, *arow (optional) = the largest sum of |a_ij| over the rows
+ * not marked.  tg_csr_sym_defect: max |A - at| over the union pattern and
+ * max |A_ij| over i != j (the scale: a penalty on the diagonal does not hide a defect) for at = tg_csr_transpose(A) (rows of both ascending; *unsorted = 1 when a row of A is not). */
+int tg_spmm(tg_csr_t a, tg_vec_t x, int k, tg_vec_t y);
+int tg_block_gram(tg_vec_t x, int kx, tg_vec_t y, int ky, int64_t n, double *g_host);
+int tg_block_combine(tg_vec_t y, int ky, int64_t n, tg_vec_t x0, int k0, const double *c0, tg_vec_t x1, int k1,
+                     const double *c1, tg_vec_t x2, int k2, const double *c2);
+int tg_block_residual(tg_vec_t ax, tg_vec_t bx, const double *lam, int k, int64_t n, tg_vec_t mask, tg_vec_t dinv,
+                      tg_vec_t r, tg_vec_t w, double *rnorm2, double *bxnorm2);
+int tg_block_get_column(tg_vec_t x, int k, int j, tg_vec_t v);
+int tg_block_set_column(tg_vec_t x, int k, int j, tg_vec_t v);
+int tg_csr_decoupled_rows(tg_csr_t a, tg_csr_t b, tg_vec_t mark, tg_vec_t da, tg_vec_t db, int64_t *count,
+                          double *arow);
+int tg_csr_sym_defect(tg_csr_t a, tg_csr_t at, double *defect, double *amax, int *unsorted);
+
 /* generateM for a spline given by element-wise Bezier extraction operators (Rhino T-splines,
  * tIGAr/RhinoTSplines.py:37-137 + the row loop of tIGAr/common.py:1554-1571): FE row (e, n) holds
  * N_a = sum_b coef[a][b] * bern[e][n][b] for the functions a of element e (eoff[e] <= a < eoff[e+1], global index

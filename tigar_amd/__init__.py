@@ -16,3 +16,4 @@ from .common import (AbstractExtractionGenerator, AbstractCoordinateChartSpline,
                      ExtractedNonlinearProblem, ExtractedNonlinearSolver, NewtonSolver)
 from .NURBS import NURBSControlMesh      # noqa: E402,F401
 from .fastdiag import FastDiagonalization  # noqa: E402,F401
+from .eigen import SLEPcEigenSolver  # noqa: E402,F401

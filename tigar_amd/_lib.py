@@ -185,6 +185,16 @@ PROTOTYPES = {
     "tg_fd_destroy": (C.c_int, [handle]),
     "tg_krylov_solve_fd": (C.c_int, [handle, handle, handle, handle, C.c_double, C.c_double, C.c_int, C.c_int,
                                      C.POINTER(C.c_int), c_f64p, C.POINTER(C.c_int)]),
+    "tg_spmm": (C.c_int, [handle, handle, C.c_int, handle]),
+    "tg_block_gram": (C.c_int, [handle, C.c_int, handle, C.c_int, C.c_int64, c_f64p]),
+    "tg_block_combine": (C.c_int, [handle, C.c_int, C.c_int64, handle, C.c_int, c_f64p, handle, C.c_int, c_f64p, handle,
+                                   C.c_int, c_f64p]),
+    "tg_block_residual": (C.c_int, [handle, handle, c_f64p, C.c_int, C.c_int64, handle, handle, handle, handle, c_f64p,
+                                    c_f64p]),
+    "tg_block_get_column": (C.c_int, [handle, C.c_int, C.c_int, handle]),
+    "tg_block_set_column": (C.c_int, [handle, C.c_int, C.c_int, handle]),
+    "tg_csr_decoupled_rows": (C.c_int, [handle, handle, handle, handle, handle, c_i64p, c_f64p]),
+    "tg_csr_sym_defect": (C.c_int, [handle, handle, c_f64p, c_f64p, C.POINTER(C.c_int)]),
     "tg_lu_band_info": (C.c_int, [handle, C.POINTER(C.c_int), C.POINTER(C.c_int), c_i64p]),
     "tg_lu_solve": (C.c_int, [handle, handle, handle, C.POINTER(C.c_int)]),
     "tg_chol_solve": (C.c_int, [handle, handle, handle, C.POINTER(C.c_int)]),

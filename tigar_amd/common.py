@@ -2405,3 +2405,7 @@ class ExtractedNonlinearSolver(object):
         self.solver.solve(self.problem, tempVec)
         self.problem.spline.M.mult(tempVec, self.problem.solution.vector())
         return tempVec
+
+
+# the eigensolver look-alike (tigar_amd/eigen.py: block LOBPCG on the device)
+from .eigen import SLEPcEigenSolver  # noqa: E402,F401

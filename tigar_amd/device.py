@@ -79,6 +79,22 @@ class DeviceVector(object):
 
     to_numpy = get_local
 
+    def __setitem__(self, key, value):
+        """``v[:] = w`` (dolfin's whole-vector assignment): w a DeviceVector, an array or a scalar"""
+        if not (isinstance(key, slice) and key == slice(None)):
+            raise IndexError("DeviceVector supports whole-vector assignment v[:] = ... only")
+        if isinstance(value, DeviceVector):
+            if value.size() != self.size():
+                raise ValueError("v[:] = w: %d entries assigned to a vector of %d" % (value.size(), self.size()))
+            check(_lib.lib().tg_vec_copy(self._h, value._h), "tg_vec_copy")
+        elif np.ndim(value) == 0:
+            self.fill(float(value))
+        else:
+            value = _f64(value)
+            if value.shape != (self.size(),):
+                raise ValueError("v[:] = w: %s entries assigned to a vector of %d" % (value.shape, self.size()))
+            self.set_local(value)
+
     def copy(self):
         v = DeviceVector(self.size())
         check(_lib.lib().tg_vec_copy(v._h, self._h))
@@ -781,6 +797,120 @@ def krylov_solve_fd(K, fd, b, x, rtol=1e-6, atol=1e-15, maxit=10000, nonzero_ini
     check(_lib.lib().tg_krylov_solve_fd(K._h, fd._h, b._h, x._h, float(rtol), float(atol), int(maxit), flags,
                                         C.byref(iters), C.byref(res), C.byref(status)), "tg_krylov_solve_fd")
     return iters.value, res.value, status.value
+
+
+BLOCK_MAX = 64      # widest block the kernels of csrc/tg_eig.hip take
+
+
+class DeviceBlock(object):
+    """n x k fp64 block in HBM, row-major (entry (i, j) at i * k + j, 1 <= k <= 64): the operand of the block kernels of
+    csrc/tg_eig.hip (LOBPCG, tigar_amd/eigen.py).  ``vec`` is the DeviceVector of its n * k entries."""
+
+    def __init__(self, n, k, data=None, zero=True):
+        self.n, self.k = int(n), int(k)
+        if not 1 <= self.k <= BLOCK_MAX:
+            raise ValueError("DeviceBlock: width %d outside [1, %d]" % (self.k, BLOCK_MAX))
+        if data is not None:
+            data = _f64(data).reshape(self.n, self.k)
+            self.vec = DeviceVector(data=data.ravel())
+        else:
+            self.vec = DeviceVector(self.n * self.k, zero=zero)
+
+    @property
+    def _h(self):
+        return self.vec._h
+
+    def to_numpy(self):
+        return self.vec.get_local().reshape(self.n, self.k)
+
+    def get_column(self, j, v=None):
+        """column j as a DeviceVector"""
+        v = DeviceVector(self.n, zero=False) if v is None else v
+        check(_lib.lib().tg_block_get_column(self._h, self.k, int(j), v._h), "tg_block_get_column")
+        return v
+
+    def set_column(self, j, v):
+        check(_lib.lib().tg_block_set_column(self._h, self.k, int(j), v._h), "tg_block_set_column")
+
+
+def _mult_block(self, X, Y=None):
+    """Y = A X for a DeviceBlock X (tg_spmm: A is read once for all columns)"""
+    if Y is None:
+        Y = DeviceBlock(self.shape[0], X.k, zero=False)
+    check(_lib.lib().tg_spmm(self._h, X._h, int(X.k), Y._h), "tg_spmm")
+    return Y
+
+
+DeviceCSR.mult_block = _mult_block
+
+
+def spmm(A, X, k, Y):
+    """Y = A X on raw handles: X, Y DeviceVectors of ncols * k / nrows * k entries (row-major blocks)"""
+    check(_lib.lib().tg_spmm(A._h, X._h, int(k), Y._h), "tg_spmm")
+    return Y
+
+
+def block_gram(X, Y):
+    """X^T Y (X.k x Y.k) on the host"""
+    G = np.empty((X.k, Y.k), dtype=np.float64)
+    check(_lib.lib().tg_block_gram(X._h, X.k, Y._h, Y.k, X.n, _p(G, c_f64p)), "tg_block_gram")
+    return G
+
+
+def block_combine(terms, Y):
+    """Y = sum of X_s C_s over ``terms`` = [(X_s, C_s), ...] (at most three; C_s of shape X_s.k x Y.k)"""
+    if not 1 <= len(terms) <= 3:
+        raise ValueError("block_combine: 1 to 3 terms, not %d" % len(terms))
+    args, keep = [], []
+    for X, Cs in terms:
+        Cs = _f64(Cs)
+        if Cs.shape != (X.k, Y.k):
+            raise ValueError("block_combine: coefficients of shape %s for a %d-wide input and a %d-wide output"
+                             % (Cs.shape, X.k, Y.k))
+        keep.append(Cs)
+        args += [X._h, X.k, _p(Cs, c_f64p)]
+    while len(args) < 9:
+        args += [None, 0, None]
+    check(_lib.lib().tg_block_combine(Y._h, Y.k, Y.n, *args), "tg_block_combine")
+    return Y
+
+
+def block_residual(AX, BX, lam, R, W=None, mask=None, dinv=None):
+    """R = AX - BX diag(lam) (rows with mask != 0 zeroed), W = dinv .* R (or R); returns (|R_j|^2, |BX_j|^2) per column"""
+    lam = _f64(lam)
+    if lam.size != AX.k:
+        raise ValueError("block_residual: %d Ritz values for a %d-wide block" % (lam.size, AX.k))
+    rn, bn = np.empty(AX.k), np.empty(AX.k)
+    check(_lib.lib().tg_block_residual(AX._h, BX._h, _p(lam, c_f64p), AX.k, AX.n, mask._h if mask is not None else None,
+                                       dinv._h if dinv is not None else None, R._h, W._h if W is not None else None,
+                                       _p(rn, c_f64p), _p(bn, c_f64p)), "tg_block_residual")
+    return rn, bn
+
+
+def csr_decoupled_rows(A, B=None):
+    """(mark, diag A, diag B, count, arow): mark[i] = 1.0 where the only non-zero of row i of A and of B (None = identity) is
+    the diagonal (zero dofs of extractMatrix), as DeviceVectors; arow = the largest sum of |a_ij| over the other rows"""
+    n = A.shape[0]
+    mark, da = DeviceVector(n, zero=False), DeviceVector(n, zero=False)
+    db = DeviceVector(n, zero=False) if B is not None else None
+    cnt, arow = C.c_int64(), C.c_double()
+    check(_lib.lib().tg_csr_decoupled_rows(A._h, B._h if B is not None else None, mark._h, da._h,
+                                           db._h if db is not None else None, C.byref(cnt), C.byref(arow)),
+          "tg_csr_decoupled_rows")
+    return mark, da, db, cnt.value, arow.value
+
+
+def csr_sym_defect(A):
+    """(max |A - A^T|, max |A_ij|) through the explicit transpose, on the device"""
+    AT = A.transpose()
+    src = A
+    for _ in range(2):
+        d, amax, uns = C.c_double(), C.c_double(), C.c_int()
+        check(_lib.lib().tg_csr_sym_defect(src._h, AT._h, C.byref(d), C.byref(amax), C.byref(uns)), "tg_csr_sym_defect")
+        if not uns.value:
+            return d.value, amax.value
+        src = AT.transpose()        # (rows of A not ascending: compare the twice transposed copy, whose rows are)
+    raise RuntimeError("csr_sym_defect: the transpose of the transpose has unsorted rows")
 
 
 def lu_band_info(K):
