@@ -224,17 +224,20 @@ def test_cg_solve_on_the_half_storage_copy(dev, p, nel, mapped, monkeypatch):
     assert np.array_equal(U2.get_local().view(np.int64), res["1"][1].view(np.int64))
 
 
-def test_chebyshev_cg_on_the_half_storage_copy(dev, monkeypatch):
-    """CG with the Chebyshev polynomial preconditioner multiplies by the same copy (degree products per iteration)"""
+@pytest.mark.parametrize("pc", ["chebyshev", "fast_diagonalization"])
+def test_chebyshev_cg_on_the_half_storage_copy(dev, pc, monkeypatch):
+    """CG with the Chebyshev polynomial preconditioner (degree products per iteration) or with the fast diagonalization
+    multiplies by the same copy"""
     import tigar_amd as t
     from tigar_amd.device import DeviceVector
     spline, K, rhs = _poisson3d(2, (40, 40, 40))
+    assert pc != "fast_diagonalization" or getattr(K, "tensor_structure", None) is not None
     n = K.shape[0]
     monkeypatch.setenv("TIGAR_KSP_PERSISTENT", "0")
     out = {}
     for mode in ("0", "1"):
         monkeypatch.setenv("TIGAR_SPMV_SYM", mode)
-        ks = t.PETScKrylovSolver("cg", "chebyshev")
+        ks = t.PETScKrylovSolver("cg", pc)
         ks.parameters["relative_tolerance"] = 1e-9
         U = DeviceVector(n)
         c0 = dev.prof_get(7)[1]

@@ -1244,7 +1244,6 @@ class PETScKrylovSolver(object):
             x0 = DeviceVector(x.size())
             _dev.vec_copy_range(x0, 0, x, 0, x.size())
         its, res, status = run(self.preconditioner)
-        fallback = None
         if status == -2 and self.preconditioner == "chebyshev":
             # the polynomial is built on an ESTIMATE of the largest eigenvalue of D^-1 K (a few power iterations); an estimate
             # that is too small makes the polynomial indefinite and the recurrence breaks down although K is fine.
@@ -1257,18 +1256,8 @@ class PETScKrylovSolver(object):
                 _dev.vec_copy_range(x, 0, x0, 0, x.size())
             its_c = its
             its, res, status = run("jacobi")
-            fallback = {"preconditioner": "jacobi", "after_iterations": its_c}
-        self.last = {"iterations": its, "residual_norm": res, "status": status, "method": self.method,
-                     "preconditioner": fallback["preconditioner"] if fallback else self.preconditioner,
-                     "method_requested": self.method_requested, "preconditioner_requested": self.preconditioner_requested}
-        if fallback:
-            self.last["fallback"] = fallback
-        if status < 0 and self.parameters["error_on_nonconvergence"]:
-            raise RuntimeError("Krylov solver (%s, %s) did not converge: %s after %d iterations, preconditioned "
-                               "residual %.3e.%s" % (self.method, self.preconditioner,
-                                                     self.REASONS.get(status, "status %d" % status), its, res,
-                                                     self.note or ""))
-        return its
+            return self._finish(its, res, status, "jacobi", fallback={"preconditioner": "jacobi", "after_iterations": its_c})
+        return self._finish(its, res, status, self.preconditioner)
 
 
     def _solve_fd(self, A, x, b, guess):
@@ -1282,15 +1271,23 @@ class PETScKrylovSolver(object):
                                                 self.parameters["absolute_tolerance"],
                                                 self.parameters["maximum_iterations"], nonzero_initial_guess=guess,
                                                 symmetric=bool(getattr(A, "symmetric_by_construction", False)))
+        return self._finish(its, res, status, "fast_diagonalization",
+                            fd={"coefficients": fd.coefficients, "setup_seconds": fd.setup_seconds,
+                                "setup_reused": fd.setup_reused, "fit_seconds": fd.fit_seconds, "scaling": fd.scaling,
+                                "solve_seconds": time.perf_counter() - t0})
+
+    def _finish(self, its, res, status, preconditioner, **extra):
+        """records ``self.last`` (``preconditioner``: the one that ran; ``extra``: entries of that path) and raises on
+        non-convergence"""
         self.last = {"iterations": its, "residual_norm": res, "status": status, "method": self.method,
-                     "preconditioner": "fast_diagonalization", "method_requested": self.method_requested,
-                     "preconditioner_requested": self.preconditioner_requested,
-                     "fd": {"coefficients": fd.coefficients, "setup_seconds": fd.setup_seconds,
-                            "setup_reused": fd.setup_reused, "fit_seconds": fd.fit_seconds, "scaling": fd.scaling,
-                            "solve_seconds": time.perf_counter() - t0}}
+                     "preconditioner": preconditioner, "method_requested": self.method_requested,
+                     "preconditioner_requested": self.preconditioner_requested}
+        self.last.update(extra)
         if status < 0 and self.parameters["error_on_nonconvergence"]:
-            raise RuntimeError("Krylov solver (cg, fast_diagonalization) did not converge: %s after %d iterations, "
-                               "preconditioned residual %.3e." % (self.REASONS.get(status, "status %d" % status), its, res))
+            raise RuntimeError("Krylov solver (%s, %s) did not converge: %s after %d iterations, preconditioned "
+                               "residual %.3e.%s" % (self.method, self.preconditioner,
+                                                     self.REASONS.get(status, "status %d" % status), its, res,
+                                                     self.note or ""))
         return its
 
 

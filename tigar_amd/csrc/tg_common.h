@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
+#include <functional>
 #include <vector>
 #include "../../include/tigar_hip.h"
 
@@ -203,6 +204,38 @@ int tg_symgrid_spmv(tg_symgrid_s *s, tg_csr_s *a, const double *x_shifted, int64
                     const double *gate, double gate_tol);
 int tg_symgrid_chunks(const tg_symgrid_s *s);
 void tg_symgrid_info(const tg_symgrid_s *s, int64_t *val_bytes, int64_t *stage_bytes);
+
+// The products of one Krylov solve (tg_krylov.hip).  An operand is an extended vector [hlo halo | n owned | hhi halo] of
+// `next` entries that holds the global columns [cmin, cmax].  The products go through the half-storage copy of tg_symgrid.hip
+// when K is a box stencil on a 3-D grid and this rank holds all of it (CG family only: a symmetric K is its premise), else
+// through the sliced copy of tg_sell.hip (built for the solve and dropped with the context: it is a snapshot of the values; a
+// copy requested by the caller, tg_spmv_sell, is used and left alone), else through CSR.
+struct tg_comm_s;
+struct tg_ksp_op {
+  tg_csr_s *k = nullptr;
+  tg_comm_s *comm = nullptr;      // null: one rank
+  int64_t n = 0, hlo = 0, hhi = 0, row0 = 0, next = 0, cmin = 0, cmax = 0;
+  tg_symgrid_s *sym = nullptr;
+  bool sliced = false;            // the sliced copy is there (row ranges and gates of tg_sell_spmv_rows)
+  bool sell_temp = false;         // ... and was built for this solve
+  tg_ksp_op() = default;
+  tg_ksp_op(const tg_ksp_op &) = delete;
+  tg_ksp_op &operator=(const tg_ksp_op &) = delete;
+  ~tg_ksp_op();
+  // `half_storage`: the caller may use the half-storage copy; `symmetric`: TG_KSP_SYMMETRIC of the solve (the copy is then
+  // not compared with the CSR product)
+  int init(tg_csr_s *k, tg_comm_s *comm, bool half_storage, bool symmetric);
+  const double *shift(const double *xext) const { return xext - cmin; }   // xext addressed by global column index
+  // out = K xext after the halo exchange of xext.  `gate` (device, may be null): the launch returns at once when !(*gate >
+  // gate_tol) -- honoured by the half-storage and the sliced copy; without a gate the sliced copy is not asked.
+  int product(double *xext, double *out, const double *gate, double gate_tol);
+};
+// u = B r: r and u have n entries; u is the owned part of an operand of the solve's tg_ksp_op (B may multiply by K there)
+typedef std::function<int(const double *r, double *u)> tg_pc_apply;
+// preconditioned CG driven from the host (single-reduction recurrence, scalars read back every iteration), convergence on
+// ||B r|| <= max(rtol ||B b||, atol) (tg_krylov.hip)
+int tg_pcg_host(tg_ksp_op &op, const tg_pc_apply &apply, tg_vec_s *b, tg_vec_s *x, double rtol, double atol, int maxit,
+                int nonzero_guess, int *iters, double *resnorm, int *status);
 
 int tg_csr_sort_rows(tg_csr_s *m);
 int tg_csr_transpose_block(tg_csr_s *m, int64_t row_base, int64_t out_ncols, tg_csr_s **out);

@@ -15,8 +15,8 @@
 // chunks of 32 through LDS with the next chunk requested into registers before the MFMAs of the current one.  No atomics:
 // every output element is one MFMA chain in a fixed order, so applications are bit-reproducible.
 //
-// tg_pcg_fd: CG preconditioned with the FD application; the products of K as the other CG solves choose them (half-storage
-// copy of tg_symgrid.hip when it applies, else the sliced copy or CSR), convergence on ||B r|| <= max(rtol ||B b||, atol).
+// tg_krylov_solve_fd: the PCG loop of tg_krylov.hip (tg_pcg_host) with the FD application as B; the products of K as the other
+// CG solves choose them (half-storage copy of tg_symgrid.hip when it applies, else the sliced copy or CSR).
 #include "tg_common.h"
 #include <math.h>
 #include <vector>
@@ -484,185 +484,6 @@ extern "C" int tg_fd_apply(tg_fd_t fd, tg_vec_t r, tg_vec_t z) {
   return tg_fd_apply_dev(fd, r->d, z->d);
 }
 
-// ------------------------------------------------------------------------------------------------- PCG
-// partials of (r,u), (w,u), (u,u), interleaved
-__global__ void __launch_bounds__(256) k_fd_dots3(const double *__restrict__ r, const double *__restrict__ u,
-                                                  const double *__restrict__ w, int64_t n, double *__restrict__ partial) {
-  __shared__ double lds4[4];
-  double a = 0.0, b = 0.0, c = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const double ui = u[i];
-    a += r[i] * ui;
-    b += w[i] * ui;
-    c += ui * ui;
-  }
-  a = tg_block_sum256(a, lds4);
-  b = tg_block_sum256(b, lds4);
-  c = tg_block_sum256(c, lds4);
-  if (threadIdx.x == 0) {
-    partial[3 * blockIdx.x] = a;
-    partial[3 * blockIdx.x + 1] = b;
-    partial[3 * blockIdx.x + 2] = c;
-  }
-}
-// folds the nb partials of 3 interleaved streams in a fixed order
-__global__ void __launch_bounds__(256) k_fd_fold3(const double *partial, int nb, double *out) {
-  __shared__ double lds4[4];
-  for (int s = 0; s < 3; s++) {
-    double v = 0.0;
-    for (int i = threadIdx.x; i < nb; i += 256) v += partial[3 * i + s];
-    v = tg_block_sum256(v, lds4);
-    if (threadIdx.x == 0) out[s] = v;
-  }
-}
-// p = u + beta p ; s = w + beta s ; x += alpha p ; r -= alpha s
-__global__ void __launch_bounds__(256) k_fd_update(const double *__restrict__ u, const double *__restrict__ w, double alpha,
-                                                   double beta, int64_t n, double *__restrict__ p, double *__restrict__ s,
-                                                   double *__restrict__ x, double *__restrict__ r) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const double pi = u[i] + beta * p[i];
-    const double si = w[i] + beta * s[i];
-    p[i] = pi;
-    s[i] = si;
-    x[i] += alpha * pi;
-    r[i] -= alpha * si;
-  }
-}
-__global__ void __launch_bounds__(256) k_fd_residual(const double *__restrict__ b, const double *__restrict__ kx, int64_t n,
-                                                     double *__restrict__ r) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) r[i] = kx ? b[i] - kx[i] : b[i];
-}
-
-#define FD_VEC_BLOCKS 1024
-
-static int tg_pcg_fd(tg_csr_s *k, tg_fd_s *fd, tg_vec_s *b, tg_vec_s *x, double rtol, double atol, int maxit, int flags,
-                     int *iters, double *resnorm, int *status) {
-  const int64_t n = k->nrows;
-  const int vg = (int)std::max<int64_t>(1, std::min<int64_t>(tg_cdiv(n, 256), FD_VEC_BLOCKS));
-  struct ws_guard {
-    double *buf = nullptr;
-    ~ws_guard() {
-      if (buf) {
-        hipStreamSynchronize(g_tg.stream);
-        tg_dfree(buf);
-      }
-    }
-  } ws;
-  // layout: r | u | w | p | s
-  TG_TRY(tg_dmalloc(&ws.buf, 5 * n));
-  double *r = ws.buf, *u = r + n, *w = u + n, *p = w + n, *s = p + n;
-  TG_CHECK_HIP(hipMemsetAsync(ws.buf, 0, (size_t)(5 * n) * sizeof(double), g_tg.stream));
-  double *part = g_tg.scratch;                       // 3 * FD_VEC_BLOCKS
-  double *sc = g_tg.scratch + TG_SCRATCH_DOUBLES - 2048;
-  TG_TRY(tg_spmv_plan(k));
-  // the products as the other CG solves take them: the half-storage copy when K is a box stencil on a 3-D grid, else the
-  // sliced copy, else CSR (TIGAR_SPMV_SYM / TIGAR_SPMV_SYM_VERIFY as there)
-  struct sym_guard {
-    tg_symgrid_s *s = nullptr;
-    ~sym_guard() { tg_symgrid_free(s); }
-  } sym;
-  {
-    const int sym_on = getenv("TIGAR_SPMV_SYM") ? atoi(getenv("TIGAR_SPMV_SYM")) : 1;
-    const int sym_verify = getenv("TIGAR_SPMV_SYM_VERIFY") ? atoi(getenv("TIGAR_SPMV_SYM_VERIFY"))
-                                                           : !(flags & TG_KSP_SYMMETRIC);
-    if (sym_on && (n >= 65536 || sym_on > 1) && k->sell_state != 1) TG_TRY(tg_symgrid_build(k, 0, sym_verify, &sym.s));
-    if (sym.s) g_tg.prof_n[TG_PROF_KSP_SYMGRID] += 1;
-  }
-  struct sell_guard {
-    tg_csr_s *k;
-    bool temp = false;
-    int rc = 0;
-    sell_guard(tg_csr_s *m, bool skip) : k(m) {
-      if (k->sell_state == 0 && !skip) {
-        rc = tg_sell_plan(k);
-        temp = true;
-      }
-    }
-    ~sell_guard() {
-      if (temp) {
-        tg_sell_drop(k);
-        k->sell_state = 0;
-      }
-    }
-  } sell(k, sym.s != nullptr);
-  TG_TRY(sell.rc);
-  auto product = [&](const double *in, double *out) -> int {
-    if (sym.s) return tg_symgrid_spmv(sym.s, k, in, 0, n - 1, out, 0, nullptr, 0.0);
-    return tg_spmv_raw(k, in, 0, n - 1, out);
-  };
-  auto reduce3 = [&](double *host) -> int {
-    hipLaunchKernelGGL(k_fd_fold3, dim3(1), dim3(256), 0, g_tg.stream, part, vg, sc);
-    TG_LAUNCH_CHECK();
-    TG_CHECK_HIP(hipMemcpyAsync(g_tg.host_pinned, sc, 3 * sizeof(double), hipMemcpyDeviceToHost, g_tg.stream));
-    TG_CHECK_HIP(hipStreamSynchronize(g_tg.stream));
-    for (int i = 0; i < 3; i++) host[i] = g_tg.host_pinned[i];
-    return 0;
-  };
-  // reference norm ||B b|| and the initial residual
-  double h3[3];
-  hipLaunchKernelGGL(k_fd_residual, dim3(vg), dim3(256), 0, g_tg.stream, b->d, (const double *)nullptr, n, r);
-  TG_TRY(tg_fd_apply_dev(fd, r, u));
-  hipLaunchKernelGGL(k_fd_dots3, dim3(vg), dim3(256), 0, g_tg.stream, r, u, u, n, part);
-  TG_TRY(reduce3(h3));
-  const double bnorm = sqrt(h3[2]);
-  if (!(bnorm == bnorm)) {
-    *iters = 0;
-    *resnorm = bnorm;
-    *status = -2;
-    return 0;
-  }
-  if (flags & TG_KSP_NONZERO_GUESS) {
-    TG_TRY(product(x->d, w));
-    hipLaunchKernelGGL(k_fd_residual, dim3(vg), dim3(256), 0, g_tg.stream, b->d, (const double *)w, n, r);
-    TG_TRY(tg_fd_apply_dev(fd, r, u));
-  } else {
-    TG_CHECK_HIP(hipMemsetAsync(x->d, 0, (size_t)std::max<int64_t>(n, 1) * sizeof(double), g_tg.stream));
-  }
-  const double tol = std::max(rtol * bnorm, atol);
-  *iters = 0;
-  *status = -1;
-  double gamma_prev = 1.0, alpha_prev = 1.0, znorm = bnorm;
-  for (int it = 0; it <= maxit; it++) {
-    // w = K u ; gamma = (r,u), delta = (w,u), nu = (u,u)
-    TG_TRY(product(u, w));
-    hipLaunchKernelGGL(k_fd_dots3, dim3(vg), dim3(256), 0, g_tg.stream, r, u, w, n, part);
-    TG_TRY(reduce3(h3));
-    const double gamma = h3[0], delta = h3[1], nu = h3[2];
-    znorm = sqrt(nu);
-    *iters = it;
-    if (!(nu == nu) || !(gamma == gamma)) {
-      *status = -2;
-      break;
-    }
-    if (znorm <= tol) {
-      *status = (znorm <= atol && !(znorm <= rtol * bnorm)) ? 1 : 0;
-      break;
-    }
-    if (it == maxit) break;
-    double beta = 0.0, alpha;
-    if (it == 0)
-      alpha = gamma / delta;
-    else {
-      beta = gamma / gamma_prev;
-      alpha = gamma / (delta - beta * gamma / alpha_prev);
-    }
-    if (!(alpha == alpha) || alpha == 0.0 || !(gamma > 0.0)) {
-      *status = -2;
-      break;
-    }
-    gamma_prev = gamma;
-    alpha_prev = alpha;
-    hipLaunchKernelGGL(k_fd_update, dim3(vg), dim3(256), 0, g_tg.stream, u, w, alpha, beta, n, p, s, x->d, r);
-    TG_TRY(tg_fd_apply_dev(fd, r, u));
-  }
-  *resnorm = znorm;
-  TG_CHECK_HIP(hipStreamSynchronize(g_tg.stream));
-  return 0;
-}
-
 extern "C" int tg_krylov_solve_fd(tg_csr_t k, tg_fd_t fd, tg_vec_t b, tg_vec_t x, double rtol, double atol, int maxit,
                                   int flags, int *iters, double *resnorm, int *status) {
   TG_REQUIRE_INIT();
@@ -671,5 +492,8 @@ extern "C" int tg_krylov_solve_fd(tg_csr_t k, tg_fd_t fd, tg_vec_t b, tg_vec_t x
   TG_REQUIRE(k->nrows == k->ncols && k->nrows == fd->n, "tg_krylov_solve_fd: K is not %lld x %lld", (long long)fd->n,
              (long long)fd->n);
   TG_REQUIRE(b->n == k->nrows && x->n == k->nrows, "tg_krylov_solve_fd: vector length != rows of K");
-  return tg_pcg_fd(k, fd, b, x, rtol, atol, maxit, flags, iters, resnorm, status);
+  tg_ksp_op op;
+  TG_TRY(op.init(k, nullptr, true, (flags & TG_KSP_SYMMETRIC) != 0));
+  return tg_pcg_host(op, [fd](const double *r, double *u) { return tg_fd_apply_dev(fd, r, u); }, b, x, rtol, atol, maxit,
+                     (flags & TG_KSP_NONZERO_GUESS) ? 1 : 0, iters, resnorm, status);
 }

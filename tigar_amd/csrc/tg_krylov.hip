@@ -16,34 +16,48 @@
 #include <algorithm>
 #include <chrono>
 
-// The products of one solve go through the sliced, pattern-compressed copy of tg_sell.hip when the
-// matrix has the structure (built here, dropped when the solve returns: the copy is a snapshot of
-// the values).  A copy requested by the caller (tg_spmv_sell) is used and left alone.
-struct tg_sell_guard {
-  tg_csr_s *k;
-  bool temp = false;
-  int rc = 0;
-  explicit tg_sell_guard(tg_csr_s *m, bool skip = false) : k(m) {
-    if (k->sell_state == 0 && !skip) {
-      rc = tg_sell_plan(k);
-      temp = true;
-    }
+// ------------------------------------------------------------------------------ the operator of a solve (tg_common.h)
+int tg_ksp_op::init(tg_csr_s *k_, tg_comm_s *comm_, bool half_storage, bool symmetric) {
+  k = k_;
+  comm = comm_;
+  n = k->nrows;
+  hlo = comm ? comm->halo_lo : 0;
+  hhi = comm ? comm->halo_hi : 0;
+  row0 = comm ? comm->g0 : 0;
+  next = hlo + n + hhi;
+  cmin = row0 - hlo;
+  cmax = cmin + next - 1;
+  TG_TRY(tg_spmv_plan(k));
+  if (half_storage) {
+    // (TIGAR_SPMV_SYM: 0 = off, 1 = systems of at least 65536 rows [default], 2 = every size the plan accepts)
+    const int sym_on = getenv("TIGAR_SPMV_SYM") ? atoi(getenv("TIGAR_SPMV_SYM")) : 1;
+    const int sym_verify = getenv("TIGAR_SPMV_SYM_VERIFY") ? atoi(getenv("TIGAR_SPMV_SYM_VERIFY")) : !symmetric;
+    // (several ranks: every rank decides for its own z slab -- the products are local once the halo of u has arrived)
+    if (sym_on && (n >= 65536 || sym_on > 1) && k->sell_state != 1) TG_TRY(tg_symgrid_build(k, row0, sym_verify, &sym));
+    if (sym) g_tg.prof_n[TG_PROF_KSP_SYMGRID] += 1;
   }
-  ~tg_sell_guard() {
-    if (temp) {
-      tg_sell_drop(k);
-      k->sell_state = 0;
-    }
+  if (k->sell_state == 0 && !sym) {      // (the half-storage copy makes the sliced one unnecessary)
+    sell_temp = true;
+    TG_TRY(tg_sell_plan(k));
   }
-};
+  sliced = k->sell_state == 1 && k->sell && n > 0;
+  return 0;
+}
 
-static int g_ksp_symmetric_hint = 0;      // TG_KSP_SYMMETRIC of the solve under way (tg_krylov_solve_flags)
-// CG only (a symmetric K is its premise): the half-storage copy of tg_symgrid.hip when K is a box stencil on a 3-D grid
-// and this rank holds all of it; built for the solve like the sliced copy, which is then not needed.
-struct tg_symgrid_guard {
-  tg_symgrid_s *s = nullptr;
-  ~tg_symgrid_guard() { tg_symgrid_free(s); }
-};
+tg_ksp_op::~tg_ksp_op() {
+  if (sell_temp) {
+    tg_sell_drop(k);
+    k->sell_state = 0;
+  }
+  tg_symgrid_free(sym);
+}
+
+int tg_ksp_op::product(double *xext, double *out, const double *gate, double gate_tol) {
+  TG_TRY(tg_comm_halo_exchange(comm, xext));
+  if (sym) return tg_symgrid_spmv(sym, k, shift(xext), cmin, cmax, out, 0, gate, gate_tol);
+  if (sliced && gate) return tg_sell_spmv_rows(k, shift(xext), cmin, cmax, out, 0, n, gate, gate_tol);
+  return tg_spmv_raw(k, shift(xext), cmin, cmax, out);
+}
 
 static double tk_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -254,6 +268,30 @@ static int tg_read_scalars(const double *dev, int n, double *host) {
   return 0;
 }
 
+// folds the partials of `cnt` interleaved streams (`nb` blocks) into dev[0..cnt), sums them over the ranks, reads them back
+static int tg_ksp_reduce(tg_comm_s *comm, const double *part, int nb, int cnt, double *dev, double *host) {
+  hipLaunchKernelGGL(k_fold, dim3(1), dim3(256), 0, g_tg.stream, part, nb, cnt, dev);
+  TG_LAUNCH_CHECK();
+  TG_TRY(tg_comm_allreduce_dev(comm, dev, cnt));
+  return tg_read_scalars(dev, cnt, host);
+}
+
+// dinv of the Jacobi preconditioner (all 1 without it), from the recorded diagonal (tg_csr_s::diag_cache) when `cached`
+// allows it and the record is valid, else from the rows of K
+static void tg_jacobi_dinv(const tg_ksp_op &op, bool jacobi, bool cached, double *dinv) {
+  const int64_t n = op.n;
+  tg_csr_s *k = op.k;
+  if (n <= 0) return;
+  if (cached && k->diag_cache && k->diag_rows == n) {
+    hipLaunchKernelGGL(k_jacobi_from_diag, dim3(tg_vec_grid(n)), dim3(256), 0, g_tg.stream, k->diag_cache, n, jacobi ? 1 : 0,
+                       dinv);
+  } else {
+    const unsigned jg = (unsigned)std::min<int64_t>(tg_cdiv(n, 4), (int64_t)g_tg.num_cu * 16);
+    hipLaunchKernelGGL(k_jacobi_setup, dim3(jg), dim3(256), 0, g_tg.stream, k->rowptr, k->col, k->val, n, op.row0,
+                       jacobi ? 1 : 0, dinv);
+  }
+}
+
 #define TG_CG_RING 8
 struct tg_cg_ring {     // per-iteration events: norm history copies and SpMV timing
   hipEvent_t done[TG_CG_RING], t0[TG_CG_RING], t1[TG_CG_RING];
@@ -296,61 +334,36 @@ __global__ void __launch_bounds__(256)
 }
 
 static int tg_cg(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int pc, double rtol, double atol, int maxit, int nonzero_guess,
-                 tg_comm_s *comm, int *iters, double *resnorm, int *status) {
-  const int64_t n = k->nrows;
-  const int64_t hlo = comm ? comm->halo_lo : 0, hhi = comm ? comm->halo_hi : 0;
-  const int64_t row0 = comm ? comm->g0 : 0;
-  const int64_t next = hlo + n + hhi;
+                 bool symmetric, tg_comm_s *comm, int *iters, double *resnorm, int *status) {
+  tg_ksp_op op;
+  TG_TRY(op.init(k, comm, true, symmetric));
+  const int64_t n = op.n, next = op.next, row0 = op.row0, cmin = op.cmin, cmax = op.cmax;
   tg_krylov_ws ws;
   // layout: uext[next] | r[n] | w[n] | p[n] | s[n] | dinv[n]
   TG_TRY(tg_dmalloc(&ws.buf, next + 5 * n));
-  double *uext = ws.buf, *u = uext + hlo, *r = uext + next, *w = r + n, *p = w + n, *s = p + n, *dinv = s + n;
+  double *uext = ws.buf, *u = uext + op.hlo, *r = uext + next, *w = r + n, *p = w + n, *s = p + n, *dinv = s + n;
   TG_CHECK_HIP(hipMemsetAsync(uext, 0, (size_t)next * sizeof(double), g_tg.stream));
   double *part_gn = g_tg.scratch;                          // 2 * TG_VEC_BLOCKS
   double *part_d = g_tg.scratch + 2 * TG_VEC_BLOCKS;       // TG_VEC_BLOCKS
   tg_cg_scal *sc = (tg_cg_scal *)(g_tg.scratch + TG_SCRATCH_DOUBLES - 2048);   // two parities
   const int vg = tg_vec_grid(n);
-  TG_TRY(tg_spmv_plan(k));
-  tg_symgrid_guard sym;
-  {
-    // (TIGAR_SPMV_SYM: 0 = off, 1 = systems of at least 65536 rows [default], 2 = every size the plan accepts)
-    const int sym_on = getenv("TIGAR_SPMV_SYM") ? atoi(getenv("TIGAR_SPMV_SYM")) : 1;
-    const int sym_verify = getenv("TIGAR_SPMV_SYM_VERIFY") ? atoi(getenv("TIGAR_SPMV_SYM_VERIFY")) : !g_ksp_symmetric_hint;
-    // (several ranks: every rank decides for its own z slab -- the products are local once the halo of u has arrived)
-    if (sym_on && (n >= 65536 || sym_on > 1) && k->sell_state != 1)
-      TG_TRY(tg_symgrid_build(k, row0, sym_verify, &sym.s));
-    if (sym.s) g_tg.prof_n[TG_PROF_KSP_SYMGRID] += 1;
-  }
-  tg_sell_guard sell_guard(k, sym.s != nullptr);   // sliced copy of the values for the products of this solve
-  TG_TRY(sell_guard.rc);
   tg_cg_ring ring;
   TG_TRY(ring.init());
   double *hist = g_tg.host_pinned + 8;                     // TG_CG_RING x 3 doubles (pinned)
   double *hist_dev = nullptr;                              // the same ring as a kernel addresses it (one rank only)
   if (!(comm && comm->world > 1) && !getenv("TIGAR_CG_HIST_COPY"))
     TG_CHECK_HIP(hipHostGetDevicePointer((void **)&hist_dev, hist, 0));
-  const double *ushift = uext - (row0 - hlo);              // u addressed by global column index
-  const int64_t cmin = row0 - hlo, cmax = row0 - hlo + next - 1;
+  const double *ushift = op.shift(uext);                   // u addressed by global column index
 
-  if (n > 0 && k->diag_cache && k->diag_rows == n) {
-    hipLaunchKernelGGL(k_jacobi_from_diag, dim3(tg_vec_grid(n)), dim3(256), 0, g_tg.stream, k->diag_cache, n,
-                       pc == TG_PC_JACOBI ? 1 : 0, dinv);
-  } else if (n > 0) {
-    const unsigned jg = (unsigned)std::min<int64_t>(tg_cdiv(n, 4), (int64_t)g_tg.num_cu * 16);
-    hipLaunchKernelGGL(k_jacobi_setup, dim3(jg), dim3(256), 0, g_tg.stream, k->rowptr, k->col, k->val, n, row0,
-                       pc == TG_PC_JACOBI ? 1 : 0, dinv);
-  }
+  tg_jacobi_dinv(op, pc == TG_PC_JACOBI, true, dinv);
   // reference norm: ||B b|| -- also with a non-zero initial guess (KSPConvergedDefault without
   // -ksp_converged_use_initial_residual_norm [ext])
   double bnorm2 = 0.0;
   if (nonzero_guess) {
     hipLaunchKernelGGL(k_cg1_init, dim3(vg), dim3(256), 0, g_tg.stream, b->d, (const double *)nullptr, dinv, r, u, p, s,
                        n, part_gn);
-    hipLaunchKernelGGL(k_fold, dim3(1), dim3(256), 0, g_tg.stream, part_gn, vg, 2, (double *)&sc[0]);
-    TG_LAUNCH_CHECK();
-    TG_TRY(tg_comm_allreduce_dev(comm, (double *)&sc[0], 2));
     double h2[2];
-    TG_TRY(tg_read_scalars((double *)&sc[0], 2, h2));
+    TG_TRY(tg_ksp_reduce(comm, part_gn, vg, 2, (double *)&sc[0], h2));
     bnorm2 = h2[1];
     // r = b - K x0: x0 with its halo goes through uext, the product lands in w
     TG_CHECK_HIP(hipMemcpyAsync(u, x->d, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, g_tg.stream));
@@ -370,7 +383,7 @@ static int tg_cg(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int pc, double rtol, dou
   // sliced copy, whose launches can be restricted to row ranges; TIGAR_CG_OVERLAP=0 keeps the exchange in front.)
   int64_t in0 = 0, in1 = 0;
   static int overlap_on = getenv("TIGAR_CG_OVERLAP") ? atoi(getenv("TIGAR_CG_OVERLAP")) : 1;
-  if (comm && comm->world > 1 && overlap_on && k->sell_state == 1 && k->sell && n > 0 && n < 0x7fffffffll) {
+  if (comm && comm->world > 1 && overlap_on && op.sliced && n < 0x7fffffffll) {
     int *d_ends = (int *)(g_tg.scratch + TG_SCRATCH_DOUBLES - 2048 + 64);
     const int ends0[2] = {0, (int)n};
     int ends[2];
@@ -389,7 +402,6 @@ static int tg_cg(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int pc, double rtol, dou
   }
   // `gate`: the norm (device) the update in front of this product tested; with that update frozen (converged while the
   // host was still enqueueing) u is unchanged and so is w = K u: the launch returns at once
-  const bool sliced = k->sell_state == 1 && k->sell && n > 0;
   auto product = [&](const double *gate) -> int {
     if (in1 > in0) {
       TG_TRY(tg_comm_halo_begin(comm, uext));
@@ -401,19 +413,16 @@ static int tg_cg(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int pc, double rtol, dou
       g_tg.prof_n[TG_PROF_KSP_OVERLAPPED] += 1;
       return 0;
     }
-    if (sym.s && comm && comm->world > 1 && overlap_on && tg_symgrid_chunks(sym.s) > 1) {
+    if (op.sym && comm && comm->world > 1 && overlap_on && tg_symgrid_chunks(op.sym) > 1) {
       // all z chunks but the last read no halo plane of u: they run while it travels
       TG_TRY(tg_comm_halo_begin(comm, uext));
-      int rc = tg_symgrid_spmv(sym.s, k, ushift, cmin, cmax, w, 1, gate, tol2_dev);
+      int rc = tg_symgrid_spmv(op.sym, k, ushift, cmin, cmax, w, 1, gate, tol2_dev);
       TG_TRY(tg_comm_halo_end(comm, uext));
       TG_TRY(rc);
       g_tg.prof_n[TG_PROF_KSP_OVERLAPPED] += 1;
-      return tg_symgrid_spmv(sym.s, k, ushift, cmin, cmax, w, 2, gate, tol2_dev);
+      return tg_symgrid_spmv(op.sym, k, ushift, cmin, cmax, w, 2, gate, tol2_dev);
     }
-    TG_TRY(tg_comm_halo_exchange(comm, uext));
-    if (sym.s) return tg_symgrid_spmv(sym.s, k, ushift, cmin, cmax, w, 0, gate, tol2_dev);
-    if (sliced && gate) return tg_sell_spmv_rows(k, ushift, cmin, cmax, w, 0, n, gate, tol2_dev);
-    return tg_spmv_raw(k, ushift, cmin, cmax, w);
+    return op.product(uext, w, gate, tol2_dev);
   };
   // w = K u, delta; scalars of parity 0
   auto product_and_reduce = [&](tg_cg_scal *cur, int slot, const double *gate) -> int {
@@ -799,17 +808,16 @@ __global__ void __launch_bounds__(256) k_gm_residual(const tg_gm_state *st, cons
 
 static int tg_gmres(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int pc, double rtol, double atol, int maxit, int restart,
                     int nonzero_guess, int stagnation_guard, tg_comm_s *comm, int *iters, double *resnorm, int *status) {
-  const int64_t n = k->nrows;
-  const int64_t hlo = comm ? comm->halo_lo : 0, hhi = comm ? comm->halo_hi : 0;
-  const int64_t row0 = comm ? comm->g0 : 0;
-  const int64_t next = hlo + n + hhi;
+  tg_ksp_op op;
+  TG_TRY(op.init(k, comm, false, false));
+  const int64_t n = op.n, next = op.next;
   const int m = restart;
   tg_krylov_ws ws;
   // layout: ext[next] (SpMV input with halo) | w[n] | dinv[n] | V[(m+1) n] | small: H[(m+1) m] cs[m] sn[m] g[m+1] y[m]
   //         hcol[m+2] scal[4] state
   const int64_t nsmall = (int64_t)(m + 1) * m + 3 * (int64_t)m + (m + 1) + (m + 2) + 4 + 16;
   TG_TRY(tg_dmalloc(&ws.buf, next + 2 * n + (int64_t)(m + 1) * n + nsmall));
-  double *ext = ws.buf, *xin = ext + hlo, *w = ext + next, *dinv = w + n, *V = dinv + n;
+  double *ext = ws.buf, *xin = ext + op.hlo, *w = ext + next, *dinv = w + n, *V = dinv + n;
   double *H = V + (int64_t)(m + 1) * n, *cs = H + (int64_t)(m + 1) * m, *sn = cs + m, *g = sn + m, *y = g + (m + 1),
          *hdev = y + m, *scal = hdev + (m + 2);
   tg_gm_state *st = (tg_gm_state *)(scal + 4);
@@ -817,42 +825,24 @@ static int tg_gmres(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int pc, double rtol, 
   TG_CHECK_HIP(hipMemsetAsync(H, 0, (size_t)nsmall * sizeof(double), g_tg.stream));
   double *partial = g_tg.scratch;
   const int vg = std::min(tg_vec_grid(n), 256);
-  TG_TRY(tg_spmv_plan(k));
-  tg_sell_guard sell_guard(k);   // sliced copy of the values for the products of this solve
-  TG_TRY(sell_guard.rc);
-  const bool sliced = k->sell_state == 1 && k->sell && n > 0;
   tg_cg_ring ring;
   TG_TRY(ring.init());
   double *hist = g_tg.host_pinned + 8;                     // TG_CG_RING x 4 doubles (pinned)
   double *hist_dev = nullptr;                              // the same ring as the kernels address it
   TG_CHECK_HIP(hipHostGetDevicePointer((void **)&hist_dev, hist, 0));
-  const double *xshift = ext - (row0 - hlo);
-  const int64_t cmin = row0 - hlo, cmax = row0 - hlo + next - 1;
-  if (n > 0 && k->diag_cache && k->diag_rows == n) {
-    hipLaunchKernelGGL(k_jacobi_from_diag, dim3(tg_vec_grid(n)), dim3(256), 0, g_tg.stream, k->diag_cache, n,
-                       pc == TG_PC_JACOBI ? 1 : 0, dinv);
-  } else if (n > 0) {
-    const unsigned jg = (unsigned)std::min<int64_t>(tg_cdiv(n, 4), (int64_t)g_tg.num_cu * 16);
-    hipLaunchKernelGGL(k_jacobi_setup, dim3(jg), dim3(256), 0, g_tg.stream, k->rowptr, k->col, k->val, n, row0,
-                       pc == TG_PC_JACOBI ? 1 : 0, dinv);
-  }
-  // w = K * (the vector in xin, halo exchanged); products past the end of the solve return at once (sliced copy)
+  tg_jacobi_dinv(op, pc == TG_PC_JACOBI, true, dinv);
+  // w = K src; `gated`: products past the end of the solve return at once (sliced copy)
   // (slot >= 0: timed with the event pair of that ring slot -- the product of an inner iteration, accounted when the
   //  host reads that iteration's history entry)
-  // w = K src.  One rank: the product reads src where it lies; several: src goes into the extended vector first and
-  // its halo is exchanged.
-  auto product = [&](const double *src, bool gated, int slot) -> int {
-    const double *xs = src;
+  // One rank: the product reads src where it lies; several: src goes into the extended vector first and its halo is
+  // exchanged.
+  auto product = [&](double *src, bool gated, int slot) -> int {
     if (comm) {
       TG_CHECK_HIP(hipMemcpyAsync(xin, src, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, g_tg.stream));
-      xs = xshift;
+      src = ext;
     }
     if (slot >= 0) hipEventRecord(ring.t0[slot], g_tg.stream);
-    TG_TRY(tg_comm_halo_exchange(comm, ext));
-    if (sliced && gated)
-      TG_TRY(tg_sell_spmv_rows(k, xs, cmin, cmax, w, 0, n, &st->live, 0.5));
-    else
-      TG_TRY(tg_spmv_raw(k, xs, cmin, cmax, w));
+    TG_TRY(op.product(src, w, gated ? &st->live : nullptr, 0.5));
     if (slot >= 0) hipEventRecord(ring.t1[slot], g_tg.stream);
     return 0;
   };
@@ -1177,34 +1167,20 @@ __global__ void __launch_bounds__(256) k_residual(const double *__restrict__ b, 
   for (; i < n; i += stride) r[i] = kx ? b[i] - kx[i] : b[i];
 }
 
-static int tg_pcg_cheb(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int degree, double rtol, double atol, int maxit, int nonzero_guess,
-                       tg_comm_s *comm, int *iters, double *resnorm, int *status) {
-  const int64_t n = k->nrows;
-  const int64_t hlo = comm ? comm->halo_lo : 0, hhi = comm ? comm->halo_hi : 0;
-  const int64_t row0 = comm ? comm->g0 : 0;
-  const int64_t next = hlo + n + hhi;
-  const int m = std::max(1, std::min(degree, 64));
+// Host-driven PCG (tg_common.h): the recurrence of tg_cg with one reduction of gamma, delta, nu per iteration, the scalars
+// read back by the host.  The preconditioner is any fixed symmetric positive definite operator (`apply`): the Chebyshev
+// polynomial below, the fast diagonalization of tg_fd.hip.
+int tg_pcg_host(tg_ksp_op &op, const tg_pc_apply &apply, tg_vec_s *b, tg_vec_s *x, double rtol, double atol, int maxit,
+                int nonzero_guess, int *iters, double *resnorm, int *status) {
+  const int64_t n = op.n;
   tg_krylov_ws ws;
-  // layout: uext[next] | r | w | p | s | dinv | g | d | kz
-  TG_TRY(tg_dmalloc(&ws.buf, next + 8 * n));
-  double *uext = ws.buf, *u = uext + hlo, *r = uext + next, *w = r + n, *p = w + n, *s = p + n, *dinv = s + n, *g = dinv + n,
-         *dd = g + n, *kz = dd + n;
-  TG_CHECK_HIP(hipMemsetAsync(ws.buf, 0, (size_t)(next + 8 * n) * sizeof(double), g_tg.stream));
+  // layout: uext[next] | r | w | p | s
+  TG_TRY(tg_dmalloc(&ws.buf, op.next + 4 * n));
+  double *uext = ws.buf, *u = uext + op.hlo, *r = uext + op.next, *w = r + n, *p = w + n, *s = p + n;
+  TG_CHECK_HIP(hipMemsetAsync(ws.buf, 0, (size_t)(op.next + 4 * n) * sizeof(double), g_tg.stream));
   double *part = g_tg.scratch;                       // 3 * TG_VEC_BLOCKS
   double *sc = g_tg.scratch + TG_SCRATCH_DOUBLES - 2048;
   const int vg = tg_vec_grid(n);
-  TG_TRY(tg_spmv_plan(k));
-  tg_symgrid_guard sym;        // (CG with a polynomial preconditioner: the same premise, the same half-storage copy)
-  {
-    const int sym_on = getenv("TIGAR_SPMV_SYM") ? atoi(getenv("TIGAR_SPMV_SYM")) : 1;
-    const int sym_verify = getenv("TIGAR_SPMV_SYM_VERIFY") ? atoi(getenv("TIGAR_SPMV_SYM_VERIFY")) : !g_ksp_symmetric_hint;
-    if (sym_on && (n >= 65536 || sym_on > 1) && k->sell_state != 1) TG_TRY(tg_symgrid_build(k, row0, sym_verify, &sym.s));
-    if (sym.s) g_tg.prof_n[TG_PROF_KSP_SYMGRID] += 1;
-  }
-  tg_sell_guard sell_guard(k, sym.s != nullptr);
-  TG_TRY(sell_guard.rc);
-  const double *ushift = uext - (row0 - hlo);
-  const int64_t cmin = row0 - hlo, cmax = row0 - hlo + next - 1;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   TG_CHECK_HIP(hipEventCreate(&e0));
   TG_CHECK_HIP(hipEventCreate(&e1));
@@ -1215,21 +1191,94 @@ static int tg_pcg_cheb(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int degree, double
       hipEventDestroy(b);
     }
   } evg{e0, e1};
-  auto product = [&](double *out) -> int {            // out = K (vector in uext)
-    TG_TRY(tg_comm_halo_exchange(comm, uext));
-    if (sym.s) return tg_symgrid_spmv(sym.s, k, ushift, cmin, cmax, out, 0, nullptr, 0.0);
-    return tg_spmv_raw(k, ushift, cmin, cmax, out);
-  };
-  auto reduce = [&](int cnt, double *host) -> int {    // folds `cnt` interleaved partial streams, sums over ranks, reads
-    hipLaunchKernelGGL(k_fold, dim3(1), dim3(256), 0, g_tg.stream, part, vg, cnt, sc);
-    TG_LAUNCH_CHECK();
-    TG_TRY(tg_comm_allreduce_dev(comm, sc, cnt));
-    return tg_read_scalars(sc, cnt, host);
-  };
-  if (n > 0) {
-    const unsigned jg = (unsigned)std::min<int64_t>(tg_cdiv(n, 4), (int64_t)g_tg.num_cu * 16);
-    hipLaunchKernelGGL(k_jacobi_setup, dim3(jg), dim3(256), 0, g_tg.stream, k->rowptr, k->col, k->val, n, row0, 1, dinv);
+  // ---- reference norm ||B b|| and the initial residual
+  double h3[3];
+  hipLaunchKernelGGL(k_residual, dim3(vg), dim3(256), 0, g_tg.stream, b->d, (const double *)nullptr, n, r);
+  TG_TRY(apply(r, u));
+  hipLaunchKernelGGL(k_dots3, dim3(vg), dim3(256), 0, g_tg.stream, r, u, u, n, part);
+  TG_TRY(tg_ksp_reduce(op.comm, part, vg, 3, sc, h3));
+  const double bnorm = sqrt(h3[2]);
+  if (!(bnorm == bnorm)) {                           // (NaN in b or in B: x is left as it is)
+    *iters = 0;
+    *resnorm = bnorm;
+    *status = -2;
+    return 0;
   }
+  if (nonzero_guess) {
+    TG_CHECK_HIP(hipMemcpyAsync(u, x->d, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, g_tg.stream));
+    TG_TRY(op.product(uext, w, nullptr, 0.0));
+    hipLaunchKernelGGL(k_residual, dim3(vg), dim3(256), 0, g_tg.stream, b->d, (const double *)w, n, r);
+    TG_TRY(apply(r, u));
+  } else {
+    TG_CHECK_HIP(hipMemsetAsync(x->d, 0, (size_t)std::max<int64_t>(n, 1) * sizeof(double), g_tg.stream));
+  }
+  const double tol = std::max(rtol * bnorm, atol);
+  *iters = 0;
+  *status = -1;
+  double gamma_prev = 1.0, alpha_prev = 1.0, znorm = bnorm;
+  for (int it = 0; it <= maxit; it++) {
+    // w = K u ; gamma = (r,u), delta = (w,u), nu = (u,u)
+    hipEventRecord(e0, g_tg.stream);
+    TG_TRY(op.product(uext, w, nullptr, 0.0));
+    hipEventRecord(e1, g_tg.stream);
+    hipLaunchKernelGGL(k_dots3, dim3(vg), dim3(256), 0, g_tg.stream, r, u, w, n, part);
+    TG_TRY(tg_ksp_reduce(op.comm, part, vg, 3, sc, h3));
+    {
+      float ems = 0.f;
+      if (hipEventElapsedTime(&ems, e0, e1) == hipSuccess) {
+        g_tg.prof_ms[TG_PROF_KSP_SPMV] += ems;
+        g_tg.prof_n[TG_PROF_KSP_SPMV] += 1;
+      }
+    }
+    const double gamma = h3[0], delta = h3[1], nu = h3[2];
+    znorm = sqrt(nu);
+    *iters = it;
+    if (!(nu == nu) || !(gamma == gamma)) {
+      *status = -2;
+      break;
+    }
+    if (znorm <= tol) {
+      *status = (znorm <= atol && !(znorm <= rtol * bnorm)) ? 1 : 0;
+      break;
+    }
+    if (it == maxit) break;
+    double beta = 0.0, alpha;
+    if (it == 0)
+      alpha = gamma / delta;
+    else {
+      beta = gamma / gamma_prev;
+      alpha = gamma / (delta - beta * gamma / alpha_prev);
+    }
+    if (!(alpha == alpha) || alpha == 0.0 || !(gamma > 0.0)) {     // (a preconditioner that is not positive definite, breakdown)
+      *status = -2;
+      break;
+    }
+    gamma_prev = gamma;
+    alpha_prev = alpha;
+    hipLaunchKernelGGL(k_pcg_update, dim3(vg), dim3(256), 0, g_tg.stream, u, w, alpha, beta, n, p, s, x->d, r);
+    TG_TRY(apply(r, u));
+  }
+  *resnorm = znorm;
+  TG_CHECK_HIP(hipStreamSynchronize(g_tg.stream));
+  TG_TRY(tg_comm_check(op.comm));
+  return 0;
+}
+
+static int tg_pcg_cheb(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int degree, double rtol, double atol, int maxit, int nonzero_guess,
+                       bool symmetric, tg_comm_s *comm, int *iters, double *resnorm, int *status) {
+  const int m = std::max(1, std::min(degree, 64));
+  tg_ksp_op op;        // (CG with a polynomial preconditioner: the same premise, the same half-storage copy)
+  TG_TRY(op.init(k, comm, true, symmetric));
+  const int64_t n = op.n;
+  tg_krylov_ws ws;
+  // layout: lext[next] (operand of the Lanczos products) | dinv | g | d | kz
+  TG_TRY(tg_dmalloc(&ws.buf, op.next + 4 * n));
+  double *lext = ws.buf, *lop = lext + op.hlo, *dinv = lext + op.next, *g = dinv + n, *dd = g + n, *kz = dd + n;
+  TG_CHECK_HIP(hipMemsetAsync(ws.buf, 0, (size_t)(op.next + 4 * n) * sizeof(double), g_tg.stream));
+  double *part = g_tg.scratch;
+  double *sc = g_tg.scratch + TG_SCRATCH_DOUBLES - 2048;
+  const int vg = tg_vec_grid(n);
+  tg_jacobi_dinv(op, true, false, dinv);
   // ---- extreme eigenvalues of D^-1 K: 12 Lanczos steps on D^-1/2 K D^-1/2 from D^1/2-scaled b (both ends of the spectrum at
   // once; the power method needs 20 products for the upper end alone).  theta_max approaches lambda_max from below (safety
   // 1.1, capped by the Gershgorin bound: an interval that ends below lambda_max makes the polynomial indefinite), theta_min
@@ -1245,13 +1294,13 @@ static int tg_pcg_cheb(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int degree, double
       TG_TRY(tg_comm_allreduce_sum(comm, &gg, 1));
       gersh = gg;
     }
-    // v (Lanczos vector) in g, previous one in dd, operand D^-1/2 v in u, D^-1/2 K D^-1/2 v in kz
+    // v (Lanczos vector) in g, previous one in dd, operand D^-1/2 v in lop, D^-1/2 K D^-1/2 v in kz
     constexpr int LZ = 12;
     double al[LZ], be[LZ + 1];
     int kdim = 0;
-    hipLaunchKernelGGL(k_lz_start, dim3(vg), dim3(256), 0, g_tg.stream, b->d, dinv, n, (int64_t)row0, g, part);
+    hipLaunchKernelGGL(k_lz_start, dim3(vg), dim3(256), 0, g_tg.stream, b->d, dinv, n, op.row0, g, part);
     double nn = 0.0;
-    TG_TRY(reduce(1, &nn));
+    TG_TRY(tg_ksp_reduce(comm, part, vg, 1, sc, &nn));
     if (nn != nn) {                                   // NaN in b or on the diagonal of K: breakdown, not "b = 0"
       *iters = 0;
       *resnorm = nn;
@@ -1268,16 +1317,16 @@ static int tg_pcg_cheb(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int degree, double
     double inv_norm = 1.0 / sqrt(nn), beta = 0.0;
     be[0] = 0.0;
     for (int j = 0; j < LZ; j++) {
-      // g <- g * inv_norm ; u = sqrt(dinv) g
-      hipLaunchKernelGGL(k_lz_operand, dim3(vg), dim3(256), 0, g_tg.stream, dinv, inv_norm, n, g, u);
-      TG_TRY(product(kz));
+      // g <- g * inv_norm ; lop = sqrt(dinv) g
+      hipLaunchKernelGGL(k_lz_operand, dim3(vg), dim3(256), 0, g_tg.stream, dinv, inv_norm, n, g, lop);
+      TG_TRY(op.product(lext, kz, nullptr, 0.0));
       // kz <- sqrt(dinv) kz - beta dd ; alpha = (kz, g)
       hipLaunchKernelGGL(k_lz_alpha, dim3(vg), dim3(256), 0, g_tg.stream, dinv, dd, beta, g, n, kz, part);
       double alpha = 0.0;
-      TG_TRY(reduce(1, &alpha));
+      TG_TRY(tg_ksp_reduce(comm, part, vg, 1, sc, &alpha));
       // kz <- kz - alpha g ; dd <- g ; g <- kz ; beta' = ||kz||
       hipLaunchKernelGGL(k_lz_next, dim3(vg), dim3(256), 0, g_tg.stream, alpha, n, kz, g, dd, part);
-      TG_TRY(reduce(1, &nn));
+      TG_TRY(tg_ksp_reduce(comm, part, vg, 1, sc, &nn));
       al[j] = alpha;
       kdim = j + 1;
       if (!(nn > 1e-28 * alpha * alpha) || !(nn == nn)) break;      // invariant subspace
@@ -1326,90 +1375,26 @@ static int tg_pcg_cheb(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int degree, double
   const double lmin = lmax / ratio;
   const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin);
   if (!comm && tg_cg_persistent_applies(k)) {
-    // small systems: the loop below as one persistent kernel (tg_krylov_small.hip); 100 = not taken
+    // small systems: the loop of tg_pcg_host as one persistent kernel (tg_krylov_small.hip); 100 = not taken
     const int rcp = tg_pcg_cheb_persistent(k, b, x, m, theta, delta, rtol, atol, maxit, nonzero_guess, iters, resnorm, status);
     if (rcp != 100) return rcp;
   }
-  // u = B r
-  auto apply_pc = [&]() -> int {
+  // u = B r (the loop's u is the owned part of an operand of op: the polynomial multiplies by K there)
+  auto apply = [&](const double *r, double *u) -> int {
+    double *uext = u - op.hlo;
     hipLaunchKernelGGL(k_cheb_first, dim3(vg), dim3(256), 0, g_tg.stream, r, dinv, 1.0 / theta, n, g, u, dd);
     const double sigma = theta / delta;
     double rho = 1.0 / sigma;
     for (int j = 1; j < m; j++) {
       const double rho_new = 1.0 / (2.0 * sigma - rho);
-      TG_TRY(product(kz));
+      TG_TRY(op.product(uext, kz, nullptr, 0.0));
       hipLaunchKernelGGL(k_cheb_step, dim3(vg), dim3(256), 0, g_tg.stream, g, dinv, kz, rho_new * rho, 2.0 * rho_new / delta, n, u, dd);
       rho = rho_new;
     }
     TG_LAUNCH_CHECK();
     return 0;
   };
-  // ---- reference norm ||B b|| and the initial residual
-  double h3[3];
-  hipLaunchKernelGGL(k_residual, dim3(vg), dim3(256), 0, g_tg.stream, b->d, (const double *)nullptr, n, r);
-  TG_TRY(apply_pc());
-  hipLaunchKernelGGL(k_dots3, dim3(vg), dim3(256), 0, g_tg.stream, r, u, u, n, part);
-  TG_TRY(reduce(3, h3));
-  const double bnorm = sqrt(h3[2]);
-  if (nonzero_guess) {
-    TG_CHECK_HIP(hipMemcpyAsync(u, x->d, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, g_tg.stream));
-    TG_TRY(product(w));
-    hipLaunchKernelGGL(k_residual, dim3(vg), dim3(256), 0, g_tg.stream, b->d, (const double *)w, n, r);
-    TG_TRY(apply_pc());
-  } else {
-    TG_CHECK_HIP(hipMemsetAsync(x->d, 0, (size_t)std::max<int64_t>(n, 1) * sizeof(double), g_tg.stream));
-  }
-  const double tol = std::max(rtol * bnorm, atol);
-  *iters = 0;
-  *status = -1;
-  double gamma_prev = 1.0, alpha_prev = 1.0, znorm = bnorm;
-  TG_CHECK_HIP(hipMemsetAsync(p, 0, (size_t)(2 * n) * sizeof(double), g_tg.stream));   // p, s adjacent
-  for (int it = 0; it <= maxit; it++) {
-    // w = K u ; gamma = (r,u), delta = (w,u), nu = (u,u)
-    hipEventRecord(e0, g_tg.stream);
-    TG_TRY(product(w));
-    hipEventRecord(e1, g_tg.stream);
-    hipLaunchKernelGGL(k_dots3, dim3(vg), dim3(256), 0, g_tg.stream, r, u, w, n, part);
-    TG_TRY(reduce(3, h3));
-    {
-      float ems = 0.f;
-      if (hipEventElapsedTime(&ems, e0, e1) == hipSuccess) {
-        g_tg.prof_ms[TG_PROF_KSP_SPMV] += ems;
-        g_tg.prof_n[TG_PROF_KSP_SPMV] += 1;
-      }
-    }
-    const double gamma = h3[0], delta_ = h3[1], nu = h3[2];
-    znorm = sqrt(nu);
-    *iters = it;
-    if (!(nu == nu) || !(gamma == gamma)) {
-      *status = -2;
-      break;
-    }
-    if (znorm <= tol) {
-      *status = (znorm <= atol && !(znorm <= rtol * bnorm)) ? 1 : 0;
-      break;
-    }
-    if (it == maxit) break;
-    double beta = 0.0, alpha;
-    if (it == 0)
-      alpha = gamma / delta_;
-    else {
-      beta = gamma / gamma_prev;
-      alpha = gamma / (delta_ - beta * gamma / alpha_prev);
-    }
-    if (!(alpha == alpha) || alpha == 0.0 || !(gamma > 0.0)) {     // (a polynomial that is not positive definite, breakdown)
-      *status = -2;
-      break;
-    }
-    gamma_prev = gamma;
-    alpha_prev = alpha;
-    hipLaunchKernelGGL(k_pcg_update, dim3(vg), dim3(256), 0, g_tg.stream, u, w, alpha, beta, n, p, s, x->d, r);
-    TG_TRY(apply_pc());
-  }
-  *resnorm = znorm;
-  TG_CHECK_HIP(hipStreamSynchronize(g_tg.stream));
-  TG_TRY(tg_comm_check(comm));
-  return 0;
+  return tg_pcg_host(op, apply, b, x, rtol, atol, maxit, nonzero_guess, iters, resnorm, status);
 }
 
 // ------------------------------------------------------------------------------------ BiCGStab
@@ -1488,39 +1473,21 @@ __global__ void __launch_bounds__(256) k_bcgs_x(const double *__restrict__ p, co
 
 static int tg_bicgstab(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int pc, double rtol, double atol, int maxit, int nonzero_guess,
                        tg_comm_s *comm, int *iters, double *resnorm, int *status) {
-  const int64_t n = k->nrows;
-  const int64_t hlo = comm ? comm->halo_lo : 0, hhi = comm ? comm->halo_hi : 0;
-  const int64_t row0 = comm ? comm->g0 : 0;
-  const int64_t next = hlo + n + hhi;
+  tg_ksp_op kop;
+  TG_TRY(kop.init(k, comm, false, false));
+  const int64_t n = kop.n, next = kop.next;
   tg_krylov_ws ws;
   // layout: opext[next] (operand of the products: p, then s) | r | rhat | v | t | kp | dinv | pvec
   TG_TRY(tg_dmalloc(&ws.buf, next + 7 * n));
-  double *opext = ws.buf, *op = opext + hlo, *r = opext + next, *rhat = r + n, *v = rhat + n, *t = v + n, *kp = t + n,
+  double *opext = ws.buf, *op = opext + kop.hlo, *r = opext + next, *rhat = r + n, *v = rhat + n, *t = v + n, *kp = t + n,
          *dinv = kp + n, *pv = dinv + n;
   TG_CHECK_HIP(hipMemsetAsync(ws.buf, 0, (size_t)(next + 7 * n) * sizeof(double), g_tg.stream));
   double *part = g_tg.scratch;                       // 5 * TG_VEC_BLOCKS
   double *sc = g_tg.scratch + TG_SCRATCH_DOUBLES - 2048;
   const int vg = tg_vec_grid(n);
-  TG_TRY(tg_spmv_plan(k));
-  tg_sell_guard sell_guard(k);
-  TG_TRY(sell_guard.rc);
-  const double *opshift = opext - (row0 - hlo);
-  const int64_t cmin = row0 - hlo, cmax = row0 - hlo + next - 1;
-  auto product = [&](double *out) -> int {
-    TG_TRY(tg_comm_halo_exchange(comm, opext));
-    return tg_spmv_raw(k, opshift, cmin, cmax, out);
-  };
-  auto reduce = [&](int cnt, double *host) -> int {
-    hipLaunchKernelGGL(k_fold, dim3(1), dim3(256), 0, g_tg.stream, part, vg, cnt, sc);
-    TG_LAUNCH_CHECK();
-    TG_TRY(tg_comm_allreduce_dev(comm, sc, cnt));
-    return tg_read_scalars(sc, cnt, host);
-  };
-  if (n > 0) {
-    const unsigned jg = (unsigned)std::min<int64_t>(tg_cdiv(n, 4), (int64_t)g_tg.num_cu * 16);
-    hipLaunchKernelGGL(k_jacobi_setup, dim3(jg), dim3(256), 0, g_tg.stream, k->rowptr, k->col, k->val, n, row0,
-                       pc == TG_PC_JACOBI ? 1 : 0, dinv);
-  }
+  auto product = [&](double *out) { return kop.product(opext, out, nullptr, 0.0); };
+  auto reduce = [&](int cnt, double *host) { return tg_ksp_reduce(comm, part, vg, cnt, sc, host); };
+  tg_jacobi_dinv(kop, pc == TG_PC_JACOBI, false, dinv);
   // reference norm ||B b||; r = B (b - K x0)
   double h5[5];
   hipLaunchKernelGGL(k_scaled_copy_norm, dim3(vg), dim3(256), 0, g_tg.stream, b->d, (const double *)dinv, 1.0, n, r, part);
@@ -1606,7 +1573,7 @@ extern "C" int tg_krylov_solve_flags(tg_csr_t k, tg_vec_t b, tg_vec_t x, int met
                                      int maxit, int restart, int flags, tg_comm_t comm, int *iters, double *resnorm,
                                      int *status) {
   const int g_krylov_nonzero_guess = (flags & TG_KSP_NONZERO_GUESS) ? 1 : 0;
-  g_ksp_symmetric_hint = (flags & TG_KSP_SYMMETRIC) ? 1 : 0;
+  const bool symmetric = (flags & TG_KSP_SYMMETRIC) != 0;
   TG_REQUIRE_INIT();
   TG_REQUIRE(k && b && x && iters && resnorm && status, "null argument to tg_krylov_solve");
   TG_REQUIRE(b->n == k->nrows && x->n == k->nrows, "tg_krylov_solve: vector length != local rows");
@@ -1619,14 +1586,15 @@ extern "C" int tg_krylov_solve_flags(tg_csr_t k, tg_vec_t b, tg_vec_t x, int met
   }
   if (method == TG_KSP_CG && pc == TG_PC_CHEBYSHEV)
     // (`restart` carries the degree of the polynomial: the number of products per application + 1)
-    return tg_pcg_cheb(k, b, x, restart, rtol, atol, maxit, g_krylov_nonzero_guess, comm, iters, resnorm, status);
+    return tg_pcg_cheb(k, b, x, restart, rtol, atol, maxit, g_krylov_nonzero_guess, symmetric, comm, iters, resnorm, status);
   TG_REQUIRE(pc == TG_PC_NONE || pc == TG_PC_JACOBI, "the Chebyshev polynomial preconditioner serves CG only");
   if (method == TG_KSP_CG && !comm && tg_cg_persistent_applies(k)) {
     // small systems (K in the Infinity Cache): the whole loop in one persistent kernel; 100 = could not run, the loop below does
     const int rcp = tg_cg_persistent(k, b, x, pc, rtol, atol, maxit, g_krylov_nonzero_guess, iters, resnorm, status);
     if (rcp != 100) return rcp;
   }
-  if (method == TG_KSP_CG) return tg_cg(k, b, x, pc, rtol, atol, maxit, g_krylov_nonzero_guess, comm, iters, resnorm, status);
+  if (method == TG_KSP_CG)
+    return tg_cg(k, b, x, pc, rtol, atol, maxit, g_krylov_nonzero_guess, symmetric, comm, iters, resnorm, status);
   if (method == TG_KSP_BICGSTAB && !comm && tg_cg_persistent_applies(k)) {
     const int rcp = tg_bicgstab_persistent(k, b, x, pc, rtol, atol, maxit, g_krylov_nonzero_guess, iters, resnorm, status);
     if (rcp != 100) return rcp;
