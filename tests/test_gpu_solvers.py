@@ -74,6 +74,22 @@ def _nonsymmetric(n=40, seed=5):
     return A, rng.standard_normal(A.shape[0])
 
 
+def _three_fields(nel, seed):
+    """non-symmetric, random values shifted by a quarter of the row's absolute sum, three coupled fields on the 2-D p=3
+    element-coupling pattern: 147 entries per interior row (cfg5's rows) -- more than 128, so the persistent GMRES and
+    BiCGStab keep one layer of K in LDS --, and on 256 CUs 155 (nel = 112) or 184 (nel = 122) rows per workgroup; b = A x
+    for a known x (a direct solve takes a minute)"""
+    m = nel + 3
+    band = sp.diags([np.ones(m - abs(o)) for o in range(-3, 4)], list(range(-3, 4)))
+    A = sp.kron(np.ones((3, 3)), sp.kron(band, band)).tocsr()
+    rng = np.random.default_rng(seed)
+    A.data = rng.standard_normal(A.nnz)
+    A = (A + sp.diags(np.asarray(abs(A).sum(axis=1)).ravel() * 0.25)).tocsr()
+    A.sort_indices()
+    exact = rng.standard_normal(A.shape[0])
+    return A, A @ exact, exact
+
+
 @pytest.mark.parametrize("pc", ["jacobi", "none"])
 def test_bicgstab_on_a_nonsymmetric_system(pc):
     import tigar_amd as t
@@ -186,17 +202,21 @@ def test_persistent_cg_for_small_systems(d, p, nel, pc, monkeypatch):
     assert iz == 0 == iz0 and not Uz.any() and lz["status"] == lz0["status"]
 
 
-@pytest.mark.parametrize("pc,restart", [("jacobi", 30), ("jacobi", 5), ("none", 12)])
-def test_persistent_gmres_for_small_systems(pc, restart, monkeypatch):
+@pytest.mark.parametrize("pc,restart,nel", [("jacobi", 30, None), ("jacobi", 5, None), ("none", 12, None), ("jacobi", 30, 112)],
+                         ids=["jacobi-30", "jacobi-5", "none-12", "jacobi-30-lds-layer"])
+def test_persistent_gmres_for_small_systems(pc, restart, nel, monkeypatch):
     """GMRES(m) in one cooperative kernel (csrc/tg_krylov_small.hip: rows of K in registers, the workgroup's rows of the
     basis in LDS, three device-wide barriers per inner iteration) against the multi-kernel loop on a non-symmetric system:
     iteration count (restart cycles included), solution, reported norm, guess, iteration limit, b = 0, bit-reproducibility"""
     import tigar_amd as t
     from tigar_amd.device import DeviceCSR, DeviceVector
-    A, b = _nonsymmetric(n=36, seed=9)
-    # (more weight on the diagonal: the short restarts must converge, not stagnate)
-    A = (A + sp.diags(np.asarray(abs(A).sum(axis=1)).ravel() * 0.5)).tocsr()
-    exact = sla.spsolve(A.tocsc(), b)
+    if nel:
+        A, b, exact = _three_fields(nel, seed=9)
+    else:
+        A, b = _nonsymmetric(n=36, seed=9)
+        # (more weight on the diagonal: the short restarts must converge, not stagnate)
+        A = (A + sp.diags(np.asarray(abs(A).sum(axis=1)).ravel() * 0.5)).tocsr()
+        exact = sla.spsolve(A.tocsc(), b)
     Ad = DeviceCSR.from_scipy(A)
 
     def run(mode, guess=None, rtol=1e-10, maxit=None, vec=b):
@@ -242,14 +262,17 @@ def test_persistent_gmres_for_small_systems(pc, restart, monkeypatch):
     assert iz == 0 == iz0 and not xz.any() and lz["status"] == lz0["status"]
 
 
-@pytest.mark.parametrize("pc", ["jacobi", "none"])
-def test_persistent_bicgstab_for_small_systems(pc, monkeypatch):
+@pytest.mark.parametrize("pc,nel", [("jacobi", None), ("none", None), ("jacobi", 122)], ids=["jacobi", "none", "jacobi-lds-layer"])
+def test_persistent_bicgstab_for_small_systems(pc, nel, monkeypatch):
     """BiCGStab in one cooperative kernel (four device-wide barriers per iteration, both reductions folded by every
     workgroup instead of read back on the host) against the multi-kernel loop on a non-symmetric system"""
     import tigar_amd as t
     from tigar_amd.device import DeviceCSR, DeviceVector
-    A, b = _nonsymmetric(n=36, seed=11)
-    exact = sla.spsolve(A.tocsc(), b)
+    if nel:
+        A, b, exact = _three_fields(nel, seed=11)
+    else:
+        A, b = _nonsymmetric(n=36, seed=11)
+        exact = sla.spsolve(A.tocsc(), b)
     Ad = DeviceCSR.from_scipy(A)
 
     def run(mode, guess=None, rtol=1e-11, maxit=None, vec=b):

@@ -35,7 +35,7 @@ struct tg_ps_ctrl {
   unsigned top;                  // second level: groups that are complete
   unsigned pad1[31];
   unsigned grp[(PS_MAXG / PS_FAN) * 32];   // first level, one 128-byte line per group of PS_FAN workgroups
-  double out[8];                 // [0] iterations, [1] nu at the end, [2] nu0 (reference), [3] status, [4..7] phase ticks
+  double out[4];                 // [0] iterations, [1] nu (CG) or the norm at the end, [2] nu0 (CG's reference), [3] status
 };
 
 struct tg_ps_args {
@@ -142,49 +142,67 @@ struct ps_lds {
   double red[3 * 17];
 };
 
-template <int EPR, int RI>
-__device__ __forceinline__ void ps_product(const double (&v)[RI][EPR], const unsigned (&c)[RI][EPR], const double *__restrict__ xg,
-                                           double *__restrict__ w_lds, int nloc) {
+// The workgroup's rows: a contiguous block [c0, c0 + nloc) of ceil(n / G) rows
+__device__ __forceinline__ int64_t ps_rows(int64_t n, int &nloc) {
+  const unsigned G = gridDim.x;
+  const int64_t per = (n + G - 1) / G;
+  const int64_t c0r = (int64_t)blockIdx.x * per, c0 = c0r < n ? c0r : n, c1 = c0 + per < n ? c0 + per : n;
+  nloc = (int)(c1 - c0);
+  return c0;
+}
+
+// The rows of K into registers (v, c: the first EPR - EL entries per lane and row) and, for EL > 0, the last EL into the
+// LDS layer (lv / lc: [RI][EL][PS_NT]); the Jacobi diagonal into dinv (PCJACOBI [ext]: 1 where the diagonal is zero / absent,
+// and everywhere without Jacobi).
+template <int EPR, int RI, int EL>
+__device__ __forceinline__ void ps_load_rows(const tg_ps_args &A, int64_t c0, int nloc, double (&v)[RI][EPR - EL],
+                                             unsigned (&c)[RI][EPR - EL], double *lv, unsigned *lc, double *dinv) {
+  constexpr int ER = EPR - EL;
+  const int tid = threadIdx.x, g = tid >> 5, l = tid & 31;
+#pragma unroll
+  for (int ri = 0; ri < RI; ri++) {
+    const int lrow = g + PS_GROUPS * ri;
+    const int64_t row = c0 + lrow;
+    const bool live = lrow < nloc;
+    const int64_t a = live ? A.rowptr[row] : 0, e = live ? A.rowptr[row + 1] : 0;
+    double dd = 0.0;
+#pragma unroll
+    for (int k = 0; k < EPR; k++) {
+      const int64_t q = a + l + 32 * k;
+      const bool in = q < e;
+      const double vq = in ? A.val[q] : 0.0;
+      const int cq = in ? A.col[q] : (int)(live ? row : 0);
+      if (k < ER) {
+        v[ri][k < ER ? k : 0] = vq;
+        c[ri][k < ER ? k : 0] = 8u * (unsigned)cq;       // byte offsets of the columns
+      } else {
+        lv[(ri * EL + (k - ER)) * PS_NT + tid] = vq;
+        lc[(ri * EL + (k - ER)) * PS_NT + tid] = 8u * (unsigned)cq;
+      }
+      if (in && cq == row) dd = vq;
+    }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) dd += __shfl_xor(dd, o, 64);
+    if (l == 0 && live) dinv[lrow] = (A.jacobi && dd != 0.0) ? 1.0 / dd : 1.0;
+  }
+  __syncthreads();
+}
+
+// w = K xg on the own rows.  EL > 0 holds the last EL of the EPR entries per lane and row in LDS (lv / lc) instead of
+// registers: for rows of 129-160 entries (cfg5: 147) the 65 slots of a lane do not fit the register file next to the GMRES
+// body -- the kernel spilled ~100 registers per lane to scratch, re-read in every product.
+template <int EPR, int RI, int EL>
+__device__ __forceinline__ void ps_product(const double (&v)[RI][EPR - EL], const unsigned (&c)[RI][EPR - EL],
+                                           const double *__restrict__ lv, const unsigned *__restrict__ lc,
+                                           const double *__restrict__ xg, double *__restrict__ w_lds, int nloc) {
   // c: BYTE offsets into xg (uniform base + 32-bit lane offset: no 64-bit address per entry).  The gathers are issued in
   // batches of PS_BATCH rows -- all of them at once (what the scheduler does when left alone) needs two registers per entry
   // for the values in flight on top of the three that hold the entry, and the kernel spills.
+  constexpr int ER = EPR - EL;
   constexpr int PS_BATCH = EPR >= 5 ? 2 : EPR == 4 ? 3 : EPR == 3 ? 4 : EPR == 2 ? 6 : 12;
   const int g = threadIdx.x >> 5, l = threadIdx.x & 31;
   // (raw buffer loads: the descriptor in scalar registers, ONE 32-bit register per entry for the offset -- as pointers the
   //  compiler kept a 64-bit offset per entry: 4 registers per entry instead of 3)
-  const __amdgpu_buffer_rsrc_t xb = __builtin_amdgcn_make_buffer_rsrc((void *)xg, 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-  for (int r0 = 0; r0 < RI; r0 += PS_BATCH) {
-    double xs[PS_BATCH][EPR];
-#pragma unroll
-    for (int ri = r0; ri < r0 + PS_BATCH && ri < RI; ri++)
-#pragma unroll
-      for (int k = 0; k < EPR; k++)
-        xs[ri - r0][k] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(xb, (int)c[ri][k], 0, PS_AUX_SC1));
-#pragma unroll
-    for (int ri = r0; ri < r0 + PS_BATCH && ri < RI; ri++) {
-      double acc = 0.0;
-#pragma unroll
-      for (int k = 0; k < EPR; k++) acc = fma(v[ri][k], xs[ri - r0][k], acc);
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-      const int lrow = g + PS_GROUPS * ri;
-      if (l == 0 && lrow < nloc) w_lds[lrow] = acc;
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// The same with the last EL of the EPR entries per lane and row held in LDS (lv / lc: [RI][EL][PS_NT]) instead of registers:
-// for rows of 129-160 entries (cfg5: 147) the 65 slots of a lane do not fit the register file next to the GMRES body -- the
-// kernel spilled ~100 registers per lane to scratch, re-read in every product.
-template <int EPR, int RI, int EL>
-__device__ __forceinline__ void ps_product_l(const double (&v)[RI][EPR - EL], const unsigned (&c)[RI][EPR - EL],
-                                             const double *__restrict__ lv, const unsigned *__restrict__ lc,
-                                             const double *__restrict__ xg, double *__restrict__ w_lds, int nloc) {
-  constexpr int ER = EPR - EL;
-  constexpr int PS_BATCH = EPR >= 5 ? 2 : EPR == 4 ? 3 : EPR == 3 ? 4 : EPR == 2 ? 6 : 12;
-  const int g = threadIdx.x >> 5, l = threadIdx.x & 31;
   const __amdgpu_buffer_rsrc_t xb = __builtin_amdgcn_make_buffer_rsrc((void *)xg, 0, 0x7fffffff, 0x00020000);
 #pragma unroll
   for (int r0 = 0; r0 < RI; r0 += PS_BATCH) {
@@ -218,43 +236,35 @@ __device__ __forceinline__ void ps_product_l(const double (&v)[RI][EPR - EL], co
   }
 }
 
+// The end of every solve: the own rows of x to HBM; workgroup 0 reports the iterations, the norm (nu for CG), CG's nu0 and
+// the status.
+__device__ __forceinline__ void ps_finish(const tg_ps_args &A, const double *x_lds, int64_t c0, int nloc, int its, double res,
+                                          int status, double nu0 = 0.0) {
+#pragma unroll 1
+  for (int i = threadIdx.x; i < nloc; i += PS_NT) A.x[c0 + i] = x_lds[i];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    A.ctrl->out[0] = (double)its;
+    A.ctrl->out[1] = res;
+    A.ctrl->out[2] = nu0;
+    A.ctrl->out[3] = (double)status;
+  }
+}
+
 template <int EPR, int RI>
 __global__ void __launch_bounds__(PS_NT) k_cg_persistent(tg_ps_args A) {
   extern __shared__ double ps_dyn[];
   ps_lds &L = *(ps_lds *)ps_dyn;
   const unsigned G = gridDim.x;
   unsigned gen = 0;
-  const int64_t per = (A.n + G - 1) / G;
-  const int64_t c0r = (int64_t)blockIdx.x * per, c0 = c0r < A.n ? c0r : A.n, c1 = c0 + per < A.n ? c0 + per : A.n;
-  const int nloc = (int)(c1 - c0);
-  const int tid = threadIdx.x, g = tid >> 5, l = tid & 31;
-  // ---- the rows of K into registers; the Jacobi diagonal (PCJACOBI [ext]: 1 where the diagonal is zero / absent)
+  int nloc;
+  const int64_t c0 = ps_rows(A.n, nloc);
+  const int tid = threadIdx.x;
   double v[RI][EPR];
-  unsigned c[RI][EPR];           // byte offsets of the columns
-#pragma unroll
-  for (int ri = 0; ri < RI; ri++) {
-    const int lrow = g + PS_GROUPS * ri;
-    const int64_t row = c0 + lrow;
-    const bool live = lrow < nloc;
-    const int64_t a = live ? A.rowptr[row] : 0, e = live ? A.rowptr[row + 1] : 0;
-    double dd = 0.0;
-#pragma unroll
-    for (int k = 0; k < EPR; k++) {
-      const int64_t q = a + l + 32 * k;
-      const bool in = q < e;
-      v[ri][k] = in ? A.val[q] : 0.0;
-      const int cq = in ? A.col[q] : (int)(live ? row : 0);
-      c[ri][k] = 8u * (unsigned)cq;
-      if (in && cq == row) dd = v[ri][k];
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) dd += __shfl_xor(dd, o, 64);
-    if (l == 0 && live) L.dinv[lrow] = (A.jacobi && dd != 0.0) ? 1.0 / dd : 1.0;
-  }
-  __syncthreads();
+  unsigned c[RI][EPR];
+  ps_load_rows<EPR, RI, 0>(A, c0, nloc, v, c, nullptr, nullptr, L.dinv);
   double bn = 0.0;                         // ||B b||^2 of the own rows (reference norm when a guess is given)
   if (A.nonzero_guess) {
-    ps_product<EPR, RI>(v, c, A.x, L.w, nloc);      // r = b - K x0: all of x0 was written before the launch
+    ps_product<EPR, RI, 0>(v, c, nullptr, nullptr, A.x, L.w, nloc);      // r = b - K x0: all of x0 was written before the launch
     __syncthreads();
   }
   double gp = 0.0, np = 0.0, dp = 0.0;     // this thread's terms of (r,u), (u,u), (w,u)
@@ -281,23 +291,9 @@ __global__ void __launch_bounds__(PS_NT) k_cg_persistent(tg_ps_args A) {
   if (!ps_barrier(A.ctrl, G, gen, A.budget_ticks)) return;          // u complete
   double gamma_prev = 0.0, alpha_prev = 0.0, tol2 = 0.0, nu0 = 0.0, nu = 0.0;
   int it = 0, status = -1;
-  long long t_spmv = 0, t_bar1 = 0, t_upd = 0, t_bar2 = 0;
-#ifdef PS_TIMING
-  long long t_mark = wall_clock64();
-#endif
-#ifdef PS_TIMING
-#define PS_MARK(acc)                       \
-  do {                                     \
-    const long long now_ = wall_clock64(); \
-    acc += now_ - t_mark;                  \
-    t_mark = now_;                         \
-  } while (0)
-#else
-#define PS_MARK(acc) (void)acc
-#endif
   for (;;) {
     // ---- w = K u on the own rows, the three inner products of the own rows
-    ps_product<EPR, RI>(v, c, A.u, L.w, nloc);
+    ps_product<EPR, RI, 0>(v, c, nullptr, nullptr, A.u, L.w, nloc);
     __syncthreads();
     dp = 0.0;
     for (int i = tid; i < nloc; i += PS_NT) dp += L.w[i] * L.u[i];
@@ -310,9 +306,7 @@ __global__ void __launch_bounds__(PS_NT) k_cg_persistent(tg_ps_args A) {
         ps_store(&A.partial[4 * blockIdx.x + 2], cc);
       }
     }
-    PS_MARK(t_spmv);
     if (!ps_barrier(A.ctrl, G, gen, A.budget_ticks)) return;
-    PS_MARK(t_bar1);
     double gamma = 0.0, delta = 0.0;
     nu = 0.0;
     if (tid < (int)G) {
@@ -369,21 +363,9 @@ __global__ void __launch_bounds__(PS_NT) k_cg_persistent(tg_ps_args A) {
       np += ui * ui;
     }
     it++;
-    PS_MARK(t_upd);
     if (!ps_barrier(A.ctrl, G, gen, A.budget_ticks)) return;        // u complete before the next product
-    PS_MARK(t_bar2);
   }
-  for (int i = tid; i < nloc; i += PS_NT) A.x[c0 + i] = L.x[i];
-  if (blockIdx.x == 0 && tid == 0) {
-    A.ctrl->out[0] = (double)it;
-    A.ctrl->out[1] = nu;
-    A.ctrl->out[2] = nu0;
-    A.ctrl->out[3] = (double)status;
-    A.ctrl->out[4] = (double)t_spmv;
-    A.ctrl->out[5] = (double)t_bar1;
-    A.ctrl->out[6] = (double)t_upd;
-    A.ctrl->out[7] = (double)t_bar2;
-  }
+  ps_finish(A, L.x, c0, nloc, it, nu, status, nu0);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -435,39 +417,12 @@ __global__ void __launch_bounds__(PS_NT) k_gmres_persistent(tg_pg_args Q) {
   const int m = Q.m;
   const unsigned G = gridDim.x;
   unsigned gen = 0;
-  const int64_t per = (A.n + G - 1) / G;
-  const int64_t c0r = (int64_t)blockIdx.x * per, c0 = c0r < A.n ? c0r : A.n, c1 = c0 + per < A.n ? c0 + per : A.n;
-  const int nloc = (int)(c1 - c0);
-  const int tid = threadIdx.x, g = tid >> 5, l = tid & 31, lane = tid & 63, wv = tid >> 6;
+  int nloc;
+  const int64_t c0 = ps_rows(A.n, nloc);
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   double v[RI][ER];
   unsigned c[RI][ER];
-#pragma unroll
-  for (int ri = 0; ri < RI; ri++) {
-    const int lrow = g + PS_GROUPS * ri;
-    const int64_t row = c0 + lrow;
-    const bool live = lrow < nloc;
-    const int64_t a = live ? A.rowptr[row] : 0, e = live ? A.rowptr[row + 1] : 0;
-    double dd = 0.0;
-#pragma unroll
-    for (int k = 0; k < EPR; k++) {
-      const int64_t q = a + l + 32 * k;
-      const bool in = q < e;
-      const double vq = in ? A.val[q] : 0.0;
-      const int cq = in ? A.col[q] : (int)(live ? row : 0);
-      if (k < ER) {
-        v[ri][k < ER ? k : 0] = vq;
-        c[ri][k < ER ? k : 0] = 8u * (unsigned)cq;
-      } else {
-        lv[(ri * EL + (k - ER)) * PS_NT + tid] = vq;
-        lc[(ri * EL + (k - ER)) * PS_NT + tid] = 8u * (unsigned)cq;
-      }
-      if (in && cq == row) dd = vq;
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) dd += __shfl_xor(dd, o, 64);
-    if (l == 0 && live) L.dinv[lrow] = (A.jacobi && dd != 0.0) ? 1.0 / dd : 1.0;
-  }
-  __syncthreads();
+  ps_load_rows<EPR, RI, EL>(A, c0, nloc, v, c, lv, lc, L.dinv);
   const bool mine = tid < nloc;            // one row per thread (nloc <= PG_ROWS <= PS_NT)
   double bn = 0.0;
   if (mine) {
@@ -499,7 +454,7 @@ __global__ void __launch_bounds__(PS_NT) k_gmres_persistent(tg_pg_args Q) {
         if (mine) ps_store(&A.u[c0 + tid], L.x[tid]);
         if (!ps_barrier(A.ctrl, G, gen, A.budget_ticks)) return;
       }
-      ps_product_l<EPR, RI, EL>(v, c, lv, lc, A.u, L.w, nloc);
+      ps_product<EPR, RI, EL>(v, c, lv, lc, A.u, L.w, nloc);
       __syncthreads();
     }
     double rr = 0.0;
@@ -550,7 +505,7 @@ __global__ void __launch_bounds__(PS_NT) k_gmres_persistent(tg_pg_args Q) {
     #pragma unroll 1
     for (int j = 0; j < m && alive; j++) {
       // ---- w = B K v_j
-      ps_product_l<EPR, RI, EL>(v, c, lv, lc, A.u, L.w, nloc);
+      ps_product<EPR, RI, EL>(v, c, lv, lc, A.u, L.w, nloc);
       __syncthreads();
       if (mine) L.w[tid] *= L.dinv[tid];
       __syncthreads();
@@ -661,12 +616,7 @@ __global__ void __launch_bounds__(PS_NT) k_gmres_persistent(tg_pg_args Q) {
     }
     __syncthreads();
   }
-  if (mine) A.x[c0 + tid] = L.x[tid];
-  if (blockIdx.x == 0 && tid == 0) {
-    A.ctrl->out[0] = (double)its;
-    A.ctrl->out[1] = res;
-    A.ctrl->out[3] = (double)status;
-  }
+  ps_finish(A, L.x, c0, nloc, its, res, status);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -692,39 +642,12 @@ __global__ void __launch_bounds__(PS_NT) k_bicgstab_persistent(tg_pg_args Q) {
   const tg_ps_args &A = Q.P;
   const unsigned G = gridDim.x;
   unsigned gen = 0;
-  const int64_t per = (A.n + G - 1) / G;
-  const int64_t c0r = (int64_t)blockIdx.x * per, c0 = c0r < A.n ? c0r : A.n, c1 = c0 + per < A.n ? c0 + per : A.n;
-  const int nloc = (int)(c1 - c0);
-  const int tid = threadIdx.x, g = tid >> 5, l = tid & 31;
+  int nloc;
+  const int64_t c0 = ps_rows(A.n, nloc);
+  const int tid = threadIdx.x;
   double v[RI][ER];
   unsigned c[RI][ER];
-#pragma unroll
-  for (int ri = 0; ri < RI; ri++) {
-    const int lrow = g + PS_GROUPS * ri;
-    const int64_t row = c0 + lrow;
-    const bool live = lrow < nloc;
-    const int64_t a = live ? A.rowptr[row] : 0, e = live ? A.rowptr[row + 1] : 0;
-    double dd = 0.0;
-#pragma unroll
-    for (int k = 0; k < EPR; k++) {
-      const int64_t q = a + l + 32 * k;
-      const bool in = q < e;
-      const double vq = in ? A.val[q] : 0.0;
-      const int cq = in ? A.col[q] : (int)(live ? row : 0);
-      if (k < ER) {
-        v[ri][k < ER ? k : 0] = vq;
-        c[ri][k < ER ? k : 0] = 8u * (unsigned)cq;
-      } else {
-        lv[(ri * EL + (k - ER)) * PS_NT + tid] = vq;
-        lc[(ri * EL + (k - ER)) * PS_NT + tid] = 8u * (unsigned)cq;
-      }
-      if (in && cq == row) dd = vq;
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) dd += __shfl_xor(dd, o, 64);
-    if (l == 0 && live) L.dinv[lrow] = (A.jacobi && dd != 0.0) ? 1.0 / dd : 1.0;
-  }
-  __syncthreads();
+  ps_load_rows<EPR, RI, EL>(A, c0, nloc, v, c, lv, lc, L.dinv);
   // ---- reference norm ||B b||, r = B (b - K x0), rhat = r
   double bn = 0.0;
 #pragma unroll 1
@@ -734,7 +657,7 @@ __global__ void __launch_bounds__(PS_NT) k_bicgstab_persistent(tg_pg_args Q) {
     L.x[i] = A.nonzero_guess ? A.x[c0 + i] : 0.0;
   }
   if (A.nonzero_guess) {
-    ps_product_l<EPR, RI, EL>(v, c, lv, lc, A.x, L.w, nloc);
+    ps_product<EPR, RI, EL>(v, c, lv, lc, A.x, L.w, nloc);
     __syncthreads();
   }
   double rn = 0.0;
@@ -777,7 +700,7 @@ __global__ void __launch_bounds__(PS_NT) k_bicgstab_persistent(tg_pg_args Q) {
         ps_store(&A.u[c0 + i], pi);
       }
       if (!ps_barrier(A.ctrl, G, gen, A.budget_ticks)) return;
-      ps_product_l<EPR, RI, EL>(v, c, lv, lc, A.u, L.w, nloc);
+      ps_product<EPR, RI, EL>(v, c, lv, lc, A.u, L.w, nloc);
       __syncthreads();
       double hv = 0.0;
 #pragma unroll 1
@@ -809,7 +732,7 @@ __global__ void __launch_bounds__(PS_NT) k_bicgstab_persistent(tg_pg_args Q) {
         ps_store(&A.u[c0 + i], si);
       }
       if (!ps_barrier(A.ctrl, G, gen, A.budget_ticks)) return;
-      ps_product_l<EPR, RI, EL>(v, c, lv, lc, A.u, L.w, nloc);
+      ps_product<EPR, RI, EL>(v, c, lv, lc, A.u, L.w, nloc);
       __syncthreads();
       double ts = 0.0, tt = 0.0, hs = 0.0, ht = 0.0, ss = 0.0;
 #pragma unroll 1
@@ -873,13 +796,7 @@ __global__ void __launch_bounds__(PS_NT) k_bicgstab_persistent(tg_pg_args Q) {
     }
   }
   __syncthreads();
-#pragma unroll 1
-  for (int i = tid; i < nloc; i += PS_NT) A.x[c0 + i] = L.x[i];
-  if (blockIdx.x == 0 && tid == 0) {
-    A.ctrl->out[0] = (double)its;
-    A.ctrl->out[1] = znorm;
-    A.ctrl->out[3] = (double)status;
-  }
+  ps_finish(A, L.x, c0, nloc, its, znorm, status);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -909,34 +826,13 @@ __global__ void __launch_bounds__(PS_NT) k_pcg_cheb_persistent(tg_pc_args Q) {
   const tg_ps_args &A = Q.P;
   const unsigned G = gridDim.x;
   unsigned gen = 0;
-  const int64_t per = (A.n + G - 1) / G;
-  const int64_t c0r = (int64_t)blockIdx.x * per, c0 = c0r < A.n ? c0r : A.n, c1 = c0 + per < A.n ? c0 + per : A.n;
-  const int nloc = (int)(c1 - c0);
-  const int tid = threadIdx.x, g = tid >> 5, l = tid & 31;
+  int nloc;
+  const int64_t c0 = ps_rows(A.n, nloc);
+  const int tid = threadIdx.x;
   double v[RI][EPR];
   unsigned c[RI][EPR];
-#pragma unroll
-  for (int ri = 0; ri < RI; ri++) {
-    const int lrow = g + PS_GROUPS * ri;
-    const int64_t row = c0 + lrow;
-    const bool live = lrow < nloc;
-    const int64_t a = live ? A.rowptr[row] : 0, e = live ? A.rowptr[row + 1] : 0;
-    double dd = 0.0;
-#pragma unroll
-    for (int k = 0; k < EPR; k++) {
-      const int64_t q = a + l + 32 * k;
-      const bool in = q < e;
-      v[ri][k] = in ? A.val[q] : 0.0;
-      const int cq = in ? A.col[q] : (int)(live ? row : 0);
-      c[ri][k] = 8u * (unsigned)cq;
-      if (in && cq == row) dd = v[ri][k];
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) dd += __shfl_xor(dd, o, 64);
-    if (l == 0 && live) L.dinv[lrow] = dd != 0.0 ? 1.0 / dd : 1.0;       // (the polynomial is in D^-1 K: always Jacobi)
-  }
-  __syncthreads();
-  int flip = 0;                                    // which gather buffer the next write goes to
+  ps_load_rows<EPR, RI, 0>(A, c0, nloc, v, c, nullptr, nullptr, L.dinv);
+  int flip = 0;                                   // which gather buffer the next write goes to
   double *const gb[2] = {A.u, Q.u2};
   const double inv_theta = 1.0 / Q.theta, sigma = Q.theta / Q.delta;
   bool ok = true;
@@ -963,7 +859,7 @@ __global__ void __launch_bounds__(PS_NT) k_pcg_cheb_persistent(tg_pc_args Q) {
         ok = false;
         break;
       }
-      ps_product<EPR, RI>(v, c, buf, L.w, nloc);
+      ps_product<EPR, RI, 0>(v, c, nullptr, nullptr, buf, L.w, nloc);
       __syncthreads();
 #pragma unroll 1
       for (int i = tid; i < nloc; i += PS_NT) {
@@ -985,7 +881,7 @@ __global__ void __launch_bounds__(PS_NT) k_pcg_cheb_persistent(tg_pc_args Q) {
       ok = false;
       return;
     }
-    ps_product<EPR, RI>(v, c, buf, L.w, nloc);
+    ps_product<EPR, RI, 0>(v, c, nullptr, nullptr, buf, L.w, nloc);
     __syncthreads();
   };
   // ---- reference norm ||B b||: u = B b
@@ -1081,20 +977,27 @@ __global__ void __launch_bounds__(PS_NT) k_pcg_cheb_persistent(tg_pc_args Q) {
     apply_pc();
     if (!ok) return;
   }
-#pragma unroll 1
-  for (int i = tid; i < nloc; i += PS_NT) A.x[c0 + i] = L.x[i];
-  if (blockIdx.x == 0 && tid == 0) {
-    A.ctrl->out[0] = (double)its;
-    A.ctrl->out[1] = znorm;
-    A.ctrl->out[3] = (double)status;
-  }
+  ps_finish(A, L.x, c0, nloc, its, znorm, status);
 }
+
+// The (EPR, RI) shapes the kernels are compiled for: RI rows per group of lanes at EPR entries per lane and row, RI rising
+// for each EPR.  GMRES and BiCGStab hold one layer of K in LDS at EPR 5 with RI >= 11 (ps_el); CG and Chebyshev-CG never.
+#define PS_SHAPES(X)                  \
+  X(1, 16) X(1, 32) X(1, 48) X(1, 56) \
+  X(2, 8) X(2, 16) X(2, 24) X(2, 28)  \
+  X(3, 6) X(3, 12) X(3, 17) X(3, 18)  \
+  X(4, 4) X(4, 8) X(4, 12) X(4, 14)   \
+  X(5, 4) X(5, 8) X(5, 11) X(5, 13)
+static constexpr int ps_el(int epr, int ri) { return epr == 5 && ri >= 11 ? 1 : 0; }
+
+struct ps_dims {
+  int epr, ri, G, el;                        // entries per lane and row, rows per group of lanes, workgroups, layers in LDS
+};
 
 // Whether a system is taken by the persistent loop: one rank, at least a thousand rows (below, the launches are not what
 // the solve costs), rows of at most 128 entries, and all of K in the registers of one workgroup per CU
 // (TIGAR_KSP_PERSISTENT=0 turns it off, =1 lifts the lower limit).
-static const int PS_RI[5][4] = {{16, 32, 48, 56}, {8, 16, 24, 28}, {6, 12, 17, 18}, {4, 8, 12, 14}, {4, 8, 11, 13}};   // rows per group of lanes, by EPR
-static bool ps_shape(const tg_csr_s *k, int64_t rows_max, int *epr_out, int *ri_out, int *g_out) {
+static bool ps_shape(const tg_csr_s *k, int64_t rows_max, bool lds_layer, ps_dims *d) {
   const int64_t n = k->nrows;
   const int maxlen = k->max_row_nnz;
   if (maxlen < 1 || maxlen > 160) return false;
@@ -1103,11 +1006,14 @@ static bool ps_shape(const tg_csr_s *k, int64_t rows_max, int *epr_out, int *ri_
   G = (int)std::min<int64_t>(G, std::max<int64_t>(1, tg_cdiv(n, PS_GROUPS)));
   const int64_t per = tg_cdiv(n, G);
   if (per > rows_max) return false;
-  for (int q = 0; q < 4; q++)
-    if (per <= (int64_t)PS_RI[epr - 1][q] * PS_GROUPS) {
-      *epr_out = epr;
-      *ri_out = PS_RI[epr - 1][q];
-      *g_out = G;
+  static const int shapes[][2] = {
+#define PS_ROW(E, R) {E, R},
+      PS_SHAPES(PS_ROW)
+#undef PS_ROW
+  };
+  for (const auto &s : shapes)
+    if (s[0] == epr && per <= (int64_t)s[1] * PS_GROUPS) {
+      *d = {epr, s[1], G, lds_layer ? ps_el(epr, s[1]) : 0};
       return true;
     }
   return false;
@@ -1119,158 +1025,55 @@ bool tg_cg_persistent_applies(const tg_csr_s *k) {
   return mode == 1 || k->nrows >= 1024;
 }
 
-// Returns 0 with the results set, 100 when the kernel could not be used (K beyond the registers, workgroups not resident,
-// barrier time-out): the caller runs the multi-kernel loop instead.
-int tg_cg_persistent(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int pc, double rtol, double atol, int maxit, int nonzero_guess,
-                     int *iters, double *resnorm, int *status) {
-  const int64_t n = k->nrows;
-  TG_TRY(tg_spmv_plan(k));                   // (longest row)
-  int epr = 0, ri = 0, G = 0;
-  if (!ps_shape(k, PS_ROWS_MAX, &epr, &ri, &G)) return 100;
-  double *buf = nullptr;
-  const int64_t ctrl_doubles = (int64_t)(sizeof(tg_ps_ctrl) + 7) / 8 + 16;
-  TG_TRY(tg_dmalloc(&buf, n + 4 * (int64_t)G + 16 + ctrl_doubles));
+// The arguments every solver takes (the pointers into the work buffer are set by ps_launch)
+static tg_ps_args ps_args(const tg_csr_s *k, const tg_vec_s *b, tg_vec_s *x, int jacobi, double rtol, double atol, int maxit,
+                          int nonzero_guess) {
   tg_ps_args A;
   memset(&A, 0, sizeof(A));
   A.rowptr = k->rowptr;
   A.col = k->col;
   A.val = k->val;
-  A.n = n;
+  A.n = k->nrows;
   A.b = b->d;
   A.x = x->d;
-  A.u = buf;
-  A.partial = buf + n;
-  A.ctrl = (tg_ps_ctrl *)(((uintptr_t)(buf + n + 4 * (int64_t)G) + 127) & ~(uintptr_t)127);
   A.rtol = rtol;
   A.atol = atol;
   A.maxit = maxit;
-  A.jacobi = pc == TG_PC_JACOBI ? 1 : 0;
+  A.jacobi = jacobi;
   A.nonzero_guess = nonzero_guess;
   A.budget_ticks = 100000000ll * 5;          // wall_clock64 runs at 100 MHz: 5 s at one barrier
-  hipMemsetAsync(A.ctrl, 0, sizeof(tg_ps_ctrl), g_tg.stream);
-  void *params[] = {&A};
-  const void *fn = nullptr;
-#define PS_PICK(E, R) \
-  if (epr == E && ri == R) fn = (const void *)k_cg_persistent<E, R>
-  PS_PICK(1, 16); PS_PICK(1, 32); PS_PICK(1, 48); PS_PICK(1, 56);
-  PS_PICK(2, 8); PS_PICK(2, 16); PS_PICK(2, 24); PS_PICK(2, 28);
-  PS_PICK(3, 6); PS_PICK(3, 12); PS_PICK(3, 17); PS_PICK(3, 18);
-  PS_PICK(4, 4); PS_PICK(4, 8); PS_PICK(4, 12); PS_PICK(4, 14);
-  PS_PICK(5, 4); PS_PICK(5, 8); PS_PICK(5, 11); PS_PICK(5, 13);
-#undef PS_PICK
-  if (!fn) {
-    tg_dfree(buf);
-    return 100;
-  }
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEventCreate(&ev0);
-  hipEventCreate(&ev1);
-  hipEventRecord(ev0, g_tg.stream);
-  hipError_t e = hipLaunchCooperativeKernel(fn, dim3((unsigned)G), dim3(PS_NT), params, sizeof(ps_lds), g_tg.stream);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    hipEventDestroy(ev0);
-    hipEventDestroy(ev1);
-    tg_dfree(buf);
-    return 100;
-  }
-  hipEventRecord(ev1, g_tg.stream);
-  tg_ps_ctrl h;
-  e = hipMemcpyAsync(&h, A.ctrl, sizeof(h), hipMemcpyDeviceToHost, g_tg.stream);
-  const hipError_t e2 = hipStreamSynchronize(g_tg.stream);
-  float ems = 0.f;
-  if (e2 == hipSuccess && hipEventElapsedTime(&ems, ev0, ev1) != hipSuccess) ems = 0.f;
-  hipEventDestroy(ev0);
-  hipEventDestroy(ev1);
-  tg_dfree(buf);
-  if (e != hipSuccess || e2 != hipSuccess) {
-    tg_set_error("persistent CG: %s", hipGetErrorString(e2 != hipSuccess ? e2 : e));
-    return 1;
-  }
-  if (h.abort_flag) return 100;
-  if (getenv("TIGAR_TRACE"))
-    fprintf(stderr, "[trace] persistent cg: %d its, workgroup 0 per iteration: product+dots %.2f us, barrier %.2f us, fold+update %.2f us, "
-            "barrier %.2f us (%d workgroups, %d entries per lane and row, %d rows per group of lanes)\n", (int)h.out[0], h.out[4] / 100.0 / std::max(1.0, h.out[0]),
-            h.out[5] / 100.0 / std::max(1.0, h.out[0]), h.out[6] / 100.0 / std::max(1.0, h.out[0]),
-            h.out[7] / 100.0 / std::max(1.0, h.out[0]), G, epr, ri);
-  g_tg.prof_n[TG_PROF_KSP_PERSISTENT] += 1;
-  g_tg.prof_ms[TG_PROF_KSP_PERSISTENT] += ems;
-  g_tg.prof_n[TG_PROF_KSP_SPMV] += (int64_t)h.out[0] + 1 + (nonzero_guess ? 1 : 0);
-  g_tg.prof_ms[TG_PROF_KSP_SPMV] += ems;
-  *iters = (int)h.out[0];
-  *resnorm = sqrt(h.out[1]);
-  *status = (int)h.out[3];
-  return 0;
+  return A;
 }
 
-// GMRES(m), m <= 30, one rank, no stagnation guard (restart >= 1), or BiCGStab (restart = 0): as tg_cg_persistent
-// (100 = not taken, the caller runs tg_gmres / tg_bicgstab)
-static int ps_run_pg(bool bicgstab, tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int pc, double rtol, double atol, int maxit, int restart,
-                     int nonzero_guess, int *iters, double *resnorm, int *status) {
-  const int64_t n = k->nrows;
-  if (!bicgstab && (restart < 1 || restart > PG_M)) return 100;
-  TG_TRY(tg_spmv_plan(k));
-  int epr = 0, ri = 0, G = 0;
-  if (!ps_shape(k, bicgstab ? PS_ROWS_MAX : PG_ROWS, &epr, &ri, &G)) return 100;
-  size_t lds_bytes = bicgstab ? sizeof(pb_lds) : sizeof(pg_lds);
-  double *buf = nullptr;
-  const int64_t ctrl_doubles = (int64_t)(sizeof(tg_ps_ctrl) + 7) / 8 + 16;
-  const int64_t npart = (int64_t)G * (PG_M + 1) + 2 * (int64_t)G;
-  TG_TRY(tg_dmalloc(&buf, n + npart + 16 + ctrl_doubles));
-  tg_pg_args Q;
-  memset(&Q, 0, sizeof(Q));
-  tg_ps_args &A = Q.P;
-  A.rowptr = k->rowptr;
-  A.col = k->col;
-  A.val = k->val;
-  A.n = n;
-  A.b = b->d;
-  A.x = x->d;
-  A.u = buf;
-  Q.pdots = buf + n;
-  Q.pnorm = Q.pdots + (int64_t)G * (PG_M + 1);
-  A.ctrl = (tg_ps_ctrl *)(((uintptr_t)(buf + n + npart) + 127) & ~(uintptr_t)127);
-  A.rtol = rtol;
-  A.atol = atol;
-  A.maxit = maxit;
-  A.jacobi = pc == TG_PC_JACOBI ? 1 : 0;
-  A.nonzero_guess = nonzero_guess;
-  A.budget_ticks = 100000000ll * 5;
-  Q.m = restart;
-  hipMemsetAsync(A.ctrl, 0, sizeof(tg_ps_ctrl), g_tg.stream);
-  void *params[] = {&Q};
-  const void *fn = nullptr;
-  int el = 0;                                // layers of K in LDS (GMRES with rows of 129-160 entries)
-#define PS_PICK(E, R)                                                                                  \
-  if (epr == E && ri == R) {                                                                           \
-    if (bicgstab && E == 5 && R >= 11) {                                                               \
-      fn = (const void *)k_bicgstab_persistent<E, R, (E == 5 && R >= 11) ? 1 : 0>;                     \
-      el = 1;                                                                                          \
-    } else if (bicgstab)                                                                               \
-      fn = (const void *)k_bicgstab_persistent<E, R, 0>;                                               \
-    else if (E == 5 && R >= 11) {                                                                      \
-      fn = (const void *)k_gmres_persistent<E, R, (E == 5 && R >= 11) ? 1 : 0>;                        \
-      el = 1;                                                                                          \
-    } else                                                                                             \
-      fn = (const void *)k_gmres_persistent<E, R, 0>;                                                  \
-  }
-  PS_PICK(1, 16); PS_PICK(1, 32); PS_PICK(1, 48); PS_PICK(1, 56);
-  PS_PICK(2, 8); PS_PICK(2, 16); PS_PICK(2, 24); PS_PICK(2, 28);
-  PS_PICK(3, 6); PS_PICK(3, 12); PS_PICK(3, 17); PS_PICK(3, 18);
-  PS_PICK(4, 4); PS_PICK(4, 8); PS_PICK(4, 12); PS_PICK(4, 14);
-  PS_PICK(5, 4); PS_PICK(5, 8); PS_PICK(5, 11); PS_PICK(5, 13);
-#undef PS_PICK
-  if (el) lds_bytes = (((bicgstab ? sizeof(pb_lds) : sizeof(pg_lds)) + 7) / 8) * 8 + (size_t)ri * el * PS_NT * 12;
-  if (!fn || lds_bytes > 160 * 1024 || hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) {
+// One persistent solve, the same for every solver.  The work buffer holds nvec gather vectors of n rows (A.u is the first),
+// npart doubles of partial sums -- place(part) points the solver's own fields at them -- and the control block on 128-byte
+// lines of its own.  Q: the kernel's arguments, A their common part; lds_base: the kernel's LDS struct, the layer of K
+// (d.el) comes on top.  Products counted: spmv_it per iteration + spmv_once.  Returns 0 with the results set (resnorm: the
+// kernel's out[1]), 1 on a runtime error, 100 when the kernel could not be used (LDS beyond the CU, workgroups not
+// resident, barrier time-out): the caller runs the multi-kernel loop instead.
+template <class Place>
+static int ps_launch(const char *name, const void *fn, size_t lds_base, const ps_dims &d, void *Q, tg_ps_args &A, int nvec,
+                     int64_t npart, Place place, int64_t spmv_it, int64_t spmv_once, int *iters, double *resnorm, int *status) {
+  const size_t lds_bytes = (lds_base + 7) / 8 * 8 + (size_t)d.ri * d.el * PS_NT * 12;
+  if (!fn || lds_bytes > 160 * 1024 ||
+      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) {
     (void)hipGetLastError();
-    tg_dfree(buf);
     return 100;
   }
+  const int64_t n = A.n;
+  double *buf = nullptr;
+  const int64_t ctrl_doubles = (int64_t)(sizeof(tg_ps_ctrl) + 7) / 8 + 16;
+  TG_TRY(tg_dmalloc(&buf, nvec * n + npart + 16 + ctrl_doubles));
+  A.u = buf;
+  A.ctrl = (tg_ps_ctrl *)(((uintptr_t)(buf + nvec * n + npart) + 127) & ~(uintptr_t)127);
+  place(buf + nvec * n);
+  hipMemsetAsync(A.ctrl, 0, sizeof(tg_ps_ctrl), g_tg.stream);
+  void *params[] = {Q};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEventCreate(&ev0);
   hipEventCreate(&ev1);
   hipEventRecord(ev0, g_tg.stream);
-  hipError_t e = hipLaunchCooperativeKernel(fn, dim3((unsigned)G), dim3(PS_NT), params, lds_bytes, g_tg.stream);
+  hipError_t e = hipLaunchCooperativeKernel(fn, dim3((unsigned)d.G), dim3(PS_NT), params, lds_bytes, g_tg.stream);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     hipEventDestroy(ev0);
@@ -1288,21 +1091,59 @@ static int ps_run_pg(bool bicgstab, tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int p
   hipEventDestroy(ev1);
   tg_dfree(buf);
   if (e != hipSuccess || e2 != hipSuccess) {
-    tg_set_error("persistent %s: %s", bicgstab ? "BiCGStab" : "GMRES", hipGetErrorString(e2 != hipSuccess ? e2 : e));
+    tg_set_error("persistent %s: %s", name, hipGetErrorString(e2 != hipSuccess ? e2 : e));
     return 1;
   }
   if (h.abort_flag) return 100;
   if (getenv("TIGAR_TRACE"))
-    fprintf(stderr, "[trace] persistent %s(%d): %d its in %.3f ms (%d workgroups, %d entries per lane and row, %d rows per group)\n",
-            bicgstab ? "bicgstab" : "gmres", restart, (int)h.out[0], ems, G, epr, ri);
+    fprintf(stderr, "[trace] persistent %s: %d its in %.3f ms (%d workgroups, %d entries per lane and row, %d rows per group of "
+            "lanes, %d layers of K in LDS)\n", name, (int)h.out[0], ems, d.G, d.epr, d.ri, d.el);
   g_tg.prof_n[TG_PROF_KSP_PERSISTENT] += 1;
   g_tg.prof_ms[TG_PROF_KSP_PERSISTENT] += ems;
-  g_tg.prof_n[TG_PROF_KSP_SPMV] += (bicgstab ? 2 : 1) * (int64_t)h.out[0] + 1;
+  g_tg.prof_n[TG_PROF_KSP_SPMV] += spmv_it * (int64_t)h.out[0] + spmv_once;
   g_tg.prof_ms[TG_PROF_KSP_SPMV] += ems;
   *iters = (int)h.out[0];
   *resnorm = h.out[1];
   *status = (int)h.out[3];
   return 0;
+}
+
+int tg_cg_persistent(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int pc, double rtol, double atol, int maxit, int nonzero_guess,
+                     int *iters, double *resnorm, int *status) {
+  TG_TRY(tg_spmv_plan(k));                   // (longest row)
+  ps_dims d;
+  if (!ps_shape(k, PS_ROWS_MAX, false, &d)) return 100;
+  const void *fn = nullptr;
+#define PS_PICK(E, R) \
+  if (d.epr == E && d.ri == R) fn = (const void *)k_cg_persistent<E, R>;
+  PS_SHAPES(PS_PICK)
+#undef PS_PICK
+  tg_ps_args A = ps_args(k, b, x, pc == TG_PC_JACOBI ? 1 : 0, rtol, atol, maxit, nonzero_guess);
+  const int rc = ps_launch("CG", fn, sizeof(ps_lds), d, &A, A, 1, 4 * (int64_t)d.G, [&](double *part) { A.partial = part; }, 1,
+                           1 + (nonzero_guess ? 1 : 0), iters, resnorm, status);
+  if (rc == 0) *resnorm = sqrt(*resnorm);    // (the kernel reports nu = ||B r||^2)
+  return rc;
+}
+
+// GMRES(m), m <= 30, one rank, no stagnation guard (restart >= 1), or BiCGStab (restart = 0): the same work buffer
+// (pdots [G][PG_M + 1], pnorm [G][2]) and arguments; 100 = not taken, the caller runs tg_gmres / tg_bicgstab
+static int ps_run_pg(bool bicgstab, tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int pc, double rtol, double atol, int maxit, int restart,
+                     int nonzero_guess, int *iters, double *resnorm, int *status) {
+  if (!bicgstab && (restart < 1 || restart > PG_M)) return 100;
+  TG_TRY(tg_spmv_plan(k));
+  ps_dims d;
+  if (!ps_shape(k, bicgstab ? PS_ROWS_MAX : PG_ROWS, true, &d)) return 100;
+  const void *fn = nullptr;
+#define PS_PICK(E, R)                                                                                         \
+  if (d.epr == E && d.ri == R)                                                                                \
+    fn = bicgstab ? (const void *)k_bicgstab_persistent<E, R, ps_el(E, R)> : (const void *)k_gmres_persistent<E, R, ps_el(E, R)>;
+  PS_SHAPES(PS_PICK)
+#undef PS_PICK
+  tg_pg_args Q = {ps_args(k, b, x, pc == TG_PC_JACOBI ? 1 : 0, rtol, atol, maxit, nonzero_guess), restart, nullptr, nullptr};
+  const int64_t G = d.G;
+  return ps_launch(bicgstab ? "BiCGStab" : "GMRES", fn, bicgstab ? sizeof(pb_lds) : sizeof(pg_lds), d, &Q, Q.P, 1,
+                   G * (PG_M + 1) + 2 * G, [&](double *part) { Q.pdots = part; Q.pnorm = part + G * (PG_M + 1); },
+                   bicgstab ? 2 : 1, 1, iters, resnorm, status);
 }
 
 int tg_gmres_persistent(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int pc, double rtol, double atol, int maxit, int restart,
@@ -1314,90 +1155,20 @@ int tg_bicgstab_persistent(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int pc, double
   return ps_run_pg(true, k, b, x, pc, rtol, atol, maxit, 0, nonzero_guess, iters, resnorm, status);
 }
 
-
 // CG with the Chebyshev polynomial preconditioner of degree m on [theta - delta, theta + delta] (from tg_pcg_cheb's Lanczos
-// steps); 100 = not taken
+// steps), the gather vector in two buffers; 100 = not taken
 int tg_pcg_cheb_persistent(tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, int m, double theta, double delta, double rtol, double atol,
                            int maxit, int nonzero_guess, int *iters, double *resnorm, int *status) {
-  const int64_t n = k->nrows;
   TG_TRY(tg_spmv_plan(k));
-  int epr = 0, ri = 0, G = 0;
-  if (!ps_shape(k, PS_ROWS_MAX, &epr, &ri, &G) || !(delta > 0.0) || !(theta > delta)) return 100;
-  double *buf = nullptr;
-  const int64_t ctrl_doubles = (int64_t)(sizeof(tg_ps_ctrl) + 7) / 8 + 16;
-  TG_TRY(tg_dmalloc(&buf, 2 * n + 4 * (int64_t)G + 16 + ctrl_doubles));
-  tg_pc_args Q;
-  memset(&Q, 0, sizeof(Q));
-  tg_ps_args &A = Q.P;
-  A.rowptr = k->rowptr;
-  A.col = k->col;
-  A.val = k->val;
-  A.n = n;
-  A.b = b->d;
-  A.x = x->d;
-  A.u = buf;
-  Q.u2 = buf + n;
-  Q.psum = buf + 2 * n;
-  A.ctrl = (tg_ps_ctrl *)(((uintptr_t)(buf + 2 * n + 4 * (int64_t)G) + 127) & ~(uintptr_t)127);
-  A.rtol = rtol;
-  A.atol = atol;
-  A.maxit = maxit;
-  A.jacobi = 1;
-  A.nonzero_guess = nonzero_guess;
-  A.budget_ticks = 100000000ll * 5;
-  Q.m = m;
-  Q.theta = theta;
-  Q.delta = delta;
-  hipMemsetAsync(A.ctrl, 0, sizeof(tg_ps_ctrl), g_tg.stream);
-  void *params[] = {&Q};
+  ps_dims d;
+  if (!ps_shape(k, PS_ROWS_MAX, false, &d) || !(delta > 0.0) || !(theta > delta)) return 100;
   const void *fn = nullptr;
 #define PS_PICK(E, R) \
-  if (epr == E && ri == R) fn = (const void *)k_pcg_cheb_persistent<E, R>
-  PS_PICK(1, 16); PS_PICK(1, 32); PS_PICK(1, 48); PS_PICK(1, 56);
-  PS_PICK(2, 8); PS_PICK(2, 16); PS_PICK(2, 24); PS_PICK(2, 28);
-  PS_PICK(3, 6); PS_PICK(3, 12); PS_PICK(3, 17); PS_PICK(3, 18);
-  PS_PICK(4, 4); PS_PICK(4, 8); PS_PICK(4, 12); PS_PICK(4, 14);
-  PS_PICK(5, 4); PS_PICK(5, 8); PS_PICK(5, 11); PS_PICK(5, 13);
+  if (d.epr == E && d.ri == R) fn = (const void *)k_pcg_cheb_persistent<E, R>;
+  PS_SHAPES(PS_PICK)
 #undef PS_PICK
-  if (!fn || hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(pc_lds)) != hipSuccess) {
-    (void)hipGetLastError();
-    tg_dfree(buf);
-    return 100;
-  }
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEventCreate(&ev0);
-  hipEventCreate(&ev1);
-  hipEventRecord(ev0, g_tg.stream);
-  hipError_t e = hipLaunchCooperativeKernel(fn, dim3((unsigned)G), dim3(PS_NT), params, sizeof(pc_lds), g_tg.stream);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    hipEventDestroy(ev0);
-    hipEventDestroy(ev1);
-    tg_dfree(buf);
-    return 100;
-  }
-  hipEventRecord(ev1, g_tg.stream);
-  tg_ps_ctrl h;
-  e = hipMemcpyAsync(&h, A.ctrl, sizeof(h), hipMemcpyDeviceToHost, g_tg.stream);
-  const hipError_t e2 = hipStreamSynchronize(g_tg.stream);
-  float ems = 0.f;
-  if (e2 == hipSuccess && hipEventElapsedTime(&ems, ev0, ev1) != hipSuccess) ems = 0.f;
-  hipEventDestroy(ev0);
-  hipEventDestroy(ev1);
-  tg_dfree(buf);
-  if (e != hipSuccess || e2 != hipSuccess) {
-    tg_set_error("persistent Chebyshev-CG: %s", hipGetErrorString(e2 != hipSuccess ? e2 : e));
-    return 1;
-  }
-  if (h.abort_flag) return 100;
-  if (getenv("TIGAR_TRACE"))
-    fprintf(stderr, "[trace] persistent chebyshev(%d)-cg: %d its in %.3f ms (%d workgroups)\n", m, (int)h.out[0], ems, G);
-  g_tg.prof_n[TG_PROF_KSP_PERSISTENT] += 1;
-  g_tg.prof_ms[TG_PROF_KSP_PERSISTENT] += ems;
-  g_tg.prof_n[TG_PROF_KSP_SPMV] += ((int64_t)h.out[0] + 2) * m;
-  g_tg.prof_ms[TG_PROF_KSP_SPMV] += ems;
-  *iters = (int)h.out[0];
-  *resnorm = h.out[1];
-  *status = (int)h.out[3];
-  return 0;
+  // (Jacobi always: the polynomial is in D^-1 K)
+  tg_pc_args Q = {ps_args(k, b, x, 1, rtol, atol, maxit, nonzero_guess), m, theta, delta, nullptr, nullptr};
+  return ps_launch("Chebyshev-CG", fn, sizeof(pc_lds), d, &Q, Q.P, 2, 4 * (int64_t)d.G,
+                   [&](double *part) { Q.u2 = Q.P.u + Q.P.n; Q.psum = part; }, m, 2 * (int64_t)m, iters, resnorm, status);
 }
