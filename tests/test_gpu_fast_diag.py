@@ -88,6 +88,43 @@ def test_apply_matches_dense(d, p, nels, coef, scaling):
     assert np.linalg.norm(a - want) <= 1e-12 * np.linalg.norm(want)
 
 
+# relative 2-norm of B (K x) - x on the free dofs of _identity_case() with B evaluated by the float64 numpy reference of
+# tests/fd_reference.py and K x by scipy from K.to_scipy(): 1.02e-14 (9.8e-15 with the reference in longdouble; the kernel gave 7.7e-15 on an MI355X) (measured; the error is the conditioning of P, 2.4e3 by its
+# eigenvalue sums, times a few unit roundoffs, whatever evaluates B)
+IDENTITY_HOST_ERROR = 1.02e-14
+
+
+def _identity_case():
+    """unmapped Laplace, p = 3, 62 x 30 x 14 elements: free box 63 x 31 x 15, padded to 64 x 32 x 16 (all different, and
+    none the 16 x 16 x 16 of test_apply_matches_dense); P with coefficients (1, 1, 1, 0) is K on the free dofs"""
+    import tigar_amd as t
+    from tigar_amd.forms import LaplaceForm
+    gen, spline = _spline(3, 3, (62, 30, 14))
+    K = spline.assembleMatrix(LaplaceForm())
+    fd = t.FastDiagonalization(K, coefficients=(1.0, 1.0, 1.0, 0.0), scaling="none")
+    shape = K.tensor_structure.shape
+    assert shape == [65, 33, 17]
+    grid = np.arange(K.shape[0]).reshape(shape[::-1])
+    free = grid[1:-1, 1:-1, 1:-1].ravel()
+    x = np.zeros(K.shape[0])
+    x[free] = np.random.default_rng(12).standard_normal(free.size)
+    return K, fd, free, x
+
+
+def test_apply_inverts_k_on_a_noncubic_box():
+    from tigar_amd.device import DeviceVector
+    K, fd, free, x = _identity_case()
+    y = DeviceVector(K.shape[0])
+    K.mult(DeviceVector(data=x), y)
+    z = DeviceVector(data=np.full(K.shape[0], np.nan))
+    fd.apply(y, z)
+    z = z.get_local()
+    assert np.all(np.isfinite(z))
+    err = np.linalg.norm(z[free] - x[free]) / np.linalg.norm(x[free])
+    print("FD identity: kernel %.3g, 4 x host %.3g" % (err, 4 * IDENTITY_HOST_ERROR))
+    assert err <= 4 * IDENTITY_HOST_ERROR
+
+
 def _poisson(d, p, nel, pc, rtol):
     import tigar_amd as t
     from tigar_amd import forms as F

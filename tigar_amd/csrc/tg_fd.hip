@@ -408,16 +408,24 @@ extern "C" int tg_fd_set_coefficients(tg_fd_t fd, const double *coef, int scalin
   TG_REQUIRE_INIT();
   TG_REQUIRE(fd && coef, "tg_fd_set_coefficients: null argument");
   TG_REQUIRE(fd->fitted, "tg_fd_set_coefficients: tg_fd_fit (diagonal of K) must come first");
+  // every block's coefficients are checked before any is stored: a refusal leaves the previous set in force
+  for (size_t bi = 0; bi < fd->blocks.size(); bi++) {
+    const fd_block &b = fd->blocks[bi];
+    double top = coef[4 * bi + 3];
+    for (int a = 0; a < 4; a++) {
+      const double c = (a < b.d || a == 3) ? coef[4 * bi + a] : 0.0;
+      TG_REQUIRE(c >= 0.0 && c == c, "tg_fd_set_coefficients: negative or NaN coefficient");
+      if (a < b.d) top += c * b.lam_max[a];
+    }
+    TG_REQUIRE(top > 0.0, "tg_fd_set_coefficients: every coefficient is zero");
+  }
   if (!fd->sv) TG_TRY(tg_dmalloc(&fd->sv, fd->n));
+  fd->ready = false;                     // (until every block's sv is written again)
   for (size_t bi = 0; bi < fd->blocks.size(); bi++) {
     fd_block &b = fd->blocks[bi];
     double top = coef[4 * bi + 3];
-    for (int a = 0; a < 4; a++) {
-      b.coef[a] = (a < b.d || a == 3) ? coef[4 * bi + a] : 0.0;
-      TG_REQUIRE(b.coef[a] >= 0.0 && b.coef[a] == b.coef[a], "tg_fd_set_coefficients: negative or NaN coefficient");
-    }
+    for (int a = 0; a < 4; a++) b.coef[a] = (a < b.d || a == 3) ? coef[4 * bi + a] : 0.0;
     for (int k = 0; k < b.d; k++) top += b.coef[k] * b.lam_max[k];
-    TG_REQUIRE(top > 0.0, "tg_fd_set_coefficients: every coefficient is zero");
     b.floor = 1e-13 * top;
     const int64_t nb = b.N[0] * b.N[1] * b.N[2];
     hipLaunchKernelGGL(k_fd_scale, dim3(tg_grid_1d(nb, 256)), dim3(256), 0, g_tg.stream, fd->diag + b.off, fd_args(b), scaling,
