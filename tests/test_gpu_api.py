@@ -234,8 +234,9 @@ def test_extract_matrix_on_a_periodic_patch(T, nel, periodic):
     spline = t.ExtractedSpline(gen, 2 * p)
     A = F.LaplaceForm().assemble_matrix(spline.V)
     dev.prof_reset()
-    K = spline.extractMatrix(A, diag=1.5).to_scipy()
-    assert dev.prof_get(5)[1] > 0
+    Kd = spline.extractMatrix(A, diag=1.5)
+    K = Kd.to_scipy()
+    assert dev.prof_get(5)[1] > 0 and Kd.ptap_route == "kron"          # (the unwrap and the fold happen inside ptap_factored)
     Ko = O.extract_matrix(gen.M.to_scipy(), A.to_scipy(), list(spline.zeroDofs), diag=1.5)
     assert np.array_equal(K.indptr, Ko.indptr) and np.array_equal(K.indices, Ko.indices)
     assert abs(K - Ko).max() <= 1e-12 * abs(Ko).max()
@@ -280,8 +281,9 @@ def test_extract_matrix_on_a_doubly_periodic_2d_patch(T, p, nel, nfields):
     A.sort_indices()
     A.data = np.random.default_rng(p + nel).standard_normal(A.nnz)             # values arbitrary, non-symmetric
     dev.prof_reset()
-    K = spline.extractMatrix(A, diag=2.0).to_scipy()
-    assert dev.prof_get(5)[1] > 0
+    Kd = spline.extractMatrix(A, diag=2.0)
+    K = Kd.to_scipy()
+    assert dev.prof_get(5)[1] > 0 and Kd.ptap_route == "walks2d+fold"
     Ko = O.extract_matrix(gen.M.to_scipy(), A, list(spline.zeroDofs), diag=2.0)
     assert np.array_equal(K.indptr, Ko.indptr) and np.array_equal(K.indices, Ko.indices)
     assert abs(K - Ko).max() <= 1e-12 * abs(Ko).max()

@@ -81,8 +81,9 @@ def test_tspline_extract_matrix_takes_the_cell_block_product(monkeypatch):
     rng = np.random.default_rng(8)
     A = sp.block_diag([rng.standard_normal((16, 16)) for _ in range(6)], format="csr")
     M = gen.M.to_scipy()
-    K = spline.extractMatrix(A).to_scipy().tocsr()
-    assert spline.__dict__.get("_cell_plans", {}).get(16) is not None            # the plan was built and used
+    Kd = spline.extractMatrix(A)
+    K = Kd.to_scipy().tocsr()
+    assert Kd.ptap_route == "cells"                                              # the plan was built and used
     Ko = O.extract_matrix(M, A, [0, 1, 2, 29]).tocsr()
     K.sort_indices(), Ko.sort_indices()
     assert np.array_equal(K.indices, Ko.indices) and abs(K - Ko).max() <= 1e-12 * abs(Ko).max()
@@ -118,16 +119,16 @@ def test_cell_blocks_plus_couplings_outside_the_blocks(ncell, b, ncp, nextra, mo
     assert cell_size_with_extras(Ad) == b
     D, R = split_cells(Ad, b)
     assert abs(D.to_scipy() - A).max() == 0.0 and abs(R.to_scipy() - E).max() == 0.0
-    # through the API: an ExtractedSpline whose M is this cell-local operator
-    spline = t.ExtractedSpline.__new__(t.ExtractedSpline)
-    spline.M, spline.MT = DeviceCSR.from_scipy(M), DeviceCSR.from_scipy(M.T.tocsr())
-    spline.M._T = spline.MT
-    spline.nFields, spline.comm, spline._kron, spline._kron_scalar, spline._kron_fields = 1, tc.selfcomm, None, None, None
-    spline._ptap_plan = spline._ptap_plan_key = spline._slab = None
+    # through the routes extractMatrix walks, for this cell-local operator
+    from tigar_amd.ptaproutes import ResidentPtAP
+    Md, MTd = DeviceCSR.from_scipy(M), DeviceCSR.from_scipy(M.T.tocsr())
+    Md._T = MTd
+    routes = ResidentPtAP(Md, MTd, 1)
     zd = np.unique(rng.integers(0, ncp, size=5)).astype(np.int32)
-    spline.zeroDofs = zd
-    K = spline.extractMatrix(Ad, diag=3.0).to_scipy().tocsr()
-    assert spline.__dict__.get("_cellR_key") is not None               # the split path ran
+    extract = lambda X: routes.product(X, zd, 3.0)
+    Kd = extract(Ad)
+    K = Kd.to_scipy().tocsr()
+    assert Kd.ptap_route == "cells+extras"                             # the split path ran
     Ko = O.extract_matrix(M, Ax, list(zd), diag=3.0).tocsr()
     K.sort_indices(), Ko.sort_indices()
     assert np.array_equal(K.indptr, Ko.indptr) and np.array_equal(K.indices, Ko.indices)
@@ -135,10 +136,10 @@ def test_cell_blocks_plus_couplings_outside_the_blocks(ncell, b, ncp, nextra, mo
     # entries away from the penalty keep their own accuracy (the two parts are summed separately)
     small = abs(Ko.data) < 1e3
     assert np.max(np.abs(K.data[small] - Ko.data[small])) <= 1e-10 * max(1.0, np.max(np.abs(Ko.data[small])))
-    K2 = spline.extractMatrix(Ad, diag=3.0).to_scipy().tocsr()          # plans reused
+    K2 = extract(Ad).to_scipy().tocsr()          # plans reused
     assert np.array_equal(K2.data.view(np.int64), K.data.view(np.int64))
     monkeypatch.setenv("TIGAR_PTAP_CELLS", "0")
-    Kg = spline.extractMatrix(Ad, diag=3.0).to_scipy().tocsr()
+    Kg = extract(Ad).to_scipy().tocsr()
     Kg.sort_indices()
     assert np.array_equal(Kg.indices, K.indices) and abs(Kg - K).max() <= 1e-12 * abs(Ko).max()
     # a matrix whose cell blocks are incomplete is declined by the split and still extracted
@@ -148,7 +149,7 @@ def test_cell_blocks_plus_couplings_outside_the_blocks(ncell, b, ncp, nextra, mo
     A3 = A3.tocsr()
     A3.eliminate_zeros()
     assert split_cells(DeviceCSR.from_scipy(A3), b) is None
-    K3 = spline.extractMatrix(DeviceCSR.from_scipy(A3), diag=3.0).to_scipy().tocsr()
+    K3 = extract(DeviceCSR.from_scipy(A3)).to_scipy().tocsr()
     K3o = O.extract_matrix(M, A3, list(zd), diag=3.0).tocsr()
     K3.sort_indices(), K3o.sort_indices()
     assert np.array_equal(K3.indices, K3o.indices) and abs(K3 - K3o).max() <= 1e-12 * abs(K3o).max()

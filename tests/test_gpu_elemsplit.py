@@ -132,9 +132,9 @@ def test_extract_matrix_takes_the_element_split_product(monkeypatch, d, p, nel):
     A = F.LaplaceForm().assemble_matrix(spline.V).to_scipy().tocsr()
     rng = np.random.default_rng(p)
     A.data = A.data + 0.1 * rng.standard_normal(A.nnz)
-    K = spline.extractMatrix(A).to_scipy().tocsr()
-    plan = spline.__dict__.get("_elem_plan")
-    assert plan is not None and plan[1] is not None and plan[1]._chunk is not None          # the element path ran
+    Kd = spline.extractMatrix(A)
+    K = Kd.to_scipy().tocsr()
+    assert Kd.ptap_route == "elements"                                                      # the element path ran
     M = gen.M.to_scipy()
     ref = (M.T @ A @ M).tolil()
     zd = np.asarray(gen.zeroDofsArray(), dtype=np.int64)
@@ -152,7 +152,9 @@ def test_extract_matrix_takes_the_element_split_product(monkeypatch, d, p, nel):
         P = sp.kron(C1, P, format="csr")
     Bm = P.astype(np.float64).tocsr()
     Bm.data = rng.standard_normal(Bm.nnz)
-    K2 = spline.extractMatrix(Bm).to_scipy().tocsr()
+    K2d = spline.extractMatrix(Bm)
+    K2 = K2d.to_scipy().tocsr()
+    assert K2d.ptap_route == "general"
     ref2 = (M.T @ Bm @ M).tolil()
     ref2[zd, :] = 0.0
     ref2[:, zd] = 0.0

@@ -238,19 +238,23 @@ def test_several_fields_on_one_basis_go_block_by_block(p, nels, nF):
     Mo = O.generate_M_tensor(s, nfields=nF)
     zd = list(spline.zeroDofs)
     Ko = O.extract_matrix(Mo, A, zd, diag=3.0)
-    calls = []
-    orig = spline._extract_matrix_by_field_blocks
-    spline._extract_matrix_by_field_blocks = lambda *a, **k: (calls.append(1), orig(*a, **k))[1]
-    K = spline.extractMatrix(A, diag=3.0).to_scipy()
-    assert calls == [1]
+    Kd = spline.extractMatrix(A, diag=3.0)
+    K = Kd.to_scipy()
+    uncoupled = ((0, 2), (2, 0)) if nF == 3 else ()
+    clean = [["empty" if (i, j) in uncoupled else "walks3d" for j in range(nF)] for i in range(nF)]
+    assert Kd.ptap_route == "field-blocks" and Kd.ptap_block_routes == clean
     assert np.array_equal(K.indptr, Ko.indptr) and np.array_equal(K.indices, Ko.indices)
     assert np.max(np.abs(K.data - Ko.data)) <= 1e-13 * np.max(np.abs(Ko.data))
-    assert np.array_equal(spline.extractMatrix(A, diag=3.0).to_scipy().data, K.data)      # bit-reproducible
+    Kd2 = spline.extractMatrix(A, diag=3.0)
+    assert Kd2.ptap_route == "field-blocks" and np.array_equal(Kd2.to_scipy().data, K.data)      # bit-reproducible
     os.environ["TIGAR_PTAP_FACTORED"] = "0"
     try:
-        Kg = spline.extractMatrix(A, diag=3.0).to_scipy()
+        Kgd = spline.extractMatrix(A, diag=3.0)
+        Kg = Kgd.to_scipy()
     finally:
         del os.environ["TIGAR_PTAP_FACTORED"]
+    # (the element split is left to systems of 20000 FE rows and more, and asks for one field)
+    assert Kgd.ptap_route == "general"
     assert np.array_equal(Kg.indptr, K.indptr) and np.array_equal(Kg.indices, K.indices)
     assert np.max(np.abs(Kg.data - K.data)) <= 1e-12 * np.max(np.abs(K.data))
     # a block without the element-coupling pattern is multiplied by the general kernels -- that block alone, on the
@@ -260,11 +264,15 @@ def test_several_fields_on_one_basis_go_block_by_block(p, nels, nF):
     Ar = Ar.tocsr()
     Ar.sort_indices()
     Kro = O.extract_matrix(Mo, Ar, zd, diag=3.0)
-    Kr = spline.extractMatrix(Ar, diag=3.0).to_scipy()
-    assert calls == [1, 1, 1]
+    Krd = spline.extractMatrix(Ar, diag=3.0)
+    Kr = Krd.to_scipy()
+    # (the hand-added entry lies in block (0, nF - 1): declined by the walks, taken by the Kronecker stages)
+    assert Krd.ptap_route == "field-blocks" and Krd.ptap_block_routes[0][nF - 1] == "kron"
+    assert [[h for j, h in enumerate(row) if (i, j) != (0, nF - 1)] for i, row in enumerate(Krd.ptap_block_routes)] == \
+        [[h for j, h in enumerate(row) if (i, j) != (0, nF - 1)] for i, row in enumerate(clean)]
     assert np.array_equal(Kr.indptr, Kro.indptr) and np.array_equal(Kr.indices, Kro.indices)
     assert np.max(np.abs(Kr.data - Kro.data)) <= 1e-12 * np.max(np.abs(Kro.data))
-    Kb = orig(dev.DeviceCSR.from_scipy(A), np.asarray(zd), 3.0, False).to_scipy()
+    Kb = spline._ptap.field_blocks(dev.DeviceCSR.from_scipy(A), np.asarray(zd), 3.0, tensor=False).to_scipy()
     assert np.array_equal(Kb.indices, K.indices) and np.max(np.abs(Kb.data - K.data)) <= 1e-12 * np.max(np.abs(K.data))
 
 
@@ -596,8 +604,10 @@ def test_extract_matrix_on_a_compatible_spline_takes_the_pair_walks(degs, nels, 
     A = F.ElasticityForm(1.3, 0.7).assemble_matrix(spline.V)
     zd = [int(i) for i in gen.zeroDofsArray()]
     dev.prof_reset()
-    K = spline.extractMatrix(A, diag=2.5).to_scipy()
+    Kd = spline.extractMatrix(A, diag=2.5)
+    K = Kd.to_scipy()
     assert dev.prof_get(5)[1] == 9                       # nine blocks, nine final passes of the walks
+    assert Kd.ptap_route == "field-list" and Kd.ptap_block_routes == [["walks3d"] * 3] * 3
     Kr = O.extract_matrix(Mo, A.to_scipy(), zd, diag=2.5)
     assert np.array_equal(K.indptr, Kr.indptr) and np.array_equal(K.indices, Kr.indices)
     assert abs(K - Kr).max() <= 1e-12 * abs(Kr).max()
@@ -605,7 +615,11 @@ def test_extract_matrix_on_a_compatible_spline_takes_the_pair_walks(degs, nels, 
     Ah = A.to_scipy().tolil()
     Ah[3, Ah.shape[1] - 5] = 0.25
     Ah = Ah.tocsr()
-    K2 = spline.extractMatrix(Ah, diag=2.5).to_scipy()
+    K2d = spline.extractMatrix(Ah, diag=2.5)
+    K2 = K2d.to_scipy()
+    # (row 3 belongs to field 0, column n - 5 to field 2: that block alone)
+    assert K2d.ptap_route == "field-list" and K2d.ptap_block_routes == \
+        [["walks3d", "walks3d", "general"], ["walks3d"] * 3, ["walks3d"] * 3]
     K2r = O.extract_matrix(Mo, Ah, zd, diag=2.5)
     assert np.array_equal(K2.indptr, K2r.indptr) and np.array_equal(K2.indices, K2r.indices)
     assert abs(K2 - K2r).max() <= 1e-12 * abs(K2r).max()
@@ -704,8 +718,10 @@ def test_extract_matrix_on_a_2d_compatible_spline_takes_the_pair_walks(degs, nel
     A = sps.bmat(blk, format="csr")
     zd = [int(i) for i in gen.zeroDofsArray()]
     dev.prof_reset()
-    K = spline.extractMatrix(A, diag=2.5).to_scipy()
+    Kd = spline.extractMatrix(A, diag=2.5)
+    K = Kd.to_scipy()
     assert dev.prof_get(5)[1] == 4                       # four blocks, four final passes of the walks
+    assert Kd.ptap_route == "field-list" and Kd.ptap_block_routes == [["walks2d"] * 2] * 2
     Kr = O.extract_matrix(Mo, A, zd, diag=2.5)
     assert np.array_equal(K.indptr, Kr.indptr) and np.array_equal(K.indices, Kr.indices)
     assert abs(K - Kr).max() <= 1e-12 * abs(Kr).max()

@@ -1515,7 +1515,7 @@ class ExtractedSpline(object):
         if self.M_control.shape != (self.V_control.dim(), ncp_control) or self.M.shape != (self.V.dim(), sum(ncp)):
             raise ValueError("extraction matrices in %s do not match extraction-info.txt" % dirname)
         self.zeroDofs = numpy.asarray(petscio.read_is(os.path.join(dirname, EXTRACTION_ZERO_DOFS_FILE)), dtype=INDEX_TYPE)
-        self._kron = None
+        self._kron = self._kron_scalar = self._kron_fields = None       # (M read from files: an arbitrary sparse matrix)
 
     def initFromGenerator(self, generator, quadDeg, doPermutation=DEFAULT_DO_PERMUTATION):
         """tIGAr/common.py:708-746 -- shares M, M_control, V, cpFuncs with the generator."""
@@ -1544,9 +1544,14 @@ class ExtractedSpline(object):
     def genericSetup(self):
         self.setSolverOptions()
         self.MT = self.M.transpose()          # explicit M^T (cached on M by the generator)
-        self._ptap_plan = None
-        self._ptap_plan_key = None
         self._slab = None
+        import weakref
+        from .ptaproutes import ResidentPtAP
+        me = weakref.proxy(self)              # (no reference cycle: what the spline holds on the device goes with its last user)
+        self._ptap = ResidentPtAP(self.M, self.MT, self.nFields, self._kron, self._kron_scalar, self._kron_fields,
+                                  grids=getattr(self.V, "grids", None), distributed=self._distributed(),
+                                  slab=lambda: me._slab_path(), row_blocks=self._row_blocks_of,
+                                  field_blocks=lambda A: me._block_producer(A), timers=lambda: getattr(me, "stage_timers", None))
 
     # -- streamed / distributed engine -------------------------------------------------------------
     def _implicit(self):
@@ -1561,31 +1566,24 @@ class ExtractedSpline(object):
         sub-slabs of dof planes, only K resident (PETSc's row-block MatPtAP, tIGAr/common.py:1194-1195)."""
         if self._slab is None and getattr(self, "_generator_engine", None) is not None and self.nFields == 1:
             self._slab = self._generator_engine
-        if self._slab is None and self._kron is None and getattr(self, "_kron_scalar", None) is not None:
-            # several fields on one tensor basis: the scalar engine per block, fields interleaved plane by plane
-            from .dist import FieldSlabPath
-            kx = self._kron_scalar
-            dc = self.comm.device() if self._distributed() else None
-            self._slab = FieldSlabPath(kx.basis, kx.grid, self.nFields, self.comm.rank if dc is not None else 0,
-                                       self.comm.size if dc is not None else 1, dc, sub_planes="auto",
-                                       eps=getattr(self.M, "eps", DEFAULT_BASIS_FUNC_IGNORE_EPS), kx=kx)
-        if self._slab is None and self._kron is None and getattr(self, "_kron_fields", None) is not None:
-            # fields on different tensor bases over one node grid: one split of the plane index, pair walks per block
-            from .dist import FieldListSlabPath
-            dc = self.comm.device() if self._distributed() else None
-            self._slab = FieldListSlabPath(self._kron_fields, self.comm.rank if dc is not None else 0,
-                                           self.comm.size if dc is not None else 1, dc, sub_planes="auto",
-                                           eps=getattr(self.M, "eps", DEFAULT_BASIS_FUNC_IGNORE_EPS))
         if self._slab is None:
-            if self._kron is None:
+            from .dist import FieldListSlabPath, FieldSlabPath, SlabHotPath
+            dc = self.comm.device() if self._distributed() else None
+            rank, world = (self.comm.rank, self.comm.size) if dc is not None else (0, 1)
+            eps = getattr(self.M, "eps", DEFAULT_BASIS_FUNC_IGNORE_EPS)
+            kx = self._kron if self._kron is not None else self._kron_scalar
+            if kx is not None:
+                # one field: the scalar engine; several fields on one tensor basis: the scalar engine per block, fields
+                # interleaved plane by plane
+                self._slab = SlabHotPath(kx.basis, kx.grid, rank, world, dc, sub_planes="auto", eps=eps, kx=kx) \
+                    if self._kron is not None else \
+                    FieldSlabPath(kx.basis, kx.grid, self.nFields, rank, world, dc, sub_planes="auto", eps=eps, kx=kx)
+            elif self._kron_fields is not None:
+                # fields on different tensor bases over one node grid: one split of the plane index, pair walks per block
+                self._slab = FieldListSlabPath(self._kron_fields, rank, world, dc, sub_planes="auto", eps=eps)
+            else:
                 raise NotImplementedError("the streamed / multi-GPU path needs tensor-product B-spline fields (one basis, or "
                                           "several bases over one node grid)")
-            from .dist import SlabHotPath
-            kx = self._kron
-            dc = self.comm.device() if self._distributed() else None
-            self._slab = SlabHotPath(kx.basis, kx.grid, self.comm.rank if dc is not None else 0,
-                                     self.comm.size if dc is not None else 1, dc, sub_planes="auto",
-                                     eps=getattr(self.M, "eps", DEFAULT_BASIS_FUNC_IGNORE_EPS), kx=kx)
         return self._slab
 
     def localDofRange(self):
@@ -1680,9 +1678,9 @@ class ExtractedSpline(object):
         if perm is not None and numpy.asarray(perm).size and \
                 not numpy.array_equal(numpy.asarray(perm), numpy.arange(numpy.asarray(perm).size)):
             return None, "a dof permutation was applied to the generator (the dofs are no longer numbered as a tensor grid)"
-        if getattr(self, "_kron_fields", None) is not None and self._kron is None:
+        if self._kron_fields is not None and self._kron is None:
             return None, "fields on different bases (FieldListSpline / compatible spaces) are not supported"
-        kx = self._kron if self._kron is not None else getattr(self, "_kron_scalar", None)
+        kx = self._kron if self._kron is not None else self._kron_scalar
         if kx is None:
             return None, ("the extraction operator is not the Kronecker product of 1-D B-spline factors (not a single "
                           "tensor-product patch)")
@@ -1696,171 +1694,8 @@ class ExtractedSpline(object):
         return TensorStructure(kx, nf, self.zeroDofs if applyBCs else None, cache), None
 
     def _extract_matrix(self, A, applyBCs=True, diag=1):
-        from .implicit import LazyFEMatrix
-        zd = self.zeroDofs if applyBCs else None
-        if isinstance(A, LazyFEMatrix) or self._distributed() or (self._implicit() and self.nFields > 1):
-            # (several fields with an implicit operator, also on one rank: the field-block engine and its plane-wise
-            #  numbering -- the same guard as extractVector / solveLinearSystem, so that K, M^T b and U share it;
-            #  an explicit A -- FEtoIGA's identity, an uploaded matrix -- is cut into the blocks the engine asks for)
-            a_fac = None
-            if self.nFields > 1 and self._kron is None and (getattr(self, "_kron_scalar", None) is not None or
-                                                            getattr(self, "_kron_fields", None) is not None):
-                return self._slab_path().assemble_matrix(self._block_producer(A), zd, float(diag),
-                                                         getattr(self, "stage_timers", None),
-                                                         block_factors=getattr(A, "block_factors", None))
-            if isinstance(A, LazyFEMatrix):
-                a_rows = A.rows
-                a_fac = A.kron_factors
-            else:
-                # an assembled FE matrix handed to every rank (the reference's A is a distributed PETSc matrix whose
-                # rows MatPtAP redistributes, tIGAr/common.py:1194-1195): every rank cuts the row blocks of its slab out
-                # of its copy -- on the device when it is a DeviceCSR, on the host (then uploaded) when it is scipy
-                a_rows = self._row_blocks_of(A)
-            return self._slab_path().assemble_matrix(a_rows, zd, float(diag), getattr(self, "stage_timers", None),
-                                                     a_factors=a_fac)
-        A = _as_device_csr(A)
-        by_blocks = self._kron is None and getattr(self, "_kron_scalar", None) is not None
-        # 2-D tensor patches (one or several fields on one basis): the whole product in two line-walk passes when A
-        # carries the element-coupling pattern (verified on the device; csrc/tg_tensor_body.h)
-        kx2 = self._kron if self._kron is not None else getattr(self, "_kron_scalar", None)
-        if kx2 is not None and kx2.d == 2 and not A.is_loose() and os.environ.get("TIGAR_PTAP_FACTORED", "1") != "0":
-            from .tensorptap import TensorPtAP2D
-            nF2 = self.nFields if by_blocks else 1
-            plan2 = TensorPtAP2D.for_extraction(kx2, nF2)
-            if plan2 is not None:
-                K = plan2.ptap(A, zd, float(diag))
-                if K is not None:
-                    return K
-            elif os.environ.get("TIGAR_PTAP_UNWRAP", "1") != "0":
-                # periodic directions (tIGAr/BSplines.py:204-212): the walks on the space before the wrapped functions
-                # are identified, then K = R^T K_u R (kronptap.KronExtraction.unwrapped / fold)
-                ku2 = kx2.unwrapped()
-                plan2 = TensorPtAP2D.for_extraction(ku2, nF2) if ku2 is not None else None
-                K_u = plan2.ptap(A, None, 1.0) if plan2 is not None else None
-                if K_u is not None:
-                    return ku2.fold(K_u, zd, float(diag), nfields=nF2)
-        if by_blocks and os.environ.get("TIGAR_PTAP_FACTORED", "1") != "0":
-            K = self._extract_matrix_by_field_blocks(A, zd, float(diag))
-            if K is not None:
-                return K
-        if self._kron is None and not by_blocks and getattr(self, "_kron_fields", None) is not None and \
-                os.environ.get("TIGAR_PTAP_FACTORED", "1") != "0":
-            K = self._extract_matrix_by_field_list(A, zd, float(diag))
-            if K is not None:
-                return K
-        if self._kron is not None:
-            from .kronptap import default_groups, ptap_factored
-            kx = self._kron
-            groups = default_groups(kx.d, max(s1.p for s1 in kx.basis.splines))
-            if os.environ.get("TIGAR_PTAP_FACTORED", "1") != "0":
-                # Kronecker-structured M: dense-box kernel (one stage or sum-factorised stages)
-                stored = None if self._implicit() else (self.M, self.MT)
-                return ptap_factored(kx, A, (0, kx.nfe[-1]), (0, kx.nfe[-1]), (0, kx.ncp[-1]), zd, float(diag), groups,
-                                     stored=stored)
-        if self._implicit():
-            # an implicit operator that is not to be used as a Kronecker product (TIGAR_PTAP_FACTORED=0) with an assembled A: the
-            # streamed engine materialises M chunk by chunk and takes its general stages -- element chunks, or the row-wise
-            # kernels for a matrix they decline (round 6; until then: NotImplementedError)
-            return self._slab_path().assemble_matrix(self._row_blocks_of(A), zd, float(diag), getattr(self, "stage_timers", None))
-        # cell-local FE spaces (T-splines, multi-patch B-splines: meshes of disconnected cells): an assembled A is block
-        # diagonal with one dense block per cell and the product is a sum of small dense triple products
-        # (tigar_amd/cellptap.py); the plan depends on M only and is kept, A is verified on the device at every call
-        if os.environ.get("TIGAR_PTAP_CELLS", "1") != "0":
-            from .cellptap import CellBlockPtAP, block_size_of, cell_size_with_extras, split_cells
-            b = block_size_of(A)
-            extras = False
-            if not b:
-                b = cell_size_with_extras(A)
-                extras = bool(b)
-            if b and A.shape[0] == self.M.shape[0]:
-                plans = self.__dict__.setdefault("_cell_plans", {})
-                if b not in plans:
-                    try:
-                        plans[b] = CellBlockPtAP(self.M, b)
-                    except ValueError:
-                        plans[b] = None
-                if plans[b] is not None and not extras:
-                    K = plans[b].ptap(A, zd, float(diag))
-                    if K is not None:
-                        return K
-                elif plans[b] is not None:
-                    # couplings outside the cell blocks (contact / penalty terms added by hand: the reason extractMatrix takes
-                    # any A, tIGAr/common.py:1175; demos/kl-shell-svk/reef-knot.py:455-467): A = D + R on the device, the
-                    # dense blocks D through the cell-block product, the few entries of R through the general kernels, the
-                    # two added on the union of their patterns (= the structural product of A), then MatZeroRowsColumns
-                    parts = plans[b].ptap_extras(A)
-                    if parts is not None:
-                        KD, R = parts
-                        if KD is not None:
-                            from .cellptap import remainder_product
-                            KR = remainder_product(R, self.M, self.__dict__.setdefault("_cellR_cache", {}))
-                            self._cellR_key = ("cells-R", R.shape, R.nnz)
-                            if KR is None:
-                                KR = DeviceCSR.from_scipy(_scipy_zero(KD.shape))
-                            K = KD.add(KR)
-                            del KD, KR
-                            if zd is not None and len(zd):
-                                K.zero_rows_cols(numpy.asarray(zd, dtype=numpy.int32), float(diag))
-                            return K
-        # connected meshes (what dolfin assembles on the Q_p / P_p mesh of the extraction, with an M that is used as a general
-        # CSR matrix): A split into one dense block per cell, then the same dense cell products (tigar_amd/elemptap.py)
-        if os.environ.get("TIGAR_PTAP_ELEMENTS", "1") != "0" and not A.is_loose():
-            K = self._extract_matrix_by_elements(A, zd, float(diag))
-            if K is not None:
-                return K
-        key = (A.shape, A.nnz)
-        fresh = self._ptap_plan is None or self._ptap_plan_key != key
-        if fresh:
-            self._ptap_plan = _dev.ptap_symbolic(A, self.M, self.MT)
-            self._ptap_plan_key = key
-        try:
-            return _dev.ptap_numeric(self._ptap_plan, A, self.M, self.MT, zd, float(diag))
-        except _dev.TigarHipError:
-            if fresh and by_blocks:
-                # rows of the whole product beyond the general kernels' per-row tables (three fields at p = 3 in 3-D):
-                # the same kernels block by block, on the scalar operands
-                self._ptap_plan = self._ptap_plan_key = None
-                K = self._extract_matrix_by_field_blocks(A, zd, float(diag), tensor=False)
-                if K is not None:
-                    return K
-            if fresh:
-                raise
-            # same shape and nnz but another sparsity pattern than the cached plan's: the reference
-            # recomputes the symbolic product on every call (tIGAr/common.py:1194-1195) -- plan again
-            self._ptap_plan = _dev.ptap_symbolic(A, self.M, self.MT)
-            return _dev.ptap_numeric(self._ptap_plan, A, self.M, self.MT, zd, float(diag))
-
-    def _extract_matrix_by_elements(self, A, zd, diag):
-        """M^T A M by the element-split cell-block product, or None when it does not apply: one field on one mesh whose cells
-        hold at most 125 nodes (the cells' node lists are the dofmap of ``self.V``), a system large enough for the plan to pay
-        (``TIGAR_PTAP_ELEMENTS=2``: any size), every entry of A between nodes of a common cell (any assembled FE matrix;
-        others fall through to the general kernels)"""
-        grids = getattr(getattr(self, "V", None), "grids", None)
-        if self.nFields != 1 or not grids or len(grids) != 1 or A.shape != (self.M.shape[0], self.M.shape[0]):
-            return None
-        plan = self.__dict__.get("_elem_plan")
-        if plan is None or plan[0] is not self.M:
-            plan = (self.M, self._element_plan_for(self.M))
-            self.__dict__["_elem_plan"] = plan
-        if plan[1] is None:
-            return None
-        return plan[1].ptap(A, zd, diag)
-
-    def _element_plan_for(self, M):
-        """ElementSplitPtAP for the scalar extraction operator ``M`` on the (first) mesh of the FE space, or None"""
-        if os.environ.get("TIGAR_PTAP_ELEMENTS", "1") == "0":
-            return None
-        grids = getattr(getattr(self, "V", None), "grids", None)
-        if not grids or (M.shape[0] < 20000 and os.environ.get("TIGAR_PTAP_ELEMENTS", "1") != "2"):
-            return None
-        g = grids[0]
-        if (int(g.degree) + 1) ** g.dim() > 125 or int(g.degree) < 1 or getattr(g, "dg", False) or g.num_nodes() != M.shape[0]:
-            return None
-        from .elemptap import ElementSplitPtAP, CellNodes
-        try:
-            return ElementSplitPtAP(M, CellNodes.from_grid(g))       # (the dofmap of V, generated on the device)
-        except (ValueError, _dev.TigarHipError):
-            return None
+        """which product forms M^T A M: ``tigar_amd.ptaproutes.ResidentPtAP`` (one ordered table of routes)"""
+        return self._ptap.product(A, self.zeroDofs if applyBCs else None, diag)
 
     def _block_producer(self, A):
         """``a_block(f, g, r0, r1)`` for the field-block engine: rows [r0, r1) of block (f, g) of an FE matrix on the mixed
@@ -1887,152 +1722,6 @@ class ExtractedSpline(object):
             raise TypeError("extractMatrix: a DeviceCSR, a scipy sparse matrix or a LazyFEMatrix is expected")
         Ah = _sp.csr_matrix(A)
         return lambda r0, r1: DeviceCSR.from_scipy(Ah[int(r0):int(r1)])
-
-    def _extract_matrix_by_field_blocks(self, A, zd, diag, tensor=True):
-        """M^T A M for several fields on one tensor basis (M = diag(M_s, ..., M_s), dofs field after field): block
-        (i, j) of the result is M_s^T A_ij M_s, computed on the block cut out of A -- by the scalar tensor-pattern
-        passes (csrc/tg_tensor_body.h) where the patch and the block qualify, by the general kernels on the scalar
-        operands otherwise (whose per-row tables hold a scalar row's intermediate, not that of nFields of them).  The
-        blocks are put together and MatZeroRowsColumns is applied to the whole (tIGAr/common.py:1194-1200).  None
-        when A is not a matrix on this mixed space."""
-        from .tensorptap import TensorPtAP
-        kx = self._kron_scalar
-        plan = TensorPtAP.for_extraction(kx) if tensor else None
-        nF = self.nFields
-        nfe = int(numpy.prod(kx.nfe, dtype=numpy.int64))
-        ncp = int(numpy.prod(kx.ncp, dtype=numpy.int64))
-        if A.shape != (nF * nfe, nF * nfe):
-            return None
-        nz, kz = int(kx.nfe[-1]), int(kx.ncp[-1])
-        # FE planes per call of the x / y passes: their first intermediate is about 2.5 x the block's own bytes
-        step = max(kx.basis.splines[-1].p, min(nz, int(2.0e10 // max(1.0, 12.0 * 2.5 * (A.nnz / float(nF * nF)) / nz))))
-        scalar = {}
-
-        def general(Aij):
-            if tensor:
-                # the scalar machinery for a Kronecker M: pattern split (entries outside the element-coupling pattern
-                # apart), else the general line kernels
-                from .kronptap import default_groups, ptap_factored
-                groups = default_groups(kx.d, max(s1.p for s1 in kx.basis.splines))
-                return ptap_factored(kx, Aij, (0, nz), (0, nz), (0, kz), None, 1.0, groups)
-            if not scalar:
-                scalar["M"] = self.M.block(0, nfe, 0, ncp)
-                scalar["MT"] = scalar["M"].transpose()
-                scalar["elem"] = self._element_plan_for(scalar["M"])
-            if scalar["elem"] is not None and not Aij.is_loose():
-                # (every block of an assembled matrix on the mixed space couples nodes of common cells of the scalar mesh)
-                Kij = scalar["elem"].ptap(Aij, None, 1.0)
-                if Kij is not None:
-                    return Kij
-            return _dev.ptap_numeric(_dev.ptap_symbolic(Aij, scalar["M"], scalar["MT"]), Aij, scalar["M"], scalar["MT"])
-
-        blocks = []
-        for i in range(nF):
-            row = []
-            for j in range(nF):
-                Aij = A.block(i * nfe, (i + 1) * nfe, j * nfe, (j + 1) * nfe)
-                Kij = None
-                if Aij.nnz == 0:
-                    # fields i and j are not coupled by this form: no entries in this block of the product either
-                    import scipy.sparse as _sp
-                    Kij = DeviceCSR.from_scipy(_sp.csr_matrix((ncp, ncp)))
-                elif plan is not None:
-                    pieces = []
-                    for z0 in range(0, nz, step):
-                        pc = plan.planes(Aij, 0, z0, min(nz, z0 + step))
-                        if pc is None:
-                            pieces = None
-                            break
-                        pieces.append(pc)
-                    if pieces is not None:
-                        Kij = plan.zstage(pieces, 0, kz)
-                    del pieces
-                if Kij is None:
-                    Kij = general(Aij)
-                row.append(Kij)
-                del Aij
-            blocks.append(row)
-        K = _dev.csr_from_blocks(blocks)
-        del blocks
-        if zd is not None and len(zd):
-            K.zero_rows_cols(numpy.asarray(zd, dtype=numpy.int32), diag)
-        return K
-
-    def _extract_matrix_by_field_list(self, A, zd, diag):
-        """M^T A M for fields on DIFFERENT tensor bases (M = diag(M_f)): block (f, g) = M_f^T A_fg M_g by the line walks with
-        separate row- and column-side weights where the pair qualifies (all fields on one Q_P node grid, degrees <= 3 in 3-D:
-        ``TensorPtAP.for_pair``, <= 4 in 2-D: ``TensorPtAP2D.for_pair``; csrc/tg_tensor_body.h), by the general kernels on the
-        scalar operands otherwise; the
-        blocks are put together and MatZeroRowsColumns is applied to the whole (tIGAr/common.py:1194-1200).  None when A
-        is not a matrix on this mixed space."""
-        from .tensorptap import TensorPtAP
-        kxs = self._kron_fields
-        nF = self.nFields
-        nfe = [int(numpy.prod(kx.nfe, dtype=numpy.int64)) for kx in kxs]
-        ncp = [int(numpy.prod(kx.ncp, dtype=numpy.int64)) for kx in kxs]
-        fo, co = numpy.concatenate([[0], numpy.cumsum(nfe)]), numpy.concatenate([[0], numpy.cumsum(ncp)])
-        if A.shape != (int(fo[-1]), int(fo[-1])):
-            return None
-        scalar = {}
-
-        def general(f, g, Aij):
-            import scipy.sparse as _sp
-            for q in (f, g):
-                if q not in scalar:
-                    Mq = self.M.block(int(fo[q]), int(fo[q + 1]), int(co[q]), int(co[q + 1]))
-                    scalar[q] = (Mq, Mq.transpose())
-            if f == g:
-                return _dev.ptap_numeric(_dev.ptap_symbolic(Aij, scalar[f][0], scalar[f][1]), Aij, scalar[f][0], scalar[f][1])
-            # the general kernels form P^T A P with ONE operator: block (0, 1) of the product on the two-field space
-            # diag(M_f, M_g) with A_fg as its only non-zero block
-            def zero(r, cc):
-                return DeviceCSR.from_scipy(_sp.csr_matrix((int(r), int(cc))))
-            Mp = _dev.csr_from_blocks([[scalar[f][0], zero(nfe[f], ncp[g])], [zero(nfe[g], ncp[f]), scalar[g][0]]])
-            Ap = _dev.csr_from_blocks([[zero(nfe[f], nfe[f]), Aij], [zero(nfe[g], nfe[f]), zero(nfe[g], nfe[g])]])
-            MpT = Mp.transpose()
-            Kp = _dev.ptap_numeric(_dev.ptap_symbolic(Ap, Mp, MpT), Ap, Mp, MpT)
-            return Kp.block(0, ncp[f], ncp[f], ncp[f] + ncp[g])
-
-        blocks = []
-        for f in range(nF):
-            row = []
-            for g in range(nF):
-                Aij = A.block(int(fo[f]), int(fo[f + 1]), int(fo[g]), int(fo[g + 1]))
-                Kij = None
-                if Aij.nnz == 0:
-                    import scipy.sparse as _sp
-                    Kij = DeviceCSR.from_scipy(_sp.csr_matrix((ncp[f], ncp[g])))
-                else:
-                    plan = TensorPtAP.for_pair(kxs[f], kxs[g]) if (kxs[f].d == 3 and not Aij.is_loose()) else None
-                    if plan is not None:
-                        nz, kz = int(kxs[f].nfe[-1]), int(kxs[f].ncp[-1])
-                        step = max(int(kxs[f].grid.degree), min(nz, int(2.0e10 // max(1.0, 12.0 * 2.5 * Aij.nnz / nz))))
-                        pieces = []
-                        for z0 in range(0, nz, step):
-                            pc = plan.planes(Aij, 0, z0, min(nz, z0 + step))
-                            if pc is None:
-                                pieces = None
-                                break
-                            pieces.append(pc)
-                        if pieces is not None:
-                            Kij = plan.zstage(pieces, 0, kz)
-                        del pieces
-                    if Kij is None and kxs[f].d == 2 and not Aij.is_loose():
-                        # 2-D compatible splines (demos/taylor-green/taylor-green-2d.py): the block in two walks
-                        from .tensorptap import TensorPtAP2D
-                        plan2 = TensorPtAP2D.for_pair(kxs[f], kxs[g])
-                        if plan2 is not None:
-                            Kij = plan2.ptap(Aij)
-                    if Kij is None:
-                        Kij = general(f, g, Aij)
-                row.append(Kij)
-                del Aij
-            blocks.append(row)
-        K = _dev.csr_from_blocks(blocks)
-        del blocks
-        if zd is not None and len(zd):
-            K.zero_rows_cols(numpy.asarray(zd, dtype=numpy.int32), diag)
-        return K
 
     def assembleMatrix(self, form, applyBCs=True, diag=1):
         """tIGAr/common.py:1206-1220.  When the assembled FE matrix cannot be resident next to K (implicit
@@ -2324,11 +2013,6 @@ class ExtractedSpline(object):
             raise RuntimeError("Nonlinear solver failed to converge.")
         return history
 
-
-
-def _scipy_zero(shape):
-    import scipy.sparse as _sp
-    return _sp.csr_matrix((int(shape[0]), int(shape[1])))
 
 
 def _scipy_identity(n):

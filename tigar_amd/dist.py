@@ -232,13 +232,10 @@ class SlabHotPath(object):
         # sum-factorised PtAP when M is exactly a Kronecker product (checked against the
         # closed-form nnz of M on the tensor grid); TIGAR_PTAP_FACTORED=0/1 overrides
         env = os.environ.get("TIGAR_PTAP_FACTORED")
-        from .kronptap import default_groups
+        from .kronptap import default_groups, parse_direction_groups
         self.groups = default_groups(basis.nvar, max(s1.p for s1 in basis.splines))
         if env is not None and env not in ("0", "1"):           # e.g. TIGAR_PTAP_FACTORED=0,1;2 or 0;1;2
-            g_env = [[int(c) for c in g.split(",") if int(c) < basis.nvar] for g in env.split(";")]
-            g_env = [g for g in g_env if g]
-            if sorted(sum(g_env, [])) == list(range(basis.nvar)):
-                self.groups = g_env
+            self.groups = parse_direction_groups(env, basis.nvar, False) or self.groups
         if factored is True and len(self.groups) == 1:
             self.groups = [[k] for k in range(basis.nvar)]
         explicit = env is not None and env not in ("0", "1")
@@ -333,18 +330,13 @@ class SlabHotPath(object):
         subs = self.sub_slabs()
         # tensor-pattern fast path (csrc/tg_tensor_body.h): the plane-local passes give dense B2 planes that are
         # kept in the ring, the z pass writes the rows of K at closed-form positions (exact capacity known)
-        from .tensorptap import TensorPtAP
-        tplan = TensorPtAP.for_extraction(self.kx) if (self.factored and self.kron_exact and not getattr(
-            self, "_tensor_declined", False)) else None
         # directions other than the slab direction that wrap (periodic, tIGAr/BSplines.py:204-212): the walks on the
         # unwrapped space, this rank's rows of K_u folded at the end (kronptap.KronExtraction.unwrapped / fold)
-        fold = None
-        if tplan is None and self.factored and self.kron_exact and not getattr(self, "_tensor_declined", False) \
-                and os.environ.get("TIGAR_PTAP_UNWRAP", "1") != "0":
-            ku = self.kx.unwrapped()
-            if ku is not None and np.array_equal(ku.fold_maps[-1], np.arange(ku.ncp[-1])):
-                tplan = TensorPtAP.for_extraction(ku)
-                fold = ku if tplan is not None else None
+        from .tensorptap import TensorPtAP, plan_or_unwrapped
+        tplan = fold = None
+        if self.factored and self.kron_exact and not getattr(self, "_tensor_declined", False):
+            tplan, fold = plan_or_unwrapped(TensorPtAP, self.kx, unwrap=os.environ.get("TIGAR_PTAP_UNWRAP", "1") != "0",
+                                            accept=lambda ku: np.array_equal(ku.fold_maps[-1], np.arange(ku.ncp[-1])))
         ring["tensor"] = tplan
         # an FE matrix that is a Kronecker sum of 1-D matrices on the element-coupling pattern is never written: the x
         # pass forms its entries (tg_tensor_planes_kron; TIGAR_PTAP_FUSED=0 materialises the row blocks as before)

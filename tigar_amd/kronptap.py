@@ -272,6 +272,17 @@ class KronExtraction(object):
         return _dev.kron_csr_rect(self._factors(done, group, True), row0, row1)
 
 
+def parse_direction_groups(text, d, last_in_last_group):
+    """Direction groups written as "0;1;2" or "0,1;2" (groups separated by ";", directions of a group by ","; directions
+    >= ``d`` are dropped): the list of groups when they cover 0 .. d-1 exactly once -- and, with ``last_in_last_group``,
+    the last direction (the one planes refer to) sits in the last group --, else None"""
+    groups = [[int(c) for c in g.split(",") if int(c) < d] for g in text.split(";")]
+    groups = [g for g in groups if g]
+    if sorted(sum(groups, [])) != list(range(d)) or (last_in_last_group and (d - 1) not in groups[-1]):
+        return None
+    return groups
+
+
 def default_groups(d, p):
     """Which directions to contract together.  One-shot ([[0..d-1]]) is the plain PtAP with the
     workgroup-per-row box kernel; one direction at a time runs the wave-per-run line kernel
@@ -281,11 +292,9 @@ def default_groups(d, p):
     and loses now: 51.5 vs 35.0 ms)."""
     import os
     env = os.environ.get("TIGAR_PTAP_GROUPS")            # e.g. "0;1;2" or "0,1;2" (experiments)
-    if env:
-        groups = [[int(c) for c in g.split(",") if int(c) < d] for g in env.split(";")]
-        groups = [g for g in groups if g]
-        if sorted(sum(groups, [])) == list(range(d)) and (d - 1) in groups[-1]:
-            return groups
+    groups = parse_direction_groups(env, d, True) if env else None
+    if groups is not None:
+        return groups
     if d == 3 and p >= 2:
         return [[0], [1], [2]]
     return [list(range(d))]
@@ -340,15 +349,13 @@ def ptap_factored(kx, A, a_planes, c_planes, k_planes, zero_dofs=None, diag=1.0,
     k0, k1 = k_planes
     # tensor-pattern fast path (csrc/tg_tensor_body.h): line walks without column decode; declines (None)
     # when the patch or A's pattern does not qualify, and the general stages below take over
-    from .tensorptap import TensorPtAP
-    plan = TensorPtAP.for_extraction(kx)
-    if plan is None and not A.is_loose() and (za, zb) == (0, kx.nfe[-1]) and (k0, k1) == (0, kx.ncp[-1]) \
-            and os.environ.get("TIGAR_PTAP_UNWRAP", "1") != "0":
+    from .tensorptap import TensorPtAP, plan_or_unwrapped
+    plan, ku = plan_or_unwrapped(TensorPtAP, kx, unwrap=not A.is_loose() and (za, zb) == (0, kx.nfe[-1]) and
+                                 (k0, k1) == (0, kx.ncp[-1]) and os.environ.get("TIGAR_PTAP_UNWRAP", "1") != "0")
+    if ku is not None:
         # periodic directions: the line walks on the unwrapped space, then the identification of the wrapped functions
-        ku = kx.unwrapped()
-        if ku is not None and TensorPtAP.for_extraction(ku) is not None:
-            K_u = ptap_factored(ku, A, a_planes, c_planes, (0, ku.ncp[-1]), None, 1.0, None, _split)
-            return ku.fold(K_u, zero_dofs, diag)
+        K_u = ptap_factored(ku, A, a_planes, c_planes, (0, ku.ncp[-1]), None, 1.0, None, _split)
+        return ku.fold(K_u, zero_dofs, diag)
     if plan is not None and not A.is_loose():
         piece = plan.planes(A, za * kx.plane(set()), za, zb)
         if piece is not None:

@@ -131,6 +131,89 @@ def band_pattern_ok(M1, p, nel):
     return bool(present.all())
 
 
+def patch_structure(kx, d, max_degree):
+    """(p, nels, wls) if the ``d``-dimensional patch of the ``KronExtraction`` has the structure of the fast path (one degree
+    1 .. ``max_degree`` in every direction, on the CG grid of that degree), else None"""
+    if kx.d != d:
+        return None
+    grid = kx.grid
+    ps = [s.p for s in kx.basis.splines]
+    p = ps[0]
+    if any(q != p for q in ps) or p < 1 or p > max_degree or getattr(grid, "dg", False) or grid.degree != p:
+        return None
+    nels, wls, keys = [], [], []
+    for k in range(d):
+        nel = len(grid.vertices[k]) - 1
+        wl, key = checked_weights(kx.M1[k], p, nel)
+        if wl is None:
+            return None
+        nels.append(nel)
+        wls.append(wl)
+        keys.append(key)
+    kx._tensor_keys = keys
+    return p, nels, wls
+
+
+def structure_pair(kx_row, kx_col, d, max_degree):
+    """(P, nels, column weights, (row weights, row degrees, column degrees), keys) when block (row basis, column basis)
+    of a space on ONE ``d``-dimensional Q_P node grid, P <= ``max_degree``, has the structure of the walks, else None"""
+    if kx_row.d != d or kx_col.d != d:
+        return None
+    g, g2 = kx_row.grid, kx_col.grid
+    if getattr(g, "dg", False) or getattr(g2, "dg", False) or g.degree != g2.degree or g.degree < 1 or g.degree > max_degree:
+        return None
+    if any(not np.array_equal(a, b) for a, b in zip(g.axes, g2.axes)):
+        return None
+    P = int(g.degree)
+    nels, wlc, wlr, pr, pc, keys = [], [], [], [], [], []
+    for k in range(d):
+        nel = len(g.vertices[k]) - 1
+        psr, psc = int(kx_row.basis.splines[k].p), int(kx_col.basis.splines[k].p)
+        wr, wc = local_weights_padded(kx_row.M1[k], P, nel, psr), local_weights_padded(kx_col.M1[k], P, nel, psc)
+        if wr is None or wc is None:
+            return None
+        nels.append(nel)
+        wlr.append(wr)
+        wlc.append(wc)
+        pr.append(psr)
+        pc.append(psc)
+        keys.append((P, nel, psr, psc, _digest(kx_row.M1[k]), _digest(kx_col.M1[k])))
+    return P, nels, wlc, (wlr, pr, pc), keys
+
+
+def pair_plan(cls, kx_row, kx_col, d, max_degree):
+    """plan (``cls``) of block (row basis, column basis), kept on the row side; None when the pair does not qualify or
+    TIGAR_PTAP_TENSOR=0"""
+    if os.environ.get("TIGAR_PTAP_TENSOR", "1") == "0":
+        return None
+    if kx_row is kx_col:
+        plan = cls.for_extraction(kx_row)
+        if plan is not None:
+            return plan
+    cache = kx_row.__dict__.setdefault("_tensor_pair_plans" if d == 3 else "_tensor2_pair_plans", {})
+    if id(kx_col) not in cache:
+        st = structure_pair(kx_row, kx_col, d, max_degree)
+        cache[id(kx_col)] = (kx_col, _cached_plan("%dd-pair" % d, st[0], st[1], 1, st[4],
+                                                  lambda: cls(st[0], st[1], st[2], pair=st[3])) if st is not None else None)
+    return cache[id(kx_col)][1]
+
+
+def plan_or_unwrapped(cls, kx, nfields=None, unwrap=True, accept=None):
+    """(plan, None): the tensor plan (``cls``: TensorPtAP / TensorPtAP2D) of the patch itself; (plan, ku): the patch has
+    periodic directions (tIGAr/BSplines.py:204-212) and the plan is that of its unwrapped space ``ku``, whose K the caller
+    folds (kronptap.KronExtraction.unwrapped / fold) -- only with ``unwrap`` and where ``accept(ku)`` agrees; else
+    (None, None)"""
+    args = () if nfields is None else (nfields,)
+    plan = cls.for_extraction(kx, *args)
+    if plan is not None or not unwrap:
+        return plan, None
+    ku = kx.unwrapped()
+    if ku is None or (accept is not None and not accept(ku)):
+        return None, None
+    plan = cls.for_extraction(ku, *args)
+    return plan, (ku if plan is not None else None)
+
+
 class TensorPlanes(object):
     """B2 planes of FE planes [z0, z1) (device, dense blocks); input of the z pass"""
 
@@ -146,7 +229,18 @@ class TensorPlanes(object):
             pass
 
 
-class TensorPtAP(object):
+class _PlanHandle(object):
+    """owner of a ``tg_tensor_plan`` handle"""
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().tg_tensor_plan_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+class TensorPtAP(_PlanHandle):
     """Plan of the tensor-pattern PtAP for one patch (1-D tables in HBM)."""
 
     def __init__(self, p, nels, wls, pair=None):
@@ -176,36 +270,6 @@ class TensorPtAP(object):
             arr[k].wlc = self._keep[k].ctypes.data_as(c_f64p)
         check(_lib.lib().tg_tensor_plan_create_pair(3, arr, C.byref(self._h)), "tg_tensor_plan_create_pair")
 
-    def __del__(self):
-        try:
-            if self._h:
-                _lib.lib().tg_tensor_plan_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    @staticmethod
-    def structure(kx):
-        """(p, nels, wls) if the patch of the ``KronExtraction`` has the structure of the fast path, else None"""
-        if kx.d != 3:
-            return None
-        grid = kx.grid
-        ps = [s.p for s in kx.basis.splines]
-        p = ps[0]
-        if any(q != p for q in ps) or p < 1 or p > 3 or getattr(grid, "dg", False) or grid.degree != p:
-            return None
-        nels, wls, keys = [], [], []
-        for k in range(3):
-            nel = len(grid.vertices[k]) - 1
-            wl, key = checked_weights(kx.M1[k], p, nel)
-            if wl is None:
-                return None
-            nels.append(nel)
-            wls.append(wl)
-            keys.append(key)
-        kx._tensor_keys = keys
-        return p, nels, wls
-
     @staticmethod
     def for_extraction(kx):
         """plan cached on the ``KronExtraction`` (None if the patch does not qualify or TIGAR_PTAP_TENSOR=0); patches
@@ -213,54 +277,15 @@ class TensorPtAP(object):
         if os.environ.get("TIGAR_PTAP_TENSOR", "1") == "0":
             return None
         if not hasattr(kx, "_tensor_plan"):
-            st = TensorPtAP.structure(kx)
+            st = patch_structure(kx, 3, 3)
             kx._tensor_plan = _cached_plan("3d", st[0], st[1], 1, kx._tensor_keys, lambda: TensorPtAP(*st)) \
                 if st is not None else None
         return kx._tensor_plan
 
     @staticmethod
-    def structure_pair(kx_row, kx_col):
-        """(P, nels, column weights, (row weights, row degrees, column degrees), keys) when block (row basis, column basis)
-        of a space on ONE Q_P node grid has the structure of the walks, else None"""
-        if kx_row.d != 3 or kx_col.d != 3:
-            return None
-        g, g2 = kx_row.grid, kx_col.grid
-        if getattr(g, "dg", False) or getattr(g2, "dg", False) or g.degree != g2.degree or g.degree < 1 or g.degree > 3:
-            return None
-        if any(not np.array_equal(a, b) for a, b in zip(g.axes, g2.axes)):
-            return None
-        P = int(g.degree)
-        nels, wlc, wlr, pr, pc, keys = [], [], [], [], [], []
-        for k in range(3):
-            nel = len(g.vertices[k]) - 1
-            psr, psc = int(kx_row.basis.splines[k].p), int(kx_col.basis.splines[k].p)
-            wr, wc = local_weights_padded(kx_row.M1[k], P, nel, psr), local_weights_padded(kx_col.M1[k], P, nel, psc)
-            if wr is None or wc is None:
-                return None
-            nels.append(nel)
-            wlr.append(wr)
-            wlc.append(wc)
-            pr.append(psr)
-            pc.append(psc)
-            keys.append((P, nel, psr, psc, _digest(kx_row.M1[k]), _digest(kx_col.M1[k])))
-        return P, nels, wlc, (wlr, pr, pc), keys
-
-    @staticmethod
     def for_pair(kx_row, kx_col):
         """plan of block (row basis, column basis); the square plan when both are the same object"""
-        if kx_row is kx_col:
-            plan = TensorPtAP.for_extraction(kx_row)
-            if plan is not None:
-                return plan
-        if os.environ.get("TIGAR_PTAP_TENSOR", "1") == "0":
-            return None
-        cache = kx_row.__dict__.setdefault("_tensor_pair_plans", {})
-        if id(kx_col) not in cache:
-            st = TensorPtAP.structure_pair(kx_row, kx_col)
-            cache[id(kx_col)] = (kx_col, _cached_plan("3d-pair", st[0], st[1], 1, st[4],
-                                                      lambda: TensorPtAP(st[0], st[1], st[2], pair=st[3]))
-                                 if st is not None else None)
-        return cache[id(kx_col)][1]
+        return pair_plan(TensorPtAP, kx_row, kx_col, 3, 3)
 
     def k_nnz(self, ka, kb):
         """entries of the rows of K of the dof planes [ka, kb) (clipped band, Kronecker product)"""
@@ -361,7 +386,7 @@ class TensorPtAP(object):
         return True if append_to is not None else _dev.DeviceCSR(out)
 
 
-class TensorPtAP2D(object):
+class TensorPtAP2D(_PlanHandle):
     """Plan of the tensor-pattern PtAP for a patch with TWO parametric directions and ``nfields`` fields on one scalar
     basis (csrc/tg_ptap_tensor.hip: tg_tensor2_*): the whole product in two line-walk passes, degrees 1..4."""
 
@@ -390,36 +415,6 @@ class TensorPtAP2D(object):
             arr[k].wl = self._keep[k].ctypes.data_as(c_f64p)
         check(_lib.lib().tg_tensor2_plan_create(self.nfields, arr, C.byref(self._h)), "tg_tensor2_plan_create")
 
-    def __del__(self):
-        try:
-            if self._h:
-                _lib.lib().tg_tensor_plan_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    @staticmethod
-    def structure(kx):
-        """(p, nels, wls) if the 2-D patch of the ``KronExtraction`` has the structure of the fast path, else None"""
-        if kx.d != 2:
-            return None
-        grid = kx.grid
-        ps = [s.p for s in kx.basis.splines]
-        p = ps[0]
-        if any(q != p for q in ps) or p < 1 or p > 4 or getattr(grid, "dg", False) or grid.degree != p:
-            return None
-        nels, wls, keys = [], [], []
-        for k in range(2):
-            nel = len(grid.vertices[k]) - 1
-            wl, key = checked_weights(kx.M1[k], p, nel)
-            if wl is None:
-                return None
-            nels.append(nel)
-            wls.append(wl)
-            keys.append(key)
-        kx._tensor_keys = keys
-        return p, nels, wls
-
     @staticmethod
     def for_extraction(kx, nfields=1):
         """plan cached on the ``KronExtraction`` per number of fields (None if the patch does not qualify or
@@ -428,55 +423,16 @@ class TensorPtAP2D(object):
             return None
         cache = kx.__dict__.setdefault("_tensor2_plans", {})
         if nfields not in cache:
-            st = TensorPtAP2D.structure(kx)
+            st = patch_structure(kx, 2, 4)
             ok = st is not None and (2 * st[0] + 1) * nfields <= 64
             cache[nfields] = _cached_plan("2d", st[0], st[1], nfields, kx._tensor_keys,
                                           lambda: TensorPtAP2D(*st, nfields=nfields)) if ok else None
         return cache[nfields]
 
     @staticmethod
-    def structure_pair(kx_row, kx_col):
-        """(P, nels, column weights, (row weights, row degrees, column degrees), keys) when block (row basis, column basis) of a
-        space on ONE 2-D Q_P node grid has the structure of the walks, else None"""
-        if kx_row.d != 2 or kx_col.d != 2:
-            return None
-        g, g2 = kx_row.grid, kx_col.grid
-        if getattr(g, "dg", False) or getattr(g2, "dg", False) or g.degree != g2.degree or g.degree < 1 or g.degree > 4:
-            return None
-        if any(not np.array_equal(a, b) for a, b in zip(g.axes, g2.axes)):
-            return None
-        P = int(g.degree)
-        nels, wlc, wlr, pr, pc, keys = [], [], [], [], [], []
-        for k in range(2):
-            nel = len(g.vertices[k]) - 1
-            psr, psc = int(kx_row.basis.splines[k].p), int(kx_col.basis.splines[k].p)
-            wr, wc = local_weights_padded(kx_row.M1[k], P, nel, psr), local_weights_padded(kx_col.M1[k], P, nel, psc)
-            if wr is None or wc is None:
-                return None
-            nels.append(nel)
-            wlr.append(wr)
-            wlc.append(wc)
-            pr.append(psr)
-            pc.append(psc)
-            keys.append((P, nel, psr, psc, _digest(kx_row.M1[k]), _digest(kx_col.M1[k])))
-        return P, nels, wlc, (wlr, pr, pc), keys
-
-    @staticmethod
     def for_pair(kx_row, kx_col):
         """plan of block (row basis, column basis) of a 2-D space; the square plan when both are the same object"""
-        if os.environ.get("TIGAR_PTAP_TENSOR", "1") == "0":
-            return None
-        if kx_row is kx_col:
-            plan = TensorPtAP2D.for_extraction(kx_row, 1)
-            if plan is not None:
-                return plan
-        cache = kx_row.__dict__.setdefault("_tensor2_pair_plans", {})
-        if id(kx_col) not in cache:
-            st = TensorPtAP2D.structure_pair(kx_row, kx_col)
-            cache[id(kx_col)] = (kx_col, _cached_plan("2d-pair", st[0], st[1], 1, st[4],
-                                                      lambda: TensorPtAP2D(st[0], st[1], st[2], 1, pair=st[3]))
-                                 if st is not None else None)
-        return cache[id(kx_col)][1]
+        return pair_plan(TensorPtAP2D, kx_row, kx_col, 2, 4)
 
     def ptap(self, A, zero_dofs=None, diag=1.0):
         """K = M^T A M with MatZeroRowsColumns fused, or None when A does not carry the element-coupling pattern in all
