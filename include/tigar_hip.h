@@ -227,6 +227,15 @@ int tg_spmv_sell(tg_csr_t a, int enable, int *nclasses, int64_t *padded);
  * K one product reads / size of the window staging. */
 int tg_spmv_symgrid(tg_csr_t a, int64_t row0, tg_vec_t x, tg_vec_t y, int *accepted, int64_t *value_bytes,
                     int64_t *staging_bytes);
+/* The same, with the account of the delta-coded values (TIGAR_SYMGRID_DELTA, default on: the values of a scalar plan as
+ * int16 distances, in 64-bit integer arithmetic, from the fp64 blocks of one reference plane -- restored bit for bit in the
+ * product; a matrix whose planes are unlike each other keeps fp64 values).  value_bytes stays the fp64 half-storage figure.
+ * info[12]: [0] 1 = delta-coded, [1] parts (32 rows of a sub-step; radius 4: 16) a product reads, [2] parts stored as
+ * deltas, [3] reference plane (global index: the plane of the block nearest n2 / 2), [4] template bytes, [5] delta bytes,
+ * [6] pool bytes in use (fp64 parts that did not fit), [7] pool capacity in parts, [8] largest distance of a part that
+ * fits, [9] value bytes one product reads from HBM, [10] bytes the values occupy, [11] 0. */
+int tg_spmv_symgrid_delta(tg_csr_t a, int64_t row0, tg_vec_t x, tg_vec_t y, int *accepted, int64_t *value_bytes,
+                          int64_t *staging_bytes, int64_t *info);
 /* Y = A X for k <= 4 right-hand sides (cpFuncs = M_control * P, tIGAr/common.py:367-380);
  * X, Y are column-major host arrays. */
 int tg_spmm_host(tg_csr_t a, const double *X, int k, double *Y);

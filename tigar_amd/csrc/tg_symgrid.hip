@@ -23,6 +23,10 @@
 // row, the conversion checks the length and every column index of every row it copies against the box stencil, and the
 // finished plan is compared with the CSR product on a pseudo-random vector (which a matrix that is not symmetric fails
 // by O(1)).  A matrix that does not pass keeps the sliced copy / the CSR kernel.
+//
+// Fewer bytes again: where the planes of the grid hold the same rows up to rounding (uniform knots along z), the scalar
+// plan stores the values as int16 distances from the fp64 blocks of one reference plane and the product restores them bit
+// for bit -- 2 B per value instead of 8 (see "delta coding" at the conversion kernel; TIGAR_SYMGRID_DELTA=0: off).
 #include "tg_common.h"
 #include <algorithm>
 #include <utility>
@@ -119,6 +123,14 @@ struct tg_symgrid_s {
   double *stage = nullptr;      // [patch][chunk][plane of the chunk + P][W]
   int64_t val_bytes = 0, stage_bytes = 0;
   int64_t rows_stored = 0;      // lanes that hold a row (the bytes a product reads: rows_stored * NG * 16)
+  // delta-coded values (scalar plan, see "delta coding" below): `val` stays nullptr
+  sg_d2 *tmpl = nullptr;        // [patch][sub-step][pair][lane]: the fp64 blocks of the reference plane zref
+  unsigned *dlt = nullptr;      // [patch][plane][sub-step][pair][lane]: two int16, value - template as 64-bit integers
+  sg_d2 *pool = nullptr;        // fp64 parts that do not fit: slot s in lanes [(s % PARTS) ROWS, ...) of block s / PARTS
+  int32_t *mis = nullptr;       // [patch][plane][sub-step][part]: -1 = the template, else the slot in the pool
+  int zref = 0;                 // the reference plane (local index)
+  int64_t tmpl_bytes = 0, dlt_bytes = 0, pool_bytes = 0, mis_bytes = 0;
+  int64_t parts = 0, parts_fit = 0, parts_fit32 = 0, pool_cap = 0, part_bytes = 0, max_dist = 0;
   // several fields on one scalar basis (nf > 1): this object is the container -- gd / gf hold the geometry (tables, staging
   // array) of the diagonal and of the full blocks, vd[f] / vf[f * 4 + g] (f < g) the values
   int nf = 1;
@@ -158,6 +170,10 @@ void tg_symgrid_free(tg_symgrid_s *s) {
     tg_dfree(s->tabs);
     tg_dfree(s->val);
     tg_dfree(s->stage);
+    tg_dfree(s->tmpl);
+    tg_dfree(s->dlt);
+    tg_dfree(s->pool);
+    tg_dfree(s->mis);
     for (int i = 0; i < 4; i++) tg_dfree(s->vd[i]);
     for (int i = 0; i < 16; i++) tg_dfree(s->vf[i]);
   }
@@ -177,26 +193,53 @@ template <int P>
 struct sg_cv {
   static constexpr int ROWS = P == 4 ? 16 : 32, RW = ROWS / 4, PARTS = 64 / ROWS;
 };
-template <int P>
+// ---- delta coding of the values (scalar plan).  On a patch with uniform knots along z the rows (i, j, k) and (i, j, k')
+// of K are equal up to rounding: as 64-bit integers the two doubles differ by thousands at most.  The blocks of ONE reference
+// plane are kept in fp64 (the template, small enough to live in L2); every other block stores, per value, the int16
+//     d = int64(value) - int64(template value at the same (patch, sub-step, pair, lane))
+// computed in two's complement, and the product restores the value BIT FOR BIT as bitcast<double>(int64(template) + d):
+// 2 B per value instead of 8, the same sums in the same order.  A part (the ROWS rows one conversion workgroup builds)
+// fits when every d of it lies in [-32768, 32767]; a part that does not gets its fp64 values in a slot of the pool and
+// zeros as deltas, and the table `mis` names, per part, what the deltas are added to: the template (-1) or a slot.  The
+// product has one code path.  More misfits than the pool holds: the plan is dropped and the plain one built.
+// ctl: [0] slots handed out, [1] largest distance of a part that fits, [2] parts that would fit int32
+struct sg_dl {
+  const sg_d2 *tmpl;
+  unsigned *dlt;
+  sg_d2 *pool;
+  int32_t *mis;
+  unsigned *ctl;
+  int cap, zref;
+};
+__device__ __forceinline__ unsigned long long sg_dist(double v, double t, long long *d) {
+  *d = (long long)((unsigned long long)__double_as_longlong(v) - (unsigned long long)__double_as_longlong(t));
+  return (unsigned long long)(*d < 0 ? ~*d : *d);          // d in [-2^k, 2^k - 1]  <=>  this < 2^k
+}
+// MODE 0: fp64 blocks of every plane (the plain plan); 1: the blocks of plane D.zref into the template (out, indexed
+// [patch][sub-step]); 2: every plane against the template
+template <int P, int MODE>
 __global__ void __launch_bounds__(256)
     k_symgrid_convert(sg_dev G, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                      const double *__restrict__ val, sg_d2 *__restrict__ out, int64_t nblk, int *__restrict__ fail) {
+                      const double *__restrict__ val, sg_d2 *__restrict__ out, int64_t nblk, int *__restrict__ fail, sg_dl D) {
   typedef sg_c<P> C;
   constexpr int SG_CV_ROWS = sg_cv<P>::ROWS, RW = sg_cv<P>::RW, PARTS = sg_cv<P>::PARTS;
   constexpr int LD = 2 * C::NG + 1;          // odd row length of the tile
   __shared__ double tile[SG_CV_ROWS * LD];
+  __shared__ unsigned s_far;
+  __shared__ int s_slot;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int64_t blk = (int64_t)blockIdx.x / PARTS;
   const int half = (int)(blockIdx.x % PARTS);
   const int sub = (int)(blk % G.m);
   const int64_t pz = blk / G.m;
-  const int z = (int)(pz % G.n2), patch = (int)(pz / G.n2);
+  const int z = MODE == 1 ? D.zref : (int)(pz % G.n2), patch = MODE == 1 ? (int)pz : (int)(pz / G.n2);
   const int a = patch % G.npx, b = patch / G.npx;
   const int xa = G.x0[a], pxv = G.x0[a + 1] - xa, ya = G.y0[b], pyv = G.y0[b + 1] - ya;
   const int cnt = pxv * pyv;
   const int t0 = sub * 64 + half * SG_CV_ROWS;
   if (sub * 64 >= cnt) return;                 // (a block no product touches)
   for (int i = tid; i < SG_CV_ROWS * LD; i += 256) tile[i] = 0.0;
+  if (tid == 0) s_far = 0u, s_slot = -1;
   __syncthreads();
   const int n0 = G.n0, n01 = G.n0 * G.n1;
   const int zg = z + G.zoff;                  // (a z slab of the grid: the rows hold the box of the WHOLE grid)
@@ -265,14 +308,86 @@ __global__ void __launch_bounds__(256)
     }
   }
   __syncthreads();
-  sg_d2 *o = out + blk * (int64_t)(C::NG * 64) + half * SG_CV_ROWS;
-  for (int i = tid; i < C::NG * SG_CV_ROWS; i += 256) {
-    const int g = i / SG_CV_ROWS, l = i - g * SG_CV_ROWS;
-    sg_d2 v;
-    v.x = tile[l * LD + 2 * g], v.y = tile[l * LD + 2 * g + 1];
-    o[g * 64 + l] = v;
+  if constexpr (MODE != 2) {
+    sg_d2 *o = out + blk * (int64_t)(C::NG * 64) + half * SG_CV_ROWS;
+    for (int i = tid; i < C::NG * SG_CV_ROWS; i += 256) {
+      const int g = i / SG_CV_ROWS, l = i - g * SG_CV_ROWS;
+      sg_d2 v;
+      v.x = tile[l * LD + 2 * g], v.y = tile[l * LD + 2 * g + 1];
+      o[g * 64 + l] = v;
+    }
+  } else {
+    // a thread forms the deltas of its pairs once and keeps them packed until the part is known to fit
+    constexpr int NIT = (C::NG * SG_CV_ROWS + 255) / 256;
+    const sg_d2 *tp = D.tmpl + ((int64_t)patch * G.m + sub) * (int64_t)(C::NG * 64) + half * SG_CV_ROWS;
+    unsigned pk[NIT];
+    unsigned long long far = 0;
+#pragma unroll
+    for (int it = 0; it < NIT; it++) {
+      const int i = tid + it * 256, g = i / SG_CV_ROWS, l = i - g * SG_CV_ROWS;
+      pk[it] = 0u;
+      if (i < C::NG * SG_CV_ROWS) {
+        const sg_d2 t = tp[g * 64 + l];
+        long long d0, d1;
+        const unsigned long long a0 = sg_dist(tile[l * LD + 2 * g], t.x, &d0), a1 = sg_dist(tile[l * LD + 2 * g + 1], t.y, &d1);
+        far = far > a0 ? far : a0;
+        far = far > a1 ? far : a1;
+        pk[it] = ((unsigned)d0 & 0xffffu) | ((unsigned)d1 << 16);
+      }
+    }
+    // largest distance of the part, capped: 0xffffffff = beyond int32
+    const unsigned cap32 = far > 0x7fffffffull ? 0xffffffffu : (unsigned)far;
+    if (cap32) atomicMax(&s_far, cap32);
+    __syncthreads();
+    const unsigned pfar = s_far;
+    const bool fit = pfar <= 32767u;
+    if (!fit) {          // (the same for every thread of the workgroup)
+      if (tid == 0) s_slot = (int)atomicAdd(D.ctl, 1u);        // (which slot a part gets enters no result)
+      __syncthreads();
+    }
+    const int slot = s_slot;
+    const bool room = slot >= 0 && slot < D.cap;      // (beyond the capacity nothing is written: the plan is dropped)
+    if (tid == 0) {
+      if (fit) atomicMax(D.ctl + 1, pfar);
+      if (pfar <= 0x7fffffffu) atomicAdd(D.ctl + 2, 1u);
+      D.mis[blk * PARTS + half] = room ? slot : -1;
+    }
+    unsigned *dq = D.dlt + blk * (int64_t)(C::NG * 64) + half * SG_CV_ROWS;
+    sg_d2 *pq = D.pool + (int64_t)(room ? slot / PARTS : 0) * (C::NG * 64) + (room ? slot % PARTS : 0) * SG_CV_ROWS;
+#pragma unroll
+    for (int it = 0; it < NIT; it++) {
+      const int i = tid + it * 256, g = i / SG_CV_ROWS, l = i - g * SG_CV_ROWS;
+      if (i < C::NG * SG_CV_ROWS) {
+        __builtin_nontemporal_store(fit ? pk[it] : 0u, dq + g * 64 + l);
+        if (room) {
+          sg_d2 v;
+          v.x = tile[l * LD + 2 * g], v.y = tile[l * LD + 2 * g + 1];
+          pq[g * 64 + l] = v;
+        }
+      }
+    }
   }
   if (bad) atomicExch(fail, 1);
+}
+
+// the probe before a delta-coded plan is tried: rows (ix, iy) of the planes z1 and z2, sampled, entry by entry straight
+// from the CSR arrays; out[0] counts the samples whose rows are as long as each other and differ by int16 at most
+__global__ void __launch_bounds__(256)
+    k_symgrid_probe(sg_dev G, const int64_t *__restrict__ rowptr, const double *__restrict__ val, int z1, int z2, int nsamp,
+                    unsigned *__restrict__ out) {
+  const int lane = threadIdx.x & 63, s = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= nsamp) return;
+  const unsigned h = (unsigned)s * 2654435761u;
+  const int ix = (int)((h >> 8) % (unsigned)G.n0), iy = (int)((h >> 20) % (unsigned)G.n1);
+  const int64_t r1 = ((int64_t)z1 * G.n1 + iy) * G.n0 + ix, r2 = ((int64_t)z2 * G.n1 + iy) * G.n0 + ix;
+  const int64_t e1 = rowptr[r1], e2 = rowptr[r2], len = rowptr[r1 + 1] - e1;
+  bool ok = rowptr[r2 + 1] - e2 == len;
+  if (ok)
+    for (int64_t k = lane; k < len; k += 64) {
+      long long d;
+      ok &= sg_dist(val[e2 + k], val[e1 + k], &d) <= 32767ull;
+    }
+  if (__all(ok) && lane == 0) atomicAdd(out, 1u);
 }
 
 // ---- the product: one wave per (patch, z chunk).  Two rings of P + 1 window planes in LDS: the sums (current plane and
@@ -295,11 +410,17 @@ __global__ void __launch_bounds__(256)
 // xw[xoff + r]; reads beyond it return 0 (buffer range check; such entries of K are stored zeros: rows at the faces of the
 // grid).  What is scattered beyond the block's last plane is dropped: those rows belong to the next rank, which holds the
 // transposed entries in ITS rows (k_symgrid_lowhalo).
-template <int P>
+//
+// DL (a delta-coded plan): the value stream is 4 B per pair and lane (nontemporal, as the fp64 values of the plain plan)
+// beside the 16 B of the template -- or pool -- pair, which come with the default cache policy: the template of a patch
+// is read by all its chunks and planes and is what must stay in L2 (tg_xcd_block hands an XCD a contiguous range of
+// L = patch * chunks + chunk).  Per value a sign extension and one 64-bit integer add before its two uses; the rings,
+// the groups, the barriers and the order of the sums are those of the plain kernel, so y is the same bit for bit.
+template <int P, bool DL>
 __global__ void __launch_bounds__(64)
     k_symgrid_spmv(sg_dev G, const sg_d2 *__restrict__ val, const double *__restrict__ xw, int xoff, int xlen,
                       double *__restrict__ stage, int64_t nwaves, int c_begin, int c_count, const double *__restrict__ gate,
-                      double gate_tol) {
+                      double gate_tol, sg_dl D) {
   typedef sg_c<P> C;
   typedef sg_lay<P> Y;
   constexpr int Wx = C::Wx, W = C::W, GB = Y::GBMAX, NB = Y::NBATCH, NXL = (W + 63) / 64;
@@ -353,25 +474,46 @@ __global__ void __launch_bounds__(64)
   }
   __syncthreads();
   double *st = stage + ((int64_t)patch * G.nch + c) * (int64_t)(G.czmax + P) * W;
-  const sg_d2 *vp = val + (int64_t)patch * G.n2 * G.m * (int64_t)(C::NG * 64) + lane;
+  const sg_d2 *vp = DL ? nullptr : val + (int64_t)patch * G.n2 * G.m * (int64_t)(C::NG * 64) + lane;
   struct ctx_t {
     int lb;
-    const sg_d2 *v;
+    const sg_d2 *v;          // the fp64 pairs: the values (plain plan), the template or a pool slot (delta-coded)
+    const unsigned *d;       // the packed deltas
   };
   auto ctx_of = [&](int z, int sub) {
     ctx_t k;
     const int t = sub * 64 + lane, zc = min(z, G.n2 - 1);
     const int tl = t < cnt ? tab[t] : 0, ly = tl >> 8, lx = tl & 255;
     k.lb = ly * Wx + lx;
-    k.v = vp + ((int64_t)zc * G.m + sub) * (C::NG * 64);
+    if constexpr (DL) {
+      constexpr int ROWS = sg_cv<P>::ROWS, PARTS = sg_cv<P>::PARTS;
+      const int64_t blk = ((int64_t)patch * G.n2 + zc) * G.m + sub;
+      k.d = D.dlt + blk * (C::NG * 64) + lane;
+      const int e = D.mis[blk * PARTS + lane / ROWS];       // (once per plane and sub-step, a batch round ahead of its use)
+      k.v = e < 0 ? D.tmpl + ((int64_t)patch * G.m + sub) * (C::NG * 64) + lane
+                  : D.pool + (int64_t)(e / PARTS) * (C::NG * 64) + (e % PARTS) * ROWS + (lane % ROWS);
+    } else {
+      k.d = nullptr;
+      k.v = vp + ((int64_t)zc * G.m + sub) * (C::NG * 64);
+    }
     return k;
   };
-  constexpr int VD = 4;      // batches of values held in registers (deeper rings: no gain)
+  // batches of values held in registers (deeper rings: no gain -- the plain plan sits at the HBM ceiling; delta-coded,
+  // cfg3: 4 / 6 / 8 / 12 batches 2.89 / 2.90 / 2.97 / 3.22 ms, the wave is bound by its own instruction stream)
+  constexpr int VD = 4;
   sg_d2 vv[VD][GB];
+  unsigned dd[DL ? VD : 1][DL ? GB : 1];
   auto issue_v = [&](const ctx_t &k, auto btc) {
     constexpr int BT = decltype(btc)::value, b0 = Y::bstart(BT), b1 = Y::bstart(BT + 1);
 #pragma unroll
-    for (int j = 0; j < (b1 - b0) / 2; j++) vv[BT % VD][j] = __builtin_nontemporal_load(k.v + (b0 / 2 + j) * 64);
+    for (int j = 0; j < (b1 - b0) / 2; j++) {
+      if constexpr (DL) {
+        dd[BT % VD][j] = __builtin_nontemporal_load(k.d + (b0 / 2 + j) * 64);
+        vv[BT % VD][j] = k.v[(b0 / 2 + j) * 64];
+      } else {
+        vv[BT % VD][j] = __builtin_nontemporal_load(k.v + (b0 / 2 + j) * 64);
+      }
+    }
   };
   ctx_t cur = ctx_of(za, 0);
   sg_each(std::make_integer_sequence<int, VD - 1>{}, [&](auto btc) { issue_v(cur, btc); });
@@ -403,7 +545,12 @@ __global__ void __launch_bounds__(64)
             constexpr int Pc = P;
             const int kk = b0 + gq * gs + t, l = kk - b0;
             const int pos = (kk < b1 && kk < Y::NP) ? Y::pos(kk) : -1;
-            const double vq = (l & 1) ? vv[BT % VD][l >> 1].y : vv[BT % VD][l >> 1].x;
+            double vq = (l & 1) ? vv[BT % VD][l >> 1].y : vv[BT % VD][l >> 1].x;
+            if constexpr (DL) {
+              const int w2 = (int)dd[BT % VD][l >> 1];
+              const int dl = (l & 1) ? (w2 >> 16) : ((int)((unsigned)w2 << 16) >> 16);
+              vq = __longlong_as_double((long long)((unsigned long long)__double_as_longlong(vq) + (unsigned long long)(long long)dl));
+            }
             if (pos == 0) {
               sum += vq * xi;
             } else if (pos > 0) {
@@ -814,8 +961,18 @@ __global__ void k_symgrid_compare(const double *__restrict__ y1, const double *_
 template <int P>
 static void sg_launch_convert(const tg_symgrid_s *s, tg_csr_s *a, int *fail) {
   const int64_t nblk = (int64_t)s->npx * s->npy * s->n2 * s->m;
-  hipLaunchKernelGGL(k_symgrid_convert<P>, dim3((unsigned)(nblk * sg_cv<P>::PARTS)), dim3(256), 0, g_tg.stream, sg_view(s),
-                     a->rowptr, a->col, a->val, s->val, nblk, fail);
+  hipLaunchKernelGGL((k_symgrid_convert<P, 0>), dim3((unsigned)(nblk * sg_cv<P>::PARTS)), dim3(256), 0, g_tg.stream, sg_view(s),
+                     a->rowptr, a->col, a->val, s->val, nblk, fail, sg_dl{});
+}
+// the template plane, then every plane against it
+template <int P>
+static void sg_launch_convert_delta(const tg_symgrid_s *s, tg_csr_s *a, int *fail, unsigned *ctl) {
+  const int64_t nblk = (int64_t)s->npx * s->npy * s->n2 * s->m, ntb = (int64_t)s->npx * s->npy * s->m;
+  const sg_dl D = {s->tmpl, s->dlt, s->pool, s->mis, ctl, (int)s->pool_cap, s->zref};
+  hipLaunchKernelGGL((k_symgrid_convert<P, 1>), dim3((unsigned)(ntb * sg_cv<P>::PARTS)), dim3(256), 0, g_tg.stream, sg_view(s),
+                     a->rowptr, a->col, a->val, s->tmpl, ntb, fail, D);
+  hipLaunchKernelGGL((k_symgrid_convert<P, 2>), dim3((unsigned)(nblk * sg_cv<P>::PARTS)), dim3(256), 0, g_tg.stream, sg_view(s),
+                     a->rowptr, a->col, a->val, (sg_d2 *)nullptr, nblk, fail, D);
 }
 // part 0: all of it; 1: the chunks that read no halo plane of x (all but the last one of every patch) -- what may run while
 // the halo of x is still travelling; 2: the rest (last chunks, the sum of the windows, the rows next to the previous slab)
@@ -828,8 +985,13 @@ static void sg_launch_spmv(const tg_symgrid_s *s, tg_csr_s *a, const double *x_s
   auto chunks = [&](int c0, int cn) {
     if (cn <= 0) return;
     const int64_t nw = npatch * cn;
-    hipLaunchKernelGGL(k_symgrid_spmv<P>, dim3((unsigned)(tg_cdiv(nw, 8) * 8)), dim3(64), 0, g_tg.stream, sg_view(s), s->val,
-                       xw, xoff, xlen, s->stage, nw, c0, cn, gate, tol);
+    if (s->dlt)
+      hipLaunchKernelGGL((k_symgrid_spmv<P, true>), dim3((unsigned)(tg_cdiv(nw, 8) * 8)), dim3(64), 0, g_tg.stream, sg_view(s),
+                         (const sg_d2 *)nullptr, xw, xoff, xlen, s->stage, nw, c0, cn, gate, tol,
+                         sg_dl{s->tmpl, s->dlt, s->pool, s->mis, nullptr, (int)s->pool_cap, s->zref});
+    else
+      hipLaunchKernelGGL((k_symgrid_spmv<P, false>), dim3((unsigned)(tg_cdiv(nw, 8) * 8)), dim3(64), 0, g_tg.stream, sg_view(s),
+                         s->val, xw, xoff, xlen, s->stage, nw, c0, cn, gate, tol, sg_dl{});
   };
   if (part == 0) chunks(0, s->nch);
   if (part == 1) chunks(0, s->nch - 1);
@@ -1173,6 +1335,103 @@ static int sg_build_multi(tg_csr_s *a, int verify, tg_symgrid_s **out) {
   return 0;
 }
 
+// The delta-coded values of a scalar plan (see sg_dl).  Reference plane: the plane of the block whose GLOBAL index is
+// nearest n2g / 2.  Capacity of the pool: a quarter of the parts (a patch with uniform knots misfits in the 2P planes at
+// either z face only: 12 of 259 planes at 256 elements, p = 3; a z slab of 32 planes at a face: 6 of 32) -- with more the
+// copy would no longer be smaller than half the plain one.  *coded stays false (and nothing stays allocated) when the
+// switch is off, the probe finds the planes unlike each other, there is no room, or the pool overflows; a row that is not
+// the box stencil is reported through `fail` as by the plain conversion.
+static void sg_drop_delta(tg_symgrid_s *s) {
+  tg_dfree(s->tmpl), tg_dfree(s->dlt), tg_dfree(s->pool), tg_dfree(s->mis);
+  s->tmpl = nullptr, s->dlt = nullptr, s->pool = nullptr, s->mis = nullptr;
+  s->tmpl_bytes = s->dlt_bytes = s->pool_bytes = s->mis_bytes = 0;
+  s->parts = s->parts_fit = s->parts_fit32 = s->pool_cap = s->max_dist = 0;
+}
+static int sg_try_delta(tg_symgrid_s *s, tg_csr_s *a, int *fail, const int32_t *x0, const int32_t *y0, bool *coded) {
+  *coded = false;
+  const bool trace = getenv("TIGAR_TRACE") != nullptr;
+  if (getenv("TIGAR_SYMGRID_DELTA") && atoi(getenv("TIGAR_SYMGRID_DELTA")) == 0) return 0;
+  const int P = s->P;
+  const int NG = P == 1 ? sg_c<1>::NG : P == 2 ? sg_c<2>::NG : P == 4 ? sg_c<4>::NG : sg_c<3>::NG;
+  const int PARTS = P == 4 ? sg_cv<4>::PARTS : sg_cv<3>::PARTS, ROWS = 64 / PARTS;
+  s->zref = std::min(std::max(s->n2g / 2 - s->zoff, 0), s->n2 - 1);
+  unsigned *dctl = nullptr;
+  TG_TRY(tg_dmalloc(&dctl, 4));
+  unsigned hctl[4] = {0, 0, 0, 0};
+  int rc = 0;
+  do {
+    // probe: 256 rows of the reference plane against the plane next to it
+    const int zo = s->zref + 1 < s->n2 ? s->zref + 1 : s->zref - 1, nsamp = 256;
+    if (hipMemcpyAsync(dctl, hctl, sizeof(hctl), hipMemcpyHostToDevice, g_tg.stream) != hipSuccess) {
+      rc = 1;
+      break;
+    }
+    hipLaunchKernelGGL(k_symgrid_probe, dim3(nsamp / 4), dim3(256), 0, g_tg.stream, sg_view(s), a->rowptr, a->val, s->zref, zo,
+                       nsamp, dctl + 3);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(hctl, dctl, sizeof(hctl), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess ||
+        hipStreamSynchronize(g_tg.stream) != hipSuccess) {
+      tg_set_error("tg_symgrid_build: probe failed to run");
+      rc = 1;
+      break;
+    }
+    if (trace) fprintf(stderr, "[trace] symgrid delta: probe: %u of %d rows of plane %d within int16 of plane %d\n", hctl[3], nsamp, zo, s->zref);
+    if (2 * (int)hctl[3] < nsamp) break;
+    // the parts a product reads: the sub-steps that hold rows of their patch
+    int64_t subs = 0;
+    for (int y = 0; y < s->npy; y++)
+      for (int x = 0; x < s->npx; x++) subs += ((x0[x + 1] - x0[x]) * (y0[y + 1] - y0[y]) + 63) / 64;
+    const int64_t npatch = (int64_t)s->npx * s->npy, nblk = npatch * s->n2 * s->m;
+    s->parts = subs * s->n2 * PARTS;
+    s->pool_cap = s->parts / 4 + PARTS;
+    s->part_bytes = (int64_t)NG * ROWS * 16;
+    s->tmpl_bytes = npatch * s->m * (int64_t)NG * 64 * 16;
+    s->dlt_bytes = nblk * (int64_t)NG * 64 * 4;
+    s->pool_bytes = tg_cdiv(s->pool_cap, PARTS) * (int64_t)NG * 64 * 16;
+    s->mis_bytes = nblk * PARTS * 4;
+    if (s->pool_cap >= (int64_t)1 << 30 || nblk * PARTS >= (int64_t)1 << 31) break;
+    void *p = nullptr;
+    bool room = !tg_dmalloc_bytes(&p, (size_t)s->tmpl_bytes);
+    if (room) s->tmpl = (sg_d2 *)p, room = !tg_dmalloc_bytes(&p, (size_t)s->dlt_bytes);
+    if (room) s->dlt = (unsigned *)p, room = !tg_dmalloc_bytes(&p, (size_t)s->pool_bytes);
+    if (room) s->pool = (sg_d2 *)p, room = !tg_dmalloc_bytes(&p, (size_t)s->mis_bytes);
+    if (room) s->mis = (int32_t *)p;
+    if (!room) break;
+    hctl[3] = 0;
+    switch (P) {
+      case 1: sg_launch_convert_delta<1>(s, a, fail, dctl); break;
+      case 2: sg_launch_convert_delta<2>(s, a, fail, dctl); break;
+      case 4: sg_launch_convert_delta<4>(s, a, fail, dctl); break;
+      default: sg_launch_convert_delta<3>(s, a, fail, dctl); break;
+    }
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(hctl, dctl, sizeof(hctl), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess ||
+        hipStreamSynchronize(g_tg.stream) != hipSuccess) {
+      tg_set_error("tg_symgrid_build: conversion failed to run");
+      rc = 1;
+      break;
+    }
+    s->parts_fit = s->parts - (int64_t)hctl[0];
+    s->parts_fit32 = (int64_t)hctl[2];
+    s->max_dist = (int64_t)hctl[1];
+    if (trace)
+      fprintf(stderr, "[trace] symgrid delta: reference plane %d (global %d), %lld of %lld parts fit int16 (share %.4f, int32: %.4f), largest distance of a fitting part %lld, pool %lld of %lld slots\n",
+              s->zref, s->zref + s->zoff, (long long)s->parts_fit, (long long)s->parts, (double)s->parts_fit / (double)s->parts,
+              (double)s->parts_fit32 / (double)s->parts, (long long)s->max_dist, (long long)hctl[0], (long long)s->pool_cap);
+    if ((int64_t)hctl[0] > s->pool_cap) {
+      if (trace) fprintf(stderr, "[trace] symgrid delta: the pool overflows: plain plan\n");
+      break;
+    }
+    *coded = true;
+    if (trace)
+      fprintf(stderr, "[trace] symgrid delta: template %.3f GB, deltas %.2f GB, pool %.2f GB used of %.2f GB (plain values: %.2f GB)\n",
+              s->tmpl_bytes / 1e9, s->dlt_bytes / 1e9, (double)hctl[0] * s->part_bytes / 1e9, s->pool_bytes / 1e9, s->val_bytes / 1e9);
+  } while (0);
+  tg_dfree(dctl);
+  if (!*coded) sg_drop_delta(s);
+  return rc;
+}
+
 // Builds the plan for the rows [row0, row0 + nrows) of a square matrix (the whole matrix, or the z slab of planes one
 // rank holds: whole planes of the grid); *out stays nullptr when the matrix is not a symmetric box stencil on a 3-D grid
 // (or there is no room for the copy).  verify: compare with the CSR product on a pseudo-random vector.
@@ -1257,13 +1516,8 @@ int tg_symgrid_build(tg_csr_s *a, int64_t row0, int verify, tg_symgrid_s **out) 
     if ((rc = tg_dmalloc(&s->tabs, (int64_t)h.size()))) break;
     if ((rc = tg_h2d_staged(s->tabs, h.data(), h.size() * sizeof(int32_t)))) break;
     void *p = nullptr;
-    if (tg_dmalloc_bytes(&p, (size_t)s->val_bytes)) {
-      declined = true;      // no room: not an error
-      break;
-    }
-    s->val = (sg_d2 *)p;
     if (tg_dmalloc_bytes(&p, (size_t)s->stage_bytes)) {
-      declined = true;
+      declined = true;      // no room: not an error
       break;
     }
     s->stage = (double *)p;
@@ -1273,11 +1527,21 @@ int tg_symgrid_build(tg_csr_s *a, int64_t row0, int verify, tg_symgrid_s **out) 
       rc = 1;
       break;
     }
-    switch (P) {
-      case 1: sg_launch_convert<1>(s, a, ctl); break;
-      case 2: sg_launch_convert<2>(s, a, ctl); break;
-      case 4: sg_launch_convert<4>(s, a, ctl); break;
-      default: sg_launch_convert<3>(s, a, ctl); break;
+    // the delta-coded values first; a matrix they do not suit (or TIGAR_SYMGRID_DELTA=0) gets the fp64 blocks of every plane
+    bool coded = false;
+    if ((rc = sg_try_delta(s, a, ctl, h.data() + ox, h.data() + oy, &coded))) break;
+    if (!coded) {
+      if (tg_dmalloc_bytes(&p, (size_t)s->val_bytes)) {
+        declined = true;
+        break;
+      }
+      s->val = (sg_d2 *)p;
+      switch (P) {
+        case 1: sg_launch_convert<1>(s, a, ctl); break;
+        case 2: sg_launch_convert<2>(s, a, ctl); break;
+        case 4: sg_launch_convert<4>(s, a, ctl); break;
+        default: sg_launch_convert<3>(s, a, ctl); break;
+      }
     }
     if (hipGetLastError() != hipSuccess ||
         hipMemcpyAsync(hflag, ctl, sizeof(hflag), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess ||
@@ -1351,11 +1615,31 @@ void tg_symgrid_info(const tg_symgrid_s *s, int64_t *val_bytes, int64_t *stage_b
   if (stage_bytes) *stage_bytes = s->stage_bytes;
 }
 
+// what a delta-coded plan holds and what a product reads of it from HBM (info[12]); a plain plan: compressed = 0
+static void sg_info_delta(const tg_symgrid_s *s, int64_t *info) {
+  int64_t vb = 0;
+  tg_symgrid_info(s, &vb, nullptr);
+  const bool on = s->nf == 1 && s->dlt;
+  info[0] = on ? 1 : 0;
+  info[1] = on ? s->parts : 0;
+  info[2] = on ? s->parts_fit : 0;
+  info[3] = on ? s->zref + s->zoff : -1;
+  info[4] = on ? s->tmpl_bytes : 0;
+  info[5] = on ? s->dlt_bytes : 0;
+  info[6] = on ? (s->parts - s->parts_fit) * s->part_bytes : 0;
+  info[7] = on ? s->pool_cap : 0;
+  info[8] = on ? s->max_dist : 0;
+  // the deltas of the lanes that hold a row, the misfits in fp64, the template once
+  info[9] = on ? vb / 4 + info[6] + s->tmpl_bytes : vb;
+  info[10] = on ? s->tmpl_bytes + s->dlt_bytes + s->pool_bytes + s->mis_bytes : (s->nf == 1 ? s->val_bytes : vb);
+  info[11] = 0;
+}
+
 /* Plans the half-storage product for a matrix -- or for the block of rows [row0, row0 + nrows) of one, whole planes of
  * the grid -- and runs y = K x with it (tests, bench accounting); x covers ALL columns.  *accepted = 0 when the matrix is
  * not a symmetric 3-D box stencil.  value_bytes: what one product reads of K; staging_bytes: window staging. */
-extern "C" int tg_spmv_symgrid(tg_csr_t a, int64_t row0, tg_vec_t x, tg_vec_t y, int *accepted, int64_t *value_bytes,
-                               int64_t *staging_bytes) {
+static int sg_spmv_entry(tg_csr_t a, int64_t row0, tg_vec_t x, tg_vec_t y, int *accepted, int64_t *value_bytes,
+                         int64_t *staging_bytes, int64_t *info) {
   TG_REQUIRE_INIT();
   TG_REQUIRE(a && accepted, "null argument to tg_spmv_symgrid");
   TG_REQUIRE_CANONICAL(a);
@@ -1375,7 +1659,21 @@ extern "C" int tg_spmv_symgrid(tg_csr_t a, int64_t row0, tg_vec_t x, tg_vec_t y,
   }
   *accepted = 1;
   tg_symgrid_info(s, value_bytes, staging_bytes);
+  if (info) sg_info_delta(s, info);
   if (g_tg.ready) hipStreamSynchronize(g_tg.stream);
   tg_symgrid_free(s);
   return rc;
+}
+extern "C" int tg_spmv_symgrid(tg_csr_t a, int64_t row0, tg_vec_t x, tg_vec_t y, int *accepted, int64_t *value_bytes,
+                               int64_t *staging_bytes) {
+  return sg_spmv_entry(a, row0, x, y, accepted, value_bytes, staging_bytes, nullptr);
+}
+/* tg_spmv_symgrid with the account of the delta-coded values in info[12]: [0] 1 = the plan is delta-coded, [1] parts (the
+ * rows one conversion workgroup builds: 32, radius 4: 16) a product reads, [2] parts stored as int16 deltas, [3] the
+ * reference plane (global index), [4] template, [5] delta, [6] used pool bytes, [7] pool capacity (slots), [8] largest
+ * integer distance of a part that fits, [9] value bytes one product reads from HBM, [10] bytes the values occupy. */
+extern "C" int tg_spmv_symgrid_delta(tg_csr_t a, int64_t row0, tg_vec_t x, tg_vec_t y, int *accepted, int64_t *value_bytes,
+                                     int64_t *staging_bytes, int64_t *info) {
+  TG_REQUIRE(info, "null argument to tg_spmv_symgrid_delta");
+  return sg_spmv_entry(a, row0, x, y, accepted, value_bytes, staging_bytes, info);
 }

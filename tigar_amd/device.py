@@ -303,15 +303,25 @@ class DeviceCSR(object):
         """The half-storage product of the CG solve (tg_spmv_symgrid): plans the copy, checks it against the CSR product
         and, with x given, returns (y, info); ``row0``: this matrix holds the rows [row0, row0 + nrows) of a square one (a z
         slab, all columns; x covers all columns).  info = None when the matrix is not a symmetric 3-D box stencil (y is then
-        None as well), else {"value_bytes": bytes of K one product reads, "staging_bytes": ...}."""
+        None as well), else {"value_bytes": the fp64 half-storage bytes of K (what a product reads of a plan that is not
+        delta-coded), "staging_bytes": ..., and the account of the delta coding (TIGAR_SYMGRID_DELTA): "compressed",
+        "compressed_share" (parts stored as int16 deltas / parts a product reads), "parts", "parts_compressed",
+        "reference_plane" (global index), "template_bytes", "delta_bytes", "pool_bytes", "pool_capacity_parts",
+        "max_fit_distance", "hbm_value_bytes" (what a product really reads of K from HBM), "stored_value_bytes"}."""
         ok, vb, sb = C.c_int(0), C.c_int64(0), C.c_int64(0)
+        info = (C.c_int64 * 12)()
         if x is not None and y is None:
             y = DeviceVector(self.shape[0])
-        check(_lib.lib().tg_spmv_symgrid(self._h, int(row0), x._h if x is not None else None, y._h if x is not None else None,
-                                         C.byref(ok), C.byref(vb), C.byref(sb)), "tg_spmv_symgrid")
+        check(_lib.lib().tg_spmv_symgrid_delta(self._h, int(row0), x._h if x is not None else None,
+                                               y._h if x is not None else None, C.byref(ok), C.byref(vb), C.byref(sb), info),
+              "tg_spmv_symgrid_delta")
         if not ok.value:
             return None, None
-        return y, {"value_bytes": vb.value, "staging_bytes": sb.value}
+        return y, {"value_bytes": vb.value, "staging_bytes": sb.value, "compressed": bool(info[0]),
+                   "compressed_share": (info[2] / info[1]) if info[1] else 0.0, "parts": info[1], "parts_compressed": info[2],
+                   "reference_plane": info[3], "template_bytes": info[4], "delta_bytes": info[5], "pool_bytes": info[6],
+                   "pool_capacity_parts": info[7], "max_fit_distance": info[8], "hbm_value_bytes": info[9],
+                   "stored_value_bytes": info[10]}
 
     def mult_offset(self, x, x_col0, y=None):
         """y = A x where x holds only the columns [x_col0, x_col0+len(x)) (slab pieces)"""

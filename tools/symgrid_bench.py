@@ -1,5 +1,6 @@
 """Times the products of a CG solve on K = M^T A M of a 3-D Poisson problem: sliced copy (tg_sell.hip) vs half-storage copy
-(tg_symgrid.hip).  usage: python tools/symgrid_bench.py [nel] [p] [out.json]"""
+(tg_symgrid.hip), the latter with its values delta-coded (TIGAR_SYMGRID_DELTA=1) and in fp64 (=0), all in one process.
+usage: python tools/symgrid_bench.py [nel] [p] [out.json]"""
 import json
 import os
 import sys
@@ -26,10 +27,12 @@ def main():
     K = spline.assembleMatrix(F.LaplaceForm())
     rhs = spline.assembleVector(F.SeparableLoadForm([lambda x: np.sin(np.pi * x)] * 3, scale=3 * np.pi ** 2))
     n = K.shape[0]
+    os.environ["TIGAR_SYMGRID_DELTA"] = "1"
     _, info = K.mult_symgrid()
     res = {"nel": nel, "p": p, "rows": n, "nnz": K.nnz, "symgrid": info}
-    for mode in ("0", "1"):
+    for mode, delta in (("0", "1"), ("1", "0"), ("1", "1")):
         os.environ["TIGAR_SPMV_SYM"] = mode
+        os.environ["TIGAR_SYMGRID_DELTA"] = delta
         ks = t.PETScKrylovSolver("cg", "jacobi")
         ks.parameters["relative_tolerance"] = 1e-6
         best = None
@@ -45,10 +48,15 @@ def main():
             row = {"solve_s": dt, "iterations": its, "product_ms": ms / max(cnt, 1), "products": cnt}
             if best is None or dt < best["solve_s"]:
                 best = row
-        res["sym" if mode == "1" else "sell"] = best
-        print(mode, best, flush=True)
+        key = "sell" if mode == "0" else "sym" if delta == "1" else "sym_fp64"
+        res[key] = best
+        print(key, best, flush=True)
     if info:
+        # (fp64 values: what the product reads; delta-coded: GBps_values is the fp64-equivalent rate, GBps_hbm_values the
+        #  bytes the product really reads of K)
+        res["sym_fp64"]["GBps_values"] = info["value_bytes"] / res["sym_fp64"]["product_ms"] / 1e6
         res["sym"]["GBps_values"] = info["value_bytes"] / res["sym"]["product_ms"] / 1e6
+        res["sym"]["GBps_hbm_values"] = info["hbm_value_bytes"] / res["sym"]["product_ms"] / 1e6
     res["sell"]["GBps_values"] = 8.0 * K.nnz / res["sell"]["product_ms"] / 1e6
     print(json.dumps(res))
     if out:
