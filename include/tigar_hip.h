@@ -588,6 +588,30 @@ int tg_assemble_mapped_load_rows(const tg_patch_t *patch, tg_vec_t fnodal, int64
 int tg_assemble_mapped_elasticity_rows(const tg_patch_t *patch, int fi, int fj, double lambda, double mu, int64_t row0,
                                        int64_t row1, int64_t cp_node0, tg_csr_t *out);
 
+/* ---- FE operands in the caller's dof order (csrc/tg_feorder.hip, tigar_amd/feorder.py) ----------------------------
+ * tg_nodes_locate: recognises the caller's node coordinates x[nrows x d] (host, row-major) as a permutation of the node
+ * grid of an FE space of `nfields` scalar fields: field f lives on the tensor grid of the d ascending axes
+ * axes[f * d + k] (axis_len[f * d + k] nodes, host), numbered lexicographically with direction 0 fastest, field after
+ * field.  field[nrows] (host) names the field of every row; NULL with one field.  Per row every coordinate is snapped to
+ * the nearest node of its axis and accepted when the distance is at most tol x (smallest spacing of that axis), 0 <= tol <
+ * 0.5; a bijection check on the device follows.  The handle holds grid_of_fe / fe_of_grid (int32, device) and the largest
+ * accepted distance.  Status 100 = declined, nothing is kept allocated and tg_last_error names the first offending row
+ * and the reason: "off the grid", "two rows on one node", "wrong row count", "node of another field".
+ * tg_feorder_from_perm: the handle of a given permutation grid_of_fe[n] (host); 100 when it is none.
+ * tg_csr_permute_sym: B = P A P^T, B[g(i), g(j)] = A[i, j] with g = grid_of_fe (inverse != 0: B[i, j] = A[g(i), g(j)]):
+ * every row is read once, its columns renamed, sorted by new column on chip and written once; values are copied
+ * bit for bit, no atomics on values.  Canonical CSR out.  A must be square and match the handle.
+ * tg_vec_permute: y[g(i)] = x[i] (to_caller == 0) or y[i] = x[g(i)] (to_caller != 0); x and y distinct. */
+typedef struct tg_feorder_s *tg_feorder_t;
+int tg_nodes_locate(int d, int nfields, const int64_t *axis_len, const double *const *axes, const double *x,
+                    const int32_t *field, int64_t nrows, double tol, tg_feorder_t *out);
+int tg_feorder_from_perm(const int32_t *grid_of_fe, int64_t n, tg_feorder_t *out);
+int tg_feorder_info(tg_feorder_t h, int64_t *n, int *identity, double *max_snap);
+int tg_feorder_download(tg_feorder_t h, int32_t *grid_of_fe, int32_t *fe_of_grid);
+int tg_feorder_destroy(tg_feorder_t h);
+int tg_csr_permute_sym(tg_feorder_t h, tg_csr_t a, int inverse, tg_csr_t *out);
+int tg_vec_permute(tg_feorder_t h, tg_vec_t x, tg_vec_t y, int to_caller);
+
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) --------- */
 int tg_comm_unique_id(char *id128);                          /* ncclGetUniqueId   */
 int tg_comm_create(const char *id128, int rank, int world, tg_comm_t *out);

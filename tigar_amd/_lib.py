@@ -231,6 +231,14 @@ PROTOTYPES = {
     "tg_comm_halo_extend": (C.c_int, [handle, handle, handle]),
     "tg_comm_destroy": (C.c_int, [handle]),
     "tg_comm_selftest": (C.c_int, [handle, C.c_double]),
+    "tg_nodes_locate": (C.c_int, [C.c_int, C.c_int, c_i64p, C.POINTER(c_f64p), c_f64p, c_i32p, C.c_int64, C.c_double,
+                                  C.POINTER(handle)]),
+    "tg_feorder_from_perm": (C.c_int, [c_i32p, C.c_int64, C.POINTER(handle)]),
+    "tg_feorder_info": (C.c_int, [handle, c_i64p, C.POINTER(C.c_int), c_f64p]),
+    "tg_feorder_download": (C.c_int, [handle, c_i32p, c_i32p]),
+    "tg_feorder_destroy": (C.c_int, [handle]),
+    "tg_csr_permute_sym": (C.c_int, [handle, handle, C.c_int, C.POINTER(handle)]),
+    "tg_vec_permute": (C.c_int, [handle, handle, handle, C.c_int]),
 }
 
 _lib = None

@@ -24,6 +24,7 @@ from numpy import array, zeros, arange
 
 from . import device as _dev
 from .device import DeviceCSR, DeviceVector
+from .feorder import FEOrder, as_device_csr as _as_device_csr, as_device_vector as _as_device_vector, fe_matrix as _fe_matrix
 
 # ---- module-level configuration, same names as tIGAr/common.py:35-84 ---------------------
 mpisize = int(os.environ.get("WORLD_SIZE", "1"))
@@ -300,6 +301,10 @@ class TensorFunctionSpace(object):
         return sum(g.num_nodes() for g in self.grids[:field])
 
     def tabulate_dof_coordinates(self):
+        """node coordinates of the dofs: the caller's array once ``setFENodes`` has taken it, else the node grid's"""
+        nodes = self.__dict__.get("_fe_nodes")
+        if nodes is not None:
+            return nodes
         return numpy.vstack([g.coordinates() for g in self.grids])
 
 
@@ -354,20 +359,6 @@ class Function(object):
         return self.V
 
 
-def _as_device_vector(b):
-    if isinstance(b, DeviceVector):
-        return b
-    if hasattr(b, "vector") and callable(b.vector):
-        return b.vector()
-    return DeviceVector(data=numpy.asarray(b, dtype=numpy.float64))
-
-
-def _as_device_csr(A):
-    if isinstance(A, DeviceCSR):
-        return A
-    return DeviceCSR.from_scipy(A)
-
-
 def multTranspose(M, b):
     """Returns ``M^T*b`` (tIGAr/common.py:97-109)."""
     return M.mult_transpose(_as_device_vector(b))
@@ -387,7 +378,8 @@ class AbstractExtractionGenerator(object):
 
     __metaclass__ = abc.ABCMeta
 
-    def __init__(self, comm, *args):
+    def __init__(self, comm, *args, fe_nodes=None, fe_fields=None, fe_node_tol=1e-6):
+        """``fe_nodes`` / ``fe_fields`` / ``fe_node_tol``: the caller's FE dof order, see ``setFENodes``"""
         if not isinstance(comm, _Comm):
             args = (comm,) + args
             self.comm = worldcomm
@@ -395,6 +387,41 @@ class AbstractExtractionGenerator(object):
             self.comm = comm
         self.customSetup(args)
         self.genericSetup()
+        self.feOrder = None
+        if fe_nodes is not None:
+            self.setFENodes(fe_nodes, fe_fields, fe_node_tol)
+
+    def setFENodes(self, x, fields=None, tol=1e-6):
+        """Takes the FE dof order of the caller: ``x`` [V.dim() x d] are the node coordinates of its dofs (what
+        ``V.tabulate_dof_coordinates()`` returns in an FE library), ``fields`` the field of every row (the dofs of
+        ``V.sub(f)``; needed with several fields).  The rows must be a permutation of the node grid: every coordinate within
+        ``tol`` x the smallest node spacing of its axis from a node (a condition, not a measurement: anything below 0.5 is
+        unambiguous), every node named once -- else ``ValueError`` with the first offending row and the reason.
+        Afterwards ``V.tabulate_dof_coordinates()`` returns ``x``, ``feOrder`` is set, and an ``ExtractedSpline`` made from
+        this generator takes FE matrices / vectors and returns FE functions in the caller's order.  ``M``, ``MT``,
+        ``cpFuncs`` and ``writeExtraction`` stay in the order of the node grid."""
+        if getattr(self.comm, "size", 1) > 1:
+            raise NotImplementedError("setFENodes: a caller-ordered FE space on several ranks is not supported")
+        grids = self.V.grids
+        for f, g in enumerate(grids):
+            if not isinstance(g, TensorNodeGrid) or not getattr(g, "axes", None):
+                raise ValueError("setFENodes: field %d does not live on a TensorNodeGrid (multi-patch and T-spline node sets "
+                                 "are no permutation of one tensor grid)" % f)
+            if getattr(g, "dg", False):
+                raise ValueError("setFENodes: field %d is discontinuous (DG): several dofs share a node, so coordinates do "
+                                 "not name them" % f)
+        d = grids[0].dim()
+        x = numpy.array(x, dtype=numpy.float64)
+        if x.ndim == 1 and d == 1:
+            x = x.reshape(-1, 1)
+        if x.ndim != 2 or x.shape[1] != d:
+            raise ValueError("setFENodes: wrong shape: node coordinates [%d x %d] are expected, got %s"
+                             % (self.V.dim(), d, x.shape))
+        if len(grids) > 1 and fields is None:
+            raise ValueError("setFENodes: fe_fields (the field of every row) is needed for a space of %d fields" % len(grids))
+        self.feOrder = FEOrder.locate([g.axes for g in grids], x, fields, tol)
+        self.V._fe_nodes = x
+        return self.feOrder
 
     def getComm(self):
         return self.comm
@@ -1448,6 +1475,11 @@ class ExtractedSpline(object):
     extraction operators, their application to FE matrices/vectors, and the linear solve.
     UFL form construction (``grad``, ``dx``, ``rationalize`` ...) needs FEniCS and is not
     provided here.
+
+    With a generator that was given the caller's FE dof order (``fe_nodes=`` / ``setFENodes``) the spline carries
+    ``feOrder``: assembled matrices / vectors handed in are taken in the caller's order and FE functions are returned in
+    it.  ``M``, ``MT``, ``cpFuncs`` and everything the package's own forms assemble stay in the order of the node grid;
+    K, M^T b and U are IGA objects and do not depend on the order.
     """
 
     def __init__(self, sourceArg, quadDeg=None, mesh=None, doPermutation=DEFAULT_DO_PERMUTATION,
@@ -1516,6 +1548,7 @@ class ExtractedSpline(object):
             raise ValueError("extraction matrices in %s do not match extraction-info.txt" % dirname)
         self.zeroDofs = numpy.asarray(petscio.read_is(os.path.join(dirname, EXTRACTION_ZERO_DOFS_FILE)), dtype=INDEX_TYPE)
         self._kron = self._kron_scalar = self._kron_fields = None       # (M read from files: an arbitrary sparse matrix)
+        self.feOrder = None
 
     def initFromGenerator(self, generator, quadDeg, doPermutation=DEFAULT_DO_PERMUTATION):
         """tIGAr/common.py:708-746 -- shares M, M_control, V, cpFuncs with the generator."""
@@ -1540,6 +1573,7 @@ class ExtractedSpline(object):
         self._kron_scalar = getattr(generator, "_kron_scalar", None)
         self._kron_fields = getattr(generator, "_kron_fields", None)
         self.zeroDofs = generator.zeroDofsArray().astype(INDEX_TYPE)
+        self.feOrder = getattr(generator, "feOrder", None)
 
     def genericSetup(self):
         self.setSolverOptions()
@@ -1610,9 +1644,31 @@ class ExtractedSpline(object):
         return (0, self.M.shape[0])
 
     # -- a-10
+    def _caller_ordered(self):
+        return self.feOrder is not None and not self.feOrder.is_identity
+
+    def extractionMatrixFE(self):
+        """M as a stored CSR matrix whose rows are in the caller's FE order (``self.M`` itself stays in grid order; it is
+        returned as it is when the caller numbers like the grid)"""
+        if not self._caller_ordered():
+            return self.M
+        if self._implicit():
+            raise NotImplementedError("extractionMatrixFE: the extraction operator of this spline is never stored")
+        return self.M.gather_rows(self.feOrder.grid_of_fe)
+
     def extractVector(self, b, applyBCs=True):
         """Apply extraction to an FE vector ``b``: ``M^T b``, zeroed at ``zeroDofs`` if
-        ``applyBCs`` (tIGAr/common.py:1142-1160)."""
+        ``applyBCs`` (tIGAr/common.py:1142-1160).  ``b`` is in the caller's FE order when the spline has an ``feOrder``."""
+        if self._caller_ordered():
+            from .implicit import LazyFEVector
+            if isinstance(b, LazyFEVector):
+                raise NotImplementedError("extractVector: a LazyFEVector produces rows of the node grid; a caller-ordered "
+                                          "spline takes assembled vectors")
+            b = self.feOrder.to_grid(b)
+        return self._extract_vector_grid(b, applyBCs)
+
+    def _extract_vector_grid(self, b, applyBCs=True):
+        """``extractVector`` of a vector in grid order"""
         from .implicit import LazyFEVector
         if isinstance(b, LazyFEVector) or self._distributed() or (self._implicit() and self.nFields > 1):
             # (several fields with an implicit operator: the field-block engine and its plane-wise numbering, also on
@@ -1646,8 +1702,8 @@ class ExtractedSpline(object):
             else:
                 b = form.assemble_vector(self.V)
         else:
-            b = form
-        return self.extractVector(b, applyBCs=applyBCs)
+            return self.extractVector(form, applyBCs=applyBCs)       # (assembled by the caller: in the caller's order)
+        return self._extract_vector_grid(b, applyBCs)                 # (the package's forms number the node grid)
 
     # -- a-11
     def extractMatrix(self, A, applyBCs=True, diag=1):
@@ -1655,8 +1711,19 @@ class ExtractedSpline(object):
         of ``zeroDofs`` zeroed with ``diag`` on the diagonal (tIGAr/common.py:1176-1204).
         The symbolic plan is cached and reused while A's pattern is unchanged.  A K of a single tensor-product patch on
         one rank carries ``K.tensor_structure`` (what the fast diagonalization preconditioner needs, tigar_amd/fastdiag.py);
-        otherwise ``K.tensor_structure_refusal`` says why not."""
-        K = self._extract_matrix(A, applyBCs, diag)
+        otherwise ``K.tensor_structure_refusal`` says why not.  ``A`` is in the caller's FE order when the spline has an
+        ``feOrder``; it is brought to grid order on the device first and reaches the same route as a grid-ordered A."""
+        if self._caller_ordered():
+            from .implicit import LazyFEMatrix
+            if isinstance(A, LazyFEMatrix):
+                raise NotImplementedError("extractMatrix: a LazyFEMatrix produces rows of the node grid; a caller-ordered "
+                                          "spline takes assembled matrices")
+            A = self.feOrder.permute_matrix(A)
+        return self._extract_matrix_grid(A, applyBCs, diag)
+
+    def _extract_matrix_grid(self, A, applyBCs=True, diag=1):
+        """``extractMatrix`` of a matrix in grid order"""
+        K = self._extract_matrix(_fe_matrix(A), applyBCs, diag)
         if isinstance(K, DeviceCSR):
             ts, why = self._tensor_structure(applyBCs)
             if ts is not None:
@@ -1717,10 +1784,10 @@ class ExtractedSpline(object):
         if isinstance(A, DeviceCSR):
             ncols = A.shape[1]
             return lambda r0, r1: A.block(int(r0), int(r1), 0, ncols)
-        import scipy.sparse as _sp
-        if not _sp.issparse(A):
-            raise TypeError("extractMatrix: a DeviceCSR, a scipy sparse matrix or a LazyFEMatrix is expected")
-        Ah = _sp.csr_matrix(A)
+        Ah = _fe_matrix(A)
+        if not hasattr(Ah, "tocsr"):
+            raise TypeError("extractMatrix: an assembled FE matrix is expected here, not %s" % type(A).__name__)
+        Ah = Ah.tocsr()
         return lambda r0, r1: DeviceCSR.from_scipy(Ah[int(r0):int(r1)])
 
     def assembleMatrix(self, form, applyBCs=True, diag=1):
@@ -1743,9 +1810,10 @@ class ExtractedSpline(object):
                     A.block_factors = form.block_factors(self.V) if hasattr(form, "block_factors") else None
             else:
                 A = form.assemble_matrix(self.V)
+            K = self._extract_matrix_grid(A, applyBCs=applyBCs, diag=diag)     # (the package's forms number the node grid)
         else:
             A = form
-        K = self.extractMatrix(A, applyBCs=applyBCs, diag=diag)
+            K = self.extractMatrix(A, applyBCs=applyBCs, diag=diag)            # (assembled by the caller: in its order)
         proof = None
         if getattr(form, "symmetric", False) is True and isinstance(K, DeviceCSR) and self.nFields == 1 and \
                 hasattr(form, "factors") and getattr(form, "geometry", None) is None:
@@ -1772,7 +1840,11 @@ class ExtractedSpline(object):
         """Solve ``MTAM*U = MTb`` and store ``M*U`` in the FE function ``u``; returns ``U``
         (tIGAr/common.py:1236-1263).  With ``linearSolver == None`` the reference calls dolfin's direct LU;
         here: the banded LU of csrc/tg_lu.hip while its band storage fits (``_DefaultSolver``), Jacobi-GMRES at
-        tight tolerance beyond, with a message that says so."""
+        tight tolerance beyond, with a message that says so.  On a spline with an ``feOrder`` ``u`` is written -- and a
+        non-zero initial guess in it read -- in the caller's FE order."""
+        reorder = self._caller_ordered()
+        if reorder and (self._distributed() or (self._implicit() and self.nFields > 1)):
+            raise NotImplementedError("solveLinearSystem: caller-ordered FE functions with the streamed field engine")
         MTU = DeviceVector(MTAM.shape[0])          # (local rows of MTAM: all of them on one rank)
         solver = self.linearSolver if self.linearSolver is not None else _default_linear_solver()
         if getattr(solver, "parameters", {}).get("nonzero_initial_guess", False):
@@ -1782,7 +1854,7 @@ class ExtractedSpline(object):
             if self._distributed() or (self._implicit() and self.nFields > 1):
                 MTU = self._initial_guess_through_slabs(u)
             else:
-                self.M.mult_transpose(_as_device_vector(u), MTU)
+                self.M.mult_transpose(self.feOrder.to_grid(u) if reorder else _as_device_vector(u), MTU)
         if self._distributed() and getattr(solver, "comm", False) is None:
             solver.comm = self.comm.device()
         solver.solve(MTAM, MTU, MTb)
@@ -1791,6 +1863,8 @@ class ExtractedSpline(object):
             # M*MTU followed by the ghost update)
             u_loc = self._slab_path().prolong(MTU)
             u._vec, u.local_range = u_loc, self._slab_path().mine["u_rows"]
+        elif reorder:
+            self.feOrder.to_caller(self.M.mult(MTU), out=_as_device_vector(u))
         else:
             self.M.mult(MTU, _as_device_vector(u))
         if hasattr(u, "invalidate_ghosts"):
@@ -1956,7 +2030,7 @@ class ExtractedSpline(object):
         uv = _as_device_vector(u)
         MTtemp = self.extractVector(uv, applyBCs=False)
         ident = DeviceCSR.from_scipy(_scipy_identity(self.M.shape[0]))
-        MTM = self.extractMatrix(ident, applyBCs=False)
+        MTM = self._extract_matrix_grid(ident, applyBCs=False)       # (the identity is the same in every order)
         x = DeviceVector(self.M.shape[1])
         solver = self.linearSolver if self.linearSolver is not None else _default_linear_solver("cg")
         solver.solve(MTM, x, MTtemp)
@@ -1971,6 +2045,9 @@ class ExtractedSpline(object):
         read the current state of ``u`` (as UFL forms reference their coefficient).  Prints the
         reference's progress line; non-convergence raises instead of the reference's exit().
         Returns the list of relative norms."""
+        if self._caller_ordered():
+            raise NotImplementedError("solveNonlinearVariationalProblem: the forms read the Function in the order of the node "
+                                      "grid; a caller-ordered spline is not supported")
         returningDoFs = igaDoFs is not None
         dist = self._distributed()
         if dist:
@@ -2062,6 +2139,9 @@ class ExtractedNonlinearProblem(object):
     return the extracted residual / tangent."""
 
     def __init__(self, spline, residual, tangent, solution, **kwargs):
+        if getattr(spline, "feOrder", None) is not None and not spline.feOrder.is_identity:
+            raise NotImplementedError("ExtractedNonlinearProblem: the forms read the solution Function in the order of the "
+                                      "node grid; a caller-ordered spline is not supported")
         self.spline, self.residual, self.tangent, self.solution = spline, residual, tangent, solution
 
     def form(self, A, P, B, x):

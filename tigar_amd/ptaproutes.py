@@ -10,6 +10,7 @@ import numpy
 
 from . import device as _dev
 from .device import DeviceCSR
+from .feorder import as_device_csr
 from .implicit import LazyFEMatrix
 from .tensorptap import TensorPtAP, TensorPtAP2D, plan_or_unwrapped
 
@@ -39,8 +40,7 @@ class _Call(object):
     @property
     def A(self):
         """A on the device (the slab engine takes the FE matrix as it was handed in)"""
-        if not isinstance(self.raw, DeviceCSR):
-            self.raw = DeviceCSR.from_scipy(self.raw)
+        self.raw = as_device_csr(self.raw)
         return self.raw
 
 
