@@ -128,6 +128,39 @@ static inline int tg_dmalloc(T **p, int64_t count) {
     if (_rc) return _rc;      \
   } while (0)
 
+// move-only owner of one tg_dmalloc block: freed when it goes out of scope, unless it was released to a plan or a matrix
+template <typename T>
+struct tg_dbuf {
+  T *p = nullptr;
+  tg_dbuf() = default;
+  tg_dbuf(const tg_dbuf &) = delete;
+  tg_dbuf &operator=(const tg_dbuf &) = delete;
+  tg_dbuf(tg_dbuf &&o) noexcept : p(o.release()) {}
+  tg_dbuf &operator=(tg_dbuf &&o) noexcept {
+    if (this != &o) {
+      reset();
+      p = o.release();
+    }
+    return *this;
+  }
+  ~tg_dbuf() { reset(); }
+  int alloc(int64_t count) {
+    reset();
+    return tg_dmalloc(&p, count);
+  }
+  T *get() const { return p; }
+  operator T *() const { return p; }
+  void reset() {             // frees now
+    tg_dfree(p);
+    p = nullptr;
+  }
+  T *release() {             // the caller owns the block from here on
+    T *q = p;
+    p = nullptr;
+    return q;
+  }
+};
+
 static inline int64_t tg_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // device-wide in-place exclusive scan of int64 (n elements; out[n] gets the total if
@@ -136,6 +169,10 @@ int tg_exclusive_scan_i64(int64_t *d, int64_t n, int64_t *host_total);
 // deterministic reduction of `n` partial doubles (device) into out_dev[0..k) sums of k
 // interleaved streams -- tg_core.hip
 int tg_csr_alloc(int64_t nrows, int64_t ncols, int64_t nnz, tg_csr_s **out);
+// rows that lie at tmp_off[r] of (tcol, tval) -> CSR order under rowptr (tg_core.hip); tmp_off_val: separate starts of the
+// values or null; tval null: columns only; `who` opens the error text
+int tg_rows_reorder(const char *who, const int64_t *rowptr, const int64_t *tmp_off, const int64_t *tmp_off_val, const int32_t *tcol,
+                    const double *tval, int64_t nrows, int32_t *col, double *val);
 struct tg_csr_builder_s {      // incremental vstack into one allocation (tg_extract.hip)
   tg_csr_s *m = nullptr;
   int64_t rows_done = 0, nnz_done = 0, cap = 0;
@@ -260,6 +297,20 @@ __device__ __forceinline__ int64_t tg_xcd_block(int64_t b, int64_t nb) {
 }
 
 // ---- small host/device helpers shared by the translation units ----
+static inline int tg_pow2_ge(int64_t v) {
+  int p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+static inline int tg_lg(int v) {
+  int l = 0;
+  while ((1 << l) < v) l++;
+  return l;
+}
+static inline int tg_env_int(const char *name, int dflt) {
+  const char *s = getenv(name);
+  return s ? atoi(s) : dflt;
+}
 static inline int tg_grid_1d(int64_t n, int block) {
   int64_t g = tg_cdiv(n, block);
   int64_t cap = (int64_t)g_tg.num_cu * 8;

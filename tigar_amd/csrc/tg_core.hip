@@ -980,3 +980,35 @@ int tg_exclusive_scan_i64(int64_t *d, int64_t n, int64_t *host_total) {
   }
   return 0;
 }
+
+// copies rows that lie anywhere in (tcol, tval) -- reserved by a bump-allocating pass, or loose rows -- into CSR order:
+// wave per row.  tmp_off_val: where the rows' values start when that differs from the columns (stacked views), else null;
+// tval null: a pattern without values
+__global__ void __launch_bounds__(256)
+    k_rows_reorder(const int64_t *__restrict__ rowptr, const int64_t *__restrict__ tmp_off, const int64_t *__restrict__ tmp_off_val,
+                   const int32_t *__restrict__ tcol, const double *__restrict__ tval, int64_t nrows, int32_t *__restrict__ col,
+                   double *__restrict__ val) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t r = wave; r < nrows; r += nwaves) {
+    const int64_t dst = rowptr[r], n = rowptr[r + 1] - dst, src = tmp_off[r];
+    const int64_t srcv = tmp_off_val ? tmp_off_val[r] : src;
+    for (int64_t q = lane; q < n; q += 64) {
+      col[dst + q] = tcol[src + q];
+      if (tval) val[dst + q] = tval[srcv + q];
+    }
+  }
+}
+
+int tg_rows_reorder(const char *who, const int64_t *rowptr, const int64_t *tmp_off, const int64_t *tmp_off_val, const int32_t *tcol,
+                    const double *tval, int64_t nrows, int32_t *col, double *val) {
+  if (nrows <= 0) return 0;
+  const unsigned rg = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tg_cdiv(nrows, 4), (int64_t)g_tg.num_cu * 16));
+  hipLaunchKernelGGL(k_rows_reorder, dim3(rg), dim3(256), 0, g_tg.stream, rowptr, tmp_off, tmp_off_val, tcol, tval, nrows, col, val);
+  if (hipGetLastError() != hipSuccess) {
+    tg_set_error("%s reorder launch failed", who);
+    return 1;
+  }
+  return 0;
+}

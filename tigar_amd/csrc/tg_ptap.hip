@@ -19,7 +19,7 @@
 // A and M).  Once a plan knows the row pointer (second call with the same pattern, e.g. a
 // Newton loop), rows are PLACED directly.
 // Inputs are row blocks (z-slabs) with GLOBAL column indices: local row = global - row0.
-#include "tg_common.h"
+#include "tg_bump.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstring>
@@ -395,37 +395,6 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// copies bump-allocated rows into CSR order: wave per row
-__global__ void __launch_bounds__(256)
-    k_ptap_reorder(const int64_t *__restrict__ rowptr, const int64_t *__restrict__ tmp_off,
-                   const int32_t *__restrict__ tcol, const double *__restrict__ tval, int64_t nrows,
-                   int32_t *__restrict__ col, double *__restrict__ val) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t r = wave; r < nrows; r += nwaves) {
-    const int64_t dst = rowptr[r], n = rowptr[r + 1] - dst, src = tmp_off[r];
-    for (int64_t q = lane; q < n; q += 64) {
-      col[dst + q] = tcol[src + q];
-      val[dst + q] = tval[src + q];
-    }
-  }
-}
-
-static int tg_pow2_ge(int64_t v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-static int tg_lg(int v) {
-  int l = 0;
-  while ((1 << l) < v) l++;
-  return l;
-}
-static int tg_env_int(const char *name, int dflt) {
-  const char *s = getenv(name);
-  return s ? atoi(s) : dflt;
-}
 // lanes per operand row: largest power of two <= 0.44 * mean row length, in [4,64]
 static int tg_group_for(double avg) {
   const double target = avg * 0.44;
@@ -480,6 +449,11 @@ static void tg_ptap_launch(int nt, unsigned grid, size_t lds, const tg_ptap_args
                        k_val, cursor, capacity, mask, diag, status, status + 1);
 }
 
+static int P_accum_mode_env() {
+  const char *am = getenv("TIGAR_PTAP_ACCUM");
+  return am && !strcmp(am, "int") ? 1 : am && !strcmp(am, "float") ? 2 : 0;
+}
+
 static void tg_fill_args(tg_ptap_args &P, tg_csr_s *a, int64_t a_row0, tg_csr_s *m, int64_t m_row0, tg_csr_s *mt,
                          int64_t mt_row0) {
   P.mt_rowptr = mt->rowptr;
@@ -500,13 +474,7 @@ static void tg_fill_args(tg_ptap_args &P, tg_csr_s *a, int64_t a_row0, tg_csr_s 
   P.row_stride = 1;
   P.a_rowmax = nullptr;
   P.m_rowmax = nullptr;
-  const char *am = getenv("TIGAR_PTAP_ACCUM");
-  P.accum_mode = am && !strcmp(am, "int") ? 1 : am && !strcmp(am, "float") ? 2 : 0;
-}
-
-static int P_accum_mode_env() {
-  const char *am = getenv("TIGAR_PTAP_ACCUM");
-  return am && !strcmp(am, "int") ? 1 : am && !strcmp(am, "float") ? 2 : 0;
+  P.accum_mode = P_accum_mode_env();
 }
 
 static int tg_status_error(int st) {
@@ -626,15 +594,14 @@ extern "C" int tg_ptap_numeric(tg_ptap_t plan, tg_csr_t a, tg_csr_t m, tg_csr_t 
   TG_REQUIRE(mt->nrows == plan->nrows && m->ncols == plan->ncols, "PtAP plan does not match the operands");
   tg_ptap_set_lds_limits();
   int rc = 0;
-  uint8_t *mask = nullptr;
-  if (nzero > 0) TG_TRY(tg_build_dof_mask(zero_dofs, nzero, plan->ncols, &mask));
+  tg_dbuf<uint8_t> mask;
+  if (nzero > 0) TG_TRY(tg_build_dof_mask(zero_dofs, nzero, plan->ncols, &mask.p));
   tg_csr_s *k = nullptr;
   // (TIGAR_PTAP_ACCUM=int asks for the integer grid of the workgroup kernel: the wave kernels add floating-point numbers)
   if (plan->wave.usable && plan->nrows > 0 && P_accum_mode_env() != 1) {
     // two Gustavson products, one wave per row (tg_ptap_wave.hip); 100 = declined, the workgroup kernel below takes over
     rc = tg_ptap_wave_numeric(&plan->wave, a, plan->a_row0, m, plan->m_row0, mt, plan->mt_row0, mask, diag, &k);
     if (rc != 100) {
-      tg_dfree(mask);
       if (!rc) *k_out = k;
       return rc;
     }
@@ -650,20 +617,16 @@ extern "C" int tg_ptap_numeric(tg_ptap_t plan, tg_csr_t a, tg_csr_t m, tg_csr_t 
   P.lg1 = tg_lg(P.g1);
   P.lg2 = tg_lg(P.g2);
   const unsigned grid = (unsigned)(tg_cdiv(std::max<int64_t>(plan->nrows, 1), 8) * 8);
-  double *a_rowmax = nullptr, *m_rowmax = nullptr;
+  tg_dbuf<double> a_rowmax, m_rowmax;
   if (plan->nrows > 0) {
-    rc = tg_dmalloc(&a_rowmax, std::max<int64_t>(a->nrows, 1)) || tg_dmalloc(&m_rowmax, std::max<int64_t>(m->nrows, 1));
-    if (rc) {
-      tg_dfree(a_rowmax);
-      tg_dfree(mask);
-      return rc;
-    }
+    TG_TRY(a_rowmax.alloc(std::max<int64_t>(a->nrows, 1)));
+    TG_TRY(m_rowmax.alloc(std::max<int64_t>(m->nrows, 1)));
     if (a->nrows > 0)
       hipLaunchKernelGGL(k_row_absmax, dim3((unsigned)std::min<int64_t>(tg_cdiv(a->nrows, 4), (int64_t)g_tg.num_cu * 16)), dim3(256),
-                         0, g_tg.stream, a->rowptr, a->val, a->nrows, a_rowmax);
+                         0, g_tg.stream, a->rowptr, a->val, a->nrows, a_rowmax.get());
     if (m->nrows > 0)
       hipLaunchKernelGGL(k_row_absmax, dim3((unsigned)std::min<int64_t>(tg_cdiv(m->nrows, 4), (int64_t)g_tg.num_cu * 16)), dim3(256),
-                         0, g_tg.stream, m->rowptr, m->val, m->nrows, m_rowmax);
+                         0, g_tg.stream, m->rowptr, m->val, m->nrows, m_rowmax.get());
   }
   P.a_rowmax = a_rowmax;
   P.m_rowmax = m_rowmax;
@@ -699,89 +662,55 @@ extern "C" int tg_ptap_numeric(tg_ptap_t plan, tg_csr_t a, tg_csr_t m, tg_csr_t 
     }
   } else {
     // ---- first numeric pass: bump-allocate rows, scan counts, copy into CSR order
-    int64_t *cnt = nullptr, *off = nullptr;
-    unsigned long long *cursor = nullptr;
-    int32_t *tcol = nullptr;
-    double *tval = nullptr;
+    tg_bump t("workgroup kernel");
     int ts1 = plan->ts1, ts2 = plan->ts2;
-    int64_t capacity = (int64_t)(plan->mean_k * 1.05 * (double)plan->nrows) + plan->max_k + 1024;
-    rc = tg_dmalloc(&cnt, plan->nrows + 1) || tg_dmalloc(&off, plan->nrows + 1) || tg_dmalloc(&cursor, 1);
+    t.capacity = (int64_t)(plan->mean_k * 1.05 * (double)plan->nrows) + plan->max_k + 1024;
+    rc = t.init(plan->nrows, true, 1, 3);
     // (tables and capacity start from the symbolic pass's SAMPLE of rows; a matrix with a few rows far longer than the rest
     //  needs several rounds: double at first, quadruple from the fourth round on)
     const int max_attempts = 20;
-    for (int attempt = 0; attempt < max_attempts && !rc; attempt++) {
-      rc = tg_dmalloc(&tcol, capacity + TG_CSR_PAD) || tg_dmalloc(&tval, capacity + TG_CSR_PAD);
-      if (rc) break;
-      P.ts1 = std::max(ts1, ts2);
-      P.ts2 = ts2;
-      hipMemsetAsync(status, 0, 3 * sizeof(int), g_tg.stream);
-      hipMemsetAsync(cursor, 0, sizeof(unsigned long long), g_tg.stream);
-      hipMemsetAsync(cnt, 0, (size_t)(plan->nrows + 1) * sizeof(int64_t), g_tg.stream);
-      const int nt = tg_ptap_threads(P.ts1, P.ts2, true);
-      const size_t lds = tg_ptap_lds_bytes(P.ts1, P.ts2, true, nt);
-      if (lds > 160 * 1024) {
-        tg_set_error("PtAP: K row too dense for the LDS tables (%d / %d slots)", P.ts1, P.ts2);
-        rc = 4;
-        break;
-      }
-      tg_ptap_launch<TG_MODE_BUMP>(nt, grid, lds, P, cnt, off, tcol, tval, cursor, capacity, mask, diag, status);
-      int h = 0;
-      unsigned long long used = 0;
-      hipMemcpyAsync(&h, status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream);
-      hipMemcpyAsync(&used, cursor, sizeof(used), hipMemcpyDeviceToHost, g_tg.stream);
-      if (hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-        tg_set_error("PtAP numeric failed to run (LDS %zu B)", lds);
-        rc = 1;
-        break;
-      }
-      if ((rc = tg_status_error(h))) break;
-      if (h == TG_PTAP_OK) break;
-      // grow whatever overflowed and retry
-      tg_dfree(tcol);
-      tg_dfree(tval);
-      tcol = nullptr;
-      tval = nullptr;
-      if (h == TG_PTAP_CAP) capacity = std::max<int64_t>((int64_t)used + 1024, capacity * 2);
-      if (h == TG_PTAP_OVF1) ts1 *= attempt >= 3 ? 4 : 2;
-      if (h == TG_PTAP_OVF2) ts2 *= attempt >= 3 ? 4 : 2;
-      if (attempt == max_attempts - 1) {
-        tg_set_error("PtAP numeric: could not size tables / output (status %d)", h);
-        rc = 4;
-      }
+    size_t lds = 0;
+    if (!rc)
+      rc = t.run(
+          max_attempts,
+          [&](int) {
+            P.ts1 = t.ts[0] = std::max(ts1, ts2);
+            P.ts2 = t.ts[1] = ts2;
+            const int nt = tg_ptap_threads(P.ts1, P.ts2, true);
+            lds = tg_ptap_lds_bytes(P.ts1, P.ts2, true, nt);
+            if (lds > 160 * 1024) {
+              tg_set_error("PtAP: K row too dense for the LDS tables (%d / %d slots)", P.ts1, P.ts2);
+              return 4;
+            }
+            tg_ptap_launch<TG_MODE_BUMP>(nt, grid, lds, P, t.cnt, t.off, t.tcol, t.tval, t.cursor, t.capacity, mask, diag, status);
+            return 0;
+          },
+          [&](int attempt, const int *h, unsigned long long used) {
+            if (int e = tg_status_error(h[0])) return e;
+            if (h[0] == TG_PTAP_OK) return (int)TG_BUMP_DONE;
+            // grow whatever overflowed and retry
+            if (h[0] == TG_PTAP_CAP) t.capacity = std::max<int64_t>((int64_t)used + 1024, t.capacity * 2);
+            if (h[0] == TG_PTAP_OVF1) ts1 *= attempt >= 3 ? 4 : 2;
+            if (h[0] == TG_PTAP_OVF2) ts2 *= attempt >= 3 ? 4 : 2;
+            if (attempt == max_attempts - 1) {
+              tg_set_error("PtAP numeric: could not size tables / output (status %d)", h[0]);
+              return 4;
+            }
+            return (int)TG_BUMP_RETRY;
+          });
+    if (rc == TG_BUMP_NORUN) {
+      tg_set_error("PtAP numeric failed to run (LDS %zu B)", lds);
+      rc = 1;
     }
+    // the scanned counts are the pattern remembered for later calls with the same operands' structure
+    if (!rc) rc = t.finish_csr("PtAP", plan->ncols, &k, &plan->rowptr, &plan->nnz);
     if (!rc) {
-      int64_t nnz = 0;
-      rc = tg_exclusive_scan_i64(cnt, plan->nrows, &nnz);
-      if (!rc) rc = tg_csr_alloc(plan->nrows, plan->ncols, nnz, &k);
-      if (!rc) {
-        hipMemcpyAsync(k->rowptr, cnt, (size_t)(plan->nrows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice,
-                       g_tg.stream);
-        const unsigned rg = (unsigned)std::min<int64_t>(tg_cdiv(plan->nrows, 4), (int64_t)g_tg.num_cu * 16);
-        hipLaunchKernelGGL(k_ptap_reorder, dim3(rg), dim3(256), 0, g_tg.stream, k->rowptr, off, tcol, tval,
-                           plan->nrows, k->col, k->val);
-        if (hipGetLastError() != hipSuccess) {
-          tg_set_error("PtAP reorder launch failed");
-          rc = 1;
-        }
-        // remember the pattern for later calls with the same operands' structure
-        plan->rowptr = cnt;
-        cnt = nullptr;
-        plan->nnz = nnz;
-        plan->ts1 = std::max(ts1, ts2);
-        plan->ts2 = ts2;
-      }
+      plan->ts1 = std::max(ts1, ts2);
+      plan->ts2 = ts2;
     }
     hipStreamSynchronize(g_tg.stream);
-    tg_dfree(cnt);
-    tg_dfree(off);
-    tg_dfree(cursor);
-    tg_dfree(tcol);
-    tg_dfree(tval);
   }
   hipStreamSynchronize(g_tg.stream);
-  tg_dfree(mask);
-  tg_dfree(a_rowmax);
-  tg_dfree(m_rowmax);
   if (rc) {
     if (k) tg_csr_destroy(k);
     return rc;

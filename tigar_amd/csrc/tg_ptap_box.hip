@@ -17,7 +17,7 @@
 // the structural pattern of P^T A P exactly as the general hash kernel produces it.
 // If a box would not fit in LDS (or A couples outside the measured bandwidth, impossible by
 // construction) the host falls back to the general kernel (tg_ptap.hip).
-#include "tg_common.h"
+#include "tg_bump.h"
 #include <array>
 #include <map>
 #include <algorithm>
@@ -591,25 +591,6 @@ __global__ void __launch_bounds__(NT)
   }
 }
 
-__global__ void __launch_bounds__(256)
-    k_box_reorder(const int64_t *__restrict__ rowptr, const int64_t *__restrict__ tmp_off,
-                  const int64_t *__restrict__ tmp_off_val,
-                  const int32_t *__restrict__ tcol, const double *__restrict__ tval, int64_t nrows,
-                  int32_t *__restrict__ col, double *__restrict__ val) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t r = wave; r < nrows; r += nwaves) {
-    const int64_t dst = rowptr[r], n = rowptr[r + 1] - dst, src = tmp_off[r];
-    const int64_t srcv = tmp_off_val ? tmp_off_val[r] : src;
-    for (int64_t q = lane; q < n; q += 64) {
-      col[dst + q] = tcol[src + q];
-      val[dst + q] = tval[srcv + q];
-    }
-  }
-}
-
-
 // ------------------------------------------------------------------------------------------------
 // "Line" kernel: ONE contracted direction a, one WAVE per run of output rows.
 //
@@ -627,7 +608,7 @@ __global__ void __launch_bounds__(256)
 //   * the box is contracted out of registers against the dense (D x B_a) slice of F_a (LDS broadcast
 //     reads) and stored over the head of its own line (no second box), "touched" travels as a bit mask,
 //   * output space comes from a wave-private chunk of the temporary (one global atomic per
-//     TG grab, not per row); rows are put in final order by k_box_reorder as before.
+//     TG grab, not per row); rows are put in final order by tg_rows_reorder as before.
 #define TG_LINE_NB 4
 
 __device__ __forceinline__ int64_t tg_readlane_i64(int64_t v, int l) {
@@ -1069,27 +1050,22 @@ __global__ void k_i32_to_i64(const int32_t *__restrict__ a, int64_t *__restrict_
 int tg_csr_compact_impl(tg_csr_s *in, tg_csr_s **out) {
   TG_REQUIRE_INIT();
   TG_REQUIRE(in && out && in->rowcnt, "tg_csr_compact: not a loose-row matrix");
-  int64_t *cnt = nullptr;
-  TG_TRY(tg_dmalloc(&cnt, in->nrows + 1));
+  tg_dbuf<int64_t> cnt;
+  TG_TRY(cnt.alloc(in->nrows + 1));
   if (in->nrows > 0)
-    hipLaunchKernelGGL(k_i32_to_i64, dim3(tg_grid_1d(in->nrows, 256)), dim3(256), 0, g_tg.stream, in->rowcnt, cnt, in->nrows);
+    hipLaunchKernelGGL(k_i32_to_i64, dim3(tg_grid_1d(in->nrows, 256)), dim3(256), 0, g_tg.stream, in->rowcnt, cnt.get(), in->nrows);
   int64_t nnz = 0;
   int rc = tg_exclusive_scan_i64(cnt, in->nrows, &nnz);
   tg_csr_s *k = nullptr;
   if (!rc) rc = tg_csr_alloc(in->nrows, in->ncols, nnz, &k);
   if (!rc) {
     hipMemcpyAsync(k->rowptr, cnt, (size_t)(in->nrows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream);
-    if (in->nrows > 0) {
-      const unsigned rg = (unsigned)std::min<int64_t>(tg_cdiv(in->nrows, 4), (int64_t)g_tg.num_cu * 16);
-      hipLaunchKernelGGL(k_box_reorder, dim3(rg), dim3(256), 0, g_tg.stream, k->rowptr, in->rowptr,
-                         (const int64_t *)in->rowptr_val, in->col, in->val, in->nrows, k->col, k->val);
-    }
-    if (hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
+    const int rr = tg_rows_reorder("tg_csr_compact:", k->rowptr, in->rowptr, in->rowptr_val, in->col, in->val, in->nrows, k->col, k->val);
+    if (hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess || rr) {
       tg_set_error("tg_csr_compact: kernel failed");
       rc = 1;
     }
   }
-  tg_dfree(cnt);
   if (rc) {
     if (k) tg_csr_destroy(k);
     return rc;
@@ -1164,7 +1140,13 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
   P.nrows = cur->nrows;
   P.d = d;
   int64_t nin_total = 1, nout_total = 1;
-  std::vector<void *> dev;
+  struct dev_list {            // factor tables, reach, row maxima: back to the pool when the function returns, the stream drained
+    std::vector<void *> p;
+    ~dev_list() {
+      hipStreamSynchronize(g_tg.stream);
+      for (void *q : p) tg_dfree(q);
+    }
+  } dev;
   int rc = 0;
   int maxlen[3] = {1, 1, 1};
   for (int k = 0; k < 3; k++) {
@@ -1186,7 +1168,7 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
       double *v = nullptr, *tv = nullptr;
       rc = tg_dmalloc(&a, F.n + 1) || tg_dmalloc(&b, nnz1) || tg_dmalloc(&v, nnz1) || tg_dmalloc(&c, F.m + 1) ||
            tg_dmalloc(&e, nnz1) || tg_dmalloc(&tv, nnz1);
-      dev.insert(dev.end(), {(void *)a, (void *)b, (void *)v, (void *)c, (void *)e, (void *)tv});
+      dev.p.insert(dev.p.end(), {(void *)a, (void *)b, (void *)v, (void *)c, (void *)e, (void *)tv});
       if (rc) break;
       hipMemcpyAsync(a, F.rowptr, (F.n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, g_tg.stream);
       hipMemcpyAsync(b, F.col, nnz1 * sizeof(int32_t), hipMemcpyHostToDevice, g_tg.stream);
@@ -1208,16 +1190,8 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
     nin_total *= P.nin[k];
     nout_total *= P.nout[k];
   }
-  auto cleanup = [&]() {
-    hipStreamSynchronize(g_tg.stream);
-    for (void *p : dev) tg_dfree(p);
-  };
-  if (rc) {
-    cleanup();
-    return rc;
-  }
+  if (rc) return rc;
   if (!(out_row1 <= nout_total && cur->ncols == nin_total)) {
-    cleanup();
     tg_set_error("tg_ptap_kron: index spaces do not match the operands (cols %lld vs %lld)", (long long)cur->ncols,
                  (long long)nin_total);
     return 2;
@@ -1228,14 +1202,10 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
   const int ntot = P.nin[0] + P.nin[1] + P.nin[2];
   int *reach = nullptr;                  // lmax[ntot] | rmax[ntot]
   rc = tg_dmalloc(&reach, 2 * (int64_t)ntot);
-  if (rc) {
-    cleanup();
-    return rc;
-  }
-  dev.push_back(reach);
+  if (rc) return rc;
+  dev.p.push_back(reach);
   hipMemsetAsync(reach, 0, 2 * (size_t)ntot * sizeof(int), g_tg.stream);
   if ((int64_t)P.nin[0] * P.nin[1] >= (1ll << 31) || nin_total >= (1ll << 31)) {
-    cleanup();
     tg_set_error("tg_ptap_kron: index space too large for 32-bit decomposition");
     return 100;
   }
@@ -1296,10 +1266,9 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
   int *dbox = nullptr;
   rc = tg_dmalloc(&dbox, (int64_t)hb.size());
   if (rc) {
-    cleanup();
     return rc;
   }
-  dev.push_back(dbox);
+  dev.p.push_back(dbox);
   hipMemcpyAsync(dbox, hb.data(), hb.size() * sizeof(int), hipMemcpyHostToDevice, g_tg.stream);
   for (int k = 0; k < 3; k++) {
     P.blo[k] = dbox + boff[k];
@@ -1386,7 +1355,6 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
   }
   const size_t lds = tg_box_lds(cap, cap1, ctab, nlist, nt);
   if (boxmax > (1 << 20) || lds > 150 * 1024 || maxl > TG_BOX_MAXLIST || too_many) {
-    cleanup();
     tg_set_error("tg_ptap_kron: accumulator box (%lld entries) does not fit in LDS", (long long)boxmax);
     return 100;
   }
@@ -1404,7 +1372,7 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
   }
   unsigned long long *prof = nullptr;
   if (getenv("TIGAR_BOX_PROF") && !tg_dmalloc(&prof, 8)) {
-    dev.push_back(prof);
+    dev.p.push_back(prof);
     hipMemsetAsync(prof, 0, 8 * sizeof(unsigned long long), g_tg.stream);
     P.prof = prof;
   }
@@ -1443,11 +1411,9 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
     }
   }
   if (cur->rowptr_val && !line_variant) {   // the box kernel reads col and val through one row start
-    cleanup();
     return 102;
   }
   if ((int64_t)P.nin[0] * P.nin[1] >= (1ll << 31) || nin_total >= (1ll << 31)) {
-    cleanup();
     tg_set_error("tg_ptap_kron: index space too large for 32-bit decomposition");
     return 100;
   }
@@ -1465,17 +1431,15 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
   P.row_stride = 1;
   const int64_t nrows = P.out_nrows;
   tg_csr_s *k = nullptr;
-  uint8_t *mask = nullptr;
-  int64_t *cnt = nullptr, *off = nullptr;
-  unsigned long long *cursor = nullptr;
-  int32_t *tcol = nullptr;
-  double *tval = nullptr;
+  tg_dbuf<uint8_t> mask;
+  tg_bump t(line_variant ? "line stage" : "box stage");
   if (nrows == 0) {
     rc = tg_csr_alloc(0, nout_total, 0, &k);
     if (!rc) hipMemsetAsync(k->rowptr, 0, sizeof(int64_t), g_tg.stream);
   } else {
-    if (nzero > 0) rc = tg_build_dof_mask(zero_dofs, nzero, nout_total, &mask);
-    if (!rc) rc = tg_dmalloc(&cnt, nrows + 1) || tg_dmalloc(&off, nrows + 1) || tg_dmalloc(&cursor, 1);
+    if (nzero > 0) rc = tg_build_dof_mask(zero_dofs, nzero, nout_total, &mask.p);
+    if (!rc) rc = t.init(nrows, true, 1, 3);
+    int64_t *const cnt = t.cnt, *const off = t.off;
     double mean_k = 0.0;
     int hmax[3] = {0, 0, 0};
     // Capacity of the temporary: from the last product with the same signature (stage, index spaces in
@@ -1533,7 +1497,6 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
       }
       mean_k = (double)total / (double)nsample;
     }
-    unsigned long long used_final = 0;
     int64_t capacity = (int64_t)(mean_k * 1.05 * (double)nrows) + hmax[2] + 1024;
     if (line_variant && !have_cached) capacity = (int64_t)(capacity * 1.3) + nrows / 8 * 64;   // slack of the wave-private chunks
     // (measured use incl. the slack of the wave-private chunks, which varies with the order in which the
@@ -1544,7 +1507,7 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
       double *rowmax = nullptr;
       rc = tg_dmalloc(&rowmax, std::max<int64_t>(cur->nrows, 1));
       if (!rc) {
-        dev.push_back(rowmax);
+        dev.p.push_back(rowmax);
         if (cur->nrows > 0)
           hipLaunchKernelGGL(k_box_row_absmax, dim3((unsigned)std::min<int64_t>(tg_cdiv(cur->nrows, 4), (int64_t)g_tg.num_cu * 16)),
                              dim3(256), 0, g_tg.stream, cur->rowptr, (const int64_t *)cur->rowptr_val, (const int32_t *)cur->rowcnt,
@@ -1552,12 +1515,12 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
         P.rowmax = rowmax;
       }
     }
-    for (int attempt = 0; attempt < 6 && !rc; attempt++) {
-      rc = tg_dmalloc(&tcol, capacity + TG_CSR_PAD) || tg_dmalloc(&tval, capacity + TG_CSR_PAD);
-      if (rc) break;
-      hipMemsetAsync(status, 0, 3 * sizeof(int), g_tg.stream);
-      hipMemsetAsync(cursor, 0, sizeof(unsigned long long), g_tg.stream);
-      hipMemsetAsync(cnt, 0, (size_t)(nrows + 1) * sizeof(int64_t), g_tg.stream);
+    t.capacity = capacity;
+    auto launch = [&](int) {
+      int32_t *const tcol = t.tcol;
+      double *const tval = t.tval;
+      unsigned long long *const cursor = t.cursor;
+      const int64_t capacity = t.capacity;
       if (line_variant) {
         // runs along the first uncontracted direction; output space in wave-private chunks
         const int u = Q.u;
@@ -1620,8 +1583,7 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
           TG_LINE_DISPATCH(32, 16);
       } else if (!P.rowmax) {
         tg_set_error("tg_ptap_kron: internal error (no row maxima for the box kernel)");
-        rc = 1;
-        break;
+        return 1;
       } else if (nt == 64)
         hipLaunchKernelGGL((k_ptap_box<TG_BOXMODE_BUMP, 64>), dim3((unsigned)(tg_cdiv(nrows, 8) * 8)), dim3(64), lds,
                            g_tg.stream, P, cnt, off, tcol, tval, cursor, capacity, (const uint8_t *)mask, diag, status,
@@ -1630,15 +1592,11 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
         hipLaunchKernelGGL((k_ptap_box<TG_BOXMODE_BUMP, 256>), dim3((unsigned)(tg_cdiv(nrows, 8) * 8)), dim3(256), lds,
                            g_tg.stream, P, cnt, off, tcol, tval, cursor, capacity, (const uint8_t *)mask, diag, status,
                            status + 1);
-      int h = 0;
-      unsigned long long used = 0;
-      hipMemcpyAsync(&h, status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream);
-      hipMemcpyAsync(&used, cursor, sizeof(used), hipMemcpyDeviceToHost, g_tg.stream);
-      if (hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-        tg_set_error("tg_ptap_kron: kernel failed to run (LDS %zu B)", lds);
-        rc = 1;
-        break;
-      }
+      return 0;
+    };
+    // growth rule: an overflow doubles the temporary; what was used, and the capacity that worked, go to the cache
+    auto decide = [&](int attempt, const int *hs, unsigned long long used) {
+      const int h = hs[0];
       if (prof) {
         unsigned long long hp[8];
         hipMemcpy(hp, prof, sizeof(hp), hipMemcpyDeviceToHost);
@@ -1647,46 +1605,38 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
                 line_variant ? "line" : "box", (long long)nrows, P.fast24, 100.0 * hp[0] / tot, 100.0 * hp[1] / tot,
                 100.0 * hp[2] / tot, 100.0 * hp[3] / tot);
       }
-      used_final = used;
       if (h == TG_BOX_OK) {
-        if (nrows > 0) {
-          tg_cap_entry &c = cap_cache[cap_key];
-          c.used_pr = std::max(c.used_pr, (double)used / (double)nrows);
-          c.hmax2 = std::max(c.hmax2, hmax[2]);
-          const double cp = (double)std::max<int64_t>(capacity - 65536, 0) / (double)nrows;
-          // fixed once it has worked (a capacity that follows the largest use seen creeps upwards over
-          // the first steps and every change is a round of hipMalloc); only an overflow moves it
-          if (c.cap_pr == 0.0 || attempt > 0) c.cap_pr = cp;
-        }
-        break;
+        tg_cap_entry &c = cap_cache[cap_key];
+        c.used_pr = std::max(c.used_pr, (double)used / (double)nrows);
+        c.hmax2 = std::max(c.hmax2, hmax[2]);
+        const double cp = (double)std::max<int64_t>(t.capacity - 65536, 0) / (double)nrows;
+        // fixed once it has worked (a capacity that follows the largest use seen creeps upwards over
+        // the first steps and every change is a round of hipMalloc); only an overflow moves it
+        if (c.cap_pr == 0.0 || attempt > 0) c.cap_pr = cp;
+        return (int)TG_BUMP_DONE;
       }
-      tg_dfree(tcol);
-      tg_dfree(tval);
-      tcol = nullptr;
-      tval = nullptr;
       if (h == TG_BOX_CAP) {
-        if (getenv("TIGAR_TRACE"))
-          fprintf(stderr, "[tigar] ptap temporary too small: capacity %lld, used %llu, rows %lld, mean row %.1f, run %d -> retry\n",
-                  (long long)capacity, used, (long long)nrows, mean_k, Q.mlen);
-        if (nrows > 0) {
-          tg_cap_entry &c = cap_cache[cap_key];      // what was reserved before the kernel gave up is a lower bound
-          c.used_pr = std::max(c.used_pr, (double)used / (double)nrows);
-          c.hmax2 = std::max(c.hmax2, hmax[2]);
-        }
-        capacity = std::max<int64_t>((int64_t)used + 1024, capacity * 2);
-        continue;
+        tg_cap_entry &c = cap_cache[cap_key];      // what was reserved before the kernel gave up is a lower bound
+        c.used_pr = std::max(c.used_pr, (double)used / (double)nrows);
+        c.hmax2 = std::max(c.hmax2, hmax[2]);
+        t.capacity = std::max<int64_t>((int64_t)used + 1024, t.capacity * 2);
+        return (int)TG_BUMP_RETRY;
       }
-      if (h == TG_BOX_TOOBIG) {
-        rc = 100;
-        break;
-      }
-      if (h == TG_BOX_OUTSIDE) {
-        rc = 101;
-        break;
-      }
+      if (h == TG_BOX_TOOBIG) return 100;
+      if (h == TG_BOX_OUTSIDE) return 101;
       tg_set_error("tg_ptap_kron: kernel status %d", h);
-      rc = h == TG_BOX_RANGE ? 3 : 4;
+      return h == TG_BOX_RANGE ? 3 : 4;
+    };
+    if (!rc) rc = t.run(6, launch, decide);
+    if (rc == TG_BUMP_NORUN) {
+      tg_set_error("tg_ptap_kron: kernel failed to run (LDS %zu B)", lds);
+      rc = 1;
     }
+    if (rc == TG_BUMP_RETRY) {                       // (six doublings were not enough)
+      tg_set_error("tg_ptap_kron: kernel status %d", (int)TG_BOX_CAP);
+      rc = 4;
+    }
+    const unsigned long long used_final = t.used;
     if (!rc && loose_out) {
       // intermediate stage: hand the temporary over as it is (rows where the kernel put them, lengths
       // in rowcnt) -- the consumers (next stage, vstack) read (start, length) pairs, so the
@@ -1695,18 +1645,15 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
       k->nrows = nrows;
       k->ncols = nout_total;
       k->nnz = (int64_t)used_final;
-      k->rowptr = off;
-      k->col = tcol;
-      k->val = tval;
       rc = tg_dmalloc(&k->rowcnt, nrows);
       if (!rc) {
         hipLaunchKernelGGL(k_i64_to_i32, dim3(tg_grid_1d(nrows, 256)), dim3(256), 0, g_tg.stream, cnt, k->rowcnt, nrows);
         const int64_t endm = (int64_t)used_final;
         hipMemcpyAsync(off + nrows, &endm, sizeof(int64_t), hipMemcpyHostToDevice, g_tg.stream);
         hipStreamSynchronize(g_tg.stream);
-        off = nullptr;      // owned by k now
-        tcol = nullptr;
-        tval = nullptr;
+        k->rowptr = t.off.release();
+        k->col = t.tcol.release();
+        k->val = t.tval.release();
       } else {
         delete k;
         k = nullptr;
@@ -1726,41 +1673,17 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
         int64_t *rp = dest->m->rowptr + dest->rows_done;       // rp[0] == nnz_done already
         hipLaunchKernelGGL(k_shift_i64, dim3(tg_grid_1d(nrows, 256)), dim3(256), 0, g_tg.stream, rp + 1, cnt + 1, nrows,
                            dest->nnz_done);
-        const unsigned rg = (unsigned)std::min<int64_t>(tg_cdiv(nrows, 4), (int64_t)g_tg.num_cu * 16);
-        hipLaunchKernelGGL(k_box_reorder, dim3(rg), dim3(256), 0, g_tg.stream, rp, off, (const int64_t *)nullptr, tcol, tval,
-                           nrows, dest->m->col, dest->m->val);
-        if (hipGetLastError() != hipSuccess) {
-          tg_set_error("tg_ptap_kron_append: reorder launch failed");
-          rc = 1;
-        } else {
+        rc = tg_rows_reorder("tg_ptap_kron_append:", rp, off, nullptr, t.tcol, t.tval, nrows, dest->m->col, dest->m->val);
+        if (!rc) {
           dest->rows_done += nrows;
           dest->nnz_done += nnz;
         }
       }
     } else if (!rc) {
-      int64_t nnz = 0;
-      rc = tg_exclusive_scan_i64(cnt, nrows, &nnz);
-      if (!rc) rc = tg_csr_alloc(nrows, nout_total, nnz, &k);
-      if (!rc) {
-        hipMemcpyAsync(k->rowptr, cnt, (size_t)(nrows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream);
-        const unsigned rg = (unsigned)std::min<int64_t>(tg_cdiv(nrows, 4), (int64_t)g_tg.num_cu * 16);
-        hipLaunchKernelGGL(k_box_reorder, dim3(rg), dim3(256), 0, g_tg.stream, k->rowptr, off, (const int64_t *)nullptr,
-                           tcol, tval, nrows, k->col, k->val);
-        if (hipGetLastError() != hipSuccess) {
-          tg_set_error("tg_ptap_kron: reorder launch failed");
-          rc = 1;
-        }
-      }
+      rc = t.finish_csr("tg_ptap_kron:", nout_total, &k, nullptr, nullptr);
     }
   }
   hipStreamSynchronize(g_tg.stream);
-  tg_dfree(cnt);
-  tg_dfree(off);
-  tg_dfree(cursor);
-  tg_dfree(tcol);
-  tg_dfree(tval);
-  tg_dfree(mask);
-  cleanup();
   if (rc) {
     if (k) tg_csr_destroy(k);
     return rc;

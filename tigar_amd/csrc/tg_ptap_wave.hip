@@ -19,7 +19,7 @@
 // one atomic per row, (start, count) per row); K's rows are rank-sorted, MatZeroRowsColumns applied on the way, and go to
 // their CSR place directly when the plan knows the row pointer (second call with the same pattern) or through a
 // reserve-scan-reorder pass otherwise.
-#include "tg_common.h"
+#include "tg_bump.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstring>
@@ -432,43 +432,12 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// copies reserved rows into CSR order: wave per row
-__global__ void __launch_bounds__(256)
-    k_gw_reorder(const int64_t *__restrict__ rowptr, const int64_t *__restrict__ tmp_off, const int32_t *__restrict__ tcol,
-                 const double *__restrict__ tval, int64_t nrows, int32_t *__restrict__ col, double *__restrict__ val) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t r = wave; r < nrows; r += nwaves) {
-    const int64_t dst = rowptr[r], n = rowptr[r + 1] - dst, src = tmp_off[r];
-    for (int64_t q = lane; q < n; q += 64) {
-      col[dst + q] = tcol[src + q];
-      val[dst + q] = tval[src + q];
-    }
-  }
-}
-
-static int gw_lg(int v) {
-  int l = 0;
-  while ((1 << l) < v) l++;
-  return l;
-}
-static int gw_pow2_ge(int64_t v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
 // lanes per operand row from its mean length: the smallest power of two >= 0.75 * mean, in [8, 64]
 static int gw_lg_group(double mean) {
   int g = 8;
   while (g < 64 && g < 0.75 * mean) g <<= 1;
-  return gw_lg(g);
+  return tg_lg(g);
 }
-static int gw_env_int(const char *name, int dflt) {
-  const char *s = getenv(name);
-  return s ? atoi(s) : dflt;
-}
-
 template <int MODE, bool FINAL>
 static void gw_launch(int lg, unsigned grid, size_t lds, const gw_args &P, int64_t *out_off, int32_t *out_cnt,
                       int64_t *row_cnt, uint32_t *ocol, double *oval, unsigned long long *cursor, int64_t capacity,
@@ -521,12 +490,12 @@ static void gw_tile_hint(gw_args &P, const char *env) {
 }
 
 // mixed copy of a matrix' column indices (padded like the column array itself)
-static int gw_mix_columns(tg_csr_s *m, uint32_t **out) {
-  TG_TRY(tg_dmalloc(out, m->nnz + TG_CSR_PAD));
+static int gw_mix_columns(tg_csr_s *m, tg_dbuf<uint32_t> &out) {
+  TG_TRY(out.alloc(m->nnz + TG_CSR_PAD));
   if (m->nnz > 0)
     hipLaunchKernelGGL(k_gw_mix, dim3((unsigned)std::min<int64_t>(tg_cdiv(m->nnz, 256), (int64_t)g_tg.num_cu * 32)), dim3(256), 0,
-                       g_tg.stream, m->col, m->nnz, *out);
-  hipMemsetAsync(*out + m->nnz, 0, TG_CSR_PAD * sizeof(uint32_t), g_tg.stream);
+                       g_tg.stream, m->col, m->nnz, out.get());
+  TG_CHECK_HIP(hipMemsetAsync(out.get() + m->nnz, 0, TG_CSR_PAD * sizeof(uint32_t), g_tg.stream));
   TG_LAUNCH_CHECK();
   return 0;
 }
@@ -570,7 +539,7 @@ int tg_ptap_wave_plan(tg_csr_s *a, tg_csr_s *m, int64_t m_row0, tg_csr_s *mt, in
   // leave most lanes of a row-per-wave walk idle and the fused kernel is up to 2 x faster there; so is it when the product
   // is streamed in row blocks whose operand rows overlap (every block recomputes the rows of A M in its halo).
   // TIGAR_PTAP_WAVE=1/0 and tg_ptap_prefer() override the rule.
-  const int forced = gw_env_int("TIGAR_PTAP_WAVE", -1);
+  const int forced = tg_env_int("TIGAR_PTAP_WAVE", -1);
   const int pref = forced == 1 ? 1 : forced == 0 ? 2 : g_gw_prefer;
   if (pref == 2) return 0;
   const double mean_m = (double)m->nnz / (double)std::max<int64_t>(m->nrows, 1);
@@ -579,8 +548,8 @@ int tg_ptap_wave_plan(tg_csr_s *a, tg_csr_s *m, int64_t m_row0, tg_csr_s *mt, in
   gw_set_lds_limits();
   int *status = (int *)g_tg.scratch;           // [0] status, [1] maximum, [2..3] sum
   unsigned long long *sum = (unsigned long long *)(status + 2);
-  uint32_t *m_mix = nullptr;
-  TG_TRY(gw_mix_columns(m, &m_mix));
+  tg_dbuf<uint32_t> m_mix;
+  TG_TRY(gw_mix_columns(m, m_mix));
   gw_args S;
   gw_fill_stage1(S, a, m, m_mix, m_row0);
   const int64_t nsample = std::min<int64_t>(a->nrows, 4096);
@@ -589,7 +558,7 @@ int tg_ptap_wave_plan(tg_csr_s *a, tg_csr_s *m, int64_t m_row0, tg_csr_s *mt, in
   S.ts = 2048;                                 // 4 waves x 2048 x 14 B = 112 KB
   S.lgts = 11;
   S.rows_per_wave = 4;
-  plan->lg_m = gw_env_int("TIGAR_PTAP_WAVE_LG1", gw_lg_group((double)m->nnz / (double)std::max<int64_t>(m->nrows, 1)));
+  plan->lg_m = tg_env_int("TIGAR_PTAP_WAVE_LG1", gw_lg_group((double)m->nnz / (double)std::max<int64_t>(m->nrows, 1)));
   TG_CHECK_HIP(hipMemsetAsync(status, 0, 4 * sizeof(int), g_tg.stream));
   gw_launch<GW_COUNT, false>(plan->lg_m, gw_grid(nsample, S.rows_per_wave), 4 * gw_wave_bytes(S.ts), S, nullptr, nullptr, nullptr,
                              nullptr, nullptr, nullptr, 0, nullptr, 0.0, 0, status, sum);
@@ -597,7 +566,7 @@ int tg_ptap_wave_plan(tg_csr_s *a, tg_csr_s *m, int64_t m_row0, tg_csr_s *mt, in
   const hipError_t e1 = hipGetLastError();
   const hipError_t e2 = hipMemcpyAsync(h, status, sizeof(h), hipMemcpyDeviceToHost, g_tg.stream);
   const hipError_t e3 = hipStreamSynchronize(g_tg.stream);
-  tg_dfree(m_mix);
+  m_mix.reset();
   TG_CHECK_HIP(e1);
   TG_CHECK_HIP(e2);
   TG_CHECK_HIP(e3);
@@ -614,9 +583,9 @@ int tg_ptap_wave_plan(tg_csr_s *a, tg_csr_s *m, int64_t m_row0, tg_csr_s *mt, in
   plan->max_k = max_k;
   plan->mean_k = mean_k;
   const double load_inv = getenv("TIGAR_PTAP_WAVE_LOADINV") ? atof(getenv("TIGAR_PTAP_WAVE_LOADINV")) : 2.5;
-  plan->ts_am = std::max(64, gw_pow2_ge((int64_t)(plan->max_am * load_inv) + 4));
-  plan->ts_k = std::max(64, gw_pow2_ge((int64_t)(max_k * load_inv) + 4));
-  plan->lg_am = gw_env_int("TIGAR_PTAP_WAVE_LG2", gw_lg_group(plan->mean_am));
+  plan->ts_am = std::max(64, tg_pow2_ge((int64_t)(plan->max_am * load_inv) + 4));
+  plan->ts_k = std::max(64, tg_pow2_ge((int64_t)(max_k * load_inv) + 4));
+  plan->lg_am = tg_env_int("TIGAR_PTAP_WAVE_LG2", gw_lg_group(plan->mean_am));
   if (getenv("TIGAR_PTAP_WAVE_DEBUG"))
     fprintf(stderr, "[gw] max_am %d mean_am %.1f max_k %d mean_k %.1f ts %d / %d lg %d / %d\n", plan->max_am, plan->mean_am, max_k,
             mean_k, plan->ts_am, plan->ts_k, plan->lg_m, plan->lg_am);
@@ -639,106 +608,63 @@ int tg_ptap_wave_numeric(tg_gw_plan *plan, tg_csr_s *a, int64_t a_row0, tg_csr_s
   int *status = (int *)g_tg.scratch;
   unsigned long long *sum = (unsigned long long *)(status + 2);
   int rc = 0;
-  int64_t *am_off = nullptr;
-  int32_t *am_cnt = nullptr;
-  uint32_t *am_col = nullptr, *m_mix = nullptr;     // (am_col: the intermediate's columns, mixed)
-  double *am_val = nullptr;
-  unsigned long long *cursor = nullptr;
-  int64_t *cnt = nullptr, *off = nullptr;
-  int32_t *tcol = nullptr;
-  double *tval = nullptr;
   tg_csr_s *k = nullptr;
-  auto cleanup = [&]() {
-    tg_dfree(am_off);
-    tg_dfree(am_cnt);
-    tg_dfree(am_col);
-    tg_dfree(m_mix);
-    tg_dfree(am_val);
-    tg_dfree(cursor);
-    tg_dfree(cnt);
-    tg_dfree(off);
-    tg_dfree(tcol);
-    tg_dfree(tval);
-  };
-  rc = tg_dmalloc(&am_off, a->nrows + 1) || tg_dmalloc(&am_cnt, a->nrows + 1) || tg_dmalloc(&cursor, 2);
-  if (rc) {
-    cleanup();
-    return rc;
-  }
-  // ---- stage 1: the intermediate A M in loose rows
-  rc = gw_mix_columns(m, &m_mix);
-  if (rc) {
-    cleanup();
-    return rc;
-  }
+  // ---- stage 1: the intermediate A M in loose rows (its columns mixed), lengths in am_cnt
+  tg_bump t1("wave kernels, A M");
+  tg_dbuf<int32_t> am_cnt;
+  tg_dbuf<uint32_t> m_mix;
+  TG_TRY(t1.init(a->nrows, false, 2, 4));
+  TG_TRY(am_cnt.alloc(a->nrows + 1));
+  TG_TRY(gw_mix_columns(m, m_mix));
   gw_args P1;
   gw_fill_stage1(P1, a, m, m_mix, m_row0);
-  P1.rows_per_wave = gw_env_int("TIGAR_PTAP_WAVE_RPW1", 8);
+  P1.rows_per_wave = tg_env_int("TIGAR_PTAP_WAVE_RPW1", 8);
   gw_tile_hint(P1, "TIGAR_PTAP_WAVE_TILE1");
   // rows of the temporary at a fixed stride (no atomics) unless the longest row is far above the mean
-  int64_t stride1 = (plan->max_am <= 2.0 * plan->mean_am + 32.0 && gw_env_int("TIGAR_PTAP_WAVE_STRIDED", 1)) ? ((plan->max_am + 7) & ~7) : 0;
-  int64_t cap1 = stride1 ? stride1 * a->nrows : (int64_t)(plan->mean_am * 1.08 * (double)a->nrows) + plan->max_am + 4096;
-  bool done = false;
-  for (int attempt = 0; attempt < 6 && !done; attempt++) {
-    rc = tg_dmalloc(&am_col, cap1 + TG_CSR_PAD) || tg_dmalloc(&am_val, cap1 + TG_CSR_PAD);
-    if (rc) break;
-    P1.ts = plan->ts_am;
-    P1.lgts = gw_lg(plan->ts_am);
-    P1.out_stride = stride1;
-    const size_t lds = 4 * gw_wave_bytes(P1.ts);
-    if (lds > 160 * 1024) {
-      rc = 100;
-      break;
-    }
-    hipMemsetAsync(status, 0, 4 * sizeof(int), g_tg.stream);
-    hipMemsetAsync(cursor, 0, 2 * sizeof(unsigned long long), g_tg.stream);
-    gw_launch<GW_BUMP, false>(plan->lg_m, gw_grid(a->nrows, P1.rows_per_wave), lds, P1, am_off, am_cnt, nullptr, am_col, am_val,
-                              cursor, cap1, nullptr, 0.0, 0, status, sum);
-    int h = 0;
-    unsigned long long used = 0;
-    hipMemcpyAsync(&h, status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream);
-    hipMemcpyAsync(&used, cursor, sizeof(used), hipMemcpyDeviceToHost, g_tg.stream);
-    if (hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-      tg_set_error("PtAP (wave kernels): stage A M failed to run (LDS %zu B)", lds);
-      rc = 1;
-      break;
-    }
-    if (h == GW_RANGE) {
-      tg_set_error("PtAP: a row block does not cover the rows referenced (slab halo too small)");
-      rc = 3;
-      break;
-    }
-    if (getenv("TIGAR_PTAP_WAVE_DEBUG"))
-      fprintf(stderr, "[gw] stage 1 attempt %d: status %d used %llu cap %lld ts %d\n", attempt, h, used, (long long)cap1, plan->ts_am);
-    if (h == GW_OK) {
-      done = true;
-      plan->mean_am = std::max(plan->mean_am, (double)used / (double)a->nrows);
-      break;
-    }
-    tg_dfree(am_col);
-    tg_dfree(am_val);
-    am_col = nullptr;
-    am_val = nullptr;
-    if (h == GW_OVF) {
-      plan->ts_am *= 2;
-      if (!stride1) cap1 = std::max<int64_t>(cap1, (int64_t)used + 4096);
-    } else if (stride1) {
-      int hm = 0;
-      hipMemcpy(&hm, status + 1, sizeof(int), hipMemcpyDeviceToHost);
-      plan->max_am = std::max(plan->max_am, hm);
-      stride1 = (std::max<int64_t>(hm, stride1 + stride1 / 4) + 7) & ~(int64_t)7;
-      cap1 = stride1 * a->nrows;
-    } else {
-      cap1 = std::max<int64_t>((int64_t)used + 4096, cap1 + cap1 / 2);
-    }
+  int64_t stride1 = (plan->max_am <= 2.0 * plan->mean_am + 32.0 && tg_env_int("TIGAR_PTAP_WAVE_STRIDED", 1)) ? ((plan->max_am + 7) & ~7) : 0;
+  t1.capacity = stride1 ? stride1 * a->nrows : (int64_t)(plan->mean_am * 1.08 * (double)a->nrows) + plan->max_am + 4096;
+  size_t lds = 0;
+  rc = t1.run(
+      6,
+      [&](int) {
+        P1.ts = t1.ts[0] = plan->ts_am;
+        P1.lgts = tg_lg(plan->ts_am);
+        P1.out_stride = stride1;
+        lds = 4 * gw_wave_bytes(P1.ts);
+        if (lds > 160 * 1024) return 100;
+        gw_launch<GW_BUMP, false>(plan->lg_m, gw_grid(a->nrows, P1.rows_per_wave), lds, P1, t1.off, am_cnt, nullptr,
+                                  (uint32_t *)t1.tcol.get(), t1.tval, t1.cursor, t1.capacity, nullptr, 0.0, 0, status, sum);
+        return 0;
+      },
+      [&](int, const int *h, unsigned long long used) {
+        if (h[0] == GW_RANGE) {
+          tg_set_error("PtAP: a row block does not cover the rows referenced (slab halo too small)");
+          return 3;
+        }
+        if (h[0] == GW_OK) {
+          plan->mean_am = std::max(plan->mean_am, (double)used / (double)a->nrows);
+          return (int)TG_BUMP_DONE;
+        }
+        if (h[0] == GW_OVF) {
+          plan->ts_am *= 2;
+          if (!stride1) t1.capacity = std::max<int64_t>(t1.capacity, (int64_t)used + 4096);
+        } else if (stride1) {
+          const int hm = h[1];                 // the longest row met
+          plan->max_am = std::max(plan->max_am, hm);
+          stride1 = (std::max<int64_t>(hm, stride1 + stride1 / 4) + 7) & ~(int64_t)7;
+          t1.capacity = stride1 * a->nrows;
+        } else {
+          t1.capacity = std::max<int64_t>((int64_t)used + 4096, t1.capacity + t1.capacity / 2);
+        }
+        return (int)TG_BUMP_RETRY;
+      });
+  if (rc == TG_BUMP_NORUN) {
+    tg_set_error("PtAP (wave kernels): stage A M failed to run (LDS %zu B)", lds);
+    rc = 1;
   }
-  if (!rc && !done) rc = 100;
-  if (rc) {
-    cleanup();
-    return rc;
-  }
-  tg_dfree(m_mix);
-  m_mix = nullptr;
+  if (rc == TG_BUMP_RETRY) rc = 100;
+  if (rc) return rc;
+  m_mix.reset();
   // ---- stage 2: K = M^T (A M), operand rows = the loose rows of the intermediate (FE row r -> r - a_row0)
   gw_args P2;
   P2.x_rowptr = mt->rowptr;
@@ -747,15 +673,15 @@ int tg_ptap_wave_numeric(tg_gw_plan *plan, tg_csr_s *a, int64_t a_row0, tg_csr_s
   P2.x_nrows = mt->nrows;
   P2.row_stride = 1;
   P2.y_start_mix = nullptr;
-  P2.y_start = am_off;
+  P2.y_start = t1.off;
   P2.y_cnt = am_cnt;
-  P2.y_mix = am_col;
-  P2.y_val = am_val;
+  P2.y_mix = (const uint32_t *)t1.tcol.get();
+  P2.y_val = t1.tval;
   P2.y_row0 = a_row0;
   P2.y_nrows = a->nrows;
   P2.debug = P1.debug & ~1;
   P2.out_stride = 0;
-  P2.rows_per_wave = gw_env_int("TIGAR_PTAP_WAVE_RPW2", 2);
+  P2.rows_per_wave = tg_env_int("TIGAR_PTAP_WAVE_RPW2", 2);
   gw_tile_hint(P2, "TIGAR_PTAP_WAVE_TILE2");
   const int64_t nrows = mt->nrows;
   if (plan->k_nnz >= 0) {
@@ -764,7 +690,7 @@ int tg_ptap_wave_numeric(tg_gw_plan *plan, tg_csr_s *a, int64_t a_row0, tg_csr_s
     if (!rc) {
       hipMemcpyAsync(k->rowptr, plan->k_rowptr, (size_t)(nrows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream);
       P2.ts = plan->ts_k;
-      P2.lgts = gw_lg(plan->ts_k);
+      P2.lgts = tg_lg(plan->ts_k);
       hipMemsetAsync(status, 0, 4 * sizeof(int), g_tg.stream);
       gw_launch<GW_PLACED, true>(plan->lg_am, gw_grid(nrows, P2.rows_per_wave), 4 * gw_wave_bytes(P2.ts), P2, k->rowptr, nullptr,
                                  nullptr, (uint32_t *)k->col, k->val, nullptr, 0, mask, diag, mt_row0, status, sum);
@@ -782,87 +708,52 @@ int tg_ptap_wave_numeric(tg_gw_plan *plan, tg_csr_s *a, int64_t a_row0, tg_csr_s
       }
     }
   } else {
-    int64_t stride2 = (plan->max_k <= 2.0 * plan->mean_k + 32.0 && gw_env_int("TIGAR_PTAP_WAVE_STRIDED", 1)) ? ((plan->max_k + 7) & ~7) : 0;
-    int64_t cap2 = stride2 ? stride2 * nrows : (int64_t)(plan->mean_k * 1.05 * (double)nrows) + plan->max_k + 1024;
-    rc = tg_dmalloc(&cnt, nrows + 1) || tg_dmalloc(&off, nrows + 1);
-    done = false;
-    for (int attempt = 0; attempt < 6 && !rc && !done; attempt++) {
-      rc = tg_dmalloc(&tcol, cap2 + TG_CSR_PAD) || tg_dmalloc(&tval, cap2 + TG_CSR_PAD);
-      if (rc) break;
-      P2.ts = plan->ts_k;
-      P2.lgts = gw_lg(plan->ts_k);
-      P2.out_stride = stride2;
-      const size_t lds = 4 * gw_wave_bytes(P2.ts);
-      if (lds > 160 * 1024) {
-        rc = 100;
-        break;
-      }
-      hipMemsetAsync(status, 0, 4 * sizeof(int), g_tg.stream);
-      hipMemsetAsync(cursor, 0, 2 * sizeof(unsigned long long), g_tg.stream);
-      hipMemsetAsync(cnt, 0, (size_t)(nrows + 1) * sizeof(int64_t), g_tg.stream);
-      gw_launch<GW_BUMP, true>(plan->lg_am, gw_grid(nrows, P2.rows_per_wave), lds, P2, off, nullptr, cnt, (uint32_t *)tcol, tval, cursor, cap2,
-                               mask, diag, mt_row0, status, sum);
-      int h = 0;
-      unsigned long long used = 0;
-      hipMemcpyAsync(&h, status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream);
-      hipMemcpyAsync(&used, cursor, sizeof(used), hipMemcpyDeviceToHost, g_tg.stream);
-      if (hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-        tg_set_error("PtAP (wave kernels): stage M^T (A M) failed to run (LDS %zu B)", lds);
-        rc = 1;
-        break;
-      }
-      if (h == GW_RANGE) {
-        tg_set_error("PtAP: a row block does not cover the rows referenced (slab halo too small)");
-        rc = 3;
-        break;
-      }
-      if (getenv("TIGAR_PTAP_WAVE_DEBUG"))
-        fprintf(stderr, "[gw] stage 2 attempt %d: status %d used %llu cap %lld ts %d\n", attempt, h, used, (long long)cap2, plan->ts_k);
-      if (h == GW_OK) {
-        done = true;
-        break;
-      }
-      tg_dfree(tcol);
-      tg_dfree(tval);
-      tcol = nullptr;
-      tval = nullptr;
-      if (h == GW_OVF) {
-        plan->ts_k *= 2;
-        if (!stride2) cap2 = std::max<int64_t>(cap2, (int64_t)used + 1024);
-      } else if (stride2) {
-        int hm = 0;
-        hipMemcpy(&hm, status + 1, sizeof(int), hipMemcpyDeviceToHost);
-        plan->max_k = std::max(plan->max_k, hm);
-        stride2 = (std::max<int64_t>(hm, stride2 + stride2 / 4) + 7) & ~(int64_t)7;
-        cap2 = stride2 * nrows;
-      } else {
-        cap2 = std::max<int64_t>((int64_t)used + 1024, cap2 + cap2 / 2);
-      }
+    tg_bump t2("wave kernels, Mt (A M)");
+    int64_t stride2 = (plan->max_k <= 2.0 * plan->mean_k + 32.0 && tg_env_int("TIGAR_PTAP_WAVE_STRIDED", 1)) ? ((plan->max_k + 7) & ~7) : 0;
+    t2.capacity = stride2 ? stride2 * nrows : (int64_t)(plan->mean_k * 1.05 * (double)nrows) + plan->max_k + 1024;
+    rc = t2.init(nrows, true, 2, 4);
+    if (!rc)
+      rc = t2.run(
+          6,
+          [&](int) {
+            P2.ts = t2.ts[0] = plan->ts_k;
+            P2.lgts = tg_lg(plan->ts_k);
+            P2.out_stride = stride2;
+            lds = 4 * gw_wave_bytes(P2.ts);
+            if (lds > 160 * 1024) return 100;
+            gw_launch<GW_BUMP, true>(plan->lg_am, gw_grid(nrows, P2.rows_per_wave), lds, P2, t2.off, nullptr, t2.cnt,
+                                     (uint32_t *)t2.tcol.get(), t2.tval, t2.cursor, t2.capacity, mask, diag, mt_row0, status, sum);
+            return 0;
+          },
+          [&](int, const int *h, unsigned long long used) {
+            if (h[0] == GW_RANGE) {
+              tg_set_error("PtAP: a row block does not cover the rows referenced (slab halo too small)");
+              return 3;
+            }
+            if (h[0] == GW_OK) return (int)TG_BUMP_DONE;
+            if (h[0] == GW_OVF) {
+              plan->ts_k *= 2;
+              if (!stride2) t2.capacity = std::max<int64_t>(t2.capacity, (int64_t)used + 1024);
+            } else if (stride2) {
+              const int hm = h[1];
+              plan->max_k = std::max(plan->max_k, hm);
+              stride2 = (std::max<int64_t>(hm, stride2 + stride2 / 4) + 7) & ~(int64_t)7;
+              t2.capacity = stride2 * nrows;
+            } else {
+              t2.capacity = std::max<int64_t>((int64_t)used + 1024, t2.capacity + t2.capacity / 2);
+            }
+            return (int)TG_BUMP_RETRY;
+          });
+    if (rc == TG_BUMP_NORUN) {
+      tg_set_error("PtAP (wave kernels): stage M^T (A M) failed to run (LDS %zu B)", lds);
+      rc = 1;
     }
-    if (!rc && !done) rc = 100;
-    if (!rc) {
-      int64_t nnz = 0;
-      rc = tg_exclusive_scan_i64(cnt, nrows, &nnz);
-      if (!rc) rc = tg_csr_alloc(nrows, m->ncols, nnz, &k);
-      if (!rc) {
-        hipMemcpyAsync(k->rowptr, cnt, (size_t)(nrows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream);
-        const unsigned rg = (unsigned)std::min<int64_t>(tg_cdiv(nrows, 4), (int64_t)g_tg.num_cu * 16);
-        hipLaunchKernelGGL(k_gw_reorder, dim3(std::max(1u, rg)), dim3(256), 0, g_tg.stream, k->rowptr, off, tcol, tval, nrows,
-                           k->col, k->val);
-        if (hipGetLastError() != hipSuccess) {
-          tg_set_error("PtAP reorder launch failed");
-          rc = 1;
-        }
-        // remember the pattern for later calls with the same operands' structure
-        tg_dfree(plan->k_rowptr);
-        plan->k_rowptr = cnt;
-        cnt = nullptr;
-        plan->k_nnz = nnz;
-      }
-    }
+    if (rc == TG_BUMP_RETRY) rc = 100;
+    // the scanned counts are the pattern remembered for later calls with the same operands' structure
+    if (!rc) rc = t2.finish_csr("PtAP", m->ncols, &k, &plan->k_rowptr, &plan->k_nnz);
+    hipStreamSynchronize(g_tg.stream);
   }
   hipStreamSynchronize(g_tg.stream);
-  cleanup();
   if (rc) {
     if (k) tg_csr_destroy(k);
     return rc;
@@ -1148,7 +1039,7 @@ static int tg_cellplan_create_common(int64_t ncell, int b, int nfmax, int64_t nc
     return rc;
   }
   const double load_inv = 2.5;
-  pl->gw.ts_k = std::max(64, gw_pow2_ge((int64_t)(max_k * load_inv) + 4));
+  pl->gw.ts_k = std::max(64, tg_pow2_ge((int64_t)(max_k * load_inv) + 4));
   pl->gw.lg_am = gw_lg_group((double)nfmax);
   pl->gw.max_k = max_k;
   pl->gw.mean_k = mean_k;
@@ -1218,47 +1109,28 @@ static int tg_cellplan_ptap_impl(tg_cellplan_t pl, tg_csr_t a, const int64_t *rs
     TG_CHECK_HIP(hipStreamSynchronize(g_tg.stream));
     if (hbad) return 100;                     // not block diagonal with dense b x b blocks: the general kernels
   }
-  uint8_t *mask = nullptr;
-  if (nzero > 0) TG_TRY(tg_build_dof_mask(zero_dofs, nzero, pl->ncols, &mask));
-  double *eval = nullptr;
-  int64_t *cnt = nullptr, *off = nullptr;
-  int32_t *tcol = nullptr;
-  double *tval = nullptr;
-  unsigned long long *cursor = nullptr;
+  tg_dbuf<uint8_t> mask;
+  if (nzero > 0) TG_TRY(tg_build_dof_mask(zero_dofs, nzero, pl->ncols, &mask.p));
+  tg_dbuf<double> eval;
   tg_csr_s *k = nullptr;
-  auto cleanup = [&]() {
-    tg_dfree(eval);
-    tg_dfree(cnt);
-    tg_dfree(off);
-    tg_dfree(tcol);
-    tg_dfree(tval);
-    tg_dfree(cursor);
-    tg_dfree(mask);
-  };
   const int64_t nrowsE = pl->ncell * pl->nfmax;
-  int rc = tg_dmalloc(&eval, nrowsE * pl->nfmax + TG_CSR_PAD) || tg_dmalloc(&cursor, 2);
-  if (rc) {
-    cleanup();
-    return rc;
-  }
+  TG_TRY(eval.alloc(nrowsE * pl->nfmax + TG_CSR_PAD));
+  int rc = 0;
   // ---- element matrices
   {
     const size_t lds = 4 * ((size_t)pl->b * pl->b + 2 * (size_t)pl->b * pl->nfmax) * sizeof(double);
     const unsigned grid = (unsigned)tg_cdiv(pl->ncell, 4);
-    const int lgf = gw_lg(pl->nfmax <= 8 ? 8 : pl->nfmax <= 16 ? 16 : pl->nfmax <= 32 ? 32 : 64);
+    const int lgf = tg_lg(pl->nfmax <= 8 ? 8 : pl->nfmax <= 16 ? 16 : pl->nfmax <= 32 ? 32 : 64);
 #define CELL_GO(LGV)                                                                                                    \
   do {                                                                                                                  \
     hipFuncSetAttribute((const void *)k_cell_element<LGV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);      \
     hipLaunchKernelGGL((k_cell_element<LGV>), dim3(grid), dim3(256), lds, g_tg.stream, a->val, rstart, pl->md, pl->nf,   \
-                       pl->ncell, pl->b, pl->nfmax, eval);                                                              \
+                       pl->ncell, pl->b, pl->nfmax, eval.get());                                                        \
   } while (0)
-    if (lds > 160 * 1024 && rstart) {
-      cleanup();
-      return 100;
-    }
+    if (lds > 160 * 1024 && rstart) return 100;
     if (lds > 160 * 1024) {
       hipLaunchKernelGGL(k_cell_element_big, dim3((unsigned)std::min<int64_t>(pl->ncell, (int64_t)g_tg.num_cu * 64)), dim3(256), 0,
-                         g_tg.stream, a->val, pl->md, pl->nf, pl->ncell, pl->b, pl->nfmax, eval);
+                         g_tg.stream, a->val, pl->md, pl->nf, pl->ncell, pl->b, pl->nfmax, eval.get());
     } else
     switch (lgf) {
       case 3: CELL_GO(3); break;
@@ -1269,7 +1141,6 @@ static int tg_cellplan_ptap_impl(tg_cellplan_t pl, tg_csr_t a, const int64_t *rs
 #undef CELL_GO
     if (hipGetLastError() != hipSuccess) {
       tg_set_error("cell-block PtAP: the element kernel failed to launch");
-      cleanup();
       return 1;
     }
   }
@@ -1297,8 +1168,8 @@ static int tg_cellplan_ptap_impl(tg_cellplan_t pl, tg_csr_t a, const int64_t *rs
   auto merge_by_places = [&](tg_csr_s *kk) -> int {
     const unsigned grid = (unsigned)std::min<int64_t>(tg_cdiv(nrows, 4), (int64_t)g_tg.num_cu * 32);
 #define CELL_MERGE(LGV)                                                                                                         \
-  hipLaunchKernelGGL((k_cell_merge<LGV>), dim3(std::max(1u, grid)), dim3(256), 0, g_tg.stream, pl->inc->rowptr, pl->inc->col, eval, \
-                     pl->slot, pl->nf, pl->nfmax, nrows, kk->rowptr, kk->col, mask, diag, kk->val)
+  hipLaunchKernelGGL((k_cell_merge<LGV>), dim3(std::max(1u, grid)), dim3(256), 0, g_tg.stream, pl->inc->rowptr, pl->inc->col,       \
+                     eval.get(), pl->slot, pl->nf, pl->nfmax, nrows, kk->rowptr, kk->col, mask.get(), diag, kk->val)
     if (pl->nfmax <= 16) CELL_MERGE(4);
     else if (pl->nfmax <= 32) CELL_MERGE(5);
     else CELL_MERGE(6);
@@ -1326,7 +1197,7 @@ static int tg_cellplan_ptap_impl(tg_cellplan_t pl, tg_csr_t a, const int64_t *rs
     if (!rc) {
       hipMemcpyAsync(k->rowptr, plan->k_rowptr, (size_t)(nrows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream);
       P2.ts = plan->ts_k;
-      P2.lgts = gw_lg(plan->ts_k);
+      P2.lgts = tg_lg(plan->ts_k);
       hipMemsetAsync(status, 0, 4 * sizeof(int), g_tg.stream);
       gw_launch_shared<GW_PLACED>(plan->lg_am, gw_grid(nrows, P2.rows_per_wave), 4 * gw_wave_bytes(P2.ts), P2, k->rowptr, nullptr,
                                   (uint32_t *)k->col, k->val, nullptr, 0, mask, diag, status, sum);
@@ -1341,65 +1212,47 @@ static int tg_cellplan_ptap_impl(tg_cellplan_t pl, tg_csr_t a, const int64_t *rs
       }
     }
   } else {
+    tg_bump t("cell-block gather");
     int64_t stride2 = (plan->max_k + 7) & ~7;
-    int64_t cap2 = stride2 * nrows;
-    rc = tg_dmalloc(&cnt, nrows + 1) || tg_dmalloc(&off, nrows + 1);
-    bool done = false;
-    for (int attempt = 0; attempt < 6 && !rc && !done; attempt++) {
-      rc = tg_dmalloc(&tcol, cap2 + TG_CSR_PAD) || tg_dmalloc(&tval, cap2 + TG_CSR_PAD);
-      if (rc) break;
-      P2.ts = plan->ts_k;
-      P2.lgts = gw_lg(plan->ts_k);
-      P2.out_stride = stride2;
-      const size_t lds = 4 * gw_wave_bytes(P2.ts);
-      if (lds > 160 * 1024) {
-        rc = 100;
-        break;
-      }
-      hipMemsetAsync(status, 0, 4 * sizeof(int), g_tg.stream);
-      hipMemsetAsync(cnt, 0, (size_t)(nrows + 1) * sizeof(int64_t), g_tg.stream);
-      gw_launch_shared<GW_BUMP>(plan->lg_am, gw_grid(nrows, P2.rows_per_wave), lds, P2, off, cnt, (uint32_t *)tcol, tval, cursor, cap2,
-                                mask, diag, status, sum);
-      int h[2] = {0, 0};
-      hipMemcpyAsync(h, status, sizeof(h), hipMemcpyDeviceToHost, g_tg.stream);
-      if (hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-        tg_set_error("cell-block PtAP: the gather stage failed to run (LDS %zu B)", lds);
-        rc = 1;
-        break;
-      }
-      if (h[0] == GW_OK) {
-        done = true;
-        break;
-      }
-      tg_dfree(tcol);
-      tg_dfree(tval);
-      tcol = nullptr;
-      tval = nullptr;
-      if (h[0] == GW_OVF)
-        plan->ts_k *= 2;
-      else if (h[0] == GW_CAP) {
-        plan->max_k = std::max(plan->max_k, h[1]);
-        stride2 = (std::max<int64_t>(h[1], stride2 + stride2 / 4) + 7) & ~(int64_t)7;
-        cap2 = stride2 * nrows;
-      } else {
-        tg_set_error("cell-block PtAP: kernel status %d", h[0]);
-        rc = 4;
-      }
+    t.capacity = stride2 * nrows;
+    rc = t.init(nrows, true, 2, 4);
+    size_t lds = 0;
+    if (!rc)
+      rc = t.run(
+          6,
+          [&](int) {
+            P2.ts = t.ts[0] = plan->ts_k;
+            P2.lgts = tg_lg(plan->ts_k);
+            P2.out_stride = stride2;
+            lds = 4 * gw_wave_bytes(P2.ts);
+            if (lds > 160 * 1024) return 100;
+            gw_launch_shared<GW_BUMP>(plan->lg_am, gw_grid(nrows, P2.rows_per_wave), lds, P2, t.off, t.cnt, (uint32_t *)t.tcol.get(), t.tval,
+                                      t.cursor, t.capacity, mask, diag, status, sum);
+            return 0;
+          },
+          [&](int, const int *h, unsigned long long) {
+            if (h[0] == GW_OK) return (int)TG_BUMP_DONE;
+            if (h[0] == GW_OVF)
+              plan->ts_k *= 2;
+            else if (h[0] == GW_CAP) {
+              plan->max_k = std::max(plan->max_k, h[1]);
+              stride2 = (std::max<int64_t>(h[1], stride2 + stride2 / 4) + 7) & ~(int64_t)7;
+              t.capacity = stride2 * nrows;
+            } else {
+              tg_set_error("cell-block PtAP: kernel status %d", h[0]);
+              return 4;
+            }
+            return (int)TG_BUMP_RETRY;
+          });
+    if (rc == TG_BUMP_NORUN) {
+      tg_set_error("cell-block PtAP: the gather stage failed to run (LDS %zu B)", lds);
+      rc = 1;
     }
-    if (!rc && !done) rc = 100;
+    if (rc == TG_BUMP_RETRY) rc = 100;
     if (!rc) {
-      int64_t nnz = 0;
-      rc = tg_exclusive_scan_i64(cnt, nrows, &nnz);
-      if (!rc) rc = tg_csr_alloc(nrows, pl->ncols, nnz, &k);
+      rc = t.finish_csr("cell-block PtAP:", pl->ncols, &k, &plan->k_rowptr, &plan->k_nnz);
       if (!rc) {
-        hipMemcpyAsync(k->rowptr, cnt, (size_t)(nrows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream);
-        const unsigned rg = (unsigned)std::min<int64_t>(tg_cdiv(nrows, 4), (int64_t)g_tg.num_cu * 16);
-        hipLaunchKernelGGL(k_gw_reorder, dim3(std::max(1u, rg)), dim3(256), 0, g_tg.stream, k->rowptr, off, tcol, tval, nrows, k->col,
-                           k->val);
-        tg_dfree(plan->k_rowptr);
-        plan->k_rowptr = cnt;
-        cnt = nullptr;
-        plan->k_nnz = nnz;
+        const int64_t nnz = plan->k_nnz;
         // the places of the element entries in their rows of K, for all later products -- and for THIS one: its values
         // are formed again by places, so that every product on the plan adds in the same order (bit for bit the same K)
         if (plan->max_k < (pl->nfmax > 32 ? TG_CELL_ROWCAP : 256) && nnz < 0x7fffffffll * 4 && !getenv("TIGAR_CELL_MERGE_HASH")) {
@@ -1430,7 +1283,6 @@ static int tg_cellplan_ptap_impl(tg_cellplan_t pl, tg_csr_t a, const int64_t *rs
     }
   }
   hipStreamSynchronize(g_tg.stream);
-  cleanup();
   if (rc) {
     if (k) tg_csr_destroy(k);
     return rc;
