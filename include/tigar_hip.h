@@ -233,9 +233,19 @@ int tg_spmv_symgrid(tg_csr_t a, int64_t row0, tg_vec_t x, tg_vec_t y, int *accep
  * info[12]: [0] 1 = delta-coded, [1] parts (32 rows of a sub-step; radius 4: 16) a product reads, [2] parts stored as
  * deltas, [3] reference plane (global index: the plane of the block nearest n2 / 2), [4] template bytes, [5] delta bytes,
  * [6] pool bytes in use (fp64 parts that did not fit), [7] pool capacity in parts, [8] largest distance of a part that
- * fits, [9] value bytes one product reads from HBM, [10] bytes the values occupy, [11] 0. */
+ * fits, [9] value bytes one product reads from HBM, [10] bytes the values occupy, [11] z chunks of the plan. */
 int tg_spmv_symgrid_delta(tg_csr_t a, int64_t row0, tg_vec_t x, tg_vec_t y, int *accepted, int64_t *value_bytes,
                           int64_t *staging_bytes, int64_t *info);
+/* How the scalar half-storage product of radius P (1..4; coded: the delta-coded plan's kernel, else the plain one) fills
+ * the chip -- out[8]: [0] workgroups (one wave each) a CU holds, as hipOccupancyMaxActiveBlocksPerMultiprocessor reports for
+ * that kernel, [1] its static LDS bytes, [2] places = [0] x the CUs, [3] the z chunks the plan builder chooses for a whole
+ * grid of n0 x n1 x n2 points on those places (TIGAR_SYMGRID_CHUNKS overrides it here as it does there; 0 when n0 <= 0),
+ * [4], [5] the largest patch (points in x, y), [6] CUs, [7] 0.  Host arithmetic and two runtime queries: no plan is built. */
+int tg_symgrid_occupancy(int P, int coded, int n0, int n1, int n2, int64_t *out);
+/* The scalar half-storage plan this process built last (by tg_spmv_symgrid* or by a CG solve) -- out[4]: [0] its radius P
+ * (0: none built yet), [1] its z chunks, [2] the places its builder chose them for, [3] the workgroups per CU behind [2]
+ * (the fewer of the plain and the delta-coded kernel's when the coding was tried, else the plain kernel's). */
+int tg_symgrid_last_plan(int64_t *out);
 /* Y = A X for k <= 4 right-hand sides (cpFuncs = M_control * P, tIGAr/common.py:367-380);
  * X, Y are column-major host arrays. */
 int tg_spmm_host(tg_csr_t a, const double *X, int k, double *Y);

@@ -127,6 +127,8 @@ PROTOTYPES = {
     "tg_spmv_symgrid": (C.c_int, [handle, C.c_int64, handle, handle, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tg_spmv_symgrid_delta": (C.c_int, [handle, C.c_int64, handle, handle, C.POINTER(C.c_int), C.POINTER(C.c_int64),
                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tg_symgrid_occupancy": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "tg_symgrid_last_plan": (C.c_int, [C.POINTER(C.c_int64)]),
     "tg_spmm_host": (C.c_int, [handle, c_f64p, C.c_int, c_f64p]),
     "tg_spmv_t": (C.c_int, [handle, handle, handle]),
     "tg_ptap_symbolic": (C.c_int, [handle, C.c_int64, handle, C.c_int64, handle, C.c_int64,

@@ -10,9 +10,9 @@
 //     y[i+off]   += K[i][i+off] * x[i]           (the transposed entry),
 //
 // so a product moves HALF the bytes.  The second line is a scatter; what makes it cheap is the geometry, not the CSR
-// arrays: the grid is cut into patches of at most 24 x 16 points in (x, y), a wave owns one patch and walks it plane by
+// arrays: the grid is cut into patches of at most 20 x 16 points in (x, y), a wave owns one patch and walks it plane by
 // plane along z.  Everything the wave scatters lands in the window (patch + P points on every side) of the current and
-// the next P planes, which it keeps in LDS as a ring of P + 1 planes (21 KB for P = 3, beside a ring of the same planes of
+// the next P planes, which it keeps in LDS as a ring of P + 1 planes (18 KB for P = 3, beside a ring of the same planes of
 // x) and adds to by read - add - write -- one wave per window, LDS operations of a wave complete in order, so the sums are
 // the same bit for bit in every run.  When
 // a plane is finished its window goes to a staging array (1 % of the value bytes); a second small kernel adds, for
@@ -33,13 +33,15 @@
 #include <vector>
 
 #ifndef SG_PX
-#define SG_PX 24          // widest / highest patch (points), P <= 3
+#define SG_PX 20          // widest / highest patch (points), P <= 3: 320 rows = five sub-steps of 64, and at P = 3 two rings of
+                          // four 26 x 22 windows + tab = 37 248 B of LDS -- FOUR workgroups per CU, a wave on every SIMD (24 x 16:
+                          // 43 008 B, three)
 #endif
 #ifndef SG_PY
 #define SG_PY 16
 #endif
 // P = 4 (round 6; 3-D quartics: 729 entries per row, 365 stored): patches of 16 x 12 points -- two rings of five window
-// planes of 24 x 20 entries are 38 KB, as many waves per CU as at P = 3 (with 24 x 16 patches: 61 KB, two waves)
+// planes of 24 x 20 entries are 38 KB, four waves per CU as at P = 3 (with 24 x 16 patches: 61 KB, two waves)
 #define SG_PX4 16
 #define SG_PY4 12
 
@@ -118,6 +120,8 @@ struct tg_symgrid_s {
   int n2g = 0, zoff = 0;                 // planes of the whole grid, first plane of the block (several ranks: z slabs)
   int64_t row0 = 0;
   int npx = 0, npy = 0, nch = 0, m = 0, czmax = 0;
+  int64_t places = 0;           // waves of the product kernel the chip holds (scalar plan: what the chunks were chosen for)
+  int per_cu = 0;               // ... per CU
   int32_t *tabs = nullptr;      // device: x0[npx+1] | y0[npy+1] | z0[nch+1] | px_of[n0] | py_of[n1] | pc_of[n2]
   sg_d2 *val = nullptr;         // [patch][plane][sub-step][pair][lane]
   double *stage = nullptr;      // [patch][chunk][plane of the chunk + P][W]
@@ -391,8 +395,8 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---- the product: one wave per (patch, z chunk).  Two rings of P + 1 window planes in LDS: the sums (current plane and
-// the P planes the transposed entries reach) and the x the wave multiplies with (loaded once per plane, 43 KB together at
-// P = 3 -> 3 waves per CU).  For a stored value a = K[i][i+off] ONE window index serves both uses: sum_i += a * xs[idx],
+// the P planes the transposed entries reach) and the x the wave multiplies with (loaded once per plane, 36.4 KB together at
+// P = 3 -> 4 waves per CU, one per SIMD; sg_occupancy asks the runtime).  For a stored value a = K[i][i+off] ONE window index serves both uses: sum_i += a * xs[idx],
 // acc[idx] += a * x_i.  The vector memory pipe carries the value stream only; its loads are issued three batches (18 KB
 // per wave) before they are multiplied.  (With x gathered from global memory -- 171 gathers per row through the L1, whose
 // 32 KB do not hold the windows of the waves of a CU -- the product took 0.55 ms longer at cfg3's size, and vmcnt, which
@@ -1137,17 +1141,20 @@ static int sg_detect_multi(tg_csr_s *a, int *nfo, int *Pout, int *n0o, int *n1o,
   return 0;
 }
 
-// patches, chunks and their tables for an n0 x n1 x n2 grid cut into px x py patches (what tg_symgrid_build does inline for
-// the scalar plan); staging for `overhang` planes of windows beyond a chunk
-static int sg_geometry(tg_symgrid_s *s, int px, int py, int overhang, int W) {
+// patches, chunks and their tables for an n0 x n1 x n2 grid cut into px x py patches; staging for `overhang` planes of
+// windows beyond a chunk.  nch > 0: that many z chunks (the scalar plan: sg_choose_chunks); 0: the rule of the
+// several-field plan.  tables (may be nullptr): the host copy of the tables, x0 at 0, y0 at npx + 1.  100: no room (declined)
+static int sg_geometry(tg_symgrid_s *s, int px, int py, int overhang, int W, int nch, std::vector<int32_t> *tables) {
   const int n0 = s->n0, n1 = s->n1, n2 = s->n2, P = s->P;
   s->npx = (n0 + px - 1) / px;
   s->npy = (n1 + py - 1) / py;
   const int64_t npatch = (int64_t)s->npx * s->npy;
-  int want = getenv("TIGAR_SYMGRID_CHUNKS") ? atoi(getenv("TIGAR_SYMGRID_CHUNKS")) : 0;
+  int want = nch > 0 ? nch : getenv("TIGAR_SYMGRID_CHUNKS") ? atoi(getenv("TIGAR_SYMGRID_CHUNKS")) : 0;
   if (want <= 0) want = (int)std::max<int64_t>(n2 / 12, tg_cdiv((int64_t)g_tg.num_cu * 2, npatch));
   s->nch = std::max(1, std::min(want, n2 / std::max(P, 4)));
-  std::vector<int32_t> h;
+  std::vector<int32_t> own;
+  std::vector<int32_t> &h = tables ? *tables : own;
+  h.clear();
   auto split = [&](int n, int parts) {
     for (int k = 0; k <= parts; k++) h.push_back((int32_t)((int64_t)k * n / parts));
   };
@@ -1265,7 +1272,7 @@ static int sg_build_multi(tg_csr_s *a, int verify, tg_symgrid_s **out) {
       g->P = P, g->n0 = n0, g->n1 = n1, g->n2 = n2, g->n2g = n2, g->zs = s->zs;
       const int W = k == 0 ? (P == 1 ? sg_c<1>::W : P == 2 ? sg_c<2>::W : sg_c<3>::W)
                            : (P == 1 ? sg_cf<1>::W : P == 2 ? sg_cf<2>::W : sg_cf<3>::W);
-      rc = sg_geometry(g, k == 0 ? SG_PX : SG_PX4, k == 0 ? SG_PY : SG_PY4, k == 0 ? P : 2 * P, W);
+      rc = sg_geometry(g, k == 0 ? SG_PX : SG_PX4, k == 0 ? SG_PY : SG_PY4, k == 0 ? P : 2 * P, W, 0, nullptr);
       if (rc) break;
       s->stage_bytes += g->stage_bytes;
     }
@@ -1432,6 +1439,59 @@ static int sg_try_delta(tg_symgrid_s *s, tg_csr_s *a, int *fail, const int32_t *
   return rc;
 }
 
+// ---- how many waves of the scalar product the chip holds, and the z chunks that follow from it
+static int64_t g_sg_last[4] = {0, 0, 0, 0};      // the scalar plan built last: P, chunks, places, workgroups per CU (tg_symgrid_last_plan)
+static const void *sg_spmv_kernel(int P, bool coded) {
+  switch (P) {
+    case 1: return coded ? (const void *)k_symgrid_spmv<1, true> : (const void *)k_symgrid_spmv<1, false>;
+    case 2: return coded ? (const void *)k_symgrid_spmv<2, true> : (const void *)k_symgrid_spmv<2, false>;
+    case 4: return coded ? (const void *)k_symgrid_spmv<4, true> : (const void *)k_symgrid_spmv<4, false>;
+    default: return coded ? (const void *)k_symgrid_spmv<3, true> : (const void *)k_symgrid_spmv<3, false>;
+  }
+}
+// workgroups (= waves) of the product kernel a CU holds, as the runtime counts them for the instantiation that runs, and
+// its static LDS; places = that x the CUs
+static int sg_occupancy(int P, bool coded, int *per_cu, int64_t *lds_bytes) {
+  const void *k = sg_spmv_kernel(P, coded);
+  int nb = 0;
+  hipFuncAttributes fa;
+  TG_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64, 0));
+  TG_CHECK_HIP(hipFuncGetAttributes(&fa, k));
+  if (nb < 1) {
+    tg_set_error("tg_symgrid: the runtime reports that no workgroup of the product kernel (P = %d, %s) fits a CU", P,
+                 coded ? "delta-coded" : "plain");
+    return 1;
+  }
+  *per_cu = nb;
+  if (lds_bytes) *lds_bytes = (int64_t)fa.sharedSizeBytes;
+  return 0;
+}
+// z chunks of a scalar plan.  The npatch x c waves of a product are equally long and run in rounds of `places`; a chunk
+// costs its n2 / c planes and a start (P + 1 planes of x loaded, P planes of windows more to stage and to sum):
+//     cost(c) = rounds x (n2 / c + start),   rounds = ceil(npatch c / places).
+// Measured on the delta-coded and on the plain kernel at 259^3 points, P = 3, for 24 x 16, 20 x 16, 16 x 16, 16 x 12 and
+// 16 x 8 patches (profiles/symgrid_occupancy_cfg3_summary.md): the rounds are real at every count, not only below three
+// (20 x 16, 1024 places: 9 / 13 / 18 chunks = 1.94 / 2.81 / 3.88 rounds 2.60 / 2.60 / 2.57 ms, but 8 / 12 / 21 chunks = 1.73 /
+// 2.59 / 4.53 rounds 2.87 / 2.80 / 2.66 ms: a part-empty round costs most of a full one, later rounds overlap a little),
+// and the start is small -- full rounds of 29, 20 and 14 planes take the same time, which fits start = -0.4 .. 0 planes;
+// by the instructions of a start it is a fraction of a plane.  Half a plane is used: it decides between counts whose rounds
+// are equally full for the fewer chunks (less staging, less for k_symgrid_combine to add).
+// slab: the block is the z slab of one of several ranks -- all chunks but the last run beside the halo exchange
+// (tg_symgrid_spmv, part 1 / 2), so there are two where the planes allow it.  TIGAR_SYMGRID_CHUNKS overrides the choice.
+static constexpr double SG_CHUNK_START = 0.5;
+static int sg_choose_chunks(int P, int64_t npatch, int n2, int64_t places, bool slab) {
+  const int cmax = std::max(1, n2 / std::max(P, 4));
+  const int want = getenv("TIGAR_SYMGRID_CHUNKS") ? atoi(getenv("TIGAR_SYMGRID_CHUNKS")) : 0;
+  if (want > 0) return std::min(want, cmax);
+  double best = 1e300;
+  int pick = cmax;
+  for (int c = slab ? std::min(2, cmax) : 1; c <= cmax; c++) {
+    const double cost = (double)tg_cdiv(npatch * c, places) * ((double)n2 / c + SG_CHUNK_START);
+    if (cost < best - 1e-9) best = cost, pick = c;
+  }
+  return pick;
+}
+
 // Builds the plan for the rows [row0, row0 + nrows) of a square matrix (the whole matrix, or the z slab of planes one
 // rank holds: whole planes of the grid); *out stays nullptr when the matrix is not a symmetric box stencil on a 3-D grid
 // (or there is no room for the copy).  verify: compare with the CSR product on a pseudo-random vector.
@@ -1450,77 +1510,33 @@ int tg_symgrid_build(tg_csr_s *a, int64_t row0, int verify, tg_symgrid_s **out) 
     if (trace) fprintf(stderr, "[trace] symgrid: no 3-D box stencil found (%lld rows)\n", (long long)a->nrows);
     return 0;
   }
+  // places of the kernel that will run: the plain one, or -- the coding is tried first and may be declined -- the fewer of
+  // the two (the rings are the same: they hold as many waves, tests/test_gpu_symgrid_occupancy.py)
+  int per_cu = 0, per_cu_coded = 0;
+  int64_t lds_bytes = 0;
+  TG_TRY(sg_occupancy(P, false, &per_cu, &lds_bytes));
+  if (!(getenv("TIGAR_SYMGRID_DELTA") && atoi(getenv("TIGAR_SYMGRID_DELTA")) == 0)) {
+    TG_TRY(sg_occupancy(P, true, &per_cu_coded, &lds_bytes));
+    per_cu = std::min(per_cu, per_cu_coded);
+  }
+  const int64_t places = (int64_t)g_tg.num_cu * per_cu;
   tg_symgrid_s *s = new tg_symgrid_s;
   s->P = P, s->n0 = n0, s->n1 = n1, s->n2 = n2;
   s->row0 = row0, s->zoff = (int)(row0 / ((int64_t)n0 * n1)), s->n2g = (int)(a->ncols / ((int64_t)n0 * n1));
-  s->npx = (n0 + sg_px(P) - 1) / sg_px(P);
-  s->npy = (n1 + sg_py(P) - 1) / sg_py(P);
-  const int64_t npatch = (int64_t)s->npx * s->npy;
-  {
-    int want = getenv("TIGAR_SYMGRID_CHUNKS") ? atoi(getenv("TIGAR_SYMGRID_CHUNKS")) : 0;
-    // (measured, 64^3 .. 256^3, p = 2, 3: chunks of 11-13 planes are best -- a chunk pays for P extra window planes and
-    // the start of its load pipeline -- as long as there are about two waves per CU)
-    const bool chosen = want > 0;
-    if (want <= 0) want = (int)std::max<int64_t>(n2 / 12, tg_cdiv((int64_t)g_tg.num_cu * 2, npatch));
-    const int minplanes = std::max(P, 4);
-    s->nch = std::max(1, std::min(want, n2 / minplanes));
-    // Few planes (the z slab of one of several ranks, a short patch): the waves of a product are one or two rounds of what
-    // the chip holds, and the number of chunks decides how full the last round is -- 67 planes of cfg3's grid: 5 chunks
-    // (935 waves on 768 places) 1.38 ms, 4 chunks (748 waves) 1.15 ms.  Cost of a choice: rounds x (planes per chunk + the P + 1
-    // planes a chunk pays for its start); with three rounds or more the rounds overlap and the 11-13 planes above stand.
-    const int64_t lds_wave = (int64_t)2 * (P + 1) * (sg_px(P) + 2 * P) * (sg_py(P) + 2 * P) * 8 + 1024;
-    const int64_t places = (int64_t)g_tg.num_cu * std::max<int64_t>(1, std::min<int64_t>(8, (160 * 1024) / lds_wave));
-    if (!chosen && npatch * s->nch < 3 * places) {
-      double best = 1e300;
-      int pick = s->nch;
-      for (int c = 1; c <= std::max(1, n2 / minplanes); c++) {
-        const double cost = (double)tg_cdiv(npatch * c, places) * ((double)n2 / c + P + 1);
-        if (cost < best - 1e-9) best = cost, pick = c;
-      }
-      s->nch = pick;
-    }
-  }
-  std::vector<int32_t> h;
-  auto split = [&](int n, int parts) {
-    for (int k = 0; k <= parts; k++) h.push_back((int32_t)((int64_t)k * n / parts));
-  };
-  const size_t ox = 0;
-  split(n0, s->npx);
-  const size_t oy = h.size();
-  split(n1, s->npy);
-  const size_t oz = h.size();
-  split(n2, s->nch);
-  auto owner = [&](size_t o, int parts, int n) {
-    int k = 0;
-    for (int i = 0; i < n; i++) {
-      while (k + 1 < parts && h[o + k + 1] <= i) k++;
-      h.push_back(k);
-    }
-  };
-  owner(ox, s->npx, n0);
-  owner(oy, s->npy, n1);
-  owner(oz, s->nch, n2);
-  int cmax = 0;
-  for (int x = 0; x < s->npx; x++)
-    for (int y = 0; y < s->npy; y++) cmax = std::max(cmax, (h[ox + x + 1] - h[ox + x]) * (h[oy + y + 1] - h[oy + y]));
-  s->m = (cmax + 63) / 64;
-  for (int c = 0; c < s->nch; c++) s->czmax = std::max(s->czmax, h[oz + c + 1] - h[oz + c]);
+  s->places = places, s->per_cu = per_cu;
+  const int64_t npatch = (int64_t)tg_cdiv(n0, sg_px(P)) * tg_cdiv(n1, sg_py(P));
   const int NG = P == 1 ? sg_c<1>::NG : P == 2 ? sg_c<2>::NG : P == 4 ? sg_c<4>::NG : sg_c<3>::NG;
   const int W = P == 1 ? sg_c<1>::W : P == 2 ? sg_c<2>::W : P == 4 ? sg_c<4>::W : sg_c<3>::W;
-  s->val_bytes = npatch * n2 * s->m * (int64_t)NG * 64 * 16;
-  s->stage_bytes = npatch * s->nch * (int64_t)(s->czmax + P) * W * 8;
   s->rows_stored = a->nrows;
+  std::vector<int32_t> h;          // host copy of the tables: x0 at 0, y0 at npx + 1
   int rc = 0;
   bool declined = false;
   do {
-    if ((rc = tg_dmalloc(&s->tabs, (int64_t)h.size()))) break;
-    if ((rc = tg_h2d_staged(s->tabs, h.data(), h.size() * sizeof(int32_t)))) break;
+    rc = sg_geometry(s, sg_px(P), sg_py(P), P, W, sg_choose_chunks(P, npatch, n2, places, n2 < s->n2g), &h);
+    if (rc == 100) rc = 0, declined = true;      // no room: not an error
+    if (rc || declined) break;
+    s->val_bytes = npatch * n2 * s->m * (int64_t)NG * 64 * 16;
     void *p = nullptr;
-    if (tg_dmalloc_bytes(&p, (size_t)s->stage_bytes)) {
-      declined = true;      // no room: not an error
-      break;
-    }
-    s->stage = (double *)p;
     int *ctl = (int *)(g_tg.scratch + 64);
     int hflag[2] = {0, 0};
     if (hipMemcpyAsync(ctl, hflag, sizeof(hflag), hipMemcpyHostToDevice, g_tg.stream) != hipSuccess) {
@@ -1529,7 +1545,7 @@ int tg_symgrid_build(tg_csr_s *a, int64_t row0, int verify, tg_symgrid_s **out) 
     }
     // the delta-coded values first; a matrix they do not suit (or TIGAR_SYMGRID_DELTA=0) gets the fp64 blocks of every plane
     bool coded = false;
-    if ((rc = sg_try_delta(s, a, ctl, h.data() + ox, h.data() + oy, &coded))) break;
+    if ((rc = sg_try_delta(s, a, ctl, h.data(), h.data() + s->npx + 1, &coded))) break;
     if (!coded) {
       if (tg_dmalloc_bytes(&p, (size_t)s->val_bytes)) {
         declined = true;
@@ -1600,6 +1616,10 @@ int tg_symgrid_build(tg_csr_s *a, int64_t row0, int verify, tg_symgrid_s **out) 
   if (trace)
     fprintf(stderr, "[trace] symgrid: P=%d grid %d x %d x %d (planes %d..%d of %d), %d x %d patches, %d chunks, %d sub-steps, values %.2f GB, staging %.2f GB\n",
             P, n0, n1, n2, s->zoff, s->zoff + n2, s->n2g, s->npx, s->npy, s->nch, s->m, s->val_bytes / 1e9, s->stage_bytes / 1e9);
+  if (trace)
+    fprintf(stderr, "[trace] symgrid: %d workgroups per CU (%lld B of LDS each), %lld places: %lld waves, %.2f rounds\n", per_cu,
+            (long long)lds_bytes, (long long)places, (long long)(npatch * s->nch), (double)(npatch * s->nch) / (double)places);
+  g_sg_last[0] = P, g_sg_last[1] = s->nch, g_sg_last[2] = places, g_sg_last[3] = per_cu;
   *out = s;
   return 0;
 }
@@ -1632,7 +1652,7 @@ static void sg_info_delta(const tg_symgrid_s *s, int64_t *info) {
   // the deltas of the lanes that hold a row, the misfits in fp64, the template once
   info[9] = on ? vb / 4 + info[6] + s->tmpl_bytes : vb;
   info[10] = on ? s->tmpl_bytes + s->dlt_bytes + s->pool_bytes + s->mis_bytes : (s->nf == 1 ? s->val_bytes : vb);
-  info[11] = 0;
+  info[11] = s->nf == 1 ? s->nch : 1;
 }
 
 /* Plans the half-storage product for a matrix -- or for the block of rows [row0, row0 + nrows) of one, whole planes of
@@ -1676,4 +1696,26 @@ extern "C" int tg_spmv_symgrid_delta(tg_csr_t a, int64_t row0, tg_vec_t x, tg_ve
                                      int64_t *staging_bytes, int64_t *info) {
   TG_REQUIRE(info, "null argument to tg_spmv_symgrid_delta");
   return sg_spmv_entry(a, row0, x, y, accepted, value_bytes, staging_bytes, info);
+}
+/* see include/tigar_hip.h */
+extern "C" int tg_symgrid_occupancy(int P, int coded, int n0, int n1, int n2, int64_t *out) {
+  TG_REQUIRE_INIT();
+  TG_REQUIRE(out && P >= 1 && P <= 4, "tg_symgrid_occupancy: radius 1..4 and an output array");
+  int per_cu = 0;
+  int64_t lds_bytes = 0;
+  TG_TRY(sg_occupancy(P, coded != 0, &per_cu, &lds_bytes));
+  const int64_t places = (int64_t)g_tg.num_cu * per_cu;
+  out[0] = per_cu, out[1] = lds_bytes, out[2] = places, out[3] = 0;
+  out[4] = sg_px(P), out[5] = sg_py(P), out[6] = g_tg.num_cu, out[7] = 0;
+  if (n0 > 0 && n1 > 0 && n2 > 0) {
+    const int64_t npatch = (int64_t)tg_cdiv(n0, sg_px(P)) * tg_cdiv(n1, sg_py(P));
+    out[3] = sg_choose_chunks(P, npatch, n2, places, false);
+  }
+  return 0;
+}
+/* see include/tigar_hip.h */
+extern "C" int tg_symgrid_last_plan(int64_t *out) {
+  TG_REQUIRE(out, "null argument to tg_symgrid_last_plan");
+  for (int i = 0; i < 4; i++) out[i] = g_sg_last[i];
+  return 0;
 }

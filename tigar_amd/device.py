@@ -307,7 +307,8 @@ class DeviceCSR(object):
         delta-coded), "staging_bytes": ..., and the account of the delta coding (TIGAR_SYMGRID_DELTA): "compressed",
         "compressed_share" (parts stored as int16 deltas / parts a product reads), "parts", "parts_compressed",
         "reference_plane" (global index), "template_bytes", "delta_bytes", "pool_bytes", "pool_capacity_parts",
-        "max_fit_distance", "hbm_value_bytes" (what a product really reads of K from HBM), "stored_value_bytes"}."""
+        "max_fit_distance", "hbm_value_bytes" (what a product really reads of K from HBM), "stored_value_bytes", "chunks" (z chunks
+        of the plan)}."""
         ok, vb, sb = C.c_int(0), C.c_int64(0), C.c_int64(0)
         info = (C.c_int64 * 12)()
         if x is not None and y is None:
@@ -321,7 +322,7 @@ class DeviceCSR(object):
                    "compressed_share": (info[2] / info[1]) if info[1] else 0.0, "parts": info[1], "parts_compressed": info[2],
                    "reference_plane": info[3], "template_bytes": info[4], "delta_bytes": info[5], "pool_bytes": info[6],
                    "pool_capacity_parts": info[7], "max_fit_distance": info[8], "hbm_value_bytes": info[9],
-                   "stored_value_bytes": info[10]}
+                   "stored_value_bytes": info[10], "chunks": info[11]}
 
     def mult_offset(self, x, x_col0, y=None):
         """y = A x where x holds only the columns [x_col0, x_col0+len(x)) (slab pieces)"""
@@ -1199,6 +1200,30 @@ def device_info():
     ncu, hbm = C.c_int(), C.c_int64()
     check(_lib.lib().tg_device_info(name, 256, C.byref(ncu), C.byref(hbm)))
     return {"name": name.value.decode(), "num_cu": ncu.value, "hbm_bytes": hbm.value}
+
+
+def symgrid_occupancy(reach, coded=True, grid=None):
+    """How the scalar half-storage product of stencil radius ``reach`` fills the chip (tg_symgrid_occupancy; ``coded``: the
+    kernel of the delta-coded plan, else of the plain one): {"workgroups_per_cu" (the runtime's occupancy query),
+    "lds_bytes" (static LDS of the kernel), "places" (waves the chip holds), "num_cu", "patch" (largest patch, points in x and
+    y)} and, with ``grid`` = (n0, n1, n2), "chunks": the z chunks the plan builder chooses for that grid.  No plan is built."""
+    out = (C.c_int64 * 8)()
+    n0, n1, n2 = grid if grid is not None else (0, 0, 0)
+    check(_lib.lib().tg_symgrid_occupancy(int(reach), 1 if coded else 0, int(n0), int(n1), int(n2), out), "tg_symgrid_occupancy")
+    res = {"workgroups_per_cu": out[0], "lds_bytes": out[1], "places": out[2], "num_cu": out[6], "patch": (out[4], out[5])}
+    if grid is not None:
+        res["chunks"] = out[3]
+    return res
+
+
+def symgrid_last_plan():
+    """The scalar half-storage plan built last in this process, by ``mult_symgrid`` or by a CG solve (tg_symgrid_last_plan):
+    {"reach", "chunks", "places" (what the builder chose the chunks for), "workgroups_per_cu"}; None before the first."""
+    out = (C.c_int64 * 4)()
+    check(_lib.lib().tg_symgrid_last_plan(out), "tg_symgrid_last_plan")
+    if out[0] == 0:
+        return None
+    return {"reach": out[0], "chunks": out[1], "places": out[2], "workgroups_per_cu": out[3]}
 
 
 def pool_stats():
