@@ -622,6 +622,25 @@ int tg_feorder_destroy(tg_feorder_t h);
 int tg_csr_permute_sym(tg_feorder_t h, tg_csr_t a, int inverse, tg_csr_t *out);
 int tg_vec_permute(tg_feorder_t h, tg_vec_t x, tg_vec_t y, int to_caller);
 
+/* ---- time integration (csrc/tg_timeint.hip, tigar_amd/timeIntegration.py; tIGAr/timeIntegration.py) ----------------
+ * tg_vec_lincomb: out = sum_{i<k} coef[i] v[i] in one pass, 1 <= k <= 8, all of one size; coef and v are host arrays.
+ * out may be any of the v[i].  Fixed order (s = coef[0] v[0], then s = fma(coef[i], v[i], s)): same inputs, same bits.
+ * tg_state_advance: the state update at the end of a step, in place and in registers:
+ *   v = c[0] x + c[1] x_old + c[2] xdot_old + c[3] xddot_old,  a = c[4] v + c[5] xdot_old + c[6] xddot_old,
+ *   then x_old = x, xdot_old = v, xddot_old = a.  order == 1: xddot_old is NULL, c[3] and the `a` line are ignored.
+ *   c: 7 host doubles.  x is not written; the vectors must be distinct (status 2 otherwise).
+ * tg_csr_pair_create: two matrices on ONE sparsity pattern (row pointers and columns compared on the device once;
+ *   status 2 when they differ).  The pair borrows the two handles: they must outlive it and keep their pattern.
+ * tg_spmv_pair: y = y0 - A xa - B xb; y0 may be NULL (= 0), y may be y0, y must differ from xa and xb.  Every stored
+ *   entry is read once: one column, two values (20 B instead of 2 x 12 B), and y is passed over once.  Runs on A's
+ *   CSR row-block plan (or a wave per row when a row exceeds it); bit-reproducible. */
+typedef struct tg_csr_pair_s *tg_csr_pair_t;
+int tg_vec_lincomb(tg_vec_t out, int k, const double *coef, const tg_vec_t *v);
+int tg_state_advance(int order, const double *c, tg_vec_t x, tg_vec_t x_old, tg_vec_t xdot_old, tg_vec_t xddot_old);
+int tg_csr_pair_create(tg_csr_t A, tg_csr_t B, tg_csr_pair_t *out);
+int tg_csr_pair_destroy(tg_csr_pair_t p);
+int tg_spmv_pair(tg_csr_pair_t p, tg_vec_t xa, tg_vec_t xb, tg_vec_t y0, tg_vec_t y);
+
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) --------- */
 int tg_comm_unique_id(char *id128);                          /* ncclGetUniqueId   */
 int tg_comm_create(const char *id128, int rank, int world, tg_comm_t *out);

@@ -17,3 +17,4 @@ from .common import (AbstractExtractionGenerator, AbstractCoordinateChartSpline,
 from .NURBS import NURBSControlMesh      # noqa: E402,F401
 from .fastdiag import FastDiagonalization  # noqa: E402,F401
 from .eigen import SLEPcEigenSolver  # noqa: E402,F401
+from . import timeIntegration  # noqa: E402,F401

@@ -241,6 +241,11 @@ PROTOTYPES = {
     "tg_feorder_destroy": (C.c_int, [handle]),
     "tg_csr_permute_sym": (C.c_int, [handle, handle, C.c_int, C.POINTER(handle)]),
     "tg_vec_permute": (C.c_int, [handle, handle, handle, C.c_int]),
+    "tg_vec_lincomb": (C.c_int, [handle, C.c_int, c_f64p, C.POINTER(handle)]),
+    "tg_state_advance": (C.c_int, [C.c_int, c_f64p, handle, handle, handle, handle]),
+    "tg_csr_pair_create": (C.c_int, [handle, handle, C.POINTER(handle)]),
+    "tg_csr_pair_destroy": (C.c_int, [handle]),
+    "tg_spmv_pair": (C.c_int, [handle, handle, handle, handle, handle]),
 }
 
 _lib = None

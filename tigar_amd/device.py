@@ -206,11 +206,26 @@ class DeviceCSR(object):
         return sp.csr_matrix((val[:cnt], col[:cnt], rowptr), shape=(n, self.shape[1]))
 
     def combine(self, a, other, b, colscale=None):
-        """a*self + b*other*diag(colscale) for two matrices on one pattern (checked on the device)"""
+        """a*self + b*other*diag(colscale) for two matrices on one pattern (checked on the device).  Without a column
+        scaling the result keeps what BOTH operands carry: the same ``tensor_structure`` (or, failing that, a
+        ``tensor_structure_refusal``) and ``symmetric_by_construction`` -- a combination c_K K + c_M M of a spline's
+        stiffness and mass is then still served by the fast diagonalization preconditioner and the unverified half-storage
+        product."""
         h = handle()
         check(_lib.lib().tg_csr_combine(float(a), self._h, float(b), other._h,
                                         colscale._h if colscale is not None else None, C.byref(h)), "tg_csr_combine")
-        return DeviceCSR(h)
+        out = DeviceCSR(h)
+        if colscale is None:
+            ts, ts_o = getattr(self, "tensor_structure", None), getattr(other, "tensor_structure", None)
+            if ts is not None and ts_o is not None and (ts is ts_o or (ts.kx is ts_o.kx and ts.key() == ts_o.key())):
+                out.tensor_structure = ts
+            else:
+                why = getattr(self, "tensor_structure_refusal", None)
+                if why is not None and why == getattr(other, "tensor_structure_refusal", None):
+                    out.tensor_structure_refusal = why
+            if getattr(self, "symmetric_by_construction", False) and getattr(other, "symmetric_by_construction", False):
+                out.symmetric_by_construction = True
+        return out
 
     def rowptr_at(self, r):
         v = C.c_int64()
@@ -1151,6 +1166,61 @@ def vec_concat(parts):
         check(_lib.lib().tg_vec_copy_range(out._h, off, p._h, 0, n), "tg_vec_copy_range")
         off += n
     return out
+
+
+# ------------------------------------------------------------------------------- time integration (csrc/tg_timeint.hip)
+def vec_lincomb(out, coef, vecs):
+    """out = sum_i coef[i] * vecs[i] in one pass (tg_vec_lincomb: 1 to 8 terms, fixed evaluation order); ``out`` may be one
+    of ``vecs``"""
+    coef = _f64(coef).ravel()
+    k = len(vecs)
+    if coef.size != k:
+        raise ValueError("vec_lincomb: %d coefficients for %d vectors" % (coef.size, k))
+    hs = (handle * max(k, 1))(*[v._h for v in vecs])
+    check(_lib.lib().tg_vec_lincomb(out._h, k, _p(coef, c_f64p), hs), "tg_vec_lincomb")
+    return out
+
+
+def state_advance(c, x, x_old, xdot_old, xddot_old=None):
+    """The fused state update of a time step (tg_state_advance): v = c[0] x + c[1] x_old + c[2] xdot_old + c[3] xddot_old,
+    a = c[4] v + c[5] xdot_old + c[6] xddot_old, then x_old = x, xdot_old = v, xddot_old = a.  Without ``xddot_old``
+    (order 1) c[3] and the ``a`` line are ignored."""
+    c = _f64(c).ravel()
+    if c.size != 7:
+        raise ValueError("state_advance: 7 coefficients are expected, not %d" % c.size)
+    check(_lib.lib().tg_state_advance(1 if xddot_old is None else 2, _p(c, c_f64p), x._h, x_old._h, xdot_old._h,
+                                      xddot_old._h if xddot_old is not None else None), "tg_state_advance")
+
+
+class CSRPair(object):
+    """Two matrices on one sparsity pattern (verified once on the device; ValueError when they differ) for the fused product
+    ``y = y0 - A xa - B xb`` (tg_spmv_pair).  Keeps A and B alive; their patterns must not change."""
+
+    def __init__(self, A, B):
+        self._h = None
+        self.A, self.B = A, B
+        h = handle()
+        L = _lib.lib()
+        rc = L.tg_csr_pair_create(A._h, B._h, C.byref(h))
+        if rc == 2:
+            raise ValueError("CSRPair: %s" % L.tg_last_error().decode())
+        check(rc, "tg_csr_pair_create")
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().tg_csr_pair_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def mult(self, xa, xb, y0=None, y=None):
+        """y = y0 - A xa - B xb (``y0`` None: 0; ``y`` may be ``y0``, not ``xa`` or ``xb``)"""
+        if y is None:
+            y = DeviceVector(self.A.shape[0], zero=False)
+        check(_lib.lib().tg_spmv_pair(self._h, xa._h, xb._h, y0._h if y0 is not None else None, y._h), "tg_spmv_pair")
+        return y
 
 
 # ------------------------------------------------------------------------------- timers / info
