@@ -82,6 +82,7 @@ int tg_vec_copy_range(tg_vec_t dst, int64_t dst_off, tg_vec_t src, int64_t src_o
 int tg_vec_axpy(tg_vec_t y, double a, tg_vec_t x);          /* y += a x */
 int tg_vec_dot(tg_vec_t x, tg_vec_t y, double *out);        /* deterministic two-stage */
 int tg_vec_pointwise_mult(tg_vec_t w, tg_vec_t x, tg_vec_t y);   /* w = x .* y (VecPointwiseMult) */
+int tg_vec_pointwise_divide(tg_vec_t w, tg_vec_t x, tg_vec_t y); /* w = x ./ y (VecPointwiseDivide) */
 /* GenericVector::norm: kind 0 = "l1", 1 = "l2", 2 = "linf" (tIGAr/common.py:1330 norm(MTb)) */
 int tg_vec_norm(tg_vec_t x, int kind, double *out);
 /* as_backend_type(MTb).vec().setValues(zeroDofs, 0)  -- tIGAr/common.py:1154-1158 */
@@ -572,6 +573,8 @@ typedef struct {
   tg_vec_t cp[4];           /* nsd+1 homogeneous control functions on the FE nodes    */
   int nq;                   /* Gauss points per direction                             */
 } tg_patch_t;
+/* limits of the element kernels on these patches: (p+1)^d local nodes, Gauss points per direction (no device needed) */
+int tg_assemble_limits(int *max_local_nodes, int *max_gauss_points);
 /* form: 0 = (u,v), 1 = (grad u, grad v), 4 = (lap u, lap v) element by element with lap = spline.div(spline.grad(.)) and
  * the second derivatives of the map (nsd == d; demos/biharmonic/biharmonic.py:100-103); result on the element-coupling
  * pattern */
@@ -597,6 +600,23 @@ int tg_assemble_mapped_load_rows(const tg_patch_t *patch, tg_vec_t fnodal, int64
  * (row0 = row1 = -1: the whole block); same pattern, same kernels (the coefficient tensor per point is not symmetric). */
 int tg_assemble_mapped_elasticity_rows(const tg_patch_t *patch, int fi, int fj, double lambda, double mu, int64_t row0,
                                        int64_t row1, int64_t cp_node0, tg_csr_t *out);
+
+/* ---- quadrature-point evaluation on the same patches (csrc/tg_postproc.hip): L2 projection (tIGAr/common.py:1392-1433)
+ * and error norms (the demos' sqrt(assemble(((u-soln)**2)*spline.dx))) need the points, u_h and its Cartesian gradient
+ * there, a load vector from point values and three weighted sums.  Points are numbered element-major: elements
+ * lexicographic with direction 0 fastest, the nq^d Gauss points of an element likewise; npts = nq^d prod nel_k.  Arrays
+ * with nsd components per point are component-major (component c of point q at c npts + q).  The control functions are
+ * given on all FE nodes.  Sum-factorised, no floating-point atomics: the same inputs give the same bits. */
+/* x_q = F(xi_q) = cp[i]/cp[nsd] (nsd npts values) and wdet_q = w_q sqrt(det g) prod h_k, the weight of every form above */
+int tg_quad_points(const tg_patch_t *patch, tg_vec_t x_out, tg_vec_t wdet_out);
+/* u_h(x_q) of a nodal vector; with_grad: also the Cartesian gradient DF g^-1 grad_xi u_h (pinv(DF) and the quotient rule
+ * of the rational map, the operator of form 1) into grad_out (nsd npts values; ignored without with_grad) */
+int tg_quad_eval(const tg_patch_t *patch, tg_vec_t u_nodal, int with_grad, tg_vec_t val_out, tg_vec_t grad_out);
+/* out[node] = sum_q wdet_q f_q phi_node(xi_q): the load vector of a function given by its values at the points */
+int tg_quad_load(const tg_patch_t *patch, tg_vec_t f_q, tg_vec_t out);
+/* out[0] = sum wdet (u_h - e)^2, out[1] = sum wdet |grad u_h - ge|^2, out[2] = sum wdet e^2 (host array of 3).  e_q (npts)
+ * and ge_q (nsd npts) may be null: the term is 0; u_nodal may be null: u_h = 0 */
+int tg_quad_error(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, tg_vec_t ge_q, double *out);
 
 /* ---- FE operands in the caller's dof order (csrc/tg_feorder.hip, tigar_amd/feorder.py) ----------------------------
  * tg_nodes_locate: recognises the caller's node coordinates x[nrows x d] (host, row-major) as a permutation of the node

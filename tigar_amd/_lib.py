@@ -209,10 +209,16 @@ PROTOTYPES = {
     "tg_kron3_csr": (C.c_int, [C.c_int, C.POINTER(tg_kron_dir_t), c_i64p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                C.POINTER(handle)]),
     "tg_vec_pointwise_mult": (C.c_int, [handle, handle, handle]),
+    "tg_vec_pointwise_divide": (C.c_int, [handle, handle, handle]),
     "tg_csr_combine": (C.c_int, [C.c_double, handle, C.c_double, handle, handle, C.POINTER(handle)]),
     "tg_tensor_apply_1d": (C.c_int, [C.c_int, c_i64p, C.c_int, C.c_int64, c_i32p, c_i32p, c_f64p, C.c_int64, handle, handle]),
     "tg_assemble_mapped_matrix": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.POINTER(handle)]),
+    "tg_assemble_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tg_assemble_mapped_load": (C.c_int, [C.POINTER(tg_patch_t), handle, handle]),
+    "tg_quad_points": (C.c_int, [C.POINTER(tg_patch_t), handle, handle]),
+    "tg_quad_eval": (C.c_int, [C.POINTER(tg_patch_t), handle, C.c_int, handle, handle]),
+    "tg_quad_load": (C.c_int, [C.POINTER(tg_patch_t), handle, handle]),
+    "tg_quad_error": (C.c_int, [C.POINTER(tg_patch_t), handle, handle, handle, c_f64p]),
     "tg_assemble_mapped_matrix_rows": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                                   C.POINTER(handle)]),
     "tg_assemble_mapped_load_rows": (C.c_int, [C.POINTER(tg_patch_t), handle, C.c_int64, C.c_int64, C.c_int64, handle]),

@@ -2036,6 +2036,130 @@ class ExtractedSpline(object):
         solver.solve(MTM, x, MTtemp)
         return x
 
+    # -- projection, error norms, quadrature-point evaluation (csrc/tg_postproc.hip)
+    def _quadrature_scope(self, who):
+        """Refuses what the quadrature-point operands do not cover: they are provided for the scalar Q_p space of one
+        tensor-product patch held by one rank, in the order of the node grid."""
+        if self._distributed():
+            raise NotImplementedError("%s: several ranks are not supported (the point values are numbered over the whole "
+                                      "patch)" % who)
+        if self._implicit():
+            raise NotImplementedError("%s: the streamed engine asks its forms for row blocks, which the quadrature-point "
+                                      "load does not hand out" % who)
+        if self._caller_ordered():
+            raise NotImplementedError("%s: a spline with the caller's FE dof order (feOrder) is not supported; the point "
+                                      "kernels number the node grid" % who)
+        if self.nFields != 1:
+            raise NotImplementedError("%s: nFields = %d; only scalar spaces are supported" % (who, self.nFields))
+        if isinstance(getattr(self, "_generator", None), FieldListSpline):
+            raise NotImplementedError("%s: FieldListSpline spaces (fields on their own bases) are not supported" % who)
+        grids = getattr(self.V, "grids", None)
+        if grids is None or len(grids) != 1 or not isinstance(grids[0], TensorNodeGrid) or grids[0].dg:
+            raise NotImplementedError("%s: the FE space is not the continuous Q_p space of a single tensor-product patch "
+                                      "(FieldListSpline, compatible, multi-patch, T-spline and DG spaces are not supported)" % who)
+
+    def quadraturePoints(self, nq=None):
+        """The Gauss points of the patch (``nq`` per direction, p + 1 when None) as a ``forms.QuadraturePoints``: ``.x``
+        (host array [npts, nsd], downloaded on first use), ``.x_device``, ``.weights`` (DeviceVector of w_q sqrt(det g)
+        prod h_k), ``.nq``, ``.npts``; kept per ``nq`` and per set of control-function vectors (the geometry is taken as
+        frozen: values written into those vectors in place after the first call are not noticed).  Numbering: element-major, elements and the nq^d points of an
+        element lexicographic with direction 0 fastest."""
+        from . import forms
+        self._quadrature_scope("quadraturePoints")
+        return forms.quadrature_points(self, self.V, nq, "quadraturePoints")
+
+    def evaluateAtQuadrature(self, u, grad=False, nq=None):
+        """u_h at the quadrature points for an FE ``Function`` (or nodal vector) ``u``: a DeviceVector, or with ``grad``
+        ``(values, [nsd DeviceVectors])`` with the components of the Cartesian gradient (``spline.grad``: pinv(DF) and
+        the quotient rule of the rational map)."""
+        pts = self.quadraturePoints(nq)
+        uv = _as_device_vector(u)
+        if uv.size() != self.V.dim():
+            raise ValueError("evaluateAtQuadrature: %d nodal values given, the space has %d" % (uv.size(), self.V.dim()))
+        if not grad:
+            return _dev.quad_eval(pts.verts, pts.p, pts.cp, uv, nq=pts.nq)
+        val, g = _dev.quad_eval(pts.verts, pts.p, pts.cp, uv, grad=True, nq=pts.nq)
+        comps = []
+        for i in range(pts.nsd):
+            c = DeviceVector(pts.npts, zero=False)
+            _dev.vec_copy_range(c, 0, g, i * pts.npts, pts.npts)
+            comps.append(c)
+        return val, comps
+
+    def integrate(self, f, nq=None):
+        """sum_q wdet_q f(x_q): the integral of ``f`` over the patch with the spline's measure; ``f`` as for
+        ``forms.QuadratureLoadForm`` (callable on the points, number, point values, Function)."""
+        pts = self.quadraturePoints(nq)
+        return pts.weights.inner(pts.values(f, "integrate"))
+
+    def errorNorm(self, u, exact, kind="L2", exact_grad=None, nq=None, relative=False):
+        """Error of the FE ``Function`` (or nodal vector) ``u`` against ``exact`` in dolfin's ``errornorm`` kinds: "L2",
+        "H10" (the seminorm of the Cartesian gradient) or "H1" = sqrt(L2^2 + H10^2).  ``exact`` / ``exact_grad``:
+        callables on the physical points [npts, nsd] -> [npts] / [npts, nsd], numbers or point-value arrays;
+        ``exact_grad`` is required for "H10" / "H1".  ``relative``: divided by the same norm of ``exact``.  ``u`` is taken
+        un-rationalised, as the package's forms take their unknown: the polynomial spline pushed forward by the map."""
+        if kind not in ("L2", "H10", "H1"):
+            raise ValueError("errorNorm: unknown kind %r (L2, H10, H1)" % (kind,))
+        if kind != "L2" and exact_grad is None:
+            raise ValueError("errorNorm: kind %r needs exact_grad" % (kind,))
+        pts = self.quadraturePoints(nq)
+        uv = _as_device_vector(u)
+        if uv.size() != self.V.dim():
+            raise ValueError("errorNorm: %d nodal values given, the space has %d" % (uv.size(), self.V.dim()))
+        e = pts.values(exact, "errorNorm: exact")
+        ge = pts.vector_values(exact_grad, "errorNorm: exact_grad") if kind != "L2" else None
+        s0, s1, e2 = _dev.quad_error(pts.verts, pts.p, pts.cp, uv, e, ge, nq=pts.nq)
+        num = {"L2": s0, "H10": s1, "H1": s0 + s1}[kind]
+        if not relative:
+            return float(numpy.sqrt(num))
+        g2 = _dev.quad_error(pts.verts, pts.p, pts.cp, None, None, ge, nq=pts.nq)[1] if kind != "L2" else 0.0
+        den = {"L2": e2, "H10": g2, "H1": e2 + g2}[kind]
+        return float(numpy.sqrt(num / den))
+
+    def projectDofs(self, toProject, applyBCs=False, lumpMass=False, linearSolver=None, nq=None):
+        """IGA dofs of the L2 projection of ``toProject`` (given as for ``forms.QuadratureLoadForm``) onto the spline space
+        (tIGAr/common.py:1392-1433).  Consistent: ``M^T A_mass M U = M^T b`` with the load and the mass matrix integrated by
+        the same ``nq`` points, so that a function of the space is reproduced whatever the quadrature error; solved by
+        ``linearSolver``, else ``self.linearSolver``, else the default solver; the extracted mass matrix is kept per
+        ``(applyBCs, nq, zeroDofs)`` (``_projection_mass``; ``_projection_mass_builds`` counts the assemblies); like the
+        quadrature points it is computed from the control functions as they are at the first call -- control functions
+        overwritten in place afterwards are not noticed (new vectors are).  ``lumpMass``:
+        ``U = M^T b ./ M^T (load of 1)``, the denominator extracted without the boundary conditions as in the reference
+        (common.py:1416-1430); no matrix."""
+        from . import forms
+        self._quadrature_scope("projectDofs")
+        nq = forms._check_nq(nq, int(self.V.grids[0].degree))
+        rhs = self.assembleVector(forms.QuadratureLoadForm(toProject, self, nq), applyBCs=applyBCs)
+        if lumpMass:
+            den = self.assembleVector(forms.QuadratureLoadForm(1.0, self, nq), applyBCs=False)
+            return rhs.pointwise_divide(den)
+        cache = self.__dict__.setdefault("_projection_mass", {})
+        # (the zero dofs are part of the key: a spline whose zeroDofs were changed after a projection gets a new matrix)
+        key = (bool(applyBCs), nq, numpy.asarray(self.zeroDofs).tobytes() if applyBCs else b"")
+        if key not in cache:
+            cache[key] = self.assembleMatrix(forms.MassForm(geometry=self, nq=nq), applyBCs=applyBCs)
+            self._projection_mass_builds = self.__dict__.get("_projection_mass_builds", 0) + 1
+        U = DeviceVector(cache[key].shape[0])
+        solver = linearSolver if linearSolver is not None else \
+            (self.linearSolver if self.linearSolver is not None else _default_linear_solver())
+        solver.solve(cache[key], U, rhs)
+        return U
+
+    def project(self, toProject, applyBCs=False, rationalize=False, lumpMass=False):
+        """FE ``Function`` M * projectDofs(...) (tIGAr/common.py:1392-1433).  The package takes the unknown un-rationalised
+        (the polynomial spline pushed forward by the rational map); with unit weights ``rationalize`` changes nothing, with
+        others ``rationalize=True`` is refused."""
+        if rationalize:
+            w = self.cpFuncs[self.nsd].vector().get_local()
+            if numpy.max(numpy.abs(w - 1.0)) > 64 * numpy.finfo(numpy.float64).eps:      # (unit up to the extraction's rounding)
+                raise NotImplementedError("project(rationalize=True): the control mesh has non-unit weights; the package's "
+                                          "forms and norms take the un-rationalised spline, and dividing by the weight "
+                                          "function is not implemented")
+        U = self.projectDofs(toProject, applyBCs=applyBCs, lumpMass=lumpMass)
+        u = Function(self.V)
+        self.M.mult(U, u.vector())
+        return u
+
     def solveNonlinearVariationalProblem(self, residualForm, J, u, referenceError=None, igaDoFs=None):
         """Newton iteration of tIGAr/common.py:1304-1348, same control flow: assemble
         (M^T J M, M^T R) at the current ``u``, stop when ||M^T R|| / reference < relativeTolerance

@@ -28,11 +28,9 @@
 // caller step before the hot path, not the hot path; the identity-geometry inputs of the
 // benchmark configurations use the Kronecker-sum generator (tg_kron.hip) instead.
 #include "tg_common.h"
+#include "tg_asm_shared.h"
 #include <cmath>
 #include <utility>
-
-#define TG_ASM_MAXLOC 128      // (p+1)^d local nodes: p <= 4 in 3-D, p <= 8 in 2-D (<= 81), any p <= 8 in 1-D
-#define TG_ASM_MAXQ1 10        // Gauss points per direction
 
 struct tg_asm_args {
   int d, p, nsd, nq;
@@ -53,31 +51,6 @@ struct tg_asm_args {
   int64_t row0, row1;          // rows written: [row0, row1); rowptr / val / bout are those of the block (row - row0)
   int64_t cp_node0;            // the control functions (and fnod) hold the nodes from cp_node0 on
 };
-
-__device__ __forceinline__ void tg_sym_inverse(int d, const double *g, double *gi, double *det) {
-  if (d == 1) {
-    *det = g[0];
-    gi[0] = 1.0 / g[0];
-  } else if (d == 2) {
-    const double a = g[0], b = g[1], c = g[3];
-    const double dt = a * c - b * b;
-    *det = dt;
-    gi[0] = c / dt;
-    gi[1] = gi[2] = -b / dt;
-    gi[3] = a / dt;
-  } else {
-    const double a = g[0], b = g[1], c = g[2], e = g[4], f = g[5], i = g[8];
-    const double c00 = e * i - f * f, c01 = c * f - b * i, c02 = b * f - c * e;
-    const double dt = a * c00 + b * c01 + c * c02;
-    *det = dt;
-    gi[0] = c00 / dt;
-    gi[1] = gi[3] = c01 / dt;
-    gi[2] = gi[6] = c02 / dt;
-    gi[4] = (a * i - c * c) / dt;
-    gi[5] = gi[7] = (b * c - a * f) / dt;
-    gi[8] = (a * e - b * b) / dt;
-  }
-}
 
 // 1-D pattern of the element-coupling matrix: columns of node r form the contiguous range
 // [lo, lo+width): both neighbouring elements for an interior vertex, the own element otherwise
@@ -1385,13 +1358,7 @@ static void tg_asm_tables(int p, int nq, std::vector<double> &tab) {
 // Device copies of the small per-call tables (element vertices, reference-element tables) of the last patch description: the
 // z-slab pipeline calls once per sub-slab with the same patch, and the uploads with the wait that keeps the host arrays
 // alive stood between the kernels of consecutive sub-slabs.
-struct tg_asm_cache_t {
-  int d = 0, p = 0, nq = 0, nverts[3] = {0, 0, 0};
-  std::vector<double> hverts[3];
-  double *verts[3] = {nullptr, nullptr, nullptr};
-  double *tab = nullptr;
-};
-static tg_asm_cache_t g_asm_cache;
+tg_asm_cache_t g_asm_cache;
 
 void tg_asm_cache_clear(void) {
   if (g_tg.ready) hipStreamSynchronize(g_tg.stream);
@@ -1403,7 +1370,7 @@ void tg_asm_cache_clear(void) {
   g_asm_cache = tg_asm_cache_t();
 }
 
-static int tg_asm_cache_get(const tg_patch_t *pt) {
+int tg_asm_cache_get(const tg_patch_t *pt) {
   tg_asm_cache_t &C = g_asm_cache;
   bool same = C.d == pt->d && C.p == pt->p && C.nq == pt->nq && C.tab;
   for (int k = 0; k < pt->d && same; k++)
@@ -1663,6 +1630,12 @@ static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int6
     return 1;
   }
   if (mout) *mout = m;
+  return 0;
+}
+
+extern "C" int tg_assemble_limits(int *max_local_nodes, int *max_gauss_points) {
+  if (max_local_nodes) *max_local_nodes = TG_ASM_MAXLOC;
+  if (max_gauss_points) *max_gauss_points = TG_ASM_MAXQ1;
   return 0;
 }
 

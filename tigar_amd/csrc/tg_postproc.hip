@@ -1,0 +1,477 @@
+// Quadrature-point evaluation on mapped tensor-product patches: what a caller needs around the solve -- L2 projection of a
+// function onto the spline space (initial and boundary data), and the error of a computed solution against an exact one
+// (tIGAr/common.py:1392-1433 project; the demos' sqrt(assemble(((u-soln)**2)*spline.dx))).
+//
+// Scalar Q_p Lagrange space on the tensor node grid, geometry F = cp[i]/cp[nsd], Gauss-Legendre with nq points per
+// direction: the conventions of tg_assemble.hip.  Points are numbered element-major (elements lexicographic with
+// direction 0 fastest, the nq^d points of an element likewise); point arrays with several components are component-major.
+//
+//   tg_quad_points   x_q = F(xi_q) and wdet_q = w_q sqrt(det g) prod h_k
+//   tg_quad_eval     u_h(x_q) and the Cartesian gradient DF g^-1 grad_xi u_h (pinv(DF), quotient rule of the rational map)
+//   tg_quad_load     out[node] = sum_q wdet_q f_q phi_node(xi_q)
+//   tg_quad_error    sum wdet (u_h - e)^2,  sum wdet |grad u_h - ge|^2,  sum wdet e^2
+//
+// One kernel, four endings.  A workgroup of 256 threads takes max(1, 256 / nq^d) elements (fewer where
+// their LDS areas would exceed 64 KiB).  The nodal values of the
+// nsd + 1 control functions (and of u) go to the points by SUM FACTORISATION: one 1-D contraction per direction through
+// LDS, O((p+1) nq^d) per field instead of the O((p+1)^d nq^d) of the plain assembly kernel; the load goes back to the
+// nodes the same way.  Everything is done in the coordinates of the reference element [0,1]^d: DF, g and the gradients
+// of the Lagrange functions refer to them, so that no element size appears -- w_q sqrt(det g_hat) IS w_q sqrt(det g)
+// prod h_k, and DF g^-1 grad u is the same vector in any parametrisation (tIGAr/calculusUtils.py:56-70).
+// No floating-point atomics: the load adds element by element, colour by colour (parities of the element index, the
+// colours of k_assemble_mapped in the same order); the error sums are per-element trees, then one fixed pass over the
+// elements.  Same inputs, same bits.
+#include "tg_common.h"
+#include "tg_asm_shared.h"
+#include <cmath>
+
+struct tg_pp_args {
+  int d, p, nsd, nq;
+  int nel[3], n[3];            // elements / nodes per direction (1 beyond d)
+  const double *f[5];          // nodal fields: 0..2 homogeneous coordinates (the first nsd), 3 the weight function, 4 u (or null)
+  int nc;                      // how many of them there are
+  const double *tab;           // l[a][q] | dl[a][q] | w[q]
+  int epg;                     // elements per workgroup
+  int szA, szB;                // doubles per element of the two LDS areas
+  int efirst[3], ncol[3], estep;   // the elements of this launch: efirst[k] + estep i, i < ncol[k]
+  int64_t nelem;               // ... their number
+  int64_t npts;                // points of the patch
+  double *x, *wdet;            // points
+  double *val, *grad;          // eval (grad may be null)
+  const double *fq;            // load: point values
+  double *out;                 //       nodal vector
+  const double *eq, *geq;      // error: point values of e and of its gradient (either may be null)
+  double *part;                //        [3][elements of the patch] partial sums
+};
+
+__device__ __forceinline__ bool tg_pp_has(int c, const tg_pp_args &P) { return c < 3 ? c < P.nsd : P.f[c] != nullptr; }
+// position of field c among the fields present
+__device__ __forceinline__ int tg_pp_ci(int c, int nsd) { return c < 3 ? c : nsd + (c - 3); }
+
+// element number e of the launch -> element indices; returns the lexicographic index in the patch
+__device__ __forceinline__ int64_t tg_pp_element(const tg_pp_args &P, int64_t e, int *el) {
+  el[0] = P.efirst[0] + P.estep * (int)(e % P.ncol[0]);
+  e /= P.ncol[0];
+  el[1] = P.efirst[1] + P.estep * (int)(e % P.ncol[1]);
+  e /= P.ncol[1];
+  el[2] = P.efirst[2] + P.estep * (int)e;
+  return (int64_t)el[0] + (int64_t)P.nel[0] * ((int64_t)el[1] + (int64_t)P.nel[1] * el[2]);
+}
+
+__device__ __forceinline__ int64_t tg_pp_node(const tg_pp_args &P, const int *el, int a) {
+  const int p1 = P.p + 1;
+  const int a0 = a % p1, a1 = (a / p1) % p1, a2 = a / (p1 * p1);
+  return (int64_t)(el[0] * P.p + a0) + (int64_t)P.n[0] * ((int64_t)(el[1] * P.p + a1) + (int64_t)P.n[1] * (el[2] * P.p + a2));
+}
+
+// MODE 0 points, 1 eval, 2 load, 3 error
+template <int MODE>
+__global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int d = P.d, p1 = P.p + 1, nq = P.nq, nsd = P.nsd, nc = P.nc, epg = P.epg;
+  const int nloc = d == 1 ? p1 : (d == 2 ? p1 * p1 : p1 * p1 * p1);
+  const int nqt = d == 1 ? nq : (d == 2 ? nq * nq : nq * nq * nq);
+  double *tl = reinterpret_cast<double *>(smem);   // l[a][q]
+  double *tdl = tl + p1 * nq;                      // dl[a][q]
+  double *tw = tdl + p1 * nq;                      // w[q]
+  double *bufA = tw + nq;
+  double *bufB = bufA + (size_t)epg * P.szA;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int64_t g0 = (int64_t)blockIdx.x * epg;    // first element of the group (of this launch's elements)
+  for (int s = tid; s < 2 * p1 * nq + nq; s += nt) tl[s] = P.tab[s];
+  // nodal values -> area A [field][local node]
+  for (int i = tid; i < epg * nloc; i += nt) {
+    const int es = i / nloc, a = i - es * nloc;
+    if (g0 + es >= P.nelem) continue;
+    int el[3];
+    tg_pp_element(P, g0 + es, el);
+    const int64_t node = tg_pp_node(P, el, a);
+#pragma unroll
+    for (int c = 0; c < 5; c++)
+      if (tg_pp_has(c, P)) bufA[(size_t)es * P.szA + tg_pp_ci(c, nsd) * nloc + a] = P.f[c][node];
+  }
+  __syncthreads();
+  // ---- to the points: directions 0 .. d-2 through LDS.  Before direction k an area holds k + 1 "slots" per field --
+  // the function and its derivatives in the directions done -- on [q_0 .. q_k-1 | a_k .. a_d-1]; the contraction with
+  // l gives each slot on [q_0 .. q_k | a_k+1 ..], the contraction of the function with dl the new derivative.
+  // Layout: area[(slot nc + field) S + index].
+  int nqk = 1, rest = nloc / p1;                   // nq^k, (p+1)^(d-k-1)
+  for (int k = 0; k + 1 < d; k++) {
+    const double *in = (k & 1) ? bufB : bufA;
+    double *out = (k & 1) ? bufA : bufB;
+    const int szi = (k & 1) ? P.szB : P.szA, szo = (k & 1) ? P.szA : P.szB;
+    const int Sin = nqk * p1 * rest, Sout = nqk * nq * rest, work = nc * Sout;
+    for (int i = tid; i < epg * work; i += nt) {
+      const int es = i / work, r = i - es * work;
+      if (g0 + es >= P.nelem) continue;
+      const int ci = r / Sout, idx = r - ci * Sout;
+      const int Q = idx % nqk, t = idx / nqk, qk = t % nq, R = t / nq;
+      const double *I = in + (size_t)es * szi + ci * Sin;
+      double v0 = 0.0, v1 = 0.0, vd = 0.0;
+      for (int a = 0; a < p1; a++) {
+        const double l = tl[a * nq + qk], dl = tdl[a * nq + qk];
+        const int off = Q + nqk * (a + p1 * R);
+        const double f0 = I[off];
+        v0 = fma(l, f0, v0);
+        vd = fma(dl, f0, vd);
+        if (k >= 1) v1 = fma(l, I[nc * Sin + off], v1);
+      }
+      double *O = out + (size_t)es * szo + ci * Sout;
+      O[idx] = v0;
+      if (k >= 1) O[nc * Sout + idx] = v1;
+      O[(k + 1) * nc * Sout + idx] = vd;
+    }
+    __syncthreads();
+    nqk *= nq;
+    rest /= p1;
+  }
+  // ---- the last direction: a thread per point, results in registers
+  const bool lastB = ((d - 1) & 1) != 0;           // the area the last contraction reads; the OTHER one is free
+  const double *fin = lastB ? bufB : bufA;
+  double *oth = lastB ? bufA : bufB;
+  const int szf = lastB ? P.szB : P.szA, szt = lastB ? P.szA : P.szB;
+  const int Sin = nqk * p1;
+  for (int i = tid; i < epg * nqt; i += nt) {
+    const int es = i / nqt, q = i - es * nqt;
+    if (g0 + es >= P.nelem) continue;
+    const int Q = q % nqk, ql = q / nqk;
+    double N[5], dN[5][3];
+#pragma unroll
+    for (int c = 0; c < 5; c++) {
+      N[c] = 0.0;
+      dN[c][0] = dN[c][1] = dN[c][2] = 0.0;
+      if (!tg_pp_has(c, P)) continue;
+      const double *I = fin + (size_t)es * szf + tg_pp_ci(c, nsd) * Sin;
+      double v = 0.0, e0 = 0.0, e1 = 0.0, vd = 0.0;
+      for (int a = 0; a < p1; a++) {
+        const double l = tl[a * nq + ql], dl = tdl[a * nq + ql];
+        const int off = Q + nqk * a;
+        const double f0 = I[off];
+        v = fma(l, f0, v);
+        vd = fma(dl, f0, vd);
+        if (d >= 2) e0 = fma(l, I[nc * Sin + off], e0);
+        if (d >= 3) e1 = fma(l, I[2 * nc * Sin + off], e1);
+      }
+      N[c] = v;
+      dN[c][0] = d == 1 ? vd : e0;
+      dN[c][1] = d == 2 ? vd : e1;
+      dN[c][2] = d == 3 ? vd : 0.0;
+    }
+    // DF[i][k] = d(N_i / W)/dxi_k ; metric g = DF^T DF
+    const double W = N[3];
+    double G[3][3], DF[3][3] = {{0}};
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      if (c >= nsd) continue;
+#pragma unroll
+      for (int k = 0; k < 3; k++)
+        if (k < d) DF[c][k] = (dN[c][k] * W - N[c] * dN[3][k]) / (W * W);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+      for (int m = 0; m < 3; m++) G[k][m] = DF[0][k] * DF[0][m] + DF[1][k] * DF[1][m] + DF[2][k] * DF[2][m];   // (zero beyond nsd, d)
+    // inverse and determinant of the leading d x d block (constant indices in every branch: the arrays stay in registers)
+    double gi[3][3] = {{0}}, det, gm[9], gq[9];
+    if (d == 1) {
+      gm[0] = G[0][0];
+      tg_sym_inverse(1, gm, gq, &det);
+      gi[0][0] = gq[0];
+    } else if (d == 2) {
+      gm[0] = G[0][0];
+      gm[1] = G[0][1];
+      gm[2] = G[1][0];
+      gm[3] = G[1][1];
+      tg_sym_inverse(2, gm, gq, &det);
+      gi[0][0] = gq[0];
+      gi[0][1] = gq[1];
+      gi[1][0] = gq[2];
+      gi[1][1] = gq[3];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 3; k++)
+#pragma unroll
+        for (int m = 0; m < 3; m++) gm[3 * k + m] = G[k][m];
+      tg_sym_inverse(3, gm, gq, &det);
+#pragma unroll
+      for (int k = 0; k < 3; k++)
+#pragma unroll
+        for (int m = 0; m < 3; m++) gi[k][m] = gq[3 * k + m];
+    }
+    const int q0 = q % nq, q1 = (q / nq) % nq, q2 = q / (nq * nq);
+    const double wq = tw[q0] * (d > 1 ? tw[q1] : 1.0) * (d > 2 ? tw[q2] : 1.0);
+    const double wdet = wq * sqrt(fabs(det));
+    // Cartesian gradient of u: DF g^-1 grad_xi u
+    double gu[3] = {0, 0, 0};
+    if (MODE == 1 || MODE == 3) {
+      double t[3];
+#pragma unroll
+      for (int k = 0; k < 3; k++) t[k] = gi[k][0] * dN[4][0] + gi[k][1] * dN[4][1] + gi[k][2] * dN[4][2];
+#pragma unroll
+      for (int c = 0; c < 3; c++) gu[c] = DF[c][0] * t[0] + DF[c][1] * t[1] + DF[c][2] * t[2];
+    }
+    int el[3];
+    const int64_t gp = tg_pp_element(P, g0 + es, el) * nqt + q;    // the point's number in the patch
+    if (MODE == 0) {
+#pragma unroll
+      for (int c = 0; c < 3; c++)
+        if (c < nsd) P.x[(int64_t)c * P.npts + gp] = N[c] / W;
+      P.wdet[gp] = wdet;
+    } else if (MODE == 1) {
+      P.val[gp] = N[4];
+      if (P.grad) {
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+          if (c < nsd) P.grad[(int64_t)c * P.npts + gp] = gu[c];
+      }
+    } else if (MODE == 2) {
+      oth[(size_t)es * szt + q] = wdet * P.fq[gp];
+    } else {
+      const double e = P.eq ? P.eq[gp] : 0.0;
+      const double du = N[4] - e;
+      double s1 = 0.0;
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        if (c >= nsd) continue;
+        const double dg = gu[c] - (P.geq ? P.geq[(int64_t)c * P.npts + gp] : 0.0);
+        s1 = fma(dg, dg, s1);
+      }
+      double *T = oth + (size_t)es * szt;
+      T[q] = wdet * (du * du);
+      T[nqt + q] = wdet * s1;
+      T[2 * nqt + q] = wdet * (e * e);
+    }
+  }
+  if (MODE == 0 || MODE == 1) return;
+  __syncthreads();
+  if (MODE == 3) {
+    // the three sums of each element: a tree over its points (fixed shape), then one value per element and term
+    int p2 = 1;
+    while (p2 < nqt) p2 <<= 1;
+    for (int o = p2 >> 1; o > 0; o >>= 1) {
+      for (int i = tid; i < epg * 3 * o; i += nt) {
+        const int es = i / (3 * o), r = i - es * 3 * o, t = r / o, j = r - t * o;
+        if (j + o < nqt) oth[(size_t)es * szt + t * nqt + j] += oth[(size_t)es * szt + t * nqt + j + o];
+      }
+      __syncthreads();
+    }
+    for (int i = tid; i < epg * 3; i += nt) {
+      const int es = i / 3, t = i - es * 3;
+      if (g0 + es >= P.nelem) continue;
+      int el[3];
+      const int64_t ei = tg_pp_element(P, g0 + es, el);
+      P.part[(int64_t)t * P.nelem + ei] = oth[(size_t)es * szt + t * nqt];
+    }
+    return;
+  }
+  // ---- load: wdet f back to the nodes, direction by direction.  Before direction k: [a_0 .. a_k-1 | q_k .. q_d-1]
+  double *cur = oth, *nxt = lastB ? bufB : bufA;
+  int szc = szt, szn = szf;
+  int pk = 1, qrest = nqt / nq;                    // (p+1)^k, nq^(d-k-1)
+  for (int k = 0; k < d; k++) {
+    const int Sout = pk * p1 * qrest;
+    for (int i = tid; i < epg * Sout; i += nt) {
+      const int es = i / Sout, idx = i - es * Sout;
+      if (g0 + es >= P.nelem) continue;
+      const int Ai = idx % pk, t = idx / pk, ak = t % p1, R = t / p1;
+      const double *I = cur + (size_t)es * szc;
+      double acc = 0.0;
+      for (int q = 0; q < nq; q++) acc = fma(tl[ak * nq + q], I[Ai + pk * (q + nq * R)], acc);
+      nxt[(size_t)es * szn + idx] = acc;
+    }
+    __syncthreads();
+    double *sw = cur;
+    cur = nxt;
+    nxt = sw;
+    const int si = szc;
+    szc = szn;
+    szn = si;
+    pk *= p1;
+    qrest /= nq;
+  }
+  // elements of one launch share no node (one colour): plain adds, the colours follow each other in a fixed order
+  for (int i = tid; i < epg * nloc; i += nt) {
+    const int es = i / nloc, a = i - es * nloc;
+    if (g0 + es >= P.nelem) continue;
+    int el[3];
+    tg_pp_element(P, g0 + es, el);
+    P.out[tg_pp_node(P, el, a)] += cur[(size_t)es * szc + a];
+  }
+}
+
+// one workgroup per term: thread t adds the elements t, t + 256, ... in that order, then the tree of the workgroup
+__global__ void __launch_bounds__(256) k_postproc_fold(const double *part, int64_t nelem, double *out) {
+  __shared__ double s[256];
+  const double *v = part + (int64_t)blockIdx.x * nelem;
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < nelem; i += 256) acc += v[i];
+  const double r = tg_block_sum_ordered(acc, s);
+  if (threadIdx.x == 0) out[blockIdx.x] = r;
+}
+
+#define TG_PP_LDS_DEFAULT ((size_t)64 * 1024)     // dynamic LDS of a launch without an attribute
+#define TG_PP_LDS_MAX ((size_t)160 * 1024)        // LDS of a compute unit
+
+static int tg_pp_pow(int b, int e) {
+  int r = 1;
+  for (int i = 0; i < e; i++) r *= b;
+  return r;
+}
+
+// checks the patch, fills what every mode shares; `u`: the nodal vector taken to the points (may be null)
+static int tg_pp_setup(const tg_patch_t *pt, int mode, tg_vec_t u, tg_pp_args *A, size_t *lds) {
+  TG_REQUIRE_INIT();
+  TG_REQUIRE(pt && pt->d >= 1 && pt->d <= 3 && pt->p >= 1 && pt->p <= TG_MAX_DEGREE && pt->nsd >= pt->d && pt->nsd <= 3,
+             "bad patch description");
+  TG_REQUIRE(pt->nq >= 1 && pt->nq <= TG_ASM_MAXQ1, "1..%d Gauss points per direction", TG_ASM_MAXQ1);
+  const int d = pt->d, p1 = pt->p + 1, nq = pt->nq;
+  const int nloc = tg_pp_pow(p1, d), nqt = tg_pp_pow(nq, d);
+  TG_REQUIRE(nloc <= TG_ASM_MAXLOC, "(p+1)^d = %d local nodes exceed the kernel limit %d", nloc, TG_ASM_MAXLOC);
+  memset(A, 0, sizeof(*A));
+  A->d = d;
+  A->p = pt->p;
+  A->nsd = pt->nsd;
+  A->nq = nq;
+  int64_t nnodes = 1, nelem = 1;
+  for (int k = 0; k < 3; k++) {
+    A->nel[k] = A->n[k] = A->ncol[k] = 1;
+    A->efirst[k] = 0;
+  }
+  for (int k = 0; k < d; k++) {
+    TG_REQUIRE(pt->nverts[k] >= 2 && pt->verts[k], "direction %d needs at least one element", k);
+    A->nel[k] = A->ncol[k] = pt->nverts[k] - 1;
+    A->n[k] = A->nel[k] * pt->p + 1;
+    nnodes *= A->n[k];
+    nelem *= A->nel[k];
+  }
+  A->estep = 1;
+  A->nelem = nelem;
+  A->npts = nelem * nqt;
+  for (int c = 0; c <= pt->nsd; c++) {
+    TG_REQUIRE(pt->cp[c] && pt->cp[c]->n == nnodes, "control function %d: a vector on the %lld FE nodes of the patch", c,
+               (long long)nnodes);
+    A->f[c < pt->nsd ? c : 3] = pt->cp[c]->d;
+  }
+  A->nc = pt->nsd + 1;
+  if (u) {
+    TG_REQUIRE(u->n == nnodes, "the nodal vector holds %lld values, the patch has %lld FE nodes", (long long)u->n,
+               (long long)nnodes);
+    A->f[4] = u->d;
+    A->nc++;
+  }
+  TG_TRY(tg_asm_cache_get(pt));
+  A->tab = g_asm_cache.tab;
+  A->epg = std::max(1, 256 / nqt);
+  // LDS per element: area A holds the nodal values, then (3-D) the output of direction 1; area B the output of direction
+  // 0; the area the last contraction does not read takes the point values of the load / the terms of the error sums, and
+  // the load goes back to the nodes through both
+  const int nc = A->nc;
+  int szA = nc * nloc, szB = 0;
+  if (d >= 2) szB = 2 * nc * nq * (nloc / p1);
+  if (d == 3) szA = std::max(szA, 3 * nc * nq * nq * p1);
+  const int back = tg_pp_pow(std::max(p1, nq), d);
+  int &other = ((d - 1) & 1) ? szA : szB;
+  if (mode == 2) {
+    szA = std::max(szA, back);
+    szB = std::max(szB, back);
+  }
+  if (mode == 3) other = std::max(other, 3 * nqt);
+  A->szA = szA;
+  A->szB = szB;
+  // fewer elements per workgroup until the group fits the 64 KiB a launch gets without asking (nq < p + 1: many points'
+  // worth of threads, but the areas grow with the nodes); one element of the largest shapes (3-D, p = 4, nq >= 9: 84 KB)
+  // needs more than that and asks for it (tg_pp_launch)
+  auto bytes = [&](int epg) { return ((size_t)2 * p1 * nq + nq + (size_t)epg * ((size_t)szA + szB)) * sizeof(double); };
+  while (A->epg > 1 && bytes(A->epg) > TG_PP_LDS_DEFAULT) A->epg--;
+  *lds = bytes(A->epg);
+  TG_REQUIRE(*lds <= TG_PP_LDS_MAX, "element data (%zu B) does not fit in LDS", *lds);
+  TG_REQUIRE(tg_cdiv(nelem, A->epg) < (1ll << 31), "too many elements for one launch");
+  return 0;
+}
+
+template <int MODE>
+static int tg_pp_launch(const tg_pp_args &A, size_t lds) {
+  if (A.nelem <= 0) return 0;
+  if (lds > TG_PP_LDS_DEFAULT)
+    TG_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_postproc<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)TG_PP_LDS_MAX));
+  hipLaunchKernelGGL((k_postproc<MODE>), dim3((unsigned)tg_cdiv(A.nelem, A.epg)), dim3(256), lds, g_tg.stream, A);
+  TG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tg_quad_points(const tg_patch_t *patch, tg_vec_t x_out, tg_vec_t wdet_out) {
+  tg_pp_args A;
+  size_t lds;
+  TG_TRY(tg_pp_setup(patch, 0, nullptr, &A, &lds));
+  TG_REQUIRE(x_out && x_out->n == (int64_t)A.nsd * A.npts && wdet_out && wdet_out->n == A.npts,
+             "tg_quad_points: outputs of nsd * npts = %lld and npts = %lld values", (long long)(A.nsd * A.npts), (long long)A.npts);
+  A.x = x_out->d;
+  A.wdet = wdet_out->d;
+  return tg_pp_launch<0>(A, lds);
+}
+
+extern "C" int tg_quad_eval(const tg_patch_t *patch, tg_vec_t u_nodal, int with_grad, tg_vec_t val_out, tg_vec_t grad_out) {
+  tg_pp_args A;
+  size_t lds;
+  TG_REQUIRE(u_nodal, "tg_quad_eval: no nodal vector");
+  TG_TRY(tg_pp_setup(patch, 1, u_nodal, &A, &lds));
+  TG_REQUIRE(val_out && val_out->n == A.npts, "tg_quad_eval: an output of npts = %lld values", (long long)A.npts);
+  A.val = val_out->d;
+  if (with_grad) {
+    TG_REQUIRE(grad_out && grad_out->n == (int64_t)A.nsd * A.npts, "tg_quad_eval: a gradient output of nsd * npts = %lld values",
+               (long long)(A.nsd * A.npts));
+    A.grad = grad_out->d;
+  }
+  return tg_pp_launch<1>(A, lds);
+}
+
+extern "C" int tg_quad_load(const tg_patch_t *patch, tg_vec_t f_q, tg_vec_t out) {
+  tg_pp_args A;
+  size_t lds;
+  TG_TRY(tg_pp_setup(patch, 2, nullptr, &A, &lds));
+  int64_t nnodes = 1;
+  for (int k = 0; k < A.d; k++) nnodes *= A.n[k];
+  TG_REQUIRE(f_q && f_q->n == A.npts && out && out->n == nnodes,
+             "tg_quad_load: npts = %lld point values and an output on the %lld FE nodes", (long long)A.npts, (long long)nnodes);
+  A.fq = f_q->d;
+  A.out = out->d;
+  TG_CHECK_HIP(hipMemsetAsync(out->d, 0, (size_t)nnodes * sizeof(double), g_tg.stream));
+  // one launch per colour (parity of the element index per direction), colours in ascending order
+  A.estep = 2;
+  for (int c = 0; c < (1 << A.d); c++) {
+    int64_t ne = 1;
+    for (int k = 0; k < A.d; k++) {
+      A.efirst[k] = (c >> k) & 1;
+      A.ncol[k] = A.nel[k] > A.efirst[k] ? (A.nel[k] - A.efirst[k] + 1) / 2 : 0;
+      ne *= A.ncol[k];
+    }
+    if (ne == 0) continue;
+    A.nelem = ne;
+    TG_TRY(tg_pp_launch<2>(A, lds));
+  }
+  return 0;
+}
+
+extern "C" int tg_quad_error(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, tg_vec_t ge_q, double *out) {
+  tg_pp_args A;
+  size_t lds;
+  TG_REQUIRE(out, "tg_quad_error: no output");
+  TG_TRY(tg_pp_setup(patch, 3, u_nodal, &A, &lds));
+  TG_REQUIRE(!e_q || e_q->n == A.npts, "tg_quad_error: npts = %lld point values of e", (long long)A.npts);
+  TG_REQUIRE(!ge_q || ge_q->n == (int64_t)A.nsd * A.npts, "tg_quad_error: nsd * npts = %lld point values of the gradient of e",
+             (long long)(A.nsd * A.npts));
+  A.eq = e_q ? e_q->d : nullptr;
+  A.geq = ge_q ? ge_q->d : nullptr;
+  tg_dbuf<double> part;
+  TG_TRY(part.alloc(3 * A.nelem + 3));
+  A.part = part.get();
+  TG_TRY(tg_pp_launch<3>(A, lds));
+  double *sums = part.get() + 3 * A.nelem;
+  hipLaunchKernelGGL(k_postproc_fold, dim3(3), dim3(256), 0, g_tg.stream, part.get(), A.nelem, sums);
+  TG_LAUNCH_CHECK();
+  TG_CHECK_HIP(hipMemcpyAsync(g_tg.host_pinned, sums, 3 * sizeof(double), hipMemcpyDeviceToHost, g_tg.stream));
+  TG_CHECK_HIP(hipStreamSynchronize(g_tg.stream));
+  for (int t = 0; t < 3; t++) out[t] = g_tg.host_pinned[t];
+  return 0;
+}

@@ -115,6 +115,12 @@ class DeviceVector(object):
         check(_lib.lib().tg_vec_pointwise_mult(out._h, self._h, other._h), "tg_vec_pointwise_mult")
         return out
 
+    def pointwise_divide(self, other, out=None):
+        """out = self ./ other (PETSc VecPointwiseDivide)"""
+        out = DeviceVector(self.size(), zero=False) if out is None else out
+        check(_lib.lib().tg_vec_pointwise_divide(out._h, self._h, other._h), "tg_vec_pointwise_divide")
+        return out
+
     def inner(self, other):
         out = C.c_double()
         check(_lib.lib().tg_vec_dot(self._h, other._h, C.byref(out)))
@@ -1117,6 +1123,63 @@ def assemble_mapped_load(vertices, p, cp, fnodal, nq=None, row0=None, row1=None,
         check(_lib.lib().tg_assemble_mapped_load_rows(C.byref(pt), fnodal._h, int(row0), int(row1), int(cp_node0), out._h),
               "tg_assemble_mapped_load_rows")
     return out
+
+
+def assemble_limits():
+    """(largest (p+1)^d, largest nq) the element kernels on mapped patches take: the library's own figures"""
+    a, b = C.c_int(), C.c_int()
+    check(_lib.load(require_device=False).tg_assemble_limits(C.byref(a), C.byref(b)), "tg_assemble_limits")
+    return a.value, b.value
+
+
+def quad_count(vertices, nq):
+    """number of quadrature points of the patch: nq^d per element"""
+    n = 1
+    for v in vertices:
+        n *= (len(v) - 1) * int(nq)
+    return n
+
+
+def quad_points(vertices, p, cp, nq=None):
+    """(x, wdet): the physical positions x_q = F(xi_q) of the Gauss points (DeviceVector of nsd * npts values,
+    component-major) and the weights wdet_q = w_q sqrt(det g) prod h_k of the mapped forms (``tg_quad_points``).  Points
+    are numbered element-major, elements and the nq^d points of an element lexicographic with direction 0 fastest."""
+    nq = p + 1 if nq is None else nq
+    pt, keep = _patch(vertices, p, cp, nq)
+    npts = quad_count(vertices, nq)
+    x, w = DeviceVector((len(cp) - 1) * npts, zero=False), DeviceVector(npts, zero=False)
+    check(_lib.lib().tg_quad_points(C.byref(pt), x._h, w._h), "tg_quad_points")
+    return x, w
+
+
+def quad_eval(vertices, p, cp, u, grad=False, nq=None):
+    """u_h at the Gauss points for the nodal DeviceVector ``u``; with ``grad`` also the Cartesian gradient (nsd * npts
+    values, component-major): returns ``values`` or ``(values, gradient)`` (``tg_quad_eval``)."""
+    nq = p + 1 if nq is None else nq
+    pt, keep = _patch(vertices, p, cp, nq)
+    npts = quad_count(vertices, nq)
+    val = DeviceVector(npts, zero=False)
+    g = DeviceVector((len(cp) - 1) * npts, zero=False) if grad else None
+    check(_lib.lib().tg_quad_eval(C.byref(pt), u._h, 1 if grad else 0, val._h, g._h if grad else None), "tg_quad_eval")
+    return (val, g) if grad else val
+
+
+def quad_load(vertices, p, cp, fq, nq=None):
+    """L(v) = sum_q wdet_q f_q v(xi_q) for the DeviceVector ``fq`` of point values (``tg_quad_load``)."""
+    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
+    out = DeviceVector(n=cp[0].size(), zero=False)          # (the entry zeroes it before the colours add)
+    check(_lib.lib().tg_quad_load(C.byref(pt), fq._h, out._h), "tg_quad_load")
+    return out
+
+
+def quad_error(vertices, p, cp, u=None, e=None, ge=None, nq=None):
+    """(sum wdet (u_h - e)^2, sum wdet |grad u_h - ge|^2, sum wdet e^2) with ``u`` a nodal DeviceVector, ``e`` / ``ge``
+    point values (npts / nsd * npts, component-major); any of the three may be None and counts as 0 (``tg_quad_error``)."""
+    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
+    out = np.zeros(3)
+    check(_lib.lib().tg_quad_error(C.byref(pt), u._h if u is not None else None, e._h if e is not None else None,
+                                   ge._h if ge is not None else None, _p(out, c_f64p)), "tg_quad_error")
+    return float(out[0]), float(out[1]), float(out[2])
 
 
 def tensor_apply_1d(x, dims_in, k, F, col_shift=0, out=None):

@@ -8,6 +8,7 @@ on the knot mesh so that the path can be driven (and benchmarked) without FEniCS
     LaplaceForm()            a(u,v) = (grad u, grad v)     -> K1xM1xM1 + M1xK1xM1 + M1xM1xK1
     MassForm()               a(u,v) = (u, v)
     SeparableLoadForm(f1d)   L(v)   = (f, v) with f(x) = scale * prod_k f1d[k](x_k)
+    QuadratureLoadForm(f, geometry)   L(v) = (f, v) on a mapped patch, f given at the quadrature points
 
 Quadrature: Gauss-Legendre with p+1 points per direction (what ``quadrature_degree = 2p``
 selects on quads/hexes [ext], demos/poisson/poisson.py:89).  The d-dimensional objects are
@@ -179,7 +180,7 @@ def _control_window(geometry, plane, fa, fb):
     return gen.controlFunctionWindow(fa, fb), fa * plane
 
 
-def _mapped(geometry, V, form, row0=None, row1=None, grid=None, block=None):
+def _mapped(geometry, V, form, row0=None, row1=None, grid=None, block=None, nq=None):
     """dolfin.assemble stand-in on a mapped patch: ``geometry`` is a generator / ExtractedSpline
     whose ``cpFuncs`` (nsd+1 homogeneous control functions on the FE nodes of ``V_control``) define
     F = cpFuncs[i]/cpFuncs[nsd] (tIGAr/common.py:917-921); metric-based measure and gradient.  ``row0, row1``: the FE
@@ -197,7 +198,7 @@ def _mapped(geometry, V, form, row0=None, row1=None, grid=None, block=None):
             if len(cp) - 1 != g.dim():
                 raise ValueError("the elasticity form needs as many physical as parametric directions")
             return _dev.assemble_mapped_elasticity_block(verts, g.degree, cp, block[0], block[1], block[2], block[3], **rows)
-        return _dev.assemble_mapped_matrix(verts, g.degree, cp, form, **rows)
+        return _dev.assemble_mapped_matrix(verts, g.degree, cp, form, nq=nq, **rows)
 
     row0, row1 = (0 if row0 is None else int(row0)), (n if row1 is None else int(row1))       # (either may be left out)
     if (row0, row1) == (0, n):
@@ -309,12 +310,16 @@ class ElasticityForm(object):
 
 
 class MassForm(object):
-    """a(u,v) = int u v (``geometry``: see LaplaceForm)."""
+    """a(u,v) = int u v (``geometry``: see LaplaceForm; ``nq``: Gauss points per direction on the mapped patch, p + 1
+    when None)."""
 
-    def __init__(self, geometry=None):
+    def __init__(self, geometry=None, nq=None):
         # a(u, v) = a(v, u) for THIS class; a subclass that adds terms says so itself (ADVICE r5: not inherited)
         self.symmetric = type(self) is MassForm
         self.geometry = geometry
+        if nq is not None and geometry is None:
+            raise ValueError("MassForm: nq belongs to a mapped patch (geometry=...)")
+        self.nq = nq
 
     def factors(self, V):
         g = _single_grid(V)
@@ -322,7 +327,7 @@ class MassForm(object):
 
     def assemble_matrix(self, V, row0=None, row1=None):
         if self.geometry is not None:
-            return _mapped(self.geometry, V, "mass", row0, row1)
+            return _mapped(self.geometry, V, "mass", row0, row1, nq=self.nq)
         return _dev.kron_sum_csr(self.factors(V), row0, row1)
 
 
@@ -382,6 +387,123 @@ class NodalLoadForm(object):
             _dev.vec_copy_range(piece, 0, b, int(row0) - za * plane, int(row1) - int(row0))
             b = piece
         return b
+
+
+def _whole_patch(geometry, V, who):
+    """(element vertices, degree, control functions) of a patch whose control functions this rank holds in full"""
+    g = _single_grid(V)
+    if _single_grid(geometry.V_control).shape() != g.shape():
+        raise ValueError("the geometry lives on a different node grid than the space")
+    cp, node0 = _control_window(geometry, 1, 0, g.shape()[-1])
+    if node0 != 0 or any(v.size() != g.num_nodes() for v in cp):
+        raise NotImplementedError("%s: the control functions are spread over several ranks; quadrature-point operands are "
+                                  "provided on one rank" % who)
+    return [g.vertices[k] for k in range(g.dim())], int(g.degree), cp
+
+
+def _check_nq(nq, p):
+    nq = p + 1 if nq is None else nq
+    most = _dev.assemble_limits()[1]
+    if int(nq) != nq or not 1 <= int(nq) <= most:
+        raise ValueError("nq = %r: 1..%d Gauss points per direction" % (nq, most))
+    return int(nq)
+
+
+class QuadraturePoints(object):
+    """The Gauss points of a mapped patch, element-major (elements and the nq^d points of an element lexicographic with
+    direction 0 fastest): ``x`` host array [npts, nsd] (downloaded on first use), ``x_device`` (nsd * npts values,
+    component-major), ``weights`` = w_q sqrt(det g) prod h_k as a DeviceVector, ``nq``, ``npts``, ``nsd``."""
+
+    def __init__(self, verts, p, cp, nq):
+        self.verts, self.p, self.cp, self.nq, self.nsd = verts, p, cp, nq, len(cp) - 1
+        self.x_device, self.weights = _dev.quad_points(verts, p, cp, nq)
+        self.npts = self.weights.size()
+        self._x = None
+
+    @property
+    def x(self):
+        if self._x is None:
+            self._x = numpy.ascontiguousarray(self.x_device.get_local().reshape(self.nsd, self.npts).T)
+        return self._x
+
+    def values(self, f, who="f"):
+        """point values of ``f`` as a DeviceVector: a callable on ``x`` [npts, nsd] -> [npts], a number, the values
+        themselves (array / DeviceVector), or a Function of the space (evaluated by ``tg_quad_eval``)"""
+        if hasattr(f, "vector") and hasattr(f, "function_space"):
+            return _dev.quad_eval(self.verts, self.p, self.cp, f.vector(), nq=self.nq)
+        if isinstance(f, _dev.DeviceVector):
+            if f.size() != self.npts:
+                raise ValueError("%s: %d point values given, the patch has %d quadrature points" % (who, f.size(), self.npts))
+            return f
+        if callable(f):
+            v = numpy.asarray(f(self.x), dtype=numpy.float64)
+            if v.shape != (self.npts,):
+                raise ValueError("%s: the callable returned an array of shape %s for %d points; expected (%d,)"
+                                 % (who, v.shape, self.npts, self.npts))
+            return _dev.DeviceVector(data=v)
+        if numpy.ndim(f) == 0:
+            v = _dev.DeviceVector(self.npts, zero=False)
+            v.fill(float(f))
+            return v
+        v = numpy.asarray(f, dtype=numpy.float64)
+        if v.shape != (self.npts,):
+            raise ValueError("%s: an array of shape %s given, the patch has %d quadrature points" % (who, v.shape, self.npts))
+        return _dev.DeviceVector(data=v)
+
+    def vector_values(self, f, who="f"):
+        """point values of a vector field (nsd * npts, component-major): a callable ``x -> [npts, nsd]``, an array
+        [npts, nsd], a sequence of nsd numbers, or a DeviceVector already in that layout"""
+        if isinstance(f, _dev.DeviceVector):
+            if f.size() != self.nsd * self.npts:
+                raise ValueError("%s: %d values given, expected nsd * npts = %d" % (who, f.size(), self.nsd * self.npts))
+            return f
+        v = numpy.asarray(f(self.x) if callable(f) else f, dtype=numpy.float64)
+        if v.shape == (self.nsd,):
+            v = numpy.tile(v, (self.npts, 1))
+        if v.shape != (self.npts, self.nsd):
+            raise ValueError("%s: an array of shape %s for %d points; expected (%d, %d)"
+                             % (who, v.shape, self.npts, self.npts, self.nsd))
+        return _dev.DeviceVector(data=numpy.ascontiguousarray(v.T).ravel())
+
+
+def quadrature_points(geometry, V, nq=None, who="quadrature points"):
+    """the ``QuadraturePoints`` of the patch of ``geometry`` (a generator or ExtractedSpline), kept on it per nq and per
+    set of control-function vectors: new vectors give new points, values overwritten in place are not noticed"""
+    verts, p, cp = _whole_patch(geometry, V, who)
+    nq = _check_nq(nq, p)
+    cache = geometry.__dict__.setdefault("_quad_points", {})
+    key = (nq, tuple(id(v) for v in cp))
+    if key not in cache:
+        cache[key] = QuadraturePoints(verts, p, cp, nq)
+    return cache[key]
+
+
+class QuadratureLoadForm(object):
+    """L(v) = sum_q wdet_q f(x_q) v(xi_q) on the mapped patch: the load of ``f`` itself, not of its nodal interpolant
+    (``NodalLoadForm``).  ``f``: a callable on the physical points ``[npts, nsd] -> [npts]`` (evaluated on the host once
+    per geometry), a number, the ``npts`` point values (array / DeviceVector, numbered as ``QuadraturePoints``), or a
+    ``Function`` on the space.  ``nq`` Gauss points per direction (p + 1 when None)."""
+
+    def __init__(self, f, geometry, nq=None):
+        self.f, self.geometry, self.nq = f, geometry, nq
+
+    def point_values(self, V):
+        pts = quadrature_points(self.geometry, V, self.nq, "QuadratureLoadForm")
+        if callable(self.f) and not hasattr(self.f, "vector"):
+            cache = self.__dict__.setdefault("_fq", {})
+            if id(pts) not in cache:
+                cache.clear()
+                cache[id(pts)] = (pts.values(self.f, "QuadratureLoadForm"), pts)      # (pts kept alive: id)
+            return pts, cache[id(pts)][0]
+        return pts, pts.values(self.f, "QuadratureLoadForm")
+
+    def assemble_vector(self, V, row0=None, row1=None):
+        n = _single_grid(V).num_nodes()
+        if (0 if row0 is None else int(row0), n if row1 is None else int(row1)) != (0, n):
+            raise NotImplementedError("QuadratureLoadForm: row blocks (several ranks, streamed operands) are not supported; "
+                                      "the point values are numbered over the whole patch")
+        pts, fq = self.point_values(V)
+        return _dev.quad_load(pts.verts, pts.p, pts.cp, fq, nq=pts.nq)
 
 
 class SeparableLoadForm(object):

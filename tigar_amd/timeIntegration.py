@@ -273,7 +273,8 @@ class LinearTransientProblem(object):
     predictor) and ``advance()`` is one kernel.  Nothing leaves the device between steps.
 
     ``load``: None or a callable ``t -> form`` (anything ``spline.assembleVector`` takes) or ``t -> DeviceVector`` of IGA
-    dofs.  ``x0`` / ``xdot0``: IGA-dof ``DeviceVector`` s, or FE ``Function`` s (brought over by ``spline.FEtoIGA``); None = 0,
+    dofs.  ``x0`` / ``xdot0``: IGA-dof ``DeviceVector`` s, FE ``Function`` s (brought over by ``spline.FEtoIGA``) or callables
+    on the physical points ``[npts, nsd] -> [npts]`` (L2-projected by ``spline.projectDofs(.., applyBCs=True)``); None = 0,
     except ``xdot0=None`` of a first-order generalized-alpha problem: solved from ``M xdot0 = f(t0) - K x0``.  For order 2
     the initial acceleration is solved from ``M a0 = f(t0) - C xdot0 - K x0``.
 
@@ -391,8 +392,11 @@ class LinearTransientProblem(object):
             return out
         if hasattr(v, "vector"):
             v = self.spline.FEtoIGA(v)
+        elif callable(v):
+            v = self.spline.projectDofs(v, applyBCs=True)     # a function of x: its L2 projection
         if not isinstance(v, DeviceVector) or v.size() != self.n:
-            raise ValueError("LinearTransientProblem: initial data must be a DeviceVector of %d IGA dofs or an FE Function" % self.n)
+            raise ValueError("LinearTransientProblem: initial data must be a DeviceVector of %d IGA dofs, an FE Function or a "
+                             "callable" % self.n)
         out[:] = v
         out.zero_entries(self._zero)
         return out
