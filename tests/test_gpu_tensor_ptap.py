@@ -469,7 +469,9 @@ def test_kronecker_sum_forms_are_fused_into_the_x_pass_bit_for_bit():
     #  with a last piece shorter than the others)
     for p, nels, form in ((3, (6, 5, 9), F.LaplaceForm()), (2, (7, 8, 10), F.MassForm()), (1, (4, 4, 6), F.LaplaceForm()),
                           (3, (50, 3, 5), F.LaplaceForm()), (2, (95, 3, 4), F.MassForm()), (1, (130, 3, 4), F.LaplaceForm()),
-                          (3, (70, 2, 4), F.MassForm())):
+                          (3, (70, 2, 4), F.MassForm()),
+                          # (a full piece and a last piece of ONE element, shorter than the p elements it re-walks)
+                          (3, (22, 2, 3), F.LaplaceForm()), (2, (86, 2, 3), F.MassForm()), (1, (119, 2, 3), F.LaplaceForm())):
         Ks = []
         for fused in ("1", "0"):
             os.environ["TIGAR_PTAP_FUSED"] = fused

@@ -10,6 +10,7 @@
 #include "tg_common.h"
 #include "tg_tensor_body.h"
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 struct tg_tensor_plan_s {
@@ -45,6 +46,15 @@ struct tg_tensor_planes_s {
   std::vector<int64_t> pb;          // offset of plane r2 in buf, indexed r2 - z0
 };
 
+// owner of a handle under construction: destroyed on every early return, released to the caller at the end
+struct tt_drop {
+  void operator()(tg_tensor_plan_s *p) const { tg_tensor_plan_destroy(p); }
+  void operator()(tg_tensor_planes_s *p) const { tg_tensor_planes_destroy(p); }
+  void operator()(tg_csr_s *p) const { tg_csr_destroy(p); }
+};
+template <typename T>
+using tt_own = std::unique_ptr<T, tt_drop>;
+
 template <int P>
 __global__ void __launch_bounds__(256) k_tt_check_rows(tt_check_args A, int64_t n, int *status) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -54,42 +64,50 @@ __global__ void __launch_bounds__(256) k_tt_check_rows(tt_check_args A, int64_t 
 // a partly filled last round of waves (26.9 k waves on 4096 slots: 6.6 rounds); four launches pay that four times
 // (x+y over 36 planes at cfg3, both variants alternating inside one process: 12.36 vs 12.49 ms).
 // Workgroups [first[c], first[c+1]) belong to class c, x fastest; the classes with the widest windows come first.
-struct tt_x_multi {
-  tt_x_args c[4];
-  unsigned first[5], gx[4];
+template <typename Args, int N>
+struct tt_multi {
+  Args c[N];
+  unsigned first[N + 1], gx[N];
   int n;
+  // blockIdx.x -> class (returned), workgroup inside the class and piece of the walk (if it is cut into pieces, the piece
+  // is the slowest-varying index: tt_xg_args::ech)
+  __device__ __forceinline__ int decode(unsigned &local, unsigned &piece) const {
+    piece = blockIdx.x / first[n];
+    const unsigned b = blockIdx.x - piece * first[n];
+    int cl = 0;
+    while (cl + 1 < n && b >= first[cl + 1]) cl++;
+    local = b - first[cl];
+    return cl;
+  }
 };
-struct tt_y_multi {
-  tt_y_args c[2];
-  unsigned first[3], gx[2];
-  int n;
-};
+using tt_x_multi = tt_multi<tt_x_args, 4>;
+using tt_y_multi = tt_multi<tt_y_args, 2>;
+template <int NT>
+using tt_xg_multi = tt_multi<tt_xg_args<NT>, 4>;
+
+// a piece length asked for -> the one walked: 0 (one walk) unless it cuts the direction, and never shorter than the 2 P
+// elements a piece needs (it re-walks P of them)
+static int tt_ech(int pick, int nel, int P) { return pick > 0 && pick < nel ? std::max(pick, 2 * P) : 0; }
+static unsigned tt_pieces(int nel, int ech) { return ech > 0 ? (unsigned)tg_cdiv(nel, ech) : 1u; }
 // piece length of the y walk (TIGAR_TT_Y_ECH=n for experiments; default 0 = one walk: the pass is HBM-bound, two / three /
 // four pieces at cfg3 gave 3.07 / 3.12 / 3.05 ms against 3.07)
 static int tt_y_ech(int nel, int P) {
-  static const int env = getenv("TIGAR_TT_Y_ECH") ? atoi(getenv("TIGAR_TT_Y_ECH")) : 0;
-  const int pick = env;
-  return pick > 0 && pick < nel ? std::max(pick, 2 * P) : 0;
+  static const int env = tg_env_int("TIGAR_TT_Y_ECH", 0);
+  return tt_ech(env, nel, P);
 }
-static unsigned tt_pieces(int nel, int ech) { return ech > 0 ? (unsigned)tg_cdiv(nel, ech) : 1u; }
 template <int P, bool V>
 __global__ void __launch_bounds__(64) k_tt_x_multi(tt_x_multi M) {
-  // (the piece of the walk, if it is cut into pieces, is the slowest-varying index: tt_xg_args::ech)
-  const unsigned piece = blockIdx.x / M.first[M.n], b = blockIdx.x - piece * M.first[M.n];
-  int c = 0;
-  while (c + 1 < M.n && b >= M.first[c + 1]) c++;
+  unsigned local, piece;
+  const int c = M.decode(local, piece);
   const tt_x_args &A = M.c[c];
   if (*(volatile int *)A.status) return;     // row lengths differ from the pattern: the closed-form addresses do not apply
-  const unsigned local = b - M.first[c];
   const int bad = tt_x_lane<P, V>(A, (int)(local % M.gx[c]), (int)(local / M.gx[c]), threadIdx.x, (int)piece);
   if (bad) atomicOr(A.status, 1);
 }
 template <int P>
 __global__ void __launch_bounds__(64) k_tt_y_multi(tt_y_multi M) {
-  const unsigned piece = blockIdx.x / M.first[M.n], b = blockIdx.x - piece * M.first[M.n];
-  int c = 0;
-  while (c + 1 < M.n && b >= M.first[c + 1]) c++;
-  const unsigned local = b - M.first[c];
+  unsigned local, piece;
+  const int c = M.decode(local, piece);
   tt_y_lane<P>(M.c[c], (int)(local % M.gx[c]), (int)(local / M.gx[c]), threadIdx.x, (int)piece);
 }
 template <int P>
@@ -102,16 +120,28 @@ __global__ void __launch_bounds__(256) k_tt_rowptr(tt_rowptr_args A, int64_t n) 
 }
 
 template <typename T>
-static int tt_upload(T **dst, const std::vector<T> &h) {
-  TG_TRY(tg_dmalloc(dst, (int64_t)std::max<size_t>(h.size(), 1)));
-  if (!h.empty()) TG_TRY(tg_h2d_staged(*dst, h.data(), h.size() * sizeof(T)));   // (h may be a temporary)
+static int tt_upload(T **dst, const T *h, size_t n) {
+  TG_TRY(tg_dmalloc(dst, (int64_t)std::max<size_t>(n, 1)));
+  if (n) TG_TRY(tg_h2d_staged(*dst, h, n * sizeof(T)));   // (h may be a temporary)
   return 0;
+}
+template <typename T>
+static int tt_upload(T **dst, const std::vector<T> &h) {
+  return tt_upload(dst, h.data(), h.size());
 }
 
 static int tt_rn_host(int P, int a, int nfe) { return (a % P == 0 && a > 0 && a < nfe - 1) ? 2 * P + 1 : P + 1; }
 static int tt_rlo_host(int P, int a, int nfe) {
   (void)nfe;
   return (a % P == 0 && a > 0) ? a - P : (a / P) * P;
+}
+
+// A matrix written by this library with exactly the plan's pattern says so (tg_csr_s::pattern_tag): its column indices
+// need not be read again (227 GB per pass at cfg3).  Any other matrix is verified entry by entry while it is read;
+// TIGAR_PTAP_VERIFY=1 verifies always (read per call: it is switched inside one process).
+static bool tt_certified(const tg_tensor_plan_s *pl, const tg_csr_s *a, int64_t row0) {
+  return a->pattern_tag != 0 && a->pattern_tag == pl->expect_tag && a->pattern_row0 == row0 &&
+         !tg_env_int("TIGAR_PTAP_VERIFY", 0);
 }
 
 extern "C" int tg_tensor_plan_destroy(tg_tensor_plan_t p) {
@@ -131,82 +161,95 @@ extern "C" int tg_tensor_plan_destroy(tg_tensor_plan_t p) {
   return 0;
 }
 
-static int tt_plan_create3(const tg_tensor_pair_dir_t *dirs, bool pair, tg_tensor_plan_t *out) {
-  const int P = dirs[0].p;
-  TG_REQUIRE(P >= 1 && P <= 3 && dirs[1].p == P && dirs[2].p == P,
-             "tg_tensor_plan_create: equal degrees 1..3 in all directions ((2p+1)^2 lanes must fit a wave)");
-  tg_tensor_plan_s *pl = new tg_tensor_plan_s();
-  pl->P = P;
-  pl->pair = pair;
-  int rc = 0;
-  for (int k = 0; k < 3 && !rc; k++) {
+// ---- the steps of plan creation shared by the 3-D and the 2-D plans (pl->P and pl->pair are set) ----
+// the parametric directions [0, nd): host and device tables, function counts and degrees of both sides
+static int tt_plan_dirs(tg_tensor_plan_s *pl, int nd, const tg_tensor_pair_dir_t *dirs, const char *who) {
+  const int P = pl->P;
+  const bool pair = pl->pair;
+  for (int k = 0; k < nd; k++) {
     const int nel = dirs[k].nel, nfe = P * nel + 1, ncp = nel + P;
     const int pr = pair ? dirs[k].pr : P, pc = pair ? dirs[k].pc : P;
-    if (nel < 1 || !dirs[k].wlc || (pair && !dirs[k].wlr) || pr < 1 || pr > P || pc < 1 || pc > P) {
-      tg_set_error("tg_tensor_plan_create: bad direction %d (spline degrees 1..%d on both sides)", k, P);
-      rc = 2;
-      break;
-    }
+    TG_REQUIRE(nel >= 1 && dirs[k].wlc && (!pair || dirs[k].wlr) && pr >= 1 && pr <= P && pc >= 1 && pc <= P,
+               "%s: bad direction %d (spline degrees 1..%d on both sides)", who, k, P);
     const int ncr = nel + pr, ncc = nel + pc;
     pl->pr[k] = pr;
     pl->pc[k] = pc;
     pl->ncr[k] = ncr;
     pl->ncc[k] = ncc;
-    std::vector<double> w(dirs[k].wlc, dirs[k].wlc + (size_t)nel * (P + 1) * (P + 1));
     pl->h_rps[k].assign(nfe + 1, 0);
     for (int a = 0; a < nfe; a++) pl->h_rps[k][a + 1] = pl->h_rps[k][a] + tt_rn_host(P, a, nfe);
     // 1-D pattern of the product: row function i couples to the column functions [i - pr, i + pc], clipped
     pl->h_kps[k].assign(ncr + 1, 0);
     for (int i = 0; i < ncr; i++)
       pl->h_kps[k][i + 1] = pl->h_kps[k][i] + (std::min(ncc - 1, i + pc) - std::max(0, i - pr) + 1);
-    rc = tt_upload(&pl->wl[k], w);
-    if (!rc && pair) {
-      std::vector<double> wr(dirs[k].wlr, dirs[k].wlr + (size_t)nel * (P + 1) * (P + 1));
-      rc = tt_upload(&pl->wlr[k], wr);
-    }
-    if (!rc) rc = tt_upload(&pl->rps[k], pl->h_rps[k]);
-    if (!rc) rc = tt_upload(&pl->kps[k], pl->h_kps[k]);
+    const size_t nw = (size_t)nel * (P + 1) * (P + 1);
+    TG_TRY(tt_upload(&pl->wl[k], dirs[k].wlc, nw));
+    if (pair) TG_TRY(tt_upload(&pl->wlr[k], dirs[k].wlr, nw));
+    TG_TRY(tt_upload(&pl->rps[k], pl->h_rps[k]));
+    TG_TRY(tt_upload(&pl->kps[k], pl->h_kps[k]));
     pl->dir[k].nel = nel;
     pl->dir[k].nfe = nfe;
     pl->dir[k].ncp = ncp;                 // (padded: the layout of the intermediates)
     pl->dir[k].wl = pl->wl[k];
-    pl->dir[k].wlr = pair ? pl->wlr[k] : nullptr;
+    pl->dir[k].wlr = pl->wlr[k];          // (null unless pair)
     pl->dir[k].rps = pl->rps[k];
     pl->dir[k].kps = pl->kps[k];
   }
-  if (!rc) {
-    // the pattern the FE matrix must have, as 1-D CSR patterns: row a couples to the columns [lo(a), lo(a) + n(a))
-    std::vector<int32_t> ecol[3];
-    const int32_t *rps[3], *cls[3];
-    int64_t nr[3], nc[3];
-    for (int k = 0; k < 3; k++) {
-      const int nfe = pl->dir[k].nfe;
-      for (int a = 0; a < nfe; a++) {
-        const int lo = tt_rlo_host(P, a, nfe), n = tt_rn_host(P, a, nfe);
-        for (int j = 0; j < n; j++) ecol[k].push_back(lo + j);
-      }
-      rps[k] = pl->h_rps[k].data();
-      cls[k] = ecol[k].data();
-      nr[k] = nc[k] = nfe;
+  return 0;
+}
+
+// the pattern the FE matrix must have, as 1-D CSR patterns over nd directions: row a couples to the columns
+// [lo(a), lo(a) + n(a)); its hash is the certificate of a matrix written by tg_kron_sum_csr on this grid
+static void tt_plan_pattern(tg_tensor_plan_s *pl, int nd) {
+  const int32_t *rps[3], *cls[3];
+  int64_t nr[3], nc[3];
+  for (int k = 0; k < nd; k++) {
+    const int nfe = pl->dir[k].nfe;
+    for (int a = 0; a < nfe; a++) {
+      const int lo = tt_rlo_host(pl->P, a, nfe), n = tt_rn_host(pl->P, a, nfe);
+      for (int j = 0; j < n; j++) pl->h_ecol[k].push_back(lo + j);
     }
-    pl->expect_tag = tg_pattern_hash(3, nr, nc, rps, cls, 0);
-    for (int k = 0; k < 3; k++) pl->h_ecol[k] = ecol[k];
+    rps[k] = pl->h_rps[k].data();
+    cls[k] = pl->h_ecol[k].data();
+    nr[k] = nc[k] = nfe;
   }
-  if (!rc) {
-    std::vector<int32_t> ls, lv;
-    const int nfe1 = pl->dir[1].nfe;
-    for (int a = 0; a < nfe1; a++) (tt_rn_host(P, a, nfe1) == P + 1 ? ls : lv).push_back(a);
-    pl->nlines1[0] = (int)ls.size();
-    pl->nlines1[1] = (int)lv.size();
-    rc = tt_upload(&pl->lines1[0], ls);
-    if (!rc) rc = tt_upload(&pl->lines1[1], lv);
-    if (!rc) rc = tg_dmalloc(&pl->status, 4);
+  pl->expect_tag = tg_pattern_hash(nd, nr, nc, rps, cls, 0);
+}
+
+// the lines of direction 1 by block extent
+static int tt_plan_lines1(tg_tensor_plan_s *pl) {
+  std::vector<int32_t> ls, lv;
+  const int P = pl->P, nfe1 = pl->dir[1].nfe;
+  for (int a = 0; a < nfe1; a++) (tt_rn_host(P, a, nfe1) == P + 1 ? ls : lv).push_back(a);
+  pl->nlines1[0] = (int)ls.size();
+  pl->nlines1[1] = (int)lv.size();
+  TG_TRY(tt_upload(&pl->lines1[0], ls));
+  return tt_upload(&pl->lines1[1], lv);
+}
+
+// plain directions as pair directions with the degree on both sides
+static void tt_as_pair_dirs(int nd, const tg_tensor_dir_t *dirs, tg_tensor_pair_dir_t *pd) {
+  for (int k = 0; k < nd; k++) {
+    pd[k].p = dirs[k].p;
+    pd[k].nel = dirs[k].nel;
+    pd[k].pr = pd[k].pc = dirs[k].p;
+    pd[k].wlr = nullptr;
+    pd[k].wlc = dirs[k].wl;
   }
-  if (rc) {
-    tg_tensor_plan_destroy(pl);
-    return rc;
-  }
-  *out = pl;
+}
+
+static int tt_plan_create3(const tg_tensor_pair_dir_t *dirs, bool pair, tg_tensor_plan_t *out) {
+  const int P = dirs[0].p;
+  TG_REQUIRE(P >= 1 && P <= 3 && dirs[1].p == P && dirs[2].p == P,
+             "tg_tensor_plan_create: equal degrees 1..3 in all directions ((2p+1)^2 lanes must fit a wave)");
+  tt_own<tg_tensor_plan_s> pl(new tg_tensor_plan_s());
+  pl->P = P;
+  pl->pair = pair;
+  TG_TRY(tt_plan_dirs(pl.get(), 3, dirs, "tg_tensor_plan_create"));
+  tt_plan_pattern(pl.get(), 3);
+  TG_TRY(tt_plan_lines1(pl.get()));
+  TG_TRY(tg_dmalloc(&pl->status, 4));
+  *out = pl.release();
   return 0;
 }
 
@@ -214,13 +257,7 @@ extern "C" int tg_tensor_plan_create(int d, const tg_tensor_dir_t *dirs, tg_tens
   TG_REQUIRE_INIT();
   TG_REQUIRE(d == 3 && dirs && out, "tg_tensor_plan_create: three parametric directions expected");
   tg_tensor_pair_dir_t pd[3];
-  for (int k = 0; k < 3; k++) {
-    pd[k].p = dirs[k].p;
-    pd[k].nel = dirs[k].nel;
-    pd[k].pr = pd[k].pc = dirs[k].p;
-    pd[k].wlr = nullptr;
-    pd[k].wlc = dirs[k].wl;
-  }
+  tt_as_pair_dirs(3, dirs, pd);
   return tt_plan_create3(pd, false, out);
 }
 
@@ -250,234 +287,64 @@ extern "C" int tg_tensor_planes_destroy(tg_tensor_planes_t p) {
     }                          \
   } while (0)
 
-extern "C" int tg_tensor_planes(tg_tensor_plan_t pl, tg_csr_t a, int64_t a_row0, int z0, int z1,
-                                tg_tensor_planes_t *out) {
-  TG_REQUIRE_INIT();
-  TG_REQUIRE(pl && a && out, "null argument to tg_tensor_planes");
-  TG_REQUIRE(pl->d == 3, "tg_tensor_planes: the plan belongs to a 2-D patch (tg_tensor2_ptap)");
-  TG_REQUIRE_CANONICAL(a);
-  const int P = pl->P, W = 2 * P + 1;
-  const tt_dir_t &D0 = pl->dir[0], &D1 = pl->dir[1], &D2 = pl->dir[2];
-  const int64_t plane_fe = (int64_t)D0.nfe * D1.nfe;
-  TG_REQUIRE(z0 >= 0 && z1 > z0 && z1 <= D2.nfe, "tg_tensor_planes: plane range out of bounds");
-  TG_REQUIRE(a_row0 % plane_fe == 0 && a_row0 <= z0 * plane_fe && a_row0 + a->nrows >= z1 * plane_fe,
-             "tg_tensor_planes: the FE rows given do not cover whole planes [%d,%d)", z0, z1);
-  if (a->ncols != plane_fe * D2.nfe) return 100;     // not a matrix on this node grid
-  const int aplane0 = (int)(a_row0 / plane_fe);
-  const int np = z1 - z0;
-  // plane bases of the two intermediates (B1: [c2][m0][c1] blocks, B2: [m1][m0][c2] blocks)
-  std::vector<int64_t> pb1(np + 1, 0), pb2(np + 1, 0);
-  std::vector<int32_t> pls[2];
-  for (int q = 0; q < np; q++) {
-    const int n2 = tt_rn_host(P, z0 + q, D2.nfe);
-    pb1[q + 1] = pb1[q] + (int64_t)W * n2 * D0.ncp * pl->h_rps[1][D1.nfe];
-    pb2[q + 1] = pb2[q] + (int64_t)W * W * n2 * D0.ncp * D1.ncp;
-    pls[n2 == P + 1 ? 0 : 1].push_back(z0 + q);
-  }
-  double *b1 = nullptr;
-  int64_t *d_pb1 = nullptr, *d_pb2 = nullptr;
-  int32_t *d_pl[2] = {nullptr, nullptr};
-  tg_tensor_planes_s *res = new tg_tensor_planes_s();
-  res->z0 = z0;
-  res->z1 = z1;
-  res->pb = pb2;
-  int rc = tg_dmalloc(&b1, pb1[np]);
-  if (!rc) rc = tg_dmalloc(&res->buf, pb2[np]);
-  if (!rc) rc = tg_dmalloc(&res->status, 4);
-  if (!rc) rc = tt_upload(&d_pb1, pb1);
-  if (!rc) rc = tt_upload(&d_pb2, pb2);
-  if (!rc) rc = tt_upload(&d_pl[0], pls[0]);
-  if (!rc) rc = tt_upload(&d_pl[1], pls[1]);
-  // (one flag per set of planes, not per plan: with a certified matrix nobody waits here, and the flag of an earlier
-  //  piece of the ring must still be there when the z stage reads it)
-  if (!rc && hipMemsetAsync(res->status, 0, sizeof(int), g_tg.stream) != hipSuccess) rc = 1;
-  int bad = 0;
-  bool certified_pass = false;
-  if (!rc) {
-    // row lengths of the planes against the pattern (8 B per row; the x pass then needs no row pointers)
-    {
-      tt_check_args Cq;
-      Cq.rowptr = a->rowptr;
-      Cq.nfe0 = D0.nfe;
-      Cq.nfe1 = D1.nfe;
-      Cq.nfe2 = D2.nfe;
-      Cq.aplane0 = aplane0;
-      Cq.z0 = z0;
-      Cq.dense2 = 0;
-      const int64_t nr = (int64_t)np * plane_fe;
-#define TT_C(PP) hipLaunchKernelGGL((k_tt_check_rows<PP>), dim3((unsigned)tg_cdiv(nr, 256)), dim3(256), 0, g_tg.stream, Cq, nr, res->status)
-      TT_DISPATCH_P(P, TT_C);
-#undef TT_C
-    }
-    // x pass: the (plane class, line class) combinations in one launch, widest windows first
-    // The walk in TWO pieces (each lane walks half of the direction; the second piece re-reads the rows of A of p elements:
-    // +1-2 % of A): 6.71 -> 6.27 ms per sub-slab at cfg3 with the FE matrix materialised, 3.76 -> 3.50 ms at cfg2; three and
-    // more pieces (96, 64, 48 elements at cfg3) gave nothing (6.76-6.86 ms) -- unlike the pass that forms A's entries itself
-    // this one is not waiting for its scalar tables.  TIGAR_TT_X_ECH=n: pieces of n elements, 0: one walk.
-    static const int x_ech_env = getenv("TIGAR_TT_X_ECH") ? atoi(getenv("TIGAR_TT_X_ECH")) : -1;
-    const int x_ech_pick = x_ech_env >= 0 ? x_ech_env : (D0.nel >= 64 ? (D0.nel + 1) / 2 : 0);
-    const int x_ech = x_ech_pick > 0 && x_ech_pick < D0.nel ? std::max(x_ech_pick, 2 * P) : 0;
-    const unsigned x_pieces = x_ech > 0 ? (unsigned)tg_cdiv(D0.nel, x_ech) : 1u;
-    {
-      tt_x_multi XM;
-      memset(&XM, 0, sizeof(XM));
-      for (int pc = 1; pc >= 0; pc--) {
-        if (pls[pc].empty()) continue;
-        const int n2 = pc == 0 ? P + 1 : W;
-        for (int lc = 1; lc >= 0; lc--) {
-          if (!pl->nlines1[lc]) continue;
-          const int n1 = lc == 0 ? P + 1 : W;
-          tt_x_args &X = XM.c[XM.n];
-          X.rowptr = a->rowptr;
-          X.col = a->col;
-          X.val = a->val;
-          X.rps2 = D2.rps;
-          X.aplane0 = aplane0;
-          X.d0 = D0;
-          X.nfe1 = D1.nfe;
-          X.nfe2 = D2.nfe;
-          X.rps1 = D1.rps;
-          X.lines = pl->lines1[lc];
-          X.nlines = pl->nlines1[lc];
-          X.n1 = n1;
-          X.L = std::max(1, 64 / (n1 * n2));
-          X.planes = d_pl[pc];
-          X.n2 = n2;
-          X.b1 = b1;
-          X.pb1 = d_pb1;
-          X.z0 = z0;
-          X.status = res->status;
-          X.ech = x_ech;
-          XM.gx[XM.n] = (unsigned)tg_cdiv(X.nlines, X.L);
-          XM.first[XM.n + 1] = XM.first[XM.n] + XM.gx[XM.n] * (unsigned)pls[pc].size();
-          XM.n++;
-        }
-      }
-      // A matrix written by this library with exactly this pattern says so (tg_csr_s::pattern_tag): its column indices
-      // need not be read again (227 GB per pass at cfg3).  Any other matrix is verified entry by entry while it is read;
-      // TIGAR_PTAP_VERIFY=1 verifies always.
-      const bool certified = certified_pass = a->pattern_tag != 0 && a->pattern_tag == pl->expect_tag && a->pattern_row0 == a_row0 &&
-                             !(getenv("TIGAR_PTAP_VERIFY") && atoi(getenv("TIGAR_PTAP_VERIFY")));
-      if (XM.n > 0 && XM.first[XM.n] > 0) {
-#define TT_X(PP) hipLaunchKernelGGL((k_tt_x_multi<PP, true>), dim3(XM.first[XM.n] * x_pieces), dim3(64), 0, g_tg.stream, XM)
-#define TT_XC(PP) hipLaunchKernelGGL((k_tt_x_multi<PP, false>), dim3(XM.first[XM.n] * x_pieces), dim3(64), 0, g_tg.stream, XM)
-        if (certified) TT_DISPATCH_P(P, TT_XC);
-        else TT_DISPATCH_P(P, TT_X);
-#undef TT_X
-#undef TT_XC
-        g_tg.prof_n[TG_PROF_PTAP_CERTIFIED] += certified ? 1 : 0;
-      }
-    }
-    // y pass: both plane classes in one launch
-    {
-      tt_y_multi YM;
-      memset(&YM, 0, sizeof(YM));
-      for (int pc = 1; pc >= 0; pc--) {
-        if (pls[pc].empty()) continue;
-        const int n2 = pc == 0 ? P + 1 : W;
-        tt_y_args &Y = YM.c[YM.n];
-        Y.b1 = b1;
-        Y.pb1 = d_pb1;
-        Y.b2 = res->buf;
-        Y.pb2 = d_pb2;
-        Y.z0 = z0;
-        Y.d1 = D1;
-        Y.ncp0 = D0.ncp;
-        Y.planes = d_pl[pc];
-        Y.n2 = n2;
-        Y.L = std::max(1, 64 / (W * n2));
-        Y.ech = tt_y_ech(D1.nel, P);
-        YM.gx[YM.n] = (unsigned)tg_cdiv(D0.ncp, Y.L);
-        YM.first[YM.n + 1] = YM.first[YM.n] + YM.gx[YM.n] * (unsigned)pls[pc].size();
-        YM.n++;
-      }
-      if (YM.n > 0 && YM.first[YM.n] > 0) {
-#define TT_Y(PP) \
-  hipLaunchKernelGGL((k_tt_y_multi<PP>), dim3(YM.first[YM.n] * tt_pieces(D1.nel, tt_y_ech(D1.nel, P))), dim3(64), 0, g_tg.stream, YM)
-        TT_DISPATCH_P(P, TT_Y);
-#undef TT_Y
-      }
-    }
-    if (hipGetLastError() != hipSuccess) {
-      tg_set_error("tg_tensor_planes: kernel launch failed");
-      rc = 1;
-    }
-    // a matrix whose pattern was verified entry by entry may have failed: the caller is told now (status 100).  A
-    // certified matrix cannot, and the host goes on enqueueing (the z stage reads the flag when it waits anyway).
-    if (!certified_pass) {
-      if (!rc && hipMemcpyAsync(&bad, res->status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess) rc = 1;
-      if (!rc && hipStreamSynchronize(g_tg.stream) != hipSuccess) {
-        tg_set_error("tg_tensor_planes: %s", hipGetErrorString(hipGetLastError()));
-        rc = 1;
-      }
-    }
-  }
-  tg_dfree(b1);
-  tg_dfree(d_pb1);
-  tg_dfree(d_pb2);
-  tg_dfree(d_pl[0]);
-  tg_dfree(d_pl[1]);
-  if (rc || bad) {
-    tg_tensor_planes_destroy(res);
-    return rc ? rc : 100;          // 100: A does not have the element-coupling pattern -> general path
-  }
-  *out = res;
-  return 0;
-}
+// What the x and y passes over the FE planes [z0, z1) share, whatever forms the entries of A: the layout of the two
+// intermediates (B1: [c2][m0][c1] blocks, B2: [m1][m0][c2] blocks), the planes by class, their device copies, B1 itself
+// and the planes being built.  Everything but the planes released to the caller is freed with the set.
+struct tt_plane_set {
+  int z0 = 0;
+  std::vector<int64_t> pb1;           // plane bases in B1 (those in B2: res->pb)
+  std::vector<int32_t> pls[2];        // FE planes by block extent in direction 2: short (P+1) and vertex (2P+1)
+  tg_dbuf<double> b1;
+  tg_dbuf<int64_t> d_pb1, d_pb2;
+  tg_dbuf<int32_t> d_pl[2];
+  tt_own<tg_tensor_planes_s> res;
 
-// ------------------------------------------------------------------------------------------------------
-// x and y passes for an FE matrix given as a Kronecker sum of 1-D matrices on the element-coupling pattern: the matrix
-// is never materialised (tt_xg_lane); everything downstream (y pass, z stage) is unchanged and the planes returned are
-// bit for bit those tg_tensor_planes computes from the matrix tg_kron_sum_csr would have written.
-template <int NT>
-struct tt_xg_multi {
-  tt_xg_args<NT> c[4];
-  unsigned first[5], gx[4];
-  int n;
+  int init(const tg_tensor_plan_s *pl, int z0_, int z1) {
+    const int P = pl->P, W = 2 * P + 1, np = z1 - z0_;
+    const tt_dir_t &D0 = pl->dir[0], &D1 = pl->dir[1], &D2 = pl->dir[2];
+    z0 = z0_;
+    res.reset(new tg_tensor_planes_s());
+    res->z0 = z0;
+    res->z1 = z1;
+    std::vector<int64_t> &pb2 = res->pb;
+    pb1.assign(np + 1, 0);
+    pb2.assign(np + 1, 0);
+    for (int q = 0; q < np; q++) {
+      const int n2 = tt_rn_host(P, z0 + q, D2.nfe);
+      pb1[q + 1] = pb1[q] + (int64_t)W * n2 * D0.ncp * pl->h_rps[1][D1.nfe];
+      pb2[q + 1] = pb2[q] + (int64_t)W * W * n2 * D0.ncp * D1.ncp;
+      pls[n2 == P + 1 ? 0 : 1].push_back(z0 + q);
+    }
+    TG_TRY(b1.alloc(pb1[np]));
+    TG_TRY(tg_dmalloc(&res->buf, pb2[np]));
+    TG_TRY(tg_dmalloc(&res->status, 4));
+    TG_TRY(tt_upload(&d_pb1.p, pb1));
+    TG_TRY(tt_upload(&d_pb2.p, pb2));
+    TG_TRY(tt_upload(&d_pl[0].p, pls[0]));
+    TG_TRY(tt_upload(&d_pl[1].p, pls[1]));
+    // (one flag per set of planes, not per plan: with a certified matrix nobody waits here, and the flag of an earlier
+    //  piece of the ring must still be there when the z stage reads it)
+    return hipMemsetAsync(res->status, 0, sizeof(int), g_tg.stream) != hipSuccess;
+  }
+  tg_tensor_planes_s *release() { return res.release(); }
 };
-template <int P, int NT>
-__global__ void __launch_bounds__(64) k_tt_xg_multi(tt_xg_multi<NT> M) {
-  // (the piece of the walk is the slowest-varying index: see tt_xg_args::ech)
-  const unsigned piece = blockIdx.x / M.first[M.n], b = blockIdx.x - piece * M.first[M.n];
-  int c = 0;
-  while (c + 1 < M.n && b >= M.first[c + 1]) c++;
-  const unsigned local = b - M.first[c];
-  tt_xg_lane<P, NT>(M.c[c], (int)(local % M.gx[c]), (int)(local / M.gx[c]), threadIdx.x, (int)piece);
-}
 
-template <int NT>
-static int tt_launch_xg(tg_tensor_plan_s *pl, int z0, const std::vector<int32_t> *pls, int32_t *const *d_pl, double *b1,
-                        const int64_t *d_pb1, const int *nnz1d) {
+// The (plane class, line class) combinations of an x pass over the planes of S, widest windows first: the class table and
+// the fields tt_x_args and tt_xg_args<NT> have in common; `own(X)` sets those only one of them has.
+template <typename Args, typename F>
+static void tt_x_classes(const tg_tensor_plan_s *pl, const tt_plane_set &S, int ech, tt_multi<Args, 4> &XM, F own) {
   const int P = pl->P, W = 2 * P + 1;
   const tt_dir_t &D0 = pl->dir[0], &D1 = pl->dir[1], &D2 = pl->dir[2];
-  tt_xg_multi<NT> XM;
   memset(&XM, 0, sizeof(XM));
-  // The walk in pieces, the piece as the slowest-varying block index: what a wave reads through the scalar unit per element --
-  // the rows of the x factor of every term (P nodes x NT terms x ~1.5 (P + 1) doubles) and the local weights ((P + 1)^2
-  // doubles) -- is 0.56 KB at P = 3 with three terms, 140 KB for the whole direction at cfg3: the waves of a CU, spread over
-  // the direction, kept missing the 16 KB scalar cache (six batches of scalar loads per element, each waited for: 36 % of the
-  // vector cycles busy).  With all resident workgroups inside one window of ~12 KB the loads hit: 3.41 -> 2.34 ms per
-  // sub-slab at cfg3 (pieces of 8 / 12 / 16 / 20 / 24 / 32 / 40 / 48 / 64 elements: 2.60 / 2.46 / 2.38 / 2.34 / 2.35 / 2.38 /
-  // 2.63 / 2.97 / 3.34 ms; a piece re-walks P elements, its rows are bit for bit those of the whole walk).
-  // TIGAR_TT_XG_ECH=n sets the piece length, 0 walks the direction at once.
-  static const int ech_env = getenv("TIGAR_TT_XG_ECH") ? atoi(getenv("TIGAR_TT_XG_ECH")) : -1;
-  const double per_element = 8.0 * (P * NT * 1.5 * (P + 1) + (P + 1) * (P + 1));
-  int ech = ech_env >= 0 ? ech_env : (int)(12288.0 / per_element);
-  ech = ech > 0 && ech < D0.nel ? std::max(ech, 2 * P) : 0;
   for (int pc = 1; pc >= 0; pc--) {
-    if (pls[pc].empty()) continue;
+    if (S.pls[pc].empty()) continue;
     const int n2 = pc == 0 ? P + 1 : W;
     for (int lc = 1; lc >= 0; lc--) {
       if (!pl->nlines1[lc]) continue;
       const int n1 = lc == 0 ? P + 1 : W;
-      tt_xg_args<NT> &X = XM.c[XM.n];
+      Args &X = XM.c[XM.n];
+      own(X);
       X.d0 = D0;
-      X.cv0 = pl->kcv[0];
-      X.cv1 = pl->kcv[1];
-      X.cv2 = pl->kcv[2];
-      X.nnz0 = nnz1d[0];
-      X.nnz1 = nnz1d[1];
-      X.nnz2 = nnz1d[2];
       X.rps1 = D1.rps;
       X.rps2 = D2.rps;
       X.nfe1 = D1.nfe;
@@ -486,23 +353,167 @@ static int tt_launch_xg(tg_tensor_plan_s *pl, int z0, const std::vector<int32_t>
       X.nlines = pl->nlines1[lc];
       X.n1 = n1;
       X.L = std::max(1, 64 / (n1 * n2));
-      X.planes = d_pl[pc];
+      X.planes = S.d_pl[pc];
       X.n2 = n2;
-      X.b1 = b1;
-      X.pb1 = d_pb1;
-      X.z0 = z0;
+      X.b1 = S.b1;
+      X.pb1 = S.d_pb1;
+      X.z0 = S.z0;
       X.ech = ech;
       XM.gx[XM.n] = (unsigned)tg_cdiv(X.nlines, X.L);
-      XM.first[XM.n + 1] = XM.first[XM.n] + XM.gx[XM.n] * (unsigned)pls[pc].size();
+      XM.first[XM.n + 1] = XM.first[XM.n] + XM.gx[XM.n] * (unsigned)S.pls[pc].size();
       XM.n++;
     }
   }
-  if (XM.n == 0 || XM.first[XM.n] == 0) return 0;
-  const unsigned npieces = ech > 0 ? (unsigned)tg_cdiv(D0.nel, ech) : 1u;
-#define TT_XG(PP) hipLaunchKernelGGL((k_tt_xg_multi<PP, NT>), dim3(XM.first[XM.n] * npieces), dim3(64), 0, g_tg.stream, XM)
+}
+
+// y pass of the 3-D path: both plane classes in one launch
+static void tt_launch_y(const tg_tensor_plan_s *pl, const tt_plane_set &S) {
+  const int P = pl->P, W = 2 * P + 1;
+  const tt_dir_t &D0 = pl->dir[0], &D1 = pl->dir[1];
+  const int ech = tt_y_ech(D1.nel, P);
+  tt_y_multi YM;
+  memset(&YM, 0, sizeof(YM));
+  for (int pc = 1; pc >= 0; pc--) {
+    if (S.pls[pc].empty()) continue;
+    const int n2 = pc == 0 ? P + 1 : W;
+    tt_y_args &Y = YM.c[YM.n];
+    Y.b1 = S.b1;
+    Y.pb1 = S.d_pb1;
+    Y.b2 = S.res->buf;
+    Y.pb2 = S.d_pb2;
+    Y.z0 = S.z0;
+    Y.d1 = D1;
+    Y.ncp0 = D0.ncp;
+    Y.planes = S.d_pl[pc];
+    Y.n2 = n2;
+    Y.L = std::max(1, 64 / (W * n2));
+    Y.ech = ech;
+    YM.gx[YM.n] = (unsigned)tg_cdiv(D0.ncp, Y.L);
+    YM.first[YM.n + 1] = YM.first[YM.n] + YM.gx[YM.n] * (unsigned)S.pls[pc].size();
+    YM.n++;
+  }
+  if (YM.n == 0 || YM.first[YM.n] == 0) return;
+#define TT_Y(PP) hipLaunchKernelGGL((k_tt_y_multi<PP>), dim3(YM.first[YM.n] * tt_pieces(D1.nel, ech)), dim3(64), 0, g_tg.stream, YM)
+  TT_DISPATCH_P(P, TT_Y);
+#undef TT_Y
+}
+
+extern "C" int tg_tensor_planes(tg_tensor_plan_t pl, tg_csr_t a, int64_t a_row0, int z0, int z1,
+                                tg_tensor_planes_t *out) {
+  TG_REQUIRE_INIT();
+  TG_REQUIRE(pl && a && out, "null argument to tg_tensor_planes");
+  TG_REQUIRE(pl->d == 3, "tg_tensor_planes: the plan belongs to a 2-D patch (tg_tensor2_ptap)");
+  TG_REQUIRE_CANONICAL(a);
+  const int P = pl->P;
+  const tt_dir_t &D0 = pl->dir[0], &D1 = pl->dir[1], &D2 = pl->dir[2];
+  const int64_t plane_fe = (int64_t)D0.nfe * D1.nfe;
+  TG_REQUIRE(z0 >= 0 && z1 > z0 && z1 <= D2.nfe, "tg_tensor_planes: plane range out of bounds");
+  TG_REQUIRE(a_row0 % plane_fe == 0 && a_row0 <= z0 * plane_fe && a_row0 + a->nrows >= z1 * plane_fe,
+             "tg_tensor_planes: the FE rows given do not cover whole planes [%d,%d)", z0, z1);
+  if (a->ncols != plane_fe * D2.nfe) return 100;     // not a matrix on this node grid
+  const int aplane0 = (int)(a_row0 / plane_fe);
+  tt_plane_set S;
+  TG_TRY(S.init(pl, z0, z1));
+  int *status = S.res->status;
+  // row lengths of the planes against the pattern (8 B per row; the x pass then needs no row pointers)
+  {
+    tt_check_args Cq;
+    Cq.rowptr = a->rowptr;
+    Cq.nfe0 = D0.nfe;
+    Cq.nfe1 = D1.nfe;
+    Cq.nfe2 = D2.nfe;
+    Cq.aplane0 = aplane0;
+    Cq.z0 = z0;
+    Cq.dense2 = 0;
+    const int64_t nr = (int64_t)(z1 - z0) * plane_fe;
+#define TT_C(PP) hipLaunchKernelGGL((k_tt_check_rows<PP>), dim3((unsigned)tg_cdiv(nr, 256)), dim3(256), 0, g_tg.stream, Cq, nr, status)
+    TT_DISPATCH_P(P, TT_C);
+#undef TT_C
+  }
+  // x pass: the (plane class, line class) combinations in one launch, widest windows first
+  // The walk in TWO pieces (each lane walks half of the direction; the second piece re-reads the rows of A of p elements:
+  // +1-2 % of A): 6.71 -> 6.27 ms per sub-slab at cfg3 with the FE matrix materialised, 3.76 -> 3.50 ms at cfg2; three and
+  // more pieces (96, 64, 48 elements at cfg3) gave nothing (6.76-6.86 ms) -- unlike the pass that forms A's entries itself
+  // this one is not waiting for its scalar tables.  TIGAR_TT_X_ECH=n: pieces of n elements, 0: one walk.
+  static const int x_ech_env = tg_env_int("TIGAR_TT_X_ECH", -1);
+  const int x_ech = tt_ech(x_ech_env >= 0 ? x_ech_env : (D0.nel >= 64 ? (D0.nel + 1) / 2 : 0), D0.nel, P);
+  tt_x_multi XM;
+  tt_x_classes(pl, S, x_ech, XM, [&](tt_x_args &X) {
+    X.rowptr = a->rowptr;
+    X.col = a->col;
+    X.val = a->val;
+    X.aplane0 = aplane0;
+    X.status = status;
+  });
+  const bool certified = tt_certified(pl, a, a_row0);
+  if (XM.n > 0 && XM.first[XM.n] > 0) {
+    const dim3 grid(XM.first[XM.n] * tt_pieces(D0.nel, x_ech));
+#define TT_X(PP) hipLaunchKernelGGL((k_tt_x_multi<PP, true>), grid, dim3(64), 0, g_tg.stream, XM)
+#define TT_XC(PP) hipLaunchKernelGGL((k_tt_x_multi<PP, false>), grid, dim3(64), 0, g_tg.stream, XM)
+    if (certified) TT_DISPATCH_P(P, TT_XC);
+    else TT_DISPATCH_P(P, TT_X);
+#undef TT_X
+#undef TT_XC
+    g_tg.prof_n[TG_PROF_PTAP_CERTIFIED] += certified ? 1 : 0;
+  }
+  tt_launch_y(pl, S);
+  if (hipGetLastError() != hipSuccess) {
+    tg_set_error("tg_tensor_planes: kernel launch failed");
+    return 1;
+  }
+  // a matrix whose pattern was verified entry by entry may have failed: the caller is told now (status 100).  A
+  // certified matrix cannot, and the host goes on enqueueing (the z stage reads the flag when it waits anyway).
+  if (!certified) {
+    int bad = 0;
+    if (hipMemcpyAsync(&bad, status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess) return 1;
+    if (hipStreamSynchronize(g_tg.stream) != hipSuccess) {
+      tg_set_error("tg_tensor_planes: %s", hipGetErrorString(hipGetLastError()));
+      return 1;
+    }
+    if (bad) return 100;           // A does not have the element-coupling pattern -> general path
+  }
+  *out = S.release();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// x and y passes for an FE matrix given as a Kronecker sum of 1-D matrices on the element-coupling pattern: the matrix
+// is never materialised (tt_xg_lane); everything downstream (y pass, z stage) is unchanged and the planes returned are
+// bit for bit those tg_tensor_planes computes from the matrix tg_kron_sum_csr would have written.
+template <int P, int NT>
+__global__ void __launch_bounds__(64) k_tt_xg_multi(tt_xg_multi<NT> M) {
+  unsigned local, piece;
+  const int c = M.decode(local, piece);
+  tt_xg_lane<P, NT>(M.c[c], (int)(local % M.gx[c]), (int)(local / M.gx[c]), threadIdx.x, (int)piece);
+}
+
+template <int NT>
+static void tt_launch_xg(const tg_tensor_plan_s *pl, const tt_plane_set &S, const int *nnz1d) {
+  const int P = pl->P, nel0 = pl->dir[0].nel;
+  // The walk in pieces, the piece as the slowest-varying block index: what a wave reads through the scalar unit per element --
+  // the rows of the x factor of every term (P nodes x NT terms x ~1.5 (P + 1) doubles) and the local weights ((P + 1)^2
+  // doubles) -- is 0.56 KB at P = 3 with three terms, 140 KB for the whole direction at cfg3: the waves of a CU, spread over
+  // the direction, kept missing the 16 KB scalar cache (six batches of scalar loads per element, each waited for: 36 % of the
+  // vector cycles busy).  With all resident workgroups inside one window of ~12 KB the loads hit: 3.41 -> 2.34 ms per
+  // sub-slab at cfg3 (pieces of 8 / 12 / 16 / 20 / 24 / 32 / 40 / 48 / 64 elements: 2.60 / 2.46 / 2.38 / 2.34 / 2.35 / 2.38 /
+  // 2.63 / 2.97 / 3.34 ms; a piece re-walks P elements, its rows are bit for bit those of the whole walk).
+  // TIGAR_TT_XG_ECH=n sets the piece length, 0 walks the direction at once.
+  static const int ech_env = tg_env_int("TIGAR_TT_XG_ECH", -1);
+  const double per_element = 8.0 * (P * NT * 1.5 * (P + 1) + (P + 1) * (P + 1));
+  const int ech = tt_ech(ech_env >= 0 ? ech_env : (int)(12288.0 / per_element), nel0, P);
+  tt_xg_multi<NT> XM;
+  tt_x_classes(pl, S, ech, XM, [&](tt_xg_args<NT> &X) {
+    X.cv0 = pl->kcv[0];
+    X.cv1 = pl->kcv[1];
+    X.cv2 = pl->kcv[2];
+    X.nnz0 = nnz1d[0];
+    X.nnz1 = nnz1d[1];
+    X.nnz2 = nnz1d[2];
+  });
+  if (XM.n == 0 || XM.first[XM.n] == 0) return;
+#define TT_XG(PP) hipLaunchKernelGGL((k_tt_xg_multi<PP, NT>), dim3(XM.first[XM.n] * tt_pieces(nel0, ech)), dim3(64), 0, g_tg.stream, XM)
   TT_DISPATCH_P(P, TT_XG);
 #undef TT_XG
-  return 0;
 }
 
 extern "C" int tg_tensor_planes_kron(tg_tensor_plan_t pl, int nterms, const tg_kron_dir_t *dirs, int z0, int z1,
@@ -511,9 +522,7 @@ extern "C" int tg_tensor_planes_kron(tg_tensor_plan_t pl, int nterms, const tg_k
   TG_REQUIRE(pl && dirs && out, "null argument to tg_tensor_planes_kron");
   TG_REQUIRE(pl->d == 3, "tg_tensor_planes_kron: 3-D plans only");
   if (nterms < 1 || nterms > 3) return 100;
-  const int P = pl->P, W = 2 * P + 1;
-  const tt_dir_t &D0 = pl->dir[0], &D1 = pl->dir[1], &D2 = pl->dir[2];
-  TG_REQUIRE(z0 >= 0 && z1 > z0 && z1 <= D2.nfe, "tg_tensor_planes_kron: plane range out of bounds");
+  TG_REQUIRE(z0 >= 0 && z1 > z0 && z1 <= pl->dir[2].nfe, "tg_tensor_planes_kron: plane range out of bounds");
   // the 1-D factors must sit on exactly the 1-D element-coupling patterns of the plan
   int nnz1d[3];
   uint64_t key = 1469598103934665603ull ^ (uint64_t)nterms;
@@ -527,6 +536,9 @@ extern "C" int tg_tensor_planes_kron(tg_tensor_plan_t pl, int nterms, const tg_k
     for (int64_t i = 0; i < (int64_t)nterms * nnz1d[k]; i++) key = (key ^ w[i]) * 1099511628211ull + (uint64_t)k;
   }
   if (key != pl->kcv_key || nterms != pl->kcv_terms || !pl->kcv[0]) {
+    // (no key while the tables are replaced: a failure half way must not leave the old key on a mix of old and new tables)
+    pl->kcv_key = 0;
+    pl->kcv_terms = 0;
     // (the previous tables may still be read by kernels in flight: released to the pool in stream order)
     for (int k = 0; k < 3; k++) {
       tg_dfree(pl->kcv[k]);
@@ -537,76 +549,17 @@ extern "C" int tg_tensor_planes_kron(tg_tensor_plan_t pl, int nterms, const tg_k
     pl->kcv_key = key;
     pl->kcv_terms = nterms;
   }
-  const int np = z1 - z0;
-  std::vector<int64_t> pb1(np + 1, 0), pb2(np + 1, 0);
-  std::vector<int32_t> pls[2];
-  for (int q = 0; q < np; q++) {
-    const int n2 = tt_rn_host(P, z0 + q, D2.nfe);
-    pb1[q + 1] = pb1[q] + (int64_t)W * n2 * D0.ncp * pl->h_rps[1][D1.nfe];
-    pb2[q + 1] = pb2[q] + (int64_t)W * W * n2 * D0.ncp * D1.ncp;
-    pls[n2 == P + 1 ? 0 : 1].push_back(z0 + q);
+  tt_plane_set S;
+  TG_TRY(S.init(pl, z0, z1));
+  if (nterms == 1) tt_launch_xg<1>(pl, S, nnz1d);
+  else if (nterms == 2) tt_launch_xg<2>(pl, S, nnz1d);
+  else tt_launch_xg<3>(pl, S, nnz1d);
+  tt_launch_y(pl, S);
+  if (hipGetLastError() != hipSuccess) {
+    tg_set_error("tg_tensor_planes_kron: kernel launch failed");
+    return 1;
   }
-  double *b1 = nullptr;
-  int64_t *d_pb1 = nullptr, *d_pb2 = nullptr;
-  int32_t *d_pl[2] = {nullptr, nullptr};
-  tg_tensor_planes_s *res = new tg_tensor_planes_s();
-  res->z0 = z0;
-  res->z1 = z1;
-  res->pb = pb2;
-  int rc = tg_dmalloc(&b1, pb1[np]);
-  if (!rc) rc = tg_dmalloc(&res->buf, pb2[np]);
-  if (!rc) rc = tg_dmalloc(&res->status, 4);
-  if (!rc) rc = tt_upload(&d_pb1, pb1);
-  if (!rc) rc = tt_upload(&d_pb2, pb2);
-  if (!rc) rc = tt_upload(&d_pl[0], pls[0]);
-  if (!rc) rc = tt_upload(&d_pl[1], pls[1]);
-  if (!rc && hipMemsetAsync(res->status, 0, sizeof(int), g_tg.stream) != hipSuccess) rc = 1;
-  if (!rc) {
-    if (nterms == 1) rc = tt_launch_xg<1>(pl, z0, pls, d_pl, b1, d_pb1, nnz1d);
-    else if (nterms == 2) rc = tt_launch_xg<2>(pl, z0, pls, d_pl, b1, d_pb1, nnz1d);
-    else rc = tt_launch_xg<3>(pl, z0, pls, d_pl, b1, d_pb1, nnz1d);
-    tt_y_multi YM;
-    memset(&YM, 0, sizeof(YM));
-    for (int pc = 1; pc >= 0; pc--) {
-      if (pls[pc].empty()) continue;
-      const int n2 = pc == 0 ? P + 1 : W;
-      tt_y_args &Y = YM.c[YM.n];
-      Y.b1 = b1;
-      Y.pb1 = d_pb1;
-      Y.b2 = res->buf;
-      Y.pb2 = d_pb2;
-      Y.z0 = z0;
-      Y.d1 = D1;
-      Y.ncp0 = D0.ncp;
-      Y.planes = d_pl[pc];
-      Y.n2 = n2;
-      Y.L = std::max(1, 64 / (W * n2));
-      Y.ech = tt_y_ech(D1.nel, P);
-      YM.gx[YM.n] = (unsigned)tg_cdiv(D0.ncp, Y.L);
-      YM.first[YM.n + 1] = YM.first[YM.n] + YM.gx[YM.n] * (unsigned)pls[pc].size();
-      YM.n++;
-    }
-    if (!rc && YM.n > 0 && YM.first[YM.n] > 0) {
-#define TT_Y(PP) \
-  hipLaunchKernelGGL((k_tt_y_multi<PP>), dim3(YM.first[YM.n] * tt_pieces(D1.nel, tt_y_ech(D1.nel, P))), dim3(64), 0, g_tg.stream, YM)
-      TT_DISPATCH_P(P, TT_Y);
-#undef TT_Y
-    }
-    if (hipGetLastError() != hipSuccess) {
-      tg_set_error("tg_tensor_planes_kron: kernel launch failed");
-      rc = 1;
-    }
-  }
-  tg_dfree(b1);
-  tg_dfree(d_pb1);
-  tg_dfree(d_pb2);
-  tg_dfree(d_pl[0]);
-  tg_dfree(d_pl[1]);
-  if (rc) {
-    tg_tensor_planes_destroy(res);
-    return rc;
-  }
-  *out = res;
+  *out = S.release();
   return 0;
 }
 
@@ -704,56 +657,55 @@ extern "C" int tg_tensor_split(tg_tensor_plan_t pl, tg_csr_t a, tg_csr_t *on_pat
     dirs[k].col = pl->h_ecol[k].data();
     dirs[k].val = zeros[k].data();
   }
-  tg_csr_s *conf = nullptr, *rem = nullptr;
-  TG_TRY(tg_kron_sum_csr(3, 1, dirs, 0, n, &conf));
-  int rc = 0;
-  if (conf->pattern_tag != pl->expect_tag) {
-    tg_set_error("tg_tensor_split: the pattern matrix does not carry the plan's certificate");
-    rc = 1;
-  }
-  int64_t *rlen = nullptr;
-  if (!rc) rc = tg_dmalloc(&rlen, n + 1);
-  tt_split_args S;
-  S.rowptr = a->rowptr;
-  S.col = a->col;
-  S.val = a->val;
-  S.nfe0 = D0.nfe;
-  S.nfe1 = D1.nfe;
-  S.nfe2 = D2.nfe;
-  S.crowptr = conf->rowptr;
-  S.cval = conf->val;
-  S.nrows = n;
-  const unsigned grid = (unsigned)std::min<int64_t>(tg_cdiv(n, 4), (int64_t)g_tg.num_cu * 32);
-  if (!rc) {
+  tg_csr_s *conf_new = nullptr, *rem_new = nullptr;
+  TG_TRY(tg_kron_sum_csr(3, 1, dirs, 0, n, &conf_new));
+  tt_own<tg_csr_s> conf(conf_new), rem;
+  tg_dbuf<int64_t> rlen;
+  // the passes; whatever they return, the stream is waited for before anything is released
+  auto passes = [&]() -> int {
+    if (conf->pattern_tag != pl->expect_tag) {
+      tg_set_error("tg_tensor_split: the pattern matrix does not carry the plan's certificate");
+      return 1;
+    }
+    TG_TRY(rlen.alloc(n + 1));
+    tt_split_args S;
+    S.rowptr = a->rowptr;
+    S.col = a->col;
+    S.val = a->val;
+    S.nfe0 = D0.nfe;
+    S.nfe1 = D1.nfe;
+    S.nfe2 = D2.nfe;
+    S.crowptr = conf->rowptr;
+    S.cval = conf->val;
+    S.nrows = n;
+    const unsigned grid = (unsigned)std::min<int64_t>(tg_cdiv(n, 4), (int64_t)g_tg.num_cu * 32);
     // (the values written by the Kronecker kernel are 0.0 * ... = 0.0: every slot A does not fill stays zero)
-#define TT_S0(PP) hipLaunchKernelGGL((k_tt_split<PP, false>), dim3(grid), dim3(256), 0, g_tg.stream, S, rlen, (int32_t *)nullptr, (double *)nullptr)
+#define TT_S0(PP) hipLaunchKernelGGL((k_tt_split<PP, false>), dim3(grid), dim3(256), 0, g_tg.stream, S, rlen.p, (int32_t *)nullptr, (double *)nullptr)
     TT_DISPATCH_P(P, TT_S0);
 #undef TT_S0
-    if (hipGetLastError() != hipSuccess) rc = 1;
-  }
-  int64_t total = 0;
-  if (!rc) rc = tg_exclusive_scan_i64(rlen, n, &total);
-  if (!rc) rc = tg_csr_alloc(n, n, total, &rem);
-  if (!rc) {
+    if (hipGetLastError() != hipSuccess) return 1;
+    int64_t total = 0;
+    TG_TRY(tg_exclusive_scan_i64(rlen, n, &total));
+    TG_TRY(tg_csr_alloc(n, n, total, &rem_new));
+    rem.reset(rem_new);
     if (hipMemcpyAsync(rem->rowptr, rlen, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream) != hipSuccess)
-      rc = 1;
-    if (!rc && total > 0) {
+      return 1;
+    if (total > 0) {
 #define TT_S1(PP) hipLaunchKernelGGL((k_tt_split<PP, true>), dim3(grid), dim3(256), 0, g_tg.stream, S, rem->rowptr, rem->col, rem->val)
       TT_DISPATCH_P(P, TT_S1);
 #undef TT_S1
-      if (hipGetLastError() != hipSuccess) rc = 1;
+      if (hipGetLastError() != hipSuccess) return 1;
     }
-  }
+    return 0;
+  };
+  int rc = passes();
   if (hipStreamSynchronize(g_tg.stream) != hipSuccess) rc = 1;
-  tg_dfree(rlen);
   if (rc) {
-    tg_csr_destroy(conf);
-    if (rem) tg_csr_destroy(rem);
     tg_set_error("tg_tensor_split failed");
     return 1;
   }
-  *on_pattern = conf;
-  *remainder = rem;
+  *on_pattern = conf.release();
+  *remainder = rem.release();
   return 0;
 }
 
@@ -787,6 +739,7 @@ extern "C" int tg_tensor_zstage(tg_tensor_plan_t pl, int npieces, const tg_tenso
   const int64_t ncols = (int64_t)pl->ncc[0] * pl->ncc[1] * pl->ncc[2];
   // destination
   tg_csr_s *m = nullptr;
+  tt_own<tg_csr_s> m_new;           // (a matrix of our own is dropped on failure; the builder's stays as it was)
   int64_t row_at = 0, nnz_at = 0;
   if (dest) {
     TG_REQUIRE(dest->m && dest->m->ncols == ncols, "tg_tensor_zstage: builder has other dimensions");
@@ -796,88 +749,78 @@ extern "C" int tg_tensor_zstage(tg_tensor_plan_t pl, int npieces, const tg_tenso
     nnz_at = dest->nnz_done;
   } else {
     TG_TRY(tg_csr_alloc(nrows, ncols, nnz, &m));
+    m_new.reset(m);
   }
-  uint8_t *mask = nullptr;
-  const double **d_ptr = nullptr;
-  int rc = 0;
-  if (zero_dofs && nzero > 0) rc = tg_build_dof_mask(zero_dofs, nzero, ncols, &mask);
-  if (!rc) rc = tt_upload(&d_ptr, ptr);
-  if (!rc) {
-    tt_rowptr_args R;
-    R.kps0 = D0.kps;
-    R.kps1 = D1.kps;
-    R.kps2 = D2.kps;
-    R.ncp0 = ncr0;
-    R.ncp1 = ncr1;
-    R.ka = ka;
-    R.kb = kb;
-    R.base = nnz_at;
-    R.rowptr_out = m->rowptr + row_at;
-    hipLaunchKernelGGL(k_tt_rowptr, dim3((unsigned)tg_cdiv(nrows, 256)), dim3(256), 0, g_tg.stream, R, nrows);
-    const int64_t end = nnz_at + nnz;
-    if (hipMemcpyAsync(m->rowptr + row_at + nrows, &end, sizeof(int64_t), hipMemcpyHostToDevice, g_tg.stream) != hipSuccess)
-      rc = 1;
-    tt_z_args Z;
-    Z.planes = d_ptr;
-    Z.plane_lo = plo;
-    Z.d2 = D2;
-    Z.ncp0 = D0.ncp;
-    Z.ncp1 = D1.ncp;
-    Z.kps0 = D0.kps;
-    Z.kps1 = D1.kps;
-    Z.ka = ka;
-    Z.kb = kb;
-    Z.ncr0 = ncr0;
-    Z.ncr1 = ncr1;
-    Z.ncc0 = pl->ncc[0];
-    Z.ncc1 = pl->ncc[1];
-    Z.pr0 = pl->pr[0];
-    Z.pr1 = pl->pr[1];
-    Z.pr2 = pl->pr[2];
-    Z.L = std::max(1, 64 / (W * W));
-    // the diagonal is recorded while the rows are written (only while every row so far came from here)
-    if (row_at == 0 && !m->diag_cache && !pl->pair) {
-      if (tg_dmalloc(&m->diag_cache, m->nrows)) m->diag_cache = nullptr;
-      m->diag_rows = 0;
-    }
-    const bool keep_diag = m->diag_cache && m->diag_rows == row_at;
-    Z.kdiag = keep_diag ? m->diag_cache + row_at : nullptr;
-    Z.kcol = m->col + nnz_at;
-    Z.kval = m->val + nnz_at;
-    Z.mask = mask;
-    Z.diag = diag;
-    const unsigned grid = (unsigned)tg_cdiv(pd_pad, Z.L);
+  tg_dbuf<uint8_t> mask;
+  tg_dbuf<const double *> d_ptr;
+  if (zero_dofs && nzero > 0) TG_TRY(tg_build_dof_mask(zero_dofs, nzero, ncols, &mask.p));
+  TG_TRY(tt_upload(&d_ptr.p, ptr));
+  tt_rowptr_args R;
+  R.kps0 = D0.kps;
+  R.kps1 = D1.kps;
+  R.kps2 = D2.kps;
+  R.ncp0 = ncr0;
+  R.ncp1 = ncr1;
+  R.ka = ka;
+  R.kb = kb;
+  R.base = nnz_at;
+  R.rowptr_out = m->rowptr + row_at;
+  hipLaunchKernelGGL(k_tt_rowptr, dim3((unsigned)tg_cdiv(nrows, 256)), dim3(256), 0, g_tg.stream, R, nrows);
+  const int64_t end = nnz_at + nnz;
+  TG_TRY(tg_h2d_staged(m->rowptr + row_at + nrows, &end, sizeof(int64_t)));
+  tt_z_args Z;
+  Z.planes = d_ptr;
+  Z.plane_lo = plo;
+  Z.d2 = D2;
+  Z.ncp0 = D0.ncp;
+  Z.ncp1 = D1.ncp;
+  Z.kps0 = D0.kps;
+  Z.kps1 = D1.kps;
+  Z.ka = ka;
+  Z.kb = kb;
+  Z.ncr0 = ncr0;
+  Z.ncr1 = ncr1;
+  Z.ncc0 = pl->ncc[0];
+  Z.ncc1 = pl->ncc[1];
+  Z.pr0 = pl->pr[0];
+  Z.pr1 = pl->pr[1];
+  Z.pr2 = pl->pr[2];
+  Z.L = std::max(1, 64 / (W * W));
+  // the diagonal is recorded while the rows are written (only while every row so far came from here)
+  if (row_at == 0 && !m->diag_cache && !pl->pair) {
+    if (tg_dmalloc(&m->diag_cache, m->nrows)) m->diag_cache = nullptr;
+    m->diag_rows = 0;
+  }
+  const bool keep_diag = m->diag_cache && m->diag_rows == row_at;
+  Z.kdiag = keep_diag ? m->diag_cache + row_at : nullptr;
+  Z.kcol = m->col + nnz_at;
+  Z.kval = m->val + nnz_at;
+  Z.mask = mask;
+  Z.diag = diag;
+  const unsigned grid = (unsigned)tg_cdiv(pd_pad, Z.L);
 #define TT_Z(PP) hipLaunchKernelGGL((k_tt_z<PP>), dim3(grid), dim3(64), 0, g_tg.stream, Z)
-    TT_DISPATCH_P(P, TT_Z);
+  TT_DISPATCH_P(P, TT_Z);
 #undef TT_Z
-    if (hipGetLastError() != hipSuccess) {
-      tg_set_error("tg_tensor_zstage: kernel launch failed");
-      rc = 1;
-    }
-    // the flag of the x / y passes that fed this stage (read here when they ran on a certified matrix without waiting)
-    std::vector<int> piece_bad((size_t)npieces, 0);
-    for (int q = 0; q < npieces && !rc; q++)
-      if (pieces[q]->status &&
-          hipMemcpyAsync(&piece_bad[(size_t)q], pieces[q]->status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess)
-        rc = 1;
-    if (!rc && hipStreamSynchronize(g_tg.stream) != hipSuccess) {   // (`end`, the mask and the pointer table are released below)
-      tg_set_error("tg_tensor_zstage: %s", hipGetErrorString(hipGetLastError()));
-      rc = 1;
-    }
-    int passes_bad = 0;
-    for (int q = 0; q < npieces; q++) passes_bad |= piece_bad[(size_t)q];
-    if (!rc && passes_bad) {
+  if (hipGetLastError() != hipSuccess) {
+    tg_set_error("tg_tensor_zstage: kernel launch failed");
+    return 1;
+  }
+  // the flag of the x / y passes that fed this stage (read here when they ran on a certified matrix without waiting)
+  std::vector<int> piece_bad((size_t)npieces, 0);
+  for (int q = 0; q < npieces; q++)
+    if (pieces[q]->status &&
+        hipMemcpyAsync(&piece_bad[(size_t)q], pieces[q]->status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess)
+      return 1;
+  if (hipStreamSynchronize(g_tg.stream) != hipSuccess) {
+    tg_set_error("tg_tensor_zstage: %s", hipGetErrorString(hipGetLastError()));
+    return 1;
+  }
+  for (int q = 0; q < npieces; q++)
+    if (piece_bad[(size_t)q]) {
       tg_set_error("tg_tensor_zstage: the planes of this stage come from a matrix whose rows do not have the lengths of "
                    "the pattern it was certified for");
-      rc = 1;
+      return 1;
     }
-  }
-  tg_dfree(mask);
-  tg_dfree(d_ptr);
-  if (rc) {
-    if (!dest) tg_csr_destroy(m);
-    return rc;
-  }
   if (m->diag_cache && m->diag_rows == row_at) m->diag_rows = row_at + nrows;
   g_tg.prof_n[TG_PROF_PTAP_TENSOR_WALKS] += 1;
   if (dest) {
@@ -885,7 +828,7 @@ extern "C" int tg_tensor_zstage(tg_tensor_plan_t pl, int npieces, const tg_tenso
     dest->nnz_done += nnz;
   } else {
     m->nnz = nnz;
-    *out = m;
+    *out = m_new.release();
   }
   return 0;
 }
@@ -935,85 +878,24 @@ static int tt_plan_create2(int nfields, const tg_tensor_pair_dir_t *dirs, bool p
   TG_REQUIRE(P >= 1 && P <= 4 && dirs[1].p == P, "tg_tensor2_plan_create: equal degrees 1..4 in both directions");
   TG_REQUIRE((2 * P + 1) * nfields <= 64, "tg_tensor2_plan_create: (2p+1) * nfields lanes must fit a wave");
   TG_REQUIRE(!pair || nfields == 1, "tg_tensor2_plan_create_pair: one field on either side");
-  tg_tensor_plan_s *pl = new tg_tensor_plan_s();
+  tt_own<tg_tensor_plan_s> pl(new tg_tensor_plan_s());
   pl->P = P;
   pl->d = 2;
   pl->nF = nfields;
   pl->pair = pair;
-  int rc = 0;
-  for (int k = 0; k < 2 && !rc; k++) {
-    const int nel = dirs[k].nel, nfe = P * nel + 1, ncp = nel + P;
-    const int pr = pair ? dirs[k].pr : P, pc = pair ? dirs[k].pc : P;
-    if (nel < 1 || !dirs[k].wlc || (pair && !dirs[k].wlr) || pr < 1 || pr > P || pc < 1 || pc > P) {
-      tg_set_error("tg_tensor2_plan_create: bad direction %d (spline degrees 1..%d on both sides)", k, P);
-      rc = 2;
-      break;
-    }
-    const int ncr = nel + pr, ncc = nel + pc;
-    pl->pr[k] = pr, pl->pc[k] = pc, pl->ncr[k] = ncr, pl->ncc[k] = ncc;
-    std::vector<double> w(dirs[k].wlc, dirs[k].wlc + (size_t)nel * (P + 1) * (P + 1));
-    pl->h_rps[k].assign(nfe + 1, 0);
-    for (int a = 0; a < nfe; a++) pl->h_rps[k][a + 1] = pl->h_rps[k][a] + tt_rn_host(P, a, nfe);
-    // 1-D pattern of the product: row function i couples to the column functions [i - pr, i + pc], clipped
-    pl->h_kps[k].assign(ncr + 1, 0);
-    for (int i = 0; i < ncr; i++)
-      pl->h_kps[k][i + 1] = pl->h_kps[k][i] + (std::min(ncc - 1, i + pc) - std::max(0, i - pr) + 1);
-    rc = tt_upload(&pl->wl[k], w);
-    if (!rc && pair) {
-      std::vector<double> wr(dirs[k].wlr, dirs[k].wlr + (size_t)nel * (P + 1) * (P + 1));
-      rc = tt_upload(&pl->wlr[k], wr);
-    }
-    if (!rc) rc = tt_upload(&pl->rps[k], pl->h_rps[k]);
-    if (!rc) rc = tt_upload(&pl->kps[k], pl->h_kps[k]);
-    pl->dir[k].nel = nel;
-    pl->dir[k].nfe = nfe;
-    pl->dir[k].ncp = ncp;                 // (padded: the layout of the intermediate)
-    pl->dir[k].wl = pl->wl[k];
-    pl->dir[k].wlr = pair ? pl->wlr[k] : nullptr;
-    pl->dir[k].rps = pl->rps[k];
-    pl->dir[k].kps = pl->kps[k];
-  }
-  if (!rc) {
-    // direction 2 = the field index: row f couples to all nF fields
-    pl->h_rps[2].assign(nfields + 1, 0);
-    for (int f = 0; f <= nfields; f++) pl->h_rps[2][f] = f * nfields;
-    rc = tt_upload(&pl->rps[2], pl->h_rps[2]);
-    pl->dir[2].nel = 0;
-    pl->dir[2].nfe = pl->dir[2].ncp = nfields;
-    pl->dir[2].rps = pl->rps[2];
-  }
-  if (!rc && nfields == 1) {
-    // certificate of a scalar matrix written by tg_kron_sum_csr on this grid (two directions)
-    std::vector<int32_t> ecol[2];
-    const int32_t *rps[2], *cls[2];
-    int64_t nr[2], nc[2];
-    for (int k = 0; k < 2; k++) {
-      const int nfe = pl->dir[k].nfe;
-      for (int a = 0; a < nfe; a++) {
-        const int lo = tt_rlo_host(P, a, nfe), n = tt_rn_host(P, a, nfe);
-        for (int j = 0; j < n; j++) ecol[k].push_back(lo + j);
-      }
-      rps[k] = pl->h_rps[k].data();
-      cls[k] = ecol[k].data();
-      nr[k] = nc[k] = nfe;
-    }
-    pl->expect_tag = tg_pattern_hash(2, nr, nc, rps, cls, 0);
-  }
-  if (!rc) {
-    std::vector<int32_t> ls, lv;
-    const int nfe1 = pl->dir[1].nfe;
-    for (int a = 0; a < nfe1; a++) (tt_rn_host(P, a, nfe1) == P + 1 ? ls : lv).push_back(a);
-    pl->nlines1[0] = (int)ls.size();
-    pl->nlines1[1] = (int)lv.size();
-    rc = tt_upload(&pl->lines1[0], ls);
-    if (!rc) rc = tt_upload(&pl->lines1[1], lv);
-    if (!rc) rc = tg_dmalloc(&pl->status, 4);
-  }
-  if (rc) {
-    tg_tensor_plan_destroy(pl);
-    return rc;
-  }
-  *out = pl;
+  TG_TRY(tt_plan_dirs(pl.get(), 2, dirs, "tg_tensor2_plan_create"));
+  // direction 2 = the field index: row f couples to all nF fields
+  pl->h_rps[2].assign(nfields + 1, 0);
+  for (int f = 0; f <= nfields; f++) pl->h_rps[2][f] = f * nfields;
+  TG_TRY(tt_upload(&pl->rps[2], pl->h_rps[2]));
+  pl->dir[2].nel = 0;
+  pl->dir[2].nfe = pl->dir[2].ncp = nfields;
+  pl->dir[2].rps = pl->rps[2];
+  // certificate of a scalar matrix written by tg_kron_sum_csr on this grid (two directions)
+  if (nfields == 1) tt_plan_pattern(pl.get(), 2);
+  TG_TRY(tt_plan_lines1(pl.get()));
+  TG_TRY(tg_dmalloc(&pl->status, 4));
+  *out = pl.release();
   return 0;
 }
 
@@ -1021,13 +903,7 @@ extern "C" int tg_tensor2_plan_create(int nfields, const tg_tensor_dir_t *dirs, 
   TG_REQUIRE_INIT();
   TG_REQUIRE(dirs && out && nfields >= 1, "bad arguments to tg_tensor2_plan_create");
   tg_tensor_pair_dir_t pd[2];
-  for (int k = 0; k < 2; k++) {
-    pd[k].p = dirs[k].p;
-    pd[k].nel = dirs[k].nel;
-    pd[k].pr = pd[k].pc = dirs[k].p;
-    pd[k].wlr = nullptr;
-    pd[k].wlc = dirs[k].wl;
-  }
+  tt_as_pair_dirs(2, dirs, pd);
   return tt_plan_create2(nfields, pd, false, out);
 }
 
@@ -1049,7 +925,7 @@ extern "C" int tg_tensor2_ptap(tg_tensor_plan_t pl, tg_csr_t a, const int32_t *z
   TG_REQUIRE_CANONICAL(a);
   const int P = pl->P, W = 2 * P + 1, nF = pl->nF;
   const tt_dir_t &D0 = pl->dir[0], &D1 = pl->dir[1];
-  const int64_t nfe = (int64_t)D0.nfe * D1.nfe, ncp = (int64_t)D0.ncp * D1.ncp;
+  const int64_t nfe = (int64_t)D0.nfe * D1.nfe;
   if (a->nrows != nF * nfe || a->ncols != nF * nfe) return 100;        // not a matrix on this mixed space
   const int64_t t0 = pl->h_rps[0][D0.nfe], t1 = pl->h_rps[1][D1.nfe];
   if (a->nnz != (int64_t)nF * nF * t0 * t1) return 100;                 // (cheap: the pattern has exactly this many entries)
@@ -1057,7 +933,6 @@ extern "C" int tg_tensor2_ptap(tg_tensor_plan_t pl, tg_csr_t a, const int32_t *z
   const int ncc0 = pl->pair ? pl->ncc[0] : D0.ncp, ncc1 = pl->pair ? pl->ncc[1] : D1.ncp;
   const int64_t w0tot = pl->h_kps[0][ncr0], w1tot = pl->h_kps[1][ncr1];
   const int64_t knnz = (int64_t)nF * nF * w0tot * w1tot, krows = (int64_t)nF * ncr0 * ncr1, kcols = (int64_t)nF * ncc0 * ncc1;
-  (void)ncp;
   TG_REQUIRE(nF * nfe < 0x7fffffffll && krows < 0x7fffffffll && kcols < 0x7fffffffll, "tg_tensor2_ptap: index range");
   TG_REQUIRE(!pl->pair || !(zero_dofs && nzero > 0), "tg_tensor2_ptap: boundary conditions belong to the assembled matrix, not to a block");
   // elements per piece of the walks: enough pieces to give the chip a few thousand waves, not so short that the P
@@ -1072,14 +947,15 @@ extern "C" int tg_tensor2_ptap(tg_tensor_plan_t pl, tg_csr_t a, const int32_t *z
     return ech >= nel ? 0 : ech;
   };
   const int64_t plane_b1 = (int64_t)W * nF * D0.ncp * t1;
-  double *b1 = nullptr;
+  tg_dbuf<double> b1;
+  tg_dbuf<uint8_t> mask;
+  tg_dbuf<int64_t> d_pb1;
+  tg_dbuf<int32_t> d_planes;
   tg_csr_s *m = nullptr;
-  uint8_t *mask = nullptr;
-  int64_t *d_pb1 = nullptr;
-  int32_t *d_planes = nullptr;
-  int rc = tg_dmalloc(&b1, plane_b1 * nF);
-  if (!rc) rc = tg_csr_alloc(krows, kcols, knnz, &m);
-  if (!rc && zero_dofs && nzero > 0) rc = tg_build_dof_mask(zero_dofs, nzero, krows, &mask);
+  TG_TRY(b1.alloc(plane_b1 * nF));
+  TG_TRY(tg_csr_alloc(krows, kcols, knnz, &m));
+  tt_own<tg_csr_s> m_own(m);               // (dropped unless it is handed out at the end)
+  if (zero_dofs && nzero > 0) TG_TRY(tg_build_dof_mask(zero_dofs, nzero, krows, &mask.p));
   {
     std::vector<int64_t> pb1(nF + 1, 0);
     std::vector<int32_t> planes(nF, 0);
@@ -1087,126 +963,116 @@ extern "C" int tg_tensor2_ptap(tg_tensor_plan_t pl, tg_csr_t a, const int32_t *z
       pb1[f + 1] = pb1[f] + plane_b1;
       planes[f] = f;
     }
-    if (!rc) rc = tt_upload(&d_pb1, pb1);
-    if (!rc) rc = tt_upload(&d_planes, planes);
+    TG_TRY(tt_upload(&d_pb1.p, pb1));
+    TG_TRY(tt_upload(&d_planes.p, planes));
   }
-  if (!rc && hipMemsetAsync(pl->status, 0, sizeof(int), g_tg.stream) != hipSuccess) rc = 1;
-  int bad = 0;
-  if (!rc) {
-    tt_check_args Cq;
-    Cq.rowptr = a->rowptr;
-    Cq.nfe0 = D0.nfe;
-    Cq.nfe1 = D1.nfe;
-    Cq.nfe2 = nF;
-    Cq.aplane0 = 0;
-    Cq.z0 = 0;
-    Cq.dense2 = 1;
-    const int64_t nr = nF * nfe;
+  if (hipMemsetAsync(pl->status, 0, sizeof(int), g_tg.stream) != hipSuccess) return 1;
+  tt_check_args Cq;
+  Cq.rowptr = a->rowptr;
+  Cq.nfe0 = D0.nfe;
+  Cq.nfe1 = D1.nfe;
+  Cq.nfe2 = nF;
+  Cq.aplane0 = 0;
+  Cq.z0 = 0;
+  Cq.dense2 = 1;
+  const int64_t nr = nF * nfe;
 #define TT_C(PP) hipLaunchKernelGGL((k_tt_check_rows<PP>), dim3((unsigned)tg_cdiv(nr, 256)), dim3(256), 0, g_tg.stream, Cq, nr, pl->status)
-    TT_DISPATCH_P4(P, TT_C);
+  TT_DISPATCH_P4(P, TT_C);
 #undef TT_C
-    // x pass: both line classes in one launch
-    tt_x2_multi XM;
-    memset(&XM, 0, sizeof(XM));
-    XM.nF = nF;
-    int64_t waves = 0;
-    for (int lc = 1; lc >= 0; lc--)
-      if (pl->nlines1[lc]) waves += tg_cdiv(pl->nlines1[lc], std::max(1, 64 / ((lc == 0 ? P + 1 : W) * nF))) * nF;
-    const int ech0 = pick_ech(D0.nel, waves, "TIGAR_TT2_ECH_X", 4 * P);
-    const unsigned np0 = ech0 ? (unsigned)tg_cdiv(D0.nel, ech0) : 1u;
-    for (int lc = 1; lc >= 0; lc--) {
-      if (!pl->nlines1[lc]) continue;
-      const int n1 = lc == 0 ? P + 1 : W;
-      tt_x_args &X = XM.c[XM.n];
-      X.rowptr = a->rowptr;
-      X.col = a->col;
-      X.val = a->val;
-      X.rps2 = pl->rps[2];
-      X.aplane0 = 0;
-      X.d0 = D0;
-      X.nfe1 = D1.nfe;
-      X.nfe2 = nF;
-      X.rps1 = D1.rps;
-      X.lines = pl->lines1[lc];
-      X.nlines = pl->nlines1[lc];
-      X.n1 = n1;
-      X.n2 = nF;
-      X.L = std::max(1, 64 / (n1 * nF));
-      X.planes = d_planes;
-      X.b1 = b1;
-      X.pb1 = d_pb1;
-      X.z0 = 0;
-      X.status = pl->status;
-      X.dense2 = 1;
-      X.ech = ech0;
-      XM.gx[XM.n] = (unsigned)tg_cdiv(X.nlines, X.L);
-      XM.first[XM.n + 1] = XM.first[XM.n] + XM.gx[XM.n] * (unsigned)nF * np0;
-      XM.n++;
-    }
-    const bool certified = a->pattern_tag != 0 && a->pattern_tag == pl->expect_tag && a->pattern_row0 == 0 &&
-                           !(getenv("TIGAR_PTAP_VERIFY") && atoi(getenv("TIGAR_PTAP_VERIFY")));
-    if (XM.n > 0 && XM.first[XM.n] > 0) {
+  // x pass: both line classes in one launch
+  tt_x2_multi XM;
+  memset(&XM, 0, sizeof(XM));
+  XM.nF = nF;
+  int64_t waves = 0;
+  for (int lc = 1; lc >= 0; lc--)
+    if (pl->nlines1[lc]) waves += tg_cdiv(pl->nlines1[lc], std::max(1, 64 / ((lc == 0 ? P + 1 : W) * nF))) * nF;
+  const int ech0 = pick_ech(D0.nel, waves, "TIGAR_TT2_ECH_X", 4 * P);
+  const unsigned np0 = tt_pieces(D0.nel, ech0);
+  for (int lc = 1; lc >= 0; lc--) {
+    if (!pl->nlines1[lc]) continue;
+    const int n1 = lc == 0 ? P + 1 : W;
+    tt_x_args &X = XM.c[XM.n];
+    X.rowptr = a->rowptr;
+    X.col = a->col;
+    X.val = a->val;
+    X.rps2 = pl->rps[2];
+    X.aplane0 = 0;
+    X.d0 = D0;
+    X.nfe1 = D1.nfe;
+    X.nfe2 = nF;
+    X.rps1 = D1.rps;
+    X.lines = pl->lines1[lc];
+    X.nlines = pl->nlines1[lc];
+    X.n1 = n1;
+    X.n2 = nF;
+    X.L = std::max(1, 64 / (n1 * nF));
+    X.planes = d_planes;
+    X.b1 = b1;
+    X.pb1 = d_pb1;
+    X.z0 = 0;
+    X.status = pl->status;
+    X.dense2 = 1;
+    X.ech = ech0;
+    XM.gx[XM.n] = (unsigned)tg_cdiv(X.nlines, X.L);
+    XM.first[XM.n + 1] = XM.first[XM.n] + XM.gx[XM.n] * (unsigned)nF * np0;
+    XM.n++;
+  }
+  const bool certified = tt_certified(pl, a, 0);
+  if (XM.n > 0 && XM.first[XM.n] > 0) {
 #define TT_X(PP) hipLaunchKernelGGL((k_tt_x2<PP, true>), dim3(XM.first[XM.n]), dim3(64), 0, g_tg.stream, XM)
 #define TT_XC(PP) hipLaunchKernelGGL((k_tt_x2<PP, false>), dim3(XM.first[XM.n]), dim3(64), 0, g_tg.stream, XM)
-      if (certified) TT_DISPATCH_P4(P, TT_XC);
-      else TT_DISPATCH_P4(P, TT_X);
+    if (certified) TT_DISPATCH_P4(P, TT_XC);
+    else TT_DISPATCH_P4(P, TT_X);
 #undef TT_X
 #undef TT_XC
-      g_tg.prof_n[TG_PROF_PTAP_CERTIFIED] += certified ? 1 : 0;
-    }
-    // final pass along direction 1: rows of K
-    tt_rowptr2_args R;
-    R.kps0 = D0.kps;
-    R.kps1 = D1.kps;
-    R.ncp0 = ncr0;
-    R.ncp1 = ncr1;
-    R.nF = nF;
-    R.rowptr_out = m->rowptr;
-    hipLaunchKernelGGL(k_tt_rowptr2, dim3((unsigned)tg_cdiv(krows, 256)), dim3(256), 0, g_tg.stream, R, krows);
-    if (hipMemcpyAsync(m->rowptr + krows, &knnz, sizeof(int64_t), hipMemcpyHostToDevice, g_tg.stream) != hipSuccess) rc = 1;
-    tt_y2_args Y;
-    Y.b1 = b1;
-    Y.plane_b1 = plane_b1;
-    Y.d1 = D1;
-    Y.ncp0 = D0.ncp;
-    Y.nF = nF;
-    Y.kps0 = D0.kps;
-    Y.ncr0 = Y.ncr1 = Y.ncc0 = Y.ncc1 = Y.pr0 = Y.pr1 = 0;
-    if (pl->pair) Y.ncr0 = ncr0, Y.ncr1 = ncr1, Y.ncc0 = ncc0, Y.ncc1 = ncc1, Y.pr0 = pl->pr[0], Y.pr1 = pl->pr[1];
-    Y.L = std::max(1, 64 / (W * nF));
-    const unsigned gx = (unsigned)tg_cdiv(D0.ncp, Y.L);
-    Y.ech = pick_ech(D1.nel, (int64_t)gx * nF, "TIGAR_TT2_ECH_Y", 2 * P);
-    const unsigned np1 = Y.ech ? (unsigned)tg_cdiv(D1.nel, Y.ech) : 1u;
-    if (!pl->pair && !m->diag_cache && tg_dmalloc(&m->diag_cache, krows)) m->diag_cache = nullptr;
-    Y.kdiag = m->diag_cache;
-    Y.kcol = m->col;
-    Y.kval = m->val;
-    Y.mask = mask;
-    Y.diag = diag;
+    g_tg.prof_n[TG_PROF_PTAP_CERTIFIED] += certified ? 1 : 0;
+  }
+  // final pass along direction 1: rows of K
+  tt_rowptr2_args R;
+  R.kps0 = D0.kps;
+  R.kps1 = D1.kps;
+  R.ncp0 = ncr0;
+  R.ncp1 = ncr1;
+  R.nF = nF;
+  R.rowptr_out = m->rowptr;
+  hipLaunchKernelGGL(k_tt_rowptr2, dim3((unsigned)tg_cdiv(krows, 256)), dim3(256), 0, g_tg.stream, R, krows);
+  TG_TRY(tg_h2d_staged(m->rowptr + krows, &knnz, sizeof(int64_t)));
+  tt_y2_args Y;
+  Y.b1 = b1;
+  Y.plane_b1 = plane_b1;
+  Y.d1 = D1;
+  Y.ncp0 = D0.ncp;
+  Y.nF = nF;
+  Y.kps0 = D0.kps;
+  Y.ncr0 = Y.ncr1 = Y.ncc0 = Y.ncc1 = Y.pr0 = Y.pr1 = 0;
+  if (pl->pair) Y.ncr0 = ncr0, Y.ncr1 = ncr1, Y.ncc0 = ncc0, Y.ncc1 = ncc1, Y.pr0 = pl->pr[0], Y.pr1 = pl->pr[1];
+  Y.L = std::max(1, 64 / (W * nF));
+  const unsigned gx = (unsigned)tg_cdiv(D0.ncp, Y.L);
+  Y.ech = pick_ech(D1.nel, (int64_t)gx * nF, "TIGAR_TT2_ECH_Y", 2 * P);
+  const unsigned np1 = tt_pieces(D1.nel, Y.ech);
+  if (!pl->pair && !m->diag_cache && tg_dmalloc(&m->diag_cache, krows)) m->diag_cache = nullptr;
+  Y.kdiag = m->diag_cache;
+  Y.kcol = m->col;
+  Y.kval = m->val;
+  Y.mask = mask;
+  Y.diag = diag;
 #define TT_Y2(PP) hipLaunchKernelGGL((k_tt_y2<PP>), dim3(gx * (unsigned)nF * np1), dim3(64), 0, g_tg.stream, Y, gx)
-    TT_DISPATCH_P4(P, TT_Y2);
+  TT_DISPATCH_P4(P, TT_Y2);
 #undef TT_Y2
-    if (hipGetLastError() != hipSuccess) {
-      tg_set_error("tg_tensor2_ptap: kernel launch failed");
-      rc = 1;
-    }
-    if (!rc && hipMemcpyAsync(&bad, pl->status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess) rc = 1;
-    if (!rc && hipStreamSynchronize(g_tg.stream) != hipSuccess) {
-      tg_set_error("tg_tensor2_ptap: %s", hipGetErrorString(hipGetLastError()));
-      rc = 1;
-    }
+  if (hipGetLastError() != hipSuccess) {
+    tg_set_error("tg_tensor2_ptap: kernel launch failed");
+    return 1;
   }
-  tg_dfree(b1);
-  tg_dfree(mask);
-  tg_dfree(d_pb1);
-  tg_dfree(d_planes);
-  if (rc || bad) {
-    if (m) tg_csr_destroy(m);
-    return rc ? rc : 100;
+  int bad = 0;
+  if (hipMemcpyAsync(&bad, pl->status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess) return 1;
+  if (hipStreamSynchronize(g_tg.stream) != hipSuccess) {
+    tg_set_error("tg_tensor2_ptap: %s", hipGetErrorString(hipGetLastError()));
+    return 1;
   }
+  if (bad) return 100;
   m->nnz = knnz;
   m->diag_rows = m->diag_cache ? krows : 0;
   g_tg.prof_n[TG_PROF_PTAP_TENSOR_WALKS] += 1;
-  *out = m;
+  *out = m_own.release();
   return 0;
 }

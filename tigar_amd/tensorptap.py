@@ -58,6 +58,22 @@ def _cached_plan(kind, p, nels, nfields, keys, build):
     return plan
 
 
+def _element_windows(M1, P):
+    """the nonzero stored entries of M1 (CSR, rows = the nodes of the CG degree-P grid) as the elements see them:
+    (e1, j1, q1, v1) -- every node but the last belongs to element a // P as local node a % P -- and (e2, q2, v2) -- a
+    vertex node (but the first) also to the element before it, as its local node P; q = column - element"""
+    nfe = M1.shape[0]
+    a = np.repeat(np.arange(nfe), np.diff(M1.indptr))
+    c, v = M1.indices.astype(np.int64), M1.data
+    keep = v != 0.0
+    a, c, v = a[keep], c[keep], v[keep]
+    m1 = a < nfe - 1
+    e1, j1 = a[m1] // P, a[m1] % P
+    m2 = ((a % P) == 0) & (a > 0)
+    e2 = a[m2] // P - 1
+    return (e1, j1, c[m1] - e1, v[m1]), (e2, c[m2] - e2, v[m2])
+
+
 def local_weights(M1, p, nel):
     """wl[e, j, q] = M1[p*e + j, e + q] (value at node j of element e of spline function e+q), or None when a
     stored entry of M1 lies outside that window, i.e. the direction does not have the structure of an open
@@ -66,24 +82,12 @@ def local_weights(M1, p, nel):
     nfe, ncp = M1.shape
     if nfe != p * nel + 1 or ncp != nel + p:
         return None
-    a = np.repeat(np.arange(nfe), np.diff(M1.indptr))
-    c, v = M1.indices.astype(np.int64), M1.data
-    keep = v != 0.0
-    a, c, v = a[keep], c[keep], v[keep]
-    wl = np.zeros((nel, p + 1, p + 1))
-    vertex = (a % p) == 0
-    # every node belongs to element a // p as local node a % p (not the last node) ...
-    m1 = a < nfe - 1
-    e1, j1 = a[m1] // p, a[m1] % p
-    q1 = c[m1] - e1
-    # ... and a vertex node (but the first) also to the element before it, as its local node p
-    m2 = vertex & (a > 0)
-    e2 = a[m2] // p - 1
-    q2 = c[m2] - e2
+    (e1, j1, q1, v1), (e2, q2, v2) = _element_windows(M1, p)
     if np.any(q1 < 0) or np.any(q1 > p) or np.any(q2 < 0) or np.any(q2 > p):
         return None
-    wl[e1, j1, q1] = v[m1]
-    wl[e2, p, q2] = v[m2]
+    wl = np.zeros((nel, p + 1, p + 1))
+    wl[e1, j1, q1] = v1
+    wl[e2, p, q2] = v2
     return wl
 
 
@@ -96,21 +100,12 @@ def local_weights_padded(M1, P, nel, ps):
     nfe, ncp = M1.shape
     if ps < 1 or ps > P or nfe != P * nel + 1 or ncp != nel + ps:
         return None
-    a = np.repeat(np.arange(nfe), np.diff(M1.indptr))
-    c, v = M1.indices.astype(np.int64), M1.data
-    keep = v != 0.0
-    a, c, v = a[keep], c[keep], v[keep]
-    wl = np.zeros((nel, P + 1, P + 1))
-    m1 = a < nfe - 1
-    e1, j1 = a[m1] // P, a[m1] % P
-    q1 = c[m1] - e1
-    m2 = ((a % P) == 0) & (a > 0)
-    e2 = a[m2] // P - 1
-    q2 = c[m2] - e2
+    (e1, j1, q1, v1), (e2, q2, v2) = _element_windows(M1, P)
     if np.any(q1 < 0) or np.any(q1 > ps) or np.any(q2 < 0) or np.any(q2 > ps):
         return None
-    wl[e1, j1, q1] = v[m1]
-    wl[e2, P, q2] = v[m2]
+    wl = np.zeros((nel, P + 1, P + 1))
+    wl[e1, j1, q1] = v1
+    wl[e2, P, q2] = v2
     if not (wl[:, :, :ps + 1] != 0.0).any(axis=1).all():
         return None
     # (the closing vertex of an element carries no weight of the element's first function: the walk relies on it)
@@ -214,6 +209,29 @@ def plan_or_unwrapped(cls, kx, nfields=None, unwrap=True, accept=None):
     return plan, (ku if plan is not None else None)
 
 
+def _dir_array(p, nels, wlc, pair=None):
+    """the directions of a plan for the C interface: ``tg_tensor_dir_t`` per direction, or ``tg_tensor_pair_dir_t`` with
+    ``pair`` = (row-side weights, row degrees, column degrees); the weight arrays must outlive the call"""
+    arr = ((tg_tensor_dir_t if pair is None else tg_tensor_pair_dir_t) * len(nels))()
+    for k, nel in enumerate(nels):
+        arr[k].p, arr[k].nel = p, nel
+        if pair is None:
+            arr[k].wl = wlc[k].ctypes.data_as(c_f64p)
+        else:
+            arr[k].pr, arr[k].pc = int(pair[1][k]), int(pair[2][k])
+            arr[k].wlr = pair[0][k].ctypes.data_as(c_f64p)
+            arr[k].wlc = wlc[k].ctypes.data_as(c_f64p)
+    return arr
+
+
+def _zero_dofs_args(zero_dofs):
+    """(pointer, count, array to keep alive) of the zero dofs for the C interface; (None, 0, None) when there are none"""
+    if zero_dofs is None or not len(zero_dofs):
+        return None, 0, None
+    zd = np.ascontiguousarray(zero_dofs, dtype=np.int32)
+    return zd.ctypes.data_as(c_i32p), zd.size, zd
+
+
 class TensorPlanes(object):
     """B2 planes of FE planes [z0, z1) (device, dense blocks); input of the z pass"""
 
@@ -251,23 +269,12 @@ class TensorPtAP(_PlanHandle):
         self._h = handle()
         if pair is None:
             self.pr = self.pc = [self.p] * 3
-            arr = (tg_tensor_dir_t * 3)()
-            for k in range(3):
-                arr[k].p = self.p
-                arr[k].nel = self.nels[k]
-                arr[k].wl = self._keep[k].ctypes.data_as(c_f64p)
-            check(_lib.lib().tg_tensor_plan_create(3, arr, C.byref(self._h)), "tg_tensor_plan_create")
+            check(_lib.lib().tg_tensor_plan_create(3, _dir_array(self.p, self.nels, self._keep), C.byref(self._h)),
+                  "tg_tensor_plan_create")
             return
-        wlr, self.pr, self.pc = pair
-        self.pr, self.pc = [int(v) for v in self.pr], [int(v) for v in self.pc]
-        self._keep_r = [np.ascontiguousarray(w, dtype=np.float64) for w in wlr]
-        arr = (tg_tensor_pair_dir_t * 3)()
-        for k in range(3):
-            arr[k].p = self.p
-            arr[k].nel = self.nels[k]
-            arr[k].pr, arr[k].pc = self.pr[k], self.pc[k]
-            arr[k].wlr = self._keep_r[k].ctypes.data_as(c_f64p)
-            arr[k].wlc = self._keep[k].ctypes.data_as(c_f64p)
+        self._keep_r = [np.ascontiguousarray(w, dtype=np.float64) for w in pair[0]]
+        self.pr, self.pc = [int(v) for v in pair[1]], [int(v) for v in pair[2]]
+        arr = _dir_array(self.p, self.nels, self._keep, (self._keep_r, self.pr, self.pc))
         check(_lib.lib().tg_tensor_plan_create_pair(3, arr, C.byref(self._h)), "tg_tensor_plan_create_pair")
 
     @staticmethod
@@ -376,11 +383,9 @@ class TensorPtAP(_PlanHandle):
     def zstage(self, pieces, ka, kb, zero_dofs=None, diag=1.0, append_to=None):
         """rows of K for the dof planes [ka, kb): a new DeviceCSR, or True when appended to the builder"""
         arr = (handle * len(pieces))(*[pc._h for pc in pieces])
-        zd = np.ascontiguousarray(zero_dofs, dtype=np.int32) if zero_dofs is not None and len(zero_dofs) else None
+        zd, nzero, _keep = _zero_dofs_args(zero_dofs)
         out = handle()
-        check(_lib.lib().tg_tensor_zstage(self._h, len(pieces), arr, int(ka), int(kb),
-                                          zd.ctypes.data_as(c_i32p) if zd is not None else None,
-                                          zd.size if zd is not None else 0, float(diag),
+        check(_lib.lib().tg_tensor_zstage(self._h, len(pieces), arr, int(ka), int(kb), zd, nzero, float(diag),
                                           append_to._h if append_to is not None else None, C.byref(out)),
               "tg_tensor_zstage")
         return True if append_to is not None else _dev.DeviceCSR(out)
@@ -397,23 +402,12 @@ class TensorPtAP2D(_PlanHandle):
         self._keep = [np.ascontiguousarray(w, dtype=np.float64) for w in wls]
         self._h = handle()
         if pair is not None:
-            wlr, pr, pc = pair
-            self._keep_r = [np.ascontiguousarray(w, dtype=np.float64) for w in wlr]
-            arr = (tg_tensor_pair_dir_t * 2)()
-            for k in range(2):
-                arr[k].p = self.p
-                arr[k].nel = self.nels[k]
-                arr[k].pr, arr[k].pc = int(pr[k]), int(pc[k])
-                arr[k].wlr = self._keep_r[k].ctypes.data_as(c_f64p)
-                arr[k].wlc = self._keep[k].ctypes.data_as(c_f64p)
+            self._keep_r = [np.ascontiguousarray(w, dtype=np.float64) for w in pair[0]]
+            arr = _dir_array(self.p, self.nels, self._keep, (self._keep_r, pair[1], pair[2]))
             check(_lib.lib().tg_tensor2_plan_create_pair(arr, C.byref(self._h)), "tg_tensor2_plan_create_pair")
             return
-        arr = (tg_tensor_dir_t * 2)()
-        for k in range(2):
-            arr[k].p = self.p
-            arr[k].nel = self.nels[k]
-            arr[k].wl = self._keep[k].ctypes.data_as(c_f64p)
-        check(_lib.lib().tg_tensor2_plan_create(self.nfields, arr, C.byref(self._h)), "tg_tensor2_plan_create")
+        check(_lib.lib().tg_tensor2_plan_create(self.nfields, _dir_array(self.p, self.nels, self._keep), C.byref(self._h)),
+              "tg_tensor2_plan_create")
 
     @staticmethod
     def for_extraction(kx, nfields=1):
@@ -437,10 +431,9 @@ class TensorPtAP2D(_PlanHandle):
     def ptap(self, A, zero_dofs=None, diag=1.0):
         """K = M^T A M with MatZeroRowsColumns fused, or None when A does not carry the element-coupling pattern in all
         of its nfields^2 blocks (verified on the device)."""
-        zd = np.ascontiguousarray(zero_dofs, dtype=np.int32) if zero_dofs is not None and len(zero_dofs) else None
+        zd, nzero, _keep = _zero_dofs_args(zero_dofs)
         out = handle()
-        rc = _lib.lib().tg_tensor2_ptap(self._h, A._h, zd.ctypes.data_as(c_i32p) if zd is not None else None,
-                                        zd.size if zd is not None else 0, float(diag), C.byref(out))
+        rc = _lib.lib().tg_tensor2_ptap(self._h, A._h, zd, nzero, float(diag), C.byref(out))
         if rc == 100:
             return None
         check(rc, "tg_tensor2_ptap")
