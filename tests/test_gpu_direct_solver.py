@@ -226,7 +226,7 @@ def test_default_solver_reorders_field_major_systems_and_hands_large_ones_to_cho
     assert r.norm() <= 1e-9 * b3.norm()
 
 
-def test_default_solver_tries_the_rcm_band_before_giving_lu_up():
+def test_default_solver_tries_the_rcm_band_before_giving_lu_up(monkeypatch):
     """linearSolver=None on a field-major three-field system whose band as numbered (~2n/3) is far beyond the direct
     solver's budget: the reverse Cuthill-McKee band is evaluated before falling back to Jacobi-GMRES, and the system is
     solved directly like the reference's default LU would; also: a non-zero initial guess set in u reaches the
@@ -261,7 +261,12 @@ def test_default_solver_tries_the_rcm_band_before_giving_lu_up():
     assert nb > 8 * 2 ** 30                                   # as numbered: beyond the budget
     d = tc._default_linear_solver()
     x = dev.DeviceVector(K.shape[0])
+    import scipy.sparse.csgraph as csgraph
+    rcm, orderings = csgraph.reverse_cuthill_mckee, []
+    monkeypatch.setattr(csgraph, "reverse_cuthill_mckee", lambda *a, **kw: orderings.append(1) or rcm(*a, **kw))
     d.solve(K, x, rhs)
+    monkeypatch.undo()
+    assert len(orderings) == 1                               # K is downloaded and ordered once per solve
     assert d.last["solver"] == "lu" and d.last["reordered"] and d.last["band_bytes"] < 4 * 2 ** 30
     r = K.mult(x)
     r.axpy(-1.0, rhs)

@@ -23,6 +23,7 @@ import numpy
 from numpy import array, zeros, arange
 
 from . import device as _dev
+from . import direct_plan as _plan
 from .device import DeviceCSR, DeviceVector
 from .feorder import FEOrder, as_device_csr as _as_device_csr, as_device_vector as _as_device_vector, fe_matrix as _fe_matrix
 
@@ -1321,6 +1322,24 @@ class PETScKrylovSolver(object):
 KrylovSolver = PETScKrylovSolver
 
 
+def _rcm_ordering(A):
+    """(host matrix, reverse Cuthill-McKee permutation of its stored pattern, (kl, ku) of the reordered matrix) of a
+    ``DeviceCSR``: the bandwidth-reducing ordering of the PATTERN on the host (symbolic step; the values stay on the device
+    except for this download)"""
+    import scipy.sparse as _sp
+    from scipy.sparse.csgraph import reverse_cuthill_mckee
+    S = A.to_scipy()
+    # (the STORED pattern: entries zeroed by MatZeroRowsColumns stay in the band storage, so they must stay in
+    #  the graph -- scipy's sum of abs(S) would drop them and leave the boundary dofs isolated)
+    ones = _sp.csr_matrix((numpy.ones(S.nnz, dtype=numpy.int8), S.indices, S.indptr), shape=S.shape)
+    prm = numpy.asarray(reverse_cuthill_mckee((ones + ones.T).tocsr(), symmetric_mode=True), dtype=numpy.int64)
+    inv = numpy.empty_like(prm)
+    inv[prm] = numpy.arange(prm.size)
+    coo = S.tocoo()
+    dist = inv[coo.row] - inv[coo.col]
+    return S, prm, (int(max(0, dist.max())), int(max(0, -dist.min())))
+
+
 class PETScLUSolver(object):
     """Look-alike of dolfin's ``PETScLUSolver`` / ``LUSolver``: direct solve on the GPU by banded LU with partial
     pivoting (``tg_lu_solve``, LAPACK dgbtrf's storage and pivoting).  Plugs into ``ExtractedSpline.linearSolver``.
@@ -1329,37 +1348,28 @@ class PETScLUSolver(object):
     permutation of the pattern first.  Refuses systems whose band storage exceeds ``max_band_bytes``."""
 
     def __init__(self, method="default", comm=None):
-        self.parameters = {"reorder": "auto", "max_band_bytes": 16 * 2 ** 30, "report": False,
+        # ("symmetric", "reuse_factorization": dolfin users set them; accepted and ignored)
+        self.parameters = {"reorder": "auto", "max_band_bytes": _plan.LU_SOLVER_MAX_BAND_BYTES, "report": False,
                            "symmetric": False, "reuse_factorization": False}
         self.last = None
 
     def band_cost(self, A):
         """(bytes of band storage, multiply-adds) of factorising ``A`` as it is numbered"""
-        kl, ku, nb = _dev.lu_band_info(A)
-        return nb, 2.0 * A.shape[0] * kl * (kl + ku)
+        kl, ku, _ = _dev.lu_band_info(A)
+        return _plan.lu_band_bytes(A.shape[0], kl, ku), _plan.lu_madds(A.shape[0], kl, ku)
 
-    def solve(self, A, x, b):
+    def solve(self, A, x, b, _ordering=None):
+        """``_ordering``: ``_rcm_ordering(A)`` where the caller has it already"""
         A, x, b = _as_device_csr(A), _as_device_vector(x), _as_device_vector(b)
         n = A.shape[0]
         kl, ku, nb = _dev.lu_band_info(A)
         perm = None
         mode = self.parameters["reorder"]
-        if mode is True or (mode == "auto" and nb > 2 ** 28 and (kl + ku) > n // 8):
-            # bandwidth-reducing ordering of the PATTERN on the host (symbolic step; values stay on the device
-            # except for this one re-upload of the permuted matrix)
-            import scipy.sparse as _sp
-            from scipy.sparse.csgraph import reverse_cuthill_mckee
-            S = A.to_scipy()
-            # (the STORED pattern: entries zeroed by MatZeroRowsColumns stay in the band storage, so they must stay in
-            #  the graph -- scipy's sum of abs(S) would drop them and leave the boundary dofs isolated)
-            ones = _sp.csr_matrix((numpy.ones(S.nnz, dtype=numpy.int8), S.indices, S.indptr), shape=S.shape)
-            pat = (ones + ones.T).tocsr()
-            prm = numpy.asarray(reverse_cuthill_mckee(pat, symmetric_mode=True), dtype=numpy.int64)
-            Sp = S[prm][:, prm].tocsr()
-            Ap = DeviceCSR.from_scipy(Sp)
-            kl2, ku2, nb2 = _dev.lu_band_info(Ap)
-            if nb2 < nb:
-                A, perm, kl, ku, nb = Ap, prm, kl2, ku2, nb2
+        if mode is True or (mode == "auto" and _plan.auto_reorders(n, kl, ku)):
+            S, prm, (kl2, ku2) = _ordering or _rcm_ordering(A)
+            nb2 = _plan.lu_band_bytes(n, kl2, ku2)
+            if nb2 < nb:       # (one re-upload, of the permuted matrix)
+                A, perm, kl, ku, nb = DeviceCSR.from_scipy(S[prm][:, prm].tocsr()), prm, kl2, ku2, nb2
         if nb > self.parameters["max_band_bytes"]:
             raise MemoryError("direct solve: the band storage of this %d x %d system (half-bandwidths %d / %d) needs %.1f GB; "
                               "use a Krylov solver (PETScKrylovSolver) for systems of this size" % (n, n, kl, ku, nb / 2 ** 30))
@@ -1388,11 +1398,15 @@ LUSolver = PETScLUSolver
 
 class _DefaultSolver(object):
     """What runs when ``linearSolver`` is None.  The reference calls dolfin's ``solve`` there, i.e. a sparse direct LU
-    (tIGAr/common.py:1255-1256 [ext]) -- every demo relies on it.  Here: the banded direct solver above whenever its
-    cost is moderate (band storage <= 8 GB and <= 4e12 multiply-adds: all 2-D patches of the demos, small 3-D ones),
-    otherwise Jacobi-preconditioned GMRES(30) (CG for the normal equations of ``FEtoIGA``) to a relative residual of
-    1e-12, bounded by PETSc's default 10 000 iterations and by the solver's stagnation guard, with an error message
-    that names the deviation when it gives up."""
+    (tIGAr/common.py:1255-1256 [ext]) -- every demo relies on it.  Here: the attempts of ``direct_plan.default_plan``
+    in order.  The banded direct solver above whenever its cost is moderate (band storage <= 8 GiB and <= 4e12
+    multiply-adds: all 2-D patches of the demos, small 3-D ones), as numbered or in the reverse Cuthill-McKee ordering
+    (field-major systems of several fields, kl ~ n (nF-1)/nF: the saddle point and elasticity cases where the reference's
+    direct solver matters); beyond that a symmetric positive definite system -- the common case -- still gets a direct
+    solve, by the banded Cholesky factorisation (a quarter of the LU's multiply-adds, on the matrix cores, a third of its
+    band; it declines what is not SPD and the next choice runs); otherwise Jacobi-preconditioned GMRES(30) (CG for the
+    normal equations of ``FEtoIGA``) to a relative residual of 1e-12, bounded by PETSc's default 10 000 iterations and by
+    the solver's stagnation guard, with an error message that names the deviation when it gives up."""
 
     def __init__(self, method="gmres"):
         self.method = method
@@ -1401,57 +1415,32 @@ class _DefaultSolver(object):
 
     def solve(self, A, x, b):
         A = _as_device_csr(A)
-        if self.comm is None and os.environ.get("TIGAR_DEFAULT_SOLVER", "auto") != "krylov":
-            lu = PETScLUSolver()
-            kl, ku, nb = _dev.lu_band_info(A)
-            flops = 2.0 * A.shape[0] * kl * (kl + ku)
-            fits = nb <= 8 * 2 ** 30 and flops <= 4e12 and A.shape[0] <= 400000
-            # Beyond the LU's limits (3-D patches): a symmetric positive definite system -- the common case -- still gets
-            # a direct solve, by the banded Cholesky factorisation: a quarter of the LU's multiply-adds, on the matrix
-            # cores, a third of its band (csrc/tg_chol.hip; it declines what is not SPD and the next choice runs).
-            chol_fits = kl == ku and 8.0 * A.shape[0] * (kl + 1) <= 96 * 2 ** 30 and float(A.shape[0]) * kl * kl <= 4e13 \
-                and kl <= 16000 and os.environ.get("TIGAR_LU_CHOLESKY", "1") != "0"
-
-            def cholesky():
-                xd, bd = _as_device_vector(x), _as_device_vector(b)
-                if not _dev.chol_solve(A, bd, xd):
-                    return False
-                self.last = {"solver": "lu", "factorisation": "cholesky", "info": 0, "kl": kl, "ku": ku,
-                             "band_bytes": 8 * A.shape[0] * (kl + 1), "reordered": False}
-                return True
-
-            # a band as numbered (kl well below n: one field) goes there at once; a field-major system of several fields
-            # (kl ~ n (nF-1)/nF) has its reordered band evaluated first (a download of K and a host ordering: 0.2-0.45 s for
-            # 15-34 M entries, which the single-field solves paid for nothing)
-            chol_tried = False
-            if not fits and chol_fits and 4 * kl < A.shape[0]:
-                if cholesky():
+        n = A.shape[0]
+        kl = ku = 0
+        if self.comm is None:
+            kl, ku, _ = _dev.lu_band_info(A)
+        ordering = None
+        for attempt in _plan.default_plan(n, A.nnz, kl, ku, self.comm is not None, os.environ.get("TIGAR_DEFAULT_SOLVER"),
+                                          os.environ.get("TIGAR_LU_CHOLESKY")):
+            if attempt == "cholesky":
+                if _dev.chol_solve(A, _as_device_vector(b), _as_device_vector(x)):
+                    self.last = {"solver": "lu", "factorisation": "cholesky", "info": 0, "kl": kl, "ku": ku,
+                                 "band_bytes": _plan.chol_band_bytes(n, kl), "reordered": False}
                     return 1
-                chol_tried = True
-            if not fits and A.shape[0] <= 400000 and A.nnz <= 2e8:
-                # as numbered the band is too wide -- field-major systems of several fields (kl ~ n (nF-1)/nF): the saddle
-                # point and elasticity cases where the reference's direct solver matters.  Evaluate the band of the
-                # reverse Cuthill-McKee ordering of the pattern before giving LU up.
-                import scipy.sparse as _sp
-                from scipy.sparse.csgraph import reverse_cuthill_mckee
-                S = A.to_scipy()
-                pat = _sp.csr_matrix((numpy.ones(S.nnz, dtype=numpy.int8), S.indices, S.indptr), shape=S.shape)
-                prm = numpy.asarray(reverse_cuthill_mckee((pat + pat.T).tocsr(), symmetric_mode=True), dtype=numpy.int64)
-                inv = numpy.empty_like(prm)
-                inv[prm] = numpy.arange(prm.size)
-                coo = S.tocoo()
-                dist = inv[coo.row] - inv[coo.col]
-                kl2, ku2 = int(max(0, dist.max())), int(max(0, -dist.min()))
-                nb2 = 8.0 * A.shape[0] * (2 * kl2 + ku2 + 1)
-                if nb2 <= 8 * 2 ** 30 and 2.0 * A.shape[0] * kl2 * (kl2 + ku2) <= 4e12:
-                    fits = True
+            elif attempt == "krylov":
+                return self._krylov(A, x, b)
+            else:
+                lu = PETScLUSolver()
+                if attempt == "rcm":
+                    ordering = _rcm_ordering(A)
+                    if not _plan.lu_fits(n, *ordering[2]):
+                        continue
                     lu.parameters["reorder"] = True
-            if fits or os.environ.get("TIGAR_DEFAULT_SOLVER") == "lu":
-                lu.solve(A, x, b)
+                lu.solve(A, x, b, _ordering=ordering)
                 self.last = dict(lu.last, solver="lu")
                 return 1
-            if chol_fits and not chol_tried and cholesky():
-                return 1
+
+    def _krylov(self, A, x, b):
         ks = PETScKrylovSolver(self.method, "jacobi", comm=self.comm)
         ks.parameters["relative_tolerance"] = 1e-12
         ks.parameters["maximum_iterations"] = 10000

@@ -804,203 +804,234 @@ __global__ void __launch_bounds__(256) k_chol_sweep(const double *__restrict__ l
     if (!body(step, pv)) return;
 }
 
+// ---- host driver: qualify, load and check, factorise, substitute --------------------------------------------------------
+struct ch_knobs {        // the switches, read once per solve
+  int enabled = tg_env_int("TIGAR_LU_CHOLESKY", 1);         // 0: never tried
+  int pair_kl = tg_env_int("TIGAR_CHOL_PAIR_KL", 2048);     // the half-width from which on two panels per pass, twice that: four
+  int group = tg_env_int("TIGAR_CHOL_GROUP", 0);            // g > 0: always g panels per pass (at most 16)
+  int lookahead = tg_env_int("TIGAR_CHOL_LOOKAHEAD", 1);    // 0: the update kernel does not factorise the next diagonal block
+  int fused = tg_env_int("TIGAR_CHOL_FUSED", 1);            // 0: a panel and an update kernel per block
+  int sweep = tg_env_int("TIGAR_CHOL_SWEEP", 1);            // 0: the substitutions on one workgroup
+  int sweep_wgs = tg_env_int("TIGAR_CHOL_SWEEP_WGS", 0);    // n > 1: on n workgroups (at most 128)
+  bool trace = getenv("TIGAR_TRACE") != nullptr;
+};
+
+struct ch_system {       // the lower band, the factors of two diagonal blocks, the inverse pivots and the counters of the checks
+  int64_t n = 0, ldl = 0;
+  int kl = 0, W = 0;     // W: slots of the substitutions' window of x in LDS (a power of two)
+  size_t lds = 0;        // bytes of LDS of a substitution kernel
+  tg_dbuf<double> lb, l11, l11b, dinv;
+  tg_dbuf<ch_stats> st;
+};
+
+enum ch_result { CH_OK, CH_ERROR, CH_DECLINE };      // (CH_DECLINE: not for this factorisation -- the caller goes on with the LU)
+
+// symmetric band of at least 8, two blocks of columns, and a window of x that fits in LDS
+static bool ch_qualifies(ch_system &s, int64_t n, int kl, int ku) {
+  if (kl != ku || kl < 8 || n < 2 * CH_NB) return false;
+  s.n = n;
+  s.kl = kl;
+  s.ldl = (int64_t)kl + 1;
+  s.W = 64;
+  while (s.W < kl + 2 * CH_NB) s.W <<= 1;
+  s.lds = (size_t)(s.W + CH_NB + CH_NB * (CH_NB + 1)) * sizeof(double);
+  return s.lds <= 150 * 1024;
+}
+
+static bool ch_read_stats(const ch_system &s, ch_stats *h) {
+  return hipGetLastError() == hipSuccess && hipMemcpyAsync(h, s.st, sizeof(*h), hipMemcpyDeviceToHost, g_tg.stream) == hipSuccess &&
+         hipStreamSynchronize(g_tg.stream) == hipSuccess;
+}
+
+// scatter the lower triangle into the band and compare K with its transpose
+static ch_result ch_load(ch_system &s, tg_csr_s *k, const ch_knobs &e) {
+  const int64_t n = s.n;
+  if (s.lb.alloc(s.ldl * n)) {
+    (void)hipGetLastError();
+    return CH_DECLINE;               // (no room: the LU reports it)
+  }
+  ch_stats h;
+  memset(&h, 0, sizeof(h));
+  if (s.st.alloc(1) || s.l11.alloc(CH_NB * CH_NB) || s.l11b.alloc(CH_NB * CH_NB) || s.dinv.alloc(n) ||
+      hipMemsetAsync(s.lb, 0, (size_t)(s.ldl * n) * sizeof(double), g_tg.stream) != hipSuccess ||
+      hipMemcpyAsync(s.st, &h, sizeof(h), hipMemcpyHostToDevice, g_tg.stream) != hipSuccess)
+    return CH_ERROR;
+  const unsigned g = (unsigned)std::min<int64_t>(tg_cdiv(n, 4), (int64_t)g_tg.num_cu * 16);
+  hipLaunchKernelGGL(k_chol_scatter, dim3(g), dim3(256), 0, g_tg.stream, k->rowptr, k->col, k->val, n, s.ldl, s.lb.get(), s.st.get());
+  hipLaunchKernelGGL(k_chol_symcheck, dim3(g), dim3(256), 0, g_tg.stream, k->rowptr, k->col, k->val, n, s.kl, s.ldl, s.lb.get(), 1e-11,
+                     s.st.get());
+  if (!ch_read_stats(s, &h)) return CH_ERROR;
+  if (h.asym || h.lower != h.upper) {
+    if (e.trace) fprintf(stderr, "[trace] cholesky: the matrix is not symmetric: LU\n");
+    return CH_DECLINE;
+  }
+  if (hipFuncSetAttribute((const void *)k_chol_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds) != hipSuccess ||
+      hipFuncSetAttribute((const void *)k_chol_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return CH_DECLINE;
+  }
+  return CH_OK;
+}
+
+static ch_result ch_factorise(ch_system &s, const ch_knobs &e) {
+  const int64_t n = s.n, ldl = s.ldl;
+  const int kl = s.kl;
+  double *lb = s.lb, *dinv = s.dinv;
+  ch_stats *st = s.st;
+  // wide bands: groups of 2 / 4 panels per pass over the trailing triangle.  Inside a group the 32 columns of the next block
+  // get their share of the panels before them from the tiles of one tile column (col0 = 1, cw = 32).
+  int ng = kl >= 2 * (int64_t)e.pair_kl ? 4 : kl >= e.pair_kl ? 2 : 1;
+  if (e.group > 0) ng = std::min(e.group, 16);
+  const int big = 1 << 30;
+  // one panel per update: the factor of the next diagonal block comes out of the update kernel
+  const bool ahead = ng == 1 && kl >= 64 && e.lookahead != 0;
+  double *lcur = s.l11, *lnext = s.l11b;
+  bool have = false;
+  // ... and with its factor known a block takes ONE launch: the update kernel solves the rows of the panel it needs itself
+  // (k_chol_fused)
+  const int64_t ph = (int64_t)kl + 2 * CH_NB;
+  tg_dbuf<double> pan[2];
+  bool fused = ahead && e.fused != 0;
+  if (fused && (pan[0].alloc(ph * CH_NB) || pan[1].alloc(ph * CH_NB))) {
+    (void)hipGetLastError();
+    fused = false;
+  }
+  int pcur = 0;
+  bool pending = false;                  // a solved panel waits in pan[pcur ^ 1] for its copy into the band
+  int64_t jpend = 0;
+  auto flush = [&]() {
+    if (pending)
+      hipLaunchKernelGGL(k_chol_pancopy, dim3(CH_NCOPY), dim3(256), 0, g_tg.stream, lb, ldl, n, kl, jpend, (const double *)pan[pcur ^ 1], ph);
+    pending = false;
+  };
+  for (int64_t j0 = 0; j0 < n;) {
+    if (fused && have) {
+      // (ng == 1; `have`: the previous launch saw rows below its block, so this block is a full one)
+      const int64_t j1 = j0 + CH_NB;
+      const int64_t m = std::max<int64_t>(0, std::min<int64_t>(n - 1, j0 + CH_NB - 1 + kl) - j1 + 1);
+      const int nt = (int)tg_cdiv(m, 64);
+      if (nt > 0) {
+        hipLaunchKernelGGL(k_chol_fused, dim3((unsigned)(nt * (nt + 1) / 2 + 1 + CH_NCOPY)), dim3(256), 0, g_tg.stream, lb, ldl, n, kl,
+                           j0, nt, (const double *)lcur, lnext, dinv, st, pan[pcur].get(), ph,
+                           pending ? (const double *)pan[pcur ^ 1] : (const double *)nullptr, jpend);
+        pending = true;
+        jpend = j0;
+        pcur ^= 1;
+        std::swap(lcur, lnext);
+        j0 = j1;
+        continue;
+      }
+    }
+    flush();
+    int64_t jg = j0;
+    int nk = 0;
+    for (int g = 0; g < ng && jg < n; g++) {
+      const int nbc = (int)std::min<int64_t>(CH_NB, n - jg);
+      const int64_t mrows = std::min<int64_t>(kl, n - jg - nbc);        // rows below the block
+      hipLaunchKernelGGL(k_chol_panel, dim3((unsigned)std::max<int64_t>(1, tg_cdiv(mrows, 256))), dim3(256), 0, g_tg.stream, lb, ldl,
+                         n, kl, jg, lcur, dinv, st, have ? (const double *)lcur : (const double *)nullptr);
+      nk += nbc;
+      const int64_t jn = jg + nbc;
+      const int64_t m = std::max<int64_t>(0, std::min<int64_t>(n - 1, j0 + nk - 1 + kl) - jn + 1);
+      const int nt = (int)tg_cdiv(m, 64);
+      have = ahead && nt > 0;
+      if (g + 1 < ng && jn < n)
+        hipLaunchKernelGGL(k_chol_syrk<false>, dim3((unsigned)(nt + 1)), dim3(256), 0, g_tg.stream, lb, ldl, n, kl, j0, nk, jn, CH_NB,
+                           nt, 1, (const double *)lcur, jg, nbc, (double *)nullptr, dinv, st);
+      else if (have)
+        hipLaunchKernelGGL(k_chol_syrk<true>, dim3((unsigned)(nt * (nt + 1) / 2 + 1)), dim3(256), 0, g_tg.stream, lb, ldl, n, kl, j0,
+                           nk, jn, big, nt, 0, (const double *)lcur, jg, nbc, lnext, dinv, st);
+      else
+        hipLaunchKernelGGL(k_chol_syrk<false>, dim3((unsigned)(nt * (nt + 1) / 2 + 1)), dim3(256), 0, g_tg.stream, lb, ldl, n, kl, j0,
+                           nk, jn, big, nt, 0, (const double *)lcur, jg, nbc, (double *)nullptr, dinv, st);
+      if (have) std::swap(lcur, lnext);
+      jg = jn;
+    }
+    j0 = jg;
+  }
+  flush();
+  ch_stats h;
+  if (!ch_read_stats(s, &h)) return CH_ERROR;
+  if (h.notpd) {
+    if (e.trace) fprintf(stderr, "[trace] cholesky: pivot %d is not positive: LU\n", h.notpd - 1);
+    return CH_DECLINE;
+  }
+  return CH_OK;
+}
+
+// the substitutions on `sg` workgroups with a flag per block; CH_DECLINE: not run, or a wait gave up and x is what it was
+static ch_result ch_sweep(const ch_system &s, const ch_knobs &e, int sg, double *x) {
+  const int64_t n = s.n, nblk = tg_cdiv(n, CH_NB), npub = 2 * nblk * CH_NB;
+  tg_dbuf<double> pub, xsave;
+  tg_dbuf<int> errf;
+  if (pub.alloc(npub) || xsave.alloc(n) || errf.alloc(4) ||
+      hipMemsetAsync(pub, 0xff, (size_t)npub * sizeof(double), g_tg.stream) != hipSuccess ||          // (NaNs: nothing published)
+      hipMemsetAsync(errf, 0, 4 * sizeof(int), g_tg.stream) != hipSuccess ||
+      hipMemcpyAsync(xsave, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, g_tg.stream) != hipSuccess ||
+      hipFuncSetAttribute((const void *)k_chol_sweep<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds) != hipSuccess ||
+      hipFuncSetAttribute((const void *)k_chol_sweep<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return CH_DECLINE;
+  }
+  hipLaunchKernelGGL(k_chol_sweep<true>, dim3(sg), dim3(256), s.lds, g_tg.stream, (const double *)s.lb, (const double *)s.dinv, s.ldl,
+                     n, s.kl, s.W, x, pub.get(), errf.get());
+  hipLaunchKernelGGL(k_chol_sweep<false>, dim3(sg), dim3(256), s.lds, g_tg.stream, (const double *)s.lb, (const double *)s.dinv, s.ldl,
+                     n, s.kl, s.W, x, pub + nblk * CH_NB, errf.get());
+  int herr = 1;
+  if (hipGetLastError() == hipSuccess && hipMemcpyAsync(&herr, errf, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream) == hipSuccess &&
+      hipStreamSynchronize(g_tg.stream) == hipSuccess && herr == 0) {
+    if (e.trace) fprintf(stderr, "[trace] cholesky: substitutions on %d workgroups\n", sg);
+    return CH_OK;
+  }
+  (void)hipGetLastError();
+  if (e.trace) fprintf(stderr, "[trace] cholesky: the sweeps on several workgroups gave up: one workgroup\n");
+  return hipMemcpyAsync(x, xsave, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, g_tg.stream) == hipSuccess ? CH_DECLINE : CH_ERROR;
+}
+
+static ch_result ch_substitute(const ch_system &s, const ch_knobs &e, const double *b, double *x) {
+  const int64_t n = s.n;
+  if (x != b && hipMemcpyAsync(x, b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, g_tg.stream) != hipSuccess) return CH_ERROR;
+  // several workgroups with a flag per block (TIGAR_CHOL_SWEEP=0, or a wait that gave up: one workgroup)
+  ch_result swept = CH_DECLINE;
+  const int64_t nblk = tg_cdiv(n, CH_NB);
+  // a workgroup's six groups of 32 threads take the tiles of ~4 owned blocks per step in one pass
+  int sg = (int)std::min<int64_t>(CH_SG_MAX, std::max<int64_t>(CH_SG_MIN, (s.kl + 2 * CH_NB - 1) / CH_NB / 4));
+  if (e.sweep_wgs > 1) sg = std::min(e.sweep_wgs, 128);
+  if (e.sweep != 0 && nblk >= 4 * sg && g_tg.num_cu >= 2 * sg) swept = ch_sweep(s, e, sg, x);
+  if (swept == CH_DECLINE) {
+    hipLaunchKernelGGL(k_chol_fwd, dim3(1), dim3(CH_NT), s.lds, g_tg.stream, (const double *)s.lb, (const double *)s.dinv, s.ldl, n, s.kl,
+                       s.W, x);
+    hipLaunchKernelGGL(k_chol_bwd, dim3(1), dim3(CH_NT), s.lds, g_tg.stream, (const double *)s.lb, (const double *)s.dinv, s.ldl, n, s.kl,
+                       s.W, x);
+  }
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(g_tg.stream) != hipSuccess) return CH_ERROR;
+  return swept == CH_ERROR ? CH_ERROR : CH_OK;
+}
+
 // 0 = solved by Cholesky (*done = 1) or not applicable (*done = 0: the caller goes on with the LU)
 int tg_chol_try(tg_csr_s *k, int kl, int ku, const double *b, double *x, int *done) {
   *done = 0;
-  if (getenv("TIGAR_LU_CHOLESKY") && atoi(getenv("TIGAR_LU_CHOLESKY")) == 0) return 0;
-  const int64_t n = k->nrows;
-  if (kl != ku || kl < 8 || n < 2 * CH_NB) return 0;
-  int W = 64;
-  while (W < kl + 2 * CH_NB) W <<= 1;
-  const size_t lds = (size_t)(W + CH_NB + CH_NB * (CH_NB + 1)) * sizeof(double);
-  if (lds > 150 * 1024) return 0;
-  const bool trace = getenv("TIGAR_TRACE") != nullptr;
-  const int64_t ldl = (int64_t)kl + 1;
-  double *lb = nullptr, *l11 = nullptr, *l11b = nullptr, *dinv = nullptr;
-  ch_stats *st = nullptr;
-  if (tg_dmalloc(&lb, ldl * n)) {
-    (void)hipGetLastError();
-    return 0;                        // (no room: the LU reports it)
+  const ch_knobs e;
+  ch_system s;
+  if (!e.enabled || !ch_qualifies(s, k->nrows, kl, ku)) return 0;
+  ch_result r = ch_load(s, k, e);
+  if (r == CH_OK) r = ch_factorise(s, e);
+  if (r == CH_OK) r = ch_substitute(s, e, b, x);
+  if (r == CH_ERROR) {
+    tg_set_error("tg_chol_try: a kernel or a copy failed");
+    return 1;
   }
-  int rc = tg_dmalloc_bytes((void **)&st, sizeof(ch_stats)) || tg_dmalloc(&l11, CH_NB * CH_NB) || tg_dmalloc(&l11b, CH_NB * CH_NB) ||
-           tg_dmalloc(&dinv, n);
-  ch_stats h;
-  memset(&h, 0, sizeof(h));
-  if (!rc && (hipMemsetAsync(lb, 0, (size_t)(ldl * n) * sizeof(double), g_tg.stream) != hipSuccess ||
-              hipMemcpyAsync(st, &h, sizeof(h), hipMemcpyHostToDevice, g_tg.stream) != hipSuccess))
-    rc = 1;
-  if (!rc) {
-    const unsigned g = (unsigned)std::min<int64_t>(tg_cdiv(n, 4), (int64_t)g_tg.num_cu * 16);
-    hipLaunchKernelGGL(k_chol_scatter, dim3(g), dim3(256), 0, g_tg.stream, k->rowptr, k->col, k->val, n, ldl, lb, st);
-    hipLaunchKernelGGL(k_chol_symcheck, dim3(g), dim3(256), 0, g_tg.stream, k->rowptr, k->col, k->val, n, kl, ldl, lb, 1e-11, st);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess ||
-        hipStreamSynchronize(g_tg.stream) != hipSuccess)
-      rc = 1;
-  }
-  bool go = !rc && !h.asym && h.lower == h.upper;
-  if (!rc && !go && trace) fprintf(stderr, "[trace] cholesky: the matrix is not symmetric: LU\n");
-  if (go) {
-    if (hipFuncSetAttribute((const void *)k_chol_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_chol_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      (void)hipGetLastError();
-      go = false;
-    }
-  }
-  if (go) {
-    // wide bands: groups of 2 / 4 panels per pass over the trailing triangle (TIGAR_CHOL_PAIR_KL: the half-width from which on
-    // two, twice that: four; TIGAR_CHOL_GROUP=g: always g).  Inside a group the 32 columns of the next block get their share of
-    // the panels before them from the tiles of one tile column (col0 = 1, cw = 32).
-    const int pair_kl = getenv("TIGAR_CHOL_PAIR_KL") ? atoi(getenv("TIGAR_CHOL_PAIR_KL")) : 2048;
-    int ng = kl >= 2 * (int64_t)pair_kl ? 4 : kl >= pair_kl ? 2 : 1;
-    if (getenv("TIGAR_CHOL_GROUP") && atoi(getenv("TIGAR_CHOL_GROUP")) > 0) ng = std::min(atoi(getenv("TIGAR_CHOL_GROUP")), 16);
-    const int big = 1 << 30;
-    // one panel per update: the factor of the next diagonal block comes out of the update kernel (TIGAR_CHOL_LOOKAHEAD=0: not)
-    const bool ahead = ng == 1 && kl >= 64 && l11b && !(getenv("TIGAR_CHOL_LOOKAHEAD") && atoi(getenv("TIGAR_CHOL_LOOKAHEAD")) == 0);
-    double *lcur = l11, *lnext = l11b;
-    bool have = false;
-    // ... and with its factor known a block takes ONE launch: the update kernel solves the rows of the panel it needs itself
-    // (k_chol_fused; TIGAR_CHOL_FUSED=0: a panel and an update kernel per block)
-    const int64_t ph = (int64_t)kl + 2 * CH_NB;
-    double *pan[2] = {nullptr, nullptr};
-    bool fused = ahead && !(getenv("TIGAR_CHOL_FUSED") && atoi(getenv("TIGAR_CHOL_FUSED")) == 0);
-    if (fused && (tg_dmalloc(&pan[0], ph * CH_NB) || tg_dmalloc(&pan[1], ph * CH_NB))) {
-      (void)hipGetLastError();
-      fused = false;
-    }
-    int pcur = 0;
-    bool pending = false;                  // a solved panel waits in pan[pcur ^ 1] for its copy into the band
-    int64_t jpend = 0;
-    auto flush = [&]() {
-      if (pending)
-        hipLaunchKernelGGL(k_chol_pancopy, dim3(CH_NCOPY), dim3(256), 0, g_tg.stream, lb, ldl, n, kl, jpend, (const double *)pan[pcur ^ 1], ph);
-      pending = false;
-    };
-    for (int64_t j0 = 0; j0 < n;) {
-      if (fused && have) {
-        // (ng == 1; `have`: the previous launch saw rows below its block, so this block is a full one)
-        const int64_t j1 = j0 + CH_NB;
-        const int64_t m = std::max<int64_t>(0, std::min<int64_t>(n - 1, j0 + CH_NB - 1 + kl) - j1 + 1);
-        const int nt = (int)tg_cdiv(m, 64);
-        if (nt > 0) {
-          hipLaunchKernelGGL(k_chol_fused, dim3((unsigned)(nt * (nt + 1) / 2 + 1 + CH_NCOPY)), dim3(256), 0, g_tg.stream, lb, ldl, n, kl,
-                             j0, nt, (const double *)lcur, lnext, dinv, st, pan[pcur], ph,
-                             pending ? (const double *)pan[pcur ^ 1] : (const double *)nullptr, jpend);
-          pending = true;
-          jpend = j0;
-          pcur ^= 1;
-          std::swap(lcur, lnext);
-          j0 = j1;
-          continue;
-        }
-      }
-      flush();
-      int64_t jg = j0;
-      int nk = 0;
-      for (int g = 0; g < ng && jg < n; g++) {
-        const int nbc = (int)std::min<int64_t>(CH_NB, n - jg);
-        const int64_t mrows = std::min<int64_t>(kl, n - jg - nbc);        // rows below the block
-        hipLaunchKernelGGL(k_chol_panel, dim3((unsigned)std::max<int64_t>(1, tg_cdiv(mrows, 256))), dim3(256), 0, g_tg.stream, lb, ldl,
-                           n, kl, jg, lcur, dinv, st, have ? (const double *)lcur : (const double *)nullptr);
-        nk += nbc;
-        const int64_t jn = jg + nbc;
-        const int64_t m = std::max<int64_t>(0, std::min<int64_t>(n - 1, j0 + nk - 1 + kl) - jn + 1);
-        const int nt = (int)tg_cdiv(m, 64);
-        have = ahead && nt > 0;
-        if (g + 1 < ng && jn < n)
-          hipLaunchKernelGGL(k_chol_syrk<false>, dim3((unsigned)(nt + 1)), dim3(256), 0, g_tg.stream, lb, ldl, n, kl, j0, nk, jn, CH_NB,
-                             nt, 1, (const double *)lcur, jg, nbc, (double *)nullptr, dinv, st);
-        else if (have)
-          hipLaunchKernelGGL(k_chol_syrk<true>, dim3((unsigned)(nt * (nt + 1) / 2 + 1)), dim3(256), 0, g_tg.stream, lb, ldl, n, kl, j0,
-                             nk, jn, big, nt, 0, (const double *)lcur, jg, nbc, lnext, dinv, st);
-        else
-          hipLaunchKernelGGL(k_chol_syrk<false>, dim3((unsigned)(nt * (nt + 1) / 2 + 1)), dim3(256), 0, g_tg.stream, lb, ldl, n, kl, j0,
-                             nk, jn, big, nt, 0, (const double *)lcur, jg, nbc, (double *)nullptr, dinv, st);
-        if (have) std::swap(lcur, lnext);
-        jg = jn;
-      }
-      j0 = jg;
-    }
-    flush();
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess ||
-        hipStreamSynchronize(g_tg.stream) != hipSuccess)
-      rc = 1;
-    if (!rc && h.notpd) {
-      if (trace) fprintf(stderr, "[trace] cholesky: pivot %d is not positive: LU\n", h.notpd - 1);
-      go = false;
-    }
-    tg_dfree(pan[0]);
-    tg_dfree(pan[1]);
-  }
-  if (!rc && go) {
-    if (x != b && hipMemcpyAsync(x, b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, g_tg.stream) != hipSuccess) rc = 1;
-    if (!rc) {
-      // several workgroups with a flag per block (TIGAR_CHOL_SWEEP=0, or a wait that gave up: one workgroup)
-      bool swept = false;
-      const int64_t nblk = tg_cdiv(n, CH_NB);
-      // a workgroup's six groups of 32 threads take the tiles of ~4 owned blocks per step in one pass
-      int sg = (int)std::min<int64_t>(CH_SG_MAX, std::max<int64_t>(CH_SG_MIN, (kl + 2 * CH_NB - 1) / CH_NB / 4));
-      if (getenv("TIGAR_CHOL_SWEEP_WGS") && atoi(getenv("TIGAR_CHOL_SWEEP_WGS")) > 1) sg = std::min(atoi(getenv("TIGAR_CHOL_SWEEP_WGS")), 128);
-      if (!(getenv("TIGAR_CHOL_SWEEP") && atoi(getenv("TIGAR_CHOL_SWEEP")) == 0) && nblk >= 4 * sg && g_tg.num_cu >= 2 * sg) {
-        double *pub = nullptr, *xsave = nullptr;
-        int *errf = nullptr;
-        const int64_t npub = 2 * nblk * CH_NB;
-        if (!tg_dmalloc(&pub, npub) && !tg_dmalloc(&xsave, n) && !tg_dmalloc(&errf, 4) &&
-            hipMemsetAsync(pub, 0xff, (size_t)npub * sizeof(double), g_tg.stream) == hipSuccess &&          // (NaNs: nothing published)
-            hipMemsetAsync(errf, 0, 4 * sizeof(int), g_tg.stream) == hipSuccess &&
-            hipMemcpyAsync(xsave, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, g_tg.stream) == hipSuccess &&
-            hipFuncSetAttribute((const void *)k_chol_sweep<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-            hipFuncSetAttribute((const void *)k_chol_sweep<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) {
-          hipLaunchKernelGGL(k_chol_sweep<true>, dim3(sg), dim3(256), lds, g_tg.stream, (const double *)lb, (const double *)dinv, ldl,
-                             n, kl, W, x, pub, errf);
-          hipLaunchKernelGGL(k_chol_sweep<false>, dim3(sg), dim3(256), lds, g_tg.stream, (const double *)lb, (const double *)dinv, ldl,
-                             n, kl, W, x, pub + nblk * CH_NB, errf);
-          int herr = 1;
-          if (hipGetLastError() == hipSuccess && hipMemcpyAsync(&herr, errf, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream) == hipSuccess &&
-              hipStreamSynchronize(g_tg.stream) == hipSuccess && herr == 0)
-          {
-            swept = true;
-            if (trace) fprintf(stderr, "[trace] cholesky: substitutions on %d workgroups\n", sg);
-          } else {
-            (void)hipGetLastError();
-            if (trace) fprintf(stderr, "[trace] cholesky: the sweeps on several workgroups gave up: one workgroup\n");
-            if (hipMemcpyAsync(x, xsave, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, g_tg.stream) != hipSuccess) rc = 1;
-          }
-        } else
-          (void)hipGetLastError();
-        tg_dfree(pub);
-        tg_dfree(errf);
-        tg_dfree(xsave);
-      }
-      if (!rc && !swept) {
-        hipLaunchKernelGGL(k_chol_fwd, dim3(1), dim3(CH_NT), lds, g_tg.stream, (const double *)lb, (const double *)dinv, ldl, n, kl, W, x);
-        hipLaunchKernelGGL(k_chol_bwd, dim3(1), dim3(CH_NT), lds, g_tg.stream, (const double *)lb, (const double *)dinv, ldl, n, kl, W, x);
-      }
-      if (hipGetLastError() != hipSuccess || hipStreamSynchronize(g_tg.stream) != hipSuccess) rc = 1;
-    }
-    if (!rc) *done = 1;
-    if (!rc && trace) fprintf(stderr, "[trace] cholesky: %lld x %lld, kl = %d, band %.2f GB\n", (long long)n, (long long)n, kl, ldl * n * 8e-9);
-  }
-  if (rc) tg_set_error("tg_chol_try: a kernel or a copy failed");
-  tg_dfree(lb);
-  tg_dfree(l11);
-  tg_dfree(l11b);
-  tg_dfree(dinv);
-  tg_dfree(st);
-  return rc;
+  if (r == CH_DECLINE) return 0;
+  *done = 1;
+  g_tg.prof_n[TG_PROF_LU_CHOLESKY] += 1;
+  if (e.trace)
+    fprintf(stderr, "[trace] cholesky: %lld x %lld, kl = %d, band %.2f GB\n", (long long)s.n, (long long)s.n, kl, s.ldl * s.n * 8e-9);
+  return 0;
 }
 
 extern "C" int tg_chol_solve(tg_csr_t k, tg_vec_t b, tg_vec_t x, int *done) {
-  TG_REQUIRE_INIT();
-  TG_REQUIRE(k && b && x && done, "null argument to tg_chol_solve");
-  TG_REQUIRE_CANONICAL(k);
-  const int64_t n = k->nrows;
-  TG_REQUIRE(k->ncols == n && b->n == n && x->n == n, "tg_chol_solve: square system with matching vectors expected");
-  *done = 0;
-  if (n == 0) return 0;
   int kl = 0, ku = 0;
-  int64_t bytes = 0;
-  TG_TRY(tg_lu_band_info(k, &kl, &ku, &bytes));
-  TG_TRY(tg_chol_try(k, kl, ku, b->d, x->d, done));
-  g_tg.prof_n[TG_PROF_LU_CHOLESKY] += *done;
-  return 0;
+  TG_TRY(tg_band_system("tg_chol_solve", k, b, x, done, &kl, &ku));
+  *done = 0;
+  return k->nrows ? tg_chol_try(k, kl, ku, b->d, x->d, done) : 0;
 }

@@ -231,7 +231,10 @@ int tg_sell_spmv_rows(tg_csr_s *a, const double *x_shifted, int64_t cmin, int64_
                       int64_t r1, const double *gate, double gate_tol);
 
 // banded Cholesky for symmetric positive definite systems (tg_chol.hip): *done = 1 when it solved K x = b
+// (it counts its solves in TG_PROF_LU_CHOLESKY)
 int tg_chol_try(tg_csr_s *k, int kl, int ku, const double *b, double *x, int *done);
+// the argument checks of tg_lu_solve / tg_chol_solve and the half-bandwidths of k (tg_lu.hip)
+int tg_band_system(const char *who, tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, const void *out, int *kl, int *ku);
 // half-storage product for symmetric box-stencil matrices on a 3-D grid (tg_symgrid.hip)
 struct tg_symgrid_s;
 int tg_symgrid_build(tg_csr_s *a, int64_t row0, int verify, tg_symgrid_s **out);   // *out = nullptr: declined

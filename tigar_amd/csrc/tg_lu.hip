@@ -12,6 +12,7 @@
 // column), meant for the moderate sizes where the reference uses LU; large 3-D systems belong to the Krylov solvers.
 #include "tg_common.h"
 #include <algorithm>
+#include <climits>
 
 struct tg_lu_state {     // device-resident control block
   int ju;                // last column touched by the row interchanges so far (LAPACK's JU), 0-based
@@ -947,152 +948,204 @@ extern "C" int tg_lu_band_info(tg_csr_t k, int *kl_out, int *ku_out, int64_t *by
   return 0;
 }
 
+// the argument checks of a direct solve (`who`: the entry point, `out`: its result pointer) and the band of k
+int tg_band_system(const char *who, tg_csr_s *k, tg_vec_s *b, tg_vec_s *x, const void *out, int *kl, int *ku) {
+  TG_REQUIRE_INIT();
+  TG_REQUIRE(k && b && x && out, "null argument to %s", who);
+  TG_REQUIRE(!k->rowcnt, "%s: loose-row intermediate of a PtAP stage; call tg_csr_compact first", who);
+  const int64_t n = k->nrows;
+  TG_REQUIRE(k->ncols == n && b->n == n && x->n == n, "%s: square system with matching vectors expected", who);
+  *kl = *ku = 0;
+  int64_t bytes = 0;
+  return n ? tg_lu_band_info(k, kl, ku, &bytes) : 0;
+}
+
+// ---- host driver: load, factorise, read info, substitute ----------------------------------------------------------------
+struct lu_knobs {        // the TIGAR_LU_* switches, read once per solve
+  int fused = tg_env_int("TIGAR_LU_FUSED", 1);                       // 0: a pivot and an update launch per column (round 2), not one
+  int blocked = tg_env_int("TIGAR_LU_BLOCKED", 1);                   // 0: column by column
+  int nb = tg_env_int("TIGAR_LU_NB", INT_MIN);                       // the panel width, at most 32 (INT_MIN: not set)
+  int panel_reg = tg_env_int("TIGAR_LU_PANEL_REG", 1);               // 0: the panel in LDS
+  bool solve_global = getenv("TIGAR_LU_SOLVE_GLOBAL") != nullptr;    // set, to whatever: substitutions without the ring in LDS
+};
+
+struct lu_system {       // the matrix in dgbtrf's band storage, its pivots and the state block of the column kernels
+  int64_t n = 0, ldab = 0;
+  int kl = 0, ku = 0, kv = 0;
+  tg_dbuf<double> ab;
+  tg_dbuf<int32_t> ipiv;
+  tg_dbuf<tg_lu_state> st;
+  int info_slot = 0;     // the slot of `st` that holds `info` after the factorisation
+};
+
+template <typename F>
+struct lu_kernel {
+  F fn;
+  int nt;                // threads per block
+};
+typedef void (*lu_trail_fn)(double *, int64_t, int64_t, int, int, int64_t, int, const int32_t *, const tg_lu_state *);
+typedef void (*lu_panel_reg_fn)(double *, int64_t, int64_t, int, int, int64_t, int32_t *, tg_lu_state *);
+typedef void (*lu_fwd_fn)(const double *, int64_t, int64_t, int, int, const int32_t *, double *);
+typedef void (*lu_bwd_fn)(const double *, int64_t, int64_t, int, double *);
+
+// trailing-column kernel by the rows below the diagonal (the widest bands: the one that reads its multipliers in place)
+static lu_kernel<lu_trail_fn> lu_pick_trail(int kl) {
+  return {kl <= 512 ? k_lu_trail<1> : kl <= 1024 ? k_lu_trail<2> : kl <= 1536 ? k_lu_trail<3> : kl <= 2048 ? k_lu_trail<4> : k_lu_trail<0>,
+          256};
+}
+
+// register panel by the rows of the panel (NT threads x RS rows each); {nullptr, 0}: the panel in LDS
+static lu_kernel<lu_panel_reg_fn> lu_pick_panel_reg(int nb, int rows) {
+  if (nb == 16) {
+    if (rows <= 256) return {k_lu_panel_reg<16, 1, 256>, 256};
+    if (rows <= 512) return {k_lu_panel_reg<16, 2, 256>, 256};
+    if (rows <= 768) return {k_lu_panel_reg<16, 3, 256>, 256};
+    if (rows <= 1152) return {k_lu_panel_reg<16, 3, 384>, 384};
+  } else if (nb == 8) {
+    if (rows <= 1536) return {k_lu_panel_reg<8, 4, 384>, 384};
+    if (rows <= 2304) return {k_lu_panel_reg<8, 6, 384>, 384};
+  }
+  return {nullptr, 0};
+}
+
+// substitution kernels by the entries of the ring per thread: 1024 threads x R entries each (measured at cfg4: 256 / 512
+// threads with more entries each are slower, 148 / 103 ms against 89 ms)
+static lu_kernel<lu_fwd_fn> lu_pick_fwd(int r) {
+  return {r <= 1 ? k_lu_fwd<1, 16, 1024> : r == 2 ? k_lu_fwd<2, 16, 1024> : r == 3 ? k_lu_fwd<3, 8, 1024>
+          : r == 4 ? k_lu_fwd<4, 8, 1024> : k_lu_fwd<6, 4, 1024>, 1024};
+}
+static lu_kernel<lu_bwd_fn> lu_pick_bwd(int r) {
+  return {r <= 1 ? k_lu_bwd<1, 16, 1024> : r == 2 ? k_lu_bwd<2, 16, 1024> : r == 3 ? k_lu_bwd<3, 8, 1024>
+          : r == 4 ? k_lu_bwd<4, 8, 1024> : k_lu_bwd<6, 4, 1024>, 1024};
+}
+
+// allocate, clear, initialise both state slots, scatter the CSR matrix into the band
+static int lu_load(lu_system &s, tg_csr_s *k, int kl, int ku) {
+  s.n = k->nrows;
+  s.kl = kl;
+  s.ku = ku;
+  s.kv = kl + ku;
+  s.ldab = 2 * (int64_t)kl + ku + 1;
+  TG_TRY(s.ab.alloc(s.ldab * s.n));
+  TG_TRY(s.ipiv.alloc(s.n));
+  TG_TRY(s.st.alloc(2));
+  if (hipMemsetAsync(s.ab, 0, (size_t)(s.ldab * s.n) * sizeof(double), g_tg.stream) != hipSuccess) return 1;
+  tg_lu_state h0;
+  h0.ju = 0;
+  h0.info = 0;
+  h0.km = 0;
+  h0.jp = 0;
+  h0.pivinv = 0.0;
+  const bool ok = hipMemcpyAsync(s.st, &h0, sizeof(h0), hipMemcpyHostToDevice, g_tg.stream) == hipSuccess &&
+                  hipMemcpyAsync(s.st + 1, &h0, sizeof(h0), hipMemcpyHostToDevice, g_tg.stream) == hipSuccess;
+  hipStreamSynchronize(g_tg.stream);
+  if (!ok) return 1;
+  hipLaunchKernelGGL(k_lu_scatter, dim3((unsigned)std::min<int64_t>(tg_cdiv(s.n, 4), (int64_t)g_tg.num_cu * 16)), dim3(256), 0,
+                     g_tg.stream, k->rowptr, k->col, k->val, s.n, s.kv, s.ldab, s.ab.get());
+  return 0;
+}
+
+static int lu_factorise(lu_system &s, const lu_knobs &e) {
+  const int64_t n = s.n, ldab = s.ldab;
+  const int kl = s.kl, kv = s.kv;
+  double *ab = s.ab;
+  int32_t *ipiv = s.ipiv;
+  tg_lu_state *st = s.st;
+  // panel width: the widest of 16 / 8 / 4 columns whose panel ((kl + nb) x nb doubles) fits in LDS
+  int nb = 0;
+  for (int cand = 16; cand >= 4 && !nb; cand >>= 1)
+    if ((size_t)(kl + cand) * cand * sizeof(double) <= 140 * 1024) nb = cand;
+  if (e.nb != INT_MIN) nb = std::min(32, e.nb);
+  bool use_blocked = e.blocked && nb >= 2 && kl > 0;
+  const lu_kernel<lu_trail_fn> trail = lu_pick_trail(kl);
+  const lu_kernel<lu_panel_reg_fn> panel_reg = e.panel_reg ? lu_pick_panel_reg(nb, kl + nb) : lu_kernel<lu_panel_reg_fn>{nullptr, 0};
+  const size_t lds = (size_t)(kl + nb) * nb * sizeof(double);        // the panel
+  const size_t ldt = (size_t)TG_LU_TC * (kl + nb) * sizeof(double);  // TG_LU_TC trailing columns
+  if (use_blocked &&
+      (hipFuncSetAttribute((const void *)k_lu_panel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+       hipFuncSetAttribute((const void *)trail.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldt) != hipSuccess)) {
+    (void)hipGetLastError();
+    use_blocked = false;
+  }
+  // (fused: the state of the last column is in slot (n-1) & 1; `info` is carried from slot to slot)
+  s.info_slot = (e.fused && !use_blocked) ? (int)((n - 1) & 1) : 0;
+  if (use_blocked) {
+    const unsigned gt = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tg_cdiv((int64_t)kv + nb, TG_LU_TC), (int64_t)g_tg.num_cu * 8));
+    for (int64_t j0 = 0; j0 < n; j0 += nb) {
+      if (panel_reg.fn) hipLaunchKernelGGL(panel_reg.fn, dim3(1), dim3(panel_reg.nt), 0, g_tg.stream, ab, ldab, n, kl, kv, j0, ipiv, st);
+      else hipLaunchKernelGGL(k_lu_panel, dim3(1), dim3(1024), lds, g_tg.stream, ab, ldab, n, kl, kv, j0, nb, ipiv, st);
+      if (j0 + nb >= n) break;
+      hipLaunchKernelGGL(trail.fn, dim3(gt), dim3(trail.nt), ldt, g_tg.stream, ab, ldab, n, kl, kv, j0, nb, (const int32_t *)ipiv,
+                         (const tg_lu_state *)st);
+    }
+  } else if (e.fused) {
+    // column 0: pivot search alone (its state lands in slot 0); then ONE launch per column: launch j interchanges and
+    // eliminates with column j and prepares column j+1
+    hipLaunchKernelGGL(k_lu_pivot, dim3(1), dim3(256), 0, g_tg.stream, ab, ldab, n, kl, kv, (int64_t)0, ipiv, st, 0);
+    const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)kv, (int64_t)g_tg.num_cu * 8));
+    for (int64_t j = 0; j + 1 < n; j++)
+      hipLaunchKernelGGL(k_lu_step, dim3(1, gy), dim3(256), 0, g_tg.stream, ab, ldab, n, kl, kv, j, ipiv, st);
+  } else {
+    // trailing window of a column: at most kl rows x kv columns
+    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tg_cdiv(kl, 256), 64));
+    const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)kv, (int64_t)g_tg.num_cu * 8 / gx));
+    for (int64_t j = 0; j < n; j++) {
+      hipLaunchKernelGGL(k_lu_pivot, dim3(1), dim3(256), 0, g_tg.stream, ab, ldab, n, kl, kv, j, ipiv, st, 1);
+      if (kl > 0 && j + 1 < n)
+        hipLaunchKernelGGL(k_lu_update, dim3(gx, gy), dim3(256), 0, g_tg.stream, ab, ldab, kv, j, st);
+    }
+  }
+  if (hipGetLastError() != hipSuccess) {
+    tg_set_error("tg_lu_solve: kernel launch failed");
+    return 1;
+  }
+  return 0;
+}
+
+static int lu_read_info(const lu_system &s, int *info) {
+  tg_lu_state h1;
+  if (hipMemcpyAsync(&h1, s.st + s.info_slot, sizeof(h1), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess) return 1;
+  if (hipStreamSynchronize(g_tg.stream) != hipSuccess) {
+    tg_set_error("tg_lu_solve: %s", hipGetErrorString(hipGetLastError()));
+    return 1;
+  }
+  *info = h1.info;
+  return 0;
+}
+
+static int lu_substitute(const lu_system &s, const lu_knobs &e, const double *b, double *x) {
+  const int kl = s.kl, kv = s.kv;
+  bool ok = x == b || hipMemcpyAsync(x, b, (size_t)s.n * sizeof(double), hipMemcpyDeviceToDevice, g_tg.stream) == hipSuccess;
+  const int rf = (int)tg_cdiv(std::max(kl, 1), 1024), rb = (int)tg_cdiv(std::max(kv, 1), 1024);
+  if (rb <= 6 && !e.solve_global) {
+    const lu_kernel<lu_fwd_fn> fwd = lu_pick_fwd(rf);
+    const lu_kernel<lu_bwd_fn> bwd = lu_pick_bwd(rb);
+    hipLaunchKernelGGL(fwd.fn, dim3(1), dim3(fwd.nt), (size_t)(kl + 2 + TG_LU_CH) * sizeof(double), g_tg.stream, (const double *)s.ab,
+                       s.ldab, s.n, kl, kv, (const int32_t *)s.ipiv, x);
+    hipLaunchKernelGGL(bwd.fn, dim3(1), dim3(bwd.nt), (size_t)(kv + 2 + TG_LU_CH) * sizeof(double), g_tg.stream, (const double *)s.ab,
+                       s.ldab, s.n, kv, x);
+  } else
+    hipLaunchKernelGGL(k_lu_solve_global, dim3(1), dim3(1024), 0, g_tg.stream, s.ab.get(), s.ldab, s.n, kl, kv, s.ipiv.get(), x);
+  if (hipGetLastError() != hipSuccess) ok = false;
+  if (hipStreamSynchronize(g_tg.stream) != hipSuccess) ok = false;
+  if (!ok) tg_set_error("tg_lu_solve: substitution failed");
+  return ok ? 0 : 1;
+}
+
 // status 0 = solved; info > 0: U(info-1, info-1) is exactly zero (the matrix is singular to working precision)
 extern "C" int tg_lu_solve(tg_csr_t k, tg_vec_t b, tg_vec_t x, int *info) {
-  TG_REQUIRE_INIT();
-  TG_REQUIRE(k && b && x && info, "null argument to tg_lu_solve");
-  TG_REQUIRE_CANONICAL(k);
-  const int64_t n = k->nrows;
-  TG_REQUIRE(k->ncols == n && b->n == n && x->n == n, "tg_lu_solve: square system with matching vectors expected");
-  *info = 0;
-  if (n == 0) return 0;
   int kl = 0, ku = 0;
-  int64_t bytes = 0;
-  TG_TRY(tg_lu_band_info(k, &kl, &ku, &bytes));
-  {   // a symmetric positive definite system: blocked banded Cholesky (tg_chol.hip); otherwise -- or TIGAR_LU_CHOLESKY=0 -- the LU
-    int done = 0;
-    TG_TRY(tg_chol_try(k, kl, ku, b->d, x->d, &done));
-    g_tg.prof_n[TG_PROF_LU_CHOLESKY] += done;
-    if (done) return 0;
-  }
-  const int kv = kl + ku;
-  const int64_t ldab = 2 * (int64_t)kl + ku + 1;
-  double *ab = nullptr;
-  int32_t *ipiv = nullptr;
-  tg_lu_state *st = nullptr;
-  bool blocked_used = false;
-  int rc = tg_dmalloc(&ab, ldab * n);
-  if (!rc) rc = tg_dmalloc(&ipiv, n);
-  if (!rc) rc = tg_dmalloc_bytes((void **)&st, 2 * sizeof(tg_lu_state));
-  if (!rc && hipMemsetAsync(ab, 0, (size_t)(ldab * n) * sizeof(double), g_tg.stream) != hipSuccess) rc = 1;
-  if (!rc) {
-    tg_lu_state h0;
-    h0.ju = 0;
-    h0.info = 0;
-    h0.km = 0;
-    h0.jp = 0;
-    h0.pivinv = 0.0;
-    if (hipMemcpyAsync(st, &h0, sizeof(h0), hipMemcpyHostToDevice, g_tg.stream) != hipSuccess) rc = 1;
-    if (!rc && hipMemcpyAsync(st + 1, &h0, sizeof(h0), hipMemcpyHostToDevice, g_tg.stream) != hipSuccess) rc = 1;
-    hipStreamSynchronize(g_tg.stream);
-  }
-  if (!rc) {
-    hipLaunchKernelGGL(k_lu_scatter, dim3((unsigned)std::min<int64_t>(tg_cdiv(n, 4), (int64_t)g_tg.num_cu * 16)), dim3(256), 0,
-                       g_tg.stream, k->rowptr, k->col, k->val, n, kv, ldab, ab);
-    // column 0: pivot search alone (its state lands in slot 0); then ONE launch per column: launch j interchanges and
-    // eliminates with column j and prepares column j+1 (TIGAR_LU_FUSED=0: the two launches per column of round 2)
-    const int fused = getenv("TIGAR_LU_FUSED") ? atoi(getenv("TIGAR_LU_FUSED")) : 1;
-    const int blocked = getenv("TIGAR_LU_BLOCKED") ? atoi(getenv("TIGAR_LU_BLOCKED")) : 1;
-    // panel width: the widest of 16 / 8 / 4 columns whose panel ((kl + nb) x nb doubles) fits in LDS
-    int nb = 0;
-    for (int cand = 16; cand >= 4 && !nb; cand >>= 1)
-      if ((size_t)(kl + cand) * cand * sizeof(double) <= 140 * 1024) nb = cand;
-    if (getenv("TIGAR_LU_NB")) nb = std::min(32, atoi(getenv("TIGAR_LU_NB")));
-    bool use_blocked = blocked && nb >= 2 && kl > 0;
-    typedef void (*trail_fn)(double *, int64_t, int64_t, int, int, int64_t, int, const int32_t *, const tg_lu_state *);
-    const trail_fn trail = kl <= 512 ? k_lu_trail<1> : kl <= 1024 ? k_lu_trail<2> : kl <= 1536 ? k_lu_trail<3>
-                           : kl <= 2048 ? k_lu_trail<4> : k_lu_trail<0>;
-    typedef void (*panel_reg_fn)(double *, int64_t, int64_t, int, int, int64_t, int32_t *, tg_lu_state *);
-    panel_reg_fn panel_reg = nullptr;              // (TIGAR_LU_PANEL_REG=0: the panel in LDS)
-    int panel_nt = 0;
-    if (!(getenv("TIGAR_LU_PANEL_REG") && atoi(getenv("TIGAR_LU_PANEL_REG")) == 0)) {
-      const int rows = kl + nb;                    // rows of the panel: NT threads x RS rows each
-      if (nb == 16) {
-        if (rows <= 256) panel_reg = k_lu_panel_reg<16, 1, 256>, panel_nt = 256;
-        else if (rows <= 512) panel_reg = k_lu_panel_reg<16, 2, 256>, panel_nt = 256;
-        else if (rows <= 768) panel_reg = k_lu_panel_reg<16, 3, 256>, panel_nt = 256;
-        else if (rows <= 1152) panel_reg = k_lu_panel_reg<16, 3, 384>, panel_nt = 384;
-      } else if (nb == 8) {
-        if (rows <= 1536) panel_reg = k_lu_panel_reg<8, 4, 384>, panel_nt = 384;
-        else if (rows <= 2304) panel_reg = k_lu_panel_reg<8, 6, 384>, panel_nt = 384;
-      }
-    }
-    const size_t lds = (size_t)(kl + nb) * nb * sizeof(double);        // the panel
-    const size_t ldt = (size_t)TG_LU_TC * (kl + nb) * sizeof(double);  // TG_LU_TC trailing columns
-    if (use_blocked &&
-        (hipFuncSetAttribute((const void *)k_lu_panel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-         hipFuncSetAttribute((const void *)trail, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldt) != hipSuccess)) {
-      (void)hipGetLastError();
-      use_blocked = false;
-    }
-    blocked_used = use_blocked;
-    if (use_blocked) {
-      const unsigned gt = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tg_cdiv((int64_t)kv + nb, TG_LU_TC), (int64_t)g_tg.num_cu * 8));
-      for (int64_t j0 = 0; j0 < n; j0 += nb) {
-        if (panel_reg) hipLaunchKernelGGL(panel_reg, dim3(1), dim3(panel_nt), 0, g_tg.stream, ab, ldab, n, kl, kv, j0, ipiv, st);
-        else hipLaunchKernelGGL(k_lu_panel, dim3(1), dim3(1024), lds, g_tg.stream, ab, ldab, n, kl, kv, j0, nb, ipiv, st);
-        if (j0 + nb >= n) break;
-        hipLaunchKernelGGL(trail, dim3(gt), dim3(256), ldt, g_tg.stream, ab, ldab, n, kl, kv, j0, nb, (const int32_t *)ipiv,
-                             (const tg_lu_state *)st);
-      }
-    } else if (fused) {
-      hipLaunchKernelGGL(k_lu_pivot, dim3(1), dim3(256), 0, g_tg.stream, ab, ldab, n, kl, kv, (int64_t)0, ipiv, st, 0);
-      const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)kv, (int64_t)g_tg.num_cu * 8));
-      for (int64_t j = 0; j + 1 < n; j++)
-        hipLaunchKernelGGL(k_lu_step, dim3(1, gy), dim3(256), 0, g_tg.stream, ab, ldab, n, kl, kv, j, ipiv, st);
-    } else {
-      // trailing window of a column: at most kl rows x kv columns
-      const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tg_cdiv(kl, 256), 64));
-      const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)kv, (int64_t)g_tg.num_cu * 8 / gx));
-      for (int64_t j = 0; j < n; j++) {
-        hipLaunchKernelGGL(k_lu_pivot, dim3(1), dim3(256), 0, g_tg.stream, ab, ldab, n, kl, kv, j, ipiv, st, 1);
-        if (kl > 0 && j + 1 < n)
-          hipLaunchKernelGGL(k_lu_update, dim3(gx, gy), dim3(256), 0, g_tg.stream, ab, ldab, kv, j, st);
-      }
-    }
-    if (hipGetLastError() != hipSuccess) {
-      tg_set_error("tg_lu_solve: kernel launch failed");
-      rc = 1;
-    }
-  }
-  if (!rc) {
-    tg_lu_state h1;
-    // (fused: the state of the last column is in slot (n-1) & 1; `info` is carried from slot to slot)
-    const int fused1 = getenv("TIGAR_LU_FUSED") ? atoi(getenv("TIGAR_LU_FUSED")) : 1;
-    if (hipMemcpyAsync(&h1, st + ((fused1 && !blocked_used) ? ((n - 1) & 1) : 0), sizeof(h1), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess) rc = 1;
-    if (!rc && hipStreamSynchronize(g_tg.stream) != hipSuccess) {
-      tg_set_error("tg_lu_solve: %s", hipGetErrorString(hipGetLastError()));
-      rc = 1;
-    }
-    if (!rc) *info = h1.info;
-  }
-  if (!rc && *info == 0) {
-    if (x->d != b->d &&
-        hipMemcpyAsync(x->d, b->d, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, g_tg.stream) != hipSuccess)
-      rc = 1;
-    // 1024 threads x R entries each (measured at cfg4: 256 / 512 threads with more entries each are slower, 148 / 103 ms
-    // against 89 ms)
-    const int nt = 1024;
-    const int rf = (int)tg_cdiv(std::max(kl, 1), nt), rb = (int)tg_cdiv(std::max(kv, 1), nt);
-    if (rb <= 6 && !getenv("TIGAR_LU_SOLVE_GLOBAL")) {
-      typedef void (*fwd_fn)(const double *, int64_t, int64_t, int, int, const int32_t *, double *);
-      typedef void (*bwd_fn)(const double *, int64_t, int64_t, int, double *);
-      const fwd_fn fwd = rf <= 1 ? k_lu_fwd<1, 16, 1024> : rf == 2 ? k_lu_fwd<2, 16, 1024> : rf == 3 ? k_lu_fwd<3, 8, 1024>
-                         : rf == 4 ? k_lu_fwd<4, 8, 1024> : k_lu_fwd<6, 4, 1024>;
-      const bwd_fn bwd = rb <= 1 ? k_lu_bwd<1, 16, 1024> : rb == 2 ? k_lu_bwd<2, 16, 1024> : rb == 3 ? k_lu_bwd<3, 8, 1024>
-                         : rb == 4 ? k_lu_bwd<4, 8, 1024> : k_lu_bwd<6, 4, 1024>;
-      hipLaunchKernelGGL(fwd, dim3(1), dim3(nt), (size_t)(kl + 2 + TG_LU_CH) * sizeof(double), g_tg.stream, (const double *)ab,
-                         ldab, n, kl, kv, (const int32_t *)ipiv, x->d);
-      hipLaunchKernelGGL(bwd, dim3(1), dim3(nt), (size_t)(kv + 2 + TG_LU_CH) * sizeof(double), g_tg.stream, (const double *)ab,
-                         ldab, n, kv, x->d);
-    } else
-      hipLaunchKernelGGL(k_lu_solve_global, dim3(1), dim3(1024), 0, g_tg.stream, ab, ldab, n, kl, kv, ipiv, x->d);
-    if (hipGetLastError() != hipSuccess) rc = 1;
-    if (hipStreamSynchronize(g_tg.stream) != hipSuccess) rc = 1;
-    if (rc) tg_set_error("tg_lu_solve: substitution failed");
-  }
-  tg_dfree(ab);
-  tg_dfree(ipiv);
-  tg_dfree(st);
-  return rc;
+  TG_TRY(tg_band_system("tg_lu_solve", k, b, x, info, &kl, &ku));
+  *info = 0;
+  if (k->nrows == 0) return 0;
+  // a symmetric positive definite system: blocked banded Cholesky (tg_chol.hip); otherwise -- or TIGAR_LU_CHOLESKY=0 -- the LU
+  int done = 0;
+  TG_TRY(tg_chol_try(k, kl, ku, b->d, x->d, &done));
+  if (done) return 0;
+  const lu_knobs e;
+  lu_system s;
+  TG_TRY(lu_load(s, k, kl, ku));
+  TG_TRY(lu_factorise(s, e));
+  TG_TRY(lu_read_info(s, info));
+  return *info == 0 ? lu_substitute(s, e, b->d, x->d) : 0;
 }
