@@ -618,6 +618,31 @@ int tg_quad_load(const tg_patch_t *patch, tg_vec_t f_q, tg_vec_t out);
  * and ge_q (nsd npts) may be null: the term is 0; u_nodal may be null: u_h = 0 */
 int tg_quad_error(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, tg_vec_t ge_q, double *out);
 
+/* ---- rational (NURBS) trial and test functions ----------------------------------------------------------------------
+ * The reference's demos solve in the rational space: u = spline.rationalize(TrialFunction(V)), v likewise
+ * (demos/poisson/poisson-nurbs.py:121-124; ExtractedSpline.project, tIGAr/common.py:1408-1409), i.e. with the basis
+ * psi_a = phi_a / W_h, W_h = cp[nsd] interpolated.  With beta = grad_xi W_h / W_h, grad_xi psi_a = (grad_xi phi_a -
+ * phi_a beta) / W_h: every point coefficient of the entries above carries over -- the tensor of the stiffness / elasticity
+ * integrand acts on (grad_xi phi - phi beta) with the factor 1 / W_h^2, the mass weight takes 1 / W_h^2, the load 1 / W_h
+ * (f_h stays the nodal interpolant of fnodal).  Same pattern, same symmetry, same arguments and row blocks as the twins
+ * without `rational` (row0 = row1 = -1: all rows); the same bits for the same inputs.  With unit weights the results are
+ * those of the twins up to rounding.  3-D, nq = p + 1, p = 2, 3: mass, stiffness and load run sum-factorised; p = 1 and
+ * the elasticity blocks take the plain element kernel, for every shape it takes for the twins (the rational stiffness /
+ * elasticity of a shape whose twin fills the 64 KiB of LDS a launch gets by itself asks for up to 13 KB more).
+ * form: 0 = mass, 1 = laplace (no rational biharmonic form). */
+int tg_assemble_rational_matrix_rows(const tg_patch_t *patch, int form, int64_t row0, int64_t row1, int64_t cp_node0,
+                                     tg_csr_t *out);
+int tg_assemble_rational_elasticity_rows(const tg_patch_t *patch, int fi, int fj, double lambda, double mu, int64_t row0,
+                                         int64_t row1, int64_t cp_node0, tg_csr_t *out);
+int tg_assemble_rational_load_rows(const tg_patch_t *patch, tg_vec_t fnodal, int64_t row0, int64_t row1, int64_t cp_node0,
+                                   tg_vec_t out);
+/* u = u_h / W_h at the points and its Cartesian gradient DF g^-1 (grad_xi u_h - u grad_xi W_h) / W_h */
+int tg_quad_eval_rational(const tg_patch_t *patch, tg_vec_t u_nodal, int with_grad, tg_vec_t val_out, tg_vec_t grad_out);
+/* out[node] = sum_q wdet_q f_q phi_node(xi_q) / W_h(xi_q) */
+int tg_quad_load_rational(const tg_patch_t *patch, tg_vec_t f_q, tg_vec_t out);
+/* the three sums of tg_quad_error with u = u_h / W_h */
+int tg_quad_error_rational(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, tg_vec_t ge_q, double *out);
+
 /* ---- FE operands in the caller's dof order (csrc/tg_feorder.hip, tigar_amd/feorder.py) ----------------------------
  * tg_nodes_locate: recognises the caller's node coordinates x[nrows x d] (host, row-major) as a permutation of the node
  * grid of an FE space of `nfields` scalar fields: field f lives on the tensor grid of the d ascending axes

@@ -1462,8 +1462,9 @@ class ExtractedSpline(object):
     """
     An extracted spline (tIGAr/common.py:667-1433), restricted to the hot path: the
     extraction operators, their application to FE matrices/vectors, and the linear solve.
-    UFL form construction (``grad``, ``dx``, ``rationalize`` ...) needs FEniCS and is not
-    provided here.
+    UFL form construction (``grad``, ``dx`` ...) needs FEniCS and is not provided here; the package's own forms
+    (tigar_amd/forms.py) stand in for it, with ``rational=True`` for the reference's ``spline.rationalize`` of trial and
+    test functions.
 
     With a generator that was given the caller's FE dof order (``fe_nodes=`` / ``setFENodes``) the spline carries
     ``feOrder``: assembled matrices / vectors handed in are taken in the caller's order and FE functions are returned in
@@ -2057,17 +2058,31 @@ class ExtractedSpline(object):
         self._quadrature_scope("quadraturePoints")
         return forms.quadrature_points(self, self.V, nq, "quadraturePoints")
 
-    def evaluateAtQuadrature(self, u, grad=False, nq=None):
+    def rationalize(self, u):
+        """The FE ``Function`` with the nodal values u_i / w_i, w = ``cpFuncs[nsd]`` (tIGAr/common.py:923-932 divides the
+        UFL expression by the weight function; the NURBS demo's "the solution would be u/F3").  This is the NODAL quotient:
+        the interpolant of u_h / W_h on the FE nodes, what a file of nodal values for plotting needs.  The quotient at
+        the quadrature points is ``evaluateAtQuadrature(u, rational=True)``; the norms take ``rational=True``."""
+        uv = _as_device_vector(u)
+        w = self.cpFuncs[self.nsd].vector()
+        if uv.size() != w.size():
+            raise ValueError("rationalize: %d nodal values given, the weight function has %d" % (uv.size(), w.size()))
+        out = Function(self.V)
+        uv.pointwise_divide(w, out=out.vector())
+        return out
+
+    def evaluateAtQuadrature(self, u, grad=False, nq=None, rational=False):
         """u_h at the quadrature points for an FE ``Function`` (or nodal vector) ``u``: a DeviceVector, or with ``grad``
         ``(values, [nsd DeviceVectors])`` with the components of the Cartesian gradient (``spline.grad``: pinv(DF) and
-        the quotient rule of the rational map)."""
+        the quotient rule of the rational map).  ``rational``: u_h / W_h and its gradient -- the reference's
+        ``spline.rationalize(u)`` for the solution of the rational forms."""
         pts = self.quadraturePoints(nq)
         uv = _as_device_vector(u)
         if uv.size() != self.V.dim():
             raise ValueError("evaluateAtQuadrature: %d nodal values given, the space has %d" % (uv.size(), self.V.dim()))
         if not grad:
-            return _dev.quad_eval(pts.verts, pts.p, pts.cp, uv, nq=pts.nq)
-        val, g = _dev.quad_eval(pts.verts, pts.p, pts.cp, uv, grad=True, nq=pts.nq)
+            return _dev.quad_eval(pts.verts, pts.p, pts.cp, uv, nq=pts.nq, rational=rational)
+        val, g = _dev.quad_eval(pts.verts, pts.p, pts.cp, uv, grad=True, nq=pts.nq, rational=rational)
         comps = []
         for i in range(pts.nsd):
             c = DeviceVector(pts.npts, zero=False)
@@ -2081,12 +2096,14 @@ class ExtractedSpline(object):
         pts = self.quadraturePoints(nq)
         return pts.weights.inner(pts.values(f, "integrate"))
 
-    def errorNorm(self, u, exact, kind="L2", exact_grad=None, nq=None, relative=False):
+    def errorNorm(self, u, exact, kind="L2", exact_grad=None, nq=None, relative=False, rational=False):
         """Error of the FE ``Function`` (or nodal vector) ``u`` against ``exact`` in dolfin's ``errornorm`` kinds: "L2",
         "H10" (the seminorm of the Cartesian gradient) or "H1" = sqrt(L2^2 + H10^2).  ``exact`` / ``exact_grad``:
         callables on the physical points [npts, nsd] -> [npts] / [npts, nsd], numbers or point-value arrays;
-        ``exact_grad`` is required for "H10" / "H1".  ``relative``: divided by the same norm of ``exact``.  ``u`` is taken
-        un-rationalised, as the package's forms take their unknown: the polynomial spline pushed forward by the map."""
+        ``exact_grad`` is required for "H10" / "H1".  ``relative``: divided by the same norm of ``exact``.  ``rational=False``:
+        ``u`` is taken un-rationalised (the polynomial spline pushed forward by the map), as the forms without the keyword
+        take their unknown; ``rational=True``: the error of u_h / W_h, the reference's
+        ``(spline.rationalize(u) - soln)**2`` for the solution of the forms with ``rational=True``."""
         if kind not in ("L2", "H10", "H1"):
             raise ValueError("errorNorm: unknown kind %r (L2, H10, H1)" % (kind,))
         if kind != "L2" and exact_grad is None:
@@ -2097,7 +2114,7 @@ class ExtractedSpline(object):
             raise ValueError("errorNorm: %d nodal values given, the space has %d" % (uv.size(), self.V.dim()))
         e = pts.values(exact, "errorNorm: exact")
         ge = pts.vector_values(exact_grad, "errorNorm: exact_grad") if kind != "L2" else None
-        s0, s1, e2 = _dev.quad_error(pts.verts, pts.p, pts.cp, uv, e, ge, nq=pts.nq)
+        s0, s1, e2 = _dev.quad_error(pts.verts, pts.p, pts.cp, uv, e, ge, nq=pts.nq, rational=rational)
         num = {"L2": s0, "H10": s1, "H1": s0 + s1}[kind]
         if not relative:
             return float(numpy.sqrt(num))
@@ -2105,7 +2122,7 @@ class ExtractedSpline(object):
         den = {"L2": e2, "H10": g2, "H1": e2 + g2}[kind]
         return float(numpy.sqrt(num / den))
 
-    def projectDofs(self, toProject, applyBCs=False, lumpMass=False, linearSolver=None, nq=None):
+    def projectDofs(self, toProject, applyBCs=False, lumpMass=False, linearSolver=None, nq=None, rational=False):
         """IGA dofs of the L2 projection of ``toProject`` (given as for ``forms.QuadratureLoadForm``) onto the spline space
         (tIGAr/common.py:1392-1433).  Consistent: ``M^T A_mass M U = M^T b`` with the load and the mass matrix integrated by
         the same ``nq`` points, so that a function of the space is reproduced whatever the quadrature error; solved by
@@ -2114,19 +2131,22 @@ class ExtractedSpline(object):
         quadrature points it is computed from the control functions as they are at the first call -- control functions
         overwritten in place afterwards are not noticed (new vectors are).  ``lumpMass``:
         ``U = M^T b ./ M^T (load of 1)``, the denominator extracted without the boundary conditions as in the reference
-        (common.py:1416-1430); no matrix."""
+        (common.py:1416-1430); no matrix.  ``rational``: the projection in the rational space, as the reference projects
+        (trial and test function rationalised, common.py:1408-1409): rational load, rational mass matrix, the dofs of the
+        homogeneous function u_h = W_h u."""
         from . import forms
         self._quadrature_scope("projectDofs")
         nq = forms._check_nq(nq, int(self.V.grids[0].degree))
-        rhs = self.assembleVector(forms.QuadratureLoadForm(toProject, self, nq), applyBCs=applyBCs)
+        rational = bool(rational)
+        rhs = self.assembleVector(forms.QuadratureLoadForm(toProject, self, nq, rational=rational), applyBCs=applyBCs)
         if lumpMass:
-            den = self.assembleVector(forms.QuadratureLoadForm(1.0, self, nq), applyBCs=False)
+            den = self.assembleVector(forms.QuadratureLoadForm(1.0, self, nq, rational=rational), applyBCs=False)
             return rhs.pointwise_divide(den)
         cache = self.__dict__.setdefault("_projection_mass", {})
         # (the zero dofs are part of the key: a spline whose zeroDofs were changed after a projection gets a new matrix)
-        key = (bool(applyBCs), nq, numpy.asarray(self.zeroDofs).tobytes() if applyBCs else b"")
+        key = (bool(applyBCs), nq, numpy.asarray(self.zeroDofs).tobytes() if applyBCs else b"") + ((True,) if rational else ())
         if key not in cache:
-            cache[key] = self.assembleMatrix(forms.MassForm(geometry=self, nq=nq), applyBCs=applyBCs)
+            cache[key] = self.assembleMatrix(forms.MassForm(geometry=self, nq=nq, rational=rational), applyBCs=applyBCs)
             self._projection_mass_builds = self.__dict__.get("_projection_mass_builds", 0) + 1
         U = DeviceVector(cache[key].shape[0])
         solver = linearSolver if linearSolver is not None else \
@@ -2134,17 +2154,20 @@ class ExtractedSpline(object):
         solver.solve(cache[key], U, rhs)
         return U
 
-    def project(self, toProject, applyBCs=False, rationalize=False, lumpMass=False):
-        """FE ``Function`` M * projectDofs(...) (tIGAr/common.py:1392-1433).  The package takes the unknown un-rationalised
-        (the polynomial spline pushed forward by the rational map); with unit weights ``rationalize`` changes nothing, with
-        others ``rationalize=True`` is refused."""
+    def project(self, toProject, applyBCs=False, rationalize=False, lumpMass=False, rational=False):
+        """FE ``Function`` M * projectDofs(...) (tIGAr/common.py:1392-1433).  ``rational`` selects the space the projection
+        is taken in (see ``projectDofs``); ``project(f, rational=True, rationalize=False)`` is the reference's
+        ``project(f, rationalize=False)``: the homogeneous function u_h, whose quotient by the weight function approximates
+        f.  ``rationalize`` (whether the RETURNED function is divided as well) keeps its meaning: with unit weights it
+        changes nothing, with others ``rationalize=True`` is refused (``spline.rationalize(u)`` gives the nodal quotient)."""
         if rationalize:
             w = self.cpFuncs[self.nsd].vector().get_local()
             if numpy.max(numpy.abs(w - 1.0)) > 64 * numpy.finfo(numpy.float64).eps:      # (unit up to the extraction's rounding)
-                raise NotImplementedError("project(rationalize=True): the control mesh has non-unit weights; the package's "
-                                          "forms and norms take the un-rationalised spline, and dividing by the weight "
-                                          "function is not implemented")
-        U = self.projectDofs(toProject, applyBCs=applyBCs, lumpMass=lumpMass)
+                raise NotImplementedError("project(rationalize=True): the control mesh has non-unit weights, and dividing the "
+                                          "returned FE function by the weight function W_h is not implemented (the quotient "
+                                          "is no function of the FE space); spline.rationalize(u) gives the nodal quotient, "
+                                          "evaluateAtQuadrature(u, rational=True) the quotient at the quadrature points")
+        U = self.projectDofs(toProject, applyBCs=applyBCs, lumpMass=lumpMass, rational=rational)
         u = Function(self.V)
         self.M.mult(U, u.vector())
         return u

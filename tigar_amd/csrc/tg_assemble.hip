@@ -20,6 +20,14 @@
 //               b_k = -sum_r Jinv[k][r] sum_sm g^-1[s][m] H_r,sm   (d_m Jinv = -Jinv (d_m DF) Jinv).  Plain kernel only.
 // nsd >= d is allowed (surfaces in 3-D: Laplace-Beltrami), geometry is rational (quotient rule).
 //
+// RATIONAL trial and test functions (the reference's spline.rationalize(TrialFunction(V)), demos/poisson/poisson-nurbs.py:
+// 121-124): psi_a = phi_a / W_h with W_h the interpolated weight function cp[nsd].  With beta = grad_xi W_h / W_h at a point,
+//     grad_xi psi_a = (grad_xi phi_a - phi_a beta) / W_h,
+// so every form above keeps its point coefficient, scaled: the tensor C of the stiffness / elasticity integrand becomes
+// C / W_h^2 acting on (grad_xi phi - phi beta) on both sides, the mass weight s becomes s / W_h^2, the load s f_h becomes
+// s f_h / W_h (f_h stays the nodal interpolant of the given values).  Pattern and symmetry are those of the plain forms.
+// The biharmonic form has no rational variant.
+//
 // One workgroup per element: local control values and the 1-D Lagrange tables go to LDS, one
 // thread per quadrature point builds w_q sqrt(det g) g^-1, then one thread per (a,b) pair of
 // local nodes sums over the quadrature points and adds into the CSR slot, which is known in closed
@@ -50,6 +58,7 @@ struct tg_asm_args {
   // row blocks (the z-slab pipeline asks for the FE rows of a range of node planes of the LAST direction):
   int64_t row0, row1;          // rows written: [row0, row1); rowptr / val / bout are those of the block (row - row0)
   int64_t cp_node0;            // the control functions (and fnod) hold the nodes from cp_node0 on
+  int rat;                     // rational trial / test functions phi / W_h (forms 0 - 3)
 };
 
 // 1-D pattern of the element-coupling matrix: columns of node r form the contiguous range
@@ -79,6 +88,10 @@ __global__ void __launch_bounds__(256) k_assemble_mapped(tg_asm_args P) {
   double *G = cpl + (P.nsd + 1) * nloc;            // [nqt][9]  w sqrt(det g) g^-1   (biharmonic: g^-1 (6) | b (3))
   double *S = G + (size_t)nqt * 9;                 // [nqt]     w sqrt(det g)   (load: times f_h)
   double *fl = S + nqt;                            // [nloc]    load: nodal values
+  // rational stiffness / elasticity: beta = grad_xi W_h / W_h, [nqt][3], in the place of S and fl, which these forms do not
+  // read (the host sizes the area for it); the rational mass and load need no beta
+  const bool with_beta = P.rat && (P.form == 1 || P.form == 3);
+  double *BT = S;
   const int tid = threadIdx.x, nt = blockDim.x;
   // element: the blockIdx-th of this launch's colour.  Elements of one colour share no node, so they add into the output
   // without atomics; the 2^d colours follow each other in a fixed order: the assembled values are bit-reproducible
@@ -149,7 +162,10 @@ __global__ void __launch_bounds__(256) k_assemble_mapped(tg_asm_args P) {
     tg_sym_inverse(d, g, gi, &det);
     double wq = 1.0;
     for (int k = 0; k < d; k++) wq *= tw[qk[k]] * h[k];
-    const double s = wq * sqrt(fabs(det));
+    double s = wq * sqrt(fabs(det));
+    if (P.rat) s = P.form == 2 ? s / W : s / (W * W);   // psi = phi / W: tensors and mass weight take 1 / W^2, the load 1 / W
+    if (with_beta)
+      for (int k = 0; k < 3; k++) BT[(size_t)q * 3 + k] = k < d ? dN[P.nsd][k] / W : 0.0;
     if (P.form == 3) {
       // Jinv[k][i] = d xi_k / d x_i = (g^-1 DF^T)[k][i]   (nsd == d: checked on the host)
       double ji[3] = {0, 0, 0}, jj[3] = {0, 0, 0};
@@ -189,7 +205,7 @@ __global__ void __launch_bounds__(256) k_assemble_mapped(tg_asm_args P) {
     } else {
       for (int k = 0; k < d * d; k++) G[(size_t)q * 9 + k] = s * gi[k];
     }
-    S[q] = (P.form == 2) ? s * fh : s;
+    if (!with_beta) S[q] = (P.form == 2) ? s * fh : s;
   }
   __syncthreads();
   if (P.form == 2) {
@@ -239,9 +255,16 @@ __global__ void __launch_bounds__(256) k_assemble_mapped(tg_asm_args P) {
                           Gq[6] * (db[0] * lb[1] * lb[2]) + Gq[7] * (lb[0] * db[1] * lb[2]) + Gq[8] * (lb[0] * lb[1] * db[2]);
         acc += S[q] * La * Lb;
       } else {
-        const double ga[3] = {da[0] * la[1] * la[2], la[0] * da[1] * la[2], la[0] * la[1] * da[2]};
-        const double gb[3] = {db[0] * lb[1] * lb[2], lb[0] * db[1] * lb[2], lb[0] * lb[1] * db[2]};
+        double ga[3] = {da[0] * la[1] * la[2], la[0] * da[1] * la[2], la[0] * la[1] * da[2]};
+        double gb[3] = {db[0] * lb[1] * lb[2], lb[0] * db[1] * lb[2], lb[0] * lb[1] * db[2]};
         const double *Gq = G + (size_t)q * 9;
+        if (with_beta) {       // W grad_xi psi = grad_xi phi - phi beta
+          const double pa = la[0] * la[1] * la[2], pb = lb[0] * lb[1] * lb[2];
+          for (int k = 0; k < 3; k++) {
+            ga[k] -= pa * BT[(size_t)q * 3 + k];
+            gb[k] -= pb * BT[(size_t)q * 3 + k];
+          }
+        }
         double t = 0.0;
         for (int k = 0; k < d; k++) {
           double u = 0.0;
@@ -432,7 +455,9 @@ __device__ __forceinline__ void tg_asf_to_points(double *W, const double *TL, co
 #undef TG_B2
 }
 
-// w sqrt(det g) g^-1 (G[0..5]: 00 01 02 11 12 22) and w sqrt(det g) (G[6]) at the lane's quadrature point
+// w sqrt(det g) g^-1 (G[0..5]: 00 01 02 11 12 22) and w sqrt(det g) (G[6]) at the lane's quadrature point.
+// RAT (rational functions phi / W_h): both scaled by 1 / W_h^2, and beta = grad_xi W_h / W_h in G[7..9]
+template <bool RAT = false>
 __device__ __forceinline__ void tg_asf_metric(const double *N, const double (*dN)[3], double w, double *G) {
   const double Wt = N[3];
   double g[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -448,7 +473,14 @@ __device__ __forceinline__ void tg_asf_metric(const double *N, const double (*dN
   }
   double gi[9], det;
   tg_sym_inverse(3, g, gi, &det);
-  const double s = w * sqrt(fabs(det));
+  double s = w * sqrt(fabs(det));
+  if constexpr (RAT) {
+    const double rw = 1.0 / Wt;
+    s *= rw * rw;
+    G[7] = dN[3][0] * rw;
+    G[8] = dN[3][1] * rw;
+    G[9] = dN[3][2] * rw;
+  }
   G[0] = s * gi[0];
   G[1] = s * gi[1];
   G[2] = s * gi[2];
@@ -519,6 +551,16 @@ __device__ __forceinline__ void tg_asf_flux(const double *Gq, double f0, double 
   }
 }
 
+// Rational stiffness: the column's W grad_xi psi_b = grad_xi phi_b - phi_b beta goes through the (scaled) tensor, and the
+// test function's value term -phi_a beta . X joins the d_0 term, whose remaining tables l_1 l_2 it shares: Xv rides on the
+// first contraction with the table l instead of dl
+__device__ __forceinline__ void tg_asf_flux_rat(const double *Gq, double ph, double f0, double f1, double f2, double &X0, double &X1,
+                                                double &X2, double &Xv) {
+  const double b0 = Gq[7], b1 = Gq[8], b2 = Gq[9];
+  tg_asf_flux<1>(Gq, fma(-b0, ph, f0), fma(-b1, ph, f1), fma(-b2, ph, f2), X0, X1, X2);
+  Xv = -fma(b2, X2, fma(b1, X1, b0 * X0));
+}
+
 // 1-D row data of node a of element e (direction with nel elements): vertex shared with a neighbour?, row length,
 // position of the element's first column in the row, entries of the 1-D rows before the node
 template <int P>
@@ -529,11 +571,16 @@ __device__ __forceinline__ void tg_asf_row1d(int a, int e, int nel, bool &v, int
   rps = (int64_t)(P + 1) * (P * e + a) + (a > 0 ? (int64_t)P * e : (e > 0 ? (int64_t)P * (e - 1) : 0));
 }
 
-template <int P1, int EPW, int FORM>
+// FORM: 0 mass, 1 stiffness, 2 elasticity block; + 4 (TG_ASF_RAT): rational functions phi / W_h (mass, stiffness)
+#define TG_ASF_RAT 4
+template <int P1, int EPW, int FORMR>
 __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3(tg_asf_args A) {
+  constexpr int FORM = FORMR & 3;
+  constexpr bool RAT = (FORMR & TG_ASF_RAT) != 0;
+  static_assert(!(RAT && FORM == 2), "rational elasticity blocks go through the plain kernel");
   constexpr int P = P1 - 1, NL = P1 * P1 * P1, LPE = 64 / EPW, PP = P1 * P1;
   constexpr int AH = P1;                 // (rows of the first local index a0 handled at once: all)
-  constexpr int GS = FORM == 2 ? 10 : 8, GN = FORM == 2 ? 9 : 7;     // doubles per quadrature point in LDS: stride, values
+  constexpr int GS = (FORM == 2 || RAT) ? 10 : 8, GN = RAT ? 10 : (FORM == 2 ? 9 : 7);     // doubles per quadrature point in LDS: stride, values
   static_assert(NL <= LPE, "an element needs a lane per local node");
   __shared__ __attribute__((aligned(16))) double s_tab[2 * PP + P1];
   __shared__ __attribute__((aligned(16))) double s_w[TG_ASF_NW][TG_ASF_AREA(4)];
@@ -605,7 +652,7 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3(tg_asf_args A) {
         if constexpr (FORM == 2)
           tg_asf_elast(N, dN, TW[x0] * TW[x1] * TW[x2], A.ei, A.ej, A.lam, A.mu, G);
         else
-          tg_asf_metric(N, dN, TW[x0] * TW[x1] * TW[x2], G);
+          tg_asf_metric<RAT>(N, dN, TW[x0] * TW[x1] * TW[x2], G);
       }
       tg_wave_sync();      // (the area of the nodal values is free: nobody reads it any more)
       if (active) {
@@ -654,11 +701,15 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3(tg_asf_args A) {
               for (int q0 = 0; q0 < P1; q0++) {
                 const double *Gq = Wh + (eb + q0 + P1 * (q1 + P1 * q2)) * GS;
                 const double f0 = d0[q0] * mll, f1 = l0[q0] * mdl, f2 = l0[q0] * mld;
-                double X0, X1, X2;
-                tg_asf_flux<FORM>(Gq, f0, f1, f2, X0, X1, X2);
+                double X0, X1, X2, Xv = 0.0;
+                if constexpr (RAT)
+                  tg_asf_flux_rat(Gq, l0[q0] * mll, f0, f1, f2, X0, X1, X2, Xv);
+                else
+                  tg_asf_flux<FORM>(Gq, f0, f1, f2, X0, X1, X2);
 #pragma unroll
                 for (int a = 0; a < AH; a++) {
                   Y0[a] = fma(UD[a * P1 + q0], X0, Y0[a]);
+                  if constexpr (RAT) Y0[a] = fma(UL[a * P1 + q0], Xv, Y0[a]);
                   Y1[a] = fma(UL[a * P1 + q0], X1, Y1[a]);
                   Y2[a] = fma(UL[a * P1 + q0], X2, Y2[a]);
                 }
@@ -677,7 +728,7 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3(tg_asf_args A) {
               for (int a = 0; a < AH; a++) Y0[a] = 0.0;
 #pragma unroll
               for (int q0 = 0; q0 < P1; q0++) {
-                const double X0 = Wh[(eb + q0 + P1 * (q1 + P1 * q2)) * 8 + 6] * (l0[q0] * mll);
+                const double X0 = Wh[(eb + q0 + P1 * (q1 + P1 * q2)) * GS + 6] * (l0[q0] * mll);
 #pragma unroll
                 for (int a = 0; a < AH; a++) Y0[a] = fma(UL[a * P1 + q0], X0, Y0[a]);
               }
@@ -1005,10 +1056,13 @@ __device__ __forceinline__ void tg_asf_each4(F &&f) {
   f(std::integral_constant<int, 2>{});
   f(std::integral_constant<int, 3>{});
 }
-template <int P1, int FORM, int PRE, int LOOP>
+template <int P1, int FORMR, int PRE, int LOOP>
 __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3_quad(tg_asf_args A) {
+  constexpr int FORM = FORMR & 3;
+  constexpr bool RAT = (FORMR & TG_ASF_RAT) != 0;
+  static_assert(!(RAT && FORM != 1), "the rational variant of this kernel is the stiffness matrix");
   constexpr int P = P1 - 1, NL = P1 * P1 * P1, PP = P1 * P1;
-  constexpr int GS = FORM == 2 ? 10 : 8, GN = FORM == 2 ? 9 : 7;
+  constexpr int GS = (FORM == 2 || RAT) ? 10 : 8, GN = RAT ? 10 : (FORM == 2 ? 9 : 7);
   static_assert(NL == 64 && PP <= 16, "one element per wave, a lane per local node");
   __shared__ __attribute__((aligned(16))) double s_tab[2 * PP + P1];
   __shared__ __attribute__((aligned(16))) double s_w[TG_ASF_NW][TG_ASF_AREA(4)];
@@ -1067,7 +1121,7 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3_quad(tg_asf_args A) {
       if constexpr (FORM == 2)
         tg_asf_elast(N, dN, TW[x0] * TW[x1] * TW[x2], A.ei, A.ej, A.lam, A.mu, G);
       else
-        tg_asf_metric(N, dN, TW[x0] * TW[x1] * TW[x2], G);
+        tg_asf_metric<RAT>(N, dN, TW[x0] * TW[x1] * TW[x2], G);
       tg_wave_sync();
 #pragma unroll
       for (int j = 0; j < GN; j++) W[ln * GS + j] = G[j];
@@ -1162,11 +1216,15 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3_quad(tg_asf_args A) {
           for (int q0 = 0; q0 < P1; q0++) {
             const double *Gq = W + (q0 + P1 * (q1 + P1 * q2)) * GS;
             const double f0 = d0[q0] * mll, f1 = l0[q0] * mdl, f2 = l0[q0] * mld;
-            double X0, X1, X2;
-            tg_asf_flux<FORM>(Gq, f0, f1, f2, X0, X1, X2);
+            double X0, X1, X2, Xv = 0.0;
+            if constexpr (RAT)
+              tg_asf_flux_rat(Gq, l0[q0] * mll, f0, f1, f2, X0, X1, X2, Xv);
+            else
+              tg_asf_flux<FORM>(Gq, f0, f1, f2, X0, X1, X2);
 #pragma unroll
             for (int a = 0; a < P1; a++) {
               Y0[a] = fma(UD[a * P1 + q0], X0, Y0[a]);
+              if constexpr (RAT) Y0[a] = fma(UL[a * P1 + q0], Xv, Y0[a]);
               Y1[a] = fma(UL[a * P1 + q0], X1, Y1[a]);
               Y2[a] = fma(UL[a * P1 + q0], X2, Y2[a]);
             }
@@ -1214,8 +1272,12 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3_quad(tg_asf_args A) {
 
 // L(v) = int f_h v: lane = quadrature point computes w sqrt(det g) f_h, three 1-D contractions back to the nodes (through
 // LDS), each node's value added to the vector (zeroed before; colour by colour, elements of a launch share no node)
-template <int P1, int EPW>
+// EPWR: elements per wave; + 16 (TG_ASF_LOAD_RAT): tested against phi / W_h -- the point value takes 1 / W_h
+#define TG_ASF_LOAD_RAT 16
+template <int P1, int EPWR>
 __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3_load(tg_asf_args A) {
+  constexpr int EPW = EPWR & 15;
+  constexpr bool RAT = (EPWR & TG_ASF_LOAD_RAT) != 0;
   constexpr int P = P1 - 1, NL = P1 * P1 * P1, LPE = 64 / EPW, PP = P1 * P1;
   __shared__ __attribute__((aligned(16))) double s_tab[2 * PP + P1];
   __shared__ __attribute__((aligned(16))) double s_w[TG_ASF_NW][TG_ASF_AREA(5)];
@@ -1249,7 +1311,7 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3_load(tg_asf_args A) {
   tg_wave_sync();
   // s(q) = w sqrt(det g) f_h(q) back to the nodes: lane (a0, q1, q2), then (a0, a1, q2), then (a0, a1, a2)
   double *S0 = W, *S1 = W + 64, *S2 = W + 128;
-  if (active) S0[lane] = G[6] * N[4];
+  if (active) S0[lane] = RAT ? G[6] * N[4] / N[3] : G[6] * N[4];
   tg_wave_sync();
   if (active) {
     double v = 0.0;
@@ -1275,6 +1337,26 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3_load(tg_asf_args A) {
 }
 
 static inline int64_t tg_rps_host(int p, int a) { return (int64_t)(p + 1) * a + (a > 0 ? (int64_t)p * ((a - 1) / p) : 0); }
+
+// The rational forms take the default route of their un-rationalised twin and nothing else (p = 2: the walk; p = 3: the
+// walk for the mass matrix, the groups of four for the stiffness matrix): the routes the switches TIGAR_ASM_WALK / _QUAD /
+// _PRE force are not instantiated for them (the p = 3 stiffness walk runs out of registers as it is).
+template <int P1, int EPW>
+static void tg_asf_launch_rat(int form, const tg_asf_args &A, unsigned nblk) {
+  const dim3 g(nblk), b(64 * TG_ASF_NW);
+  if (form == 2) {
+    hipLaunchKernelGGL((k_asf3_load<P1, EPW | TG_ASF_LOAD_RAT>), g, b, 0, g_tg.stream, A);
+  } else if (form == 0) {
+    hipLaunchKernelGGL((k_asf3<P1, EPW, 0 | TG_ASF_RAT>), g, b, 0, g_tg.stream, A);
+  } else if constexpr (P1 == 4) {
+    if (A.chunk > 1)             // (pieces of several groups: the workgroup loops)
+      hipLaunchKernelGGL((k_asf3_quad<P1, 1 | TG_ASF_RAT, 1, 1>), g, b, 0, g_tg.stream, A);
+    else
+      hipLaunchKernelGGL((k_asf3_quad<P1, 1 | TG_ASF_RAT, 1, 0>), g, b, 0, g_tg.stream, A);
+  } else {
+    hipLaunchKernelGGL((k_asf3<P1, EPW, 1 | TG_ASF_RAT>), g, b, 0, g_tg.stream, A);
+  }
+}
 
 template <int P1, int EPW>
 static void tg_asf_launch(int form, const tg_asf_args &A, unsigned nblk, bool walk, bool line) {
@@ -1402,7 +1484,7 @@ struct tg_elast_block {
 };
 
 static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int64_t row1, int64_t cp_node0, tg_csr_t *mout,
-                              tg_vec_t fnod, tg_vec_t bout, const tg_elast_block *eb = nullptr) {
+                              tg_vec_t fnod, tg_vec_t bout, const tg_elast_block *eb = nullptr, bool rat = false) {
   TG_REQUIRE_INIT();
   TG_REQUIRE(pt && pt->d >= 1 && pt->d <= 3 && pt->p >= 1 && pt->p <= TG_MAX_DEGREE && pt->nsd >= pt->d && pt->nsd <= 3,
              "bad patch description");
@@ -1421,6 +1503,8 @@ static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int6
   A.nsd = pt->nsd;
   A.nq = pt->nq;
   A.form = form;
+  A.rat = rat ? 1 : 0;
+  TG_REQUIRE(!(rat && form == 4), "the biharmonic form has no rational variant");
   if (form == 4) TG_REQUIRE(pt->nsd == pt->d, "the biharmonic form needs as many physical as parametric directions");
   if (form == 3) {
     TG_REQUIRE(eb && pt->nsd == pt->d && eb->i >= 0 && eb->i < pt->d && eb->j >= 0 && eb->j < pt->d,
@@ -1473,6 +1557,8 @@ static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int6
   for (int k = 0; k < d; k++) A.verts[k] = g_asm_cache.verts[k];
   A.tab = g_asm_cache.tab;
   bool fast = d == 3 && pt->nsd == 3 && pt->nq == p1 && p <= 3 && form != 4 && !getenv("TIGAR_ASM_LEGACY");
+  // rational functions: mass, stiffness and load at p = 2, 3; the elasticity blocks and p = 1 take the plain kernel
+  if (rat && (form == 3 || p == 1)) fast = false;
   if (fast) {   // the walk kernel addresses the entries of one plane of rows in 32 bits
     const double t0 = (double)p1 * A.n[0] + (double)p * (A.nel[0] - 1), t1 = (double)p1 * A.n[1] + (double)p * (A.nel[1] - 1);
     if ((2.0 * p + 1.0) * t0 * t1 * 8.0 >= 4294967000.0) fast = false;      // (byte offsets inside one plane of rows)
@@ -1522,8 +1608,21 @@ static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int6
     A.bout = bout->d;
     TG_CHECK_HIP(hipMemsetAsync(bout->d, 0, (size_t)(row1 - row0) * sizeof(double), g_tg.stream));
   }
-  const size_t lds = ((size_t)3 * p1 * pt->nq + pt->nq + (size_t)(pt->nsd + 1) * nloc + (size_t)nqt * 10 + nloc) * sizeof(double);
-  if (!fast && lds > 64 * 1024) {
+  // (rational stiffness / elasticity: beta, 3 values per point, lies over S and fl, which these forms do not use)
+  const size_t tail = (rat && (form == 1 || form == 3)) ? std::max((size_t)nqt + nloc, (size_t)3 * nqt) : (size_t)nqt + nloc;
+  const size_t lds = ((size_t)3 * p1 * pt->nq + pt->nq + (size_t)(pt->nsd + 1) * nloc + (size_t)nqt * 9 + tail) * sizeof(double);
+  // What a launch gets without asking is 64 KiB.  The rational stiffness / elasticity of a shape whose un-rationalised
+  // twin fits into that may need up to 2 nqt doubles more: it asks for the LDS of a compute unit, so that every shape the
+  // twins take is taken (the twins' own limit stays where it was)
+  const size_t lds_twin = ((size_t)3 * p1 * pt->nq + pt->nq + (size_t)(pt->nsd + 1) * nloc + (size_t)nqt * 10 + nloc) * sizeof(double);
+  if (!fast && lds > 64 * 1024 && lds_twin <= 64 * 1024) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_assemble_mapped), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            160 * 1024) != hipSuccess) {
+      if (m) tg_csr_destroy(m);
+      tg_set_error("element data (%zu B): the launch could not get more than 64 KiB of LDS", lds);
+      return 2;
+    }
+  } else if (!fast && lds > 64 * 1024) {
     if (m) tg_csr_destroy(m);
     tg_set_error("element data (%zu B) does not fit in LDS", lds);
     return 2;
@@ -1565,11 +1664,11 @@ static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int6
   // sum-factorised matrix kernel need no colouring in direction 0
   // the walk along direction 0 for every matrix form but the p = 3 stiffness matrix (see k_asf3_elem); TIGAR_ASM_WALK=0/1 forces
   bool walk = fast && form != 2 && !(p == 3 && (form == 1 || form == 3)) && p != 1;
-  if (fast && form != 2 && getenv("TIGAR_ASM_WALK")) walk = atoi(getenv("TIGAR_ASM_WALK")) != 0;
+  if (fast && form != 2 && !rat && getenv("TIGAR_ASM_WALK")) walk = atoi(getenv("TIGAR_ASM_WALK")) != 0;
   // p = 3 stiffness / elasticity: the four waves of a workgroup on four consecutive elements of a line (k_asf3_quad;
   // TIGAR_ASM_QUAD=0: independent elements); direction 0 of a colour then counts GROUPS
   bool line = fast && !walk && p == 3 && (form == 1 || form == 3);
-  if (line && getenv("TIGAR_ASM_QUAD")) line = atoi(getenv("TIGAR_ASM_QUAD")) != 0;
+  if (line && !rat && getenv("TIGAR_ASM_QUAD")) line = atoi(getenv("TIGAR_ASM_QUAD")) != 0;
   if (line) {           // pieces of `chunk` groups of four elements (a function of nothing but the environment: the seams
                         // fix the order of the sums, and row blocks must reproduce the whole matrix bit for bit)
     int chunk = getenv("TIGAR_ASM_QUAD_CHUNK") ? atoi(getenv("TIGAR_ASM_QUAD_CHUNK")) : 8;
@@ -1604,7 +1703,11 @@ static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int6
         F.ngroups = (int64_t)F.ngy * F.ncol[1] * F.ncol[2];
       }
       const unsigned nb = line ? (unsigned)F.ngroups : (unsigned)((F.ngroups + TG_ASF_NW - 1) / TG_ASF_NW);   // (quad: a workgroup per group)
-      if (p == 3)
+      if (rat && p == 3)
+        tg_asf_launch_rat<4, 1>(form, F, nb);
+      else if (rat)
+        tg_asf_launch_rat<3, 2>(form, F, nb);
+      else if (p == 3)
         tg_asf_launch<4, 1>(form, F, nb, walk, line);
       else if (p == 2)
         tg_asf_launch<3, 2>(form, F, nb, walk, false);
@@ -1616,13 +1719,15 @@ static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int6
     }
     bad = hipGetLastError() != hipSuccess;
   }
+  if (timeit && rat && fast && (getenv("TIGAR_ASM_WALK") || getenv("TIGAR_ASM_QUAD") || getenv("TIGAR_ASM_PRE")))
+    fprintf(stderr, "[tg_assemble] rational forms keep their default route: TIGAR_ASM_WALK / _QUAD / _PRE are not applied\n");
   if (timeit) {
     hipEventRecord(g_tg.ev1[0], g_tg.stream);
     hipEventSynchronize(g_tg.ev1[0]);
     float ms = 0.f;
     hipEventElapsedTime(&ms, g_tg.ev0[0], g_tg.ev1[0]);
-    fprintf(stderr, "[tg_assemble] form %d rows [%lld, %lld): element kernels %.3f ms (%s)\n", form, (long long)row0, (long long)row1,
-            ms, fast ? "sum-factorised" : "plain");
+    fprintf(stderr, "[tg_assemble] form %d%s rows [%lld, %lld): element kernels %.3f ms (%s)\n", form, rat ? " rational" : "",
+            (long long)row0, (long long)row1, ms, fast ? "sum-factorised" : "plain");
   }
   if (bad) {
     if (m) tg_csr_destroy(m);
@@ -1664,4 +1769,23 @@ extern "C" int tg_assemble_mapped_elasticity_rows(const tg_patch_t *patch, int f
 extern "C" int tg_assemble_mapped_load_rows(const tg_patch_t *patch, tg_vec_t fnodal, int64_t row0, int64_t row1,
                                             int64_t cp_node0, tg_vec_t out) {
   return tg_assemble_common(patch, 2, row0, row1, cp_node0, nullptr, fnodal, out);
+}
+
+// ---- rational trial and test functions phi / W_h: the same host driver with the flag
+extern "C" int tg_assemble_rational_matrix_rows(const tg_patch_t *patch, int form, int64_t row0, int64_t row1, int64_t cp_node0,
+                                                tg_csr_t *out) {
+  TG_REQUIRE(out && (form == 0 || form == 1), "form: 0 = mass, 1 = laplace");
+  return tg_assemble_common(patch, form, row0, row1, cp_node0, out, nullptr, nullptr, nullptr, true);
+}
+
+extern "C" int tg_assemble_rational_elasticity_rows(const tg_patch_t *patch, int fi, int fj, double lambda, double mu, int64_t row0,
+                                                    int64_t row1, int64_t cp_node0, tg_csr_t *out) {
+  TG_REQUIRE(out, "null output");
+  const tg_elast_block eb = {fi, fj, lambda, mu};
+  return tg_assemble_common(patch, 3, row0, row1, cp_node0, out, nullptr, nullptr, &eb, true);
+}
+
+extern "C" int tg_assemble_rational_load_rows(const tg_patch_t *patch, tg_vec_t fnodal, int64_t row0, int64_t row1,
+                                              int64_t cp_node0, tg_vec_t out) {
+  return tg_assemble_common(patch, 2, row0, row1, cp_node0, nullptr, fnodal, out, nullptr, true);
 }

@@ -21,6 +21,10 @@
 // No floating-point atomics: the load adds element by element, colour by colour (parities of the element index, the
 // colours of k_assemble_mapped in the same order); the error sums are per-element trees, then one fixed pass over the
 // elements.  Same inputs, same bits.
+//
+// RATIONAL functions (u = u_h / W_h, the reference's spline.rationalize(u); tested against phi / W_h): W_h and its gradient
+// are at the points anyway --  u = u_h / W_h,  grad_xi u = (grad_xi u_h - u grad_xi W_h) / W_h  before the Cartesian
+// gradient and the error terms are formed, and the load's point value takes 1 / W_h.
 #include "tg_common.h"
 #include "tg_asm_shared.h"
 #include <cmath>
@@ -64,9 +68,13 @@ __device__ __forceinline__ int64_t tg_pp_node(const tg_pp_args &P, const int *el
   return (int64_t)(el[0] * P.p + a0) + (int64_t)P.n[0] * ((int64_t)(el[1] * P.p + a1) + (int64_t)P.n[1] * (el[2] * P.p + a2));
 }
 
-// MODE 0 points, 1 eval, 2 load, 3 error
-template <int MODE>
+// MODE 0 points, 1 eval, 2 load, 3 error; + 4 (TG_PP_RAT): rational functions (eval, load, error)
+#define TG_PP_RAT 4
+template <int MODER>
 __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
+  constexpr int MODE = MODER & 3;
+  constexpr bool RAT = (MODER & TG_PP_RAT) != 0;
+  static_assert(!(RAT && MODE == 0), "the points do not depend on the function space");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int d = P.d, p1 = P.p + 1, nq = P.nq, nsd = P.nsd, nc = P.nc, epg = P.epg;
   const int nloc = d == 1 ? p1 : (d == 2 ? p1 * p1 : p1 * p1 * p1);
@@ -159,6 +167,13 @@ __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
     }
     // DF[i][k] = d(N_i / W)/dxi_k ; metric g = DF^T DF
     const double W = N[3];
+    if constexpr (RAT && (MODE == 1 || MODE == 3)) {
+      // the difference first, with one rounding (for a function of the space the two products nearly cancel), then the division
+      const double rw = 1.0 / W;
+#pragma unroll
+      for (int k = 0; k < 3; k++) dN[4][k] = fma(dN[4][k], W, -(N[4] * dN[3][k])) * (rw * rw);
+      N[4] *= rw;
+    }
     double G[3][3], DF[3][3] = {{0}};
 #pragma unroll
     for (int c = 0; c < 3; c++) {
@@ -225,7 +240,7 @@ __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
           if (c < nsd) P.grad[(int64_t)c * P.npts + gp] = gu[c];
       }
     } else if (MODE == 2) {
-      oth[(size_t)es * szt + q] = wdet * P.fq[gp];
+      oth[(size_t)es * szt + q] = RAT ? wdet * P.fq[gp] / W : wdet * P.fq[gp];
     } else {
       const double e = P.eq ? P.eq[gp] : 0.0;
       const double du = N[4] - e;
@@ -411,7 +426,7 @@ extern "C" int tg_quad_points(const tg_patch_t *patch, tg_vec_t x_out, tg_vec_t 
   return tg_pp_launch<0>(A, lds);
 }
 
-extern "C" int tg_quad_eval(const tg_patch_t *patch, tg_vec_t u_nodal, int with_grad, tg_vec_t val_out, tg_vec_t grad_out) {
+static int tg_pp_eval(const tg_patch_t *patch, tg_vec_t u_nodal, int with_grad, tg_vec_t val_out, tg_vec_t grad_out, bool rat) {
   tg_pp_args A;
   size_t lds;
   TG_REQUIRE(u_nodal, "tg_quad_eval: no nodal vector");
@@ -423,10 +438,10 @@ extern "C" int tg_quad_eval(const tg_patch_t *patch, tg_vec_t u_nodal, int with_
                (long long)(A.nsd * A.npts));
     A.grad = grad_out->d;
   }
-  return tg_pp_launch<1>(A, lds);
+  return rat ? tg_pp_launch<1 | TG_PP_RAT>(A, lds) : tg_pp_launch<1>(A, lds);
 }
 
-extern "C" int tg_quad_load(const tg_patch_t *patch, tg_vec_t f_q, tg_vec_t out) {
+static int tg_pp_load(const tg_patch_t *patch, tg_vec_t f_q, tg_vec_t out, bool rat) {
   tg_pp_args A;
   size_t lds;
   TG_TRY(tg_pp_setup(patch, 2, nullptr, &A, &lds));
@@ -448,12 +463,15 @@ extern "C" int tg_quad_load(const tg_patch_t *patch, tg_vec_t f_q, tg_vec_t out)
     }
     if (ne == 0) continue;
     A.nelem = ne;
-    TG_TRY(tg_pp_launch<2>(A, lds));
+    if (rat)
+      TG_TRY(tg_pp_launch<2 | TG_PP_RAT>(A, lds));
+    else
+      TG_TRY(tg_pp_launch<2>(A, lds));
   }
   return 0;
 }
 
-extern "C" int tg_quad_error(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, tg_vec_t ge_q, double *out) {
+static int tg_pp_error(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, tg_vec_t ge_q, double *out, bool rat) {
   tg_pp_args A;
   size_t lds;
   TG_REQUIRE(out, "tg_quad_error: no output");
@@ -466,7 +484,10 @@ extern "C" int tg_quad_error(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t
   tg_dbuf<double> part;
   TG_TRY(part.alloc(3 * A.nelem + 3));
   A.part = part.get();
-  TG_TRY(tg_pp_launch<3>(A, lds));
+  if (rat)
+    TG_TRY(tg_pp_launch<3 | TG_PP_RAT>(A, lds));
+  else
+    TG_TRY(tg_pp_launch<3>(A, lds));
   double *sums = part.get() + 3 * A.nelem;
   hipLaunchKernelGGL(k_postproc_fold, dim3(3), dim3(256), 0, g_tg.stream, part.get(), A.nelem, sums);
   TG_LAUNCH_CHECK();
@@ -474,4 +495,20 @@ extern "C" int tg_quad_error(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t
   TG_CHECK_HIP(hipStreamSynchronize(g_tg.stream));
   for (int t = 0; t < 3; t++) out[t] = g_tg.host_pinned[t];
   return 0;
+}
+
+extern "C" int tg_quad_eval(const tg_patch_t *patch, tg_vec_t u_nodal, int with_grad, tg_vec_t val_out, tg_vec_t grad_out) {
+  return tg_pp_eval(patch, u_nodal, with_grad, val_out, grad_out, false);
+}
+extern "C" int tg_quad_load(const tg_patch_t *patch, tg_vec_t f_q, tg_vec_t out) { return tg_pp_load(patch, f_q, out, false); }
+extern "C" int tg_quad_error(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, tg_vec_t ge_q, double *out) {
+  return tg_pp_error(patch, u_nodal, e_q, ge_q, out, false);
+}
+// ---- rational functions u_h / W_h, tested against phi / W_h
+extern "C" int tg_quad_eval_rational(const tg_patch_t *patch, tg_vec_t u_nodal, int with_grad, tg_vec_t val_out, tg_vec_t grad_out) {
+  return tg_pp_eval(patch, u_nodal, with_grad, val_out, grad_out, true);
+}
+extern "C" int tg_quad_load_rational(const tg_patch_t *patch, tg_vec_t f_q, tg_vec_t out) { return tg_pp_load(patch, f_q, out, true); }
+extern "C" int tg_quad_error_rational(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, tg_vec_t ge_q, double *out) {
+  return tg_pp_error(patch, u_nodal, e_q, ge_q, out, true);
 }

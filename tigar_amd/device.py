@@ -1084,15 +1084,23 @@ def _patch(vertices, p, cp, nq):
 _MAPPED_FORMS = {"mass": 0, "laplace": 1, "biharmonic": 4}
 
 
-def assemble_mapped_matrix(vertices, p, cp, form, nq=None, row0=None, row1=None, cp_node0=0):
+def assemble_mapped_matrix(vertices, p, cp, form, nq=None, row0=None, row1=None, cp_node0=0, rational=False):
     """FE mass (form 'mass'), stiffness ('laplace') or element-wise biharmonic ('biharmonic': int lap u lap v, nsd == d)
     matrix of the scalar Q_p space on the tensor
     grid with element ``vertices`` per direction, geometry F = cp[i]/cp[nsd] given by DeviceVectors on
     the FE nodes (dolfin.assemble stand-in, tIGAr/common.py:1206-1220, 917-945).  ``row0, row1``: the rows of
-    whole node planes of the last direction only (global columns), ``cp`` then holding the nodes from ``cp_node0`` on."""
+    whole node planes of the last direction only (global columns), ``cp`` then holding the nodes from ``cp_node0`` on.
+    ``rational``: trial and test functions phi / W_h (the reference's ``spline.rationalize``; 'mass' and 'laplace';
+    ``tg_assemble_rational_matrix_rows``)."""
     pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
     h = handle()
-    if row0 is None and row1 is None and not cp_node0:
+    if rational:
+        if form not in ("mass", "laplace"):
+            raise ValueError("assemble_mapped_matrix: the %r form has no rational variant" % (form,))
+        r0, r1 = (-1, -1) if (row0 is None and row1 is None) else (int(row0), int(row1))
+        check(_lib.lib().tg_assemble_rational_matrix_rows(C.byref(pt), _MAPPED_FORMS[form], r0, r1, int(cp_node0),
+                                                          C.byref(h)), "tg_assemble_rational_matrix_rows")
+    elif row0 is None and row1 is None and not cp_node0:
         check(_lib.lib().tg_assemble_mapped_matrix(C.byref(pt), _MAPPED_FORMS[form], C.byref(h)),
               "tg_assemble_mapped_matrix")
     else:
@@ -1101,21 +1109,31 @@ def assemble_mapped_matrix(vertices, p, cp, form, nq=None, row0=None, row1=None,
     return DeviceCSR(h)
 
 
-def assemble_mapped_elasticity_block(vertices, p, cp, i, j, lmbda, mu, nq=None, row0=None, row1=None, cp_node0=0):
+def assemble_mapped_elasticity_block(vertices, p, cp, i, j, lmbda, mu, nq=None, row0=None, row1=None, cp_node0=0,
+                                     rational=False):
     """Block (i, j) (test component i, trial component j) of a(u,v) = int lambda div u div v + 2 mu eps(u):eps(v) dx on the
-    mapped patch (nsd == d), rows / window as ``assemble_mapped_matrix`` (``tg_assemble_mapped_elasticity_rows``)."""
+    mapped patch (nsd == d), rows / window as ``assemble_mapped_matrix`` (``tg_assemble_mapped_elasticity_rows``;
+    ``rational``: component functions phi / W_h, ``tg_assemble_rational_elasticity_rows``)."""
     pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
     h = handle()
     r0, r1 = (-1, -1) if (row0 is None and row1 is None) else (int(row0), int(row1))
-    check(_lib.lib().tg_assemble_mapped_elasticity_rows(C.byref(pt), int(i), int(j), float(lmbda), float(mu), r0, r1,
-                                                        int(cp_node0), C.byref(h)), "tg_assemble_mapped_elasticity_rows")
+    name = "tg_assemble_rational_elasticity_rows" if rational else "tg_assemble_mapped_elasticity_rows"
+    check(getattr(_lib.lib(), name)(C.byref(pt), int(i), int(j), float(lmbda), float(mu), r0, r1, int(cp_node0),
+                                    C.byref(h)), name)
     return DeviceCSR(h)
 
 
-def assemble_mapped_load(vertices, p, cp, fnodal, nq=None, row0=None, row1=None, cp_node0=0):
-    """L(v) = int f_h v dx with f_h the nodal interpolant of the DeviceVector ``fnodal`` (on the nodes of ``cp``)."""
+def assemble_mapped_load(vertices, p, cp, fnodal, nq=None, row0=None, row1=None, cp_node0=0, rational=False):
+    """L(v) = int f_h v dx with f_h the nodal interpolant of the DeviceVector ``fnodal`` (on the nodes of ``cp``);
+    ``rational``: tested against phi / W_h (``tg_assemble_rational_load_rows``)."""
     pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
-    if row0 is None and row1 is None and not cp_node0:
+    if rational:
+        whole = row0 is None and row1 is None
+        out = DeviceVector(n=fnodal.size() if whole else int(row1) - int(row0))
+        check(_lib.lib().tg_assemble_rational_load_rows(C.byref(pt), fnodal._h, -1 if whole else int(row0),
+                                                        -1 if whole else int(row1), int(cp_node0), out._h),
+              "tg_assemble_rational_load_rows")
+    elif row0 is None and row1 is None and not cp_node0:
         out = DeviceVector(n=fnodal.size())
         check(_lib.lib().tg_assemble_mapped_load(C.byref(pt), fnodal._h, out._h), "tg_assemble_mapped_load")
     else:
@@ -1152,33 +1170,39 @@ def quad_points(vertices, p, cp, nq=None):
     return x, w
 
 
-def quad_eval(vertices, p, cp, u, grad=False, nq=None):
+def quad_eval(vertices, p, cp, u, grad=False, nq=None, rational=False):
     """u_h at the Gauss points for the nodal DeviceVector ``u``; with ``grad`` also the Cartesian gradient (nsd * npts
-    values, component-major): returns ``values`` or ``(values, gradient)`` (``tg_quad_eval``)."""
+    values, component-major): returns ``values`` or ``(values, gradient)`` (``tg_quad_eval``).  ``rational``: u_h / W_h and
+    its gradient (``tg_quad_eval_rational``)."""
     nq = p + 1 if nq is None else nq
     pt, keep = _patch(vertices, p, cp, nq)
     npts = quad_count(vertices, nq)
     val = DeviceVector(npts, zero=False)
     g = DeviceVector((len(cp) - 1) * npts, zero=False) if grad else None
-    check(_lib.lib().tg_quad_eval(C.byref(pt), u._h, 1 if grad else 0, val._h, g._h if grad else None), "tg_quad_eval")
+    name = "tg_quad_eval_rational" if rational else "tg_quad_eval"
+    check(getattr(_lib.lib(), name)(C.byref(pt), u._h, 1 if grad else 0, val._h, g._h if grad else None), name)
     return (val, g) if grad else val
 
 
-def quad_load(vertices, p, cp, fq, nq=None):
-    """L(v) = sum_q wdet_q f_q v(xi_q) for the DeviceVector ``fq`` of point values (``tg_quad_load``)."""
+def quad_load(vertices, p, cp, fq, nq=None, rational=False):
+    """L(v) = sum_q wdet_q f_q v(xi_q) for the DeviceVector ``fq`` of point values (``tg_quad_load``); ``rational``: v the
+    functions phi / W_h (``tg_quad_load_rational``)."""
     pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
     out = DeviceVector(n=cp[0].size(), zero=False)          # (the entry zeroes it before the colours add)
-    check(_lib.lib().tg_quad_load(C.byref(pt), fq._h, out._h), "tg_quad_load")
+    name = "tg_quad_load_rational" if rational else "tg_quad_load"
+    check(getattr(_lib.lib(), name)(C.byref(pt), fq._h, out._h), name)
     return out
 
 
-def quad_error(vertices, p, cp, u=None, e=None, ge=None, nq=None):
+def quad_error(vertices, p, cp, u=None, e=None, ge=None, nq=None, rational=False):
     """(sum wdet (u_h - e)^2, sum wdet |grad u_h - ge|^2, sum wdet e^2) with ``u`` a nodal DeviceVector, ``e`` / ``ge``
-    point values (npts / nsd * npts, component-major); any of the three may be None and counts as 0 (``tg_quad_error``)."""
+    point values (npts / nsd * npts, component-major); any of the three may be None and counts as 0 (``tg_quad_error``).
+    ``rational``: u_h / W_h in the place of u_h (``tg_quad_error_rational``)."""
     pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
     out = np.zeros(3)
-    check(_lib.lib().tg_quad_error(C.byref(pt), u._h if u is not None else None, e._h if e is not None else None,
-                                   ge._h if ge is not None else None, _p(out, c_f64p)), "tg_quad_error")
+    name = "tg_quad_error_rational" if rational else "tg_quad_error"
+    check(getattr(_lib.lib(), name)(C.byref(pt), u._h if u is not None else None, e._h if e is not None else None,
+                                    ge._h if ge is not None else None, _p(out, c_f64p)), name)
     return float(out[0]), float(out[1]), float(out[2])
 
 

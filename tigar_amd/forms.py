@@ -180,12 +180,19 @@ def _control_window(geometry, plane, fa, fb):
     return gen.controlFunctionWindow(fa, fb), fa * plane
 
 
-def _mapped(geometry, V, form, row0=None, row1=None, grid=None, block=None, nq=None):
+def _need_geometry(who, geometry, rational):
+    if rational and geometry is None:
+        raise ValueError("%s: rational=True divides by the weight function of a mapped patch (geometry=...)" % who)
+    return bool(rational)
+
+
+def _mapped(geometry, V, form, row0=None, row1=None, grid=None, block=None, nq=None, rational=False):
     """dolfin.assemble stand-in on a mapped patch: ``geometry`` is a generator / ExtractedSpline
     whose ``cpFuncs`` (nsd+1 homogeneous control functions on the FE nodes of ``V_control``) define
     F = cpFuncs[i]/cpFuncs[nsd] (tIGAr/common.py:917-921); metric-based measure and gradient.  ``row0, row1``: the FE
     rows of a block only (global columns), as the z-slab pipeline asks for them.  ``form`` "elasticity": ``block`` =
-    (i, j, lambda, mu), ``grid`` the node grid the fields share."""
+    (i, j, lambda, mu), ``grid`` the node grid the fields share.  ``rational``: trial and test functions phi / W_h, W_h
+    the weight function ``cpFuncs[nsd]`` -- the reference's ``spline.rationalize(TrialFunction(V))``."""
     g = _single_grid(V) if grid is None else grid
     gc = _single_grid(geometry.V_control)
     if gc.shape() != g.shape():
@@ -197,8 +204,9 @@ def _mapped(geometry, V, form, row0=None, row1=None, grid=None, block=None, nq=N
         if form == "elasticity":
             if len(cp) - 1 != g.dim():
                 raise ValueError("the elasticity form needs as many physical as parametric directions")
-            return _dev.assemble_mapped_elasticity_block(verts, g.degree, cp, block[0], block[1], block[2], block[3], **rows)
-        return _dev.assemble_mapped_matrix(verts, g.degree, cp, form, nq=nq, **rows)
+            return _dev.assemble_mapped_elasticity_block(verts, g.degree, cp, block[0], block[1], block[2], block[3],
+                                                         rational=rational, **rows)
+        return _dev.assemble_mapped_matrix(verts, g.degree, cp, form, nq=nq, rational=rational, **rows)
 
     row0, row1 = (0 if row0 is None else int(row0)), (n if row1 is None else int(row1))       # (either may be left out)
     if (row0, row1) == (0, n):
@@ -217,12 +225,16 @@ def _mapped(geometry, V, form, row0=None, row1=None, grid=None, block=None, nq=N
 class LaplaceForm(object):
     """a(u,v) = int grad u . grad v: on the parametric box (Kronecker sum of 1-D factors), or --
     with ``geometry`` (a generator or ExtractedSpline) -- in physical space on the mapped patch,
-    grad and dx as ``spline.grad`` / ``spline.dx`` (tIGAr/common.py:917-945)."""
+    grad and dx as ``spline.grad`` / ``spline.dx`` (tIGAr/common.py:917-945).  ``rational`` (mapped patch only): trial
+    and test functions divided by the weight function, ``spline.rationalize(TrialFunction(V))`` of the reference's NURBS
+    demos (demos/poisson/poisson-nurbs.py:121-124); the unknown's nodal values are then those of the homogeneous
+    function u_h = W_h u."""
 
-    def __init__(self, geometry=None):
+    def __init__(self, geometry=None, rational=False):
         # a(u, v) = a(v, u) for THIS class; a subclass that adds terms says so itself (ADVICE r5: not inherited)
         self.symmetric = type(self) is LaplaceForm
         self.geometry = geometry
+        self.rational = _need_geometry("LaplaceForm", geometry, rational)
 
     def factors(self, V):
         def build():
@@ -234,7 +246,7 @@ class LaplaceForm(object):
 
     def assemble_matrix(self, V, row0=None, row1=None):
         if self.geometry is not None:
-            return _mapped(self.geometry, V, "laplace", row0, row1)
+            return _mapped(self.geometry, V, "laplace", row0, row1, rational=self.rational)
         return _dev.kron_sum_csr(self.factors(V), row0, row1)
 
 
@@ -249,13 +261,15 @@ class ElasticityForm(object):
     With ``geometry`` (a generator or ExtractedSpline with nsd == d): in physical space on the mapped patch --
     ``inner(sigma(u), spline.sym(spline.grad(v)))*spline.dx`` with the Cartesian derivatives of ``spline.grad`` /
     ``spline.div`` (tIGAr/common.py:1022-1040, calculusUtils.py:255-276); each block from the element kernels of
-    csrc/tg_assemble.hip (no Kronecker factors: the PtAP takes the assembled blocks)."""
+    csrc/tg_assemble.hip (no Kronecker factors: the PtAP takes the assembled blocks).  ``rational``: every component
+    function divided by the weight function (see LaplaceForm); the space then holds the rigid motions."""
 
-    def __init__(self, lmbda=1.0, mu=1.0, geometry=None):
+    def __init__(self, lmbda=1.0, mu=1.0, geometry=None, rational=False):
         # a(u, v) = a(v, u) for THIS class; a subclass that adds terms says so itself (ADVICE r5: not inherited)
         self.symmetric = type(self) is ElasticityForm
         self.lmbda, self.mu = float(lmbda), float(mu)
         self.geometry = geometry
+        self.rational = _need_geometry("ElasticityForm", geometry, rational)
 
     def _grid(self, V):
         g = V.grids[0]
@@ -295,7 +309,8 @@ class ElasticityForm(object):
     def assemble_block(self, V, i, j, row0=None, row1=None):
         """rows [row0, row1) of block (i, j) (fields i, j; columns of one field)"""
         if self.geometry is not None:
-            return _mapped(self.geometry, V, "elasticity", row0, row1, grid=self._grid(V), block=(i, j, self.lmbda, self.mu))
+            return _mapped(self.geometry, V, "elasticity", row0, row1, grid=self._grid(V), block=(i, j, self.lmbda, self.mu),
+                           rational=self.rational)
         return _dev.kron_sum_csr(self.block_factors(V)[i][j], row0, row1)
 
     def assemble_matrix(self, V, row0=None, row1=None):
@@ -311,12 +326,13 @@ class ElasticityForm(object):
 
 class MassForm(object):
     """a(u,v) = int u v (``geometry``: see LaplaceForm; ``nq``: Gauss points per direction on the mapped patch, p + 1
-    when None)."""
+    when None; ``rational``: see LaplaceForm)."""
 
-    def __init__(self, geometry=None, nq=None):
+    def __init__(self, geometry=None, nq=None, rational=False):
         # a(u, v) = a(v, u) for THIS class; a subclass that adds terms says so itself (ADVICE r5: not inherited)
         self.symmetric = type(self) is MassForm
         self.geometry = geometry
+        self.rational = _need_geometry("MassForm", geometry, rational)
         if nq is not None and geometry is None:
             raise ValueError("MassForm: nq belongs to a mapped patch (geometry=...)")
         self.nq = nq
@@ -327,17 +343,19 @@ class MassForm(object):
 
     def assemble_matrix(self, V, row0=None, row1=None):
         if self.geometry is not None:
-            return _mapped(self.geometry, V, "mass", row0, row1, nq=self.nq)
+            return _mapped(self.geometry, V, "mass", row0, row1, nq=self.nq, rational=self.rational)
         return _dev.kron_sum_csr(self.factors(V), row0, row1)
 
 
 class NodalLoadForm(object):
     """L(v) = int f_h v dx on the mapped patch, f_h = nodal interpolant of ``f``: a callable evaluated at the
     physical node positions x = F(node) (array of shape [nnodes, nsd] -> values), a number (constant load), or the node
-    values themselves (array / DeviceVector on all FE nodes)."""
+    values themselves (array / DeviceVector on all FE nodes).  ``rational``: v the test functions phi / W_h (f_h stays
+    the interpolant of the node values)."""
 
-    def __init__(self, f, geometry):
+    def __init__(self, f, geometry, rational=False):
         self.f, self.geometry = f, geometry
+        self.rational = _need_geometry("NodalLoadForm", geometry, rational)
 
     def _nodal_values(self, cp, node0, n_nodes):
         """f on the nodes [node0, node0 + n_nodes) that the control functions ``cp`` are given on"""
@@ -373,7 +391,7 @@ class NodalLoadForm(object):
         if (row0, row1) == (0, n):
             cp, node0 = _control_window(self.geometry, 1, 0, g.shape()[-1])
             if node0 == 0 and all(v.size() == n for v in cp):
-                return _dev.assemble_mapped_load(verts, g.degree, cp, self._nodal_values(cp, 0, n))
+                return _dev.assemble_mapped_load(verts, g.degree, cp, self._nodal_values(cp, 0, n), rational=self.rational)
             row0, row1 = 0, n
         plane, za, zb, fa, fb = _plane_window(g, row0, row1)
         cp, node0 = _control_window(self.geometry, plane, fa, fb)
@@ -381,7 +399,8 @@ class NodalLoadForm(object):
             fn = self._nodal_values(cp, 0, n)
         else:
             fn = self._nodal_values(cp, node0, cp[0].size())
-        b = _dev.assemble_mapped_load(verts, g.degree, cp, fn, row0=za * plane, row1=zb * plane, cp_node0=node0)
+        b = _dev.assemble_mapped_load(verts, g.degree, cp, fn, row0=za * plane, row1=zb * plane, cp_node0=node0,
+                                      rational=self.rational)
         if (za * plane, zb * plane) != (int(row0), int(row1)):
             piece = _dev.DeviceVector(int(row1) - int(row0), zero=False)
             _dev.vec_copy_range(piece, 0, b, int(row0) - za * plane, int(row1) - int(row0))
@@ -482,10 +501,13 @@ class QuadratureLoadForm(object):
     """L(v) = sum_q wdet_q f(x_q) v(xi_q) on the mapped patch: the load of ``f`` itself, not of its nodal interpolant
     (``NodalLoadForm``).  ``f``: a callable on the physical points ``[npts, nsd] -> [npts]`` (evaluated on the host once
     per geometry), a number, the ``npts`` point values (array / DeviceVector, numbered as ``QuadraturePoints``), or a
-    ``Function`` on the space.  ``nq`` Gauss points per direction (p + 1 when None)."""
+    ``Function`` on the space.  ``nq`` Gauss points per direction (p + 1 when None).  ``rational``: v the test functions
+    phi / W_h; a ``Function`` given as ``f`` is still read un-rationalised -- hand in
+    ``spline.evaluateAtQuadrature(f, rational=True)`` for its rational values."""
 
-    def __init__(self, f, geometry, nq=None):
+    def __init__(self, f, geometry, nq=None, rational=False):
         self.f, self.geometry, self.nq = f, geometry, nq
+        self.rational = _need_geometry("QuadratureLoadForm", geometry, rational)
 
     def point_values(self, V):
         pts = quadrature_points(self.geometry, V, self.nq, "QuadratureLoadForm")
@@ -503,7 +525,7 @@ class QuadratureLoadForm(object):
             raise NotImplementedError("QuadratureLoadForm: row blocks (several ranks, streamed operands) are not supported; "
                                       "the point values are numbered over the whole patch")
         pts, fq = self.point_values(V)
-        return _dev.quad_load(pts.verts, pts.p, pts.cp, fq, nq=pts.nq)
+        return _dev.quad_load(pts.verts, pts.p, pts.cp, fq, nq=pts.nq, rational=self.rational)
 
 
 class SeparableLoadForm(object):

@@ -274,7 +274,8 @@ class LinearTransientProblem(object):
 
     ``load``: None or a callable ``t -> form`` (anything ``spline.assembleVector`` takes) or ``t -> DeviceVector`` of IGA
     dofs.  ``x0`` / ``xdot0``: IGA-dof ``DeviceVector`` s, FE ``Function`` s (brought over by ``spline.FEtoIGA``) or callables
-    on the physical points ``[npts, nsd] -> [npts]`` (L2-projected by ``spline.projectDofs(.., applyBCs=True)``); None = 0,
+    on the physical points ``[npts, nsd] -> [npts]`` (L2-projected by ``spline.projectDofs(.., applyBCs=True,
+    rational=rational)``: ``rational=True`` with stiffness and mass forms of the rational space); None = 0,
     except ``xdot0=None`` of a first-order generalized-alpha problem: solved from ``M xdot0 = f(t0) - K x0``.  For order 2
     the initial acceleration is solved from ``M a0 = f(t0) - C xdot0 - K x0``.
 
@@ -296,7 +297,7 @@ class LinearTransientProblem(object):
     timing = True
 
     def __init__(self, spline, stiffness, mass, order=2, scheme="generalized_alpha", RHO_INF=0.5, DELTA_T=None, damping=None,
-                 load=None, x0=None, xdot0=None, t=0.0):
+                 load=None, x0=None, xdot0=None, t=0.0, rational=False):
         if order not in (1, 2):
             raise ValueError("LinearTransientProblem: order must be 1 or 2, not %r" % (order,))
         if scheme not in ("generalized_alpha", "backward_euler"):
@@ -312,6 +313,7 @@ class LinearTransientProblem(object):
         if spline._caller_ordered():
             raise NotImplementedError("LinearTransientProblem: a spline with the caller's FE dof order (feOrder) is not supported")
         self.spline, self.order, self.scheme, self.load = spline, int(order), scheme, load
+        self.rational = bool(rational)        # the space callable initial data are projected in (that of the forms handed in)
         self.DELTA_T = dt = float(DELTA_T)
         self.damping = (0.0, 0.0) if damping is None else (float(damping[0]), float(damping[1]))
         self.K = spline.assembleMatrix(stiffness)
@@ -393,7 +395,7 @@ class LinearTransientProblem(object):
         if hasattr(v, "vector"):
             v = self.spline.FEtoIGA(v)
         elif callable(v):
-            v = self.spline.projectDofs(v, applyBCs=True)     # a function of x: its L2 projection
+            v = self.spline.projectDofs(v, applyBCs=True, rational=self.rational)     # a function of x: its L2 projection
         if not isinstance(v, DeviceVector) or v.size() != self.n:
             raise ValueError("LinearTransientProblem: initial data must be a DeviceVector of %d IGA dofs, an FE Function or a "
                              "callable" % self.n)
