@@ -643,6 +643,45 @@ int tg_quad_load_rational(const tg_patch_t *patch, tg_vec_t f_q, tg_vec_t out);
 /* the three sums of tg_quad_error with u = u_h / W_h */
 int tg_quad_error_rational(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, tg_vec_t ge_q, double *out);
 
+/* ---- boundary integrals on the same patches (csrc/tg_boundary.hip): the boundary measure and the mapped normal of the
+ * reference's ExtractedSpline (spline.ds, spline.n; tIGAr/common.py:931-939, calculusUtils.py:37-52, 71-80).  d = 2, 3,
+ * nsd >= d.  A face is (direction dir, side 0 | 1), numbered as getSideDofs; its parametric normal is N = (2 side - 1) e_dir.
+ * In reference-element coordinates (g_hat = DF^T DF of the element map, no element size appears), at a face Gauss point
+ *   wsurf = w_q sqrt(det g_hat (g_hat^-1)_kk)   (w_q: product of the d-1 tangential Gauss weights; surfaceJacobian times the
+ *                                                face element's parametric area)
+ *   n     = DF g^-1 N / |DF g^-1 N|             (nsd components)
+ *   d_n u = (g^-1 N).grad_xi u / sqrt(N.g^-1 N)
+ *   h_n   = 1 / sqrt((g_hat^-1)_kk)             (thickness of the boundary element normal to the face)
+ * Points are numbered face-element-major: face elements lexicographic in the remaining directions with the lower
+ * direction fastest, the nq^(d-1) points of a face element likewise; npts = nq^(d-1) prod_{j != dir} nel_j.  Arrays with
+ * nsd components per point are component-major.  The control functions are given on all FE nodes.  No floating-point
+ * atomics (colours over the parities of the tangential element indices): the same inputs give the same bits. */
+/* x_q (nsd npts), wsurf_q (npts), n_q (nsd npts), h_n (npts); any output may be null */
+int tg_face_points(const tg_patch_t *patch, int dir, int side, tg_vec_t x_out, tg_vec_t wsurf_out, tg_vec_t normal_out,
+                   tg_vec_t hn_out);
+/* u_h at the face points, its Cartesian gradient (nsd npts) and d_n u_h; grad_out and dn_out may be null */
+int tg_face_eval(const tg_patch_t *patch, int dir, int side, tg_vec_t u_nodal, tg_vec_t val_out, tg_vec_t grad_out,
+                 tg_vec_t dn_out);
+/* out[node] += sum_q wsurf_q (f_q phi_node + fn_q d_n phi_node); either array may be null.  Adds into out: several faces go
+ * into one vector.  f_q alone: Neumann / Robin data; both: the Nitsche right-hand side */
+int tg_face_load(const tg_patch_t *patch, int dir, int side, tg_vec_t f_q, tg_vec_t fn_q, tg_vec_t out);
+/* A_ab = sum_q wsurf_q (a_q phi_a phi_b + b_q phi_a d_n phi_b + c_q d_n phi_a phi_b), each array may be null: an n x n CSR
+ * whose non-empty rows are those of the boundary-layer nodes; pattern = the element coupling restricted to the boundary
+ * layer, in closed form */
+int tg_face_matrix(const tg_patch_t *patch, int dir, int side, tg_vec_t a_q, tg_vec_t b_q, tg_vec_t c_q, tg_csr_t *out);
+/* the same entries times `scale`, added in place into A (rows ascending), which must hold them -- every mapped form above
+ * does: they return the element-coupling pattern.  Columns by search in the sorted row.  The pattern is checked first: if
+ * an entry is missing the call returns 3 and A is unchanged.  A keeps its pattern certificate. */
+int tg_face_matrix_add(const tg_patch_t *patch, int dir, int side, tg_vec_t a_q, tg_vec_t b_q, tg_vec_t c_q, double scale,
+                       tg_csr_t A);
+/* rational twins: u = u_h / W_h, phi -> phi / W_h, grad_xi phi -> (grad_xi phi - phi beta) / W_h */
+int tg_face_eval_rational(const tg_patch_t *patch, int dir, int side, tg_vec_t u_nodal, tg_vec_t val_out, tg_vec_t grad_out,
+                          tg_vec_t dn_out);
+int tg_face_load_rational(const tg_patch_t *patch, int dir, int side, tg_vec_t f_q, tg_vec_t fn_q, tg_vec_t out);
+int tg_face_matrix_rational(const tg_patch_t *patch, int dir, int side, tg_vec_t a_q, tg_vec_t b_q, tg_vec_t c_q, tg_csr_t *out);
+int tg_face_matrix_add_rational(const tg_patch_t *patch, int dir, int side, tg_vec_t a_q, tg_vec_t b_q, tg_vec_t c_q,
+                                double scale, tg_csr_t A);
+
 /* ---- FE operands in the caller's dof order (csrc/tg_feorder.hip, tigar_amd/feorder.py) ----------------------------
  * tg_nodes_locate: recognises the caller's node coordinates x[nrows x d] (host, row-major) as a permutation of the node
  * grid of an FE space of `nfields` scalar fields: field f lives on the tensor grid of the d ascending axes

@@ -232,6 +232,16 @@ PROTOTYPES = {
     "tg_quad_eval_rational": (C.c_int, [C.POINTER(tg_patch_t), handle, C.c_int, handle, handle]),
     "tg_quad_load_rational": (C.c_int, [C.POINTER(tg_patch_t), handle, handle]),
     "tg_quad_error_rational": (C.c_int, [C.POINTER(tg_patch_t), handle, handle, handle, c_f64p]),
+    "tg_face_points": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, handle]),
+    "tg_face_eval": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, handle]),
+    "tg_face_load": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle]),
+    "tg_face_matrix": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, C.POINTER(handle)]),
+    "tg_face_matrix_add": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, C.c_double, handle]),
+    "tg_face_eval_rational": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, handle]),
+    "tg_face_load_rational": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle]),
+    "tg_face_matrix_rational": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, C.POINTER(handle)]),
+    "tg_face_matrix_add_rational": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, C.c_double,
+                                              handle]),
     "tg_comm_unique_id": (C.c_int, [C.c_char_p]),
     "tg_comm_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(handle)]),
     "tg_comm_create2": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(handle)]),

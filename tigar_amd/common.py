@@ -2096,6 +2096,65 @@ class ExtractedSpline(object):
         pts = self.quadraturePoints(nq)
         return pts.weights.inner(pts.values(f, "integrate"))
 
+    # -- boundary integrals (csrc/tg_boundary.hip): the reference's spline.ds and spline.n
+    def boundaryPoints(self, direction, side, nq=None):
+        """The Gauss points of the face (direction, side) -- numbered as ``getSideDofs`` -- as a ``forms.FacePoints``:
+        ``.x`` (host array [npts, nsd], lazy), ``.x_device``, ``.weights`` (the surface weights, ``spline.ds``),
+        ``.normals`` (the unit normal ``spline.n``, nsd * npts values, component-major), ``.h_normal``, ``.npts``, ``.nq``;
+        kept per (face, nq, control-function vectors) like the volume points."""
+        from . import forms
+        self._quadrature_scope("boundaryPoints")
+        return forms.face_points(self, self.V, direction, side, nq, "boundaryPoints")
+
+    def evaluateAtBoundary(self, u, direction, side, grad=False, normal_derivative=False, nq=None, rational=False):
+        """u_h at the points of a face for an FE ``Function`` (or nodal vector): a DeviceVector; with ``grad`` and / or
+        ``normal_derivative`` a tuple ``(values[, [nsd DeviceVectors of the Cartesian gradient]][, d_n u])``.
+        ``rational``: u_h / W_h."""
+        pts = self.boundaryPoints(direction, side, nq)
+        uv = _as_device_vector(u)
+        if uv.size() != self.V.dim():
+            raise ValueError("evaluateAtBoundary: %d nodal values given, the space has %d" % (uv.size(), self.V.dim()))
+        val, g, dn = _dev.face_eval(pts.verts, pts.p, pts.cp, pts.direction, pts.side, uv, grad=grad,
+                                    normal_derivative=normal_derivative, nq=pts.nq, rational=rational)
+        out = [val]
+        if grad:
+            comps = []
+            for i in range(pts.nsd):
+                c = DeviceVector(pts.npts, zero=False)
+                _dev.vec_copy_range(c, 0, g, i * pts.npts, pts.npts)
+                comps.append(c)
+            out.append(comps)
+        if normal_derivative:
+            out.append(dn)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def _boundary_faces(self, faces, who):
+        from . import forms
+        self._quadrature_scope(who)
+        return forms.check_faces(faces, self.V.grids[0].dim(), who, forms._periodic_directions(self))
+
+    def integrateBoundary(self, f, faces=None, nq=None):
+        """sum over the faces of sum_q wsurf_q f(x_q): the integral of ``f`` over (part of) the boundary with
+        ``spline.ds``.  ``f``: a callable on the points (of ``x`` or of ``(x, n)``), a number, a ``Function``, or a list
+        with point values / one of these per face; ``faces=None``: all 2 d faces."""
+        from . import forms
+        faces = self._boundary_faces(faces, "integrateBoundary")
+        total = 0.0
+        for i, (k, s) in enumerate(faces):
+            pts = self.boundaryPoints(k, s, nq)
+            total += pts.weights.inner(forms._face_values(pts, forms._per_face(f, i, len(faces), "integrateBoundary"),
+                                                          "integrateBoundary"))
+        return total
+
+    def boundaryFlux(self, u, faces=None, nq=None, rational=False):
+        """sum over the faces of sum_q wsurf_q d_n u(x_q): the flux of grad u through (part of) the boundary"""
+        faces = self._boundary_faces(faces, "boundaryFlux")
+        total = 0.0
+        for k, s in faces:
+            pts = self.boundaryPoints(k, s, nq)
+            total += pts.weights.inner(self.evaluateAtBoundary(u, k, s, normal_derivative=True, nq=nq, rational=rational)[1])
+        return total
+
     def errorNorm(self, u, exact, kind="L2", exact_grad=None, nq=None, relative=False, rational=False):
         """Error of the FE ``Function`` (or nodal vector) ``u`` against ``exact`` in dolfin's ``errornorm`` kinds: "L2",
         "H10" (the seminorm of the Cartesian gradient) or "H1" = sqrt(L2^2 + H10^2).  ``exact`` / ``exact_grad``:

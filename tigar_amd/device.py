@@ -1206,6 +1206,83 @@ def quad_error(vertices, p, cp, u=None, e=None, ge=None, nq=None, rational=False
     return float(out[0]), float(out[1]), float(out[2])
 
 
+def face_count(vertices, direction, nq):
+    """number of Gauss points of the face (direction, side): nq^(d-1) per face element"""
+    n = 1
+    for k, v in enumerate(vertices):
+        if k != direction:
+            n *= (len(v) - 1) * int(nq)
+    return n
+
+
+def face_points(vertices, p, cp, direction, side, nq=None):
+    """(x, wsurf, normals, h_normal) of the face (direction, side) of the patch (``tg_face_points``): positions and unit
+    normals with nsd * npts values (component-major), the surface weights w_q sqrt(det g_hat (g_hat^-1)_kk) and the
+    thickness of the boundary element normal to the face.  Points are numbered face-element-major, the face elements and
+    the nq^(d-1) points of one lexicographic in the remaining directions with the lower direction fastest."""
+    nq = p + 1 if nq is None else nq
+    pt, keep = _patch(vertices, p, cp, nq)
+    npts, nsd = face_count(vertices, direction, nq), len(cp) - 1
+    x, nrm = DeviceVector(nsd * npts, zero=False), DeviceVector(nsd * npts, zero=False)
+    w, hn = DeviceVector(npts, zero=False), DeviceVector(npts, zero=False)
+    check(_lib.lib().tg_face_points(C.byref(pt), int(direction), int(side), x._h, w._h, nrm._h, hn._h), "tg_face_points")
+    return x, w, nrm, hn
+
+
+def face_eval(vertices, p, cp, direction, side, u, grad=False, normal_derivative=False, nq=None, rational=False):
+    """(values, gradient or None, d_n u or None) of the nodal DeviceVector ``u`` at the points of the face
+    (``tg_face_eval``; ``rational``: u_h / W_h, ``tg_face_eval_rational``)"""
+    nq = p + 1 if nq is None else nq
+    pt, keep = _patch(vertices, p, cp, nq)
+    npts = face_count(vertices, direction, nq)
+    val = DeviceVector(npts, zero=False)
+    g = DeviceVector((len(cp) - 1) * npts, zero=False) if grad else None
+    dn = DeviceVector(npts, zero=False) if normal_derivative else None
+    name = "tg_face_eval_rational" if rational else "tg_face_eval"
+    check(getattr(_lib.lib(), name)(C.byref(pt), int(direction), int(side), u._h, val._h, g._h if grad else None,
+                                    dn._h if normal_derivative else None), name)
+    return val, g, dn
+
+
+def face_load(vertices, p, cp, direction, side, fq, fnq, out, nq=None, rational=False):
+    """out[node] += sum_q wsurf_q (f_q phi_node + fn_q d_n phi_node) for point values ``fq`` / ``fnq`` (either may be
+    None) of the face (``tg_face_load``; ``rational``: phi / W_h, ``tg_face_load_rational``); returns ``out``"""
+    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
+    name = "tg_face_load_rational" if rational else "tg_face_load"
+    check(getattr(_lib.lib(), name)(C.byref(pt), int(direction), int(side), fq._h if fq is not None else None,
+                                    fnq._h if fnq is not None else None, out._h), name)
+    return out
+
+
+def _h_or_none(v):
+    return v._h if v is not None else None
+
+
+def face_matrix(vertices, p, cp, direction, side, a=None, b=None, c=None, nq=None, rational=False):
+    """A_ab = sum_q wsurf_q (a_q phi_a phi_b + b_q phi_a d_n phi_b + c_q d_n phi_a phi_b) of the face as a DeviceCSR on
+    all FE nodes, pattern = the element coupling restricted to the boundary layer (``tg_face_matrix``)"""
+    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
+    h = handle()
+    name = "tg_face_matrix_rational" if rational else "tg_face_matrix"
+    check(getattr(_lib.lib(), name)(C.byref(pt), int(direction), int(side), _h_or_none(a), _h_or_none(b), _h_or_none(c),
+                                    C.byref(h)), name)
+    return DeviceCSR(h)
+
+
+def face_matrix_add(A, vertices, p, cp, direction, side, a=None, b=None, c=None, scale=1.0, nq=None, rational=False):
+    """the entries of ``face_matrix`` times ``scale`` added in place into ``A`` (``tg_face_matrix_add``).  Returns False,
+    with ``A`` unchanged, when the pattern of ``A`` lacks one of them."""
+    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
+    name = "tg_face_matrix_add_rational" if rational else "tg_face_matrix_add"
+    rc = getattr(_lib.lib(), name)(C.byref(pt), int(direction), int(side), _h_or_none(a), _h_or_none(b), _h_or_none(c),
+                                   float(scale), A._h)
+    if rc == 3:
+        return False
+    check(rc, name)
+    A._T = None
+    return True
+
+
 def tensor_apply_1d(x, dims_in, k, F, col_shift=0, out=None):
     """Apply the scipy CSR 1-D factor ``F`` (rows = output indices of direction k, columns = input
     indices + col_shift) along direction ``k`` of the tensor-indexed DeviceVector ``x`` (direction 0

@@ -646,3 +646,406 @@ class _SemilinearTangent(object):
         if row0 is not None and (row0, row1) != (0, K.shape[0]):
             K, Mm = self.res._row_blocks(V, row0, row1)
         return K.combine(1.0, Mm, 1.0, self.res.dg(uv))
+
+
+# ---- boundary integrals on a mapped patch (csrc/tg_boundary.hip): spline.ds and spline.n of the reference -----------------
+def _periodic_directions(geometry):
+    """directions whose knot vector is not open (the faces there are no boundary), as far as the geometry tells"""
+    gen = getattr(geometry, "_generator", geometry)
+    mesh = getattr(gen, "controlMesh", None)
+    try:
+        splines = mesh.getScalarSpline().splines
+    except Exception:
+        return set()
+    out = set()
+    for k, s in enumerate(splines):
+        kn, p = numpy.asarray(getattr(s, "knots", ()), dtype=float), int(getattr(s, "p", 0))
+        if kn.size and not (numpy.all(kn[:p + 1] == kn[0]) and numpy.all(kn[-(p + 1):] == kn[-1])):
+            out.add(k)
+    return out
+
+
+def check_faces(faces, d, who, periodic=()):
+    """the faces as a list of (direction, side): None = all 2 d faces of a d-dimensional patch, one pair, or a sequence of
+    pairs; ValueError for anything else, for a face outside 0 <= direction < d, side in {0, 1}, and for a face of a
+    periodic direction"""
+    if faces is None:
+        faces = [(k, s) for k in range(d) if k not in periodic for s in (0, 1)]
+        if not faces:
+            raise ValueError("%s: every direction of the patch is periodic; it has no boundary" % who)
+        return faces
+    try:
+        if len(faces) == 2 and all(numpy.ndim(v) == 0 for v in faces):
+            faces = [tuple(faces)]
+        faces = [tuple(f) for f in faces]
+    except TypeError:
+        raise ValueError("%s: faces = %r: (direction, side) pairs expected" % (who, faces))
+    if not faces:
+        raise ValueError("%s: no face given" % who)
+    for f in faces:
+        if len(f) != 2 or any(isinstance(v, bool) or int(v) != v for v in f):
+            raise ValueError("%s: face %r: a (direction, side) pair of integers expected" % (who, f))
+        if not (0 <= f[0] < d and f[1] in (0, 1)):
+            raise ValueError("%s: face %r: 0 <= direction < %d and side 0 or 1" % (who, f, d))
+        if f[0] in periodic:
+            raise ValueError("%s: face %r: direction %d of the patch is periodic; it has no boundary there" % (who, f, f[0]))
+    if len(set(faces)) != len(faces):
+        raise ValueError("%s: a face is listed twice" % who)
+    return [(int(k), int(s)) for k, s in faces]
+
+
+def _need_boundary_geometry(who, geometry):
+    if geometry is None:
+        raise ValueError("%s: boundary integrals are taken on a mapped patch (geometry=...)" % who)
+
+
+def _face_grid(V, who):
+    """(node grid, number of fields) of a space whose fields share one CG node grid"""
+    g = V.grids[0]
+    if getattr(g, "dg", True) or not hasattr(g, "axes") or any(
+            gi.degree != g.degree or gi.dg or len(gi.axes) != len(g.axes) or
+            any(not numpy.array_equal(a, b) for a, b in zip(gi.axes, g.axes)) for gi in V.grids[1:]):
+        raise NotImplementedError("%s: the fields of the space must share one continuous Q_p node grid of a tensor-product "
+                                  "patch" % who)
+    if g.dim() not in (2, 3):
+        raise NotImplementedError("%s: faces are provided for 2-D and 3-D patches" % who)
+    return g, len(V.grids)
+
+
+def _fields_of_the_patch(geometry, who):
+    """Refuses a geometry whose generator puts its fields on bases of their own (FieldListSpline, compatible spaces):
+    their FE fields may share one node grid and still are not the Q_p functions of the patch that the face kernels
+    integrate.  The node grid alone does not tell, so the generator is asked."""
+    gen = getattr(geometry, "_generator", geometry)
+    on_control = getattr(gen, "_fields_on_control_basis", None)
+    if on_control is not None and not on_control():
+        raise NotImplementedError("%s: the fields of %s are not discretised with the control mesh's scalar basis "
+                                  "(FieldListSpline and compatible spaces are not supported)" % (who, type(gen).__name__))
+
+
+def _whole_rows(n, row0, row1, who):
+    if (0 if row0 is None else int(row0), n if row1 is None else int(row1)) != (0, n):
+        raise NotImplementedError("%s: row blocks (several ranks, streamed operands) are not supported; the point values "
+                                  "are numbered over the whole face" % who)
+
+
+class FacePoints(QuadraturePoints):
+    """The Gauss points of the face (direction, side) of a mapped patch, face-element-major (the face elements and the
+    nq^(d-1) points of one lexicographic in the remaining directions with the lower direction fastest): ``x`` host array
+    [npts, nsd] (downloaded on first use), ``x_device`` and ``normals`` (nsd * npts values, component-major; the unit
+    normal DF g^-1 N / |.|), ``weights`` = w_q sqrt(det g_hat (g_hat^-1)_kk) (the reference's surfaceJacobian times the face
+    element's parametric area), ``h_normal`` = 1 / sqrt((g_hat^-1)_kk) (the thickness of the boundary element normal to
+    the face), ``n`` (host [npts, nsd]), ``nq``, ``npts``, ``nsd``, ``direction``, ``side``."""
+
+    def __init__(self, verts, p, cp, nq, direction, side):
+        self.verts, self.p, self.cp, self.nq, self.nsd = verts, p, cp, nq, len(cp) - 1
+        self.direction, self.side = int(direction), int(side)
+        self.x_device, self.weights, self.normals, self.h_normal = _dev.face_points(verts, p, cp, direction, side, nq)
+        self.npts = self.weights.size()
+        self._x = self._n = None
+
+    @property
+    def n(self):
+        if self._n is None:
+            self._n = numpy.ascontiguousarray(self.normals.get_local().reshape(self.nsd, self.npts).T)
+        return self._n
+
+    def values(self, f, who="f"):
+        """as ``QuadraturePoints.values``; a Function of the space is evaluated by ``tg_face_eval``"""
+        if hasattr(f, "vector") and hasattr(f, "function_space"):
+            return _dev.face_eval(self.verts, self.p, self.cp, self.direction, self.side, f.vector(), nq=self.nq)[0]
+        return QuadraturePoints.values(self, f, who)
+
+
+def face_points(geometry, V, direction, side, nq=None, who="boundary points"):
+    """the ``FacePoints`` of one face of the patch of ``geometry``, kept on it per (face, nq, control-function vectors)"""
+    _need_boundary_geometry(who, geometry)
+    g, _ = _face_grid(V, who)
+    _fields_of_the_patch(geometry, who)
+    (direction, side), = check_faces((direction, side), g.dim(), who, _periodic_directions(geometry))
+    gc = _single_grid(geometry.V_control)
+    if gc.shape() != g.shape():
+        raise ValueError("the geometry lives on a different node grid than the space")
+    cp, node0 = _control_window(geometry, 1, 0, g.shape()[-1])
+    if node0 != 0 or any(v.size() != g.num_nodes() for v in cp):
+        raise NotImplementedError("%s: the control functions are spread over several ranks; boundary operands are provided "
+                                  "on one rank" % who)
+    nq = _check_nq(nq, int(g.degree))
+    cache = geometry.__dict__.setdefault("_face_points", {})
+    key = (direction, side, nq, tuple(id(v) for v in cp))
+    if key not in cache:
+        cache[key] = FacePoints([g.vertices[k] for k in range(g.dim())], int(g.degree), cp, nq, direction, side)
+    return cache[key]
+
+
+def _argcount(f):
+    import inspect
+    try:
+        return len([q for q in inspect.signature(f).parameters.values()
+                    if q.kind in (q.POSITIONAL_ONLY, q.POSITIONAL_OR_KEYWORD) and q.default is q.empty])
+    except (TypeError, ValueError):
+        return 1
+
+
+def _per_face(f, i, nfaces, who):
+    """the data of face i: a list holds one entry per face, anything else serves every face"""
+    if isinstance(f, list):
+        if len(f) != nfaces:
+            raise ValueError("%s: a list of %d entries given for %d faces" % (who, len(f), nfaces))
+        return f[i]
+    return f
+
+
+def _face_values(pts, f, who):
+    """scalar point values on a face; a callable may take (x) or (x, n)"""
+    if callable(f) and not hasattr(f, "vector") and _argcount(f) >= 2:
+        v = numpy.asarray(f(pts.x, pts.n), dtype=numpy.float64)
+        if v.shape != (pts.npts,):
+            raise ValueError("%s: the callable returned an array of shape %s for %d points; expected (%d,)"
+                             % (who, v.shape, pts.npts, pts.npts))
+        return _dev.DeviceVector(data=v)
+    return pts.values(f, who)
+
+
+class BoundaryLoadForm(object):
+    """L(v) = int_faces f v ds on the mapped patch, ds and the unit normal n as ``spline.ds`` / ``spline.n`` of the
+    reference.  ``faces``: (direction, side) pairs numbered as ``getSideDofs``, one pair, or None = all faces.  ``f``: a
+    callable of the points ``x [npts, nsd] -> [npts]``, or of ``(x, n)`` when it takes two arguments; a number; point
+    values (numbered as ``FacePoints``); a ``Function``; or a list with one of these per face (a list always means that).  On a space of several
+    fields sharing one node grid (the space of ``ElasticityForm``) ``f`` gives [npts, nF] -- a traction -- and the
+    component loads are written field after field.  ``fn``: adds int fn d_n v ds (the Nitsche right-hand side).
+    ``rational``: v the functions phi / W_h."""
+
+    def __init__(self, f, geometry, faces=None, nq=None, rational=False, fn=None):
+        _need_boundary_geometry("BoundaryLoadForm", geometry)
+        self.f, self.fn, self.geometry, self.faces, self.nq = f, fn, geometry, faces, nq
+        self.rational = bool(rational)
+
+    @classmethod
+    def pressure(cls, p, geometry, faces=None, nq=None, rational=False):
+        """the traction f = -p n of a pressure ``p`` (a number, or a callable of the points)"""
+        def traction(x, n):
+            pv = numpy.asarray(p(x), dtype=numpy.float64) if callable(p) else numpy.full(x.shape[0], float(p))
+            return -pv[:, None] * n
+        return cls(traction, geometry, faces, nq, rational)
+
+    def _components(self, pts, f, nF):
+        if nF == 1:
+            return [_face_values(pts, f, "BoundaryLoadForm")]
+        v = numpy.asarray((f(pts.x, pts.n) if _argcount(f) >= 2 else f(pts.x)) if callable(f) else f, dtype=numpy.float64)
+        if v.shape == (nF,):
+            v = numpy.tile(v, (pts.npts, 1))
+        if v.shape != (pts.npts, nF):
+            raise ValueError("BoundaryLoadForm: an array of shape %s for %d points and %d fields; expected (%d, %d)"
+                             % (v.shape, pts.npts, nF, pts.npts, nF))
+        return [_dev.DeviceVector(data=numpy.ascontiguousarray(v[:, c])) for c in range(nF)]
+
+    def assemble_vector(self, V, row0=None, row1=None):
+        g, nF = _face_grid(V, "BoundaryLoadForm")
+        n = g.num_nodes()
+        _whole_rows(nF * n, row0, row1, "BoundaryLoadForm")
+        faces = check_faces(self.faces, g.dim(), "BoundaryLoadForm", _periodic_directions(self.geometry))
+        if self.fn is not None and nF != 1:
+            raise NotImplementedError("BoundaryLoadForm: the normal-derivative term is provided for scalar spaces")
+        parts = [_dev.DeviceVector(n) for _ in range(nF)]
+        for i, (k, s) in enumerate(faces):
+            pts = face_points(self.geometry, V, k, s, self.nq, "BoundaryLoadForm")
+            comps = self._components(pts, _per_face(self.f, i, len(faces), "BoundaryLoadForm"), nF) \
+                if self.f is not None else [None] * nF
+            fn = _face_values(pts, _per_face(self.fn, i, len(faces), "BoundaryLoadForm"), "BoundaryLoadForm: fn") \
+                if self.fn is not None else None
+            for c in range(nF):
+                _dev.face_load(pts.verts, pts.p, pts.cp, k, s, comps[c], fn, parts[c], nq=pts.nq, rational=self.rational)
+        if nF == 1:
+            return parts[0]
+        out = _dev.DeviceVector(nF * n, zero=False)
+        for c in range(nF):
+            _dev.vec_copy_range(out, c * n, parts[c], 0, n)
+        return out
+
+
+class _FaceMatrixForm(object):
+    """what the boundary matrix forms share: the point coefficients (a, b, c) per face, the assembly on the face pattern
+    and the in-place addition into a matrix that holds the entries"""
+
+    def _setup(self, who, geometry, faces, nq, rational):
+        _need_boundary_geometry(who, geometry)
+        self.geometry, self.faces, self.nq, self.rational = geometry, faces, nq, bool(rational)
+
+    def _faces(self, V):
+        who = type(self).__name__
+        g = _single_grid(V)
+        _face_grid(V, who)
+        faces = check_faces(self.faces, g.dim(), who, _periodic_directions(self.geometry))
+        return g, [(i, face_points(self.geometry, V, k, s, self.nq, who)) for i, (k, s) in enumerate(faces)]
+
+    def assemble_matrix(self, V, row0=None, row1=None):
+        g, faces = self._faces(V)
+        _whole_rows(g.num_nodes(), row0, row1, type(self).__name__)
+        A = None
+        for i, pts in faces:
+            a, b, c = self.coefficients(pts, i, len(faces))
+            if A is None:
+                A = _dev.face_matrix(pts.verts, pts.p, pts.cp, pts.direction, pts.side, a, b, c, nq=pts.nq,
+                                     rational=self.rational)
+            elif not _dev.face_matrix_add(A, pts.verts, pts.p, pts.cp, pts.direction, pts.side, a, b, c, nq=pts.nq,
+                                          rational=self.rational):
+                A = A.add(_dev.face_matrix(pts.verts, pts.p, pts.cp, pts.direction, pts.side, a, b, c, nq=pts.nq,
+                                           rational=self.rational))
+        return A
+
+    def add_into(self, A, V, scale=1.0):
+        """adds ``scale`` times the form's entries in place into ``A``; False, with ``A`` unchanged, when the pattern of
+        ``A`` lacks entries of one of the faces"""
+        g, faces = self._faces(V)
+        todo = [(pts, self.coefficients(pts, i, len(faces))) for i, pts in faces]
+        # the pattern of every face first (a call without coefficients only looks), then the additions
+        for pts, _ in todo:
+            if not _dev.face_matrix_add(A, pts.verts, pts.p, pts.cp, pts.direction, pts.side, nq=pts.nq):
+                return False
+        for pts, (a, b, c) in todo:
+            _dev.face_matrix_add(A, pts.verts, pts.p, pts.cp, pts.direction, pts.side, a, b, c, scale=scale, nq=pts.nq,
+                                 rational=self.rational)
+        return True
+
+
+class BoundaryMassForm(_FaceMatrixForm):
+    """a(u, v) = int_faces alpha u v ds (a Robin term).  ``alpha``: as ``f`` of ``BoundaryLoadForm`` on a scalar space."""
+
+    def __init__(self, alpha, geometry, faces=None, nq=None, rational=False):
+        self._setup("BoundaryMassForm", geometry, faces, nq, rational)
+        self.alpha = alpha
+        self.symmetric = type(self) is BoundaryMassForm
+
+    def coefficients(self, pts, i, nfaces):
+        return _face_values(pts, _per_face(self.alpha, i, nfaces, "BoundaryMassForm"), "BoundaryMassForm: alpha"), None, None
+
+
+class NitscheForm(_FaceMatrixForm):
+    """a(u, v) = int_faces (gamma u v - d_n u v -+ u d_n v) ds: a Dirichlet condition imposed weakly; the minus sign is the
+    symmetric variant.  ``penalty``: a number C, meaning gamma = C p^2 / h_n with the thickness h_n of the boundary
+    element normal to the face, or point values / a callable for gamma itself.  ``load(g)`` is the matching right-hand
+    side int (gamma g v -+ g d_n v) ds."""
+
+    def __init__(self, geometry, faces, penalty, symmetric=True, nq=None, rational=False):
+        self._setup("NitscheForm", geometry, faces, nq, rational)
+        self.penalty = penalty
+        self.symmetric = bool(symmetric) and type(self) is NitscheForm
+        self._sign = -1.0 if symmetric else 1.0
+
+    def gamma(self, pts, i=0, nfaces=1):
+        pen = _per_face(self.penalty, i, nfaces, "NitscheForm")
+        if numpy.ndim(pen) == 0 and not callable(pen) and not isinstance(pen, _dev.DeviceVector):
+            one = _dev.DeviceVector(pts.npts, zero=False)
+            one.fill(float(pen) * float(pts.p) ** 2)
+            return one.pointwise_divide(pts.h_normal)
+        return _face_values(pts, pen, "NitscheForm: penalty")
+
+    def coefficients(self, pts, i, nfaces):
+        minus = _dev.DeviceVector(pts.npts, zero=False)
+        minus.fill(-1.0)
+        other = minus
+        if self._sign > 0:
+            other = _dev.DeviceVector(pts.npts, zero=False)
+            other.fill(1.0)
+        return self.gamma(pts, i, nfaces), minus, other
+
+    def load(self, g):
+        """L(v) = int_faces (gamma g v -+ g d_n v) ds for the Dirichlet data ``g`` (as ``f`` of ``BoundaryLoadForm``)"""
+        return _NitscheLoad(self, g)
+
+
+class _NitscheLoad(object):
+    def __init__(self, form, g):
+        self.form, self.g = form, g
+
+    def assemble_vector(self, V, row0=None, row1=None):
+        F = self.form
+        g, faces = F._faces(V)
+        _whole_rows(g.num_nodes(), row0, row1, "NitscheForm.load")
+        out = _dev.DeviceVector(g.num_nodes())
+        for i, pts in faces:
+            gq = _face_values(pts, _per_face(self.g, i, len(faces), "NitscheForm.load"), "NitscheForm.load")
+            fq = F.gamma(pts, i, len(faces)).pointwise_mult(gq)
+            fnq = gq
+            if F._sign < 0:
+                fnq = gq.copy()
+                fnq.axpy(-2.0, gq)
+            _dev.face_load(pts.verts, pts.p, pts.cp, pts.direction, pts.side, fq, fnq, out, nq=pts.nq, rational=F.rational)
+        return out
+
+
+class Sum(object):
+    """sum_t c_t form_t for ``(coefficient, form)`` pairs or bare forms (coefficient 1): ``assemble_matrix`` and
+    ``assemble_vector``.  Matrices: the first volume term is assembled; ``BoundaryMassForm`` and ``NitscheForm`` terms are
+    added in place (``tg_face_matrix_add``) when its pattern holds their entries -- every mapped form's does -- so that
+    the sum keeps the pattern certificate of the volume term; otherwise, and for further volume terms,
+    ``DeviceCSR.combine`` on equal patterns, else ``DeviceCSR.add``.  ``symmetric`` is true only if every term's is."""
+
+    def __init__(self, *terms):
+        if not terms:
+            raise ValueError("Sum: no term given")
+        self.terms = []
+        for t in terms:
+            c, form = (t if isinstance(t, tuple) else (1.0, t))
+            if isinstance(t, tuple) and (len(t) != 2 or numpy.ndim(t[0]) != 0):
+                raise ValueError("Sum: a term is a form or a (coefficient, form) pair")
+            if not (hasattr(form, "assemble_matrix") or hasattr(form, "assemble_vector")):
+                raise ValueError("Sum: %r has neither assemble_matrix nor assemble_vector" % (form,))
+            self.terms.append((float(c), form))
+        kinds = set(hasattr(f, "assemble_matrix") for _, f in self.terms)
+        if len(kinds) != 1:
+            raise ValueError("Sum: matrix forms and vector forms cannot be added")
+        self.symmetric = all(getattr(f, "symmetric", False) is True for _, f in self.terms)
+        self.in_place = 0          # face terms the last assemble_matrix added in place
+
+    @staticmethod
+    def _axpby(A, a, B, b):
+        """a A + b B: on one pattern if the two share it, else on the union"""
+        try:
+            return A.combine(a, B, b)
+        except _dev.TigarHipError:
+            if a != 1.0:
+                A = A.combine(a, A, 0.0)
+            return A.add(B if b == 1.0 else B.combine(b, B, 0.0))
+
+    def assemble_matrix(self, V, row0=None, row1=None):
+        if not hasattr(self.terms[0][1], "assemble_matrix"):
+            raise TypeError("Sum: the terms are vector forms")
+        volume = [(c, f) for c, f in self.terms if not isinstance(f, _FaceMatrixForm)]
+        faces = [(c, f) for c, f in self.terms if isinstance(f, _FaceMatrixForm)]
+        self.in_place = 0
+        A = None
+        for c, f in volume:
+            B = f.assemble_matrix(V, row0, row1)
+            if A is None:
+                A = B if c == 1.0 else B.combine(c, B, 0.0)
+            else:
+                A = self._axpby(A, 1.0, B, c)
+        for c, f in faces:
+            if A is None:
+                B = f.assemble_matrix(V, row0, row1)
+                A = B if c == 1.0 else B.combine(c, B, 0.0)
+                continue
+            _whole_rows(_single_grid(V).num_nodes(), row0, row1, "Sum")
+            if f.add_into(A, V, c):
+                self.in_place += 1
+            else:
+                A = self._axpby(A, 1.0, f.assemble_matrix(V), c)
+        return A
+
+    def assemble_vector(self, V, row0=None, row1=None):
+        if not hasattr(self.terms[0][1], "assemble_vector"):
+            raise TypeError("Sum: the terms are matrix forms")
+        out = None
+        for c, f in self.terms:
+            v = f.assemble_vector(V, row0, row1)
+            if out is None:
+                out = v
+                if c != 1.0:
+                    out = v.copy()
+                    out.zero()
+                    out.axpy(c, v)
+            else:
+                out.axpy(c, v)
+        return out
