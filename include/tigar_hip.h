@@ -643,6 +643,38 @@ int tg_quad_load_rational(const tg_patch_t *patch, tg_vec_t f_q, tg_vec_t out);
 /* the three sums of tg_quad_error with u = u_h / W_h */
 int tg_quad_error_rational(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, tg_vec_t ge_q, double *out);
 
+/* ---- volume forms with point coefficients (csrc/tg_coef.hip, endings of csrc/tg_postproc.hip) ------------------------------
+ *   a(u, v) = int grad v . (A grad u) + (b . grad v) u + v (c . grad u) + m u v dx     (u: trial = column, v: test = row)
+ *   L(v)    = int s v + F . grad v dx
+ * on the patches above (scalar Q_p space, d = 1, 2, 3, nsd >= d), grad the Cartesian gradient DF g^-1 grad_xi, with A, b, c,
+ * m, s, F given at the quadrature points, numbered as tg_quad_points, vectors and tensors component-major (component (i, j)
+ * of A at (i nsd + j) npts + q).  Any point array may be null: zero.
+ * tg_coef_transform: one pass over the points, Cartesian data -> reference element.  With P = DF g^-1 and wdet = w sqrt(det g):
+ * C^ = wdet P^T A P, b^ = wdet P^T b, c^ = wdet P^T c, m^ = wdet m -- coef_out holds (d^2 + 2 d + 1) npts values,
+ * component-major: C^ row-major (d^2), b^ (d), c^ (d), m^.  a_kind: 0 no diffusion (A_q null), 1 one value per point
+ * (A = a I), 2 an nsd x nsd tensor per point, which need not be symmetric.  rational != 0: trial and test functions
+ * phi / W_h; with beta = grad_xi W_h / W_h the data become C' = C^ / W^2, b' = b^ / W^2 - C' beta, c' = c^ / W^2 - C'^T beta,
+ * m' = m^ / W^2 - beta . b^ / W^2 - beta . c^ / W^2 + beta . C' beta, so that the matrix entry needs no rational twin.
+ * tg_flux_transform: s^ = wdet s, F^ = wdet P^T F ((d + 1) npts values: s^, then F^); rational: F' = F^ / W,
+ * s' = (s^ - F^ . beta) / W. */
+int tg_coef_transform(const tg_patch_t *patch, int rational, int a_kind, tg_vec_t A_q, tg_vec_t b_q, tg_vec_t c_q, tg_vec_t m_q,
+                      tg_vec_t coef_out);
+int tg_flux_transform(const tg_patch_t *patch, int rational, tg_vec_t s_q, tg_vec_t F_q, tg_vec_t out);
+/* A_ab = sum_q grad_xi phi_a . C_q grad_xi phi_b + (b_q . grad_xi phi_a) phi_b + phi_a (c_q . grad_xi phi_b) + m_q phi_a phi_b
+ * from the output of tg_coef_transform, on the element-coupling pattern with its certificate (the pattern of every mapped
+ * form).  All rows; colours in the order of the other element kernels, no floating-point atomics, the same bits in every run.
+ * 3-D, nsd = 3, nq = p + 1, p = 2, 3: sum-factorised instantiations of k_asf3 (p = 2, the walk) and k_asf3_quad (p = 3) whose
+ * phase 0 loads the point data (csrc/tg_assemble.hip); TIGAR_ASM_LEGACY selects the plain kernel (csrc/tg_coef.hip), which
+ * takes every other shape; TIGAR_ASM_CHUNK / TIGAR_ASM_QUAD_CHUNK size the pieces as for the stiffness matrix.
+ * The patch gives the shape (d, p, nq, element counts); its control functions are not read, and its element vertices serve
+ * the cache of the reference-element tables only.  Nothing ties `coef` to the patch, nq or rational setting it was
+ * transformed for but its length: a mismatch of nq between transform and assembly is caught only when the sizes differ. */
+int tg_assemble_coef_matrix(const tg_patch_t *patch, tg_vec_t coef, tg_csr_t *out);
+/* out[node] = sum_q wdet_q (s_q phi_node + F_q . grad phi_node)(xi_q), the Cartesian gradient; either array may be null.
+ * _rational: tested against phi / W_h.  Sum-factorised both ways, added colour by colour as tg_quad_load. */
+int tg_quad_load_flux(const tg_patch_t *patch, tg_vec_t s_q, tg_vec_t F_q, tg_vec_t out);
+int tg_quad_load_flux_rational(const tg_patch_t *patch, tg_vec_t s_q, tg_vec_t F_q, tg_vec_t out);
+
 /* ---- boundary integrals on the same patches (csrc/tg_boundary.hip): the boundary measure and the mapped normal of the
  * reference's ExtractedSpline (spline.ds, spline.n; tIGAr/common.py:931-939, calculusUtils.py:37-52, 71-80).  d = 2, 3,
  * nsd >= d.  A face is (direction dir, side 0 | 1), numbered as getSideDofs; its parametric normal is N = (2 side - 1) e_dir.

@@ -232,6 +232,11 @@ PROTOTYPES = {
     "tg_quad_eval_rational": (C.c_int, [C.POINTER(tg_patch_t), handle, C.c_int, handle, handle]),
     "tg_quad_load_rational": (C.c_int, [C.POINTER(tg_patch_t), handle, handle]),
     "tg_quad_error_rational": (C.c_int, [C.POINTER(tg_patch_t), handle, handle, handle, c_f64p]),
+    "tg_coef_transform": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, handle, handle]),
+    "tg_flux_transform": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, handle, handle, handle]),
+    "tg_assemble_coef_matrix": (C.c_int, [C.POINTER(tg_patch_t), handle, C.POINTER(handle)]),
+    "tg_quad_load_flux": (C.c_int, [C.POINTER(tg_patch_t), handle, handle, handle]),
+    "tg_quad_load_flux_rational": (C.c_int, [C.POINTER(tg_patch_t), handle, handle, handle]),
     "tg_face_points": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, handle]),
     "tg_face_eval": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, handle]),
     "tg_face_load": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle]),

@@ -40,3 +40,7 @@ struct tg_asm_cache_t {
 };
 extern tg_asm_cache_t g_asm_cache;
 int tg_asm_cache_get(const tg_patch_t *pt);   // uploads (or keeps) the tables of this patch description
+// the element-coupling pattern with its certificate, rows [row0, row1); n[k] nodes per direction (tg_assemble.hip)
+int tg_asm_coupling_pattern(int d, int p, const int *n, int64_t row0, int64_t row1, bool pattern_only, tg_csr_t *out);
+// the point-coefficient form of tg_coef.hip through the sum-factorised kernels, where the shape has such a route (*taken)
+int tg_asm_coef_fast(const tg_patch_t *pt, tg_vec_t coef, tg_csr_t *out, bool *taken);

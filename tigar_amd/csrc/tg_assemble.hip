@@ -366,6 +366,8 @@ struct tg_asf_args {
   int64_t ngroups;
   int ei, ej;                // elasticity: the block
   double lam, mu;
+  const double *coef;        // point-coefficient form (TG_ASF_COEF): 16 values per point, component-major (tg_coef_transform)
+  int64_t npts;              // ... points of the patch
 };
 
 __device__ __forceinline__ void tg_wave_sync() {
@@ -561,6 +563,26 @@ __device__ __forceinline__ void tg_asf_flux_rat(const double *Gq, double ph, dou
   Xv = -fma(b2, X2, fma(b1, X1, b0 * X0));
 }
 
+// Point-coefficient form (tg_coef.hip): the 16 values of a point are C (9, row index = derivative of the TEST function, as
+// FORM 2) | b (3) | c (3) | m.  The column's flux X = C grad_xi phi_b + b phi_b; its value term Xv = c . grad_xi phi_b + m phi_b
+// meets the test function's VALUE and rides on the first contraction exactly as the rational Xv does
+__device__ __forceinline__ void tg_asf_flux_coef(const double *Gq, double ph, double f0, double f1, double f2, double &X0, double &X1,
+                                                 double &X2, double &Xv) {
+  X0 = fma(Gq[9], ph, fma(Gq[2], f2, fma(Gq[1], f1, Gq[0] * f0)));
+  X1 = fma(Gq[10], ph, fma(Gq[5], f2, fma(Gq[4], f1, Gq[3] * f0)));
+  X2 = fma(Gq[11], ph, fma(Gq[8], f2, fma(Gq[7], f1, Gq[6] * f0)));
+  Xv = fma(Gq[15], ph, fma(Gq[14], f2, fma(Gq[13], f1, Gq[12] * f0)));
+}
+// phase 0 of that form: the lane's point (number gp of the patch) from memory
+#define TG_ASF_NCOEF 16
+__device__ __forceinline__ void tg_asf_load_coef(const double *coef, int64_t npts, int64_t gp, double *Wq) {
+  double G[TG_ASF_NCOEF];
+#pragma unroll
+  for (int j = 0; j < TG_ASF_NCOEF; j++) G[j] = coef[(int64_t)j * npts + gp];
+#pragma unroll
+  for (int j = 0; j < TG_ASF_NCOEF; j++) Wq[j] = G[j];
+}
+
 // 1-D row data of node a of element e (direction with nel elements): vertex shared with a neighbour?, row length,
 // position of the element's first column in the row, entries of the 1-D rows before the node
 template <int P>
@@ -571,16 +593,19 @@ __device__ __forceinline__ void tg_asf_row1d(int a, int e, int nel, bool &v, int
   rps = (int64_t)(P + 1) * (P * e + a) + (a > 0 ? (int64_t)P * e : (e > 0 ? (int64_t)P * (e - 1) : 0));
 }
 
-// FORM: 0 mass, 1 stiffness, 2 elasticity block; + 4 (TG_ASF_RAT): rational functions phi / W_h (mass, stiffness)
+// FORM: 0 mass, 1 stiffness, 2 elasticity block; + 4 (TG_ASF_RAT): rational functions phi / W_h (mass, stiffness);
+// 1 + 8 (TG_ASF_COEF): the point-coefficient form -- phase 0 is a load of the transformed point data
 #define TG_ASF_RAT 4
+#define TG_ASF_COEF 8
 template <int P1, int EPW, int FORMR>
 __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3(tg_asf_args A) {
   constexpr int FORM = FORMR & 3;
-  constexpr bool RAT = (FORMR & TG_ASF_RAT) != 0;
+  constexpr bool RAT = (FORMR & TG_ASF_RAT) != 0, COEF = (FORMR & TG_ASF_COEF) != 0;
   static_assert(!(RAT && FORM == 2), "rational elasticity blocks go through the plain kernel");
+  static_assert(!(COEF && (RAT || FORM != 1)), "point coefficients: the data hold the rational space already");
   constexpr int P = P1 - 1, NL = P1 * P1 * P1, LPE = 64 / EPW, PP = P1 * P1;
   constexpr int AH = P1;                 // (rows of the first local index a0 handled at once: all)
-  constexpr int GS = (FORM == 2 || RAT) ? 10 : 8, GN = RAT ? 10 : (FORM == 2 ? 9 : 7);     // doubles per quadrature point in LDS: stride, values
+  constexpr int GS = COEF ? TG_ASF_NCOEF : ((FORM == 2 || RAT) ? 10 : 8), GN = RAT ? 10 : (FORM == 2 ? 9 : 7);     // doubles per quadrature point in LDS: stride, values
   static_assert(NL <= LPE, "an element needs a lane per local node");
   __shared__ __attribute__((aligned(16))) double s_tab[2 * PP + P1];
   __shared__ __attribute__((aligned(16))) double s_w[TG_ASF_NW][TG_ASF_AREA(4)];
@@ -606,7 +631,7 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3(tg_asf_args A) {
   const int nel0 = A.nel[0];
   double *CR = s_c[wv];                 // carried rows [a1 + P1 a2][lane]
   double cpn[4];
-  {
+  if constexpr (!COEF) {
     const int li = lane - eb, x0 = li % P1, x1 = (li / P1) % P1, x2 = (li / PP) % P1;
     const int64_t nodebase = (int64_t)x0 + (int64_t)A.n[0] * ((e1_ * P + x1) + (int64_t)A.n[1] * (e2_ * P + x2)) - A.cp_node0;
     const int ef = e_lo > 0 ? e_lo - 1 : 0;
@@ -633,17 +658,21 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3(tg_asf_args A) {
     const int64_t T0 = (int64_t)P1 * A.n[0] + (int64_t)P * (A.nel[0] - 1), T1 = (int64_t)P1 * A.n[1] + (int64_t)P * (A.nel[1] - 1);
     const int par1 = e1 & 1, par2 = e2 & 1;
     // ---- phase 0 --------------------------------------------------------------------------------------------
-    if (active) {
+    if constexpr (COEF) {                // the lane's point of element (e0, e1, e2): li is its number in the element
+      if (active)
+        tg_asf_load_coef(A.coef, A.npts, ((int64_t)e0 + (int64_t)nel0 * (e1 + (int64_t)A.nel[1] * e2)) * NL + li, W + (eb + li) * GS);
+      tg_wave_sync();
+    } else {
+      if (active) {
 #pragma unroll
-      for (int c = 0; c < 4; c++) W[c * 64 + ln] = cpn[c];
-    }
-    tg_wave_sync();
-    if (e0 + 1 < e_hi) {                 // the next element's nodal values travel while this one is integrated
-      const int64_t nodebase = (int64_t)x0 + (int64_t)A.n[0] * ((e1 * P + x1) + (int64_t)A.n[1] * (e2 * P + x2)) - A.cp_node0;
+        for (int c = 0; c < 4; c++) W[c * 64 + ln] = cpn[c];
+      }
+      tg_wave_sync();
+      if (e0 + 1 < e_hi) {                 // the next element's nodal values travel while this one is integrated
+        const int64_t nodebase = (int64_t)x0 + (int64_t)A.n[0] * ((e1 * P + x1) + (int64_t)A.n[1] * (e2 * P + x2)) - A.cp_node0;
 #pragma unroll
-      for (int c = 0; c < 4; c++) cpn[c] = active ? A.cp[c][nodebase + (int64_t)(e0 + 1) * P] : 0.0;
-    }
-    {
+        for (int c = 0; c < 4; c++) cpn[c] = active ? A.cp[c][nodebase + (int64_t)(e0 + 1) * P] : 0.0;
+      }
       double N[4], dN[4][3], G[GN];
 #pragma unroll
       for (int j = 0; j < GN; j++) G[j] = 0.0;
@@ -702,14 +731,16 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3(tg_asf_args A) {
                 const double *Gq = Wh + (eb + q0 + P1 * (q1 + P1 * q2)) * GS;
                 const double f0 = d0[q0] * mll, f1 = l0[q0] * mdl, f2 = l0[q0] * mld;
                 double X0, X1, X2, Xv = 0.0;
-                if constexpr (RAT)
+                if constexpr (COEF)
+                  tg_asf_flux_coef(Gq, l0[q0] * mll, f0, f1, f2, X0, X1, X2, Xv);
+                else if constexpr (RAT)
                   tg_asf_flux_rat(Gq, l0[q0] * mll, f0, f1, f2, X0, X1, X2, Xv);
                 else
                   tg_asf_flux<FORM>(Gq, f0, f1, f2, X0, X1, X2);
 #pragma unroll
                 for (int a = 0; a < AH; a++) {
                   Y0[a] = fma(UD[a * P1 + q0], X0, Y0[a]);
-                  if constexpr (RAT) Y0[a] = fma(UL[a * P1 + q0], Xv, Y0[a]);
+                  if constexpr (RAT || COEF) Y0[a] = fma(UL[a * P1 + q0], Xv, Y0[a]);
                   Y1[a] = fma(UL[a * P1 + q0], X1, Y1[a]);
                   Y2[a] = fma(UL[a * P1 + q0], X2, Y2[a]);
                 }
@@ -1059,10 +1090,11 @@ __device__ __forceinline__ void tg_asf_each4(F &&f) {
 template <int P1, int FORMR, int PRE, int LOOP>
 __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3_quad(tg_asf_args A) {
   constexpr int FORM = FORMR & 3;
-  constexpr bool RAT = (FORMR & TG_ASF_RAT) != 0;
+  constexpr bool RAT = (FORMR & TG_ASF_RAT) != 0, COEF = (FORMR & TG_ASF_COEF) != 0;
   static_assert(!(RAT && FORM != 1), "the rational variant of this kernel is the stiffness matrix");
+  static_assert(!(COEF && (RAT || FORM != 1)), "point coefficients: the data hold the rational space already");
   constexpr int P = P1 - 1, NL = P1 * P1 * P1, PP = P1 * P1;
-  constexpr int GS = (FORM == 2 || RAT) ? 10 : 8, GN = RAT ? 10 : (FORM == 2 ? 9 : 7);
+  constexpr int GS = COEF ? TG_ASF_NCOEF : ((FORM == 2 || RAT) ? 10 : 8), GN = RAT ? 10 : (FORM == 2 ? 9 : 7);
   static_assert(NL == 64 && PP <= 16, "one element per wave, a lane per local node");
   __shared__ __attribute__((aligned(16))) double s_tab[2 * PP + P1];
   __shared__ __attribute__((aligned(16))) double s_w[TG_ASF_NW][TG_ASF_AREA(4)];
@@ -1086,7 +1118,7 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3_quad(tg_asf_args A) {
   const int64_t T0 = (int64_t)P1 * A.n[0] + (int64_t)P * (A.nel[0] - 1), T1 = (int64_t)P1 * A.n[1] + (int64_t)P * (A.nel[1] - 1);
   const unsigned uT0 = (unsigned)T0;
   double cpn[4];
-  {
+  if constexpr (!COEF) {
     const int x0 = lane % P1, x1 = (lane / P1) % P1, x2 = lane / PP;
     const int e0 = min(q_lo * TG_ASF_NW + wv, A.nel[0] - 1);
     const int64_t node = (int64_t)(e0 * P + x0) + (int64_t)A.n[0] * ((e1_ * P + x1) + (int64_t)A.n[1] * (e2_ * P + x2)) - A.cp_node0;
@@ -1112,10 +1144,13 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3_quad(tg_asf_args A) {
     const double *CF = wv > 0 ? s_f[gen][wv - 1] : s_f[LOOP ? (q + 2) % 3 : 0][TG_ASF_NW - 1];
     const int par1 = e1 & 1, par2 = e2 & 1;
     // ---- phase 0 ----------------------------------------------------------------------------------------------
+    if constexpr (COEF) {                // the lane's point of element (e0, e1, e2)
+      tg_asf_load_coef(A.coef, A.npts, ((int64_t)e0 + (int64_t)A.nel[0] * (e1 + (int64_t)A.nel[1] * e2)) * NL + ln, W + ln * GS);
+      tg_wave_sync();
+    } else {
 #pragma unroll
-    for (int c = 0; c < 4; c++) W[c * 64 + ln] = cpn[c];
-    tg_wave_sync();
-    {
+      for (int c = 0; c < 4; c++) W[c * 64 + ln] = cpn[c];
+      tg_wave_sync();
       double N[4], dN[4][3], G[GN];
       tg_asf_to_points<P1, 4>(W, TL, TD, ln, 0, x0, x1, x2, true, N, dN);
       if constexpr (FORM == 2)
@@ -1217,14 +1252,16 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3_quad(tg_asf_args A) {
             const double *Gq = W + (q0 + P1 * (q1 + P1 * q2)) * GS;
             const double f0 = d0[q0] * mll, f1 = l0[q0] * mdl, f2 = l0[q0] * mld;
             double X0, X1, X2, Xv = 0.0;
-            if constexpr (RAT)
+            if constexpr (COEF)
+              tg_asf_flux_coef(Gq, l0[q0] * mll, f0, f1, f2, X0, X1, X2, Xv);
+            else if constexpr (RAT)
               tg_asf_flux_rat(Gq, l0[q0] * mll, f0, f1, f2, X0, X1, X2, Xv);
             else
               tg_asf_flux<FORM>(Gq, f0, f1, f2, X0, X1, X2);
 #pragma unroll
             for (int a = 0; a < P1; a++) {
               Y0[a] = fma(UD[a * P1 + q0], X0, Y0[a]);
-              if constexpr (RAT) Y0[a] = fma(UL[a * P1 + q0], Xv, Y0[a]);
+              if constexpr (RAT || COEF) Y0[a] = fma(UL[a * P1 + q0], Xv, Y0[a]);
               Y1[a] = fma(UL[a * P1 + q0], X1, Y1[a]);
               Y2[a] = fma(UL[a * P1 + q0], X2, Y2[a]);
             }
@@ -1252,7 +1289,7 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3_quad(tg_asf_args A) {
 #pragma unroll
       for (int i = 0; i < PP; i++) FW[(x0 == P ? i * 16 : 0) + fo] = acc[P + P1 * i];
     }
-    if (LOOP) {       // the next group's nodal values travel while the rows of this one leave
+    if (LOOP && !COEF) {       // the next group's nodal values travel while the rows of this one leave
       const int en = min(min(q + 1, q_hi - 1) * TG_ASF_NW + wv, A.nel[0] - 1);
       const int64_t node = (int64_t)(en * P + x0) + (int64_t)A.n[0] * ((e1 * P + x1) + (int64_t)A.n[1] * (e2 * P + x2)) - A.cp_node0;
 #pragma unroll
@@ -1355,6 +1392,21 @@ static void tg_asf_launch_rat(int form, const tg_asf_args &A, unsigned nblk) {
       hipLaunchKernelGGL((k_asf3_quad<P1, 1 | TG_ASF_RAT, 1, 0>), g, b, 0, g_tg.stream, A);
   } else {
     hipLaunchKernelGGL((k_asf3<P1, EPW, 1 | TG_ASF_RAT>), g, b, 0, g_tg.stream, A);
+  }
+}
+
+// The point-coefficient form takes the default route of the stiffness matrix of its degree: p = 2 the walk, p = 3 the
+// groups of four (looping over its pieces or not)
+template <int P1, int EPW>
+static void tg_asf_launch_coef(const tg_asf_args &A, unsigned nblk) {
+  const dim3 g(nblk), b(64 * TG_ASF_NW);
+  if constexpr (P1 == 4) {
+    if (A.chunk > 1)
+      hipLaunchKernelGGL((k_asf3_quad<P1, 1 | TG_ASF_COEF, 1, 1>), g, b, 0, g_tg.stream, A);
+    else
+      hipLaunchKernelGGL((k_asf3_quad<P1, 1 | TG_ASF_COEF, 1, 0>), g, b, 0, g_tg.stream, A);
+  } else {
+    hipLaunchKernelGGL((k_asf3<P1, EPW, 1 | TG_ASF_COEF>), g, b, 0, g_tg.stream, A);
   }
 }
 
@@ -1476,6 +1528,38 @@ int tg_asm_cache_get(const tg_patch_t *pt) {
   return 0;
 }
 
+// pattern of every matrix form: the Kronecker product of the 1-D element-coupling patterns (carries the pattern certificate of
+// tg_kron_sum_csr); rows [row0, row1).  pattern_only: the values are left unwritten (the caller stores every entry)
+int tg_asm_coupling_pattern(int d, int p, const int *nn, int64_t row0, int64_t row1, bool pattern_only, tg_csr_t *out) {
+  std::vector<std::vector<int32_t>> rp(d), cl(d);
+  std::vector<std::vector<double>> vl(d);
+  tg_kron_dir_t dirs[3];
+  for (int k = 0; k < d; k++) {
+    const int n = nn[k];
+    rp[k].assign(n + 1, 0);
+    for (int r = 0; r < n; r++) {
+      int lo, width;
+      if (r % p == 0) {
+        const int l = std::max(0, r - p), hh = std::min(n - 1, r + p);
+        lo = l;
+        width = hh - l + 1;
+      } else {
+        lo = (r / p) * p;
+        width = p + 1;
+      }
+      for (int c = 0; c < width; c++) cl[k].push_back(lo + c);
+      rp[k][r + 1] = rp[k][r] + width;
+    }
+    vl[k].assign(cl[k].size(), 0.0);
+    dirs[k].n = n;
+    dirs[k].rowptr = rp[k].data();
+    dirs[k].col = cl[k].data();
+    dirs[k].val = vl[k].data();
+  }
+  if (pattern_only) tg_kron_pattern_only();
+  return tg_kron_sum_csr(d, 1, dirs, row0, row1, out);
+}
+
 // rows [row0, row1) of the matrix / vector -- whole node planes of the LAST direction (any range when d == 1); the control
 // functions (and fnod) hold the nodes [cp_node0, cp_node0 + n), which must cover every element that touches the rows
 struct tg_elast_block {
@@ -1483,8 +1567,11 @@ struct tg_elast_block {
   double lam, mu;
 };
 
+// coef (with form 1): the point-coefficient form from its transformed data -- the sum-factorised route only; *coef_taken says
+// whether the shape has one (if not, nothing is done: tg_coef.hip has the plain kernel).  The control functions are not read.
 static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int64_t row1, int64_t cp_node0, tg_csr_t *mout,
-                              tg_vec_t fnod, tg_vec_t bout, const tg_elast_block *eb = nullptr, bool rat = false) {
+                              tg_vec_t fnod, tg_vec_t bout, const tg_elast_block *eb = nullptr, bool rat = false,
+                              tg_vec_t coef = nullptr, bool *coef_taken = nullptr) {
   TG_REQUIRE_INIT();
   TG_REQUIRE(pt && pt->d >= 1 && pt->d <= 3 && pt->p >= 1 && pt->p <= TG_MAX_DEGREE && pt->nsd >= pt->d && pt->nsd <= 3,
              "bad patch description");
@@ -1543,7 +1630,7 @@ static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int6
     if (ez0 >= nelL) ez0 = nelL - 1;           // (the last node plane belongs to the last layer)
   }
   const int64_t need0 = (int64_t)ez0 * p * plane, need1 = (zb > za) ? ((int64_t)ez1 * p + 1) * plane : need0;
-  for (int c = 0; c <= pt->nsd; c++) {
+  for (int c = 0; c <= pt->nsd && !coef; c++) {
     TG_REQUIRE(pt->cp[c], "control function %d missing", c);
     TG_REQUIRE(cp_node0 >= 0 && cp_node0 <= need0 && cp_node0 + pt->cp[c]->n >= need1,
                "control function %d holds the FE nodes [%lld, %lld), the rows need [%lld, %lld)", c, (long long)cp_node0,
@@ -1563,38 +1650,16 @@ static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int6
     const double t0 = (double)p1 * A.n[0] + (double)p * (A.nel[0] - 1), t1 = (double)p1 * A.n[1] + (double)p * (A.nel[1] - 1);
     if ((2.0 * p + 1.0) * t0 * t1 * 8.0 >= 4294967000.0) fast = false;      // (byte offsets inside one plane of rows)
   }
+  if (coef) {           // p = 2, 3
+    if (p == 1) fast = false;
+    *coef_taken = fast;
+    if (!fast) return 0;
+  }
 
   tg_csr_s *m = nullptr;
   if (form != 2) {
-    // pattern: Kronecker product of the 1-D element-coupling patterns (carries the pattern certificate of tg_kron_sum_csr)
-    std::vector<std::vector<int32_t>> rp(d), cl(d);
-    std::vector<std::vector<double>> vl(d);
-    tg_kron_dir_t dirs[3];
-    for (int k = 0; k < d; k++) {
-      const int n = A.n[k];
-      rp[k].assign(n + 1, 0);
-      for (int r = 0; r < n; r++) {
-        int lo, width;
-        if (r % p == 0) {
-          const int l = std::max(0, r - p), hh = std::min(n - 1, r + p);
-          lo = l;
-          width = hh - l + 1;
-        } else {
-          lo = (r / p) * p;
-          width = p + 1;
-        }
-        for (int c = 0; c < width; c++) cl[k].push_back(lo + c);
-        rp[k][r + 1] = rp[k][r] + width;
-      }
-      vl[k].assign(cl[k].size(), 0.0);
-      dirs[k].n = n;
-      dirs[k].rowptr = rp[k].data();
-      dirs[k].col = cl[k].data();
-      dirs[k].val = vl[k].data();
-    }
     tg_csr_t pat = nullptr;
-    if (fast) tg_kron_pattern_only();     // (the sum-factorised kernels store every entry before anybody adds to it)
-    TG_TRY(tg_kron_sum_csr(d, 1, dirs, row0, row1, &pat));
+    TG_TRY(tg_asm_coupling_pattern(d, p, A.n, row0, row1, fast, &pat));
     m = pat;
     // (the pattern kernel wrote 0 * 0 * 0 into every value: the plain kernel adds into that; the sum-factorised kernel
     //  stores every entry before anybody adds to it)
@@ -1654,6 +1719,10 @@ static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int6
     F.ej = A.ej;
     F.lam = A.lam;
     F.mu = A.mu;
+    if (coef) {
+      F.coef = coef->d;
+      F.npts = coef->n / TG_ASF_NCOEF;
+    }
   }
   const int nt = (form == 2) ? 128 : 256;
   bool bad = false;
@@ -1664,11 +1733,11 @@ static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int6
   // sum-factorised matrix kernel need no colouring in direction 0
   // the walk along direction 0 for every matrix form but the p = 3 stiffness matrix (see k_asf3_elem); TIGAR_ASM_WALK=0/1 forces
   bool walk = fast && form != 2 && !(p == 3 && (form == 1 || form == 3)) && p != 1;
-  if (fast && form != 2 && !rat && getenv("TIGAR_ASM_WALK")) walk = atoi(getenv("TIGAR_ASM_WALK")) != 0;
+  if (fast && form != 2 && !rat && !coef && getenv("TIGAR_ASM_WALK")) walk = atoi(getenv("TIGAR_ASM_WALK")) != 0;
   // p = 3 stiffness / elasticity: the four waves of a workgroup on four consecutive elements of a line (k_asf3_quad;
   // TIGAR_ASM_QUAD=0: independent elements); direction 0 of a colour then counts GROUPS
   bool line = fast && !walk && p == 3 && (form == 1 || form == 3);
-  if (line && !rat && getenv("TIGAR_ASM_QUAD")) line = atoi(getenv("TIGAR_ASM_QUAD")) != 0;
+  if (line && !rat && !coef && getenv("TIGAR_ASM_QUAD")) line = atoi(getenv("TIGAR_ASM_QUAD")) != 0;
   if (line) {           // pieces of `chunk` groups of four elements (a function of nothing but the environment: the seams
                         // fix the order of the sums, and row blocks must reproduce the whole matrix bit for bit)
     int chunk = getenv("TIGAR_ASM_QUAD_CHUNK") ? atoi(getenv("TIGAR_ASM_QUAD_CHUNK")) : 8;
@@ -1703,7 +1772,11 @@ static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int6
         F.ngroups = (int64_t)F.ngy * F.ncol[1] * F.ncol[2];
       }
       const unsigned nb = line ? (unsigned)F.ngroups : (unsigned)((F.ngroups + TG_ASF_NW - 1) / TG_ASF_NW);   // (quad: a workgroup per group)
-      if (rat && p == 3)
+      if (coef && p == 3)
+        tg_asf_launch_coef<4, 1>(F, nb);
+      else if (coef)
+        tg_asf_launch_coef<3, 2>(F, nb);
+      else if (rat && p == 3)
         tg_asf_launch_rat<4, 1>(form, F, nb);
       else if (rat)
         tg_asf_launch_rat<3, 2>(form, F, nb);
@@ -1726,7 +1799,8 @@ static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int6
     hipEventSynchronize(g_tg.ev1[0]);
     float ms = 0.f;
     hipEventElapsedTime(&ms, g_tg.ev0[0], g_tg.ev1[0]);
-    fprintf(stderr, "[tg_assemble] form %d%s rows [%lld, %lld): element kernels %.3f ms (%s)\n", form, rat ? " rational" : "",
+    fprintf(stderr, "[tg_assemble] form %d%s rows [%lld, %lld): element kernels %.3f ms (%s)\n", form,
+            coef ? " with point coefficients" : (rat ? " rational" : ""),
             (long long)row0, (long long)row1, ms, fast ? "sum-factorised" : "plain");
   }
   if (bad) {
@@ -1769,6 +1843,14 @@ extern "C" int tg_assemble_mapped_elasticity_rows(const tg_patch_t *patch, int f
 extern "C" int tg_assemble_mapped_load_rows(const tg_patch_t *patch, tg_vec_t fnodal, int64_t row0, int64_t row1,
                                             int64_t cp_node0, tg_vec_t out) {
   return tg_assemble_common(patch, 2, row0, row1, cp_node0, nullptr, fnodal, out);
+}
+
+// ---- the point-coefficient form (tg_coef.hip) on the sum-factorised route: 3-D, nsd = 3, nq = p + 1, p = 2, 3, unless
+// TIGAR_ASM_LEGACY is set; TIGAR_ASM_CHUNK / TIGAR_ASM_QUAD_CHUNK size the pieces as for the stiffness matrix
+int tg_asm_coef_fast(const tg_patch_t *pt, tg_vec_t coef, tg_csr_t *out, bool *taken) {
+  *taken = false;
+  if (pt->d != 3 || coef->n % TG_ASF_NCOEF) return 0;
+  return tg_assemble_common(pt, 1, -1, -1, 0, out, nullptr, nullptr, nullptr, false, coef, taken);
 }
 
 // ---- rational trial and test functions phi / W_h: the same host driver with the flag

@@ -10,8 +10,10 @@
 //   tg_quad_eval     u_h(x_q) and the Cartesian gradient DF g^-1 grad_xi u_h (pinv(DF), quotient rule of the rational map)
 //   tg_quad_load     out[node] = sum_q wdet_q f_q phi_node(xi_q)
 //   tg_quad_error    sum wdet (u_h - e)^2,  sum wdet |grad u_h - ge|^2,  sum wdet e^2
+//   tg_coef_transform / tg_flux_transform   Cartesian point coefficients -> the reference element (formulas: tg_coef.hip)
+//   tg_quad_load_flux   out[node] = sum_q wdet_q (s_q phi_node + F_q . grad phi_node)(xi_q)
 //
-// One kernel, four endings.  A workgroup of 256 threads takes max(1, 256 / nq^d) elements (fewer where
+// One kernel, four endings (and the three that take point coefficients).  A workgroup of 256 threads takes max(1, 256 / nq^d) elements (fewer where
 // their LDS areas would exceed 64 KiB).  The nodal values of the
 // nsd + 1 control functions (and of u) go to the points by SUM FACTORISATION: one 1-D contraction per direction through
 // LDS, O((p+1) nq^d) per field instead of the O((p+1)^d nq^d) of the plain assembly kernel; the load goes back to the
@@ -46,6 +48,11 @@ struct tg_pp_args {
   double *out;                 //       nodal vector
   const double *eq, *geq;      // error: point values of e and of its gradient (either may be null)
   double *part;                //        [3][elements of the patch] partial sums
+  // point coefficients (TG_PP_COEF, TG_PP_FLUX): Cartesian data at the points, any of them null = 0
+  int akind;                   // diffusion: 0 none, 1 one value per point, 2 an nsd x nsd tensor per point
+  const double *Aq, *bq, *cq, *mq;   // a(u, v) = int grad v . (A grad u) + (b . grad v) u + v (c . grad u) + m u v
+  const double *sq, *Fq;       // L(v) = int s v + F . grad v
+  double *cout;                // the data on the reference element, component-major
 };
 
 __device__ __forceinline__ bool tg_pp_has(int c, const tg_pp_args &P) { return c < 3 ? c < P.nsd : P.f[c] != nullptr; }
@@ -69,12 +76,19 @@ __device__ __forceinline__ int64_t tg_pp_node(const tg_pp_args &P, const int *el
 }
 
 // MODE 0 points, 1 eval, 2 load, 3 error; + 4 (TG_PP_RAT): rational functions (eval, load, error)
+// Point coefficients (tg_coef.hip has the formulas): 0 + TG_PP_COEF writes the d^2 + 2d + 1 reference-element coefficients
+// of the matrix form in the place of the points, 0 + TG_PP_FLUX the d + 1 of the load; 2 + TG_PP_FLUX is the load of
+// s v + F . grad v.  All three take TG_PP_RAT: beta is folded into the data.
 #define TG_PP_RAT 4
+#define TG_PP_COEF 8
+#define TG_PP_FLUX 16
 template <int MODER>
 __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
   constexpr int MODE = MODER & 3;
   constexpr bool RAT = (MODER & TG_PP_RAT) != 0;
-  static_assert(!(RAT && MODE == 0), "the points do not depend on the function space");
+  constexpr bool COEF = (MODER & TG_PP_COEF) != 0, FLUX = (MODER & TG_PP_FLUX) != 0;
+  static_assert(!(RAT && MODE == 0 && !COEF && !FLUX), "the points do not depend on the function space");
+  static_assert(!(COEF && (MODE != 0 || FLUX)) && !(FLUX && MODE != 0 && MODE != 2), "endings that take point coefficients");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int d = P.d, p1 = P.p + 1, nq = P.nq, nsd = P.nsd, nc = P.nc, epg = P.epg;
   const int nloc = d == 1 ? p1 : (d == 2 ? p1 * p1 : p1 * p1 * p1);
@@ -227,7 +241,121 @@ __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
     }
     int el[3];
     const int64_t gp = tg_pp_element(P, g0 + es, el) * nqt + q;    // the point's number in the patch
-    if (MODE == 0) {
+    if constexpr (COEF || FLUX) {
+      // Cartesian data -> reference element: P = DF g^-1 (nsd x d; zero beyond), beta = grad_xi W_h / W_h
+      double Pm[3][3], bt[3];
+#pragma unroll
+      for (int c = 0; c < 3; c++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) Pm[c][k] = DF[c][0] * gi[0][k] + DF[c][1] * gi[1][k] + DF[c][2] * gi[2][k];
+#pragma unroll
+      for (int k = 0; k < 3; k++) bt[k] = RAT ? dN[3][k] / W : 0.0;
+      [[maybe_unused]] const double rw = 1.0 / W;
+      if constexpr (COEF) {
+        double Ch[3][3] = {{0}}, bh[3] = {0, 0, 0}, ch[3] = {0, 0, 0}, mh = 0.0;
+        if (P.akind == 1) {            // P^T P = g^-1
+          const double a = wdet * P.Aq[gp];
+#pragma unroll
+          for (int k = 0; k < 3; k++)
+#pragma unroll
+            for (int m = 0; m < 3; m++) Ch[k][m] = a * gi[k][m];
+        } else if (P.akind == 2) {
+          double T[3][3] = {{0}};      // A P
+#pragma unroll
+          for (int c = 0; c < 3; c++)
+#pragma unroll
+            for (int e = 0; e < 3; e++) {
+              if (c >= nsd || e >= nsd) continue;
+              const double a = P.Aq[(int64_t)(c * nsd + e) * P.npts + gp];
+#pragma unroll
+              for (int m = 0; m < 3; m++) T[c][m] = fma(a, Pm[e][m], T[c][m]);
+            }
+#pragma unroll
+          for (int k = 0; k < 3; k++)
+#pragma unroll
+            for (int m = 0; m < 3; m++) Ch[k][m] = wdet * (Pm[0][k] * T[0][m] + Pm[1][k] * T[1][m] + Pm[2][k] * T[2][m]);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          if (c >= nsd) continue;
+          const double bc = P.bq ? wdet * P.bq[(int64_t)c * P.npts + gp] : 0.0;
+          const double cc = P.cq ? wdet * P.cq[(int64_t)c * P.npts + gp] : 0.0;
+#pragma unroll
+          for (int k = 0; k < 3; k++) {
+            bh[k] = fma(Pm[c][k], bc, bh[k]);
+            ch[k] = fma(Pm[c][k], cc, ch[k]);
+          }
+        }
+        if (P.mq) mh = wdet * P.mq[gp];
+        if constexpr (RAT) {
+          // psi = phi / W, grad_xi psi = (grad_xi phi - phi beta) / W: everything takes 1 / W^2, then the terms with beta move
+          // from the tensor to the vectors and from the vectors to the scalar
+          const double rw2 = rw * rw;
+          double Cb[3], Ctb[3];
+#pragma unroll
+          for (int k = 0; k < 3; k++) {
+#pragma unroll
+            for (int m = 0; m < 3; m++) Ch[k][m] *= rw2;
+            bh[k] *= rw2;
+            ch[k] *= rw2;
+          }
+#pragma unroll
+          for (int k = 0; k < 3; k++) {
+            Cb[k] = Ch[k][0] * bt[0] + Ch[k][1] * bt[1] + Ch[k][2] * bt[2];
+            Ctb[k] = Ch[0][k] * bt[0] + Ch[1][k] * bt[1] + Ch[2][k] * bt[2];
+          }
+          mh = mh * rw2 - (bt[0] * bh[0] + bt[1] * bh[1] + bt[2] * bh[2]) - (bt[0] * ch[0] + bt[1] * ch[1] + bt[2] * ch[2]) +
+               (bt[0] * Cb[0] + bt[1] * Cb[1] + bt[2] * Cb[2]);
+#pragma unroll
+          for (int k = 0; k < 3; k++) {
+            bh[k] -= Cb[k];
+            ch[k] -= Ctb[k];
+          }
+        }
+        double *o = P.cout + gp;       // C (row-major d x d) | b | c | m
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+#pragma unroll
+          for (int m = 0; m < 3; m++)
+            if (k < d && m < d) o[(int64_t)(k * d + m) * P.npts] = Ch[k][m];
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+          if (k < d) {
+            o[(int64_t)(d * d + k) * P.npts] = bh[k];
+            o[(int64_t)(d * d + d + k) * P.npts] = ch[k];
+          }
+        o[(int64_t)(d * d + 2 * d) * P.npts] = mh;
+      } else {
+        double sh = P.sq ? wdet * P.sq[gp] : 0.0, Fh[3] = {0, 0, 0};
+        if (P.Fq) {
+#pragma unroll
+          for (int c = 0; c < 3; c++) {
+            if (c >= nsd) continue;
+            const double fc = wdet * P.Fq[(int64_t)c * P.npts + gp];
+#pragma unroll
+            for (int k = 0; k < 3; k++) Fh[k] = fma(Pm[c][k], fc, Fh[k]);
+          }
+        }
+        if constexpr (RAT) {
+          sh = (sh - (Fh[0] * bt[0] + Fh[1] * bt[1] + Fh[2] * bt[2])) * rw;
+#pragma unroll
+          for (int k = 0; k < 3; k++) Fh[k] *= rw;
+        }
+        // s | F: to memory, or to the slots of the way back to the nodes
+        if (MODE == 0) {
+          P.cout[gp] = sh;
+#pragma unroll
+          for (int k = 0; k < 3; k++)
+            if (k < d) P.cout[(int64_t)(1 + k) * P.npts + gp] = Fh[k];
+        } else {
+          double *T = oth + (size_t)es * szt;
+          T[q] = sh;
+#pragma unroll
+          for (int k = 0; k < 3; k++)
+            if (k < d) T[(1 + k) * nqt + q] = Fh[k];
+        }
+      }
+    } else if (MODE == 0) {
 #pragma unroll
       for (int c = 0; c < 3; c++)
         if (c < nsd) P.x[(int64_t)c * P.npts + gp] = N[c] / W;
@@ -257,7 +385,7 @@ __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
       T[2 * nqt + q] = wdet * (e * e);
     }
   }
-  if (MODE == 0 || MODE == 1) return;
+  if (MODE == 0 || MODE == 1) return;      // (the transforms of the point coefficients are MODE 0)
   __syncthreads();
   if (MODE == 3) {
     // the three sums of each element: a tree over its points (fixed shape), then one value per element and term
@@ -285,14 +413,31 @@ __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
   int pk = 1, qrest = nqt / nq;                    // (p+1)^k, nq^(d-k-1)
   for (int k = 0; k < d; k++) {
     const int Sout = pk * p1 * qrest;
-    for (int i = tid; i < epg * Sout; i += nt) {
-      const int es = i / Sout, idx = i - es * Sout;
-      if (g0 + es >= P.nelem) continue;
-      const int Ai = idx % pk, t = idx / pk, ak = t % p1, R = t / p1;
-      const double *I = cur + (size_t)es * szc;
-      double acc = 0.0;
-      for (int q = 0; q < nq; q++) acc = fma(tl[ak * nq + q], I[Ai + pk * (q + nq * R)], acc);
-      nxt[(size_t)es * szn + idx] = acc;
+    if constexpr (FLUX) {
+      // d - k + 1 slots come in: the sum so far, whose remaining tables are all l, and F_k .. F_d-1, each waiting for dl in
+      // its own direction.  Direction k contracts F_k with dl into the sum; the others pass with l: d - k slots go out
+      const int Sin = pk * nq * qrest, nso = d - k;
+      for (int i = tid; i < epg * nso * Sout; i += nt) {
+        const int es = i / (nso * Sout), r = i - es * nso * Sout, sl = r / Sout, idx = r - sl * Sout;
+        if (g0 + es >= P.nelem) continue;
+        const int Ai = idx % pk, t = idx / pk, ak = t % p1, R = t / p1;
+        const double *I = cur + (size_t)es * szc + (sl == 0 ? 0 : (sl + 1) * Sin);
+        double acc = 0.0;
+        for (int q = 0; q < nq; q++) acc = fma(tl[ak * nq + q], I[Ai + pk * (q + nq * R)], acc);
+        if (sl == 0)
+          for (int q = 0; q < nq; q++) acc = fma(tdl[ak * nq + q], I[Sin + Ai + pk * (q + nq * R)], acc);
+        nxt[(size_t)es * szn + sl * Sout + idx] = acc;
+      }
+    } else {
+      for (int i = tid; i < epg * Sout; i += nt) {
+        const int es = i / Sout, idx = i - es * Sout;
+        if (g0 + es >= P.nelem) continue;
+        const int Ai = idx % pk, t = idx / pk, ak = t % p1, R = t / p1;
+        const double *I = cur + (size_t)es * szc;
+        double acc = 0.0;
+        for (int q = 0; q < nq; q++) acc = fma(tl[ak * nq + q], I[Ai + pk * (q + nq * R)], acc);
+        nxt[(size_t)es * szn + idx] = acc;
+      }
     }
     __syncthreads();
     double *sw = cur;
@@ -333,7 +478,8 @@ static int tg_pp_pow(int b, int e) {
   return r;
 }
 
-// checks the patch, fills what every mode shares; `u`: the nodal vector taken to the points (may be null)
+// checks the patch, fills what every mode shares; `u`: the nodal vector taken to the points (may be null).  mode: 0 - 3 as
+// the kernel's, 4 the flux load
 static int tg_pp_setup(const tg_patch_t *pt, int mode, tg_vec_t u, tg_pp_args *A, size_t *lds) {
   TG_REQUIRE_INIT();
   TG_REQUIRE(pt && pt->d >= 1 && pt->d <= 3 && pt->p >= 1 && pt->p <= TG_MAX_DEGREE && pt->nsd >= pt->d && pt->nsd <= 3,
@@ -390,6 +536,10 @@ static int tg_pp_setup(const tg_patch_t *pt, int mode, tg_vec_t u, tg_pp_args *A
     szA = std::max(szA, back);
     szB = std::max(szB, back);
   }
+  if (mode == 4) {     // the flux load goes back with up to d + 1 slots
+    szA = std::max(szA, (d + 1) * back);
+    szB = std::max(szB, (d + 1) * back);
+  }
   if (mode == 3) other = std::max(other, 3 * nqt);
   A->szA = szA;
   A->szB = szB;
@@ -412,6 +562,24 @@ static int tg_pp_launch(const tg_pp_args &A, size_t lds) {
                                      (int)TG_PP_LDS_MAX));
   hipLaunchKernelGGL((k_postproc<MODE>), dim3((unsigned)tg_cdiv(A.nelem, A.epg)), dim3(256), lds, g_tg.stream, A);
   TG_LAUNCH_CHECK();
+  return 0;
+}
+
+// one launch per colour (parity of the element index per direction), colours in ascending order
+template <int MODE>
+static int tg_pp_launch_colours(tg_pp_args &A, size_t lds) {
+  A.estep = 2;
+  for (int c = 0; c < (1 << A.d); c++) {
+    int64_t ne = 1;
+    for (int k = 0; k < A.d; k++) {
+      A.efirst[k] = (c >> k) & 1;
+      A.ncol[k] = A.nel[k] > A.efirst[k] ? (A.nel[k] - A.efirst[k] + 1) / 2 : 0;
+      ne *= A.ncol[k];
+    }
+    if (ne == 0) continue;
+    A.nelem = ne;
+    TG_TRY(tg_pp_launch<MODE>(A, lds));
+  }
   return 0;
 }
 
@@ -452,23 +620,62 @@ static int tg_pp_load(const tg_patch_t *patch, tg_vec_t f_q, tg_vec_t out, bool 
   A.fq = f_q->d;
   A.out = out->d;
   TG_CHECK_HIP(hipMemsetAsync(out->d, 0, (size_t)nnodes * sizeof(double), g_tg.stream));
-  // one launch per colour (parity of the element index per direction), colours in ascending order
-  A.estep = 2;
-  for (int c = 0; c < (1 << A.d); c++) {
-    int64_t ne = 1;
-    for (int k = 0; k < A.d; k++) {
-      A.efirst[k] = (c >> k) & 1;
-      A.ncol[k] = A.nel[k] > A.efirst[k] ? (A.nel[k] - A.efirst[k] + 1) / 2 : 0;
-      ne *= A.ncol[k];
-    }
-    if (ne == 0) continue;
-    A.nelem = ne;
-    if (rat)
-      TG_TRY(tg_pp_launch<2 | TG_PP_RAT>(A, lds));
-    else
-      TG_TRY(tg_pp_launch<2>(A, lds));
-  }
+  return rat ? tg_pp_launch_colours<2 | TG_PP_RAT>(A, lds) : tg_pp_launch_colours<2>(A, lds);
+}
+
+// ---- point coefficients.  The checks of the point arrays are shared: `n` values per point or null
+static int tg_pp_point_array(const char *who, const char *name, tg_vec_t v, int64_t n, int64_t npts, const double **out) {
+  *out = nullptr;
+  if (!v) return 0;
+  TG_REQUIRE(v->n == n * npts, "%s: %s holds %lld values, expected %lld per point of %lld points", who, name, (long long)v->n,
+             (long long)n, (long long)npts);
+  *out = v->d;
   return 0;
+}
+
+extern "C" int tg_coef_transform(const tg_patch_t *patch, int rational, int a_kind, tg_vec_t A_q, tg_vec_t b_q, tg_vec_t c_q,
+                                 tg_vec_t m_q, tg_vec_t coef_out) {
+  tg_pp_args A;
+  size_t lds;
+  TG_TRY(tg_pp_setup(patch, 0, nullptr, &A, &lds));
+  const int d = A.d, nsd = A.nsd;
+  TG_REQUIRE(a_kind >= 0 && a_kind <= 2 && (a_kind == 0) == (A_q == nullptr),
+             "tg_coef_transform: a_kind 0 = no diffusion (A_q null), 1 = one value per point, 2 = an nsd x nsd tensor per point");
+  TG_REQUIRE(coef_out && coef_out->n == (int64_t)(d * d + 2 * d + 1) * A.npts,
+             "tg_coef_transform: an output of (d^2 + 2 d + 1) npts = %lld values", (long long)((d * d + 2 * d + 1) * A.npts));
+  A.akind = a_kind;
+  TG_TRY(tg_pp_point_array("tg_coef_transform", "A_q", A_q, a_kind == 2 ? nsd * nsd : 1, A.npts, &A.Aq));
+  TG_TRY(tg_pp_point_array("tg_coef_transform", "b_q", b_q, nsd, A.npts, &A.bq));
+  TG_TRY(tg_pp_point_array("tg_coef_transform", "c_q", c_q, nsd, A.npts, &A.cq));
+  TG_TRY(tg_pp_point_array("tg_coef_transform", "m_q", m_q, 1, A.npts, &A.mq));
+  A.cout = coef_out->d;
+  return rational ? tg_pp_launch<TG_PP_COEF | TG_PP_RAT>(A, lds) : tg_pp_launch<TG_PP_COEF>(A, lds);
+}
+
+extern "C" int tg_flux_transform(const tg_patch_t *patch, int rational, tg_vec_t s_q, tg_vec_t F_q, tg_vec_t out) {
+  tg_pp_args A;
+  size_t lds;
+  TG_TRY(tg_pp_setup(patch, 0, nullptr, &A, &lds));
+  TG_REQUIRE(out && out->n == (int64_t)(A.d + 1) * A.npts, "tg_flux_transform: an output of (d + 1) npts = %lld values",
+             (long long)((A.d + 1) * A.npts));
+  TG_TRY(tg_pp_point_array("tg_flux_transform", "s_q", s_q, 1, A.npts, &A.sq));
+  TG_TRY(tg_pp_point_array("tg_flux_transform", "F_q", F_q, A.nsd, A.npts, &A.Fq));
+  A.cout = out->d;
+  return rational ? tg_pp_launch<TG_PP_FLUX | TG_PP_RAT>(A, lds) : tg_pp_launch<TG_PP_FLUX>(A, lds);
+}
+
+static int tg_pp_load_flux(const tg_patch_t *patch, tg_vec_t s_q, tg_vec_t F_q, tg_vec_t out, bool rat) {
+  tg_pp_args A;
+  size_t lds;
+  TG_TRY(tg_pp_setup(patch, 4, nullptr, &A, &lds));
+  int64_t nnodes = 1;
+  for (int k = 0; k < A.d; k++) nnodes *= A.n[k];
+  TG_REQUIRE(out && out->n == nnodes, "tg_quad_load_flux: an output on the %lld FE nodes", (long long)nnodes);
+  TG_TRY(tg_pp_point_array("tg_quad_load_flux", "s_q", s_q, 1, A.npts, &A.sq));
+  TG_TRY(tg_pp_point_array("tg_quad_load_flux", "F_q", F_q, A.nsd, A.npts, &A.Fq));
+  A.out = out->d;
+  TG_CHECK_HIP(hipMemsetAsync(out->d, 0, (size_t)nnodes * sizeof(double), g_tg.stream));
+  return rat ? tg_pp_launch_colours<2 | TG_PP_FLUX | TG_PP_RAT>(A, lds) : tg_pp_launch_colours<2 | TG_PP_FLUX>(A, lds);
 }
 
 static int tg_pp_error(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, tg_vec_t ge_q, double *out, bool rat) {
@@ -509,6 +716,12 @@ extern "C" int tg_quad_eval_rational(const tg_patch_t *patch, tg_vec_t u_nodal, 
   return tg_pp_eval(patch, u_nodal, with_grad, val_out, grad_out, true);
 }
 extern "C" int tg_quad_load_rational(const tg_patch_t *patch, tg_vec_t f_q, tg_vec_t out) { return tg_pp_load(patch, f_q, out, true); }
+extern "C" int tg_quad_load_flux(const tg_patch_t *patch, tg_vec_t s_q, tg_vec_t F_q, tg_vec_t out) {
+  return tg_pp_load_flux(patch, s_q, F_q, out, false);
+}
+extern "C" int tg_quad_load_flux_rational(const tg_patch_t *patch, tg_vec_t s_q, tg_vec_t F_q, tg_vec_t out) {
+  return tg_pp_load_flux(patch, s_q, F_q, out, true);
+}
 extern "C" int tg_quad_error_rational(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, tg_vec_t ge_q, double *out) {
   return tg_pp_error(patch, u_nodal, e_q, ge_q, out, true);
 }

@@ -1206,6 +1206,57 @@ def quad_error(vertices, p, cp, u=None, e=None, ge=None, nq=None, rational=False
     return float(out[0]), float(out[1]), float(out[2])
 
 
+def _h_or_none(v):
+    return v._h if v is not None else None
+
+
+def coef_transform(vertices, p, cp, A=None, b=None, c=None, m=None, a_kind=None, nq=None, rational=False):
+    """The point coefficients of a(u,v) = int grad v . (A grad u) + (b . grad v) u + v (c . grad u) + m u v dx brought to the
+    reference element (``tg_coef_transform``): a DeviceVector of (d^2 + 2 d + 1) * npts values, component-major, which
+    ``assemble_coef_matrix`` takes.  ``A``: npts values (isotropic, ``a_kind`` 1) or nsd * nsd * npts (a tensor per point,
+    ``a_kind`` 2; told apart by the size when ``a_kind`` is None); ``b``, ``c``: nsd * npts; ``m``: npts; DeviceVectors
+    numbered as ``quad_points``, None = zero.  ``rational``: functions phi / W_h, beta folded into the data."""
+    nq = p + 1 if nq is None else nq
+    pt, keep = _patch(vertices, p, cp, nq)
+    d, npts = len(vertices), quad_count(vertices, nq)
+    if a_kind is None:
+        a_kind = 0 if A is None else (1 if A.size() == npts else 2)
+    out = DeviceVector((d * d + 2 * d + 1) * npts, zero=False)
+    check(_lib.lib().tg_coef_transform(C.byref(pt), 1 if rational else 0, int(a_kind), _h_or_none(A), _h_or_none(b),
+                                       _h_or_none(c), _h_or_none(m), out._h), "tg_coef_transform")
+    return out
+
+
+def flux_transform(vertices, p, cp, s=None, F=None, nq=None, rational=False):
+    """(s^, F^) of L(v) = int s v + F . grad v dx on the reference element: (d + 1) * npts values (``tg_flux_transform``)"""
+    nq = p + 1 if nq is None else nq
+    pt, keep = _patch(vertices, p, cp, nq)
+    out = DeviceVector((len(vertices) + 1) * quad_count(vertices, nq), zero=False)
+    check(_lib.lib().tg_flux_transform(C.byref(pt), 1 if rational else 0, _h_or_none(s), _h_or_none(F), out._h),
+          "tg_flux_transform")
+    return out
+
+
+def assemble_coef_matrix(vertices, p, cp, coef, nq=None):
+    """the matrix of the transformed point coefficients ``coef`` (``coef_transform``) on the element-coupling pattern
+    (``tg_assemble_coef_matrix``)"""
+    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
+    h = handle()
+    check(_lib.lib().tg_assemble_coef_matrix(C.byref(pt), coef._h, C.byref(h)), "tg_assemble_coef_matrix")
+    return DeviceCSR(h)
+
+
+def quad_load_flux(vertices, p, cp, s=None, F=None, nq=None, rational=False):
+    """L(v) = sum_q wdet_q (s_q v + F_q . grad v)(xi_q) for point values ``s`` (npts) and ``F`` (nsd * npts,
+    component-major), either may be None (``tg_quad_load_flux``; ``rational``: v = phi / W_h,
+    ``tg_quad_load_flux_rational``)."""
+    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
+    out = DeviceVector(n=cp[0].size(), zero=False)          # (the entry zeroes it before the colours add)
+    name = "tg_quad_load_flux_rational" if rational else "tg_quad_load_flux"
+    check(getattr(_lib.lib(), name)(C.byref(pt), _h_or_none(s), _h_or_none(F), out._h), name)
+    return out
+
+
 def face_count(vertices, direction, nq):
     """number of Gauss points of the face (direction, side): nq^(d-1) per face element"""
     n = 1
@@ -1252,10 +1303,6 @@ def face_load(vertices, p, cp, direction, side, fq, fnq, out, nq=None, rational=
     check(getattr(_lib.lib(), name)(C.byref(pt), int(direction), int(side), fq._h if fq is not None else None,
                                     fnq._h if fnq is not None else None, out._h), name)
     return out
-
-
-def _h_or_none(v):
-    return v._h if v is not None else None
 
 
 def face_matrix(vertices, p, cp, direction, side, a=None, b=None, c=None, nq=None, rational=False):

@@ -9,6 +9,8 @@ on the knot mesh so that the path can be driven (and benchmarked) without FEniCS
     MassForm()               a(u,v) = (u, v)
     SeparableLoadForm(f1d)   L(v)   = (f, v) with f(x) = scale * prod_k f1d[k](x_k)
     QuadratureLoadForm(f, geometry)   L(v) = (f, v) on a mapped patch, f given at the quadrature points
+    CoefficientForm(geometry, ...)    a(u,v) with diffusion, advection and reaction coefficients at the quadrature points
+    QuasilinearResidual(u, geometry, residual, tangent)   Newton on a point-wise nonlinear flux / source
 
 Quadrature: Gauss-Legendre with p+1 points per direction (what ``quadrature_degree = 2p``
 selects on quads/hexes [ext], demos/poisson/poisson.py:89).  The d-dimensional objects are
@@ -503,11 +505,15 @@ class QuadratureLoadForm(object):
     per geometry), a number, the ``npts`` point values (array / DeviceVector, numbered as ``QuadraturePoints``), or a
     ``Function`` on the space.  ``nq`` Gauss points per direction (p + 1 when None).  ``rational``: v the test functions
     phi / W_h; a ``Function`` given as ``f`` is still read un-rationalised -- hand in
-    ``spline.evaluateAtQuadrature(f, rational=True)`` for its rational values."""
+    ``spline.evaluateAtQuadrature(f, rational=True)`` for its rational values.  ``flux``: adds int F . grad v dx with the
+    Cartesian gradient (``tg_quad_load_flux``); ``F`` a callable ``x -> [npts, nsd]``, an array of that shape, nsd numbers
+    or a DeviceVector of nsd * npts values, component-major; ``f`` may then be None."""
 
-    def __init__(self, f, geometry, nq=None, rational=False):
-        self.f, self.geometry, self.nq = f, geometry, nq
+    def __init__(self, f, geometry, nq=None, rational=False, flux=None):
+        self.f, self.geometry, self.nq, self.flux = f, geometry, nq, flux
         self.rational = _need_geometry("QuadratureLoadForm", geometry, rational)
+        if flux is not None and geometry is None:
+            raise ValueError("QuadratureLoadForm: the flux term is integrated on a mapped patch (geometry=...)")
 
     def point_values(self, V):
         pts = quadrature_points(self.geometry, V, self.nq, "QuadratureLoadForm")
@@ -520,12 +526,26 @@ class QuadratureLoadForm(object):
         return pts, pts.values(self.f, "QuadratureLoadForm")
 
     def assemble_vector(self, V, row0=None, row1=None):
+        if self.flux is not None:
+            _point_form_scope(self.geometry, "QuadratureLoadForm")
         n = _single_grid(V).num_nodes()
         if (0 if row0 is None else int(row0), n if row1 is None else int(row1)) != (0, n):
             raise NotImplementedError("QuadratureLoadForm: row blocks (several ranks, streamed operands) are not supported; "
                                       "the point values are numbered over the whole patch")
-        pts, fq = self.point_values(V)
-        return _dev.quad_load(pts.verts, pts.p, pts.cp, fq, nq=pts.nq, rational=self.rational)
+        if self.flux is None:
+            pts, fq = self.point_values(V)
+            return _dev.quad_load(pts.verts, pts.p, pts.cp, fq, nq=pts.nq, rational=self.rational)
+        pts, fq = self.point_values(V) if self.f is not None else \
+            (quadrature_points(self.geometry, V, self.nq, "QuadratureLoadForm"), None)
+        if callable(self.flux):
+            cache = self.__dict__.setdefault("_Fq", {})
+            if id(pts) not in cache:
+                cache.clear()
+                cache[id(pts)] = (pts.vector_values(self.flux, "QuadratureLoadForm: flux"), pts)     # (pts kept alive: id)
+            Fq = cache[id(pts)][0]
+        else:
+            Fq = pts.vector_values(self.flux, "QuadratureLoadForm: flux")
+        return _dev.quad_load_flux(pts.verts, pts.p, pts.cp, fq, Fq, nq=pts.nq, rational=self.rational)
 
 
 class SeparableLoadForm(object):
@@ -648,6 +668,189 @@ class _SemilinearTangent(object):
         return K.combine(1.0, Mm, 1.0, self.res.dg(uv))
 
 
+# ---- volume forms with point coefficients (csrc/tg_coef.hip) ---------------------------------------------------------------
+def _point_form_scope(geometry, who):
+    """Refuses what the forms with point data do not cover: an ExtractedSpline says itself what its quadrature-point
+    operands serve (one rank, the order of the node grid, one scalar field on the control mesh's basis)"""
+    if geometry is None:
+        raise ValueError("%s: point coefficients live on a mapped patch (geometry=...)" % who)
+    scope = getattr(geometry, "_quadrature_scope", None)
+    if scope is not None:
+        scope(who)
+    _fields_of_the_patch(geometry, who)
+
+
+def _same_bits(a, b):
+    a, b = numpy.ascontiguousarray(a, dtype=numpy.float64), numpy.ascontiguousarray(b, dtype=numpy.float64)
+    return a.shape == b.shape and numpy.array_equal(a.view(numpy.int64), b.view(numpy.int64))
+
+
+def _tensor_values(pts, A, who):
+    """(kind, DeviceVector, symmetric) of a diffusion given at the points: kind 1 = one value per point, 2 = an nsd x nsd
+    tensor per point (component (i, j) of point q at (i nsd + j) npts + q)"""
+    nsd, npts = pts.nsd, pts.npts
+    if isinstance(A, _dev.DeviceVector):
+        if A.size() == npts:
+            return 1, A, True
+        if A.size() != nsd * nsd * npts:
+            raise ValueError("%s: %d values given, expected npts = %d or nsd * nsd * npts = %d"
+                             % (who, A.size(), npts, nsd * nsd * npts))
+        h = A.get_local().reshape(nsd, nsd, npts)
+        return 2, A, _same_bits(h, h.transpose(1, 0, 2))
+    if hasattr(A, "vector") and hasattr(A, "function_space") or numpy.ndim(A) == 0 and not callable(A):
+        return 1, pts.values(A, who), True
+    v = numpy.asarray(A(pts.x) if callable(A) else A, dtype=numpy.float64)
+    if v.shape == (npts,):
+        return 1, _dev.DeviceVector(data=v), True
+    if v.shape == (nsd, nsd):
+        v = numpy.tile(v, (npts, 1, 1))
+    if v.shape != (npts, nsd, nsd):
+        raise ValueError("%s: an array of shape %s for %d points; expected (%d,) or (%d, %d, %d)"
+                         % (who, v.shape, npts, npts, npts, nsd, nsd))
+    return 2, _dev.DeviceVector(data=numpy.ascontiguousarray(v.transpose(1, 2, 0)).ravel()), _same_bits(v, v.transpose(0, 2, 1))
+
+
+class CoefficientForm(object):
+    """a(u, v) = int grad v . (A grad u) + (b . grad v) u + v (c . grad u) + m u v dx on the mapped patch, with coefficients
+    given AT THE QUADRATURE POINTS: ``diffusion`` A, ``flux_velocity`` b, ``velocity`` c, ``reaction`` m (u the trial
+    function = column, v the test function = row; grad and dx as ``spline.grad`` / ``spline.dx``).  What a user of the
+    reference writes as ``kappa*inner(spline.grad(u), spline.grad(v))*spline.dx``, an advection-diffusion-reaction operator,
+    or the Newton tangent of a scalar quasilinear equation (``QuasilinearResidual``).
+
+    Every coefficient: a number, a callable of the points ``x [npts, nsd]``, or point values (array / DeviceVector,
+    numbered as ``QuadraturePoints``); the scalar ones (an isotropic ``diffusion``, ``reaction``) also a ``Function`` of the
+    space, read at assembly time.  ``diffusion`` may be ``[npts, nsd, nsd]`` (or a callable returning that, or one nsd x nsd
+    matrix): a full tensor per point, which need not be symmetric.  Vectors: ``[npts, nsd]``, nsd numbers, or a
+    DeviceVector of nsd * npts values, component-major.  ``nq`` Gauss points per direction (p + 1 when None).
+    ``rational``: trial and test functions phi / W_h.
+
+    ``symmetric`` is True only when the inputs prove it: A isotropic or bitwise equal to its transpose, and b and c both
+    absent or bitwise equal.  The matrix lies on the element-coupling pattern with its certificate, as every mapped form's:
+    the PtAP routes, plan caches and solvers serve it unchanged.  One rank, all rows (``tg_coef_transform``,
+    ``tg_assemble_coef_matrix``)."""
+
+    def __init__(self, geometry, diffusion=None, flux_velocity=None, velocity=None, reaction=None, nq=None, rational=False):
+        if geometry is None:
+            raise ValueError("CoefficientForm: point coefficients live on a mapped patch (geometry=...)")
+        self.geometry, self.nq, self.rational = geometry, nq, bool(rational)
+        self.diffusion, self.flux_velocity, self.velocity, self.reaction = diffusion, flux_velocity, velocity, reaction
+
+    @staticmethod
+    def _is_function(f):
+        return hasattr(f, "vector") and hasattr(f, "function_space")
+
+    def coefficients(self, V):
+        """(points, kind of A, A, b, c, m, symmetric) with the point data as DeviceVectors (None = absent).  What does not
+        depend on a Function is computed once per set of points."""
+        who = "CoefficientForm"
+        _point_form_scope(self.geometry, who)
+        pts = quadrature_points(self.geometry, V, self.nq, who)
+        cache = self.__dict__.setdefault("_static", {})
+        if id(pts) not in cache:
+            cache.clear()
+            kind, A, symA = 0, None, True
+            if self.diffusion is not None and not self._is_function(self.diffusion):
+                kind, A, symA = _tensor_values(pts, self.diffusion, who + ": diffusion")
+            b = pts.vector_values(self.flux_velocity, who + ": flux_velocity") if self.flux_velocity is not None else None
+            c = pts.vector_values(self.velocity, who + ": velocity") if self.velocity is not None else None
+            m = None
+            if self.reaction is not None and not self._is_function(self.reaction):
+                m = pts.values(self.reaction, who + ": reaction")
+            symbc = (b is None and c is None) or (b is not None and c is not None and
+                                                   (b is c or _same_bits(b.get_local(), c.get_local())))
+            cache[id(pts)] = (pts, kind, A, b, c, m, bool(symA and symbc))
+        pts, kind, A, b, c, m, sym = cache[id(pts)]
+        if self._is_function(self.diffusion):
+            kind, A = 1, pts.values(self.diffusion, who + ": diffusion")
+        if self._is_function(self.reaction):
+            m = pts.values(self.reaction, who + ": reaction")
+        return pts, kind, A, b, c, m, sym
+
+    @property
+    def symmetric(self):
+        return self.coefficients(self.geometry.V_control)[6]
+
+    def assemble_matrix(self, V, row0=None, row1=None):
+        _point_form_scope(self.geometry, "CoefficientForm")
+        _whole_rows(_single_grid(V).num_nodes(), row0, row1, "CoefficientForm", "patch")
+        pts, kind, A, b, c, m, _ = self.coefficients(V)
+        coef = _dev.coef_transform(pts.verts, pts.p, pts.cp, A, b, c, m, a_kind=kind, nq=pts.nq, rational=self.rational)
+        return _dev.assemble_coef_matrix(pts.verts, pts.p, pts.cp, coef, nq=pts.nq)
+
+
+class QuasilinearResidual(object):
+    """Residual of a scalar quasilinear equation  -div flux(x, u, grad u) + source(x, u, grad u) = f  in weak form,
+    R(v) = int flux . grad v + source v - f v dx, with the nonlinearity evaluated AT THE QUADRATURE POINTS (what
+    ``derivative(residual, u)`` of the reference works on; ``SemilinearResidual`` is the group-FE product approximation).
+
+    ``residual(x, u_q, grad_q) -> (flux [npts, nsd] | None, source [npts] | None)`` and
+    ``tangent(x, u_q, grad_q) -> (A, b, c, m)`` = (d flux / d grad u [npts, nsd, nsd] or [npts], d flux / d u [npts, nsd],
+    d source / d grad u [npts, nsd], d source / d u [npts]), any of them None, are host callables of the points
+    ``x [npts, nsd]`` and of ``u`` and its Cartesian gradient there.  ``u``: the current FE ``Function``, read at assembly
+    time through the kernel of ``evaluateAtQuadrature(u, grad=True, rational=...)``.  ``f``: as for
+    ``QuadratureLoadForm``.  ``assemble_vector`` is the flux load minus the load of ``f``; ``tangent()`` the form whose
+    ``assemble_matrix`` is the ``CoefficientForm`` of the tangent data.  Runs under ``solveNonlinearVariationalProblem``
+    and inside ``Sum`` with the boundary forms.  ``rational``: u = u_h / W_h, tested against phi / W_h."""
+
+    def __init__(self, u, geometry, residual, tangent, f=None, nq=None, rational=False):
+        if geometry is None:
+            raise ValueError("QuasilinearResidual: point coefficients live on a mapped patch (geometry=...)")
+        self.u, self.geometry, self.residual, self._tangent = u, geometry, residual, tangent
+        self.f, self.nq, self.rational = f, nq, bool(rational)
+        self._load = QuadratureLoadForm(f, geometry, nq, rational=rational) if f is not None else None
+
+    def state(self, V):
+        """(points, u at the points [npts], its Cartesian gradient [npts, nsd]) on the host"""
+        who = "QuasilinearResidual"
+        _point_form_scope(self.geometry, who)
+        pts = quadrature_points(self.geometry, V, self.nq, who)
+        uv = self.u.vector() if hasattr(self.u, "vector") else self.u
+        if uv.size() != _single_grid(V).num_nodes():
+            raise ValueError("%s: u holds %d nodal values, the space has %d" % (who, uv.size(), _single_grid(V).num_nodes()))
+        val, g = _dev.quad_eval(pts.verts, pts.p, pts.cp, uv, grad=True, nq=pts.nq, rational=self.rational)
+        return pts, val.get_local(), numpy.ascontiguousarray(g.get_local().reshape(pts.nsd, pts.npts).T)
+
+    def assemble_vector(self, V, row0=None, row1=None):
+        _point_form_scope(self.geometry, "QuasilinearResidual")
+        _whole_rows(_single_grid(V).num_nodes(), row0, row1, "QuasilinearResidual", "patch")
+        pts, uq, gq = self.state(V)
+        out = self.residual(pts.x, uq, gq)
+        if not isinstance(out, tuple) or len(out) != 2:
+            raise ValueError("QuasilinearResidual: residual(x, u, grad u) returns (flux or None, source or None)")
+        F = pts.vector_values(out[0], "QuasilinearResidual: flux") if out[0] is not None else None
+        s = pts.values(out[1], "QuasilinearResidual: source") if out[1] is not None else None
+        r = _dev.quad_load_flux(pts.verts, pts.p, pts.cp, s, F, nq=pts.nq, rational=self.rational)
+        if self._load is not None:
+            r.axpy(-1.0, self._load.assemble_vector(V))
+        return r
+
+    def tangent(self):
+        return _QuasilinearTangent(self)
+
+
+class _QuasilinearTangent(object):
+    """``symmetric`` is that of the last assembled tangent and False before the first assembly: the tangent data depend on
+    the state, so nothing is proved until they have been seen.  A ``Sum`` reads the attribute when it is BUILT and so takes
+    this term for non-symmetric, which is the safe side; on a mapped patch the attribute informs the caller only
+    (``assembleMatrix`` uses it for forms without a geometry)."""
+
+    def __init__(self, res):
+        self.res, self.geometry, self.symmetric = res, res.geometry, False
+
+    def assemble_matrix(self, V, row0=None, row1=None):
+        res = self.res
+        _point_form_scope(res.geometry, "QuasilinearResidual.tangent")
+        _whole_rows(_single_grid(V).num_nodes(), row0, row1, "QuasilinearResidual.tangent", "patch")
+        pts, uq, gq = res.state(V)
+        out = res._tangent(pts.x, uq, gq)
+        if not isinstance(out, tuple) or len(out) != 4:
+            raise ValueError("QuasilinearResidual: tangent(x, u, grad u) returns (A, b, c, m), any of them None")
+        form = CoefficientForm(res.geometry, out[0], out[1], out[2], out[3], nq=res.nq, rational=res.rational)
+        A = form.assemble_matrix(V)
+        self.symmetric = form.coefficients(V)[6]
+        return A
+
+
 # ---- boundary integrals on a mapped patch (csrc/tg_boundary.hip): spline.ds and spline.n of the reference -----------------
 def _periodic_directions(geometry):
     """directions whose knot vector is not open (the faces there are no boundary), as far as the geometry tells"""
@@ -723,10 +926,10 @@ def _fields_of_the_patch(geometry, who):
                                   "(FieldListSpline and compatible spaces are not supported)" % (who, type(gen).__name__))
 
 
-def _whole_rows(n, row0, row1, who):
+def _whole_rows(n, row0, row1, who, over="face"):
     if (0 if row0 is None else int(row0), n if row1 is None else int(row1)) != (0, n):
         raise NotImplementedError("%s: row blocks (several ranks, streamed operands) are not supported; the point values "
-                                  "are numbered over the whole face" % who)
+                                  "are numbered over the whole %s" % (who, over))
 
 
 class FacePoints(QuadraturePoints):
