@@ -670,6 +670,28 @@ int tg_flux_transform(const tg_patch_t *patch, int rational, tg_vec_t s_q, tg_ve
  * the cache of the reference-element tables only.  Nothing ties `coef` to the patch, nq or rational setting it was
  * transformed for but its length: a mismatch of nq between transform and assembly is caught only when the sizes differ. */
 int tg_assemble_coef_matrix(const tg_patch_t *patch, tg_vec_t coef, tg_csr_t *out);
+/* ---- vector-valued unknowns with a point tangent: nF = nsd = d (2 or 3) fields on the scalar Q_p space, dofs field after
+ * field (the space of the mapped elasticity form), a(u, v) = int d_K v_i A_iKjL d_L u_j + v_i M_ij u_j dx.
+ * tg_coef_transform_blocks: A_q holds A_iKjL at (((i nF + j) nsd + K) nsd + L) npts + q -- block (i, j) a contiguous nsd x nsd
+ * tensor in the layout of a_kind = 2 --, M_q (may be null) M_ij at (i nF + j) npts + q.  coef_out: nF^2 consecutive scalar
+ * coefficient sets of (d^2 + 2 d + 1) npts values each, block (i, j) at (i nF + j), every one in the layout of
+ * tg_coef_transform (rational: b', c', m' per block as there).  One pass: the geometry of a point is formed once for all
+ * blocks (an ending of k_postproc).
+ * tg_assemble_coef_blocks: every block through tg_assemble_coef_matrix on a view of its slice (same routes and environment
+ * variables), then tg_csr_from_blocks: the nF n x nF n matrix, rows and columns field-major.
+ * Point data held at the peak of one tangent assembly: A_q (d^4 npts) and the transformed sets (d^2 (d^2 + 2 d + 1) npts),
+ * i.e. (d^4 + 16 d^2) npts = 225 npts doubles at d = 3 (52 npts at d = 2). */
+int tg_coef_transform_blocks(const tg_patch_t *patch, int rational, int nF, tg_vec_t A_q, tg_vec_t M_q, tg_vec_t coef_out);
+int tg_assemble_coef_blocks(const tg_patch_t *patch, int nF, tg_vec_t coef_blocks, tg_csr_t *out);
+/* ---- material laws at the points (csrc/tg_material.hip): F = I + grad u, J = det F, C = F^T F, nsd = 2 (plane strain) or 3.
+ * gradu: d u_i / d x_K at (i nsd + K) npts + q; P_out: the first Piola-Kirchhoff stress in the same layout; A_out:
+ * A_iKjL = d P_iK / d F_jL in the layout of tg_coef_transform_blocks; psi_out: the energy density; any output may be null.
+ * params = {lambda, mu} (host).  kind 0 linear: psi = lambda/2 (tr eps)^2 + mu eps:eps; 1 St. Venant-Kirchhoff:
+ * S = lambda tr E I + 2 mu E, P = F S; 2 compressible neo-Hookean: psi = mu/2 (tr C - nsd) - mu ln J + lambda/2 (ln J)^2.
+ * Kind 2 writes nothing at a point with J <= 0; *nbad counts those points, *Jmin is the smallest J of all points (any kind;
+ * kinds 0 and 1 count no point).  Integer atomics only: the same bits in every run.  Synchronises the stream. */
+int tg_material_points(int kind, const double *params, int nsd, int64_t npts, tg_vec_t gradu, tg_vec_t P_out, tg_vec_t A_out,
+                       tg_vec_t psi_out, int64_t *nbad, double *Jmin);
 /* out[node] = sum_q wdet_q (s_q phi_node + F_q . grad phi_node)(xi_q), the Cartesian gradient; either array may be null.
  * _rational: tested against phi / W_h.  Sum-factorised both ways, added colour by colour as tg_quad_load. */
 int tg_quad_load_flux(const tg_patch_t *patch, tg_vec_t s_q, tg_vec_t F_q, tg_vec_t out);

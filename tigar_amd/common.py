@@ -2048,6 +2048,28 @@ class ExtractedSpline(object):
             raise NotImplementedError("%s: the FE space is not the continuous Q_p space of a single tensor-product patch "
                                       "(FieldListSpline, compatible, multi-patch, T-spline and DG spaces are not supported)" % who)
 
+    def _vector_quadrature_scope(self, who):
+        """As ``_quadrature_scope`` for the point forms of a vector-valued unknown: nFields = nsd fields, all on the control
+        mesh's scalar basis (``EqualOrderSpline(nsd, mesh)``: one continuous Q_p node grid, dofs field after field)."""
+        if self._distributed():
+            raise NotImplementedError("%s: several ranks are not supported (the point values are numbered over the whole "
+                                      "patch)" % who)
+        if self._implicit():
+            raise NotImplementedError("%s: the streamed engine asks its forms for row blocks, which the quadrature-point "
+                                      "forms do not hand out" % who)
+        if self._caller_ordered():
+            raise NotImplementedError("%s: a spline with the caller's FE dof order (feOrder) is not supported; the point "
+                                      "kernels number the node grid" % who)
+        if isinstance(getattr(self, "_generator", None), FieldListSpline):
+            raise NotImplementedError("%s: FieldListSpline spaces (fields on their own bases) are not supported" % who)
+        grids = getattr(self.V, "grids", None)
+        if grids is None or len(grids) != self.nFields or any(not isinstance(g, TensorNodeGrid) or g.dg for g in grids):
+            raise NotImplementedError("%s: the FE fields are not continuous Q_p fields of a single tensor-product patch "
+                                      "(FieldListSpline, compatible, multi-patch, T-spline and DG spaces are not supported)" % who)
+        if self.nFields != self.nsd:
+            raise NotImplementedError("%s: nFields = %d on a patch with nsd = %d; the displacement has as many fields as "
+                                      "there are physical directions" % (who, self.nFields, self.nsd))
+
     def quadraturePoints(self, nq=None):
         """The Gauss points of the patch (``nq`` per direction, p + 1 when None) as a ``forms.QuadraturePoints``: ``.x``
         (host array [npts, nsd], downloaded on first use), ``.x_device``, ``.weights`` (DeviceVector of w_q sqrt(det g)

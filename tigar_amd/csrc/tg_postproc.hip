@@ -11,6 +11,7 @@
 //   tg_quad_load     out[node] = sum_q wdet_q f_q phi_node(xi_q)
 //   tg_quad_error    sum wdet (u_h - e)^2,  sum wdet |grad u_h - ge|^2,  sum wdet e^2
 //   tg_coef_transform / tg_flux_transform   Cartesian point coefficients -> the reference element (formulas: tg_coef.hip)
+//   tg_coef_transform_blocks   the same for the nF^2 blocks of a vector-valued unknown's tangent, the geometry formed once
 //   tg_quad_load_flux   out[node] = sum_q wdet_q (s_q phi_node + F_q . grad phi_node)(xi_q)
 //
 // One kernel, four endings (and the three that take point coefficients).  A workgroup of 256 threads takes max(1, 256 / nq^d) elements (fewer where
@@ -53,6 +54,7 @@ struct tg_pp_args {
   const double *Aq, *bq, *cq, *mq;   // a(u, v) = int grad v . (A grad u) + (b . grad v) u + v (c . grad u) + m u v
   const double *sq, *Fq;       // L(v) = int s v + F . grad v
   double *cout;                // the data on the reference element, component-major
+  int nblk;                    // TG_PP_BLOCKS: Aq, mq and cout hold this many consecutive sets (a tensor per point each)
 };
 
 __device__ __forceinline__ bool tg_pp_has(int c, const tg_pp_args &P) { return c < 3 ? c < P.nsd : P.f[c] != nullptr; }
@@ -78,15 +80,19 @@ __device__ __forceinline__ int64_t tg_pp_node(const tg_pp_args &P, const int *el
 // MODE 0 points, 1 eval, 2 load, 3 error; + 4 (TG_PP_RAT): rational functions (eval, load, error)
 // Point coefficients (tg_coef.hip has the formulas): 0 + TG_PP_COEF writes the d^2 + 2d + 1 reference-element coefficients
 // of the matrix form in the place of the points, 0 + TG_PP_FLUX the d + 1 of the load; 2 + TG_PP_FLUX is the load of
-// s v + F . grad v.  All three take TG_PP_RAT: beta is folded into the data.
+// s v + F . grad v.  All three take TG_PP_RAT: beta is folded into the data.  TG_PP_COEF + TG_PP_BLOCKS: the coefficient ending
+// looped over nblk sets of (tensor, reaction) -- the nF^2 blocks of a vector-valued unknown's tangent (tg_material.hip) --
+// with the point's geometry (P = DF g^-1, wdet, W, beta) computed once.
 #define TG_PP_RAT 4
 #define TG_PP_COEF 8
 #define TG_PP_FLUX 16
+#define TG_PP_BLOCKS 32
 template <int MODER>
 __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
   constexpr int MODE = MODER & 3;
   constexpr bool RAT = (MODER & TG_PP_RAT) != 0;
-  constexpr bool COEF = (MODER & TG_PP_COEF) != 0, FLUX = (MODER & TG_PP_FLUX) != 0;
+  constexpr bool COEF = (MODER & TG_PP_COEF) != 0, FLUX = (MODER & TG_PP_FLUX) != 0, BLK = (MODER & TG_PP_BLOCKS) != 0;
+  static_assert(!BLK || COEF, "the blocks are sets of point coefficients");
   static_assert(!(RAT && MODE == 0 && !COEF && !FLUX), "the points do not depend on the function space");
   static_assert(!(COEF && (MODE != 0 || FLUX)) && !(FLUX && MODE != 0 && MODE != 2), "endings that take point coefficients");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -252,79 +258,89 @@ __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
       for (int k = 0; k < 3; k++) bt[k] = RAT ? dN[3][k] / W : 0.0;
       [[maybe_unused]] const double rw = 1.0 / W;
       if constexpr (COEF) {
-        double Ch[3][3] = {{0}}, bh[3] = {0, 0, 0}, ch[3] = {0, 0, 0}, mh = 0.0;
-        if (P.akind == 1) {            // P^T P = g^-1
-          const double a = wdet * P.Aq[gp];
+        const int nblk = BLK ? P.nblk : 1;
+        for (int blk = 0; blk < nblk; blk++) {
+          const double *Aq = P.Aq, *mq = P.mq;
+          double *co = P.cout;
+          if constexpr (BLK) {           // set blk: an nsd x nsd tensor and (optionally) a reaction value per point
+            Aq += (int64_t)blk * nsd * nsd * P.npts;
+            if (mq) mq += (int64_t)blk * P.npts;
+            co += (int64_t)blk * (d * d + 2 * d + 1) * P.npts;
+          }
+          double Ch[3][3] = {{0}}, bh[3] = {0, 0, 0}, ch[3] = {0, 0, 0}, mh = 0.0;
+          if (P.akind == 1) {            // P^T P = g^-1
+            const double a = wdet * Aq[gp];
 #pragma unroll
-          for (int k = 0; k < 3; k++)
+            for (int k = 0; k < 3; k++)
 #pragma unroll
-            for (int m = 0; m < 3; m++) Ch[k][m] = a * gi[k][m];
-        } else if (P.akind == 2) {
-          double T[3][3] = {{0}};      // A P
+              for (int m = 0; m < 3; m++) Ch[k][m] = a * gi[k][m];
+          } else if (P.akind == 2) {
+            double T[3][3] = {{0}};      // A P
 #pragma unroll
-          for (int c = 0; c < 3; c++)
+            for (int c = 0; c < 3; c++)
 #pragma unroll
-            for (int e = 0; e < 3; e++) {
-              if (c >= nsd || e >= nsd) continue;
-              const double a = P.Aq[(int64_t)(c * nsd + e) * P.npts + gp];
+              for (int e = 0; e < 3; e++) {
+                if (c >= nsd || e >= nsd) continue;
+                const double a = Aq[(int64_t)(c * nsd + e) * P.npts + gp];
 #pragma unroll
-              for (int m = 0; m < 3; m++) T[c][m] = fma(a, Pm[e][m], T[c][m]);
+                for (int m = 0; m < 3; m++) T[c][m] = fma(a, Pm[e][m], T[c][m]);
+              }
+#pragma unroll
+            for (int k = 0; k < 3; k++)
+#pragma unroll
+              for (int m = 0; m < 3; m++) Ch[k][m] = wdet * (Pm[0][k] * T[0][m] + Pm[1][k] * T[1][m] + Pm[2][k] * T[2][m]);
+          }
+#pragma unroll
+          for (int c = 0; c < 3; c++) {
+            if (c >= nsd) continue;
+            const double bc = P.bq ? wdet * P.bq[(int64_t)c * P.npts + gp] : 0.0;
+            const double cc = P.cq ? wdet * P.cq[(int64_t)c * P.npts + gp] : 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+              bh[k] = fma(Pm[c][k], bc, bh[k]);
+              ch[k] = fma(Pm[c][k], cc, ch[k]);
+            }
+          }
+          if (mq) mh = wdet * mq[gp];
+          if constexpr (RAT) {
+            // psi = phi / W, grad_xi psi = (grad_xi phi - phi beta) / W: everything takes 1 / W^2, then the terms with beta move
+            // from the tensor to the vectors and from the vectors to the scalar
+            const double rw2 = rw * rw;
+            double Cb[3], Ctb[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+#pragma unroll
+              for (int m = 0; m < 3; m++) Ch[k][m] *= rw2;
+              bh[k] *= rw2;
+              ch[k] *= rw2;
             }
 #pragma unroll
+            for (int k = 0; k < 3; k++) {
+              Cb[k] = Ch[k][0] * bt[0] + Ch[k][1] * bt[1] + Ch[k][2] * bt[2];
+              Ctb[k] = Ch[0][k] * bt[0] + Ch[1][k] * bt[1] + Ch[2][k] * bt[2];
+            }
+            mh = mh * rw2 - (bt[0] * bh[0] + bt[1] * bh[1] + bt[2] * bh[2]) - (bt[0] * ch[0] + bt[1] * ch[1] + bt[2] * ch[2]) +
+                 (bt[0] * Cb[0] + bt[1] * Cb[1] + bt[2] * Cb[2]);
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+              bh[k] -= Cb[k];
+              ch[k] -= Ctb[k];
+            }
+          }
+          double *o = co + gp;           // C (row-major d x d) | b | c | m
+#pragma unroll
           for (int k = 0; k < 3; k++)
 #pragma unroll
-            for (int m = 0; m < 3; m++) Ch[k][m] = wdet * (Pm[0][k] * T[0][m] + Pm[1][k] * T[1][m] + Pm[2][k] * T[2][m]);
+            for (int m = 0; m < 3; m++)
+              if (k < d && m < d) o[(int64_t)(k * d + m) * P.npts] = Ch[k][m];
+#pragma unroll
+          for (int k = 0; k < 3; k++)
+            if (k < d) {
+              o[(int64_t)(d * d + k) * P.npts] = bh[k];
+              o[(int64_t)(d * d + d + k) * P.npts] = ch[k];
+            }
+          o[(int64_t)(d * d + 2 * d) * P.npts] = mh;
         }
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-          if (c >= nsd) continue;
-          const double bc = P.bq ? wdet * P.bq[(int64_t)c * P.npts + gp] : 0.0;
-          const double cc = P.cq ? wdet * P.cq[(int64_t)c * P.npts + gp] : 0.0;
-#pragma unroll
-          for (int k = 0; k < 3; k++) {
-            bh[k] = fma(Pm[c][k], bc, bh[k]);
-            ch[k] = fma(Pm[c][k], cc, ch[k]);
-          }
-        }
-        if (P.mq) mh = wdet * P.mq[gp];
-        if constexpr (RAT) {
-          // psi = phi / W, grad_xi psi = (grad_xi phi - phi beta) / W: everything takes 1 / W^2, then the terms with beta move
-          // from the tensor to the vectors and from the vectors to the scalar
-          const double rw2 = rw * rw;
-          double Cb[3], Ctb[3];
-#pragma unroll
-          for (int k = 0; k < 3; k++) {
-#pragma unroll
-            for (int m = 0; m < 3; m++) Ch[k][m] *= rw2;
-            bh[k] *= rw2;
-            ch[k] *= rw2;
-          }
-#pragma unroll
-          for (int k = 0; k < 3; k++) {
-            Cb[k] = Ch[k][0] * bt[0] + Ch[k][1] * bt[1] + Ch[k][2] * bt[2];
-            Ctb[k] = Ch[0][k] * bt[0] + Ch[1][k] * bt[1] + Ch[2][k] * bt[2];
-          }
-          mh = mh * rw2 - (bt[0] * bh[0] + bt[1] * bh[1] + bt[2] * bh[2]) - (bt[0] * ch[0] + bt[1] * ch[1] + bt[2] * ch[2]) +
-               (bt[0] * Cb[0] + bt[1] * Cb[1] + bt[2] * Cb[2]);
-#pragma unroll
-          for (int k = 0; k < 3; k++) {
-            bh[k] -= Cb[k];
-            ch[k] -= Ctb[k];
-          }
-        }
-        double *o = P.cout + gp;       // C (row-major d x d) | b | c | m
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-#pragma unroll
-          for (int m = 0; m < 3; m++)
-            if (k < d && m < d) o[(int64_t)(k * d + m) * P.npts] = Ch[k][m];
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-          if (k < d) {
-            o[(int64_t)(d * d + k) * P.npts] = bh[k];
-            o[(int64_t)(d * d + d + k) * P.npts] = ch[k];
-          }
-        o[(int64_t)(d * d + 2 * d) * P.npts] = mh;
       } else {
         double sh = P.sq ? wdet * P.sq[gp] : 0.0, Fh[3] = {0, 0, 0};
         if (P.Fq) {
@@ -650,6 +666,30 @@ extern "C" int tg_coef_transform(const tg_patch_t *patch, int rational, int a_ki
   TG_TRY(tg_pp_point_array("tg_coef_transform", "m_q", m_q, 1, A.npts, &A.mq));
   A.cout = coef_out->d;
   return rational ? tg_pp_launch<TG_PP_COEF | TG_PP_RAT>(A, lds) : tg_pp_launch<TG_PP_COEF>(A, lds);
+}
+
+// the nF^2 blocks of a vector-valued unknown (nF = nsd = d fields on the scalar space): block (i, j) of A_q is the tensor
+// A_ij[K][L] of d P_iK / d F_jL, block (i, j) of M_q the reaction of int v_i M_ij u_j; each block comes out as one scalar
+// coefficient set of tg_coef_transform
+extern "C" int tg_coef_transform_blocks(const tg_patch_t *patch, int rational, int nF, tg_vec_t A_q, tg_vec_t M_q, tg_vec_t coef_out) {
+  tg_pp_args A;
+  size_t lds;
+  TG_TRY(tg_pp_setup(patch, 0, nullptr, &A, &lds));
+  const int d = A.d, nsd = A.nsd;
+  TG_REQUIRE((d == 2 || d == 3) && nsd == d && nF == d,
+             "tg_coef_transform_blocks: as many fields as physical and parametric directions, 2 or 3 (nF = %d, nsd = %d, d = %d)", nF,
+             nsd, d);
+  const int64_t nb = (int64_t)nF * nF;
+  TG_REQUIRE(A_q, "tg_coef_transform_blocks: no tangent");
+  TG_REQUIRE(coef_out && coef_out->n == nb * (d * d + 2 * d + 1) * A.npts,
+             "tg_coef_transform_blocks: an output of nF^2 (d^2 + 2 d + 1) npts = %lld values",
+             (long long)(nb * (d * d + 2 * d + 1) * A.npts));
+  A.akind = 2;
+  A.nblk = (int)nb;
+  TG_TRY(tg_pp_point_array("tg_coef_transform_blocks", "A_q", A_q, nb * nsd * nsd, A.npts, &A.Aq));
+  TG_TRY(tg_pp_point_array("tg_coef_transform_blocks", "M_q", M_q, nb, A.npts, &A.mq));
+  A.cout = coef_out->d;
+  return rational ? tg_pp_launch<TG_PP_COEF | TG_PP_BLOCKS | TG_PP_RAT>(A, lds) : tg_pp_launch<TG_PP_COEF | TG_PP_BLOCKS>(A, lds);
 }
 
 extern "C" int tg_flux_transform(const tg_patch_t *patch, int rational, tg_vec_t s_q, tg_vec_t F_q, tg_vec_t out) {

@@ -1257,6 +1257,56 @@ def quad_load_flux(vertices, p, cp, s=None, F=None, nq=None, rational=False):
     return out
 
 
+def coef_transform_blocks(vertices, p, cp, A, M=None, nq=None, rational=False):
+    """The tangent of a vector-valued unknown (nF = nsd = d fields) brought to the reference element in one pass
+    (``tg_coef_transform_blocks``): ``A`` holds A_iKjL at (((i nF + j) nsd + K) nsd + L) npts + q, ``M`` (or None) the reaction
+    M_ij at (i nF + j) npts + q.  Returns nF^2 consecutive coefficient sets in the layout of ``coef_transform``, which
+    ``assemble_coef_blocks`` takes."""
+    nq = p + 1 if nq is None else nq
+    pt, keep = _patch(vertices, p, cp, nq)
+    d, npts = len(vertices), quad_count(vertices, nq)
+    out = DeviceVector(d * d * (d * d + 2 * d + 1) * npts, zero=False)
+    check(_lib.lib().tg_coef_transform_blocks(C.byref(pt), 1 if rational else 0, d, _h_or_none(A), _h_or_none(M), out._h),
+          "tg_coef_transform_blocks")
+    return out
+
+
+def assemble_coef_blocks(vertices, p, cp, coef_blocks, nq=None):
+    """the nF n x nF n matrix (field-major) of the transformed blocks ``coef_blocks`` (``tg_assemble_coef_blocks``)"""
+    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
+    h = handle()
+    check(_lib.lib().tg_assemble_coef_blocks(C.byref(pt), len(vertices), coef_blocks._h, C.byref(h)), "tg_assemble_coef_blocks")
+    return DeviceCSR(h)
+
+
+def coef_block(vertices, coef_blocks, i, j, nq):
+    """the coefficient set of block (i, j) of ``coef_blocks`` as a DeviceVector of its own (a copy of that slice)"""
+    d = len(vertices)
+    each = (d * d + 2 * d + 1) * quad_count(vertices, nq)
+    out = DeviceVector(each, zero=False)
+    vec_copy_range(out, 0, coef_blocks, (i * d + j) * each, each)
+    return out
+
+
+MATERIAL_KINDS = {"linear": 0, "svk": 1, "neohookean": 2}
+
+
+def material_points(kind, lmbda, mu, nsd, gradu, stress=True, tangent=False, energy=False):
+    """The material law ``kind`` (0 linear, 1 St. Venant-Kirchhoff, 2 compressible neo-Hookean) at the points
+    (``tg_material_points``): ``gradu`` holds d u_i / d x_K at (i nsd + K) npts + q.  Returns (P, A, psi, nbad, Jmin) with
+    the outputs not asked for None; P in the layout of ``gradu``, A in that of ``coef_transform_blocks``."""
+    nsd = int(nsd)
+    npts = gradu.size() // (nsd * nsd)
+    P = DeviceVector(nsd * nsd * npts, zero=False) if stress else None
+    A = DeviceVector(nsd ** 4 * npts, zero=False) if tangent else None
+    psi = DeviceVector(npts, zero=False) if energy else None
+    par = _f64([float(lmbda), float(mu)])
+    nbad, jmin = C.c_int64(0), C.c_double(0.0)
+    check(_lib.lib().tg_material_points(int(kind), _p(par, c_f64p), nsd, npts, gradu._h, _h_or_none(P), _h_or_none(A),
+                                        _h_or_none(psi), C.byref(nbad), C.byref(jmin)), "tg_material_points")
+    return P, A, psi, int(nbad.value), float(jmin.value)
+
+
 def face_count(vertices, direction, nq):
     """number of Gauss points of the face (direction, side): nq^(d-1) per face element"""
     n = 1

@@ -851,6 +851,407 @@ class _QuasilinearTangent(object):
         return A
 
 
+# ---- vector-valued unknowns with point tangents: finite-strain elasticity (csrc/tg_material.hip) ----------------------------
+def _vector_form_scope(geometry, V, who):
+    """(node grid, nF) of a displacement space on the patch of ``geometry``: nF = nsd = d fields on one continuous Q_p node
+    grid, dofs field after field (``EqualOrderSpline(d, mesh)``); refuses everything else with the reason.  An
+    ExtractedSpline says itself what its vector point forms serve (``_vector_quadrature_scope``)."""
+    if geometry is None:
+        raise ValueError("%s: point tangents live on a mapped patch (geometry=...)" % who)
+    scope = getattr(geometry, "_vector_quadrature_scope", None)
+    if scope is not None:
+        scope(who)
+    _fields_of_the_patch(geometry, who)
+    g = V.grids[0]
+    if getattr(g, "dg", True) or not hasattr(g, "axes") or any(
+            gi.degree != g.degree or gi.dg or len(gi.axes) != len(g.axes) or
+            any(not numpy.array_equal(a, b) for a, b in zip(gi.axes, g.axes)) for gi in V.grids[1:]):
+        raise NotImplementedError("%s: the fields of the space must share one continuous Q_p node grid of a tensor-product "
+                                  "patch (compatible, FieldList, multi-patch, T-spline and DG spaces are not supported)" % who)
+    nF, nsd, d = len(V.grids), len(geometry.cpFuncs) - 1, g.dim()
+    if nsd != d or d not in (2, 3):
+        raise NotImplementedError("%s: nsd = %d physical directions on a patch of d = %d parametric ones; a solid has "
+                                  "nsd = d = 2 (plane strain) or 3" % (who, nsd, d))
+    if nF != nsd:
+        raise NotImplementedError("%s: nFields = %d; the displacement has nsd = %d fields" % (who, nF, nsd))
+    return g, nF
+
+
+def _vector_points(geometry, nq, who):
+    """the quadrature points of the patch (those of the scalar space the fields share)"""
+    return quadrature_points(geometry, geometry.V_control, nq, who)
+
+
+def _det_inv(F):
+    """(det F, F^-1) of [npts, n, n] matrices, n = 2, 3, by cofactors: any float dtype (numpy.linalg has no longdouble)"""
+    n = F.shape[-1]
+    cof = numpy.empty_like(F)
+    if n == 2:
+        cof[:, 0, 0], cof[:, 0, 1], cof[:, 1, 0], cof[:, 1, 1] = F[:, 1, 1], -F[:, 1, 0], -F[:, 0, 1], F[:, 0, 0]
+        J = F[:, 0, 0] * F[:, 1, 1] - F[:, 0, 1] * F[:, 1, 0]
+    else:
+        for i in range(3):
+            for K in range(3):
+                i1, i2, K1, K2 = (i + 1) % 3, (i + 2) % 3, (K + 1) % 3, (K + 2) % 3
+                cof[:, i, K] = F[:, i1, K1] * F[:, i2, K2] - F[:, i1, K2] * F[:, i2, K1]
+        J = F[:, 0, 0] * cof[:, 0, 0] + F[:, 0, 1] * cof[:, 0, 1] + F[:, 0, 2] * cof[:, 0, 2]
+    return J, cof.transpose(0, 2, 1) / J[:, None, None]
+
+
+class _Material(object):
+    """A built-in law: evaluated on the device by ``tg_material_points`` (``kind``), and on the host by ``host(F)`` for
+    deformation gradients ``F [npts, nsd, nsd]`` of any float dtype -> (P [npts, nsd, nsd], A [npts, nsd, nsd, nsd, nsd] with
+    A[q, i, K, j, L] = d P_iK / d F_jL, psi [npts])."""
+    kind = None
+
+    def __init__(self, lmbda, mu):
+        self.lmbda, self.mu = float(lmbda), float(mu)
+
+
+class LinearElastic(_Material):
+    """psi = lambda/2 (tr eps)^2 + mu eps:eps with eps = sym grad u: small strain, the law of ``ElasticityForm``"""
+    kind = 0
+
+    def host(self, F):
+        F = numpy.asarray(F)
+        dt, n = F.dtype.type, F.shape[-1]
+        lam, mu, I = dt(self.lmbda), dt(self.mu), numpy.eye(n, dtype=F.dtype)
+        eps = dt(0.5) * (F + F.transpose(0, 2, 1)) - I
+        tr = numpy.einsum("qii->q", eps)
+        P = lam * tr[:, None, None] * I + dt(2) * mu * eps
+        A = lam * numpy.einsum("iK,jL->iKjL", I, I) + mu * (numpy.einsum("ij,KL->iKjL", I, I) + numpy.einsum("iL,jK->iKjL", I, I))
+        psi = dt(0.5) * lam * tr * tr + mu * numpy.einsum("qij,qij->q", eps, eps)
+        return P, numpy.broadcast_to(A, (F.shape[0],) + A.shape).copy(), psi
+
+
+class StVenantKirchhoff(_Material):
+    """S = lambda tr E I + 2 mu E with E = (C - I)/2, P = F S; defined for any F"""
+    kind = 1
+
+    def host(self, F):
+        F = numpy.asarray(F)
+        dt, n = F.dtype.type, F.shape[-1]
+        lam, mu, I = dt(self.lmbda), dt(self.mu), numpy.eye(n, dtype=F.dtype)
+        E = dt(0.5) * (numpy.einsum("qaK,qaL->qKL", F, F) - I)
+        trE = numpy.einsum("qii->q", E)
+        S = lam * trE[:, None, None] * I + dt(2) * mu * E
+        P = numpy.einsum("qia,qaK->qiK", F, S)
+        B = numpy.einsum("qia,qja->qij", F, F)
+        A = numpy.einsum("ij,qKL->qiKjL", I, S) + lam * numpy.einsum("qiK,qjL->qiKjL", F, F) + \
+            mu * (numpy.einsum("qiL,qjK->qiKjL", F, F) + numpy.einsum("KL,qij->qiKjL", I, B))
+        psi = dt(0.5) * lam * trE * trE + mu * numpy.einsum("qij,qij->q", E, E)
+        return P, A, psi
+
+
+class NeoHookean(_Material):
+    """compressible neo-Hookean, psi = mu/2 (tr C - nsd) - mu ln J + lambda/2 (ln J)^2; needs J > 0"""
+    kind = 2
+
+    def host(self, F):
+        F = numpy.asarray(F)
+        dt, n = F.dtype.type, F.shape[-1]
+        lam, mu, I = dt(self.lmbda), dt(self.mu), numpy.eye(n, dtype=F.dtype)
+        J, Fi = _det_inv(F)
+        if numpy.any(~(J > 0)):
+            raise ValueError("NeoHookean: %d points with J <= 0 (smallest J = %g)" % (int(numpy.sum(~(J > 0))), float(numpy.min(J))))
+        lnJ = numpy.log(J)
+        FiT = Fi.transpose(0, 2, 1)
+        c1 = (mu - lam * lnJ)[:, None, None]
+        P = mu * F - c1 * FiT
+        A = mu * numpy.einsum("ij,KL->iKjL", I, I)[None] + c1[:, :, :, None, None] * numpy.einsum("qLi,qKj->qiKjL", Fi, Fi) + \
+            lam * numpy.einsum("qKi,qLj->qiKjL", Fi, Fi)
+        psi = dt(0.5) * mu * (numpy.einsum("qiK,qiK->q", F, F) - dt(n)) - mu * lnJ + dt(0.5) * lam * lnJ * lnJ
+        return P, A, psi
+
+
+def _tangent_to_device(A):
+    """[npts, nF, nsd, nF, nsd] (A[q, i, K, j, L]) -> the block layout of ``tg_coef_transform_blocks``"""
+    return _dev.DeviceVector(data=numpy.ascontiguousarray(numpy.asarray(A, dtype=numpy.float64).transpose(1, 3, 2, 4, 0)).ravel())
+
+
+class VectorCoefficientForm(object):
+    """a(u, v) = int d_K v_i A_iKjL d_L u_j + v_i M_ij u_j dx on the mapped patch for a vector-valued unknown: nF = nsd = d
+    fields on one continuous Q_p node grid, dofs field after field (the space of ``ElasticityForm``); grad and dx as
+    ``spline.grad`` / ``spline.dx``.  The tangent of a solid, ``derivative(derivative(psi*spline.dx, u), u)`` of the reference.
+
+    ``tangent``: ``[npts, nF, nsd, nF, nsd]`` point values A[q, i, K, j, L] (numbered as ``QuadraturePoints``), a callable of
+    the points ``x [npts, nsd]`` returning that, or a DeviceVector in the block layout -- A_iKjL at
+    (((i nF + j) nsd + K) nsd + L) npts + q.  ``reaction``: ``[npts, nF, nF]`` (or one nF x nF matrix, a callable, or a
+    DeviceVector with M_ij at (i nF + j) npts + q): inertia and spring terms.  ``nq`` Gauss points per direction (p + 1 when
+    None).  ``rational``: every component function phi / W_h.
+
+    ``symmetric`` is True only when the bits prove it: A[i, K, j, L] == A[j, L, i, K] and M[i, j] == M[j, i] at every point.
+    One pass brings all nF^2 blocks to the reference element (``tg_coef_transform_blocks``), each block is then a scalar
+    coefficient form on the element-coupling pattern (``tg_assemble_coef_blocks``); peak point data (d^4 + 16 d^2) npts
+    doubles in 3-D.  One rank, all rows."""
+
+    def __init__(self, geometry, tangent, reaction=None, nq=None, rational=False):
+        if geometry is None:
+            raise ValueError("VectorCoefficientForm: point tangents live on a mapped patch (geometry=...)")
+        if tangent is None:
+            raise ValueError("VectorCoefficientForm: no tangent")
+        self.geometry, self.tangent, self.reaction, self.nq, self.rational = geometry, tangent, reaction, nq, bool(rational)
+        self._symmetric_hint = None          # (set by a caller whose law proves the symmetry: HyperelasticResidual)
+
+    def coefficients(self, V):
+        """(points, A, M, symmetric) with the point data as DeviceVectors in the block layout (M None = absent): computed
+        once per set of points"""
+        who = "VectorCoefficientForm"
+        g, nF = _vector_form_scope(self.geometry, V, who)
+        pts = _vector_points(self.geometry, self.nq, who)
+        cache = self.__dict__.setdefault("_static", {})
+        if id(pts) in cache:
+            return cache[id(pts)]
+        cache.clear()
+        npts, nsd = pts.npts, pts.nsd
+        if isinstance(self.tangent, _dev.DeviceVector):
+            A = self.tangent
+            if A.size() != nF * nF * nsd * nsd * npts:
+                raise ValueError("%s: tangent: %d values given, expected nF^2 nsd^2 npts = %d"
+                                 % (who, A.size(), nF * nF * nsd * nsd * npts))
+            sym = None
+            if self._symmetric_hint is None:
+                h = A.get_local().reshape(nF, nF, nsd, nsd, npts)
+                sym = _same_bits(h, h.transpose(1, 0, 3, 2, 4))
+        else:
+            v = numpy.asarray(self.tangent(pts.x) if callable(self.tangent) else self.tangent, dtype=numpy.float64)
+            if v.shape == (nF, nsd, nF, nsd):
+                v = numpy.tile(v, (npts, 1, 1, 1, 1))
+            if v.shape != (npts, nF, nsd, nF, nsd):
+                raise ValueError("%s: tangent: an array of shape %s for %d points; expected (%d, %d, %d, %d, %d)"
+                                 % (who, v.shape, npts, npts, nF, nsd, nF, nsd))
+            A, sym = _tangent_to_device(v), _same_bits(v, v.transpose(0, 3, 4, 1, 2))
+        M, symM = None, True
+        if isinstance(self.reaction, _dev.DeviceVector):
+            M = self.reaction
+            if M.size() != nF * nF * npts:
+                raise ValueError("%s: reaction: %d values given, expected nF^2 npts = %d" % (who, M.size(), nF * nF * npts))
+            h = M.get_local().reshape(nF, nF, npts)
+            symM = _same_bits(h, h.transpose(1, 0, 2))
+        elif self.reaction is not None:
+            v = numpy.asarray(self.reaction(pts.x) if callable(self.reaction) else self.reaction, dtype=numpy.float64)
+            if v.shape == (nF, nF):
+                v = numpy.tile(v, (npts, 1, 1))
+            if v.shape != (npts, nF, nF):
+                raise ValueError("%s: reaction: an array of shape %s for %d points; expected (%d, %d, %d)"
+                                 % (who, v.shape, npts, npts, nF, nF))
+            M, symM = _dev.DeviceVector(data=numpy.ascontiguousarray(v.transpose(1, 2, 0)).ravel()), _same_bits(v, v.transpose(0, 2, 1))
+        if sym is None:
+            sym = bool(self._symmetric_hint)
+        cache[id(pts)] = (pts, A, M, bool(sym and symM))
+        return cache[id(pts)]
+
+    @property
+    def symmetric(self):
+        return self.coefficients(self.geometry.V)[3]
+
+    def _transformed(self, V):
+        pts, A, M, _ = self.coefficients(V)
+        return pts, _dev.coef_transform_blocks(pts.verts, pts.p, pts.cp, A, M, nq=pts.nq, rational=self.rational)
+
+    def assemble_block(self, V, i, j, row0=None, row1=None):
+        """block (i, j): test field i, trial field j (all rows of the field)"""
+        g, nF = _vector_form_scope(self.geometry, V, "VectorCoefficientForm")
+        if not (0 <= int(i) < nF and 0 <= int(j) < nF):
+            raise ValueError("VectorCoefficientForm: block (%r, %r) of a %d-field space" % (i, j, nF))
+        _whole_rows(g.num_nodes(), row0, row1, "VectorCoefficientForm", "patch")
+        pts, coef = self._transformed(V)
+        return _dev.assemble_coef_matrix(pts.verts, pts.p, pts.cp, _dev.coef_block(pts.verts, coef, int(i), int(j), pts.nq), nq=pts.nq)
+
+    def assemble_matrix(self, V, row0=None, row1=None):
+        g, nF = _vector_form_scope(self.geometry, V, "VectorCoefficientForm")
+        _whole_rows(nF * g.num_nodes(), row0, row1, "VectorCoefficientForm", "patch")
+        pts, coef = self._transformed(V)
+        return _dev.assemble_coef_blocks(pts.verts, pts.p, pts.cp, coef, nq=pts.nq)
+
+
+def _field_loads(pts, n, nF, s, F, rational):
+    """the nF component loads of int s_i v_i + F_iK d_K v_i, written field after field: nF calls of ``tg_quad_load_flux``;
+    ``s``: list of nF DeviceVectors (or None), ``F``: DeviceVector with F_iK at (i nsd + K) npts + q (or None)"""
+    out = _dev.DeviceVector(nF * n, zero=False)
+    size = pts.nsd * pts.npts
+    Fi = _dev.DeviceVector(size, zero=False) if F is not None else None
+    for i in range(nF):
+        if F is not None:
+            _dev.vec_copy_range(Fi, 0, F, i * size, size)
+        if F is None and (s is None or s[i] is None):
+            part = _dev.DeviceVector(n)
+        else:
+            part = _dev.quad_load_flux(pts.verts, pts.p, pts.cp, s[i] if s is not None else None, Fi, nq=pts.nq, rational=rational)
+        _dev.vec_copy_range(out, i * n, part, 0, n)
+    return out
+
+
+def _field_values(pts, f, nF, who, scale=1.0):
+    """nF DeviceVectors of the components of a vector field at the points: a callable ``x -> [npts, nF]``, an array of
+    that shape, or nF numbers"""
+    v = numpy.asarray(f(pts.x) if callable(f) else f, dtype=numpy.float64)
+    if v.shape == (nF,):
+        v = numpy.tile(v, (pts.npts, 1))
+    if v.shape != (pts.npts, nF):
+        raise ValueError("%s: an array of shape %s for %d points and %d fields; expected (%d, %d)"
+                         % (who, v.shape, pts.npts, nF, pts.npts, nF))
+    return [_dev.DeviceVector(data=numpy.ascontiguousarray(scale * v[:, c])) for c in range(nF)]
+
+
+class VectorLoadForm(object):
+    """L(v) = int f . v + flux : grad v dx on the space of ``VectorCoefficientForm``: ``f`` ``[npts, nF]`` (or a callable of the
+    points returning that, nF numbers, or None), ``flux`` ``[npts, nF, nsd]`` (flux[q, i, K] pairs with d_K v_i; a callable,
+    or a DeviceVector with flux_iK at (i nsd + K) npts + q).  The component loads are written field after field.
+    ``rational``: v_i the functions phi / W_h."""
+
+    def __init__(self, f, geometry, flux=None, nq=None, rational=False):
+        if geometry is None:
+            raise ValueError("VectorLoadForm: point values live on a mapped patch (geometry=...)")
+        if f is None and flux is None:
+            raise ValueError("VectorLoadForm: neither f nor flux given")
+        self.f, self.geometry, self.flux, self.nq, self.rational = f, geometry, flux, nq, bool(rational)
+
+    def assemble_vector(self, V, row0=None, row1=None):
+        who = "VectorLoadForm"
+        g, nF = _vector_form_scope(self.geometry, V, who)
+        n = g.num_nodes()
+        _whole_rows(nF * n, row0, row1, who, "patch")
+        pts = _vector_points(self.geometry, self.nq, who)
+        cache = self.__dict__.setdefault("_static", {})
+        if id(pts) not in cache:
+            cache.clear()
+            s = _field_values(pts, self.f, nF, who + ": f") if self.f is not None else None
+            F = None
+            if isinstance(self.flux, _dev.DeviceVector):
+                F = self.flux
+                if F.size() != nF * pts.nsd * pts.npts:
+                    raise ValueError("%s: flux: %d values given, expected nF nsd npts = %d" % (who, F.size(), nF * pts.nsd * pts.npts))
+            elif self.flux is not None:
+                v = numpy.asarray(self.flux(pts.x) if callable(self.flux) else self.flux, dtype=numpy.float64)
+                if v.shape != (pts.npts, nF, pts.nsd):
+                    raise ValueError("%s: flux: an array of shape %s for %d points; expected (%d, %d, %d)"
+                                     % (who, v.shape, pts.npts, pts.npts, nF, pts.nsd))
+                F = _dev.DeviceVector(data=numpy.ascontiguousarray(v.transpose(1, 2, 0)).ravel())
+            cache[id(pts)] = (s, F, pts)                                # (pts kept alive: id)
+        s, F, _ = cache[id(pts)]
+        return _field_loads(pts, n, nF, s, F, self.rational)
+
+
+class HyperelasticResidual(object):
+    """Residual of finite-strain elasticity on the mapped patch, R(v) = int P(F) : grad v - f . v dx with F = I + grad u: what
+    ``derivative(psi*spline.dx, u)`` of the reference gives for a solid.  The reference configuration is the patch
+    (x = F_geom(xi), grad = ``spline.grad``); ``u`` the displacement ``Function`` on the space of ``ElasticityForm`` (nF = nsd
+    = d fields, d = 2 is plane strain), read at assembly time.
+
+    ``material``: ``LinearElastic``, ``StVenantKirchhoff`` or ``NeoHookean`` -- evaluated at the points ON THE DEVICE
+    (``tg_material_points``): grad u, P and the tangent never leave it -- or any object with
+    ``host(F [npts, nsd, nsd]) -> (P [npts, nsd, nsd], A [npts, nsd, nsd, nsd, nsd], psi [npts])``, a host law whose arrays
+    are uploaded and go through the same transform and assembly.  ``body_force``: as ``f`` of ``VectorLoadForm``.
+
+    ``assemble_vector``: grad u per field by the kernel of ``evaluateAtQuadrature(grad=True)``, the law, then the flux loads.
+    ``tangent()``: the form of A = dP/dF (``VectorCoefficientForm``); for a built-in material ``symmetric`` is True, proved by
+    the law (A derives from an energy); for a host law it is what the bits of the last assembled tangent prove.
+    ``energy(V)`` = sum_q wdet_q psi_q.  A neo-Hookean state with J <= 0 somewhere raises ``RuntimeError`` naming the number
+    of such points and the smallest J.  Runs under ``solveNonlinearVariationalProblem`` and inside ``Sum`` with
+    ``BoundaryLoadForm`` tractions.  ``rational``: u_i = u_h,i / W_h, tested against phi / W_h."""
+
+    def __init__(self, u, geometry, material, body_force=None, nq=None, rational=False):
+        if geometry is None:
+            raise ValueError("HyperelasticResidual: point tangents live on a mapped patch (geometry=...)")
+        builtin = isinstance(material, _Material) and material.kind in (0, 1, 2)
+        if not builtin and not callable(getattr(material, "host", None)):
+            raise ValueError("HyperelasticResidual: unknown material %r; LinearElastic, StVenantKirchhoff, NeoHookean, or an "
+                             "object with host(F) -> (P, A, psi)" % (material,))
+        self.u, self.geometry, self.material, self.builtin = u, geometry, material, builtin
+        self.body_force, self.nq, self.rational = body_force, nq, bool(rational)
+
+    def grad_u(self, V):
+        """(points, node grid, nF, DeviceVector with d u_i / d x_K at (i nsd + K) npts + q)"""
+        who = "HyperelasticResidual"
+        g, nF = _vector_form_scope(self.geometry, V, who)
+        pts = _vector_points(self.geometry, self.nq, who)
+        n = g.num_nodes()
+        uv = self.u.vector() if hasattr(self.u, "vector") else self.u
+        if uv.size() != nF * n:
+            raise ValueError("%s: u holds %d nodal values, the space has %d fields of %d" % (who, uv.size(), nF, n))
+        size = pts.nsd * pts.npts
+        H, ui = _dev.DeviceVector(nF * size, zero=False), _dev.DeviceVector(n, zero=False)
+        for i in range(nF):
+            _dev.vec_copy_range(ui, 0, uv, i * n, n)
+            _, gi = _dev.quad_eval(pts.verts, pts.p, pts.cp, ui, grad=True, nq=pts.nq, rational=self.rational)
+            _dev.vec_copy_range(H, i * size, gi, 0, size)
+        return pts, g, nF, H
+
+    def law(self, V, stress=True, tangent=False, energy=False):
+        """(points, node grid, nF, P, A, psi) at the current state, as DeviceVectors (None where not asked for)"""
+        pts, g, nF, H = self.grad_u(V)
+        nsd, npts = pts.nsd, pts.npts
+        if self.builtin:
+            m = self.material
+            P, A, psi, nbad, jmin = _dev.material_points(m.kind, m.lmbda, m.mu, nsd, H, stress, tangent, energy)
+            if nbad > 0:
+                raise RuntimeError("HyperelasticResidual: %d quadrature points with J <= 0 (smallest J = %g): %s is not "
+                                   "defined there" % (nbad, jmin, type(m).__name__))
+            return pts, g, nF, P, A, psi
+        F = numpy.ascontiguousarray(H.get_local().reshape(nsd, nsd, npts).transpose(2, 0, 1)) + numpy.eye(nsd)
+        out = self.material.host(F)
+        if not isinstance(out, tuple) or len(out) != 3:
+            raise ValueError("HyperelasticResidual: material.host(F) returns (P, A, psi)")
+        Ph, Ah, psih = (numpy.asarray(o, dtype=numpy.float64) for o in out)
+        if Ph.shape != (npts, nsd, nsd) or Ah.shape != (npts, nsd, nsd, nsd, nsd) or psih.shape != (npts,):
+            raise ValueError("HyperelasticResidual: material.host(F) returned shapes %s, %s, %s for %d points in %d-D"
+                             % (Ph.shape, Ah.shape, psih.shape, npts, nsd))
+        self._host_symmetric = _same_bits(Ah, Ah.transpose(0, 3, 4, 1, 2))
+        P = _dev.DeviceVector(data=numpy.ascontiguousarray(Ph.transpose(1, 2, 0)).ravel()) if stress else None
+        return pts, g, nF, P, (_tangent_to_device(Ah) if tangent else None), (_dev.DeviceVector(data=psih) if energy else None)
+
+    def assemble_vector(self, V, row0=None, row1=None):
+        who = "HyperelasticResidual"
+        g, nF = _vector_form_scope(self.geometry, V, who)
+        _whole_rows(nF * g.num_nodes(), row0, row1, who, "patch")
+        pts, g, nF, P, _, _ = self.law(V)
+        s = None
+        if self.body_force is not None:
+            cache = self.__dict__.setdefault("_fq", {})
+            if id(pts) not in cache:
+                cache.clear()
+                cache[id(pts)] = (_field_values(pts, self.body_force, nF, who + ": body_force", scale=-1.0), pts)
+            s = cache[id(pts)][0]
+        return _field_loads(pts, g.num_nodes(), nF, s, P, self.rational)
+
+    def energy(self, V=None):
+        if V is None:
+            V = self.u.function_space()
+        pts, g, nF, _, _, psi = self.law(V, stress=False, energy=True)
+        return pts.weights.inner(psi)
+
+    def tangent(self):
+        return _HyperelasticTangent(self)
+
+
+class _HyperelasticTangent(object):
+    """``symmetric``: True for a built-in material (the tangent derives from an energy: major symmetry by the law); for a host
+    law that of the last assembled tangent and False before the first assembly (see ``_QuasilinearTangent``)."""
+
+    def __init__(self, res):
+        self.res, self.geometry, self.symmetric = res, res.geometry, bool(res.builtin)
+
+    def _form(self, V):
+        res = self.res
+        pts, g, nF, _, A, _ = res.law(V, stress=False, tangent=True)
+        form = VectorCoefficientForm(res.geometry, A, nq=res.nq, rational=res.rational)
+        form._symmetric_hint = True if res.builtin else bool(res._host_symmetric)
+        if not res.builtin:
+            self.symmetric = bool(res._host_symmetric)
+        return form
+
+    def assemble_block(self, V, i, j, row0=None, row1=None):
+        g, nF = _vector_form_scope(self.res.geometry, V, "HyperelasticResidual.tangent")
+        _whole_rows(g.num_nodes(), row0, row1, "HyperelasticResidual.tangent", "patch")
+        return self._form(V).assemble_block(V, i, j)
+
+    def assemble_matrix(self, V, row0=None, row1=None):
+        g, nF = _vector_form_scope(self.res.geometry, V, "HyperelasticResidual.tangent")
+        _whole_rows(nF * g.num_nodes(), row0, row1, "HyperelasticResidual.tangent", "patch")
+        return self._form(V).assemble_matrix(V)
+
+
 # ---- boundary integrals on a mapped patch (csrc/tg_boundary.hip): spline.ds and spline.n of the reference -----------------
 def _periodic_directions(geometry):
     """directions whose knot vector is not open (the faces there are no boundary), as far as the geometry tells"""

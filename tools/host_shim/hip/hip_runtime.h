@@ -1,5 +1,6 @@
-// Host stand-ins for the HIP names that csrc/tg_common.h, csrc/tg_postproc.hip and csrc/tg_coef.hip use, so that their kernel
-// source compiles as plain C++ for tools/coef_host_sweep.cpp (address / undefined-behaviour sanitizer sweep on the CPU).
+// Host stand-ins for the HIP names that csrc/tg_common.h, csrc/tg_postproc.hip, csrc/tg_coef.hip and csrc/tg_material.hip use, so
+// that their kernel source compiles as plain C++ for tools/coef_host_sweep.cpp and tools/material_host_sweep.cpp (address /
+// undefined-behaviour sanitizer sweeps on the CPU).
 // A launch runs the blocks one after the other with ONE thread each: every loop of these kernels strides by blockDim.x, so
 // one thread does the work of the block and the barriers are no-ops.  The dynamic LDS area is a global array of which
 // everything beyond the size the launch asked for is poisoned for the address sanitizer.
@@ -46,6 +47,7 @@ static inline double __longlong_as_double(long long v) { double r; memcpy(&r, &v
 static inline long long __double2ll_rn(double v) { return llrint(v); }
 static inline double __ll2double_rn(long long v) { return (double)v; }
 template <typename T> static inline T atomicAdd(T *p, T v) { T o = *p; *p += v; return o; }
+template <typename T> static inline T atomicMin(T *p, T v) { T o = *p; if (v < o) *p = v; return o; }
 static inline double unsafeAtomicAdd(double *p, double v) { double o = *p; *p += v; return o; }
 
 typedef int hipError_t;
