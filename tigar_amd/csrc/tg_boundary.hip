@@ -25,8 +25,11 @@
 //
 // RATIONAL functions psi = phi / W_h: u = u_h / W_h, grad_xi u = (grad_xi u_h - u grad_xi W_h) / W_h; a test function's
 // value becomes phi / W_h and its grad_xi phi becomes (grad_xi phi - phi beta) / W_h, beta = grad_xi W_h / W_h.
+//
+// The check of the patch, the LDS fit, the colour loop and the nodal fields' has / ci are tg_point_shared.h's, shared with
+// tg_postproc.hip and tg_coef.hip.
 #include "tg_common.h"
-#include "tg_asm_shared.h"
+#include "tg_point_shared.h"
 #include <cmath>
 
 struct tg_bd_args {
@@ -53,9 +56,6 @@ struct tg_bd_args {
   const int32_t *col;
   double *mval;
 };
-
-__device__ __forceinline__ bool tg_bd_has(int c, const tg_bd_args &P) { return c < 3 ? c < P.nsd : P.f[c] != nullptr; }
-__device__ __forceinline__ int tg_bd_ci(int c, int nsd) { return c < 3 ? c : nsd + (c - 3); }
 
 // face element e of the launch -> element indices of the boundary-layer element; returns the face element's number
 __device__ __forceinline__ int64_t tg_bd_element(const tg_bd_args &P, int64_t e, int *el) {
@@ -130,14 +130,14 @@ __global__ void __launch_bounds__(256) k_boundary(tg_bd_args P) {
     double *A = bufA + (size_t)es * P.szA;
 #pragma unroll
     for (int c = 0; c < 5; c++) {
-      if (!tg_bd_has(c, P)) continue;
+      if (!tg_pt_has(c, nsd, P.f)) continue;
       double dn = 0.0, fv = 0.0;
       for (int m = 0; m < p1; m++) {
         const double v = P.f[c][tg_bd_node(P, el, at, m)];
         dn = fma(P.dle[m], v, dn);
         if (m == mface) fv = v;
       }
-      const int ci = tg_bd_ci(c, nsd);
+      const int ci = tg_pt_ci(c, nsd);
       A[ci * nlt + at] = fv;
       A[(nc + ci) * nlt + at] = dn;
     }
@@ -183,8 +183,8 @@ __global__ void __launch_bounds__(256) k_boundary(tg_bd_args P) {
     for (int c = 0; c < 5; c++) {
       N[c] = 0.0;
       dN[c][0] = dN[c][1] = dN[c][2] = 0.0;
-      if (!tg_bd_has(c, P)) continue;
-      const double *I = fin + (size_t)es * szf + tg_bd_ci(c, nsd) * Sin;
+      if (!tg_pt_has(c, nsd, P.f)) continue;
+      const double *I = fin + (size_t)es * szf + tg_pt_ci(c, nsd) * Sin;
       double v = 0.0, vn = 0.0, e0 = 0.0, vd = 0.0;
       for (int a = 0; a < p1; a++) {
         const double l = tl[a * nq + ql], dl = tdl[a * nq + ql];
@@ -199,6 +199,7 @@ __global__ void __launch_bounds__(256) k_boundary(tg_bd_args P) {
 #pragma unroll
       for (int m = 0; m < 3; m++) dN[c][m] = m == kdir ? vn : (m == t0 ? (dt == 2 ? e0 : vd) : (m == t1 ? vd : 0.0));
     }
+    // DF[i][k] = d(N_i / W)/dxi_k ; metric g = DF^T DF  (the twin of quotient, DF and g: k_postproc, tg_postproc.hip)
     const double W = N[3];
     if constexpr (RAT && MODE == 1) {
       const double rw = 1.0 / W;
@@ -218,28 +219,8 @@ __global__ void __launch_bounds__(256) k_boundary(tg_bd_args P) {
     for (int k = 0; k < 3; k++)
 #pragma unroll
       for (int m = 0; m < 3; m++) G[k][m] = DF[0][k] * DF[0][m] + DF[1][k] * DF[1][m] + DF[2][k] * DF[2][m];
-    double gi[3][3] = {{0}}, det, gm[9], gq[9];
-    if (d == 2) {
-      gm[0] = G[0][0];
-      gm[1] = G[0][1];
-      gm[2] = G[1][0];
-      gm[3] = G[1][1];
-      tg_sym_inverse(2, gm, gq, &det);
-      gi[0][0] = gq[0];
-      gi[0][1] = gq[1];
-      gi[1][0] = gq[2];
-      gi[1][1] = gq[3];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-#pragma unroll
-        for (int m = 0; m < 3; m++) gm[3 * k + m] = G[k][m];
-      tg_sym_inverse(3, gm, gq, &det);
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-#pragma unroll
-        for (int m = 0; m < 3; m++) gi[k][m] = gq[3 * k + m];
-    }
+    double gi[3][3];
+    const double det = tg_point_metric_inverse<false>(d, G, gi);
     // g^-1 N, its length sqrt(N.g^-1 N) = sqrt((g^-1)_kk), and cn = g^-1 N / sqrt(N.g^-1 N): d_n = cn . grad_xi
     double gN[3];
 #pragma unroll
@@ -474,42 +455,20 @@ __global__ void __launch_bounds__(256) k_face_pattern_check(tg_bd_args P, const 
 
 #define TG_BD_LDS_DEFAULT ((size_t)64 * 1024)
 
-static int tg_bd_pow(int b, int e) {
-  int r = 1;
-  for (int i = 0; i < e; i++) r *= b;
-  return r;
-}
-
 // checks patch and face, fills what every ending shares; `u`: the nodal vector taken to the points (may be null);
 // `nch`: channels of the load ending
 static int tg_bd_setup(const char *who, const tg_patch_t *pt, int dir, int side, int mode, int nch, tg_vec_t u, tg_bd_args *A,
                        size_t *lds, int64_t *nnodes_out) {
-  TG_REQUIRE_INIT();
-  TG_REQUIRE(pt && (pt->d == 2 || pt->d == 3) && pt->p >= 1 && pt->p <= TG_MAX_DEGREE && pt->nsd >= pt->d && pt->nsd <= 3,
-             "%s: a patch with d = 2 or 3, d <= nsd <= 3 and 1 <= p <= %d", who, TG_MAX_DEGREE);
-  TG_REQUIRE(dir >= 0 && dir < pt->d && (side == 0 || side == 1), "%s: face (%d, %d): 0 <= direction < %d, side 0 or 1", who, dir,
-             side, pt->d);
-  TG_REQUIRE(pt->nq >= 1 && pt->nq <= TG_ASM_MAXQ1, "%s: 1..%d Gauss points per direction", who, TG_ASM_MAXQ1);
-  const int d = pt->d, p = pt->p, p1 = p + 1, nq = pt->nq, dt = d - 1;
-  TG_REQUIRE(tg_bd_pow(p1, d) <= TG_ASM_MAXLOC, "%s: (p+1)^d = %d local nodes exceed the kernel limit %d", who, tg_bd_pow(p1, d),
-             TG_ASM_MAXLOC);
-  memset(A, 0, sizeof(*A));
-  A->d = d;
-  A->p = p;
-  A->nsd = pt->nsd;
-  A->nq = nq;
+  tg_patch_dims D;
+  TG_TRY(tg_patch_check(who, pt, 2, true, u, &D));
+  TG_REQUIRE(dir >= 0 && dir < D.d && (side == 0 || side == 1), "%s: face (%d, %d): 0 <= direction < %d, side 0 or 1", who, dir,
+             side, D.d);
+  TG_REQUIRE(D.nnodes < (1ll << 31), "%s: too many FE nodes for 32-bit column indices", who);
+  const int d = D.d, p = D.p, p1 = p + 1, nq = D.nq, dt = d - 1;
+  tg_point_args_init(D, A);
   A->kdir = dir;
   A->side = side;
   A->dt = dt;
-  int64_t nnodes = 1;
-  for (int k = 0; k < 3; k++) A->nel[k] = A->n[k] = 1;
-  for (int k = 0; k < d; k++) {
-    TG_REQUIRE(pt->nverts[k] >= 2 && pt->verts[k], "%s: direction %d needs at least one element", who, k);
-    A->nel[k] = pt->nverts[k] - 1;
-    A->n[k] = A->nel[k] * p + 1;
-    nnodes *= A->n[k];
-  }
-  TG_REQUIRE(nnodes < (1ll << 31), "%s: too many FE nodes for 32-bit column indices", who);
   A->t[0] = A->t[1] = -1;
   A->nelt[0] = A->nelt[1] = 1;
   for (int k = 0, j = 0; k < d; k++)
@@ -524,20 +483,9 @@ static int tg_bd_setup(const char *who, const tg_patch_t *pt, int dir, int side,
   }
   A->estep = 1;
   A->nelem = (int64_t)A->nelt[0] * A->nelt[1];
-  const int nlt = tg_bd_pow(p1, dt), nqf = tg_bd_pow(nq, dt);
+  const int nlt = tg_ipow(p1, dt), nqf = tg_ipow(nq, dt);
   A->npts = A->nelem * nqf;
-  for (int c = 0; c <= pt->nsd; c++) {
-    TG_REQUIRE(pt->cp[c] && pt->cp[c]->n == nnodes, "%s: control function %d: a vector on the %lld FE nodes of the patch", who, c,
-               (long long)nnodes);
-    A->f[c < pt->nsd ? c : 3] = pt->cp[c]->d;
-  }
-  A->nc = pt->nsd + 1;
-  if (u) {
-    TG_REQUIRE(u->n == nnodes, "%s: the nodal vector holds %lld values, the patch has %lld FE nodes", who, (long long)u->n,
-               (long long)nnodes);
-    A->f[4] = u->d;
-    A->nc++;
-  }
+  A->nc = tg_point_fields(pt, u, A->f);
   // dl_a at the end of the reference interval: nodes a / p
   for (int a = 0; a < p1; a++) {
     const long double xe = side ? 1.0L : 0.0L;
@@ -560,7 +508,7 @@ static int tg_bd_setup(const char *who, const tg_patch_t *pt, int dir, int side,
   int szA = 2 * nc * nlt, szB = dt == 2 ? 3 * nc * nq * p1 : 0;
   int &other = dt == 2 ? szA : szB;
   if (mode == 2) {
-    const int back = nch * tg_bd_pow(std::max(p1, nq), dt);
+    const int back = nch * tg_ipow(std::max(p1, nq), dt);
     szA = std::max(szA, back);
     szB = std::max(szB, back);
   }
@@ -570,12 +518,9 @@ static int tg_bd_setup(const char *who, const tg_patch_t *pt, int dir, int side,
   // the matrix ending gives every face element a workgroup of its own: the (p+1)^2d entries of its block keep 256 threads
   // busy, and with several elements per workgroup the searches in the rows of the matrix, one after the other per
   // thread, set the time of the call whatever the size of the face
-  A->epg = mode == 3 ? 1 : std::max(1, 256 / nqf);
-  auto bytes = [&](int epg) { return ((size_t)2 * p1 * nq + nq + (size_t)epg * ((size_t)szA + szB)) * sizeof(double); };
-  while (A->epg > 1 && bytes(A->epg) > TG_BD_LDS_DEFAULT) A->epg--;
-  *lds = bytes(A->epg);
+  tg_point_lds_fit(p1, nq, szA, szB, mode == 3 ? 1 : std::max(1, 256 / nqf), TG_BD_LDS_DEFAULT, &A->epg, lds);
   TG_REQUIRE(*lds <= TG_BD_LDS_DEFAULT, "%s: face element data (%zu B) does not fit in LDS", who, *lds);
-  if (nnodes_out) *nnodes_out = nnodes;
+  if (nnodes_out) *nnodes_out = D.nnodes;
   return 0;
 }
 
@@ -587,22 +532,19 @@ static int tg_bd_launch(const tg_bd_args &A, size_t lds) {
   return 0;
 }
 
-// one launch per colour (parity of the tangential element indices), colours in ascending order
-template <int MODE>
-static int tg_bd_colours(tg_bd_args &A, size_t lds) {
+// the endings that add (MODE 2 into the nodes, 3 into the matrix) take one launch per colour of the tangential element
+// indices, the others one launch; plain or rational
+template <int M>
+static int tg_bd_launch_rat(bool rat, tg_bd_args &A, size_t lds) {
+  auto launch = [&] { return rat ? tg_bd_launch<M | TG_BD_RAT>(A, lds) : tg_bd_launch<M>(A, lds); };
+  if (M < 2) return launch();
   A.estep = 2;
-  for (int c = 0; c < (1 << A.dt); c++) {
-    int64_t ne = 1;
-    for (int j = 0; j < 2; j++) {
-      A.efirst[j] = j < A.dt ? (c >> j) & 1 : 0;
-      A.ncol[j] = j < A.dt ? (A.nelt[j] > A.efirst[j] ? (A.nelt[j] - A.efirst[j] + 1) / 2 : 0) : 1;
-      ne *= A.ncol[j];
-    }
-    if (ne == 0) continue;
-    A.nelem = ne;
-    TG_TRY(tg_bd_launch<MODE>(A, lds));
-  }
-  return 0;
+  return tg_for_colours(A.dt, A.nelt, [&](const int *efirst, const int *ncol, int64_t count) {
+    std::copy_n(efirst, 2, A.efirst);
+    std::copy_n(ncol, 2, A.ncol);
+    A.nelem = count;
+    return launch();
+  });
 }
 
 extern "C" int tg_face_points(const tg_patch_t *patch, int dir, int side, tg_vec_t x_out, tg_vec_t wsurf_out, tg_vec_t normal_out,
@@ -634,7 +576,7 @@ static int tg_bd_eval(const tg_patch_t *patch, int dir, int side, tg_vec_t u_nod
   A.val = val_out->d;
   A.grad = grad_out ? grad_out->d : nullptr;
   A.dn = dn_out ? dn_out->d : nullptr;
-  return rat ? tg_bd_launch<1 | TG_BD_RAT>(A, lds) : tg_bd_launch<1>(A, lds);
+  return tg_bd_launch_rat<1>(rat, A, lds);
 }
 
 static int tg_bd_load(const tg_patch_t *patch, int dir, int side, tg_vec_t f_q, tg_vec_t fn_q, tg_vec_t out, bool rat) {
@@ -649,7 +591,7 @@ static int tg_bd_load(const tg_patch_t *patch, int dir, int side, tg_vec_t f_q, 
   A.fq = f_q ? f_q->d : nullptr;
   A.fnq = fn_q ? fn_q->d : nullptr;
   A.out = out->d;
-  return rat ? tg_bd_colours<2 | TG_BD_RAT>(A, lds) : tg_bd_colours<2>(A, lds);
+  return tg_bd_launch_rat<2>(rat, A, lds);
 }
 
 // the entries of the face into (rowptr, col, val) of m, which must hold them; check: look first, error 3 if one is missing
@@ -666,7 +608,7 @@ static int tg_bd_matrix_into(const tg_patch_t *patch, int dir, int side, tg_vec_
   if (check) {
     int *flag = reinterpret_cast<int *>(g_tg.scratch);
     TG_CHECK_HIP(hipMemsetAsync(flag, 0, sizeof(int), g_tg.stream));
-    const int64_t nloc = tg_bd_pow(A.p + 1, A.d), work = A.nelem * nloc * nloc;
+    const int64_t nloc = tg_ipow(A.p + 1, A.d), work = A.nelem * nloc * nloc;
     TG_REQUIRE(tg_cdiv(work, 256) < (1ll << 31), "%s: too many face elements for one launch", who);
     hipLaunchKernelGGL(k_face_pattern_check, dim3((unsigned)tg_cdiv(work, 256)), dim3(256), 0, g_tg.stream, A, m->rowptr, m->col,
                        flag);
@@ -694,7 +636,7 @@ static int tg_bd_matrix_into(const tg_patch_t *patch, int dir, int side, tg_vec_
   A.rowptr = m->rowptr;
   A.col = m->col;
   A.mval = m->val;
-  return rat ? tg_bd_colours<3 | TG_BD_RAT>(A, lds) : tg_bd_colours<3>(A, lds);
+  return tg_bd_launch_rat<3>(rat, A, lds);
 }
 
 static int tg_bd_matrix(const tg_patch_t *patch, int dir, int side, tg_vec_t a_q, tg_vec_t b_q, tg_vec_t c_q, tg_csr_t *out,

@@ -25,7 +25,7 @@
 // per pair (a, b).  Elements of one launch share no node (the colours of k_assemble_mapped, in the same order) and add
 // without atomics: the same inputs give the same bits.  The load L(v) is an ending of k_postproc (tg_quad_load_flux).
 #include "tg_common.h"
-#include "tg_asm_shared.h"
+#include "tg_point_shared.h"
 
 struct tg_coef_args {
   int d, p, nq;
@@ -126,34 +126,21 @@ __global__ void __launch_bounds__(256) k_coef_matrix(tg_coef_args P) {
 }
 
 extern "C" int tg_assemble_coef_matrix(const tg_patch_t *pt, tg_vec_t coef, tg_csr_t *out) {
-  TG_REQUIRE_INIT();
-  TG_REQUIRE(pt && pt->d >= 1 && pt->d <= 3 && pt->p >= 1 && pt->p <= TG_MAX_DEGREE && pt->nsd >= pt->d && pt->nsd <= 3,
-             "bad patch description");
-  TG_REQUIRE(pt->nq >= 1 && pt->nq <= TG_ASM_MAXQ1, "1..%d Gauss points per direction", TG_ASM_MAXQ1);
-  TG_REQUIRE(out, "null output");
-  const int d = pt->d, p = pt->p, p1 = p + 1, nq = pt->nq;
-  int nloc = 1, nqt = 1;
-  for (int k = 0; k < d; k++) {
-    nloc *= p1;
-    nqt *= nq;
-  }
-  TG_REQUIRE(nloc <= TG_ASM_MAXLOC, "(p+1)^d = %d local nodes exceed the kernel limit %d", nloc, TG_ASM_MAXLOC);
+  tg_patch_dims D;
+  TG_TRY(tg_patch_check("tg_assemble_coef_matrix", pt, 1, false, nullptr, &D));     // (the control functions are not read)
+  TG_REQUIRE(out, "tg_assemble_coef_matrix: null output");
+  const int d = D.d, p = D.p, p1 = p + 1, nq = D.nq, nqt = D.nqt;
   tg_coef_args A;
   memset(&A, 0, sizeof(A));
   A.d = d;
   A.p = p;
   A.nq = nq;
-  int64_t nnodes = 1, nelem = 1;
-  for (int k = 0; k < 3; k++) A.nel[k] = A.n[k] = A.ncol[k] = 1;
-  for (int k = 0; k < d; k++) {
-    TG_REQUIRE(pt->nverts[k] >= 2 && pt->verts[k], "direction %d needs at least one element", k);
-    A.nel[k] = pt->nverts[k] - 1;
-    A.n[k] = A.nel[k] * p + 1;
-    nnodes *= A.n[k];
-    nelem *= A.nel[k];
+  for (int k = 0; k < 3; k++) {
+    A.nel[k] = D.nel[k];
+    A.n[k] = D.n[k];
   }
   const int ncomp = d * d + 2 * d + 1;
-  A.npts = nelem * nqt;
+  A.npts = D.npts;
   TG_REQUIRE(coef && coef->n == (int64_t)ncomp * A.npts,
              "tg_assemble_coef_matrix: (d^2 + 2 d + 1) npts = %lld transformed point coefficients (tg_coef_transform)",
              (long long)(ncomp * A.npts));
@@ -170,27 +157,22 @@ extern "C" int tg_assemble_coef_matrix(const tg_patch_t *pt, tg_vec_t coef, tg_c
     TG_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_coef_matrix), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      160 * 1024));
   tg_csr_t m = nullptr;
-  TG_TRY(tg_asm_coupling_pattern(d, p, A.n, 0, nnodes, false, &m));    // (values 0: the colours add into them)
+  TG_TRY(tg_asm_coupling_pattern(d, p, A.n, 0, D.nnodes, false, &m));    // (values 0: the colours add into them)
   A.rowptr = m->rowptr;
   A.val = m->val;
-  bool bad = false;
   const bool timeit = getenv("TIGAR_ASM_TIME") != nullptr;
   if (timeit) hipEventRecord(g_tg.ev0[0], g_tg.stream);
-  for (int c = 0; c < (1 << d) && !bad; c++) {
-    int64_t nblk = 1;
-    for (int k = 0; k < d; k++) {
-      A.efirst[k] = (c >> k) & 1;
-      A.ncol[k] = A.nel[k] > A.efirst[k] ? (A.nel[k] - A.efirst[k] + 1) / 2 : 0;
-      nblk *= A.ncol[k];
-    }
-    if (nblk == 0) continue;
-    if (nblk >= (1ll << 31)) {
-      tg_csr_destroy(m);
-      tg_set_error("too many elements for one launch");
-      return 2;
-    }
+  const int rc = tg_for_colours(d, A.nel, [&](const int *efirst, const int *ncol, int64_t nblk) {
+    if (nblk >= (1ll << 31)) return 2;
+    std::copy_n(efirst, 3, A.efirst);
+    std::copy_n(ncol, 3, A.ncol);
     hipLaunchKernelGGL(k_coef_matrix, dim3((unsigned)nblk), dim3(256), lds, g_tg.stream, A);
-    bad = hipGetLastError() != hipSuccess;
+    return hipGetLastError() != hipSuccess ? 1 : 0;
+  });
+  if (rc == 2) {
+    tg_csr_destroy(m);
+    tg_set_error("too many elements for one launch");
+    return 2;
   }
   if (timeit) {
     hipEventRecord(g_tg.ev1[0], g_tg.stream);
@@ -199,7 +181,7 @@ extern "C" int tg_assemble_coef_matrix(const tg_patch_t *pt, tg_vec_t coef, tg_c
     hipEventElapsedTime(&ms, g_tg.ev0[0], g_tg.ev1[0]);
     fprintf(stderr, "[tg_assemble] coefficient form, %lld points: element kernels %.3f ms (plain)\n", (long long)A.npts, ms);
   }
-  if (bad) {
+  if (rc) {
     tg_csr_destroy(m);
     tg_set_error("the coefficient-form kernel failed to launch");
     return 1;

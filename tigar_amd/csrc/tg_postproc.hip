@@ -28,8 +28,11 @@
 // RATIONAL functions (u = u_h / W_h, the reference's spline.rationalize(u); tested against phi / W_h): W_h and its gradient
 // are at the points anyway --  u = u_h / W_h,  grad_xi u = (grad_xi u_h - u grad_xi W_h) / W_h  before the Cartesian
 // gradient and the error terms are formed, and the load's point value takes 1 / W_h.
+//
+// The check of the patch, the LDS fit, the colour loop and the nodal fields' has / ci are tg_point_shared.h's, shared with
+// tg_boundary.hip and tg_coef.hip.
 #include "tg_common.h"
-#include "tg_asm_shared.h"
+#include "tg_point_shared.h"
 #include <cmath>
 
 struct tg_pp_args {
@@ -56,10 +59,6 @@ struct tg_pp_args {
   double *cout;                // the data on the reference element, component-major
   int nblk;                    // TG_PP_BLOCKS: Aq, mq and cout hold this many consecutive sets (a tensor per point each)
 };
-
-__device__ __forceinline__ bool tg_pp_has(int c, const tg_pp_args &P) { return c < 3 ? c < P.nsd : P.f[c] != nullptr; }
-// position of field c among the fields present
-__device__ __forceinline__ int tg_pp_ci(int c, int nsd) { return c < 3 ? c : nsd + (c - 3); }
 
 // element number e of the launch -> element indices; returns the lexicographic index in the patch
 __device__ __forceinline__ int64_t tg_pp_element(const tg_pp_args &P, int64_t e, int *el) {
@@ -116,7 +115,7 @@ __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
     const int64_t node = tg_pp_node(P, el, a);
 #pragma unroll
     for (int c = 0; c < 5; c++)
-      if (tg_pp_has(c, P)) bufA[(size_t)es * P.szA + tg_pp_ci(c, nsd) * nloc + a] = P.f[c][node];
+      if (tg_pt_has(c, nsd, P.f)) bufA[(size_t)es * P.szA + tg_pt_ci(c, nsd) * nloc + a] = P.f[c][node];
   }
   __syncthreads();
   // ---- to the points: directions 0 .. d-2 through LDS.  Before direction k an area holds k + 1 "slots" per field --
@@ -168,8 +167,8 @@ __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
     for (int c = 0; c < 5; c++) {
       N[c] = 0.0;
       dN[c][0] = dN[c][1] = dN[c][2] = 0.0;
-      if (!tg_pp_has(c, P)) continue;
-      const double *I = fin + (size_t)es * szf + tg_pp_ci(c, nsd) * Sin;
+      if (!tg_pt_has(c, nsd, P.f)) continue;
+      const double *I = fin + (size_t)es * szf + tg_pt_ci(c, nsd) * Sin;
       double v = 0.0, e0 = 0.0, e1 = 0.0, vd = 0.0;
       for (int a = 0; a < p1; a++) {
         const double l = tl[a * nq + ql], dl = tdl[a * nq + ql];
@@ -185,7 +184,7 @@ __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
       dN[c][1] = d == 2 ? vd : e1;
       dN[c][2] = d == 3 ? vd : 0.0;
     }
-    // DF[i][k] = d(N_i / W)/dxi_k ; metric g = DF^T DF
+    // DF[i][k] = d(N_i / W)/dxi_k ; metric g = DF^T DF  (the twin of quotient, DF and g: k_boundary, tg_boundary.hip)
     const double W = N[3];
     if constexpr (RAT && (MODE == 1 || MODE == 3)) {
       // the difference first, with one rounding (for a function of the space the two products nearly cancel), then the division
@@ -206,33 +205,8 @@ __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
     for (int k = 0; k < 3; k++)
 #pragma unroll
       for (int m = 0; m < 3; m++) G[k][m] = DF[0][k] * DF[0][m] + DF[1][k] * DF[1][m] + DF[2][k] * DF[2][m];   // (zero beyond nsd, d)
-    // inverse and determinant of the leading d x d block (constant indices in every branch: the arrays stay in registers)
-    double gi[3][3] = {{0}}, det, gm[9], gq[9];
-    if (d == 1) {
-      gm[0] = G[0][0];
-      tg_sym_inverse(1, gm, gq, &det);
-      gi[0][0] = gq[0];
-    } else if (d == 2) {
-      gm[0] = G[0][0];
-      gm[1] = G[0][1];
-      gm[2] = G[1][0];
-      gm[3] = G[1][1];
-      tg_sym_inverse(2, gm, gq, &det);
-      gi[0][0] = gq[0];
-      gi[0][1] = gq[1];
-      gi[1][0] = gq[2];
-      gi[1][1] = gq[3];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-#pragma unroll
-        for (int m = 0; m < 3; m++) gm[3 * k + m] = G[k][m];
-      tg_sym_inverse(3, gm, gq, &det);
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-#pragma unroll
-        for (int m = 0; m < 3; m++) gi[k][m] = gq[3 * k + m];
-    }
+    double gi[3][3];
+    const double det = tg_point_metric_inverse<true>(d, G, gi);
     const int q0 = q % nq, q1 = (q / nq) % nq, q2 = q / (nq * nq);
     const double wq = tw[q0] * (d > 1 ? tw[q1] : 1.0) * (d > 2 ? tw[q2] : 1.0);
     const double wdet = wq * sqrt(fabs(det));
@@ -488,57 +462,22 @@ __global__ void __launch_bounds__(256) k_postproc_fold(const double *part, int64
 #define TG_PP_LDS_DEFAULT ((size_t)64 * 1024)     // dynamic LDS of a launch without an attribute
 #define TG_PP_LDS_MAX ((size_t)160 * 1024)        // LDS of a compute unit
 
-static int tg_pp_pow(int b, int e) {
-  int r = 1;
-  for (int i = 0; i < e; i++) r *= b;
-  return r;
-}
-
 // checks the patch, fills what every mode shares; `u`: the nodal vector taken to the points (may be null).  mode: 0 - 3 as
 // the kernel's, 4 the flux load
-static int tg_pp_setup(const tg_patch_t *pt, int mode, tg_vec_t u, tg_pp_args *A, size_t *lds) {
-  TG_REQUIRE_INIT();
-  TG_REQUIRE(pt && pt->d >= 1 && pt->d <= 3 && pt->p >= 1 && pt->p <= TG_MAX_DEGREE && pt->nsd >= pt->d && pt->nsd <= 3,
-             "bad patch description");
-  TG_REQUIRE(pt->nq >= 1 && pt->nq <= TG_ASM_MAXQ1, "1..%d Gauss points per direction", TG_ASM_MAXQ1);
-  const int d = pt->d, p1 = pt->p + 1, nq = pt->nq;
-  const int nloc = tg_pp_pow(p1, d), nqt = tg_pp_pow(nq, d);
-  TG_REQUIRE(nloc <= TG_ASM_MAXLOC, "(p+1)^d = %d local nodes exceed the kernel limit %d", nloc, TG_ASM_MAXLOC);
-  memset(A, 0, sizeof(*A));
-  A->d = d;
-  A->p = pt->p;
-  A->nsd = pt->nsd;
-  A->nq = nq;
-  int64_t nnodes = 1, nelem = 1;
-  for (int k = 0; k < 3; k++) {
-    A->nel[k] = A->n[k] = A->ncol[k] = 1;
-    A->efirst[k] = 0;
-  }
-  for (int k = 0; k < d; k++) {
-    TG_REQUIRE(pt->nverts[k] >= 2 && pt->verts[k], "direction %d needs at least one element", k);
-    A->nel[k] = A->ncol[k] = pt->nverts[k] - 1;
-    A->n[k] = A->nel[k] * pt->p + 1;
-    nnodes *= A->n[k];
-    nelem *= A->nel[k];
-  }
+static int tg_pp_setup(const char *who, const tg_patch_t *pt, int mode, tg_vec_t u, tg_pp_args *A, size_t *lds,
+                       int64_t *nnodes_out = nullptr) {
+  tg_patch_dims D;
+  TG_TRY(tg_patch_check(who, pt, 1, true, u, &D));
+  const int d = D.d, p1 = D.p + 1, nq = D.nq, nloc = D.nloc, nqt = D.nqt;
+  tg_point_args_init(D, A);
+  std::copy_n(D.nel, 3, A->ncol);
   A->estep = 1;
-  A->nelem = nelem;
-  A->npts = nelem * nqt;
-  for (int c = 0; c <= pt->nsd; c++) {
-    TG_REQUIRE(pt->cp[c] && pt->cp[c]->n == nnodes, "control function %d: a vector on the %lld FE nodes of the patch", c,
-               (long long)nnodes);
-    A->f[c < pt->nsd ? c : 3] = pt->cp[c]->d;
-  }
-  A->nc = pt->nsd + 1;
-  if (u) {
-    TG_REQUIRE(u->n == nnodes, "the nodal vector holds %lld values, the patch has %lld FE nodes", (long long)u->n,
-               (long long)nnodes);
-    A->f[4] = u->d;
-    A->nc++;
-  }
+  A->nelem = D.nelem;
+  A->npts = D.npts;
+  A->nc = tg_point_fields(pt, u, A->f);
+  if (nnodes_out) *nnodes_out = D.nnodes;
   TG_TRY(tg_asm_cache_get(pt));
   A->tab = g_asm_cache.tab;
-  A->epg = std::max(1, 256 / nqt);
   // LDS per element: area A holds the nodal values, then (3-D) the output of direction 1; area B the output of direction
   // 0; the area the last contraction does not read takes the point values of the load / the terms of the error sums, and
   // the load goes back to the nodes through both
@@ -546,7 +485,7 @@ static int tg_pp_setup(const tg_patch_t *pt, int mode, tg_vec_t u, tg_pp_args *A
   int szA = nc * nloc, szB = 0;
   if (d >= 2) szB = 2 * nc * nq * (nloc / p1);
   if (d == 3) szA = std::max(szA, 3 * nc * nq * nq * p1);
-  const int back = tg_pp_pow(std::max(p1, nq), d);
+  const int back = tg_ipow(std::max(p1, nq), d);
   int &other = ((d - 1) & 1) ? szA : szB;
   if (mode == 2) {
     szA = std::max(szA, back);
@@ -562,11 +501,9 @@ static int tg_pp_setup(const tg_patch_t *pt, int mode, tg_vec_t u, tg_pp_args *A
   // fewer elements per workgroup until the group fits the 64 KiB a launch gets without asking (nq < p + 1: many points'
   // worth of threads, but the areas grow with the nodes); one element of the largest shapes (3-D, p = 4, nq >= 9: 84 KB)
   // needs more than that and asks for it (tg_pp_launch)
-  auto bytes = [&](int epg) { return ((size_t)2 * p1 * nq + nq + (size_t)epg * ((size_t)szA + szB)) * sizeof(double); };
-  while (A->epg > 1 && bytes(A->epg) > TG_PP_LDS_DEFAULT) A->epg--;
-  *lds = bytes(A->epg);
-  TG_REQUIRE(*lds <= TG_PP_LDS_MAX, "element data (%zu B) does not fit in LDS", *lds);
-  TG_REQUIRE(tg_cdiv(nelem, A->epg) < (1ll << 31), "too many elements for one launch");
+  tg_point_lds_fit(p1, nq, szA, szB, std::max(1, 256 / nqt), TG_PP_LDS_DEFAULT, &A->epg, lds);
+  TG_REQUIRE(*lds <= TG_PP_LDS_MAX, "%s: element data (%zu B) does not fit in LDS", who, *lds);
+  TG_REQUIRE(tg_cdiv(D.nelem, A->epg) < (1ll << 31), "%s: too many elements for one launch", who);
   return 0;
 }
 
@@ -581,28 +518,24 @@ static int tg_pp_launch(const tg_pp_args &A, size_t lds) {
   return 0;
 }
 
-// one launch per colour (parity of the element index per direction), colours in ascending order
-template <int MODE>
-static int tg_pp_launch_colours(tg_pp_args &A, size_t lds) {
+// the endings that add into the nodes (MODE 2) take one launch per colour, the others one launch; plain or rational
+template <int M>
+static int tg_pp_launch_rat(bool rat, tg_pp_args &A, size_t lds) {
+  auto launch = [&] { return rat ? tg_pp_launch<M | TG_PP_RAT>(A, lds) : tg_pp_launch<M>(A, lds); };
+  if ((M & 3) != 2) return launch();
   A.estep = 2;
-  for (int c = 0; c < (1 << A.d); c++) {
-    int64_t ne = 1;
-    for (int k = 0; k < A.d; k++) {
-      A.efirst[k] = (c >> k) & 1;
-      A.ncol[k] = A.nel[k] > A.efirst[k] ? (A.nel[k] - A.efirst[k] + 1) / 2 : 0;
-      ne *= A.ncol[k];
-    }
-    if (ne == 0) continue;
-    A.nelem = ne;
-    TG_TRY(tg_pp_launch<MODE>(A, lds));
-  }
-  return 0;
+  return tg_for_colours(A.d, A.nel, [&](const int *efirst, const int *ncol, int64_t count) {
+    std::copy_n(efirst, 3, A.efirst);
+    std::copy_n(ncol, 3, A.ncol);
+    A.nelem = count;
+    return launch();
+  });
 }
 
 extern "C" int tg_quad_points(const tg_patch_t *patch, tg_vec_t x_out, tg_vec_t wdet_out) {
   tg_pp_args A;
   size_t lds;
-  TG_TRY(tg_pp_setup(patch, 0, nullptr, &A, &lds));
+  TG_TRY(tg_pp_setup("tg_quad_points", patch, 0, nullptr, &A, &lds));
   TG_REQUIRE(x_out && x_out->n == (int64_t)A.nsd * A.npts && wdet_out && wdet_out->n == A.npts,
              "tg_quad_points: outputs of nsd * npts = %lld and npts = %lld values", (long long)(A.nsd * A.npts), (long long)A.npts);
   A.x = x_out->d;
@@ -614,7 +547,7 @@ static int tg_pp_eval(const tg_patch_t *patch, tg_vec_t u_nodal, int with_grad, 
   tg_pp_args A;
   size_t lds;
   TG_REQUIRE(u_nodal, "tg_quad_eval: no nodal vector");
-  TG_TRY(tg_pp_setup(patch, 1, u_nodal, &A, &lds));
+  TG_TRY(tg_pp_setup("tg_quad_eval", patch, 1, u_nodal, &A, &lds));
   TG_REQUIRE(val_out && val_out->n == A.npts, "tg_quad_eval: an output of npts = %lld values", (long long)A.npts);
   A.val = val_out->d;
   if (with_grad) {
@@ -622,21 +555,18 @@ static int tg_pp_eval(const tg_patch_t *patch, tg_vec_t u_nodal, int with_grad, 
                (long long)(A.nsd * A.npts));
     A.grad = grad_out->d;
   }
-  return rat ? tg_pp_launch<1 | TG_PP_RAT>(A, lds) : tg_pp_launch<1>(A, lds);
+  return tg_pp_launch_rat<1>(rat, A, lds);
 }
 
 static int tg_pp_load(const tg_patch_t *patch, tg_vec_t f_q, tg_vec_t out, bool rat) {
   tg_pp_args A;
   size_t lds;
-  TG_TRY(tg_pp_setup(patch, 2, nullptr, &A, &lds));
-  int64_t nnodes = 1;
-  for (int k = 0; k < A.d; k++) nnodes *= A.n[k];
-  TG_REQUIRE(f_q && f_q->n == A.npts && out && out->n == nnodes,
-             "tg_quad_load: npts = %lld point values and an output on the %lld FE nodes", (long long)A.npts, (long long)nnodes);
+  int64_t nnodes;
+  TG_TRY(tg_pp_setup("tg_quad_load", patch, 2, nullptr, &A, &lds, &nnodes));
+  TG_REQUIRE(f_q && f_q->n == A.npts, "tg_quad_load: npts = %lld point values", (long long)A.npts);
   A.fq = f_q->d;
-  A.out = out->d;
-  TG_CHECK_HIP(hipMemsetAsync(out->d, 0, (size_t)nnodes * sizeof(double), g_tg.stream));
-  return rat ? tg_pp_launch_colours<2 | TG_PP_RAT>(A, lds) : tg_pp_launch_colours<2>(A, lds);
+  TG_TRY(tg_point_nodal_output("tg_quad_load", out, nnodes, &A.out));
+  return tg_pp_launch_rat<2>(rat, A, lds);
 }
 
 // ---- point coefficients.  The checks of the point arrays are shared: `n` values per point or null
@@ -653,7 +583,7 @@ extern "C" int tg_coef_transform(const tg_patch_t *patch, int rational, int a_ki
                                  tg_vec_t m_q, tg_vec_t coef_out) {
   tg_pp_args A;
   size_t lds;
-  TG_TRY(tg_pp_setup(patch, 0, nullptr, &A, &lds));
+  TG_TRY(tg_pp_setup("tg_coef_transform", patch, 0, nullptr, &A, &lds));
   const int d = A.d, nsd = A.nsd;
   TG_REQUIRE(a_kind >= 0 && a_kind <= 2 && (a_kind == 0) == (A_q == nullptr),
              "tg_coef_transform: a_kind 0 = no diffusion (A_q null), 1 = one value per point, 2 = an nsd x nsd tensor per point");
@@ -665,7 +595,7 @@ extern "C" int tg_coef_transform(const tg_patch_t *patch, int rational, int a_ki
   TG_TRY(tg_pp_point_array("tg_coef_transform", "c_q", c_q, nsd, A.npts, &A.cq));
   TG_TRY(tg_pp_point_array("tg_coef_transform", "m_q", m_q, 1, A.npts, &A.mq));
   A.cout = coef_out->d;
-  return rational ? tg_pp_launch<TG_PP_COEF | TG_PP_RAT>(A, lds) : tg_pp_launch<TG_PP_COEF>(A, lds);
+  return tg_pp_launch_rat<TG_PP_COEF>(rational != 0, A, lds);
 }
 
 // the nF^2 blocks of a vector-valued unknown (nF = nsd = d fields on the scalar space): block (i, j) of A_q is the tensor
@@ -674,7 +604,7 @@ extern "C" int tg_coef_transform(const tg_patch_t *patch, int rational, int a_ki
 extern "C" int tg_coef_transform_blocks(const tg_patch_t *patch, int rational, int nF, tg_vec_t A_q, tg_vec_t M_q, tg_vec_t coef_out) {
   tg_pp_args A;
   size_t lds;
-  TG_TRY(tg_pp_setup(patch, 0, nullptr, &A, &lds));
+  TG_TRY(tg_pp_setup("tg_coef_transform_blocks", patch, 0, nullptr, &A, &lds));
   const int d = A.d, nsd = A.nsd;
   TG_REQUIRE((d == 2 || d == 3) && nsd == d && nF == d,
              "tg_coef_transform_blocks: as many fields as physical and parametric directions, 2 or 3 (nF = %d, nsd = %d, d = %d)", nF,
@@ -689,40 +619,37 @@ extern "C" int tg_coef_transform_blocks(const tg_patch_t *patch, int rational, i
   TG_TRY(tg_pp_point_array("tg_coef_transform_blocks", "A_q", A_q, nb * nsd * nsd, A.npts, &A.Aq));
   TG_TRY(tg_pp_point_array("tg_coef_transform_blocks", "M_q", M_q, nb, A.npts, &A.mq));
   A.cout = coef_out->d;
-  return rational ? tg_pp_launch<TG_PP_COEF | TG_PP_BLOCKS | TG_PP_RAT>(A, lds) : tg_pp_launch<TG_PP_COEF | TG_PP_BLOCKS>(A, lds);
+  return tg_pp_launch_rat<TG_PP_COEF | TG_PP_BLOCKS>(rational != 0, A, lds);
 }
 
 extern "C" int tg_flux_transform(const tg_patch_t *patch, int rational, tg_vec_t s_q, tg_vec_t F_q, tg_vec_t out) {
   tg_pp_args A;
   size_t lds;
-  TG_TRY(tg_pp_setup(patch, 0, nullptr, &A, &lds));
+  TG_TRY(tg_pp_setup("tg_flux_transform", patch, 0, nullptr, &A, &lds));
   TG_REQUIRE(out && out->n == (int64_t)(A.d + 1) * A.npts, "tg_flux_transform: an output of (d + 1) npts = %lld values",
              (long long)((A.d + 1) * A.npts));
   TG_TRY(tg_pp_point_array("tg_flux_transform", "s_q", s_q, 1, A.npts, &A.sq));
   TG_TRY(tg_pp_point_array("tg_flux_transform", "F_q", F_q, A.nsd, A.npts, &A.Fq));
   A.cout = out->d;
-  return rational ? tg_pp_launch<TG_PP_FLUX | TG_PP_RAT>(A, lds) : tg_pp_launch<TG_PP_FLUX>(A, lds);
+  return tg_pp_launch_rat<TG_PP_FLUX>(rational != 0, A, lds);
 }
 
 static int tg_pp_load_flux(const tg_patch_t *patch, tg_vec_t s_q, tg_vec_t F_q, tg_vec_t out, bool rat) {
   tg_pp_args A;
   size_t lds;
-  TG_TRY(tg_pp_setup(patch, 4, nullptr, &A, &lds));
-  int64_t nnodes = 1;
-  for (int k = 0; k < A.d; k++) nnodes *= A.n[k];
-  TG_REQUIRE(out && out->n == nnodes, "tg_quad_load_flux: an output on the %lld FE nodes", (long long)nnodes);
+  int64_t nnodes;
+  TG_TRY(tg_pp_setup("tg_quad_load_flux", patch, 4, nullptr, &A, &lds, &nnodes));
   TG_TRY(tg_pp_point_array("tg_quad_load_flux", "s_q", s_q, 1, A.npts, &A.sq));
   TG_TRY(tg_pp_point_array("tg_quad_load_flux", "F_q", F_q, A.nsd, A.npts, &A.Fq));
-  A.out = out->d;
-  TG_CHECK_HIP(hipMemsetAsync(out->d, 0, (size_t)nnodes * sizeof(double), g_tg.stream));
-  return rat ? tg_pp_launch_colours<2 | TG_PP_FLUX | TG_PP_RAT>(A, lds) : tg_pp_launch_colours<2 | TG_PP_FLUX>(A, lds);
+  TG_TRY(tg_point_nodal_output("tg_quad_load_flux", out, nnodes, &A.out));
+  return tg_pp_launch_rat<2 | TG_PP_FLUX>(rat, A, lds);
 }
 
 static int tg_pp_error(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, tg_vec_t ge_q, double *out, bool rat) {
   tg_pp_args A;
   size_t lds;
   TG_REQUIRE(out, "tg_quad_error: no output");
-  TG_TRY(tg_pp_setup(patch, 3, u_nodal, &A, &lds));
+  TG_TRY(tg_pp_setup("tg_quad_error", patch, 3, u_nodal, &A, &lds));
   TG_REQUIRE(!e_q || e_q->n == A.npts, "tg_quad_error: npts = %lld point values of e", (long long)A.npts);
   TG_REQUIRE(!ge_q || ge_q->n == (int64_t)A.nsd * A.npts, "tg_quad_error: nsd * npts = %lld point values of the gradient of e",
              (long long)(A.nsd * A.npts));
@@ -731,10 +658,7 @@ static int tg_pp_error(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, 
   tg_dbuf<double> part;
   TG_TRY(part.alloc(3 * A.nelem + 3));
   A.part = part.get();
-  if (rat)
-    TG_TRY(tg_pp_launch<3 | TG_PP_RAT>(A, lds));
-  else
-    TG_TRY(tg_pp_launch<3>(A, lds));
+  TG_TRY(tg_pp_launch_rat<3>(rat, A, lds));
   double *sums = part.get() + 3 * A.nelem;
   hipLaunchKernelGGL(k_postproc_fold, dim3(3), dim3(256), 0, g_tg.stream, part.get(), A.nelem, sums);
   TG_LAUNCH_CHECK();

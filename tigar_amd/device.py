@@ -1158,6 +1158,10 @@ def quad_count(vertices, nq):
     return n
 
 
+def _h_or_none(v):
+    return v._h if v is not None else None
+
+
 def quad_points(vertices, p, cp, nq=None):
     """(x, wdet): the physical positions x_q = F(xi_q) of the Gauss points (DeviceVector of nsd * npts values,
     component-major) and the weights wdet_q = w_q sqrt(det g) prod h_k of the mapped forms (``tg_quad_points``).  Points
@@ -1180,7 +1184,7 @@ def quad_eval(vertices, p, cp, u, grad=False, nq=None, rational=False):
     val = DeviceVector(npts, zero=False)
     g = DeviceVector((len(cp) - 1) * npts, zero=False) if grad else None
     name = "tg_quad_eval_rational" if rational else "tg_quad_eval"
-    check(getattr(_lib.lib(), name)(C.byref(pt), u._h, 1 if grad else 0, val._h, g._h if grad else None), name)
+    check(getattr(_lib.lib(), name)(C.byref(pt), u._h, 1 if grad else 0, val._h, _h_or_none(g)), name)
     return (val, g) if grad else val
 
 
@@ -1201,13 +1205,8 @@ def quad_error(vertices, p, cp, u=None, e=None, ge=None, nq=None, rational=False
     pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
     out = np.zeros(3)
     name = "tg_quad_error_rational" if rational else "tg_quad_error"
-    check(getattr(_lib.lib(), name)(C.byref(pt), u._h if u is not None else None, e._h if e is not None else None,
-                                    ge._h if ge is not None else None, _p(out, c_f64p)), name)
+    check(getattr(_lib.lib(), name)(C.byref(pt), _h_or_none(u), _h_or_none(e), _h_or_none(ge), _p(out, c_f64p)), name)
     return float(out[0]), float(out[1]), float(out[2])
-
-
-def _h_or_none(v):
-    return v._h if v is not None else None
 
 
 def coef_transform(vertices, p, cp, A=None, b=None, c=None, m=None, a_kind=None, nq=None, rational=False):
@@ -1340,8 +1339,7 @@ def face_eval(vertices, p, cp, direction, side, u, grad=False, normal_derivative
     g = DeviceVector((len(cp) - 1) * npts, zero=False) if grad else None
     dn = DeviceVector(npts, zero=False) if normal_derivative else None
     name = "tg_face_eval_rational" if rational else "tg_face_eval"
-    check(getattr(_lib.lib(), name)(C.byref(pt), int(direction), int(side), u._h, val._h, g._h if grad else None,
-                                    dn._h if normal_derivative else None), name)
+    check(getattr(_lib.lib(), name)(C.byref(pt), int(direction), int(side), u._h, val._h, _h_or_none(g), _h_or_none(dn)), name)
     return val, g, dn
 
 
@@ -1350,8 +1348,7 @@ def face_load(vertices, p, cp, direction, side, fq, fnq, out, nq=None, rational=
     None) of the face (``tg_face_load``; ``rational``: phi / W_h, ``tg_face_load_rational``); returns ``out``"""
     pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
     name = "tg_face_load_rational" if rational else "tg_face_load"
-    check(getattr(_lib.lib(), name)(C.byref(pt), int(direction), int(side), fq._h if fq is not None else None,
-                                    fnq._h if fnq is not None else None, out._h), name)
+    check(getattr(_lib.lib(), name)(C.byref(pt), int(direction), int(side), _h_or_none(fq), _h_or_none(fnq), out._h), name)
     return out
 
 

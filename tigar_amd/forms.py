@@ -410,16 +410,26 @@ class NodalLoadForm(object):
         return b
 
 
-def _whole_patch(geometry, V, who):
-    """(element vertices, degree, control functions) of a patch whose control functions this rank holds in full"""
-    g = _single_grid(V)
+def _whole_patch(geometry, g, who, operands="quadrature-point operands"):
+    """(element vertices, degree, control functions) of a patch with the node grid ``g`` whose control functions this rank
+    holds in full"""
     if _single_grid(geometry.V_control).shape() != g.shape():
         raise ValueError("the geometry lives on a different node grid than the space")
     cp, node0 = _control_window(geometry, 1, 0, g.shape()[-1])
     if node0 != 0 or any(v.size() != g.num_nodes() for v in cp):
-        raise NotImplementedError("%s: the control functions are spread over several ranks; quadrature-point operands are "
-                                  "provided on one rank" % who)
+        raise NotImplementedError("%s: the control functions are spread over several ranks; %s are provided on one rank"
+                                  % (who, operands))
     return [g.vertices[k] for k in range(g.dim())], int(g.degree), cp
+
+
+def _per_points(obj, slot, pts, build):
+    """``build()``: the point data of a callable, computed once per ``QuadraturePoints`` object and kept on ``obj`` under
+    ``slot``, one set of points at a time (``pts`` is kept alive next to the value: its id is the key)"""
+    cache = obj.__dict__.setdefault(slot, {})
+    if id(pts) not in cache:
+        cache.clear()
+        cache[id(pts)] = (build(), pts)
+    return cache[id(pts)][0]
 
 
 def _check_nq(nq, p):
@@ -490,7 +500,7 @@ class QuadraturePoints(object):
 def quadrature_points(geometry, V, nq=None, who="quadrature points"):
     """the ``QuadraturePoints`` of the patch of ``geometry`` (a generator or ExtractedSpline), kept on it per nq and per
     set of control-function vectors: new vectors give new points, values overwritten in place are not noticed"""
-    verts, p, cp = _whole_patch(geometry, V, who)
+    verts, p, cp = _whole_patch(geometry, _single_grid(V), who)
     nq = _check_nq(nq, p)
     cache = geometry.__dict__.setdefault("_quad_points", {})
     key = (nq, tuple(id(v) for v in cp))
@@ -518,31 +528,20 @@ class QuadratureLoadForm(object):
     def point_values(self, V):
         pts = quadrature_points(self.geometry, V, self.nq, "QuadratureLoadForm")
         if callable(self.f) and not hasattr(self.f, "vector"):
-            cache = self.__dict__.setdefault("_fq", {})
-            if id(pts) not in cache:
-                cache.clear()
-                cache[id(pts)] = (pts.values(self.f, "QuadratureLoadForm"), pts)      # (pts kept alive: id)
-            return pts, cache[id(pts)][0]
+            return pts, _per_points(self, "_fq", pts, lambda: pts.values(self.f, "QuadratureLoadForm"))
         return pts, pts.values(self.f, "QuadratureLoadForm")
 
     def assemble_vector(self, V, row0=None, row1=None):
         if self.flux is not None:
             _point_form_scope(self.geometry, "QuadratureLoadForm")
-        n = _single_grid(V).num_nodes()
-        if (0 if row0 is None else int(row0), n if row1 is None else int(row1)) != (0, n):
-            raise NotImplementedError("QuadratureLoadForm: row blocks (several ranks, streamed operands) are not supported; "
-                                      "the point values are numbered over the whole patch")
+        _whole_rows(_single_grid(V).num_nodes(), row0, row1, "QuadratureLoadForm", "patch")
         if self.flux is None:
             pts, fq = self.point_values(V)
             return _dev.quad_load(pts.verts, pts.p, pts.cp, fq, nq=pts.nq, rational=self.rational)
         pts, fq = self.point_values(V) if self.f is not None else \
             (quadrature_points(self.geometry, V, self.nq, "QuadratureLoadForm"), None)
         if callable(self.flux):
-            cache = self.__dict__.setdefault("_Fq", {})
-            if id(pts) not in cache:
-                cache.clear()
-                cache[id(pts)] = (pts.vector_values(self.flux, "QuadratureLoadForm: flux"), pts)     # (pts kept alive: id)
-            Fq = cache[id(pts)][0]
+            Fq = _per_points(self, "_Fq", pts, lambda: pts.vector_values(self.flux, "QuadratureLoadForm: flux"))
         else:
             Fq = pts.vector_values(self.flux, "QuadratureLoadForm: flux")
         return _dev.quad_load_flux(pts.verts, pts.p, pts.cp, fq, Fq, nq=pts.nq, rational=self.rational)
@@ -745,9 +744,8 @@ class CoefficientForm(object):
         who = "CoefficientForm"
         _point_form_scope(self.geometry, who)
         pts = quadrature_points(self.geometry, V, self.nq, who)
-        cache = self.__dict__.setdefault("_static", {})
-        if id(pts) not in cache:
-            cache.clear()
+
+        def static():
             kind, A, symA = 0, None, True
             if self.diffusion is not None and not self._is_function(self.diffusion):
                 kind, A, symA = _tensor_values(pts, self.diffusion, who + ": diffusion")
@@ -758,8 +756,8 @@ class CoefficientForm(object):
                 m = pts.values(self.reaction, who + ": reaction")
             symbc = (b is None and c is None) or (b is not None and c is not None and
                                                    (b is c or _same_bits(b.get_local(), c.get_local())))
-            cache[id(pts)] = (pts, kind, A, b, c, m, bool(symA and symbc))
-        pts, kind, A, b, c, m, sym = cache[id(pts)]
+            return kind, A, b, c, m, bool(symA and symbc)
+        kind, A, b, c, m, sym = _per_points(self, "_static", pts, static)
         if self._is_function(self.diffusion):
             kind, A = 1, pts.values(self.diffusion, who + ": diffusion")
         if self._is_function(self.reaction):
@@ -852,6 +850,16 @@ class _QuasilinearTangent(object):
 
 
 # ---- vector-valued unknowns with point tangents: finite-strain elasticity (csrc/tg_material.hip) ----------------------------
+def _shared_grid(V):
+    """the node grid of a space whose fields share one continuous Q_p node grid of a tensor-product patch, or None"""
+    g = V.grids[0]
+    if getattr(g, "dg", True) or not hasattr(g, "axes") or any(
+            gi.degree != g.degree or gi.dg or len(gi.axes) != len(g.axes) or
+            any(not numpy.array_equal(a, b) for a, b in zip(gi.axes, g.axes)) for gi in V.grids[1:]):
+        return None
+    return g
+
+
 def _vector_form_scope(geometry, V, who):
     """(node grid, nF) of a displacement space on the patch of ``geometry``: nF = nsd = d fields on one continuous Q_p node
     grid, dofs field after field (``EqualOrderSpline(d, mesh)``); refuses everything else with the reason.  An
@@ -862,10 +870,8 @@ def _vector_form_scope(geometry, V, who):
     if scope is not None:
         scope(who)
     _fields_of_the_patch(geometry, who)
-    g = V.grids[0]
-    if getattr(g, "dg", True) or not hasattr(g, "axes") or any(
-            gi.degree != g.degree or gi.dg or len(gi.axes) != len(g.axes) or
-            any(not numpy.array_equal(a, b) for a, b in zip(gi.axes, g.axes)) for gi in V.grids[1:]):
+    g = _shared_grid(V)
+    if g is None:
         raise NotImplementedError("%s: the fields of the space must share one continuous Q_p node grid of a tensor-product "
                                   "patch (compatible, FieldList, multi-patch, T-spline and DG spaces are not supported)" % who)
     nF, nsd, d = len(V.grids), len(geometry.cpFuncs) - 1, g.dim()
@@ -999,10 +1005,9 @@ class VectorCoefficientForm(object):
         who = "VectorCoefficientForm"
         g, nF = _vector_form_scope(self.geometry, V, who)
         pts = _vector_points(self.geometry, self.nq, who)
-        cache = self.__dict__.setdefault("_static", {})
-        if id(pts) in cache:
-            return cache[id(pts)]
-        cache.clear()
+        return _per_points(self, "_static", pts, lambda: self._static_coefficients(pts, nF, who))
+
+    def _static_coefficients(self, pts, nF, who):
         npts, nsd = pts.npts, pts.nsd
         if isinstance(self.tangent, _dev.DeviceVector):
             A = self.tangent
@@ -1038,8 +1043,7 @@ class VectorCoefficientForm(object):
             M, symM = _dev.DeviceVector(data=numpy.ascontiguousarray(v.transpose(1, 2, 0)).ravel()), _same_bits(v, v.transpose(0, 2, 1))
         if sym is None:
             sym = bool(self._symmetric_hint)
-        cache[id(pts)] = (pts, A, M, bool(sym and symM))
-        return cache[id(pts)]
+        return pts, A, M, bool(sym and symM)
 
     @property
     def symmetric(self):
@@ -1113,9 +1117,8 @@ class VectorLoadForm(object):
         n = g.num_nodes()
         _whole_rows(nF * n, row0, row1, who, "patch")
         pts = _vector_points(self.geometry, self.nq, who)
-        cache = self.__dict__.setdefault("_static", {})
-        if id(pts) not in cache:
-            cache.clear()
+
+        def static():
             s = _field_values(pts, self.f, nF, who + ": f") if self.f is not None else None
             F = None
             if isinstance(self.flux, _dev.DeviceVector):
@@ -1128,8 +1131,8 @@ class VectorLoadForm(object):
                     raise ValueError("%s: flux: an array of shape %s for %d points; expected (%d, %d, %d)"
                                      % (who, v.shape, pts.npts, pts.npts, nF, pts.nsd))
                 F = _dev.DeviceVector(data=numpy.ascontiguousarray(v.transpose(1, 2, 0)).ravel())
-            cache[id(pts)] = (s, F, pts)                                # (pts kept alive: id)
-        s, F, _ = cache[id(pts)]
+            return s, F
+        s, F = _per_points(self, "_static", pts, static)
         return _field_loads(pts, n, nF, s, F, self.rational)
 
 
@@ -1208,11 +1211,7 @@ class HyperelasticResidual(object):
         pts, g, nF, P, _, _ = self.law(V)
         s = None
         if self.body_force is not None:
-            cache = self.__dict__.setdefault("_fq", {})
-            if id(pts) not in cache:
-                cache.clear()
-                cache[id(pts)] = (_field_values(pts, self.body_force, nF, who + ": body_force", scale=-1.0), pts)
-            s = cache[id(pts)][0]
+            s = _per_points(self, "_fq", pts, lambda: _field_values(pts, self.body_force, nF, who + ": body_force", scale=-1.0))
         return _field_loads(pts, g.num_nodes(), nF, s, P, self.rational)
 
     def energy(self, V=None):
@@ -1305,10 +1304,8 @@ def _need_boundary_geometry(who, geometry):
 
 def _face_grid(V, who):
     """(node grid, number of fields) of a space whose fields share one CG node grid"""
-    g = V.grids[0]
-    if getattr(g, "dg", True) or not hasattr(g, "axes") or any(
-            gi.degree != g.degree or gi.dg or len(gi.axes) != len(g.axes) or
-            any(not numpy.array_equal(a, b) for a, b in zip(gi.axes, g.axes)) for gi in V.grids[1:]):
+    g = _shared_grid(V)
+    if g is None:
         raise NotImplementedError("%s: the fields of the space must share one continuous Q_p node grid of a tensor-product "
                                   "patch" % who)
     if g.dim() not in (2, 3):
@@ -1367,18 +1364,12 @@ def face_points(geometry, V, direction, side, nq=None, who="boundary points"):
     g, _ = _face_grid(V, who)
     _fields_of_the_patch(geometry, who)
     (direction, side), = check_faces((direction, side), g.dim(), who, _periodic_directions(geometry))
-    gc = _single_grid(geometry.V_control)
-    if gc.shape() != g.shape():
-        raise ValueError("the geometry lives on a different node grid than the space")
-    cp, node0 = _control_window(geometry, 1, 0, g.shape()[-1])
-    if node0 != 0 or any(v.size() != g.num_nodes() for v in cp):
-        raise NotImplementedError("%s: the control functions are spread over several ranks; boundary operands are provided "
-                                  "on one rank" % who)
-    nq = _check_nq(nq, int(g.degree))
+    verts, p, cp = _whole_patch(geometry, g, who, "boundary operands")
+    nq = _check_nq(nq, p)
     cache = geometry.__dict__.setdefault("_face_points", {})
     key = (direction, side, nq, tuple(id(v) for v in cp))
     if key not in cache:
-        cache[key] = FacePoints([g.vertices[k] for k in range(g.dim())], int(g.degree), cp, nq, direction, side)
+        cache[key] = FacePoints(verts, p, cp, nq, direction, side)
     return cache[key]
 
 

@@ -72,7 +72,7 @@ int main() {
         }
   free(g_asm_cache.tab);
   free(g_tg.host_pinned);
-  printf("coef_host_sweep: %ld cases (patch x space x diffusion kind), every entry point, largest LDS request %zu B: clean\n", cases,
-         g_host_lds_max);
+  printf("coef_host_sweep: %ld cases (patch x space x diffusion kind), every entry point, largest LDS request %zu B, outputs fnv1a %016llx: clean\n",
+         cases, g_host_lds_max, (unsigned long long)g_fnv);
   return 0;
 }

@@ -2,7 +2,8 @@
 // source of csrc/tg_postproc.hip and csrc/tg_coef.hip WITH their host drivers, compiled as plain C++ against this directory's
 // hip/hip_runtime.h, and host stand-ins for what those drivers call in the rest of the library -- the allocator, the
 // reference-element tables, the element-coupling pattern, tg_csr_from_blocks -- each allocating EXACTLY what the kernels may
-// touch.  Include once, from the file that has main().
+// touch.  Both sources include csrc/tg_point_shared.h (static inline and templates only: one translation unit here).  Include
+// once, from the file that has main().
 #pragma once
 #include <hip/hip_runtime.h>
 dim3 threadIdx, blockIdx, blockDim;
@@ -125,7 +126,12 @@ static void drop(tg_vec_s *v) {
     }                                                                    \
   } while (0)
 
+// every output array passes through here: finite, and folded into a running 64-bit FNV-1a of its bytes.  Two builds of a
+// sweep (without sanitizers, -ffp-contract=off) that print the same value computed the same numbers
+static uint64_t g_fnv = 1469598103934665603ull;
 static int finite_all(const double *v, int64_t n) {
+  const unsigned char *b = reinterpret_cast<const unsigned char *>(v);
+  for (int64_t i = 0; i < n * (int64_t)sizeof(double); i++) g_fnv = (g_fnv ^ b[i]) * 1099511628211ull;
   for (int64_t i = 0; i < n; i++)
     if (!std::isfinite(v[i])) return 0;
   return 1;

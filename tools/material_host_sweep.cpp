@@ -145,7 +145,7 @@ int main() {
       }
   free(g_asm_cache.tab);
   free(g_tg.host_pinned);
-  printf("material_host_sweep: %ld cases (laws x outputs x point counts, patches x space x reaction), largest LDS request %zu B: clean\n",
-         cases, g_host_lds_max);
+  printf("material_host_sweep: %ld cases (laws x outputs x point counts, patches x space x reaction), largest LDS request %zu B, outputs fnv1a %016llx: clean\n",
+         cases, g_host_lds_max, (unsigned long long)g_fnv);
   return 0;
 }
