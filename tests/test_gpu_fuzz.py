@@ -81,7 +81,8 @@ def test_hand_added_couplings_on_patches_with_repeated_knots():
 
 
 @pytest.mark.parametrize("seed,env", [(201, {}), (202, {"TIGAR_PTAP_WAVE": "1"}), (203, {"TIGAR_PTAP_ACCUM": "int"}),
-                                      (204, {"TIGAR_POOL_POISON": "1", "TIGAR_KSP_PERSISTENT": "1"})])
+                                      (204, {"TIGAR_POOL_POISON": "1", "TIGAR_KSP_PERSISTENT": "1"}),
+                                      (205, {"TIGAR_KSP_PERSISTENT": "1", "TIGAR_KSP_PERSISTENT_WGS": "2"})])
 def test_random_sparse_matrices_through_the_kernels(seed, env):
     """`tests/fuzz/fuzz_kernels.py`: matrices of any shape and row-length profile (empty, one row, empty rows, a few rows that fill
     the matrix) through SpMV / M^T b / transpose / add / selections / the general PtAP (structural pattern, values,

@@ -996,7 +996,8 @@ struct ps_dims {
 
 // Whether a system is taken by the persistent loop: one rank, at least a thousand rows (below, the launches are not what
 // the solve costs), rows of at most 128 entries, and all of K in the registers of one workgroup per CU
-// (TIGAR_KSP_PERSISTENT=0 turns it off, =1 lifts the lower limit).
+// (TIGAR_KSP_PERSISTENT=0 turns it off, =1 lifts the lower limit).  TIGAR_KSP_PERSISTENT_WGS=<k>, k >= 1, caps the number
+// of workgroups (never raises it): more rows per workgroup, so the shapes with many rows per group of lanes at a small n.
 static bool ps_shape(const tg_csr_s *k, int64_t rows_max, bool lds_layer, ps_dims *d) {
   const int64_t n = k->nrows;
   const int maxlen = k->max_row_nnz;
@@ -1004,6 +1005,8 @@ static bool ps_shape(const tg_csr_s *k, int64_t rows_max, bool lds_layer, ps_dim
   const int epr = (maxlen + 31) / 32;
   int G = std::min<int>(g_tg.num_cu, PS_MAXG);
   G = (int)std::min<int64_t>(G, std::max<int64_t>(1, tg_cdiv(n, PS_GROUPS)));
+  const int cap = getenv("TIGAR_KSP_PERSISTENT_WGS") ? atoi(getenv("TIGAR_KSP_PERSISTENT_WGS")) : 0;
+  if (cap >= 1) G = std::min(G, cap);
   const int64_t per = tg_cdiv(n, G);
   if (per > rows_max) return false;
   static const int shapes[][2] = {
