@@ -37,6 +37,7 @@
 // benchmark configurations use the Kronecker-sum generator (tg_kron.hip) instead.
 #include "tg_common.h"
 #include "tg_asm_shared.h"
+#include "tg_point_shared.h"     // (host side only: the patch check and the colour loop)
 #include <cmath>
 #include <utility>
 
@@ -1375,80 +1376,117 @@ __global__ void __launch_bounds__(64 * TG_ASF_NW) k_asf3_load(tg_asf_args A) {
 
 static inline int64_t tg_rps_host(int p, int a) { return (int64_t)(p + 1) * a + (a > 0 ? (int64_t)p * ((a - 1) / p) : 0); }
 
-// The rational forms take the default route of their un-rationalised twin and nothing else (p = 2: the walk; p = 3: the
-// walk for the mass matrix, the groups of four for the stiffness matrix): the routes the switches TIGAR_ASM_WALK / _QUAD /
-// _PRE force are not instantiated for them (the p = 3 stiffness walk runs out of registers as it is).
-template <int P1, int EPW>
-static void tg_asf_launch_rat(int form, const tg_asf_args &A, unsigned nblk) {
-  const dim3 g(nblk), b(64 * TG_ASF_NW);
-  if (form == 2) {
-    hipLaunchKernelGGL((k_asf3_load<P1, EPW | TG_ASF_LOAD_RAT>), g, b, 0, g_tg.stream, A);
-  } else if (form == 0) {
-    hipLaunchKernelGGL((k_asf3<P1, EPW, 0 | TG_ASF_RAT>), g, b, 0, g_tg.stream, A);
-  } else if constexpr (P1 == 4) {
-    if (A.chunk > 1)             // (pieces of several groups: the workgroup loops)
-      hipLaunchKernelGGL((k_asf3_quad<P1, 1 | TG_ASF_RAT, 1, 1>), g, b, 0, g_tg.stream, A);
-    else
-      hipLaunchKernelGGL((k_asf3_quad<P1, 1 | TG_ASF_RAT, 1, 0>), g, b, 0, g_tg.stream, A);
-  } else {
-    hipLaunchKernelGGL((k_asf3<P1, EPW, 1 | TG_ASF_RAT>), g, b, 0, g_tg.stream, A);
-  }
+// ---- the routes of the sum-factorised kernels: ONE table with a row per instantiation, ONE chooser (DESIGN.md has the rules)
+enum { TG_ASF_FAM_LOAD, TG_ASF_FAM_WALK, TG_ASF_FAM_ELEM, TG_ASF_FAM_QUAD };
+enum { TG_ASM_PLAIN, TG_ASM_RATIONAL, TG_ASM_COEF };     // the variant of a form: which functions, which coefficient
+
+struct tg_asf_key {
+  int p1, family;
+  int formr;           // 0 mass, 1 stiffness, 2 elasticity (load: 0), | TG_ASF_RAT, | TG_ASF_COEF
+  int pre, loop;       // the groups of four only
+};
+struct tg_asf_route {
+  tg_asf_key key;
+  void (*kernel)(tg_asf_args);
+  const char *name;
+};
+#define TG_ASF_ROW(P1, FAM, FORMR, PRE, LOOP, ...) {{P1, TG_ASF_FAM_##FAM, FORMR, PRE, LOOP}, &__VA_ARGS__, #__VA_ARGS__}
+static const tg_asf_route g_asf_routes[] = {
+    // point coefficients: the default route of the stiffness matrix of the degree
+    TG_ASF_ROW(4, QUAD, 1 | TG_ASF_COEF, 1, 1, k_asf3_quad<4,9,1,1>),
+    TG_ASF_ROW(4, QUAD, 1 | TG_ASF_COEF, 1, 0, k_asf3_quad<4,9,1,0>),
+    TG_ASF_ROW(3, WALK, 1 | TG_ASF_COEF, 0, 0, k_asf3<3,2,9>),
+    // rational functions: the default route of the un-rationalised twin and nothing else (the routes the switches force are
+    // not instantiated: the p = 3 stiffness walk runs out of registers as it is)
+    TG_ASF_ROW(4, LOAD, TG_ASF_RAT, 0, 0, k_asf3_load<4,17>),
+    TG_ASF_ROW(4, WALK, 0 | TG_ASF_RAT, 0, 0, k_asf3<4,1,4>),
+    TG_ASF_ROW(4, QUAD, 1 | TG_ASF_RAT, 1, 1, k_asf3_quad<4,5,1,1>),
+    TG_ASF_ROW(4, QUAD, 1 | TG_ASF_RAT, 1, 0, k_asf3_quad<4,5,1,0>),
+    TG_ASF_ROW(3, LOAD, TG_ASF_RAT, 0, 0, k_asf3_load<3,18>),
+    TG_ASF_ROW(3, WALK, 0 | TG_ASF_RAT, 0, 0, k_asf3<3,2,4>),
+    TG_ASF_ROW(3, WALK, 1 | TG_ASF_RAT, 0, 0, k_asf3<3,2,5>),
+    // p = 3
+    TG_ASF_ROW(4, QUAD, 2, 1, 1, k_asf3_quad<4,2,1,1>),
+    TG_ASF_ROW(4, QUAD, 2, 1, 0, k_asf3_quad<4,2,1,0>),
+    TG_ASF_ROW(4, QUAD, 2, 0, 0, k_asf3_quad<4,2,0,0>),
+    TG_ASF_ROW(4, QUAD, 1, 1, 1, k_asf3_quad<4,1,1,1>),
+    TG_ASF_ROW(4, QUAD, 1, 1, 0, k_asf3_quad<4,1,1,0>),
+    TG_ASF_ROW(4, QUAD, 1, 0, 0, k_asf3_quad<4,1,0,0>),
+    TG_ASF_ROW(4, ELEM, 2, 0, 0, k_asf3_elem<4,1,2>),
+    TG_ASF_ROW(4, WALK, 2, 0, 0, k_asf3<4,1,2>),
+    TG_ASF_ROW(4, ELEM, 1, 0, 0, k_asf3_elem<4,1,1>),
+    TG_ASF_ROW(4, ELEM, 0, 0, 0, k_asf3_elem<4,1,0>),
+    TG_ASF_ROW(4, WALK, 1, 0, 0, k_asf3<4,1,1>),
+    TG_ASF_ROW(4, WALK, 0, 0, 0, k_asf3<4,1,0>),
+    TG_ASF_ROW(4, LOAD, 0, 0, 0, k_asf3_load<4,1>),
+    // p = 2
+    TG_ASF_ROW(3, ELEM, 2, 0, 0, k_asf3_elem<3,2,2>),
+    TG_ASF_ROW(3, WALK, 2, 0, 0, k_asf3<3,2,2>),
+    TG_ASF_ROW(3, ELEM, 1, 0, 0, k_asf3_elem<3,2,1>),
+    TG_ASF_ROW(3, ELEM, 0, 0, 0, k_asf3_elem<3,2,0>),
+    TG_ASF_ROW(3, WALK, 1, 0, 0, k_asf3<3,2,1>),
+    TG_ASF_ROW(3, WALK, 0, 0, 0, k_asf3<3,2,0>),
+    TG_ASF_ROW(3, LOAD, 0, 0, 0, k_asf3_load<3,2>),
+    // p = 1
+    TG_ASF_ROW(2, ELEM, 2, 0, 0, k_asf3_elem<2,8,2>),
+    TG_ASF_ROW(2, WALK, 2, 0, 0, k_asf3<2,8,2>),
+    TG_ASF_ROW(2, ELEM, 1, 0, 0, k_asf3_elem<2,8,1>),
+    TG_ASF_ROW(2, ELEM, 0, 0, 0, k_asf3_elem<2,8,0>),
+    TG_ASF_ROW(2, WALK, 1, 0, 0, k_asf3<2,8,1>),
+    TG_ASF_ROW(2, WALK, 0, 0, 0, k_asf3<2,8,0>),
+    TG_ASF_ROW(2, LOAD, 0, 0, 0, k_asf3_load<2,8>),
+};
+#undef TG_ASF_ROW
+
+static const tg_asf_route *tg_asf_find(const tg_asf_key &k) {
+  for (const tg_asf_route &r : g_asf_routes)
+    if (memcmp(&r.key, &k, sizeof(k)) == 0) return &r;          // (five ints: no padding)
+  return nullptr;
 }
 
-// The point-coefficient form takes the default route of the stiffness matrix of its degree: p = 2 the walk, p = 3 the
-// groups of four (looping over its pieces or not)
-template <int P1, int EPW>
-static void tg_asf_launch_coef(const tg_asf_args &A, unsigned nblk) {
-  const dim3 g(nblk), b(64 * TG_ASF_NW);
-  if constexpr (P1 == 4) {
-    if (A.chunk > 1)
-      hipLaunchKernelGGL((k_asf3_quad<P1, 1 | TG_ASF_COEF, 1, 1>), g, b, 0, g_tg.stream, A);
-    else
-      hipLaunchKernelGGL((k_asf3_quad<P1, 1 | TG_ASF_COEF, 1, 0>), g, b, 0, g_tg.stream, A);
-  } else {
-    hipLaunchKernelGGL((k_asf3<P1, EPW, 1 | TG_ASF_COEF>), g, b, 0, g_tg.stream, A);
-  }
+// the switches of the environment, read once per call
+struct tg_asm_switches {
+  bool legacy, time;
+  bool forced;                 // one of TIGAR_ASM_WALK / _QUAD / _PRE is set
+  int walk, quad, pre;         // their values, -1: not set
+  int chunk, quad_chunk;       // elements per piece of a line (16) / groups of four per piece (8), at least 1
+};
+
+static tg_asm_switches tg_asm_switches_read() {
+  auto num = [](const char *name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; };
+  tg_asm_switches S;
+  S.legacy = getenv("TIGAR_ASM_LEGACY") != nullptr;
+  S.time = getenv("TIGAR_ASM_TIME") != nullptr;
+  S.walk = getenv("TIGAR_ASM_WALK") ? num("TIGAR_ASM_WALK", 0) != 0 : -1;
+  S.quad = getenv("TIGAR_ASM_QUAD") ? num("TIGAR_ASM_QUAD", 0) != 0 : -1;
+  S.pre = num("TIGAR_ASM_PRE", -1);
+  S.forced = getenv("TIGAR_ASM_WALK") || getenv("TIGAR_ASM_QUAD") || getenv("TIGAR_ASM_PRE");
+  S.chunk = std::max(1, num("TIGAR_ASM_CHUNK", 16));
+  S.quad_chunk = std::max(1, num("TIGAR_ASM_QUAD_CHUNK", 8));
+  return S;
 }
 
-template <int P1, int EPW>
-static void tg_asf_launch(int form, const tg_asf_args &A, unsigned nblk, bool walk, bool line) {
-  if constexpr (P1 == 4) {
-    const bool pre = !(getenv("TIGAR_ASM_PRE") && atoi(getenv("TIGAR_ASM_PRE")) == 0);
-    const bool loop = A.chunk > 1;             // (pieces of several groups: the workgroup loops)
-    const dim3 g(nblk), b(64 * TG_ASF_NW);
-    if (line && form == 3) {
-      if (loop)
-        hipLaunchKernelGGL((k_asf3_quad<P1, 2, 1, 1>), g, b, 0, g_tg.stream, A);
-      else if (pre)
-        hipLaunchKernelGGL((k_asf3_quad<P1, 2, 1, 0>), g, b, 0, g_tg.stream, A);
-      else
-        hipLaunchKernelGGL((k_asf3_quad<P1, 2, 0, 0>), g, b, 0, g_tg.stream, A);
-      return;
-    }
-    if (line && form == 1) {
-      if (loop)
-        hipLaunchKernelGGL((k_asf3_quad<P1, 1, 1, 1>), g, b, 0, g_tg.stream, A);
-      else if (pre)
-        hipLaunchKernelGGL((k_asf3_quad<P1, 1, 1, 0>), g, b, 0, g_tg.stream, A);
-      else
-        hipLaunchKernelGGL((k_asf3_quad<P1, 1, 0, 0>), g, b, 0, g_tg.stream, A);
-      return;
-    }
+// which sum-factorised kernel a form of degree p takes (the shape has such a route: tg_asm_plan_make decides that)
+static tg_asf_key tg_asf_choose(int p, int form, int variant, const tg_asm_switches &S) {
+  const int p1 = p + 1, loop = S.quad_chunk > 1;             // (pieces of several groups: the workgroup loops)
+  if (form == 2) return {p1, TG_ASF_FAM_LOAD, variant == TG_ASM_RATIONAL ? TG_ASF_RAT : 0, 0, 0};
+  if (variant != TG_ASM_PLAIN) {           // mass and stiffness only; the switches are not applied
+    const int v = variant == TG_ASM_RATIONAL ? TG_ASF_RAT : TG_ASF_COEF;
+    if (form == 1 && p == 3) return {p1, TG_ASF_FAM_QUAD, 1 | v, 1, loop};
+    return {p1, TG_ASF_FAM_WALK, form | v, 0, 0};
   }
-  if (!walk && form == 3)
-    hipLaunchKernelGGL((k_asf3_elem<P1, EPW, 2>), dim3(nblk), dim3(64 * TG_ASF_NW), 0, g_tg.stream, A);
-  else if (form == 3)
-    hipLaunchKernelGGL((k_asf3<P1, EPW, 2>), dim3(nblk), dim3(64 * TG_ASF_NW), 0, g_tg.stream, A);
-  else if (!walk && form == 1)
-    hipLaunchKernelGGL((k_asf3_elem<P1, EPW, 1>), dim3(nblk), dim3(64 * TG_ASF_NW), 0, g_tg.stream, A);
-  else if (!walk && form == 0)
-    hipLaunchKernelGGL((k_asf3_elem<P1, EPW, 0>), dim3(nblk), dim3(64 * TG_ASF_NW), 0, g_tg.stream, A);
-  else if (form == 1)
-    hipLaunchKernelGGL((k_asf3<P1, EPW, 1>), dim3(nblk), dim3(64 * TG_ASF_NW), 0, g_tg.stream, A);
-  else if (form == 0)
-    hipLaunchKernelGGL((k_asf3<P1, EPW, 0>), dim3(nblk), dim3(64 * TG_ASF_NW), 0, g_tg.stream, A);
-  else
-    hipLaunchKernelGGL((k_asf3_load<P1, EPW>), dim3(nblk), dim3(64 * TG_ASF_NW), 0, g_tg.stream, A);
+  const bool stiff = form == 1 || form == 3;
+  const int f = form == 3 ? 2 : form;
+  // the walk along direction 0 for every matrix form but the p = 3 stiffness matrix (see k_asf3_elem); TIGAR_ASM_WALK=0/1 forces
+  bool walk = p == 2 || (p == 3 && !stiff);
+  if (S.walk >= 0) walk = S.walk != 0;
+  // p = 3 stiffness / elasticity: the four waves of a workgroup on four consecutive elements of a line (k_asf3_quad;
+  // TIGAR_ASM_QUAD=0: independent elements)
+  bool quad = !walk && p == 3 && stiff;
+  if (quad && S.quad >= 0) quad = S.quad != 0;
+  if (walk) return {p1, TG_ASF_FAM_WALK, f, 0, 0};
+  if (quad) return {p1, TG_ASF_FAM_QUAD, f, loop || S.pre != 0, loop};
+  return {p1, TG_ASF_FAM_ELEM, f, 0, 0};
 }
 
 // reference-element tables l[a][q] | dl[a][q] | w[q]: equispaced Lagrange nodes a/p at the Gauss points
@@ -1560,253 +1598,233 @@ int tg_asm_coupling_pattern(int d, int p, const int *nn, int64_t row0, int64_t r
   return tg_kron_sum_csr(d, 1, dirs, row0, row1, out);
 }
 
-// rows [row0, row1) of the matrix / vector -- whole node planes of the LAST direction (any range when d == 1); the control
-// functions (and fnod) hold the nodes [cp_node0, cp_node0 + n), which must cover every element that touches the rows
+// ---- the host driver of every mapped form: request -> plan -> tables -> pattern or zeroed vector -> one launch per colour
 struct tg_elast_block {
   int i, j;
   double lam, mu;
 };
 
-// coef (with form 1): the point-coefficient form from its transformed data -- the sum-factorised route only; *coef_taken says
-// whether the shape has one (if not, nothing is done: tg_coef.hip has the plain kernel).  The control functions are not read.
-static int tg_assemble_common(const tg_patch_t *pt, int form, int64_t row0, int64_t row1, int64_t cp_node0, tg_csr_t *mout,
-                              tg_vec_t fnod, tg_vec_t bout, const tg_elast_block *eb = nullptr, bool rat = false,
-                              tg_vec_t coef = nullptr, bool *coef_taken = nullptr) {
-  TG_REQUIRE_INIT();
-  TG_REQUIRE(pt && pt->d >= 1 && pt->d <= 3 && pt->p >= 1 && pt->p <= TG_MAX_DEGREE && pt->nsd >= pt->d && pt->nsd <= 3,
-             "bad patch description");
-  TG_REQUIRE(pt->nq >= 1 && pt->nq <= TG_ASM_MAXQ1, "1..%d Gauss points per direction", TG_ASM_MAXQ1);
-  const int d = pt->d, p = pt->p, p1 = p + 1;
-  int nloc = 1, nqt = 1;
-  for (int k = 0; k < d; k++) {
-    nloc *= p1;
-    nqt *= pt->nq;
-  }
-  TG_REQUIRE(nloc <= TG_ASM_MAXLOC, "(p+1)^d = %d local nodes exceed the kernel limit %d", nloc, TG_ASM_MAXLOC);
-  tg_asm_args A;
-  memset(&A, 0, sizeof(A));
-  A.d = d;
-  A.p = p;
-  A.nsd = pt->nsd;
-  A.nq = pt->nq;
-  A.form = form;
-  A.rat = rat ? 1 : 0;
-  TG_REQUIRE(!(rat && form == 4), "the biharmonic form has no rational variant");
-  if (form == 4) TG_REQUIRE(pt->nsd == pt->d, "the biharmonic form needs as many physical as parametric directions");
-  if (form == 3) {
-    TG_REQUIRE(eb && pt->nsd == pt->d && eb->i >= 0 && eb->i < pt->d && eb->j >= 0 && eb->j < pt->d,
-               "elasticity block (i, j): as many physical as parametric directions (nsd == d = %d), 0 <= i, j < d", pt->d);
-    A.ei = eb->i;
-    A.ej = eb->j;
-    A.lam = eb->lam;
-    A.mu = eb->mu;
-  }
-  int64_t nnodes = 1, plane = 1;
-  for (int k = 0; k < 3; k++) {
-    A.nel[k] = 1;
-    A.n[k] = 1;
-  }
-  for (int k = 0; k < d; k++) {
-    TG_REQUIRE(pt->nverts[k] >= 2 && pt->verts[k], "direction %d needs at least one element", k);
-    A.nel[k] = pt->nverts[k] - 1;
-    A.n[k] = A.nel[k] * p + 1;
-    nnodes *= A.n[k];
-    if (k < d - 1) plane *= A.n[k];
-  }
-  if (row0 < 0 && row1 < 0) {
-    row0 = 0;
-    row1 = nnodes;
-  }
-  TG_REQUIRE(row0 >= 0 && row1 >= row0 && row1 <= nnodes && row0 % plane == 0 && row1 % plane == 0,
-             "row range [%lld, %lld): whole node planes of the last direction (%lld nodes each) of the %lld FE nodes",
-             (long long)row0, (long long)row1, (long long)plane, (long long)nnodes);
-  const int za = (int)(row0 / plane), zb = (int)(row1 / plane);
+// rows [row0, row1) of the matrix / vector -- whole node planes of the LAST direction (any range when d == 1; both negative:
+// all rows); the control functions (and fnod) hold the nodes [cp_node0, cp_node0 + n), which must cover every element that
+// touches the rows
+struct tg_asm_request {
+  const char *who;             // the C entry point the caller came through
+  int form;                    // 0 mass, 1 laplace, 2 load, 3 block eb of the elasticity form, 4 biharmonic
+  int64_t row0 = -1, row1 = -1, cp_node0 = 0;
+  bool rat = false;            // rational trial / test functions
+  tg_elast_block eb = {0, 0, 0.0, 0.0};
+  tg_vec_t fnod = nullptr, bout = nullptr;     // load: nodal values, output
+  // (with form 1) the point-coefficient form from its transformed data -- the sum-factorised route only: a shape without one is
+  // not taken (tg_coef.hip has the plain kernel).  The control functions are not read.
+  tg_vec_t coef = nullptr;
+};
+
+struct tg_asm_plan {
+  tg_patch_dims D;
+  tg_asm_switches S;
+  int64_t row0, row1;
+  int za, zb;                  // node planes of the last direction that hold the rows
+  int ez0, ez1;                // element layers of the last direction that touch them ...
+  int64_t need0, need1;        // ... and the nodes those need
+  const tg_asf_route *route;   // null: k_assemble_mapped
+  int chunk, nchunks;          // pieces of a line of elements (walk) or of groups of four (quad)
+  int64_t base;                // position of the first entry of FE plane za in the whole matrix
+  size_t lds;                  // k_assemble_mapped: dynamic LDS, and whether it needs the 160 KiB attribute
+  bool lds_attr;
+};
+
+// Step 1: everything that is decided from the request, the patch and the environment -- no HIP call
+static int tg_asm_plan_make(const tg_patch_t *pt, const tg_asm_request &rq, tg_asm_plan *P) {
+  tg_patch_dims &D = P->D;
+  TG_TRY(tg_patch_check(rq.who, pt, 1, /*fields=*/false, nullptr, &D));
+  const int d = D.d, p = D.p, p1 = p + 1, form = rq.form;
+  TG_REQUIRE(!(rq.rat && form == 4), "%s: the biharmonic form has no rational variant", rq.who);
+  if (form == 4) TG_REQUIRE(D.nsd == d, "%s: the biharmonic form needs as many physical as parametric directions", rq.who);
+  if (form == 3)
+    TG_REQUIRE(D.nsd == d && rq.eb.i >= 0 && rq.eb.i < d && rq.eb.j >= 0 && rq.eb.j < d,
+               "%s: elasticity block (i, j): as many physical as parametric directions (nsd == d = %d), 0 <= i, j < d", rq.who, d);
+  const int64_t plane = D.nnodes / D.n[d - 1];
+  const bool all = rq.row0 < 0 && rq.row1 < 0;
+  const int64_t row0 = P->row0 = all ? 0 : rq.row0, row1 = P->row1 = all ? D.nnodes : rq.row1;
+  TG_REQUIRE(row0 >= 0 && row1 >= row0 && row1 <= D.nnodes && row0 % plane == 0 && row1 % plane == 0,
+             "%s: row range [%lld, %lld): whole node planes of the last direction (%lld nodes each) of the %lld FE nodes", rq.who,
+             (long long)row0, (long long)row1, (long long)plane, (long long)D.nnodes);
+  const int za = P->za = (int)(row0 / plane), zb = P->zb = (int)(row1 / plane);
   // element layers of the last direction that touch the node planes [za, zb), and the nodes they need
-  const int nelL = A.nel[d - 1];
-  int ez0 = 0, ez1 = 0;
+  const int nelL = D.nel[d - 1];
+  int &ez0 = P->ez0 = 0, &ez1 = P->ez1 = 0;
   if (zb > za) {
     ez0 = (za > 0 && za % p == 0) ? za / p - 1 : za / p;
     ez1 = std::min(nelL, (zb - 1) / p + 1);
     if (ez0 >= nelL) ez0 = nelL - 1;           // (the last node plane belongs to the last layer)
   }
-  const int64_t need0 = (int64_t)ez0 * p * plane, need1 = (zb > za) ? ((int64_t)ez1 * p + 1) * plane : need0;
-  for (int c = 0; c <= pt->nsd && !coef; c++) {
-    TG_REQUIRE(pt->cp[c], "control function %d missing", c);
-    TG_REQUIRE(cp_node0 >= 0 && cp_node0 <= need0 && cp_node0 + pt->cp[c]->n >= need1,
-               "control function %d holds the FE nodes [%lld, %lld), the rows need [%lld, %lld)", c, (long long)cp_node0,
-               (long long)(cp_node0 + pt->cp[c]->n), (long long)need0, (long long)need1);
-    A.cp[c] = pt->cp[c]->d;
-  }
-  A.cp_node0 = cp_node0;
-  A.row0 = row0;
-  A.row1 = row1;
-  TG_TRY(tg_asm_cache_get(pt));
-  for (int k = 0; k < d; k++) A.verts[k] = g_asm_cache.verts[k];
-  A.tab = g_asm_cache.tab;
-  bool fast = d == 3 && pt->nsd == 3 && pt->nq == p1 && p <= 3 && form != 4 && !getenv("TIGAR_ASM_LEGACY");
-  // rational functions: mass, stiffness and load at p = 2, 3; the elasticity blocks and p = 1 take the plain kernel
-  if (rat && (form == 3 || p == 1)) fast = false;
-  if (fast) {   // the walk kernel addresses the entries of one plane of rows in 32 bits
-    const double t0 = (double)p1 * A.n[0] + (double)p * (A.nel[0] - 1), t1 = (double)p1 * A.n[1] + (double)p * (A.nel[1] - 1);
-    if ((2.0 * p + 1.0) * t0 * t1 * 8.0 >= 4294967000.0) fast = false;      // (byte offsets inside one plane of rows)
-  }
-  if (coef) {           // p = 2, 3
-    if (p == 1) fast = false;
-    *coef_taken = fast;
-    if (!fast) return 0;
+  P->need0 = (int64_t)ez0 * p * plane;
+  P->need1 = (zb > za) ? ((int64_t)ez1 * p + 1) * plane : P->need0;
+  for (int c = 0; c <= D.nsd && !rq.coef; c++) {       // (the point kernels have no windows: this check is the driver's)
+    TG_REQUIRE(pt->cp[c], "%s: control function %d missing", rq.who, c);
+    TG_REQUIRE(rq.cp_node0 >= 0 && rq.cp_node0 <= P->need0 && rq.cp_node0 + pt->cp[c]->n >= P->need1,
+               "%s: control function %d holds the FE nodes [%lld, %lld), the rows need [%lld, %lld)", rq.who, c,
+               (long long)rq.cp_node0, (long long)(rq.cp_node0 + pt->cp[c]->n), (long long)P->need0, (long long)P->need1);
   }
 
-  tg_csr_s *m = nullptr;
-  if (form != 2) {
-    tg_csr_t pat = nullptr;
-    TG_TRY(tg_asm_coupling_pattern(d, p, A.n, row0, row1, fast, &pat));
-    m = pat;
-    // (the pattern kernel wrote 0 * 0 * 0 into every value: the plain kernel adds into that; the sum-factorised kernel
-    //  stores every entry before anybody adds to it)
-    A.rowptr = m->rowptr;
-    A.val = m->val;
-  } else {
-    TG_REQUIRE(fnod && cp_node0 + fnod->n >= need1 && bout && bout->n == row1 - row0,
-               "load assembly needs nodal values on the nodes of the control functions and an output vector of %lld rows",
-               (long long)(row1 - row0));
-    A.fnod = fnod->d;
-    A.bout = bout->d;
-    TG_CHECK_HIP(hipMemsetAsync(bout->d, 0, (size_t)(row1 - row0) * sizeof(double), g_tg.stream));
+  const tg_asm_switches &S = P->S = tg_asm_switches_read();
+  const int variant = rq.coef ? TG_ASM_COEF : (rq.rat ? TG_ASM_RATIONAL : TG_ASM_PLAIN);
+  bool fast = d == 3 && D.nsd == 3 && D.nq == p1 && p <= 3 && form != 4 && !S.legacy;
+  // rational functions: mass, stiffness and load at p = 2, 3 (the elasticity blocks and p = 1 take the plain kernel); point
+  // coefficients: p = 2, 3
+  if ((rq.rat && form == 3) || (variant != TG_ASM_PLAIN && p == 1)) fast = false;
+  const int64_t T0 = (int64_t)p1 * D.n[0] + (int64_t)p * (D.nel[0] - 1), T1 = (int64_t)p1 * D.n[1] + (int64_t)p * (D.nel[1] - 1);
+  // the walk kernel addresses the entries of one plane of rows in 32 bits (byte offsets inside one plane of rows)
+  if (fast && (2.0 * p + 1.0) * (double)T0 * (double)T1 * 8.0 >= 4294967000.0) fast = false;
+  P->route = nullptr;
+  P->chunk = P->nchunks = 0;
+  P->base = T0 * T1 * tg_rps_host(p, za);
+  if (fast) {
+    const tg_asf_key k = tg_asf_choose(p, form, variant, S);
+    P->route = tg_asf_find(k);
+    TG_REQUIRE(P->route, "%s: internal error: no sum-factorised kernel for p1 %d, family %d, form %d, pre %d, loop %d", rq.who, k.p1,
+               k.family, k.formr, k.pre, k.loop);
+    // pieces of a line of elements: long enough that the element a piece starts early with (it only feeds the carry) costs
+    // little, short enough that a launch has waves for every SIMD.  Groups of four: pieces of `chunk` groups (a function of
+    // nothing but the environment: the seams fix the order of the sums, and row blocks must reproduce the whole matrix bit
+    // for bit)
+    const bool quad = k.family == TG_ASF_FAM_QUAD;
+    P->chunk = quad ? S.quad_chunk : S.chunk;
+    P->nchunks = ((quad ? (D.nel[0] + TG_ASF_NW - 1) / TG_ASF_NW : D.nel[0]) + P->chunk - 1) / P->chunk;
   }
+
   // (rational stiffness / elasticity: beta, 3 values per point, lies over S and fl, which these forms do not use)
-  const size_t tail = (rat && (form == 1 || form == 3)) ? std::max((size_t)nqt + nloc, (size_t)3 * nqt) : (size_t)nqt + nloc;
-  const size_t lds = ((size_t)3 * p1 * pt->nq + pt->nq + (size_t)(pt->nsd + 1) * nloc + (size_t)nqt * 9 + tail) * sizeof(double);
+  const size_t nqt = D.nqt, nloc = D.nloc, head = (size_t)3 * p1 * D.nq + D.nq + (size_t)(D.nsd + 1) * nloc;
+  const size_t tail = (rq.rat && (form == 1 || form == 3)) ? std::max(nqt + nloc, 3 * nqt) : nqt + nloc;
+  P->lds = (head + nqt * 9 + tail) * sizeof(double);
   // What a launch gets without asking is 64 KiB.  The rational stiffness / elasticity of a shape whose un-rationalised
   // twin fits into that may need up to 2 nqt doubles more: it asks for the LDS of a compute unit, so that every shape the
   // twins take is taken (the twins' own limit stays where it was)
-  const size_t lds_twin = ((size_t)3 * p1 * pt->nq + pt->nq + (size_t)(pt->nsd + 1) * nloc + (size_t)nqt * 10 + nloc) * sizeof(double);
-  if (!fast && lds > 64 * 1024 && lds_twin <= 64 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_assemble_mapped), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024) != hipSuccess) {
-      if (m) tg_csr_destroy(m);
-      tg_set_error("element data (%zu B): the launch could not get more than 64 KiB of LDS", lds);
-      return 2;
-    }
-  } else if (!fast && lds > 64 * 1024) {
-    if (m) tg_csr_destroy(m);
-    tg_set_error("element data (%zu B) does not fit in LDS", lds);
+  const size_t lds_twin = (head + nqt * 10 + nloc) * sizeof(double);
+  P->lds_attr = !fast && P->lds > 64 * 1024 && lds_twin <= 64 * 1024;
+  // (point coefficients without a route are not taken: tg_coef.hip's plain kernel has its own limit)
+  TG_REQUIRE(fast || rq.coef || P->lds <= 64 * 1024 || P->lds_attr, "%s: element data (%zu B) does not fit in LDS", rq.who, P->lds);
+  return 0;
+}
+
+// Step 3: the pattern of a matrix form, or the checked and zeroed vector of the load
+static int tg_asm_output(const tg_asm_request &rq, const tg_asm_plan &P, tg_csr_t *m) {
+  // (the pattern kernel wrote 0 * 0 * 0 into every value: the plain kernel adds into that; the sum-factorised kernel
+  //  stores every entry before anybody adds to it)
+  if (rq.form != 2) return tg_asm_coupling_pattern(P.D.d, P.D.p, P.D.n, P.row0, P.row1, P.route != nullptr, m);
+  TG_REQUIRE(rq.fnod && rq.cp_node0 + rq.fnod->n >= P.need1 && rq.bout && rq.bout->n == P.row1 - P.row0,
+             "%s: load assembly needs nodal values on the nodes of the control functions and an output vector of %lld rows", rq.who,
+             (long long)(P.row1 - P.row0));
+  TG_CHECK_HIP(hipMemsetAsync(rq.bout->d, 0, (size_t)(P.row1 - P.row0) * sizeof(double), g_tg.stream));
+  return 0;
+}
+
+// Step 4: one launch per colour (parity of the element index per direction), colours in ascending order, of the layers
+// [ez0, ez1) of the last direction.  The walk needs no colouring in direction 0; direction 0 of the groups of four counts PIECES
+static int tg_asm_launch(const tg_patch_t *pt, const tg_asm_request &rq, const tg_asm_plan &P, tg_csr_t m) {
+  const tg_patch_dims &D = P.D;
+  const int d = D.d, p = D.p, form = rq.form;
+  if (P.lds_attr && hipFuncSetAttribute(reinterpret_cast<const void *>(&k_assemble_mapped),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+    tg_set_error("%s: element data (%zu B): the launch could not get more than 64 KiB of LDS", rq.who, P.lds);
     return 2;
   }
-  tg_asf_args F;
+  tg_asm_args A;           // k_assemble_mapped
+  tg_asf_args F;           // the sum-factorised kernels
+  tg_point_args_init(D, &A);
   memset(&F, 0, sizeof(F));
-  if (fast) {
-    for (int k = 0; k < 3; k++) {
-      F.nel[k] = A.nel[k];
-      F.n[k] = A.n[k];
+  if (P.route) {
+    for (int k = 0; k < 3; k++) F.nel[k] = D.nel[k], F.n[k] = D.n[k];
+    for (int c = 0; c < 4 && !rq.coef; c++) F.cp[c] = pt->cp[c]->d;
+    F.cp_node0 = rq.cp_node0;
+    F.tab = g_asm_cache.tab;
+    F.val = form == 2 ? rq.bout->d : m->val;
+    if (form == 2) F.fnod = rq.fnod->d;
+    F.row0 = P.row0;
+    F.za = P.za;
+    F.zb = P.zb;
+    F.base = P.base;
+    F.chunk = P.chunk;
+    F.nchunks = P.nchunks;
+    if (form == 3) F.ei = rq.eb.i, F.ej = rq.eb.j, F.lam = rq.eb.lam, F.mu = rq.eb.mu;
+    if (rq.coef) {
+      F.coef = rq.coef->d;
+      F.npts = rq.coef->n / TG_ASF_NCOEF;
     }
-    for (int c = 0; c < 4; c++) F.cp[c] = A.cp[c];
-    F.fnod = A.fnod;
-    F.cp_node0 = cp_node0;
-    F.tab = A.tab;
-    F.val = form == 2 ? A.bout : m->val;
-    F.row0 = row0;
-    F.za = za;
-    F.zb = zb;
-    const int64_t T0 = (int64_t)p1 * A.n[0] + (int64_t)p * (A.nel[0] - 1), T1 = (int64_t)p1 * A.n[1] + (int64_t)p * (A.nel[1] - 1);
-    F.base = T0 * T1 * tg_rps_host(p, za);
-    // pieces of a line of elements: long enough that the element a piece starts early with (it only feeds the carry)
-    // costs little, short enough that a launch has waves for every SIMD
-    int chunk = getenv("TIGAR_ASM_CHUNK") ? atoi(getenv("TIGAR_ASM_CHUNK")) : 16;
-    if (chunk < 1) chunk = 1;
-    F.chunk = chunk;
-    F.nchunks = (A.nel[0] + chunk - 1) / chunk;
-    F.ei = A.ei;
-    F.ej = A.ej;
-    F.lam = A.lam;
-    F.mu = A.mu;
-    if (coef) {
-      F.coef = coef->d;
-      F.npts = coef->n / TG_ASF_NCOEF;
-    }
-  }
-  const int nt = (form == 2) ? 128 : 256;
-  bool bad = false;
-  const bool timeit = getenv("TIGAR_ASM_TIME") != nullptr;
-  if (timeit) hipEventRecord(g_tg.ev0[0], g_tg.stream);
-  const int epw = p == 3 ? 1 : (p == 2 ? 2 : 8);
-  // one launch per colour (parity of the element index per direction), colours in ascending order; the walks of the
-  // sum-factorised matrix kernel need no colouring in direction 0
-  // the walk along direction 0 for every matrix form but the p = 3 stiffness matrix (see k_asf3_elem); TIGAR_ASM_WALK=0/1 forces
-  bool walk = fast && form != 2 && !(p == 3 && (form == 1 || form == 3)) && p != 1;
-  if (fast && form != 2 && !rat && !coef && getenv("TIGAR_ASM_WALK")) walk = atoi(getenv("TIGAR_ASM_WALK")) != 0;
-  // p = 3 stiffness / elasticity: the four waves of a workgroup on four consecutive elements of a line (k_asf3_quad;
-  // TIGAR_ASM_QUAD=0: independent elements); direction 0 of a colour then counts GROUPS
-  bool line = fast && !walk && p == 3 && (form == 1 || form == 3);
-  if (line && !rat && !coef && getenv("TIGAR_ASM_QUAD")) line = atoi(getenv("TIGAR_ASM_QUAD")) != 0;
-  if (line) {           // pieces of `chunk` groups of four elements (a function of nothing but the environment: the seams
-                        // fix the order of the sums, and row blocks must reproduce the whole matrix bit for bit)
-    int chunk = getenv("TIGAR_ASM_QUAD_CHUNK") ? atoi(getenv("TIGAR_ASM_QUAD_CHUNK")) : 8;
-    if (chunk < 1) chunk = 1;
-    const int nq = (A.nel[0] + TG_ASF_NW - 1) / TG_ASF_NW;
-    F.chunk = chunk;
-    F.nchunks = (nq + chunk - 1) / chunk;
-  }
-  for (int c = 0; c < (1 << d) && !bad && zb > za; c++) {
-    if (walk && (c & 1)) continue;
-    int64_t nblk = 1;
-    for (int k = 0; k < 3; k++) {
-      const int par = k < d ? (c >> k) & 1 : 0;
-      int lo = 0, hi = A.nel[k];
-      if (k == d - 1) {
-        lo = ez0;
-        hi = ez1;
-      }
-      if (line && k == 0) hi = F.nchunks;
-      const int first = lo + (((par - lo) % 2) + 2) % 2;       // first index >= lo with this parity
-      A.efirst[k] = F.efirst[k] = k < d ? first : 0;
-      A.ncol[k] = F.ncol[k] = k < d ? (hi > first ? (hi - first + 1) / 2 : 0) : 1;
-      if (!(walk && k == 0)) nblk *= A.ncol[k];
-    }
-    if (nblk == 0) continue;
-    if (fast) {
-      if (walk) {
-        F.ngy = (F.ncol[1] + epw - 1) / epw;
-        F.ngroups = (int64_t)F.nchunks * F.ngy * F.ncol[2];
-      } else {
-        F.ngy = (F.ncol[0] + epw - 1) / epw;
-        F.ngroups = (int64_t)F.ngy * F.ncol[1] * F.ncol[2];
-      }
-      const unsigned nb = line ? (unsigned)F.ngroups : (unsigned)((F.ngroups + TG_ASF_NW - 1) / TG_ASF_NW);   // (quad: a workgroup per group)
-      if (coef && p == 3)
-        tg_asf_launch_coef<4, 1>(F, nb);
-      else if (coef)
-        tg_asf_launch_coef<3, 2>(F, nb);
-      else if (rat && p == 3)
-        tg_asf_launch_rat<4, 1>(form, F, nb);
-      else if (rat)
-        tg_asf_launch_rat<3, 2>(form, F, nb);
-      else if (p == 3)
-        tg_asf_launch<4, 1>(form, F, nb, walk, line);
-      else if (p == 2)
-        tg_asf_launch<3, 2>(form, F, nb, walk, false);
-      else
-        tg_asf_launch<2, 8>(form, F, nb, walk, false);
+  } else {
+    A.form = form;
+    A.rat = rq.rat ? 1 : 0;
+    if (form == 3) A.ei = rq.eb.i, A.ej = rq.eb.j, A.lam = rq.eb.lam, A.mu = rq.eb.mu;
+    for (int k = 0; k < d; k++) A.verts[k] = g_asm_cache.verts[k];
+    for (int c = 0; c <= D.nsd; c++) A.cp[c] = pt->cp[c]->d;
+    A.tab = g_asm_cache.tab;
+    A.cp_node0 = rq.cp_node0;
+    A.row0 = P.row0;
+    A.row1 = P.row1;
+    if (form == 2) {
+      A.fnod = rq.fnod->d;
+      A.bout = rq.bout->d;
     } else {
-      TG_REQUIRE(nblk < (1ll << 31), "too many elements for one launch");
-      hipLaunchKernelGGL(k_assemble_mapped, dim3((unsigned)nblk), dim3(nt), lds, g_tg.stream, A);
+      A.rowptr = m->rowptr;
+      A.val = m->val;
     }
-    bad = hipGetLastError() != hipSuccess;
   }
-  if (timeit && rat && fast && (getenv("TIGAR_ASM_WALK") || getenv("TIGAR_ASM_QUAD") || getenv("TIGAR_ASM_PRE")))
+  const int family = P.route ? P.route->key.family : -1;
+  const bool walk = family == TG_ASF_FAM_WALK, quad = family == TG_ASF_FAM_QUAD;
+  const int epw = p == 3 ? 1 : (p == 2 ? 2 : 8);
+  int lo[3] = {0, 0, 0}, hi[3] = {D.nel[0], D.nel[1], D.nel[2]};
+  lo[d - 1] = P.ez0;
+  hi[d - 1] = P.ez1;
+  if (quad) hi[0] = P.nchunks;
+  if (P.S.time) hipEventRecord(g_tg.ev0[0], g_tg.stream);
+  bool bad = false;
+  const int rc = tg_for_colours(d, lo, hi, walk ? 1u : 0u, [&](const int *efirst, const int *ncol, int64_t count) {
+    if (P.route) {
+      for (int k = 0; k < 3; k++) F.efirst[k] = efirst[k], F.ncol[k] = ncol[k];
+      F.ngy = (ncol[walk ? 1 : 0] + epw - 1) / epw;
+      F.ngroups = walk ? (int64_t)F.nchunks * F.ngy * ncol[2] : (int64_t)F.ngy * ncol[1] * ncol[2];
+      const int64_t nb = quad ? F.ngroups : (F.ngroups + TG_ASF_NW - 1) / TG_ASF_NW;    // (quad: a workgroup per group)
+      hipLaunchKernelGGL(P.route->kernel, dim3((unsigned)nb), dim3(64 * TG_ASF_NW), 0, g_tg.stream, F);
+    } else {
+      TG_REQUIRE(count < (1ll << 31), "%s: too many elements for one launch", rq.who);
+      for (int k = 0; k < 3; k++) A.efirst[k] = efirst[k], A.ncol[k] = ncol[k];
+      hipLaunchKernelGGL(k_assemble_mapped, dim3((unsigned)count), dim3(form == 2 ? 128 : 256), P.lds, g_tg.stream, A);
+    }
+    return (bad = hipGetLastError() != hipSuccess) ? 1 : 0;
+  });
+  if (rc && !bad) return rc;
+  if (P.S.time && rq.rat && P.route && P.S.forced)
     fprintf(stderr, "[tg_assemble] rational forms keep their default route: TIGAR_ASM_WALK / _QUAD / _PRE are not applied\n");
-  if (timeit) {
+  if (P.S.time) {
     hipEventRecord(g_tg.ev1[0], g_tg.stream);
     hipEventSynchronize(g_tg.ev1[0]);
     float ms = 0.f;
     hipEventElapsedTime(&ms, g_tg.ev0[0], g_tg.ev1[0]);
-    fprintf(stderr, "[tg_assemble] form %d%s rows [%lld, %lld): element kernels %.3f ms (%s)\n", form,
-            coef ? " with point coefficients" : (rat ? " rational" : ""),
-            (long long)row0, (long long)row1, ms, fast ? "sum-factorised" : "plain");
+    fprintf(stderr, "[tg_assemble] form %d%s rows [%lld, %lld): element kernels %.3f ms (%s) %s\n", form,
+            rq.coef ? " with point coefficients" : (rq.rat ? " rational" : ""), (long long)P.row0, (long long)P.row1, ms,
+            P.route ? "sum-factorised" : "plain", P.route ? P.route->name : "k_assemble_mapped");
   }
   if (bad) {
-    if (m) tg_csr_destroy(m);
-    tg_set_error("the assembly kernel failed to launch");
+    tg_set_error("%s: the assembly kernel failed to launch", rq.who);
     return 1;
+  }
+  return 0;
+}
+
+static int tg_assemble_common(const tg_patch_t *pt, const tg_asm_request &rq, tg_csr_t *mout, bool *coef_taken = nullptr) {
+  tg_asm_plan P;
+  TG_TRY(tg_asm_plan_make(pt, rq, &P));
+  TG_TRY(tg_asm_cache_get(pt));
+  if (rq.coef) {
+    *coef_taken = P.route != nullptr;
+    if (!P.route) return 0;
+  }
+  tg_csr_t m = nullptr;
+  TG_TRY(tg_asm_output(rq, P, &m));
+  const int rc = tg_asm_launch(pt, rq, P, m);
+  if (rc) {                // (no refusal and no failure after the pattern exists leaves it behind)
+    if (m) tg_csr_destroy(m);
+    return rc;
   }
   if (mout) *mout = m;
   return 0;
@@ -1820,29 +1838,28 @@ extern "C" int tg_assemble_limits(int *max_local_nodes, int *max_gauss_points) {
 
 extern "C" int tg_assemble_mapped_matrix(const tg_patch_t *patch, int form, tg_csr_t *out) {
   TG_REQUIRE(out && (form == 0 || form == 1 || form == 4), "form: 0 = mass, 1 = laplace, 4 = biharmonic");
-  return tg_assemble_common(patch, form, -1, -1, 0, out, nullptr, nullptr);
+  return tg_assemble_common(patch, {__func__, form}, out);
 }
 
 extern "C" int tg_assemble_mapped_load(const tg_patch_t *patch, tg_vec_t fnodal, tg_vec_t out) {
-  return tg_assemble_common(patch, 2, -1, -1, 0, nullptr, fnodal, out);
+  return tg_assemble_common(patch, {__func__, 2, -1, -1, 0, false, {}, fnodal, out}, nullptr);
 }
 
 extern "C" int tg_assemble_mapped_matrix_rows(const tg_patch_t *patch, int form, int64_t row0, int64_t row1, int64_t cp_node0,
                                               tg_csr_t *out) {
   TG_REQUIRE(out && (form == 0 || form == 1 || form == 4), "form: 0 = mass, 1 = laplace, 4 = biharmonic");
-  return tg_assemble_common(patch, form, row0, row1, cp_node0, out, nullptr, nullptr);
+  return tg_assemble_common(patch, {__func__, form, row0, row1, cp_node0}, out);
 }
 
 extern "C" int tg_assemble_mapped_elasticity_rows(const tg_patch_t *patch, int fi, int fj, double lambda, double mu, int64_t row0,
                                                   int64_t row1, int64_t cp_node0, tg_csr_t *out) {
   TG_REQUIRE(out, "null output");
-  const tg_elast_block eb = {fi, fj, lambda, mu};
-  return tg_assemble_common(patch, 3, row0, row1, cp_node0, out, nullptr, nullptr, &eb);
+  return tg_assemble_common(patch, {__func__, 3, row0, row1, cp_node0, false, {fi, fj, lambda, mu}}, out);
 }
 
 extern "C" int tg_assemble_mapped_load_rows(const tg_patch_t *patch, tg_vec_t fnodal, int64_t row0, int64_t row1,
                                             int64_t cp_node0, tg_vec_t out) {
-  return tg_assemble_common(patch, 2, row0, row1, cp_node0, nullptr, fnodal, out);
+  return tg_assemble_common(patch, {__func__, 2, row0, row1, cp_node0, false, {}, fnodal, out}, nullptr);
 }
 
 // ---- the point-coefficient form (tg_coef.hip) on the sum-factorised route: 3-D, nsd = 3, nq = p + 1, p = 2, 3, unless
@@ -1850,24 +1867,23 @@ extern "C" int tg_assemble_mapped_load_rows(const tg_patch_t *patch, tg_vec_t fn
 int tg_asm_coef_fast(const tg_patch_t *pt, tg_vec_t coef, tg_csr_t *out, bool *taken) {
   *taken = false;
   if (pt->d != 3 || coef->n % TG_ASF_NCOEF) return 0;
-  return tg_assemble_common(pt, 1, -1, -1, 0, out, nullptr, nullptr, nullptr, false, coef, taken);
+  return tg_assemble_common(pt, {"tg_assemble_coef_matrix", 1, -1, -1, 0, false, {}, nullptr, nullptr, coef}, out, taken);
 }
 
 // ---- rational trial and test functions phi / W_h: the same host driver with the flag
 extern "C" int tg_assemble_rational_matrix_rows(const tg_patch_t *patch, int form, int64_t row0, int64_t row1, int64_t cp_node0,
                                                 tg_csr_t *out) {
   TG_REQUIRE(out && (form == 0 || form == 1), "form: 0 = mass, 1 = laplace");
-  return tg_assemble_common(patch, form, row0, row1, cp_node0, out, nullptr, nullptr, nullptr, true);
+  return tg_assemble_common(patch, {__func__, form, row0, row1, cp_node0, true}, out);
 }
 
 extern "C" int tg_assemble_rational_elasticity_rows(const tg_patch_t *patch, int fi, int fj, double lambda, double mu, int64_t row0,
                                                     int64_t row1, int64_t cp_node0, tg_csr_t *out) {
   TG_REQUIRE(out, "null output");
-  const tg_elast_block eb = {fi, fj, lambda, mu};
-  return tg_assemble_common(patch, 3, row0, row1, cp_node0, out, nullptr, nullptr, &eb, true);
+  return tg_assemble_common(patch, {__func__, 3, row0, row1, cp_node0, true, {fi, fj, lambda, mu}}, out);
 }
 
 extern "C" int tg_assemble_rational_load_rows(const tg_patch_t *patch, tg_vec_t fnodal, int64_t row0, int64_t row1,
                                               int64_t cp_node0, tg_vec_t out) {
-  return tg_assemble_common(patch, 2, row0, row1, cp_node0, nullptr, fnodal, out, nullptr, true);
+  return tg_assemble_common(patch, {__func__, 2, row0, row1, cp_node0, true, {}, fnodal, out}, nullptr);
 }

@@ -1,5 +1,5 @@
 // What the point kernels on mapped patches share (tg_postproc.hip: the volume; tg_boundary.hip: the faces; tg_coef.hip: the
-// plain point-coefficient matrix): ONE check of the patch description, the LDS fit, the loop over the colours, the zeroed
+// plain point-coefficient matrix; tg_assemble.hip: the host driver of the mapped forms, host side only): ONE check of the patch description, the LDS fit, the loop over the colours, the zeroed
 // nodal output; on the device which nodal fields are present and where, and the inverse of a point's metric.  All static
 // inline or templates: a host build has tg_postproc.hip and tg_coef.hip in one translation unit (tools/host_shim).
 // NOT shared: the contractions through LDS to the points and back (slot layouts, merged slots and channels differ), and the
@@ -53,7 +53,7 @@ static inline int tg_patch_check(const char *who, const tg_patch_t *pt, int dmin
   return 0;
 }
 
-// zeroes the arguments of k_postproc / k_boundary and fills what both have from the patch
+// zeroes the arguments of k_postproc / k_boundary / k_assemble_mapped and fills what all have from the patch
 template <class Args>
 static inline void tg_point_args_init(const tg_patch_dims &D, Args *A) {
   memset(A, 0, sizeof(*A));
@@ -78,22 +78,33 @@ static inline void tg_point_lds_fit(int p1, int nq, int szA, int szB, int epg_st
   *bytes = need(*epg);
 }
 
-// one launch per colour: the elements efirst[k] + 2 i, i < ncol[k], of the parities of the element indices in the first ndir
-// directions (0 and 1 beyond), colours in ascending order, empty ones skipped.  launch(efirst, ncol, count) returns 0 to go on
+// one launch per colour: the elements efirst[k] + 2 i, i < ncol[k], of [lo[k], hi[k]) with the parities of the element
+// indices in the first ndir directions (0 and 1 beyond), colours in ascending order, empty ones skipped.  A direction whose
+// bit is set in `uncoloured` is one colour: efirst = lo, ncol as for parity 0 but not a factor of count (the launch walks along
+// it, or counts it its own way).  launch(efirst, ncol, count) returns 0 to go on
 template <class F>
-static inline int tg_for_colours(int ndir, const int *nel, F &&launch) {
+static inline int tg_for_colours(int ndir, const int *lo, const int *hi, unsigned uncoloured, F &&launch) {
   for (int c = 0; c < (1 << ndir); c++) {
+    if (c & uncoloured) continue;
     int efirst[3] = {0, 0, 0}, ncol[3] = {1, 1, 1};
     int64_t count = 1;
     for (int k = 0; k < ndir; k++) {
-      efirst[k] = (c >> k) & 1;
-      ncol[k] = nel[k] > efirst[k] ? (nel[k] - efirst[k] + 1) / 2 : 0;
-      count *= ncol[k];
+      const bool coloured = !((uncoloured >> k) & 1);
+      efirst[k] = coloured ? lo[k] + ((lo[k] ^ (c >> k)) & 1) : lo[k];       // the first index >= lo of this parity
+      ncol[k] = hi[k] > efirst[k] ? (hi[k] - efirst[k] + 1) / 2 : 0;
+      if (coloured) count *= ncol[k];
     }
     if (count == 0) continue;
     TG_TRY(launch(efirst, ncol, count));
   }
   return 0;
+}
+
+// ... every element of every direction, all directions coloured
+template <class F>
+static inline int tg_for_colours(int ndir, const int *nel, F &&launch) {
+  const int lo[3] = {0, 0, 0};
+  return tg_for_colours(ndir, lo, nel, 0u, launch);
 }
 
 // an output on the FE nodes, zeroed: the colours add into it
