@@ -696,6 +696,41 @@ int tg_material_points(int kind, const double *params, int nsd, int64_t npts, tg
  * _rational: tested against phi / W_h.  Sum-factorised both ways, added colour by colour as tg_quad_load. */
 int tg_quad_load_flux(const tg_patch_t *patch, tg_vec_t s_q, tg_vec_t F_q, tg_vec_t out);
 int tg_quad_load_flux_rational(const tg_patch_t *patch, tg_vec_t s_q, tg_vec_t F_q, tg_vec_t out);
+/* ---- second-derivative point forms (csrc/tg_jet.hip): d = 1, 2, nsd >= d, the scalar Q_p space; nF >= 1 fields share it,
+ * dofs field after field.  The JET of a function at a point: value | first | second derivatives (order 00, 01, 11) with
+ * respect to the patch's parametric (knot) coordinates xi -- spline.parametricGrad of the reference --, nJ = 3 (d = 1) or 6
+ * (d = 2) components; component alpha of field i at (i nJ + alpha) npts + q, points numbered as tg_quad_points.
+ * With S = diag(1, 1/h_k, 1/(h_k h_m)) (h: the element's sizes) and L the lower-triangular matrix of the quotient rule
+ * jet(phi / W_h) = L jet(phi) (identity without `rational`), Q = S L_ref:  jet_xi(u) = Q jet_ref(u_h).
+ * tg_quad_jet: nJ npts values of u_h (rational: u_h / W_h).  tg_quad_geometry_jet: nsd nJ npts values of x = N / W,
+ *   component c at (c nJ + alpha) npts + q.
+ * tg_jet_transform: nblk blocks of nJ x nJ point matrices T (row alpha: test, column beta: trial) at
+ *   (b nJ^2 + alpha nJ + beta) npts + q  ->  T' = wdet Q^T T Q in the same layout (wdet: the weight of tg_quad_points); the
+ *   point's geometry, W-jet and Q are formed once for all blocks.  tg_jet_load_transform: s' = wdet Q^T s for nF fields.
+ *   Input and output must be different vectors.
+ * tg_assemble_jet_blocks: block (i, j), A_e[a][b] = sum_q sum_{alpha beta} J^alpha_ref phi_a T'^{alpha beta}_{ij,q} J^beta_ref phi_b,
+ *   each on the element-coupling pattern with its certificate, put together by tg_csr_from_blocks (nF = 1: the block
+ *   itself); any nF >= 1.  `coef`: nF^2 consecutive sets of tg_jet_transform.  The control functions of the patch are not read.
+ * tg_quad_load_jet: out[i n + a] = sum_q sum_alpha s'^alpha_{i,q} J^alpha_ref phi_a, an output of nF n values, zeroed here.
+ * The matrix and the load add colour by colour without floating-point atomics: the same inputs give the same bits. */
+int tg_quad_jet(const tg_patch_t *patch, tg_vec_t u_nodal, int rational, tg_vec_t jet_out);
+int tg_quad_geometry_jet(const tg_patch_t *patch, tg_vec_t jet_out);
+int tg_jet_transform(const tg_patch_t *patch, int rational, int nblk, tg_vec_t T_q, tg_vec_t coef_out);
+int tg_jet_load_transform(const tg_patch_t *patch, int rational, int nF, tg_vec_t s_q, tg_vec_t out);
+int tg_assemble_jet_blocks(const tg_patch_t *patch, int nF, tg_vec_t coef, tg_csr_t *out);
+int tg_quad_load_jet(const tg_patch_t *patch, int nF, tg_vec_t s_t, tg_vec_t out);
+/* ---- Kirchhoff-Love shell laws at the points (csrc/tg_shell.hip): d = 2, nsd = nF = 3.  Xjet: the jets of the reference
+ * surface (tg_quad_geometry_jet), ujet: those of the three displacement fields (tg_quad_jet per field, one after the other),
+ * 18 npts values each, component alpha of coordinate / field c at (6 c + alpha) npts + q; x = X + u.
+ * kind 0, params = {E, nu, thickness} (host): psi = h/2 eps:C:eps + h^3/24 kappa:C:kappa per unit reference area, with
+ * eps_ab = (a_ab - A_ab)/2, kappa_ab = B_ab - b_ab, C^abcd = E/(1 - nu^2) [nu A^ab A^cd + (1 - nu)/2 (A^ac A^bd + A^ad A^bc)].
+ * psi_out: npts values; s_out = d psi / d jet(u): 18 npts values in the layout tg_jet_load_transform reads (value slots 0);
+ * T_out = d^2 psi / d jet(u)^2: 324 npts values, T_ij^{alpha beta} at ((3 i + j) 36 + 6 alpha + beta) npts + q, the layout
+ * tg_jet_transform reads with nblk = 9.  Any output may be null; the same subsets give the same bits.
+ * A point with |X_,1 x X_,2| or |x_,1 x x_,2| below 1e-14 |X_,1| |X_,2| writes nothing; *nbad counts those points (integer
+ * atomics only).  Synchronises the stream. */
+int tg_shell_points(int kind, const double *params, int64_t npts, tg_vec_t Xjet, tg_vec_t ujet, tg_vec_t s_out, tg_vec_t T_out,
+                    tg_vec_t psi_out, int64_t *nbad);
 
 /* ---- boundary integrals on the same patches (csrc/tg_boundary.hip): the boundary measure and the mapped normal of the
  * reference's ExtractedSpline (spline.ds, spline.n; tIGAr/common.py:931-939, calculusUtils.py:37-52, 71-80).  d = 2, 3,

@@ -240,6 +240,13 @@ PROTOTYPES = {
     "tg_material_points": (C.c_int, [C.c_int, c_f64p, C.c_int, C.c_int64, handle, handle, handle, handle, c_i64p, c_f64p]),
     "tg_quad_load_flux": (C.c_int, [C.POINTER(tg_patch_t), handle, handle, handle]),
     "tg_quad_load_flux_rational": (C.c_int, [C.POINTER(tg_patch_t), handle, handle, handle]),
+    "tg_quad_jet": (C.c_int, [C.POINTER(tg_patch_t), handle, C.c_int, handle]),
+    "tg_quad_geometry_jet": (C.c_int, [C.POINTER(tg_patch_t), handle]),
+    "tg_jet_transform": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle]),
+    "tg_jet_load_transform": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle]),
+    "tg_assemble_jet_blocks": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, handle, C.POINTER(handle)]),
+    "tg_quad_load_jet": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, handle, handle]),
+    "tg_shell_points": (C.c_int, [C.c_int, c_f64p, C.c_int64, handle, handle, handle, handle, handle, c_i64p]),
     "tg_face_points": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, handle]),
     "tg_face_eval": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, handle]),
     "tg_face_load": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle]),

@@ -2070,6 +2070,68 @@ class ExtractedSpline(object):
             raise NotImplementedError("%s: nFields = %d on a patch with nsd = %d; the displacement has as many fields as "
                                       "there are physical directions" % (who, self.nFields, self.nsd))
 
+    def _jet_scope(self, who):
+        """Refuses what the second-derivative point forms (csrc/tg_jet.hip) do not cover.  They serve one mapped
+        tensor-product patch on one rank, the continuous Q_p node grid, nF >= 1 fields sharing that grid with dofs numbered
+        field after field, d = 1 or 2 parametric directions and nsd >= d, B-spline or NURBS control mesh."""
+        if self._distributed():
+            raise NotImplementedError("%s: several ranks are not supported (the point values are numbered over the whole "
+                                      "patch)" % who)
+        if self._implicit():
+            raise NotImplementedError("%s: the streamed engine asks its forms for row blocks, which the second-derivative "
+                                      "point forms do not hand out" % who)
+        if self._caller_ordered():
+            raise NotImplementedError("%s: a spline with the caller's FE dof order (feOrder) is not supported; the point "
+                                      "kernels number the node grid" % who)
+        gen = getattr(self, "_generator", None)
+        if isinstance(gen, FieldListSpline):
+            raise NotImplementedError("%s: FieldListSpline spaces (fields on their own bases) are not supported" % who)
+        on_control = getattr(gen, "_fields_on_control_basis", None)
+        if on_control is not None and not on_control():
+            raise NotImplementedError("%s: the fields of %s are not discretised with the control mesh's scalar basis "
+                                      "(FieldListSpline and compatible spaces are not supported)" % (who, type(gen).__name__))
+        grids = getattr(self.V, "grids", None)
+        if grids is None or len(grids) != self.nFields or any(not isinstance(g, TensorNodeGrid) or g.dg for g in grids):
+            raise NotImplementedError("%s: the FE fields are not continuous Q_p fields of a single tensor-product patch "
+                                      "(FieldListSpline, compatible, multi-patch, T-spline and DG spaces are not supported)" % who)
+        g = grids[0]
+        if any(gi.degree != g.degree or gi.shape() != g.shape() for gi in grids[1:]):
+            raise NotImplementedError("%s: the fields do not share one node grid (compatible spaces are not supported)" % who)
+        if g.dim() not in (1, 2):
+            raise NotImplementedError("%s: d = %d parametric directions; second-derivative point forms are provided for "
+                                      "curves and surfaces (d = 1, 2)" % (who, g.dim()))
+
+    def evaluateJetsAtQuadrature(self, u, nq=None, rational=False):
+        """The JET of u_h (``rational``: of u_h / W_h) at the quadrature points: value, first parametric derivatives, second
+        parametric derivatives in the order 00, 01, 11 -- ``spline.parametricGrad`` of the reference and its derivative, with
+        respect to the patch's knot coordinates.  A DeviceVector of nJ * npts values (nJ = 3 for d = 1, 6 for d = 2),
+        component alpha at alpha * npts + q, points numbered as ``quadraturePoints``; for nFields > 1 a list with one per
+        field (``tg_quad_jet``)."""
+        from . import forms
+        who = "evaluateJetsAtQuadrature"
+        self._jet_scope(who)
+        pts = forms.quadrature_points(self, self.V_control, nq, who)
+        uv = _as_device_vector(u)
+        n = self.V.grids[0].num_nodes()
+        if uv.size() != self.nFields * n:
+            raise ValueError("%s: %d nodal values given, the space has %d" % (who, uv.size(), self.nFields * n))
+        if self.nFields == 1:
+            return _dev.quad_jet(pts.verts, pts.p, pts.cp, uv, nq=pts.nq, rational=rational)
+        out, ui = [], DeviceVector(n, zero=False)
+        for i in range(self.nFields):
+            _dev.vec_copy_range(ui, 0, uv, i * n, n)
+            out.append(_dev.quad_jet(pts.verts, pts.p, pts.cp, ui, nq=pts.nq, rational=rational))
+        return out
+
+    def geometryJetsAtQuadrature(self, nq=None):
+        """The jets of the physical coordinates x_c = N_c / W_h at the quadrature points: a DeviceVector of nsd * nJ * npts
+        values, component alpha of coordinate c at (c nJ + alpha) npts + q (``tg_quad_geometry_jet``)."""
+        from . import forms
+        who = "geometryJetsAtQuadrature"
+        self._jet_scope(who)
+        pts = forms.quadrature_points(self, self.V_control, nq, who)
+        return _dev.quad_geometry_jet(pts.verts, pts.p, pts.cp, nq=pts.nq)
+
     def quadraturePoints(self, nq=None):
         """The Gauss points of the patch (``nq`` per direction, p + 1 when None) as a ``forms.QuadraturePoints``: ``.x``
         (host array [npts, nsd], downloaded on first use), ``.x_device``, ``.weights`` (DeviceVector of w_q sqrt(det g)

@@ -1287,6 +1287,86 @@ def coef_block(vertices, coef_blocks, i, j, nq):
     return out
 
 
+def jet_size(d):
+    """nJ: components of a jet (value | first | second parametric derivatives 00, 01, 11) on a patch of d = 1, 2 directions"""
+    if d not in (1, 2):
+        raise NotImplementedError("second-derivative point forms: d = %d; curves and surfaces (d = 1, 2) are provided" % d)
+    return 3 if d == 1 else 6
+
+
+def quad_jet(vertices, p, cp, u, nq=None, rational=False):
+    """The jet of u_h (``rational``: of u_h / W_h) at the Gauss points with respect to the patch's parametric coordinates
+    (``tg_quad_jet``): nJ * npts values, component alpha at alpha * npts + q."""
+    nq = p + 1 if nq is None else nq
+    pt, keep = _patch(vertices, p, cp, nq)
+    out = DeviceVector(jet_size(len(vertices)) * quad_count(vertices, nq), zero=False)
+    check(_lib.lib().tg_quad_jet(C.byref(pt), u._h, 1 if rational else 0, out._h), "tg_quad_jet")
+    return out
+
+
+def quad_geometry_jet(vertices, p, cp, nq=None):
+    """The jets of the physical coordinates x_c = N_c / W (``tg_quad_geometry_jet``): nsd * nJ * npts values, component
+    alpha of coordinate c at (c nJ + alpha) npts + q."""
+    nq = p + 1 if nq is None else nq
+    pt, keep = _patch(vertices, p, cp, nq)
+    out = DeviceVector((len(cp) - 1) * jet_size(len(vertices)) * quad_count(vertices, nq), zero=False)
+    check(_lib.lib().tg_quad_geometry_jet(C.byref(pt), out._h), "tg_quad_geometry_jet")
+    return out
+
+
+def jet_transform(vertices, p, cp, T, nblk, nq=None, rational=False):
+    """T' = wdet Q^T T Q for ``nblk`` blocks of nJ x nJ point matrices, T^{alpha beta} of block b at
+    (b nJ^2 + alpha nJ + beta) npts + q (``tg_jet_transform``); the result, in the same layout, is what
+    ``assemble_jet_blocks`` takes."""
+    nq = p + 1 if nq is None else nq
+    pt, keep = _patch(vertices, p, cp, nq)
+    nJ = jet_size(len(vertices))
+    out = DeviceVector(int(nblk) * nJ * nJ * quad_count(vertices, nq), zero=False)
+    check(_lib.lib().tg_jet_transform(C.byref(pt), 1 if rational else 0, int(nblk), T._h, out._h), "tg_jet_transform")
+    return out
+
+
+def jet_load_transform(vertices, p, cp, s, nF, nq=None, rational=False):
+    """s' = wdet Q^T s for ``nF`` fields, s^alpha of field i at (i nJ + alpha) npts + q (``tg_jet_load_transform``)"""
+    nq = p + 1 if nq is None else nq
+    pt, keep = _patch(vertices, p, cp, nq)
+    out = DeviceVector(int(nF) * jet_size(len(vertices)) * quad_count(vertices, nq), zero=False)
+    check(_lib.lib().tg_jet_load_transform(C.byref(pt), 1 if rational else 0, int(nF), s._h, out._h), "tg_jet_load_transform")
+    return out
+
+
+def assemble_jet_blocks(vertices, p, cp, coef, nF, nq=None):
+    """the nF n x nF n matrix (field-major) of the transformed jet blocks ``coef`` (``tg_assemble_jet_blocks``)"""
+    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
+    h = handle()
+    check(_lib.lib().tg_assemble_jet_blocks(C.byref(pt), int(nF), coef._h, C.byref(h)), "tg_assemble_jet_blocks")
+    return DeviceCSR(h)
+
+
+def quad_load_jet(vertices, p, cp, s_t, nF, nq=None):
+    """out[i n + a] = sum_q sum_alpha s'^alpha_{i,q} J^alpha_ref phi_a for the transformed ``s_t`` (``tg_quad_load_jet``)"""
+    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
+    out = DeviceVector(n=int(nF) * cp[0].size(), zero=False)          # (the entry zeroes it before the colours add)
+    check(_lib.lib().tg_quad_load_jet(C.byref(pt), int(nF), s_t._h, out._h), "tg_quad_load_jet")
+    return out
+
+
+def shell_points(kind, E, nu, thickness, Xjet, ujet, load=True, tangent=False, energy=False):
+    """The Kirchhoff-Love shell law ``kind`` (0: St. Venant-Kirchhoff) at the points (``tg_shell_points``): ``Xjet`` /
+    ``ujet`` hold the jets of the reference surface and of the three displacement fields, 18 * npts values each.  Returns
+    (s, T, psi, nbad) with the outputs not asked for None; s in the layout of ``jet_load_transform`` (nF = 3), T in that of
+    ``jet_transform`` (nblk = 9)."""
+    npts = Xjet.size() // 18
+    s = DeviceVector(18 * npts, zero=False) if load else None
+    T = DeviceVector(324 * npts, zero=False) if tangent else None
+    psi = DeviceVector(npts, zero=False) if energy else None
+    par = _f64([float(E), float(nu), float(thickness)])
+    nbad = C.c_int64(0)
+    check(_lib.lib().tg_shell_points(int(kind), _p(par, c_f64p), npts, Xjet._h, ujet._h, _h_or_none(s), _h_or_none(T),
+                                     _h_or_none(psi), C.byref(nbad)), "tg_shell_points")
+    return s, T, psi, int(nbad.value)
+
+
 MATERIAL_KINDS = {"linear": 0, "svk": 1, "neohookean": 2}
 
 

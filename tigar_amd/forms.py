@@ -1251,6 +1251,446 @@ class _HyperelasticTangent(object):
         return self._form(V).assemble_matrix(V)
 
 
+# ---- second-derivative point forms (csrc/tg_jet.hip): spline.parametricGrad of the reference and its derivative ------------
+def _jet_form_scope(geometry, V, who):
+    """(node grid, nF, nJ) of a space the second-derivative point forms serve: nF >= 1 fields on one continuous Q_p node
+    grid of a patch with d = 1, 2 and nsd >= d, dofs field after field; refuses everything else with the reason.  An
+    ExtractedSpline says itself what it covers (``_jet_scope``)."""
+    if geometry is None:
+        raise ValueError("%s: point data live on a mapped patch (geometry=...)" % who)
+    scope = getattr(geometry, "_jet_scope", None)
+    if scope is not None:
+        scope(who)
+    _fields_of_the_patch(geometry, who)
+    g = _shared_grid(V)
+    if g is None:
+        raise NotImplementedError("%s: the fields of the space must share one continuous Q_p node grid of a tensor-product "
+                                  "patch (compatible, FieldList, multi-patch, T-spline and DG spaces are not supported)" % who)
+    d, nsd = g.dim(), len(geometry.cpFuncs) - 1
+    if d not in (1, 2):
+        raise NotImplementedError("%s: d = %d parametric directions; second-derivative point forms are provided for curves "
+                                  "and surfaces (d = 1, 2)" % (who, d))
+    if nsd < d:
+        raise NotImplementedError("%s: nsd = %d physical directions on a patch of d = %d parametric ones" % (who, nsd, d))
+    return g, len(V.grids), _dev.jet_size(d)
+
+
+class VectorJetCoefficientForm(object):
+    """a(u, v) = sum_q wdet_q sum_ij (jet v_i)^T T_ij (jet u_j) on the mapped patch: point data acting on the JETS of trial and
+    test functions -- value, first and second derivatives (order 00, 01, 11) with respect to the patch's parametric
+    coordinates, ``spline.parametricGrad`` of the reference and its derivative.  nF >= 1 fields on one continuous Q_p node
+    grid, dofs field after field; d = 1, 2 and nsd >= d (a surface in space); nF need not equal d or nsd.  The tangent of a
+    Kirchhoff-Love shell; its (0, 0) entries alone are a mass term.
+
+    ``T``: ``[npts, nF, nJ, nF, nJ]`` point values T[q, i, alpha, j, beta] (row: test field i, column: trial field j;
+    numbered as ``QuadraturePoints``), a callable of the points ``x [npts, nsd]`` returning that, or a DeviceVector with
+    T_ij^{alpha beta} at ((i nF + j) nJ^2 + alpha nJ + beta) npts + q.  ``nq`` Gauss points per direction (p + 1 when None).
+    ``rational``: every component function phi / W_h.  ``symmetric`` is True only when the bits prove it:
+    T[i, alpha, j, beta] == T[j, beta, i, alpha] at every point.  One pass brings all nF^2 blocks to the reference element
+    (``tg_jet_transform``), each block is then assembled on the element-coupling pattern (``tg_assemble_jet_blocks``).
+    One rank, all rows."""
+    _who = "VectorJetCoefficientForm"
+
+    def __init__(self, geometry, T, nq=None, rational=False):
+        if geometry is None:
+            raise ValueError("%s: point data live on a mapped patch (geometry=...)" % self._who)
+        if T is None:
+            raise ValueError("%s: no point data" % self._who)
+        self.geometry, self.T, self.nq, self.rational = geometry, T, nq, bool(rational)
+        self._symmetric_hint = None          # (set by a caller whose law proves the symmetry: ShellResidual)
+
+    def _space(self):
+        return self.geometry.V
+
+    def _shape(self, v, nF, nJ):
+        """brings what the caller gave to [npts, nF, nJ, nF, nJ]"""
+        return v
+
+    def coefficients(self, V):
+        """(points, nF, T as a DeviceVector in the block layout, symmetric): computed once per set of points"""
+        g, nF, nJ = _jet_form_scope(self.geometry, V, self._who)
+        pts = _vector_points(self.geometry, self.nq, self._who)
+        return _per_points(self, "_static", pts, lambda: self._static_coefficients(pts, nF, nJ))
+
+    def _static_coefficients(self, pts, nF, nJ):
+        who, npts = self._who, pts.npts
+        if isinstance(self.T, _dev.DeviceVector):
+            T = self.T
+            if T.size() != nF * nF * nJ * nJ * npts:
+                raise ValueError("%s: %d values given, expected nF^2 nJ^2 npts = %d" % (who, T.size(), nF * nF * nJ * nJ * npts))
+            if self._symmetric_hint is not None:
+                return pts, nF, T, bool(self._symmetric_hint)
+            h = T.get_local().reshape(nF, nF, nJ, nJ, npts)
+            return pts, nF, T, _same_bits(h, h.transpose(1, 0, 3, 2, 4))
+        v = self._shape(numpy.asarray(self.T(pts.x) if callable(self.T) else self.T, dtype=numpy.float64), nF, nJ)
+        if v.shape == (nF, nJ, nF, nJ):
+            v = numpy.tile(v, (npts, 1, 1, 1, 1))
+        if v.shape != (npts, nF, nJ, nF, nJ):
+            raise ValueError("%s: an array of shape %s for %d points; expected (%d, %d, %d, %d, %d)"
+                             % (who, v.shape, npts, npts, nF, nJ, nF, nJ))
+        T = _dev.DeviceVector(data=numpy.ascontiguousarray(v.transpose(1, 3, 2, 4, 0)).ravel())
+        return pts, nF, T, _same_bits(v, v.transpose(0, 3, 4, 1, 2))
+
+    @property
+    def symmetric(self):
+        return self.coefficients(self._space())[3]
+
+    def assemble_block(self, V, i, j, row0=None, row1=None):
+        """block (i, j): test field i, trial field j (all rows of the field)"""
+        g, nF, nJ = _jet_form_scope(self.geometry, V, self._who)
+        if not (0 <= int(i) < nF and 0 <= int(j) < nF):
+            raise ValueError("%s: block (%r, %r) of a %d-field space" % (self._who, i, j, nF))
+        _whole_rows(g.num_nodes(), row0, row1, self._who, "patch")
+        pts, nF, T, _ = self.coefficients(V)
+        each = nJ * nJ * pts.npts
+        Tij = _dev.DeviceVector(each, zero=False)
+        _dev.vec_copy_range(Tij, 0, T, (int(i) * nF + int(j)) * each, each)
+        coef = _dev.jet_transform(pts.verts, pts.p, pts.cp, Tij, 1, nq=pts.nq, rational=self.rational)
+        return _dev.assemble_jet_blocks(pts.verts, pts.p, pts.cp, coef, 1, nq=pts.nq)
+
+    def assemble_matrix(self, V, row0=None, row1=None):
+        g, nF, nJ = _jet_form_scope(self.geometry, V, self._who)
+        _whole_rows(nF * g.num_nodes(), row0, row1, self._who, "patch")
+        pts, nF, T, _ = self.coefficients(V)
+        coef = _dev.jet_transform(pts.verts, pts.p, pts.cp, T, nF * nF, nq=pts.nq, rational=self.rational)
+        return _dev.assemble_jet_blocks(pts.verts, pts.p, pts.cp, coef, nF, nq=pts.nq)
+
+
+class JetCoefficientForm(VectorJetCoefficientForm):
+    """a(u, v) = sum_q wdet_q (jet v)^T T (jet u) for a scalar unknown: ``VectorJetCoefficientForm`` with nF = 1.  ``T``:
+    ``[npts, nJ, nJ]`` (row alpha: test, column beta: trial), a callable of the points returning that, or a DeviceVector
+    with T^{alpha beta} at (alpha nJ + beta) npts + q."""
+    _who = "JetCoefficientForm"
+
+    def _space(self):
+        return self.geometry.V_control
+
+    def _shape(self, v, nF, nJ):
+        if nF != 1:
+            raise NotImplementedError("JetCoefficientForm: nFields = %d; VectorJetCoefficientForm takes several fields" % nF)
+        if v.shape == (nJ, nJ):
+            return v.reshape(1, nJ, 1, nJ)
+        return v.reshape(v.shape[0], 1, nJ, 1, nJ) if v.ndim == 3 and v.shape[1:] == (nJ, nJ) else v
+
+
+class VectorJetLoadForm(object):
+    """L(v) = sum_q wdet_q sum_i s_i . jet v_i on the space of ``VectorJetCoefficientForm``: ``s`` ``[npts, nF, nJ]`` (value slot
+    first, then the first and second parametric derivatives), a callable of the points returning that, nF x nJ numbers, or a
+    DeviceVector with s_i^alpha at (i nJ + alpha) npts + q.  The component loads are written field after field
+    (``tg_jet_load_transform``, ``tg_quad_load_jet``).  ``rational``: v_i the functions phi / W_h."""
+    _who = "VectorJetLoadForm"
+
+    def __init__(self, s, geometry, nq=None, rational=False):
+        if geometry is None:
+            raise ValueError("%s: point values live on a mapped patch (geometry=...)" % self._who)
+        if s is None:
+            raise ValueError("%s: no point values" % self._who)
+        self.s, self.geometry, self.nq, self.rational = s, geometry, nq, bool(rational)
+
+    def _shape(self, v, nF, nJ):
+        return v
+
+    def point_values(self, pts, nF, nJ):
+        who, npts = self._who, pts.npts
+        if isinstance(self.s, _dev.DeviceVector):
+            if self.s.size() != nF * nJ * npts:
+                raise ValueError("%s: %d values given, expected nF nJ npts = %d" % (who, self.s.size(), nF * nJ * npts))
+            return self.s
+        v = self._shape(numpy.asarray(self.s(pts.x) if callable(self.s) else self.s, dtype=numpy.float64), nF, nJ)
+        if v.shape == (nF, nJ):
+            v = numpy.tile(v, (npts, 1, 1))
+        if v.shape != (npts, nF, nJ):
+            raise ValueError("%s: an array of shape %s for %d points; expected (%d, %d, %d)" % (who, v.shape, npts, npts, nF, nJ))
+        return _dev.DeviceVector(data=numpy.ascontiguousarray(v.transpose(1, 2, 0)).ravel())
+
+    def assemble_vector(self, V, row0=None, row1=None):
+        g, nF, nJ = _jet_form_scope(self.geometry, V, self._who)
+        _whole_rows(nF * g.num_nodes(), row0, row1, self._who, "patch")
+        pts = _vector_points(self.geometry, self.nq, self._who)
+        s = _per_points(self, "_static", pts, lambda: self.point_values(pts, nF, nJ))
+        st = _dev.jet_load_transform(pts.verts, pts.p, pts.cp, s, nF, nq=pts.nq, rational=self.rational)
+        return _dev.quad_load_jet(pts.verts, pts.p, pts.cp, st, nF, nq=pts.nq)
+
+
+class JetLoadForm(VectorJetLoadForm):
+    """L(v) = sum_q wdet_q s . jet v for a scalar space: ``s`` ``[npts, nJ]``, a callable returning that, nJ numbers, or a
+    DeviceVector with s^alpha at alpha npts + q."""
+    _who = "JetLoadForm"
+
+    def _shape(self, v, nF, nJ):
+        if nF != 1:
+            raise NotImplementedError("JetLoadForm: nFields = %d; VectorJetLoadForm takes several fields" % nF)
+        if v.shape == (nJ,):
+            return v.reshape(1, nJ)
+        return v.reshape(v.shape[0], 1, nJ) if v.ndim == 2 and v.shape[1] == nJ else v
+
+
+# ---- Kirchhoff-Love shells: the law on the host (demos/kl-shell-svk of the reference) ------------------------------------
+def _cross(a, b):
+    return numpy.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
+                        a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], axis=1)
+
+
+class KirchhoffLoveSVK(object):
+    """St. Venant-Kirchhoff Kirchhoff-Love shell of ``thickness`` h (demos/kl-shell-svk/dynamic-tspline.py:135-212 of the
+    reference), d = 2, nsd = nF = 3.  With the reference surface X(xi) and x = X + u:
+      A_ab = X_,a . X_,b,  A_3 = X_,1 x X_,2 / |.|,  B_ab = X_,ab . A_3;  a_ab, a_3, b_ab likewise from x;
+      eps_ab = (a_ab - A_ab)/2,  kappa_ab = B_ab - b_ab,
+      C^abcd = E/(1 - nu^2) [nu A^ab A^cd + (1 - nu)/2 (A^ac A^bd + A^ad A^bc)],
+      psi = h/2 eps:C:eps + h^3/24 kappa:C:kappa   per unit reference area.
+    ``host(Xjet, ujet)``: jets ``[npts, 3, 6]`` (value | ,0 ,1 | ,00 ,01 ,11) of any float dtype -> (psi [npts],
+    s = d psi / d jet(u) [npts, 3, 6] with the value slot zero, T = d^2 psi / d jet(u)^2 [npts, 3, 6, 3, 6]), from closed
+    forms: the first and second variations of a_3, and delta b_ab = (delta x_,ab - Gamma^c_ab delta x_,c) . a_3.
+    Degenerate points (|X_,1 x X_,2| or |x_,1 x x_,2| below 1e-14 |X_,1| |X_,2|) raise ``RuntimeError`` naming their number."""
+    kind = 0
+
+    def __init__(self, E, nu, thickness):
+        self.E, self.nu, self.thickness = float(E), float(nu), float(thickness)
+
+    @staticmethod
+    def degenerate(Xjet, ujet):
+        """mask of the points whose reference or current normal is not defined"""
+        X1, X2 = Xjet[:, :, 1], Xjet[:, :, 2]
+        x1, x2 = X1 + ujet[:, :, 1], X2 + ujet[:, :, 2]
+        nrm = lambda v: numpy.sqrt(numpy.einsum("qc,qc->q", v, v))
+        floor = 1e-14 * nrm(X1) * nrm(X2)
+        return ~((nrm(_cross(X1, X2)) >= floor) & (nrm(_cross(x1, x2)) >= floor))
+
+    def host(self, Xjet, ujet):
+        Xjet, ujet = numpy.asarray(Xjet), numpy.asarray(ujet)
+        dt = numpy.result_type(Xjet.dtype, ujet.dtype).type
+        Xjet, ujet = Xjet.astype(dt), ujet.astype(dt)
+        npts = Xjet.shape[0]
+        if Xjet.shape != (npts, 3, 6) or ujet.shape != (npts, 3, 6):
+            raise ValueError("KirchhoffLoveSVK: jets of shape [npts, 3, 6] (nsd = 3, d = 2); got %s and %s" % (Xjet.shape, ujet.shape))
+        bad = self.degenerate(Xjet, ujet)
+        if numpy.any(bad):
+            raise RuntimeError("KirchhoffLoveSVK: %d points with a degenerate surface normal" % int(numpy.sum(bad)))
+        E, nu, h = dt(self.E), dt(self.nu), dt(self.thickness)
+        half, one = dt(0.5), dt(1)
+        slot = {(0, 0): 3, (0, 1): 4, (1, 0): 4, (1, 1): 5}            # second-derivative slots of the jet
+        ein = numpy.einsum
+        dot = lambda a, b: ein("qc,qc->q", a, b)
+
+        def surface(jet):
+            g1, g2 = jet[:, :, 1], jet[:, :, 2]
+            n = _cross(g1, g2)
+            J = numpy.sqrt(dot(n, n))
+            n3 = n / J[:, None]
+            met = numpy.stack([numpy.stack([dot(g1, g1), dot(g1, g2)], 1), numpy.stack([dot(g1, g2), dot(g2, g2)], 1)], 1)
+            cur = numpy.empty_like(met)
+            for (a, b) in ((0, 0), (0, 1), (1, 0), (1, 1)):
+                cur[:, a, b] = dot(jet[:, :, slot[(a, b)]], n3)
+            return (g1, g2), n3, J, met, cur
+
+        _, _, _, Am, Bm = surface(Xjet)
+        xjet = Xjet + ujet
+        (g1, g2), a3, _, am, bm = surface(xjet)
+        g = (g1, g2)
+        # contravariant reference metric and the material tensor
+        detA = Am[:, 0, 0] * Am[:, 1, 1] - Am[:, 0, 1] * Am[:, 0, 1]
+        Ai = numpy.empty_like(Am)
+        Ai[:, 0, 0], Ai[:, 1, 1], Ai[:, 0, 1], Ai[:, 1, 0] = Am[:, 1, 1] / detA, Am[:, 0, 0] / detA, -Am[:, 0, 1] / detA, -Am[:, 0, 1] / detA
+        Cm = (E / (one - nu * nu)) * (nu * ein("qab,qcd->qabcd", Ai, Ai) +
+                                      half * (one - nu) * (ein("qac,qbd->qabcd", Ai, Ai) + ein("qad,qbc->qabcd", Ai, Ai)))
+        eps, kap = half * (am - Am), Bm - bm
+        nres = h * ein("qabcd,qcd->qab", Cm, eps)                     # membrane forces  n^ab
+        mres = (h * h * h / dt(12)) * ein("qabcd,qcd->qab", Cm, kap)  # bending moments  m^ab
+        psi = half * ein("qab,qab->q", nres, eps) + half * ein("qab,qab->q", mres, kap)
+        # current contravariant basis and Christoffel symbols Gamma^c_ab = x_,ab . a^c
+        deta = am[:, 0, 0] * am[:, 1, 1] - am[:, 0, 1] * am[:, 0, 1]
+        ai = numpy.empty_like(am)
+        ai[:, 0, 0], ai[:, 1, 1], ai[:, 0, 1], ai[:, 1, 0] = am[:, 1, 1] / deta, am[:, 0, 0] / deta, -am[:, 0, 1] / deta, -am[:, 0, 1] / deta
+        gup = [ai[:, c, 0, None] * g1 + ai[:, c, 1, None] * g2 for c in range(2)]       # a^c
+        # ---- first variation.  delta eps_ab = sym(delta x_,a . x_,b); delta kappa_ab = -(delta x_,ab - Gamma^c_ab delta x_,c) . a_3
+        s = numpy.zeros((npts, 3, 6), dtype=dt)
+        Gam = numpy.empty((npts, 2, 2, 2), dtype=dt)                   # [q, c, a, b]
+        for a in range(2):
+            for b in range(2):
+                xab = xjet[:, :, slot[(a, b)]]
+                for c in range(2):
+                    Gam[:, c, a, b] = dot(xab, gup[c])
+        for a in range(2):
+            for b in range(2):
+                s[:, :, 1 + a] += nres[:, a, b, None] * g[b]
+                s[:, :, slot[(a, b)]] -= mres[:, a, b, None] * a3
+                for c in range(2):
+                    s[:, :, 1 + c] += (mres[:, a, b] * Gam[:, c, a, b])[:, None] * a3
+        # ---- second variation.  psi = f(eps(jet), kappa(jet)):  T = De^T (h C) De + Dk^T (h^3/12 C) Dk + n : D2 eps + m : D2 kappa
+        # De[q, a, b, i, alpha], Dk[q, a, b, i, alpha]: derivatives of eps_ab, kappa_ab with respect to jet(u)_i^alpha
+        De = numpy.zeros((npts, 2, 2, 3, 6), dtype=dt)
+        Dk = numpy.zeros((npts, 2, 2, 3, 6), dtype=dt)
+        for a in range(2):
+            for b in range(2):
+                De[:, a, b, :, 1 + a] += half * g[b]
+                De[:, a, b, :, 1 + b] += half * g[a]
+                Dk[:, a, b, :, slot[(a, b)]] -= a3
+                for c in range(2):
+                    Dk[:, a, b, :, 1 + c] += Gam[:, c, a, b, None] * a3
+        T = h * ein("qabiA,qabcd,qcdjB->qiAjB", De, Cm, De) + (h * h * h / dt(12)) * ein("qabiA,qabcd,qcdjB->qiAjB", Dk, Cm, Dk)
+        I3 = numpy.eye(3, dtype=dt)
+        for a in range(2):
+            for b in range(2):                                         # n^ab delta x_,a . delta x_,b
+                T[:, :, 1 + a, :, 1 + b] += nres[:, a, b, None, None] * I3
+        # m^ab D2 kappa_ab = -m^ab (w_,ab . D a_3[v] + v_,ab . D a_3[w] + x_,ab . D2 a_3[w, v]) with the variations of the normal
+        #   D a_3[v] = -a^c (a_3 . v_,c),      D a^c[v] = -(a^c . v_,d) a^d + a^cd (a_3 . v_,d) a_3
+        for a in range(2):
+            for b in range(2):
+                sl = slot[(a, b)]
+                for c in range(2):                                     # -m^ab w_,ab . D a_3[v]: row (k, sl), column (i, 1 + c)
+                    blk = ein("q,qk,qi->qki", mres[:, a, b], gup[c], a3)
+                    T[:, :, sl, :, 1 + c] += blk
+                    T[:, :, 1 + c, :, sl] += blk.transpose(0, 2, 1)
+        # with M = m^ab x_,ab:  -M . D2 a_3[w, v] = (M . D a^c[v]) (a_3 . w_,c) + (M . a^c) (D a_3[v] . w_,c)
+        #   = -(M . a^d)(a_3 . w_,c)(a^c . v_,d) + a^cd (M . a_3)(a_3 . w_,c)(a_3 . v_,d) - (M . a^c)(a^d . w_,c)(a_3 . v_,d)
+        # row: w, field i, slot 1 + c; column: v, field j, slot 1 + d
+        Mv = sum(mres[:, a, b, None] * xjet[:, :, slot[(a, b)]] for a in range(2) for b in range(2))
+        M3 = dot(Mv, a3)
+        for c in range(2):
+            for d_ in range(2):
+                Mac, Mad = dot(Mv, gup[c]), dot(Mv, gup[d_])
+                T[:, :, 1 + c, :, 1 + d_] += -ein("q,qi,qj->qij", Mad, a3, gup[c]) + ein("q,qi,qj->qij", ai[:, c, d_] * M3, a3, a3) \
+                    - ein("q,qi,qj->qij", Mac, gup[d_], a3)
+        return psi, s, T
+
+
+class ShellResidual(object):
+    """Residual of a Kirchhoff-Love shell on the mapped patch, R(v) = D psi[v] - f . v per unit reference area: what
+    ``derivative(psi*spline.dx, u)`` of the reference gives for the energy of demos/kl-shell-svk.  The reference surface is the
+    patch (d = 2, nsd = 3); ``u`` the displacement ``Function`` on nF = 3 fields of its scalar space, read at assembly time.
+
+    ``material``: ``KirchhoffLoveSVK`` -- evaluated at the points ON THE DEVICE (``tg_shell_points``): the jets, s and the
+    324 npts tangent values never leave it; ``device_law=False`` sends it through its ``host`` method instead -- or any object
+    with ``host(Xjet, ujet) -> (psi, s, T)``, a host law whose arrays are uploaded and go through the same transform and
+    assembly.  ``assemble_vector`` evaluates the jets of the geometry and of u (``tg_quad_geometry_jet``, ``tg_quad_jet``),
+    calls the law, and returns the jet load of s minus the load of ``body_force`` (a value-slot entry of a
+    ``VectorJetLoadForm``: ``[npts, 3]``, a callable of the points, or 3 numbers; per unit reference area).
+    ``tangent()``: the ``VectorJetCoefficientForm`` of T; ``symmetric`` True for ``KirchhoffLoveSVK`` (T derives from an
+    energy), for another host law what the bits of the last assembled tangent prove.  ``energy(V)`` = sum_q wdet_q psi_q.
+    Points with a degenerate normal (|X_,1 x X_,2| or |x_,1 x x_,2| below 1e-14 |X_,1| |X_,2|) raise ``RuntimeError`` naming
+    their number.  ``rational``: u_i = u_h,i / W_h, tested against phi / W_h."""
+
+    def __init__(self, u, geometry, material, body_force=None, nq=None, rational=False, device_law=True):
+        if geometry is None:
+            raise ValueError("ShellResidual: point data live on a mapped patch (geometry=...)")
+        if not callable(getattr(material, "host", None)):
+            raise ValueError("ShellResidual: unknown material %r; KirchhoffLoveSVK, or an object with "
+                             "host(Xjet, ujet) -> (psi, s, T)" % (material,))
+        self.u, self.geometry, self.material = u, geometry, material
+        self.body_force, self.nq, self.rational = body_force, nq, bool(rational)
+        self.builtin = isinstance(material, KirchhoffLoveSVK) and material.kind == 0
+        self.device_law = bool(device_law) and self.builtin
+        self._host_symmetric = False
+        self._load = None
+        if body_force is not None:
+            self._load = VectorJetLoadForm(self._force_jets, geometry, nq=nq, rational=rational)
+
+    def _force_jets(self, x):
+        f = self.body_force
+        fv = numpy.asarray(f(x) if callable(f) else f, dtype=numpy.float64)
+        if fv.shape == (3,):
+            fv = numpy.tile(fv, (x.shape[0], 1))
+        if fv.shape != (x.shape[0], 3):
+            raise ValueError("ShellResidual: body_force: an array of shape %s for %d points; expected (%d, 3)"
+                             % (fv.shape, x.shape[0], x.shape[0]))
+        s = numpy.zeros((x.shape[0], 3, 6))
+        s[:, :, 0] = fv
+        return s
+
+    def jets(self, V):
+        """(points, node grid, Xjet, ujet): the jets of the reference surface and of the three displacement fields as
+        DeviceVectors of 18 npts values (component alpha of coordinate / field c at (6 c + alpha) npts + q)"""
+        who = "ShellResidual"
+        g, nF, nJ = _jet_form_scope(self.geometry, V, who)
+        nsd = len(self.geometry.cpFuncs) - 1
+        if g.dim() != 2 or nsd != 3 or nF != 3:
+            raise NotImplementedError("%s: a shell is a surface in space with a displacement of three fields (d = %d, nsd = %d, "
+                                      "nFields = %d)" % (who, g.dim(), nsd, nF))
+        pts = _vector_points(self.geometry, self.nq, who)
+        n = g.num_nodes()
+        uv = self.u.vector() if hasattr(self.u, "vector") else self.u
+        if uv.size() != nF * n:
+            raise ValueError("%s: u holds %d nodal values, the space has %d fields of %d" % (who, uv.size(), nF, n))
+        X = _per_points(self, "_Xjet", pts, lambda: _dev.quad_geometry_jet(pts.verts, pts.p, pts.cp, nq=pts.nq))
+        size = nJ * pts.npts
+        U, ui = _dev.DeviceVector(nF * size, zero=False), _dev.DeviceVector(n, zero=False)
+        for i in range(nF):
+            _dev.vec_copy_range(ui, 0, uv, i * n, n)
+            _dev.vec_copy_range(U, i * size, _dev.quad_jet(pts.verts, pts.p, pts.cp, ui, nq=pts.nq, rational=self.rational), 0, size)
+        return pts, g, X, U
+
+    def law(self, V, load=True, tangent=False, energy=False):
+        """(points, node grid, s, T, psi) at the current state, as DeviceVectors in the layouts of ``tg_jet_load_transform``
+        and ``tg_jet_transform`` (None where not asked for)"""
+        pts, g, X, U = self.jets(V)
+        npts = pts.npts
+        if self.device_law:
+            m = self.material
+            s, T, psi, nbad = _dev.shell_points(m.kind, m.E, m.nu, m.thickness, X, U, load, tangent, energy)
+            if nbad > 0:
+                raise RuntimeError("ShellResidual: %d quadrature points with a degenerate surface normal" % nbad)
+            return pts, g, s, T, psi
+        Xh = numpy.ascontiguousarray(X.get_local().reshape(3, 6, npts).transpose(2, 0, 1))
+        Uh = numpy.ascontiguousarray(U.get_local().reshape(3, 6, npts).transpose(2, 0, 1))
+        nbad = int(numpy.sum(KirchhoffLoveSVK.degenerate(Xh, Uh)))
+        if nbad > 0:
+            raise RuntimeError("ShellResidual: %d quadrature points with a degenerate surface normal" % nbad)
+        out = self.material.host(Xh, Uh)
+        if not isinstance(out, tuple) or len(out) != 3:
+            raise ValueError("ShellResidual: material.host(Xjet, ujet) returns (psi, s, T)")
+        psih, sh, Th = (numpy.asarray(o, dtype=numpy.float64) for o in out)
+        if psih.shape != (npts,) or sh.shape != (npts, 3, 6) or Th.shape != (npts, 3, 6, 3, 6):
+            raise ValueError("ShellResidual: material.host returned shapes %s, %s, %s for %d points"
+                             % (psih.shape, sh.shape, Th.shape, npts))
+        self._host_symmetric = _same_bits(Th, Th.transpose(0, 3, 4, 1, 2))
+        s = _dev.DeviceVector(data=numpy.ascontiguousarray(sh.transpose(1, 2, 0)).ravel()) if load else None
+        T = _dev.DeviceVector(data=numpy.ascontiguousarray(Th.transpose(1, 3, 2, 4, 0)).ravel()) if tangent else None
+        return pts, g, s, T, (_dev.DeviceVector(data=psih) if energy else None)
+
+    def assemble_vector(self, V, row0=None, row1=None):
+        who = "ShellResidual"
+        g, nF, nJ = _jet_form_scope(self.geometry, V, who)
+        _whole_rows(nF * g.num_nodes(), row0, row1, who, "patch")
+        pts, g, s, _, _ = self.law(V)
+        r = VectorJetLoadForm(s, self.geometry, nq=self.nq, rational=self.rational).assemble_vector(V)
+        if self._load is not None:
+            r.axpy(-1.0, self._load.assemble_vector(V))
+        return r
+
+    def energy(self, V=None):
+        if V is None:
+            V = self.u.function_space()
+        pts, g, _, _, psi = self.law(V, load=False, energy=True)
+        return pts.weights.inner(psi)
+
+    def tangent(self):
+        return _ShellTangent(self)
+
+
+class _ShellTangent(object):
+    """``symmetric``: True for ``KirchhoffLoveSVK`` (the tangent derives from an energy: major symmetry by the law, in the
+    matrix to rounding); for another host law that of the last assembled tangent and False before the first assembly (see
+    ``_QuasilinearTangent``)."""
+
+    def __init__(self, res):
+        self.res, self.geometry, self.symmetric = res, res.geometry, bool(res.builtin)
+
+    def _form(self, V):
+        res = self.res
+        pts, g, _, T, _ = res.law(V, load=False, tangent=True)
+        form = VectorJetCoefficientForm(res.geometry, T, nq=res.nq, rational=res.rational)
+        form._symmetric_hint = True if res.builtin else bool(res._host_symmetric)
+        if not res.builtin:
+            self.symmetric = bool(res._host_symmetric)
+        return form
+
+    def assemble_block(self, V, i, j, row0=None, row1=None):
+        return self._form(V).assemble_block(V, i, j, row0, row1)
+
+    def assemble_matrix(self, V, row0=None, row1=None):
+        return self._form(V).assemble_matrix(V, row0, row1)
+
+
 # ---- boundary integrals on a mapped patch (csrc/tg_boundary.hip): spline.ds and spline.n of the reference -----------------
 def _periodic_directions(geometry):
     """directions whose knot vector is not open (the faces there are no boundary), as far as the geometry tells"""

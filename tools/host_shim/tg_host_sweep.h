@@ -3,7 +3,9 @@
 // hip/hip_runtime.h, and host stand-ins for what those drivers call in the rest of the library -- the allocator, the
 // reference-element tables, the element-coupling pattern, tg_csr_from_blocks -- each allocating EXACTLY what the kernels may
 // touch.  Both sources include csrc/tg_point_shared.h (static inline and templates only: one translation unit here).  Include
-// once, from the file that has main().
+// once, from the file that has main().  TG_HOST_SWEEP_JET (tools/jet_host_sweep.cpp): also csrc/tg_jet.hip and csrc/tg_shell.hip,
+// whose kernels read the fourth table d2l[a][q] and the device copies of the element vertices: both are then allocated, again
+// at exactly their sizes.
 #pragma once
 #include <hip/hip_runtime.h>
 dim3 threadIdx, blockIdx, blockDim;
@@ -12,6 +14,10 @@ size_t g_host_lds_max = 0;
 
 #include "../../tigar_amd/csrc/tg_postproc.hip"
 #include "../../tigar_amd/csrc/tg_coef.hip"
+#ifdef TG_HOST_SWEEP_JET
+#include "../../tigar_amd/csrc/tg_jet.hip"
+#include "../../tigar_amd/csrc/tg_shell.hip"
+#endif
 #include <cstdarg>
 #include <random>
 
@@ -46,7 +52,18 @@ int tg_asm_coef_fast(const tg_patch_t *, tg_vec_t, tg_csr_t *, bool *taken) {
 int tg_asm_cache_get(const tg_patch_t *pt) {
   const int p = pt->p, p1 = p + 1, nq = pt->nq;
   free(g_asm_cache.tab);
+#ifdef TG_HOST_SWEEP_JET
+  double *tab = (double *)malloc(((size_t)3 * p1 * nq + nq) * sizeof(double));      // (l | dl | w | d2l: exactly what the kernels may read)
+  for (int k = 0; k < 3; k++) {
+    free(g_asm_cache.verts[k]);
+    g_asm_cache.verts[k] = nullptr;
+    if (k >= pt->d) continue;
+    g_asm_cache.verts[k] = (double *)malloc(pt->nverts[k] * sizeof(double));
+    memcpy(g_asm_cache.verts[k], pt->verts[k], pt->nverts[k] * sizeof(double));
+  }
+#else
   double *tab = (double *)malloc(((size_t)2 * p1 * nq + nq) * sizeof(double));      // (exactly what the kernels may read)
+#endif
   for (int q = 0; q < nq; q++) {
     double z = cos(M_PI * (q + 0.75) / (nq + 0.5)), pp = 1.0;
     for (int it = 0; it < 50; it++) {
@@ -74,6 +91,18 @@ int tg_asm_cache_get(const tg_patch_t *pt) {
       }
       tab[a * nq + q] = l;
       tab[p1 * nq + a * nq + q] = dl;
+#ifdef TG_HOST_SWEEP_JET
+      double d2l = 0.0;
+      for (int m = 0; m < p1; m++)
+        for (int r = 0; r < p1; r++) {
+          if (m == a || r == a || r == m) continue;
+          double term = 1.0 / (((double)(a - m) / p) * ((double)(a - r) / p));
+          for (int u = 0; u < p1; u++)
+            if (u != a && u != m && u != r) term *= (t - (double)u / p) / ((double)(a - u) / p);
+          d2l += term;
+        }
+      tab[2 * p1 * nq + nq + a * nq + q] = d2l;
+#endif
     }
   }
   g_asm_cache.tab = tab;
