@@ -2027,79 +2027,53 @@ class ExtractedSpline(object):
         return x
 
     # -- projection, error norms, quadrature-point evaluation (csrc/tg_postproc.hip)
-    def _quadrature_scope(self, who):
-        """Refuses what the quadrature-point operands do not cover: they are provided for the scalar Q_p space of one
-        tensor-product patch held by one rank, in the order of the node grid."""
+    def _point_scope(self, who, nfields=None, shared_dims=None):
+        """Refuses what the quadrature-point operands and point forms do not cover.  They serve one mapped tensor-product
+        patch held by one rank, in the order of the node grid, with continuous Q_p fields.  What differs between the kinds
+        of point forms comes as data: ``nfields`` the number of fields they take (None: any), ``shared_dims`` the parametric
+        dimensions d of those whose fields must lie on the control mesh's scalar basis and share one node grid."""
+        no = NotImplementedError
         if self._distributed():
-            raise NotImplementedError("%s: several ranks are not supported (the point values are numbered over the whole "
-                                      "patch)" % who)
+            raise no("%s: several ranks are not supported (the point values are numbered over the whole patch)" % who)
         if self._implicit():
-            raise NotImplementedError("%s: the streamed engine asks its forms for row blocks, which the quadrature-point "
-                                      "load does not hand out" % who)
+            raise no("%s: the streamed engine asks its forms for row blocks, which the point forms do not hand out" % who)
         if self._caller_ordered():
-            raise NotImplementedError("%s: a spline with the caller's FE dof order (feOrder) is not supported; the point "
-                                      "kernels number the node grid" % who)
-        if self.nFields != 1:
-            raise NotImplementedError("%s: nFields = %d; only scalar spaces are supported" % (who, self.nFields))
-        if isinstance(getattr(self, "_generator", None), FieldListSpline):
-            raise NotImplementedError("%s: FieldListSpline spaces (fields on their own bases) are not supported" % who)
-        grids = getattr(self.V, "grids", None)
-        if grids is None or len(grids) != 1 or not isinstance(grids[0], TensorNodeGrid) or grids[0].dg:
-            raise NotImplementedError("%s: the FE space is not the continuous Q_p space of a single tensor-product patch "
-                                      "(FieldListSpline, compatible, multi-patch, T-spline and DG spaces are not supported)" % who)
-
-    def _vector_quadrature_scope(self, who):
-        """As ``_quadrature_scope`` for the point forms of a vector-valued unknown: nFields = nsd fields, all on the control
-        mesh's scalar basis (``EqualOrderSpline(nsd, mesh)``: one continuous Q_p node grid, dofs field after field)."""
-        if self._distributed():
-            raise NotImplementedError("%s: several ranks are not supported (the point values are numbered over the whole "
-                                      "patch)" % who)
-        if self._implicit():
-            raise NotImplementedError("%s: the streamed engine asks its forms for row blocks, which the quadrature-point "
-                                      "forms do not hand out" % who)
-        if self._caller_ordered():
-            raise NotImplementedError("%s: a spline with the caller's FE dof order (feOrder) is not supported; the point "
-                                      "kernels number the node grid" % who)
-        if isinstance(getattr(self, "_generator", None), FieldListSpline):
-            raise NotImplementedError("%s: FieldListSpline spaces (fields on their own bases) are not supported" % who)
-        grids = getattr(self.V, "grids", None)
-        if grids is None or len(grids) != self.nFields or any(not isinstance(g, TensorNodeGrid) or g.dg for g in grids):
-            raise NotImplementedError("%s: the FE fields are not continuous Q_p fields of a single tensor-product patch "
-                                      "(FieldListSpline, compatible, multi-patch, T-spline and DG spaces are not supported)" % who)
-        if self.nFields != self.nsd:
-            raise NotImplementedError("%s: nFields = %d on a patch with nsd = %d; the displacement has as many fields as "
-                                      "there are physical directions" % (who, self.nFields, self.nsd))
-
-    def _jet_scope(self, who):
-        """Refuses what the second-derivative point forms (csrc/tg_jet.hip) do not cover.  They serve one mapped
-        tensor-product patch on one rank, the continuous Q_p node grid, nF >= 1 fields sharing that grid with dofs numbered
-        field after field, d = 1 or 2 parametric directions and nsd >= d, B-spline or NURBS control mesh."""
-        if self._distributed():
-            raise NotImplementedError("%s: several ranks are not supported (the point values are numbered over the whole "
-                                      "patch)" % who)
-        if self._implicit():
-            raise NotImplementedError("%s: the streamed engine asks its forms for row blocks, which the second-derivative "
-                                      "point forms do not hand out" % who)
-        if self._caller_ordered():
-            raise NotImplementedError("%s: a spline with the caller's FE dof order (feOrder) is not supported; the point "
-                                      "kernels number the node grid" % who)
+            raise no("%s: a spline with the caller's FE dof order (feOrder) is not supported; the point kernels number the "
+                     "node grid" % who)
         gen = getattr(self, "_generator", None)
         if isinstance(gen, FieldListSpline):
-            raise NotImplementedError("%s: FieldListSpline spaces (fields on their own bases) are not supported" % who)
+            raise no("%s: FieldListSpline spaces (fields on their own bases) are not supported" % who)
         on_control = getattr(gen, "_fields_on_control_basis", None)
-        if on_control is not None and not on_control():
-            raise NotImplementedError("%s: the fields of %s are not discretised with the control mesh's scalar basis "
-                                      "(FieldListSpline and compatible spaces are not supported)" % (who, type(gen).__name__))
+        if shared_dims is not None and on_control is not None and not on_control():
+            raise no("%s: the fields of %s are not discretised with the control mesh's scalar basis (FieldListSpline and "
+                     "compatible spaces are not supported)" % (who, type(gen).__name__))
         grids = getattr(self.V, "grids", None)
         if grids is None or len(grids) != self.nFields or any(not isinstance(g, TensorNodeGrid) or g.dg for g in grids):
-            raise NotImplementedError("%s: the FE fields are not continuous Q_p fields of a single tensor-product patch "
-                                      "(FieldListSpline, compatible, multi-patch, T-spline and DG spaces are not supported)" % who)
-        g = grids[0]
-        if any(gi.degree != g.degree or gi.shape() != g.shape() for gi in grids[1:]):
-            raise NotImplementedError("%s: the fields do not share one node grid (compatible spaces are not supported)" % who)
-        if g.dim() not in (1, 2):
-            raise NotImplementedError("%s: d = %d parametric directions; second-derivative point forms are provided for "
-                                      "curves and surfaces (d = 1, 2)" % (who, g.dim()))
+            raise no("%s: the FE fields are not continuous Q_p fields of a single tensor-product patch (FieldListSpline, "
+                     "compatible, multi-patch, T-spline and DG spaces are not supported)" % who)
+        if nfields is not None and self.nFields != nfields:
+            raise no("%s: nFields = %d; %s" % (who, self.nFields, "only scalar spaces are supported" if nfields == 1 else
+                     "on a patch with nsd = %d the displacement has as many fields as there are physical directions" % nfields))
+        if shared_dims is not None:
+            g = grids[0]
+            if any(gi.degree != g.degree or gi.shape() != g.shape() for gi in grids[1:]):
+                raise no("%s: the fields do not share one node grid (compatible spaces are not supported)" % who)
+            if g.dim() not in shared_dims:
+                raise no("%s: d = %d parametric directions; second-derivative point forms are provided for curves and "
+                         "surfaces (d = 1, 2)" % (who, g.dim()))
+
+    def _quadrature_scope(self, who):
+        """the scalar point operands: one field"""
+        self._point_scope(who, nfields=1)
+
+    def _vector_quadrature_scope(self, who):
+        """the point forms of a vector-valued unknown: nFields = nsd (``EqualOrderSpline(nsd, mesh)``)"""
+        self._point_scope(who, nfields=self.nsd)
+
+    def _jet_scope(self, who):
+        """the second-derivative point forms (csrc/tg_jet.hip): nF >= 1 fields on the control basis sharing one node grid,
+        d = 1 or 2 parametric directions and nsd >= d"""
+        self._point_scope(who, shared_dims=(1, 2))
 
     def evaluateJetsAtQuadrature(self, u, nq=None, rational=False):
         """The JET of u_h (``rational``: of u_h / W_h) at the quadrature points: value, first parametric derivatives, second
@@ -2115,13 +2089,8 @@ class ExtractedSpline(object):
         n = self.V.grids[0].num_nodes()
         if uv.size() != self.nFields * n:
             raise ValueError("%s: %d nodal values given, the space has %d" % (who, uv.size(), self.nFields * n))
-        if self.nFields == 1:
-            return _dev.quad_jet(pts.verts, pts.p, pts.cp, uv, nq=pts.nq, rational=rational)
-        out, ui = [], DeviceVector(n, zero=False)
-        for i in range(self.nFields):
-            _dev.vec_copy_range(ui, 0, uv, i * n, n)
-            out.append(_dev.quad_jet(pts.verts, pts.p, pts.cp, ui, nq=pts.nq, rational=rational))
-        return out
+        jet = lambda ui: _dev.quad_jet(pts.verts, pts.p, pts.cp, ui, nq=pts.nq, rational=rational)
+        return jet(uv) if self.nFields == 1 else forms._field_by_field(uv, self.nFields, n, jet)
 
     def geometryJetsAtQuadrature(self, nq=None):
         """The jets of the physical coordinates x_c = N_c / W_h at the quadrature points: a DeviceVector of nsd * nJ * npts

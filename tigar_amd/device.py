@@ -1162,15 +1162,32 @@ def _h_or_none(v):
     return v._h if v is not None else None
 
 
+def _nq(p, nq):
+    return p + 1 if nq is None else nq
+
+
+def _point_call(name, vertices, p, cp, nq, *args, rational=False, accept=()):
+    """The one way to call a point kernel: the entry ``name(&patch, *args)`` on the patch (vertices, p, cp) with ``nq`` Gauss
+    points per direction (p + 1 when None), its return code checked.  ``rational`` picks ``name + "_rational"`` where the
+    entry comes as such a pair (an entry that takes the flag as an argument gets it among ``args``).  A DeviceVector or
+    DeviceCSR among ``args`` goes as its handle, None as no vector.  ``accept``: return codes handed back instead of
+    raised.  The host arrays of the patch live until the entry returns."""
+    pt, keep = _patch(vertices, p, cp, _nq(p, nq))
+    if rational:
+        name += "_rational"
+    rc = getattr(_lib.lib(), name)(C.byref(pt), *[getattr(a, "_h", a) for a in args])
+    if rc not in accept:
+        check(rc, name)
+    return rc
+
+
 def quad_points(vertices, p, cp, nq=None):
     """(x, wdet): the physical positions x_q = F(xi_q) of the Gauss points (DeviceVector of nsd * npts values,
     component-major) and the weights wdet_q = w_q sqrt(det g) prod h_k of the mapped forms (``tg_quad_points``).  Points
     are numbered element-major, elements and the nq^d points of an element lexicographic with direction 0 fastest."""
-    nq = p + 1 if nq is None else nq
-    pt, keep = _patch(vertices, p, cp, nq)
-    npts = quad_count(vertices, nq)
+    npts = quad_count(vertices, _nq(p, nq))
     x, w = DeviceVector((len(cp) - 1) * npts, zero=False), DeviceVector(npts, zero=False)
-    check(_lib.lib().tg_quad_points(C.byref(pt), x._h, w._h), "tg_quad_points")
+    _point_call("tg_quad_points", vertices, p, cp, nq, x, w)
     return x, w
 
 
@@ -1178,23 +1195,18 @@ def quad_eval(vertices, p, cp, u, grad=False, nq=None, rational=False):
     """u_h at the Gauss points for the nodal DeviceVector ``u``; with ``grad`` also the Cartesian gradient (nsd * npts
     values, component-major): returns ``values`` or ``(values, gradient)`` (``tg_quad_eval``).  ``rational``: u_h / W_h and
     its gradient (``tg_quad_eval_rational``)."""
-    nq = p + 1 if nq is None else nq
-    pt, keep = _patch(vertices, p, cp, nq)
-    npts = quad_count(vertices, nq)
+    npts = quad_count(vertices, _nq(p, nq))
     val = DeviceVector(npts, zero=False)
     g = DeviceVector((len(cp) - 1) * npts, zero=False) if grad else None
-    name = "tg_quad_eval_rational" if rational else "tg_quad_eval"
-    check(getattr(_lib.lib(), name)(C.byref(pt), u._h, 1 if grad else 0, val._h, _h_or_none(g)), name)
+    _point_call("tg_quad_eval", vertices, p, cp, nq, u, 1 if grad else 0, val, g, rational=rational)
     return (val, g) if grad else val
 
 
 def quad_load(vertices, p, cp, fq, nq=None, rational=False):
     """L(v) = sum_q wdet_q f_q v(xi_q) for the DeviceVector ``fq`` of point values (``tg_quad_load``); ``rational``: v the
     functions phi / W_h (``tg_quad_load_rational``)."""
-    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
     out = DeviceVector(n=cp[0].size(), zero=False)          # (the entry zeroes it before the colours add)
-    name = "tg_quad_load_rational" if rational else "tg_quad_load"
-    check(getattr(_lib.lib(), name)(C.byref(pt), fq._h, out._h), name)
+    _point_call("tg_quad_load", vertices, p, cp, nq, fq, out, rational=rational)
     return out
 
 
@@ -1202,10 +1214,8 @@ def quad_error(vertices, p, cp, u=None, e=None, ge=None, nq=None, rational=False
     """(sum wdet (u_h - e)^2, sum wdet |grad u_h - ge|^2, sum wdet e^2) with ``u`` a nodal DeviceVector, ``e`` / ``ge``
     point values (npts / nsd * npts, component-major); any of the three may be None and counts as 0 (``tg_quad_error``).
     ``rational``: u_h / W_h in the place of u_h (``tg_quad_error_rational``)."""
-    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
     out = np.zeros(3)
-    name = "tg_quad_error_rational" if rational else "tg_quad_error"
-    check(getattr(_lib.lib(), name)(C.byref(pt), _h_or_none(u), _h_or_none(e), _h_or_none(ge), _p(out, c_f64p)), name)
+    _point_call("tg_quad_error", vertices, p, cp, nq, u, e, ge, _p(out, c_f64p), rational=rational)
     return float(out[0]), float(out[1]), float(out[2])
 
 
@@ -1215,33 +1225,26 @@ def coef_transform(vertices, p, cp, A=None, b=None, c=None, m=None, a_kind=None,
     ``assemble_coef_matrix`` takes.  ``A``: npts values (isotropic, ``a_kind`` 1) or nsd * nsd * npts (a tensor per point,
     ``a_kind`` 2; told apart by the size when ``a_kind`` is None); ``b``, ``c``: nsd * npts; ``m``: npts; DeviceVectors
     numbered as ``quad_points``, None = zero.  ``rational``: functions phi / W_h, beta folded into the data."""
-    nq = p + 1 if nq is None else nq
-    pt, keep = _patch(vertices, p, cp, nq)
-    d, npts = len(vertices), quad_count(vertices, nq)
+    d, npts = len(vertices), quad_count(vertices, _nq(p, nq))
     if a_kind is None:
         a_kind = 0 if A is None else (1 if A.size() == npts else 2)
     out = DeviceVector((d * d + 2 * d + 1) * npts, zero=False)
-    check(_lib.lib().tg_coef_transform(C.byref(pt), 1 if rational else 0, int(a_kind), _h_or_none(A), _h_or_none(b),
-                                       _h_or_none(c), _h_or_none(m), out._h), "tg_coef_transform")
+    _point_call("tg_coef_transform", vertices, p, cp, nq, 1 if rational else 0, int(a_kind), A, b, c, m, out)
     return out
 
 
 def flux_transform(vertices, p, cp, s=None, F=None, nq=None, rational=False):
     """(s^, F^) of L(v) = int s v + F . grad v dx on the reference element: (d + 1) * npts values (``tg_flux_transform``)"""
-    nq = p + 1 if nq is None else nq
-    pt, keep = _patch(vertices, p, cp, nq)
-    out = DeviceVector((len(vertices) + 1) * quad_count(vertices, nq), zero=False)
-    check(_lib.lib().tg_flux_transform(C.byref(pt), 1 if rational else 0, _h_or_none(s), _h_or_none(F), out._h),
-          "tg_flux_transform")
+    out = DeviceVector((len(vertices) + 1) * quad_count(vertices, _nq(p, nq)), zero=False)
+    _point_call("tg_flux_transform", vertices, p, cp, nq, 1 if rational else 0, s, F, out)
     return out
 
 
 def assemble_coef_matrix(vertices, p, cp, coef, nq=None):
     """the matrix of the transformed point coefficients ``coef`` (``coef_transform``) on the element-coupling pattern
     (``tg_assemble_coef_matrix``)"""
-    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
     h = handle()
-    check(_lib.lib().tg_assemble_coef_matrix(C.byref(pt), coef._h, C.byref(h)), "tg_assemble_coef_matrix")
+    _point_call("tg_assemble_coef_matrix", vertices, p, cp, nq, coef, C.byref(h))
     return DeviceCSR(h)
 
 
@@ -1249,10 +1252,8 @@ def quad_load_flux(vertices, p, cp, s=None, F=None, nq=None, rational=False):
     """L(v) = sum_q wdet_q (s_q v + F_q . grad v)(xi_q) for point values ``s`` (npts) and ``F`` (nsd * npts,
     component-major), either may be None (``tg_quad_load_flux``; ``rational``: v = phi / W_h,
     ``tg_quad_load_flux_rational``)."""
-    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
     out = DeviceVector(n=cp[0].size(), zero=False)          # (the entry zeroes it before the colours add)
-    name = "tg_quad_load_flux_rational" if rational else "tg_quad_load_flux"
-    check(getattr(_lib.lib(), name)(C.byref(pt), _h_or_none(s), _h_or_none(F), out._h), name)
+    _point_call("tg_quad_load_flux", vertices, p, cp, nq, s, F, out, rational=rational)
     return out
 
 
@@ -1261,20 +1262,16 @@ def coef_transform_blocks(vertices, p, cp, A, M=None, nq=None, rational=False):
     (``tg_coef_transform_blocks``): ``A`` holds A_iKjL at (((i nF + j) nsd + K) nsd + L) npts + q, ``M`` (or None) the reaction
     M_ij at (i nF + j) npts + q.  Returns nF^2 consecutive coefficient sets in the layout of ``coef_transform``, which
     ``assemble_coef_blocks`` takes."""
-    nq = p + 1 if nq is None else nq
-    pt, keep = _patch(vertices, p, cp, nq)
-    d, npts = len(vertices), quad_count(vertices, nq)
+    d, npts = len(vertices), quad_count(vertices, _nq(p, nq))
     out = DeviceVector(d * d * (d * d + 2 * d + 1) * npts, zero=False)
-    check(_lib.lib().tg_coef_transform_blocks(C.byref(pt), 1 if rational else 0, d, _h_or_none(A), _h_or_none(M), out._h),
-          "tg_coef_transform_blocks")
+    _point_call("tg_coef_transform_blocks", vertices, p, cp, nq, 1 if rational else 0, d, A, M, out)
     return out
 
 
 def assemble_coef_blocks(vertices, p, cp, coef_blocks, nq=None):
     """the nF n x nF n matrix (field-major) of the transformed blocks ``coef_blocks`` (``tg_assemble_coef_blocks``)"""
-    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
     h = handle()
-    check(_lib.lib().tg_assemble_coef_blocks(C.byref(pt), len(vertices), coef_blocks._h, C.byref(h)), "tg_assemble_coef_blocks")
+    _point_call("tg_assemble_coef_blocks", vertices, p, cp, nq, len(vertices), coef_blocks, C.byref(h))
     return DeviceCSR(h)
 
 
@@ -1297,20 +1294,16 @@ def jet_size(d):
 def quad_jet(vertices, p, cp, u, nq=None, rational=False):
     """The jet of u_h (``rational``: of u_h / W_h) at the Gauss points with respect to the patch's parametric coordinates
     (``tg_quad_jet``): nJ * npts values, component alpha at alpha * npts + q."""
-    nq = p + 1 if nq is None else nq
-    pt, keep = _patch(vertices, p, cp, nq)
-    out = DeviceVector(jet_size(len(vertices)) * quad_count(vertices, nq), zero=False)
-    check(_lib.lib().tg_quad_jet(C.byref(pt), u._h, 1 if rational else 0, out._h), "tg_quad_jet")
+    out = DeviceVector(jet_size(len(vertices)) * quad_count(vertices, _nq(p, nq)), zero=False)
+    _point_call("tg_quad_jet", vertices, p, cp, nq, u, 1 if rational else 0, out)
     return out
 
 
 def quad_geometry_jet(vertices, p, cp, nq=None):
     """The jets of the physical coordinates x_c = N_c / W (``tg_quad_geometry_jet``): nsd * nJ * npts values, component
     alpha of coordinate c at (c nJ + alpha) npts + q."""
-    nq = p + 1 if nq is None else nq
-    pt, keep = _patch(vertices, p, cp, nq)
-    out = DeviceVector((len(cp) - 1) * jet_size(len(vertices)) * quad_count(vertices, nq), zero=False)
-    check(_lib.lib().tg_quad_geometry_jet(C.byref(pt), out._h), "tg_quad_geometry_jet")
+    out = DeviceVector((len(cp) - 1) * jet_size(len(vertices)) * quad_count(vertices, _nq(p, nq)), zero=False)
+    _point_call("tg_quad_geometry_jet", vertices, p, cp, nq, out)
     return out
 
 
@@ -1318,36 +1311,30 @@ def jet_transform(vertices, p, cp, T, nblk, nq=None, rational=False):
     """T' = wdet Q^T T Q for ``nblk`` blocks of nJ x nJ point matrices, T^{alpha beta} of block b at
     (b nJ^2 + alpha nJ + beta) npts + q (``tg_jet_transform``); the result, in the same layout, is what
     ``assemble_jet_blocks`` takes."""
-    nq = p + 1 if nq is None else nq
-    pt, keep = _patch(vertices, p, cp, nq)
     nJ = jet_size(len(vertices))
-    out = DeviceVector(int(nblk) * nJ * nJ * quad_count(vertices, nq), zero=False)
-    check(_lib.lib().tg_jet_transform(C.byref(pt), 1 if rational else 0, int(nblk), T._h, out._h), "tg_jet_transform")
+    out = DeviceVector(int(nblk) * nJ * nJ * quad_count(vertices, _nq(p, nq)), zero=False)
+    _point_call("tg_jet_transform", vertices, p, cp, nq, 1 if rational else 0, int(nblk), T, out)
     return out
 
 
 def jet_load_transform(vertices, p, cp, s, nF, nq=None, rational=False):
     """s' = wdet Q^T s for ``nF`` fields, s^alpha of field i at (i nJ + alpha) npts + q (``tg_jet_load_transform``)"""
-    nq = p + 1 if nq is None else nq
-    pt, keep = _patch(vertices, p, cp, nq)
-    out = DeviceVector(int(nF) * jet_size(len(vertices)) * quad_count(vertices, nq), zero=False)
-    check(_lib.lib().tg_jet_load_transform(C.byref(pt), 1 if rational else 0, int(nF), s._h, out._h), "tg_jet_load_transform")
+    out = DeviceVector(int(nF) * jet_size(len(vertices)) * quad_count(vertices, _nq(p, nq)), zero=False)
+    _point_call("tg_jet_load_transform", vertices, p, cp, nq, 1 if rational else 0, int(nF), s, out)
     return out
 
 
 def assemble_jet_blocks(vertices, p, cp, coef, nF, nq=None):
     """the nF n x nF n matrix (field-major) of the transformed jet blocks ``coef`` (``tg_assemble_jet_blocks``)"""
-    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
     h = handle()
-    check(_lib.lib().tg_assemble_jet_blocks(C.byref(pt), int(nF), coef._h, C.byref(h)), "tg_assemble_jet_blocks")
+    _point_call("tg_assemble_jet_blocks", vertices, p, cp, nq, int(nF), coef, C.byref(h))
     return DeviceCSR(h)
 
 
 def quad_load_jet(vertices, p, cp, s_t, nF, nq=None):
     """out[i n + a] = sum_q sum_alpha s'^alpha_{i,q} J^alpha_ref phi_a for the transformed ``s_t`` (``tg_quad_load_jet``)"""
-    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
     out = DeviceVector(n=int(nF) * cp[0].size(), zero=False)          # (the entry zeroes it before the colours add)
-    check(_lib.lib().tg_quad_load_jet(C.byref(pt), int(nF), s_t._h, out._h), "tg_quad_load_jet")
+    _point_call("tg_quad_load_jet", vertices, p, cp, nq, int(nF), s_t, out)
     return out
 
 
@@ -1400,59 +1387,45 @@ def face_points(vertices, p, cp, direction, side, nq=None):
     normals with nsd * npts values (component-major), the surface weights w_q sqrt(det g_hat (g_hat^-1)_kk) and the
     thickness of the boundary element normal to the face.  Points are numbered face-element-major, the face elements and
     the nq^(d-1) points of one lexicographic in the remaining directions with the lower direction fastest."""
-    nq = p + 1 if nq is None else nq
-    pt, keep = _patch(vertices, p, cp, nq)
-    npts, nsd = face_count(vertices, direction, nq), len(cp) - 1
+    npts, nsd = face_count(vertices, direction, _nq(p, nq)), len(cp) - 1
     x, nrm = DeviceVector(nsd * npts, zero=False), DeviceVector(nsd * npts, zero=False)
     w, hn = DeviceVector(npts, zero=False), DeviceVector(npts, zero=False)
-    check(_lib.lib().tg_face_points(C.byref(pt), int(direction), int(side), x._h, w._h, nrm._h, hn._h), "tg_face_points")
+    _point_call("tg_face_points", vertices, p, cp, nq, int(direction), int(side), x, w, nrm, hn)
     return x, w, nrm, hn
 
 
 def face_eval(vertices, p, cp, direction, side, u, grad=False, normal_derivative=False, nq=None, rational=False):
     """(values, gradient or None, d_n u or None) of the nodal DeviceVector ``u`` at the points of the face
     (``tg_face_eval``; ``rational``: u_h / W_h, ``tg_face_eval_rational``)"""
-    nq = p + 1 if nq is None else nq
-    pt, keep = _patch(vertices, p, cp, nq)
-    npts = face_count(vertices, direction, nq)
+    npts = face_count(vertices, direction, _nq(p, nq))
     val = DeviceVector(npts, zero=False)
     g = DeviceVector((len(cp) - 1) * npts, zero=False) if grad else None
     dn = DeviceVector(npts, zero=False) if normal_derivative else None
-    name = "tg_face_eval_rational" if rational else "tg_face_eval"
-    check(getattr(_lib.lib(), name)(C.byref(pt), int(direction), int(side), u._h, val._h, _h_or_none(g), _h_or_none(dn)), name)
+    _point_call("tg_face_eval", vertices, p, cp, nq, int(direction), int(side), u, val, g, dn, rational=rational)
     return val, g, dn
 
 
 def face_load(vertices, p, cp, direction, side, fq, fnq, out, nq=None, rational=False):
     """out[node] += sum_q wsurf_q (f_q phi_node + fn_q d_n phi_node) for point values ``fq`` / ``fnq`` (either may be
     None) of the face (``tg_face_load``; ``rational``: phi / W_h, ``tg_face_load_rational``); returns ``out``"""
-    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
-    name = "tg_face_load_rational" if rational else "tg_face_load"
-    check(getattr(_lib.lib(), name)(C.byref(pt), int(direction), int(side), _h_or_none(fq), _h_or_none(fnq), out._h), name)
+    _point_call("tg_face_load", vertices, p, cp, nq, int(direction), int(side), fq, fnq, out, rational=rational)
     return out
 
 
 def face_matrix(vertices, p, cp, direction, side, a=None, b=None, c=None, nq=None, rational=False):
     """A_ab = sum_q wsurf_q (a_q phi_a phi_b + b_q phi_a d_n phi_b + c_q d_n phi_a phi_b) of the face as a DeviceCSR on
     all FE nodes, pattern = the element coupling restricted to the boundary layer (``tg_face_matrix``)"""
-    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
     h = handle()
-    name = "tg_face_matrix_rational" if rational else "tg_face_matrix"
-    check(getattr(_lib.lib(), name)(C.byref(pt), int(direction), int(side), _h_or_none(a), _h_or_none(b), _h_or_none(c),
-                                    C.byref(h)), name)
+    _point_call("tg_face_matrix", vertices, p, cp, nq, int(direction), int(side), a, b, c, C.byref(h), rational=rational)
     return DeviceCSR(h)
 
 
 def face_matrix_add(A, vertices, p, cp, direction, side, a=None, b=None, c=None, scale=1.0, nq=None, rational=False):
     """the entries of ``face_matrix`` times ``scale`` added in place into ``A`` (``tg_face_matrix_add``).  Returns False,
     with ``A`` unchanged, when the pattern of ``A`` lacks one of them."""
-    pt, keep = _patch(vertices, p, cp, p + 1 if nq is None else nq)
-    name = "tg_face_matrix_add_rational" if rational else "tg_face_matrix_add"
-    rc = getattr(_lib.lib(), name)(C.byref(pt), int(direction), int(side), _h_or_none(a), _h_or_none(b), _h_or_none(c),
-                                   float(scale), A._h)
-    if rc == 3:
+    if _point_call("tg_face_matrix_add", vertices, p, cp, nq, int(direction), int(side), a, b, c, float(scale), A,
+                   rational=rational, accept=(3,)) == 3:
         return False
-    check(rc, name)
     A._T = None
     return True
 

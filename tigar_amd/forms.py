@@ -440,6 +440,72 @@ def _check_nq(nq, p):
     return int(nq)
 
 
+# ---- the point-data reader: what a caller gives at the points -> one device array, point index last -------------------------
+def _same_bits(a, b):
+    a, b = numpy.ascontiguousarray(a, dtype=numpy.float64), numpy.ascontiguousarray(b, dtype=numpy.float64)
+    return a.shape == b.shape and bool(numpy.array_equal(a.view(numpy.int64), b.view(numpy.int64)))
+
+
+def point_array(v, npts, shape, who="point data"):
+    """``v`` as a float64 array ``[npts] + shape``: one block of the component ``shape`` serves every point; anything else
+    but ``[npts] + shape`` is a ValueError naming the given and the expected shape.  Host only."""
+    v, shape = numpy.asarray(v, dtype=numpy.float64), tuple(int(s) for s in shape)
+    if shape and v.shape == shape:
+        v = numpy.broadcast_to(v, (npts,) + shape)
+    if v.shape != (npts,) + shape:
+        raise ValueError("%s: an array of shape %s for %d points; expected %s%s"
+                         % (who, v.shape, npts, (npts,) + shape, " or %s" % (shape,) if shape else ""))
+    return v
+
+
+def point_block(v, npts, shape, perm=None, swap=None, who="point data"):
+    """The host half of the reader: ``v`` (``point_array``) as the contiguous 1-D array of the device layout -- the
+    component axes in the order ``perm`` (a permutation of range(len(shape)); None: as given), the point index last and
+    fastest.  With ``swap`` (a permutation of the component axes) returns ``(array, symmetric)``: whether ``v`` equals, BIT
+    FOR BIT, itself with the component axes so permuted (-0.0 differs from 0.0, a NaN equals itself)."""
+    v = point_array(v, npts, shape, who)
+    order = range(len(shape)) if perm is None else perm
+    flat = numpy.ascontiguousarray(v.transpose(tuple(1 + a for a in order) + (0,))).ravel()
+    if swap is None:
+        return flat
+    return flat, _same_bits(v, v.transpose((0,) + tuple(1 + a for a in swap)))
+
+
+def point_unblock(flat, npts, shape):
+    """the reverse of ``point_block`` without ``perm``: device layout (point index last) -> ``[npts] + shape``"""
+    k = len(shape)
+    return numpy.ascontiguousarray(numpy.asarray(flat).reshape(tuple(shape) + (npts,)).transpose((k,) + tuple(range(k))))
+
+
+def _on_points(f, pts):
+    """what ``f`` gives at the points: a callable is called on ``x [npts, nsd]``, on a face with ``(x, n)`` when it takes two"""
+    if not callable(f):
+        return f
+    return f(pts.x, pts.n) if hasattr(pts, "normals") and _argcount(f) >= 2 else f(pts.x)
+
+
+def _point_data(f, pts, shape, who, perm=None, swap=None, hint=None, pre=None):
+    """The device half of the reader: the DeviceVector of ``f`` in the layout of ``point_block`` (with ``swap``:
+    ``(DeviceVector, symmetric)``).  A DeviceVector is taken as it is after a length check, its symmetry is ``hint`` when
+    one is set and is read from its bits otherwise; anything else (a callable of the points, an array, one block) goes
+    through ``point_block`` (after ``pre``, where a form reshapes what it was given) and one upload."""
+    if not isinstance(f, _dev.DeviceVector):
+        v = numpy.asarray(_on_points(f, pts), dtype=numpy.float64)
+        out = point_block(v if pre is None else pre(v), pts.npts, shape, perm, swap, who)
+        return _dev.DeviceVector(data=out) if swap is None else (_dev.DeviceVector(data=out[0]), out[1])
+    each = int(numpy.prod(shape, dtype=numpy.int64))
+    if f.size() != each * pts.npts:
+        raise ValueError("%s: %d values given, expected %d per point at %d points = %d"
+                         % (who, f.size(), each, pts.npts, each * pts.npts))
+    if swap is None:
+        return f
+    if hint is not None:
+        return f, bool(hint)
+    order = list(range(len(shape)) if perm is None else perm)
+    h = f.get_local().reshape(tuple(shape[a] for a in order) + (pts.npts,))
+    return f, _same_bits(h, h.transpose(tuple(order.index(swap[a]) for a in order) + (len(order),)))
+
+
 class QuadraturePoints(object):
     """The Gauss points of a mapped patch, element-major (elements and the nq^d points of an element lexicographic with
     direction 0 fastest): ``x`` host array [npts, nsd] (downloaded on first use), ``x_device`` (nsd * npts values,
@@ -454,7 +520,7 @@ class QuadraturePoints(object):
     @property
     def x(self):
         if self._x is None:
-            self._x = numpy.ascontiguousarray(self.x_device.get_local().reshape(self.nsd, self.npts).T)
+            self._x = point_unblock(self.x_device.get_local(), self.npts, (self.nsd,))
         return self._x
 
     def values(self, f, who="f"):
@@ -484,17 +550,7 @@ class QuadraturePoints(object):
     def vector_values(self, f, who="f"):
         """point values of a vector field (nsd * npts, component-major): a callable ``x -> [npts, nsd]``, an array
         [npts, nsd], a sequence of nsd numbers, or a DeviceVector already in that layout"""
-        if isinstance(f, _dev.DeviceVector):
-            if f.size() != self.nsd * self.npts:
-                raise ValueError("%s: %d values given, expected nsd * npts = %d" % (who, f.size(), self.nsd * self.npts))
-            return f
-        v = numpy.asarray(f(self.x) if callable(f) else f, dtype=numpy.float64)
-        if v.shape == (self.nsd,):
-            v = numpy.tile(v, (self.npts, 1))
-        if v.shape != (self.npts, self.nsd):
-            raise ValueError("%s: an array of shape %s for %d points; expected (%d, %d)"
-                             % (who, v.shape, self.npts, self.npts, self.nsd))
-        return _dev.DeviceVector(data=numpy.ascontiguousarray(v.T).ravel())
+        return _point_data(f, self, (self.nsd,), who)
 
 
 def quadrature_points(geometry, V, nq=None, who="quadrature points"):
@@ -533,7 +589,7 @@ class QuadratureLoadForm(object):
 
     def assemble_vector(self, V, row0=None, row1=None):
         if self.flux is not None:
-            _point_form_scope(self.geometry, "QuadratureLoadForm")
+            _point_scope(self.geometry, V, "QuadratureLoadForm", "scalar")
         _whole_rows(_single_grid(V).num_nodes(), row0, row1, "QuadratureLoadForm", "patch")
         if self.flux is None:
             pts, fq = self.point_values(V)
@@ -668,45 +724,55 @@ class _SemilinearTangent(object):
 
 
 # ---- volume forms with point coefficients (csrc/tg_coef.hip) ---------------------------------------------------------------
-def _point_form_scope(geometry, who):
-    """Refuses what the forms with point data do not cover: an ExtractedSpline says itself what its quadrature-point
-    operands serve (one rank, the order of the node grid, one scalar field on the control mesh's basis)"""
+_SCOPE_OF_KIND = {"scalar": "_quadrature_scope", "vector": "_vector_quadrature_scope", "jet": "_jet_scope"}
+
+
+def _point_scope(geometry, V, who, kind):
+    """What a point form of ``kind`` works on, or the refusal with its reason.  An ExtractedSpline says itself what its
+    point operands serve (one rank, the order of the node grid, ...: ``_point_scope`` there), the generator whether its
+    fields lie on the control mesh's scalar basis.
+      "scalar": one scalar field; returns None.
+      "vector": a displacement, nF = nsd = d fields (d = 2 plane strain, or 3) on one continuous Q_p node grid, dofs field
+                after field (``EqualOrderSpline(d, mesh)``); returns (node grid, nF).
+      "jet":    nF >= 1 fields on one such grid of a patch with d = 1, 2 and nsd >= d; returns (node grid, nF, nJ)."""
     if geometry is None:
-        raise ValueError("%s: point coefficients live on a mapped patch (geometry=...)" % who)
-    scope = getattr(geometry, "_quadrature_scope", None)
+        raise ValueError("%s: point data live on a mapped patch (geometry=...)" % who)
+    scope = getattr(geometry, _SCOPE_OF_KIND[kind], None)
     if scope is not None:
         scope(who)
     _fields_of_the_patch(geometry, who)
-
-
-def _same_bits(a, b):
-    a, b = numpy.ascontiguousarray(a, dtype=numpy.float64), numpy.ascontiguousarray(b, dtype=numpy.float64)
-    return a.shape == b.shape and numpy.array_equal(a.view(numpy.int64), b.view(numpy.int64))
+    if kind == "scalar":
+        return None
+    g = _one_shared_grid(V, who)
+    nF, nsd, d = len(V.grids), len(geometry.cpFuncs) - 1, g.dim()
+    if kind == "jet":
+        if d not in (1, 2):
+            raise NotImplementedError("%s: d = %d parametric directions; second-derivative point forms are provided for "
+                                      "curves and surfaces (d = 1, 2)" % (who, d))
+        if nsd < d:
+            raise NotImplementedError("%s: nsd = %d physical directions on a patch of d = %d parametric ones" % (who, nsd, d))
+        return g, nF, _dev.jet_size(d)
+    if nsd != d or d not in (2, 3):
+        raise NotImplementedError("%s: nsd = %d physical directions on a patch of d = %d parametric ones; a solid has "
+                                  "nsd = d = 2 (plane strain) or 3" % (who, nsd, d))
+    if nF != nsd:
+        raise NotImplementedError("%s: nFields = %d; the displacement has nsd = %d fields" % (who, nF, nsd))
+    return g, nF
 
 
 def _tensor_values(pts, A, who):
     """(kind, DeviceVector, symmetric) of a diffusion given at the points: kind 1 = one value per point, 2 = an nsd x nsd
     tensor per point (component (i, j) of point q at (i nsd + j) npts + q)"""
-    nsd, npts = pts.nsd, pts.npts
     if isinstance(A, _dev.DeviceVector):
-        if A.size() == npts:
+        if A.size() == pts.npts:
             return 1, A, True
-        if A.size() != nsd * nsd * npts:
-            raise ValueError("%s: %d values given, expected npts = %d or nsd * nsd * npts = %d"
-                             % (who, A.size(), npts, nsd * nsd * npts))
-        h = A.get_local().reshape(nsd, nsd, npts)
-        return 2, A, _same_bits(h, h.transpose(1, 0, 2))
-    if hasattr(A, "vector") and hasattr(A, "function_space") or numpy.ndim(A) == 0 and not callable(A):
+    elif hasattr(A, "vector") and hasattr(A, "function_space") or numpy.ndim(A) == 0 and not callable(A):
         return 1, pts.values(A, who), True
-    v = numpy.asarray(A(pts.x) if callable(A) else A, dtype=numpy.float64)
-    if v.shape == (npts,):
-        return 1, _dev.DeviceVector(data=v), True
-    if v.shape == (nsd, nsd):
-        v = numpy.tile(v, (npts, 1, 1))
-    if v.shape != (npts, nsd, nsd):
-        raise ValueError("%s: an array of shape %s for %d points; expected (%d,) or (%d, %d, %d)"
-                         % (who, v.shape, npts, npts, npts, nsd, nsd))
-    return 2, _dev.DeviceVector(data=numpy.ascontiguousarray(v.transpose(1, 2, 0)).ravel()), _same_bits(v, v.transpose(0, 2, 1))
+    else:
+        A = numpy.asarray(_on_points(A, pts), dtype=numpy.float64)
+        if A.shape == (pts.npts,):
+            return 1, _dev.DeviceVector(data=A), True
+    return (2,) + _point_data(A, pts, (pts.nsd, pts.nsd), who, swap=(1, 0))
 
 
 class CoefficientForm(object):
@@ -742,7 +808,7 @@ class CoefficientForm(object):
         """(points, kind of A, A, b, c, m, symmetric) with the point data as DeviceVectors (None = absent).  What does not
         depend on a Function is computed once per set of points."""
         who = "CoefficientForm"
-        _point_form_scope(self.geometry, who)
+        _point_scope(self.geometry, V, who, "scalar")
         pts = quadrature_points(self.geometry, V, self.nq, who)
 
         def static():
@@ -769,7 +835,7 @@ class CoefficientForm(object):
         return self.coefficients(self.geometry.V_control)[6]
 
     def assemble_matrix(self, V, row0=None, row1=None):
-        _point_form_scope(self.geometry, "CoefficientForm")
+        _point_scope(self.geometry, V, "CoefficientForm", "scalar")
         _whole_rows(_single_grid(V).num_nodes(), row0, row1, "CoefficientForm", "patch")
         pts, kind, A, b, c, m, _ = self.coefficients(V)
         coef = _dev.coef_transform(pts.verts, pts.p, pts.cp, A, b, c, m, a_kind=kind, nq=pts.nq, rational=self.rational)
@@ -800,21 +866,18 @@ class QuasilinearResidual(object):
     def state(self, V):
         """(points, u at the points [npts], its Cartesian gradient [npts, nsd]) on the host"""
         who = "QuasilinearResidual"
-        _point_form_scope(self.geometry, who)
+        _point_scope(self.geometry, V, who, "scalar")
         pts = quadrature_points(self.geometry, V, self.nq, who)
-        uv = self.u.vector() if hasattr(self.u, "vector") else self.u
-        if uv.size() != _single_grid(V).num_nodes():
-            raise ValueError("%s: u holds %d nodal values, the space has %d" % (who, uv.size(), _single_grid(V).num_nodes()))
+        uv = _nodal_vector(self.u, 1, _single_grid(V).num_nodes(), who)
         val, g = _dev.quad_eval(pts.verts, pts.p, pts.cp, uv, grad=True, nq=pts.nq, rational=self.rational)
-        return pts, val.get_local(), numpy.ascontiguousarray(g.get_local().reshape(pts.nsd, pts.npts).T)
+        return pts, val.get_local(), point_unblock(g.get_local(), pts.npts, (pts.nsd,))
 
     def assemble_vector(self, V, row0=None, row1=None):
-        _point_form_scope(self.geometry, "QuasilinearResidual")
+        _point_scope(self.geometry, V, "QuasilinearResidual", "scalar")
         _whole_rows(_single_grid(V).num_nodes(), row0, row1, "QuasilinearResidual", "patch")
         pts, uq, gq = self.state(V)
-        out = self.residual(pts.x, uq, gq)
-        if not isinstance(out, tuple) or len(out) != 2:
-            raise ValueError("QuasilinearResidual: residual(x, u, grad u) returns (flux or None, source or None)")
+        out = _law_result(self.residual(pts.x, uq, gq), "QuasilinearResidual", "residual(x, u, grad u)",
+                          "(flux or None, source or None)", [None] * 2)
         F = pts.vector_values(out[0], "QuasilinearResidual: flux") if out[0] is not None else None
         s = pts.values(out[1], "QuasilinearResidual: source") if out[1] is not None else None
         r = _dev.quad_load_flux(pts.verts, pts.p, pts.cp, s, F, nq=pts.nq, rational=self.rational)
@@ -837,12 +900,11 @@ class _QuasilinearTangent(object):
 
     def assemble_matrix(self, V, row0=None, row1=None):
         res = self.res
-        _point_form_scope(res.geometry, "QuasilinearResidual.tangent")
+        _point_scope(res.geometry, V, "QuasilinearResidual.tangent", "scalar")
         _whole_rows(_single_grid(V).num_nodes(), row0, row1, "QuasilinearResidual.tangent", "patch")
         pts, uq, gq = res.state(V)
-        out = res._tangent(pts.x, uq, gq)
-        if not isinstance(out, tuple) or len(out) != 4:
-            raise ValueError("QuasilinearResidual: tangent(x, u, grad u) returns (A, b, c, m), any of them None")
+        out = _law_result(res._tangent(pts.x, uq, gq), "QuasilinearResidual", "tangent(x, u, grad u)",
+                          "(A, b, c, m), any of them None", [None] * 4)
         form = CoefficientForm(res.geometry, out[0], out[1], out[2], out[3], nq=res.nq, rational=res.rational)
         A = form.assemble_matrix(V)
         self.symmetric = form.coefficients(V)[6]
@@ -860,32 +922,82 @@ def _shared_grid(V):
     return g
 
 
-def _vector_form_scope(geometry, V, who):
-    """(node grid, nF) of a displacement space on the patch of ``geometry``: nF = nsd = d fields on one continuous Q_p node
-    grid, dofs field after field (``EqualOrderSpline(d, mesh)``); refuses everything else with the reason.  An
-    ExtractedSpline says itself what its vector point forms serve (``_vector_quadrature_scope``)."""
-    if geometry is None:
-        raise ValueError("%s: point tangents live on a mapped patch (geometry=...)" % who)
-    scope = getattr(geometry, "_vector_quadrature_scope", None)
-    if scope is not None:
-        scope(who)
-    _fields_of_the_patch(geometry, who)
+def _one_shared_grid(V, who):
+    """``_shared_grid`` or the refusal"""
     g = _shared_grid(V)
     if g is None:
         raise NotImplementedError("%s: the fields of the space must share one continuous Q_p node grid of a tensor-product "
                                   "patch (compatible, FieldList, multi-patch, T-spline and DG spaces are not supported)" % who)
-    nF, nsd, d = len(V.grids), len(geometry.cpFuncs) - 1, g.dim()
-    if nsd != d or d not in (2, 3):
-        raise NotImplementedError("%s: nsd = %d physical directions on a patch of d = %d parametric ones; a solid has "
-                                  "nsd = d = 2 (plane strain) or 3" % (who, nsd, d))
-    if nF != nsd:
-        raise NotImplementedError("%s: nFields = %d; the displacement has nsd = %d fields" % (who, nF, nsd))
-    return g, nF
+    return g
 
 
 def _vector_points(geometry, nq, who):
     """the quadrature points of the patch (those of the scalar space the fields share)"""
     return quadrature_points(geometry, geometry.V_control, nq, who)
+
+
+def _nodal_vector(u, nF, n, who):
+    """the nodal DeviceVector of a Function (or the vector itself), holding nF fields of n values"""
+    uv = u.vector() if hasattr(u, "vector") else u
+    if uv.size() != nF * n:
+        raise ValueError("%s: u holds %d nodal values, the space has %s" % (who, uv.size(), n if nF == 1 else "%d fields of %d" % (nF, n)))
+    return uv
+
+
+def _field_by_field(uv, nF, n, call, size=None):
+    """``call(u_i)`` for the nF fields of the nodal vector ``uv``, each copied into one scratch vector of n values.  With
+    ``size`` the results (DeviceVectors of that many values) are gathered field after field in one DeviceVector, else
+    they are returned as a list."""
+    ui = _dev.DeviceVector(n, zero=False)
+    out = _dev.DeviceVector(nF * size, zero=False) if size is not None else []
+    for i in range(nF):
+        _dev.vec_copy_range(ui, 0, uv, i * n, n)
+        part = call(ui)
+        if size is None:
+            out.append(part)
+        else:
+            _dev.vec_copy_range(out, i * size, part, 0, size)
+    return out
+
+
+def _law_result(out, who, call, names, shapes):
+    """what a host law returned: a tuple of len(shapes) entries, each brought to a float64 array of the given shape (None:
+    the entry is handed on as it is)"""
+    if not isinstance(out, tuple) or len(out) != len(shapes):
+        raise ValueError("%s: %s returns %s" % (who, call, names))
+    arrays = [o if s is None else numpy.asarray(o, dtype=numpy.float64) for o, s in zip(out, shapes)]
+    if any(s is not None and a.shape != tuple(s) for a, s in zip(arrays, shapes)):
+        raise ValueError("%s: %s returned shapes %s; %s has shapes %s" % (
+            who, call, ", ".join(str(getattr(a, "shape", None)) for a in arrays), names, ", ".join(str(s) for s in shapes)))
+    return arrays
+
+
+class _LawTangent(object):
+    """The tangent form of a residual with a point law (``res.builtin``, ``res._host_symmetric``, ``res.law``): the
+    ``_form_class`` of the tangent data ``_data(V)`` at the current state.  ``symmetric``: True for a built-in law (the
+    tangent derives from an energy: major symmetry by the law, in the matrix to rounding); for a host law that of the last
+    assembled tangent and False before the first assembly (see ``_QuasilinearTangent``)."""
+    _form_class = None
+
+    def __init__(self, res):
+        self.res, self.geometry, self.symmetric = res, res.geometry, bool(res.builtin)
+
+    def _rows(self, V, row0, row1, block):
+        """a refusal of row blocks that comes before the law is evaluated (none: the form refuses)"""
+
+    def _form(self, V):
+        res = self.res
+        form = self._form_class(res.geometry, self._data(V), nq=res.nq, rational=res.rational)
+        form._symmetric_hint = self.symmetric = True if res.builtin else bool(res._host_symmetric)
+        return form
+
+    def assemble_block(self, V, i, j, row0=None, row1=None):
+        self._rows(V, row0, row1, True)
+        return self._form(V).assemble_block(V, i, j, row0, row1)
+
+    def assemble_matrix(self, V, row0=None, row1=None):
+        self._rows(V, row0, row1, False)
+        return self._form(V).assemble_matrix(V, row0, row1)
 
 
 def _det_inv(F):
@@ -970,9 +1082,10 @@ class NeoHookean(_Material):
         return P, A, psi
 
 
-def _tangent_to_device(A):
-    """[npts, nF, nsd, nF, nsd] (A[q, i, K, j, L]) -> the block layout of ``tg_coef_transform_blocks``"""
-    return _dev.DeviceVector(data=numpy.ascontiguousarray(numpy.asarray(A, dtype=numpy.float64).transpose(1, 3, 2, 4, 0)).ravel())
+# [npts, nF, nK, nF, nK] point tangents (A[q, i, K, j, L], T[q, i, alpha, j, beta]) go to the device block by block, in
+# the order (i, j, K, L, q) that ``tg_coef_transform_blocks`` and ``tg_jet_transform`` read; their major symmetry swaps (i, K)
+# with (j, L)
+_BLOCK_ORDER, _MAJOR_SWAP = (0, 2, 1, 3), (2, 3, 0, 1)
 
 
 class VectorCoefficientForm(object):
@@ -1003,46 +1116,16 @@ class VectorCoefficientForm(object):
         """(points, A, M, symmetric) with the point data as DeviceVectors in the block layout (M None = absent): computed
         once per set of points"""
         who = "VectorCoefficientForm"
-        g, nF = _vector_form_scope(self.geometry, V, who)
+        g, nF = _point_scope(self.geometry, V, who, "vector")
         pts = _vector_points(self.geometry, self.nq, who)
         return _per_points(self, "_static", pts, lambda: self._static_coefficients(pts, nF, who))
 
     def _static_coefficients(self, pts, nF, who):
-        npts, nsd = pts.npts, pts.nsd
-        if isinstance(self.tangent, _dev.DeviceVector):
-            A = self.tangent
-            if A.size() != nF * nF * nsd * nsd * npts:
-                raise ValueError("%s: tangent: %d values given, expected nF^2 nsd^2 npts = %d"
-                                 % (who, A.size(), nF * nF * nsd * nsd * npts))
-            sym = None
-            if self._symmetric_hint is None:
-                h = A.get_local().reshape(nF, nF, nsd, nsd, npts)
-                sym = _same_bits(h, h.transpose(1, 0, 3, 2, 4))
-        else:
-            v = numpy.asarray(self.tangent(pts.x) if callable(self.tangent) else self.tangent, dtype=numpy.float64)
-            if v.shape == (nF, nsd, nF, nsd):
-                v = numpy.tile(v, (npts, 1, 1, 1, 1))
-            if v.shape != (npts, nF, nsd, nF, nsd):
-                raise ValueError("%s: tangent: an array of shape %s for %d points; expected (%d, %d, %d, %d, %d)"
-                                 % (who, v.shape, npts, npts, nF, nsd, nF, nsd))
-            A, sym = _tangent_to_device(v), _same_bits(v, v.transpose(0, 3, 4, 1, 2))
+        A, sym = _point_data(self.tangent, pts, (nF, pts.nsd, nF, pts.nsd), who + ": tangent", _BLOCK_ORDER, _MAJOR_SWAP,
+                             hint=self._symmetric_hint)
         M, symM = None, True
-        if isinstance(self.reaction, _dev.DeviceVector):
-            M = self.reaction
-            if M.size() != nF * nF * npts:
-                raise ValueError("%s: reaction: %d values given, expected nF^2 npts = %d" % (who, M.size(), nF * nF * npts))
-            h = M.get_local().reshape(nF, nF, npts)
-            symM = _same_bits(h, h.transpose(1, 0, 2))
-        elif self.reaction is not None:
-            v = numpy.asarray(self.reaction(pts.x) if callable(self.reaction) else self.reaction, dtype=numpy.float64)
-            if v.shape == (nF, nF):
-                v = numpy.tile(v, (npts, 1, 1))
-            if v.shape != (npts, nF, nF):
-                raise ValueError("%s: reaction: an array of shape %s for %d points; expected (%d, %d, %d)"
-                                 % (who, v.shape, npts, npts, nF, nF))
-            M, symM = _dev.DeviceVector(data=numpy.ascontiguousarray(v.transpose(1, 2, 0)).ravel()), _same_bits(v, v.transpose(0, 2, 1))
-        if sym is None:
-            sym = bool(self._symmetric_hint)
+        if self.reaction is not None:
+            M, symM = _point_data(self.reaction, pts, (nF, nF), who + ": reaction", swap=(1, 0))
         return pts, A, M, bool(sym and symM)
 
     @property
@@ -1055,7 +1138,7 @@ class VectorCoefficientForm(object):
 
     def assemble_block(self, V, i, j, row0=None, row1=None):
         """block (i, j): test field i, trial field j (all rows of the field)"""
-        g, nF = _vector_form_scope(self.geometry, V, "VectorCoefficientForm")
+        g, nF = _point_scope(self.geometry, V, "VectorCoefficientForm", "vector")
         if not (0 <= int(i) < nF and 0 <= int(j) < nF):
             raise ValueError("VectorCoefficientForm: block (%r, %r) of a %d-field space" % (i, j, nF))
         _whole_rows(g.num_nodes(), row0, row1, "VectorCoefficientForm", "patch")
@@ -1063,7 +1146,7 @@ class VectorCoefficientForm(object):
         return _dev.assemble_coef_matrix(pts.verts, pts.p, pts.cp, _dev.coef_block(pts.verts, coef, int(i), int(j), pts.nq), nq=pts.nq)
 
     def assemble_matrix(self, V, row0=None, row1=None):
-        g, nF = _vector_form_scope(self.geometry, V, "VectorCoefficientForm")
+        g, nF = _point_scope(self.geometry, V, "VectorCoefficientForm", "vector")
         _whole_rows(nF * g.num_nodes(), row0, row1, "VectorCoefficientForm", "patch")
         pts, coef = self._transformed(V)
         return _dev.assemble_coef_blocks(pts.verts, pts.p, pts.cp, coef, nq=pts.nq)
@@ -1087,15 +1170,10 @@ def _field_loads(pts, n, nF, s, F, rational):
 
 
 def _field_values(pts, f, nF, who, scale=1.0):
-    """nF DeviceVectors of the components of a vector field at the points: a callable ``x -> [npts, nF]``, an array of
-    that shape, or nF numbers"""
-    v = numpy.asarray(f(pts.x) if callable(f) else f, dtype=numpy.float64)
-    if v.shape == (nF,):
-        v = numpy.tile(v, (pts.npts, 1))
-    if v.shape != (pts.npts, nF):
-        raise ValueError("%s: an array of shape %s for %d points and %d fields; expected (%d, %d)"
-                         % (who, v.shape, pts.npts, nF, pts.npts, nF))
-    return [_dev.DeviceVector(data=numpy.ascontiguousarray(scale * v[:, c])) for c in range(nF)]
+    """nF DeviceVectors of the components of a vector field at the points: a callable ``x -> [npts, nF]`` (on a face also
+    of ``(x, n)``), an array of that shape, or nF numbers"""
+    v = scale * point_block(_on_points(f, pts), pts.npts, (nF,), who=who)
+    return [_dev.DeviceVector(data=v[c * pts.npts:(c + 1) * pts.npts]) for c in range(nF)]
 
 
 class VectorLoadForm(object):
@@ -1113,25 +1191,14 @@ class VectorLoadForm(object):
 
     def assemble_vector(self, V, row0=None, row1=None):
         who = "VectorLoadForm"
-        g, nF = _vector_form_scope(self.geometry, V, who)
+        g, nF = _point_scope(self.geometry, V, who, "vector")
         n = g.num_nodes()
         _whole_rows(nF * n, row0, row1, who, "patch")
         pts = _vector_points(self.geometry, self.nq, who)
 
         def static():
             s = _field_values(pts, self.f, nF, who + ": f") if self.f is not None else None
-            F = None
-            if isinstance(self.flux, _dev.DeviceVector):
-                F = self.flux
-                if F.size() != nF * pts.nsd * pts.npts:
-                    raise ValueError("%s: flux: %d values given, expected nF nsd npts = %d" % (who, F.size(), nF * pts.nsd * pts.npts))
-            elif self.flux is not None:
-                v = numpy.asarray(self.flux(pts.x) if callable(self.flux) else self.flux, dtype=numpy.float64)
-                if v.shape != (pts.npts, nF, pts.nsd):
-                    raise ValueError("%s: flux: an array of shape %s for %d points; expected (%d, %d, %d)"
-                                     % (who, v.shape, pts.npts, pts.npts, nF, pts.nsd))
-                F = _dev.DeviceVector(data=numpy.ascontiguousarray(v.transpose(1, 2, 0)).ravel())
-            return s, F
+            return s, (_point_data(self.flux, pts, (nF, pts.nsd), who + ": flux") if self.flux is not None else None)
         s, F = _per_points(self, "_static", pts, static)
         return _field_loads(pts, n, nF, s, F, self.rational)
 
@@ -1163,23 +1230,16 @@ class HyperelasticResidual(object):
                              "object with host(F) -> (P, A, psi)" % (material,))
         self.u, self.geometry, self.material, self.builtin = u, geometry, material, builtin
         self.body_force, self.nq, self.rational = body_force, nq, bool(rational)
+        self._host_symmetric = False
 
     def grad_u(self, V):
         """(points, node grid, nF, DeviceVector with d u_i / d x_K at (i nsd + K) npts + q)"""
         who = "HyperelasticResidual"
-        g, nF = _vector_form_scope(self.geometry, V, who)
+        g, nF = _point_scope(self.geometry, V, who, "vector")
         pts = _vector_points(self.geometry, self.nq, who)
-        n = g.num_nodes()
-        uv = self.u.vector() if hasattr(self.u, "vector") else self.u
-        if uv.size() != nF * n:
-            raise ValueError("%s: u holds %d nodal values, the space has %d fields of %d" % (who, uv.size(), nF, n))
-        size = pts.nsd * pts.npts
-        H, ui = _dev.DeviceVector(nF * size, zero=False), _dev.DeviceVector(n, zero=False)
-        for i in range(nF):
-            _dev.vec_copy_range(ui, 0, uv, i * n, n)
-            _, gi = _dev.quad_eval(pts.verts, pts.p, pts.cp, ui, grad=True, nq=pts.nq, rational=self.rational)
-            _dev.vec_copy_range(H, i * size, gi, 0, size)
-        return pts, g, nF, H
+        uv = _nodal_vector(self.u, nF, g.num_nodes(), who)
+        grad = lambda ui: _dev.quad_eval(pts.verts, pts.p, pts.cp, ui, grad=True, nq=pts.nq, rational=self.rational)[1]
+        return pts, g, nF, _field_by_field(uv, nF, g.num_nodes(), grad, pts.nsd * pts.npts)
 
     def law(self, V, stress=True, tangent=False, energy=False):
         """(points, node grid, nF, P, A, psi) at the current state, as DeviceVectors (None where not asked for)"""
@@ -1192,21 +1252,18 @@ class HyperelasticResidual(object):
                 raise RuntimeError("HyperelasticResidual: %d quadrature points with J <= 0 (smallest J = %g): %s is not "
                                    "defined there" % (nbad, jmin, type(m).__name__))
             return pts, g, nF, P, A, psi
-        F = numpy.ascontiguousarray(H.get_local().reshape(nsd, nsd, npts).transpose(2, 0, 1)) + numpy.eye(nsd)
-        out = self.material.host(F)
-        if not isinstance(out, tuple) or len(out) != 3:
-            raise ValueError("HyperelasticResidual: material.host(F) returns (P, A, psi)")
-        Ph, Ah, psih = (numpy.asarray(o, dtype=numpy.float64) for o in out)
-        if Ph.shape != (npts, nsd, nsd) or Ah.shape != (npts, nsd, nsd, nsd, nsd) or psih.shape != (npts,):
-            raise ValueError("HyperelasticResidual: material.host(F) returned shapes %s, %s, %s for %d points in %d-D"
-                             % (Ph.shape, Ah.shape, psih.shape, npts, nsd))
-        self._host_symmetric = _same_bits(Ah, Ah.transpose(0, 3, 4, 1, 2))
-        P = _dev.DeviceVector(data=numpy.ascontiguousarray(Ph.transpose(1, 2, 0)).ravel()) if stress else None
-        return pts, g, nF, P, (_tangent_to_device(Ah) if tangent else None), (_dev.DeviceVector(data=psih) if energy else None)
+        F = point_unblock(H.get_local(), npts, (nsd, nsd)) + numpy.eye(nsd)
+        Ph, Ah, psih = _law_result(self.material.host(F), "HyperelasticResidual", "material.host(F)", "(P, A, psi)",
+                                   [(npts, nsd, nsd), (npts, nsd, nsd, nsd, nsd), (npts,)])
+        P = _point_data(Ph, pts, (nsd, nsd), "HyperelasticResidual: P") if stress else None
+        A = None
+        if tangent:
+            A, self._host_symmetric = _point_data(Ah, pts, (nsd,) * 4, "HyperelasticResidual: A", _BLOCK_ORDER, _MAJOR_SWAP)
+        return pts, g, nF, P, A, (_dev.DeviceVector(data=psih) if energy else None)
 
     def assemble_vector(self, V, row0=None, row1=None):
         who = "HyperelasticResidual"
-        g, nF = _vector_form_scope(self.geometry, V, who)
+        g, nF = _point_scope(self.geometry, V, who, "vector")
         _whole_rows(nF * g.num_nodes(), row0, row1, who, "patch")
         pts, g, nF, P, _, _ = self.law(V)
         s = None
@@ -1224,57 +1281,18 @@ class HyperelasticResidual(object):
         return _HyperelasticTangent(self)
 
 
-class _HyperelasticTangent(object):
-    """``symmetric``: True for a built-in material (the tangent derives from an energy: major symmetry by the law); for a host
-    law that of the last assembled tangent and False before the first assembly (see ``_QuasilinearTangent``)."""
+class _HyperelasticTangent(_LawTangent):
+    _form_class = VectorCoefficientForm
 
-    def __init__(self, res):
-        self.res, self.geometry, self.symmetric = res, res.geometry, bool(res.builtin)
+    def _data(self, V):
+        return self.res.law(V, stress=False, tangent=True)[4]
 
-    def _form(self, V):
-        res = self.res
-        pts, g, nF, _, A, _ = res.law(V, stress=False, tangent=True)
-        form = VectorCoefficientForm(res.geometry, A, nq=res.nq, rational=res.rational)
-        form._symmetric_hint = True if res.builtin else bool(res._host_symmetric)
-        if not res.builtin:
-            self.symmetric = bool(res._host_symmetric)
-        return form
-
-    def assemble_block(self, V, i, j, row0=None, row1=None):
-        g, nF = _vector_form_scope(self.res.geometry, V, "HyperelasticResidual.tangent")
-        _whole_rows(g.num_nodes(), row0, row1, "HyperelasticResidual.tangent", "patch")
-        return self._form(V).assemble_block(V, i, j)
-
-    def assemble_matrix(self, V, row0=None, row1=None):
-        g, nF = _vector_form_scope(self.res.geometry, V, "HyperelasticResidual.tangent")
-        _whole_rows(nF * g.num_nodes(), row0, row1, "HyperelasticResidual.tangent", "patch")
-        return self._form(V).assemble_matrix(V)
+    def _rows(self, V, row0, row1, block):
+        g, nF = _point_scope(self.res.geometry, V, "HyperelasticResidual.tangent", "vector")
+        _whole_rows((1 if block else nF) * g.num_nodes(), row0, row1, "HyperelasticResidual.tangent", "patch")
 
 
 # ---- second-derivative point forms (csrc/tg_jet.hip): spline.parametricGrad of the reference and its derivative ------------
-def _jet_form_scope(geometry, V, who):
-    """(node grid, nF, nJ) of a space the second-derivative point forms serve: nF >= 1 fields on one continuous Q_p node
-    grid of a patch with d = 1, 2 and nsd >= d, dofs field after field; refuses everything else with the reason.  An
-    ExtractedSpline says itself what it covers (``_jet_scope``)."""
-    if geometry is None:
-        raise ValueError("%s: point data live on a mapped patch (geometry=...)" % who)
-    scope = getattr(geometry, "_jet_scope", None)
-    if scope is not None:
-        scope(who)
-    _fields_of_the_patch(geometry, who)
-    g = _shared_grid(V)
-    if g is None:
-        raise NotImplementedError("%s: the fields of the space must share one continuous Q_p node grid of a tensor-product "
-                                  "patch (compatible, FieldList, multi-patch, T-spline and DG spaces are not supported)" % who)
-    d, nsd = g.dim(), len(geometry.cpFuncs) - 1
-    if d not in (1, 2):
-        raise NotImplementedError("%s: d = %d parametric directions; second-derivative point forms are provided for curves "
-                                  "and surfaces (d = 1, 2)" % (who, d))
-    if nsd < d:
-        raise NotImplementedError("%s: nsd = %d physical directions on a patch of d = %d parametric ones" % (who, nsd, d))
-    return g, len(V.grids), _dev.jet_size(d)
-
-
 class VectorJetCoefficientForm(object):
     """a(u, v) = sum_q wdet_q sum_ij (jet v_i)^T T_ij (jet u_j) on the mapped patch: point data acting on the JETS of trial and
     test functions -- value, first and second derivatives (order 00, 01, 11) with respect to the patch's parametric
@@ -1308,28 +1326,14 @@ class VectorJetCoefficientForm(object):
 
     def coefficients(self, V):
         """(points, nF, T as a DeviceVector in the block layout, symmetric): computed once per set of points"""
-        g, nF, nJ = _jet_form_scope(self.geometry, V, self._who)
+        g, nF, nJ = _point_scope(self.geometry, V, self._who, "jet")
         pts = _vector_points(self.geometry, self.nq, self._who)
         return _per_points(self, "_static", pts, lambda: self._static_coefficients(pts, nF, nJ))
 
     def _static_coefficients(self, pts, nF, nJ):
-        who, npts = self._who, pts.npts
-        if isinstance(self.T, _dev.DeviceVector):
-            T = self.T
-            if T.size() != nF * nF * nJ * nJ * npts:
-                raise ValueError("%s: %d values given, expected nF^2 nJ^2 npts = %d" % (who, T.size(), nF * nF * nJ * nJ * npts))
-            if self._symmetric_hint is not None:
-                return pts, nF, T, bool(self._symmetric_hint)
-            h = T.get_local().reshape(nF, nF, nJ, nJ, npts)
-            return pts, nF, T, _same_bits(h, h.transpose(1, 0, 3, 2, 4))
-        v = self._shape(numpy.asarray(self.T(pts.x) if callable(self.T) else self.T, dtype=numpy.float64), nF, nJ)
-        if v.shape == (nF, nJ, nF, nJ):
-            v = numpy.tile(v, (npts, 1, 1, 1, 1))
-        if v.shape != (npts, nF, nJ, nF, nJ):
-            raise ValueError("%s: an array of shape %s for %d points; expected (%d, %d, %d, %d, %d)"
-                             % (who, v.shape, npts, npts, nF, nJ, nF, nJ))
-        T = _dev.DeviceVector(data=numpy.ascontiguousarray(v.transpose(1, 3, 2, 4, 0)).ravel())
-        return pts, nF, T, _same_bits(v, v.transpose(0, 3, 4, 1, 2))
+        T, sym = _point_data(self.T, pts, (nF, nJ, nF, nJ), self._who, _BLOCK_ORDER, _MAJOR_SWAP, hint=self._symmetric_hint,
+                             pre=lambda v: self._shape(v, nF, nJ))
+        return pts, nF, T, sym
 
     @property
     def symmetric(self):
@@ -1337,7 +1341,7 @@ class VectorJetCoefficientForm(object):
 
     def assemble_block(self, V, i, j, row0=None, row1=None):
         """block (i, j): test field i, trial field j (all rows of the field)"""
-        g, nF, nJ = _jet_form_scope(self.geometry, V, self._who)
+        g, nF, nJ = _point_scope(self.geometry, V, self._who, "jet")
         if not (0 <= int(i) < nF and 0 <= int(j) < nF):
             raise ValueError("%s: block (%r, %r) of a %d-field space" % (self._who, i, j, nF))
         _whole_rows(g.num_nodes(), row0, row1, self._who, "patch")
@@ -1349,7 +1353,7 @@ class VectorJetCoefficientForm(object):
         return _dev.assemble_jet_blocks(pts.verts, pts.p, pts.cp, coef, 1, nq=pts.nq)
 
     def assemble_matrix(self, V, row0=None, row1=None):
-        g, nF, nJ = _jet_form_scope(self.geometry, V, self._who)
+        g, nF, nJ = _point_scope(self.geometry, V, self._who, "jet")
         _whole_rows(nF * g.num_nodes(), row0, row1, self._who, "patch")
         pts, nF, T, _ = self.coefficients(V)
         coef = _dev.jet_transform(pts.verts, pts.p, pts.cp, T, nF * nF, nq=pts.nq, rational=self.rational)
@@ -1391,20 +1395,10 @@ class VectorJetLoadForm(object):
         return v
 
     def point_values(self, pts, nF, nJ):
-        who, npts = self._who, pts.npts
-        if isinstance(self.s, _dev.DeviceVector):
-            if self.s.size() != nF * nJ * npts:
-                raise ValueError("%s: %d values given, expected nF nJ npts = %d" % (who, self.s.size(), nF * nJ * npts))
-            return self.s
-        v = self._shape(numpy.asarray(self.s(pts.x) if callable(self.s) else self.s, dtype=numpy.float64), nF, nJ)
-        if v.shape == (nF, nJ):
-            v = numpy.tile(v, (npts, 1, 1))
-        if v.shape != (npts, nF, nJ):
-            raise ValueError("%s: an array of shape %s for %d points; expected (%d, %d, %d)" % (who, v.shape, npts, npts, nF, nJ))
-        return _dev.DeviceVector(data=numpy.ascontiguousarray(v.transpose(1, 2, 0)).ravel())
+        return _point_data(self.s, pts, (nF, nJ), self._who, pre=lambda v: self._shape(v, nF, nJ))
 
     def assemble_vector(self, V, row0=None, row1=None):
-        g, nF, nJ = _jet_form_scope(self.geometry, V, self._who)
+        g, nF, nJ = _point_scope(self.geometry, V, self._who, "jet")
         _whole_rows(nF * g.num_nodes(), row0, row1, self._who, "patch")
         pts = _vector_points(self.geometry, self.nq, self._who)
         s = _per_points(self, "_static", pts, lambda: self.point_values(pts, nF, nJ))
@@ -1587,37 +1581,24 @@ class ShellResidual(object):
 
     def _force_jets(self, x):
         f = self.body_force
-        fv = numpy.asarray(f(x) if callable(f) else f, dtype=numpy.float64)
-        if fv.shape == (3,):
-            fv = numpy.tile(fv, (x.shape[0], 1))
-        if fv.shape != (x.shape[0], 3):
-            raise ValueError("ShellResidual: body_force: an array of shape %s for %d points; expected (%d, 3)"
-                             % (fv.shape, x.shape[0], x.shape[0]))
         s = numpy.zeros((x.shape[0], 3, 6))
-        s[:, :, 0] = fv
+        s[:, :, 0] = point_array(f(x) if callable(f) else f, x.shape[0], (3,), "ShellResidual: body_force")
         return s
 
     def jets(self, V):
         """(points, node grid, Xjet, ujet): the jets of the reference surface and of the three displacement fields as
         DeviceVectors of 18 npts values (component alpha of coordinate / field c at (6 c + alpha) npts + q)"""
         who = "ShellResidual"
-        g, nF, nJ = _jet_form_scope(self.geometry, V, who)
+        g, nF, nJ = _point_scope(self.geometry, V, who, "jet")
         nsd = len(self.geometry.cpFuncs) - 1
         if g.dim() != 2 or nsd != 3 or nF != 3:
             raise NotImplementedError("%s: a shell is a surface in space with a displacement of three fields (d = %d, nsd = %d, "
                                       "nFields = %d)" % (who, g.dim(), nsd, nF))
         pts = _vector_points(self.geometry, self.nq, who)
-        n = g.num_nodes()
-        uv = self.u.vector() if hasattr(self.u, "vector") else self.u
-        if uv.size() != nF * n:
-            raise ValueError("%s: u holds %d nodal values, the space has %d fields of %d" % (who, uv.size(), nF, n))
+        uv = _nodal_vector(self.u, nF, g.num_nodes(), who)
         X = _per_points(self, "_Xjet", pts, lambda: _dev.quad_geometry_jet(pts.verts, pts.p, pts.cp, nq=pts.nq))
-        size = nJ * pts.npts
-        U, ui = _dev.DeviceVector(nF * size, zero=False), _dev.DeviceVector(n, zero=False)
-        for i in range(nF):
-            _dev.vec_copy_range(ui, 0, uv, i * n, n)
-            _dev.vec_copy_range(U, i * size, _dev.quad_jet(pts.verts, pts.p, pts.cp, ui, nq=pts.nq, rational=self.rational), 0, size)
-        return pts, g, X, U
+        jet = lambda ui: _dev.quad_jet(pts.verts, pts.p, pts.cp, ui, nq=pts.nq, rational=self.rational)
+        return pts, g, X, _field_by_field(uv, nF, g.num_nodes(), jet, nJ * pts.npts)
 
     def law(self, V, load=True, tangent=False, energy=False):
         """(points, node grid, s, T, psi) at the current state, as DeviceVectors in the layouts of ``tg_jet_load_transform``
@@ -1630,26 +1611,21 @@ class ShellResidual(object):
             if nbad > 0:
                 raise RuntimeError("ShellResidual: %d quadrature points with a degenerate surface normal" % nbad)
             return pts, g, s, T, psi
-        Xh = numpy.ascontiguousarray(X.get_local().reshape(3, 6, npts).transpose(2, 0, 1))
-        Uh = numpy.ascontiguousarray(U.get_local().reshape(3, 6, npts).transpose(2, 0, 1))
+        Xh, Uh = point_unblock(X.get_local(), npts, (3, 6)), point_unblock(U.get_local(), npts, (3, 6))
         nbad = int(numpy.sum(KirchhoffLoveSVK.degenerate(Xh, Uh)))
         if nbad > 0:
             raise RuntimeError("ShellResidual: %d quadrature points with a degenerate surface normal" % nbad)
-        out = self.material.host(Xh, Uh)
-        if not isinstance(out, tuple) or len(out) != 3:
-            raise ValueError("ShellResidual: material.host(Xjet, ujet) returns (psi, s, T)")
-        psih, sh, Th = (numpy.asarray(o, dtype=numpy.float64) for o in out)
-        if psih.shape != (npts,) or sh.shape != (npts, 3, 6) or Th.shape != (npts, 3, 6, 3, 6):
-            raise ValueError("ShellResidual: material.host returned shapes %s, %s, %s for %d points"
-                             % (psih.shape, sh.shape, Th.shape, npts))
-        self._host_symmetric = _same_bits(Th, Th.transpose(0, 3, 4, 1, 2))
-        s = _dev.DeviceVector(data=numpy.ascontiguousarray(sh.transpose(1, 2, 0)).ravel()) if load else None
-        T = _dev.DeviceVector(data=numpy.ascontiguousarray(Th.transpose(1, 3, 2, 4, 0)).ravel()) if tangent else None
+        psih, sh, Th = _law_result(self.material.host(Xh, Uh), "ShellResidual", "material.host(Xjet, ujet)", "(psi, s, T)",
+                                   [(npts,), (npts, 3, 6), (npts, 3, 6, 3, 6)])
+        s = _point_data(sh, pts, (3, 6), "ShellResidual: s") if load else None
+        T = None
+        if tangent:
+            T, self._host_symmetric = _point_data(Th, pts, (3, 6, 3, 6), "ShellResidual: T", _BLOCK_ORDER, _MAJOR_SWAP)
         return pts, g, s, T, (_dev.DeviceVector(data=psih) if energy else None)
 
     def assemble_vector(self, V, row0=None, row1=None):
         who = "ShellResidual"
-        g, nF, nJ = _jet_form_scope(self.geometry, V, who)
+        g, nF, nJ = _point_scope(self.geometry, V, who, "jet")
         _whole_rows(nF * g.num_nodes(), row0, row1, who, "patch")
         pts, g, s, _, _ = self.law(V)
         r = VectorJetLoadForm(s, self.geometry, nq=self.nq, rational=self.rational).assemble_vector(V)
@@ -1667,28 +1643,11 @@ class ShellResidual(object):
         return _ShellTangent(self)
 
 
-class _ShellTangent(object):
-    """``symmetric``: True for ``KirchhoffLoveSVK`` (the tangent derives from an energy: major symmetry by the law, in the
-    matrix to rounding); for another host law that of the last assembled tangent and False before the first assembly (see
-    ``_QuasilinearTangent``)."""
+class _ShellTangent(_LawTangent):
+    _form_class = VectorJetCoefficientForm
 
-    def __init__(self, res):
-        self.res, self.geometry, self.symmetric = res, res.geometry, bool(res.builtin)
-
-    def _form(self, V):
-        res = self.res
-        pts, g, _, T, _ = res.law(V, load=False, tangent=True)
-        form = VectorJetCoefficientForm(res.geometry, T, nq=res.nq, rational=res.rational)
-        form._symmetric_hint = True if res.builtin else bool(res._host_symmetric)
-        if not res.builtin:
-            self.symmetric = bool(res._host_symmetric)
-        return form
-
-    def assemble_block(self, V, i, j, row0=None, row1=None):
-        return self._form(V).assemble_block(V, i, j, row0, row1)
-
-    def assemble_matrix(self, V, row0=None, row1=None):
-        return self._form(V).assemble_matrix(V, row0, row1)
+    def _data(self, V):
+        return self.res.law(V, load=False, tangent=True)[3]
 
 
 # ---- boundary integrals on a mapped patch (csrc/tg_boundary.hip): spline.ds and spline.n of the reference -----------------
@@ -1744,10 +1703,7 @@ def _need_boundary_geometry(who, geometry):
 
 def _face_grid(V, who):
     """(node grid, number of fields) of a space whose fields share one CG node grid"""
-    g = _shared_grid(V)
-    if g is None:
-        raise NotImplementedError("%s: the fields of the space must share one continuous Q_p node grid of a tensor-product "
-                                  "patch" % who)
+    g = _one_shared_grid(V, who)
     if g.dim() not in (2, 3):
         raise NotImplementedError("%s: faces are provided for 2-D and 3-D patches" % who)
     return g, len(V.grids)
@@ -1788,7 +1744,7 @@ class FacePoints(QuadraturePoints):
     @property
     def n(self):
         if self._n is None:
-            self._n = numpy.ascontiguousarray(self.normals.get_local().reshape(self.nsd, self.npts).T)
+            self._n = point_unblock(self.normals.get_local(), self.npts, (self.nsd,))
         return self._n
 
     def values(self, f, who="f"):
@@ -1867,13 +1823,7 @@ class BoundaryLoadForm(object):
     def _components(self, pts, f, nF):
         if nF == 1:
             return [_face_values(pts, f, "BoundaryLoadForm")]
-        v = numpy.asarray((f(pts.x, pts.n) if _argcount(f) >= 2 else f(pts.x)) if callable(f) else f, dtype=numpy.float64)
-        if v.shape == (nF,):
-            v = numpy.tile(v, (pts.npts, 1))
-        if v.shape != (pts.npts, nF):
-            raise ValueError("BoundaryLoadForm: an array of shape %s for %d points and %d fields; expected (%d, %d)"
-                             % (v.shape, pts.npts, nF, pts.npts, nF))
-        return [_dev.DeviceVector(data=numpy.ascontiguousarray(v[:, c])) for c in range(nF)]
+        return _field_values(pts, f, nF, "BoundaryLoadForm")
 
     def assemble_vector(self, V, row0=None, row1=None):
         g, nF = _face_grid(V, "BoundaryLoadForm")
