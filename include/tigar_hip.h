@@ -728,9 +728,19 @@ int tg_quad_load_jet(const tg_patch_t *patch, int nF, tg_vec_t s_t, tg_vec_t out
  * T_out = d^2 psi / d jet(u)^2: 324 npts values, T_ij^{alpha beta} at ((3 i + j) 36 + 6 alpha + beta) npts + q, the layout
  * tg_jet_transform reads with nblk = 9.  Any output may be null; the same subsets give the same bits.
  * A point with |X_,1 x X_,2| or |x_,1 x x_,2| below 1e-14 |X_,1| |X_,2| writes nothing; *nbad counts those points (integer
- * atomics only).  Synchronises the stream. */
+ * atomics only).  Synchronises the stream.
+ * kind 1, params = {mu, thickness, n_thickness} (n_thickness = 1, 2, 3 or 4 as a double): the incompressible neo-Hookean shell of
+ * demos/kl-shell-hyper/kl-hyper.py:98-215, psi = sum_k w_k mu/2 (tr C_2D + 1 / det C_2D - 3)(xi_k) with the Gauss rule of
+ * n_thickness points on (-h/2, h/2), C_2D = I + R (gm - Gm) R^T from the truncated metrics Gm = A - 2 xi B, gm = a - 2 xi b and
+ * the local Cartesian frame of the reference at xi.  Same outputs and layouts; a point is also counted and left alone when
+ * det Gm <= 0 or det C_2D <= 0 at one of its thickness points. */
 int tg_shell_points(int kind, const double *params, int64_t npts, tg_vec_t Xjet, tg_vec_t ujet, tg_vec_t s_out, tg_vec_t T_out,
                     tg_vec_t psi_out, int64_t *nbad);
+/* The follower pressure of kl-hyper.py:231 per unit reference area, -P (x_,1 x x_,2) . v / |X_,1 x X_,2|, ADDED to the outputs of
+ * tg_shell_points (same layouts; either may be null): s_i^0 += -P (x_,1 x x_,2)_i / J_A,  T_ij^{0,1} += -(P / J_A) eps_ijk x_,2k,
+ * T_ij^{0,2} += (P / J_A) eps_ijk x_,1k -- no transposed entries: the tangent is not symmetric.  A point whose reference normal is
+ * below the floor of tg_shell_points is left alone (the law has counted it).  Does not synchronise. */
+int tg_shell_pressure_points(int64_t npts, double pressure, tg_vec_t Xjet, tg_vec_t ujet, tg_vec_t s_inout, tg_vec_t T_inout);
 
 /* ---- boundary integrals on the same patches (csrc/tg_boundary.hip): the boundary measure and the mapped normal of the
  * reference's ExtractedSpline (spline.ds, spline.n; tIGAr/common.py:931-939, calculusUtils.py:37-52, 71-80).  d = 2, 3,

@@ -247,6 +247,7 @@ PROTOTYPES = {
     "tg_assemble_jet_blocks": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, handle, C.POINTER(handle)]),
     "tg_quad_load_jet": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, handle, handle]),
     "tg_shell_points": (C.c_int, [C.c_int, c_f64p, C.c_int64, handle, handle, handle, handle, handle, c_i64p]),
+    "tg_shell_pressure_points": (C.c_int, [C.c_int64, C.c_double, handle, handle, handle, handle]),
     "tg_face_points": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, handle]),
     "tg_face_eval": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, handle]),
     "tg_face_load": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle]),

@@ -101,6 +101,31 @@ def near(a, b, eps=DOLFIN_EPS):
     return abs(a - b) <= eps
 
 
+_GAUSS_RULES = {
+    1: ((0.0,), (2.0,)),
+    2: ((-0.5773502691896257645091488, 0.5773502691896257645091488), (1.0, 1.0)),
+    3: ((-0.77459666924148337703585308, 0.0, 0.77459666924148337703585308),
+        (0.55555555555555555555555556, 0.88888888888888888888888889, 0.55555555555555555555555556)),
+    4: ((-0.86113631159405257524, -0.33998104358485626481, 0.33998104358485626481, 0.86113631159405257524),
+        (0.34785484513745385736, 0.65214515486254614264, 0.65214515486254614264, 0.34785484513745385736)),
+}
+
+
+def getQuadRule(n):
+    """(points, weights) of the ``n``-point Gauss rule on (-1, 1) as lists of plain floats, n = 1..4
+    (tIGAr/calculusUtils.py:412-457; through-thickness integration of the Kirchhoff-Love shell laws)"""
+    if n not in _GAUSS_RULES:
+        raise ValueError("getQuadRule: %r quadrature points; rules of 1 to 4 points are provided" % (n,))
+    xi, w = _GAUSS_RULES[n]
+    return list(xi), list(w)
+
+
+def getQuadRuleInterval(n, L):
+    """the ``n``-point rule on (-L/2, L/2) (tIGAr/calculusUtils.py:459-470)"""
+    xi_hat, w_hat = getQuadRule(n)
+    return [L * x / 2.0 for x in xi_hat], [L * w / 2.0 for w in w_hat]
+
+
 # ---- FE-side stand-ins ------------------------------------------------------------------
 class TensorNodeGrid(object):
     """The "mesh" of the extraction: a tensor-product grid of Lagrange nodes on the knot

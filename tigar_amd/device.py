@@ -1343,15 +1343,36 @@ def shell_points(kind, E, nu, thickness, Xjet, ujet, load=True, tangent=False, e
     ``ujet`` hold the jets of the reference surface and of the three displacement fields, 18 * npts values each.  Returns
     (s, T, psi, nbad) with the outputs not asked for None; s in the layout of ``jet_load_transform`` (nF = 3), T in that of
     ``jet_transform`` (nblk = 9)."""
+    return shell_law_points(kind, (E, nu, thickness), Xjet, ujet, load, tangent, energy)
+
+
+SHELL_KINDS = {"svk": 0, "hyper": 1}
+
+
+def shell_law_points(kind, params, Xjet, ujet, load=True, tangent=False, energy=False):
+    """``shell_points`` for any kind: ``params`` the three numbers of the kind -- 0: (E, nu, thickness); 1, the incompressible
+    neo-Hookean law integrated through the thickness: (mu, thickness, n_thickness), n_thickness = 1..4.  ``nbad`` counts the
+    inadmissible points (nothing is written there)."""
     npts = Xjet.size() // 18
     s = DeviceVector(18 * npts, zero=False) if load else None
     T = DeviceVector(324 * npts, zero=False) if tangent else None
     psi = DeviceVector(npts, zero=False) if energy else None
-    par = _f64([float(E), float(nu), float(thickness)])
+    par = _f64([float(v) for v in params])
+    if par.size != 3:
+        raise ValueError("shell_law_points: three parameters per kind, %d given" % par.size)
     nbad = C.c_int64(0)
     check(_lib.lib().tg_shell_points(int(kind), _p(par, c_f64p), npts, Xjet._h, ujet._h, _h_or_none(s), _h_or_none(T),
                                      _h_or_none(psi), C.byref(nbad)), "tg_shell_points")
     return s, T, psi, int(nbad.value)
+
+
+def shell_pressure_points(pressure, Xjet, ujet, s=None, T=None):
+    """Adds the follower pressure -P (x_,1 x x_,2) / |X_,1 x X_,2| to the law's outputs in place (``tg_shell_pressure_points``):
+    the load into the value slots of ``s``, its derivative into the (value, first-derivative) entries of ``T``; either may be
+    None."""
+    npts = Xjet.size() // 18
+    check(_lib.lib().tg_shell_pressure_points(npts, float(pressure), Xjet._h, ujet._h, _h_or_none(s), _h_or_none(T)),
+          "tg_shell_pressure_points")
 
 
 MATERIAL_KINDS = {"linear": 0, "svk": 1, "neohookean": 2}

@@ -1425,6 +1425,119 @@ def _cross(a, b):
                         a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], axis=1)
 
 
+_KL_SLOT = {(0, 0): 3, (0, 1): 4, (1, 0): 4, (1, 1): 5}            # second-derivative slots of the jet
+
+
+def _kl_dot(a, b):
+    return numpy.einsum("qc,qc->q", a, b)
+
+
+def _kl_jets(who, Xjet, ujet):
+    """the two jets in their common float dtype, after the shape check: (dtype, Xjet, ujet)"""
+    Xjet, ujet = numpy.asarray(Xjet), numpy.asarray(ujet)
+    dt = numpy.result_type(Xjet.dtype, ujet.dtype).type
+    Xjet, ujet = Xjet.astype(dt), ujet.astype(dt)
+    npts = Xjet.shape[0]
+    if Xjet.shape != (npts, 3, 6) or ujet.shape != (npts, 3, 6):
+        raise ValueError("%s: jets of shape [npts, 3, 6] (nsd = 3, d = 2); got %s and %s" % (who, Xjet.shape, ujet.shape))
+    return dt, Xjet, ujet
+
+
+def _kl_normal_floor(Xjet, ujet):
+    """mask of the points whose reference or current normal is not defined"""
+    X1, X2 = Xjet[:, :, 1], Xjet[:, :, 2]
+    x1, x2 = X1 + ujet[:, :, 1], X2 + ujet[:, :, 2]
+    nrm = lambda v: numpy.sqrt(numpy.einsum("qc,qc->q", v, v))
+    floor = 1e-14 * nrm(X1) * nrm(X2)
+    return ~((nrm(_cross(X1, X2)) >= floor) & (nrm(_cross(x1, x2)) >= floor))
+
+
+def _kl_surface(jet):
+    """((x_,0, x_,1), unit normal, |x_,0 x x_,1|, metric [q, 2, 2], curvature x_,ab . a_3 [q, 2, 2]) of a configuration"""
+    dot = _kl_dot
+    g1, g2 = jet[:, :, 1], jet[:, :, 2]
+    n = _cross(g1, g2)
+    J = numpy.sqrt(dot(n, n))
+    n3 = n / J[:, None]
+    met = numpy.stack([numpy.stack([dot(g1, g1), dot(g1, g2)], 1), numpy.stack([dot(g1, g2), dot(g2, g2)], 1)], 1)
+    cur = numpy.empty_like(met)
+    for (a, b) in ((0, 0), (0, 1), (1, 0), (1, 1)):
+        cur[:, a, b] = dot(jet[:, :, _KL_SLOT[(a, b)]], n3)
+    return (g1, g2), n3, J, met, cur
+
+
+def _kl_inverse(m):
+    """inverse of symmetric [q, 2, 2] matrices (the entry (0, 1) is read for both off-diagonal places)"""
+    det = m[:, 0, 0] * m[:, 1, 1] - m[:, 0, 1] * m[:, 0, 1]
+    inv = numpy.empty_like(m)
+    inv[:, 0, 0], inv[:, 1, 1], inv[:, 0, 1], inv[:, 1, 0] = m[:, 1, 1] / det, m[:, 0, 0] / det, -m[:, 0, 1] / det, -m[:, 0, 1] / det
+    return inv
+
+
+def _kl_variations(xjet, g, a3, am, nres, mres, quadratic):
+    """(s, T) of an energy psi(eps, kappa) per unit reference area at the configuration ``xjet`` (tangents ``g``, normal
+    ``a3``, metric ``am``) from its resultants n^ab = d psi / d eps_ab, m^ab = d psi / d kappa_ab and ``quadratic(De, Dk)``,
+    the part of T that holds the second derivatives of psi:  T = quadratic + n : D2 eps + m : D2 kappa, with
+    De[q, a, b, i, alpha], Dk[q, a, b, i, alpha] the derivatives of eps_ab, kappa_ab with respect to jet(u)_i^alpha."""
+    dt = xjet.dtype.type
+    npts = xjet.shape[0]
+    half = dt(0.5)
+    slot, ein, dot = _KL_SLOT, numpy.einsum, _kl_dot
+    g1, g2 = g
+    # current contravariant basis and Christoffel symbols Gamma^c_ab = x_,ab . a^c
+    ai = _kl_inverse(am)
+    gup = [ai[:, c, 0, None] * g1 + ai[:, c, 1, None] * g2 for c in range(2)]       # a^c
+    # ---- first variation.  delta eps_ab = sym(delta x_,a . x_,b); delta kappa_ab = -(delta x_,ab - Gamma^c_ab delta x_,c) . a_3
+    s = numpy.zeros((npts, 3, 6), dtype=dt)
+    Gam = numpy.empty((npts, 2, 2, 2), dtype=dt)                   # [q, c, a, b]
+    for a in range(2):
+        for b in range(2):
+            xab = xjet[:, :, slot[(a, b)]]
+            for c in range(2):
+                Gam[:, c, a, b] = dot(xab, gup[c])
+    for a in range(2):
+        for b in range(2):
+            s[:, :, 1 + a] += nres[:, a, b, None] * g[b]
+            s[:, :, slot[(a, b)]] -= mres[:, a, b, None] * a3
+            for c in range(2):
+                s[:, :, 1 + c] += (mres[:, a, b] * Gam[:, c, a, b])[:, None] * a3
+    # ---- second variation
+    De = numpy.zeros((npts, 2, 2, 3, 6), dtype=dt)
+    Dk = numpy.zeros((npts, 2, 2, 3, 6), dtype=dt)
+    for a in range(2):
+        for b in range(2):
+            De[:, a, b, :, 1 + a] += half * g[b]
+            De[:, a, b, :, 1 + b] += half * g[a]
+            Dk[:, a, b, :, slot[(a, b)]] -= a3
+            for c in range(2):
+                Dk[:, a, b, :, 1 + c] += Gam[:, c, a, b, None] * a3
+    T = quadratic(De, Dk)
+    I3 = numpy.eye(3, dtype=dt)
+    for a in range(2):
+        for b in range(2):                                         # n^ab delta x_,a . delta x_,b
+            T[:, :, 1 + a, :, 1 + b] += nres[:, a, b, None, None] * I3
+    # m^ab D2 kappa_ab = -m^ab (w_,ab . D a_3[v] + v_,ab . D a_3[w] + x_,ab . D2 a_3[w, v]) with the variations of the normal
+    #   D a_3[v] = -a^c (a_3 . v_,c),      D a^c[v] = -(a^c . v_,d) a^d + a^cd (a_3 . v_,d) a_3
+    for a in range(2):
+        for b in range(2):
+            sl = slot[(a, b)]
+            for c in range(2):                                     # -m^ab w_,ab . D a_3[v]: row (k, sl), column (i, 1 + c)
+                blk = ein("q,qk,qi->qki", mres[:, a, b], gup[c], a3)
+                T[:, :, sl, :, 1 + c] += blk
+                T[:, :, 1 + c, :, sl] += blk.transpose(0, 2, 1)
+    # with M = m^ab x_,ab:  -M . D2 a_3[w, v] = (M . D a^c[v]) (a_3 . w_,c) + (M . a^c) (D a_3[v] . w_,c)
+    #   = -(M . a^d)(a_3 . w_,c)(a^c . v_,d) + a^cd (M . a_3)(a_3 . w_,c)(a_3 . v_,d) - (M . a^c)(a^d . w_,c)(a_3 . v_,d)
+    # row: w, field i, slot 1 + c; column: v, field j, slot 1 + d
+    Mv = sum(mres[:, a, b, None] * xjet[:, :, slot[(a, b)]] for a in range(2) for b in range(2))
+    M3 = dot(Mv, a3)
+    for c in range(2):
+        for d_ in range(2):
+            Mac, Mad = dot(Mv, gup[c]), dot(Mv, gup[d_])
+            T[:, :, 1 + c, :, 1 + d_] += -ein("q,qi,qj->qij", Mad, a3, gup[c]) + ein("q,qi,qj->qij", ai[:, c, d_] * M3, a3, a3) \
+                - ein("q,qi,qj->qij", Mac, gup[d_], a3)
+    return s, T
+
+
 class KirchhoffLoveSVK(object):
     """St. Venant-Kirchhoff Kirchhoff-Love shell of ``thickness`` h (demos/kl-shell-svk/dynamic-tspline.py:135-212 of the
     reference), d = 2, nsd = nF = 3.  With the reference surface X(xi) and x = X + u:
@@ -1437,115 +1550,180 @@ class KirchhoffLoveSVK(object):
     forms: the first and second variations of a_3, and delta b_ab = (delta x_,ab - Gamma^c_ab delta x_,c) . a_3.
     Degenerate points (|X_,1 x X_,2| or |x_,1 x x_,2| below 1e-14 |X_,1| |X_,2|) raise ``RuntimeError`` naming their number."""
     kind = 0
+    inadmissible = "with a degenerate surface normal"
 
     def __init__(self, E, nu, thickness):
         self.E, self.nu, self.thickness = float(E), float(nu), float(thickness)
 
+    def params(self):
+        """the parameters of ``tg_shell_points`` for this kind"""
+        return (self.E, self.nu, self.thickness)
+
     @staticmethod
     def degenerate(Xjet, ujet):
         """mask of the points whose reference or current normal is not defined"""
-        X1, X2 = Xjet[:, :, 1], Xjet[:, :, 2]
-        x1, x2 = X1 + ujet[:, :, 1], X2 + ujet[:, :, 2]
-        nrm = lambda v: numpy.sqrt(numpy.einsum("qc,qc->q", v, v))
-        floor = 1e-14 * nrm(X1) * nrm(X2)
-        return ~((nrm(_cross(X1, X2)) >= floor) & (nrm(_cross(x1, x2)) >= floor))
+        return _kl_normal_floor(Xjet, ujet)
 
     def host(self, Xjet, ujet):
-        Xjet, ujet = numpy.asarray(Xjet), numpy.asarray(ujet)
-        dt = numpy.result_type(Xjet.dtype, ujet.dtype).type
-        Xjet, ujet = Xjet.astype(dt), ujet.astype(dt)
-        npts = Xjet.shape[0]
-        if Xjet.shape != (npts, 3, 6) or ujet.shape != (npts, 3, 6):
-            raise ValueError("KirchhoffLoveSVK: jets of shape [npts, 3, 6] (nsd = 3, d = 2); got %s and %s" % (Xjet.shape, ujet.shape))
+        dt, Xjet, ujet = _kl_jets("KirchhoffLoveSVK", Xjet, ujet)
         bad = self.degenerate(Xjet, ujet)
         if numpy.any(bad):
             raise RuntimeError("KirchhoffLoveSVK: %d points with a degenerate surface normal" % int(numpy.sum(bad)))
         E, nu, h = dt(self.E), dt(self.nu), dt(self.thickness)
         half, one = dt(0.5), dt(1)
-        slot = {(0, 0): 3, (0, 1): 4, (1, 0): 4, (1, 1): 5}            # second-derivative slots of the jet
         ein = numpy.einsum
-        dot = lambda a, b: ein("qc,qc->q", a, b)
-
-        def surface(jet):
-            g1, g2 = jet[:, :, 1], jet[:, :, 2]
-            n = _cross(g1, g2)
-            J = numpy.sqrt(dot(n, n))
-            n3 = n / J[:, None]
-            met = numpy.stack([numpy.stack([dot(g1, g1), dot(g1, g2)], 1), numpy.stack([dot(g1, g2), dot(g2, g2)], 1)], 1)
-            cur = numpy.empty_like(met)
-            for (a, b) in ((0, 0), (0, 1), (1, 0), (1, 1)):
-                cur[:, a, b] = dot(jet[:, :, slot[(a, b)]], n3)
-            return (g1, g2), n3, J, met, cur
-
-        _, _, _, Am, Bm = surface(Xjet)
+        _, _, _, Am, Bm = _kl_surface(Xjet)
         xjet = Xjet + ujet
-        (g1, g2), a3, _, am, bm = surface(xjet)
-        g = (g1, g2)
+        g, a3, _, am, bm = _kl_surface(xjet)
         # contravariant reference metric and the material tensor
-        detA = Am[:, 0, 0] * Am[:, 1, 1] - Am[:, 0, 1] * Am[:, 0, 1]
-        Ai = numpy.empty_like(Am)
-        Ai[:, 0, 0], Ai[:, 1, 1], Ai[:, 0, 1], Ai[:, 1, 0] = Am[:, 1, 1] / detA, Am[:, 0, 0] / detA, -Am[:, 0, 1] / detA, -Am[:, 0, 1] / detA
+        Ai = _kl_inverse(Am)
         Cm = (E / (one - nu * nu)) * (nu * ein("qab,qcd->qabcd", Ai, Ai) +
                                       half * (one - nu) * (ein("qac,qbd->qabcd", Ai, Ai) + ein("qad,qbc->qabcd", Ai, Ai)))
         eps, kap = half * (am - Am), Bm - bm
         nres = h * ein("qabcd,qcd->qab", Cm, eps)                     # membrane forces  n^ab
         mres = (h * h * h / dt(12)) * ein("qabcd,qcd->qab", Cm, kap)  # bending moments  m^ab
         psi = half * ein("qab,qab->q", nres, eps) + half * ein("qab,qab->q", mres, kap)
-        # current contravariant basis and Christoffel symbols Gamma^c_ab = x_,ab . a^c
-        deta = am[:, 0, 0] * am[:, 1, 1] - am[:, 0, 1] * am[:, 0, 1]
-        ai = numpy.empty_like(am)
-        ai[:, 0, 0], ai[:, 1, 1], ai[:, 0, 1], ai[:, 1, 0] = am[:, 1, 1] / deta, am[:, 0, 0] / deta, -am[:, 0, 1] / deta, -am[:, 0, 1] / deta
-        gup = [ai[:, c, 0, None] * g1 + ai[:, c, 1, None] * g2 for c in range(2)]       # a^c
-        # ---- first variation.  delta eps_ab = sym(delta x_,a . x_,b); delta kappa_ab = -(delta x_,ab - Gamma^c_ab delta x_,c) . a_3
-        s = numpy.zeros((npts, 3, 6), dtype=dt)
-        Gam = numpy.empty((npts, 2, 2, 2), dtype=dt)                   # [q, c, a, b]
-        for a in range(2):
-            for b in range(2):
-                xab = xjet[:, :, slot[(a, b)]]
-                for c in range(2):
-                    Gam[:, c, a, b] = dot(xab, gup[c])
-        for a in range(2):
-            for b in range(2):
-                s[:, :, 1 + a] += nres[:, a, b, None] * g[b]
-                s[:, :, slot[(a, b)]] -= mres[:, a, b, None] * a3
-                for c in range(2):
-                    s[:, :, 1 + c] += (mres[:, a, b] * Gam[:, c, a, b])[:, None] * a3
-        # ---- second variation.  psi = f(eps(jet), kappa(jet)):  T = De^T (h C) De + Dk^T (h^3/12 C) Dk + n : D2 eps + m : D2 kappa
-        # De[q, a, b, i, alpha], Dk[q, a, b, i, alpha]: derivatives of eps_ab, kappa_ab with respect to jet(u)_i^alpha
-        De = numpy.zeros((npts, 2, 2, 3, 6), dtype=dt)
-        Dk = numpy.zeros((npts, 2, 2, 3, 6), dtype=dt)
-        for a in range(2):
-            for b in range(2):
-                De[:, a, b, :, 1 + a] += half * g[b]
-                De[:, a, b, :, 1 + b] += half * g[a]
-                Dk[:, a, b, :, slot[(a, b)]] -= a3
-                for c in range(2):
-                    Dk[:, a, b, :, 1 + c] += Gam[:, c, a, b, None] * a3
-        T = h * ein("qabiA,qabcd,qcdjB->qiAjB", De, Cm, De) + (h * h * h / dt(12)) * ein("qabiA,qabcd,qcdjB->qiAjB", Dk, Cm, Dk)
-        I3 = numpy.eye(3, dtype=dt)
-        for a in range(2):
-            for b in range(2):                                         # n^ab delta x_,a . delta x_,b
-                T[:, :, 1 + a, :, 1 + b] += nres[:, a, b, None, None] * I3
-        # m^ab D2 kappa_ab = -m^ab (w_,ab . D a_3[v] + v_,ab . D a_3[w] + x_,ab . D2 a_3[w, v]) with the variations of the normal
-        #   D a_3[v] = -a^c (a_3 . v_,c),      D a^c[v] = -(a^c . v_,d) a^d + a^cd (a_3 . v_,d) a_3
-        for a in range(2):
-            for b in range(2):
-                sl = slot[(a, b)]
-                for c in range(2):                                     # -m^ab w_,ab . D a_3[v]: row (k, sl), column (i, 1 + c)
-                    blk = ein("q,qk,qi->qki", mres[:, a, b], gup[c], a3)
-                    T[:, :, sl, :, 1 + c] += blk
-                    T[:, :, 1 + c, :, sl] += blk.transpose(0, 2, 1)
-        # with M = m^ab x_,ab:  -M . D2 a_3[w, v] = (M . D a^c[v]) (a_3 . w_,c) + (M . a^c) (D a_3[v] . w_,c)
-        #   = -(M . a^d)(a_3 . w_,c)(a^c . v_,d) + a^cd (M . a_3)(a_3 . w_,c)(a_3 . v_,d) - (M . a^c)(a^d . w_,c)(a_3 . v_,d)
-        # row: w, field i, slot 1 + c; column: v, field j, slot 1 + d
-        Mv = sum(mres[:, a, b, None] * xjet[:, :, slot[(a, b)]] for a in range(2) for b in range(2))
-        M3 = dot(Mv, a3)
-        for c in range(2):
-            for d_ in range(2):
-                Mac, Mad = dot(Mv, gup[c]), dot(Mv, gup[d_])
-                T[:, :, 1 + c, :, 1 + d_] += -ein("q,qi,qj->qij", Mad, a3, gup[c]) + ein("q,qi,qj->qij", ai[:, c, d_] * M3, a3, a3) \
-                    - ein("q,qi,qj->qij", Mac, gup[d_], a3)
+        # psi = f(eps(jet), kappa(jet)):  T = De^T (h C) De + Dk^T (h^3/12 C) Dk + n : D2 eps + m : D2 kappa
+        s, T = _kl_variations(xjet, g, a3, am, nres, mres, lambda De, Dk:
+                              h * ein("qabiA,qabcd,qcdjB->qiAjB", De, Cm, De) + (h * h * h / dt(12)) * ein("qabiA,qabcd,qcdjB->qiAjB", Dk, Cm, Dk))
         return psi, s, T
+
+
+class KirchhoffLoveHyper(object):
+    """Incompressible neo-Hookean Kirchhoff-Love shell of ``thickness`` h, the energy integrated through the thickness with
+    the ``n_thickness``-point rule of ``getQuadRuleInterval`` (demos/kl-shell-hyper/kl-hyper.py:98-215 of the reference),
+    d = 2, nsd = nF = 3.  With A, B, a, b the metrics and curvatures of ``KirchhoffLoveSVK``, at the thickness point xi:
+      Gm = A - 2 xi B,  gm = a - 2 xi b                        the truncated metrics,
+      G_b = A_b + xi d_b A_3 = (I - xi B A^-1)_bd A_d          (Weingarten),   G^a = (Gm^-1)_ab G_b,
+      e_0, e_1: Gram-Schmidt on G_0, G_1,   R_ia = e_i . G^a,   C_2D = I + Chat,  Chat = R (gm - Gm) R^T,
+      psi(xi) = mu/2 (tr C_2D + 1 / det C_2D - 3) = mu/2 (tr Chat - t / (1 + t)),   t = tr Chat + det Chat
+    (the multiplier term of the demo vanishes: C_22 = 1 / det C_2D makes J = 1), psi = sum_k w_k psi(xi_k) per unit
+    reference area.  gm - Gm = 2 (eps + xi kappa) is formed from the strains, so small strains do not cancel.
+    Chat is affine in (eps, kappa) and R depends on the reference alone:
+      d psi(xi) / d Chat = mu/2 (t (2 + t) I - adj Chat) / (1 + t)^2,
+      d2 psi(xi) / d Chat2 = mu/2 (2 adj C (x) adj C / (1 + t)^3 - L / (1 + t)^2),   L = d adj C / d C,
+    pulled back by R to F = d psi(xi) / d gm and H; n = 2 sum w F, m = 2 sum w xi F, D_ee = 4 sum w H, D_ek = 4 sum w xi H,
+    D_kk = 4 sum w xi^2 H, and s, T follow with the kinematic variations of ``KirchhoffLoveSVK``.
+    ``host(Xjet, ujet)`` as there.  ``degenerate``: the points that fail the normal floors of ``KirchhoffLoveSVK`` or have
+    det Gm(xi_k) <= 0 or det C_2D(xi_k) <= 0 at some thickness point."""
+    kind = 1
+    inadmissible = "with a degenerate surface normal, or with det Gm <= 0 or det C_2D <= 0 at a thickness point"
+
+    def __init__(self, mu, thickness, n_thickness=4):
+        from .common import getQuadRuleInterval
+        if n_thickness not in (1, 2, 3, 4):
+            raise ValueError("KirchhoffLoveHyper: n_thickness = %r; rules of 1 to 4 thickness points are provided" % (n_thickness,))
+        self.mu, self.thickness, self.n_thickness = float(mu), float(thickness), int(n_thickness)
+        self.rule = getQuadRuleInterval(self.n_thickness, self.thickness)
+
+    def params(self):
+        """the parameters of ``tg_shell_points`` for this kind"""
+        return (self.mu, self.thickness, float(self.n_thickness))
+
+    @staticmethod
+    def _frame(Am, Bm, Ai, xi):
+        """(R [q, 2, 2], det Gm) at the thickness coordinate xi, from the reference surface alone"""
+        ein = numpy.einsum
+        one = Am.dtype.type(1)
+        Q = -xi * ein("qbc,qcd->qbd", Bm, Ai)
+        Q[:, 0, 0] += one
+        Q[:, 1, 1] += one
+        Gg = ein("qbc,qcd,qed->qbe", Q, Am, Q)                          # G_b . G_e
+        Gm = Am - (xi + xi) * Bm
+        detGm = Gm[:, 0, 0] * Gm[:, 1, 1] - Gm[:, 0, 1] * Gm[:, 0, 1]
+        l0 = numpy.sqrt(Gg[:, 0, 0])
+        Eg = numpy.zeros_like(Am)                                       # e_i . G_b: upper triangular
+        Eg[:, 0, 0], Eg[:, 0, 1] = l0, Gg[:, 0, 1] / l0
+        Eg[:, 1, 1] = numpy.sqrt((Gg[:, 0, 0] * Gg[:, 1, 1] - Gg[:, 0, 1] * Gg[:, 0, 1]) / Gg[:, 0, 0])
+        return ein("qib,qba->qia", Eg, _kl_inverse(Gm)), detGm
+
+    def _through(self, dt, Am, Bm, eps, kap):
+        """yields (xi, w, R, det Gm, Chat, t) per thickness point"""
+        Ai = _kl_inverse(Am)
+        for xi, w in zip(*self.rule):
+            xi, w = dt(xi), dt(w)
+            R, detGm = self._frame(Am, Bm, Ai, xi)
+            Ch = numpy.einsum("qia,qab,qjb->qij", R, dt(2) * (eps + xi * kap), R)
+            tr = Ch[:, 0, 0] + Ch[:, 1, 1]
+            t = tr + (Ch[:, 0, 0] * Ch[:, 1, 1] - Ch[:, 0, 1] * Ch[:, 0, 1])
+            yield xi, w, R, detGm, Ch, tr, t
+
+    def degenerate(self, Xjet, ujet):
+        """mask of the inadmissible points"""
+        dt, Xjet, ujet = _kl_jets("KirchhoffLoveHyper", Xjet, ujet)
+        bad = _kl_normal_floor(Xjet, ujet)
+        with numpy.errstate(all="ignore"):
+            _, _, _, Am, Bm = _kl_surface(Xjet)
+            _, _, _, am, bm = _kl_surface(Xjet + ujet)
+            for _, _, _, detGm, _, _, t in self._through(dt, Am, Bm, dt(0.5) * (am - Am), Bm - bm):
+                bad = bad | ~(detGm > 0) | ~(dt(1) + t > 0)
+        return bad
+
+    def host(self, Xjet, ujet):
+        dt, Xjet, ujet = _kl_jets("KirchhoffLoveHyper", Xjet, ujet)
+        bad = self.degenerate(Xjet, ujet)
+        if numpy.any(bad):
+            raise RuntimeError("KirchhoffLoveHyper: %d inadmissible points (a degenerate surface normal, or det Gm <= 0 or "
+                               "det C_2D <= 0 at a thickness point)" % int(numpy.sum(bad)))
+        npts = Xjet.shape[0]
+        half, one, two, hmu = dt(0.5), dt(1), dt(2), dt(0.5) * dt(self.mu)
+        ein = numpy.einsum
+        _, _, _, Am, Bm = _kl_surface(Xjet)
+        xjet = Xjet + ujet
+        g, a3, _, am, bm = _kl_surface(xjet)
+        eps, kap = half * (am - Am), Bm - bm
+        I2 = numpy.eye(2, dtype=dt)
+        # L = d adj C / d C of a symmetric 2 x 2 matrix: adj C = tr(C) I - C
+        Lh = ein("ij,kl->ijkl", I2, I2) - half * (ein("ik,jl->ijkl", I2, I2) + ein("il,jk->ijkl", I2, I2))
+        psi = numpy.zeros(npts, dtype=dt)
+        nres, mres = numpy.zeros((npts, 2, 2), dtype=dt), numpy.zeros((npts, 2, 2), dtype=dt)
+        Dee, Dek, Dkk = (numpy.zeros((npts, 2, 2, 2, 2), dtype=dt) for _ in range(3))
+        for xi, w, R, _, Ch, tr, t in self._through(dt, Am, Bm, eps, kap):
+            delta = one + t
+            psi += w * hmu * (tr - t / delta)
+            adjh = numpy.empty_like(Ch)
+            adjh[:, 0, 0], adjh[:, 1, 1], adjh[:, 0, 1], adjh[:, 1, 0] = Ch[:, 1, 1], Ch[:, 0, 0], -Ch[:, 0, 1], -Ch[:, 0, 1]
+            Fh = (hmu / (delta * delta))[:, None, None] * ((t * (two + t))[:, None, None] * I2 - adjh)
+            adjC = adjh + I2
+            Hh = (two * hmu / (delta * delta * delta))[:, None, None, None, None] * ein("qij,qkl->qijkl", adjC, adjC) \
+                - (hmu / (delta * delta))[:, None, None, None, None] * Lh
+            F = ein("qia,qij,qjb->qab", R, Fh, R)
+            H = ein("qkc,qld,qabkl->qabcd", R, R, ein("qia,qjb,qijkl->qabkl", R, R, Hh))
+            nres += (two * w) * F
+            mres += (two * w * xi) * F
+            Dee += (dt(4) * w) * H
+            Dek += (dt(4) * w * xi) * H
+            Dkk += (dt(4) * w * xi * xi) * H
+        def quadratic(De, Dk):
+            """De^T D_ee De + De^T D_ek Dk + Dk^T D_ek^T De + Dk^T D_kk Dk, through d n / d jet and d m / d jet"""
+            dn = ein("qabcd,qcdjB->qabjB", Dee, De) + ein("qabcd,qcdjB->qabjB", Dek, Dk)
+            dm = ein("qcdab,qcdjB->qabjB", Dek, De) + ein("qabcd,qcdjB->qabjB", Dkk, Dk)
+            return ein("qabiA,qabjB->qiAjB", De, dn) + ein("qabiA,qabjB->qiAjB", Dk, dm)
+        s, T = _kl_variations(xjet, g, a3, am, nres, mres, quadratic)
+        return psi, s, T
+
+
+def shell_pressure_host(pressure, Xjet, ujet):
+    """The follower pressure of demos/kl-shell-hyper/kl-hyper.py:231 per unit reference area, dWext = -P sqrt(det a / det A)
+    a_3 . v = -P (x_,1 x x_,2) . v / |X_,1 x X_,2|: (s, T) of the jets [npts, 3, 6] in their dtype -- s in the value slot, T in
+    the (value, first-derivative) entries alone, without a transpose: the tangent of a follower load is not symmetric."""
+    dt, Xjet, ujet = _kl_jets("shell_pressure_host", Xjet, ujet)
+    npts = Xjet.shape[0]
+    xjet = Xjet + ujet
+    X1, X2, x1, x2 = Xjet[:, :, 1], Xjet[:, :, 2], xjet[:, :, 1], xjet[:, :, 2]
+    N = _cross(X1, X2)
+    c = -dt(pressure) / numpy.sqrt(_kl_dot(N, N))
+    s = numpy.zeros((npts, 3, 6), dtype=dt)
+    T = numpy.zeros((npts, 3, 6, 3, 6), dtype=dt)
+    s[:, :, 0] = c[:, None] * _cross(x1, x2)
+    for i in range(3):
+        j, k = (i + 1) % 3, (i + 2) % 3           # eps_ijk = +1, eps_ikj = -1
+        # d (x_,1 x x_,2)_i = eps_ijk (dx_,1j x_,2k + x_,1j dx_,2k)
+        T[:, i, 0, j, 1] += c * x2[:, k]
+        T[:, i, 0, k, 1] -= c * x2[:, j]
+        T[:, i, 0, k, 2] += c * x1[:, j]
+        T[:, i, 0, j, 2] -= c * x1[:, k]
+    return s, T
 
 
 class ShellResidual(object):
@@ -1553,31 +1731,49 @@ class ShellResidual(object):
     ``derivative(psi*spline.dx, u)`` of the reference gives for the energy of demos/kl-shell-svk.  The reference surface is the
     patch (d = 2, nsd = 3); ``u`` the displacement ``Function`` on nF = 3 fields of its scalar space, read at assembly time.
 
-    ``material``: ``KirchhoffLoveSVK`` -- evaluated at the points ON THE DEVICE (``tg_shell_points``): the jets, s and the
-    324 npts tangent values never leave it; ``device_law=False`` sends it through its ``host`` method instead -- or any object
-    with ``host(Xjet, ujet) -> (psi, s, T)``, a host law whose arrays are uploaded and go through the same transform and
+    ``material``: ``KirchhoffLoveSVK`` or ``KirchhoffLoveHyper`` -- evaluated at the points ON THE DEVICE (``tg_shell_points``
+    with the material's ``kind`` and ``params()``): the jets, s and the 324 npts tangent values never leave it;
+    ``device_law=False`` sends it through its ``host`` method instead -- or any object with
+    ``host(Xjet, ujet) -> (psi, s, T)``, a host law whose arrays are uploaded and go through the same transform and
     assembly.  ``assemble_vector`` evaluates the jets of the geometry and of u (``tg_quad_geometry_jet``, ``tg_quad_jet``),
     calls the law, and returns the jet load of s minus the load of ``body_force`` (a value-slot entry of a
     ``VectorJetLoadForm``: ``[npts, 3]``, a callable of the points, or 3 numbers; per unit reference area).
-    ``tangent()``: the ``VectorJetCoefficientForm`` of T; ``symmetric`` True for ``KirchhoffLoveSVK`` (T derives from an
-    energy), for another host law what the bits of the last assembled tangent prove.  ``energy(V)`` = sum_q wdet_q psi_q.
-    Points with a degenerate normal (|X_,1 x X_,2| or |x_,1 x x_,2| below 1e-14 |X_,1| |X_,2|) raise ``RuntimeError`` naming
-    their number.  ``rational``: u_i = u_h,i / W_h, tested against phi / W_h."""
+    ``pressure``: a follower pressure P, dWext = -P sqrt(det a / det A) a_3 . v (demos/kl-shell-hyper/kl-hyper.py:231): a
+    number, or a callable without arguments read at every assembly (``lambda: P * stepper.t`` follows a ``LoadStepper``); its
+    load and its tangent are added to the law's outputs at the points (``tg_shell_pressure_points``; in numpy on the host
+    route).  ``tangent()``: the ``VectorJetCoefficientForm`` of T; ``symmetric`` True for the two built-in laws (T derives from
+    an energy) unless there is a pressure -- a follower load has no potential, the direct solver then takes the LU -- and for
+    another host law what the bits of the last assembled tangent prove.  ``energy(V)`` = sum_q wdet_q psi_q, the strain
+    energy.  Inadmissible points -- a degenerate normal (|X_,1 x X_,2| or |x_,1 x x_,2| below 1e-14 |X_,1| |X_,2|), for
+    ``KirchhoffLoveHyper`` also det Gm <= 0 or det C_2D <= 0 at a thickness point; the material's ``degenerate`` on the host
+    route -- raise ``RuntimeError`` naming their number.  ``rational``: u_i = u_h,i / W_h, tested against phi / W_h."""
 
-    def __init__(self, u, geometry, material, body_force=None, nq=None, rational=False, device_law=True):
+    def __init__(self, u, geometry, material, body_force=None, nq=None, rational=False, device_law=True, pressure=None):
         if geometry is None:
             raise ValueError("ShellResidual: point data live on a mapped patch (geometry=...)")
         if not callable(getattr(material, "host", None)):
-            raise ValueError("ShellResidual: unknown material %r; KirchhoffLoveSVK, or an object with "
+            raise ValueError("ShellResidual: unknown material %r; KirchhoffLoveSVK, KirchhoffLoveHyper, or an object with "
                              "host(Xjet, ujet) -> (psi, s, T)" % (material,))
+        if pressure is not None and not callable(pressure):
+            pressure = float(pressure)
         self.u, self.geometry, self.material = u, geometry, material
-        self.body_force, self.nq, self.rational = body_force, nq, bool(rational)
-        self.builtin = isinstance(material, KirchhoffLoveSVK) and material.kind == 0
+        self.body_force, self.nq, self.rational, self.pressure = body_force, nq, bool(rational), pressure
+        # a law of the device: the material names its kind, its parameters and its inadmissible points
+        self.builtin = getattr(material, "kind", None) in _dev.SHELL_KINDS.values() and callable(getattr(material, "params", None))
         self.device_law = bool(device_law) and self.builtin
         self._host_symmetric = False
         self._load = None
         if body_force is not None:
             self._load = VectorJetLoadForm(self._force_jets, geometry, nq=nq, rational=rational)
+
+    def _pressure(self):
+        """the follower pressure now: a number, or None"""
+        return float(self.pressure()) if callable(self.pressure) else self.pressure
+
+    def _refuse(self, nbad):
+        if nbad > 0:
+            raise RuntimeError("ShellResidual: %d quadrature points %s" % (nbad, getattr(
+                self.material, "inadmissible", KirchhoffLoveSVK.inadmissible)))
 
     def _force_jets(self, x):
         f = self.body_force
@@ -1605,18 +1801,21 @@ class ShellResidual(object):
         and ``tg_jet_transform`` (None where not asked for)"""
         pts, g, X, U = self.jets(V)
         npts = pts.npts
+        P = self._pressure()
         if self.device_law:
             m = self.material
-            s, T, psi, nbad = _dev.shell_points(m.kind, m.E, m.nu, m.thickness, X, U, load, tangent, energy)
-            if nbad > 0:
-                raise RuntimeError("ShellResidual: %d quadrature points with a degenerate surface normal" % nbad)
+            s, T, psi, nbad = _dev.shell_law_points(m.kind, m.params(), X, U, load, tangent, energy)
+            self._refuse(nbad)
+            if P is not None and (load or tangent):
+                _dev.shell_pressure_points(P, X, U, s, T)
             return pts, g, s, T, psi
         Xh, Uh = point_unblock(X.get_local(), npts, (3, 6)), point_unblock(U.get_local(), npts, (3, 6))
-        nbad = int(numpy.sum(KirchhoffLoveSVK.degenerate(Xh, Uh)))
-        if nbad > 0:
-            raise RuntimeError("ShellResidual: %d quadrature points with a degenerate surface normal" % nbad)
+        self._refuse(int(numpy.sum(getattr(self.material, "degenerate", KirchhoffLoveSVK.degenerate)(Xh, Uh))))
         psih, sh, Th = _law_result(self.material.host(Xh, Uh), "ShellResidual", "material.host(Xjet, ujet)", "(psi, s, T)",
                                    [(npts,), (npts, 3, 6), (npts, 3, 6, 3, 6)])
+        if P is not None and (load or tangent):
+            sp, Tp = shell_pressure_host(P, Xh, Uh)
+            sh, Th = sh + sp, Th + Tp
         s = _point_data(sh, pts, (3, 6), "ShellResidual: s") if load else None
         T = None
         if tangent:
@@ -1645,6 +1844,16 @@ class ShellResidual(object):
 
 class _ShellTangent(_LawTangent):
     _form_class = VectorJetCoefficientForm
+
+    def __init__(self, res):
+        _LawTangent.__init__(self, res)
+        self.symmetric = self.symmetric and res.pressure is None
+
+    def _form(self, V):
+        form = _LawTangent._form(self, V)
+        if self.res.pressure is not None:               # a follower load has no potential
+            form._symmetric_hint = self.symmetric = False
+        return form
 
     def _data(self, V):
         return self.res.law(V, load=False, tangent=True)[3]

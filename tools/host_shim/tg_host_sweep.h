@@ -3,7 +3,8 @@
 // hip/hip_runtime.h, and host stand-ins for what those drivers call in the rest of the library -- the allocator, the
 // reference-element tables, the element-coupling pattern, tg_csr_from_blocks -- each allocating EXACTLY what the kernels may
 // touch.  Both sources include csrc/tg_point_shared.h (static inline and templates only: one translation unit here).  Include
-// once, from the file that has main().  TG_HOST_SWEEP_JET (tools/jet_host_sweep.cpp): also csrc/tg_jet.hip and csrc/tg_shell.hip,
+// once, from the file that has main().  TG_HOST_SWEEP_JET (tools/jet_host_sweep.cpp, tools/shell_hyper_host_sweep.cpp): also
+// csrc/tg_jet.hip and csrc/tg_shell.hip,
 // whose kernels read the fourth table d2l[a][q] and the device copies of the element vertices: both are then allocated, again
 // at exactly their sizes.
 #pragma once
