@@ -5,7 +5,9 @@ matrices -- through
 * SpMV (CSR kernels and the sliced copy), M^T b, transpose, add, column selection / permutation, row gather, blocks;
 * the general PtAP K = M^T A M (tIGAr/common.py:1194-1195 applies it to ANY A and M): structural pattern and values, the
   second product on the plan bit-identical, MatZeroRowsColumns fused;
-* the Krylov solvers on diagonally dominant systems.
+* the Krylov solvers on diagonally dominant systems;
+* `csr_from_blocks` on rectangular, empty and zero-row blocks and MatZeroRowsColumns on a row slab (`run_structure_case`,
+  from a generator of its own per case).
 
     python tests/fuzz/fuzz_kernels.py [--seed S] [--cases N] [-v]
 
@@ -172,6 +174,72 @@ def run_case(rng, verbose):
         assert np.allclose(ys, B @ xs, rtol=1e-12, atol=1e-12 * abs(B).max() * n), "sliced SpMV"
 
 
+def draw_blocks(rng):
+    """a square arrangement of 1 .. 4 x 1 .. 4 blocks whose row counts differ per block row and column counts per block
+    column: rectangular blocks, empty blocks, block rows without rows, and -- three block rows or more -- now and then a
+    block row without entries between two that have some"""
+    nb = int(rng.integers(1, 5))
+    rown = [int(rng.choice([0, 1, 5, 63, 64, 65, 200])) for _ in range(nb)]
+    coln = [int(rng.choice([1, 3, 33, 64, 130])) for _ in range(nb)]
+    hollow = int(rng.integers(1, nb - 1)) if (nb >= 3 and rng.random() < 0.5) else -1
+    if hollow >= 0:
+        rown[hollow] = max(rown[hollow], 5)
+        rown[hollow - 1], rown[hollow + 1] = max(rown[hollow - 1], 5), max(rown[hollow + 1], 5)
+    blocks = []
+    for i in range(nb):
+        row = []
+        for j in range(nb):
+            kind = str(rng.choice(["uniform", "ragged", "banded", "long"]))
+            forced = hollow >= 0 and i in (hollow - 1, hollow + 1) and j == 0       # (the neighbours of the hollow row have entries)
+            if i == hollow or (not forced and rng.random() < 0.3):
+                row.append(sp.csr_matrix((rown[i], coln[j])))
+            else:
+                Bij = rand_csr(rng, rown[i], coln[j], kind)
+                if forced and Bij.nnz == 0:
+                    Bij = sp.csr_matrix(([1.25], ([rown[i] - 1], [coln[j] - 1])), shape=(rown[i], coln[j]))
+                row.append(Bij)
+        blocks.append(row)
+    return blocks
+
+
+def run_structure_case(rng, verbose):
+    """``csr_from_blocks`` (what puts the field blocks of every multi-field product together) and the offset form of
+    ``zero_rows_cols`` (MatZeroRowsColumns on the row slab of a rank), against scipy: exact values and pattern"""
+    from tigar_amd import device as dev
+    blocks = draw_blocks(rng)
+    if verbose:
+        print("  blocks %s" % [[(b.shape, b.nnz) for b in row] for row in blocks], flush=True)
+    ref = sp.bmat(blocks, format="csr")
+    ref.sort_indices()
+    assert ref.shape == (sum(row[0].shape[0] for row in blocks), sum(b.shape[1] for b in blocks[0]))
+    Kd = dev.csr_from_blocks([[dev.DeviceCSR.from_scipy(b) for b in row] for row in blocks])
+    K = same(Kd, ref, 0.0, "csr_from_blocks")
+    assert np.array_equal(K.indptr, ref.indptr) and np.array_equal(K.indices, ref.indices), \
+        "pattern of csr_from_blocks: %d stored, %d in the blocks" % (K.nnz, ref.nnz)
+    assert Kd.nnz == ref.nnz
+    # ---- MatZeroRowsColumns on the rows [r0, r1) of a square matrix
+    n = int(rng.choice([1, 2, 7, 64, 65, 300, 1500]))
+    A = (rand_csr(rng, n, n, str(rng.choice(["uniform", "ragged", "banded", "long"])))
+         + sp.diags((rng.random(n) < 0.8) * rng.standard_normal(n))).tocsr()
+    A.sort_indices()
+    r0, r1 = sorted(rng.integers(0, n + 1, size=2).tolist())
+    dofs = np.unique(rng.integers(0, n, size=int(rng.integers(0, 7)))).astype(np.int32)
+    diag = float(rng.choice([1.0, 2.5]))
+    S = A[r0:r1].tocsr()
+    S.sort_indices()
+    Sd = dev.DeviceCSR.from_scipy(S)
+    Sd.zero_rows_cols(dofs, diag, r0)
+    want = S.copy()
+    g = np.repeat(np.arange(r0, r1), np.diff(S.indptr))
+    hit_r, hit_c = np.isin(g, dofs), np.isin(S.indices, dofs)
+    want.data = np.where(hit_r & (S.indices == g), diag, np.where(hit_r | hit_c, 0.0, S.data))
+    Z = Sd.to_scipy().tocsr()
+    Z.sort_indices()
+    assert Z.shape == want.shape and np.array_equal(Z.indptr, want.indptr) and np.array_equal(Z.indices, want.indices), \
+        "zero_rows_cols changed the pattern"
+    assert np.array_equal(Z.data, want.data), "zero_rows_cols on rows %d .. %d of %d, dofs %s" % (r0, r1, n, dofs.tolist())
+
+
 def main():
     import faulthandler
     faulthandler.enable()
@@ -193,6 +261,14 @@ def main():
         except Exception as e:  # noqa: BLE001
             bad += 1
             print(json.dumps({"failed": i, "seed": a.seed, "error": "%s: %s" % (type(e).__name__, str(e)[:300])}), flush=True)
+            if a.v:
+                traceback.print_exc()
+        try:
+            run_structure_case(np.random.default_rng([a.seed, i, 1]), a.v)      # (draws of its own: the case above keeps its)
+        except Exception as e:  # noqa: BLE001
+            bad += 1
+            print(json.dumps({"failed": i, "seed": a.seed, "part": "blocks / zeroed slab",
+                              "error": "%s: %s" % (type(e).__name__, str(e)[:300])}), flush=True)
             if a.v:
                 traceback.print_exc()
     print(json.dumps({"cases": a.cases, "failed": bad, "seed": a.seed}))

@@ -101,6 +101,17 @@ def test_sequences_of_different_matrices_through_one_spline():
     assert rc == 0 and summary["failed"] == 0, "\n".join(failures)[:4000]
 
 
+def test_sequences_of_different_matrices_through_the_streamed_field_engine():
+    """the same tool with the operator kept implicit: patches with two fields go through the streamed field engine, whose
+    blocks off the diagonal hold NOTHING but the three hand-added couplings -- anywhere on the patch.  Until the entries of
+    such a block were counted the engine looked at three node planes of it and dropped the block when the couplings sat
+    elsewhere; the summary says how many cases put them there."""
+    rc, summary, failures = _run(["--seed", "3", "--cases", "12", "--max-dofs", "4000"], {"TIGAR_IMPLICIT_M": "1"},
+                                 tool="fuzz_sequences.py")
+    assert rc == 0 and summary["failed"] == 0, "\n".join(failures)[:4000]
+    assert summary["streamed_couplings_off_the_probed_planes"] >= 3, summary
+
+
 def test_random_mapped_patches_through_the_assembly():
     """`tests/fuzz/fuzz_assembly.py`: 80 random mapped patches (1-3 parametric in 1-3 physical dimensions, degrees 1-4, rational
     and perturbed maps, non-uniform elements, p+1 / p+2 Gauss points) through the element kernels of csrc/tg_assemble.hip:

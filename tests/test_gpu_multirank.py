@@ -216,6 +216,17 @@ def test_several_fields_on_several_ranks(tmp_path, case, world, kind):
     _several_fields(tmp_path, case, world, kind, {})
 
 
+@pytest.mark.parametrize("world,kind", [(2, "ipc"), (3, "host")])
+@pytest.mark.parametrize("case", ["couple_eq3d_b", "couple_eq3d_c", "couple_rt3d_b", "couple_rt3d_c"])
+def test_fields_coupled_on_a_few_nodes_on_several_ranks(tmp_path, case, world, kind):
+    """an explicit FE matrix whose fields 0 and 1 are coupled by ONE entry (b) or on the rows of two node planes (c), inside
+    rank 1's rows and off their first, middle and last plane (tests/gpu_rank_worker_fields.py: ``coupled_space``): every
+    rank counts the entries of a block on its rows instead of looking at three planes, on one basis for all fields
+    (``FieldSlabPath``) and on different bases (``FieldListSlabPath``).  (rt3d, case c on three ranks: plane 14 is the last
+    of rank 1's and the middle of rank 2's rows -- that one case was right before as well.)"""
+    _several_fields(tmp_path, case, world, kind, {})
+
+
 @pytest.mark.parametrize("case,world,p,nels,periodic", [
     ("elasticity3d", 2, 1, (5, 3, 8), ""),            # trilinear, different element counts
     ("elasticity3d", 3, 2, (3, 6, 9), "0"),           # periodic in x
@@ -322,6 +333,7 @@ def _several_fields(tmp_path, case, world, kind, env_more):
     assert not getattr(gen.M, "is_implicit", False)
     solver = t.PETScKrylovSolver(*(method.split(":") if ":" in method else (method, "jacobi")))
     solver.parameters["relative_tolerance"] = 1e-10
+    solver.parameters.update(W.solver_parameters(case))
     spline.setSolverOptions(linearSolver=solver)
     u = t.Function(spline.V)
     U = spline.solveLinearSystem(K, rhs, u).get_local()
@@ -350,11 +362,16 @@ def _several_fields(tmp_path, case, world, kind, env_more):
         assert np.array_equal(Kl.indptr, Kr.indptr) and np.array_equal(Kl.indices, Kr.indices)   # pattern identical
         assert abs(Kl - Kr).max() <= 1e-12 * abs(Kref).max()
         assert np.max(np.abs(z["rhs"] - rref[dofs])) <= 1e-13 * np.max(np.abs(rref))
-        assert np.max(np.abs(z["U"] - U[dofs])) <= 1e-8 * np.max(np.abs(U))
         rows = np.concatenate([np.arange(a, b) for a, b in z["fe"]])
-        if rows.size:                                # (a rank of a thin slab may own no FE rows)
-            assert np.max(np.abs(z["u"] - uref[rows])) <= 1e-8 * np.max(np.abs(uref))
-        assert abs(int(z["its"][0]) - its) <= max(1, its // 20)
+        if W.couples_beyond_the_halo(case):
+            # (the rows of K are right; a product with them would read outside the exchanged vector: every rank refuses)
+            assert "further apart than the halo" in str(z["refused"][0]) and int(z["its"][0]) == -1
+        else:
+            assert str(z["refused"][0]) == ""
+            assert np.max(np.abs(z["U"] - U[dofs])) <= 1e-8 * np.max(np.abs(U))
+            if rows.size:                                # (a rank of a thin slab may own no FE rows)
+                assert np.max(np.abs(z["u"] - uref[rows])) <= 1e-8 * np.max(np.abs(uref))
+            assert abs(int(z["its"][0]) - its) <= max(1, its // 20)
         if kind == "ipc":
             assert int(z["host_waits"][0]) == 0 and int(z["kind"][0]) == 2
         cover[dofs] += 1

@@ -1781,17 +1781,38 @@ class ExtractedSpline(object):
 
     def _block_producer(self, A):
         """``a_block(f, g, r0, r1)`` for the field-block engine: rows [r0, r1) of block (f, g) of an FE matrix on the mixed
-        space, columns of one field; None where the producer says the fields are not coupled"""
+        space, columns of one field; None where the producer says the fields are not coupled.  Which fields an EXPLICIT matrix
+        couples is counted (``a_block.is_empty``, read by ``dist._block_is_empty``): a coupling added by hand may sit on a few
+        nodes.  ``block_rows`` of a LazyFEMatrix carry their maker's declaration (``dist.populates_every_plane``) or none; a
+        LazyFEMatrix with ``rows`` only declares nothing and is asked for all its rows."""
         from .implicit import LazyFEMatrix
         nfe = self.V.dim() // self.nFields
-        if isinstance(A, LazyFEMatrix) and getattr(A, "block_rows", None) is not None:
+        lazy = isinstance(A, LazyFEMatrix)
+        if lazy and getattr(A, "block_rows", None) is not None:
             return A.block_rows
-        rows = A.rows if isinstance(A, LazyFEMatrix) else self._row_blocks_of(A)
+        rows = A.rows if lazy else self._row_blocks_of(A)
 
         def a_block(f, g, r0, r1):
             blk = rows(f * nfe + int(r0), f * nfe + int(r1))
             return blk.block(0, int(r1) - int(r0), g * nfe, (g + 1) * nfe)
+        if not lazy:
+            a_block.is_empty = self._explicit_block_is_empty(A, nfe)
         return a_block
+
+    @staticmethod
+    def _explicit_block_is_empty(A, nfe):
+        """``is_empty(f, g, r0, r1)`` of an explicit FE matrix: no stored entry in rows [r0, r1) of block (f, g) -- the question
+        ``ptaproutes.product_by_field_blocks`` asks of the whole block (``Afg.nnz == 0``), on the host for a scipy matrix,
+        on the device for a DeviceCSR"""
+        nfe = int(nfe)
+        Ah = A if isinstance(A, DeviceCSR) else _fe_matrix(A).tocsr()
+
+        def is_empty(f, g, r0, r1):
+            a, b, c = f * nfe + int(r0), f * nfe + int(r1), g * nfe
+            if isinstance(Ah, DeviceCSR):
+                return Ah.block(a, b, c, c + nfe).nnz == 0
+            return Ah[a:b, c:c + nfe].nnz == 0
+        return is_empty
 
     @staticmethod
     def _row_blocks_of(A):
@@ -1820,8 +1841,10 @@ class ExtractedSpline(object):
                     fac = form.factors(self.V)          # Kronecker sum of 1-D matrices: may be fused into the PtAP
                 A = LazyFEMatrix(lambda r0, r1: form.assemble_matrix(self.V, r0, r1), (n, n), kron_factors=fac)
                 if self.nFields > 1 and hasattr(form, "assemble_block"):
-                    # forms on a mixed space hand out their field blocks (rows of one block, columns of one field)
-                    A.block_rows = lambda f, g, r0, r1: form.assemble_block(self.V, f, g, r0, r1)
+                    # forms on a mixed space hand out their field blocks (rows of one block, columns of one field); a block of
+                    # an integral over the patch is structurally empty or has entries on every node plane
+                    from .dist import populates_every_plane
+                    A.block_rows = populates_every_plane(lambda f, g, r0, r1: form.assemble_block(self.V, f, g, r0, r1))
                     A.block_factors = form.block_factors(self.V) if hasattr(form, "block_factors") else None
             else:
                 A = form.assemble_matrix(self.V)
@@ -1861,7 +1884,9 @@ class ExtractedSpline(object):
         if reorder and (self._distributed() or (self._implicit() and self.nFields > 1)):
             raise NotImplementedError("solveLinearSystem: caller-ordered FE functions with the streamed field engine")
         MTU = DeviceVector(MTAM.shape[0])          # (local rows of MTAM: all of them on one rank)
-        solver = self.linearSolver if self.linearSolver is not None else _default_linear_solver()
+        if self._distributed():
+            self._require_columns_within_halo(MTAM)
+        solver =self.linearSolver if self.linearSolver is not None else _default_linear_solver()
         if getattr(solver, "parameters", {}).get("nonzero_initial_guess", False):
             # the reference sizes AND seeds MTU = M^T u.vector() (tIGAr/common.py:1250-1254): a guess set in u is used.
             # Distributed or several implicit fields: through the slab engine, which gives the rank's rows of M^T u in
@@ -1885,6 +1910,31 @@ class ExtractedSpline(object):
         if hasattr(u, "invalidate_ghosts"):
             u.invalidate_ghosts()              # (new coefficients: ghost rows fetched before are stale)
         return MTU
+
+    def _require_columns_within_halo(self, K):
+        """Several ranks: the products of the Krylov solvers read the direction vector on this rank's dofs and the halo planes
+        of its neighbours, addressed by K's column indices WITHOUT a range check.  The K of an assembled form stays inside; a
+        coupling added by hand between far nodes (kept since the field engines count the entries of explicit blocks) does not
+        -- the product would read outside the exchanged vector.  That is an error here, raised on every rank (one all-reduce
+        of a flag per solve; the count is kept on the matrix).  Stored zeros outside (a far coupling zeroed with the boundary
+        dofs) do not count."""
+        dc = self.comm.device()
+        if getattr(dc, "g0", None) is None:
+            return                             # (no slab set on this communicator: nothing is exchanged through it)
+        lo, hi = int(dc.g0 - dc.halo_lo), int(dc.g1 + dc.halo_hi)
+        kept = getattr(K, "_beyond_halo", None)
+        if kept is None or kept[0] != (lo, hi):
+            n, ncols, far = K.shape[0], K.shape[1], 0
+            for c0, c1 in ((0, lo), (hi, ncols)):
+                if n > 0 and c1 > c0:
+                    out = K.block(0, n, c0, c1)
+                    if out.nnz:
+                        far += int(numpy.count_nonzero(out.to_scipy().data))
+            K._beyond_halo = kept = ((lo, hi), far)
+        if dc.allreduce_sum([float(kept[1])])[0] > 0:
+            raise NotImplementedError("solveLinearSystem on several ranks: K couples dofs that are further apart than the halo "
+                                      "planes the Krylov vectors exchange (%d entries of this rank's rows lie outside the "
+                                      "columns %d .. %d): a coupling added by hand between far nodes needs one rank" % (kept[1], lo, hi))
 
     # -- rank-local FE functions (tIGAr/common.py:1304-1348 runs on distributed PETSc vectors with ghost updates)
     def _register_ghosted(self, f):

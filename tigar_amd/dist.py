@@ -116,6 +116,19 @@ def layout_for(bspline, grid):
     return ZSlabLayout(s.knots, s.p, grid.axes[-1], grid.degree, plane_dofs, plane_fe)
 
 
+def element_pattern_nnz(shape, q, za, zb):
+    """entries of the node planes [za, zb) of an FE matrix that holds the whole element-coupling pattern of a CG degree-``q``
+    node grid with ``shape`` nodes per direction: a vertex node couples to the nodes of both its elements, the others to
+    those of their own, direction by direction"""
+    def per_node(n):
+        i = np.arange(int(n), dtype=np.int64)
+        return np.where(i % q == 0, 1 + q * (i > 0) + q * (i < n - 1), q + 1)
+    out = int(per_node(shape[-1])[int(za):int(zb)].sum())
+    for n in shape[:-1]:
+        out *= int(per_node(n).sum())
+    return out
+
+
 def pick_sub_planes(d, p, nel, planes_mine, free_bytes):
     """dof planes per sub-slab so that one slab of A and the PtAP temporaries use at most about half
     of the free HBM (K needs the rest).  Measured at 256^3 p=3 with the 3/4-of-HBM allocator pool, per step:
@@ -171,6 +184,10 @@ class _ChunkRows(object):
 
     def add_chunk(self, Kc, d0, d1, done_row):
         """``Kc``: rows [d0, d1) of a chunk's contribution; rows below ``done_row`` receive nothing after it"""
+        if d0 < self.pend0:
+            # (the rows below the carried block are final: they went to the result, or belong to another rank)
+            raise RuntimeError("element chunks: rows %d .. %d of a chunk arrive after the rows below %d were final"
+                               % (d0, min(d1, self.pend0), self.pend0))
         if self.pending is not None:
             pend0, pending = self.pend0, self.pending
             p1 = pend0 + pending.shape[0]
@@ -296,7 +313,7 @@ class SlabHotPath(object):
         ``a_rows(r0, r1)`` / ``b_rows(r0, r1)`` return the FE matrix rows (DeviceCSR, global
         columns) / FE vector entries (DeviceVector) of global FE rows [r0, r1).
         ``col``: the ``KronExtraction`` of the COLUMN side when it is another basis than this engine's (block (f, g) of a
-        space whose fields sit on different bases over one node grid: K_fg = M_f^T A_fg M_g) -- tensor line walks only."""
+        space whose fields sit on different bases over one node grid: K_fg = M_f^T A_fg M_g) -- tensor line walks; the general kernels for a block that is not on the element-coupling pattern."""
         import time
         dev = self.dev
         if col is not None:
@@ -582,7 +599,13 @@ class SlabHotPath(object):
                 A = a_rows(r0, r1)
                 tick("input", t0)
                 t0 = time.perf_counter()
-                Kc = chunk.ptap(A, r0, (r0, r1 if e1 == nel_z else e1 * q * pf))
+                c1 = r1 if e1 == nel_z else e1 * q * pf
+                if A.rowptr_at(c1 - r0) != element_pattern_nnz(nn, q, r0 // pf, c1 // pf):
+                    # the plan writes K on the pattern of the CELLS, which is the structural product only when A holds every
+                    # entry of the element-coupling pattern (what an assembled form does); a block with a few couplings added
+                    # by hand would come back with stored zeros: the row-wise stages form its structural pattern
+                    return None
+                Kc = chunk.ptap(A, r0, (r0, c1))
                 del A
                 if Kc is None:
                     return None                  # an entry between nodes of no common cell: the row-wise stages
@@ -665,8 +688,10 @@ class SlabHotPath(object):
                     piece = tplan.planes(A, new_lo * pf, new_lo, zb)
                     del A
                 if piece is None:
-                    raise NotImplementedError("the streamed / multi-GPU path for fields on different bases needs FE matrices "
-                                              "on the element-coupling pattern of the node grid")
+                    # not the element-coupling pattern of the node grid (a block that holds a few couplings added by hand):
+                    # nothing of the walks is kept, the general kernels form the block
+                    del pieces, builder
+                    return self._assemble_pair_general(a_rows, col, t), None
                 pieces.append((new_lo, zb, piece))
                 hi = zb
             pieces = [pc for pc in pieces if pc[1] > za]
@@ -674,6 +699,43 @@ class SlabHotPath(object):
             dev.sync()
             t["ptap"] = t.get("ptap", 0.0) + time.perf_counter() - t0
         return (builder.finish() if builder is not None else out), None
+
+    def _assemble_pair_general(self, a_rows, col, t):
+        """rows [k0, k1) of K_fg = M_f^T A_fg M_g for ANY A_fg (tIGAr/common.py:1194-1200), by the general kernels.  They
+        form P^T A P for one P: here P = [M_f | M_g] (the columns of field g behind those of field f), of whose product the
+        rows of field f and the columns of field g are the block -- twice the work of the block, for the blocks the line
+        walks decline (couplings added by hand: a few entries).  Sub-slab by sub-slab as the scalar engine's general stages."""
+        import time
+        dev = self.dev
+        axes, ncp_f = self.grid.axes, self.ncp
+        ncp_g = int(np.prod(col.ncp, dtype=np.int64))
+        ncols = ncp_f + ncp_g
+
+        def m_rows(r0, r1):
+            Mf = dev.extract_csr_tensor(self.basis.splines, axes, 0, ncols, self.eps, r0, r1)
+            return Mf.add(dev.extract_csr_tensor(col.basis.splines, col.grid.axes, ncp_f, ncols, self.eps, r0, r1))
+        parts = []
+        for (ka, kb) in self.sub_slabs():
+            S = self.layout.slab(ka, kb)
+            t0 = time.perf_counter()
+            MT = dev.extract_csr_tensor_t(self.basis.splines, axes, 0, self.n_fe, self.eps, S["dofs"][0], S["dofs"][1])
+            A = a_rows(S["a_rows"][0], S["a_rows"][1])
+            try:
+                M = m_rows(S["m_rows"][0], S["m_rows"][1])
+                plan = dev.ptap_symbolic(A, M, MT, S["a_rows"][0], S["m_rows"][0], S["dofs"][0])
+                Kaug = dev.ptap_numeric(plan, A, M, MT, None, 1.0)
+            except dev.TigarHipError as e:
+                if "does not cover" not in str(e):
+                    raise
+                # columns beyond the FE rows the slab's elements couple to (a coupling added by hand): all rows of P
+                M = m_rows(0, self.n_fe)
+                plan = dev.ptap_symbolic(A, M, MT, S["a_rows"][0], 0, S["dofs"][0])
+                Kaug = dev.ptap_numeric(plan, A, M, MT, None, 1.0)
+            parts.append(Kaug.block(0, Kaug.shape[0], ncp_f, ncols))
+            del A, M, MT, plan, Kaug
+            dev.sync()
+            t["ptap"] = t.get("ptap", 0.0) + time.perf_counter() - t0
+        return parts[0] if len(parts) == 1 else dev.csr_vstack(parts)
 
     def assemble_matrix(self, a_rows, zero_dofs, diag=1.0, timers=None, a_factors=None):
         """K_loc = rows of M^T A M owned by this rank (extractMatrix, tIGAr/common.py:1176-1204)."""
@@ -812,21 +874,46 @@ class SlabHotPath(object):
         return dev.extract_apply_tensor(self.basis.splines, self.grid.axes, 0, self.eps, x, x_col0, r0, r1)
 
 
+def populates_every_plane(a_block):
+    """Declare that every block ``a_block`` hands out is structurally empty or has entries on every node plane -- what the
+    blocks of an assembled form are.  ``_block_is_empty`` then looks at three planes instead of all rows of the rank."""
+    a_block.populates_every_plane = True
+    return a_block
+
+
+_EXACT_SCAN_PLANES = 8        # node planes per request when a producer without any declaration is asked plane by plane
+
+
 def _block_is_empty(a_block, f, g, ar, plane_fe, fac):
-    """Are fields f and g uncoupled on the FE rows [ar[0], ar[1]) of a rank?  The producer says so itself (None), or three node
-    planes of the block -- the first, the middle, the last of the rows -- hold no entry.  (Until round 5 the whole row block of
-    the rank was assembled for this question and thrown away: twice the FE assembly, and in ONE piece the rows the sub-slab
-    pipeline exists to avoid holding at once -- ADVICE r5.  A block of an assembled form is structurally empty or it has
-    entries on every node plane; couplings added by hand come as explicit matrices, whose blocks are cut out, not assembled.)"""
+    """Are fields f and g uncoupled on the FE rows [ar[0], ar[1]) of a rank?  Who answers depends on what the producer says
+    about itself:
+
+    * a Kronecker factor comes with the block: one row tells whether the producer hands the block out at all (None: no);
+    * ``a_block.is_empty(f, g, r0, r1)``: the producer knows (an explicit matrix counts the entries of the block -- a
+      constraint or contact term between two fields may sit on a few nodes of ONE plane);
+    * ``a_block.populates_every_plane`` (``populates_every_plane``; the blocks of an assembled form): three node planes --
+      the first, the middle, the last of the rows -- hold no entry.  (Until round 5 the whole row block of the rank was
+      assembled for this question and thrown away: twice the FE assembly, and in ONE piece the rows the sub-slab pipeline
+      exists to avoid holding at once -- ADVICE r5.)
+    * nothing declared: all rows are asked for, a few planes at a time, until one holds an entry.
+
+    A producer that returns None says that the fields are not coupled."""
     r0, r1 = int(ar[0]), int(ar[1])
     if r1 <= r0:
         return True
     if fac is not None:
         return a_block(f, g, r0, min(r0 + 1, r1)) is None
+    hook = getattr(a_block, "is_empty", None)
+    if hook is not None:
+        return bool(hook(f, g, r0, r1))
     pf = max(1, int(plane_fe))
-    starts = sorted({r0, r0 + ((r1 - r0) // (2 * pf)) * pf, max(r0, r1 - pf)})
-    for q0 in starts:
-        probe = a_block(f, g, q0, min(q0 + pf, r1))
+    if getattr(a_block, "populates_every_plane", False):
+        pieces = [(q0, min(q0 + pf, r1)) for q0 in sorted({r0, r0 + ((r1 - r0) // (2 * pf)) * pf, max(r0, r1 - pf)})]
+    else:
+        step = _EXACT_SCAN_PLANES * pf
+        pieces = [(q0, min(q0 + step, r1)) for q0 in range(r0, r1, step)]
+    for q0, q1 in pieces:
+        probe = a_block(f, g, q0, q1)
         if probe is None:
             return True
         if probe.nnz:
