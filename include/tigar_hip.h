@@ -534,6 +534,10 @@ int tg_kron_sum_csr(int d, int nterms, const tg_kron_dir_t *dirs, int64_t row0,
  * into PtAP (never materialising A) ...". */
 int tg_tensor_planes_kron(tg_tensor_plan_t plan, int nterms, const tg_kron_dir_t *dirs, int z0, int z1,
                           tg_tensor_planes_t *out);
+/* FE planes that `p` holds, and how many of them the x and y passes contracted.  tg_tensor_planes_kron contracts one
+ * plane per class of planes whose rows of dirs[2] are equal bit for bit in every term (their blocks are equal bit for
+ * bit; the others share them) unless TIGAR_TT_PLANE_CLASSES=0; tg_tensor_planes contracts every plane. */
+int tg_tensor_planes_info(tg_tensor_planes_t p, int *n_planes, int *n_contracted);
 
 /* General Kronecker-product CSR builder on the device: out = sum_t (x)_k F[t][k] restricted to rows
  * [row0,row1), with rectangular 1-D factors (cdim[k] = number of columns of direction k; NULL =

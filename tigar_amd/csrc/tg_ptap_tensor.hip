@@ -43,7 +43,10 @@ struct tg_tensor_planes_s {
   int z0 = 0, z1 = 0;
   int *status = nullptr;            // device flag of the passes that produced these planes (read by the z stage)
   double *buf = nullptr;            // B2 planes
-  std::vector<int64_t> pb;          // offset of plane r2 in buf, indexed r2 - z0
+  // offset of plane r2 in buf, indexed r2 - z0; pb[z1 - z0] = doubles in buf.  Planes of one class (tt_plane_classes)
+  // share a block: the offsets do not increase from plane to plane
+  std::vector<int64_t> pb;
+  int n_contracted = 0;            // planes the x and y passes walked (z1 - z0 unless planes share blocks)
 };
 
 // owner of a handle under construction: destroyed on every early return, released to the caller at the end
@@ -276,6 +279,13 @@ extern "C" int tg_tensor_planes_destroy(tg_tensor_planes_t p) {
   return 0;
 }
 
+extern "C" int tg_tensor_planes_info(tg_tensor_planes_t p, int *n_planes, int *n_contracted) {
+  TG_REQUIRE(p, "null argument to tg_tensor_planes_info");
+  if (n_planes) *n_planes = p->z1 - p->z0;
+  if (n_contracted) *n_contracted = p->n_contracted;
+  return 0;
+}
+
 #define TT_DISPATCH_P(P, CALL) \
   do {                         \
     if ((P) == 1) {            \
@@ -299,7 +309,10 @@ struct tt_plane_set {
   tg_dbuf<int32_t> d_pl[2];
   tt_own<tg_tensor_planes_s> res;
 
-  int init(const tg_tensor_plan_s *pl, int z0_, int z1) {
+  // rep (or null): rep[q] = the plane of [z0, z1) whose blocks plane z0 + q shares (tt_plane_classes: itself or a lower
+  // one).  Only the representatives are listed for the x and y passes and get room in B1 and B2; the others point at
+  // their representative's blocks.  The tables stay indexed by plane - z0 (the kernels read them at the planes listed).
+  int init(const tg_tensor_plan_s *pl, int z0_, int z1, const int32_t *rep = nullptr) {
     const int P = pl->P, W = 2 * P + 1, np = z1 - z0_;
     const tt_dir_t &D0 = pl->dir[0], &D1 = pl->dir[1], &D2 = pl->dir[2];
     z0 = z0_;
@@ -309,14 +322,30 @@ struct tt_plane_set {
     std::vector<int64_t> &pb2 = res->pb;
     pb1.assign(np + 1, 0);
     pb2.assign(np + 1, 0);
+    int64_t len1 = 0, len2 = 0;
     for (int q = 0; q < np; q++) {
+      const int r = rep ? rep[q] - z0 : q;
+      if (r < 0 || r > q || (r < q && (rep[r] != rep[q] || tt_rn_host(P, z0 + r, D2.nfe) != tt_rn_host(P, z0 + q, D2.nfe)))) {
+        tg_set_error("tensor PtAP: plane %d has no valid representative", z0 + q);
+        return 1;
+      }
+      if (r < q) {
+        pb1[q] = pb1[r];
+        pb2[q] = pb2[r];
+        continue;
+      }
       const int n2 = tt_rn_host(P, z0 + q, D2.nfe);
-      pb1[q + 1] = pb1[q] + (int64_t)W * n2 * D0.ncp * pl->h_rps[1][D1.nfe];
-      pb2[q + 1] = pb2[q] + (int64_t)W * W * n2 * D0.ncp * D1.ncp;
+      pb1[q] = len1;
+      pb2[q] = len2;
+      len1 += (int64_t)W * n2 * D0.ncp * pl->h_rps[1][D1.nfe];
+      len2 += (int64_t)W * W * n2 * D0.ncp * D1.ncp;
       pls[n2 == P + 1 ? 0 : 1].push_back(z0 + q);
     }
-    TG_TRY(b1.alloc(pb1[np]));
-    TG_TRY(tg_dmalloc(&res->buf, pb2[np]));
+    pb1[np] = len1;
+    pb2[np] = len2;
+    res->n_contracted = (int)(pls[0].size() + pls[1].size());
+    TG_TRY(b1.alloc(len1));
+    TG_TRY(tg_dmalloc(&res->buf, len2));
     TG_TRY(tg_dmalloc(&res->status, 4));
     TG_TRY(tt_upload(&d_pb1.p, pb1));
     TG_TRY(tt_upload(&d_pb2.p, pb2));
@@ -549,8 +578,19 @@ extern "C" int tg_tensor_planes_kron(tg_tensor_plan_t pl, int nterms, const tg_k
     pl->kcv_key = key;
     pl->kcv_terms = nterms;
   }
+  // Planes whose rows of the last-direction factor are equal bit for bit in every term get equal B1 and B2 blocks
+  // (tt_plane_classes): one per class is contracted, within this call's planes only.  TIGAR_TT_PLANE_CLASSES=0 contracts
+  // every plane.  (Read per call, not once per process: the tests compare both settings in one process.)
+  std::vector<int32_t> rep;
+  if (tg_env_int("TIGAR_TT_PLANE_CLASSES", 1) != 0) {
+    rep.resize((size_t)(z1 - z0));
+    tt_plane_classes(nterms, nnz1d[2], dirs[2].val, pl->h_rps[2].data(), z0, z1, rep.data());
+  }
   tt_plane_set S;
-  TG_TRY(S.init(pl, z0, z1));
+  TG_TRY(S.init(pl, z0, z1, rep.empty() ? nullptr : rep.data()));
+  if (getenv("TIGAR_TRACE"))
+    fprintf(stderr, "[trace] tg_tensor_planes_kron planes [%d,%d): %d requested, %d contracted\n", z0, z1, z1 - z0,
+            S.res->n_contracted);
   if (nterms == 1) tt_launch_xg<1>(pl, S, nnz1d);
   else if (nterms == 2) tt_launch_xg<2>(pl, S, nnz1d);
   else tt_launch_xg<3>(pl, S, nnz1d);

@@ -30,8 +30,12 @@
 // ("local weights" wl[e][j][q], q = dof - e), the vertex nodes additionally none at dof e (j = 0, e > 0).
 #pragma once
 #include <stdint.h>
+#include <string.h>
 
 #include <math.h>
+
+#include <algorithm>
+#include <vector>
 
 #ifdef __HIPCC__
 #define TT_DEV __device__ __forceinline__
@@ -421,6 +425,45 @@ TT_DEV void tt_xg_lane(const tt_xg_args<NT> &A, int bx, int by, int lane, int pi
   int e0, e1;
   tt_piece(A.ech, piece, P, A.d0.nel, e0, e1, io.elo, io.ehi);
   tt_walk<P>(A.d0, e0, e1, io);
+}
+
+// Classes of FE planes that the x and y walks of a Kronecker-sum form cannot tell apart.  In tt_xg_lane the plane r2
+// enters a VALUE only through its row of the last-direction factor, F2u[r2][0..n2) of every term u (q2 = rps2[plane] + c2,
+// folded into the lane's scalars g[u]); everywhere else, and in all of tt_y_lane, it enters addresses only.  Two planes
+// whose rows have the same length and the same bits in every term therefore get the same B1 and B2 blocks, bit for bit:
+// one of them is contracted and the z pass reads its block for both.  (A uniform knot vector with element lengths that
+// are exact in binary leaves a handful of classes: first and last plane, the nodes inside an element, the vertices.)
+//
+// val: the factor's values, term-major (val[u * nnz + q]); rps: [nfe + 1] prefix sums of its row lengths.  rep[q - z0]
+// becomes the LOWEST plane of [z0, z1) whose row equals that of plane q -- compared byte by byte (memcmp on the 8-byte
+// patterns: -0.0 and 0.0 stay apart, equal NaN payloads match), no tolerance, no hash.  Returns the number of classes.
+// Plain host code (a sort of the planes by (length, bytes, plane), then one sweep over the runs).
+static inline int tt_plane_classes(int nterms, int64_t nnz, const double *val, const int32_t *rps, int z0, int z1,
+                                   int32_t *rep) {
+  const int np = z1 - z0;
+  if (np <= 0) return 0;
+  auto cmp = [&](int a, int b) {      // <0, 0, >0: rows of planes a and b by (length, bytes of term 0, 1, ...)
+    const int na = rps[a + 1] - rps[a], nb = rps[b + 1] - rps[b];
+    if (na != nb) return na < nb ? -1 : 1;
+    for (int u = 0; u < nterms; u++) {
+      const int c = memcmp(val + (int64_t)u * nnz + rps[a], val + (int64_t)u * nnz + rps[b], (size_t)na * sizeof(double));
+      if (c) return c;
+    }
+    return 0;
+  };
+  std::vector<int32_t> order((size_t)np);
+  for (int q = 0; q < np; q++) order[(size_t)q] = z0 + q;
+  std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+    const int c = cmp(a, b);
+    return c ? c < 0 : a < b;
+  });
+  int nclasses = 0;
+  for (int q = 0; q < np; q++) {
+    const bool first = q == 0 || cmp(order[(size_t)q - 1], order[(size_t)q]) != 0;
+    nclasses += first ? 1 : 0;
+    rep[order[(size_t)q] - z0] = first ? order[(size_t)q] : rep[order[(size_t)q - 1] - z0];
+  }
+  return nclasses;
 }
 
 // Row lengths of A against the element-coupling pattern: row (a, r1, r2) must hold n0(a)*n1(r1)*n2(r2) entries.

@@ -238,6 +238,15 @@ class TensorPlanes(object):
     def __init__(self, h, z0, z1):
         self._h, self.z0, self.z1 = h, z0, z1
 
+    @property
+    def n_contracted(self):
+        """planes the x and y passes contracted: one per class of planes with bit-identical rows of the last-direction
+        factor for a Kronecker-sum form (the others share its blocks; TIGAR_TT_PLANE_CLASSES=0: every plane), all
+        ``z1 - z0`` for a matrix handed in"""
+        n, nc = C.c_int(0), C.c_int(0)
+        check(_lib.lib().tg_tensor_planes_info(self._h, C.byref(n), C.byref(nc)), "tg_tensor_planes_info")
+        return int(nc.value)
+
     def __del__(self):
         try:
             if self._h:
