@@ -745,6 +745,22 @@ int tg_shell_points(int kind, const double *params, int64_t npts, tg_vec_t Xjet,
  * T_ij^{0,2} += (P / J_A) eps_ijk x_,1k -- no transposed entries: the tangent is not symmetric.  A point whose reference normal is
  * below the floor of tg_shell_points is left alone (the law has counted it).  Does not synchronise. */
 int tg_shell_pressure_points(int64_t npts, double pressure, tg_vec_t Xjet, tg_vec_t ujet, tg_vec_t s_inout, tg_vec_t T_inout);
+/* ---- inertia, mass damping and a rigid-plane penalty at the points (csrc/tg_dynamics.hip): what a dynamic residual adds to the
+ * VALUE slots of a law's outputs.  nF = 2, 3 fields of nJ = 1, 3, 6 slots, value slot first (other values: status 2).  u and
+ * s_inout: nF nJ npts values, slot alpha of field i at (i nJ + alpha) npts + q (a shell: ujet itself, nJ = 6; a solid: the point
+ * values, nJ = 1); T_inout: nF^2 nJ^2 npts values, the value-value entry of block (i, j) at ((i nF + j) nJ^2) npts + q (nJ = 1:
+ * the reaction layout of tg_coef_transform_blocks); X0 (reference positions) and w: nF npts values, component-major; e_out:
+ * npts values.  coef = {sigma, m_u, m_w, t_m, k_s, k_t, c_e} (host, 7 values), plane = {n[0..nF), offset, unused} (host, nF + 2
+ * values; null: no contact, and then X0 may be null):
+ *   g = offset - sum_c n_c (X0_c + u_c^0),  g+ = max(g, 0);  a point is active exactly when g > 0
+ *   s_i^alpha <- sigma s_i^alpha (every slot; sigma == 1: the bits stay);   s_i^0 += m_u u_i^0 + m_w w_i - k_s g+ n_i
+ *   T_ij^00 += delta_ij t_m + k_t [g > 0] n_i n_j   (no other entry of T is read or written)
+ *   e_q = c_e/2 sum_i w_i^2 + k_s/2 g+^2
+ * Every array may be null (an absent u or w counts as 0); a term with a zero coefficient is not added, so a value it would not
+ * change keeps its bits.  *nactive (if given) receives the number of active points: integer atomics only, and the only
+ * synchronisation of the call.  No floating-point atomics: the same inputs give the same bits. */
+int tg_point_dynamics(int nF, int nJ, int64_t npts, const double *coef, const double *plane, tg_vec_t X0, tg_vec_t u, tg_vec_t w,
+                      tg_vec_t s_inout, tg_vec_t T_inout, tg_vec_t e_out, int64_t *nactive);
 
 /* ---- boundary integrals on the same patches (csrc/tg_boundary.hip): the boundary measure and the mapped normal of the
  * reference's ExtractedSpline (spline.ds, spline.n; tIGAr/common.py:931-939, calculusUtils.py:37-52, 71-80).  d = 2, 3,

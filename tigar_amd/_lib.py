@@ -249,6 +249,8 @@ PROTOTYPES = {
     "tg_quad_load_jet": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, handle, handle]),
     "tg_shell_points": (C.c_int, [C.c_int, c_f64p, C.c_int64, handle, handle, handle, handle, handle, c_i64p]),
     "tg_shell_pressure_points": (C.c_int, [C.c_int64, C.c_double, handle, handle, handle, handle]),
+    "tg_point_dynamics": (C.c_int, [C.c_int, C.c_int, C.c_int64, c_f64p, c_f64p, handle, handle, handle, handle, handle, handle,
+                                    c_i64p]),
     "tg_face_points": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, handle]),
     "tg_face_eval": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, handle]),
     "tg_face_load": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle]),

@@ -2359,7 +2359,8 @@ class ExtractedSpline(object):
         self.M.mult(U, u.vector())
         return u
 
-    def solveNonlinearVariationalProblem(self, residualForm, J, u, referenceError=None, igaDoFs=None):
+    def solveNonlinearVariationalProblem(self, residualForm, J, u, referenceError=None, igaDoFs=None, absoluteTolerance=0.0,
+                                         phaseSeconds=None):
         """Newton iteration of tIGAr/common.py:1304-1348, same control flow: assemble
         (M^T J M, M^T R) at the current ``u``, stop when ||M^T R|| / reference < relativeTolerance
         (reference = first norm unless given), else solve for the increment and ``u <- u - du``
@@ -2367,7 +2368,11 @@ class ExtractedSpline(object):
         ``residualForm`` / ``J`` are form objects whose ``assemble_vector`` / ``assemble_matrix``
         read the current state of ``u`` (as UFL forms reference their coefficient).  Prints the
         reference's progress line; non-convergence raises instead of the reference's exit().
-        Returns the list of relative norms."""
+        Returns the list of relative norms.  Two additions, both off by default: with ``absoluteTolerance`` > 0 the iteration
+        also stops, before any solve, when the FIRST ||M^T R|| is at most that (the relative test divides by the first norm
+        and cannot pass when the start is already converged; the history is then ``[1.0]``); ``phaseSeconds``, a dict, gets
+        the seconds of the assemblies added under "assembly" and those of the solves under "solve" (three device
+        synchronisations per iteration)."""
         if self._caller_ordered():
             raise NotImplementedError("solveNonlinearVariationalProblem: the forms read the Function in the order of the node "
                                       "grid; a caller-ordered spline is not supported")
@@ -2389,9 +2394,22 @@ class ExtractedSpline(object):
             self.M.mult(igaDoFs, uv)
         history = []
         converged = False
+        def clock():
+            if phaseSeconds is None:
+                return None
+            _dev.sync()
+            return time.perf_counter()
         for i in range(0, self.maxIters):
+            t0 = clock()
             MTAM, MTb = self.assembleLinearSystem(J, residualForm)
             currentNorm = self.globalNorm(MTb, "l2")
+            t1 = clock()
+            if phaseSeconds is not None:
+                phaseSeconds["assembly"] = phaseSeconds.get("assembly", 0.0) + (t1 - t0)
+            if i == 0 and absoluteTolerance > 0.0 and currentNorm <= absoluteTolerance:
+                history.append(1.0)
+                converged = True
+                break
             if i == 0 and referenceError is None:
                 referenceError = currentNorm
             relativeNorm = currentNorm / referenceError
@@ -2404,6 +2422,8 @@ class ExtractedSpline(object):
                 break
             du = Function(self.V, self.localFERange() if dist else None)
             igaIncrement = self.solveLinearSystem(MTAM, MTb, du)
+            if phaseSeconds is not None:
+                phaseSeconds["solve"] = phaseSeconds.get("solve", 0.0) + (clock() - t1)
             uv.axpy(-1.0, du.vector())
             if hasattr(u, "invalidate_ghosts"):
                 u.invalidate_ghosts()

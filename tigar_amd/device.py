@@ -1375,6 +1375,28 @@ def shell_pressure_points(pressure, Xjet, ujet, s=None, T=None):
           "tg_shell_pressure_points")
 
 
+def point_dynamics(nF, nJ, npts, coef, plane=None, X0=None, u=None, w=None, s=None, T=None, e=None, count=False):
+    """Inertia, mass damping and a rigid-plane penalty in the value slots of a law's point data, in place
+    (``tg_point_dynamics``): ``coef`` = (sigma, m_u, m_w, t_m, k_s, k_t, c_e), ``plane`` = (n[0..nF), offset) or None;
+    with g = offset - n . (X0 + u^0), g+ = max(g, 0):  s <- sigma s in every slot, s_i^0 += m_u u_i^0 + m_w w_i - k_s g+ n_i,
+    T_ij^00 += delta_ij t_m + k_t [g > 0] n_i n_j,  e_q = c_e/2 |w|^2 + k_s/2 g+^2.  ``u`` / ``s``: nF nJ npts values (slot
+    alpha of field i at (i nJ + alpha) npts + q), ``T``: nF^2 nJ^2 npts, ``X0`` / ``w``: nF npts, ``e``: npts; every array may
+    be None.  ``count``: returns the number of active points (g > 0; the call then synchronises), else None."""
+    c = _f64([float(v) for v in coef])
+    if c.size != 7:
+        raise ValueError("point_dynamics: coef = (sigma, m_u, m_w, t_m, k_s, k_t, c_e), %d values given" % c.size)
+    pl = None
+    if plane is not None:
+        pl = _f64([float(v) for v in plane] + [0.0])
+        if pl.size != int(nF) + 2:
+            raise ValueError("point_dynamics: plane = (n[0..nF), offset), nF = %d; %d values given" % (nF, pl.size - 1))
+    nact = C.c_int64(0)
+    check(_lib.lib().tg_point_dynamics(int(nF), int(nJ), int(npts), _p(c, c_f64p), _p(pl, c_f64p) if pl is not None else None,
+                                       _h_or_none(X0), _h_or_none(u), _h_or_none(w), _h_or_none(s), _h_or_none(T), _h_or_none(e),
+                                       C.byref(nact) if count else None), "tg_point_dynamics")
+    return int(nact.value) if count else None
+
+
 MATERIAL_KINDS = {"linear": 0, "svk": 1, "neohookean": 2}
 
 

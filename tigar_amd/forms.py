@@ -1859,6 +1859,355 @@ class _ShellTangent(_LawTangent):
         return self.res.law(V, load=False, tangent=True)[3]
 
 
+# ---- structural dynamics (csrc/tg_dynamics.hip): inertia, mass damping and a rigid plane at the points ----------------------
+class PlanePenalty(object):
+    """The rigid half-space n . x >= ``offset`` enforced by a penalty: with the gap g = offset - n . x of a material point at
+    x = X + u and g+ = max(g, 0), the energy is stiffness/2 g+^2 per unit reference measure, the force on the body
+    stiffness g+ n (``contactForce`` of demos/kl-shell-svk/dynamic-tspline.py is n = e_3, offset = 0).  ``normal`` is
+    normalised on construction, so ``offset`` is the signed distance of the plane from the origin along it."""
+
+    def __init__(self, normal, offset, stiffness):
+        n = numpy.asarray(normal, dtype=numpy.float64).ravel()
+        length = float(numpy.sqrt(numpy.sum(n * n))) if n.size in (2, 3) else 0.0
+        if not (length > 0.0 and numpy.isfinite(length)):
+            raise ValueError("PlanePenalty: normal = %r; two or three numbers that are not all zero" % (normal,))
+        if not float(stiffness) > 0.0:
+            raise ValueError("PlanePenalty: stiffness = %r must be positive" % (stiffness,))
+        self.normal, self.offset, self.stiffness = n / length, float(offset), float(stiffness)
+
+    def plane(self):
+        """(n[0..nsd), offset): the plane as ``device.point_dynamics`` takes it"""
+        return tuple(float(v) for v in self.normal) + (self.offset,)
+
+    def gap(self, x):
+        """g = offset - n . x at the positions ``x [npts, nsd]`` (host)"""
+        x = numpy.asarray(x)
+        return x.dtype.type(self.offset) - x @ self.normal.astype(x.dtype)
+
+
+class _ShellTwin(ShellResidual):
+    """a ``ShellResidual`` that keeps the jets of u of its last evaluation (``held``: what ``tg_point_dynamics`` reads)"""
+    held = None
+
+    def jets(self, V):
+        out = ShellResidual.jets(self, V)
+        self.held = out[3]
+        return out
+
+
+class _SolidTwin(HyperelasticResidual):
+    """a ``HyperelasticResidual`` that keeps the point values of u (``held``) which ``tg_quad_eval`` returns next to the gradient
+    and ``HyperelasticResidual.grad_u`` drops: the same calls, both results gathered field after field"""
+    held = None
+
+    def grad_u(self, V):
+        who = "DynamicResidual"
+        g, nF = _point_scope(self.geometry, V, who, "vector")
+        pts = _vector_points(self.geometry, self.nq, who)
+        n, npts = g.num_nodes(), pts.npts
+        uv = _nodal_vector(self.u, nF, n, who)
+        ui = _dev.DeviceVector(n, zero=False)
+        val, grad = _dev.DeviceVector(nF * npts, zero=False), _dev.DeviceVector(nF * pts.nsd * npts, zero=False)
+        for i in range(nF):
+            _dev.vec_copy_range(ui, 0, uv, i * n, n)
+            v, dv = _dev.quad_eval(pts.verts, pts.p, pts.cp, ui, grad=True, nq=pts.nq, rational=self.rational)
+            _dev.vec_copy_range(val, i * npts, v, 0, npts)
+            _dev.vec_copy_range(grad, i * pts.nsd * npts, dv, 0, pts.nsd * npts)
+        self.held = val
+        return pts, g, nF, grad
+
+
+class _ReactionForm(VectorCoefficientForm):
+    """a ``VectorCoefficientForm`` whose reaction is symmetric by construction (density and k n (x) n written on the device):
+    it is not read back to compare its bits"""
+
+    def _static_coefficients(self, pts, nF, who):
+        A, sym = _point_data(self.tangent, pts, (nF, pts.nsd, nF, pts.nsd), who + ": tangent", _BLOCK_ORDER, _MAJOR_SWAP,
+                             hint=self._symmetric_hint)
+        return pts, A, self.reaction, bool(sym)
+
+
+class DynamicResidual(object):
+    """Residual of nonlinear structural dynamics on the mapped patch, the formulation of
+    demos/kl-shell-svk/dynamic-tspline.py:100-293 of the reference:
+
+        R(y)[v] = int rho (yddot_alpha + a_M ydot_alpha) . v + D psi(y_alpha)[v] - loads(y_alpha, t_alpha) . v
+                      - k g+(X + y_alpha) n . v
+        dR/dy   = rho (c_a + a_M c_v) M + alpha_f [K_law + K_pressure + k [g > 0] n (x) n](y_alpha)
+
+    ``static``: a ``ShellResidual`` or a ``HyperelasticResidual`` whose ``u`` is the Function ``integrator`` solves for; its
+    law, pressure and body force are evaluated at the alpha-level state y_alpha by a twin: a residual of the same class built
+    from the arguments ``static`` holds at this moment, which reads the alpha-level vector and shares no cache with the
+    object handed in -- that one is neither modified nor read again.  A ``pressure`` callable is read at every assembly and
+    finds the time of the loads in ``dyn.t_alpha``; a ``body_force`` callable is a function of the points alone, evaluated
+    once per set of points by the static classes and not again.
+    ``integrator``: a second-order ``GeneralizedAlphaIntegrator``, or a ``BackwardEulerIntegrator`` with two old functions
+    (alpha_f = 1, its own ``xdot()`` and ``xddot()``).  ``density``: mass per unit reference measure (rho h of a shell, rho of
+    a solid); ``mass_damping`` = a_M; ``contact``: a ``PlanePenalty`` or None.  c_a and c_v, the coefficients of y in
+    yddot_alpha and ydot_alpha, are read from the integrator's ``LinearCombination.split``.
+
+    DIVISION BY alpha_f: ``assemble_vector`` returns R / alpha_f and ``tangent()`` the form of (dR/dy) / alpha_f, so that the
+    tangent values of the law are used as the law kernel wrote them (y_alpha moves by alpha_f dy): only the nF^2 value-value
+    entries of the point tangent and the value-slot loads are modified.  Newton iterates and RELATIVE norms are those of the
+    reference's forms; absolute norms are 1 / alpha_f times the reference's.  The factor is ``dyn.scale`` = alpha_f.
+
+    Inertia is affine in y_alpha: rho (yddot_alpha + a_M ydot_alpha) / alpha_f = m_u y_alpha + w with w a combination of the
+    old state.  w is brought to the points once per time step (keyed on ``integrator.t``; ``invalidate()`` after the old state
+    was changed by hand); after that an assembly runs the point evaluations of ``static`` and one ``tg_point_dynamics`` --
+    between the law and the load / tangent assembly, on the value slots the law kernel left on the device.
+
+    ``tangent()``: ``assemble_matrix``, ``assemble_block``, ``geometry``; ``symmetric`` that of the static tangent (inertia
+    and the penalty are symmetric, a follower pressure gives False).  ``energy()``: {"strain", "kinetic", "contact", "total"}
+    at the current level ``integrator.x`` with ``xdot()`` for the velocity.  ``active_points()``: the number of points in
+    contact at the last assembly.  One rank, all rows, the order of the node grid."""
+
+    def __init__(self, static, integrator, density, mass_damping=0.0, contact=None):
+        from . import timeIntegration as _ti
+        who = "DynamicResidual"
+        if isinstance(static, ShellResidual):
+            self.kind, self.nJ = "shell", 6
+        elif isinstance(static, HyperelasticResidual):
+            self.kind, self.nJ = "solid", 1
+        else:
+            raise NotImplementedError("%s: static = %r; a ShellResidual or a HyperelasticResidual carries the law" % (who, static))
+        if isinstance(integrator, _ti.GeneralizedAlphaIntegrator):
+            self._gen_alpha = True
+        elif isinstance(integrator, _ti.BackwardEulerIntegrator):
+            self._gen_alpha = False
+        else:
+            raise ValueError("%s: integrator = %r; a GeneralizedAlphaIntegrator or a BackwardEulerIntegrator" % (who, integrator))
+        if integrator.systemOrder != 2:
+            raise ValueError("%s: a first-order integrator has no acceleration; structural dynamics is a second-order system "
+                             "(oldFunctions = [y_old, ydot_old%s])" % (who, ", yddot_old" if self._gen_alpha else ""))
+        if _ti._vec_of(static.u) is not _ti._vec_of(integrator.x):
+            raise ValueError("%s: static.u is not the Function the integrator solves for (integrator.x)" % who)
+        if not float(density) > 0.0:
+            raise ValueError("%s: density = %r must be positive (mass per unit reference measure)" % (who, density))
+        if contact is not None and not isinstance(contact, PlanePenalty):
+            raise ValueError("%s: contact = %r; a PlanePenalty or None" % (who, contact))
+        nsd = len(static.geometry.cpFuncs) - 1
+        if contact is not None and contact.normal.size != nsd:
+            raise ValueError("%s: the plane's normal has %d components, the patch lies in %d dimensions" % (who, contact.normal.size, nsd))
+        self.static, self.integrator, self.geometry = static, integrator, static.geometry
+        self.density, self.mass_damping, self.contact = float(density), float(mass_damping), contact
+        self.rational, self.nq = static.rational, static.nq
+        self.scale = float(integrator.ALPHA_F) if self._gen_alpha else 1.0
+        self._ti = _ti
+        self._twin = self._make_twin(None)              # reads y_alpha
+        self._now = self._make_twin(integrator.x)       # reads the current level (energy)
+        self._ya, self._w, self._w_key, self._nactive = None, None, None, 0
+
+    # -- the law at another state
+    def _make_twin(self, u):
+        st = self.static
+        if self.kind == "shell":
+            return _ShellTwin(u, st.geometry, st.material, body_force=st.body_force, nq=st.nq, rational=st.rational,
+                              device_law=st.device_law, pressure=st.pressure)
+        return _SolidTwin(u, st.geometry, st.material, body_force=st.body_force, nq=st.nq, rational=st.rational)
+
+    # -- the coefficients of a step
+    @property
+    def t_alpha(self):
+        """the time the loads are evaluated at: t_{n+1} - (1 - alpha_f) DELTA_T"""
+        it = self.integrator
+        return it.t - (1.0 - self.scale) * float(it.DELTA_T)
+
+    def _inertia(self):
+        """(c_M, the rest): rho-free yddot_alpha + a_M ydot_alpha = c_M y + rest, c_M = c_a + a_M c_v"""
+        it = self.integrator
+        if self._gen_alpha:
+            e = it.xddot_alpha() + self.mass_damping * it.xdot_alpha()
+        else:
+            e = it.xddot() + self.mass_damping * it.xdot()
+        return e.split(it.x)
+
+    def coefficients(self):
+        """{"c_a", "c_v", "c_M", "m_u", "t_m"}: c_a, c_v the coefficients of y in yddot_alpha and ydot_alpha, c_M = c_a + a_M c_v,
+        m_u = rho c_M / alpha_f^2 what multiplies y_alpha in R / alpha_f, t_m = rho c_M / alpha_f what multiplies the mass
+        matrix in (dR/dy) / alpha_f"""
+        it, af = self.integrator, self.scale
+        c_a = (it.xddot_alpha() if self._gen_alpha else it.xddot()).coefficient(it.x)
+        c_v = (it.xdot_alpha() if self._gen_alpha else it.xdot()).coefficient(it.x)
+        c_M = self._inertia()[0]
+        return {"c_a": c_a, "c_v": c_v, "c_M": c_M, "m_u": self.density * c_M / (af * af), "t_m": self.density * c_M / af}
+
+    def invalidate(self):
+        """forget the old-state part of the inertia at the points (the old functions were changed without ``advance()``)"""
+        self._w_key = None
+
+    def _scope(self, V, row0, row1, block=False):
+        who = "DynamicResidual"
+        if self.kind == "shell":
+            g, nF, nJ = _point_scope(self.geometry, V, who, "jet")
+        else:
+            g, nF = _point_scope(self.geometry, V, who, "vector")
+        _whole_rows((1 if block else nF) * g.num_nodes(), row0, row1, who, "patch")
+        return g, nF, _vector_points(self.geometry, self.nq, who)
+
+    def _point_values(self, pts, g, nF, nodal):
+        """the nF fields of a nodal vector at the points, field after field (``tg_quad_eval``)"""
+        n, npts = g.num_nodes(), pts.npts
+        ui, out = _dev.DeviceVector(n, zero=False), _dev.DeviceVector(nF * npts, zero=False)
+        for i in range(nF):
+            _dev.vec_copy_range(ui, 0, nodal, i * n, n)
+            _dev.vec_copy_range(out, i * npts, _dev.quad_eval(pts.verts, pts.p, pts.cp, ui, nq=pts.nq, rational=self.rational), 0, npts)
+        return out
+
+    def _state(self, g, nF, pts):
+        """y_alpha into the vector the twin reads (one ``tg_vec_lincomb``), and, once per step, w at the points"""
+        it, ti, af = self.integrator, self._ti, self.scale
+        size = nF * g.num_nodes()
+        if self._ya is None or self._ya.size() != size:
+            self._ya = _dev.DeviceVector(size, zero=False)
+            self._twin.u = self._ya
+        if ti._vec_of(it.x).size() != size:
+            raise ValueError("DynamicResidual: the unknown holds %d nodal values, the space has %d fields of %d"
+                             % (ti._vec_of(it.x).size(), nF, g.num_nodes()))
+        ti.x_alpha(af, it.x, it.x_old).evaluate(out=self._ya)
+        key = (it.t, id(pts))
+        if self._w_key != key:
+            c_M, rest = self._inertia()
+            expr = (self.density / af) * (rest - (c_M * (1.0 - af) / af) * ti.LinearCombination.of(it.x_old))
+            self._w = self._point_values(pts, g, nF, expr.evaluate(out=_dev.DeviceVector(size, zero=False)))
+            self._w_key, self._w_pts = key, pts
+        return self._w
+
+    def _plane(self):
+        return self.contact.plane() if self.contact is not None else None
+
+    def _dynamics(self, pts, nF, coef, w=None, s=None, T=None):
+        """the one launch of an assembly; the count of active points is read back only with a plane"""
+        n = _dev.point_dynamics(nF, self.nJ, pts.npts, coef, self._plane(), pts.x_device if self.contact is not None else None,
+                                self._twin.held, w, s, T, None, count=self.contact is not None)
+        self._nactive = n if n is not None else 0
+
+    def active_points(self):
+        """the number of quadrature points in contact (g > 0) at the last assembly"""
+        return self._nactive
+
+    def assemble_vector(self, V, row0=None, row1=None):
+        g, nF, pts = self._scope(V, row0, row1)
+        w = self._state(g, nF, pts)
+        twin, af, c = self._twin, self.scale, self.coefficients()
+        k = self.contact.stiffness if self.contact is not None else 0.0
+        if self.kind == "shell":
+            s = twin.law(V)[2]
+            self._dynamics(pts, nF, (1.0 / af, c["m_u"], 1.0, 0.0, k / af, 0.0, 0.0), w=w, s=s)
+            r = VectorJetLoadForm(s, self.geometry, nq=self.nq, rational=self.rational).assemble_vector(V)
+            if twin._load is not None:
+                r.axpy(-1.0 / af, twin._load.assemble_vector(V))
+            return r
+        # a solid: the stress is a flux the point kernel has no business with -- the value-slot load holds alpha_f times the
+        # inertia, and the assembled vector is divided by alpha_f
+        P, npts = twin.law(V)[3], pts.npts
+        s = _dev.DeviceVector(nF * npts)
+        if twin.body_force is not None:
+            fq = _per_points(twin, "_fq", pts, lambda: _field_values(pts, twin.body_force, nF, "DynamicResidual: body_force", scale=-1.0))
+            for i in range(nF):
+                _dev.vec_copy_range(s, i * npts, fq[i], 0, npts)
+        self._dynamics(pts, nF, (1.0, af * c["m_u"], af, 0.0, k, 0.0, 0.0), w=w, s=s)
+        si = [_dev.DeviceVector(npts, zero=False) for _ in range(nF)]
+        for i in range(nF):
+            _dev.vec_copy_range(si[i], 0, s, i * npts, npts)
+        r = _field_loads(pts, g.num_nodes(), nF, si, P, self.rational)
+        return _dev.vec_lincomb(r, [1.0 / af], [r]) if af != 1.0 else r
+
+    def _tangent_data(self, V, g, nF, pts):
+        """(the law's point tangent at y_alpha, the reaction of a solid or None) with inertia and the penalty added"""
+        self._state(g, nF, pts)
+        twin, c = self._twin, self.coefficients()
+        k = self.contact.stiffness if self.contact is not None else 0.0
+        if self.kind == "shell":
+            T = twin.law(V, load=False, tangent=True)[3]
+            self._dynamics(pts, nF, (1.0, 0.0, 0.0, c["t_m"], 0.0, k, 0.0), T=T)
+            return T, None
+        A = twin.law(V, stress=False, tangent=True)[4]
+        M = _dev.DeviceVector(nF * nF * pts.npts)
+        self._dynamics(pts, nF, (1.0, 0.0, 0.0, c["t_m"], 0.0, k, 0.0), T=M)
+        return A, M
+
+    def energy(self, V=None, y=None, ydot=None):
+        """{"strain", "kinetic", "contact", "total"} at the current level: sum_q wdet psi(y), rho/2 |ydot|^2 with ``xdot()`` of the
+        integrator, k/2 g+(X + y)^2; the last two through ``e_out`` of ``tg_point_dynamics``.  ``y`` / ``ydot``: another
+        state (Functions or nodal vectors) in the place of ``integrator.x`` and ``xdot()`` -- after ``advance()`` the formulas
+        of the integrator no longer describe the step just taken, the old functions do."""
+        it, ti = self.integrator, self._ti
+        if V is None:
+            V = it.x.function_space()
+        g, nF, pts = self._scope(V, None, None)
+        self._now.u = it.x if y is None else y
+        out = {"strain": float(self._now.energy(V))}
+        vq = self._point_values(pts, g, nF, it.xdot().evaluate() if ydot is None else ti._vec_of(ydot))
+        e = _dev.DeviceVector(pts.npts, zero=False)
+        _dev.point_dynamics(nF, 1, pts.npts, (1.0, 0.0, 0.0, 0.0, 0.0, 0.0, self.density), w=vq, e=e)
+        out["kinetic"] = float(pts.weights.inner(e))
+        out["contact"] = 0.0
+        if self.contact is not None:
+            uq = self._point_values(pts, g, nF, ti._vec_of(self._now.u))
+            _dev.point_dynamics(nF, 1, pts.npts, (1.0, 0.0, 0.0, 0.0, self.contact.stiffness, 0.0, 0.0), self._plane(), pts.x_device,
+                                u=uq, e=e)
+            out["contact"] = float(pts.weights.inner(e))
+        out["total"] = out["strain"] + out["kinetic"] + out["contact"]
+        return out
+
+    def tangent(self):
+        return _DynamicTangent(self)
+
+    def mass_form(self):
+        """the form of density * mass matrix (the value-value entries of the point tangent alone): ``assemble_matrix(V)``"""
+        return _DynamicMass(self)
+
+
+class _DynamicTangent(_LawTangent):
+    """The tangent form (dR/dy) / alpha_f of a ``DynamicResidual``: the form of the static tangent -- its class, its symmetry,
+    its transform and assembly -- on the point tangent of the law at y_alpha with rho (c_a + a_M c_v) / alpha_f and
+    k [g > 0] n (x) n added to its value-value entries at the points (a solid: as the reaction of the form)."""
+
+    def __init__(self, dyn):
+        self.dyn, self._static = dyn, dyn._twin.tangent()
+        _LawTangent.__init__(self, dyn._twin)
+        self.symmetric = self._static.symmetric
+
+    def _rows(self, V, row0, row1, block):
+        self.dyn._scope(V, row0, row1, block)
+
+    def _form(self, V):
+        dyn, st = self.dyn, self._static
+        A, M = dyn._tangent_data(V, *dyn._scope(V, None, None))
+        st._data = lambda V_: A
+        if M is not None:
+            st._form_class = _ReactionForm
+        form = st._form(V)                               # (sets the symmetry: the law's, a host law's bits, a pressure's False)
+        if M is not None:
+            form.reaction = M
+        self.symmetric = st.symmetric
+        return form
+
+
+class _DynamicMass(object):
+    """density * int y . v of a ``DynamicResidual``: the form of the tangent on point data with nothing but density in the nF
+    value-value diagonal entries (written by ``tg_point_dynamics`` into zeros)"""
+    symmetric = True
+
+    def __init__(self, dyn):
+        self.dyn, self.geometry = dyn, dyn.geometry
+
+    def assemble_matrix(self, V, row0=None, row1=None):
+        dyn = self.dyn
+        g, nF, pts = dyn._scope(V, row0, row1)
+        coef = (1.0, 0.0, 0.0, dyn.density, 0.0, 0.0, 0.0)
+        if dyn.kind == "shell":
+            T = _dev.DeviceVector(nF * nF * 36 * pts.npts)
+            _dev.point_dynamics(nF, 6, pts.npts, coef, T=T)
+            form = VectorJetCoefficientForm(dyn.geometry, T, nq=dyn.nq, rational=dyn.rational)
+        else:
+            M = _dev.DeviceVector(nF * nF * pts.npts)
+            _dev.point_dynamics(nF, 1, pts.npts, coef, T=M)
+            form = _ReactionForm(dyn.geometry, _dev.DeviceVector(nF ** 4 * pts.npts), reaction=M, nq=dyn.nq, rational=dyn.rational)
+        form._symmetric_hint = True
+        return form.assemble_matrix(V)
+
+
 # ---- boundary integrals on a mapped patch (csrc/tg_boundary.hip): spline.ds and spline.n of the reference -----------------
 def _periodic_directions(geometry):
     """directions whose knot vector is not open (the faces there are no boundary), as far as the geometry tells"""

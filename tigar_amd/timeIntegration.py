@@ -12,6 +12,9 @@ step.  There is no UFL here: ``xdot()``, ``xddot()``, ``x_alpha()`` ... return a
 a linear problem needs to form its matrix and right-hand side) and evaluated on the device in one pass
 (csrc/tg_timeint.hip: ``tg_vec_lincomb``).  ``advance()`` is one fused in-place kernel (``tg_state_advance``).
 
+``NonlinearTransientProblem`` drives nonlinear structural dynamics -- a shell or solid residual with inertia, mass damping
+and a rigid plane (``forms.DynamicResidual``, csrc/tg_dynamics.hip) -- with one Newton solve per step.
+
 ``LinearDGSpaceTimeIntegrator`` is not provided: it is a helper that arranges UFL forms over a time slab and has no
 numerics of its own.
 """
@@ -497,3 +500,164 @@ class LinearTransientProblem(object):
             return 0.5 * self._x_old.inner(self.Mm.mult(self._x_old, tmp))
         e = 0.5 * self._xdot_old.inner(self.Mm.mult(self._xdot_old, tmp))
         return e + 0.5 * self._x_old.inner(self.K.mult(self._x_old, tmp))
+
+
+class NonlinearTransientProblem(object):
+    """Nonlinear structural dynamics on an ``ExtractedSpline``, the flow of demos/kl-shell-svk/dynamic-tspline.py:100-293:
+
+        rho (yddot + a_M ydot) + D psi(y) = loads + contact        (``forms.DynamicResidual``)
+
+    by the generalized-alpha method (``scheme="generalized_alpha"``, ``RHO_INF``) or backward Euler
+    (``scheme="backward_euler"``), one ``spline.solveNonlinearVariationalProblem`` per step.  ``static``: a
+    ``forms.ShellResidual`` or ``forms.HyperelasticResidual``; its ``u`` is the unknown y of the step being computed.
+    ``density``: mass per unit reference measure; ``mass_damping`` = a_M; ``contact``: a ``forms.PlanePenalty`` or None.
+    The problem owns ``y_old``, ``ydot_old``, ``yddot_old`` (FE Functions), ``integrator`` and ``dyn`` (the
+    ``DynamicResidual``, which returns R / alpha_f and (dR/dy) / alpha_f: ``dyn.scale``).
+
+    ``step(n)``, per step: the same-velocity predictor into y (one ``tg_vec_lincomb``), the Newton solve, ``advance()`` (one
+    ``tg_state_advance``).  The Newton test is relative to the first norm, which fails when the predictor is already
+    converged (a body at rest): with ``absoluteTolerance`` > 0 the step also ends, without a Newton step, when the first
+    ||M^T R / alpha_f|| <= absoluteTolerance; 0.0 is the reference's behaviour.
+
+    ``y0`` / ``ydot0``: FE Functions, IGA-dof ``DeviceVector`` s (prolonged by M), nF numbers (a constant vector; with
+    ``rational=True`` of ``static`` the nodal values are w_i c, the homogeneous representation of the constant) or None = 0.
+    ``initial_acceleration=True`` solves rho M a0 = -R_static(y0) - rho a_M M ydot0 once (the value-value form as the mass
+    matrix; the penalty is not in it); False leaves a0 = 0, as the demo does.
+
+    ``y``, ``ydot``, ``yddot``: the state at time ``t`` (FE Functions; ``yddot`` None for backward Euler); ``t_alpha``: the
+    time the loads of the step being computed are read at; ``energy()``; ``last``: {"newton": relative norms, "iterations",
+    "active_points", "assembly_seconds", "solve_seconds"} of the last step, the seconds None when ``timing`` is off (they
+    cost three device synchronisations per Newton iteration)."""
+
+    timing = True
+
+    def __init__(self, spline, static, density, DELTA_T, RHO_INF=0.5, scheme="generalized_alpha", mass_damping=0.0, contact=None,
+                 y0=None, ydot0=None, t=0.0, initial_acceleration=True, absoluteTolerance=0.0):
+        from . import forms as _forms
+        from .common import Function
+        who = "NonlinearTransientProblem"
+        if scheme not in ("generalized_alpha", "backward_euler"):
+            raise ValueError("%s: scheme must be 'generalized_alpha' or 'backward_euler', not %r" % (who, scheme))
+        if DELTA_T is None or not float(DELTA_T) > 0.0:
+            raise ValueError("%s: DELTA_T must be positive, not %r" % (who, DELTA_T))
+        if scheme == "generalized_alpha" and not 0.0 <= float(RHO_INF) <= 1.0:
+            raise ValueError("%s: RHO_INF must lie in [0, 1], not %r" % (who, RHO_INF))
+        if not float(absoluteTolerance) >= 0.0:
+            raise ValueError("%s: absoluteTolerance = %r must not be negative" % (who, absoluteTolerance))
+        if spline._distributed():
+            raise NotImplementedError("%s: several ranks are not supported" % who)
+        if spline._caller_ordered():
+            raise NotImplementedError("%s: a spline with the caller's FE dof order (feOrder) is not supported" % who)
+        if not isinstance(static, (_forms.ShellResidual, _forms.HyperelasticResidual)):
+            raise NotImplementedError("%s: static = %r; a ShellResidual or a HyperelasticResidual carries the law" % (who, static))
+        self.spline, self.static, self.scheme = spline, static, scheme
+        self.DELTA_T, self.absoluteTolerance = float(DELTA_T), float(absoluteTolerance)
+        self._y = static.u
+        V = spline.V
+        self.y_old, self.ydot_old = Function(V), Function(V)
+        self._set_initial(self.y_old, y0)
+        self._set_initial(self.ydot_old, ydot0)
+        if scheme == "generalized_alpha":
+            self.yddot_old = Function(V)
+            self.integrator = GeneralizedAlphaIntegrator(float(RHO_INF), self.DELTA_T, self._y, [self.y_old, self.ydot_old, self.yddot_old],
+                                                         t=float(t))
+        else:
+            self.yddot_old = None
+            self.integrator = BackwardEulerIntegrator(self.DELTA_T, self._y, [self.y_old, self.ydot_old], t=float(t))
+        _vec_of(self._y)[:] = _vec_of(self.y_old)
+        self.dyn = _forms.DynamicResidual(static, self.integrator, density, mass_damping=mass_damping, contact=contact)
+        self._tangent = self.dyn.tangent()
+        self.last = None
+        self.steps_done = 0
+        if initial_acceleration and self.yddot_old is not None:
+            self._initial_acceleration()
+
+    def _set_initial(self, f, v):
+        """``v`` (an FE Function, IGA dofs, nF numbers or None) into the FE Function ``f``"""
+        import numpy
+        spline, fv = self.spline, _vec_of(f)
+        if v is None:
+            return
+        if hasattr(v, "vector"):
+            if _vec_of(v).size() != fv.size():
+                raise ValueError("NonlinearTransientProblem: an initial Function of %d nodal values, the space has %d"
+                                 % (_vec_of(v).size(), fv.size()))
+            fv[:] = _vec_of(v)
+        elif isinstance(v, DeviceVector):
+            if v.size() != spline.M.shape[1]:
+                raise ValueError("NonlinearTransientProblem: initial data of %d values, the spline has %d IGA dofs"
+                                 % (v.size(), spline.M.shape[1]))
+            spline.M.mult(v, fv)
+        else:
+            c = numpy.asarray(v, dtype=numpy.float64).ravel()
+            nF = len(spline.V.grids)
+            if c.size != nF:
+                raise ValueError("NonlinearTransientProblem: initial data must be an FE Function, a DeviceVector of %d IGA dofs or "
+                                 "%d numbers" % (spline.M.shape[1], nF))
+            n = fv.size() // nF
+            w = _vec_of(spline.cpFuncs[-1]).get_local() if self.static.rational else numpy.ones(n)
+            fv.set_local(numpy.concatenate([ci * w for ci in c]))
+        if hasattr(f, "invalidate_ghosts"):
+            f.invalidate_ghosts()
+
+    def _initial_acceleration(self):
+        """rho M a0 = -R_static(y0) - rho a_M M ydot0 in the IGA dofs; a0 = M (the solution) into ``yddot_old``"""
+        spline, dyn = self.spline, self.dyn
+        mass = dyn.mass_form().assemble_matrix(spline.V)
+        b = self.static.assemble_vector(spline.V)                   # (static.u = y = y0)
+        if dyn.mass_damping != 0.0:
+            b.axpy(dyn.mass_damping, mass.mult(_vec_of(self.ydot_old)))
+        _dev.vec_lincomb(b, [-1.0], [b])
+        spline.solveLinearSystem(spline.assembleMatrix(mass), spline.assembleVector(b), self.yddot_old)
+
+    # -- state
+    @property
+    def t(self):
+        """time of the state ``y``, ``ydot``, ``yddot``"""
+        return self.integrator.t - self.DELTA_T
+
+    @property
+    def t_alpha(self):
+        return self.dyn.t_alpha
+
+    @property
+    def y(self):
+        return self.y_old
+
+    @property
+    def ydot(self):
+        return self.ydot_old
+
+    @property
+    def yddot(self):
+        return self.yddot_old
+
+    def energy(self):
+        """``dyn.energy`` at the state of time ``t``: {"strain", "kinetic", "contact", "total"}"""
+        return self.dyn.energy(self.spline.V, y=self.y_old, ydot=self.ydot_old)
+
+    # -- stepping
+    def _predict(self):
+        it = self.integrator
+        if self.scheme == "generalized_alpha":
+            it.sameVelocityPredictor().evaluate(out=self._y)
+        else:
+            LinearCombination([(1.0, self.y_old), (self.DELTA_T, self.ydot_old)]).evaluate(out=self._y)
+        if hasattr(self._y, "invalidate_ghosts"):
+            self._y.invalidate_ghosts()
+
+    def step(self, n=1):
+        """advances the state by ``n`` steps of ``DELTA_T``"""
+        spline, dyn = self.spline, self.dyn
+        for _ in range(int(n)):
+            self._predict()
+            seconds = {"assembly": 0.0, "solve": 0.0} if self.timing else None
+            history = spline.solveNonlinearVariationalProblem(dyn, self._tangent, self._y, absoluteTolerance=self.absoluteTolerance,
+                                                              phaseSeconds=seconds)
+            active = dyn.active_points()
+            self.integrator.advance()
+            self.last = {"newton": history, "iterations": len(history) - 1, "active_points": active,
+                         "assembly_seconds": seconds["assembly"] if self.timing else None,
+                         "solve_seconds": seconds["solve"] if self.timing else None}
+            self.steps_done += 1
+        return self
