@@ -10,6 +10,7 @@ four products plus the input, so 4 eps times the sum of the absolute values of i
 longdouble run, 8 x the error of the float64 run of the same reference, never below 32 eps.  Energies: 32 eps of
 sum wdet |e|.  Flows: dofs to 1e-6 of the largest, Newton counts +- 1.  ``-s`` prints every figure.
 """
+import copy
 import itertools
 import json
 import os
@@ -188,25 +189,21 @@ def _functions(T, V, vectors):
     return out
 
 
-def _dynamic(T, name, c, spline, scheme="generalized_alpha"):
+def _dynamic(T, name, c, spline, body_force=None, device_law=True):
     info = DR.CASES[name]
     y, yo, vo, ao = _functions(T, spline.V, [c["y"]] + list(c["old"]))
     if info["kind"] == "shell":
-        static = T.F.ShellResidual(y, spline, c["material"], rational=c["rational"], pressure=info["pressure"])
+        static = T.F.ShellResidual(y, spline, c["material"], body_force=body_force, rational=c["rational"], pressure=info["pressure"],
+                                   device_law=device_law)
     else:
-        static = T.F.HyperelasticResidual(y, spline, c["material"], rational=c["rational"])
+        static = T.F.HyperelasticResidual(y, spline, c["material"], body_force=body_force, rational=c["rational"])
     it = T.ti.GeneralizedAlphaIntegrator(DR.CASE_RHO_INF, DR.CASE_DT, y, [yo, vo, ao])
     n, off, k = c["plane"]
     return static, it, T.F.DynamicResidual(static, it, c["density"], mass_damping=DR.CASE_DAMPING, contact=T.F.PlanePenalty(n, off, k))
 
 
-@pytest.mark.parametrize("name", sorted(DR.CASES))
-def test_assembled_residual_tangent_energy_and_reuse(T, name, monkeypatch):
-    c = _case(T, name)
-    spline, V, want = c["spline"], c["spline"].V, c["want"]
-    static, it, dyn = _dynamic(T, name, c, spline)
-    nF = c["dyn"][0].nF
-    untouched = dict(static.__dict__)
+def _counted_calls(T, monkeypatch):
+    """{"eval", "dynamics"}: the point evaluations of a field and the launches of ``tg_point_dynamics`` from here on"""
     calls = {"eval": 0, "dynamics": 0}
 
     def counted(key, f):
@@ -217,6 +214,17 @@ def test_assembled_residual_tangent_energy_and_reuse(T, name, monkeypatch):
     monkeypatch.setattr(T.dev, "quad_eval", counted("eval", T.dev.quad_eval))
     monkeypatch.setattr(T.dev, "quad_jet", counted("eval", T.dev.quad_jet))
     monkeypatch.setattr(T.dev, "point_dynamics", counted("dynamics", T.dev.point_dynamics))
+    return calls
+
+
+@pytest.mark.parametrize("name", sorted(DR.CASES))
+def test_assembled_residual_tangent_energy_and_reuse(T, name, monkeypatch):
+    c = _case(T, name)
+    spline, V, want = c["spline"], c["spline"].V, c["want"]
+    static, it, dyn = _dynamic(T, name, c, spline)
+    nF = c["dyn"][0].nF
+    untouched = dict(static.__dict__)
+    calls = _counted_calls(T, monkeypatch)
     assert dyn.scale == it.ALPHA_F
     R = dyn.assemble_vector(V).get_local() * dyn.scale
     first = dict(calls)
@@ -263,6 +271,44 @@ def test_assembled_residual_tangent_energy_and_reuse(T, name, monkeypatch):
     before = calls["eval"]
     dyn.assemble_vector(V)
     assert calls["eval"] == before + 2 * nF
+
+
+# per unit reference measure; large enough to move the residual by a hundredth of its largest entry, so that a force left
+# out, taken with the wrong sign or not divided by alpha_f misses the bound by many orders
+BODY_FORCE = {"cylinder-svk": (30.0, -20.0, 50.0), "annulus": (40.0, -70.0)}
+
+
+@pytest.mark.parametrize("name, variant", [("cylinder-svk", "body_force"), ("annulus", "body_force"), ("cylinder-svk", "host_law")])
+def test_assembled_body_force_and_host_law(T, name, variant, monkeypatch):
+    """a constant ``body_force`` on a shell and on a solid, and the shell law through its ``host`` method (``device_law=False``):
+    residual and tangent against the references, with the evaluations and launches of the test above"""
+    c = _case(T, name)
+    spline, V, want = c["spline"], c["spline"].V, c["want"]
+    f = BODY_FORCE[name] if variant == "body_force" else None
+    static, it, dyn = _dynamic(T, name, c, spline, body_force=f, device_law=variant != "host_law")
+    nF = c["dyn"][0].nF
+    want_R = want["R"]
+    if f is not None:
+        refs = [copy.copy(r) for r in c["dyn"]]
+        for r in refs:
+            r.f = np.broadcast_to(np.asarray(f).astype(r.dtype), (r.wdet.size, r.nF))
+        want_R = tuple(r.residual(c["y"], c["old"]) for r in refs)
+        moved = float(np.max(np.abs(want_R[0] - want["R"][0])) / np.max(np.abs(want_R[0])))
+        print("%-62s the body force moves the residual by %.2e of its largest entry" % (name, moved))
+        assert moved > 1e-3
+    calls = _counted_calls(T, monkeypatch)
+    R = dyn.assemble_vector(V).get_local() * dyn.scale
+    first = dict(calls)
+    assert first == {"eval": 2 * nF, "dynamics": 1}
+    assert dyn.active_points() == want["active"]
+    _hold("%s, %s: residual x scale" % (name, variant), R, *want_R)
+    tan = dyn.tangent()
+    K = tan.assemble_matrix(V).to_scipy().toarray() * dyn.scale
+    assert calls == {"eval": first["eval"] + nF, "dynamics": 2}
+    assert tan.symmetric is True and dyn.active_points() == want["active"]
+    _hold("%s, %s: tangent x scale" % (name, variant), K, *want["K"])
+    dyn.assemble_vector(V)
+    assert calls == {"eval": first["eval"] + 2 * nF, "dynamics": 3}
 
 
 def test_backward_euler_residual_and_tangent(T):

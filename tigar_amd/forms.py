@@ -17,6 +17,8 @@ selects on quads/hexes [ext], demos/poisson/poisson.py:89).  The d-dimensional o
 expanded on the GPU (``tg_kron_sum_csr`` / ``tg_vec_tensor3``); they are NOT timed as part
 of the hot path.
 """
+import collections
+
 import numpy
 import scipy.sparse as sp
 
@@ -947,17 +949,25 @@ def _nodal_vector(u, nF, n, who):
 def _field_by_field(uv, nF, n, call, size=None):
     """``call(u_i)`` for the nF fields of the nodal vector ``uv``, each copied into one scratch vector of n values.  With
     ``size`` the results (DeviceVectors of that many values) are gathered field after field in one DeviceVector, else
-    they are returned as a list."""
+    they are returned as a list.  A tuple of sizes: ``call`` returns that many DeviceVectors, each gathered in one of its
+    own, in the order of the tuple."""
     ui = _dev.DeviceVector(n, zero=False)
-    out = _dev.DeviceVector(nF * size, zero=False) if size is not None else []
+    sizes = size if isinstance(size, tuple) else (size,)
+    outs = [[] if s is None else _dev.DeviceVector(nF * s, zero=False) for s in sizes]
     for i in range(nF):
         _dev.vec_copy_range(ui, 0, uv, i * n, n)
-        part = call(ui)
-        if size is None:
-            out.append(part)
-        else:
-            _dev.vec_copy_range(out, i * size, part, 0, size)
-    return out
+        parts = call(ui)
+        for out, s, part in zip(outs, sizes, parts if isinstance(size, tuple) else (parts,)):
+            if s is None:
+                out.append(part)
+            else:
+                _dev.vec_copy_range(out, i * s, part, 0, s)
+    return tuple(outs) if isinstance(size, tuple) else outs[0]
+
+
+def _values_at_points(pts, nodal, nF, n, rational):
+    """the nF fields of a nodal vector at the points, field after field (``tg_quad_eval``)"""
+    return _field_by_field(nodal, nF, n, lambda ui: _dev.quad_eval(pts.verts, pts.p, pts.cp, ui, nq=pts.nq, rational=rational), pts.npts)
 
 
 def _law_result(out, who, call, names, shapes):
@@ -973,31 +983,111 @@ def _law_result(out, who, call, names, shapes):
 
 
 class _LawTangent(object):
-    """The tangent form of a residual with a point law (``res.builtin``, ``res._host_symmetric``, ``res.law``): the
-    ``_form_class`` of the tangent data ``_data(V)`` at the current state.  ``symmetric``: True for a built-in law (the
-    tangent derives from an energy: major symmetry by the law, in the matrix to rounding); for a host law that of the last
-    assembled tangent and False before the first assembly (see ``_QuasilinearTangent``)."""
-    _form_class = None
+    """The tangent form of a ``_PointLawResidual``: the form the residual makes of its point tangent at the current state
+    (``_tangent_form``).  ``symmetric`` is the residual's ``_law_symmetric()``: True for a built-in law (the tangent derives
+    from an energy: major symmetry by the law, in the matrix to rounding); for a host law that of the last assembled tangent
+    and False before the first assembly (see ``_QuasilinearTangent``).  Row blocks are refused before the law runs."""
 
     def __init__(self, res):
-        self.res, self.geometry, self.symmetric = res, res.geometry, bool(res.builtin)
+        self.res, self.geometry, self.symmetric = res, res.geometry, res._law_symmetric()
 
-    def _rows(self, V, row0, row1, block):
-        """a refusal of row blocks that comes before the law is evaluated (none: the form refuses)"""
-
-    def _form(self, V):
+    def _form(self, V, row0, row1, block):
         res = self.res
-        form = self._form_class(res.geometry, self._data(V), nq=res.nq, rational=res.rational)
-        form._symmetric_hint = self.symmetric = True if res.builtin else bool(res._host_symmetric)
+        g, nF, pts = res._scope(V, res._who + ".tangent", row0, row1, block)
+        form = res._tangent_form(pts, nF, res.law(V, False, True).tangent)
+        form._symmetric_hint = self.symmetric = res._law_symmetric()
         return form
 
     def assemble_block(self, V, i, j, row0=None, row1=None):
-        self._rows(V, row0, row1, True)
-        return self._form(V).assemble_block(V, i, j, row0, row1)
+        return self._form(V, row0, row1, True).assemble_block(V, i, j, row0, row1)
 
     def assemble_matrix(self, V, row0=None, row1=None):
-        self._rows(V, row0, row1, False)
-        return self._form(V).assemble_matrix(V, row0, row1)
+        return self._form(V, row0, row1, False).assemble_matrix(V, row0, row1)
+
+
+# [npts, nF, nK, nF, nK] point tangents (A[q, i, K, j, L], T[q, i, alpha, j, beta]) go to the device block by block, in
+# the order (i, j, K, L, q) that ``tg_coef_transform_blocks`` and ``tg_jet_transform`` read; their major symmetry swaps (i, K)
+# with (j, L)
+_BLOCK_ORDER, _MAJOR_SWAP = (0, 2, 1, 3), (2, 3, 0, 1)
+
+
+_SlotScaling = collections.namedtuple("_SlotScaling", "coef sigma after")
+
+
+class _PointLawResidual(object):
+    """A residual whose integrand is a law at the points: u is evaluated there field by field (with ``_keeps_u`` its point
+    values stay in ``_u_points``; off for a residual the user built), the law -- ``_device_law``, or ``_host_law`` whose arrays
+    are uploaded -- gives (load, tangent, psi), inadmissible points are refused, and the point data go through
+    ``_load_vector`` and ``_tangent_form``.  ``ShellResidual`` and ``HyperelasticResidual`` say these, their scope (``_kind``,
+    ``_check_space``), and where the value slots of the point data live, which is all ``DynamicResidual`` asks:
+      ``nJ``, ``_value_load(out)``   the stride of the slots, and the vector whose value slots take inertia and penalty
+      ``_slot_scaling(af, m_u, k)``  ``_SlotScaling``: ``coef`` of ``tg_point_dynamics`` for R / alpha_f, ``sigma`` = what the kernel
+                                 multiplies the law's load by, ``after`` = the factor of the assembled vector (None: none).
+                                 A shell: sigma = 1 / alpha_f; a solid: every value term times alpha_f, 1 / alpha_f after
+      ``_load_vector(V, out, values, sigma)``   the load vector with those values; a load assembled by itself times ``sigma``
+      ``_value_tangent``, ``_tangent_form``     the value-value entries of the tangent, and the form with them"""
+    _who = _kind = _names = nJ = None
+    _keeps_u, _u_points = False, None
+
+    def __init__(self, u, geometry, material, known, builtin, body_force, nq, rational, device_law=True):
+        if geometry is None:
+            raise ValueError("%s: point data live on a mapped patch (geometry=...)" % self._who)
+        if not callable(getattr(material, "host", None)):
+            raise ValueError("%s: unknown material %r; %s" % (self._who, material, known))
+        self.u, self.geometry, self.material, self.builtin = u, geometry, material, bool(builtin)
+        self.body_force, self.nq, self.rational = body_force, nq, bool(rational)
+        self.device_law = bool(device_law) and self.builtin
+        self._host_symmetric = False
+
+    def _arguments(self):
+        """the keywords of the constructor, as the object holds them now"""
+        return dict(body_force=self.body_force, nq=self.nq, rational=self.rational)
+
+    def _at(self, u, keeps_u=False):
+        """The same residual at another ``u``: built from the arguments this object holds now.  It shares no cache with
+        this object and does not modify it.  ``keeps_u``: it keeps the point values of u of its last evaluation."""
+        other = type(self)(u, self.geometry, self.material, **self._arguments())
+        other._keeps_u = bool(keeps_u)
+        return other
+
+    def _check_space(self, g, nF, who):
+        """a refusal of the space that ``_point_scope`` does not know"""
+
+    def _scope(self, V, who, row0=None, row1=None, block=False):
+        """(node grid, nF, points) of the space, or the refusal: of the scope, of row blocks, of the space"""
+        g, nF = _point_scope(self.geometry, V, who, self._kind)[:2]
+        _whole_rows((1 if block else nF) * g.num_nodes(), row0, row1, who, "patch")
+        self._check_space(g, nF, who)
+        return g, nF, _vector_points(self.geometry, self.nq, who)
+
+    def _law(self, at, load, tangent, energy):
+        """(load, tangent, psi) of the evaluation ``at`` as DeviceVectors (None where not asked for)"""
+        if self.device_law:
+            return self._device_law(at, load, tangent, energy)
+        pts, who = at.pts, self._who
+        loadh, Th, psih, shape = self._host_law(at, load or tangent)
+        s = _point_data(loadh, pts, shape, "%s: %s" % (who, self._names[0])) if load else None
+        T = None
+        if tangent:
+            T, self._host_symmetric = _point_data(Th, pts, shape + shape, "%s: %s" % (who, self._names[1]), _BLOCK_ORDER, _MAJOR_SWAP)
+        return s, T, (_dev.DeviceVector(data=psih) if energy else None)
+
+    def _law_symmetric(self):
+        """whether the law's tangent is symmetric: by the law, or by the bits of a host law's last tangent"""
+        return True if self.builtin else bool(self._host_symmetric)
+
+    def assemble_vector(self, V, row0=None, row1=None):
+        self._scope(V, self._who, row0, row1)
+        return self._load_vector(V, self.law(V))
+
+    def energy(self, V=None):
+        if V is None:
+            V = self.u.function_space()
+        out = self.law(V, False, False, True)
+        return out.pts.weights.inner(out.psi)
+
+    def tangent(self):
+        return _LawTangent(self)
 
 
 def _det_inv(F):
@@ -1082,12 +1172,6 @@ class NeoHookean(_Material):
         return P, A, psi
 
 
-# [npts, nF, nK, nF, nK] point tangents (A[q, i, K, j, L], T[q, i, alpha, j, beta]) go to the device block by block, in
-# the order (i, j, K, L, q) that ``tg_coef_transform_blocks`` and ``tg_jet_transform`` read; their major symmetry swaps (i, K)
-# with (j, L)
-_BLOCK_ORDER, _MAJOR_SWAP = (0, 2, 1, 3), (2, 3, 0, 1)
-
-
 class VectorCoefficientForm(object):
     """a(u, v) = int d_K v_i A_iKjL d_L u_j + v_i M_ij u_j dx on the mapped patch for a vector-valued unknown: nF = nsd = d
     fields on one continuous Q_p node grid, dofs field after field (the space of ``ElasticityForm``); grad and dx as
@@ -1110,7 +1194,8 @@ class VectorCoefficientForm(object):
         if tangent is None:
             raise ValueError("VectorCoefficientForm: no tangent")
         self.geometry, self.tangent, self.reaction, self.nq, self.rational = geometry, tangent, reaction, nq, bool(rational)
-        self._symmetric_hint = None          # (set by a caller whose law proves the symmetry: HyperelasticResidual)
+        # (set by a caller who proves the symmetry: HyperelasticResidual by its law, of a reaction it wrote on the device)
+        self._symmetric_hint = self._reaction_hint = None
 
     def coefficients(self, V):
         """(points, A, M, symmetric) with the point data as DeviceVectors in the block layout (M None = absent): computed
@@ -1125,7 +1210,7 @@ class VectorCoefficientForm(object):
                              hint=self._symmetric_hint)
         M, symM = None, True
         if self.reaction is not None:
-            M, symM = _point_data(self.reaction, pts, (nF, nF), who + ": reaction", swap=(1, 0))
+            M, symM = _point_data(self.reaction, pts, (nF, nF), who + ": reaction", swap=(1, 0), hint=self._reaction_hint)
         return pts, A, M, bool(sym and symM)
 
     @property
@@ -1203,7 +1288,11 @@ class VectorLoadForm(object):
         return _field_loads(pts, n, nF, s, F, self.rational)
 
 
-class HyperelasticResidual(object):
+_SolidGradient = collections.namedtuple("_SolidGradient", "pts g nF H")
+_SolidLaw = collections.namedtuple("_SolidLaw", "pts g nF load tangent psi")
+
+
+class HyperelasticResidual(_PointLawResidual):
     """Residual of finite-strain elasticity on the mapped patch, R(v) = int P(F) : grad v - f . v dx with F = I + grad u: what
     ``derivative(psi*spline.dx, u)`` of the reference gives for a solid.  The reference configuration is the patch
     (x = F_geom(xi), grad = ``spline.grad``); ``u`` the displacement ``Function`` on the space of ``ElasticityForm`` (nF = nsd
@@ -1221,75 +1310,86 @@ class HyperelasticResidual(object):
     of such points and the smallest J.  Runs under ``solveNonlinearVariationalProblem`` and inside ``Sum`` with
     ``BoundaryLoadForm`` tractions.  ``rational``: u_i = u_h,i / W_h, tested against phi / W_h."""
 
+    _who, _kind, _names, nJ = "HyperelasticResidual", "vector", ("P", "A"), 1
+
     def __init__(self, u, geometry, material, body_force=None, nq=None, rational=False):
-        if geometry is None:
-            raise ValueError("HyperelasticResidual: point tangents live on a mapped patch (geometry=...)")
-        builtin = isinstance(material, _Material) and material.kind in (0, 1, 2)
-        if not builtin and not callable(getattr(material, "host", None)):
-            raise ValueError("HyperelasticResidual: unknown material %r; LinearElastic, StVenantKirchhoff, NeoHookean, or an "
-                             "object with host(F) -> (P, A, psi)" % (material,))
-        self.u, self.geometry, self.material, self.builtin = u, geometry, material, builtin
-        self.body_force, self.nq, self.rational = body_force, nq, bool(rational)
-        self._host_symmetric = False
+        _PointLawResidual.__init__(self, u, geometry, material, "LinearElastic, StVenantKirchhoff, NeoHookean, or an object with "
+                                   "host(F) -> (P, A, psi)", isinstance(material, _Material) and material.kind in (0, 1, 2),
+                                   body_force, nq, rational)
 
     def grad_u(self, V):
         """(points, node grid, nF, DeviceVector with d u_i / d x_K at (i nsd + K) npts + q)"""
-        who = "HyperelasticResidual"
-        g, nF = _point_scope(self.geometry, V, who, "vector")
-        pts = _vector_points(self.geometry, self.nq, who)
-        uv = _nodal_vector(self.u, nF, g.num_nodes(), who)
-        grad = lambda ui: _dev.quad_eval(pts.verts, pts.p, pts.cp, ui, grad=True, nq=pts.nq, rational=self.rational)[1]
-        return pts, g, nF, _field_by_field(uv, nF, g.num_nodes(), grad, pts.nsd * pts.npts)
+        g, nF, pts = self._scope(V, self._who)
+        n, size = g.num_nodes(), pts.nsd * pts.npts
+        uv = _nodal_vector(self.u, nF, n, self._who)
+        both = lambda ui: _dev.quad_eval(pts.verts, pts.p, pts.cp, ui, grad=True, nq=pts.nq, rational=self.rational)
+        if self._keeps_u:                       # the values the kernel writes next to the gradient
+            self._u_points, H = _field_by_field(uv, nF, n, both, (pts.npts, size))
+        else:
+            H = _field_by_field(uv, nF, n, lambda ui: both(ui)[1], size)
+        return _SolidGradient(pts, g, nF, H)
 
     def law(self, V, stress=True, tangent=False, energy=False):
         """(points, node grid, nF, P, A, psi) at the current state, as DeviceVectors (None where not asked for)"""
-        pts, g, nF, H = self.grad_u(V)
-        nsd, npts = pts.nsd, pts.npts
-        if self.builtin:
-            m = self.material
-            P, A, psi, nbad, jmin = _dev.material_points(m.kind, m.lmbda, m.mu, nsd, H, stress, tangent, energy)
-            if nbad > 0:
-                raise RuntimeError("HyperelasticResidual: %d quadrature points with J <= 0 (smallest J = %g): %s is not "
-                                   "defined there" % (nbad, jmin, type(m).__name__))
-            return pts, g, nF, P, A, psi
-        F = point_unblock(H.get_local(), npts, (nsd, nsd)) + numpy.eye(nsd)
-        Ph, Ah, psih = _law_result(self.material.host(F), "HyperelasticResidual", "material.host(F)", "(P, A, psi)",
+        at = _SolidGradient(*self.grad_u(V))
+        return _SolidLaw(at.pts, at.g, at.nF, *self._law(at, stress, tangent, energy))
+
+    def _device_law(self, at, stress, tangent, energy):
+        m = self.material
+        P, A, psi, nbad, jmin = _dev.material_points(m.kind, m.lmbda, m.mu, at.pts.nsd, at.H, stress, tangent, energy)
+        if nbad > 0:
+            raise RuntimeError("HyperelasticResidual: %d quadrature points with J <= 0 (smallest J = %g): %s is not "
+                               "defined there" % (nbad, jmin, type(m).__name__))
+        return P, A, psi
+
+    def _host_law(self, at, loads):
+        nsd, npts = at.pts.nsd, at.pts.npts
+        F = point_unblock(at.H.get_local(), npts, (nsd, nsd)) + numpy.eye(nsd)
+        Ph, Ah, psih = _law_result(self.material.host(F), self._who, "material.host(F)", "(P, A, psi)",
                                    [(npts, nsd, nsd), (npts, nsd, nsd, nsd, nsd), (npts,)])
-        P = _point_data(Ph, pts, (nsd, nsd), "HyperelasticResidual: P") if stress else None
-        A = None
-        if tangent:
-            A, self._host_symmetric = _point_data(Ah, pts, (nsd,) * 4, "HyperelasticResidual: A", _BLOCK_ORDER, _MAJOR_SWAP)
-        return pts, g, nF, P, A, (_dev.DeviceVector(data=psih) if energy else None)
+        return Ph, Ah, psih, (nsd, nsd)
 
-    def assemble_vector(self, V, row0=None, row1=None):
-        who = "HyperelasticResidual"
-        g, nF = _point_scope(self.geometry, V, who, "vector")
-        _whole_rows(nF * g.num_nodes(), row0, row1, who, "patch")
-        pts, g, nF, P, _, _ = self.law(V)
-        s = None
-        if self.body_force is not None:
-            s = _per_points(self, "_fq", pts, lambda: _field_values(pts, self.body_force, nF, who + ": body_force", scale=-1.0))
-        return _field_loads(pts, g.num_nodes(), nF, s, P, self.rational)
+    def _body_force(self, pts, nF):
+        """-f at the points, one DeviceVector per field (None without a body force): once per set of points"""
+        if self.body_force is None:
+            return None
+        return _per_points(self, "_fq", pts, lambda: _field_values(pts, self.body_force, nF, self._who + ": body_force", scale=-1.0))
 
-    def energy(self, V=None):
-        if V is None:
-            V = self.u.function_space()
-        pts, g, nF, _, _, psi = self.law(V, stress=False, energy=True)
-        return pts.weights.inner(psi)
+    def _load_vector(self, V, out, values=None, sigma=1.0):
+        """the load of the flux P next to a value load: of -f, or of the ``values`` of ``_value_load``, which hold -f
+        already (``sigma`` has nothing to scale here: the body force is among the values)"""
+        pts, nF, npts = out.pts, out.nF, out.pts.npts
+        if values is None:
+            s = self._body_force(pts, nF)
+        else:
+            s = [_dev.DeviceVector(npts, zero=False) for _ in range(nF)]
+            for i in range(nF):
+                _dev.vec_copy_range(s[i], 0, values, i * npts, npts)
+        return _field_loads(pts, out.g.num_nodes(), nF, s, out.load, self.rational)
 
-    def tangent(self):
-        return _HyperelasticTangent(self)
+    # -- the value slots: the stress is a flux, so they are vectors of their own (nJ = 1) next to P and A, and every term
+    #    they hold is multiplied by alpha_f; the assembled vector is divided once
+    def _value_load(self, out):
+        pts, nF, npts = out.pts, out.nF, out.pts.npts
+        s = _dev.DeviceVector(nF * npts)
+        for i, fi in enumerate(self._body_force(pts, nF) or ()):
+            _dev.vec_copy_range(s, i * npts, fi, 0, npts)
+        return s
 
+    def _slot_scaling(self, af, m_u, k):
+        return _SlotScaling((1.0, af * m_u, af, 0.0, k, 0.0, 0.0), 1.0, 1.0 / af if af != 1.0 else None)
 
-class _HyperelasticTangent(_LawTangent):
-    _form_class = VectorCoefficientForm
+    def _value_tangent(self, pts, nF, tangent=None):
+        return _dev.DeviceVector(nF * nF * pts.npts)
 
-    def _data(self, V):
-        return self.res.law(V, stress=False, tangent=True)[4]
-
-    def _rows(self, V, row0, row1, block):
-        g, nF = _point_scope(self.res.geometry, V, "HyperelasticResidual.tangent", "vector")
-        _whole_rows((1 if block else nF) * g.num_nodes(), row0, row1, "HyperelasticResidual.tangent", "patch")
+    def _tangent_form(self, pts, nF, tangent, values=None):
+        """the ``VectorCoefficientForm`` of A (None: of zeros) with the value-value entries as its reaction: they were
+        written on the device, density and k n (x) n, and are symmetric by construction"""
+        if tangent is None:
+            tangent = _dev.DeviceVector(nF ** 4 * pts.npts)
+        form = VectorCoefficientForm(self.geometry, tangent, reaction=values, nq=self.nq, rational=self.rational)
+        form._reaction_hint = None if values is None else True
+        return form
 
 
 # ---- second-derivative point forms (csrc/tg_jet.hip): spline.parametricGrad of the reference and its derivative ------------
@@ -1726,7 +1826,11 @@ def shell_pressure_host(pressure, Xjet, ujet):
     return s, T
 
 
-class ShellResidual(object):
+_ShellJets = collections.namedtuple("_ShellJets", "pts g Xjet ujet")
+_ShellLaw = collections.namedtuple("_ShellLaw", "pts g load tangent psi")
+
+
+class ShellResidual(_PointLawResidual):
     """Residual of a Kirchhoff-Love shell on the mapped patch, R(v) = D psi[v] - f . v per unit reference area: what
     ``derivative(psi*spline.dx, u)`` of the reference gives for the energy of demos/kl-shell-svk.  The reference surface is the
     patch (d = 2, nsd = 3); ``u`` the displacement ``Function`` on nF = 3 fields of its scalar space, read at assembly time.
@@ -1748,23 +1852,20 @@ class ShellResidual(object):
     ``KirchhoffLoveHyper`` also det Gm <= 0 or det C_2D <= 0 at a thickness point; the material's ``degenerate`` on the host
     route -- raise ``RuntimeError`` naming their number.  ``rational``: u_i = u_h,i / W_h, tested against phi / W_h."""
 
+    _who, _kind, _names, nJ = "ShellResidual", "jet", ("s", "T"), 6
+
     def __init__(self, u, geometry, material, body_force=None, nq=None, rational=False, device_law=True, pressure=None):
-        if geometry is None:
-            raise ValueError("ShellResidual: point data live on a mapped patch (geometry=...)")
-        if not callable(getattr(material, "host", None)):
-            raise ValueError("ShellResidual: unknown material %r; KirchhoffLoveSVK, KirchhoffLoveHyper, or an object with "
-                             "host(Xjet, ujet) -> (psi, s, T)" % (material,))
-        if pressure is not None and not callable(pressure):
-            pressure = float(pressure)
-        self.u, self.geometry, self.material = u, geometry, material
-        self.body_force, self.nq, self.rational, self.pressure = body_force, nq, bool(rational), pressure
         # a law of the device: the material names its kind, its parameters and its inadmissible points
-        self.builtin = getattr(material, "kind", None) in _dev.SHELL_KINDS.values() and callable(getattr(material, "params", None))
-        self.device_law = bool(device_law) and self.builtin
-        self._host_symmetric = False
+        builtin = getattr(material, "kind", None) in _dev.SHELL_KINDS.values() and callable(getattr(material, "params", None))
+        _PointLawResidual.__init__(self, u, geometry, material, "KirchhoffLoveSVK, KirchhoffLoveHyper, or an object with "
+                                   "host(Xjet, ujet) -> (psi, s, T)", builtin, body_force, nq, rational, device_law)
+        self.pressure = pressure if pressure is None or callable(pressure) else float(pressure)
         self._load = None
         if body_force is not None:
             self._load = VectorJetLoadForm(self._force_jets, geometry, nq=nq, rational=rational)
+
+    def _arguments(self):
+        return dict(_PointLawResidual._arguments(self), device_law=self.device_law, pressure=self.pressure)
 
     def _pressure(self):
         """the follower pressure now: a number, or None"""
@@ -1781,82 +1882,73 @@ class ShellResidual(object):
         s[:, :, 0] = point_array(f(x) if callable(f) else f, x.shape[0], (3,), "ShellResidual: body_force")
         return s
 
-    def jets(self, V):
-        """(points, node grid, Xjet, ujet): the jets of the reference surface and of the three displacement fields as
-        DeviceVectors of 18 npts values (component alpha of coordinate / field c at (6 c + alpha) npts + q)"""
-        who = "ShellResidual"
-        g, nF, nJ = _point_scope(self.geometry, V, who, "jet")
+    def _check_space(self, g, nF, who):
         nsd = len(self.geometry.cpFuncs) - 1
         if g.dim() != 2 or nsd != 3 or nF != 3:
             raise NotImplementedError("%s: a shell is a surface in space with a displacement of three fields (d = %d, nsd = %d, "
                                       "nFields = %d)" % (who, g.dim(), nsd, nF))
-        pts = _vector_points(self.geometry, self.nq, who)
-        uv = _nodal_vector(self.u, nF, g.num_nodes(), who)
+
+    def jets(self, V):
+        """(points, node grid, Xjet, ujet): the jets of the reference surface and of the three displacement fields as
+        DeviceVectors of 18 npts values (component alpha of coordinate / field c at (6 c + alpha) npts + q)"""
+        g, nF, pts = self._scope(V, self._who)
+        uv = _nodal_vector(self.u, nF, g.num_nodes(), self._who)
         X = _per_points(self, "_Xjet", pts, lambda: _dev.quad_geometry_jet(pts.verts, pts.p, pts.cp, nq=pts.nq))
         jet = lambda ui: _dev.quad_jet(pts.verts, pts.p, pts.cp, ui, nq=pts.nq, rational=self.rational)
-        return pts, g, X, _field_by_field(uv, nF, g.num_nodes(), jet, nJ * pts.npts)
+        U = _field_by_field(uv, nF, g.num_nodes(), jet, self.nJ * pts.npts)
+        if self._keeps_u:                       # the value slots of the jets
+            self._u_points = U
+        return _ShellJets(pts, g, X, U)
 
     def law(self, V, load=True, tangent=False, energy=False):
         """(points, node grid, s, T, psi) at the current state, as DeviceVectors in the layouts of ``tg_jet_load_transform``
         and ``tg_jet_transform`` (None where not asked for)"""
-        pts, g, X, U = self.jets(V)
-        npts = pts.npts
-        P = self._pressure()
-        if self.device_law:
-            m = self.material
-            s, T, psi, nbad = _dev.shell_law_points(m.kind, m.params(), X, U, load, tangent, energy)
-            self._refuse(nbad)
-            if P is not None and (load or tangent):
-                _dev.shell_pressure_points(P, X, U, s, T)
-            return pts, g, s, T, psi
-        Xh, Uh = point_unblock(X.get_local(), npts, (3, 6)), point_unblock(U.get_local(), npts, (3, 6))
-        self._refuse(int(numpy.sum(getattr(self.material, "degenerate", KirchhoffLoveSVK.degenerate)(Xh, Uh))))
-        psih, sh, Th = _law_result(self.material.host(Xh, Uh), "ShellResidual", "material.host(Xjet, ujet)", "(psi, s, T)",
-                                   [(npts,), (npts, 3, 6), (npts, 3, 6, 3, 6)])
+        at = _ShellJets(*self.jets(V))
+        return _ShellLaw(at.pts, at.g, *self._law(at, load, tangent, energy))
+
+    def _device_law(self, at, load, tangent, energy):
+        m, P = self.material, self._pressure()
+        s, T, psi, nbad = _dev.shell_law_points(m.kind, m.params(), at.Xjet, at.ujet, load, tangent, energy)
+        self._refuse(nbad)
         if P is not None and (load or tangent):
+            _dev.shell_pressure_points(P, at.Xjet, at.ujet, s, T)
+        return s, T, psi
+
+    def _host_law(self, at, loads):
+        npts, P = at.pts.npts, self._pressure()
+        Xh, Uh = point_unblock(at.Xjet.get_local(), npts, (3, 6)), point_unblock(at.ujet.get_local(), npts, (3, 6))
+        self._refuse(int(numpy.sum(getattr(self.material, "degenerate", KirchhoffLoveSVK.degenerate)(Xh, Uh))))
+        psih, sh, Th = _law_result(self.material.host(Xh, Uh), self._who, "material.host(Xjet, ujet)", "(psi, s, T)",
+                                   [(npts,), (npts, 3, 6), (npts, 3, 6, 3, 6)])
+        if P is not None and loads:
             sp, Tp = shell_pressure_host(P, Xh, Uh)
             sh, Th = sh + sp, Th + Tp
-        s = _point_data(sh, pts, (3, 6), "ShellResidual: s") if load else None
-        T = None
-        if tangent:
-            T, self._host_symmetric = _point_data(Th, pts, (3, 6, 3, 6), "ShellResidual: T", _BLOCK_ORDER, _MAJOR_SWAP)
-        return pts, g, s, T, (_dev.DeviceVector(data=psih) if energy else None)
+        return sh, Th, psih, (3, 6)
 
-    def assemble_vector(self, V, row0=None, row1=None):
-        who = "ShellResidual"
-        g, nF, nJ = _point_scope(self.geometry, V, who, "jet")
-        _whole_rows(nF * g.num_nodes(), row0, row1, who, "patch")
-        pts, g, s, _, _ = self.law(V)
-        r = VectorJetLoadForm(s, self.geometry, nq=self.nq, rational=self.rational).assemble_vector(V)
+    def _law_symmetric(self):
+        return _PointLawResidual._law_symmetric(self) and self.pressure is None      # a follower load has no potential
+
+    def _load_vector(self, V, out, values=None, sigma=1.0):
+        """the jet load of s minus ``sigma`` times the load of f, which is assembled by itself (``values`` are the value
+        slots of s: there is nothing to put back)"""
+        r = VectorJetLoadForm(out.load, self.geometry, nq=self.nq, rational=self.rational).assemble_vector(V)
         if self._load is not None:
-            r.axpy(-1.0, self._load.assemble_vector(V))
+            r.axpy(-sigma, self._load.assemble_vector(V))
         return r
 
-    def energy(self, V=None):
-        if V is None:
-            V = self.u.function_space()
-        pts, g, _, _, psi = self.law(V, load=False, energy=True)
-        return pts.weights.inner(psi)
+    # -- the value slots: they sit inside s and T, at stride nJ = 6, so the point kernel scales s itself (sigma = 1 / alpha_f)
+    def _value_load(self, out):
+        return out.load
 
-    def tangent(self):
-        return _ShellTangent(self)
+    def _slot_scaling(self, af, m_u, k):
+        return _SlotScaling((1.0 / af, m_u, 1.0, 0.0, k / af, 0.0, 0.0), 1.0 / af, None)
 
+    def _value_tangent(self, pts, nF, tangent=None):
+        return tangent if tangent is not None else _dev.DeviceVector(nF * nF * 36 * pts.npts)
 
-class _ShellTangent(_LawTangent):
-    _form_class = VectorJetCoefficientForm
-
-    def __init__(self, res):
-        _LawTangent.__init__(self, res)
-        self.symmetric = self.symmetric and res.pressure is None
-
-    def _form(self, V):
-        form = _LawTangent._form(self, V)
-        if self.res.pressure is not None:               # a follower load has no potential
-            form._symmetric_hint = self.symmetric = False
-        return form
-
-    def _data(self, V):
-        return self.res.law(V, load=False, tangent=True)[3]
+    def _tangent_form(self, pts, nF, tangent, values=None):
+        """the ``VectorJetCoefficientForm`` of T, or of the ``values`` of ``_value_tangent``: T with its value-value entries"""
+        return VectorJetCoefficientForm(self.geometry, tangent if values is None else values, nq=self.nq, rational=self.rational)
 
 
 # ---- structural dynamics (csrc/tg_dynamics.hip): inertia, mass damping and a rigid plane at the points ----------------------
@@ -1885,48 +1977,6 @@ class PlanePenalty(object):
         return x.dtype.type(self.offset) - x @ self.normal.astype(x.dtype)
 
 
-class _ShellTwin(ShellResidual):
-    """a ``ShellResidual`` that keeps the jets of u of its last evaluation (``held``: what ``tg_point_dynamics`` reads)"""
-    held = None
-
-    def jets(self, V):
-        out = ShellResidual.jets(self, V)
-        self.held = out[3]
-        return out
-
-
-class _SolidTwin(HyperelasticResidual):
-    """a ``HyperelasticResidual`` that keeps the point values of u (``held``) which ``tg_quad_eval`` returns next to the gradient
-    and ``HyperelasticResidual.grad_u`` drops: the same calls, both results gathered field after field"""
-    held = None
-
-    def grad_u(self, V):
-        who = "DynamicResidual"
-        g, nF = _point_scope(self.geometry, V, who, "vector")
-        pts = _vector_points(self.geometry, self.nq, who)
-        n, npts = g.num_nodes(), pts.npts
-        uv = _nodal_vector(self.u, nF, n, who)
-        ui = _dev.DeviceVector(n, zero=False)
-        val, grad = _dev.DeviceVector(nF * npts, zero=False), _dev.DeviceVector(nF * pts.nsd * npts, zero=False)
-        for i in range(nF):
-            _dev.vec_copy_range(ui, 0, uv, i * n, n)
-            v, dv = _dev.quad_eval(pts.verts, pts.p, pts.cp, ui, grad=True, nq=pts.nq, rational=self.rational)
-            _dev.vec_copy_range(val, i * npts, v, 0, npts)
-            _dev.vec_copy_range(grad, i * pts.nsd * npts, dv, 0, pts.nsd * npts)
-        self.held = val
-        return pts, g, nF, grad
-
-
-class _ReactionForm(VectorCoefficientForm):
-    """a ``VectorCoefficientForm`` whose reaction is symmetric by construction (density and k n (x) n written on the device):
-    it is not read back to compare its bits"""
-
-    def _static_coefficients(self, pts, nF, who):
-        A, sym = _point_data(self.tangent, pts, (nF, pts.nsd, nF, pts.nsd), who + ": tangent", _BLOCK_ORDER, _MAJOR_SWAP,
-                             hint=self._symmetric_hint)
-        return pts, A, self.reaction, bool(sym)
-
-
 class DynamicResidual(object):
     """Residual of nonlinear structural dynamics on the mapped patch, the formulation of
     demos/kl-shell-svk/dynamic-tspline.py:100-293 of the reference:
@@ -1936,9 +1986,11 @@ class DynamicResidual(object):
         dR/dy   = rho (c_a + a_M c_v) M + alpha_f [K_law + K_pressure + k [g > 0] n (x) n](y_alpha)
 
     ``static``: a ``ShellResidual`` or a ``HyperelasticResidual`` whose ``u`` is the Function ``integrator`` solves for; its
-    law, pressure and body force are evaluated at the alpha-level state y_alpha by a twin: a residual of the same class built
-    from the arguments ``static`` holds at this moment, which reads the alpha-level vector and shares no cache with the
-    object handed in -- that one is neither modified nor read again.  A ``pressure`` callable is read at every assembly and
+    law, pressure and body force are evaluated at the alpha-level state y_alpha by the same residual at another u: one of the
+    same class built from the arguments ``static`` holds at this moment, which reads the alpha-level vector, keeps the point
+    values of u of its last evaluation and shares no cache with the object handed in -- that one is neither modified nor
+    read again.  All that is asked of the law is where the value slots of its point data live: inside s and T at stride 6
+    (a shell), or in vectors of their own next to P and A (a solid).  A ``pressure`` callable is read at every assembly and
     finds the time of the loads in ``dyn.t_alpha``; a ``body_force`` callable is a function of the points alone, evaluated
     once per set of points by the static classes and not again.
     ``integrator``: a second-order ``GeneralizedAlphaIntegrator``, or a ``BackwardEulerIntegrator`` with two old functions
@@ -1964,11 +2016,7 @@ class DynamicResidual(object):
     def __init__(self, static, integrator, density, mass_damping=0.0, contact=None):
         from . import timeIntegration as _ti
         who = "DynamicResidual"
-        if isinstance(static, ShellResidual):
-            self.kind, self.nJ = "shell", 6
-        elif isinstance(static, HyperelasticResidual):
-            self.kind, self.nJ = "solid", 1
-        else:
+        if not isinstance(static, _PointLawResidual):
             raise NotImplementedError("%s: static = %r; a ShellResidual or a HyperelasticResidual carries the law" % (who, static))
         if isinstance(integrator, _ti.GeneralizedAlphaIntegrator):
             self._gen_alpha = True
@@ -1993,17 +2041,9 @@ class DynamicResidual(object):
         self.rational, self.nq = static.rational, static.nq
         self.scale = float(integrator.ALPHA_F) if self._gen_alpha else 1.0
         self._ti = _ti
-        self._twin = self._make_twin(None)              # reads y_alpha
-        self._now = self._make_twin(integrator.x)       # reads the current level (energy)
+        self._law = static._at(None, keeps_u=True)      # reads y_alpha
+        self._now = static._at(integrator.x)            # reads the current level (energy)
         self._ya, self._w, self._w_key, self._nactive = None, None, None, 0
-
-    # -- the law at another state
-    def _make_twin(self, u):
-        st = self.static
-        if self.kind == "shell":
-            return _ShellTwin(u, st.geometry, st.material, body_force=st.body_force, nq=st.nq, rational=st.rational,
-                              device_law=st.device_law, pressure=st.pressure)
-        return _SolidTwin(u, st.geometry, st.material, body_force=st.body_force, nq=st.nq, rational=st.rational)
 
     # -- the coefficients of a step
     @property
@@ -2036,30 +2076,15 @@ class DynamicResidual(object):
         self._w_key = None
 
     def _scope(self, V, row0, row1, block=False):
-        who = "DynamicResidual"
-        if self.kind == "shell":
-            g, nF, nJ = _point_scope(self.geometry, V, who, "jet")
-        else:
-            g, nF = _point_scope(self.geometry, V, who, "vector")
-        _whole_rows((1 if block else nF) * g.num_nodes(), row0, row1, who, "patch")
-        return g, nF, _vector_points(self.geometry, self.nq, who)
-
-    def _point_values(self, pts, g, nF, nodal):
-        """the nF fields of a nodal vector at the points, field after field (``tg_quad_eval``)"""
-        n, npts = g.num_nodes(), pts.npts
-        ui, out = _dev.DeviceVector(n, zero=False), _dev.DeviceVector(nF * npts, zero=False)
-        for i in range(nF):
-            _dev.vec_copy_range(ui, 0, nodal, i * n, n)
-            _dev.vec_copy_range(out, i * npts, _dev.quad_eval(pts.verts, pts.p, pts.cp, ui, nq=pts.nq, rational=self.rational), 0, npts)
-        return out
+        return self._law._scope(V, "DynamicResidual", row0, row1, block)
 
     def _state(self, g, nF, pts):
-        """y_alpha into the vector the twin reads (one ``tg_vec_lincomb``), and, once per step, w at the points"""
+        """y_alpha into the vector the law reads (one ``tg_vec_lincomb``), and, once per step, w at the points"""
         it, ti, af = self.integrator, self._ti, self.scale
         size = nF * g.num_nodes()
         if self._ya is None or self._ya.size() != size:
             self._ya = _dev.DeviceVector(size, zero=False)
-            self._twin.u = self._ya
+            self._law.u = self._ya
         if ti._vec_of(it.x).size() != size:
             raise ValueError("DynamicResidual: the unknown holds %d nodal values, the space has %d fields of %d"
                              % (ti._vec_of(it.x).size(), nF, g.num_nodes()))
@@ -2068,17 +2093,22 @@ class DynamicResidual(object):
         if self._w_key != key:
             c_M, rest = self._inertia()
             expr = (self.density / af) * (rest - (c_M * (1.0 - af) / af) * ti.LinearCombination.of(it.x_old))
-            self._w = self._point_values(pts, g, nF, expr.evaluate(out=_dev.DeviceVector(size, zero=False)))
+            self._w = _values_at_points(pts, expr.evaluate(out=_dev.DeviceVector(size, zero=False)), nF, g.num_nodes(), self.rational)
             self._w_key, self._w_pts = key, pts
         return self._w
 
     def _plane(self):
         return self.contact.plane() if self.contact is not None else None
 
+    def _stiffness(self):
+        return self.contact.stiffness if self.contact is not None else 0.0
+
     def _dynamics(self, pts, nF, coef, w=None, s=None, T=None):
-        """the one launch of an assembly; the count of active points is read back only with a plane"""
-        n = _dev.point_dynamics(nF, self.nJ, pts.npts, coef, self._plane(), pts.x_device if self.contact is not None else None,
-                                self._twin.held, w, s, T, None, count=self.contact is not None)
+        """the one launch of an assembly, on the value slots of the law and the point values of u it kept; the count of
+        active points is read back only with a plane"""
+        law = self._law
+        n = _dev.point_dynamics(nF, law.nJ, pts.npts, coef, self._plane(), pts.x_device if self.contact is not None else None,
+                                law._u_points, w, s, T, None, count=self.contact is not None)
         self._nactive = n if n is not None else 0
 
     def active_points(self):
@@ -2088,43 +2118,13 @@ class DynamicResidual(object):
     def assemble_vector(self, V, row0=None, row1=None):
         g, nF, pts = self._scope(V, row0, row1)
         w = self._state(g, nF, pts)
-        twin, af, c = self._twin, self.scale, self.coefficients()
-        k = self.contact.stiffness if self.contact is not None else 0.0
-        if self.kind == "shell":
-            s = twin.law(V)[2]
-            self._dynamics(pts, nF, (1.0 / af, c["m_u"], 1.0, 0.0, k / af, 0.0, 0.0), w=w, s=s)
-            r = VectorJetLoadForm(s, self.geometry, nq=self.nq, rational=self.rational).assemble_vector(V)
-            if twin._load is not None:
-                r.axpy(-1.0 / af, twin._load.assemble_vector(V))
-            return r
-        # a solid: the stress is a flux the point kernel has no business with -- the value-slot load holds alpha_f times the
-        # inertia, and the assembled vector is divided by alpha_f
-        P, npts = twin.law(V)[3], pts.npts
-        s = _dev.DeviceVector(nF * npts)
-        if twin.body_force is not None:
-            fq = _per_points(twin, "_fq", pts, lambda: _field_values(pts, twin.body_force, nF, "DynamicResidual: body_force", scale=-1.0))
-            for i in range(nF):
-                _dev.vec_copy_range(s, i * npts, fq[i], 0, npts)
-        self._dynamics(pts, nF, (1.0, af * c["m_u"], af, 0.0, k, 0.0, 0.0), w=w, s=s)
-        si = [_dev.DeviceVector(npts, zero=False) for _ in range(nF)]
-        for i in range(nF):
-            _dev.vec_copy_range(si[i], 0, s, i * npts, npts)
-        r = _field_loads(pts, g.num_nodes(), nF, si, P, self.rational)
-        return _dev.vec_lincomb(r, [1.0 / af], [r]) if af != 1.0 else r
-
-    def _tangent_data(self, V, g, nF, pts):
-        """(the law's point tangent at y_alpha, the reaction of a solid or None) with inertia and the penalty added"""
-        self._state(g, nF, pts)
-        twin, c = self._twin, self.coefficients()
-        k = self.contact.stiffness if self.contact is not None else 0.0
-        if self.kind == "shell":
-            T = twin.law(V, load=False, tangent=True)[3]
-            self._dynamics(pts, nF, (1.0, 0.0, 0.0, c["t_m"], 0.0, k, 0.0), T=T)
-            return T, None
-        A = twin.law(V, stress=False, tangent=True)[4]
-        M = _dev.DeviceVector(nF * nF * pts.npts)
-        self._dynamics(pts, nF, (1.0, 0.0, 0.0, c["t_m"], 0.0, k, 0.0), T=M)
-        return A, M
+        law, c = self._law, self.coefficients()
+        out = law.law(V)
+        s = law._value_load(out)
+        scaling = law._slot_scaling(self.scale, c["m_u"], self._stiffness())
+        self._dynamics(pts, nF, scaling.coef, w=w, s=s)
+        r = law._load_vector(V, out, s, scaling.sigma)
+        return r if scaling.after is None else _dev.vec_lincomb(r, [scaling.after], [r])
 
     def energy(self, V=None, y=None, ydot=None):
         """{"strain", "kinetic", "contact", "total"} at the current level: sum_q wdet psi(y), rho/2 |ydot|^2 with ``xdot()`` of the
@@ -2135,15 +2135,16 @@ class DynamicResidual(object):
         if V is None:
             V = it.x.function_space()
         g, nF, pts = self._scope(V, None, None)
+        at = lambda nodal: _values_at_points(pts, nodal, nF, g.num_nodes(), self.rational)
         self._now.u = it.x if y is None else y
         out = {"strain": float(self._now.energy(V))}
-        vq = self._point_values(pts, g, nF, it.xdot().evaluate() if ydot is None else ti._vec_of(ydot))
+        vq = at(it.xdot().evaluate() if ydot is None else ti._vec_of(ydot))
         e = _dev.DeviceVector(pts.npts, zero=False)
         _dev.point_dynamics(nF, 1, pts.npts, (1.0, 0.0, 0.0, 0.0, 0.0, 0.0, self.density), w=vq, e=e)
         out["kinetic"] = float(pts.weights.inner(e))
         out["contact"] = 0.0
         if self.contact is not None:
-            uq = self._point_values(pts, g, nF, ti._vec_of(self._now.u))
+            uq = at(ti._vec_of(self._now.u))
             _dev.point_dynamics(nF, 1, pts.npts, (1.0, 0.0, 0.0, 0.0, self.contact.stiffness, 0.0, 0.0), self._plane(), pts.x_device,
                                 u=uq, e=e)
             out["contact"] = float(pts.weights.inner(e))
@@ -2159,28 +2160,25 @@ class DynamicResidual(object):
 
 
 class _DynamicTangent(_LawTangent):
-    """The tangent form (dR/dy) / alpha_f of a ``DynamicResidual``: the form of the static tangent -- its class, its symmetry,
-    its transform and assembly -- on the point tangent of the law at y_alpha with rho (c_a + a_M c_v) / alpha_f and
-    k [g > 0] n (x) n added to its value-value entries at the points (a solid: as the reaction of the form)."""
+    """The tangent form (dR/dy) / alpha_f of a ``DynamicResidual``: the form of the law's tangent at y_alpha -- its class, its
+    symmetry, its transform and assembly -- with rho (c_a + a_M c_v) / alpha_f and k [g > 0] n (x) n added to its value-value
+    entries at the points (a solid: as the reaction of the form)."""
 
     def __init__(self, dyn):
-        self.dyn, self._static = dyn, dyn._twin.tangent()
-        _LawTangent.__init__(self, dyn._twin)
-        self.symmetric = self._static.symmetric
+        self.dyn = dyn
+        _LawTangent.__init__(self, dyn._law)
 
-    def _rows(self, V, row0, row1, block):
-        self.dyn._scope(V, row0, row1, block)
-
-    def _form(self, V):
-        dyn, st = self.dyn, self._static
-        A, M = dyn._tangent_data(V, *dyn._scope(V, None, None))
-        st._data = lambda V_: A
-        if M is not None:
-            st._form_class = _ReactionForm
-        form = st._form(V)                               # (sets the symmetry: the law's, a host law's bits, a pressure's False)
-        if M is not None:
-            form.reaction = M
-        self.symmetric = st.symmetric
+    def _form(self, V, row0, row1, block):
+        dyn, law = self.dyn, self.res
+        g, nF, pts = dyn._scope(V, row0, row1, block)
+        dyn._state(g, nF, pts)
+        c = dyn.coefficients()
+        tangent = law.law(V, False, True).tangent
+        values = law._value_tangent(pts, nF, tangent)
+        dyn._dynamics(pts, nF, (1.0, 0.0, 0.0, c["t_m"], 0.0, dyn._stiffness(), 0.0), T=values)
+        form = law._tangent_form(pts, nF, tangent, values)
+        # (the symmetry: the law's, a host law's bits, a pressure's False; inertia and the penalty are symmetric)
+        form._symmetric_hint = self.symmetric = law._law_symmetric()
         return form
 
 
@@ -2193,17 +2191,11 @@ class _DynamicMass(object):
         self.dyn, self.geometry = dyn, dyn.geometry
 
     def assemble_matrix(self, V, row0=None, row1=None):
-        dyn = self.dyn
+        dyn, law = self.dyn, self.dyn._law
         g, nF, pts = dyn._scope(V, row0, row1)
-        coef = (1.0, 0.0, 0.0, dyn.density, 0.0, 0.0, 0.0)
-        if dyn.kind == "shell":
-            T = _dev.DeviceVector(nF * nF * 36 * pts.npts)
-            _dev.point_dynamics(nF, 6, pts.npts, coef, T=T)
-            form = VectorJetCoefficientForm(dyn.geometry, T, nq=dyn.nq, rational=dyn.rational)
-        else:
-            M = _dev.DeviceVector(nF * nF * pts.npts)
-            _dev.point_dynamics(nF, 1, pts.npts, coef, T=M)
-            form = _ReactionForm(dyn.geometry, _dev.DeviceVector(nF ** 4 * pts.npts), reaction=M, nq=dyn.nq, rational=dyn.rational)
+        values = law._value_tangent(pts, nF)
+        _dev.point_dynamics(nF, law.nJ, pts.npts, (1.0, 0.0, 0.0, dyn.density, 0.0, 0.0, 0.0), T=values)
+        form = law._tangent_form(pts, nF, None, values)
         form._symmetric_hint = True
         return form.assemble_matrix(V)
 

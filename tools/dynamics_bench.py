@@ -135,7 +135,7 @@ def measure(args, emit):
         out = {}
         g, nF, pts = dyn._scope(V, None, None)
         k, c = dyn.contact.stiffness, dyn.coefficients()
-        for name, law_obj in (("static", static), ("dynamic", dyn._twin)):
+        for name, law_obj in (("static", static), ("dynamic", dyn._law)):
             dynamic = name == "dynamic"
             parts = {k_: [] for k_ in ("jets", "law", "dynamics", "load", "tangent", "ptap", "solve")}
             for rep in range(args.reps + 1):
