@@ -538,6 +538,11 @@ int tg_tensor_planes_kron(tg_tensor_plan_t plan, int nterms, const tg_kron_dir_t
  * plane per class of planes whose rows of dirs[2] are equal bit for bit in every term (their blocks are equal bit for
  * bit; the others share them) unless TIGAR_TT_PLANE_CLASSES=0; tg_tensor_planes contracts every plane. */
 int tg_tensor_planes_info(tg_tensor_planes_t p, int *n_planes, int *n_contracted);
+/* The last tg_tensor_zstage of `plan`: the FE planes it walked, the B2 blocks a lane loaded on the way, and whether the
+ * walk held the last block of every node slot of an element in registers.  It does when some plane has the block of the
+ * plane p before it (planes sharing blocks, above) unless TIGAR_TT_Z_CACHE=0, and then loads one block per change of
+ * pointer in a slot; the plain walk loads one per plane.  K is the same bit for bit. */
+int tg_tensor_zstage_info(tg_tensor_plan_t plan, int *held, int *n_planes, int *n_block_loads);
 
 /* General Kronecker-product CSR builder on the device: out = sum_t (x)_k F[t][k] restricted to rows
  * [row0,row1), with rectangular 1-D factors (cdim[k] = number of columns of direction k; NULL =

@@ -172,6 +172,7 @@ PROTOTYPES = {
     "tg_tensor_planes_info": (C.c_int, [handle, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tg_tensor_zstage": (C.c_int, [handle, C.c_int, C.POINTER(handle), C.c_int, C.c_int, c_i32p, C.c_int64,
                                    C.c_double, handle, C.POINTER(handle)]),
+    "tg_tensor_zstage_info": (C.c_int, [handle, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tg_csr_compact": (C.c_int, [handle, C.POINTER(handle)]),
     "tg_csr_is_loose": (C.c_int, [handle, C.POINTER(C.c_int)]),
     "tg_csr_rowptr_at": (C.c_int, [handle, C.c_int64, c_i64p]),

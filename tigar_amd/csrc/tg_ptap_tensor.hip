@@ -37,6 +37,9 @@ struct tg_tensor_plan_s {
   uint64_t expect_tag = 0; // tg_pattern_hash of the element-coupling pattern the passes rely on
   std::vector<int32_t> h_ecol[3];   // that pattern's 1-D column indices (rows as in h_rps)
   int *status = nullptr;   // device flag
+  // the last z stage of this plan (tg_tensor_zstage_info): whether it held blocks in registers, the FE planes it walked
+  // and the blocks a lane loaded on the way
+  int z_held = 0, z_planes = 0, z_loads = 0;
 };
 
 struct tg_tensor_planes_s {
@@ -116,6 +119,11 @@ __global__ void __launch_bounds__(64) k_tt_y_multi(tt_y_multi M) {
 template <int P>
 __global__ void __launch_bounds__(64) k_tt_z(tt_z_args A) {
   tt_z_lane<P>(A, blockIdx.x, threadIdx.x);
+}
+// the z walk over planes that share blocks: the last block of every node slot stays in the lane's registers (tt_z_held)
+template <int P>
+__global__ void __launch_bounds__(64) k_tt_z_held(tt_z_args A) {
+  tt_z_lane<P, true>(A, blockIdx.x, threadIdx.x);
 }
 __global__ void __launch_bounds__(256) k_tt_rowptr(tt_rowptr_args A, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -283,6 +291,14 @@ extern "C" int tg_tensor_planes_info(tg_tensor_planes_t p, int *n_planes, int *n
   TG_REQUIRE(p, "null argument to tg_tensor_planes_info");
   if (n_planes) *n_planes = p->z1 - p->z0;
   if (n_contracted) *n_contracted = p->n_contracted;
+  return 0;
+}
+
+extern "C" int tg_tensor_zstage_info(tg_tensor_plan_t pl, int *held, int *n_planes, int *n_block_loads) {
+  TG_REQUIRE(pl, "null argument to tg_tensor_zstage_info");
+  if (held) *held = pl->z_held;
+  if (n_planes) *n_planes = pl->z_planes;
+  if (n_block_loads) *n_block_loads = pl->z_loads;
   return 0;
 }
 
@@ -759,6 +775,7 @@ extern "C" int tg_tensor_zstage(tg_tensor_plan_t pl, int npieces, const tg_tenso
   const tt_dir_t &D0 = pl->dir[0], &D1 = pl->dir[1], &D2 = pl->dir[2];
   const int ncr0 = pl->ncr[0], ncr1 = pl->ncr[1], ncr2 = pl->ncr[2];
   TG_REQUIRE(ka >= 0 && kb > ka && kb <= ncr2, "tg_tensor_zstage: dof planes out of range");
+  // (k_tt_z_held depends on this too: its look-ahead of the mask assumes the square window, tt_z_args::mask)
   TG_REQUIRE(!pl->pair || !(zero_dofs && nzero > 0), "tg_tensor_zstage: blocks with different bases on the two sides take no zero dofs "
                                                      "(MatZeroRowsColumns belongs to the assembled matrix)");
   const int e_begin = std::max(0, ka - pl->pr[2]), e_end = std::min(D2.nel, kb);   // (row function i lives on the elements [i - pr, i])
@@ -838,9 +855,26 @@ extern "C" int tg_tensor_zstage(tg_tensor_plan_t pl, int npieces, const tg_tenso
   Z.mask = mask;
   Z.diag = diag;
   const unsigned grid = (unsigned)tg_cdiv(pd_pad, Z.L);
+  // Planes that share blocks (one plane contracted per class: tg_tensor_planes_kron) repeat in the table at stride P: the
+  // walk that holds the last block of every node slot in registers then loads each block once per change of class instead
+  // of once per plane.  A table without such a repeat (a matrix handed in, graded knots, TIGAR_TT_PLANE_CLASSES=0) takes
+  // the plain walk, whose loads are all distinct: it pays no registers for copies that are never used.
+  // TIGAR_TT_Z_CACHE=0 forces the plain walk (read per call: the tests compare both in one process).  K is the same bit
+  // for bit.
+  const int n_ptr = (int)ptr.size();
+  const bool held = tt_z_repeats(P, ptr.data(), n_ptr) && tg_env_int("TIGAR_TT_Z_CACHE", 1) != 0;
+  pl->z_held = held ? 1 : 0;
+  pl->z_planes = n_ptr;
+  pl->z_loads = tt_z_block_loads(P, plo, D2.nfe, ptr.data(), n_ptr, held);
+  if (getenv("TIGAR_TRACE"))
+    fprintf(stderr, "[trace] tg_tensor_zstage dof planes [%d,%d): FE planes [%d,%d], %s walk, %d block loads per lane\n", ka, kb,
+            plo, phi, held ? "block-holding" : "plain", pl->z_loads);
 #define TT_Z(PP) hipLaunchKernelGGL((k_tt_z<PP>), dim3(grid), dim3(64), 0, g_tg.stream, Z)
-  TT_DISPATCH_P(P, TT_Z);
+#define TT_ZH(PP) hipLaunchKernelGGL((k_tt_z_held<PP>), dim3(grid), dim3(64), 0, g_tg.stream, Z)
+  if (held) TT_DISPATCH_P(P, TT_ZH);
+  else TT_DISPATCH_P(P, TT_Z);
 #undef TT_Z
+#undef TT_ZH
   if (hipGetLastError() != hipSuccess) {
     tg_set_error("tg_tensor_zstage: kernel launch failed");
     return 1;

@@ -65,6 +65,8 @@ typedef const int32_t __attribute__((address_space(4))) *tt_cip;
 #define TT_CI(p) ((tt_cip)(p))
 typedef const double __attribute__((address_space(1))) *tt_gdp;   // pointer known to point to global memory
 #define TT_GD(p) ((tt_gdp)(p))
+typedef const double *const __attribute__((address_space(4))) *tt_cpp;   // a small read-only table of pointers
+#define TT_CP(p) ((tt_cpp)(p))
 #else
 typedef const double *tt_cdp;
 typedef const int32_t *tt_cip;
@@ -72,6 +74,7 @@ typedef const double *tt_gdp;
 #define TT_CD(p) (p)
 #define TT_CI(p) (p)
 #define TT_GD(p) (p)
+#define TT_CP(p) (p)
 #endif
 
 struct tt_dir_t {
@@ -105,10 +108,39 @@ TT_DEV int tt_rlo(int a, int nfe) {
 
 // ------------------------------------------------------------------------------------------------------
 // The walk along the contracted direction.  IO supplies
-//   template <int N> void load(int a, int clo, double *v)   the lane's N values of row a (columns clo..clo+N-1)
+//   template <int N, int S> void load(int a, int clo, double *v)   the lane's N values of row a (columns clo..clo+N-1)
 //   void emit(int i, const double *row)                     the finished output row i: row[m] <-> column dof i-P+m
+// S is the node's slot in its element, a compile-time constant: 1..P-1 for the interior nodes (N = P+1), P for a closing
+// vertex shared with the next element (N = 2P+1), 0 for the two ends of the grid (node 0 and the last node, N = P+1).  An IO
+// may keep per-slot state in registers (tt_io_z) and says so with `static constexpr bool by_slot = true`; the others ignore S
+// (and get 0 for the interior nodes too).
 // Elements e_begin..e_end-1 are walked; an output row i is emitted after element min(i, nel-1), i.e. complete
 // rows are those with all of their elements [i-P, i] inside the walked range (the caller filters).
+
+// interior nodes J..P-1 of element e (a0 = P*e): columns = the element's P+1 nodes
+template <int P, int J, class IO>
+TT_DEV void tt_walk_interior(IO &io, tt_cdp we, tt_cdp wre, int a0, double (&acc)[P + 1][2 * P + 1]) {
+  constexpr int Q = P + 1;
+  if constexpr (J < P) {
+    double v[Q], C[Q];
+    io.template load<Q, J>(a0 + J, a0, v);
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+      double s = 0.0;
+#pragma unroll
+      for (int jj = 0; jj < Q; jj++) s = fma(v[jj], we[jj * Q + q], s);
+      C[q] = s;
+    }
+#pragma unroll
+    for (int r = 0; r < Q; r++) {
+      const double wr = wre[J * Q + r];
+#pragma unroll
+      for (int q = 0; q < Q; q++) acc[r][q - r + P] = fma(wr, C[q], acc[r][q - r + P]);
+    }
+    tt_walk_interior<P, J + 1>(io, we, wre, a0, acc);
+  }
+}
+
 template <int P, class IO>
 TT_DEV void tt_walk(const tt_dir_t &D, int e_begin, int e_end, IO &io) {
   constexpr int W = 2 * P + 1, Q = P + 1, NW = Q * Q;
@@ -122,7 +154,7 @@ TT_DEV void tt_walk(const tt_dir_t &D, int e_begin, int e_end, IO &io) {
   if (e_begin == 0) {   // opening vertex: node 0 = node j = 0 of element 0
     tt_cdp we = TT_CD(D.wl);
     double v[Q], C[Q];
-    io.template load<Q>(0, 0, v);
+    io.template load<Q, 0>(0, 0, v);
 #pragma unroll
     for (int q = 0; q < Q; q++) {
       double s = 0.0;
@@ -141,30 +173,35 @@ TT_DEV void tt_walk(const tt_dir_t &D, int e_begin, int e_end, IO &io) {
     tt_cdp we = TT_CD(D.wl) + (int64_t)e * NW;
     tt_cdp wre = wrow + (int64_t)e * NW;
     const int a0 = P * e;
-    // interior nodes of element e: columns = the element's P+1 nodes
+    // interior nodes of element e: columns = the element's P+1 nodes.  An IO that keeps state per slot gets the slot as a
+    // compile-time constant (a recursion over j); the others keep the plain loop and the code they always had
+    if constexpr (IO::by_slot) {
+      tt_walk_interior<P, 1>(io, we, wre, a0, acc);   // nodes j = 1..P-1, in this order
+    } else {
 #pragma unroll
-    for (int j = 1; j < P; j++) {
-      double v[Q], C[Q];
-      io.template load<Q>(a0 + j, a0, v);
+      for (int j = 1; j < P; j++) {
+        double v[Q], C[Q];
+        io.template load<Q, 0>(a0 + j, a0, v);
 #pragma unroll
-      for (int q = 0; q < Q; q++) {
-        double s = 0.0;
+        for (int q = 0; q < Q; q++) {
+          double s = 0.0;
 #pragma unroll
-        for (int jj = 0; jj < Q; jj++) s = fma(v[jj], we[jj * Q + q], s);
-        C[q] = s;
-      }
+          for (int jj = 0; jj < Q; jj++) s = fma(v[jj], we[jj * Q + q], s);
+          C[q] = s;
+        }
 #pragma unroll
-      for (int r = 0; r < Q; r++) {
-        const double wr = wre[j * Q + r];
+        for (int r = 0; r < Q; r++) {
+          const double wr = wre[j * Q + r];
 #pragma unroll
-        for (int q = 0; q < Q; q++) acc[r][q - r + P] = fma(wr, C[q], acc[r][q - r + P]);
+          for (int q = 0; q < Q; q++) acc[r][q - r + P] = fma(wr, C[q], acc[r][q - r + P]);
+        }
       }
     }
     // closing vertex P*(e+1): node j = P of element e; its columns also cover element e+1 unless it is the last node
     if (e + 1 < D.nel) {
       tt_cdp wn = we + NW;
       double v[W], C[Q + 1];
-      io.template load<W>(a0 + P, a0, v);
+      io.template load<W, P>(a0 + P, a0, v);
 #pragma unroll
       for (int q = 0; q < Q; q++) {
         double s = 0.0;
@@ -192,7 +229,7 @@ TT_DEV void tt_walk(const tt_dir_t &D, int e_begin, int e_end, IO &io) {
       }
     } else {
       double v[Q], C[Q];
-      io.template load<Q>(a0 + P, a0, v);
+      io.template load<Q, 0>(a0 + P, a0, v);      // the last node of the grid
 #pragma unroll
       for (int q = 0; q < Q; q++) {
         double s = 0.0;
@@ -250,6 +287,7 @@ struct tt_x_args {
 
 template <int P, bool V = true>       // V: read and verify the column indices (false: the matrix carries a pattern certificate)
 struct tt_io_x {
+  static constexpr bool by_slot = false;
   const int32_t *col;
   const double *val;
   tt_cip ps0;                 // prefix sums of the 1-D row lengths of direction 0
@@ -264,7 +302,7 @@ struct tt_io_x {
   int64_t ostride_i, ostride_m;
   // Row starts follow in closed form from the row LENGTHS (checked for every row by k_tt_check_rows before this
   // kernel runs; a mismatch stops the pass), so no row pointer is read here and nothing depends on a previous load.
-  template <int N>
+  template <int N, int S>
   TT_MEM void load(int a, int clo, double *v) {
 #pragma unroll
     for (int j = 0; j < N; j++) v[j] = 0.0;
@@ -367,6 +405,7 @@ struct tt_xg_args {
 
 template <int P, int NT>
 struct tt_io_xg {
+  static constexpr bool by_slot = false;
   tt_cdp f0;
   tt_cip ps0;
   int nnz0;
@@ -375,7 +414,7 @@ struct tt_io_xg {
   double *out;
   int64_t ostride_i, ostride_m;
   int elo, ehi;                    // rows emitted by this piece of the walk
-  template <int N>
+  template <int N, int S>
   TT_MEM void load(int a, int clo, double *v) {
     (void)clo;
     // position of row a in the 1-D factor: its pattern is the element-coupling pattern (checked on the host,
@@ -501,6 +540,7 @@ struct tt_y_args {
 
 template <int P>
 struct tt_io_y {
+  static constexpr bool by_slot = false;
   const double *in;
   tt_cip rps;
   int64_t ustride, clane;
@@ -508,7 +548,7 @@ struct tt_io_y {
   int elo, ehi;                  // rows emitted by this piece of the walk
   double *out;
   int64_t ostride_i, ostride_m;
-  template <int N>
+  template <int N, int S>
   TT_MEM void load(int a, int clo, double *v) {
 #pragma unroll
     for (int j = 0; j < N; j++) v[j] = 0.0;
@@ -561,7 +601,10 @@ struct tt_z_args {
   int32_t *kcol;                 // destination arrays, already offset to the first entry of dof plane ka
   double *kval;
   double *kdiag;                 // diagonal of the rows written (index: row - first row of dof plane ka), or null
-  const uint8_t *mask;           // zeroDofs as a byte mask over all dofs, or null
+  // zeroDofs as a byte mask over all dofs, or null.  SQUARE plans only (ncr = ncc = ncp, pr = P: the fields below zero;
+  // tg_tensor_zstage refuses a mask on a pair plan): the block-holding walk reads the mask a row ahead and relies on row i2
+  // coupling to the column planes [i2 - P, i2 + P], clipped (tt_io_z::emit)
+  const uint8_t *mask;
   double diag;
   // Blocks with different bases on the row and the column side (see tt_dir_t::wlr); 0 = the square default.  ncp0 / ncp1
   // above stay the PADDED counts nel + P (the layout of B2); these are the true ones and the spline degrees per side:
@@ -570,12 +613,34 @@ struct tt_z_args {
   int pr0, pr1, pr2;             // spline degree of the row side per direction
 };
 
+// The lane's copy of the last block loaded per node slot (tt_walk), for the z walk over planes that share blocks: when the
+// x and y passes contracted one plane per class (tt_plane_classes), planes[] points the ~P nel2 planes of a stage at a
+// handful of blocks and a lane would load the same 2P+1 + (P-1)(P+1) doubles from the same addresses in every element.
+// from[s - 1]: the block the copy of slot s came from (null: none yet).  Nothing but the pointer decides: a plane whose
+// pointer is the one held takes the registers, any other pointer (another class, a seam between the pieces of the ring,
+// equal data behind another address) loads and replaces the copy.  Slot 0 (node 0 and the last node of the grid, whose
+// blocks have P+1 entries where a vertex has 2P+1) is never held.
+template <int P, bool C>
+struct tt_z_held {};
 template <int P>
+struct tt_z_held<P, true> {
+  const double *from[P];
+  double q[P > 1 ? P - 1 : 1][P + 1];   // slots 1..P-1
+  double w[2 * P + 1];                  // slot P
+  // the mask bytes of the next row of K, read one row ahead (tt_io_z::emit): mi2 = that row, -1: none
+  int mi2;
+  uint8_t mr, mc;                       // its own byte; the byte of the column plane that enters its window
+  uint32_t bits;                        // the column planes it shares with the row before (bit m2 of that row, moved by one)
+};
+
+template <int P, bool C = false>         // C: hold the last block of every slot in registers
 struct tt_io_z {
+  static constexpr bool by_slot = C;
   const double *const *planes;
   int plane_lo;
   int64_t clane;
   bool valid, inwin;
+  tt_z_held<P, C> held;
   // K addressing
   const int32_t *kps2;
   int ka, kb, i0, i1, m0, m1, ncp0, ncp1, w0n, w1n, w0lo, w1lo;
@@ -586,8 +651,25 @@ struct tt_io_z {
   double *kdiag;
   const uint8_t *mask;
   double diag;
-  template <int N>
+  template <int N, int S>
   TT_MEM void load(int a, int clo, double *v) {
+    if constexpr (C && S > 0) {
+      static_assert(N == (S == P ? 2 * P + 1 : P + 1), "slot and block length disagree");
+      // The pointer comes through the scalar unit (a is wave-uniform): the decision is a scalar compare and no vector load
+      // stands in front of a node that is served from the registers.
+      const double *pl = TT_CP(planes)[a - plane_lo];
+      double *c = S == P ? held.w : held.q[S == P ? 0 : S - 1];
+      if (pl != held.from[S - 1]) {
+        held.from[S - 1] = pl;
+        tt_gdp g = TT_GD(pl);
+        const int64_t o = clane * N;
+#pragma unroll
+        for (int j = 0; j < N; j++) c[j] = valid ? g[o + j] : 0.0;
+      }
+#pragma unroll
+      for (int j = 0; j < N; j++) v[j] = c[j];
+      return;
+    }
 #pragma unroll
     for (int j = 0; j < N; j++) v[j] = 0.0;
     if (!valid) return;
@@ -596,13 +678,53 @@ struct tt_io_z {
 #pragma unroll
     for (int j = 0; j < N; j++) v[j] = pl[o + j];
   }
+  // the mask bytes row i2 of K needs: its own (mr) and those of the columns inside its window (mc[m2], 0 outside)
+  TT_MEM void mask_row(int i2, uint8_t &mr, uint8_t *mc) const {
+    const int w2n = kps2[i2 + 1] - kps2[i2];
+    const int w2lo = P - (i2 < pr2 ? i2 : pr2);
+    const int64_t c01 = (i0 - P + m0) + (int64_t)ncc0 * (i1 - P + m1);
+    mr = mask[i0 + (int64_t)ncp0 * (i1 + (int64_t)ncp1 * i2)];
+#pragma unroll
+    for (int m2 = 0; m2 < 2 * P + 1; m2++)
+      mc[m2] = (m2 >= w2lo && m2 < w2lo + w2n) ? mask[c01 + (int64_t)ncc0 * ncc1 * (i2 - P + m2)] : (uint8_t)0;
+  }
   TT_MEM void emit(int i2, const double *row) {
     if (!valid || !inwin || i2 < ka || i2 >= kb) return;
+    // The holding walk no longer waits for B2 loads, and what it waited for next was this row's mask bytes: two dependent
+    // loads (the row's, then its columns') issued behind the stores of the row before.  It reads the bytes of row i2 + 1
+    // here, AHEAD of the stores of row i2, so that they travel while the next element is computed and nothing younger than
+    // a store has to be waited for.  The column planes of row i2 + 1 are those of row i2 moved by one (a mask is taken on
+    // square plans only, tg_tensor_zstage: row i2 couples to the planes [i2 - P, i2 + P], clipped): their bytes stay as the
+    // bits of one register, bit m2 <-> plane i2 - P + m2, and only the plane that enters the window (m2 = 2P) is read.
+    // Same bytes, same values stored.
+    uint8_t mr = 0;
+    uint32_t bits = 0;
+    if constexpr (C) {
+      if (mask) {
+        if (held.mi2 == i2) {
+          mr = held.mr;
+          bits = held.bits | (held.mc ? 1u << (2 * P) : 0u);
+        } else {                                  // the first row this walk writes
+          uint8_t mc[2 * P + 1];
+          mask_row(i2, mr, mc);
+#pragma unroll
+          for (int m2 = 0; m2 < 2 * P + 1; m2++) bits |= mc[m2] ? 1u << m2 : 0u;
+        }
+        if (i2 + 1 < kb) {
+          const int n2 = i2 + 1;
+          const int w2hi = P - (n2 < pr2 ? n2 : pr2) + (kps2[n2 + 1] - kps2[n2]);      // end of the window of row n2
+          held.mr = mask[i0 + (int64_t)ncp0 * (i1 + (int64_t)ncp1 * n2)];
+          held.mc = 2 * P < w2hi ? mask[(i0 - P + m0) + (int64_t)ncc0 * (i1 - P + m1) + (int64_t)ncc0 * ncc1 * (n2 + P)] : (uint8_t)0;
+          held.bits = bits >> 1;
+          held.mi2 = n2;
+        }
+      }
+    }
     const int w2n = kps2[i2 + 1] - kps2[i2];
     const int w2lo = P - (i2 < pr2 ? i2 : pr2);
     const int64_t rowstart = w01tot * (kps2[i2] - kps2[ka]) + (int64_t)w2n * rowoff01;
     const int64_t R = i0 + (int64_t)ncp0 * (i1 + (int64_t)ncp1 * i2);
-    const bool mrow = mask && mask[R];
+    const bool mrow = mask && (C ? mr : mask[R]);
     const int64_t within = (int64_t)(m1 - w1lo) * w0n + (m0 - w0lo);
     const int64_t c01 = (i0 - P + m0) + (int64_t)ncc0 * (i1 - P + m1);
 #pragma unroll
@@ -611,7 +733,7 @@ struct tt_io_z {
         const int64_t pos = rowstart + (int64_t)(m2 - w2lo) * w1n * w0n + within;
         const int64_t c = c01 + (int64_t)ncc0 * ncc1 * (i2 - P + m2);
         double v = row[m2];
-        if (mask && (mrow || mask[c])) v = (mrow && c == R) ? diag : 0.0;
+        if (mask && (mrow || (C ? (bits >> m2 & 1u) != 0 : mask[c] != 0))) v = (mrow && c == R) ? diag : 0.0;
         kcol[pos] = (int32_t)c;
         kval[pos] = v;
         if (m2 == P && kdiag && m0 == P && m1 == P) kdiag[R - (int64_t)ka * ncp0 * ncp1] = v;   // c == R
@@ -620,13 +742,26 @@ struct tt_io_z {
   }
 };
 
-template <int P>
+// C: the walk holds the last block of every node slot in registers (tt_z_held) -- same loads where planes[] never repeats
+// at stride P, same arithmetic in the same order and the same stores always: K is bit for bit that of the plain walk
+template <int P, bool C = false>
 TT_DEV void tt_z_lane(const tt_z_args &A, int bx, int lane) {
   constexpr int W = 2 * P + 1;
   const int lpl = W * W;
   const int sub = lane / lpl, l = lane - sub * lpl;
   const int64_t line = (int64_t)bx * A.L + sub;
-  tt_io_z<P> io;
+  tt_io_z<P, C> io;
+  if constexpr (C) {
+#pragma unroll
+    for (int s = 0; s < P; s++) io.held.from[s] = nullptr;
+    io.held.mi2 = -1;
+#pragma unroll
+    for (int s = 0; s < (P > 1 ? P - 1 : 1); s++)
+#pragma unroll
+      for (int j = 0; j < P + 1; j++) io.held.q[s][j] = 0.0;
+#pragma unroll
+    for (int j = 0; j < W; j++) io.held.w[j] = 0.0;
+  }
   io.valid = sub < A.L && line < (int64_t)A.ncp0 * A.ncp1;
   const int i0 = io.valid ? (int)(line % A.ncp0) : 0, i1 = io.valid ? (int)(line / A.ncp0) : 0;
   const int m0 = l % W, m1 = l / W;
@@ -670,6 +805,36 @@ TT_DEV void tt_z_lane(const tt_z_args &A, int bx, int lane) {
   tt_walk<P>(A.d2, e_begin, e_end, io);
 }
 
+// HOST ONLY (never called from a kernel; here so that the emulation build reaches the same code as tg_tensor_zstage):
+// what the host knows of a z stage over the FE planes [plo, plo + n) from its pointer table alone.
+// tt_z_repeats: some plane has the block of the plane P before it, i.e. of the same node slot one element earlier -- the
+// only case in which holding blocks saves a load.  tt_z_block_loads: the blocks a lane loads in that walk, holding them
+// (tt_z_held: one load per change of pointer in a slot; the two ends of the grid, nodes 0 and nfe - 1, always load) or not
+// (one per plane).
+static inline bool tt_z_repeats(int P, const double *const *ptr, int n) {
+  for (int i = P; i < n; i++)
+    if (ptr[i] == ptr[i - P]) return true;
+  return false;
+}
+static inline int tt_z_block_loads(int P, int plo, int nfe, const double *const *ptr, int n, bool held) {
+  if (!held) return n;
+  std::vector<const double *> from((size_t)P, nullptr);
+  int loads = 0;
+  for (int i = 0; i < n; i++) {
+    const int a = plo + i;
+    if (a == 0 || a == nfe - 1) {
+      loads++;
+      continue;
+    }
+    const int s = a % P == 0 ? P : a % P;
+    if (from[(size_t)s - 1] != ptr[i]) {
+      from[(size_t)s - 1] = ptr[i];
+      loads++;
+    }
+  }
+  return loads;
+}
+
 // ------------------------------------------------------------------------------------------------------
 // 2-D patches (nF fields on one basis): K = P_y^T (P_x^T A P_x) P_y, the x pass above (direction 2 = field index,
 // dense) followed by this FINAL pass along direction 1: B1 rows (i0, r1, f) with block [g][m0][c1] -> rows of K in CSR
@@ -694,6 +859,7 @@ struct tt_y2_args {
 
 template <int P>
 struct tt_io_y2 {
+  static constexpr bool by_slot = false;
   const double *in;
   tt_cip rps;
   int64_t ustride, clane;
@@ -709,7 +875,7 @@ struct tt_io_y2 {
   double *kdiag;
   const uint8_t *mask;
   double diag;
-  template <int N>
+  template <int N, int S>
   TT_MEM void load(int a, int clo, double *v) {
 #pragma unroll
     for (int j = 0; j < N; j++) v[j] = 0.0;

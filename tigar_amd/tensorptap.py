@@ -399,6 +399,14 @@ class TensorPtAP(_PlanHandle):
               "tg_tensor_zstage")
         return True if append_to is not None else _dev.DeviceCSR(out)
 
+    def zstage_info(self):
+        """(held, planes, block loads) of this plan's last ``zstage``: whether the walk held the last B2 block of every node
+        slot in registers (it does when planes share blocks, unless TIGAR_TT_Z_CACHE=0), the FE planes it walked and the
+        blocks a lane loaded on the way (held: one per change of pointer in a slot; plain: one per plane)"""
+        held, n, loads = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(_lib.lib().tg_tensor_zstage_info(self._h, C.byref(held), C.byref(n), C.byref(loads)), "tg_tensor_zstage_info")
+        return bool(held.value), int(n.value), int(loads.value)
+
 
 class TensorPtAP2D(_PlanHandle):
     """Plan of the tensor-pattern PtAP for a patch with TWO parametric directions and ``nfields`` fields on one scalar
