@@ -204,15 +204,17 @@ def test_cell_block_gather_with_one_function_in_many_cells(dev, capfd):
 
 
 def kron_case(d, p, nel):
-    """a Kronecker-form extraction, random values on the element-coupling pattern (direction 0 fastest), M as one matrix"""
+    """a Kronecker-form extraction, random values on the element-coupling pattern (direction 0 fastest), M as one matrix;
+    `nel`: elements per direction, one number for all or one per direction"""
     from tigar_amd import BSplines as B
     from tigar_amd.kronptap import KronExtraction
-    basis = B.ExplicitBSplineControlMesh([p] * d, [B.uniformKnots(p, 0., 1., nel)] * d).getScalarSpline()
+    nels = [nel] * d if np.isscalar(nel) else list(nel)
+    basis = B.ExplicitBSplineControlMesh([p] * d, [B.uniformKnots(p, 0., 1., n) for n in nels]).getScalarSpline()
     kx = KronExtraction(basis, basis.generateMesh(degree=p))
     pats = []
     for k in range(d):
         P1 = sp.lil_matrix((kx.nfe[k], kx.nfe[k]))
-        for e in range(nel):
+        for e in range(nels[k]):
             P1[p * e:p * e + p + 1, p * e:p * e + p + 1] = 1.0
         pats.append(P1.tocsr())
     A, Mo = pats[0], sp.csr_matrix(kx.M1[0])
@@ -223,15 +225,16 @@ def kron_case(d, p, nel):
     return kx, A, Mo
 
 
-def kron_chain(dev, kx, Ad, zd, diag, loose, builder):
-    """direction after direction through ``ptap_kron``; `loose`: intermediate stages handed over as loose rows, `builder`: the
-    last stage appended to a builder (else a matrix of its own)"""
+def kron_chain(dev, kx, Ad, zd, diag, loose, builder, groups=None):
+    """direction after direction (or group of directions after group) through ``ptap_kron``; `loose`: intermediate stages
+    handed over as loose rows, `builder`: the last stage appended to a builder (else a matrix of its own)"""
     d = kx.d
+    groups = groups or [[k] for k in range(d)]
     cur, done = Ad, set()
-    for k in range(d):
-        last = k == d - 1
-        dims, fac = kx.dims(done), [kx.M1[j] if j == k else None for j in range(d)]
-        done = done | {k}
+    for gi, group in enumerate(groups):
+        last = gi == len(groups) - 1
+        dims, fac = kx.dims(done), [kx.M1[j] if j in group else None for j in range(d)]
+        done = done | set(group)
         n_out = int(np.prod(kx.dims(done)))
         if last and builder:
             bld = dev.CSRBuilder(n_out, n_out, 1)

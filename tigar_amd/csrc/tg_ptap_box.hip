@@ -67,6 +67,9 @@ struct tg_line_args {
 
 enum { TG_BOX_OK = 0, TG_BOX_TOOBIG = 1, TG_BOX_RANGE = 2, TG_BOX_CAP = 3, TG_BOX_OUTSIDE = 4 };
 enum { TG_BOXMODE_PROBE = 0, TG_BOXMODE_BUMP = 1 };
+// what a stage answers besides 0 and an error: "use the general kernels" (nothing was written), an entry fell outside a
+// box sized from sampled reach data, a stacked view met a kernel that cannot read it
+enum { TG_KRON_DECLINED = 100, TG_KRON_OUTSIDE = 101, TG_KRON_COMPACT = 102 };
 
 // s = q*dsr + r for 0 <= s < 2^31 by multiplication with a precomputed magic number:
 // q = umulhi(s, mg) >> sh  (exact: mg = ceil(2^(32+sh) / dsr), sh = ceil(log2 dsr) - 1 when dsr > 1)
@@ -1106,208 +1109,357 @@ static size_t tg_box_lds(int cap, int cap1, int ctab, int nlist, int nt) {
   return b;
 }
 
-// returns 0 ok, 100 = "use the general kernel" (box too large / not applicable), 101 = an entry fell
-// outside a box sized from SAMPLED reach data (retry with the exact reach), other = error
-static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_t *dims_in, const tg_kron1d_t *fac,
-                             int64_t out_row0, int64_t out_row1, const int32_t *zero_dofs, int64_t nzero, double diag,
-                             int64_t reach_stride, bool loose_out, tg_csr_builder_s *dest, tg_csr_t *out) {
-  TG_REQUIRE_INIT();
-  TG_REQUIRE(cur && d >= 1 && d <= 3 && dims_in && fac && (out || dest) && out_row1 >= out_row0, "bad arguments to tg_ptap_kron");
+// ---- host driver of one stage: the switches and the request go into a plan, and the stages
+// operands -> boxes -> LDS layout -> kernel choice -> capacity -> run -> ending are one function each over that plan
+
+struct tg_kron_switches {       // the environment, read once per call of an entry point
+  int accum;                    // TIGAR_PTAP_ACCUM: 0 not set, 1 "int", 2 "float" (tg_box_args::accum_mode)
+  int nt;                       // TIGAR_BOX_NT: 64, anything else 256
+  bool slowdecode, prof;        // TIGAR_BOX_SLOWDECODE, TIGAR_BOX_PROF
+  bool line;                    // TIGAR_PTAP_LINE: false only when set to 0
+  bool g1_set;                  // TIGAR_BOX_G1 ...
+  int g1;                       // ... and its value
+  bool force_probe;             // TIGAR_PTAP_PROBE=1: size every temporary from a probe, not from the capacity cache
+  int line_run;                 // TIGAR_LINE_RUN: rows per wave of the line kernels (20), at least 1
+  int64_t line_grab;            // TIGAR_LINE_GRAB: output entries a wave reserves at a time (8192)
+  bool exact_reach;             // TIGAR_BOX_EXACT_REACH: never sample the reach scan
+  int reach_stride;             // TIGAR_BOX_REACH_STRIDE: at least 1; 0: not set
+  bool noloose;                 // TIGAR_PTAP_NOLOOSE: intermediate stages as matrices of their own
+};
+
+static tg_kron_switches tg_kron_switches_read() {
+  auto num = [](const char *name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; };
+  const char *am = getenv("TIGAR_PTAP_ACCUM");
+  tg_kron_switches S;
+  S.accum = am && !strcmp(am, "int") ? 1 : am && !strcmp(am, "float") ? 2 : 0;
+  S.nt = num("TIGAR_BOX_NT", 256) == 64 ? 64 : 256;
+  S.slowdecode = getenv("TIGAR_BOX_SLOWDECODE") != nullptr;
+  S.prof = getenv("TIGAR_BOX_PROF") != nullptr;
+  S.line = num("TIGAR_PTAP_LINE", 1) != 0;
+  S.g1_set = getenv("TIGAR_BOX_G1") != nullptr;
+  S.g1 = num("TIGAR_BOX_G1", 4);
+  S.force_probe = num("TIGAR_PTAP_PROBE", 0) == 1;
+  S.line_run = std::max(1, num("TIGAR_LINE_RUN", 20));
+  S.line_grab = getenv("TIGAR_LINE_GRAB") ? atoll(getenv("TIGAR_LINE_GRAB")) : 8192;
+  S.exact_reach = getenv("TIGAR_BOX_EXACT_REACH") != nullptr;
+  S.reach_stride = getenv("TIGAR_BOX_REACH_STRIDE") ? std::max(1, num("TIGAR_BOX_REACH_STRIDE", 1)) : 0;
+  S.noloose = getenv("TIGAR_PTAP_NOLOOSE") != nullptr;
+  return S;
+}
+
+// how a stage ends: a CSR matrix of its own, loose rows (the temporary handed on to the next stage), rows appended to a builder
+enum { TG_KRON_END_CSR = 0, TG_KRON_END_LOOSE = 1, TG_KRON_END_APPEND = 2 };
+
+struct tg_kron_request {        // what the entry points pass
+  tg_csr_s *cur;
+  int64_t cur_row0;
+  int d;
+  const int64_t *dims_in;
+  const tg_kron1d_t *fac;
+  int64_t out_row0, out_row1;
+  const int32_t *zero_dofs;
+  int64_t nzero;
+  double diag;
+  int ending;                   // TG_KRON_END_*
+  tg_csr_builder_s *dest;       // TG_KRON_END_APPEND
+  tg_csr_t *out;                // the others
+};
+
+// one row per instantiation, in the order in which the instantiations are to be emitted; line rows: variant 1 = <20,10>,
+// 2 = <32,16>, (a, u) = contracted / march direction; box rows: variant 0, a = TG_BOXMODE_*, u = workgroup size
+typedef void (*tg_kron_line_fn)(tg_box_args, tg_line_args, int64_t *, int64_t *, int32_t *, double *, unsigned long long *, int64_t,
+                                const uint8_t *, double, int *);
+typedef void (*tg_kron_box_fn)(tg_box_args, int64_t *, int64_t *, int32_t *, double *, unsigned long long *, int64_t,
+                               const uint8_t *, double, int *, int *);
+struct tg_kron_route {
+  const char *name;             // as the trace prints it
+  int variant, a, u, hi;
+  tg_kron_line_fn line;
+  tg_kron_box_fn box;
+};
+
+static const tg_kron_route g_kron_routes[] = {
+    {"k_ptap_box<256>", 0, TG_BOXMODE_PROBE, 256, 0, nullptr, k_ptap_box<TG_BOXMODE_PROBE, 256>},
+    {"k_ptap_box<256>", 0, TG_BOXMODE_BUMP, 256, 0, nullptr, k_ptap_box<TG_BOXMODE_BUMP, 256>},
+    {"k_ptap_box<64>", 0, TG_BOXMODE_PROBE, 64, 0, nullptr, k_ptap_box<TG_BOXMODE_PROBE, 64>},
+    {"k_ptap_box<64>", 0, TG_BOXMODE_BUMP, 64, 0, nullptr, k_ptap_box<TG_BOXMODE_BUMP, 64>},
+    {"k_ptap_line<20,10,0,1,hi=1>", 1, 0, 1, 1, k_ptap_line<20, 10, 0, 1, true>, nullptr},
+    {"k_ptap_line<20,10,0,1,hi=0>", 1, 0, 1, 0, k_ptap_line<20, 10, 0, 1, false>, nullptr},
+    {"k_ptap_line<20,10,1,0,hi=1>", 1, 1, 0, 1, k_ptap_line<20, 10, 1, 0, true>, nullptr},
+    {"k_ptap_line<20,10,1,0,hi=0>", 1, 1, 0, 0, k_ptap_line<20, 10, 1, 0, false>, nullptr},
+    {"k_ptap_line<20,10,2,0,hi=1>", 1, 2, 0, 1, k_ptap_line<20, 10, 2, 0, true>, nullptr},
+    {"k_ptap_line<20,10,2,0,hi=0>", 1, 2, 0, 0, k_ptap_line<20, 10, 2, 0, false>, nullptr},
+    {"k_ptap_line<20,10,0,-1,hi=1>", 1, 0, -1, 1, k_ptap_line<20, 10, 0, -1, true>, nullptr},
+    {"k_ptap_line<20,10,0,-1,hi=0>", 1, 0, -1, 0, k_ptap_line<20, 10, 0, -1, false>, nullptr},
+    {"k_ptap_line<32,16,0,1,hi=1>", 2, 0, 1, 1, k_ptap_line<32, 16, 0, 1, true>, nullptr},
+    {"k_ptap_line<32,16,0,1,hi=0>", 2, 0, 1, 0, k_ptap_line<32, 16, 0, 1, false>, nullptr},
+    {"k_ptap_line<32,16,1,0,hi=1>", 2, 1, 0, 1, k_ptap_line<32, 16, 1, 0, true>, nullptr},
+    {"k_ptap_line<32,16,1,0,hi=0>", 2, 1, 0, 0, k_ptap_line<32, 16, 1, 0, false>, nullptr},
+    {"k_ptap_line<32,16,2,0,hi=1>", 2, 2, 0, 1, k_ptap_line<32, 16, 2, 0, true>, nullptr},
+    {"k_ptap_line<32,16,2,0,hi=0>", 2, 2, 0, 0, k_ptap_line<32, 16, 2, 0, false>, nullptr},
+    {"k_ptap_line<32,16,0,-1,hi=1>", 2, 0, -1, 1, k_ptap_line<32, 16, 0, -1, true>, nullptr},
+    {"k_ptap_line<32,16,0,-1,hi=0>", 2, 0, -1, 0, k_ptap_line<32, 16, 0, -1, false>, nullptr},
+};
+
+// the row of (line variant, a, u, hi) or of (0, mode, workgroup size, 0); null: not instantiated
+static const tg_kron_route *tg_kron_route_find(int variant, int a, int u, int hi) {
+  for (const tg_kron_route &r : g_kron_routes)
+    if (r.variant == variant && r.a == a && r.u == u && r.hi == hi) return &r;
+  return nullptr;
+}
+
+static void tg_kron_routes_init() {      // the box kernels carve up to 150 KiB of LDS
   static bool lim = false;
-  if (!lim) {
-    hipFuncSetAttribute((const void *)k_ptap_box<TG_BOXMODE_PROBE, 256>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        160 * 1024);
-    hipFuncSetAttribute((const void *)k_ptap_box<TG_BOXMODE_BUMP, 256>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        160 * 1024);
-    hipFuncSetAttribute((const void *)k_ptap_box<TG_BOXMODE_PROBE, 64>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        160 * 1024);
-    hipFuncSetAttribute((const void *)k_ptap_box<TG_BOXMODE_BUMP, 64>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        160 * 1024);
-    lim = true;
-  }
+  if (lim) return;
+  for (const tg_kron_route &r : g_kron_routes)
+    if (r.box) hipFuncSetAttribute((const void *)r.box, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  lim = true;
+}
+
+// Capacity of the temporary of the last product with the same signature: stage, contracted directions, index spaces in
+// the first two directions, line variant, ending.
+// (used_pr: largest use per row seen; cap_pr: capacity per row of the last allocation that was large enough -- re-used
+// as it is, so that the same sub-slab asks for the same block in every step: a capacity recomputed from the use would
+// land in another size class than the probe-sized allocation of the first step and cost a round of hipMalloc in the second)
+typedef std::array<int, 8> tg_kron_cap_key;
+struct tg_kron_cap_entry {
+  double used_pr = 0.0, cap_pr = 0.0;
+  int hmax2 = 0;
+};
+static std::map<tg_kron_cap_key, tg_kron_cap_entry> g_kron_caps;
+
+static bool tg_kron_cap_lookup(const tg_kron_cap_key &key, tg_kron_cap_entry *e) {
+  const auto it = g_kron_caps.find(key);
+  if (it == g_kron_caps.end()) return false;
+  *e = it->second;
+  return true;
+}
+
+// what an attempt used per row is a lower bound also when the kernel gave up (worked_pr < 0); worked_pr >= 0: the
+// capacity per row it ended well with -- fixed once it has worked (a capacity that follows the largest use seen creeps
+// upwards over the first steps and every change is a round of hipMalloc); only an overflow (`grew`) moves it
+static void tg_kron_cap_record(const tg_kron_cap_key &key, double used_pr, int hmax2, double worked_pr, bool grew) {
+  tg_kron_cap_entry &c = g_kron_caps[key];
+  c.used_pr = std::max(c.used_pr, used_pr);
+  c.hmax2 = std::max(c.hmax2, hmax2);
+  if (worked_pr >= 0.0 && (c.cap_pr == 0.0 || grew)) c.cap_pr = worked_pr;
+}
+
+struct tg_kron_bufs {           // device blocks of one stage call: back to the pool when the plan goes, the stream drained
+  tg_dbuf<int32_t> mrp[3], mcol[3], trp[3], tcol[3];
+  tg_dbuf<double> mval[3], tval[3], rowmax;
+  tg_dbuf<int> reach, box;      // lmax[ntot] | rmax[ntot]; blo | bhi of the three directions
+  tg_dbuf<unsigned long long> prof;
+  tg_dbuf<uint8_t> mask;
+  ~tg_kron_bufs() { hipStreamSynchronize(g_tg.stream); }      // (the members are freed after this body)
+};
+
+struct tg_kron_plan {
+  tg_kron_switches S;
+  tg_kron_request rq;
+  int64_t reach_stride = 1;
   tg_box_args P;
-  memset(&P, 0, sizeof(P));
-  {
-    const char *am = getenv("TIGAR_PTAP_ACCUM");
-    P.accum_mode = am && !strcmp(am, "int") ? 1 : am && !strcmp(am, "float") ? 2 : 0;
-  }
-  P.rowptr = cur->rowptr;
-  P.rowcnt = cur->rowcnt;
-  P.rowptr_val = cur->rowptr_val;
-  P.col = cur->col;
-  P.val = cur->val;
-  P.row0 = cur_row0;
-  P.nrows = cur->nrows;
-  P.d = d;
+  tg_line_args Q;
   int64_t nin_total = 1, nout_total = 1;
-  struct dev_list {            // factor tables, reach, row maxima: back to the pool when the function returns, the stream drained
-    std::vector<void *> p;
-    ~dev_list() {
-      hipStreamSynchronize(g_tg.stream);
-      for (void *q : p) tg_dfree(q);
-    }
-  } dev;
-  int rc = 0;
-  int maxlen[3] = {1, 1, 1};
+  int maxlen[3] = {1, 1, 1};    // longest 1-D support (first to last column of a row of F_k^T)
+  int maxBk[3] = {1, 1, 1};     // largest box extent per direction
+  int64_t boxmax = 1;           // ... and their product
+  int Dmax[3] = {1, 1, 1};      // most output indices reachable from a box
+  int nt = 256;                 // workgroup size of the box kernel
+  size_t lds = 0, line_lds = 0;
+  int line_variant = 0;         // 0: box kernel, 1: k_ptap_line<20,10>, 2: <32,16>
+  const tg_kron_route *route = nullptr;
+  tg_kron_cap_key cap_key;
+  bool have_cached = false;
+  int hmax2 = 0;                // second maximum of the probe (or the largest one seen): slack of the capacity
+  tg_kron_bufs B;
+};
+
+// one 1-D factor and its transpose to the device; the longest support of its output indices
+static int tg_kron_factor_upload(tg_kron_plan &K, int k) {
+  const tg_kron1d_t &F = K.rq.fac[k];
+  tg_box_args &P = K.P;
+  tg_kron_bufs &B = K.B;
+  TG_REQUIRE(F.n == K.rq.dims_in[k] && F.m >= 1 && F.col && F.val && F.t_rowptr && F.t_col && F.t_val, "bad 1-D factor %d", k);
+  P.contracted[k] = 1;
+  P.nout[k] = (int)F.m;
+  const int64_t nnz1 = F.rowptr[F.n];
+  TG_TRY(B.mrp[k].alloc(F.n + 1) || B.mcol[k].alloc(nnz1) || B.mval[k].alloc(nnz1) || B.trp[k].alloc(F.m + 1) ||
+         B.tcol[k].alloc(nnz1) || B.tval[k].alloc(nnz1));
+  hipMemcpyAsync(B.mrp[k], F.rowptr, (F.n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, g_tg.stream);
+  hipMemcpyAsync(B.mcol[k], F.col, nnz1 * sizeof(int32_t), hipMemcpyHostToDevice, g_tg.stream);
+  hipMemcpyAsync(B.mval[k], F.val, nnz1 * sizeof(double), hipMemcpyHostToDevice, g_tg.stream);
+  hipMemcpyAsync(B.trp[k], F.t_rowptr, (F.m + 1) * sizeof(int32_t), hipMemcpyHostToDevice, g_tg.stream);
+  hipMemcpyAsync(B.tcol[k], F.t_col, nnz1 * sizeof(int32_t), hipMemcpyHostToDevice, g_tg.stream);
+  hipMemcpyAsync(B.tval[k], F.t_val, nnz1 * sizeof(double), hipMemcpyHostToDevice, g_tg.stream);
+  P.mrp[k] = B.mrp[k];
+  P.mcol[k] = B.mcol[k];
+  P.mval[k] = B.mval[k];
+  P.trp[k] = B.trp[k];
+  P.tcol[k] = B.tcol[k];
+  P.tval[k] = B.tval[k];
+  for (int64_t i = 0; i < F.m; i++) {
+    const int p0 = F.t_rowptr[i], p1 = F.t_rowptr[i + 1];
+    if (p1 > p0) K.maxlen[k] = std::max(K.maxlen[k], F.t_col[p1 - 1] - F.t_col[p0] + 1);
+  }
+  return 0;
+}
+
+// Stage 1: the arguments, the operand part of tg_box_args, the factor tables
+static int tg_kron_operands(tg_kron_plan &K) {
+  const tg_kron_request &rq = K.rq;
+  TG_REQUIRE_INIT();
+  TG_REQUIRE(rq.cur && rq.d >= 1 && rq.d <= 3 && rq.dims_in && rq.fac && (rq.out || rq.dest) && rq.out_row1 >= rq.out_row0,
+             "bad arguments to tg_ptap_kron");
+  tg_kron_routes_init();
+  tg_box_args &P = K.P;
+  memset(&P, 0, sizeof(P));
+  memset(&K.Q, 0, sizeof(K.Q));
+  P.accum_mode = K.S.accum;
+  P.rowptr = rq.cur->rowptr;
+  P.rowcnt = rq.cur->rowcnt;
+  P.rowptr_val = rq.cur->rowptr_val;
+  P.col = rq.cur->col;
+  P.val = rq.cur->val;
+  P.row0 = rq.cur_row0;
+  P.nrows = rq.cur->nrows;
+  P.d = rq.d;
   for (int k = 0; k < 3; k++) {
     P.nin[k] = P.nout[k] = 1;
     P.contracted[k] = 0;
   }
-  for (int k = 0; k < d && !rc; k++) {
-    TG_REQUIRE(dims_in[k] >= 1 && dims_in[k] < (1ll << 31), "bad input dimension %d", k);
-    P.nin[k] = (int)dims_in[k];
+  for (int k = 0; k < rq.d; k++) {
+    TG_REQUIRE(rq.dims_in[k] >= 1 && rq.dims_in[k] < (1ll << 31), "bad input dimension %d", k);
+    P.nin[k] = (int)rq.dims_in[k];
     P.nout[k] = P.nin[k];
-    if (fac[k].rowptr) {
-      const tg_kron1d_t &F = fac[k];
-      TG_REQUIRE(F.n == dims_in[k] && F.m >= 1 && F.col && F.val && F.t_rowptr && F.t_col && F.t_val,
-                 "bad 1-D factor %d", k);
-      P.contracted[k] = 1;
-      P.nout[k] = (int)F.m;
-      const int64_t nnz1 = F.rowptr[F.n];
-      int32_t *a = nullptr, *b = nullptr, *c = nullptr, *e = nullptr;
-      double *v = nullptr, *tv = nullptr;
-      rc = tg_dmalloc(&a, F.n + 1) || tg_dmalloc(&b, nnz1) || tg_dmalloc(&v, nnz1) || tg_dmalloc(&c, F.m + 1) ||
-           tg_dmalloc(&e, nnz1) || tg_dmalloc(&tv, nnz1);
-      dev.p.insert(dev.p.end(), {(void *)a, (void *)b, (void *)v, (void *)c, (void *)e, (void *)tv});
-      if (rc) break;
-      hipMemcpyAsync(a, F.rowptr, (F.n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, g_tg.stream);
-      hipMemcpyAsync(b, F.col, nnz1 * sizeof(int32_t), hipMemcpyHostToDevice, g_tg.stream);
-      hipMemcpyAsync(v, F.val, nnz1 * sizeof(double), hipMemcpyHostToDevice, g_tg.stream);
-      hipMemcpyAsync(c, F.t_rowptr, (F.m + 1) * sizeof(int32_t), hipMemcpyHostToDevice, g_tg.stream);
-      hipMemcpyAsync(e, F.t_col, nnz1 * sizeof(int32_t), hipMemcpyHostToDevice, g_tg.stream);
-      hipMemcpyAsync(tv, F.t_val, nnz1 * sizeof(double), hipMemcpyHostToDevice, g_tg.stream);
-      P.mrp[k] = a;
-      P.mcol[k] = b;
-      P.mval[k] = v;
-      P.trp[k] = c;
-      P.tcol[k] = e;
-      P.tval[k] = tv;
-      for (int64_t i = 0; i < F.m; i++) {
-        const int p0 = F.t_rowptr[i], p1 = F.t_rowptr[i + 1];
-        if (p1 > p0) maxlen[k] = std::max(maxlen[k], F.t_col[p1 - 1] - F.t_col[p0] + 1);
-      }
-    }
-    nin_total *= P.nin[k];
-    nout_total *= P.nout[k];
+    if (rq.fac[k].rowptr) TG_TRY(tg_kron_factor_upload(K, k));
+    K.nin_total *= P.nin[k];
+    K.nout_total *= P.nout[k];
   }
-  if (rc) return rc;
-  if (!(out_row1 <= nout_total && cur->ncols == nin_total)) {
-    tg_set_error("tg_ptap_kron: index spaces do not match the operands (cols %lld vs %lld)", (long long)cur->ncols,
-                 (long long)nin_total);
+  if (!(rq.out_row1 <= K.nout_total && rq.cur->ncols == K.nin_total)) {
+    tg_set_error("tg_ptap_kron: index spaces do not match the operands (cols %lld vs %lld)", (long long)rq.cur->ncols,
+                 (long long)K.nin_total);
     return 2;
   }
-  // measured reach of cur's rows per direction and coordinate -> tight accumulator boxes
+  return 0;
+}
+
+// Stage 2: measured reach of cur's rows per direction and coordinate -> tight accumulator boxes
+static int tg_kron_boxes(tg_kron_plan &K) {
+  const tg_kron_request &rq = K.rq;
+  tg_csr_s *cur = rq.cur;
+  tg_box_args &P = K.P;
   int *status = (int *)g_tg.scratch;     // [0] status, [1..2] maxima
   hipMemsetAsync(status, 0, 8 * sizeof(int), g_tg.stream);
   const int ntot = P.nin[0] + P.nin[1] + P.nin[2];
-  int *reach = nullptr;                  // lmax[ntot] | rmax[ntot]
-  rc = tg_dmalloc(&reach, 2 * (int64_t)ntot);
-  if (rc) return rc;
-  dev.p.push_back(reach);
+  TG_TRY(K.B.reach.alloc(2 * (int64_t)ntot));
+  int *reach = K.B.reach;
   hipMemsetAsync(reach, 0, 2 * (size_t)ntot * sizeof(int), g_tg.stream);
-  if ((int64_t)P.nin[0] * P.nin[1] >= (1ll << 31) || nin_total >= (1ll << 31)) {
+  if ((int64_t)P.nin[0] * P.nin[1] >= (1ll << 31) || K.nin_total >= (1ll << 31)) {
     tg_set_error("tg_ptap_kron: index space too large for 32-bit decomposition");
-    return 100;
+    return TG_KRON_DECLINED;
   }
   tg_magic((unsigned)((int64_t)P.nin[0] * P.nin[1]), &P.mg01, &P.sh01);
   tg_magic((unsigned)P.nin[0], &P.mg0, &P.sh0);
   if (cur->nrows > 0)
     hipLaunchKernelGGL(k_box_reach, dim3((unsigned)std::min<int64_t>(tg_cdiv(cur->nrows, 4), (int64_t)g_tg.num_cu * 32)),
-                       dim3(256), 0, g_tg.stream, cur->rowptr, (const int32_t *)cur->rowcnt, cur->col, cur->nrows, cur_row0, P.nin[0],
-                       P.nin[1],
-                       P.nin[2], P.mg01, P.sh01, P.mg0, P.sh0, reach_stride, reach, reach + ntot);
+                       dim3(256), 0, g_tg.stream, cur->rowptr, (const int32_t *)cur->rowcnt, cur->col, cur->nrows, rq.cur_row0, P.nin[0],
+                       P.nin[1], P.nin[2], P.mg01, P.sh01, P.mg0, P.sh0, K.reach_stride, reach, reach + ntot);
   std::vector<int> hreach(2 * (size_t)ntot);
   hipMemcpyAsync(hreach.data(), reach, 2 * (size_t)ntot * sizeof(int), hipMemcpyDeviceToHost, g_tg.stream);
   hipStreamSynchronize(g_tg.stream);
   // box bounds per output coordinate: hull over the 1-D support of [a - lmax[a], a + rmax[a]]
-  int hw[3] = {0, 0, 0};                 // largest box extent beyond the support (only for reporting)
-  int64_t boxmax = 1;
-  int maxBk[3] = {1, 1, 1};
   std::vector<int> hb;                   // blo | bhi for the three directions, concatenated
   size_t boff[3];
-  {
-    int coord0 = 0;
-    for (int k = 0; k < 3; k++) {
-      boff[k] = hb.size();
-      const int nk = P.nin[k];
-      const int mk = P.nout[k];
-      const int *L = hreach.data() + coord0, *Rr = hreach.data() + ntot + coord0;
-      std::vector<int> lo(mk), hi(mk);
-      for (int i = 0; i < mk; i++) {
-        int l = 0x7fffffff, h = -1;
-        if (k < d && P.contracted[k]) {
-          const tg_kron1d_t &F = fac[k];
-          for (int t = F.t_rowptr[i]; t < F.t_rowptr[i + 1]; t++) {
-            const int a = F.t_col[t];
-            l = std::min(l, a - L[a]);
-            h = std::max(h, a + Rr[a]);
-          }
-          if (h < l) {
-            l = 0;
-            h = 0;
-          }
-        } else {
-          l = i - L[i];
-          h = i + Rr[i];
+  int coord0 = 0;
+  for (int k = 0; k < 3; k++) {
+    boff[k] = hb.size();
+    const int nk = P.nin[k];
+    const int mk = P.nout[k];
+    const int *L = hreach.data() + coord0, *Rr = hreach.data() + ntot + coord0;
+    std::vector<int> lo(mk), hi(mk);
+    for (int i = 0; i < mk; i++) {
+      int l = 0x7fffffff, h = -1;
+      if (k < rq.d && P.contracted[k]) {
+        const tg_kron1d_t &F = rq.fac[k];
+        for (int t = F.t_rowptr[i]; t < F.t_rowptr[i + 1]; t++) {
+          const int a = F.t_col[t];
+          l = std::min(l, a - L[a]);
+          h = std::max(h, a + Rr[a]);
         }
-        l = std::max(l, 0);
-        h = std::min(h, nk - 1);
-        lo[i] = l;
-        hi[i] = h;
-        maxBk[k] = std::max(maxBk[k], h - l + 1);
+        if (h < l) {
+          l = 0;
+          h = 0;
+        }
+      } else {
+        l = i - L[i];
+        h = i + Rr[i];
       }
-      hb.insert(hb.end(), lo.begin(), lo.end());
-      hb.insert(hb.end(), hi.begin(), hi.end());
-      coord0 += nk;
-      boxmax *= maxBk[k];
-      hw[k] = maxBk[k] - maxlen[k];
+      l = std::max(l, 0);
+      h = std::min(h, nk - 1);
+      lo[i] = l;
+      hi[i] = h;
+      K.maxBk[k] = std::max(K.maxBk[k], h - l + 1);
     }
+    hb.insert(hb.end(), lo.begin(), lo.end());
+    hb.insert(hb.end(), hi.begin(), hi.end());
+    coord0 += nk;
+    K.boxmax *= K.maxBk[k];
   }
-  int *dbox = nullptr;
-  rc = tg_dmalloc(&dbox, (int64_t)hb.size());
-  if (rc) {
-    return rc;
-  }
-  dev.p.push_back(dbox);
+  TG_TRY(K.B.box.alloc((int64_t)hb.size()));
+  int *dbox = K.B.box;
   hipMemcpyAsync(dbox, hb.data(), hb.size() * sizeof(int), hipMemcpyHostToDevice, g_tg.stream);
   for (int k = 0; k < 3; k++) {
     P.blo[k] = dbox + boff[k];
     P.bhi[k] = dbox + boff[k] + P.nout[k];
   }
-  int cap = (int)std::min<int64_t>(boxmax, 1 << 20);
+  return 0;
+}
+
+// most output indices of factor F reachable from a window of B consecutive input indices
+static int tg_kron_dmax(const tg_kron1d_t &F, int B) {
+  int D = 1;
+  for (int64_t a0 = 0; a0 + 1 <= F.n; a0++) {
+    const int64_t a1 = std::min<int64_t>(F.n, a0 + B) - 1;
+    int c0 = 0x7fffffff, c1 = -1;
+    // first / last column over the rows of the window (rows are sorted; scan ends only)
+    for (int64_t a = a0; a <= a1; a++)
+      if (F.rowptr[a + 1] > F.rowptr[a]) {
+        c0 = std::min(c0, F.col[F.rowptr[a]]);
+        break;
+      }
+    for (int64_t a = a1; a >= a0; a--)
+      if (F.rowptr[a + 1] > F.rowptr[a]) {
+        c1 = std::max(c1, F.col[F.rowptr[a + 1] - 1]);
+        break;
+      }
+    if (c1 >= c0) D = std::max(D, c1 - c0 + 1);
+  }
+  return D;
+}
+
+// Stage 3: the LDS carve of the box kernel (tables, lists, the two buffers), the column decoding, the workgroup size;
+// declines what does not fit
+static int tg_kron_lds_layout(tg_kron_plan &K) {
+  const tg_kron_request &rq = K.rq;
+  tg_box_args &P = K.P;
+  const int *maxB = K.maxBk;
+  int cap = (int)std::min<int64_t>(K.boxmax, 1 << 20);
   cap = (cap + 7) & ~7;
-  // per direction: largest box, most output indices reachable from a box, table/list layout
-  int maxB[3], Dmax[3] = {1, 1, 1};
+  // per direction: most output indices reachable from a box, table/list layout
   int ctab = 0, nlist = 0, maxl = 1;
   for (int k = 0; k < 3; k++) {
-    maxB[k] = maxBk[k];
     P.coff[k] = ctab;
     P.cstr[k] = 0;
     P.loff[k] = nlist;
-    if (k < d && P.contracted[k]) {
-      const tg_kron1d_t &F = fac[k];
-      Dmax[k] = 1;
-      for (int64_t a0 = 0; a0 + 1 <= F.n; a0++) {
-        const int64_t a1 = std::min<int64_t>(F.n, a0 + maxB[k]) - 1;
-        int c0 = 0x7fffffff, c1 = -1;
-        // first / last column over the rows of the window (rows are sorted; scan ends only)
-        for (int64_t a = a0; a <= a1; a++)
-          if (F.rowptr[a + 1] > F.rowptr[a]) {
-            c0 = std::min(c0, F.col[F.rowptr[a]]);
-            break;
-          }
-        for (int64_t a = a1; a >= a0; a--)
-          if (F.rowptr[a + 1] > F.rowptr[a]) {
-            c1 = std::max(c1, F.col[F.rowptr[a + 1] - 1]);
-            break;
-          }
-        if (c1 >= c0) Dmax[k] = std::max(Dmax[k], c1 - c0 + 1);
-      }
-      maxl = std::max(maxl, maxlen[k]);
+    if (k < rq.d && P.contracted[k]) {
+      const tg_kron1d_t &F = rq.fac[k];
+      K.Dmax[k] = tg_kron_dmax(F, maxB[k]);
+      maxl = std::max(maxl, K.maxlen[k]);
       int rowmax = 1;     // longest row of F^T (entries)
       for (int64_t i = 0; i < F.m; i++) rowmax = std::max(rowmax, F.t_rowptr[i + 1] - F.t_rowptr[i]);
       P.cstr[k] = rowmax;
-      ctab += Dmax[k] * rowmax;
+      ctab += K.Dmax[k] * rowmax;
       nlist += rowmax;
     }
   }
@@ -1317,11 +1469,11 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
   int64_t sz[4];
   int nc = 0;
   {
-    int64_t cur[3] = {maxB[0], maxB[1], maxB[2]};
-    for (int k = 0; k < d; k++)
+    int64_t ext[3] = {maxB[0], maxB[1], maxB[2]};
+    for (int k = 0; k < rq.d; k++)
       if (P.contracted[k]) {
-        cur[k] = Dmax[k];
-        sz[nc++] = cur[0] * cur[1] * cur[2];
+        ext[k] = K.Dmax[k];
+        sz[nc++] = ext[0] * ext[1] * ext[2];
       }
   }
   int64_t c1need = 8;
@@ -1339,411 +1491,405 @@ static int tg_ptap_kron_impl(tg_csr_t cur, int64_t cur_row0, int d, const int64_
   P.nlist = nlist;
   P.cap1 = cap1;
   bool too_many = false;
-  for (int k = 0; k < 3; k++) too_many |= Dmax[k] > TG_BOX_MAXD;
-  // workgroup size: one wave per output row when a row has little work (few operand rows),
-  // a full 256-thread group otherwise
-  int64_t maxcombo = 1;
-  for (int k = 0; k < 3; k++) maxcombo *= (k < d && P.contracted[k]) ? std::max(1, P.cstr[k]) : 1;
-  int nt = 256;   // (a wave-per-row variant, nt = 64, measured slower: rows in flight are LDS-bound either way)
-  (void)maxcombo;
-  if (getenv("TIGAR_BOX_NT")) nt = atoi(getenv("TIGAR_BOX_NT")) == 64 ? 64 : 256;
+  for (int k = 0; k < 3; k++) too_many |= K.Dmax[k] > TG_BOX_MAXD;
+  // workgroup size: 256 (a wave-per-row variant, nt = 64, measured slower: rows in flight are LDS-bound either way);
   // the table slices need one thread per (direction, output index)
-  {
-    int need = 0;
-    for (int k = 0; k < 3; k++) need += (k < d && P.contracted[k]) ? Dmax[k] : 0;
-    if (need > nt) nt = 256;
-  }
-  const size_t lds = tg_box_lds(cap, cap1, ctab, nlist, nt);
-  if (boxmax > (1 << 20) || lds > 150 * 1024 || maxl > TG_BOX_MAXLIST || too_many) {
-    tg_set_error("tg_ptap_kron: accumulator box (%lld entries) does not fit in LDS", (long long)boxmax);
-    return 100;
+  K.nt = K.S.nt;
+  int need = 0;
+  for (int k = 0; k < 3; k++) need += (k < rq.d && P.contracted[k]) ? K.Dmax[k] : 0;
+  if (need > K.nt) K.nt = 256;
+  K.lds = tg_box_lds(cap, cap1, ctab, nlist, K.nt);
+  if (K.boxmax > (1 << 20) || K.lds > 150 * 1024 || maxl > TG_BOX_MAXLIST || too_many) {
+    tg_set_error("tg_ptap_kron: accumulator box (%lld entries) does not fit in LDS", (long long)K.boxmax);
+    return TG_KRON_DECLINED;
   }
   P.cap = cap;
-  tg_magic((unsigned)((int64_t)P.nin[0] * P.nin[1]), &P.mg01, &P.sh01);
-  tg_magic((unsigned)P.nin[0], &P.mg0, &P.sh0);
-  {
-    const uint64_t n01u = (uint64_t)P.nin[0] * P.nin[1];
-    P.fast24 = 0;
-    if (!getenv("TIGAR_BOX_SLOWDECODE") && n01u < (1u << 23) && n01u * (uint64_t)maxBk[2] <= (1u << 24) &&
-        (int64_t)maxBk[0] * maxBk[1] < (1 << 23) &&
-        tg_magic24((unsigned)n01u, n01u * (uint64_t)maxBk[2], &P.m24a, &P.sh24a, &P.hi24a) &&
-        tg_magic24((unsigned)P.nin[0], n01u, &P.m24b, &P.sh24b, &P.hi24b))
-      P.fast24 = 1;
+  const uint64_t n01u = (uint64_t)P.nin[0] * P.nin[1];
+  P.fast24 = 0;
+  if (!K.S.slowdecode && n01u < (1u << 23) && n01u * (uint64_t)maxB[2] <= (1u << 24) && (int64_t)maxB[0] * maxB[1] < (1 << 23) &&
+      tg_magic24((unsigned)n01u, n01u * (uint64_t)maxB[2], &P.m24a, &P.sh24a, &P.hi24a) &&
+      tg_magic24((unsigned)P.nin[0], n01u, &P.m24b, &P.sh24b, &P.hi24b))
+    P.fast24 = 1;
+  if (K.S.prof && !K.B.prof.alloc(8)) {          // per-phase cycle counters
+    hipMemsetAsync(K.B.prof, 0, 8 * sizeof(unsigned long long), g_tg.stream);
+    P.prof = K.B.prof;
   }
-  unsigned long long *prof = nullptr;
-  if (getenv("TIGAR_BOX_PROF") && !tg_dmalloc(&prof, 8)) {
-    dev.p.push_back(prof);
-    hipMemsetAsync(prof, 0, 8 * sizeof(unsigned long long), g_tg.stream);
-    P.prof = prof;
-  }
+  return 0;
+}
+
+// Stage 4: line or box kernel, the variant, (a, u) and the hi flag -> the row of g_kron_routes; the rest of the arguments
+static int tg_kron_choose(tg_kron_plan &K) {
+  const tg_kron_request &rq = K.rq;
+  tg_box_args &P = K.P;
+  tg_line_args &Q = K.Q;
   // one contracted direction: wave-per-run "line" kernel
-  tg_line_args Q;
-  memset(&Q, 0, sizeof(Q));
-  int line_variant = 0;          // 0: no, 1: <20,10>, 2: <32,16>
-  size_t line_lds = 0;
-  {
-    int ncon = 0, a = -1;
-    for (int k = 0; k < d; k++)
-      if (P.contracted[k]) {
-        ncon++;
-        a = k;
-      }
-    const char *env = getenv("TIGAR_PTAP_LINE");
-    if (ncon == 1 && !(env && atoi(env) == 0) && P.cstr[a] <= 64 && boxmax <= (1 << 16) && P.fast24) {
-      if (maxBk[a] <= 20 && Dmax[a] <= 10)
-        line_variant = 1;
-      else if (maxBk[a] <= 32 && Dmax[a] <= 16)
-        line_variant = 2;
-      Q.a = a;
-      Q.capx = (int)((boxmax + 7) & ~7ll);
-      Q.capy = 0;                                  // (contracted in place)
-      if (Dmax[a] > maxBk[a]) line_variant = 0;
-      const int bam = line_variant == 1 ? 20 : 32, dmt = line_variant == 1 ? 10 : 16;
-      line_lds = ((size_t)Q.capx + (size_t)bam * dmt + dmt) * 8;
-      if (line_lds > 60 * 1024) line_variant = 0;
-      // direction of the runs: the first uncontracted one; instantiated (a, u) pairs only
-      int u = -1;
-      for (int k = 0; k < d && u < 0; k++)
-        if (!P.contracted[k] && P.nout[k] > 1) u = k;
-      if (!((a == 0 && u == 1) || (a >= 1 && u == 0))) u = -1;
-      if (u < 0 && a != 0) line_variant = 0;
-      Q.u = u;
+  int ncon = 0, a = -1;
+  for (int k = 0; k < rq.d; k++)
+    if (P.contracted[k]) {
+      ncon++;
+      a = k;
     }
+  if (ncon == 1 && K.S.line && P.cstr[a] <= 64 && K.boxmax <= (1 << 16) && P.fast24) {
+    if (K.maxBk[a] <= 20 && K.Dmax[a] <= 10)
+      K.line_variant = 1;
+    else if (K.maxBk[a] <= 32 && K.Dmax[a] <= 16)
+      K.line_variant = 2;
+    Q.a = a;
+    Q.capx = (int)((K.boxmax + 7) & ~7ll);
+    Q.capy = 0;                                  // (contracted in place)
+    if (K.Dmax[a] > K.maxBk[a]) K.line_variant = 0;
+    const int bam = K.line_variant == 1 ? 20 : 32, dmt = K.line_variant == 1 ? 10 : 16;
+    K.line_lds = ((size_t)Q.capx + (size_t)bam * dmt + dmt) * 8;
+    if (K.line_lds > 60 * 1024) K.line_variant = 0;
+    // direction of the runs: the first uncontracted one; instantiated (a, u) pairs only
+    int u = -1;
+    for (int k = 0; k < rq.d && u < 0; k++)
+      if (!P.contracted[k] && P.nout[k] > 1) u = k;
+    if (!((a == 0 && u == 1) || (a >= 1 && u == 0))) u = -1;
+    if (u < 0 && a != 0) K.line_variant = 0;
+    Q.u = u;
   }
-  if (cur->rowptr_val && !line_variant) {   // the box kernel reads col and val through one row start
-    return 102;
+  if (rq.cur->rowptr_val && !K.line_variant) return TG_KRON_COMPACT;   // the box kernel reads col and val through one row start
+  K.route = K.line_variant ? tg_kron_route_find(K.line_variant, Q.a, Q.u, P.hi24a && P.hi24b)
+                           : tg_kron_route_find(0, TG_BOXMODE_BUMP, K.nt, 0);
+  if (!K.route) {
+    tg_set_error("tg_ptap_kron: internal error (no kernel for this stage)");
+    return 1;
   }
-  if ((int64_t)P.nin[0] * P.nin[1] >= (1ll << 31) || nin_total >= (1ll << 31)) {
-    tg_set_error("tg_ptap_kron: index space too large for 32-bit decomposition");
-    return 100;
-  }
-  const double avg = cur->nrows ? (double)cur->nnz / (double)cur->nrows : 1.0;
-  {
-    const char *s = getenv("TIGAR_BOX_G1");
-    int g = s ? atoi(s) : 4;
-    if (!s) while (g < 64 && g * 2 <= avg * 0.44) g <<= 1;
-    P.g1 = g;
-    P.lg1 = 0;
-    while ((1 << P.lg1) < g) P.lg1++;
-  }
-  P.out_row0 = out_row0;
-  P.out_nrows = out_row1 - out_row0;
+  const double avg = rq.cur->nrows ? (double)rq.cur->nnz / (double)rq.cur->nrows : 1.0;
+  int g = K.S.g1;
+  if (!K.S.g1_set) while (g < 64 && g * 2 <= avg * 0.44) g <<= 1;
+  P.g1 = g;
+  P.lg1 = 0;
+  while ((1 << P.lg1) < g) P.lg1++;
+  P.out_row0 = rq.out_row0;
+  P.out_nrows = rq.out_row1 - rq.out_row0;
   P.row_stride = 1;
-  const int64_t nrows = P.out_nrows;
-  tg_csr_s *k = nullptr;
-  tg_dbuf<uint8_t> mask;
-  tg_bump t(line_variant ? "line stage" : "box stage");
-  if (nrows == 0) {
-    rc = tg_csr_alloc(0, nout_total, 0, &k);
-    if (!rc) hipMemsetAsync(k->rowptr, 0, sizeof(int64_t), g_tg.stream);
-  } else {
-    if (nzero > 0) rc = tg_build_dof_mask(zero_dofs, nzero, nout_total, &mask.p);
-    if (!rc) rc = t.init(nrows, true, 1, 3);
-    int64_t *const cnt = t.cnt, *const off = t.off;
-    double mean_k = 0.0;
-    int hmax[3] = {0, 0, 0};
-    // Capacity of the temporary: from the last product with the same signature (stage, index spaces in
-    // the first two directions, kernel variant) if there was one -- entries actually used per row, chunk
-    // slack included, largest value seen -- else from a probe of 512 sample rows.  A stage of a
-    // streamed assembly is called once per sub-slab with the same signature; probe + scan + host round
-    // trip cost ~0.8 ms of the ~9 ms a stage takes at 256^3 p=3.  An estimate that turns out too small
-    // is caught by the kernel (TG_BOX_CAP) and retried with a larger temporary as before.
-    const std::array<int, 8> cap_key = {d, P.contracted[0] | (P.contracted[1] << 1) | (P.contracted[2] << 2), P.nin[0],
-                                        P.nin[1], P.nout[0], P.nout[1], line_variant, loose_out ? 1 : (dest ? 2 : 0)};
-    // (first: largest use per row seen, second: capacity per row of the last allocation that was large
-    // enough -- re-used as it is, so that the same sub-slab asks for the same block in every step: a
-    // capacity recomputed from the use would land in another size class than the probe-sized
-    // allocation of the first step and cost a round of hipMalloc in the second)
-    struct tg_cap_entry {
-      double used_pr = 0.0, cap_pr = 0.0;
-      int hmax2 = 0;
-    };
-    static std::map<std::array<int, 8>, tg_cap_entry> cap_cache;
-    static const bool force_probe = getenv("TIGAR_PTAP_PROBE") && atoi(getenv("TIGAR_PTAP_PROBE")) == 1;
-    const auto cached = cap_cache.find(cap_key);
-    const bool have_cached = !force_probe && cached != cap_cache.end();
-    if (!rc && have_cached) {
-      mean_k = cached->second.used_pr;
-      hmax[2] = cached->second.hmax2;
-    }
-    if (!rc && !have_cached) {
-      // probe a sample of rows: mean row length -> capacity of the temporary
-      tg_box_args S = P;
-      S.prof = nullptr;
-      const int64_t nsample = std::min<int64_t>(nrows, 512);
-      S.out_nrows = nsample;
-      S.row_stride = std::max<int64_t>(1, nrows / nsample);
-      hipMemsetAsync(cnt, 0, (size_t)(nrows + 1) * sizeof(int64_t), g_tg.stream);
-      hipMemsetAsync(status, 0, 3 * sizeof(int), g_tg.stream);
-      if (nt == 64)
-        hipLaunchKernelGGL((k_ptap_box<TG_BOXMODE_PROBE, 64>), dim3((unsigned)(tg_cdiv(nsample, 8) * 8)), dim3(64), lds,
-                           g_tg.stream, S, cnt, (int64_t *)nullptr, (int32_t *)nullptr, (double *)nullptr,
-                           (unsigned long long *)nullptr, (int64_t)0, (const uint8_t *)nullptr, 0.0, status,
-                           status + 1);
-      else
-        hipLaunchKernelGGL((k_ptap_box<TG_BOXMODE_PROBE, 256>), dim3((unsigned)(tg_cdiv(nsample, 8) * 8)), dim3(256),
-                           lds, g_tg.stream, S, cnt, (int64_t *)nullptr, (int32_t *)nullptr, (double *)nullptr,
-                           (unsigned long long *)nullptr, (int64_t)0, (const uint8_t *)nullptr, 0.0, status,
-                           status + 1);
-      hipMemcpyAsync(hmax, status, 3 * sizeof(int), hipMemcpyDeviceToHost, g_tg.stream);
-      int64_t total = 0;
-      rc = tg_exclusive_scan_i64(cnt, nrows, &total);
-      hipStreamSynchronize(g_tg.stream);
-      if (!rc && hmax[0] == TG_BOX_TOOBIG) rc = 100;
-      if (!rc && hmax[0] == TG_BOX_OUTSIDE) rc = 101;
-      if (!rc && hmax[0] == TG_BOX_RANGE) {
-        tg_set_error("tg_ptap_kron: the row block does not cover the rows referenced (slab halo too small)");
-        rc = 3;
-      }
-      mean_k = (double)total / (double)nsample;
-    }
-    int64_t capacity = (int64_t)(mean_k * 1.05 * (double)nrows) + hmax[2] + 1024;
-    if (line_variant && !have_cached) capacity = (int64_t)(capacity * 1.3) + nrows / 8 * 64;   // slack of the wave-private chunks
-    // (measured use incl. the slack of the wave-private chunks, which varies with the order in which the
-    // waves reserve: +20 %.  With +10 % a stage of 128^3 p=2 overflowed now and then, and a retry means
-    // a new size class from hipMalloc: 0.19 instead of 0.035 s)
-    if (have_cached) capacity = (int64_t)(cached->second.cap_pr * (double)nrows) + 65536;
-    if (!rc && !line_variant) {        // row maxima of the operand: bounds of the box kernel's integer accumulation
-      double *rowmax = nullptr;
-      rc = tg_dmalloc(&rowmax, std::max<int64_t>(cur->nrows, 1));
-      if (!rc) {
-        dev.p.push_back(rowmax);
-        if (cur->nrows > 0)
-          hipLaunchKernelGGL(k_box_row_absmax, dim3((unsigned)std::min<int64_t>(tg_cdiv(cur->nrows, 4), (int64_t)g_tg.num_cu * 16)),
-                             dim3(256), 0, g_tg.stream, cur->rowptr, (const int64_t *)cur->rowptr_val, (const int32_t *)cur->rowcnt,
-                             cur->val, cur->nrows, rowmax);
-        P.rowmax = rowmax;
-      }
-    }
-    t.capacity = capacity;
-    auto launch = [&](int) {
-      int32_t *const tcol = t.tcol;
-      double *const tval = t.tval;
-      unsigned long long *const cursor = t.cursor;
-      const int64_t capacity = t.capacity;
-      if (line_variant) {
-        // runs along the first uncontracted direction; output space in wave-private chunks
-        const int u = Q.u;
-        int64_t nwaves = nrows;
-        if (u >= 0) {
-          const int64_t m0 = P.nout[0], m1 = P.nout[1], m01 = m0 * m1;
-          const int64_t ra = out_row0, rb = out_row1 - 1;
-          int64_t ulo, uhi, x0, nx;
-          if (u == 2) {
-            ulo = ra / m01;
-            uhi = rb / m01;
-            x0 = 0;
-            nx = m01;
-          } else if (u == 1) {
-            ulo = 0;
-            uhi = m1 - 1;
-            x0 = m0 * (ra / m01);
-            nx = m0 * (rb / m01 - ra / m01 + 1);
-          } else {
-            ulo = 0;
-            uhi = m0 - 1;
-            x0 = ra / m0;
-            nx = rb / m0 - x0 + 1;
-          }
-          const int64_t span = uhi - ulo + 1;
-          // rows per wave: 20 measured best at 96^3 and 256^3 p=3 (x/y/z stage at 96^3: 32 rows 30.9 / 15.8 / 8.5 ms,
-          // 24: 30.2 / 15.1 / 8.1, 20: 29.0 / 13.2 / 7.3, 16: 29.6 / 14.2 / 7.3, 12: 29.4 / 13.7 / 7.0)
-          int64_t T = std::min<int64_t>(getenv("TIGAR_LINE_RUN") ? std::max(1, atoi(getenv("TIGAR_LINE_RUN"))) : 20, span);
-          while (T > 1 && nx * tg_cdiv(span, T) < (int64_t)g_tg.num_cu * 64) T = (T + 1) / 2;
-          Q.mlen = (int)T;
-          Q.ulo = (int)ulo;
-          Q.uhi = (int)uhi;
-          Q.x0 = x0;
-          Q.nx = nx;
-          Q.nchunk = tg_cdiv(span, T);
-          nwaves = nx * Q.nchunk;
-        }
-        Q.grab = getenv("TIGAR_LINE_GRAB") ? atoll(getenv("TIGAR_LINE_GRAB")) : 8192;
-        const unsigned grid = (unsigned)(tg_cdiv(nwaves, 8) * 8);
-#define TG_LINE_LAUNCH(BA, DM, AA, UU)                                                                                 \
-  do {                                                                                                                  \
-    if (line_hi)                                                                                                        \
-      hipLaunchKernelGGL((k_ptap_line<BA, DM, AA, UU, true>), dim3(grid), dim3(64), line_lds, g_tg.stream, P, Q, cnt,  \
-                         off, tcol, tval, cursor, capacity, (const uint8_t *)mask, diag, status);                      \
-    else                                                                                                                \
-      hipLaunchKernelGGL((k_ptap_line<BA, DM, AA, UU, false>), dim3(grid), dim3(64), line_lds, g_tg.stream, P, Q, cnt, \
-                         off, tcol, tval, cursor, capacity, (const uint8_t *)mask, diag, status);                      \
-  } while (0)
-#define TG_LINE_DISPATCH(BA, DM)                                  \
-  do {                                                            \
-    if (Q.a == 0 && u == 1) TG_LINE_LAUNCH(BA, DM, 0, 1);         \
-    else if (Q.a == 1 && u == 0) TG_LINE_LAUNCH(BA, DM, 1, 0);    \
-    else if (Q.a == 2 && u == 0) TG_LINE_LAUNCH(BA, DM, 2, 0);    \
-    else TG_LINE_LAUNCH(BA, DM, 0, -1);                           \
-  } while (0)
-        const bool line_hi = P.hi24a && P.hi24b;
-        if (line_variant == 1)
-          TG_LINE_DISPATCH(20, 10);
-        else
-          TG_LINE_DISPATCH(32, 16);
-      } else if (!P.rowmax) {
-        tg_set_error("tg_ptap_kron: internal error (no row maxima for the box kernel)");
-        return 1;
-      } else if (nt == 64)
-        hipLaunchKernelGGL((k_ptap_box<TG_BOXMODE_BUMP, 64>), dim3((unsigned)(tg_cdiv(nrows, 8) * 8)), dim3(64), lds,
-                           g_tg.stream, P, cnt, off, tcol, tval, cursor, capacity, (const uint8_t *)mask, diag, status,
-                           status + 1);
-      else
-        hipLaunchKernelGGL((k_ptap_box<TG_BOXMODE_BUMP, 256>), dim3((unsigned)(tg_cdiv(nrows, 8) * 8)), dim3(256), lds,
-                           g_tg.stream, P, cnt, off, tcol, tval, cursor, capacity, (const uint8_t *)mask, diag, status,
-                           status + 1);
-      return 0;
-    };
-    // growth rule: an overflow doubles the temporary; what was used, and the capacity that worked, go to the cache
-    auto decide = [&](int attempt, const int *hs, unsigned long long used) {
-      const int h = hs[0];
-      if (prof) {
-        unsigned long long hp[8];
-        hipMemcpy(hp, prof, sizeof(hp), hipMemcpyDeviceToHost);
-        const double tot = (double)(hp[0] + hp[1] + hp[2] + hp[3]) + 1e-30;
-        fprintf(stderr, "[tigar] %s phases (%lld rows, fast24=%d): setup %.1f%%  scatter %.1f%%  contract %.1f%%  write %.1f%%\n",
-                line_variant ? "line" : "box", (long long)nrows, P.fast24, 100.0 * hp[0] / tot, 100.0 * hp[1] / tot,
-                100.0 * hp[2] / tot, 100.0 * hp[3] / tot);
-      }
-      if (h == TG_BOX_OK) {
-        tg_cap_entry &c = cap_cache[cap_key];
-        c.used_pr = std::max(c.used_pr, (double)used / (double)nrows);
-        c.hmax2 = std::max(c.hmax2, hmax[2]);
-        const double cp = (double)std::max<int64_t>(t.capacity - 65536, 0) / (double)nrows;
-        // fixed once it has worked (a capacity that follows the largest use seen creeps upwards over
-        // the first steps and every change is a round of hipMalloc); only an overflow moves it
-        if (c.cap_pr == 0.0 || attempt > 0) c.cap_pr = cp;
-        return (int)TG_BUMP_DONE;
-      }
-      if (h == TG_BOX_CAP) {
-        tg_cap_entry &c = cap_cache[cap_key];      // what was reserved before the kernel gave up is a lower bound
-        c.used_pr = std::max(c.used_pr, (double)used / (double)nrows);
-        c.hmax2 = std::max(c.hmax2, hmax[2]);
-        t.capacity = std::max<int64_t>((int64_t)used + 1024, t.capacity * 2);
-        return (int)TG_BUMP_RETRY;
-      }
-      if (h == TG_BOX_TOOBIG) return 100;
-      if (h == TG_BOX_OUTSIDE) return 101;
-      tg_set_error("tg_ptap_kron: kernel status %d", h);
-      return h == TG_BOX_RANGE ? 3 : 4;
-    };
-    if (!rc) rc = t.run(6, launch, decide);
-    if (rc == TG_BUMP_NORUN) {
-      tg_set_error("tg_ptap_kron: kernel failed to run (LDS %zu B)", lds);
-      rc = 1;
-    }
-    if (rc == TG_BUMP_RETRY) {                       // (six doublings were not enough)
-      tg_set_error("tg_ptap_kron: kernel status %d", (int)TG_BOX_CAP);
-      rc = 4;
-    }
-    const unsigned long long used_final = t.used;
-    if (!rc && loose_out) {
-      // intermediate stage: hand the temporary over as it is (rows where the kernel put them, lengths
-      // in rowcnt) -- the consumers (next stage, vstack) read (start, length) pairs, so the
-      // row-reorder copy and the scan are skipped
-      k = new tg_csr_s();
-      k->nrows = nrows;
-      k->ncols = nout_total;
-      k->nnz = (int64_t)used_final;
-      rc = tg_dmalloc(&k->rowcnt, nrows);
-      if (!rc) {
-        hipLaunchKernelGGL(k_i64_to_i32, dim3(tg_grid_1d(nrows, 256)), dim3(256), 0, g_tg.stream, cnt, k->rowcnt, nrows);
-        const int64_t endm = (int64_t)used_final;
-        hipMemcpyAsync(off + nrows, &endm, sizeof(int64_t), hipMemcpyHostToDevice, g_tg.stream);
-        hipStreamSynchronize(g_tg.stream);
-        k->rowptr = t.off.release();
-        k->col = t.tcol.release();
-        k->val = t.tval.release();
-      } else {
-        delete k;
-        k = nullptr;
-      }
-    } else if (!rc && dest) {
-      // last stage of a slab: rows go straight into the slab-wise builder of K (no block of its own,
-      // no second copy by tg_csr_builder_append)
-      int64_t nnz = 0;
-      rc = tg_exclusive_scan_i64(cnt, nrows, &nnz);
-      if (!rc && dest->m->ncols != nout_total) {
-        tg_set_error("tg_ptap_kron_append: the builder has %lld columns, the product %lld", (long long)dest->m->ncols,
-                     (long long)nout_total);
-        rc = 2;
-      }
-      if (!rc) rc = tg_csr_builder_reserve(dest, nrows, nnz);
-      if (!rc) {
-        int64_t *rp = dest->m->rowptr + dest->rows_done;       // rp[0] == nnz_done already
-        hipLaunchKernelGGL(k_shift_i64, dim3(tg_grid_1d(nrows, 256)), dim3(256), 0, g_tg.stream, rp + 1, cnt + 1, nrows,
-                           dest->nnz_done);
-        rc = tg_rows_reorder("tg_ptap_kron_append:", rp, off, nullptr, t.tcol, t.tval, nrows, dest->m->col, dest->m->val);
-        if (!rc) {
-          dest->rows_done += nrows;
-          dest->nnz_done += nnz;
-        }
-      }
-    } else if (!rc) {
-      rc = t.finish_csr("tg_ptap_kron:", nout_total, &k, nullptr, nullptr);
-    }
+  return 0;
+}
+
+// probe a sample of rows: mean row length -> capacity of the temporary
+static int tg_kron_probe(tg_kron_plan &K, tg_bump &t, double *mean_k) {
+  const int64_t nrows = K.P.out_nrows;
+  int *const status = t.status();
+  tg_box_args S = K.P;
+  S.prof = nullptr;
+  const int64_t nsample = std::min<int64_t>(nrows, 512);
+  S.out_nrows = nsample;
+  S.row_stride = std::max<int64_t>(1, nrows / nsample);
+  hipMemsetAsync(t.cnt, 0, (size_t)(nrows + 1) * sizeof(int64_t), g_tg.stream);
+  hipMemsetAsync(status, 0, 3 * sizeof(int), g_tg.stream);
+  hipLaunchKernelGGL(tg_kron_route_find(0, TG_BOXMODE_PROBE, K.nt, 0)->box, dim3((unsigned)(tg_cdiv(nsample, 8) * 8)), dim3(K.nt),
+                     K.lds, g_tg.stream, S, t.cnt.get(), (int64_t *)nullptr, (int32_t *)nullptr, (double *)nullptr,
+                     (unsigned long long *)nullptr, (int64_t)0, (const uint8_t *)nullptr, 0.0, status, status + 1);
+  int hmax[3] = {0, 0, 0};
+  hipMemcpyAsync(hmax, status, 3 * sizeof(int), hipMemcpyDeviceToHost, g_tg.stream);
+  int64_t total = 0;
+  const int rc = tg_exclusive_scan_i64(t.cnt, nrows, &total);
+  hipStreamSynchronize(g_tg.stream);
+  if (rc) return rc;
+  if (hmax[0] == TG_BOX_TOOBIG) return TG_KRON_DECLINED;
+  if (hmax[0] == TG_BOX_OUTSIDE) return TG_KRON_OUTSIDE;
+  if (hmax[0] == TG_BOX_RANGE) {
+    tg_set_error("tg_ptap_kron: the row block does not cover the rows referenced (slab halo too small)");
+    return 3;
   }
+  K.hmax2 = hmax[2];
+  *mean_k = (double)total / (double)nsample;
+  return 0;
+}
+
+// Stage 5.  Capacity of the temporary: from the last product with the same signature (tg_kron_cap_key) if there was
+// one -- entries actually used per row, chunk slack included, largest value seen -- else from a probe of 512 sample
+// rows.  A stage of a streamed assembly is called once per sub-slab with the same signature; probe + scan + host round
+// trip cost ~0.8 ms of the ~9 ms a stage takes at 256^3 p=3.  An estimate that turns out too small is caught by the
+// kernel (TG_BOX_CAP) and retried with a larger temporary as before.
+static int tg_kron_capacity(tg_kron_plan &K, tg_bump &t) {
+  const tg_box_args &P = K.P;
+  const int64_t nrows = P.out_nrows;
+  K.cap_key = {P.d, P.contracted[0] | (P.contracted[1] << 1) | (P.contracted[2] << 2), P.nin[0], P.nin[1], P.nout[0], P.nout[1],
+               K.line_variant, K.rq.ending};
+  tg_kron_cap_entry cached;
+  K.have_cached = !K.S.force_probe && tg_kron_cap_lookup(K.cap_key, &cached);
+  double mean_k = 0.0;
+  if (K.have_cached) {
+    mean_k = cached.used_pr;
+    K.hmax2 = cached.hmax2;
+  } else {
+    TG_TRY(tg_kron_probe(K, t, &mean_k));
+  }
+  int64_t capacity = (int64_t)(mean_k * 1.05 * (double)nrows) + K.hmax2 + 1024;
+  if (K.line_variant && !K.have_cached) capacity = (int64_t)(capacity * 1.3) + nrows / 8 * 64;   // slack of the wave-private chunks
+  // (measured use incl. the slack of the wave-private chunks, which varies with the order in which the
+  // waves reserve: +20 %.  With +10 % a stage of 128^3 p=2 overflowed now and then, and a retry means
+  // a new size class from hipMalloc: 0.19 instead of 0.035 s)
+  if (K.have_cached) capacity = (int64_t)(cached.cap_pr * (double)nrows) + 65536;
+  t.capacity = capacity;
+  return 0;
+}
+
+// runs of the line kernel along the first uncontracted direction, output space in wave-private chunks; returns the waves
+static int64_t tg_kron_line_runs(tg_kron_plan &K) {
+  const tg_box_args &P = K.P;
+  tg_line_args &Q = K.Q;
+  const int u = Q.u;
+  int64_t nwaves = P.out_nrows;
+  if (u >= 0) {
+    const int64_t m0 = P.nout[0], m1 = P.nout[1], m01 = m0 * m1;
+    const int64_t ra = K.rq.out_row0, rb = K.rq.out_row1 - 1;
+    int64_t ulo, uhi, x0, nx;
+    if (u == 2) {
+      ulo = ra / m01;
+      uhi = rb / m01;
+      x0 = 0;
+      nx = m01;
+    } else if (u == 1) {
+      ulo = 0;
+      uhi = m1 - 1;
+      x0 = m0 * (ra / m01);
+      nx = m0 * (rb / m01 - ra / m01 + 1);
+    } else {
+      ulo = 0;
+      uhi = m0 - 1;
+      x0 = ra / m0;
+      nx = rb / m0 - x0 + 1;
+    }
+    const int64_t span = uhi - ulo + 1;
+    // rows per wave: 20 measured best at 96^3 and 256^3 p=3 (x/y/z stage at 96^3: 32 rows 30.9 / 15.8 / 8.5 ms,
+    // 24: 30.2 / 15.1 / 8.1, 20: 29.0 / 13.2 / 7.3, 16: 29.6 / 14.2 / 7.3, 12: 29.4 / 13.7 / 7.0)
+    int64_t T = std::min<int64_t>(K.S.line_run, span);
+    while (T > 1 && nx * tg_cdiv(span, T) < (int64_t)g_tg.num_cu * 64) T = (T + 1) / 2;
+    Q.mlen = (int)T;
+    Q.ulo = (int)ulo;
+    Q.uhi = (int)uhi;
+    Q.x0 = x0;
+    Q.nx = nx;
+    Q.nchunk = tg_cdiv(span, T);
+    nwaves = nx * Q.nchunk;
+  }
+  Q.grab = K.S.line_grab;
+  return nwaves;
+}
+
+static void tg_kron_prof_print(const tg_kron_plan &K) {
+  unsigned long long hp[8];
+  hipMemcpy(hp, K.B.prof, sizeof(hp), hipMemcpyDeviceToHost);
+  const double tot = (double)(hp[0] + hp[1] + hp[2] + hp[3]) + 1e-30;
+  fprintf(stderr, "[tigar] %s phases (%lld rows, fast24=%d): setup %.1f%%  scatter %.1f%%  contract %.1f%%  write %.1f%%\n",
+          K.line_variant ? "line" : "box", (long long)K.P.out_nrows, K.P.fast24, 100.0 * hp[0] / tot, 100.0 * hp[1] / tot,
+          100.0 * hp[2] / tot, 100.0 * hp[3] / tot);
+}
+
+// Stage 6: the chosen kernel on the temporary, grown and launched again by tg_bump while it overflows
+static int tg_kron_run(tg_kron_plan &K, tg_bump &t) {
+  tg_csr_s *cur = K.rq.cur;
+  tg_box_args &P = K.P;
+  const int64_t nrows = P.out_nrows;
+  int *const status = t.status();
+  if (!K.line_variant) {        // row maxima of the operand: bounds of the box kernel's integer accumulation
+    TG_TRY(K.B.rowmax.alloc(std::max<int64_t>(cur->nrows, 1)));
+    if (cur->nrows > 0)
+      hipLaunchKernelGGL(k_box_row_absmax, dim3((unsigned)std::min<int64_t>(tg_cdiv(cur->nrows, 4), (int64_t)g_tg.num_cu * 16)),
+                         dim3(256), 0, g_tg.stream, cur->rowptr, (const int64_t *)cur->rowptr_val, (const int32_t *)cur->rowcnt,
+                         cur->val, cur->nrows, K.B.rowmax.get());
+    P.rowmax = K.B.rowmax;
+  }
+  const unsigned grid = (unsigned)(tg_cdiv(K.line_variant ? tg_kron_line_runs(K) : nrows, 8) * 8);
+  if (getenv("TIGAR_TRACE")) fprintf(stderr, "[tigar] kron stage: %s\n", K.route->name);
+  auto launch = [&](int) {
+    if (K.line_variant)
+      hipLaunchKernelGGL(K.route->line, dim3(grid), dim3(64), K.line_lds, g_tg.stream, P, K.Q, t.cnt.get(), t.off.get(), t.tcol.get(),
+                         t.tval.get(), t.cursor.get(), t.capacity, (const uint8_t *)K.B.mask, K.rq.diag, status);
+    else if (!P.rowmax) {
+      tg_set_error("tg_ptap_kron: internal error (no row maxima for the box kernel)");
+      return 1;
+    } else
+      hipLaunchKernelGGL(K.route->box, dim3(grid), dim3(K.nt), K.lds, g_tg.stream, P, t.cnt.get(), t.off.get(), t.tcol.get(),
+                         t.tval.get(), t.cursor.get(), t.capacity, (const uint8_t *)K.B.mask, K.rq.diag, status, status + 1);
+    return 0;
+  };
+  // growth rule: an overflow doubles the temporary; what was used, and the capacity that worked, go to the cache
+  auto decide = [&](int attempt, const int *hs, unsigned long long used) {
+    const int h = hs[0];
+    if (K.B.prof) tg_kron_prof_print(K);
+    const double used_pr = (double)used / (double)nrows;
+    if (h == TG_BOX_OK) {
+      tg_kron_cap_record(K.cap_key, used_pr, K.hmax2, (double)std::max<int64_t>(t.capacity - 65536, 0) / (double)nrows, attempt > 0);
+      return (int)TG_BUMP_DONE;
+    }
+    if (h == TG_BOX_CAP) {
+      tg_kron_cap_record(K.cap_key, used_pr, K.hmax2, -1.0, false);
+      t.capacity = std::max<int64_t>((int64_t)used + 1024, t.capacity * 2);
+      return (int)TG_BUMP_RETRY;
+    }
+    if (h == TG_BOX_TOOBIG) return (int)TG_KRON_DECLINED;
+    if (h == TG_BOX_OUTSIDE) return (int)TG_KRON_OUTSIDE;
+    tg_set_error("tg_ptap_kron: kernel status %d", h);
+    return h == TG_BOX_RANGE ? 3 : 4;
+  };
+  int rc = t.run(6, launch, decide);
+  if (rc == TG_BUMP_NORUN) {
+    tg_set_error("tg_ptap_kron: kernel failed to run (LDS %zu B)", K.lds);
+    rc = 1;
+  }
+  if (rc == TG_BUMP_RETRY) {                       // (six doublings were not enough)
+    tg_set_error("tg_ptap_kron: kernel status %d", (int)TG_BOX_CAP);
+    rc = 4;
+  }
+  return rc;
+}
+
+// Ending of an intermediate stage: hand the temporary over as it is (rows where the kernel put them, lengths in
+// rowcnt) -- the consumers (next stage, vstack) read (start, length) pairs, so the row-reorder copy and the scan are skipped
+static int tg_kron_end_loose(tg_kron_plan &K, tg_bump &t, tg_csr_s **out) {
+  const int64_t nrows = t.nrows;
+  tg_csr_s *k = new tg_csr_s();
+  k->nrows = nrows;
+  k->ncols = K.nout_total;
+  k->nnz = (int64_t)t.used;
+  const int rc = tg_dmalloc(&k->rowcnt, nrows);
+  if (rc) {
+    delete k;
+    return rc;
+  }
+  hipLaunchKernelGGL(k_i64_to_i32, dim3(tg_grid_1d(nrows, 256)), dim3(256), 0, g_tg.stream, t.cnt.get(), k->rowcnt, nrows);
+  const int64_t endm = (int64_t)t.used;
+  hipMemcpyAsync(t.off + nrows, &endm, sizeof(int64_t), hipMemcpyHostToDevice, g_tg.stream);
+  hipStreamSynchronize(g_tg.stream);
+  k->rowptr = t.off.release();
+  k->col = t.tcol.release();
+  k->val = t.tval.release();
+  *out = k;
+  return 0;
+}
+
+// Ending of the last stage of a slab: rows go straight into the slab-wise builder of K (no block of its own, no second
+// copy by tg_csr_builder_append)
+static int tg_kron_end_append(tg_kron_plan &K, tg_bump &t) {
+  tg_csr_builder_s *dest = K.rq.dest;
+  const int64_t nrows = t.nrows;
+  int64_t nnz = 0;
+  TG_TRY(tg_exclusive_scan_i64(t.cnt, nrows, &nnz));
+  if (dest->m->ncols != K.nout_total) {
+    tg_set_error("tg_ptap_kron_append: the builder has %lld columns, the product %lld", (long long)dest->m->ncols,
+                 (long long)K.nout_total);
+    return 2;
+  }
+  TG_TRY(tg_csr_builder_reserve(dest, nrows, nnz));
+  int64_t *rp = dest->m->rowptr + dest->rows_done;       // rp[0] == nnz_done already
+  hipLaunchKernelGGL(k_shift_i64, dim3(tg_grid_1d(nrows, 256)), dim3(256), 0, g_tg.stream, rp + 1, t.cnt + 1, nrows, dest->nnz_done);
+  TG_TRY(tg_rows_reorder("tg_ptap_kron_append:", rp, t.off, nullptr, t.tcol, t.tval, nrows, dest->m->col, dest->m->val));
+  dest->rows_done += nrows;
+  dest->nnz_done += nnz;
+  return 0;
+}
+
+// Ending as a CSR matrix of its own
+static int tg_kron_end_csr(tg_kron_plan &K, tg_bump &t, tg_csr_s **out) {
+  return t.finish_csr("tg_ptap_kron:", K.nout_total, out, nullptr, nullptr);
+}
+
+// an empty row range: the empty matrix
+static int tg_kron_empty(tg_kron_plan &K, tg_csr_s **out) {
+  TG_TRY(tg_csr_alloc(0, K.nout_total, 0, out));
+  hipMemsetAsync((*out)->rowptr, 0, sizeof(int64_t), g_tg.stream);
+  return 0;
+}
+
+// capacity, run and ending of a stage with rows (*out is set as soon as the matrix exists: the caller destroys it on error)
+static int tg_kron_product(tg_kron_plan &K, tg_bump &t, tg_csr_s **out) {
+  const tg_kron_request &rq = K.rq;
+  if (rq.nzero > 0) TG_TRY(tg_build_dof_mask(rq.zero_dofs, rq.nzero, K.nout_total, &K.B.mask.p));
+  TG_TRY(t.init(K.P.out_nrows, true, 1, 3));
+  TG_TRY(tg_kron_capacity(K, t));
+  TG_TRY(tg_kron_run(K, t));
+  if (rq.ending == TG_KRON_END_LOOSE) return tg_kron_end_loose(K, t, out);
+  if (rq.ending == TG_KRON_END_APPEND) return tg_kron_end_append(K, t);
+  return tg_kron_end_csr(K, t, out);
+}
+
+// returns 0 ok, TG_KRON_DECLINED = "use the general kernel" (box too large / not applicable), TG_KRON_OUTSIDE = an entry
+// fell outside a box sized from SAMPLED reach data (retry with the exact reach), TG_KRON_COMPACT = a stacked view that
+// the kernel chosen cannot read, other = error
+static int tg_ptap_kron_impl(const tg_kron_switches &S, const tg_kron_request &rq, int64_t reach_stride) {
+  tg_kron_plan K;
+  K.S = S;
+  K.rq = rq;
+  K.reach_stride = reach_stride;
+  TG_TRY(tg_kron_operands(K));
+  TG_TRY(tg_kron_boxes(K));
+  TG_TRY(tg_kron_lds_layout(K));
+  TG_TRY(tg_kron_choose(K));
+  tg_bump t(K.line_variant ? "line stage" : "box stage");
+  tg_csr_s *k = nullptr;
+  const int rc = K.P.out_nrows == 0 ? tg_kron_empty(K, &k) : tg_kron_product(K, t, &k);
   hipStreamSynchronize(g_tg.stream);
   if (rc) {
     if (k) tg_csr_destroy(k);
     return rc;
   }
-  if (out)
-    *out = k;
+  if (rq.out)
+    *rq.out = k;
   else if (k)
     tg_csr_destroy(k);
   return 0;
 }
 
-static int tg_ptap_kron_any(tg_csr_t cur, int64_t cur_row0, int d, const int64_t *dims_in, const tg_kron1d_t *fac,
-                            int64_t out_row0, int64_t out_row1, const int32_t *zero_dofs, int64_t nzero, double diag,
-                            bool loose_out, tg_csr_builder_s *dest, tg_csr_t *out) {
-  TG_REQUIRE(cur && dims_in, "bad arguments to tg_ptap_kron");
+// The ladder of attempts: the sampled reach; a compacted copy when a stacked view meets a kernel that cannot read it;
+// the exact reach when an entry fell outside a box sized from the sample; else the caller takes the general kernels.
+static int tg_ptap_kron_any(tg_kron_request rq) {
+  TG_REQUIRE(rq.cur && rq.dims_in, "bad arguments to tg_ptap_kron");
+  const tg_kron_switches S = tg_kron_switches_read();
+  if (rq.ending == TG_KRON_END_LOOSE && S.noloose) rq.ending = TG_KRON_END_CSR;
   // The accumulator boxes are sized from the reach of cur's rows.  Scanning every entry of cur costs
   // a noticeable fraction of the product, so the reach is first measured on every `stride`-th row
   // (stride coprime to the fastest dimension: every coordinate of every direction is still visited);
   // the kernel flags any entry that falls outside a box, in which case the exact reach is used.
   int64_t stride = 1;
-  if (cur->nrows > (1 << 20) && !getenv("TIGAR_BOX_EXACT_REACH")) {
+  if (rq.cur->nrows > (1 << 20) && !S.exact_reach) {
     const int64_t cand[5] = {29, 31, 37, 41, 43};
     for (int c = 0; c < 5; c++)
-      if (dims_in[0] % cand[c] != 0) {
+      if (rq.dims_in[0] % cand[c] != 0) {
         stride = cand[c];
         break;
       }
   }
-  if (getenv("TIGAR_BOX_REACH_STRIDE")) stride = std::max(1, atoi(getenv("TIGAR_BOX_REACH_STRIDE")));
-  int rc = tg_ptap_kron_impl(cur, cur_row0, d, dims_in, fac, out_row0, out_row1, zero_dofs, nzero, diag, stride, loose_out, dest, out);
-  if (rc == 102) {   // stacked view into a kernel that cannot read it: compact once, then as usual
-    tg_csr_s *flat = nullptr;
-    TG_TRY(tg_csr_compact_impl(cur, &flat));
-    rc = tg_ptap_kron_any(flat, cur_row0, d, dims_in, fac, out_row0, out_row1, zero_dofs, nzero, diag, loose_out, dest, out);
-    tg_csr_destroy(flat);
-    return rc;
+  if (S.reach_stride) stride = S.reach_stride;
+  tg_csr_s *flat = nullptr;          // compacted copy of a stacked view, destroyed on every path
+  int rc;
+  for (;;) {
+    rc = tg_ptap_kron_impl(S, rq, stride);
+    if (rc == TG_KRON_COMPACT && !flat) {           // compact once, then as usual
+      rc = tg_csr_compact_impl(rq.cur, &flat);
+      if (rc) break;
+      rq.cur = flat;
+    } else if (rc == TG_KRON_OUTSIDE && stride > 1) {
+      stride = 1;
+    } else {
+      break;
+    }
   }
-  if (rc == 101 && stride > 1)
-    rc = tg_ptap_kron_impl(cur, cur_row0, d, dims_in, fac, out_row0, out_row1, zero_dofs, nzero, diag, 1, loose_out, dest, out);
-  if (rc == 101) {
+  if (rc == TG_KRON_OUTSIDE) {
     // also with the exact reach: the support of an output row is not one interval per direction (periodic wrap) --
-    // not a product for the box kernels; the caller takes the general ones (100 = declined, nothing was written)
+    // not a product for the box kernels; the caller takes the general ones (declined, nothing was written)
     tg_set_error("tg_ptap_kron: an entry fell outside its accumulator box");
-    rc = 100;
+    rc = TG_KRON_DECLINED;
   }
+  if (flat) tg_csr_destroy(flat);
   return rc;
 }
 
 extern "C" int tg_ptap_kron(tg_csr_t cur, int64_t cur_row0, int d, const int64_t *dims_in, const tg_kron1d_t *fac,
                             int64_t out_row0, int64_t out_row1, const int32_t *zero_dofs, int64_t nzero, double diag,
                             tg_csr_t *out) {
-  return tg_ptap_kron_any(cur, cur_row0, d, dims_in, fac, out_row0, out_row1, zero_dofs, nzero, diag, false, nullptr, out);
+  return tg_ptap_kron_any({cur, cur_row0, d, dims_in, fac, out_row0, out_row1, zero_dofs, nzero, diag, TG_KRON_END_CSR, nullptr, out});
 }
 
 // intermediate stage of a direction-by-direction product: no boundary conditions, result in the
 // loose-row form (consumed by the next tg_ptap_kron* call, tg_csr_vstack or tg_csr_compact)
 extern "C" int tg_ptap_kron_stage(tg_csr_t cur, int64_t cur_row0, int d, const int64_t *dims_in, const tg_kron1d_t *fac,
                                   int64_t out_row0, int64_t out_row1, tg_csr_t *out) {
-  return tg_ptap_kron_any(cur, cur_row0, d, dims_in, fac, out_row0, out_row1, nullptr, 0, 1.0,
-                          !getenv("TIGAR_PTAP_NOLOOSE"), nullptr, out);
+  return tg_ptap_kron_any({cur, cur_row0, d, dims_in, fac, out_row0, out_row1, nullptr, 0, 1.0, TG_KRON_END_LOOSE, nullptr, out});
 }
 
 // last stage of a slab with the result appended to a slab-wise builder of K (the rows must be the next
@@ -1752,5 +1898,5 @@ extern "C" int tg_ptap_kron_append(tg_csr_t cur, int64_t cur_row0, int d, const 
                                    int64_t out_row0, int64_t out_row1, const int32_t *zero_dofs, int64_t nzero, double diag,
                                    tg_csr_builder_t dest) {
   TG_REQUIRE(dest && dest->m, "null builder");
-  return tg_ptap_kron_any(cur, cur_row0, d, dims_in, fac, out_row0, out_row1, zero_dofs, nzero, diag, false, dest, nullptr);
+  return tg_ptap_kron_any({cur, cur_row0, d, dims_in, fac, out_row0, out_row1, zero_dofs, nzero, diag, TG_KRON_END_APPEND, dest, nullptr});
 }

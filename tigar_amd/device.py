@@ -681,6 +681,9 @@ def _ptap_numeric_plain(plan, A, M, MT, zero_dofs=None, diag=1.0):
     return DeviceCSR(h)
 
 
+DECLINED = 100      # return code of an entry point that declines (nothing was written): the caller takes the general kernels
+
+
 class FoldPlan(object):
     """K = R^T K_u R on stored places (``tg_foldplan_*``): ``create`` from a first product made with the general kernels,
     ``apply`` for every later K_u with the same pattern (None: another pattern -- use the general kernels)"""
@@ -692,7 +695,7 @@ class FoldPlan(object):
     def create(K_u, R, RT, ku_row0, rt_row0, K):
         h = handle()
         rc = _lib.lib().tg_foldplan_create(K_u._h, int(ku_row0), R._h, RT._h, int(rt_row0), K._h, C.byref(h))
-        if rc == 100:
+        if rc == DECLINED:
             return None
         check(rc, "tg_foldplan_create")
         return FoldPlan(h, (R, RT))
@@ -702,7 +705,7 @@ class FoldPlan(object):
         out = handle()
         rc = _lib.lib().tg_foldplan_apply(self._h, K_u._h, _p(zd, c_i32p) if zd is not None else None,
                                           zd.size if zd is not None else 0, float(diag), C.byref(out))
-        if rc == 100:
+        if rc == DECLINED:
             return None
         check(rc, "tg_foldplan_apply")
         return DeviceCSR(out)
@@ -751,7 +754,7 @@ def ptap_kron(cur, cur_row0, dims_in, factors, out_row0, out_row1, zero_dofs=Non
         rc = _lib.lib().tg_ptap_kron_append(cur._h, int(cur_row0), d, _p(dims, c_i64p), arr, int(out_row0), int(out_row1),
                                             _p(zd, c_i32p) if zd is not None else None, zd.size if zd is not None else 0,
                                             float(diag), append_to._h)
-        if rc == 100:
+        if rc == DECLINED:
             return None
         check(rc, "tg_ptap_kron_append")
         return True
@@ -764,7 +767,7 @@ def ptap_kron(cur, cur_row0, dims_in, factors, out_row0, out_row1, zero_dofs=Non
         rc = _lib.lib().tg_ptap_kron(cur._h, int(cur_row0), d, _p(dims, c_i64p), arr, int(out_row0), int(out_row1),
                                      _p(zd, c_i32p) if zd is not None else None, zd.size if zd is not None else 0,
                                      float(diag), C.byref(h))
-    if rc == 100:
+    if rc == DECLINED:
         return None
     check(rc, "tg_ptap_kron")
     return DeviceCSR(h)
