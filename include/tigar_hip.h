@@ -692,6 +692,35 @@ int tg_assemble_coef_matrix(const tg_patch_t *patch, tg_vec_t coef, tg_csr_t *ou
  * i.e. (d^4 + 16 d^2) npts = 225 npts doubles at d = 3 (52 npts at d = 2). */
 int tg_coef_transform_blocks(const tg_patch_t *patch, int rational, int nF, tg_vec_t A_q, tg_vec_t M_q, tg_vec_t coef_out);
 int tg_assemble_coef_blocks(const tg_patch_t *patch, int nF, tg_vec_t coef_blocks, tg_csr_t *out);
+/* ---- first-order systems: nF >= 1 fields (at most 16) on the scalar Q_p space, dofs field after field, d = 1, 2, 3, nsd >= d,
+ * nF independent of nsd:
+ *   a(u, v) = sum_ij int d_K v_i A_iKjL d_L u_j + d_K v_i b_iKj u_j + v_i c_ijL d_L u_j + v_i m_ij u_j dx
+ * tg_coef_transform_system: block (i, j) = test field i, trial field j, each with its own data -- A_q holds A_iKjL at
+ * (((i nF + j) nsd + K) nsd + L) npts + q, b_q holds b_iKj at ((i nF + j) nsd + K) npts + q, c_q holds c_ijL at
+ * ((i nF + j) nsd + L) npts + q, M_q holds m_ij at (i nF + j) npts + q; any of the four may be null: zero.  coef_out: the layout
+ * of tg_coef_transform_blocks (nF^2 sets of (d^2 + 2 d + 1) npts values).  The same ending of k_postproc with the same
+ * per-block body: with b_q and c_q null the bits of tg_coef_transform_blocks, with nF = 1 those of tg_coef_transform(a_kind =
+ * 2) (a_kind = 0 where A_q is null).
+ * tg_assemble_coef_system: tg_assemble_coef_blocks for such a set of blocks, any nF (nF = 1: the block itself).
+ * tg_quad_metric: the element metric G = 4 P P^T, P = DF g^-1 -- d xi / d x of the BI-UNIT parent element contracted over
+ * the parametric index, the G of the stabilisation parameters of tg_flow_points; nsd^2 npts values, symmetric, all
+ * components stored, G_KL at (K nsd + L) npts + q; nsd >= d (rank d). */
+int tg_coef_transform_system(const tg_patch_t *patch, int rational, int nF, tg_vec_t A_q, tg_vec_t b_q, tg_vec_t c_q, tg_vec_t M_q,
+                             tg_vec_t coef_out);
+int tg_assemble_coef_system(const tg_patch_t *patch, int nF, tg_vec_t coef_blocks, tg_csr_t *out);
+int tg_quad_metric(const tg_patch_t *patch, tg_vec_t G_out);
+/* ---- the incompressible Navier-Stokes law at the points (csrc/tg_flow.hip): nsd = 2, 3, nF = nsd + 1 fields (u, p), Galerkin +
+ * SUPG + PSPG + LSIC.  params = {rho, mu, c_a, 4 / dt^2, C_I} (host), nu = mu / rho; a = c_a u + a0.
+ *   r_i = rho (a_i + u_L d_L u_i - f_i) + d_i p (the viscous part is left out), tau_M = (4 / dt^2 + u . G u + C_I nu^2 G:G)^(-1/2),
+ *   tau_C = 1 / (tau_M tr G);  s_i = r_i - d_i p,  F_iK = mu (d_K u_i + d_i u_K) - p d_iK + tau_M u_K r_i + rho tau_C div u d_iK,
+ *   s_p = div u,  F_pK = (tau_M / rho) r_K.
+ * U_q: field i at i npts + q; gradU_q: d U_i / d x_K at (i nsd + K) npts + q; a0_q, f_q (may be null: zero): nsd npts values;
+ * G_q: tg_quad_metric.  s_out (nF npts) and F_out (nF nsd npts) in the layout of tg_quad_load_flux per field; A_out, b_out,
+ * c_out, M_out: the exact derivative of (s, F), tau included, in the layouts of tg_coef_transform_system, dense (zeros
+ * written); tau_out: tau_M (npts), then tau_C (npts).  Any output may be null; every subset gives the same bits.  No atomics. */
+int tg_flow_points(const double *params, int nsd, int64_t npts, tg_vec_t U_q, tg_vec_t gradU_q, tg_vec_t a0_q, tg_vec_t f_q,
+                   tg_vec_t G_q, tg_vec_t s_out, tg_vec_t F_out, tg_vec_t A_out, tg_vec_t b_out, tg_vec_t c_out, tg_vec_t M_out,
+                   tg_vec_t tau_out);
 /* ---- material laws at the points (csrc/tg_material.hip): F = I + grad u, J = det F, C = F^T F, nsd = 2 (plane strain) or 3.
  * gradu: d u_i / d x_K at (i nsd + K) npts + q; P_out: the first Piola-Kirchhoff stress in the same layout; A_out:
  * A_iKjL = d P_iK / d F_jL in the layout of tg_coef_transform_blocks; psi_out: the energy density; any output may be null.

@@ -2150,6 +2150,10 @@ class ExtractedSpline(object):
         d = 1 or 2 parametric directions and nsd >= d"""
         self._point_scope(who, shared_dims=(1, 2))
 
+    def _system_quadrature_scope(self, who):
+        """the point forms of a first-order system: nF >= 1 fields on the control basis sharing one node grid, d = 1, 2, 3"""
+        self._point_scope(who, shared_dims=(1, 2, 3))
+
     def evaluateJetsAtQuadrature(self, u, nq=None, rational=False):
         """The JET of u_h (``rational``: of u_h / W_h) at the quadrature points: value, first parametric derivatives, second
         parametric derivatives in the order 00, 01, 11 -- ``spline.parametricGrad`` of the reference and its derivative, with

@@ -6,6 +6,7 @@
 
 #define TG_ASM_MAXLOC 128      // (p+1)^d local nodes: p <= 4 in 3-D, p <= 8 in 2-D (<= 81), any p <= 8 in 1-D
 #define TG_ASM_MAXQ1 10        // Gauss points per direction
+#define TG_SYSTEM_MAX_FIELDS 16   // fields of a first-order system (tg_coef_transform_system; tg_csr_from_blocks takes 16)
 
 __device__ __forceinline__ void tg_sym_inverse(int d, const double *g, double *gi, double *det) {
   if (d == 1) {

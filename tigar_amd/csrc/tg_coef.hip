@@ -195,14 +195,9 @@ extern "C" int tg_assemble_coef_matrix(const tg_patch_t *pt, tg_vec_t coef, tg_c
 // Every block goes through the driver above on a VIEW of its slice (no copy of the point data; the routes, TIGAR_ASM_LEGACY,
 // TIGAR_ASM_CHUNK and TIGAR_ASM_QUAD_CHUNK as for one scalar form), a block row at a time, and the nF n square matrix is
 // put together by tg_csr_from_blocks -- as the matrix of the mapped elasticity form is.
-extern "C" int tg_assemble_coef_blocks(const tg_patch_t *pt, int nF, tg_vec_t coef_blocks, tg_csr_t *out) {
-  TG_REQUIRE_INIT();
-  TG_REQUIRE(pt && out && (pt->d == 2 || pt->d == 3) && nF == pt->d && pt->nsd == pt->d,
-             "tg_assemble_coef_blocks: as many fields as physical and parametric directions, 2 or 3");
-  TG_REQUIRE(coef_blocks && coef_blocks->n > 0 && coef_blocks->n % ((int64_t)nF * nF) == 0,
-             "tg_assemble_coef_blocks: nF^2 = %d coefficient sets of equal length (tg_coef_transform_blocks)", nF * nF);
+static int tg_coef_blocks_assemble(const tg_patch_t *pt, int nF, tg_vec_t coef_blocks, tg_csr_t *out) {
   const int64_t each = coef_blocks->n / ((int64_t)nF * nF);
-  tg_csr_t blocks[9] = {nullptr};
+  tg_csr_t blocks[TG_SYSTEM_MAX_FIELDS * TG_SYSTEM_MAX_FIELDS] = {nullptr};
   int rc = 0;
   for (int b = 0; b < nF * nF && !rc; b++) {
     tg_vec_s view;                     // (tg_assemble_coef_matrix checks its length against the patch)
@@ -210,8 +205,31 @@ extern "C" int tg_assemble_coef_blocks(const tg_patch_t *pt, int nF, tg_vec_t co
     view.d = coef_blocks->d + (int64_t)b * each;
     rc = tg_assemble_coef_matrix(pt, &view, &blocks[b]);
   }
+  if (!rc && nF == 1) {                // (one field: the block itself)
+    *out = blocks[0];
+    return 0;
+  }
   if (!rc) rc = tg_csr_from_blocks(nF, blocks, out);
   for (int b = 0; b < nF * nF; b++)
     if (blocks[b]) tg_csr_destroy(blocks[b]);
   return rc;
+}
+
+extern "C" int tg_assemble_coef_blocks(const tg_patch_t *pt, int nF, tg_vec_t coef_blocks, tg_csr_t *out) {
+  TG_REQUIRE_INIT();
+  TG_REQUIRE(pt && out && (pt->d == 2 || pt->d == 3) && nF == pt->d && pt->nsd == pt->d,
+             "tg_assemble_coef_blocks: as many fields as physical and parametric directions, 2 or 3");
+  TG_REQUIRE(coef_blocks && coef_blocks->n > 0 && coef_blocks->n % ((int64_t)nF * nF) == 0,
+             "tg_assemble_coef_blocks: nF^2 = %d coefficient sets of equal length (tg_coef_transform_blocks)", nF * nF);
+  return tg_coef_blocks_assemble(pt, nF, coef_blocks, out);
+}
+
+// ... of a first-order system (tg_coef_transform_system): any 1 <= nF <= TG_SYSTEM_MAX_FIELDS fields, d = 1, 2, 3, nsd >= d
+extern "C" int tg_assemble_coef_system(const tg_patch_t *pt, int nF, tg_vec_t coef_blocks, tg_csr_t *out) {
+  TG_REQUIRE_INIT();
+  TG_REQUIRE(pt && out && nF >= 1 && nF <= TG_SYSTEM_MAX_FIELDS, "tg_assemble_coef_system: a patch, an output and 1..%d fields",
+             TG_SYSTEM_MAX_FIELDS);
+  TG_REQUIRE(coef_blocks && coef_blocks->n > 0 && coef_blocks->n % ((int64_t)nF * nF) == 0,
+             "tg_assemble_coef_system: nF^2 = %d coefficient sets of equal length (tg_coef_transform_system)", nF * nF);
+  return tg_coef_blocks_assemble(pt, nF, coef_blocks, out);
 }

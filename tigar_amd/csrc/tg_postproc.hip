@@ -12,6 +12,8 @@
 //   tg_quad_error    sum wdet (u_h - e)^2,  sum wdet |grad u_h - ge|^2,  sum wdet e^2
 //   tg_coef_transform / tg_flux_transform   Cartesian point coefficients -> the reference element (formulas: tg_coef.hip)
 //   tg_coef_transform_blocks   the same for the nF^2 blocks of a vector-valued unknown's tangent, the geometry formed once
+//   tg_coef_transform_system   ... for the nF^2 blocks of a first-order system: every block with its own A, b, c and m
+//   tg_quad_metric   G = 4 P P^T, P = DF g^-1: the element metric of the bi-unit parent element (stabilisation parameters)
 //   tg_quad_load_flux   out[node] = sum_q wdet_q (s_q phi_node + F_q . grad phi_node)(xi_q)
 //
 // One kernel, four endings (and the three that take point coefficients).  A workgroup of 256 threads takes max(1, 256 / nq^d) elements (fewer where
@@ -57,7 +59,8 @@ struct tg_pp_args {
   const double *Aq, *bq, *cq, *mq;   // a(u, v) = int grad v . (A grad u) + (b . grad v) u + v (c . grad u) + m u v
   const double *sq, *Fq;       // L(v) = int s v + F . grad v
   double *cout;                // the data on the reference element, component-major
-  int nblk;                    // TG_PP_BLOCKS: Aq, mq and cout hold this many consecutive sets (a tensor per point each)
+  int nblk;                    // TG_PP_BLOCKS: Aq, bq, cq, mq and cout hold this many consecutive sets (a tensor, two vectors
+                               // and a value per point each; any of the four may be null)
 };
 
 // element number e of the launch -> element indices; returns the lexicographic index in the patch
@@ -81,17 +84,21 @@ __device__ __forceinline__ int64_t tg_pp_node(const tg_pp_args &P, const int *el
 // of the matrix form in the place of the points, 0 + TG_PP_FLUX the d + 1 of the load; 2 + TG_PP_FLUX is the load of
 // s v + F . grad v.  All three take TG_PP_RAT: beta is folded into the data.  TG_PP_COEF + TG_PP_BLOCKS: the coefficient ending
 // looped over nblk sets of (tensor, reaction) -- the nF^2 blocks of a vector-valued unknown's tangent (tg_material.hip) --
-// with the point's geometry (P = DF g^-1, wdet, W, beta) computed once.
+// with the point's geometry (P = DF g^-1, wdet, W, beta) computed once.  0 + TG_PP_METRIC writes G = 4 P P^T (nsd x nsd) in
+// the place of the points.
 #define TG_PP_RAT 4
 #define TG_PP_COEF 8
 #define TG_PP_FLUX 16
 #define TG_PP_BLOCKS 32
+#define TG_PP_METRIC 64
 template <int MODER>
 __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
   constexpr int MODE = MODER & 3;
   constexpr bool RAT = (MODER & TG_PP_RAT) != 0;
   constexpr bool COEF = (MODER & TG_PP_COEF) != 0, FLUX = (MODER & TG_PP_FLUX) != 0, BLK = (MODER & TG_PP_BLOCKS) != 0;
+  constexpr bool METRIC = (MODER & TG_PP_METRIC) != 0;
   static_assert(!BLK || COEF, "the blocks are sets of point coefficients");
+  static_assert(!METRIC || MODER == TG_PP_METRIC, "the metric is a property of the points");
   static_assert(!(RAT && MODE == 0 && !COEF && !FLUX), "the points do not depend on the function space");
   static_assert(!(COEF && (MODE != 0 || FLUX)) && !(FLUX && MODE != 0 && MODE != 2), "endings that take point coefficients");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -234,10 +241,12 @@ __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
       if constexpr (COEF) {
         const int nblk = BLK ? P.nblk : 1;
         for (int blk = 0; blk < nblk; blk++) {
-          const double *Aq = P.Aq, *mq = P.mq;
+          const double *Aq = P.Aq, *bq = P.bq, *cq = P.cq, *mq = P.mq;
           double *co = P.cout;
-          if constexpr (BLK) {           // set blk: an nsd x nsd tensor and (optionally) a reaction value per point
-            Aq += (int64_t)blk * nsd * nsd * P.npts;
+          if constexpr (BLK) {           // set blk: an nsd x nsd tensor, two nsd-vectors and a reaction value per point, each optional
+            if (Aq) Aq += (int64_t)blk * nsd * nsd * P.npts;
+            if (bq) bq += (int64_t)blk * nsd * P.npts;
+            if (cq) cq += (int64_t)blk * nsd * P.npts;
             if (mq) mq += (int64_t)blk * P.npts;
             co += (int64_t)blk * (d * d + 2 * d + 1) * P.npts;
           }
@@ -267,8 +276,8 @@ __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
 #pragma unroll
           for (int c = 0; c < 3; c++) {
             if (c >= nsd) continue;
-            const double bc = P.bq ? wdet * P.bq[(int64_t)c * P.npts + gp] : 0.0;
-            const double cc = P.cq ? wdet * P.cq[(int64_t)c * P.npts + gp] : 0.0;
+            const double bc = bq ? wdet * bq[(int64_t)c * P.npts + gp] : 0.0;
+            const double cc = cq ? wdet * cq[(int64_t)c * P.npts + gp] : 0.0;
 #pragma unroll
             for (int k = 0; k < 3; k++) {
               bh[k] = fma(Pm[c][k], bc, bh[k]);
@@ -345,6 +354,19 @@ __global__ void __launch_bounds__(256) k_postproc(tg_pp_args P) {
             if (k < d) T[(1 + k) * nqt + q] = Fh[k];
         }
       }
+    } else if constexpr (METRIC) {
+      // d xi' / d x of the bi-unit parent element xi' = 2 xi - 1 is 2 P^T: G_KL = 4 sum_k P_Kk P_Lk, symmetric, all nsd^2 stored
+      double Pm[3][3];
+#pragma unroll
+      for (int c = 0; c < 3; c++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) Pm[c][k] = DF[c][0] * gi[0][k] + DF[c][1] * gi[1][k] + DF[c][2] * gi[2][k];
+#pragma unroll
+      for (int K = 0; K < 3; K++)
+#pragma unroll
+        for (int L = 0; L < 3; L++)
+          if (K < nsd && L < nsd)
+            P.cout[(int64_t)(K * nsd + L) * P.npts + gp] = 4.0 * (Pm[K][0] * Pm[L][0] + Pm[K][1] * Pm[L][1] + Pm[K][2] * Pm[L][2]);
     } else if (MODE == 0) {
 #pragma unroll
       for (int c = 0; c < 3; c++)
@@ -620,6 +642,41 @@ extern "C" int tg_coef_transform_blocks(const tg_patch_t *patch, int rational, i
   TG_TRY(tg_pp_point_array("tg_coef_transform_blocks", "M_q", M_q, nb, A.npts, &A.mq));
   A.cout = coef_out->d;
   return tg_pp_launch_rat<TG_PP_COEF | TG_PP_BLOCKS>(rational != 0, A, lds);
+}
+
+// a first-order system of nF fields on the scalar space (nF independent of nsd and d): block (i, j) with its own tensor, its
+// vectors b_ij (pairs with grad v_i and u_j) and c_ij (pairs with v_i and grad u_j) and its reaction; any of the four null.
+// The per-block body is the scalar ending's, so one field gives the bits of tg_coef_transform(a_kind = 2)
+extern "C" int tg_coef_transform_system(const tg_patch_t *patch, int rational, int nF, tg_vec_t A_q, tg_vec_t b_q, tg_vec_t c_q,
+                                        tg_vec_t M_q, tg_vec_t coef_out) {
+  tg_pp_args A;
+  size_t lds;
+  TG_TRY(tg_pp_setup("tg_coef_transform_system", patch, 0, nullptr, &A, &lds));
+  const int d = A.d, nsd = A.nsd;
+  TG_REQUIRE(nF >= 1 && nF <= TG_SYSTEM_MAX_FIELDS, "tg_coef_transform_system: nF = %d; 1..%d fields", nF, TG_SYSTEM_MAX_FIELDS);
+  const int64_t nb = (int64_t)nF * nF;
+  TG_REQUIRE(coef_out && coef_out->n == nb * (d * d + 2 * d + 1) * A.npts,
+             "tg_coef_transform_system: an output of nF^2 (d^2 + 2 d + 1) npts = %lld values",
+             (long long)(nb * (d * d + 2 * d + 1) * A.npts));
+  A.akind = A_q ? 2 : 0;
+  A.nblk = (int)nb;
+  TG_TRY(tg_pp_point_array("tg_coef_transform_system", "A_q", A_q, nb * nsd * nsd, A.npts, &A.Aq));
+  TG_TRY(tg_pp_point_array("tg_coef_transform_system", "b_q", b_q, nb * nsd, A.npts, &A.bq));
+  TG_TRY(tg_pp_point_array("tg_coef_transform_system", "c_q", c_q, nb * nsd, A.npts, &A.cq));
+  TG_TRY(tg_pp_point_array("tg_coef_transform_system", "M_q", M_q, nb, A.npts, &A.mq));
+  A.cout = coef_out->d;
+  return tg_pp_launch_rat<TG_PP_COEF | TG_PP_BLOCKS>(rational != 0, A, lds);
+}
+
+// G = 4 P P^T at the points: nsd^2 npts values, component (K, L) at (K nsd + L) npts + q
+extern "C" int tg_quad_metric(const tg_patch_t *patch, tg_vec_t G_out) {
+  tg_pp_args A;
+  size_t lds;
+  TG_TRY(tg_pp_setup("tg_quad_metric", patch, 0, nullptr, &A, &lds));
+  TG_REQUIRE(G_out && G_out->n == (int64_t)A.nsd * A.nsd * A.npts, "tg_quad_metric: an output of nsd^2 npts = %lld values",
+             (long long)((int64_t)A.nsd * A.nsd * A.npts));
+  A.cout = G_out->d;
+  return tg_pp_launch<TG_PP_METRIC>(A, lds);
 }
 
 extern "C" int tg_flux_transform(const tg_patch_t *patch, int rational, tg_vec_t s_q, tg_vec_t F_q, tg_vec_t out) {

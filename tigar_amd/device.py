@@ -1287,6 +1287,56 @@ def coef_block(vertices, coef_blocks, i, j, nq):
     return out
 
 
+def coef_transform_system(vertices, p, cp, nF, A=None, b=None, c=None, M=None, nq=None, rational=False):
+    """The point data of a first-order system of ``nF`` fields brought to the reference element in one pass
+    (``tg_coef_transform_system``): ``A`` holds A_iKjL at (((i nF + j) nsd + K) nsd + L) npts + q, ``b`` b_iKj at
+    ((i nF + j) nsd + K) npts + q, ``c`` c_ijL at ((i nF + j) nsd + L) npts + q, ``M`` m_ij at (i nF + j) npts + q; None = zero.
+    Returns nF^2 consecutive coefficient sets in the layout of ``coef_transform``, which ``assemble_coef_system`` takes."""
+    d, npts, nF = len(vertices), quad_count(vertices, _nq(p, nq)), int(nF)
+    out = DeviceVector(max(nF, 0) ** 2 * (d * d + 2 * d + 1) * npts, zero=False)
+    _point_call("tg_coef_transform_system", vertices, p, cp, nq, 1 if rational else 0, nF, A, b, c, M, out)
+    return out
+
+
+def assemble_coef_system(vertices, p, cp, nF, coef_blocks, nq=None):
+    """the nF n x nF n matrix (field-major) of the transformed blocks of a system (``tg_assemble_coef_system``)"""
+    h = handle()
+    _point_call("tg_assemble_coef_system", vertices, p, cp, nq, int(nF), coef_blocks, C.byref(h))
+    return DeviceCSR(h)
+
+
+def quad_metric(vertices, p, cp, nq=None):
+    """The element metric G = 4 P P^T, P = DF g^-1, at the Gauss points (``tg_quad_metric``): nsd^2 * npts values, G_KL at
+    (K nsd + L) npts + q -- d xi / d x of the bi-unit parent element contracted over the parametric index."""
+    nsd = len(cp) - 1
+    out = DeviceVector(nsd * nsd * quad_count(vertices, _nq(p, nq)), zero=False)
+    _point_call("tg_quad_metric", vertices, p, cp, nq, out)
+    return out
+
+
+def flow_points(params, nsd, U, gradU, G, a0=None, f=None, load=True, tangent=False, tau=False, want=None):
+    """The stabilised incompressible Navier-Stokes law at the points (``tg_flow_points``): ``params`` = (rho, mu, c_a,
+    4 / dt^2, C_I); ``U`` (nsd + 1 fields, the pressure last) and ``gradU`` at the points, ``G`` the metric of
+    ``quad_metric``, ``a0`` / ``f`` nsd * npts values or None.  Returns (s, F, A, b, c, M, tau) with what was not asked for
+    None: ``load`` gives s and F, ``tangent`` A, b, c, M (the layouts of ``coef_transform_system``), ``tau`` tau_M | tau_C;
+    ``want``: seven booleans, one per output, in the place of the three."""
+    nsd = int(nsd)
+    nF = nsd + 1
+    npts = U.size() // nF
+    par = _f64([float(v) for v in params])
+    if par.size != 5:
+        raise ValueError("flow_points: params = (rho, mu, c_a, 4 / dt^2, C_I), %d values given" % par.size)
+    if want is None:
+        want = (load, load, tangent, tangent, tangent, tangent, tau)
+    if len(want) != 7:
+        raise ValueError("flow_points: want = one boolean for each of (s, F, A, b, c, M, tau)")
+    sizes = (nF, nF * nsd, nF * nF * nsd * nsd, nF * nF * nsd, nF * nF * nsd, nF * nF, 2)
+    s, F, A, b, c, M, t = [DeviceVector(each * npts, zero=False) if on else None for each, on in zip(sizes, want)]
+    check(_lib.lib().tg_flow_points(_p(par, c_f64p), nsd, npts, U._h, gradU._h, _h_or_none(a0), _h_or_none(f), G._h,
+                                    *[_h_or_none(v) for v in (s, F, A, b, c, M, t)]), "tg_flow_points")
+    return s, F, A, b, c, M, t
+
+
 def jet_size(d):
     """nJ: components of a jet (value | first | second parametric derivatives 00, 01, 11) on a patch of d = 1, 2 directions"""
     if d not in (1, 2):

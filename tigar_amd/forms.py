@@ -517,13 +517,22 @@ class QuadraturePoints(object):
         self.verts, self.p, self.cp, self.nq, self.nsd = verts, p, cp, nq, len(cp) - 1
         self.x_device, self.weights = _dev.quad_points(verts, p, cp, nq)
         self.npts = self.weights.size()
-        self._x = None
+        self._x = self._metric = None
 
     @property
     def x(self):
         if self._x is None:
             self._x = point_unblock(self.x_device.get_local(), self.npts, (self.nsd,))
         return self._x
+
+    @property
+    def metric(self):
+        """the element metric G = 4 P P^T, P = DF g^-1, as a DeviceVector of nsd^2 npts values, G_KL at (K nsd + L) npts + q
+        (``tg_quad_metric``): d xi / d x of the bi-unit parent element contracted over the parametric index; computed on
+        first use and kept like ``weights``"""
+        if self._metric is None:
+            self._metric = _dev.quad_metric(self.verts, self.p, self.cp, self.nq)
+        return self._metric
 
     def values(self, f, who="f"):
         """point values of ``f`` as a DeviceVector: a callable on ``x`` [npts, nsd] -> [npts], a number, the values
@@ -726,7 +735,8 @@ class _SemilinearTangent(object):
 
 
 # ---- volume forms with point coefficients (csrc/tg_coef.hip) ---------------------------------------------------------------
-_SCOPE_OF_KIND = {"scalar": "_quadrature_scope", "vector": "_vector_quadrature_scope", "jet": "_jet_scope"}
+_SCOPE_OF_KIND = {"scalar": "_quadrature_scope", "vector": "_vector_quadrature_scope", "jet": "_jet_scope",
+                  "system": "_system_quadrature_scope"}
 
 
 def _point_scope(geometry, V, who, kind):
@@ -736,7 +746,9 @@ def _point_scope(geometry, V, who, kind):
       "scalar": one scalar field; returns None.
       "vector": a displacement, nF = nsd = d fields (d = 2 plane strain, or 3) on one continuous Q_p node grid, dofs field
                 after field (``EqualOrderSpline(d, mesh)``); returns (node grid, nF).
-      "jet":    nF >= 1 fields on one such grid of a patch with d = 1, 2 and nsd >= d; returns (node grid, nF, nJ)."""
+      "jet":    nF >= 1 fields on one such grid of a patch with d = 1, 2 and nsd >= d; returns (node grid, nF, nJ).
+      "system": nF >= 1 fields on one such grid of a patch with d = 1, 2, 3 and nsd >= d, nF independent of nsd
+                (``EqualOrderSpline(nF, mesh)``); returns (node grid, nF)."""
     if geometry is None:
         raise ValueError("%s: point data live on a mapped patch (geometry=...)" % who)
     scope = getattr(geometry, _SCOPE_OF_KIND[kind], None)
@@ -754,6 +766,10 @@ def _point_scope(geometry, V, who, kind):
         if nsd < d:
             raise NotImplementedError("%s: nsd = %d physical directions on a patch of d = %d parametric ones" % (who, nsd, d))
         return g, nF, _dev.jet_size(d)
+    if kind == "system":
+        if nsd < d:
+            raise NotImplementedError("%s: nsd = %d physical directions on a patch of d = %d parametric ones" % (who, nsd, d))
+        return g, nF
     if nsd != d or d not in (2, 3):
         raise NotImplementedError("%s: nsd = %d physical directions on a patch of d = %d parametric ones; a solid has "
                                   "nsd = d = 2 (plane strain) or 3" % (who, nsd, d))
@@ -1389,6 +1405,378 @@ class HyperelasticResidual(_PointLawResidual):
             tangent = _dev.DeviceVector(nF ** 4 * pts.npts)
         form = VectorCoefficientForm(self.geometry, tangent, reaction=values, nq=self.nq, rational=self.rational)
         form._reaction_hint = None if values is None else True
+        return form
+
+
+# ---- first-order systems: nF fields with the four point terms per block (tg_coef_transform_system) --------------------------
+def _system_block(f, pts, shape, who, perm=None):
+    """(DeviceVector, its values on the host in the device layout as [components in the order ``perm``] + [npts], or None for
+    a DeviceVector, which is taken as it is after a length check) of one term of a system form"""
+    if isinstance(f, _dev.DeviceVector):
+        return _point_data(f, pts, shape, who), None
+    flat = point_block(numpy.asarray(_on_points(f, pts), dtype=numpy.float64), pts.npts, shape, perm, who=who)
+    order = range(len(shape)) if perm is None else perm
+    return _dev.DeviceVector(data=flat), flat.reshape(tuple(shape[a] for a in order) + (pts.npts,))
+
+
+class SystemCoefficientForm(object):
+    """a(u, v) = sum_ij int d_K v_i A_iKjL d_L u_j + d_K v_i b_iKj u_j + v_i c_ijL d_L u_j + v_i m_ij u_j dx on the mapped patch for
+    a FIRST-ORDER SYSTEM: nF >= 1 fields on the control mesh's scalar basis sharing one continuous Q_p node grid, dofs field
+    after field (``EqualOrderSpline(nF, mesh)``), d = 1, 2, 3, nsd >= d, nF independent of nsd; u the trial function = column,
+    v the test function = row.  Coupled advection-diffusion-reaction, thermoelasticity, or the tangent of a stabilised flow
+    (``FlowResidual``).
+
+    ``diffusion`` A ``[npts, nF, nsd, nF, nsd]``, ``flux_velocity`` b ``[npts, nF, nsd, nF]``, ``velocity`` c
+    ``[npts, nF, nF, nsd]``, ``reaction`` m ``[npts, nF, nF]``; each an array (or one block for every point), a callable of the
+    points ``x [npts, nsd]`` returning one, None, or a DeviceVector in the device layout: A_iKjL at
+    (((i nF + j) nsd + K) nsd + L) npts + q, b_iKj at ((i nF + j) nsd + K) npts + q, c_ijL at ((i nF + j) nsd + L) npts + q, m_ij
+    at (i nF + j) npts + q.  ``nq`` Gauss points per direction (p + 1 when None).  ``rational``: every field phi / W_h.
+
+    ``symmetric`` is True only when the bits prove all of: A[i, K, j, L] == A[j, L, i, K], b[i, K, j] == c[j, i, K] (both absent,
+    or both given) and m[i, j] == m[j, i], at every point.  One pass brings all nF^2 blocks to the reference element
+    (``tg_coef_transform_system``), each block is then a scalar coefficient form on the element-coupling pattern
+    (``tg_assemble_coef_system``).  One rank, all rows."""
+
+    def __init__(self, geometry, diffusion=None, flux_velocity=None, velocity=None, reaction=None, nq=None, rational=False):
+        if geometry is None:
+            raise ValueError("SystemCoefficientForm: point coefficients live on a mapped patch (geometry=...)")
+        self.geometry, self.nq, self.rational = geometry, nq, bool(rational)
+        self.diffusion, self.flux_velocity, self.velocity, self.reaction = diffusion, flux_velocity, velocity, reaction
+        self._symmetric_hint = None              # (set by a caller who knows: FlowResidual, whose tangent is not symmetric)
+
+    def coefficients(self, V):
+        """(points, nF, A, b, c, M, symmetric) with the point data as DeviceVectors in the device layout (None = absent):
+        computed once per set of points"""
+        who = "SystemCoefficientForm"
+        g, nF = _point_scope(self.geometry, V, who, "system")
+        pts = _vector_points(self.geometry, self.nq, who)
+        return _per_points(self, "_static", pts, lambda: self._static_coefficients(pts, nF, who))
+
+    def _static_coefficients(self, pts, nF, who):
+        nsd = pts.nsd
+        terms = (("diffusion", self.diffusion, (nF, nsd, nF, nsd), _BLOCK_ORDER), ("flux_velocity", self.flux_velocity, (nF, nsd, nF), (0, 2, 1)),
+                 ("velocity", self.velocity, (nF, nF, nsd), None), ("reaction", self.reaction, (nF, nF), None))
+        dev, host = [], []
+        for name, f, shape, perm in terms:
+            v, h = (None, None) if f is None else _system_block(f, pts, shape, "%s: %s" % (who, name), perm)
+            dev.append(v)
+            host.append(h)
+        if self._symmetric_hint is not None:
+            sym = bool(self._symmetric_hint)
+        else:
+            A, b, c, M = [h if h is not None or v is None else v.get_local().reshape(h_shape + (pts.npts,))
+                          for v, h, h_shape in zip(dev, host, ((nF, nF, nsd, nsd), (nF, nF, nsd), (nF, nF, nsd), (nF, nF)))]
+            sym = (A is None or _same_bits(A, A.transpose(1, 0, 3, 2, 4))) and (M is None or _same_bits(M, M.transpose(1, 0, 2))) and \
+                ((b is None and c is None) or (b is not None and c is not None and _same_bits(b, c.transpose(1, 0, 2, 3))))
+        return (pts, nF) + tuple(dev) + (bool(sym),)
+
+    @property
+    def symmetric(self):
+        return self.coefficients(self.geometry.V)[6]
+
+    def _transformed(self, V):
+        pts, nF, A, b, c, M, _ = self.coefficients(V)
+        return pts, nF, _dev.coef_transform_system(pts.verts, pts.p, pts.cp, nF, A, b, c, M, nq=pts.nq, rational=self.rational)
+
+    def assemble_block(self, V, i, j, row0=None, row1=None):
+        """block (i, j): test field i, trial field j (all rows of the field)"""
+        g, nF = _point_scope(self.geometry, V, "SystemCoefficientForm", "system")
+        if not (0 <= int(i) < nF and 0 <= int(j) < nF):
+            raise ValueError("SystemCoefficientForm: block (%r, %r) of a %d-field space" % (i, j, nF))
+        _whole_rows(g.num_nodes(), row0, row1, "SystemCoefficientForm", "patch")
+        pts, nF, A, b, c, M, _ = self.coefficients(V)
+        # the one-field transform of the block's own data: the bits of that block in the transform of all nF^2 (tested)
+        blk, nsd, npts = int(i) * nF + int(j), pts.nsd, pts.npts
+        own = []
+        for v, each in ((A, nsd * nsd), (b, nsd), (c, nsd), (M, 1)):
+            w = None
+            if v is not None:
+                w = _dev.DeviceVector(each * npts, zero=False)
+                _dev.vec_copy_range(w, 0, v, blk * each * npts, each * npts)
+            own.append(w)
+        coef = _dev.coef_transform_system(pts.verts, pts.p, pts.cp, 1, *own, nq=pts.nq, rational=self.rational)
+        return _dev.assemble_coef_matrix(pts.verts, pts.p, pts.cp, coef, nq=pts.nq)
+
+    def assemble_matrix(self, V, row0=None, row1=None):
+        g, nF = _point_scope(self.geometry, V, "SystemCoefficientForm", "system")
+        _whole_rows(nF * g.num_nodes(), row0, row1, "SystemCoefficientForm", "patch")
+        pts, nF, coef = self._transformed(V)
+        return _dev.assemble_coef_system(pts.verts, pts.p, pts.cp, nF, coef, nq=pts.nq)
+
+
+class SystemLoadForm(object):
+    """L(v) = sum_i int s_i v_i + F_iK d_K v_i dx on the space of ``SystemCoefficientForm``: ``f`` = s ``[npts, nF]`` (or a callable
+    of the points returning that, nF numbers, or None), ``flux`` ``[npts, nF, nsd]`` (a callable, or a DeviceVector with F_iK at
+    (i nsd + K) npts + q).  nF calls of ``tg_quad_load_flux``, written field after field.  ``rational``: v_i = phi / W_h."""
+
+    def __init__(self, f=None, geometry=None, flux=None, nq=None, rational=False):
+        if geometry is None:
+            raise ValueError("SystemLoadForm: point values live on a mapped patch (geometry=...)")
+        if f is None and flux is None:
+            raise ValueError("SystemLoadForm: neither f nor flux given")
+        self.f, self.geometry, self.flux, self.nq, self.rational = f, geometry, flux, nq, bool(rational)
+
+    def assemble_vector(self, V, row0=None, row1=None):
+        who = "SystemLoadForm"
+        g, nF = _point_scope(self.geometry, V, who, "system")
+        n = g.num_nodes()
+        _whole_rows(nF * n, row0, row1, who, "patch")
+        pts = _vector_points(self.geometry, self.nq, who)
+
+        def static():
+            s = _field_values(pts, self.f, nF, who + ": f") if self.f is not None else None
+            return s, (_point_data(self.flux, pts, (nF, pts.nsd), who + ": flux") if self.flux is not None else None)
+        s, F = _per_points(self, "_static", pts, static)
+        return _field_loads(pts, n, nF, s, F, self.rational)
+
+
+def _system_state(geometry, V, u, nq, rational, who):
+    """(points, node grid, nF, values of the nF fields [nF npts], their Cartesian gradients [(i nsd + K) npts + q]) of ``u``:
+    field by field through ``tg_quad_eval``"""
+    g, nF = _point_scope(geometry, V, who, "system")
+    pts = _vector_points(geometry, nq, who)
+    n = g.num_nodes()
+    uv = _nodal_vector(u, nF, n, who)
+    both = lambda ui: _dev.quad_eval(pts.verts, pts.p, pts.cp, ui, grad=True, nq=pts.nq, rational=rational)
+    Uq, Gq = _field_by_field(uv, nF, n, both, (pts.npts, pts.nsd * pts.npts))
+    return pts, g, nF, Uq, Gq
+
+
+class SystemResidual(object):
+    """Residual of a first-order system  -d_K flux_iK(x, U, grad U) + source_i(x, U, grad U) = f_i  in weak form,
+    R(v) = sum_i int flux_iK d_K v_i + source_i v_i - f_i v_i dx, on the space of ``SystemCoefficientForm``, the nonlinearity
+    evaluated AT THE QUADRATURE POINTS by host callables: the vector analogue of ``QuasilinearResidual``.
+
+    ``residual(x, U [npts, nF], G [npts, nF, nsd]) -> (flux [npts, nF, nsd] | None, source [npts, nF] | None)`` and
+    ``tangent(x, U, G) -> (A, b, c, m)`` = (d flux / d grad U ``[npts, nF, nsd, nF, nsd]``, d flux / d U ``[npts, nF, nsd, nF]``,
+    d source / d grad U ``[npts, nF, nF, nsd]``, d source / d U ``[npts, nF, nF]``), any of them None.  ``u``: the current FE
+    ``Function``, read at assembly time; ``f``: as for ``SystemLoadForm``.  ``tangent()``: the form whose matrix is the
+    ``SystemCoefficientForm`` of the tangent data; its ``symmetric`` is that of the last assembled tangent (False before).
+    Runs under ``solveNonlinearVariationalProblem`` and inside ``Sum``.  ``rational``: U_i = u_h,i / W_h, tested against phi / W_h."""
+
+    def __init__(self, u, geometry, residual, tangent, f=None, nq=None, rational=False):
+        if geometry is None:
+            raise ValueError("SystemResidual: point coefficients live on a mapped patch (geometry=...)")
+        self.u, self.geometry, self.residual, self._tangent = u, geometry, residual, tangent
+        self.f, self.nq, self.rational = f, nq, bool(rational)
+        self._load = SystemLoadForm(f, geometry, nq=nq, rational=rational) if f is not None else None
+
+    def state(self, V):
+        """(points, node grid, nF, U [npts, nF], its Cartesian gradient [npts, nF, nsd]) on the host"""
+        pts, g, nF, Uq, Gq = _system_state(self.geometry, V, self.u, self.nq, self.rational, "SystemResidual")
+        return pts, g, nF, point_unblock(Uq.get_local(), pts.npts, (nF,)), point_unblock(Gq.get_local(), pts.npts, (nF, pts.nsd))
+
+    def assemble_vector(self, V, row0=None, row1=None):
+        who = "SystemResidual"
+        g, nF = _point_scope(self.geometry, V, who, "system")
+        _whole_rows(nF * g.num_nodes(), row0, row1, who, "patch")
+        pts, g, nF, Uq, Gq = self.state(V)
+        F, s = _law_result(self.residual(pts.x, Uq, Gq), who, "residual(x, U, grad U)", "(flux or None, source or None)", [None] * 2)
+        Fd = _point_data(F, pts, (nF, pts.nsd), who + ": flux") if F is not None else None
+        sd = _field_values(pts, s, nF, who + ": source") if s is not None else None
+        r = _field_loads(pts, g.num_nodes(), nF, sd, Fd, self.rational)
+        if self._load is not None:
+            r.axpy(-1.0, self._load.assemble_vector(V))
+        return r
+
+    def tangent(self):
+        return _SystemTangent(self)
+
+
+class _SystemTangent(object):
+    """see ``_QuasilinearTangent``: ``symmetric`` is that of the last assembled tangent"""
+
+    def __init__(self, res):
+        self.res, self.geometry, self.symmetric = res, res.geometry, False
+
+    def _form(self, V, rows, row0, row1):
+        res, who = self.res, "SystemResidual.tangent"
+        g, nF = _point_scope(res.geometry, V, who, "system")
+        _whole_rows((nF if rows else 1) * g.num_nodes(), row0, row1, who, "patch")
+        pts, g, nF, Uq, Gq = res.state(V)
+        out = _law_result(res._tangent(pts.x, Uq, Gq), "SystemResidual", "tangent(x, U, grad U)", "(A, b, c, m), any of them None",
+                          [None] * 4)
+        form = SystemCoefficientForm(res.geometry, out[0], out[1], out[2], out[3], nq=res.nq, rational=res.rational)
+        self.symmetric = form.coefficients(V)[6]
+        return form
+
+    def assemble_block(self, V, i, j, row0=None, row1=None):
+        return self._form(V, False, row0, row1).assemble_block(V, i, j)
+
+    def assemble_matrix(self, V, row0=None, row1=None):
+        return self._form(V, True, row0, row1).assemble_matrix(V)
+
+
+# ---- incompressible flow: equal-order velocity and pressure, SUPG / PSPG / LSIC (csrc/tg_flow.hip) ---------------------------
+class IncompressibleFlow(object):
+    """The stabilised incompressible Navier-Stokes law at the points, nF = nsd + 1 fields (u_1 .. u_nsd, p) of equal order:
+    Galerkin + SUPG + PSPG + LSIC (Bazilevs, Calo, Cottrell, Hughes, Reali, Scovazzi, CMAME 197 (2007) 173-201, without the
+    cross- and Reynolds-stress terms).  ``density`` rho > 0 and ``viscosity`` mu >= 0 are constants, nu = mu / rho.  With
+    a = c_a u + a0 (the acceleration of a time integrator; zero for a steady problem), f the body force per unit mass and G the
+    element metric (``QuadraturePoints.metric``):
+
+        r_i   = rho (a_i + u_L d_L u_i - f_i) + d_i p             strong momentum residual, viscous term OMITTED
+        tau_M = (4 / dt^2 + u . G u + C_I nu^2 G:G)^(-1/2)         tau_C = 1 / (tau_M tr G)         (4 / dt^2 = 0 when steady)
+        s_i   = rho (a_i + u_L d_L u_i - f_i)
+        F_iK  = mu (d_K u_i + d_i u_K) - p d_iK + tau_M u_K r_i + rho tau_C (d_L u_L) d_iK
+        s_p   = d_L u_L                                           F_pK = (tau_M / rho) r_K
+
+    and R(v, q) = int s_i v_i + F_iK d_K v_i + s_p q + F_pK d_K q dx.  The viscous part of r needs Cartesian second derivatives,
+    which the point kernels do not form; without it the stabilisation is consistent only up to O(tau_M mu lap u), which limits
+    the spatial order to about 2.  The tangent is the EXACT derivative of (s, F) with respect to (u, grad u, p, grad p), the
+    dependence of tau on u included, so that Newton on the discrete problem converges quadratically.
+
+    ``C_I``: the constant of the element-wise inverse estimate in tau_M.  The default 36 is the value Bazilevs et al. (2007) use
+    with quadratic NURBS; it is a parameter of the method, not a number tuned to the tests -- higher degrees ask for a larger one.
+
+    Evaluated on the device by ``tg_flow_points``; ``host`` is the same law in numpy for any float dtype, and any object with
+    such a ``host`` serves ``FlowResidual`` through the same path."""
+
+    def __init__(self, density, viscosity, C_I=36.0):
+        self.density, self.viscosity, self.C_I = float(density), float(viscosity), float(C_I)
+        if not self.density > 0.0 or not self.viscosity >= 0.0 or not self.C_I >= 0.0:
+            raise ValueError("IncompressibleFlow: density > 0, viscosity >= 0 and C_I >= 0 (density = %r, viscosity = %r, C_I = %r)"
+                             % (density, viscosity, C_I))
+
+    def params(self, c_a=0.0, dt4=0.0):
+        return (self.density, self.viscosity, float(c_a), float(dt4), self.C_I)
+
+    def host(self, U, gradU, G, c_a=0.0, a0=None, f=None, dt4=0.0):
+        """``U [npts, nsd + 1]``, ``gradU [npts, nsd + 1, nsd]``, ``G [npts, nsd, nsd]``, ``a0`` / ``f`` ``[npts, nsd]`` or None ->
+        (s [npts, nF], F [npts, nF, nsd], A [npts, nF, nsd, nF, nsd], b [npts, nF, nsd, nF], c [npts, nF, nF, nsd],
+        m [npts, nF, nF], tau [npts, 2]) in the dtype of ``U``"""
+        U, gradU, G = numpy.asarray(U), numpy.asarray(gradU), numpy.asarray(G)
+        dt = U.dtype.type
+        npts, nF = U.shape
+        n = nF - 1
+        rho, mu, ca, CI, d4 = dt(self.density), dt(self.viscosity), dt(c_a), dt(self.C_I), dt(dt4)
+        I = numpy.eye(n, dtype=U.dtype)
+        u, p, H, gp = U[:, :n], U[:, n], gradU[:, :n, :], gradU[:, n, :]
+        acc = ca * u + numpy.einsum("qL,qiL->qi", u, H)
+        if a0 is not None:
+            acc = acc + numpy.asarray(a0, dtype=U.dtype)
+        if f is not None:
+            acc = acc - numpy.asarray(f, dtype=U.dtype)
+        sm = rho * acc
+        r = sm + gp
+        div = numpy.einsum("qii->q", H)
+        Gu = numpy.einsum("qKL,qL->qK", G, u)
+        nu = mu / rho
+        tM = dt(1) / numpy.sqrt(d4 + numpy.einsum("qK,qK->q", u, Gu) + CI * nu * nu * numpy.einsum("qKL,qKL->q", G, G))
+        tC = dt(1) / (tM * numpy.einsum("qKK->q", G))
+        dtM = -(tM ** 3)[:, None] * Gu
+        dtC = -(tC / tM)[:, None] * dtM
+        s = numpy.zeros((npts, nF), dtype=U.dtype)
+        F = numpy.zeros((npts, nF, n), dtype=U.dtype)
+        s[:, :n], s[:, n] = sm, div
+        F[:, :n, :] = mu * (H + H.transpose(0, 2, 1)) + tM[:, None, None] * numpy.einsum("qK,qi->qiK", u, r) + \
+            ((rho * tC * div - p)[:, None, None] * I)
+        F[:, n, :] = (tM / rho)[:, None] * r
+        A = numpy.zeros((npts, nF, n, nF, n), dtype=U.dtype)
+        b = numpy.zeros((npts, nF, n, nF), dtype=U.dtype)
+        c = numpy.zeros((npts, nF, nF, n), dtype=U.dtype)
+        m = numpy.zeros((npts, nF, nF), dtype=U.dtype)
+        R = rho * (H + ca * I)                                                  # d r_i / d u_j
+        m[:, :n, :n] = R
+        c[:, :n, :n, :] = rho * numpy.einsum("ij,qL->qijL", I, u)
+        c[:, n, :n, :] = I
+        b[:, :n, :, :n] = numpy.einsum("qj,qK,qi->qiKj", dtM, u, r) + tM[:, None, None, None] * (
+            numpy.einsum("Kj,qi->qiKj", I, r) + numpy.einsum("qK,qij->qiKj", u, R)) + \
+            rho * numpy.einsum("q,iK,qj->qiKj", div, I, dtC)
+        b[:, :n, :, n] = -I
+        b[:, n, :, :n] = (numpy.einsum("qj,qK->qKj", dtM, r) + tM[:, None, None] * R) / rho
+        A[:, :n, :, :n, :] = mu * (numpy.einsum("ij,KL->iKjL", I, I) + numpy.einsum("iL,jK->iKjL", I, I)) + \
+            rho * tM[:, None, None, None, None] * numpy.einsum("ij,qK,qL->qiKjL", I, u, u) + \
+            rho * tC[:, None, None, None, None] * numpy.einsum("iK,jL->iKjL", I, I)
+        A[:, :n, :, n, :] = tM[:, None, None, None] * numpy.einsum("qK,iL->qiKL", u, I)
+        A[:, n, :, :n, :] = tM[:, None, None, None] * numpy.einsum("Kj,qL->qKjL", I, u)
+        A[:, n, :, n, :] = (tM / rho)[:, None, None] * I
+        return s, F, A, b, c, m, numpy.stack([tM, tC], axis=1)
+
+
+_FlowLaw = collections.namedtuple("_FlowLaw", "pts g nF load tangent tau")
+
+
+class FlowResidual(_PointLawResidual):
+    """Residual of the stabilised incompressible Navier-Stokes equations on the mapped patch (``IncompressibleFlow`` has the
+    formulas): ``u`` the ``Function`` of the nF = nsd + 1 fields (u_1 .. u_nsd, p) on ``EqualOrderSpline(nsd + 1, mesh)``,
+    nsd = d = 2 or 3, read at assembly time.  ``law``: an ``IncompressibleFlow`` -- evaluated at the points ON THE DEVICE
+    (``tg_flow_points``): the point values, the law's loads and the tangent never leave it -- or any object with such a
+    ``host``, whose arrays are uploaded and go through the same loads and the same ``SystemCoefficientForm``.  ``body_force``:
+    f per unit mass, ``[npts, nsd]``, a callable of the points, or nsd numbers.
+
+    ``assemble_vector``: values and gradients field by field (``tg_quad_eval``), the metric ``pts.metric``, the law, then nF flux
+    loads.  ``tangent()``: the ``SystemCoefficientForm`` of the law's A, b, c, m; ``symmetric`` is False.  For a time integrator:
+    ``c_a`` (d acceleration / d velocity), ``a0`` (its history part, a DeviceVector of nsd npts values, or None) and ``dt4`` =
+    4 / dt^2 are attributes, zero for the steady problem.  Runs under ``solveNonlinearVariationalProblem`` and inside ``Sum``.
+    ``rational``: every field u_h,i / W_h, tested against phi / W_h."""
+
+    _who, _kind, _names, nJ = "FlowResidual", "system", ("(s, F)", "(A, b, c, m)"), 1
+
+    def __init__(self, u, geometry, law, body_force=None, nq=None, rational=False):
+        _PointLawResidual.__init__(self, u, geometry, law, "IncompressibleFlow, or an object with host(U, gradU, G, c_a, a0, f, dt4) -> "
+                                   "(s, F, A, b, c, m, tau)", isinstance(law, IncompressibleFlow), body_force, nq, rational)
+        self.c_a, self.a0, self.dt4 = 0.0, None, 0.0
+
+    def _at(self, u, keeps_u=False):
+        other = _PointLawResidual._at(self, u, keeps_u)
+        other.c_a, other.a0, other.dt4 = self.c_a, self.a0, self.dt4
+        return other
+
+    def _check_space(self, g, nF, who):
+        nsd, d = len(self.geometry.cpFuncs) - 1, g.dim()
+        if d == 1 or nsd != d:
+            raise NotImplementedError("%s: nsd = %d physical directions on a patch of d = %d parametric ones; the flow law is "
+                                      "provided for nsd = d = 2 or 3" % (who, nsd, d))
+        if nF != nsd + 1:
+            raise NotImplementedError("%s: nFields = %d; the flow has nsd + 1 = %d fields (the velocity components, then the "
+                                      "pressure)" % (who, nF, nsd + 1))
+
+    def _force(self, pts):
+        if self.body_force is None:
+            return None
+        return _per_points(self, "_fq", pts, lambda: _point_data(self.body_force, pts, (pts.nsd,), self._who + ": body_force"))
+
+    def law(self, V, load=True, tangent=False, tau=False):
+        """(points, node grid, nF, (s, F), (A, b, c, m), tau) at the current state as DeviceVectors, None where not asked for"""
+        g, nF, pts = self._scope(V, self._who)
+        pts, g, nF, Uq, Gq = _system_state(self.geometry, V, self.u, self.nq, self.rational, self._who)
+        nsd, npts, fq = pts.nsd, pts.npts, self._force(pts)
+        if self.a0 is not None and self.a0.size() != nsd * npts:
+            raise ValueError("%s: a0 holds %d values, expected nsd npts = %d" % (self._who, self.a0.size(), nsd * npts))
+        if self.device_law:
+            s, F, A, b, c, M, t = _dev.flow_points(self.material.params(self.c_a, self.dt4), nsd, Uq, Gq, pts.metric, self.a0, fq,
+                                                   load, tangent, tau)
+        else:
+            un = lambda v, shape: None if v is None else point_unblock(v.get_local(), npts, shape)
+            out = self.material.host(un(Uq, (nF,)), un(Gq, (nF, nsd)), un(pts.metric, (nsd, nsd)), c_a=self.c_a,
+                                     a0=un(self.a0, (nsd,)), f=un(fq, (nsd,)), dt4=self.dt4)
+            sh, Fh, Ah, bh, ch, mh, th = _law_result(out, self._who, "law.host(U, gradU, G, ...)", "(s, F, A, b, c, m, tau)", [
+                (npts, nF), (npts, nF, nsd), (npts, nF, nsd, nF, nsd), (npts, nF, nsd, nF), (npts, nF, nF, nsd), (npts, nF, nF), (npts, 2)])
+            up = lambda v, shape, perm=None: _dev.DeviceVector(data=point_block(v, npts, shape, perm))
+            s, F = (up(sh, (nF,)), up(Fh, (nF, nsd))) if load else (None, None)
+            A, b, c, M = (up(Ah, (nF, nsd, nF, nsd), _BLOCK_ORDER), up(bh, (nF, nsd, nF), (0, 2, 1)), up(ch, (nF, nF, nsd)),
+                          up(mh, (nF, nF))) if tangent else (None,) * 4
+            t = up(th, (2,)) if tau else None
+        return _FlowLaw(pts, g, nF, (s, F) if load else None, (A, b, c, M) if tangent else None, t)
+
+    def _law_symmetric(self):
+        return False
+
+    def _load_vector(self, V, out, values=None, sigma=1.0):
+        pts, nF, npts = out.pts, out.nF, out.pts.npts
+        s, F = out.load
+        si = [_dev.DeviceVector(npts, zero=False) for _ in range(nF)]
+        for i in range(nF):
+            _dev.vec_copy_range(si[i], 0, s, i * npts, npts)
+        return _field_loads(pts, out.g.num_nodes(), nF, si, F, self.rational)
+
+    def energy(self, V=None):
+        raise NotImplementedError("FlowResidual: the flow law derives from no energy")
+
+    def _tangent_form(self, pts, nF, tangent, values=None):
+        form = SystemCoefficientForm(self.geometry, *tangent, nq=self.nq, rational=self.rational)
+        form._symmetric_hint = False
         return form
 
 
@@ -2290,6 +2678,10 @@ class FacePoints(QuadraturePoints):
         self.x_device, self.weights, self.normals, self.h_normal = _dev.face_points(verts, p, cp, direction, side, nq)
         self.npts = self.weights.size()
         self._x = self._n = None
+
+    @property
+    def metric(self):
+        raise NotImplementedError("the element metric is provided at the points of the volume, not of a face")
 
     @property
     def n(self):

@@ -14,6 +14,8 @@ a linear problem needs to form its matrix and right-hand side) and evaluated on 
 
 ``NonlinearTransientProblem`` drives nonlinear structural dynamics -- a shell or solid residual with inertia, mass damping
 and a rigid plane (``forms.DynamicResidual``, csrc/tg_dynamics.hip) -- with one Newton solve per step.
+``FlowTransientProblem`` does the same for the first-order system of the stabilised incompressible flow
+(``forms.FlowResidual``, csrc/tg_flow.hip), read at the alpha level.
 
 ``LinearDGSpaceTimeIntegrator`` is not provided: it is a helper that arranges UFL forms over a time slab and has no
 numerics of its own.
@@ -502,6 +504,36 @@ class LinearTransientProblem(object):
         return e + 0.5 * self._x_old.inner(self.K.mult(self._x_old, tmp))
 
 
+def _set_initial_state(who, spline, f, v, constants_rational=None):
+    """Initial data ``v`` into the FE Function ``f``: an FE Function (copied), a DeviceVector of IGA dofs (prolonged by M) or None
+    (``f`` stays as it is).  ``constants_rational`` not None: nF numbers are taken as well, a constant vector -- with True the
+    nodal values are w_i c, the homogeneous representation of the constant in the rational space.  Anything else: ValueError."""
+    import numpy
+    fv = _vec_of(f)
+    ndofs = spline.M.shape[1]
+    if v is None:
+        return
+    if hasattr(v, "vector"):
+        if _vec_of(v).size() != fv.size():
+            raise ValueError("%s: an initial Function of %d nodal values, the space has %d" % (who, _vec_of(v).size(), fv.size()))
+        fv[:] = _vec_of(v)
+    elif isinstance(v, DeviceVector):
+        if v.size() != ndofs:
+            raise ValueError("%s: initial data of %d values, the spline has %d IGA dofs" % (who, v.size(), ndofs))
+        spline.M.mult(v, fv)
+    else:
+        nF = len(spline.V.grids)
+        c = numpy.asarray(v, dtype=numpy.float64).ravel() if constants_rational is not None else None
+        if c is None or c.size != nF:
+            raise ValueError("%s: initial data must be an FE Function%s a DeviceVector of %d IGA dofs%s"
+                             % (who, "," if c is not None else " or", ndofs, " or %d numbers" % nF if c is not None else ""))
+        n = fv.size() // nF
+        w = _vec_of(spline.cpFuncs[-1]).get_local() if constants_rational else numpy.ones(n)
+        fv.set_local(numpy.concatenate([ci * w for ci in c]))
+    if hasattr(f, "invalidate_ghosts"):
+        f.invalidate_ghosts()
+
+
 class NonlinearTransientProblem(object):
     """Nonlinear structural dynamics on an ``ExtractedSpline``, the flow of demos/kl-shell-svk/dynamic-tspline.py:100-293:
 
@@ -574,31 +606,7 @@ class NonlinearTransientProblem(object):
 
     def _set_initial(self, f, v):
         """``v`` (an FE Function, IGA dofs, nF numbers or None) into the FE Function ``f``"""
-        import numpy
-        spline, fv = self.spline, _vec_of(f)
-        if v is None:
-            return
-        if hasattr(v, "vector"):
-            if _vec_of(v).size() != fv.size():
-                raise ValueError("NonlinearTransientProblem: an initial Function of %d nodal values, the space has %d"
-                                 % (_vec_of(v).size(), fv.size()))
-            fv[:] = _vec_of(v)
-        elif isinstance(v, DeviceVector):
-            if v.size() != spline.M.shape[1]:
-                raise ValueError("NonlinearTransientProblem: initial data of %d values, the spline has %d IGA dofs"
-                                 % (v.size(), spline.M.shape[1]))
-            spline.M.mult(v, fv)
-        else:
-            c = numpy.asarray(v, dtype=numpy.float64).ravel()
-            nF = len(spline.V.grids)
-            if c.size != nF:
-                raise ValueError("NonlinearTransientProblem: initial data must be an FE Function, a DeviceVector of %d IGA dofs or "
-                                 "%d numbers" % (spline.M.shape[1], nF))
-            n = fv.size() // nF
-            w = _vec_of(spline.cpFuncs[-1]).get_local() if self.static.rational else numpy.ones(n)
-            fv.set_local(numpy.concatenate([ci * w for ci in c]))
-        if hasattr(f, "invalidate_ghosts"):
-            f.invalidate_ghosts()
+        _set_initial_state("NonlinearTransientProblem", self.spline, f, v, constants_rational=bool(self.static.rational))
 
     def _initial_acceleration(self):
         """rho M a0 = -R_static(y0) - rho a_M M ydot0 in the IGA dofs; a0 = M (the solution) into ``yddot_old``"""
@@ -659,5 +667,150 @@ class NonlinearTransientProblem(object):
             self.last = {"newton": history, "iterations": len(history) - 1, "active_points": active,
                          "assembly_seconds": seconds["assembly"] if self.timing else None,
                          "solve_seconds": seconds["solve"] if self.timing else None}
+            self.steps_done += 1
+        return self
+
+
+class _FlowStep(object):
+    """Residual and tangent of one time step of ``FlowTransientProblem`` as forms of the unknown x of level n+1: the flow law is
+    read at the alpha-level state x_alpha (kept in a Function of its own) with the acceleration xdot_alpha = c_a x_alpha + a0,
+    and R / alpha_f and (dR/dx) / alpha_f = K(x_alpha) are handed out -- the scaling of ``forms.DynamicResidual``."""
+
+    def __init__(self, problem):
+        self.problem, self.geometry, self.symmetric = problem, problem.inner.geometry, False
+
+    def assemble_vector(self, V, row0=None, row1=None):
+        pb = self.problem
+        pb._read_state(V)
+        r = pb.inner.assemble_vector(V, row0, row1)
+        if pb.alpha_f != 1.0:
+            _dev.vec_lincomb(r, [1.0 / pb.alpha_f], [r])
+        return r
+
+    def tangent(self):
+        return self
+
+    def assemble_matrix(self, V, row0=None, row1=None):
+        self.problem._read_state(V)
+        return self.problem.inner.tangent().assemble_matrix(V, row0, row1)
+
+    def assemble_block(self, V, i, j, row0=None, row1=None):
+        self.problem._read_state(V)
+        return self.problem.inner.tangent().assemble_block(V, i, j, row0, row1)
+
+
+class FlowTransientProblem(object):
+    """Transient incompressible flow on an ``ExtractedSpline``: the first-order system of ``forms.FlowResidual`` in the state
+    x = (u_1 .. u_nsd, p) by the generalized-alpha method for first-order systems (Jansen, Whiting & Hulbert 2000;
+    ``scheme="generalized_alpha"``, ``RHO_INF``) or backward Euler (``scheme="backward_euler"``), one
+    ``spline.solveNonlinearVariationalProblem`` per step.  ``flow``: the ``FlowResidual``; its ``u`` is the unknown x of the step
+    being computed.
+
+    The law is read at the ALPHA LEVEL, the WHOLE state including the pressure: x_alpha = alpha_f x + (1 - alpha_f) x_old, with
+    the acceleration xdot_alpha = alpha_m xdot + (1 - alpha_m) xdot_old of the velocity fields (the pressure has no rate in
+    the equations: c_a acts on the velocity fields only).  The pressure of the state is therefore the one that makes
+    x_alpha satisfy the equations, extrapolated to level n+1; for backward Euler the levels coincide.  From the integrator's
+    ``xdot_alpha().split(x)`` = (c, rest):  c_a = d xdot_alpha / d x_alpha = c / alpha_f  and  a0 = rest - c_a (1 - alpha_f) x_old,
+    a nodal vector taken to the points field by field; tau_M takes 4 / DELTA_T^2.  The Newton solve sees R / alpha_f and
+    (dR/dx) / alpha_f, as ``forms.DynamicResidual`` scales them.
+
+    ``x0`` / ``xdot0``: FE Functions, IGA-dof ``DeviceVector`` s (prolonged by M) or None = 0; ``xdot0`` should be compatible
+    with the equations (generalized-alpha over-determines the start).  ``step(n)``; ``x``, ``xdot``: the state at time ``t``;
+    ``last``: {"newton": relative norms, "iterations"} of the last step.  With ``absoluteTolerance`` > 0 a step also ends,
+    without a Newton step, when the first residual norm is at most that."""
+
+    def __init__(self, spline, flow, DELTA_T, scheme="generalized_alpha", RHO_INF=0.5, x0=None, xdot0=None, t=0.0,
+                 absoluteTolerance=0.0):
+        from . import forms as _forms
+        from .common import Function
+        who = "FlowTransientProblem"
+        if scheme not in ("generalized_alpha", "backward_euler"):
+            raise ValueError("%s: scheme must be 'generalized_alpha' or 'backward_euler', not %r" % (who, scheme))
+        if DELTA_T is None or not float(DELTA_T) > 0.0:
+            raise ValueError("%s: DELTA_T must be positive, not %r" % (who, DELTA_T))
+        if scheme == "generalized_alpha" and not 0.0 <= float(RHO_INF) <= 1.0:
+            raise ValueError("%s: RHO_INF must lie in [0, 1], not %r" % (who, RHO_INF))
+        if not float(absoluteTolerance) >= 0.0:
+            raise ValueError("%s: absoluteTolerance = %r must not be negative" % (who, absoluteTolerance))
+        if spline._distributed():
+            raise NotImplementedError("%s: several ranks are not supported" % who)
+        if spline._caller_ordered():
+            raise NotImplementedError("%s: a spline with the caller's FE dof order (feOrder) is not supported" % who)
+        if not isinstance(flow, _forms.FlowResidual):
+            raise NotImplementedError("%s: flow = %r; a FlowResidual carries the law" % (who, flow))
+        self.spline, self.flow, self.scheme = spline, flow, scheme
+        self.DELTA_T, self.absoluteTolerance = float(DELTA_T), float(absoluteTolerance)
+        self._x = flow.u
+        V = spline.V
+        self.x_old, self.xdot_old, self._x_alpha = Function(V), Function(V), Function(V)
+        self._set_initial(self.x_old, x0)
+        self._set_initial(self.xdot_old, xdot0)
+        if scheme == "generalized_alpha":
+            self.integrator = GeneralizedAlphaIntegrator(float(RHO_INF), self.DELTA_T, self._x, [self.x_old, self.xdot_old], t=float(t))
+            self.alpha_f = self.integrator.ALPHA_F
+            rate = self.integrator.xdot_alpha()
+        else:
+            self.integrator = BackwardEulerIntegrator(self.DELTA_T, self._x, [self.x_old], t=float(t))
+            self.alpha_f = 1.0
+            rate = self.integrator.xdot()
+        c, rest = rate.split(self._x)
+        self.c_a = c / self.alpha_f
+        self._a0 = rest - self.c_a * (1.0 - self.alpha_f) * LinearCombination.of(self.x_old)
+        self._state = x_alpha(self.alpha_f, self._x, self.x_old)
+        _vec_of(self._x)[:] = _vec_of(self.x_old)
+        self.inner = flow._at(self._x_alpha)
+        self.inner.c_a, self.inner.dt4 = self.c_a, 4.0 / self.DELTA_T ** 2
+        self._a0_nodal = DeviceVector(_vec_of(self._x).size(), zero=False)
+        self._form = _FlowStep(self)
+        self.last = None
+        self.steps_done = 0
+
+    def _set_initial(self, f, v):
+        _set_initial_state("FlowTransientProblem", self.spline, f, v)
+
+    def _read_state(self, V):
+        """x_alpha into the Function the law reads; a0 of the velocity fields at the points once per step: it depends on the
+        old state only (``step`` and ``advance`` mark it stale)"""
+        inner = self.inner
+        self._state.evaluate(out=self._x_alpha)
+        if inner.a0 is not None:
+            return
+        self._a0.evaluate(out=self._a0_nodal)
+        g, nF, pts = inner._scope(V, "FlowTransientProblem")
+        nsd, n = pts.nsd, g.num_nodes()
+        a0 = DeviceVector(nsd * pts.npts, zero=False)
+        ui = DeviceVector(n, zero=False)
+        for i in range(nsd):
+            _dev.vec_copy_range(ui, 0, self._a0_nodal, i * n, n)
+            _dev.vec_copy_range(a0, i * pts.npts, _dev.quad_eval(pts.verts, pts.p, pts.cp, ui, nq=pts.nq, rational=inner.rational), 0, pts.npts)
+        inner.a0 = a0
+
+    @property
+    def t(self):
+        """time of the state ``x``, ``xdot``"""
+        return self.integrator.t - self.DELTA_T
+
+    @property
+    def x(self):
+        return self.x_old
+
+    @property
+    def xdot(self):
+        return self.xdot_old
+
+    def step(self, n=1):
+        """advances the state by ``n`` steps of ``DELTA_T`` (the predictor is the old state)"""
+        spline = self.spline
+        for _ in range(int(n)):
+            _vec_of(self._x)[:] = _vec_of(self.x_old)
+            if hasattr(self._x, "invalidate_ghosts"):
+                self._x.invalidate_ghosts()
+            self.inner.a0 = None                                         # (the old state is new: a0 is formed at the first assembly)
+            history = spline.solveNonlinearVariationalProblem(self._form, self._form, self._x, absoluteTolerance=self.absoluteTolerance)
+            if self.scheme == "backward_euler":
+                self.integrator.xdot().evaluate(out=self.xdot_old)       # (the state keeps a rate for either scheme)
+            self.integrator.advance()
+            self.inner.a0 = None
+            self.last = {"newton": history, "iterations": len(history) - 1}
             self.steps_done += 1
         return self
