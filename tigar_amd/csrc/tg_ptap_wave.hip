@@ -425,6 +425,8 @@ __global__ void __launch_bounds__(256)
       }
     }
   }
+  // (ovf and cap are wave-uniform; range is the flag of the lane that read the entry -- any lane of the wave)
+  range = __any(range);
   if (lane == 0) {
     if (ovf) atomicMax(status, GW_OVF);
     if (range) atomicMax(status, GW_RANGE);
