@@ -153,3 +153,86 @@ def test_cell_blocks_plus_couplings_outside_the_blocks(ncell, b, ncp, nextra, mo
     K3o = O.extract_matrix(M, A3, list(zd), diag=3.0).tocsr()
     K3.sort_indices(), K3o.sort_indices()
     assert np.array_equal(K3.indices, K3o.indices) and abs(K3 - K3o).max() <= 1e-12 * abs(K3o).max()
+
+
+def _scipy_product(M, A, zd, diag):
+    """(M^T A M with MatZeroRowsColumns, its structural pattern as a matrix of ones); the zero dofs' diagonals are structural"""
+    K = (M.T @ A @ M).tolil()
+    for i in zd:
+        K[i, :] = 0.0
+        K[:, i] = 0.0
+        K[i, i] = diag
+    ones = lambda X: sp.csr_matrix((np.ones(X.nnz), X.indices, X.indptr), shape=X.shape)
+    S = (ones(M).T @ ones(A) @ ones(M)).tocsr()
+    S.sort_indices()
+    return K.tocsr(), S
+
+
+def _same_as_scipy(K, Ko, S):
+    assert np.array_equal(K.indptr, S.indptr) and np.array_equal(K.indices, S.indices)
+    assert abs(K - Ko).max() <= 1e-12 * abs(Ko).max()
+
+
+def _sorted(Kd):
+    K = Kd.to_scipy().tocsr()
+    K.sort_indices()
+    return K
+
+
+@pytest.mark.parametrize("ncell,b,ncp,nf_lo,nf_hi", [(64, 4, 40, 1, 8), (50, 27, 400, 27, 64)])
+def test_cell_rows_placed_through_the_look_up_kernels(ncell, b, ncp, nf_lo, nf_hi, monkeypatch, capfd):
+    """TIGAR_CELL_MERGE_HASH=1: no places are recorded, so the second product on a plan puts its rows where the plan's row
+    pointer says through the look-up kernels (k_gw<GW_PLACED, true, LG, true>; lane groups 3 and 6 here) and leaves no line
+    of a temporary in the trace.  Both products against scipy, the second against a product formed without the switch."""
+    from tigar_amd.device import DeviceCSR
+    from tigar_amd.cellptap import CellBlockPtAP
+    from test_gpu_ptap_retry import attempts, CELLS
+    rng = np.random.default_rng(ncell + b)
+    M, A = _cells(rng, ncell, b, ncp, nf_lo, nf_hi)
+    used = np.unique(M.indices)
+    zd = np.unique(rng.choice(used, size=5)).astype(np.int32)
+    Ko, S = _scipy_product(M, A, list(zd), 2.5)
+    Md, Ad = DeviceCSR.from_scipy(M), DeviceCSR.from_scipy(A)
+    monkeypatch.setenv("TIGAR_CELL_MERGE_HASH", "1")
+    monkeypatch.setenv("TIGAR_TRACE", "1")
+    plan = CellBlockPtAP(Md, b)
+    capfd.readouterr()
+    K1 = _sorted(plan.ptap(Ad, zd, 2.5))
+    got = attempts(capfd.readouterr().err, CELLS)
+    assert len([a for a in got if a[2] == "done"]) == 1 and got[-1][2] == "done"
+    K2 = _sorted(plan.ptap(Ad, zd, 2.5))
+    assert not attempts(capfd.readouterr().err, CELLS)          # rows placed by the plan: no temporary
+    _same_as_scipy(K1, Ko, S)
+    _same_as_scipy(K2, Ko, S)
+    monkeypatch.delenv("TIGAR_CELL_MERGE_HASH")
+    K3 = _sorted(CellBlockPtAP(Md, b).ptap(Ad, zd, 2.5))
+    assert np.array_equal(K2.indptr, K3.indptr) and np.array_equal(K2.indices, K3.indices)
+    assert abs(K2 - K3).max() <= 1e-12 * abs(K3).max()
+    print("first and second product bit for bit the same:", np.array_equal(K1.data.view(np.int64), K2.data.view(np.int64)))
+
+
+def test_cells_too_large_for_four_in_a_workgroup():
+    """b = 64, up to 64 functions per cell: b^2 + 2 b nfmax > 5120 doubles, so the element matrices come from
+    k_cell_element_big (one cell per workgroup) and the merge from k_cell_merge<6>; rows of K hold at most ncp = 100
+    entries.  With couplings outside the blocks such cells are declined (the big kernel reads the blocks alone)."""
+    from tigar_amd.device import DeviceCSR
+    from tigar_amd.cellptap import CellBlockPtAP, block_size_of
+    ncell, b, ncp = 6, 64, 100
+    rng = np.random.default_rng(ncell + b)
+    M, A = _cells(rng, ncell, b, ncp, 40, 64)
+    zd = np.unique(rng.choice(np.unique(M.indices), size=4)).astype(np.int32)
+    Ko, S = _scipy_product(M, A, list(zd), 2.5)
+    Md, Ad = DeviceCSR.from_scipy(M), DeviceCSR.from_scipy(A)
+    assert block_size_of(Ad) == b
+    plan = CellBlockPtAP(Md, b)
+    assert b * b + 2 * b * plan.nfmax > 5120 and np.diff(S.indptr).max() <= ncp
+    K = _sorted(plan.ptap(Ad, zd, 2.5))
+    _same_as_scipy(K, Ko, S)
+    K2 = _sorted(plan.ptap(Ad, zd, 2.5))
+    assert np.array_equal(K2.indices, K.indices) and np.array_equal(K2.data.view(np.int64), K.data.view(np.int64))
+    n = A.shape[0]
+    r, c = np.array([0, 3, 70, 200, 383]), np.array([64, 130, 5, 10, 0])
+    assert np.all(r // b != c // b)
+    Ax = (A + sp.csr_matrix((rng.standard_normal(r.size), (r, c)), shape=(n, n))).tocsr()
+    Ax.sort_indices()
+    assert plan.ptap_extras(DeviceCSR.from_scipy(Ax)) is None

@@ -22,6 +22,7 @@
 #include "tg_bump.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <climits>
 #include <cstring>
 
 enum { GW_COUNT = 0, GW_BUMP = 1, GW_PLACED = 2 };
@@ -440,46 +441,57 @@ static int gw_lg_group(double mean) {
   while (g < 64 && g < 0.75 * mean) g <<= 1;
   return tg_lg(g);
 }
-template <int MODE, bool FINAL>
-static void gw_launch(int lg, unsigned grid, size_t lds, const gw_args &P, int64_t *out_off, int32_t *out_cnt,
-                      int64_t *row_cnt, uint32_t *ocol, double *oval, unsigned long long *cursor, int64_t capacity,
-                      const uint8_t *mask, double diag, int64_t out_row0, int *status, unsigned long long *sum) {
-#define GW_GO(LGV)                                                                                                    \
-  hipLaunchKernelGGL((k_gw<MODE, FINAL, LGV>), dim3(grid), dim3(256), lds, g_tg.stream, P, out_off, out_cnt, row_cnt, \
-                     ocol, oval, cursor, capacity, mask, diag, out_row0, status, status + 1, sum)
-  switch (lg) {
-    case 3: GW_GO(3); break;
-    case 4: GW_GO(4); break;
-    case 5: GW_GO(5); break;
-    default: GW_GO(6); break;
-  }
-#undef GW_GO
-}
 
-static void gw_set_lds_limits() {
-  static bool done = false;
-  if (done) return;
-#define GW_LIM(MODE, FINAL, LGV) \
-  hipFuncSetAttribute((const void *)k_gw<MODE, FINAL, LGV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-#define GW_LIM4(MODE, FINAL) \
-  GW_LIM(MODE, FINAL, 3);    \
-  GW_LIM(MODE, FINAL, 4);    \
-  GW_LIM(MODE, FINAL, 5);    \
-  GW_LIM(MODE, FINAL, 6)
-  GW_LIM4(GW_COUNT, false);
-  GW_LIM4(GW_BUMP, false);
-  GW_LIM4(GW_BUMP, true);
-  GW_LIM4(GW_PLACED, true);
-#undef GW_LIM4
-#undef GW_LIM
-  done = true;
+// ---- the host side: one table of kernels, one launch, one description of a pass ----
+// A row of the table names one instantiation: k_gw by (mode, final, shared, lanes), the two templated kernels of the
+// cell-block product by their lanes.  The table itself stands below the cell-block kernels (g_gw_routes).
+enum { GW_CELL_ELEMENT = 10, GW_CELL_MERGE = 11 };       // `mode` of the rows that are not k_gw
+typedef void (*gw_row_fn)(gw_args, int64_t *, int32_t *, int64_t *, uint32_t *, double *, unsigned long long *, int64_t,
+                          const uint8_t *, double, int64_t, int *, int *, unsigned long long *);
+typedef void (*gw_element_fn)(const double *, const int64_t *, const double *, const int32_t *, int64_t, int, int, double *);
+typedef void (*gw_merge_fn)(const int64_t *, const int32_t *, const double *, const uint16_t *, const int32_t *, int, int64_t,
+                            const int64_t *, const int32_t *, const uint8_t *, double, double *);
+struct gw_route {
+  int mode;
+  bool final, shared;
+  int lg;
+  gw_row_fn row;
+  gw_element_fn element;
+  gw_merge_fn merge;
+};
+static const gw_route *gw_route_find(int mode, bool final, bool shared, int lg);
+static void gw_routes_init();
+
+// The switches, read at every entry point (the tests change the environment between calls).
+#define GW_UNSET INT_MIN
+struct gw_switches {
+  int wave;                     // TIGAR_PTAP_WAVE: 1 / 0 = take / leave the wave kernels, -1 = the rule of tg_ptap_wave_plan
+  bool debug;                   // TIGAR_PTAP_WAVE_DEBUG (set to anything): the [gw] lines
+  int strided;                  // TIGAR_PTAP_WAVE_STRIDED: rows of a temporary at a fixed stride where the lengths allow it
+  int lg1, lg2;                 // TIGAR_PTAP_WAVE_LG1 / _LG2: lanes per operand row (GW_UNSET: from the mean row length)
+  int rpw1, rpw2;               // TIGAR_PTAP_WAVE_RPW1 / _RPW2: rows per wave
+  double load_inv;              // TIGAR_PTAP_WAVE_LOADINV: table slots per key
+  const char *tile1, *tile2;    // TIGAR_PTAP_WAVE_TILE1 / _TILE2: lattice hints (gw_tile_hint), null = none
+  bool cell_merge_hash;         // TIGAR_CELL_MERGE_HASH (set to anything): the cell-block product never merges by places
+};
+static gw_switches gw_switches_read() {
+  gw_switches w;
+  w.wave = tg_env_int("TIGAR_PTAP_WAVE", -1);
+  w.debug = getenv("TIGAR_PTAP_WAVE_DEBUG") != nullptr;
+  w.strided = tg_env_int("TIGAR_PTAP_WAVE_STRIDED", 1);
+  w.lg1 = tg_env_int("TIGAR_PTAP_WAVE_LG1", GW_UNSET);
+  w.lg2 = tg_env_int("TIGAR_PTAP_WAVE_LG2", GW_UNSET);
+  w.rpw1 = tg_env_int("TIGAR_PTAP_WAVE_RPW1", 8);
+  w.rpw2 = tg_env_int("TIGAR_PTAP_WAVE_RPW2", 2);
+  w.load_inv = getenv("TIGAR_PTAP_WAVE_LOADINV") ? atof(getenv("TIGAR_PTAP_WAVE_LOADINV")) : 2.5;
+  w.tile1 = getenv("TIGAR_PTAP_WAVE_TILE1");
+  w.tile2 = getenv("TIGAR_PTAP_WAVE_TILE2");
+  w.cell_merge_hash = getenv("TIGAR_CELL_MERGE_HASH") != nullptr;
+  return w;
 }
 
 // lattice hint "n0,n1,t0,t1,t2" (experiments: TIGAR_PTAP_WAVE_TILE1 / _TILE2); ignored unless the rows are whole planes
-static void gw_tile_hint(gw_args &P, const char *env) {
-  P.n0 = P.n1 = 0;
-  P.t0 = P.t1 = P.t2 = 1;
-  const char *s = getenv(env);
+static void gw_tile_hint(gw_args &P, const char *s) {
   long long n0 = 0, n1 = 0;
   int t0 = 8, t1 = 8, t2 = 8;
   if (!s || sscanf(s, "%lld,%lld,%d,%d,%d", &n0, &n1, &t0, &t1, &t2) < 2) return;
@@ -502,23 +514,37 @@ static int gw_mix_columns(tg_csr_s *m, tg_dbuf<uint32_t> &out) {
   return 0;
 }
 
-static void gw_fill_stage1(gw_args &P, tg_csr_s *a, tg_csr_s *m, const uint32_t *m_mix, int64_t m_row0) {
-  P.n0 = P.n1 = 0;
-  P.t0 = P.t1 = P.t2 = 1;
-  P.debug = getenv("TIGAR_PTAP_WAVE_DEBUG") ? atoi(getenv("TIGAR_PTAP_WAVE_DEBUG")) : 0;
-  P.out_stride = 0;
-  P.y_start_mix = nullptr;
-  P.x_rowptr = a->rowptr;
-  P.x_col = a->col;
-  P.x_val = a->val;
-  P.x_nrows = a->nrows;
+// ---- the arguments of a pass: outer rows = the canonical CSR x, every row in order, no tiles, rows reserved with the cursor
+static gw_args gw_args_outer(const tg_csr_s *x) {
+  gw_args P;
+  memset(&P, 0, sizeof(P));
+  P.x_rowptr = x->rowptr;
+  P.x_col = x->col;
+  P.x_val = x->val;
+  P.x_nrows = x->nrows;
   P.row_stride = 1;
-  P.y_start = m->rowptr;
+  P.t0 = P.t1 = P.t2 = 1;
+  return P;
+}
+// operand rows = the canonical CSR y, whose first row is y_row0, with its columns mixed
+static void gw_operand_csr(gw_args &P, const tg_csr_s *y, const uint32_t *y_mix, int64_t y_row0) {
+  P.y_start = y->rowptr;
   P.y_cnt = nullptr;
-  P.y_mix = m_mix;
-  P.y_val = m->val;
-  P.y_row0 = m_row0;
-  P.y_nrows = m->nrows;
+  P.y_mix = y_mix;
+  P.y_val = y->val;
+  P.y_row0 = y_row0;
+  P.y_nrows = y->nrows;
+}
+// operand rows = loose rows (start, count); start_mix: where a row's columns start when rows share one column list
+static void gw_operand_loose(gw_args &P, const int64_t *start, const int32_t *cnt, const uint32_t *mix, const double *val,
+                             int64_t y_row0, int64_t y_nrows, const int64_t *start_mix = nullptr) {
+  P.y_start = start;
+  P.y_cnt = cnt;
+  P.y_mix = mix;
+  P.y_val = val;
+  P.y_start_mix = start_mix;
+  P.y_row0 = y_row0;
+  P.y_nrows = y_nrows;
 }
 
 static unsigned gw_grid(int64_t nrows, int rows_per_wave) {
@@ -526,7 +552,137 @@ static unsigned gw_grid(int64_t nrows, int rows_per_wave) {
   return (unsigned)(tg_cdiv(nblk, 8) * 8);
 }
 
-// sizes the tables of stage 1 from a sample of A's rows; the tables of stage 2 come from the caller's probe of K's rows
+// where the rows of a pass go
+struct gw_out {
+  int64_t *off = nullptr;       // start of every row: written (BUMP), or the row pointer of K (PLACED)
+  int32_t *cnt32 = nullptr;     // lengths of the loose rows of an intermediate
+  int64_t *cnt64 = nullptr;     // lengths of the rows of K for the scan (BUMP)
+  uint32_t *col = nullptr;
+  double *val = nullptr;
+  unsigned long long *cursor = nullptr;
+  int64_t capacity = 0;
+  const uint8_t *mask = nullptr;          // MatZeroRowsColumns (rows of K)
+  double diag = 0.0;
+  int64_t row0 = 0;             // global index of the first output row
+};
+
+// status words at g_tg.scratch: [0] status, [1] longest row, [2..3] sum of the lengths
+static int gw_launch(const gw_route *r, const gw_args &P, const gw_out &o) {
+  TG_REQUIRE(r && r->row, "PtAP (wave kernels): no kernel for this pass");
+  int *status = (int *)g_tg.scratch;
+  hipLaunchKernelGGL(r->row, dim3(gw_grid(P.x_nrows, P.rows_per_wave)), dim3(256), 4 * gw_wave_bytes(P.ts), g_tg.stream, P, o.off,
+                     o.cnt32, o.cnt64, o.col, o.val, o.cursor, o.capacity, o.mask, o.diag, o.row0, status, status + 1,
+                     (unsigned long long *)(status + 2));
+  return 0;
+}
+
+// One Gustavson pass as its drivers see it.
+struct gw_stage {
+  const char *site;             // names the pass in the trace (tg_bump)
+  const char *who, *name;       // ... and in the errors: "<who>: <name> failed to run"
+  gw_args P;                    // (rows per wave and tiles included; table size and stride are set per attempt)
+  gw_out out;                   // what the caller knows: mask, diag, first row, the lengths of an intermediate
+  int lg;                       // lanes per operand row
+  int *ts, *max_len;            // the plan's table size and longest row, which growth updates
+  double mean;                  // mean row length
+  double *mean_seen = nullptr;  // (or null) raised to the mean of the rows written
+  bool final = true, shared = false;      // rows of K / operand rows that share column lists
+  int64_t slack;                // entries beyond the estimate when rows are reserved with the cursor
+  double headroom;              // ... and the factor on the mean
+  bool stride_allowed = true, stride_forced = false;      // rows at a fixed stride: where the longest row is near the mean / always
+};
+
+// what a pass reported -> return code and message: 0; 3; a bump pass then grows (TG_BUMP_RETRY), a placed one has met
+// operands of another pattern than the plan's (4)
+static int gw_outcome(const char *who, int status, bool placed) {
+  if (status == GW_OK) return 0;
+  if (status == GW_RANGE) {
+    tg_set_error("PtAP: a row block does not cover the rows referenced (slab halo too small)");
+    return 3;
+  }
+  if (!placed) return TG_BUMP_RETRY;           // GW_OVF, GW_CAP
+  tg_set_error("%s: operands no longer match the plan's pattern (status %d)", who, status);
+  return 4;
+}
+
+// The pass into a temporary, grown and repeated up to six times: 0, 100 when the kernels decline (tables beyond the LDS
+// or still growing after the last attempt), another value on error.  Rows of the temporary stand at a fixed stride (no
+// atomics) unless the longest row is far above the mean.
+static int gw_stage_bump(gw_stage &S, tg_bump &t) {
+  const int64_t nrows = S.P.x_nrows;
+  const gw_route *route = gw_route_find(GW_BUMP, S.final, S.shared, S.lg);
+  const bool strided = S.stride_forced || (*S.max_len <= 2.0 * S.mean + 32.0 && S.stride_allowed);
+  int64_t stride = strided ? ((*S.max_len + 7) & ~7) : 0;
+  t.capacity = strided ? stride * nrows : (int64_t)(S.mean * S.headroom * (double)nrows) + *S.max_len + S.slack;
+  TG_TRY(t.init(nrows, S.final, 2, 4));
+  size_t lds = 0;
+  int rc = t.run(
+      6,
+      [&](int) {
+        S.P.ts = t.ts[0] = *S.ts;
+        S.P.lgts = tg_lg(*S.ts);
+        S.P.out_stride = stride;
+        lds = 4 * gw_wave_bytes(S.P.ts);
+        if (lds > 160 * 1024) return 100;
+        gw_out o = S.out;
+        o.off = t.off;
+        if (S.final) o.cnt64 = t.cnt;
+        o.col = (uint32_t *)t.tcol.get();
+        o.val = t.tval;
+        o.cursor = t.cursor;
+        o.capacity = t.capacity;
+        return gw_launch(route, S.P, o);
+      },
+      [&](int, const int *h, unsigned long long used) {
+        const int rc = gw_outcome(S.who, h[0], false);
+        if (rc != TG_BUMP_RETRY) {
+          if (!rc && S.mean_seen) *S.mean_seen = std::max(*S.mean_seen, (double)used / (double)nrows);
+          return rc;
+        }
+        if (h[0] == GW_OVF) {
+          *S.ts *= 2;
+          if (!stride) t.capacity = std::max<int64_t>(t.capacity, (int64_t)used + S.slack);
+        } else if (stride) {
+          const int hm = h[1];                 // the longest row met
+          *S.max_len = std::max(*S.max_len, hm);
+          stride = (std::max<int64_t>(hm, stride + stride / 4) + 7) & ~(int64_t)7;
+          t.capacity = stride * nrows;
+        } else {
+          t.capacity = std::max<int64_t>((int64_t)used + S.slack, t.capacity + t.capacity / 2);
+        }
+        return (int)TG_BUMP_RETRY;
+      });
+  if (rc == TG_BUMP_NORUN) {
+    tg_set_error("%s: %s failed to run (LDS %zu B)", S.who, S.name, lds);
+    rc = 1;
+  }
+  return rc == TG_BUMP_RETRY ? 100 : rc;
+}
+
+// The pass when the plan knows K's row pointer: rows go to their CSR place directly.  *k is set as soon as it exists (the
+// caller destroys it on error); 4 when the operands no longer have the plan's pattern.
+static int gw_stage_placed(gw_stage &S, const tg_gw_plan *plan, int64_t ncols, tg_csr_s **k) {
+  const int64_t nrows = S.P.x_nrows;
+  int *status = (int *)g_tg.scratch;
+  TG_TRY(tg_csr_alloc(nrows, ncols, plan->k_nnz, k));
+  TG_CHECK_HIP(hipMemcpyAsync((*k)->rowptr, plan->k_rowptr, (size_t)(nrows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream));
+  S.P.ts = *S.ts;
+  S.P.lgts = tg_lg(*S.ts);
+  TG_CHECK_HIP(hipMemsetAsync(status, 0, 4 * sizeof(int), g_tg.stream));
+  gw_out o = S.out;
+  o.off = (*k)->rowptr;
+  o.col = (uint32_t *)(*k)->col;
+  o.val = (*k)->val;
+  TG_TRY(gw_launch(gw_route_find(GW_PLACED, true, S.shared, S.lg), S.P, o));
+  int h = 0;
+  const hipError_t e = hipMemcpyAsync(&h, status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream);
+  if (hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess || e != hipSuccess) {
+    tg_set_error("%s: numeric pass (placed) failed to run", S.who);
+    return 1;
+  }
+  return gw_outcome(S.who, h, true);
+}
+
 static int g_gw_prefer = 0;
 extern "C" int tg_ptap_prefer(int kernels) {
   const int old = g_gw_prefer;
@@ -534,49 +690,50 @@ extern "C" int tg_ptap_prefer(int kernels) {
   return old;
 }
 
+// the row sample of the plan: `nsample` rows of A M are formed and counted, nothing is written.  h: the status words
+static int gw_probe(tg_csr_s *a, tg_csr_s *m, int64_t m_row0, int lg_m, int64_t nsample, int *h) {
+  int *status = (int *)g_tg.scratch;
+  tg_dbuf<uint32_t> m_mix;
+  TG_TRY(gw_mix_columns(m, m_mix));
+  gw_args S = gw_args_outer(a);
+  gw_operand_csr(S, m, m_mix, m_row0);
+  S.x_nrows = nsample;
+  S.row_stride = std::max<int64_t>(1, a->nrows / nsample);
+  S.ts = 2048;                                 // 4 waves x 2048 x 14 B = 112 KB
+  S.lgts = 11;
+  S.rows_per_wave = 4;
+  TG_CHECK_HIP(hipMemsetAsync(status, 0, 4 * sizeof(int), g_tg.stream));
+  TG_TRY(gw_launch(gw_route_find(GW_COUNT, false, false, lg_m), S, gw_out()));
+  const hipError_t e1 = hipGetLastError();
+  const hipError_t e2 = hipMemcpyAsync(h, status, 4 * sizeof(int), hipMemcpyDeviceToHost, g_tg.stream);
+  const hipError_t e3 = hipStreamSynchronize(g_tg.stream);      // (m_mix goes back to the pool after it)
+  TG_CHECK_HIP(e1);
+  TG_CHECK_HIP(e2);
+  TG_CHECK_HIP(e3);
+  return 0;
+}
+
+// sizes the tables of stage 1 from a sample of A's rows; the tables of stage 2 come from the caller's probe of K's rows
 int tg_ptap_wave_plan(tg_csr_s *a, tg_csr_s *m, int64_t m_row0, tg_csr_s *mt, int max_k, double mean_k, tg_gw_plan *plan) {
+  const gw_switches sw = gw_switches_read();
   plan->usable = false;
   // Where the wave kernels win (MI355X, profiles/r4_general_ptap.md): operand rows that fill a wave -- 3-D patches of
   // degree >= 3 held resident (48^3 ... 96^3 elements: 1.5-1.8 x).  Short rows (2-D, p = 2, T-spline cells: 12-27 entries)
   // leave most lanes of a row-per-wave walk idle and the fused kernel is up to 2 x faster there; so is it when the product
   // is streamed in row blocks whose operand rows overlap (every block recomputes the rows of A M in its halo).
   // TIGAR_PTAP_WAVE=1/0 and tg_ptap_prefer() override the rule.
-  const int forced = tg_env_int("TIGAR_PTAP_WAVE", -1);
-  const int pref = forced == 1 ? 1 : forced == 0 ? 2 : g_gw_prefer;
+  const int pref = sw.wave == 1 ? 1 : sw.wave == 0 ? 2 : g_gw_prefer;
   if (pref == 2) return 0;
   const double mean_m = (double)m->nnz / (double)std::max<int64_t>(m->nrows, 1);
   if (pref == 0 && mean_m < 40.0) return 0;
   if (a->nrows <= 0 || mt->nrows <= 0 || a->nnz <= 0 || m->nnz <= 0) return 0;
-  gw_set_lds_limits();
-  int *status = (int *)g_tg.scratch;           // [0] status, [1] maximum, [2..3] sum
-  unsigned long long *sum = (unsigned long long *)(status + 2);
-  tg_dbuf<uint32_t> m_mix;
-  TG_TRY(gw_mix_columns(m, m_mix));
-  gw_args S;
-  gw_fill_stage1(S, a, m, m_mix, m_row0);
+  gw_routes_init();
   const int64_t nsample = std::min<int64_t>(a->nrows, 4096);
-  S.x_nrows = nsample;
-  S.row_stride = std::max<int64_t>(1, a->nrows / nsample);
-  S.ts = 2048;                                 // 4 waves x 2048 x 14 B = 112 KB
-  S.lgts = 11;
-  S.rows_per_wave = 4;
-  plan->lg_m = tg_env_int("TIGAR_PTAP_WAVE_LG1", gw_lg_group((double)m->nnz / (double)std::max<int64_t>(m->nrows, 1)));
-  TG_CHECK_HIP(hipMemsetAsync(status, 0, 4 * sizeof(int), g_tg.stream));
-  gw_launch<GW_COUNT, false>(plan->lg_m, gw_grid(nsample, S.rows_per_wave), 4 * gw_wave_bytes(S.ts), S, nullptr, nullptr, nullptr,
-                             nullptr, nullptr, nullptr, 0, nullptr, 0.0, 0, status, sum);
+  plan->lg_m = sw.lg1 != GW_UNSET ? sw.lg1 : gw_lg_group(mean_m);
   int h[4] = {0, 0, 0, 0};
-  const hipError_t e1 = hipGetLastError();
-  const hipError_t e2 = hipMemcpyAsync(h, status, sizeof(h), hipMemcpyDeviceToHost, g_tg.stream);
-  const hipError_t e3 = hipStreamSynchronize(g_tg.stream);
-  m_mix.reset();
-  TG_CHECK_HIP(e1);
-  TG_CHECK_HIP(e2);
-  TG_CHECK_HIP(e3);
-  if (h[0] == GW_RANGE) {
-    tg_set_error("PtAP: a row block does not cover the rows referenced (slab halo too small)");
-    return 3;
-  }
-  if (getenv("TIGAR_PTAP_WAVE_DEBUG")) fprintf(stderr, "[gw] probe status %d max %d sum %d lg_m %d\n", h[0], h[1], h[2], plan->lg_m);
+  TG_TRY(gw_probe(a, m, m_row0, plan->lg_m, nsample, h));
+  if (h[0] == GW_RANGE) return gw_outcome("PtAP (wave kernels)", h[0], false);
+  if (sw.debug) fprintf(stderr, "[gw] probe status %d max %d sum %d lg_m %d\n", h[0], h[1], h[2], plan->lg_m);
   if (h[0] != GW_OK) return 0;                 // a row of A M fills the probe's table: the workgroup kernel's business
   unsigned long long total;
   memcpy(&total, &h[2], sizeof(total));
@@ -584,11 +741,10 @@ int tg_ptap_wave_plan(tg_csr_s *a, tg_csr_s *m, int64_t m_row0, tg_csr_s *mt, in
   plan->mean_am = (double)total / (double)nsample;
   plan->max_k = max_k;
   plan->mean_k = mean_k;
-  const double load_inv = getenv("TIGAR_PTAP_WAVE_LOADINV") ? atof(getenv("TIGAR_PTAP_WAVE_LOADINV")) : 2.5;
-  plan->ts_am = std::max(64, tg_pow2_ge((int64_t)(plan->max_am * load_inv) + 4));
-  plan->ts_k = std::max(64, tg_pow2_ge((int64_t)(max_k * load_inv) + 4));
-  plan->lg_am = tg_env_int("TIGAR_PTAP_WAVE_LG2", gw_lg_group(plan->mean_am));
-  if (getenv("TIGAR_PTAP_WAVE_DEBUG"))
+  plan->ts_am = std::max(64, tg_pow2_ge((int64_t)(plan->max_am * sw.load_inv) + 4));
+  plan->ts_k = std::max(64, tg_pow2_ge((int64_t)(max_k * sw.load_inv) + 4));
+  plan->lg_am = sw.lg2 != GW_UNSET ? sw.lg2 : gw_lg_group(plan->mean_am);
+  if (sw.debug)
     fprintf(stderr, "[gw] max_am %d mean_am %.1f max_k %d mean_k %.1f ts %d / %d lg %d / %d\n", plan->max_am, plan->mean_am, max_k,
             mean_k, plan->ts_am, plan->ts_k, plan->lg_m, plan->lg_am);
   // (the four tables of a workgroup have to fit the 160 KB of a CU: 2048 slots each)
@@ -602,158 +758,80 @@ void tg_ptap_wave_plan_free(tg_gw_plan *plan) {
   plan->k_nnz = -1;
 }
 
+// stage 1: (A M)_r = sum_s A[r,s] M[s,:] in loose rows (columns mixed), their lengths in am_cnt
+static gw_stage gw_describe_am(const gw_switches &sw, tg_gw_plan *plan, tg_csr_s *a, tg_csr_s *m, const uint32_t *m_mix,
+                               int64_t m_row0, int32_t *am_cnt) {
+  gw_stage S;
+  S.site = "wave kernels, A M";
+  S.who = "PtAP (wave kernels)";
+  S.name = "stage A M";
+  S.P = gw_args_outer(a);
+  gw_operand_csr(S.P, m, m_mix, m_row0);
+  S.P.rows_per_wave = sw.rpw1;
+  gw_tile_hint(S.P, sw.tile1);
+  S.out.cnt32 = am_cnt;
+  S.lg = plan->lg_m;
+  S.ts = &plan->ts_am;
+  S.max_len = &plan->max_am;
+  S.mean = plan->mean_am;
+  S.mean_seen = &plan->mean_am;
+  S.final = false;
+  S.slack = 4096;
+  S.headroom = 1.08;
+  S.stride_allowed = sw.strided != 0;
+  return S;
+}
+
+// stage 2: K_i = sum_r M^T[i,r] (A M)[r,:], operand rows = the loose rows of the intermediate (FE row r -> r - a_row0)
+static gw_stage gw_describe_k(const gw_switches &sw, tg_gw_plan *plan, tg_csr_s *mt, const tg_bump &am, const int32_t *am_cnt,
+                              int64_t a_row0, int64_t a_nrows, const uint8_t *mask, double diag, int64_t mt_row0) {
+  gw_stage S;
+  S.site = "wave kernels, Mt (A M)";
+  S.who = "PtAP (wave kernels)";
+  S.name = "stage M^T (A M)";
+  S.P = gw_args_outer(mt);
+  gw_operand_loose(S.P, am.off, am_cnt, (const uint32_t *)am.tcol.get(), am.tval, a_row0, a_nrows);
+  S.P.rows_per_wave = sw.rpw2;
+  gw_tile_hint(S.P, sw.tile2);
+  S.out.mask = mask;
+  S.out.diag = diag;
+  S.out.row0 = mt_row0;
+  S.lg = plan->lg_am;
+  S.ts = &plan->ts_k;
+  S.max_len = &plan->max_k;
+  S.mean = plan->mean_k;
+  S.slack = 1024;
+  S.headroom = 1.05;
+  S.stride_allowed = sw.strided != 0;
+  return S;
+}
+
 // Returns 0 with *k_out set, 100 when the kernels decline (tables beyond their limits after the retries: the caller falls
 // back to the workgroup kernel), another value on error.
 int tg_ptap_wave_numeric(tg_gw_plan *plan, tg_csr_s *a, int64_t a_row0, tg_csr_s *m, int64_t m_row0, tg_csr_s *mt,
                          int64_t mt_row0, const uint8_t *mask, double diag, tg_csr_s **k_out) {
-  gw_set_lds_limits();
-  int *status = (int *)g_tg.scratch;
-  unsigned long long *sum = (unsigned long long *)(status + 2);
-  int rc = 0;
-  tg_csr_s *k = nullptr;
-  // ---- stage 1: the intermediate A M in loose rows (its columns mixed), lengths in am_cnt
-  tg_bump t1("wave kernels, A M");
+  const gw_switches sw = gw_switches_read();
+  gw_routes_init();
+  // ---- stage 1: the intermediate A M stays in the temporary of t1
   tg_dbuf<int32_t> am_cnt;
   tg_dbuf<uint32_t> m_mix;
-  TG_TRY(t1.init(a->nrows, false, 2, 4));
   TG_TRY(am_cnt.alloc(a->nrows + 1));
   TG_TRY(gw_mix_columns(m, m_mix));
-  gw_args P1;
-  gw_fill_stage1(P1, a, m, m_mix, m_row0);
-  P1.rows_per_wave = tg_env_int("TIGAR_PTAP_WAVE_RPW1", 8);
-  gw_tile_hint(P1, "TIGAR_PTAP_WAVE_TILE1");
-  // rows of the temporary at a fixed stride (no atomics) unless the longest row is far above the mean
-  int64_t stride1 = (plan->max_am <= 2.0 * plan->mean_am + 32.0 && tg_env_int("TIGAR_PTAP_WAVE_STRIDED", 1)) ? ((plan->max_am + 7) & ~7) : 0;
-  t1.capacity = stride1 ? stride1 * a->nrows : (int64_t)(plan->mean_am * 1.08 * (double)a->nrows) + plan->max_am + 4096;
-  size_t lds = 0;
-  rc = t1.run(
-      6,
-      [&](int) {
-        P1.ts = t1.ts[0] = plan->ts_am;
-        P1.lgts = tg_lg(plan->ts_am);
-        P1.out_stride = stride1;
-        lds = 4 * gw_wave_bytes(P1.ts);
-        if (lds > 160 * 1024) return 100;
-        gw_launch<GW_BUMP, false>(plan->lg_m, gw_grid(a->nrows, P1.rows_per_wave), lds, P1, t1.off, am_cnt, nullptr,
-                                  (uint32_t *)t1.tcol.get(), t1.tval, t1.cursor, t1.capacity, nullptr, 0.0, 0, status, sum);
-        return 0;
-      },
-      [&](int, const int *h, unsigned long long used) {
-        if (h[0] == GW_RANGE) {
-          tg_set_error("PtAP: a row block does not cover the rows referenced (slab halo too small)");
-          return 3;
-        }
-        if (h[0] == GW_OK) {
-          plan->mean_am = std::max(plan->mean_am, (double)used / (double)a->nrows);
-          return (int)TG_BUMP_DONE;
-        }
-        if (h[0] == GW_OVF) {
-          plan->ts_am *= 2;
-          if (!stride1) t1.capacity = std::max<int64_t>(t1.capacity, (int64_t)used + 4096);
-        } else if (stride1) {
-          const int hm = h[1];                 // the longest row met
-          plan->max_am = std::max(plan->max_am, hm);
-          stride1 = (std::max<int64_t>(hm, stride1 + stride1 / 4) + 7) & ~(int64_t)7;
-          t1.capacity = stride1 * a->nrows;
-        } else {
-          t1.capacity = std::max<int64_t>((int64_t)used + 4096, t1.capacity + t1.capacity / 2);
-        }
-        return (int)TG_BUMP_RETRY;
-      });
-  if (rc == TG_BUMP_NORUN) {
-    tg_set_error("PtAP (wave kernels): stage A M failed to run (LDS %zu B)", lds);
-    rc = 1;
-  }
-  if (rc == TG_BUMP_RETRY) rc = 100;
-  if (rc) return rc;
+  gw_stage S1 = gw_describe_am(sw, plan, a, m, m_mix, m_row0, am_cnt);
+  tg_bump t1(S1.site);
+  TG_TRY(gw_stage_bump(S1, t1));
   m_mix.reset();
-  // ---- stage 2: K = M^T (A M), operand rows = the loose rows of the intermediate (FE row r -> r - a_row0)
-  gw_args P2;
-  P2.x_rowptr = mt->rowptr;
-  P2.x_col = mt->col;
-  P2.x_val = mt->val;
-  P2.x_nrows = mt->nrows;
-  P2.row_stride = 1;
-  P2.y_start_mix = nullptr;
-  P2.y_start = t1.off;
-  P2.y_cnt = am_cnt;
-  P2.y_mix = (const uint32_t *)t1.tcol.get();
-  P2.y_val = t1.tval;
-  P2.y_row0 = a_row0;
-  P2.y_nrows = a->nrows;
-  P2.debug = P1.debug & ~1;
-  P2.out_stride = 0;
-  P2.rows_per_wave = tg_env_int("TIGAR_PTAP_WAVE_RPW2", 2);
-  gw_tile_hint(P2, "TIGAR_PTAP_WAVE_TILE2");
-  const int64_t nrows = mt->nrows;
+  // ---- stage 2: rows placed by the plan's row pointer, or through a temporary whose scanned counts are the pattern
+  // remembered for later calls with the same operands' structure
+  gw_stage S2 = gw_describe_k(sw, plan, mt, t1, am_cnt, a_row0, a->nrows, mask, diag, mt_row0);
+  tg_csr_s *k = nullptr;
+  int rc;
   if (plan->k_nnz >= 0) {
-    // ---- pattern known: rows are placed directly
-    rc = tg_csr_alloc(nrows, m->ncols, plan->k_nnz, &k);
-    if (!rc) {
-      hipMemcpyAsync(k->rowptr, plan->k_rowptr, (size_t)(nrows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream);
-      P2.ts = plan->ts_k;
-      P2.lgts = tg_lg(plan->ts_k);
-      hipMemsetAsync(status, 0, 4 * sizeof(int), g_tg.stream);
-      gw_launch<GW_PLACED, true>(plan->lg_am, gw_grid(nrows, P2.rows_per_wave), 4 * gw_wave_bytes(P2.ts), P2, k->rowptr, nullptr,
-                                 nullptr, (uint32_t *)k->col, k->val, nullptr, 0, mask, diag, mt_row0, status, sum);
-      int h = 0;
-      hipMemcpyAsync(&h, status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream);
-      if (hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-        tg_set_error("PtAP (wave kernels): numeric pass (placed) failed to run");
-        rc = 1;
-      } else if (h == GW_RANGE) {
-        tg_set_error("PtAP: a row block does not cover the rows referenced (slab halo too small)");
-        rc = 3;
-      } else if (h != GW_OK) {
-        tg_set_error("PtAP numeric: operands no longer match the plan's pattern (status %d)", h);
-        rc = 4;
-      }
-    }
+    rc = gw_stage_placed(S2, plan, m->ncols, &k);
   } else {
-    tg_bump t2("wave kernels, Mt (A M)");
-    int64_t stride2 = (plan->max_k <= 2.0 * plan->mean_k + 32.0 && tg_env_int("TIGAR_PTAP_WAVE_STRIDED", 1)) ? ((plan->max_k + 7) & ~7) : 0;
-    t2.capacity = stride2 ? stride2 * nrows : (int64_t)(plan->mean_k * 1.05 * (double)nrows) + plan->max_k + 1024;
-    rc = t2.init(nrows, true, 2, 4);
-    if (!rc)
-      rc = t2.run(
-          6,
-          [&](int) {
-            P2.ts = t2.ts[0] = plan->ts_k;
-            P2.lgts = tg_lg(plan->ts_k);
-            P2.out_stride = stride2;
-            lds = 4 * gw_wave_bytes(P2.ts);
-            if (lds > 160 * 1024) return 100;
-            gw_launch<GW_BUMP, true>(plan->lg_am, gw_grid(nrows, P2.rows_per_wave), lds, P2, t2.off, nullptr, t2.cnt,
-                                     (uint32_t *)t2.tcol.get(), t2.tval, t2.cursor, t2.capacity, mask, diag, mt_row0, status, sum);
-            return 0;
-          },
-          [&](int, const int *h, unsigned long long used) {
-            if (h[0] == GW_RANGE) {
-              tg_set_error("PtAP: a row block does not cover the rows referenced (slab halo too small)");
-              return 3;
-            }
-            if (h[0] == GW_OK) return (int)TG_BUMP_DONE;
-            if (h[0] == GW_OVF) {
-              plan->ts_k *= 2;
-              if (!stride2) t2.capacity = std::max<int64_t>(t2.capacity, (int64_t)used + 1024);
-            } else if (stride2) {
-              const int hm = h[1];
-              plan->max_k = std::max(plan->max_k, hm);
-              stride2 = (std::max<int64_t>(hm, stride2 + stride2 / 4) + 7) & ~(int64_t)7;
-              t2.capacity = stride2 * nrows;
-            } else {
-              t2.capacity = std::max<int64_t>((int64_t)used + 1024, t2.capacity + t2.capacity / 2);
-            }
-            return (int)TG_BUMP_RETRY;
-          });
-    if (rc == TG_BUMP_NORUN) {
-      tg_set_error("PtAP (wave kernels): stage M^T (A M) failed to run (LDS %zu B)", lds);
-      rc = 1;
-    }
-    if (rc == TG_BUMP_RETRY) rc = 100;
-    // the scanned counts are the pattern remembered for later calls with the same operands' structure
+    tg_bump t2(S2.site);
+    rc = gw_stage_bump(S2, t2);
     if (!rc) rc = t2.finish_csr("PtAP", m->ncols, &k, &plan->k_rowptr, &plan->k_nnz);
-    hipStreamSynchronize(g_tg.stream);
   }
   hipStreamSynchronize(g_tg.stream);
   if (rc) {
@@ -763,6 +841,7 @@ int tg_ptap_wave_numeric(tg_gw_plan *plan, tg_csr_s *a, int64_t a_row0, tg_csr_s
   *k_out = k;
   return 0;
 }
+
 
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -994,11 +1073,51 @@ __global__ void __launch_bounds__(256) k_cell_check(const int64_t *__restrict__ 
   if (wrong) atomicMax(bad, 1);
 }
 
-// md_host == nullptr: the dense rows of M are filled in on the device afterwards (tg_cellplan_create_from_rows)
-static int tg_cellplan_create_common(int64_t ncell, int b, int nfmax, int64_t ncols, const double *md_host, const int32_t *fl_host,
-                                     const int32_t *nf_host, tg_csr_t incidence, int max_k, double mean_k, tg_cellplan_t *out) {
+// ---- the kernel table: one row per instantiation of a templated kernel of this file, in the order in which the
+// instantiations are to be emitted (k_gw: mode, final, shared, lanes; the cell kernels: lanes)
+#define GW_ROW(MODE, FINAL, SHARED, LG) {MODE, FINAL, SHARED, LG, k_gw<MODE, FINAL, LG, SHARED>, nullptr, nullptr}
+#define GW_ROWS(MODE, FINAL, SHARED) \
+  GW_ROW(MODE, FINAL, SHARED, 3), GW_ROW(MODE, FINAL, SHARED, 4), GW_ROW(MODE, FINAL, SHARED, 5), GW_ROW(MODE, FINAL, SHARED, 6)
+static const gw_route g_gw_routes[] = {
+    GW_ROWS(GW_COUNT, false, false),
+    GW_ROWS(GW_BUMP, false, false),
+    GW_ROWS(GW_BUMP, true, false),
+    GW_ROWS(GW_PLACED, true, false),
+    {GW_CELL_ELEMENT, false, false, 3, nullptr, k_cell_element<3>, nullptr},
+    {GW_CELL_ELEMENT, false, false, 4, nullptr, k_cell_element<4>, nullptr},
+    {GW_CELL_ELEMENT, false, false, 5, nullptr, k_cell_element<5>, nullptr},
+    {GW_CELL_ELEMENT, false, false, 6, nullptr, k_cell_element<6>, nullptr},
+    {GW_CELL_MERGE, false, false, 4, nullptr, nullptr, k_cell_merge<4>},
+    {GW_CELL_MERGE, false, false, 5, nullptr, nullptr, k_cell_merge<5>},
+    {GW_CELL_MERGE, false, false, 6, nullptr, nullptr, k_cell_merge<6>},
+    GW_ROWS(GW_PLACED, true, true),
+    GW_ROWS(GW_BUMP, true, true),
+};
+#undef GW_ROWS
+#undef GW_ROW
+
+// the row of (mode, final, shared, lanes), lanes outside 3 .. 5 counting as 6; null: not instantiated
+static const gw_route *gw_route_find(int mode, bool final, bool shared, int lg) {
+  if (lg < 3 || lg > 5) lg = 6;
+  for (const gw_route &r : g_gw_routes)
+    if (r.mode == mode && r.final == final && r.shared == shared && r.lg == lg) return &r;
+  return nullptr;
+}
+
+static void gw_routes_init() {          // every kernel with dynamic LDS may take the 160 KB of a CU
+  static bool done = false;
+  if (done) return;
+  for (const gw_route &r : g_gw_routes) {
+    const void *fn = r.row ? (const void *)r.row : (const void *)r.element;
+    if (fn) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  }
+  done = true;
+}
+
+extern "C" int tg_cellplan_create(int64_t ncell, int b, int nfmax, int64_t ncols, const double *md_host, const int32_t *fl_host,
+                                  const int32_t *nf_host, tg_csr_t incidence, int max_k, double mean_k, tg_cellplan_t *out) {
   TG_REQUIRE_INIT();
-  TG_REQUIRE(ncell > 0 && b >= 1 && b <= 64 && nfmax >= 1 && nfmax <= 64 && fl_host && nf_host && incidence && out,
+  TG_REQUIRE(ncell > 0 && b >= 1 && b <= 64 && nfmax >= 1 && nfmax <= 64 && md_host && fl_host && nf_host && incidence && out,
              "bad arguments to tg_cellplan_create");
   TG_REQUIRE(incidence->nrows == ncols && incidence->ncols == ncell * nfmax, "tg_cellplan_create: incidence of the wrong shape");
   tg_cellplan_s *pl = new tg_cellplan_s();
@@ -1024,10 +1143,7 @@ static int tg_cellplan_create_common(int64_t ncell, int b, int nfmax, int64_t nc
   int rc = tg_dmalloc(&pl->md, ncell * (int64_t)b * nfmax) || tg_dmalloc(&pl->flmix, nrowsE + TG_CSR_PAD) || tg_dmalloc(&pl->nf, ncell) ||
            tg_dmalloc(&pl->e_start, nrowsE) || tg_dmalloc(&pl->e_start_mix, nrowsE) || tg_dmalloc(&pl->e_cnt, nrowsE);
   if (!rc) {
-    if (md_host)
-      hipMemcpyAsync(pl->md, md_host, (size_t)(ncell * (int64_t)b * nfmax) * sizeof(double), hipMemcpyHostToDevice, g_tg.stream);
-    else
-      hipMemsetAsync(pl->md, 0, (size_t)(ncell * (int64_t)b * nfmax) * sizeof(double), g_tg.stream);
+    hipMemcpyAsync(pl->md, md_host, (size_t)(ncell * (int64_t)b * nfmax) * sizeof(double), hipMemcpyHostToDevice, g_tg.stream);
     hipMemsetAsync(pl->flmix, 0, (size_t)(nrowsE + TG_CSR_PAD) * sizeof(uint32_t), g_tg.stream);
     hipMemcpyAsync(pl->flmix, mix.data(), mix.size() * sizeof(uint32_t), hipMemcpyHostToDevice, g_tg.stream);
     hipMemcpyAsync(pl->nf, nf_host, (size_t)ncell * sizeof(int32_t), hipMemcpyHostToDevice, g_tg.stream);
@@ -1049,12 +1165,6 @@ static int tg_cellplan_create_common(int64_t ncell, int b, int nfmax, int64_t nc
   return 0;
 }
 
-extern "C" int tg_cellplan_create(int64_t ncell, int b, int nfmax, int64_t ncols, const double *md_host, const int32_t *fl_host,
-                                  const int32_t *nf_host, tg_csr_t incidence, int max_k, double mean_k, tg_cellplan_t *out) {
-  TG_REQUIRE(md_host, "bad arguments to tg_cellplan_create");
-  return tg_cellplan_create_common(ncell, b, nfmax, ncols, md_host, fl_host, nf_host, incidence, max_k, mean_k, out);
-}
-
 extern "C" int tg_cellplan_destroy(tg_cellplan_t pl) {
   if (!pl) return 0;
   if (g_tg.ready) hipStreamSynchronize(g_tg.stream);
@@ -1071,217 +1181,149 @@ extern "C" int tg_cellplan_destroy(tg_cellplan_t pl) {
   return 0;
 }
 
-template <int MODE>
-static void gw_launch_shared(int lg, unsigned grid, size_t lds, const gw_args &P, int64_t *out_off, int64_t *row_cnt, uint32_t *ocol,
-                             double *oval, unsigned long long *cursor, int64_t capacity, const uint8_t *mask, double diag, int *status,
-                             unsigned long long *sum) {
-#define GW_GOS(LGV)                                                                                                                  \
-  do {                                                                                                                               \
-    hipFuncSetAttribute((const void *)k_gw<MODE, true, LGV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);          \
-    hipLaunchKernelGGL((k_gw<MODE, true, LGV, true>), dim3(grid), dim3(256), lds, g_tg.stream, P, out_off, (int32_t *)nullptr, row_cnt, \
-                       ocol, oval, cursor, capacity, mask, diag, (int64_t)0, status, status + 1, sum);                               \
-  } while (0)
-  switch (lg) {
-    case 3: GW_GOS(3); break;
-    case 4: GW_GOS(4); break;
-    case 5: GW_GOS(5); break;
-    default: GW_GOS(6); break;
+// ---- the steps of a cell-block product (tg_cellplan_ptap_impl) ----
+// A consists of dense b x b blocks on the diagonal alone: 0, or 100 (the general kernels)
+static int cell_check_blocks(tg_cellplan_t pl, tg_csr_t a) {
+  const int64_t nfe = pl->ncell * pl->b;
+  int *status = (int *)g_tg.scratch;
+  int hbad = 0;
+  TG_CHECK_HIP(hipMemsetAsync(status, 0, 4 * sizeof(int), g_tg.stream));
+  hipLaunchKernelGGL(k_cell_check, dim3((unsigned)std::min<int64_t>(tg_cdiv(nfe, 256), (int64_t)g_tg.num_cu * 16)), dim3(256), 0,
+                     g_tg.stream, a->rowptr, a->col, nfe, pl->b, status);
+  TG_LAUNCH_CHECK();
+  TG_CHECK_HIP(hipMemcpyAsync(&hbad, status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream));
+  TG_CHECK_HIP(hipStreamSynchronize(g_tg.stream));
+  return hbad ? 100 : 0;
+}
+
+// E_c = M_c^T (A_c M_c) for every cell: four cells per workgroup, or one where four do not fit the LDS (those read the
+// blocks alone: 100 when `a` holds other entries besides, rstart != null)
+static int cell_element_matrices(tg_cellplan_t pl, tg_csr_t a, const int64_t *rstart, double *eval) {
+  const size_t lds = 4 * ((size_t)pl->b * pl->b + 2 * (size_t)pl->b * pl->nfmax) * sizeof(double);
+  if (lds > 160 * 1024 && rstart) return 100;
+  if (lds > 160 * 1024) {
+    hipLaunchKernelGGL(k_cell_element_big, dim3((unsigned)std::min<int64_t>(pl->ncell, (int64_t)g_tg.num_cu * 64)), dim3(256), 0,
+                       g_tg.stream, a->val, pl->md, pl->nf, pl->ncell, pl->b, pl->nfmax, eval);
+  } else {
+    const int lgf = pl->nfmax <= 8 ? 3 : pl->nfmax <= 16 ? 4 : pl->nfmax <= 32 ? 5 : 6;
+    hipLaunchKernelGGL(gw_route_find(GW_CELL_ELEMENT, false, false, lgf)->element, dim3((unsigned)tg_cdiv(pl->ncell, 4)), dim3(256),
+                       lds, g_tg.stream, a->val, rstart, pl->md, pl->nf, pl->ncell, pl->b, pl->nfmax, eval);
   }
-#undef GW_GOS
+  if (hipGetLastError() != hipSuccess) {
+    tg_set_error("cell-block PtAP: the element kernel failed to launch");
+    return 1;
+  }
+  return 0;
+}
+
+// values of K by places (k_cell_merge) into an allocated k with its row pointer and columns set
+static int cell_merge_by_places(tg_cellplan_t pl, const double *eval, const uint8_t *mask, double diag, tg_csr_s *k) {
+  const int64_t nrows = pl->ncols;
+  const unsigned grid = (unsigned)std::min<int64_t>(tg_cdiv(nrows, 4), (int64_t)g_tg.num_cu * 32);
+  const int lgr = pl->nfmax <= 16 ? 4 : pl->nfmax <= 32 ? 5 : 6;
+  hipLaunchKernelGGL(gw_route_find(GW_CELL_MERGE, false, false, lgr)->merge, dim3(std::max(1u, grid)), dim3(256), 0, g_tg.stream,
+                     pl->inc->rowptr, pl->inc->col, eval, pl->slot, pl->nf, pl->nfmax, nrows, k->rowptr, k->col, mask, diag, k->val);
+  if (hipGetLastError() != hipSuccess) {
+    tg_set_error("cell-block PtAP: the merge kernel failed to launch");
+    return 1;
+  }
+  return 0;
+}
+
+// pattern and places known: no look-up at all
+static int cell_gather_by_places(tg_cellplan_t pl, const double *eval, const uint8_t *mask, double diag, tg_csr_s **k) {
+  const tg_gw_plan *plan = &pl->gw;
+  TG_TRY(tg_csr_alloc(pl->ncols, pl->ncols, plan->k_nnz, k));
+  TG_CHECK_HIP(hipMemcpyAsync((*k)->rowptr, plan->k_rowptr, (size_t)(pl->ncols + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream));
+  TG_CHECK_HIP(hipMemcpyAsync((*k)->col, pl->k_col, (size_t)plan->k_nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, g_tg.stream));
+  TG_TRY(cell_merge_by_places(pl, eval, mask, diag, *k));
+  if (hipStreamSynchronize(g_tg.stream) != hipSuccess) {
+    tg_set_error("cell-block PtAP: merge by places failed to run");
+    return 1;
+  }
+  return 0;
+}
+
+// K rows by look-up: the second Gustavson stage over the rows of the element matrices, which share their cell's column list
+static gw_stage cell_describe_gather(tg_cellplan_t pl, const double *eval, const uint8_t *mask, double diag) {
+  gw_stage S;
+  S.site = "cell-block gather";
+  S.who = "cell-block PtAP";
+  S.name = "the gather stage";
+  S.P = gw_args_outer(pl->inc);
+  gw_operand_loose(S.P, pl->e_start, pl->e_cnt, pl->flmix, eval, 0, pl->ncell * pl->nfmax, pl->e_start_mix);
+  S.P.rows_per_wave = 2;
+  S.out.mask = mask;
+  S.out.diag = diag;
+  S.lg = pl->gw.lg_am;
+  S.ts = &pl->gw.ts_k;
+  S.max_len = &pl->gw.max_k;
+  S.mean = pl->gw.mean_k;
+  S.shared = true;
+  S.slack = 1024;
+  S.headroom = 1.05;
+  S.stride_forced = true;       // (the plan knows the longest row of K from all rows, not from a sample)
+  return S;
+}
+
+// After the first product: the places of the element entries in their rows of K, for all later products -- and for THIS
+// one: its values are formed again by places, so that every product on the plan adds in the same order (bit for bit the
+// same K).  A row too long for the accumulators of k_cell_merge, or no memory: the look-up merge stays.
+static int cell_record_places(tg_cellplan_t pl, const double *eval, const uint8_t *mask, double diag, tg_csr_s *k) {
+  const int64_t nnz = pl->gw.k_nnz, nslot = pl->ncell * pl->nfmax * pl->nfmax;
+  if (pl->gw.max_k >= (pl->nfmax > 32 ? TG_CELL_ROWCAP : 256) || nnz >= 0x7fffffffll * 4) return 0;
+  tg_dfree(pl->k_col);
+  tg_dfree(pl->slot);
+  pl->k_col = nullptr;
+  pl->slot = nullptr;
+  int *bad = (int *)g_tg.scratch + 3;
+  int hbad = 0;
+  if (!tg_dmalloc(&pl->k_col, nnz + TG_CSR_PAD) && !tg_dmalloc(&pl->slot, nslot + 16)) {
+    hipMemcpyAsync(pl->k_col, k->col, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, g_tg.stream);
+    hipMemsetAsync(bad, 0, sizeof(int), g_tg.stream);
+    hipLaunchKernelGGL(k_cell_slots, dim3((unsigned)std::min<int64_t>(tg_cdiv(nslot, 256), (int64_t)g_tg.num_cu * 32)), dim3(256), 0,
+                       g_tg.stream, pl->flmix, pl->nf, pl->ncell, pl->nfmax, k->rowptr, k->col, pl->slot, bad);
+    hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream);
+    if (hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) hbad = 1;
+  } else
+    hbad = 1;
+  if (!hbad) return cell_merge_by_places(pl, eval, mask, diag, k);
+  tg_dfree(pl->k_col);
+  tg_dfree(pl->slot);
+  pl->k_col = nullptr;
+  pl->slot = nullptr;
+  return 0;
 }
 
 // rstart (device, one entry per FE row, or null): where the b values of the row's own cell block start in a->val -- for a
 // matrix that holds other entries besides its dense cell blocks (tg_cellplan_ptap_extras); null: a is verified to consist of
 // the blocks alone
-// trusted: a->val IS the array of dense blocks [ncell][b][b] (tg_elemsplit_ptap: written by this library), nothing else of
-// `a` is looked at
 static int tg_cellplan_ptap_impl(tg_cellplan_t pl, tg_csr_t a, const int64_t *rstart, const int32_t *zero_dofs, int64_t nzero,
-                                 double diag, tg_csr_t *k_out, bool trusted = false) {
+                                 double diag, tg_csr_t *k_out) {
+  const gw_switches sw = gw_switches_read();
   const int64_t nfe = pl->ncell * pl->b;
-  if (!trusted && (a->nrows != nfe || a->ncols != nfe || (!rstart && a->nnz != nfe * pl->b))) return 100;
-  int *status = (int *)g_tg.scratch;
-  unsigned long long *sum = (unsigned long long *)(status + 2);
-  if (!rstart && !trusted) {
-    int hbad = 0;
-    hipMemsetAsync(status, 0, 4 * sizeof(int), g_tg.stream);
-    hipLaunchKernelGGL(k_cell_check, dim3((unsigned)std::min<int64_t>(tg_cdiv(nfe, 256), (int64_t)g_tg.num_cu * 16)), dim3(256), 0,
-                       g_tg.stream, a->rowptr, a->col, nfe, pl->b, status);
-    TG_LAUNCH_CHECK();
-    TG_CHECK_HIP(hipMemcpyAsync(&hbad, status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream));
-    TG_CHECK_HIP(hipStreamSynchronize(g_tg.stream));
-    if (hbad) return 100;                     // not block diagonal with dense b x b blocks: the general kernels
-  }
+  if (a->nrows != nfe || a->ncols != nfe || (!rstart && a->nnz != nfe * pl->b)) return 100;
+  gw_routes_init();
+  if (!rstart) TG_TRY(cell_check_blocks(pl, a));
   tg_dbuf<uint8_t> mask;
   if (nzero > 0) TG_TRY(tg_build_dof_mask(zero_dofs, nzero, pl->ncols, &mask.p));
   tg_dbuf<double> eval;
-  tg_csr_s *k = nullptr;
-  const int64_t nrowsE = pl->ncell * pl->nfmax;
-  TG_TRY(eval.alloc(nrowsE * pl->nfmax + TG_CSR_PAD));
-  int rc = 0;
-  // ---- element matrices
-  {
-    const size_t lds = 4 * ((size_t)pl->b * pl->b + 2 * (size_t)pl->b * pl->nfmax) * sizeof(double);
-    const unsigned grid = (unsigned)tg_cdiv(pl->ncell, 4);
-    const int lgf = tg_lg(pl->nfmax <= 8 ? 8 : pl->nfmax <= 16 ? 16 : pl->nfmax <= 32 ? 32 : 64);
-#define CELL_GO(LGV)                                                                                                    \
-  do {                                                                                                                  \
-    hipFuncSetAttribute((const void *)k_cell_element<LGV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);      \
-    hipLaunchKernelGGL((k_cell_element<LGV>), dim3(grid), dim3(256), lds, g_tg.stream, a->val, rstart, pl->md, pl->nf,   \
-                       pl->ncell, pl->b, pl->nfmax, eval.get());                                                        \
-  } while (0)
-    if (lds > 160 * 1024 && rstart) return 100;
-    if (lds > 160 * 1024) {
-      hipLaunchKernelGGL(k_cell_element_big, dim3((unsigned)std::min<int64_t>(pl->ncell, (int64_t)g_tg.num_cu * 64)), dim3(256), 0,
-                         g_tg.stream, a->val, pl->md, pl->nf, pl->ncell, pl->b, pl->nfmax, eval.get());
-    } else
-    switch (lgf) {
-      case 3: CELL_GO(3); break;
-      case 4: CELL_GO(4); break;
-      case 5: CELL_GO(5); break;
-      default: CELL_GO(6); break;
-    }
-#undef CELL_GO
-    if (hipGetLastError() != hipSuccess) {
-      tg_set_error("cell-block PtAP: the element kernel failed to launch");
-      return 1;
-    }
-  }
-  // ---- K rows: the second Gustavson stage over the rows of the element matrices
-  gw_set_lds_limits();
-  gw_args P2;
-  memset(&P2, 0, sizeof(P2));
-  P2.x_rowptr = pl->inc->rowptr;
-  P2.x_col = pl->inc->col;
-  P2.x_val = pl->inc->val;
-  P2.x_nrows = pl->inc->nrows;
-  P2.row_stride = 1;
-  P2.y_start = pl->e_start;
-  P2.y_start_mix = pl->e_start_mix;
-  P2.y_cnt = pl->e_cnt;
-  P2.y_mix = pl->flmix;
-  P2.y_val = eval;
-  P2.y_row0 = 0;
-  P2.y_nrows = nrowsE;
-  P2.rows_per_wave = 2;
-  P2.t0 = P2.t1 = P2.t2 = 1;
-  const int64_t nrows = pl->ncols;
+  TG_TRY(eval.alloc(pl->ncell * pl->nfmax * pl->nfmax + TG_CSR_PAD));
+  TG_TRY(cell_element_matrices(pl, a, rstart, eval));
   tg_gw_plan *plan = &pl->gw;
-  // values of K by places (k_cell_merge) into an allocated k with its row pointer and columns set
-  auto merge_by_places = [&](tg_csr_s *kk) -> int {
-    const unsigned grid = (unsigned)std::min<int64_t>(tg_cdiv(nrows, 4), (int64_t)g_tg.num_cu * 32);
-#define CELL_MERGE(LGV)                                                                                                         \
-  hipLaunchKernelGGL((k_cell_merge<LGV>), dim3(std::max(1u, grid)), dim3(256), 0, g_tg.stream, pl->inc->rowptr, pl->inc->col,       \
-                     eval.get(), pl->slot, pl->nf, pl->nfmax, nrows, kk->rowptr, kk->col, mask.get(), diag, kk->val)
-    if (pl->nfmax <= 16) CELL_MERGE(4);
-    else if (pl->nfmax <= 32) CELL_MERGE(5);
-    else CELL_MERGE(6);
-#undef CELL_MERGE
-    if (hipGetLastError() != hipSuccess) {
-      tg_set_error("cell-block PtAP: the merge kernel failed to launch");
-      return 1;
-    }
-    return 0;
-  };
-  if (plan->k_nnz >= 0 && pl->slot && pl->k_col && !getenv("TIGAR_CELL_MERGE_HASH")) {
-    // ---- pattern and places known: no look-up at all
-    rc = tg_csr_alloc(nrows, pl->ncols, plan->k_nnz, &k);
-    if (!rc) {
-      hipMemcpyAsync(k->rowptr, plan->k_rowptr, (size_t)(nrows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream);
-      hipMemcpyAsync(k->col, pl->k_col, (size_t)plan->k_nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, g_tg.stream);
-      rc = merge_by_places(k);
-      if (!rc && hipStreamSynchronize(g_tg.stream) != hipSuccess) {
-        tg_set_error("cell-block PtAP: merge by places failed to run");
-        rc = 1;
-      }
-    }
-  } else if (plan->k_nnz >= 0) {
-    rc = tg_csr_alloc(nrows, pl->ncols, plan->k_nnz, &k);
-    if (!rc) {
-      hipMemcpyAsync(k->rowptr, plan->k_rowptr, (size_t)(nrows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream);
-      P2.ts = plan->ts_k;
-      P2.lgts = tg_lg(plan->ts_k);
-      hipMemsetAsync(status, 0, 4 * sizeof(int), g_tg.stream);
-      gw_launch_shared<GW_PLACED>(plan->lg_am, gw_grid(nrows, P2.rows_per_wave), 4 * gw_wave_bytes(P2.ts), P2, k->rowptr, nullptr,
-                                  (uint32_t *)k->col, k->val, nullptr, 0, mask, diag, status, sum);
-      int h = 0;
-      hipMemcpyAsync(&h, status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream);
-      if (hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-        tg_set_error("cell-block PtAP: numeric pass (placed) failed to run");
-        rc = 1;
-      } else if (h != GW_OK) {
-        tg_set_error("cell-block PtAP: the operands no longer match the plan's pattern (status %d)", h);
-        rc = 4;
-      }
-    }
+  tg_csr_s *k = nullptr;
+  int rc;
+  if (plan->k_nnz >= 0 && pl->slot && pl->k_col && !sw.cell_merge_hash) {
+    rc = cell_gather_by_places(pl, eval, mask, diag, &k);
   } else {
-    tg_bump t("cell-block gather");
-    int64_t stride2 = (plan->max_k + 7) & ~7;
-    t.capacity = stride2 * nrows;
-    rc = t.init(nrows, true, 2, 4);
-    size_t lds = 0;
-    if (!rc)
-      rc = t.run(
-          6,
-          [&](int) {
-            P2.ts = t.ts[0] = plan->ts_k;
-            P2.lgts = tg_lg(plan->ts_k);
-            P2.out_stride = stride2;
-            lds = 4 * gw_wave_bytes(P2.ts);
-            if (lds > 160 * 1024) return 100;
-            gw_launch_shared<GW_BUMP>(plan->lg_am, gw_grid(nrows, P2.rows_per_wave), lds, P2, t.off, t.cnt, (uint32_t *)t.tcol.get(), t.tval,
-                                      t.cursor, t.capacity, mask, diag, status, sum);
-            return 0;
-          },
-          [&](int, const int *h, unsigned long long) {
-            if (h[0] == GW_OK) return (int)TG_BUMP_DONE;
-            if (h[0] == GW_OVF)
-              plan->ts_k *= 2;
-            else if (h[0] == GW_CAP) {
-              plan->max_k = std::max(plan->max_k, h[1]);
-              stride2 = (std::max<int64_t>(h[1], stride2 + stride2 / 4) + 7) & ~(int64_t)7;
-              t.capacity = stride2 * nrows;
-            } else {
-              tg_set_error("cell-block PtAP: kernel status %d", h[0]);
-              return 4;
-            }
-            return (int)TG_BUMP_RETRY;
-          });
-    if (rc == TG_BUMP_NORUN) {
-      tg_set_error("cell-block PtAP: the gather stage failed to run (LDS %zu B)", lds);
-      rc = 1;
-    }
-    if (rc == TG_BUMP_RETRY) rc = 100;
-    if (!rc) {
-      rc = t.finish_csr("cell-block PtAP:", pl->ncols, &k, &plan->k_rowptr, &plan->k_nnz);
-      if (!rc) {
-        const int64_t nnz = plan->k_nnz;
-        // the places of the element entries in their rows of K, for all later products -- and for THIS one: its values
-        // are formed again by places, so that every product on the plan adds in the same order (bit for bit the same K)
-        if (plan->max_k < (pl->nfmax > 32 ? TG_CELL_ROWCAP : 256) && nnz < 0x7fffffffll * 4 && !getenv("TIGAR_CELL_MERGE_HASH")) {
-          tg_dfree(pl->k_col);
-          tg_dfree(pl->slot);
-          pl->k_col = nullptr;
-          pl->slot = nullptr;
-          int *bad = status + 3;
-          int hbad2 = 0;
-          if (!tg_dmalloc(&pl->k_col, nnz + TG_CSR_PAD) && !tg_dmalloc(&pl->slot, nrowsE * pl->nfmax + 16)) {
-            hipMemcpyAsync(pl->k_col, k->col, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, g_tg.stream);
-            hipMemsetAsync(bad, 0, sizeof(int), g_tg.stream);
-            hipLaunchKernelGGL(k_cell_slots, dim3((unsigned)std::min<int64_t>(tg_cdiv(nrowsE * pl->nfmax, 256), (int64_t)g_tg.num_cu * 32)),
-                               dim3(256), 0, g_tg.stream, pl->flmix, pl->nf, pl->ncell, pl->nfmax, k->rowptr, k->col, pl->slot, bad);
-            hipMemcpyAsync(&hbad2, bad, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream);
-            if (hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) hbad2 = 1;
-          } else
-            hbad2 = 1;
-          if (hbad2) {                       // (a row of more than 255 entries, or no memory: the look-up merge stays)
-            tg_dfree(pl->k_col);
-            tg_dfree(pl->slot);
-            pl->k_col = nullptr;
-            pl->slot = nullptr;
-          } else
-            rc = merge_by_places(k);
-        }
-      }
+    gw_stage S = cell_describe_gather(pl, eval, mask, diag);
+    if (plan->k_nnz >= 0) {
+      rc = gw_stage_placed(S, plan, pl->ncols, &k);
+    } else {
+      tg_bump t(S.site);
+      rc = gw_stage_bump(S, t);
+      if (!rc) rc = t.finish_csr("cell-block PtAP:", pl->ncols, &k, &plan->k_rowptr, &plan->k_nnz);
+      if (!rc && !sw.cell_merge_hash) rc = cell_record_places(pl, eval, mask, diag, k);
     }
   }
   hipStreamSynchronize(g_tg.stream);
@@ -1353,29 +1395,21 @@ extern "C" int tg_cellplan_ptap_extras(tg_cellplan_t pl, tg_csr_t a, tg_csr_t *k
   TG_REQUIRE_CANONICAL(a);
   const int64_t n = pl->ncell * pl->b;
   if (a->nrows != n || a->ncols != n) return 100;
-  int64_t *len_r = nullptr, *rstart = nullptr;
-  int *bad = nullptr;
+  tg_dbuf<int64_t> len_r, rstart;
+  tg_dbuf<int> bad;
   tg_csr_s *mr = nullptr;
-  int rc = tg_dmalloc(&len_r, n + 1) || tg_dmalloc(&rstart, n) || tg_dmalloc(&bad, 4);
+  int rc = len_r.alloc(n + 1) || rstart.alloc(n) || bad.alloc(4);
   int h_bad = 0;
   int64_t tot_r = 0;
-  auto cleanup = [&]() {
-    tg_dfree(len_r);
-    tg_dfree(rstart);
-    tg_dfree(bad);
-  };
   if (!rc) {
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tg_cdiv(n, 4), (int64_t)g_tg.num_cu * 16));
     hipMemsetAsync(bad, 0, sizeof(int), g_tg.stream);
-    hipLaunchKernelGGL(k_cellx_count, dim3(grid), dim3(256), 0, g_tg.stream, a->rowptr, a->col, pl->b, n, len_r, rstart, bad);
+    hipLaunchKernelGGL(k_cellx_count, dim3(grid), dim3(256), 0, g_tg.stream, a->rowptr, a->col, pl->b, n, len_r.get(), rstart.get(), bad.get());
     if (hipGetLastError() != hipSuccess) rc = 1;
     if (!rc && hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess) rc = 1;
   }
   if (!rc) rc = tg_exclusive_scan_i64(len_r, n, &tot_r);          // (synchronises: h_bad is valid afterwards)
-  if (!rc && h_bad) {
-    cleanup();
-    return 100;                                                    // a row lacks entries of its own cell block
-  }
+  if (!rc && h_bad) return 100;                                    // a row lacks entries of its own cell block
   if (!rc) rc = tg_csr_alloc(n, n, tot_r, &mr);
   if (!rc) {
     if (hipMemcpyAsync(mr->rowptr, len_r, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream) != hipSuccess) rc = 1;
@@ -1388,7 +1422,6 @@ extern "C" int tg_cellplan_ptap_extras(tg_cellplan_t pl, tg_csr_t a, tg_csr_t *k
   tg_csr_t k = nullptr;
   if (!rc) rc = tg_cellplan_ptap_impl(pl, a, rstart, nullptr, 0, 1.0, &k);
   if (hipStreamSynchronize(g_tg.stream) != hipSuccess && !rc) rc = 1;
-  cleanup();
   if (rc) {
     if (mr) tg_csr_destroy(mr);
     if (rc != 100) tg_set_error("tg_cellplan_ptap_extras failed");
@@ -1623,8 +1656,8 @@ extern "C" int tg_foldplan_apply(tg_foldplan_t pl, tg_csr_t ku, const int32_t *z
   unsigned long long sum = 0;
   TG_TRY(fold_checksum(ku, &sum));
   if (sum != pl->u_sum) return 100;
-  uint8_t *mask = nullptr;
-  if (nzero > 0) TG_TRY(tg_build_dof_mask(zero_dofs, nzero, pl->ncols, &mask));
+  tg_dbuf<uint8_t> mask;
+  if (nzero > 0) TG_TRY(tg_build_dof_mask(zero_dofs, nzero, pl->ncols, &mask.p));
   tg_csr_s *k = nullptr;
   int rc = tg_csr_alloc(pl->nrows, pl->ncols, pl->nnz, &k);
   if (!rc) {
@@ -1634,13 +1667,12 @@ extern "C" int tg_foldplan_apply(tg_foldplan_t pl, tg_csr_t ku, const int32_t *z
     hipFuncSetAttribute((const void *)k_fold_apply, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipLaunchKernelGGL(k_fold_apply, dim3((unsigned)std::min<int64_t>(tg_cdiv(std::max<int64_t>(pl->nrows, 1), 4), (int64_t)g_tg.num_cu * 64)),
                        dim3(256), lds, g_tg.stream, pl->rt->rowptr, pl->rt->col, pl->nrows, pl->u_row0, pl->rt_row0, ku->rowptr, ku->val,
-                       pl->place, k->rowptr, k->col, pl->max_k, mask, diag, k->val);
+                       pl->place, k->rowptr, k->col, pl->max_k, mask.get(), diag, k->val);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(g_tg.stream) != hipSuccess) {
       tg_set_error("tg_foldplan_apply: the kernel failed");
       rc = 1;
     }
   }
-  tg_dfree(mask);
   if (rc) {
     if (k) tg_csr_destroy(k);
     return rc;
