@@ -25,7 +25,8 @@ def _operands(d, p, nels, seed=0):
 
 
 @pytest.mark.parametrize("d,p,nels", [(3, 3, (5, 4, 6)), (3, 2, (7, 5, 6)), (2, 3, (17, 12)), (3, 1, (9, 8, 7)), (2, 2, (20, 15)),
-                                      (3, 4, (3, 2, 4)), (2, 5, (7, 6)), (2, 7, (5, 4))])      # (125-node cells: the panel kernel)
+                                      (3, 4, (3, 2, 4)), (2, 5, (7, 6)), (2, 7, (5, 4)),       # (125-node cells: the panel kernel)
+                                      (3, 4, (5, 5, 3))])      # (a function in 75 cells of 125 functions: the two-list merge)
 def test_element_split_product_matches_scipy(d, p, nels):
     from tigar_amd import device as dev
     from tigar_amd.elemptap import ElementSplitPtAP
@@ -112,6 +113,77 @@ def test_an_entry_outside_every_cell_is_declined():
     plan = ElementSplitPtAP(M, cells)
     assert plan.ptap(dev.DeviceCSR.from_scipy(As.tocsr())) is None
     assert plan.ptap(A) is not None
+
+
+def _star(n, seed=0):
+    """a star mesh: n cells of two nodes [0, i], node 0 in every cell; M a random CSR of 2 to 3 entries per row with sorted
+    columns, A random on the couplings of the cells ((0, 0), (0, i), (i, 0), (i, i))"""
+    rng = np.random.default_rng(1000 * n + seed)
+    ncp = 24
+    cells = np.stack([np.zeros(n, dtype=np.int32), np.arange(1, n + 1, dtype=np.int32)], axis=1)
+    rows, cols = [], []
+    for r in range(n + 1):
+        c = np.sort(rng.choice(ncp, size=int(rng.integers(2, 4)), replace=False))
+        rows += [r] * c.size
+        cols += list(c)
+    Ms = sp.csr_matrix((rng.standard_normal(len(rows)), (rows, cols)), shape=(n + 1, ncp))
+    Ms.sort_indices()
+    i = np.arange(1, n + 1)
+    ar = np.concatenate([[0], np.zeros(n, dtype=np.int64), i, i])
+    ac = np.concatenate([[0], i, np.zeros(n, dtype=np.int64), i])
+    As = sp.csr_matrix((rng.standard_normal(ar.size), (ar, ac)), shape=(n + 1, n + 1))
+    As.sort_indices()
+    return cells, Ms, As
+
+
+def test_a_node_in_forty_cells_takes_the_list_tables(monkeypatch, capfd):
+    """node 0 lies in 40 cells (more than the 8 of the node table): the node -> cells lists stay lists and ``k_el_scatter``
+    splits A, chosen by the data alone (the trace line of the product names it); K against scipy, a second product bit for
+    bit the same"""
+    from tigar_amd import device as dev
+    from tigar_amd.elemptap import CellNodes, ElementSplitPtAP
+    cells, Ms, As = _star(40)
+    plan = ElementSplitPtAP(dev.DeviceCSR.from_scipy(Ms), CellNodes.from_host(cells))
+    assert plan.b == 2 and plan._chunk.ninc_max >= 40
+    A = dev.DeviceCSR.from_scipy(As)
+    monkeypatch.setenv("TIGAR_TRACE", "1")
+    capfd.readouterr()
+    K = plan.ptap(A)
+    lines = [ln for ln in capfd.readouterr().err.splitlines() if ln.startswith("[tigar] element split:")]
+    monkeypatch.delenv("TIGAR_TRACE")
+    assert len(lines) == 1 and "split k_el_scatter," in lines[0]
+    assert K is not None
+    Ks = K.to_scipy().tocsr()
+    Ks.sort_indices()
+    ref = (Ms.T @ As @ Ms).tocsr()
+    assert Ks.shape == ref.shape
+    assert abs(Ks - ref).max() <= 1e-12 * abs(ref).max()
+    K2 = plan.ptap(A).to_scipy().tocsr()
+    K2.sort_indices()
+    assert np.array_equal(K2.indptr, Ks.indptr) and np.array_equal(K2.indices, Ks.indices)
+    assert np.array_equal(K2.data.view(np.int64), Ks.data.view(np.int64))
+
+
+def test_a_node_in_seventy_cells_is_declined():
+    """a node in more than 64 cells: the splitting pass declines (``ptap`` returns None), the general kernels give scipy's K"""
+    from tigar_amd import device as dev
+    from tigar_amd.elemptap import CellNodes, ElementSplitPtAP
+    cells, Ms, As = _star(70)
+    M, A = dev.DeviceCSR.from_scipy(Ms), dev.DeviceCSR.from_scipy(As)
+    plan = ElementSplitPtAP(M, CellNodes.from_host(cells))
+    assert plan.ptap(A) is None
+    MT = M.transpose()
+    Kg = dev.ptap_numeric(dev.ptap_symbolic(A, M, MT), A, M, MT).to_scipy().tocsr()
+    ref = (Ms.T @ As @ Ms).tocsr()
+    assert abs(Kg - ref).max() <= 1e-12 * abs(ref).max()
+
+
+def test_a_function_in_more_than_128_cells_does_not_qualify():
+    from tigar_amd import device as dev
+    from tigar_amd.elemptap import CellNodes, ElementChunk
+    cells, Ms, _ = _star(130)
+    with pytest.raises(ValueError):
+        ElementChunk(CellNodes.from_host(cells), dev.DeviceCSR.from_scipy(Ms))
 
 
 @pytest.mark.parametrize("d,p,nel", [(3, 2, 6), (2, 3, 14), (3, 3, 4)])

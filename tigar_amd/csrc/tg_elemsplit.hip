@@ -34,6 +34,8 @@
 // common cell (rows whose cells are all listed) -- the others are some other chunk's to check.
 #include "tg_common.h"
 #include <algorithm>
+#include <initializer_list>
+#include <memory>
 
 #define EL_FLS 128            // stride of a cell's function list: at most 128 functions per cell
 #define EL_INF 0x7fffffff
@@ -70,6 +72,11 @@ struct tg_elemplan_s {
   int64_t *k_rowptr = nullptr;
   int32_t *k_col = nullptr;
   uint16_t *slot = nullptr;      // [nown * S][S]
+  void free_all() {              // the one place that frees the plan's device blocks (tg_elemplan_destroy)
+    for (void *p : {(void *)nptr, (void *)nlist, (void *)nfix, (void *)fl, (void *)nf, (void *)mpos, (void *)iptr, (void *)ient,
+                    (void *)k_rowptr, (void *)k_col, (void *)slot})
+      tg_dfree(p);
+  }
 };
 
 #define EL_WAVE_SYNC()                                   \
@@ -1317,27 +1324,374 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// ---- host side ------------------------------------------------------------------------------------------------------------------
+// ---- host side: owned blocks, named scratch words, one kernel table, the plan and the product in stages --
 // grids of the kernels that renumber their blocks by XCD (tg_xcd_block): a bijection only for multiples of 8
 static inline unsigned el_grid8(int64_t g) { return (unsigned)((std::max<int64_t>(g, 1) + 7) & ~(int64_t)7); }
+
+// owner of a handle under construction: destroyed on every early return, released to the caller at the end
+struct el_drop {
+  void operator()(tg_elemplan_s *p) const { tg_elemplan_destroy(p); }
+  void operator()(tg_csr_s *p) const { tg_csr_destroy(p); }
+};
+template <typename T>
+using el_own = std::unique_ptr<T, el_drop>;
+
 extern "C" int tg_elemplan_destroy(tg_elemplan_t pl) {
   if (!pl) return 0;
   if (g_tg.ready) {
     hipStreamSynchronize(g_tg.stream);
-    tg_dfree(pl->nptr);
-    tg_dfree(pl->nlist);
-    tg_dfree(pl->nfix);
-    tg_dfree(pl->fl);
-    tg_dfree(pl->nf);
-    tg_dfree(pl->mpos);
-    tg_dfree(pl->iptr);
-    tg_dfree(pl->ient);
-    tg_dfree(pl->k_rowptr);
-    tg_dfree(pl->k_col);
-    tg_dfree(pl->slot);
+    pl->free_all();
   }
   delete pl;
   return 0;
+}
+
+// The switches, read at every entry point (the tests change the environment between calls).
+struct el_switches {
+  bool lists;     // TIGAR_EL_LISTS (set to anything): the node -> cells lists even where the table of 8 per node would do
+  int dbg;        // TIGAR_EL_DBG: the number k_el_fl receives
+  bool merge;     // TIGAR_EL_MERGE (set to anything): the pattern by the merge kernel where the hash kernel would do
+  bool valu;      // TIGAR_EL_VALU (set to anything): the register-tile element kernels (A/B runs)
+  bool debug;     // TIGAR_DEBUG (set to anything): why a product was declined
+  bool trace;     // TIGAR_TRACE (set to anything): the rows of g_el_routes a product took
+};
+static el_switches el_switches_read() {
+  el_switches w;
+  w.lists = getenv("TIGAR_EL_LISTS") != nullptr;
+  w.dbg = tg_env_int("TIGAR_EL_DBG", 0);
+  w.merge = getenv("TIGAR_EL_MERGE") != nullptr;
+  w.valu = getenv("TIGAR_EL_VALU") != nullptr;
+  w.debug = getenv("TIGAR_DEBUG") != nullptr;
+  w.trace = getenv("TIGAR_TRACE") != nullptr;
+  return w;
+}
+
+// ---- the words of g_tg.scratch the kernels report in, by phase (int words unless said otherwise).  A phase sets its words,
+// hands their addresses to its kernels and reads them back with el_words_read; no phase relies on what another left, except
+// where said.
+enum el_cells_word {          // tg_elemplan_create: node window, node -> cells, function lists
+  EL_W_NODE_MIN = 0,          // k_el_minmax: smallest / largest node number
+  EL_W_NODE_MAX = 1,
+  EL_W_MROW_MAX = 1,          // ... the same word once the window is read: k_el_maxrow, the longest row of M
+  EL_W_NODE_CELLS = 2,        // k_el_node_sort: the longest node -> cells list (the kernel reaches it as the word before its flag)
+  EL_W_NODE_TWICE = 3,        // k_el_node_sort: a node twice in one cell
+  EL_W_FN_MIN = 4,            // k_el_fl stats[0 .. 3]: smallest / largest function, longest list, EL_FL_* flags
+  EL_W_FN_MAX = 5,
+  EL_W_NF_MAX = 6,
+  EL_W_FL_BAD = 7,
+  EL_W_CELLS = 8              // (words of the phase)
+};
+enum { EL_FL_OUTSIDE = 1, EL_FL_TOO_MANY = 2 };      // EL_W_FL_BAD: a node outside the rows of M / more than EL_FLS functions
+enum el_inc_word {            // tg_elemplan_create: function -> element rows
+  EL_W_NINC_MAX = 0,          // k_el_inc_sort: the longest list
+  EL_W_INC = 4
+};
+enum el_sym_word {            // the symbolic passes
+  EL_W_STATUS = 0,            // k_el_rowsym / k_el_rowhash: EL_SYM_*
+  EL_W_CURSOR = 4,            // ONE unsigned long long (words 4 and 5): entries counted (mode 0) / reserved (mode 1)
+  EL_W_SYM = 8,               // (status and cursor are zeroed together)
+  EL_W_MAX_K = 0              // k_el_reorder: the longest row of K
+};
+enum { EL_SYM_GROW = 1, EL_SYM_TOO_LONG = 2, EL_SYM_WIDEN = 3 };
+enum el_split_word {          // the splitting of A
+  EL_W_COUNTERS = 16,         // FOUR unsigned long long (words 16 .. 23): EL_C_*
+  EL_W_SPLIT = 8
+};
+enum { EL_C_OWN = 0, EL_C_FOREIGN = 1, EL_C_NO_CELL = 2, EL_C_NODE_OVER_64 = 3 };
+
+static inline int *el_word(int w) { return (int *)g_tg.scratch + w; }
+static int el_words_zero(int w, int n) {
+  TG_CHECK_HIP(hipMemsetAsync(el_word(w), 0, (size_t)n * sizeof(int), g_tg.stream));
+  return 0;
+}
+// the pieces (host address, first word, bytes) brought back, the stream waited for and asked for its errors; the caller
+// names the pass in its message
+struct el_piece {
+  void *host;
+  int word;
+  size_t bytes;
+};
+static int el_words_read(std::initializer_list<el_piece> pieces) {
+  for (const el_piece &p : pieces)
+    if (hipMemcpyAsync(p.host, el_word(p.word), p.bytes, hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess) return 1;
+  return hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess;
+}
+
+// ---- the kernel table: one row per kernel of this file that has variants, in the order in which the instantiations are to be
+// emitted.  The key of a row: its stage, the sizes lo .. hi of the stage's measure it serves, and `alt` (-1: any).
+//   EL_FL     measure: nodes per cell b
+//   EL_SPLIT  alt 1: the table of 8 cells per node (plan->nfix), 0: the lists
+//   EL_DENSE  measure: S; alt 1: TIGAR_EL_VALU
+//   EL_SYM    measure: cells per function (ninc_max); alt: keys per lane of the hash kernel, 0 = the merge kernel
+//   EL_MERGE  measure: functions per cell (nfmax)
+enum el_stage { EL_FL, EL_SPLIT, EL_DENSE, EL_SYM, EL_MERGE };
+struct el_launch {            // what a launch takes besides the plan; a stage fills what its kernels read
+  const tg_elemplan_s *pl = nullptr;
+  unsigned grid = 1;
+  int waves = 4;
+  size_t lds = 0;
+  int LD = 0, wave_words = 0, dbg = 0;                                // function lists, symbolic merge
+  const tg_csr_s *a = nullptr;                                        // the splitting
+  int64_t a_row0 = 0, check0 = 0, check1 = 0;
+  double *blocks = nullptr;                                           // splitting, element products, merge
+  int mode = 0;                                                       // symbolic passes
+  int64_t step = 1, phase = 0, cap = 0;
+  int32_t *tcol = nullptr;
+  int64_t *off = nullptr, *cnt = nullptr;
+  uint16_t *slot = nullptr;
+  int capk = 0;                                                       // merge by places
+  const tg_csr_s *k = nullptr;
+  const uint8_t *mask = nullptr;
+  double diag = 1.0;
+};
+struct el_route {
+  const char *name;
+  int stage, lo, hi, alt;
+  const void *fn;
+  bool dyn_lds;               // el_routes_init raises its dynamic-LDS limit
+  int (*launch)(const el_launch &);
+};
+
+template <bool TWO>
+static int el_launch_fl(const el_launch &L) {
+  const tg_elemplan_s *pl = L.pl;
+  hipLaunchKernelGGL((k_el_fl<TWO>), dim3(L.grid), dim3(64 * L.waves), L.lds, g_tg.stream, pl->m->rowptr, pl->m->col, pl->m_row0, pl->m->nrows,
+                     pl->cells->nodes, pl->own0, pl->own1 - pl->own0, pl->b, L.LD, L.wave_words, L.waves, pl->fl, pl->nf, pl->mpos,
+                     el_word(EL_W_FN_MIN), L.dbg);
+  TG_LAUNCH_CHECK();
+  return 0;
+}
+template <bool TWO>
+static int el_launch_rowsym(const el_launch &L) {
+  const tg_elemplan_s *pl = L.pl;
+  hipLaunchKernelGGL((k_el_rowsym<TWO>), dim3(L.grid), dim3(64 * L.waves), L.lds, g_tg.stream, pl->iptr, pl->ient, pl->dof1 - pl->dof0, pl->fl,
+                     pl->nf, pl->S, L.LD, L.wave_words, L.waves, L.mode, L.step, L.phase, L.tcol,
+                     (unsigned long long *)el_word(EL_W_CURSOR), L.cap, L.off, L.cnt, L.slot, el_word(EL_W_STATUS));
+  TG_LAUNCH_CHECK();
+  return 0;
+}
+template <int R>
+static int el_launch_rowhash(const el_launch &L) {
+  const tg_elemplan_s *pl = L.pl;
+  hipLaunchKernelGGL((k_el_rowhash<R>), dim3(L.grid), dim3(64 * L.waves), L.lds, g_tg.stream, pl->iptr, pl->ient, pl->dof1 - pl->dof0, pl->fl,
+                     pl->nf, pl->S, L.waves, L.mode, L.step, L.phase, L.tcol, (unsigned long long *)el_word(EL_W_CURSOR), L.cap, L.off,
+                     L.cnt, L.slot, el_word(EL_W_STATUS));
+  TG_LAUNCH_CHECK();
+  return 0;
+}
+static int el_launch_scatter8(const el_launch &L) {
+  const tg_elemplan_s *pl = L.pl;
+  hipLaunchKernelGGL(k_el_scatter8, dim3(L.grid), dim3(256), 0, g_tg.stream, L.a->rowptr, L.a->col, L.a->val, L.a->nrows, L.a_row0, pl->node0,
+                     pl->nnode, pl->nfix, pl->own0, pl->own1, pl->S, L.check0, L.check1, L.blocks,
+                     (unsigned long long *)el_word(EL_W_COUNTERS));
+  TG_LAUNCH_CHECK();
+  return 0;
+}
+static int el_launch_scatter(const el_launch &L) {
+  const tg_elemplan_s *pl = L.pl;
+  hipLaunchKernelGGL(k_el_scatter, dim3(L.grid), dim3(256), 0, g_tg.stream, L.a->rowptr, L.a->col, L.a->val, L.a->nrows, L.a_row0, pl->node0,
+                     pl->nnode, pl->nptr, pl->nlist, pl->own0, pl->own1, pl->S, L.check0, L.check1, L.blocks,
+                     (unsigned long long *)el_word(EL_W_COUNTERS));
+  TG_LAUNCH_CHECK();
+  return 0;
+}
+template <int TS>
+static int el_launch_dense(const el_launch &L) {
+  const tg_elemplan_s *pl = L.pl;
+  hipLaunchKernelGGL((k_el_dense<TS>), dim3(L.grid), dim3(256), 0, g_tg.stream, L.blocks, pl->S, pl->own1 - pl->own0, pl->cells->nodes, pl->own0,
+                     pl->b, pl->m->rowptr, pl->m->col, pl->m->val, pl->m_row0, pl->fl, pl->nf);
+  return hipGetLastError() != hipSuccess;
+}
+// the panel kernel: M_c and two panels in dynamic LDS, one workgroup per CU (its own grid, not L.grid)
+static int el_launch_dense_big(const el_launch &L) {
+  const tg_elemplan_s *pl = L.pl;
+  const int64_t nown = pl->own1 - pl->own0;
+  const size_t lds = (size_t)(128 * EL_BIG_MS + 16 * 129 + 16 * 128) * sizeof(double);
+  hipLaunchKernelGGL(k_el_dense_big, dim3(el_grid8(std::min<int64_t>(nown, (int64_t)g_tg.num_cu * 8))), dim3(256), lds, g_tg.stream, L.blocks,
+                     pl->S, nown, pl->cells->nodes, pl->own0, pl->b, pl->m->rowptr, pl->m->col, pl->m->val, pl->m_row0, pl->fl, pl->nf);
+  return hipGetLastError() != hipSuccess;
+}
+template <int NB>
+static int el_launch_dense_mfma(const el_launch &L) {
+  const tg_elemplan_s *pl = L.pl;
+  hipLaunchKernelGGL((k_el_dense_mfma<NB>), dim3(L.grid), dim3(256), 0, g_tg.stream, L.blocks, pl->S, pl->own1 - pl->own0, pl->cells->nodes,
+                     pl->own0, pl->b, pl->m->rowptr, pl->m->col, pl->m->val, pl->m_row0, pl->fl, pl->nf, pl->mpos);
+  return hipGetLastError() != hipSuccess;
+}
+template <int LG>
+static int el_launch_merge(const el_launch &L) {
+  const tg_elemplan_s *pl = L.pl;
+  const size_t lds = (size_t)4 * (64 >> LG) * L.capk * sizeof(double);      // a row of capk sums per group of 2^LG lanes
+  hipLaunchKernelGGL((k_el_merge<LG>), dim3(L.grid), dim3(256), lds, g_tg.stream, pl->iptr, pl->ient, L.blocks, pl->slot, pl->nf, pl->S,
+                     pl->dof1 - pl->dof0, L.capk, L.k->rowptr, L.k->col, L.mask, pl->dof0, L.diag, L.k->val);
+  TG_LAUNCH_CHECK();
+  return 0;
+}
+
+#define EL_ROW(NAME, STAGE, LO, HI, ALT, DYN, LAUNCH) {#NAME, STAGE, LO, HI, ALT, (const void *)(NAME), DYN, LAUNCH}
+static const el_route g_el_routes[] = {
+    EL_ROW(k_el_fl<true>, EL_FL, 65, EL_INF, -1, true, el_launch_fl<true>),
+    EL_ROW(k_el_fl<false>, EL_FL, 0, 64, -1, true, el_launch_fl<false>),
+    EL_ROW(k_el_rowsym<false>, EL_SYM, 0, 64, 0, true, el_launch_rowsym<false>),
+    EL_ROW(k_el_rowsym<true>, EL_SYM, 65, 128, 0, true, el_launch_rowsym<true>),
+    EL_ROW(k_el_rowhash<8>, EL_SYM, 0, 64, 8, true, el_launch_rowhash<8>),
+    EL_ROW(k_el_rowhash<16>, EL_SYM, 0, 64, 16, true, el_launch_rowhash<16>),
+    EL_ROW(k_el_scatter8, EL_SPLIT, 0, EL_INF, 1, false, el_launch_scatter8),
+    EL_ROW(k_el_scatter, EL_SPLIT, 0, EL_INF, 0, false, el_launch_scatter),
+    EL_ROW(k_el_dense<1>, EL_DENSE, 0, 16, 1, false, el_launch_dense<1>),
+    EL_ROW(k_el_dense_mfma<1>, EL_DENSE, 0, 16, 0, false, el_launch_dense_mfma<1>),
+    EL_ROW(k_el_dense<2>, EL_DENSE, 17, 32, 1, false, el_launch_dense<2>),
+    EL_ROW(k_el_dense_mfma<2>, EL_DENSE, 17, 32, 0, false, el_launch_dense_mfma<2>),
+    EL_ROW(k_el_dense<4>, EL_DENSE, 33, 64, 1, false, el_launch_dense<4>),
+    EL_ROW(k_el_dense_mfma<3>, EL_DENSE, 33, 48, 0, false, el_launch_dense_mfma<3>),
+    EL_ROW(k_el_dense_mfma<4>, EL_DENSE, 49, 64, 0, false, el_launch_dense_mfma<4>),
+    EL_ROW(k_el_dense_big, EL_DENSE, 65, EL_BIG_MS, -1, true, el_launch_dense_big),      // (3-D p = 4: 125 nodes)
+    EL_ROW(k_el_merge<3>, EL_MERGE, 0, 8, -1, true, el_launch_merge<3>),
+    EL_ROW(k_el_merge<4>, EL_MERGE, 9, 16, -1, true, el_launch_merge<4>),
+    EL_ROW(k_el_merge<5>, EL_MERGE, 17, 32, -1, true, el_launch_merge<5>),
+    EL_ROW(k_el_merge<6>, EL_MERGE, 33, EL_INF, -1, true, el_launch_merge<6>),
+};
+#undef EL_ROW
+
+// the row of a stage for a size and an alternative; null: no kernel (cells of more than EL_BIG_MS nodes / functions)
+static const el_route *el_route_find(int stage, int size, int alt) {
+  for (const el_route &r : g_el_routes)
+    if (r.stage == stage && size >= r.lo && size <= r.hi && (r.alt < 0 || r.alt == alt)) return &r;
+  return nullptr;
+}
+
+static int el_routes_init() {           // every kernel with dynamic LDS may take the 160 KB of a CU
+  static bool done = false;
+  if (done) return 0;
+  for (const el_route &r : g_el_routes)
+    if (r.dyn_lds) TG_CHECK_HIP(hipFuncSetAttribute(r.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  done = true;
+  return 0;
+}
+
+// ---- the plan, stage by stage -------------------------------------------------------------------------------------------------
+// window of node numbers; sets the words of the whole phase (el_cells_word)
+static int el_plan_node_window(tg_elemplan_s *pl) {
+  const int64_t total = pl->cells->ncell * pl->b;
+  int init[EL_W_CELLS] = {0}, h[EL_W_CELLS];
+  init[EL_W_NODE_MIN] = init[EL_W_FN_MIN] = EL_INF;
+  init[EL_W_NODE_MAX] = init[EL_W_FN_MAX] = -1;
+  TG_TRY(tg_h2d_staged(el_word(0), init, sizeof(init)));
+  hipLaunchKernelGGL(k_el_minmax, dim3(tg_grid_1d(total, 256)), dim3(256), 0, g_tg.stream, pl->cells->nodes, total, el_word(EL_W_NODE_MIN));
+  TG_LAUNCH_CHECK();
+  if (el_words_read({{h, 0, sizeof(h)}})) {
+    tg_set_error("tg_elemplan_create: node window failed to run");
+    return 1;
+  }
+  if (h[EL_W_NODE_MIN] < 0) {
+    tg_set_error("tg_elemplan_create: negative node number");
+    return 2;
+  }
+  pl->node0 = h[EL_W_NODE_MIN], pl->nnode = (int64_t)h[EL_W_NODE_MAX] - h[EL_W_NODE_MIN] + 1;
+  return 0;
+}
+
+// node -> (cell, position) lists, ascending; EL_W_NODE_CELLS and EL_W_NODE_TWICE are left for the next stage to read
+static int el_plan_node_cells(tg_elemplan_s *pl) {
+  const tg_cells_s *cells = pl->cells;
+  const int64_t total = cells->ncell * cells->b;
+  const unsigned grid = tg_grid_1d(total, 256);
+  tg_dbuf<int32_t> cur;
+  TG_TRY(tg_dmalloc(&pl->nptr, pl->nnode + 2));
+  TG_TRY(tg_dmalloc(&pl->nlist, total));
+  TG_TRY(cur.alloc(pl->nnode));
+  TG_CHECK_HIP(hipMemsetAsync(pl->nptr, 0, (size_t)(pl->nnode + 2) * sizeof(int64_t), g_tg.stream));
+  TG_CHECK_HIP(hipMemsetAsync(cur, 0, (size_t)pl->nnode * sizeof(int32_t), g_tg.stream));
+  hipLaunchKernelGGL(k_el_node_count, dim3(grid), dim3(256), 0, g_tg.stream, cells->nodes, total, pl->node0, pl->nptr);
+  TG_LAUNCH_CHECK();
+  TG_TRY(tg_exclusive_scan_i64(pl->nptr, pl->nnode, nullptr));
+  hipLaunchKernelGGL(k_el_node_fill, dim3(grid), dim3(256), 0, g_tg.stream, cells->nodes, total, cells->b, pl->node0, pl->nptr, cur.get(),
+                     pl->nlist);
+  TG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_el_node_sort, dim3(tg_grid_1d(pl->nnode, 256)), dim3(256), 0, g_tg.stream, pl->nptr, pl->nnode, pl->nlist,
+                     el_word(EL_W_NODE_TWICE));
+  TG_LAUNCH_CHECK();
+  return 0;
+}
+
+// function lists of the own cells; with them nfmax, S and the window of functions
+static int el_plan_function_lists(tg_elemplan_s *pl, const el_switches &sw) {
+  const int64_t nown = pl->own1 - pl->own0;
+  TG_TRY(tg_dmalloc(&pl->fl, nown * EL_FLS));
+  TG_TRY(tg_dmalloc(&pl->nf, nown));
+  TG_TRY(tg_dmalloc(&pl->mpos, nown * pl->b * 64 + 64));
+  // longest row of M: the stride of the staged rows (a row of more than EL_FLS entries cannot be part of a cell's list); with
+  // it comes the longest node -> cells list (k_el_node_sort): up to 8, the lists are also kept as a table (k_el_scatter8)
+  TG_TRY(el_words_zero(EL_W_MROW_MAX, 1));
+  hipLaunchKernelGGL(k_el_maxrow, dim3(tg_grid_1d(pl->m->nrows, 256)), dim3(256), 0, g_tg.stream, pl->m->rowptr, pl->m->nrows,
+                     el_word(EL_W_MROW_MAX));
+  TG_LAUNCH_CHECK();
+  int hmax = 0, hnode = 0, h[EL_W_CELLS];
+  if (el_words_read({{&hmax, EL_W_MROW_MAX, sizeof(int)}, {&hnode, EL_W_NODE_CELLS, sizeof(int)}})) {
+    tg_set_error("tg_elemplan_create: the row-length kernel failed to run");
+    return 1;
+  }
+  if (hnode <= 8 && !sw.lists) {
+    TG_TRY(tg_dmalloc(&pl->nfix, pl->nnode * 8 + 16));
+    hipLaunchKernelGGL(k_el_node_fix, dim3(tg_grid_1d(pl->nnode * 8, 256)), dim3(256), 0, g_tg.stream, pl->nptr, pl->nlist, pl->nnode, pl->nfix);
+    TG_LAUNCH_CHECK();
+  }
+  el_launch L;
+  L.pl = pl, L.dbg = sw.dbg;
+  L.LD = std::min(hmax, EL_FLS) + 1;
+  L.wave_words = (pl->b > 64 ? 128 : 64) * L.LD + EL_FLS;
+  L.waves = (size_t)L.wave_words * 4 > 16 * 1024 ? 1 : 4;
+  L.lds = (size_t)L.waves * L.wave_words * sizeof(int32_t);
+  if (L.lds > 160 * 1024) return 100;
+  L.grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tg_cdiv(nown, L.waves), (int64_t)g_tg.num_cu * 64));
+  TG_TRY(el_route_find(EL_FL, pl->b, -1)->launch(L));        // (the two rows cover every b)
+  if (el_words_read({{h, 0, sizeof(h)}})) {
+    tg_set_error("tg_elemplan_create: the function-list kernels failed to run");
+    return 1;
+  }
+  if (h[EL_W_NODE_TWICE]) {
+    tg_set_error("tg_elemplan_create: a node is listed twice in one cell");
+    return 2;
+  }
+  if (h[EL_W_FL_BAD] & EL_FL_OUTSIDE) {
+    tg_set_error("tg_elemplan_create: a node of an own cell lies outside the rows of M handed in");
+    return 2;
+  }
+  if ((h[EL_W_FL_BAD] & EL_FL_TOO_MANY) || h[EL_W_NF_MAX] < 1) return 100;      // (or an operator without entries)
+  pl->nfmax = h[EL_W_NF_MAX];
+  pl->S = std::max(pl->b, pl->nfmax);
+  pl->dof0 = h[EL_W_FN_MIN], pl->dof1 = (int64_t)h[EL_W_FN_MAX] + 1;
+  TG_REQUIRE(nown * (int64_t)pl->S < 0x7fffffffll, "tg_elemplan_create: too many cells in one chunk");
+  return 0;
+}
+
+// function -> rows (c, q) of the element matrices, ascending; 100: a function in more than 128 cells
+static int el_plan_function_rows(tg_elemplan_s *pl) {
+  const int64_t nown = pl->own1 - pl->own0, ndof = pl->dof1 - pl->dof0;
+  const unsigned grid = tg_grid_1d(nown * EL_FLS, 256);
+  tg_dbuf<int32_t> cur;
+  TG_TRY(tg_dmalloc(&pl->iptr, ndof + 2));
+  TG_TRY(cur.alloc(ndof));
+  TG_CHECK_HIP(hipMemsetAsync(pl->iptr, 0, (size_t)(ndof + 2) * sizeof(int64_t), g_tg.stream));
+  TG_CHECK_HIP(hipMemsetAsync(cur, 0, (size_t)ndof * sizeof(int32_t), g_tg.stream));
+  hipLaunchKernelGGL(k_el_inc_count, dim3(grid), dim3(256), 0, g_tg.stream, pl->fl, pl->nf, nown, pl->dof0, pl->iptr);
+  TG_LAUNCH_CHECK();
+  int64_t ninc = 0;
+  TG_TRY(tg_exclusive_scan_i64(pl->iptr, ndof, &ninc));
+  TG_TRY(tg_dmalloc(&pl->ient, ninc));
+  TG_TRY(el_words_zero(0, EL_W_INC));
+  hipLaunchKernelGGL(k_el_inc_fill, dim3(grid), dim3(256), 0, g_tg.stream, pl->fl, pl->nf, nown, pl->S, pl->dof0, pl->iptr, cur.get(), pl->ient);
+  TG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_el_inc_sort, dim3((unsigned)std::min<int64_t>(tg_cdiv(ndof, 4), (int64_t)g_tg.num_cu * 32)), dim3(256), 0, g_tg.stream,
+                     pl->iptr, ndof, pl->ient, el_word(EL_W_NINC_MAX));
+  TG_LAUNCH_CHECK();
+  int h[EL_W_INC];
+  if (el_words_read({{h, 0, sizeof(h)}})) {
+    tg_set_error("tg_elemplan_create: the incidence kernels failed to run");
+    return 1;
+  }
+  pl->ninc_max = h[EL_W_NINC_MAX];
+  return pl->ninc_max > 128 ? 100 : 0;
 }
 
 /* The plan of the element-split product for the cells [own0, own1) of `cells` (all listed cells take part in the ownership
@@ -1349,129 +1703,15 @@ extern "C" int tg_elemplan_create(tg_cells_t cells, int64_t own0, int64_t own1, 
   TG_REQUIRE(cells && m && out && own0 >= 0 && own1 > own0 && own1 <= cells->ncell, "bad arguments to tg_elemplan_create");
   TG_REQUIRE_CANONICAL(m);
   TG_REQUIRE(cells->ncell < (1ll << (31 - EL_POSBITS)), "tg_elemplan_create: more than 16 M cells in one chunk");
-  tg_elemplan_s *pl = new tg_elemplan_s();
+  const el_switches sw = el_switches_read();
+  TG_TRY(el_routes_init());
+  el_own<tg_elemplan_s> pl(new tg_elemplan_s());
   pl->cells = cells, pl->m = m, pl->m_row0 = m_row0, pl->own0 = own0, pl->own1 = own1, pl->b = cells->b;
-  const int64_t ncell = cells->ncell, nown = own1 - own0, total = ncell * cells->b;
-  int *st = (int *)g_tg.scratch;             // [0..7] statistics
-  int h[8];
-  int32_t *cur = nullptr;
-  int rc = 0;
-  auto fail = [&](int code) {
-    tg_dfree(cur);
-    tg_elemplan_destroy(pl);
-    return code;
-  };
-#define EL_SYNC_STATS()                                                                                         \
-  (hipMemcpyAsync(h, st, sizeof(h), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess || hipStreamSynchronize(g_tg.stream) != hipSuccess || \
-   hipGetLastError() != hipSuccess)
-  // ---- window of node numbers
-  {
-    const int init[8] = {EL_INF, -1, 0, 0, EL_INF, -1, 0, 0};
-    hipMemcpyAsync(st, init, sizeof(init), hipMemcpyHostToDevice, g_tg.stream);
-    hipLaunchKernelGGL(k_el_minmax, dim3(tg_grid_1d(total, 256)), dim3(256), 0, g_tg.stream, cells->nodes, total, st);
-    if (EL_SYNC_STATS()) {
-      tg_set_error("tg_elemplan_create: node window failed to run");
-      return fail(1);
-    }
-    if (h[0] < 0) {
-      tg_set_error("tg_elemplan_create: negative node number");
-      return fail(2);
-    }
-    pl->node0 = h[0], pl->nnode = (int64_t)h[1] - h[0] + 1;
-  }
-  // ---- node -> cells
-  rc = tg_dmalloc(&pl->nptr, pl->nnode + 2) || tg_dmalloc(&pl->nlist, total) || tg_dmalloc(&cur, pl->nnode);
-  if (rc) return fail(rc);
-  hipMemsetAsync(pl->nptr, 0, (size_t)(pl->nnode + 2) * sizeof(int64_t), g_tg.stream);
-  hipMemsetAsync(cur, 0, (size_t)pl->nnode * sizeof(int32_t), g_tg.stream);
-  hipLaunchKernelGGL(k_el_node_count, dim3(tg_grid_1d(total, 256)), dim3(256), 0, g_tg.stream, cells->nodes, total, pl->node0, pl->nptr);
-  rc = tg_exclusive_scan_i64(pl->nptr, pl->nnode, nullptr);
-  if (rc) return fail(rc);
-  hipLaunchKernelGGL(k_el_node_fill, dim3(tg_grid_1d(total, 256)), dim3(256), 0, g_tg.stream, cells->nodes, total, cells->b, pl->node0,
-                     pl->nptr, cur, pl->nlist);
-  hipLaunchKernelGGL(k_el_node_sort, dim3(tg_grid_1d(pl->nnode, 256)), dim3(256), 0, g_tg.stream, pl->nptr, pl->nnode, pl->nlist, st + 3);
-  tg_dfree(cur);
-  cur = nullptr;
-  // ---- function lists of the own cells
-  rc = tg_dmalloc(&pl->fl, nown * EL_FLS) || tg_dmalloc(&pl->nf, nown) || tg_dmalloc(&pl->mpos, nown * cells->b * 64 + 64);
-  if (rc) return fail(rc);
-  {
-    // longest row of M: the stride of the staged rows (a row of more than EL_FLS entries cannot be part of a cell's list); with
-    // it comes the longest node -> cells list (k_el_node_sort): up to 8, the lists are also kept as a table (k_el_scatter8)
-    hipMemsetAsync(st + 1, 0, sizeof(int), g_tg.stream);
-    hipLaunchKernelGGL(k_el_maxrow, dim3(tg_grid_1d(m->nrows, 256)), dim3(256), 0, g_tg.stream, m->rowptr, m->nrows, st + 1);
-    int hmax = 0, hnode = 0;
-    if (hipMemcpyAsync(&hmax, st + 1, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess ||
-        hipMemcpyAsync(&hnode, st + 2, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess ||
-        hipStreamSynchronize(g_tg.stream) != hipSuccess) {
-      tg_set_error("tg_elemplan_create: the row-length kernel failed to run");
-      return fail(1);
-    }
-    if (hnode <= 8 && !getenv("TIGAR_EL_LISTS")) {
-      rc = tg_dmalloc(&pl->nfix, pl->nnode * 8 + 16);
-      if (rc) return fail(rc);
-      hipLaunchKernelGGL(k_el_node_fix, dim3(tg_grid_1d(pl->nnode * 8, 256)), dim3(256), 0, g_tg.stream, pl->nptr, pl->nlist, pl->nnode, pl->nfix);
-    }
-    const int LD = std::min(hmax, EL_FLS) + 1;
-    const bool two = cells->b > 64;
-    const int wave_words = (two ? 128 : 64) * LD + EL_FLS;
-    const int waves = (size_t)wave_words * 4 > 16 * 1024 ? 1 : 4;
-    const size_t lds = (size_t)waves * wave_words * sizeof(int32_t);
-    if (lds > 160 * 1024) return fail(100);
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tg_cdiv(nown, waves), (int64_t)g_tg.num_cu * 64));
-    if (two) {
-      hipFuncSetAttribute((const void *)k_el_fl<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL((k_el_fl<true>), dim3(grid), dim3(64 * waves), lds, g_tg.stream, m->rowptr, m->col, m_row0, m->nrows, cells->nodes, own0,
-                         nown, cells->b, LD, wave_words, waves, pl->fl, pl->nf, pl->mpos, st + 4, getenv("TIGAR_EL_DBG") ? atoi(getenv("TIGAR_EL_DBG")) : 0);
-    } else {
-      hipFuncSetAttribute((const void *)k_el_fl<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL((k_el_fl<false>), dim3(grid), dim3(64 * waves), lds, g_tg.stream, m->rowptr, m->col, m_row0, m->nrows, cells->nodes, own0,
-                         nown, cells->b, LD, wave_words, waves, pl->fl, pl->nf, pl->mpos, st + 4, getenv("TIGAR_EL_DBG") ? atoi(getenv("TIGAR_EL_DBG")) : 0);
-    }
-  }
-  if (EL_SYNC_STATS()) {
-    tg_set_error("tg_elemplan_create: the function-list kernels failed to run");
-    return fail(1);
-  }
-  if (h[3]) {
-    tg_set_error("tg_elemplan_create: a node is listed twice in one cell");
-    return fail(2);
-  }
-  if (h[7] & 1) {
-    tg_set_error("tg_elemplan_create: a node of an own cell lies outside the rows of M handed in");
-    return fail(2);
-  }
-  if ((h[7] & 2) || h[6] < 1) return fail(100);          // more than EL_FLS functions in a cell / an operator without entries
-  pl->nfmax = h[6];
-  pl->S = std::max(pl->b, pl->nfmax);
-  pl->dof0 = h[4], pl->dof1 = (int64_t)h[5] + 1;
-  TG_REQUIRE(nown * (int64_t)pl->S < 0x7fffffffll, "tg_elemplan_create: too many cells in one chunk");
-  // ---- function -> element rows
-  const int64_t ndof = pl->dof1 - pl->dof0;
-  rc = tg_dmalloc(&pl->iptr, ndof + 2) || tg_dmalloc(&cur, ndof);
-  if (rc) return fail(rc);
-  hipMemsetAsync(pl->iptr, 0, (size_t)(ndof + 2) * sizeof(int64_t), g_tg.stream);
-  hipMemsetAsync(cur, 0, (size_t)ndof * sizeof(int32_t), g_tg.stream);
-  hipLaunchKernelGGL(k_el_inc_count, dim3(tg_grid_1d(nown * EL_FLS, 256)), dim3(256), 0, g_tg.stream, pl->fl, pl->nf, nown, pl->dof0, pl->iptr);
-  int64_t ninc = 0;
-  rc = tg_exclusive_scan_i64(pl->iptr, ndof, &ninc);
-  if (!rc) rc = tg_dmalloc(&pl->ient, ninc);
-  if (rc) return fail(rc);
-  hipMemsetAsync(st, 0, 4 * sizeof(int), g_tg.stream);
-  hipLaunchKernelGGL(k_el_inc_fill, dim3(tg_grid_1d(nown * EL_FLS, 256)), dim3(256), 0, g_tg.stream, pl->fl, pl->nf, nown, pl->S, pl->dof0,
-                     pl->iptr, cur, pl->ient);
-  hipLaunchKernelGGL(k_el_inc_sort, dim3((unsigned)std::min<int64_t>(tg_cdiv(ndof, 4), (int64_t)g_tg.num_cu * 32)), dim3(256), 0, g_tg.stream,
-                     pl->iptr, ndof, pl->ient, st);
-  if (EL_SYNC_STATS()) {
-    tg_set_error("tg_elemplan_create: the incidence kernels failed to run");
-    return fail(1);
-  }
-  tg_dfree(cur);
-  cur = nullptr;
-  pl->ninc_max = h[0];
-  if (pl->ninc_max > 128) return fail(100);
-#undef EL_SYNC_STATS
-  *out = pl;
+  TG_TRY(el_plan_node_window(pl.get()));
+  TG_TRY(el_plan_node_cells(pl.get()));
+  TG_TRY(el_plan_function_lists(pl.get(), sw));
+  TG_TRY(el_plan_function_rows(pl.get()));
+  *out = pl.release();
   return 0;
 }
 
@@ -1485,142 +1725,202 @@ extern "C" int tg_elemplan_info(tg_elemplan_t pl, int64_t *dof0, int64_t *dof1, 
   return 0;
 }
 
-static int el_symbolic(tg_elemplan_s *pl) {
-  const int64_t ndof = pl->dof1 - pl->dof0, nown = pl->own1 - pl->own0;
-  // the merge kernel (any cell the plan accepts)
-  const int LD = pl->nfmax + 1;
-  const bool two = pl->ninc_max > 64;
-  const int wave_words = (two ? 128 : 64) * LD + 128 + EL_MAXROW;
-  // (one wave per workgroup when a wave's lists take more than 16 KB: more workgroups fit a CU's LDS than waves of one would)
-  const int mwaves = (size_t)wave_words * 4 > 16 * 1024 ? 1 : 4;
-  const size_t mlds = (size_t)mwaves * wave_words * sizeof(int32_t);
-  // the hash kernel: functions in at most 64 cells of at most 64 functions; 8 keys per lane (rows of up to 512 entries), 16 when a
-  // row turns out longer (status 3)
-  int hashR = (pl->ninc_max <= 64 && pl->nfmax <= 64 && !getenv("TIGAR_EL_MERGE")) ? 8 : 0;
-  if (!hashR && mlds > 160 * 1024) return 100;
-  hipFuncSetAttribute((const void *)k_el_rowsym<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipFuncSetAttribute((const void *)k_el_rowsym<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipFuncSetAttribute((const void *)k_el_rowhash<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipFuncSetAttribute((const void *)k_el_rowhash<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  int *status = (int *)g_tg.scratch;
-  unsigned long long *cursor = (unsigned long long *)(g_tg.scratch + 2);
-  int64_t *off = nullptr, *cnt = nullptr;
-  int32_t *tcol = nullptr;
-  auto cleanup = [&]() {
-    tg_dfree(off);
-    tg_dfree(cnt);
-    tg_dfree(tcol);
-  };
-  int rc = tg_dmalloc(&off, ndof + 1) || tg_dmalloc(&cnt, ndof + 2) || tg_dmalloc(&pl->slot, nown * (int64_t)pl->S * pl->S + 16);
-  if (rc) {
-    cleanup();
-    return rc;
+// ---- the pattern of K (first product of a plan) ------------------------------------------------------------------------------
+struct el_sym_pass {          // geometry of a pass for the current keys per lane: used by the launch AND by the capacity
+  const el_route *route = nullptr;
+  int keys = 0;               // keys per lane of the hash kernel (8: rows of up to 512 entries, 16), 0: the merge kernel
+  int LD = 0, wave_words = 0, waves = 0;
+  size_t lds = 0;
+  unsigned grid(int64_t nrows) const {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(tg_cdiv(nrows, waves), (int64_t)g_tg.num_cu * 32));
   }
+};
+struct el_sym_bufs {          // what the passes fill; committed to the plan by el_symbolic when all of it is there
+  tg_dbuf<int64_t> off, cnt;
+  tg_dbuf<int32_t> tcol, k_col;
+  tg_dbuf<uint16_t> slot;
+  int64_t nnz = 0;
+  int max_k = 0;
+};
+
+// 100: the lists of the merge kernel (any cell the plan accepts) do not fit the LDS
+static int el_sym_geometry(const tg_elemplan_s *pl, int keys, el_sym_pass *G) {
+  G->keys = keys;
+  G->route = el_route_find(EL_SYM, pl->ninc_max, keys);
+  if (keys) {
+    G->waves = keys == 8 ? 2 : 1;
+    G->lds = (size_t)G->waves * (256 * keys * 3 / 2 + 64 * keys) * sizeof(int32_t);
+    return 0;
+  }
+  G->LD = pl->nfmax + 1;
+  G->wave_words = (pl->ninc_max > 64 ? 128 : 64) * G->LD + 128 + EL_MAXROW;
+  // (one wave per workgroup when a wave's lists take more than 16 KB: more workgroups fit a CU's LDS than waves of one would)
+  G->waves = (size_t)G->wave_words * 4 > 16 * 1024 ? 1 : 4;
+  G->lds = (size_t)G->waves * G->wave_words * sizeof(int32_t);
+  return G->lds > 160 * 1024 ? 100 : 0;
+}
+
+// one pass: mode 0 counts the rows phase, phase + step, ... (no temporary), mode 1 writes all rows into B.tcol (cap entries)
+static int el_sym_run(const tg_elemplan_s *pl, const el_sym_pass &G, int mode, int64_t step, int64_t phase, int64_t cap,
+                      const el_sym_bufs &B, unsigned long long *hsum, int *hstat) {
+  el_launch L;
+  L.pl = pl, L.LD = G.LD, L.wave_words = G.wave_words, L.waves = G.waves, L.lds = G.lds;
+  L.grid = G.grid(tg_cdiv(pl->dof1 - pl->dof0, step));
+  L.mode = mode, L.step = step, L.phase = phase, L.cap = cap;
+  if (mode) L.tcol = B.tcol, L.off = B.off, L.cnt = B.cnt, L.slot = B.slot;
+  TG_TRY(el_words_zero(EL_W_STATUS, EL_W_SYM));
+  TG_TRY(G.route->launch(L));
+  if (el_words_read({{hsum, EL_W_CURSOR, sizeof(*hsum)}, {hstat, EL_W_STATUS, sizeof(int)}})) {
+    tg_set_error("element split: the symbolic pass failed to run (LDS %zu B)", G.lds);
+    return 1;
+  }
+  return 0;
+}
+
+// A sample of the rows gives the capacity of the temporary (1/32 of the work).  The waves reserve the temporary in blocks of
+// EL_BLOCK entries: besides the entries themselves room for the unused tail of every block (less than a row each; from the
+// sample's mean row) and for one open block per wave.  A pass that comes out short has reserved exactly what the next one --
+// same rows per wave -- will ask for.
+static int64_t el_sym_capacity(const el_sym_pass &G, int64_t ndof, int64_t step, unsigned long long hsum) {
+  const unsigned nwaves_all = G.grid(ndof) * (unsigned)G.waves;
+  const int64_t nsampled = std::max<int64_t>(1, tg_cdiv(ndof, step));
+  const double mean_row = (double)hsum / (double)nsampled, est = step == 1 ? (double)hsum : (double)hsum * (double)step * 1.04;
+  return (int64_t)(est * (1.0 + 1.25 * std::min(mean_row, (double)EL_MAXROW) / EL_BLOCK)) + ((int64_t)nwaves_all + 2) * EL_BLOCK;
+}
+
+// run from the geometry G on; grow the temporary on EL_SYM_GROW; take 16 keys per lane on EL_SYM_WIDEN (a row of more than 512
+// entries)
+static int el_sym_passes(const tg_elemplan_s *pl, el_sym_pass G, el_sym_bufs &B, const el_route **taken) {
+  const int64_t ndof = pl->dof1 - pl->dof0, step = ndof >= 8192 ? 32 : 1;
   unsigned long long hsum = 0;
   int hstat = 0;
-  auto launch = [&](int mode, int64_t step, int64_t phase, int64_t cap, unsigned *grid_out) -> int {
-    const int waves = hashR == 8 ? 2 : hashR == 16 ? 1 : mwaves;
-    const size_t lds = hashR ? (size_t)waves * (256 * hashR * 3 / 2 + 64 * hashR) * sizeof(int32_t) : mlds;
-    const int64_t nrows = tg_cdiv(ndof, step);
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tg_cdiv(nrows, waves), (int64_t)g_tg.num_cu * 32));
-    if (grid_out) *grid_out = grid * (unsigned)waves;
-    hipMemsetAsync(status, 0, 4 * sizeof(double), g_tg.stream);
-    int32_t *tc = mode ? tcol : nullptr;
-    int64_t *po = mode ? off : nullptr, *pc = mode ? cnt : nullptr;
-    uint16_t *ps = mode ? pl->slot : nullptr;
-    if (hashR == 8)
-      hipLaunchKernelGGL((k_el_rowhash<8>), dim3(grid), dim3(64 * waves), lds, g_tg.stream, pl->iptr, pl->ient, ndof, pl->fl, pl->nf, pl->S, waves,
-                         mode, step, phase, tc, cursor, cap, po, pc, ps, status);
-    else if (hashR == 16)
-      hipLaunchKernelGGL((k_el_rowhash<16>), dim3(grid), dim3(64 * waves), lds, g_tg.stream, pl->iptr, pl->ient, ndof, pl->fl, pl->nf, pl->S, waves,
-                         mode, step, phase, tc, cursor, cap, po, pc, ps, status);
-    else if (two)
-      hipLaunchKernelGGL((k_el_rowsym<true>), dim3(grid), dim3(64 * waves), lds, g_tg.stream, pl->iptr, pl->ient, ndof, pl->fl, pl->nf, pl->S, LD,
-                         wave_words, waves, mode, step, phase, tc, cursor, cap, po, pc, ps, status);
-    else
-      hipLaunchKernelGGL((k_el_rowsym<false>), dim3(grid), dim3(64 * waves), lds, g_tg.stream, pl->iptr, pl->ient, ndof, pl->fl, pl->nf, pl->S, LD,
-                         wave_words, waves, mode, step, phase, tc, cursor, cap, po, pc, ps, status);
-    if (hipMemcpyAsync(&hsum, cursor, sizeof(hsum), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess ||
-        hipMemcpyAsync(&hstat, status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess ||
-        hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-      tg_set_error("element split: the symbolic pass failed to run (LDS %zu B)", lds);
-      return 1;
-    }
-    return 0;
-  };
-  // a sample of the rows gives the capacity of the temporary (1/32 of the work).  The waves reserve the temporary in blocks of
-  // EL_BLOCK entries: besides the entries themselves room for the unused tail of every block (less than a row each; from the
-  // sample's mean row) and for one open block per wave.  A pass that comes out short has reserved exactly what the next one --
-  // same rows per wave -- will ask for.
-  const int64_t step = ndof >= 8192 ? 32 : 1;
   int64_t cap = 0;
-  for (int attempt = 0; attempt < 4 && !rc; attempt++) {
+  for (int attempt = 0; attempt < 4; attempt++) {
+    *taken = G.route;
     if (cap == 0) {
-      rc = launch(0, step, step / 2, 0, nullptr);
-      if (rc) break;
-      if (hstat == 3 && hashR == 8) {
-        hashR = 16;
+      TG_TRY(el_sym_run(pl, G, 0, step, step / 2, 0, B, &hsum, &hstat));
+      if (hstat == EL_SYM_WIDEN && G.keys == 8) {
+        TG_TRY(el_sym_geometry(pl, 16, &G));
         continue;
       }
-      if (hstat >= 2) {
-        rc = 100;
-        break;
-      }
-      unsigned nwaves_all = 0;
-      {
-        const int waves = hashR == 8 ? 2 : hashR == 16 ? 1 : mwaves;
-        nwaves_all = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tg_cdiv(ndof, waves), (int64_t)g_tg.num_cu * 32)) * (unsigned)waves;
-      }
-      const int64_t nsampled = std::max<int64_t>(1, tg_cdiv(ndof, step));
-      const double mean_row = (double)hsum / (double)nsampled, est = step == 1 ? (double)hsum : (double)hsum * (double)step * 1.04;
-      cap = (int64_t)(est * (1.0 + 1.25 * std::min(mean_row, (double)EL_MAXROW) / EL_BLOCK)) + ((int64_t)nwaves_all + 2) * EL_BLOCK;
+      if (hstat >= EL_SYM_TOO_LONG) return 100;
+      cap = el_sym_capacity(G, ndof, step, hsum);
     }
-    rc = tg_dmalloc(&tcol, cap + 16);
-    if (rc) break;
-    rc = launch(1, 1, 0, cap, nullptr);
-    if (rc) break;
-    if (hstat == 0) break;
-    tg_dfree(tcol);
-    tcol = nullptr;
-    if (hstat == 3 && hashR == 8) {           // (a row of more than 512 entries the sample did not see)
-      hashR = 16;
+    TG_TRY(B.tcol.alloc(cap + 16));
+    TG_TRY(el_sym_run(pl, G, 1, 1, 0, cap, B, &hsum, &hstat));
+    if (hstat == 0) return 0;
+    B.tcol.reset();
+    if (hstat == EL_SYM_WIDEN && G.keys == 8) {           // (a row of more than 512 entries the sample did not see)
+      TG_TRY(el_sym_geometry(pl, 16, &G));
       cap = 0;
-    } else if (hstat == 1) {
+    } else if (hstat == EL_SYM_GROW) {
       cap = (int64_t)hsum;
     } else {
-      rc = 100;
-    }
-    if (attempt == 3 && !rc) {
-      tg_set_error("element split: the symbolic pass did not come to an end");
-      rc = 1;
+      return 100;
     }
   }
-  int64_t nnz = 0;
-  if (!rc) rc = tg_exclusive_scan_i64(cnt, ndof, &nnz);
-  if (!rc) rc = tg_dmalloc(&pl->k_col, nnz + TG_CSR_PAD);
-  if (!rc) {
-    int hmax = 0;
-    hipMemsetAsync(status, 0, sizeof(int), g_tg.stream);
-    hipLaunchKernelGGL(k_el_reorder, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(tg_cdiv(ndof, 4), (int64_t)g_tg.num_cu * 16))),
-                       dim3(256), 0, g_tg.stream, cnt, off, tcol, ndof, pl->k_col, status);
-    if (hipMemcpyAsync(&hmax, status, sizeof(int), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess ||
-        hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-      tg_set_error("element split: the reorder pass failed to run");
-      rc = 1;
-    }
-    pl->max_k = hmax;
+  tg_set_error("element split: the symbolic pass did not come to an end");
+  return 1;
+}
+
+// row pointer of K from the counts, the columns from the temporary into CSR order; the longest row
+static int el_sym_reorder(const tg_elemplan_s *pl, el_sym_bufs &B) {
+  const int64_t ndof = pl->dof1 - pl->dof0;
+  TG_TRY(tg_exclusive_scan_i64(B.cnt, ndof, &B.nnz));
+  TG_TRY(B.k_col.alloc(B.nnz + TG_CSR_PAD));
+  TG_TRY(el_words_zero(EL_W_MAX_K, 1));
+  hipLaunchKernelGGL(k_el_reorder, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(tg_cdiv(ndof, 4), (int64_t)g_tg.num_cu * 16))),
+                     dim3(256), 0, g_tg.stream, B.cnt.get(), B.off.get(), B.tcol.get(), ndof, B.k_col.get(), el_word(EL_W_MAX_K));
+  TG_LAUNCH_CHECK();
+  if (el_words_read({{&B.max_k, EL_W_MAX_K, sizeof(int)}})) {
+    tg_set_error("element split: the reorder pass failed to run");
+    return 1;
   }
-  if (!rc) {
-    pl->k_rowptr = cnt;
-    cnt = nullptr;
-    pl->k_nnz = nnz;
-  } else {
-    tg_dfree(pl->slot);
-    tg_dfree(pl->k_col);
-    pl->slot = nullptr, pl->k_col = nullptr;
+  return 0;
+}
+
+// pattern of K and the places of the element matrices' entries in it; the plan is touched only when everything is there
+static int el_symbolic(tg_elemplan_s *pl, const el_switches &sw, const el_route **taken) {
+  const int64_t ndof = pl->dof1 - pl->dof0, nown = pl->own1 - pl->own0;
+  // the hash kernel: functions in at most 64 cells of at most 64 functions; else the merge kernel, which declines (100,
+  // before anything is allocated) lists that do not fit the LDS
+  el_sym_pass G;
+  TG_TRY(el_sym_geometry(pl, pl->ninc_max <= 64 && pl->nfmax <= 64 && !sw.merge ? 8 : 0, &G));
+  el_sym_bufs B;
+  TG_TRY(B.off.alloc(ndof + 1));
+  TG_TRY(B.cnt.alloc(ndof + 2));
+  TG_TRY(B.slot.alloc(nown * (int64_t)pl->S * pl->S + 16));
+  TG_TRY(el_sym_passes(pl, G, B, taken));
+  TG_TRY(el_sym_reorder(pl, B));
+  pl->k_rowptr = B.cnt.release();
+  pl->k_col = B.k_col.release();
+  pl->slot = B.slot.release();
+  pl->max_k = B.max_k;
+  pl->k_nnz = B.nnz;
+  return 0;
+}
+
+// ---- the product, stage by stage ---------------------------------------------------------------------------------------------
+// A into one dense block per own cell; 100: an entry of a checked row whose nodes share no listed cell, or a node in more
+// than 64 cells (the row-wise kernels take such a matrix)
+static int el_split_a(const tg_elemplan_s *pl, const el_switches &sw, const tg_csr_s *a, int64_t a_row0, int64_t check0, int64_t check1,
+                      double *blocks, const el_route **taken) {
+  const int64_t nown = pl->own1 - pl->own0;
+  unsigned long long hc[4];
+  TG_CHECK_HIP(hipMemsetAsync(blocks, 0, (size_t)(nown * (int64_t)pl->S * pl->S) * sizeof(double), g_tg.stream));
+  TG_TRY(el_words_zero(EL_W_COUNTERS, EL_W_SPLIT));
+  if (a->nrows > 0) {
+    el_launch L;
+    L.pl = pl, L.a = a, L.a_row0 = a_row0, L.check0 = check0, L.check1 = check1, L.blocks = blocks;
+    L.grid = el_grid8(std::min<int64_t>(tg_cdiv(a->nrows, 4), (int64_t)g_tg.num_cu * 32));
+    *taken = el_route_find(EL_SPLIT, 0, pl->nfix != nullptr);
+    TG_TRY((*taken)->launch(L));
   }
-  cleanup();
-  return rc;
+  if (el_words_read({{hc, EL_W_COUNTERS, sizeof(hc)}})) {
+    tg_set_error("element split: the splitting pass failed to run");
+    return 1;
+  }
+  if (hc[EL_C_NO_CELL] || hc[EL_C_NODE_OVER_64]) {
+    if (sw.debug)
+      fprintf(stderr, "[tigar] element split declined: %llu entries in blocks, %llu in other chunks' cells, %llu without a common cell%s\n",
+              hc[EL_C_OWN], hc[EL_C_FOREIGN], hc[EL_C_NO_CELL], hc[EL_C_NODE_OVER_64] ? ", a node in more than 64 cells" : "");
+    return 100;
+  }
+  return 0;
+}
+
+// E_c = M_c^T (A_c M_c) over the blocks; 100: cells of more than EL_BIG_MS nodes / functions
+static int el_dense_products(const tg_elemplan_s *pl, const el_switches &sw, double *blocks, const el_route **taken) {
+  const int64_t nown = pl->own1 - pl->own0;
+  const el_route *r = *taken = el_route_find(EL_DENSE, pl->S, sw.valu);
+  if (!r) return 100;
+  el_launch L;
+  L.pl = pl, L.blocks = blocks;
+  L.grid = el_grid8(std::min<int64_t>(nown, (int64_t)g_tg.num_cu * 64));
+  if (r->launch(L)) {
+    tg_set_error("element split: the element kernel failed to launch");
+    return 1;
+  }
+  return 0;
+}
+
+// the plan's pattern into k, the values by places: no look-up, a fixed order of additions
+static int el_merge_by_places(const tg_elemplan_s *pl, const double *blocks, const uint8_t *mask, double diag, tg_csr_s *k,
+                              const el_route **taken) {
+  const int64_t ndof = pl->dof1 - pl->dof0;
+  const el_route *r = *taken = el_route_find(EL_MERGE, pl->nfmax, -1);
+  TG_CHECK_HIP(hipMemcpyAsync(k->rowptr, pl->k_rowptr, (size_t)(ndof + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream));
+  TG_CHECK_HIP(hipMemcpyAsync(k->col, pl->k_col, (size_t)pl->k_nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, g_tg.stream));
+  el_launch L;
+  L.pl = pl, L.blocks = const_cast<double *>(blocks), L.k = k, L.mask = mask, L.diag = diag;
+  L.capk = (std::max(pl->max_k, 1) + 7) & ~7;
+  L.grid = el_grid8(std::min<int64_t>(tg_cdiv(ndof, 4), (int64_t)g_tg.num_cu * 32));
+  TG_TRY(r->launch(L));
+  if (hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
+    tg_set_error("element split: the merge failed to run");
+    return 1;
+  }
+  return 0;
 }
 
 /* K rows [dof0, dof1) (tg_elemplan_info) of M^T A M summed over the own cells of the plan, global columns; MatZeroRowsColumns
@@ -1632,115 +1932,24 @@ extern "C" int tg_elemplan_ptap(tg_elemplan_t pl, tg_csr_t a, int64_t a_row0, in
   TG_REQUIRE_INIT();
   TG_REQUIRE(pl && a && k_out, "null argument to tg_elemplan_ptap");
   TG_REQUIRE_CANONICAL(a);
-  const int64_t nown = pl->own1 - pl->own0, ndof = pl->dof1 - pl->dof0;
-  const int S = pl->S;
-  double *blocks = nullptr;
-  uint8_t *mask = nullptr;
-  tg_csr_s *k = nullptr;
-  auto cleanup = [&]() {
-    tg_dfree(blocks);
-    tg_dfree(mask);
-  };
-  int rc = tg_dmalloc(&blocks, nown * (int64_t)S * S + TG_CSR_PAD);
-  if (rc) return rc;
-  unsigned long long *counters = (unsigned long long *)(g_tg.scratch + 8), hc[4];
-  hipMemsetAsync(blocks, 0, (size_t)(nown * (int64_t)S * S) * sizeof(double), g_tg.stream);
-  hipMemsetAsync(counters, 0, sizeof(hc), g_tg.stream);
-  if (a->nrows > 0 && pl->nfix)
-    hipLaunchKernelGGL(k_el_scatter8, dim3(el_grid8(std::min<int64_t>(tg_cdiv(a->nrows, 4), (int64_t)g_tg.num_cu * 32))), dim3(256), 0,
-                       g_tg.stream, a->rowptr, a->col, a->val, a->nrows, a_row0, pl->node0, pl->nnode, pl->nfix, pl->own0, pl->own1, S, check_row0,
-                       check_row1, blocks, counters);
-  else if (a->nrows > 0)
-    hipLaunchKernelGGL(k_el_scatter, dim3(el_grid8(std::min<int64_t>(tg_cdiv(a->nrows, 4), (int64_t)g_tg.num_cu * 32))), dim3(256), 0,
-                       g_tg.stream, a->rowptr, a->col, a->val, a->nrows, a_row0, pl->node0, pl->nnode, pl->nptr, pl->nlist, pl->own0, pl->own1,
-                       S, check_row0, check_row1, blocks, counters);
-  if (hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, g_tg.stream) != hipSuccess ||
-      hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-    tg_set_error("element split: the splitting pass failed to run");
-    cleanup();
-    return 1;
-  }
-  if (hc[2] || hc[3]) {          // an entry whose nodes share no cell (or a node in more than 64 cells): the row-wise kernels
-    if (getenv("TIGAR_DEBUG"))
-      fprintf(stderr, "[tigar] element split declined: %llu entries in blocks, %llu in other chunks' cells, %llu without a common cell%s\n",
-              hc[0], hc[1], hc[2], hc[3] ? ", a node in more than 64 cells" : "");
-    cleanup();
-    return 100;
-  }
-  {
-    const unsigned grid = el_grid8(std::min<int64_t>(nown, (int64_t)g_tg.num_cu * 64));
-#define EL_DENSE(KERNEL)                                                                                                        \
-  hipLaunchKernelGGL((KERNEL), dim3(grid), dim3(256), 0, g_tg.stream, blocks, S, nown, pl->cells->nodes, pl->own0, pl->b, pl->m->rowptr, \
-                     pl->m->col, pl->m->val, pl->m_row0, pl->fl, pl->nf)
-#define EL_DENSE_MFMA(NBV)                                                                                                      \
-  hipLaunchKernelGGL((k_el_dense_mfma<NBV>), dim3(grid), dim3(256), 0, g_tg.stream, blocks, S, nown, pl->cells->nodes, pl->own0, pl->b, \
-                     pl->m->rowptr, pl->m->col, pl->m->val, pl->m_row0, pl->fl, pl->nf, pl->mpos)
-    const bool valu = getenv("TIGAR_EL_VALU") != nullptr;       // (the register-tile kernels: A/B runs)
-    if (S <= 16) {
-      if (valu) EL_DENSE(k_el_dense<1>); else EL_DENSE_MFMA(1);
-    } else if (S <= 32) {
-      if (valu) EL_DENSE(k_el_dense<2>); else EL_DENSE_MFMA(2);
-    } else if (S <= 48) {
-      if (valu) EL_DENSE(k_el_dense<4>); else EL_DENSE_MFMA(3);
-    } else if (S <= 64) {
-      if (valu) EL_DENSE(k_el_dense<4>); else EL_DENSE_MFMA(4);
-    } else if (S <= EL_BIG_MS) {   // (3-D p = 4: 125 nodes; one workgroup per CU)
-      const size_t lds = (size_t)(128 * EL_BIG_MS + 16 * 129 + 16 * 128) * sizeof(double);
-      hipFuncSetAttribute((const void *)k_el_dense_big, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL(k_el_dense_big, dim3(el_grid8(std::min<int64_t>(nown, (int64_t)g_tg.num_cu * 8))), dim3(256), lds, g_tg.stream, blocks, S,
-                         nown, pl->cells->nodes, pl->own0, pl->b, pl->m->rowptr, pl->m->col, pl->m->val, pl->m_row0, pl->fl, pl->nf);
-    } else {
-      cleanup();
-      return 100;                 // (cells of more than 126 nodes / functions)
-    }
-#undef EL_DENSE
-#undef EL_DENSE_MFMA
-    if (hipGetLastError() != hipSuccess) {
-      tg_set_error("element split: the element kernel failed to launch");
-      cleanup();
-      return 1;
-    }
-  }
-  if (pl->k_nnz < 0) {
-    rc = el_symbolic(pl);
-    if (rc) {
-      cleanup();
-      return rc;
-    }
-  }
-  if (nzero > 0) rc = tg_build_dof_mask(zero_dofs, nzero, pl->m->ncols, &mask);
-  if (!rc) rc = tg_csr_alloc(ndof, pl->m->ncols, pl->k_nnz, &k);
-  if (rc) {
-    cleanup();
-    return rc;
-  }
-  hipMemcpyAsync(k->rowptr, pl->k_rowptr, (size_t)(ndof + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, g_tg.stream);
-  hipMemcpyAsync(k->col, pl->k_col, (size_t)pl->k_nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, g_tg.stream);
-  {
-    const int capk = (std::max(pl->max_k, 1) + 7) & ~7;
-    const unsigned grid = el_grid8(std::min<int64_t>(tg_cdiv(ndof, 4), (int64_t)g_tg.num_cu * 32));
-#define EL_MERGE(LGV)                                                                                                                   \
-  do {                                                                                                                                  \
-    const size_t lds = (size_t)4 * (64 >> LGV) * capk * sizeof(double);                                                                 \
-    hipFuncSetAttribute((const void *)k_el_merge<LGV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                         \
-    hipLaunchKernelGGL((k_el_merge<LGV>), dim3(grid), dim3(256), lds, g_tg.stream, pl->iptr, pl->ient, blocks, pl->slot, pl->nf, S, ndof, capk, \
-                       k->rowptr, k->col, mask, pl->dof0, diag, k->val);                                                                \
-  } while (0)
-    if (pl->nfmax <= 8) EL_MERGE(3);
-    else if (pl->nfmax <= 16) EL_MERGE(4);
-    else if (pl->nfmax <= 32) EL_MERGE(5);
-    else EL_MERGE(6);
-#undef EL_MERGE
-  }
-  if (hipStreamSynchronize(g_tg.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-    tg_set_error("element split: the merge failed to run");
-    rc = 1;
-  }
-  cleanup();
-  if (rc) {
-    tg_csr_destroy(k);
-    return rc;
-  }
-  *k_out = k;
+  const el_switches sw = el_switches_read();
+  TG_TRY(el_routes_init());
+  const int64_t nown = pl->own1 - pl->own0;
+  const el_route *split = nullptr, *dense = nullptr, *pattern = nullptr, *merge = nullptr;
+  tg_dbuf<double> blocks;
+  tg_dbuf<uint8_t> mask;
+  TG_TRY(blocks.alloc(nown * (int64_t)pl->S * pl->S + TG_CSR_PAD));
+  TG_TRY(el_split_a(pl, sw, a, a_row0, check_row0, check_row1, blocks, &split));
+  TG_TRY(el_dense_products(pl, sw, blocks, &dense));
+  if (pl->k_nnz < 0) TG_TRY(el_symbolic(pl, sw, &pattern));
+  if (nzero > 0) TG_TRY(tg_build_dof_mask(zero_dofs, nzero, pl->m->ncols, &mask.p));
+  tg_csr_s *k_new = nullptr;
+  TG_TRY(tg_csr_alloc(pl->dof1 - pl->dof0, pl->m->ncols, pl->k_nnz, &k_new));
+  el_own<tg_csr_s> k(k_new);
+  TG_TRY(el_merge_by_places(pl, blocks, mask, diag, k.get(), &merge));
+  if (sw.trace)
+    fprintf(stderr, "[tigar] element split: split %s, cells %s, pattern %s, merge %s\n", split ? split->name : "none (no rows of A)",
+            dense->name, pattern ? pattern->name : "kept", merge->name);
+  *k_out = k.release();
   return 0;
 }
