@@ -4,9 +4,12 @@ product, the values within 1e-12 of the largest entry (the bound of tests/test_g
 of the table a stage took is read from the trace (``TIGAR_TRACE=1``: "[tigar] kron stage: <row>") and asserted.
 
 Rows: all eight (variant, a, u) combinations of ``k_ptap_line`` and both workgroup sizes of ``k_ptap_box``.  The hi flag follows
-from the 24-bit magic numbers of the sizes: it is set only when n0 * n1 >= 2^16 (tg_magic24: the quotient needs the high half
-of the product from bound^2 >= 2^32 on), so the small shapes here reach the hi=0 row of every pair; the hi=1 rows are the same
-template bodies and are left to the comparison of the emitted device code.
+from the 24-bit magic numbers of the sizes (tg_magic24, one flag per divisor: the quotient needs the high half of the product
+from bound * divisor >= 2^32 on; the template takes hi=1 when BOTH divisors carry it, about n0 * n1 >= 2^16), so the small
+shapes here reach the hi=0 row of every pair, with both quotients from the low word.  The hi=1 rows, the hi=0 row with one
+flag set (its 64-bit shift) and the sizes for which no 24-bit magic number exists are run by tests/test_gpu_kron_stage.py,
+which tests the kernels one stage at a time; the union of the rows asserted by name in the two files is the whole table
+(tests/test_kron_stage_reference_host.py).
 Variant <20,10> holds boxes of up to 20 nodes along the contracted direction: p = 2 and 3 (p^2 + 3 p - 1 = 9 and 17 nodes);
 p = 4 with 5 or 6 elements (21 or 25 nodes) takes <32,16>.
 

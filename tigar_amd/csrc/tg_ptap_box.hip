@@ -1120,7 +1120,8 @@ struct tg_kron_switches {       // the environment, read once per call of an ent
   bool g1_set;                  // TIGAR_BOX_G1 ...
   int g1;                       // ... and its value
   bool force_probe;             // TIGAR_PTAP_PROBE=1: size every temporary from a probe, not from the capacity cache
-  int line_run;                 // TIGAR_LINE_RUN: rows per wave of the line kernels (20), at least 1
+  int line_run;                 // TIGAR_LINE_RUN: rows per wave of the line kernels (20), 1 ... 64
+  int64_t line_min_waves;       // TIGAR_LINE_MIN_WAVES: waves below which the runs are halved, at least 1; 0: not set (64 per CU)
   int64_t line_grab;            // TIGAR_LINE_GRAB: output entries a wave reserves at a time (8192)
   bool exact_reach;             // TIGAR_BOX_EXACT_REACH: never sample the reach scan
   int reach_stride;             // TIGAR_BOX_REACH_STRIDE: at least 1; 0: not set
@@ -1139,7 +1140,9 @@ static tg_kron_switches tg_kron_switches_read() {
   S.g1_set = getenv("TIGAR_BOX_G1") != nullptr;
   S.g1 = num("TIGAR_BOX_G1", 4);
   S.force_probe = num("TIGAR_PTAP_PROBE", 0) == 1;
-  S.line_run = std::max(1, num("TIGAR_LINE_RUN", 20));
+  // (the line kernel keeps the box extents of a run's steps in the lanes of its wave: 64 rows at most)
+  S.line_run = std::min(64, std::max(1, num("TIGAR_LINE_RUN", 20)));
+  S.line_min_waves = getenv("TIGAR_LINE_MIN_WAVES") ? std::max<int64_t>(1, atoll(getenv("TIGAR_LINE_MIN_WAVES"))) : 0;
   S.line_grab = getenv("TIGAR_LINE_GRAB") ? atoll(getenv("TIGAR_LINE_GRAB")) : 8192;
   S.exact_reach = getenv("TIGAR_BOX_EXACT_REACH") != nullptr;
   S.reach_stride = getenv("TIGAR_BOX_REACH_STRIDE") ? std::max(1, num("TIGAR_BOX_REACH_STRIDE", 1)) : 0;
@@ -1658,7 +1661,8 @@ static int64_t tg_kron_line_runs(tg_kron_plan &K) {
     // rows per wave: 20 measured best at 96^3 and 256^3 p=3 (x/y/z stage at 96^3: 32 rows 30.9 / 15.8 / 8.5 ms,
     // 24: 30.2 / 15.1 / 8.1, 20: 29.0 / 13.2 / 7.3, 16: 29.6 / 14.2 / 7.3, 12: 29.4 / 13.7 / 7.0)
     int64_t T = std::min<int64_t>(K.S.line_run, span);
-    while (T > 1 && nx * tg_cdiv(span, T) < (int64_t)g_tg.num_cu * 64) T = (T + 1) / 2;
+    const int64_t min_waves = K.S.line_min_waves ? K.S.line_min_waves : std::max<int64_t>(1, (int64_t)g_tg.num_cu * 64);
+    while (T > 1 && nx * tg_cdiv(span, T) < min_waves) T = (T + 1) / 2;
     Q.mlen = (int)T;
     Q.ulo = (int)ulo;
     Q.uhi = (int)uhi;
@@ -1695,7 +1699,12 @@ static int tg_kron_run(tg_kron_plan &K, tg_bump &t) {
     P.rowmax = K.B.rowmax;
   }
   const unsigned grid = (unsigned)(tg_cdiv(K.line_variant ? tg_kron_line_runs(K) : nrows, 8) * 8);
-  if (getenv("TIGAR_TRACE")) fprintf(stderr, "[tigar] kron stage: %s\n", K.route->name);
+  if (getenv("TIGAR_TRACE")) {
+    fprintf(stderr, "[tigar] kron stage: %s\n", K.route->name);
+    if (K.line_variant)
+      fprintf(stderr, "[tigar] kron line runs: u=%d mlen=%d nchunk=%lld nx=%lld grab=%lld\n", K.Q.u, K.Q.mlen, (long long)K.Q.nchunk,
+              (long long)K.Q.nx, (long long)K.Q.grab);
+  }
   auto launch = [&](int) {
     if (K.line_variant)
       hipLaunchKernelGGL(K.route->line, dim3(grid), dim3(64), K.line_lds, g_tg.stream, P, K.Q, t.cnt.get(), t.off.get(), t.tcol.get(),
@@ -1724,8 +1733,12 @@ static int tg_kron_run(tg_kron_plan &K, tg_bump &t) {
     }
     if (h == TG_BOX_TOOBIG) return (int)TG_KRON_DECLINED;
     if (h == TG_BOX_OUTSIDE) return (int)TG_KRON_OUTSIDE;
+    if (h == TG_BOX_RANGE) {                       // (as the probe says it: with a cached capacity this is where it shows)
+      tg_set_error("tg_ptap_kron: the row block does not cover the rows referenced (slab halo too small)");
+      return 3;
+    }
     tg_set_error("tg_ptap_kron: kernel status %d", h);
-    return h == TG_BOX_RANGE ? 3 : 4;
+    return 4;
   };
   int rc = t.run(6, launch, decide);
   if (rc == TG_BUMP_NORUN) {
