@@ -721,6 +721,50 @@ int tg_quad_metric(const tg_patch_t *patch, tg_vec_t G_out);
 int tg_flow_points(const double *params, int nsd, int64_t npts, tg_vec_t U_q, tg_vec_t gradU_q, tg_vec_t a0_q, tg_vec_t f_q,
                    tg_vec_t G_q, tg_vec_t s_out, tg_vec_t F_out, tg_vec_t A_out, tg_vec_t b_out, tg_vec_t c_out, tg_vec_t M_out,
                    tg_vec_t tau_out);
+/* ---- evaluation at points the caller chooses, closest points (csrc/tg_sample.hip) --------------------------------------------
+ * The patches of the point kernels above: d = 1, 2, 3, nsd >= d, (p+1)^d <= the limit of tg_assemble_limits, control functions
+ * on all FE nodes; patch->nq is not read.  Point arrays are component-major (component c of point q at c npts + q); npts is
+ * taken from the length of the input vector; npts = 0: no launch, status 0.  One lane per point, grids capped at 1024 workgroups
+ * of 256 lanes (p <= 4: 1-D tables in registers) or 64 lanes (p > 4: tables in LDS) that stride over the rest; no atomics: a
+ * point's result depends on that point alone, the same inputs give the same bits.
+ * LOCATION RULE: a point is inside iff v_k[0] <= xi_k <= v_k[last] for every k, by exact comparisons; its element in
+ * direction k is the largest e <= nel_k - 1 with v_k[e] <= xi_k (a point on an interior vertex belongs to the upper element,
+ * the last vertex to the last element); the local coordinate is t = (xi_k - v_k[e]) / (v_k[e+1] - v_k[e]).
+ * tg_point_eval: xi holds d npts parametric (knot) coordinates; u_nodal nF >= 1 fields on the grid, field after field (null:
+ *   only x_out).  Any output may be null: x_out (nsd npts) = F(xi) = cp[i]/cp[nsd]; val_out (nF npts), field i at i npts + q;
+ *   grad_out (nF nsd npts), the Cartesian gradient DF g^-1 grad_xi, component K of field i at (i nsd + K) npts + q (the layout
+ *   of tg_flow_points).  rational: u_h / W_h and its gradient by the quotient rule, as tg_quad_eval_rational.  A point that
+ *   is not inside (NaN and +-inf included) gets NaN in every output and no field is read for it.
+ * tg_point_locate: the closest point of the patch to each of the npts physical points x (nsd npts values): the minimiser of
+ *   |x - F(xi)|^2 over the parametric box -- the inverse map for nsd = d and x in the image, the projection otherwise.
+ *   1. Seed: the point's entry of xi_guess (d npts values, clipped to the box) if given; else the nearest centre F(xi_c) among
+ *      the elements of a sub-lattice: every s_k-th element of direction k (elements 0, s_k, 2 s_k, ...), the strides grown from
+ *      (1, 1, 1) -- the direction with the most seeds first, the lowest on a tie -- until at most max_seeds seeds are left;
+ *      brute force, ties to the lowest seed index (direction 0 fastest).
+ *   2. Step: Gauss-Newton, delta = (DF^T DF)^-1 DF^T r, r = x - F(xi), formed in coordinates scaled by the box (range_k).  A
+ *      direction whose bound is active and whose gradient component (DF^T r)_k points outward is held.  The scaled normal
+ *      matrix counts as singular when its determinant is not above 1e-20 (largest diagonal entry)^d: status 3.
+ *   3. Update: xi + delta clipped to the box; the step is halved (at most 10 times) while |r|^2 does not decrease, where a
+ *      change below sum_c e_c (2 |r_c| + e_c), e_c = 32 eps (|x_c| + |F_c|), counts as rounding and not as an increase.  No
+ *      decrease after the last halving: status 1.
+ *   4. Stop when max_k |clip(xi + delta)_k - xi_k| / range_k <= tol (that last full step is taken): status 0; or after max_iter
+ *      (1..100) steps: status 1.
+ *   xi_out (d npts) always lies inside the box.  info_out (3 npts): the distance |x - F(xi)| at q, the number of steps at
+ *   npts + q, the status at 2 npts + q: 0 converged, 1 iteration limit, 2 input not finite (xi = NaN, distance NaN),
+ *   3 singular DF^T DF.  No second derivatives enter: for a non-zero residual the convergence is LINEAR with the ratio
+ *   ~ distance x curvature (no convergence beyond the centre of curvature). */
+int tg_point_eval(const tg_patch_t *patch, int nF, tg_vec_t u_nodal, tg_vec_t xi, int rational, tg_vec_t x_out, tg_vec_t val_out,
+                  tg_vec_t grad_out);
+int tg_point_locate(const tg_patch_t *patch, tg_vec_t x, tg_vec_t xi_guess, double tol, int max_iter, int64_t max_seeds,
+                    tg_vec_t xi_out, tg_vec_t info_out);
+/* ---- sampling on a lattice (endings 0 and 1 of csrc/tg_postproc.hip): m caller-given abscissae t[0..m) (host, increasing, in
+ * [0, 1], the ends allowed) per element and direction, 1 <= m <= the Gauss-point limit.  Numbering and layouts of
+ * tg_quad_points / tg_quad_eval with m for nq (points on shared element faces come once per element). */
+int tg_lattice_points(const tg_patch_t *patch, int m, const double *t, tg_vec_t x_out);
+int tg_lattice_eval(const tg_patch_t *patch, int m, const double *t, tg_vec_t u_nodal, int with_grad, tg_vec_t val_out,
+                    tg_vec_t grad_out);
+int tg_lattice_eval_rational(const tg_patch_t *patch, int m, const double *t, tg_vec_t u_nodal, int with_grad, tg_vec_t val_out,
+                             tg_vec_t grad_out);
 /* ---- material laws at the points (csrc/tg_material.hip): F = I + grad u, J = det F, C = F^T F, nsd = 2 (plane strain) or 3.
  * gradu: d u_i / d x_K at (i nsd + K) npts + q; P_out: the first Piola-Kirchhoff stress in the same layout; A_out:
  * A_iKjL = d P_iK / d F_jL in the layout of tg_coef_transform_blocks; psi_out: the energy density; any output may be null.

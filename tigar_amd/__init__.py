@@ -18,3 +18,4 @@ from .NURBS import NURBSControlMesh      # noqa: E402,F401
 from .fastdiag import FastDiagonalization  # noqa: E402,F401
 from .eigen import SLEPcEigenSolver  # noqa: E402,F401
 from . import timeIntegration  # noqa: E402,F401
+from .vtkio import File  # noqa: E402,F401

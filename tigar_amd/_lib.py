@@ -242,6 +242,11 @@ PROTOTYPES = {
     "tg_coef_transform_system": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, C.c_int, handle, handle, handle, handle, handle]),
     "tg_assemble_coef_system": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, handle, C.POINTER(handle)]),
     "tg_quad_metric": (C.c_int, [C.POINTER(tg_patch_t), handle]),
+    "tg_point_eval": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, handle, handle, C.c_int, handle, handle, handle]),
+    "tg_point_locate": (C.c_int, [C.POINTER(tg_patch_t), handle, handle, C.c_double, C.c_int, C.c_int64, handle, handle]),
+    "tg_lattice_points": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, c_f64p, handle]),
+    "tg_lattice_eval": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, c_f64p, handle, C.c_int, handle, handle]),
+    "tg_lattice_eval_rational": (C.c_int, [C.POINTER(tg_patch_t), C.c_int, c_f64p, handle, C.c_int, handle, handle]),
     "tg_flow_points": (C.c_int, [c_f64p, C.c_int, C.c_int64] + [handle] * 12),
     "tg_material_points": (C.c_int, [C.c_int, c_f64p, C.c_int, C.c_int64, handle, handle, handle, handle, c_i64p, c_f64p]),
     "tg_quad_load_flux": (C.c_int, [C.POINTER(tg_patch_t), handle, handle, handle]),

@@ -384,6 +384,30 @@ class Function(object):
     def function_space(self):
         return self.V
 
+    def rename(self, name, label):
+        """dolfin's ``Function.rename``: the name output files carry (``File << u``, the demos' ``F0`` ... ``F3``)"""
+        self._name, self._label = str(name), str(label)
+
+    def name(self):
+        return self.__dict__.get("_name", "f")
+
+    def label(self):
+        return self.__dict__.get("_label", "")
+
+    def split(self):
+        """one ``Function`` per field: copies of the fields' nodal values, each on its field's scalar space, named
+        ``name_i`` (dolfin's ``u.split(deepcopy=True)``; a scalar function gives one copy of itself)"""
+        if self.local_range is not None:
+            raise NotImplementedError("Function.split: a rank-local function is not supported")
+        out, off = [], 0
+        for i, g in enumerate(self.V.grids):
+            fi = Function(TensorFunctionSpace([g], self.V.element))
+            _dev.vec_copy_range(fi.vector(), 0, self._vec, off, g.num_nodes())
+            off += g.num_nodes()
+            fi.rename("%s_%d" % (self.name(), i) if len(self.V.grids) > 1 else self.name(), self.label())
+            out.append(fi)
+        return out
+
 
 def multTranspose(M, b):
     """Returns ``M^T*b`` (tIGAr/common.py:97-109)."""
@@ -2221,6 +2245,173 @@ class ExtractedSpline(object):
             _dev.vec_copy_range(c, 0, g, i * pts.npts, pts.npts)
             comps.append(c)
         return val, comps
+
+    # -- evaluation at points the caller chooses, closest points, lattices, VTK files (csrc/tg_sample.hip, tigar_amd/vtkio.py)
+    def _sample_patch(self, who):
+        """(element vertices, degree, control functions, node grid) of the patch the sampling operands work on: the scope
+        of the first-order systems (nF >= 1 fields on the control basis sharing one node grid)"""
+        from . import forms
+        self._system_quadrature_scope(who)
+        g = self.V.grids[0]
+        return forms._whole_patch(self, g, who, "the sampling operands") + (g,)
+
+    def _sample_nodal(self, u, g, who, control=False):
+        """(nodal DeviceVector, number of fields) of ``u`` on the spline's space (``control``: or on the scalar control space)"""
+        uv, n = _as_device_vector(u), g.num_nodes()
+        if uv.size() == self.nFields * n:
+            return uv, self.nFields
+        if control and uv.size() == n:
+            return uv, 1
+        raise ValueError("%s: %d nodal values given, the space has %d%s"
+                         % (who, uv.size(), self.nFields * n, " (the scalar control space %d)" % n if control else ""))
+
+    @staticmethod
+    def _sample_points(a, ncomp, who, name):
+        """(DeviceVector in the component-major layout, npts) of a host array [npts, ncomp] or a DeviceVector in that layout"""
+        from . import forms
+        if isinstance(a, DeviceVector):
+            if a.size() % ncomp:
+                raise ValueError("%s: %s holds %d values, not a multiple of %d" % (who, name, a.size(), ncomp))
+            return a, a.size() // ncomp
+        a = numpy.asarray(a, dtype=numpy.float64)
+        if a.ndim == 1 and ncomp == 1:
+            a = a[:, None]
+        if a.ndim != 2 or a.shape[1] != ncomp:
+            raise ValueError("%s: %s of shape %s; expected [npts, %d]" % (who, name, a.shape, ncomp))
+        return DeviceVector(data=forms.point_block(a, a.shape[0], (ncomp,))), a.shape[0]
+
+    @staticmethod
+    def _sample_split(val, g, nF, nsd, npts):
+        """the results of nF fields as the caller gets them: per field ``values`` or ``(values, [nsd gradient components])``,
+        one such for nF = 1 and a list beyond"""
+        def piece(src, off):
+            c = DeviceVector(npts, zero=False)
+            _dev.vec_copy_range(c, 0, src, off * npts, npts)
+            return c
+        out = []
+        for i in range(nF):
+            v = val if nF == 1 else piece(val, i)
+            out.append(v if g is None else (v, [piece(g, i * nsd + K) for K in range(nsd)]))
+        return out[0] if nF == 1 else out
+
+    def evaluateAtPoints(self, u, xi, grad=False, rational=False):
+        """u_h at the parametric points ``xi`` (host array [npts, d] of knot coordinates, or a DeviceVector of d * npts
+        values, component-major) for an FE ``Function`` or nodal vector ``u``: a DeviceVector of npts values, with ``grad``
+        ``(values, [nsd DeviceVectors])`` with the Cartesian gradient, for nFields > 1 a list with one such per field
+        (``tg_point_eval``).  A point outside the parametric box gets NaN.  ``rational``: u_h / W_h and its gradient."""
+        who = "evaluateAtPoints"
+        verts, p, cp, g = self._sample_patch(who)
+        uv, nF = self._sample_nodal(u, g, who)
+        xiv, npts = self._sample_points(xi, len(verts), who, "xi")
+        _, val, gr = _dev.point_eval(verts, p, cp, xiv, uv, nF=nF, grad=grad, rational=rational)
+        return self._sample_split(val, gr, nF, len(cp) - 1, npts)
+
+    def physicalPoints(self, xi):
+        """x = F(xi) of the parametric points ``xi`` (as for ``evaluateAtPoints``): a host array [npts, nsd]"""
+        from . import forms
+        who = "physicalPoints"
+        verts, p, cp, g = self._sample_patch(who)
+        xiv, npts = self._sample_points(xi, len(verts), who, "xi")
+        x = _dev.point_eval(verts, p, cp, xiv, x=True)[0]
+        return forms.point_unblock(x.get_local(), npts, (len(cp) - 1,))
+
+    def locatePoints(self, x, guess=None, tol=1e-12, maximum_iterations=50, max_seeds=32768):
+        """The closest points of the patch to the physical points ``x`` (host array [npts, nsd] or a DeviceVector of nsd *
+        npts values): the inverse map for points of the image, the projection for points off a curve or surface or outside.
+        Damped Gauss-Newton steps from ``guess`` (parametric points as for ``evaluateAtPoints``) or from the nearest centre
+        of at most ``max_seeds`` elements, until the step is below ``tol`` times the parametric range
+        (``tg_point_locate``; without second derivatives: linear convergence for a point at a distance).  Returns a
+        ``forms.LocatedPoints``."""
+        from . import forms
+        who = "locatePoints"
+        verts, p, cp, g = self._sample_patch(who)
+        if not tol > 0.0:
+            raise ValueError("%s: tol = %r; a positive tolerance" % (who, tol))
+        if int(maximum_iterations) != maximum_iterations or not 1 <= int(maximum_iterations) <= 100:
+            raise ValueError("%s: maximum_iterations = %r; 1..100" % (who, maximum_iterations))
+        if int(max_seeds) != max_seeds or int(max_seeds) < 1:
+            raise ValueError("%s: max_seeds = %r; at least one seed" % (who, max_seeds))
+        xv, npts = self._sample_points(x, len(cp) - 1, who, "x")
+        gv = None
+        if guess is not None:
+            gv, ng = self._sample_points(guess, len(verts), who, "guess")
+            if ng != npts:
+                raise ValueError("%s: %d starting values for %d points" % (who, ng, npts))
+        xi, info = _dev.point_locate(verts, p, cp, xv, gv, tol, maximum_iterations, max_seeds)
+        return forms.LocatedPoints(xi, info, len(verts))
+
+    def evaluateAtPhysicalPoints(self, u, x, grad=False, rational=False, **locate_options):
+        """``evaluateAtPoints`` at the closest points of the patch to the physical points ``x``: ``(values..., located)``
+        with what ``evaluateAtPoints`` returns followed by the ``forms.LocatedPoints`` (check ``located.distance``: a point
+        off the patch is evaluated at its projection).  ``locate_options``: those of ``locatePoints``."""
+        located = self.locatePoints(x, **locate_options)
+        res = self.evaluateAtPoints(u, located.xi_device, grad=grad, rational=rational)
+        return (res if isinstance(res, tuple) else (res,)) + (located,)
+
+    def latticePoints(self, m=None):
+        """The sampling lattice of the patch as a ``forms.LatticePoints``: ``m`` an int (that many equispaced abscissae per
+        element and direction, the ends included; 1: the centre), a sequence of abscissae in [0, 1], or None: p + 1.  Kept
+        per (abscissae, control-function vectors)."""
+        from . import forms
+        who = "latticePoints"
+        self._system_quadrature_scope(who)
+        return forms.lattice_points(self, self.V.grids[0], m, who)
+
+    def evaluateAtLattice(self, u, m=None, grad=False, rational=False):
+        """``evaluateAtQuadrature`` on the lattice ``latticePoints(m)`` in the place of the Gauss points, for nFields >= 1
+        (a list with one result per field beyond one; ``tg_lattice_eval``)"""
+        from . import forms
+        who = "evaluateAtLattice"
+        pts = self.latticePoints(m)
+        g = self.V.grids[0]
+        uv, nF = self._sample_nodal(u, g, who, control=True)
+        n, nsd = g.num_nodes(), pts.nsd
+        call = lambda ui: _dev.lattice_eval(pts.verts, pts.p, pts.cp, pts.t, ui, grad=grad, rational=rational)
+        if nF == 1:
+            res = call(uv)
+            return self._sample_split(res[0], res[1], 1, nsd, pts.npts) if grad else res
+        if not grad:
+            return forms._field_by_field(uv, nF, n, call)
+        return [self._sample_split(v, gr, 1, nsd, pts.npts) for v, gr in forms._field_by_field(uv, nF, n, call)]
+
+    def writeVTK(self, path, fields, m=None, rational=False, displacement=None, time=None, encoding="raw"):
+        """Writes ``fields`` = {name: Function | nodal vector} (on the spline's space or on the scalar control space) sampled
+        on the lattice ``latticePoints(m)`` (m >= 2 points per element and direction) as a VTK XML unstructured grid of
+        linear cells, (m - 1)^d per element: the points are the physical lattice points x = F(xi), plus the interpolated
+        ``displacement`` (nsd fields) if given -- the deformed shell --, the data come from ``evaluateAtLattice``.  A
+        function with nsd fields is written as one vector array, one field as the array ``name``, any other number as
+        ``name_i`` per field.  ``path`` ending in .vtu: that file; in .pvd: a further step (stem000000.vtu, ...) of the
+        collection, at ``time`` (the step number when None).  Returns the name of the .vtu file written."""
+        from . import forms, vtkio
+        who = "writeVTK"
+        pts = self.latticePoints(m)
+        if pts.m < 2:
+            raise ValueError("%s: a lattice of %d point per element and direction has no cells; m >= 2" % (who, pts.m))
+        nsd = pts.nsd
+
+        def sampled(u):
+            r = self.evaluateAtLattice(u, pts.t, rational=rational)
+            return numpy.stack([v.get_local() for v in (r if isinstance(r, list) else [r])], axis=1)
+        X = pts.x.copy()
+        if displacement is not None:
+            D = sampled(displacement)
+            if D.shape[1] != nsd:
+                raise ValueError("%s: the displacement has %d fields, the patch %d physical directions" % (who, D.shape[1], nsd))
+            X += D
+        data = {}
+        for name, u in fields.items():
+            A = sampled(u)
+            if A.shape[1] == 1:
+                data[str(name)] = A[:, 0]
+            elif A.shape[1] == nsd and nsd <= 3:
+                data[str(name)] = A
+            else:
+                for i in range(A.shape[1]):
+                    data["%s_%d" % (name, i)] = A[:, i]
+        cells, ctype = pts.cells()
+        series = self.__dict__.setdefault("_vtk_series", {})
+        return vtkio._series_step(str(path), series.setdefault(str(path), []), time,
+                                  lambda f: vtkio.write_vtu(f, X, cells, ctype, data, encoding))
 
     def integrate(self, f, nq=None):
         """sum_q wdet_q f(x_q): the integral of ``f`` over the patch with the spline's measure; ``f`` as for

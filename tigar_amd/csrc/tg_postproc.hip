@@ -15,6 +15,8 @@
 //   tg_coef_transform_system   ... for the nF^2 blocks of a first-order system: every block with its own A, b, c and m
 //   tg_quad_metric   G = 4 P P^T, P = DF g^-1: the element metric of the bi-unit parent element (stabilisation parameters)
 //   tg_quad_load_flux   out[node] = sum_q wdet_q (s_q phi_node + F_q . grad phi_node)(xi_q)
+//   tg_lattice_points / tg_lattice_eval   endings 0 and 1 on the tensor lattice of m abscissae the caller gives per element
+//                       (output for a viewer, sampling on a regular grid): the host builds l | dl there in the place of the Gauss table
 //
 // One kernel, four endings (and the three that take point coefficients).  A workgroup of 256 threads takes max(1, 256 / nq^d) elements (fewer where
 // their LDS areas would exceed 64 KiB).  The nodal values of the
@@ -487,7 +489,7 @@ __global__ void __launch_bounds__(256) k_postproc_fold(const double *part, int64
 // checks the patch, fills what every mode shares; `u`: the nodal vector taken to the points (may be null).  mode: 0 - 3 as
 // the kernel's, 4 the flux load
 static int tg_pp_setup(const char *who, const tg_patch_t *pt, int mode, tg_vec_t u, tg_pp_args *A, size_t *lds,
-                       int64_t *nnodes_out = nullptr) {
+                       int64_t *nnodes_out = nullptr, bool gauss_tables = true) {
   tg_patch_dims D;
   TG_TRY(tg_patch_check(who, pt, 1, true, u, &D));
   const int d = D.d, p1 = D.p + 1, nq = D.nq, nloc = D.nloc, nqt = D.nqt;
@@ -498,8 +500,10 @@ static int tg_pp_setup(const char *who, const tg_patch_t *pt, int mode, tg_vec_t
   A->npts = D.npts;
   A->nc = tg_point_fields(pt, u, A->f);
   if (nnodes_out) *nnodes_out = D.nnodes;
-  TG_TRY(tg_asm_cache_get(pt));
-  A->tab = g_asm_cache.tab;
+  if (gauss_tables) {              // (the lattice entries bring their own table)
+    TG_TRY(tg_asm_cache_get(pt));
+    A->tab = g_asm_cache.tab;
+  }
   // LDS per element: area A holds the nodal values, then (3-D) the output of direction 1; area B the output of direction
   // 0; the area the last contraction does not read takes the point values of the load / the terms of the error sums, and
   // the load goes back to the nodes through both
@@ -745,4 +749,79 @@ extern "C" int tg_quad_load_flux_rational(const tg_patch_t *patch, tg_vec_t s_q,
 }
 extern "C" int tg_quad_error_rational(const tg_patch_t *patch, tg_vec_t u_nodal, tg_vec_t e_q, tg_vec_t ge_q, double *out) {
   return tg_pp_error(patch, u_nodal, e_q, ge_q, out, true);
+}
+
+// ---- lattice sampling: the points and the evaluation on m caller-given abscissae t[0..m) in [0, 1] per element and
+// direction (the ends are allowed: the points on shared element faces then come once per element).  The kernel and its
+// endings are those of the Gauss points; the table l | dl | w of this call is built here at the abscissae (the expressions
+// of the Gauss table, tg_assemble.hip) and lives until the launch has run.  Numbering: tg_quad_points with m for nq.
+static int tg_pp_lattice_setup(const char *who, const tg_patch_t *patch, int m, const double *t, tg_vec_t u, tg_pp_args *A, size_t *lds,
+                               tg_dbuf<double> *tab) {
+  TG_REQUIRE(patch, "%s: no patch", who);
+  TG_REQUIRE(m >= 1 && m <= TG_ASM_MAXQ1 && t, "%s: m = %d; 1..%d abscissae per direction", who, m, TG_ASM_MAXQ1);
+  for (int q = 0; q < m; q++)
+    TG_REQUIRE(t[q] >= 0.0 && t[q] <= 1.0 && (q == 0 || t[q - 1] < t[q]), "%s: the abscissae increase within [0, 1] (t[%d] = %g)", who, q, t[q]);
+  tg_patch_t pt = *patch;
+  pt.nq = m;
+  TG_TRY(tg_pp_setup(who, &pt, u ? 1 : 0, u, A, lds, nullptr, false));
+  const int p = pt.p, p1 = p + 1;
+  std::vector<double> h((size_t)2 * p1 * m + m, 1.0);      // (w = 1: the weights are not an output of these entries)
+  for (int a = 0; a < p1; a++)
+    for (int q = 0; q < m; q++) {
+      double l = 1.0, dl = 0.0;
+      for (int k = 0; k < p1; k++)
+        if (k != a) l *= (t[q] - (double)k / p) / ((double)a / p - (double)k / p);
+      for (int k = 0; k < p1; k++) {
+        if (k == a) continue;
+        double term = 1.0 / ((double)a / p - (double)k / p);
+        for (int r = 0; r < p1; r++)
+          if (r != a && r != k) term *= (t[q] - (double)r / p) / ((double)a / p - (double)r / p);
+        dl += term;
+      }
+      h[(size_t)a * m + q] = l;
+      h[(size_t)p1 * m + (size_t)a * m + q] = dl;
+    }
+  TG_TRY(tab->alloc((int64_t)h.size()));
+  TG_TRY(tg_h2d_staged(tab->get(), h.data(), h.size() * sizeof(double)));
+  A->tab = tab->get();
+  return 0;
+}
+
+extern "C" int tg_lattice_points(const tg_patch_t *patch, int m, const double *t, tg_vec_t x_out) {
+  tg_pp_args A;
+  size_t lds;
+  tg_dbuf<double> tab, wdet;
+  TG_TRY(tg_pp_lattice_setup("tg_lattice_points", patch, m, t, nullptr, &A, &lds, &tab));
+  TG_REQUIRE(x_out && x_out->n == (int64_t)A.nsd * A.npts, "tg_lattice_points: an output of nsd * npts = %lld values",
+             (long long)(A.nsd * A.npts));
+  TG_TRY(wdet.alloc(A.npts));      // (ending 0 writes sqrt(det g) next to the points; not handed out)
+  A.x = x_out->d;
+  A.wdet = wdet.get();
+  return tg_pp_launch<0>(A, lds);
+}
+
+static int tg_pp_lattice_eval(const tg_patch_t *patch, int m, const double *t, tg_vec_t u_nodal, int with_grad, tg_vec_t val_out,
+                              tg_vec_t grad_out, bool rat) {
+  tg_pp_args A;
+  size_t lds;
+  tg_dbuf<double> tab;
+  TG_REQUIRE(u_nodal, "tg_lattice_eval: no nodal vector");
+  TG_TRY(tg_pp_lattice_setup("tg_lattice_eval", patch, m, t, u_nodal, &A, &lds, &tab));
+  TG_REQUIRE(val_out && val_out->n == A.npts, "tg_lattice_eval: an output of npts = %lld values", (long long)A.npts);
+  A.val = val_out->d;
+  if (with_grad) {
+    TG_REQUIRE(grad_out && grad_out->n == (int64_t)A.nsd * A.npts, "tg_lattice_eval: a gradient output of nsd * npts = %lld values",
+               (long long)(A.nsd * A.npts));
+    A.grad = grad_out->d;
+  }
+  return tg_pp_launch_rat<1>(rat, A, lds);
+}
+
+extern "C" int tg_lattice_eval(const tg_patch_t *patch, int m, const double *t, tg_vec_t u_nodal, int with_grad, tg_vec_t val_out,
+                               tg_vec_t grad_out) {
+  return tg_pp_lattice_eval(patch, m, t, u_nodal, with_grad, val_out, grad_out, false);
+}
+extern "C" int tg_lattice_eval_rational(const tg_patch_t *patch, int m, const double *t, tg_vec_t u_nodal, int with_grad,
+                                        tg_vec_t val_out, tg_vec_t grad_out) {
+  return tg_pp_lattice_eval(patch, m, t, u_nodal, with_grad, val_out, grad_out, true);
 }

@@ -1205,6 +1205,56 @@ def quad_eval(vertices, p, cp, u, grad=False, nq=None, rational=False):
     return (val, g) if grad else val
 
 
+def point_eval(vertices, p, cp, xi, u=None, nF=1, x=False, val=True, grad=False, rational=False):
+    """Evaluation at the parametric points ``xi`` (DeviceVector of d * npts knot coordinates, component-major) of the patch
+    (``tg_point_eval``): returns ``(x, values, gradients)``, each a DeviceVector or None where it was not asked for -- x =
+    F(xi) (nsd * npts), the nF fields of the nodal DeviceVector ``u`` (field i at i * npts + q) and their Cartesian
+    gradients (component K of field i at (i * nsd + K) * npts + q).  Without ``u`` only x is computed.  A point outside
+    the parametric box (NaN included) gets NaN everywhere.  ``rational``: u_h / W_h and its gradient."""
+    d, nsd = len(vertices), len(cp) - 1
+    if xi.size() % d:
+        raise ValueError("point_eval: xi holds %d values, not a multiple of d = %d" % (xi.size(), d))
+    npts = xi.size() // d
+    xo = DeviceVector(nsd * npts, zero=False) if x else None
+    vo = DeviceVector(nF * npts, zero=False) if (val and u is not None) else None
+    go = DeviceVector(nF * nsd * npts, zero=False) if (grad and u is not None) else None
+    _point_call("tg_point_eval", vertices, p, cp, 1, int(nF), u, xi, 1 if rational else 0, xo, vo, go)
+    return xo, vo, go
+
+
+def point_locate(vertices, p, cp, x, guess=None, tol=1e-12, max_iter=50, max_seeds=32768):
+    """The closest points of the patch to the physical points ``x`` (DeviceVector, nsd * npts, component-major) by the
+    damped Gauss-Newton iteration of ``tg_point_locate``: ``(xi, info)`` with xi (d * npts) inside the parametric box and
+    info = distance | iterations | status (3 * npts).  ``guess``: d * npts starting values, else the nearest centre of at
+    most ``max_seeds`` elements."""
+    d, nsd = len(vertices), len(cp) - 1
+    if x.size() % nsd:
+        raise ValueError("point_locate: x holds %d values, not a multiple of nsd = %d" % (x.size(), nsd))
+    npts = x.size() // nsd
+    xi, info = DeviceVector(d * npts, zero=False), DeviceVector(3 * npts, zero=False)
+    _point_call("tg_point_locate", vertices, p, cp, 1, x, guess, float(tol), int(max_iter), int(max_seeds), xi, info)
+    return xi, info
+
+
+def lattice_points(vertices, p, cp, t):
+    """x = F at the tensor lattice of the abscissae ``t`` (in [0, 1], per element and direction): nsd * npts values,
+    numbered as ``quad_points`` with len(t) for nq (``tg_lattice_points``)"""
+    t = _f64(t)
+    x = DeviceVector((len(cp) - 1) * quad_count(vertices, len(t)), zero=False)
+    _point_call("tg_lattice_points", vertices, p, cp, len(t), len(t), _p(t, c_f64p), x)
+    return x
+
+
+def lattice_eval(vertices, p, cp, t, u, grad=False, rational=False):
+    """``quad_eval`` on the lattice of the abscissae ``t`` in the place of the Gauss points (``tg_lattice_eval``)"""
+    t = _f64(t)
+    npts = quad_count(vertices, len(t))
+    val = DeviceVector(npts, zero=False)
+    g = DeviceVector((len(cp) - 1) * npts, zero=False) if grad else None
+    _point_call("tg_lattice_eval", vertices, p, cp, len(t), len(t), _p(t, c_f64p), u, 1 if grad else 0, val, g, rational=rational)
+    return (val, g) if grad else val
+
+
 def quad_load(vertices, p, cp, fq, nq=None, rational=False):
     """L(v) = sum_q wdet_q f_q v(xi_q) for the DeviceVector ``fq`` of point values (``tg_quad_load``); ``rational``: v the
     functions phi / W_h (``tg_quad_load_rational``)."""

@@ -576,6 +576,90 @@ def quadrature_points(geometry, V, nq=None, who="quadrature points"):
     return cache[key]
 
 
+def lattice_abscissae(m, p):
+    """the abscissae of a sampling lattice: ``m`` None: p + 1 equispaced with the ends; an int: that many equispaced with the
+    ends (1: the element centre); a sequence: the abscissae themselves, increasing within [0, 1]"""
+    most = _dev.assemble_limits()[1]
+    m = p + 1 if m is None else m
+    if numpy.ndim(m) == 0:
+        if int(m) != m or not 1 <= int(m) <= most:
+            raise ValueError("m = %r: 1..%d lattice points per element and direction" % (m, most))
+        return numpy.array([0.5]) if int(m) == 1 else numpy.linspace(0.0, 1.0, int(m))
+    t = numpy.asarray(m, dtype=numpy.float64)
+    if t.ndim != 1 or not 1 <= t.size <= most:
+        raise ValueError("lattice abscissae of shape %s: a sequence of 1..%d numbers" % (t.shape, most))
+    if not (numpy.all(t >= 0.0) and numpy.all(t <= 1.0)) or numpy.any(numpy.diff(t) <= 0.0):
+        raise ValueError("lattice abscissae %r: increasing numbers within [0, 1]" % (t.tolist(),))
+    return numpy.ascontiguousarray(t)
+
+
+class LatticePoints(object):
+    """The tensor lattice of ``m`` abscissae ``t`` per element and direction on a mapped patch, numbered as the Gauss points
+    (element-major, direction 0 fastest; with the ends among the abscissae the points on shared element faces come once per
+    element): ``x`` host array [npts, nsd] (downloaded on first use), ``x_device`` (nsd * npts, component-major), ``t``,
+    ``m``, ``npts``, ``nsd``, ``values(f)`` as on ``QuadraturePoints`` and ``cells()`` for a viewer."""
+
+    def __init__(self, verts, p, cp, t):
+        self.verts, self.p, self.cp, self.t, self.m, self.nsd = verts, p, cp, t, len(t), len(cp) - 1
+        self.x_device = _dev.lattice_points(verts, p, cp, t)
+        self.npts = _dev.quad_count(verts, self.m)
+        self._x = None
+
+    @property
+    def x(self):
+        if self._x is None:
+            self._x = point_unblock(self.x_device.get_local(), self.npts, (self.nsd,))
+        return self._x
+
+    def values(self, f, who="f"):
+        """point values of ``f`` as a DeviceVector: as ``QuadraturePoints.values``, a Function of the space evaluated by
+        ``tg_lattice_eval``"""
+        if hasattr(f, "vector") and hasattr(f, "function_space"):
+            return _dev.lattice_eval(self.verts, self.p, self.cp, self.t, f.vector())
+        return QuadraturePoints.values(self, f, who)
+
+    def cells(self):
+        """((m - 1)^d nelem linear cells [ncells, 2^d] in VTK's vertex order, the VTK cell type): ``vtkio.lattice_cells``"""
+        from . import vtkio
+        d = len(self.verts)
+        return vtkio.lattice_cells([len(v) - 1 for v in self.verts], self.m, d), vtkio.CELL_TYPE_OF_DIM[d]
+
+
+def lattice_points(geometry, g, m=None, who="lattice points"):
+    """the ``LatticePoints`` of the patch of ``geometry`` with the node grid ``g``, kept on it per set of abscissae and of
+    control-function vectors, like the quadrature points"""
+    verts, p, cp = _whole_patch(geometry, g, who, "the sampling operands")
+    t = lattice_abscissae(m, p)
+    cache = geometry.__dict__.setdefault("_lattice_points", {})
+    key = (t.tobytes(), tuple(id(v) for v in cp))
+    if key not in cache:
+        cache[key] = LatticePoints(verts, p, cp, t)
+    return cache[key]
+
+
+class LocatedPoints(object):
+    """What ``ExtractedSpline.locatePoints`` found: ``xi`` host array [npts, d] (lazy) and ``xi_device`` (d * npts,
+    component-major) inside the parametric box, ``distance`` |x - F(xi)|, ``iterations``, ``status`` (0 converged, 1
+    iteration limit, 2 input not finite, 3 singular DF^T DF) as host arrays, ``converged`` = all status 0, ``npts``."""
+
+    def __init__(self, xi_device, info, d):
+        self.xi_device, self.d = xi_device, d
+        self.npts = xi_device.size() // d
+        h = info.get_local().reshape(3, self.npts)
+        self.distance, self.iterations, self.status = h[0].copy(), h[1].astype(numpy.int64), h[2].astype(numpy.int64)
+        self._xi = None
+
+    @property
+    def xi(self):
+        if self._xi is None:
+            self._xi = point_unblock(self.xi_device.get_local(), self.npts, (self.d,))
+        return self._xi
+
+    @property
+    def converged(self):
+        return bool(numpy.all(self.status == 0))
+
+
 class QuadratureLoadForm(object):
     """L(v) = sum_q wdet_q f(x_q) v(xi_q) on the mapped patch: the load of ``f`` itself, not of its nodal interpolant
     (``NodalLoadForm``).  ``f``: a callable on the physical points ``[npts, nsd] -> [npts]`` (evaluated on the host once

@@ -30,12 +30,13 @@
 #define __shared__
 using std::max;
 using std::min;
+using std::isfinite;
 
 struct dim3 {
   unsigned x, y, z;
   dim3(unsigned x_ = 1, unsigned y_ = 1, unsigned z_ = 1) : x(x_), y(y_), z(z_) {}
 };
-extern dim3 threadIdx, blockIdx, blockDim;
+extern dim3 threadIdx, blockIdx, blockDim, gridDim;
 #define TG_HOST_LDS_BYTES (160 * 1024)
 extern __attribute__((aligned(16))) char smem[];   // what `extern __shared__ char smem[]` of a kernel refers to
 extern size_t g_host_lds_max;
@@ -72,6 +73,7 @@ static inline void tg_host_launch(F &&body, dim3 grid, size_t lds) {
   g_host_lds_max = std::max(g_host_lds_max, lds);
   TG_HOST_POISON(smem + lds, TG_HOST_LDS_BYTES - lds);
   blockDim = dim3(1);
+  gridDim = grid;                 // (kernels that stride over a capped grid: csrc/tg_sample.hip)
   threadIdx = dim3(0, 0, 0);
   for (unsigned b = 0; b < grid.x; b++) {
     blockIdx = dim3(b, 0, 0);

@@ -6,10 +6,11 @@
 // once, from the file that has main().  TG_HOST_SWEEP_JET (tools/jet_host_sweep.cpp, tools/shell_hyper_host_sweep.cpp): also
 // csrc/tg_jet.hip and csrc/tg_shell.hip,
 // whose kernels read the fourth table d2l[a][q] and the device copies of the element vertices: both are then allocated, again
-// at exactly their sizes.
+// at exactly their sizes.  TG_HOST_SWEEP_SAMPLE (tools/sample_host_sweep.cpp): also csrc/tg_sample.hip, whose kernels stride
+// over a capped grid (gridDim) and keep their own copies of the vertices.
 #pragma once
 #include <hip/hip_runtime.h>
-dim3 threadIdx, blockIdx, blockDim;
+dim3 threadIdx, blockIdx, blockDim, gridDim;
 __attribute__((aligned(16))) char smem[TG_HOST_LDS_BYTES];
 size_t g_host_lds_max = 0;
 
@@ -18,6 +19,9 @@ size_t g_host_lds_max = 0;
 #ifdef TG_HOST_SWEEP_JET
 #include "../../tigar_amd/csrc/tg_jet.hip"
 #include "../../tigar_amd/csrc/tg_shell.hip"
+#endif
+#ifdef TG_HOST_SWEEP_SAMPLE
+#include "../../tigar_amd/csrc/tg_sample.hip"
 #endif
 #include <cstdarg>
 #include <random>
@@ -36,6 +40,10 @@ int tg_dmalloc_bytes(void **p, size_t bytes) {
   return *p ? 0 : 1;
 }
 void tg_dfree(void *p) { free(p); }
+int tg_h2d_staged(void *dst, const void *src, size_t bytes) {   // (the lattice table of tg_postproc.hip, the vertices of tg_sample.hip)
+  memcpy(dst, src, bytes);
+  return 0;
+}
 extern "C" int tg_csr_destroy(tg_csr_t m) {
   if (m) {
     free(m->rowptr);
